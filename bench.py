@@ -2,6 +2,7 @@
 """bench.py — tracked frames/s of the MI355X StrongSORT pipeline on BASELINE.json's metric.
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                   (+ the last timed step's outputs as DIR/<name>.npy: dump_outputs)
 
 One "step" = one batch of `frames_per_step` consecutive frames (default one frame-batch group of 32 frames) of
 every stream owned by the rank through the whole hot path (letterbox -> detector -> NMS -> ReID crops -> OSNet ->
@@ -226,6 +227,13 @@ def _cpu_stream(job):
     return {"n_full": n_f, "t_full": t_full, "n_track": n_t, "t_track": t_track, "stage_s": st}
 
 
+def _cpu_worker_init():
+    """Pool initializer of cpu_baseline's per-core workers: they see no GPU.  The seeded network builders enter
+    torch.random.fork_rng(), which saves and restores the RNG state of every device torch counts and so starts the HIP
+    runtime on each of them: every worker would hold the GPU open beside the benchmark's own process."""
+    os.environ["HIP_VISIBLE_DEVICES"] = "-1"
+
+
 def cpu_baseline(W, H, n_ids, nc, n_anchors, detector_name, budget_s=45.0, n_track=200, n_full=200):
     """Reference-style CPU path on the host cores, bounded samples, SURVEY §8(d)'s two modes.  kind = "port".
       (a) ONE stream, all BLAS / torch threads (<= 32): `value`, per-stage milliseconds;
@@ -250,7 +258,7 @@ def cpu_baseline(W, H, n_ids, nc, n_anchors, detector_name, budget_s=45.0, n_tra
         import multiprocessing as mp
         jobs = [dict(job, threads=1, seed=900 + i, n_track=40, n_full=8, budget_s=budget_s) for i in range(nproc)]
         t0 = time.perf_counter()
-        with mp.get_context("spawn").Pool(nproc) as pool:
+        with mp.get_context("spawn").Pool(nproc, initializer=_cpu_worker_init) as pool:
             res = pool.map(_cpu_stream, jobs)
         wall = time.perf_counter() - t0
         nf = sum(r["n_full"] for r in res)
@@ -629,6 +637,40 @@ def net_outputs_check(pipe):
             "note": "last timed group: outputs left by the replayed graphs vs an eager re-run of detector and OSNet on the same buffers"}
 
 
+DUMP_HEAD_SAMPLE = 1 << 20     # head-tensor values kept by --dump-outputs (c2's whole tensor is 22.6 M values, 90 MB in fp32)
+DUMP_EMB_ROWS = 8192           # embedding rows kept by --dump-outputs (16 MB): more only with many streams or c4's 128 crops per frame
+
+
+def _seeded_positions(n, k):
+    """k of the positions 0..n-1 (all of them when k >= n), drawn with seed 0 and sorted: the same for the same n in every run."""
+    return np.arange(n) if k >= n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, pipe, out_host, nout_host, total, frames):
+    """--dump-outputs: what the timed path computed in its LAST timed step, as float32 DIR/<name>.npy.
+      track_rows    [frames of the step, streams, most rows of a frame, 8]  the tracker rows a caller receives, rows past a frame's count zeroed
+      track_counts  [frames of the step, streams]                          rows per frame
+    and with the frame pipeline, from the last group's buffers (the networks' outputs, which the synthetic workload does not consume):
+      head_sample   the detector head tensor, flattened: DUMP_HEAD_SAMPLE values at _seeded_positions
+      embeddings    [valid crops, 512]  the ReID embeddings (DUMP_EMB_ROWS rows at _seeded_positions when there are more)
+    The workload is seeded, so the same arguments give the same inputs in every run."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    counts = nout_host[total - frames:total].numpy()
+    rows = out_host[total - frames:total, :, :max(int(counts.max()), 1)].numpy().copy()
+    rows[np.arange(rows.shape[2]) >= counts[..., None]] = 0
+    arrays = {"track_rows": rows, "track_counts": counts}
+    b = pipe.bufs[(pipe.k - 1) % pipe.nb] if hasattr(pipe, "bufs") else None
+    if getattr(b, "head_out", None) is not None and getattr(b, "emb_out", None) is not None:
+        torch.cuda.synchronize(pipe.dev)
+        head = b.head_out.flatten()
+        arrays["head_sample"] = head[torch.from_numpy(_seeded_positions(head.numel(), DUMP_HEAD_SAMPLE)).to(head.device)].float().cpu()
+        emb = b.emb_out[:int(b.crop_off[pipe.Sv].item()) if pipe.pack else b.emb_out.shape[0]]
+        arrays["embeddings"] = emb[torch.from_numpy(_seeded_positions(emb.shape[0], DUMP_EMB_ROWS)).to(emb.device)].float().cpu()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def tracker_only(cfg, n_ids=30, W=1280, H=720, frames=352, timed=192, device=0, frame_batch=32, opts=()):
     """Rows a6-a10 alone, ONE stream: detections + identity features of a group copied into fixed device buffers (device-to-device),
     one tracker call per group of `frame_batch` frames — the association launch + the per-frame chain replayed as one captured
@@ -814,7 +856,10 @@ def main():
     ap.add_argument("--fused", action="append", default=[], help="A/B switch of a fused kernel family NAME=0|1 (fused.set_flags), e.g. --fused HEAD=0")
     ap.add_argument("--pipe", action="append", default=[], help="A/B switch of the frame pipeline name=0|1: pack_crops, assoc_gate, track_priority; chain_cus=N (compute units reserved for the detached tracker chain)")
     ap.add_argument("--overlap", type=int, default=2, help="N>1: N-stage frame pipeline on N HIP streams (2 or 4; stateless detector / OSNet stages of later frames overlap the tracker of earlier ones); 0/1: strictly sequential")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last timed step computed to DIR/<name>.npy (float32, rank 0's streams; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.reid_f16 and (args.reid_fp32 or args.det_fp32):
         ap.error("--reid-f16 excludes --reid-fp32 / --det-fp32")
     args.reid_fp32 = not args.reid_f16                 # round 6: the parity-meeting precision is the headline (VERDICT r5 'next' 1a; yolo_multi_model.py:41 passes no half=)
@@ -1052,6 +1097,8 @@ def main():
                                                                                    R.wls, R.gs, R.nc, R.A, R.dev)
     step_ms, assoc_ms, assoc_n, assoc_order_us, assoc_each_us, assoc_ik_us, assoc_ik_n = R.step_ms, R.assoc_ms, R.assoc_n, R.assoc_order_us, R.assoc_each_us, R.assoc_ik_us, R.assoc_ik_n
     pct = lambda a, q: round(float(np.percentile(a, q)), 2) if len(a) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pipe, R.out_host, R.nout_host, total, FPS)
 
     # ---- roofline of the association kernel ----
     # algorithmic bytes: SURVEY §8(d)'s per-frame figure (gallery T*B*512*4 + detections D*512*4 + T*576 + D*32 + cost

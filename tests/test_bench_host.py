@@ -100,3 +100,63 @@ def test_rank_affinity_follows_the_gpu_numa_node(tmp_path, monkeypatch):
     assert bench.rank_cpus(3, 4, 3, sysfs=str(tmp_path)) == ([12, 13, 14, 15], "NUMA node 1 of GPU 3")
     (tmp_path / "bus" / "pci" / "devices" / "0000:12:00.0" / "numa_node").write_text("-1\n")
     assert bench.rank_cpus(2, 4, 2, sysfs=str(tmp_path))[1] == "contiguous slice"
+
+
+def test_cpu_baseline_workers_leave_the_gpu_alone():
+    """cpu_baseline's per-core workers build the seeded networks, whose torch.random.fork_rng() reads the RNG state of every
+    device torch counts (and so opens it).  After the pool initializer torch counts none, on a host with GPUs too."""
+    import subprocess
+    import sys
+    code = ("import sys, torch, bench\n"
+            "torch.cuda._raw_device_count_amdsmi = lambda: 8\n"             # a host with eight GPUs
+            "assert torch.cuda.device_count() == 8, torch.cuda.device_count()\n"
+            "def touched(*a, **k): sys.exit('fork_rng read a device RNG state')\n"
+            "torch.cuda.get_rng_state = touched\n"
+            "bench._cpu_worker_init()\n"
+            "assert torch.cuda.device_count() == 0\n"
+            "from strongsort_yolo_amd import nets\n"
+            "nets.build_reid(1)\n"
+            "assert not torch.cuda.is_initialized()\n")
+    env = {k: v for k, v in os.environ.items() if k not in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")}
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path, monkeypatch):
+    """--dump-outputs: float32 arrays of the last step's frames only, tracker rows past a frame's count zeroed, the network outputs
+    of the last buffer set (head tensor as a fixed seeded sample, valid embedding rows), identical for identical buffers."""
+    import types
+    import torch
+    b = _bench()
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    total, frames, S = 10, 4, 2
+    g = torch.Generator().manual_seed(0)
+    out_host = torch.rand(total, S, 256, 8, generator=g)
+    nout_host = torch.randint(0, 20, (total, S), generator=g, dtype=torch.int32)
+    nout_host[-1, 1] = 0
+    head = torch.rand(frames * S, 84, 64 * 64, generator=g).half()
+    emb = torch.rand(frames * S * 32, 512, generator=g)
+    crop_off = torch.tensor([0] * frames * S + [37], dtype=torch.int32)
+    last = types.SimpleNamespace(head_out=head, emb_out=emb, crop_off=crop_off)
+    other = types.SimpleNamespace(head_out=head + 1, emb_out=emb + 1, crop_off=crop_off)
+    pipe = types.SimpleNamespace(bufs=[other, last, other], k=5, nb=3, dev="cpu", Sv=frames * S, pack=True)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), pipe, out_host, nout_host, total, frames)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["embeddings.npy", "head_sample.npy", "track_counts.npy", "track_rows.npy"]
+    z = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype == np.float32 for a in z.values())
+    assert sum((tmp_path / "a" / n).stat().st_size for n in names) <= 64 << 20
+    cnt = nout_host[total - frames:].numpy()
+    assert np.array_equal(z["track_counts"], cnt)
+    rows = z["track_rows"]
+    assert rows.shape == (frames, S, cnt.max(), 8)
+    for f in range(frames):
+        for s in range(S):
+            n = cnt[f, s]
+            assert np.array_equal(rows[f, s, :n], out_host[total - frames + f, s, :n].numpy()) and not rows[f, s, n:].any()
+    assert z["head_sample"].shape == (b.DUMP_HEAD_SAMPLE,)
+    assert np.isin(z["head_sample"], head.float().flatten().numpy()).all()
+    assert np.array_equal(z["embeddings"], emb[:37].numpy())
+    for n in names:
+        assert (tmp_path / "a" / n).read_bytes() == (tmp_path / "b" / n).read_bytes()
