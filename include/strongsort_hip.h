@@ -157,6 +157,28 @@ int ss_unpack_feats(ss_ctx* ctx, const void* d_emb, int emb_half, const int* d_o
 int ss_pack_results(ss_ctx* ctx, const int* d_n_dets, const float* d_dets, int det_ld, int det_cap, const int* d_n_out, const float* d_out,
                     int out_ld, int out_cap, float* dst);
 
+/* ---- instance masks of a segmentation head (yolo.py assemble_masks / mask_polygon on the device; YOLO(device_masks=True)) --------
+ * ss_mask_assemble: frame f's prototypes at d_proto + f*proto_frame_stride elements ([nm][mh][mw], IEEE half when proto_f16, else
+ * float), its detection rows at d_dets + f*dets_frame_stride floats ([max_rows][det_ld]: x1,y1,x2,y2 in original pixels, the nm
+ * coefficients from column coef_off), its geometry d_geom + f*geom_frame_stride = {gain, pad_x, pad_y} (0: shared by all frames).
+ * For the rows below min(d_counts[f], max_rows): box = x * gain + pad, cropped linear combination on the prototype grid, bilinear
+ * (align_corners = false) to ih x iw = 4 mh x 4 mw, > 0, in the float32 order tests/test_masks_device_cpu.py restates.  Writes whole
+ * bit planes uint32 [max_rows][ih][ceil(iw/32)] at d_bits + f*bits_frame_stride words (bit x%32 of word x/32 = pixel (y, x)); rows
+ * at or beyond the count are not written.  Constraints: 1 <= nm <= 64, mw <= 256.
+ * ss_mask_outline: for the same rows of packed planes (layout as above), the polygon yolo.mask_polygon returns: d_pts + f*pts_frame_stride
+ * int32 [max_rows][cap][2] (x, y) and d_npts[f*npts_frame_stride + r] = its length, or -length (no points written) when longer than
+ * cap.  d_bits_copy (NULL: none) receives a copy of each processed plane (e.g. pinned host memory, layout as d_bits with
+ * copy_frame_stride).  d_scratch: scratch_bytes of device memory, at least one label plane of 4 * ih * iw bytes; every whole plane in
+ * it serves one workgroup (at most 1024).  ih * ceil(iw/32) <= 12800.
+ * Both check every argument before the context: a bad call returns SS_ERR_INVALID without touching the device, even with ctx NULL. */
+int ss_mask_assemble(ss_ctx* ctx, void* hip_stream, const void* d_proto, int proto_f16, long long proto_frame_stride, int nm, int mh, int mw,
+                     const float* d_dets, long long dets_frame_stride, int det_ld, int coef_off, const int* d_counts, int n_frames,
+                     int max_rows, const float* d_geom, long long geom_frame_stride, int ih, int iw, uint32_t* d_bits,
+                     long long bits_frame_stride);
+int ss_mask_outline(ss_ctx* ctx, void* hip_stream, const uint32_t* d_bits, long long bits_frame_stride, const int* d_counts, int n_frames,
+                    int max_rows, int ih, int iw, int cap, int* d_pts, long long pts_frame_stride, int* d_npts, long long npts_frame_stride,
+                    uint32_t* d_bits_copy, long long copy_frame_stride, void* d_scratch, long long scratch_bytes);
+
 /* Largest n_frames ss_track_update_group / ss_cmc_estimate accept (compile-time SS_FMAX). */
 int ss_max_group_frames(void);
 /* hip_event (a hipEvent_t of the caller, NULL: none) is recorded on the tracker's stream right after the association launch

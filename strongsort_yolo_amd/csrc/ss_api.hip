@@ -36,6 +36,11 @@ void ss_launch_unpack_feats(const void*, int, const int*, const int*, int, int, 
 void ss_launch_pack_results(const int*, const float*, int, int, const int*, const float*, int, int, float*, hipStream_t);
 void ss_launch_overlay(uint8_t*, int, long long, int, int, int, const void*, const int*, const uint8_t*, const uint8_t*, hipStream_t);
 void ss_launch_cmc(const uint8_t*, int, long long, int, int, int, uint8_t*, long long, int, int, int, int, int, double, int*, const int*, double*, hipStream_t);
+int  ss_mask_max_words();
+void ss_launch_mask_assemble(const void*, int, long long, int, int, int, const float*, long long, int, int, const int*, int, int, const float*,
+                             long long, int, int, uint32_t*, long long, hipStream_t);
+void ss_launch_mask_outline(const uint32_t*, long long, const int*, int, int, int, int, int, int*, long long, int*, long long, uint32_t*,
+                            long long, int*, int, hipStream_t);
 extern "C" void ss_step_kernel_attr();
 
 static std::string g_last_error;
@@ -388,6 +393,55 @@ extern "C" int ss_overlay(ss_ctx* c, void* hip_stream, uint8_t* d_frames, int ba
     if (!c || !d_frames || !d_prims || !d_prim_off || !d_chars || batch < 0 || batch > 65535 || row_stride < 3 * w)
         return fail(c, SS_ERR_INVALID, "ss_overlay: bad argument");
     ss_launch_overlay(d_frames, batch, frame_batch_stride, h, w, row_stride, d_prims, d_prim_off, d_chars, c->font, (hipStream_t)hip_stream);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+// ---- instance masks of a segmentation head (ss_mask.hip) -------------------------------------------------------------------
+// Every argument is checked before the context: a bad call returns SS_ERR_INVALID without touching the device, context or not.
+extern "C" int ss_mask_assemble(ss_ctx* c, void* hip_stream, const void* d_proto, int proto_f16, long long proto_frame_stride, int nm, int mh,
+                                int mw, const float* d_dets, long long dets_frame_stride, int det_ld, int coef_off, const int* d_counts,
+                                int n_frames, int max_rows, const float* d_geom, long long geom_frame_stride, int ih, int iw, uint32_t* d_bits,
+                                long long bits_frame_stride)
+{
+    const char* bad = nullptr;
+    const long long wpr = (iw + 31) / 32;
+    if (!d_proto || !d_dets || !d_counts || !d_geom || !d_bits) bad = "null pointer";
+    else if (nm < 1 || nm > 64) bad = "nm outside 1..64";
+    else if (mh < 1 || mw < 1 || mw > 256 || ih != 4 * mh || iw != 4 * mw) bad = "input size must be 4 x the prototype size, prototype width <= 256";
+    else if (n_frames < 1 || n_frames > 65535 || max_rows < 1 || max_rows > 65535) bad = "n_frames / max_rows outside 1..65535";
+    else if (coef_off < 4 || det_ld < coef_off + nm) bad = "coefficient columns outside the detection row";
+    else if (n_frames > 1 && (proto_frame_stride < (long long)nm * mh * mw || dets_frame_stride < (long long)max_rows * det_ld ||
+                              geom_frame_stride < 0 || bits_frame_stride < (long long)max_rows * ih * wpr))
+        bad = "frame strides overlap";
+    if (bad) return fail(c, SS_ERR_INVALID, std::string("ss_mask_assemble: ") + bad);
+    if (!c) return fail(c, SS_ERR_INVALID, "ss_mask_assemble: null context");
+    ss_launch_mask_assemble(d_proto, proto_f16, proto_frame_stride, nm, mh, mw, d_dets, dets_frame_stride, det_ld, coef_off, d_counts, n_frames,
+                            max_rows, d_geom, geom_frame_stride, ih, iw, d_bits, bits_frame_stride, (hipStream_t)hip_stream);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+extern "C" int ss_mask_outline(ss_ctx* c, void* hip_stream, const uint32_t* d_bits, long long bits_frame_stride, const int* d_counts, int n_frames,
+                               int max_rows, int ih, int iw, int cap, int* d_pts, long long pts_frame_stride, int* d_npts, long long npts_frame_stride,
+                               uint32_t* d_bits_copy, long long copy_frame_stride, void* d_scratch, long long scratch_bytes)
+{
+    const char* bad = nullptr;
+    const long long wpr = (iw + 31) / 32, plane = (long long)ih * iw * 4;
+    if (!d_bits || !d_counts || !d_pts || !d_npts || !d_scratch) bad = "null pointer";
+    else if (ih < 1 || iw < 1 || ih * wpr > ss_mask_max_words()) bad = "mask larger than the kernel's LDS plane";
+    else if (n_frames < 1 || n_frames > 65535 || max_rows < 1 || max_rows > 65535) bad = "n_frames / max_rows outside 1..65535";
+    else if (cap < 1 || cap > (1 << 20)) bad = "cap outside 1..2^20";
+    else if (scratch_bytes < plane) bad = "scratch smaller than one label plane (4 * ih * iw bytes)";
+    else if (n_frames > 1 && (bits_frame_stride < (long long)max_rows * ih * wpr || pts_frame_stride < (long long)max_rows * cap * 2 ||
+                              npts_frame_stride < max_rows || (d_bits_copy && copy_frame_stride < (long long)max_rows * ih * wpr)))
+        bad = "frame strides overlap";
+    if (bad) return fail(c, SS_ERR_INVALID, std::string("ss_mask_outline: ") + bad);
+    if (!c) return fail(c, SS_ERR_INVALID, "ss_mask_outline: null context");
+    const long long slots = scratch_bytes / plane;
+    ss_launch_mask_outline(d_bits, bits_frame_stride, d_counts, n_frames, max_rows, ih, iw, cap, d_pts, pts_frame_stride, d_npts,
+                           npts_frame_stride, d_bits_copy, copy_frame_stride, (int*)d_scratch, (int)(slots < 1024 ? slots : 1024),
+                           (hipStream_t)hip_stream);
     HIPCHK(c, hipGetLastError());
     return SS_OK;
 }

@@ -438,6 +438,35 @@ class TrackerEngine:
                                         _ptr(out) if out is not None else None, out.shape[1] if out is not None else 0,
                                         out.shape[0] if out is not None else 0, _ptr(dst)))
 
+    def mask_assemble(self, proto: torch.Tensor, dets: torch.Tensor, counts: torch.Tensor, geom: torch.Tensor, coef_off: int,
+                      bits: torch.Tensor, stream=None):
+        """Packed instance masks of a frame group (csrc ss_mask.hip k_mask_assemble): proto [F, nm, mh, mw] f16 / f32, dets [F, R, ld]
+        float32 (original-pixel boxes, coefficients from column coef_off), counts [F] int32, geom [F, >=3] float32 rows (gain, pad_x,
+        pad_y) -> bits uint32-sized [F, R, 4 mh, ceil(4 mw / 32)] (int32 tensor), rows below each frame's count written."""
+        F, nm, mh, mw = proto.shape
+        assert proto.is_contiguous() and dets.is_contiguous() and bits.is_contiguous() and geom.is_contiguous()
+        assert dets.dtype == torch.float32 and geom.dtype == torch.float32 and counts.dtype == torch.int32
+        assert proto.dtype in (torch.float16, torch.float32) and dets.shape[0] == F and bits.shape[:2] == dets.shape[:2]
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        self._ck(self.L.ss_mask_assemble(self.ctx, C.c_void_p(st.cuda_stream), _ptr(proto), int(proto.dtype == torch.float16), proto.stride(0),
+                                         nm, mh, mw, _ptr(dets), dets.stride(0), dets.shape[2], coef_off, _ptr(counts), F, dets.shape[1],
+                                         _ptr(geom), geom.stride(0) if F > 1 else 0, 4 * mh, 4 * mw, _ptr(bits), bits.stride(0)))
+
+    def mask_outline(self, bits: torch.Tensor, counts: torch.Tensor, iw: int, pts: torch.Tensor, npts: torch.Tensor, scratch: torch.Tensor,
+                     bits_copy: torch.Tensor = None, stream=None):
+        """The polygon yolo.mask_polygon returns for every kept row of packed masks bits [F, R, ih, ceil(iw/32)] (csrc k_mask_outline):
+        pts [F, R, cap, 2] int32, npts [F, R] int32 (-length: longer than cap, no points).  scratch: label planes (4 ih iw bytes
+        each, one per workgroup).  bits_copy (device or pinned host, bits' shape): a copy of every processed plane."""
+        F, R, ih = bits.shape[:3]
+        assert bits.is_contiguous() and pts.is_contiguous() and npts.is_contiguous() and pts.dtype == torch.int32 and npts.dtype == torch.int32
+        assert pts.shape[:2] == (F, R) and npts.shape == (F, R) and counts.dtype == torch.int32
+        if bits_copy is not None:
+            assert bits_copy.is_contiguous() and bits_copy.shape[1:] == bits.shape[1:] and (bits_copy.is_cuda or bits_copy.is_pinned())
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        self._ck(self.L.ss_mask_outline(self.ctx, C.c_void_p(st.cuda_stream), _ptr(bits), bits.stride(0), _ptr(counts), F, R, ih, iw,
+                                        pts.shape[2], _ptr(pts), pts.stride(0), _ptr(npts), npts.stride(0), _ptr(bits_copy),
+                                        bits_copy.stride(0) if bits_copy is not None else 0, _ptr(scratch), scratch.numel() * scratch.element_size()))
+
     def nms(self, pred: torch.Tensor, nc: int, dcfg: DetectConfig, gain: float, pad_x: float, pad_y: float,
             w0: int, h0: int, n_extra: int = 0, rows=None, keep=None, count=None):
         """pred: [(4+nc+n_extra), N] float32 on the device."""

@@ -152,35 +152,49 @@ def mask_polygon(mask: np.ndarray) -> np.ndarray:
     return best.astype(np.float32)
 
 
+def unpack_masks(bits: np.ndarray, iw: int) -> torch.Tensor:
+    """Bit-packed masks uint32 / int32 [n, ih, ceil(iw/32)] (bit x % 32 of word x / 32 = pixel (y, x), csrc/ss_mask.hip) -> bool [n, ih, iw]."""
+    b = np.ascontiguousarray(bits).view(np.uint8)
+    return torch.from_numpy(np.unpackbits(b, axis=-1, bitorder="little")[..., :iw].astype(bool))
+
+
 class Masks:
     """Instance masks of one frame: the part of Ultralytics' `Masks` the reference touches (/root/reference/yolo_multi_model.py
     :71-72 iterates them in step with the boxes, :112-121 draws `masks.xy`).  `data`: bool [n, ih, iw] at the network-input size,
     `xy`: one float32 [k, 2] polygon per mask in ORIGINAL-image pixels, `xyn`: the same normalised.  Assembled lazily on the host
-    from the frame's prototypes and the kept rows' coefficients (`assemble_masks`)."""
+    from the frame's prototypes and the kept rows' coefficients (`assemble_masks`) — or, from a YOLO(device_masks=True), unpacked
+    from the device's bit-packed masks (`_bits`) with the device's polygons in mask pixels (`_polys`; None for a mask whose
+    polygon was longer than the device's capacity: traced on the host)."""
 
-    def __init__(self, proto, coef, boxes_in, in_hw, orig_shape, gain, pad_xy, _data=None):
+    def __init__(self, proto, coef, boxes_in, in_hw, orig_shape, gain, pad_xy, _data=None, _bits=None, _polys=None):
         self._proto, self._coef, self._boxes, self._in_hw = proto, coef, boxes_in, tuple(int(v) for v in in_hw)
         self.orig_shape, self._gain, self._pad = tuple(int(v) for v in orig_shape[:2]), float(gain), (float(pad_xy[0]), float(pad_xy[1]))
         self._data, self._xy = _data, None
+        self._bits, self._polys = _bits, _polys
 
     @property
     def data(self):
         if self._data is None:
-            self._data = assemble_masks(self._proto, self._coef, self._boxes, self._in_hw)
+            if self._bits is not None:
+                self._data = unpack_masks(self._bits, self._in_hw[1])
+            else:
+                self._data = assemble_masks(self._proto, self._coef, self._boxes, self._in_hw)
         return self._data
+
+    def _scale(self, p):
+        H, W = self.orig_shape
+        if len(p):
+            p = (p - np.float32(self._pad)) / np.float32(self._gain)       # scale_coords: un-pad, un-scale, clip
+            p[:, 0], p[:, 1] = p[:, 0].clip(0, W), p[:, 1].clip(0, H)
+        return p.astype(np.float32)
 
     @property
     def xy(self):
         if self._xy is None:
-            H, W = self.orig_shape
-            out = []
-            for m in self.data.numpy():
-                p = mask_polygon(m)
-                if len(p):
-                    p = (p - np.float32(self._pad)) / np.float32(self._gain)       # scale_coords: un-pad, un-scale, clip
-                    p[:, 0], p[:, 1] = p[:, 0].clip(0, W), p[:, 1].clip(0, H)
-                out.append(p.astype(np.float32))
-            self._xy = out
+            if self._polys is not None:
+                self._xy = [self._scale(mask_polygon(self.data[i].numpy()) if p is None else p) for i, p in enumerate(self._polys)]
+            else:
+                self._xy = [self._scale(mask_polygon(m)) for m in self.data.numpy()]
         return self._xy
 
     @property
@@ -193,8 +207,10 @@ class Masks:
 
     def __getitem__(self, i):
         i = _row(i, len(self))
+        sel = np.arange(len(self))[i.numpy() if isinstance(i, torch.Tensor) else i]
         return Masks(self._proto, self._coef[i], self._boxes[i], self._in_hw, self.orig_shape, self._gain, self._pad,
-                     None if self._data is None else self._data[i])
+                     None if self._data is None else self._data[i], None if self._bits is None else self._bits[sel],
+                     None if self._polys is None else [self._polys[k] for k in sel])
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
@@ -220,11 +236,15 @@ class YOLO:
     `model.track(..., persist=False)` would."""
 
     def __init__(self, weights: str = "yolov8n.pt", seed: int = 0, random_init_ok: bool = False, reid_batch: int = 128,
-                 camera_motion: bool = False, reid_weights: Optional[str] = None, reid_fp32: bool = True, half: bool = True):
+                 camera_motion: bool = False, reid_weights: Optional[str] = None, reid_fp32: bool = True, half: bool = True,
+                 device_masks: bool = False):
         """reid_fp32 (default since round 6): ReID crops + OSNet-x0.25 in fp32 on the fp32 kernels — appearance distances within 1e-4 of a CPU fp32
         network, which f16 activations miss by 330x (reid_fp32=False: the f16 throughput mode, ~1.2x the per-frame rate, 1.7x the stream rate).
         half=False: the DETECTOR in fp32 as well (the reference's own precision: it passes no half=, yolo_multi_model.py:41) on the
-        fp32 convolution kernels (csrc/ss_ops32.hip k32_conv) — NMS keep lists then equal the CPU fp32 network's; implies reid_fp32."""
+        fp32 convolution kernels (csrc/ss_ops32.hip k32_conv) — NMS keep lists then equal the CPU fp32 network's; implies reid_fp32.
+        device_masks (segmentation models): every call also assembles the kept rows' masks and traces their polygons on the device
+        (csrc/ss_mask.hip) and downloads bits and points instead of the prototypes; `Results.masks` then needs no host arithmetic
+        beyond unpacking and scale_coords.  Default False: masks are built on the host when first read (assemble_masks / mask_polygon)."""
         self.weights = weights
         self.reid_weights = reid_weights          # OSNet-x0.25 state_dict; same policy as the detector's (raise unless random init is asked for)
         self.random_init_ok = random_init_ok
@@ -247,6 +267,7 @@ class YOLO:
             self._pipe_kw["reid_half"] = False
         if not half:
             self._pipe_kw["half"] = False
+        self.device_masks = bool(device_masks)
         self._fill = None
         self._frame_index = 0
 
@@ -296,7 +317,8 @@ class YOLO:
             self._h_cnt = self._h_res[:2].view(torch.int32)
             self._h_dets = self._h_res[2:2 + nd].view(p.dets.shape[1], p.dets.shape[2])
             self._h_rows = self._h_res[2 + nd:].view(p.out.shape[1], p.out.shape[2])
-            self._h_proto = torch.empty(p.proto.shape[1:], dtype=p.proto.dtype).pin_memory() if p.nm else None
+            self._h_proto = torch.empty(p.proto.shape[1:], dtype=p.proto.dtype).pin_memory() if p.nm and not self.device_masks else None
+            self._h_masks = self._mask_host(p, 1, p.dets.shape[1]) if p.nm and self.device_masks else None
         return self._pipe
 
     def _run(self, image, device, track):
@@ -308,7 +330,9 @@ class YOLO:
             self._fill(pipe, 0, self._frame_index)
         pipe.step(track=track)
         pipe.eng.pack_results(pipe.ndets, pipe.dets[0], pipe.nout if track else None, pipe.out[0] if track else None, self._h_res)
-        if pipe.nm:
+        if self._h_masks is not None:
+            self._mask_launch(pipe, pipe.proto, pipe.dets, pipe.ndets, self._h_masks)
+        elif pipe.nm:
             self._h_proto.copy_(pipe.proto[0], non_blocking=True)
         torch.cuda.current_stream(pipe.dev).synchronize()            # the one synchronisation of the call
         pipe.eng.check_errors()
@@ -316,7 +340,7 @@ class YOLO:
         n, m = int(self._h_cnt[0]), int(self._h_cnt[1])
         self._warn_if_capped(pipe, n, track)
         return self._results(image, pipe, self._h_dets[:n].clone(), self._h_rows[:m].clone() if track else None,
-                             self._h_proto.clone() if pipe.nm else None)
+                             self._h_proto.clone() if self._h_proto is not None else None, self._mask_rows(self._h_masks, 0, n))
 
     def _warn_if_capped(self, pipe, n_kept, track):
         """The tracking pipeline carries at most pipe.max_det (<= 128, <= reid_batch) detections per frame, highest scores first;
@@ -341,7 +365,8 @@ class YOLO:
             self._pred_key = key
             self._hp_dets = torch.empty(p.dets.shape[1], p.dets.shape[2]).pin_memory()
             self._hp_cnt = torch.zeros(1, dtype=torch.int32).pin_memory()
-            self._hp_proto = torch.empty(p.proto.shape[1:], dtype=p.proto.dtype).pin_memory() if p.nm else None
+            self._hp_proto = torch.empty(p.proto.shape[1:], dtype=p.proto.dtype).pin_memory() if p.nm and not self.device_masks else None
+            self._hp_masks = self._mask_host(p, 1, p.dets.shape[1]) if p.nm and self.device_masks else None
         pipe = self._pred_pipe
         pipe.eng.upload(pipe.frames[0], image)
         if self._fill is not None:
@@ -349,28 +374,68 @@ class YOLO:
         pipe.step(track=False)
         self._hp_dets.copy_(pipe.dets[0], non_blocking=True)
         self._hp_cnt.copy_(pipe.ndets, non_blocking=True)
-        if pipe.nm:
+        if self._hp_masks is not None:
+            self._mask_launch(pipe, pipe.proto, pipe.dets, pipe.ndets, self._hp_masks)
+        elif pipe.nm:
             self._hp_proto.copy_(pipe.proto[0], non_blocking=True)
         torch.cuda.current_stream(pipe.dev).synchronize()
         pipe.eng.check_errors()
-        return self._results(image, pipe, self._hp_dets[:int(self._hp_cnt[0])].clone(), None,
-                             self._hp_proto.clone() if pipe.nm else None)
+        n = int(self._hp_cnt[0])
+        return self._results(image, pipe, self._hp_dets[:n].clone(), None,
+                             self._hp_proto.clone() if self._hp_proto is not None else None, self._mask_rows(self._hp_masks, 0, n))
 
-    def _results(self, image, pipe, dets, rows, proto=None):
+    # ---- device masks (device_masks=True) ---------------------------------------------------------------------
+    MASK_CAP = 2048            # points per device polygon; a longer one is traced on the host (instance masks on the device)
+    MASK_SLOTS = 256           # label planes of the outline kernel's scratch = its workgroups (one per CU)
+
+    def _mask_host(self, pipe, F, R):
+        """Pinned host buffers the mask kernels write the kept rows' bits, polygons and lengths into (one frame group), and the
+        pipeline's device buffers (packed masks, outline scratch: allocated once per pipeline, MASK_SLOTS label planes)."""
+        ih, iw = pipe.geom.out_h, pipe.geom.out_w
+        wpr = (iw + 31) // 32
+        dev = getattr(pipe, "_mask_dev", None)
+        if dev is None or dev["bits"].shape[0] < F or dev["bits"].shape[1] < R:
+            dev = pipe._mask_dev = {"bits": torch.empty(F, R, ih, wpr, dtype=torch.int32, device=pipe.dev),
+                                    "scratch": torch.empty(self.MASK_SLOTS * ih * iw, dtype=torch.int32, device=pipe.dev)}
+        return {"bits": torch.empty(F, R, ih, wpr, dtype=torch.int32).pin_memory(),
+                "pts": torch.empty(F, R, self.MASK_CAP, 2, dtype=torch.int32).pin_memory(),
+                "npts": torch.empty(F, R, dtype=torch.int32).pin_memory(), "dev": dev, "iw": iw}
+
+    def _mask_launch(self, pipe, proto, dets, ndets, h):
+        """Both mask kernels on the current stream for the frames of `dets` [F, R, ld]: packed masks into the pipeline's device
+        buffer, then outlines, the outline kernel copying every kept plane into the pinned `h['bits']`."""
+        F, R = dets.shape[:2]
+        d = h["dev"]
+        bits = d["bits"][:F, :R] if d["bits"].shape[:2] != (F, R) else d["bits"]
+        pipe.eng.mask_assemble(proto, dets, ndets, pipe.geom_dev[:F], 6 + pipe.nk, bits)
+        pipe.eng.mask_outline(bits, ndets, h["iw"], h["pts"][:F], h["npts"][:F], d["scratch"], bits_copy=h["bits"][:F])
+
+    @staticmethod
+    def _mask_rows(h, f, n):
+        """Frame f's first n device masks from the pinned buffers (after the synchronisation): (bits copy, polygons)."""
+        if h is None:
+            return None
+        npts = h["npts"][f, :n].numpy()
+        pts = h["pts"][f].numpy()
+        polys = [pts[r, :k].astype(np.float32) if k >= 0 else None for r, k in enumerate(npts.tolist())]
+        return h["bits"][f, :n].numpy().copy(), polys
+
+    def _results(self, image, pipe, dets, rows, proto=None, dm=None):
         kpts = masks = None
         if pipe.nk:
             k = dets[:, 6:6 + pipe.nk].reshape(dets.shape[0], pipe.nk // 3, 3).clone()
             k[..., 0] = (k[..., 0] - pipe.pad_x) / pipe.gain
             k[..., 1] = (k[..., 1] - pipe.pad_y) / pipe.gain
             kpts = k
-        if pipe.nm and proto is not None:
+        if pipe.nm and (proto is not None or dm is not None):
             # masks are cut with the DETECTION boxes (as upstream: assembled at predict time, before the tracker replaces the boxes),
             # brought back to the network-input frame: x * gain + pad
             b = dets[:, :4].clone()
             b[:, [0, 2]] = b[:, [0, 2]] * pipe.gain + pipe.pad_x
             b[:, [1, 3]] = b[:, [1, 3]] * pipe.gain + pipe.pad_y
             masks = Masks(proto, dets[:, 6 + pipe.nk:6 + pipe.nk + pipe.nm].clone(), b, (pipe.geom.out_h, pipe.geom.out_w),
-                          image.shape, pipe.gain, (pipe.pad_x, pipe.pad_y))
+                          image.shape, pipe.gain, (pipe.pad_x, pipe.pad_y), _bits=None if dm is None else dm[0],
+                          _polys=None if dm is None else dm[1])
         if rows is None:
             return [Results(image, self.names, Boxes(dets[:, :4], dets[:, 4], dets[:, 5]),
                             None if kpts is None else Keypoints(kpts), masks)]
@@ -438,7 +503,9 @@ class YOLO:
         h_rows = torch.empty(ring, F, pipe.outs.shape[2], 8).pin_memory()
         h_dets = torch.empty(ring, F, pipe.bufs[0].dets.shape[1], pipe.bufs[0].dets.shape[2]).pin_memory()
         h_cnt = torch.zeros(ring, 2, F, dtype=torch.int32).pin_memory()
-        h_proto = torch.empty((ring, F) + tuple(pipe.bufs[0].proto.shape[1:]), dtype=pipe.bufs[0].proto.dtype).pin_memory() if pipe.nm else None
+        dmask = pipe.nm and self.device_masks
+        h_proto = torch.empty((ring, F) + tuple(pipe.bufs[0].proto.shape[1:]), dtype=pipe.bufs[0].proto.dtype).pin_memory() if pipe.nm and not dmask else None
+        h_masks = [self._mask_host(pipe, F, pipe.bufs[0].dets.shape[1]) for _ in range(ring)] if dmask else None     # in place of h_proto
         d_frames = torch.empty((ring, F, H, W, 3), dtype=torch.uint8, device=pipe.dev) if keep_device_frames else None
         done = [torch.cuda.Event() for _ in range(ring)]
         pending = []                                                      # (group index, frames of the group)
@@ -458,6 +525,8 @@ class YOLO:
             h_dets[slot, :nv].copy_(b.dets[:nv], non_blocking=True)
             if h_proto is not None:
                 h_proto[slot, :nv].copy_(b.proto[:nv], non_blocking=True)
+            if h_masks is not None:
+                self._mask_launch(pipe, b.proto[:nv], b.dets[:nv], b.ndets[:nv], h_masks[slot])
             if d_frames is not None:
                 d_frames[slot, :nv].copy_(b.frames[:nv], non_blocking=True)       # the set's frames, before the set is refilled
             done[slot].record(torch.cuda.current_stream(pipe.dev))
@@ -473,7 +542,8 @@ class YOLO:
                 n, m = int(h_cnt[slot, 0, f]), int(h_cnt[slot, 1, f])
                 self._warn_if_capped(pipe, n, True)
                 res = self._results(img, pipe, h_dets[slot, f, :n].clone(), h_rows[slot, f, :m].clone(),
-                                    None if h_proto is None else h_proto[slot, f].clone())
+                                    None if h_proto is None else h_proto[slot, f].clone(),
+                                    None if h_masks is None else self._mask_rows(h_masks[slot], f, n))
                 if d_frames is not None:
                     res[0].orig_img_device = d_frames[slot, f]
                 yield res
