@@ -205,6 +205,39 @@ int ss_track_update_group(ss_ctx* ctx, int n_frames, const float* d_dets, const 
 int ss_track_update(ss_ctx* ctx, const float* d_dets, const int* d_ndets, const float* d_feats,
                     const int* d_img_hw, float* d_out, int* d_nout);
 
+/* ---- BYTE tracker family (docs/BYTETRACK.md): ByteTrack (xyah Kalman) and BoT-SORT without GMC / ReID (xywh Kalman) ------
+ * Opt-in, IoU-only association on detection scores (no ReID features).  The state is hung off an existing context (its streams,
+ * its HIP stream, its error words); ss_byte_create on a context that already has one replaces it. */
+typedef struct ss_byte_config {
+    double track_high_thresh;    /* 0.25  first-association rows: score >= this                   */
+    double track_low_thresh;     /* 0.1   second-association rows: low < score < high              */
+    double new_track_thresh;     /* 0.25  births: score >= this                                     */
+    double match_thresh;         /* 0.8   first association: fused 1-IoU <= this                    */
+    double std_weight_position;  /* 1/20                                                             */
+    double std_weight_velocity;  /* 1/160                                                            */
+    int    track_buffer;         /* 30    max_time_lost = int(frame_rate / 30 * track_buffer)         */
+    int    frame_rate;           /* 30                                                               */
+    int    fuse_score;           /* 1     cost = 1 - (1 - cost) * score in the fused stages           */
+    int    kalman_xywh;          /* 0 xyah (ByteTrack), 1 xywh (BoT-SORT)                            */
+    int    max_tracks;           /* <= SS_MAX_TRACKS per stream (tracked + lost + unconfirmed)        */
+    int    max_dets;             /* <= SS_MAX_DETS per frame                                         */
+} ss_byte_config;
+int ss_byte_create(ss_ctx* ctx, const ss_byte_config* cfg);
+int ss_byte_destroy(ss_ctx* ctx);
+/* A group of n_frames (1..32) frames of every stream in ONE launch, associated strictly in order; layouts as
+ * ss_track_update_group without features: d_dets [n_frames][n_streams][SS_MAX_DETS][6], d_ndets [n_frames][n_streams] ->
+ * d_out [n_frames][n_streams][SS_MAX_TRACKS][8] (x1,y1,x2,y2,track_id,class_id,conf,det_idx; det_idx >= 0 always),
+ * d_nout [n_frames][n_streams].  Asynchronous on the context's stream, capturable.  A frame with more than max_dets rows is
+ * tracked on its first max_dets; births beyond max_tracks are dropped; either raises SS_ERR_CAPACITY at ss_check_errors
+ * (set until ss_byte_reset). */
+int ss_byte_update_group(ss_ctx* ctx, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
+int ss_byte_update(ss_ctx* ctx, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
+int ss_byte_reset(ss_ctx* ctx, int stream);                /* stream < 0: all streams; ids restart at 1, frame_id at 1 */
+/* Synchronous: the table of one stream in list order (tracked list, then lost list); any array may be NULL.
+ * state 1 tracked, 2 lost; mean [n][8] (xyah or xywh state). */
+int ss_byte_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracked, int* n_lost, int* next_id, int* frame_id,
+                       int* track_id, int* state, int* activated, double* mean);
+
 /* ---- N4  camera-motion compensation (upstream StrongSORT: tracker.camera_update(prev, cur) before tracker.predict();
  * not in the reference snapshot; optional) ----------------------------------------------------------
  * ss_cmc_estimate: for the n_frames x n_streams BGR u8 frames at d_frames ([F][S] order, frame_stride bytes apart) build

@@ -52,3 +52,45 @@ class DetectConfig:
     pad_value: int = 114
     max_wh: float = 7680.0            # per-class box offset (non-agnostic NMS)
     max_nms: int = 8192               # candidate cap after the confidence filter (LDS sort capacity)
+
+
+@dataclass(frozen=True)
+class ByteTrackConfig:
+    """The BYTE tracker family (docs/BYTETRACK.md, decisions B-01..): Ultralytics' bytetrack.yaml / botsort.yaml defaults
+    (recalled from Ultralytics 8.3.x; botsort without GMC and ReID).  kalman = "xyah" (ByteTrack) or "xywh" (BoT-SORT)."""
+    track_high_thresh: float = 0.25
+    track_low_thresh: float = 0.1
+    new_track_thresh: float = 0.25
+    track_buffer: int = 30
+    match_thresh: float = 0.8
+    fuse_score: bool = True
+    frame_rate: int = 30
+    kalman: str = "xyah"
+    std_weight_position: float = 1.0 / 20
+    std_weight_velocity: float = 1.0 / 160
+    # capacities of the device-resident track table (per stream: tracked + lost + unconfirmed) and of a frame
+    max_tracks: int = 256
+    max_dets: int = 128
+
+    def __post_init__(self):
+        if self.kalman not in ("xyah", "xywh"):
+            raise ValueError(f"ByteTrackConfig.kalman: 'xyah' or 'xywh', not {self.kalman!r}")
+        if not (0 < self.max_tracks <= 256 and 0 < self.max_dets <= 128):
+            raise ValueError("ByteTrackConfig: max_tracks <= 256 and max_dets <= 128 (the device table's capacity)")
+
+    @property
+    def max_time_lost(self) -> int:
+        return int(self.frame_rate / 30.0 * self.track_buffer)
+
+    def as_dict(self):
+        return asdict(self)
+
+
+# tracker_type of YOLO / FramePipeline / the CLI -> the BYTE configuration it runs (None: StrongSORT)
+TRACKER_TYPES = ("strongsort", "bytetrack", "botsort")
+
+
+def byte_config(tracker_type: str):
+    if tracker_type not in TRACKER_TYPES:
+        raise ValueError(f"tracker_type must be one of {TRACKER_TYPES}, not {tracker_type!r}")
+    return None if tracker_type == "strongsort" else ByteTrackConfig(kalman="xywh" if tracker_type == "botsort" else "xyah")

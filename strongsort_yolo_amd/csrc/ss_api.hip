@@ -5,6 +5,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include "ss_common.h"
 
@@ -42,6 +43,7 @@ void ss_launch_mask_assemble(const void*, int, long long, int, int, int, const f
 void ss_launch_mask_outline(const uint32_t*, long long, const int*, int, int, int, int, int, int*, long long, int*, long long, uint32_t*,
                             long long, int*, int, hipStream_t);
 extern "C" void ss_step_kernel_attr();
+void ss_launch_byte_group(const SSByteDev&, int, const float*, const int*, float*, int*, hipStream_t);
 
 static std::string g_last_error;
 
@@ -101,6 +103,9 @@ struct ss_ctx {
     hipStream_t chain_stream;
     hipEvent_t ev_head, ev_chain;
     bool chain_pending;
+    // the BYTE tracker family (ss_byte_create), NULL until attached
+    struct Byte { SSByteDev dev; ss_byte_config cfg; std::vector<void*> allocs; };
+    Byte* byte = nullptr;
 };
 
 static int fail(ss_ctx* c, int code, const std::string& msg)
@@ -247,6 +252,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     if (c->ev_head) (void)hipEventDestroy(c->ev_head);
     if (c->ev_chain) (void)hipEventDestroy(c->ev_chain);
     for (void* p : c->allocs) (void)hipFree(p);
+    if (c->byte) { for (void* p : c->byte->allocs) (void)hipFree(p); delete c->byte; }
     for (auto& st : c->stage) { if (st.ev) (void)hipEventDestroy(st.ev); if (st.p) (void)hipHostFree(st.p); }
     for (auto& st : c->bstage) { if (st.ev) (void)hipEventDestroy(st.ev); if (st.p) (void)hipHostFree(st.p); }
     if (c->back.p) (void)hipHostFree(c->back.p);
@@ -722,6 +728,12 @@ extern "C" int ss_check_errors(ss_ctx* c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (size_t s = 0; s < e.size(); ++s)
         if (e[s]) return fail(c, e[s], "device error flag on stream " + std::to_string(s));
+    if (c->byte) {                                           // the BYTE tracker's flags (capacity, infeasible)
+        HIPCHK(c, hipMemcpyAsync(e.data(), c->byte->dev.err, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (size_t s = 0; s < e.size(); ++s)
+            if (e[s]) return fail(c, e[s], "BYTE tracker: device error flag on stream " + std::to_string(s));
+    }
     for (int u = 0; u < c->nms_units; ++u) {                 // NMS candidate overflow (flag stays set until ss_reset)
         int f = 0;
         HIPCHK(c, hipMemcpy(&f, ss_nms_error_flag(c->nms_ws, u), 4, hipMemcpyDeviceToHost));
@@ -1059,5 +1071,122 @@ extern "C" int ss_assoc_timing_values(ss_ctx* c, float* out_ms, int cap, int* n)
     if (!c || !n || cap < 0 || (cap > 0 && !out_ms)) return SS_ERR_INVALID;
     *n = (int)c->ev_ms.size();
     for (int i = 0; i < cap && i < *n; ++i) out_ms[i] = c->ev_ms[i];
+    return SS_OK;
+}
+
+// ---- BYTE tracker family (ss_byte.hip) -----------------------------------------------------------------------------
+extern "C" int ss_byte_destroy(ss_ctx* c)
+{
+    if (!c) return fail(nullptr, SS_ERR_INVALID, "ss_byte_destroy: null context");
+    if (!c->byte) return SS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (void* p : c->byte->allocs) HIPCHK(c, hipFree(p));
+    delete c->byte;
+    c->byte = nullptr;
+    return SS_OK;
+}
+
+extern "C" int ss_byte_reset(ss_ctx* c, int stream)
+{
+    if (!c || !c->byte || stream >= c->dev.S) return fail(c, SS_ERR_INVALID, "ss_byte_reset: no BYTE state or bad stream");
+    SSByteDev& b = c->byte->dev;
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? b.S : stream + 1;
+    std::vector<int> ones(b.S, 1);
+    HIPCHK(c, hipMemsetAsync(b.frame + s0, 0, (s1 - s0) * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.err + s0, 0, (s1 - s0) * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.n_trk + s0, 0, (s1 - s0) * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.n_lost + s0, 0, (s1 - s0) * 4, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.next_id + s0, ones.data(), (s1 - s0) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SS_OK;
+}
+
+extern "C" int ss_byte_create(ss_ctx* c, const ss_byte_config* cfg)
+{
+    if (!c || !cfg) return fail(c, SS_ERR_INVALID, "ss_byte_create: null argument");
+    if (cfg->max_tracks < 1 || cfg->max_tracks > SS_MAXT || cfg->max_dets < 1 || cfg->max_dets > SS_MAXD || cfg->frame_rate < 1 ||
+        cfg->track_buffer < 0 || (cfg->kalman_xywh != 0 && cfg->kalman_xywh != 1))
+        return fail(c, SS_ERR_INVALID, "ss_byte_create: 1 <= max_tracks <= 256, 1 <= max_dets <= 128, frame_rate >= 1, kalman_xywh 0 / 1");
+    if (int rc = ss_byte_destroy(c)) return rc;
+    ss_ctx::Byte* B = new ss_ctx::Byte();
+    B->cfg = *cfg;
+    SSByteDev& b = B->dev;
+    memset(&b, 0, sizeof b);
+    b.S = c->dev.S;
+    b.xywh = cfg->kalman_xywh; b.fuse = cfg->fuse_score != 0;
+    b.max_time_lost = (int)(cfg->frame_rate / 30.0 * cfg->track_buffer);
+    b.max_tracks = cfg->max_tracks; b.max_dets = cfg->max_dets;
+    b.high = (float)cfg->track_high_thresh; b.low = (float)cfg->track_low_thresh; b.new_thresh = (float)cfg->new_track_thresh;
+    b.match = cfg->match_thresh; b.wp = cfg->std_weight_position; b.wv = cfg->std_weight_velocity;
+    const size_t S = b.S, T = SS_MAXT;
+    int rc = SS_OK;
+    auto al = [&](auto** p, size_t n) {
+        if (rc != SS_OK) return;
+        void* q = nullptr;
+        const size_t bytes = n * sizeof(**p);
+        hipError_t e = hipMalloc(&q, bytes);
+        if (e == hipSuccess) { B->allocs.push_back(q); e = hipMemsetAsync(q, 0, bytes, c->stream); }
+        if (e != hipSuccess) rc = fail(c, SS_ERR_HIP, std::string("ss_byte_create: ") + hipGetErrorString(e));
+        *p = (std::remove_reference_t<decltype(**p)>*)q;
+    };
+    al(&b.frame, S); al(&b.next_id, S); al(&b.err, S); al(&b.n_trk, S); al(&b.n_lost, S);
+    al(&b.trk, S * T); al(&b.lost, S * T);
+    al(&b.state, S * T); al(&b.act, S * T); al(&b.tid, S * T); al(&b.start, S * T); al(&b.end, S * T); al(&b.len, S * T); al(&b.det, S * T);
+    al(&b.score, S * T); al(&b.cls, S * T);
+    al(&b.mean, S * T * 8); al(&b.cov, S * T * 64); al(&b.spill, S * T * SS_MAXD);
+    c->byte = B;
+    if (rc == SS_OK) rc = ss_byte_reset(c, -1);
+    if (rc != SS_OK) { std::string m = c->err; (void)ss_byte_destroy(c); c->err = m; return rc; }
+    return SS_OK;
+}
+
+extern "C" int ss_byte_update_group(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout)
+{
+    if (!c || !d_dets || !d_ndets || !d_out || !d_nout) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: null argument");
+    if (!c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: no BYTE state (ss_byte_create)");
+    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: 1 <= n_frames <= SS_FMAX");
+    ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, d_out, d_nout, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+extern "C" int ss_byte_update(ss_ctx* c, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout)
+{
+    return ss_byte_update_group(c, 1, d_dets, d_ndets, d_out, d_nout);
+}
+
+extern "C" int ss_byte_get_tracks(ss_ctx* c, int s, int cap, int* n_tracked, int* n_lost, int* next_id, int* frame_id,
+                                  int* track_id, int* state, int* activated, double* mean)
+{
+    if (!c || !c->byte || s < 0 || s >= c->dev.S || cap < 0) return fail(c, SS_ERR_INVALID, "ss_byte_get_tracks: no BYTE state or bad stream");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const SSByteDev& b = c->byte->dev;
+    int nt = 0, nl = 0, nid = 0, fr = 0;
+    HIPCHK(c, hipMemcpy(&nt, b.n_trk + s, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&nl, b.n_lost + s, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&nid, b.next_id + s, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&fr, b.frame + s, 4, hipMemcpyDeviceToHost));
+    if (n_tracked) *n_tracked = nt;
+    if (n_lost) *n_lost = nl;
+    if (next_id) *next_id = nid;
+    if (frame_id) *frame_id = fr;
+    if (nt + nl > cap) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_tracks: cap too small");
+    const size_t T = SS_MAXT, sb = (size_t)s * T;
+    std::vector<int> trk(T), lost(T), st(T), act(T), id(T);
+    std::vector<double> mn(T * 8);
+    HIPCHK(c, hipMemcpy(trk.data(), b.trk + sb, T * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(lost.data(), b.lost + sb, T * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(st.data(), b.state + sb, T * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(act.data(), b.act + sb, T * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(id.data(), b.tid + sb, T * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(mn.data(), b.mean + sb * 8, T * 64, hipMemcpyDeviceToHost));
+    for (int i = 0; i < nt + nl; ++i) {
+        const int slot = i < nt ? trk[i] : lost[i - nt];
+        if (slot < 0 || slot >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_tracks: corrupt list");
+        if (track_id) track_id[i] = id[slot];
+        if (state) state[i] = st[slot];
+        if (activated) activated[i] = act[slot];
+        if (mean) for (int k = 0; k < 8; ++k) mean[i * 8 + k] = mn[slot * 8 + k];
+    }
     return SS_OK;
 }

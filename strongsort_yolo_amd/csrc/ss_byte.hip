@@ -1,0 +1,355 @@
+// ss_byte.hip — the BYTE tracker family on the device (docs/BYTETRACK.md): ByteTrack (xyah Kalman) and BoT-SORT without
+// GMC / ReID (xywh Kalman), S independent streams, a GROUP of F <= SS_FMAX frames per call.
+//
+//   k_byte_group  one workgroup (256 threads) per stream walks the group's frames in order inside the launch: score split,
+//                 Kalman predict of the pool, three IoU associations (fused high / plain low / unconfirmed) each solved by
+//                 the one-wave LSAP (SciPy's optimum of the raw matrix, then the threshold), births, lost-track expiry, the
+//                 list rebuild with duplicate removal, output rows.  One launch per call, no host round trip: capturable.
+//
+// The list logic lives in LDS (slot fields, list orders); means / covariances stay in global memory, one thread per track
+// for the f64 Kalman work.  tests/bytetrack_ref.py restates every step in the same order (rows are compared bit for bit).
+#include "ss_common.h"
+#include "ss_lsap.h"
+
+#define SS_BYTE_COST_CAP 2048          // LDS-resident cost entries (f64); a larger matrix lives in the stream's global spill area
+
+struct ByteLds {
+    // slot fields (copies of the global table for the duration of the launch)
+    int state[SS_MAXT], act[SS_MAXT], id[SS_MAXT], start[SS_MAXT], end[SS_MAXT], len[SS_MAXT], det[SS_MAXT];
+    float score[SS_MAXT], cls[SS_MAXT];
+    int trk[SS_MAXT], lost[SS_MAXT];   // the lists, in order
+    int upd[SS_MAXT];                  // per slot: detection to apply this frame (Kalman update) or -1
+    double tl[SS_MAXT][4];             // per slot: tlwh of the current mean (predicted / updated / initiated this frame)
+    // the frame's detections
+    double dtl[SS_MAXD][4], dz[SS_MAXD][4];
+    float dsc[SS_MAXD], dcls[SS_MAXD];
+    int hi[SS_MAXD], lo[SS_MAXD], left[SS_MAXD], hused[SS_MAXD], lused[SS_MAXD];
+    // work lists (pool / unconfirmed / second-stage rows by index)
+    int pool[SS_MAXT], unc[SS_MAXT], r2[SS_MAXT], asg[SS_MAXT], col4row[SS_MAXT], freel[SS_MAXT], born[SS_MAXT], flag[SS_MAXT];
+    int dupa[SS_MAXT], dupb[SS_MAXT];
+    double cost[SS_BYTE_COST_CAP];
+    int wtot[4];
+    int n_trk, n_lost, frame, next_id;
+};
+
+// the current mean's box as tlwh (ss_track's track box for xyah; centre / size for xywh)
+__device__ inline void byte_tlwh(const double* m, bool xywh, double* t)
+{
+    if (xywh) { t[0] = m[0] - m[2] / 2; t[1] = m[1] - m[3] / 2; t[2] = m[2]; t[3] = m[3]; }
+    else { const double w = m[2] * m[3]; t[0] = m[0] - w / 2; t[1] = m[1] - m[3] / 2; t[2] = w; t[3] = m[3]; }
+}
+
+// cost of (row r, column c) as stored for the LSAP: rows = the smaller side (transposed when there are fewer columns)
+__device__ inline size_t byte_cidx(int r, int c, int n_rows, int n_cols)
+{
+    return n_cols < n_rows ? (size_t)c * n_rows + r : (size_t)r * n_cols + c;
+}
+
+// LSAP of an n_rows x n_cols matrix already stored by byte_cidx -> m.asg[row] = column or -1 (all threads call it).
+__device__ inline void byte_assign(int n_rows, int n_cols, const double* cost, bool glb, ByteLds& m, int* err)
+{
+    const int tid = threadIdx.x;
+    m.asg[tid] = -1;
+    if (glb) __threadfence();                     // the spilled matrix is read back by wave 0
+    __syncthreads();
+    if (n_rows > 0 && n_cols > 0 && (tid >> 6) == 0) {
+        const bool tr = n_cols < n_rows;
+        const int nr = tr ? n_cols : n_rows, nc = tr ? n_rows : n_cols;
+        LsapLds L;
+        L.col4row = m.col4row;
+        const int rc = lsap_wave(nr, nc, cost, L);
+        if (rc) { if (tid == 0) *err = SS_ERR_INFEASIBLE; }
+        else for (int i = tid; i < nr; i += 64) { if (tr) m.asg[L.col4row[i]] = i; else m.asg[i] = L.col4row[i]; }
+    }
+    __syncthreads();
+}
+
+template <bool XYWH>
+__global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const float* __restrict__ dets, const int* __restrict__ ndets,
+                                                    float* __restrict__ out, int* __restrict__ nout)
+{
+    __shared__ ByteLds m;
+    const int s = blockIdx.x, tid = threadIdx.x, S = b.S;
+    const size_t sb = (size_t)s * SS_MAXT;
+    double* spill = b.spill + (size_t)s * SS_MAXT * SS_MAXD;
+    int* err = b.err + s;
+    // ---- the stream's table into LDS ----
+    m.state[tid] = b.state[sb + tid]; m.act[tid] = b.act[sb + tid]; m.id[tid] = b.tid[sb + tid]; m.start[tid] = b.start[sb + tid];
+    m.end[tid] = b.end[sb + tid]; m.len[tid] = b.len[sb + tid]; m.det[tid] = b.det[sb + tid]; m.score[tid] = b.score[sb + tid];
+    m.cls[tid] = b.cls[sb + tid]; m.trk[tid] = b.trk[sb + tid]; m.lost[tid] = b.lost[sb + tid];
+    if (tid == 0) { m.n_trk = b.n_trk[s]; m.n_lost = b.n_lost[s]; m.frame = b.frame[s]; m.next_id = b.next_id[s]; }
+    __syncthreads();
+
+    for (int f = 0; f < F; ++f) {
+        const size_t fs = (size_t)f * S + s;
+        const int nraw = ndets[fs];
+        const int N = min(max(nraw, 0), b.max_dets);
+        const int nT = m.n_trk, nL = m.n_lost, n_live = nT + nL;
+        const int fid = m.frame + 1;
+        if (tid == 0 && (nraw < 0 || nraw > b.max_dets)) *err = SS_ERR_CAPACITY;
+        // ---- 1. detections and the score split ----
+        int isHi = 0, isLo = 0;
+        if (tid < N) {
+            const float* d = dets + (fs * SS_MAXD + tid) * 6;
+            const double x1 = d[0], y1 = d[1], x2 = d[2], y2 = d[3];
+            const float sc = d[4];
+            double* t = m.dtl[tid];
+            double* z = m.dz[tid];
+            t[0] = x1; t[1] = y1; t[2] = x2 - x1; t[3] = y2 - y1;
+            z[0] = t[0] + t[2] / 2; z[1] = t[1] + t[3] / 2;
+            if (XYWH) { z[2] = t[2]; z[3] = t[3]; } else { z[2] = t[2] / t[3]; z[3] = t[3]; }
+            m.dsc[tid] = sc; m.dcls[tid] = d[5];
+            isHi = sc >= b.high;
+            isLo = sc > b.low && sc < b.high;
+        }
+        if (tid < SS_MAXD) { m.hused[tid] = 0; m.lused[tid] = 0; }
+        m.upd[tid] = -1; m.flag[tid] = 0; m.dupa[tid] = 0; m.dupb[tid] = 0;
+        int pos, nHi, nLo;
+        block_scan256(isHi, m.wtot, pos, nHi);
+        if (isHi) m.hi[pos] = tid;
+        block_scan256(isLo, m.wtot, pos, nLo);
+        if (isLo) m.lo[pos] = tid;
+        // ---- 2. unconfirmed tracks and the pool (activated tracked, then lost) ----
+        const int tslot = tid < nT ? m.trk[tid] : -1;
+        const int isU = tid < nT && !m.act[tslot], isP = tid < nT && m.act[tslot];
+        int nU, nPT;
+        block_scan256(isU, m.wtot, pos, nU);
+        if (isU) m.unc[pos] = tslot;
+        block_scan256(isP, m.wtot, pos, nPT);
+        if (isP) m.pool[pos] = tslot;
+        if (tid < nL) m.pool[nPT + tid] = m.lost[tid];
+        const int nP = nPT + nL;
+        __syncthreads();
+        // ---- 3. predict the pool (thread = pool index); the unconfirmed tracks keep their mean ----
+        if (tid < nP) {
+            const int slot = m.pool[tid];
+            double mean[8], cov[64];
+            const size_t g = sb + slot;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) mean[i] = b.mean[g * 8 + i];
+#pragma unroll
+            for (int i = 0; i < 64; ++i) cov[i] = b.cov[g * 64 + i];
+            if (m.state[slot] != SS_BYTE_TRACKED) { mean[7] = 0.0; if (XYWH) mean[6] = 0.0; }
+            if (XYWH) ss_kf_predict_xywh(mean, cov, b.wp, b.wv); else ss_kf_predict(mean, cov, b.wp, b.wv);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) b.mean[g * 8 + i] = mean[i];
+#pragma unroll
+            for (int i = 0; i < 64; ++i) b.cov[g * 64 + i] = cov[i];
+            byte_tlwh(mean, XYWH, m.tl[slot]);
+        }
+        if (tid < nU) {
+            const int slot = m.unc[tid];
+            double mean[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) mean[i] = b.mean[(sb + slot) * 8 + i];
+            byte_tlwh(mean, XYWH, m.tl[slot]);
+        }
+        __syncthreads();
+        // ---- 4. first association: pool x high rows, fused 1 - IoU, match_thresh ----
+        {
+            const bool glb = nP * nHi > SS_BYTE_COST_CAP;
+            double* cost = glb ? spill : m.cost;
+            for (int e = tid; e < nP * nHi; e += 256) {
+                const int r = e / nHi, k = e - r * nHi, d = m.hi[k];
+                double c = ss_iou_cost(m.tl[m.pool[r]], m.dtl[d], 2.0);
+                if (b.fuse) c = 1.0 - (1.0 - c) * (double)m.dsc[d];
+                cost[byte_cidx(r, k, nP, nHi)] = c;
+            }
+            byte_assign(nP, nHi, cost, glb, m, err);
+            if (tid < nP) {
+                const int k = m.asg[tid];
+                if (k >= 0 && cost[byte_cidx(tid, k, nP, nHi)] <= b.match) {
+                    const int slot = m.pool[tid], d = m.hi[k];
+                    m.hused[k] = 1;
+                    m.upd[slot] = d;
+                    if (m.state[slot] == SS_BYTE_TRACKED) m.len[slot] += 1;
+                    else { m.len[slot] = 0; m.flag[tid] = 1; }            // re-found (pool index tid)
+                }
+            }
+        }
+        __syncthreads();
+        // ---- 5. second association: unmatched Tracked pool tracks x low rows, plain 1 - IoU, 0.5 ----
+        int nR2;
+        {
+            const int isR = tid < nP && m.upd[m.pool[tid]] < 0 && m.state[m.pool[tid]] == SS_BYTE_TRACKED;
+            block_scan256(isR, m.wtot, pos, nR2);
+            if (isR) m.r2[pos] = m.pool[tid];
+            __syncthreads();
+            const bool glb = nR2 * nLo > SS_BYTE_COST_CAP;
+            double* cost = glb ? spill : m.cost;
+            for (int e = tid; e < nR2 * nLo; e += 256) {
+                const int r = e / nLo, k = e - r * nLo;
+                cost[byte_cidx(r, k, nR2, nLo)] = ss_iou_cost(m.tl[m.r2[r]], m.dtl[m.lo[k]], 2.0);
+            }
+            byte_assign(nR2, nLo, cost, glb, m, err);
+            if (tid < nR2) {
+                const int k = m.asg[tid], slot = m.r2[tid];
+                if (k >= 0 && cost[byte_cidx(tid, k, nR2, nLo)] <= 0.5) { m.upd[slot] = m.lo[k]; m.len[slot] += 1; }
+                else m.state[slot] = SS_BYTE_LOST;                       // new lost (r2 index tid)
+            }
+        }
+        __syncthreads();
+        // ---- 6. unconfirmed x the high rows left over, fused, 0.7 ----
+        int nLeft;
+        {
+            const int isL = tid < nHi && !m.hused[tid];
+            block_scan256(isL, m.wtot, pos, nLeft);
+            if (isL) m.left[pos] = m.hi[tid];
+            __syncthreads();
+            const bool glb = nU * nLeft > SS_BYTE_COST_CAP;
+            double* cost = glb ? spill : m.cost;
+            for (int e = tid; e < nU * nLeft; e += 256) {
+                const int r = e / nLeft, k = e - r * nLeft, d = m.left[k];
+                double c = ss_iou_cost(m.tl[m.unc[r]], m.dtl[d], 2.0);
+                if (b.fuse) c = 1.0 - (1.0 - c) * (double)m.dsc[d];
+                cost[byte_cidx(r, k, nU, nLeft)] = c;
+            }
+            byte_assign(nU, nLeft, cost, glb, m, err);
+            if (tid < nU) {
+                const int k = m.asg[tid], slot = m.unc[tid];
+                if (k >= 0 && cost[byte_cidx(tid, k, nU, nLeft)] <= 0.7) { m.upd[slot] = m.left[k]; m.len[slot] += 1; m.lused[k] = 1; }
+                else m.state[slot] = SS_BYTE_REMOVED;
+            }
+        }
+        __syncthreads();
+        // ---- 7. births: high rows still unmatched, ascending, score >= new_track_thresh, into the free slots ascending ----
+        int nB;
+        {
+            const int isB = tid < nLeft && !m.lused[tid] && m.dsc[m.left[tid]] >= b.new_thresh;
+            int rank, nCand, fpos, nFree;
+            // a slot is free when no list holds it (the lists at the frame's start)
+            m.asg[tid] = 0;
+            __syncthreads();
+            if (tid < nT) m.asg[m.trk[tid]] = 1;
+            if (tid < nL) m.asg[m.lost[tid]] = 1;
+            __syncthreads();
+            const int isF = !m.asg[tid];
+            block_scan256(isF, m.wtot, fpos, nFree);
+            if (isF) m.freel[fpos] = tid;
+            block_scan256(isB, m.wtot, rank, nCand);
+            const int allowed = max(0, b.max_tracks - n_live);
+            nB = min(nCand, allowed);
+            if (tid == 0 && nCand > allowed) *err = SS_ERR_CAPACITY;
+            __syncthreads();
+            if (isB && rank < nB) {
+                const int slot = m.freel[rank], d = m.left[tid];
+                double mean[8], cov[64];
+                if (XYWH) ss_kf_initiate_xywh(m.dz[d], b.wp, b.wv, mean, cov); else ss_kf_initiate(m.dz[d], b.wp, b.wv, mean, cov);
+                const size_t g = sb + slot;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) b.mean[g * 8 + i] = mean[i];
+                for (int i = 0; i < 64; ++i) b.cov[g * 64 + i] = cov[i];
+                byte_tlwh(mean, XYWH, m.tl[slot]);
+                m.id[slot] = m.next_id + rank;
+                m.len[slot] = 0; m.state[slot] = SS_BYTE_TRACKED; m.act[slot] = fid == 1;
+                m.start[slot] = fid; m.end[slot] = fid;
+                m.score[slot] = m.dsc[d]; m.cls[slot] = m.dcls[d]; m.det[slot] = d;
+                m.born[rank] = slot;
+            }
+        }
+        // ---- Kalman updates of this frame's matches (thread = slot): stages 4-6 ----
+        {
+            const int d = m.upd[tid];
+            if (d >= 0) {
+                const size_t g = sb + tid;
+                double mean[8], cov[64];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) mean[i] = b.mean[g * 8 + i];
+#pragma unroll
+                for (int i = 0; i < 64; ++i) cov[i] = b.cov[g * 64 + i];
+                if (XYWH) ss_kf_update_xywh(mean, cov, m.dz[d], b.wp); else ss_kf_update(mean, cov, m.dz[d], 0.0, b.wp);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) b.mean[g * 8 + i] = mean[i];
+#pragma unroll
+                for (int i = 0; i < 64; ++i) b.cov[g * 64 + i] = cov[i];
+                byte_tlwh(mean, XYWH, m.tl[tid]);
+                m.state[tid] = SS_BYTE_TRACKED; m.act[tid] = 1; m.end[tid] = fid;
+                m.score[tid] = m.dsc[d]; m.cls[tid] = m.dcls[d]; m.det[tid] = d;
+            }
+        }
+        __syncthreads();
+        // ---- 8. lost tracks past max_time_lost ----
+        if (tid < nL) {
+            const int slot = m.lost[tid];
+            if (m.state[slot] == SS_BYTE_LOST && fid - m.end[slot] > b.max_time_lost) m.state[slot] = SS_BYTE_REMOVED;
+        }
+        __syncthreads();
+        // ---- 9. the lists: tracked = old tracked still Tracked + births + re-found; lost = old lost still Lost + new lost ----
+        int nT2, nL2;
+        {
+            const int keepT = tid < nT && m.state[m.trk[tid]] == SS_BYTE_TRACKED;
+            const int refd = tid < nP && m.flag[tid];
+            const int keepL = tid < nL && m.state[m.lost[tid]] == SS_BYTE_LOST;
+            const int isNL = tid < nR2 && m.upd[m.r2[tid]] < 0;                // the second stage's unmatched rows (now Lost)
+            int p0, p1, p2, t0, t1, t2, p3, t3;
+            block_scan256(keepT, m.wtot, p0, t0);
+            block_scan256(refd, m.wtot, p1, t1);
+            block_scan256(keepL, m.wtot, p2, t2);
+            block_scan256(isNL, m.wtot, p3, t3);
+            const int vT = keepT ? m.trk[tid] : -1, vR = refd ? m.pool[tid] : -1, vL = keepL ? m.lost[tid] : -1, vN = isNL ? m.r2[tid] : -1;
+            __syncthreads();
+            if (keepT) m.trk[p0] = vT;
+            if (tid < nB) m.trk[t0 + tid] = m.born[tid];
+            if (refd) m.trk[t0 + nB + p1] = vR;
+            if (keepL) m.lost[p2] = vL;
+            if (isNL) m.lost[t2 + p3] = vN;
+            nT2 = t0 + nB + t1;
+            nL2 = t2 + t3;
+        }
+        __syncthreads();
+        // ---- duplicates between the lists: 1 - IoU < 0.15, the shorter-lived track goes (the tracked one on a tie) ----
+        for (int e = tid; e < nT2 * nL2; e += 256) {
+            const int p = e / nL2, q = e - p * nL2, a = m.trk[p], c = m.lost[q];
+            if (ss_iou_cost(m.tl[a], m.tl[c], 2.0) < 0.15) {
+                if (m.end[a] - m.start[a] > m.end[c] - m.start[c]) m.dupb[q] = 1;
+                else m.dupa[p] = 1;
+            }
+        }
+        __syncthreads();
+        {
+            const int kA = tid < nT2 && !m.dupa[tid], kB = tid < nL2 && !m.dupb[tid];
+            int pA, pB, tA, tB;
+            block_scan256(kA, m.wtot, pA, tA);
+            block_scan256(kB, m.wtot, pB, tB);
+            const int vA = tid < nT2 ? m.trk[tid] : -1, vB = tid < nL2 ? m.lost[tid] : -1;
+            __syncthreads();
+            if (tid < nT2 && !kA) m.state[vA] = SS_BYTE_REMOVED;
+            if (tid < nL2 && !kB) m.state[vB] = SS_BYTE_REMOVED;
+            if (kA) m.trk[pA] = vA;
+            if (kB) m.lost[pB] = vB;
+            nT2 = tA; nL2 = tB;
+        }
+        __syncthreads();
+        // ---- 10. one row per activated tracked track, in list order ----
+        {
+            const int slot = tid < nT2 ? m.trk[tid] : 0;
+            const int emit = tid < nT2 && m.act[slot];
+            int row, nRow;
+            block_scan256(emit, m.wtot, row, nRow);
+            if (emit) {
+                const double* t = m.tl[slot];
+                float* o = out + (fs * SS_MAXT + row) * 8;
+                o[0] = (float)t[0]; o[1] = (float)t[1]; o[2] = (float)(t[0] + t[2]); o[3] = (float)(t[1] + t[3]);
+                o[4] = (float)m.id[slot]; o[5] = m.cls[slot]; o[6] = m.score[slot]; o[7] = (float)m.det[slot];
+            }
+            if (tid == 0) {
+                nout[fs] = nRow;
+                m.n_trk = nT2; m.n_lost = nL2; m.frame = fid; m.next_id += nB;
+            }
+        }
+        __syncthreads();
+    }
+    // ---- the table back to global memory ----
+    b.state[sb + tid] = m.state[tid]; b.act[sb + tid] = m.act[tid]; b.tid[sb + tid] = m.id[tid]; b.start[sb + tid] = m.start[tid];
+    b.end[sb + tid] = m.end[tid]; b.len[sb + tid] = m.len[tid]; b.det[sb + tid] = m.det[tid]; b.score[sb + tid] = m.score[tid];
+    b.cls[sb + tid] = m.cls[tid]; b.trk[sb + tid] = m.trk[tid]; b.lost[sb + tid] = m.lost[tid];
+    if (tid == 0) { b.n_trk[s] = m.n_trk; b.n_lost[s] = m.n_lost; b.frame[s] = m.frame; b.next_id[s] = m.next_id; }
+}
+
+size_t ss_byte_lds_bytes() { return sizeof(ByteLds); }
+
+void ss_launch_byte_group(const SSByteDev& b, int F, const float* dets, const int* ndets, float* out, int* nout, hipStream_t st)
+{
+    if (b.xywh) hipLaunchKernelGGL(k_byte_group<true>, dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    else hipLaunchKernelGGL(k_byte_group<false>, dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+}

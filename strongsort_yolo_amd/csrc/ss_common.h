@@ -394,6 +394,141 @@ __device__ inline void ss_kf_predict_wave(const double* ws, double wp, double wv
     if (l < 8) pmean[l] = l < 4 ? mean[l] + mean[l + 4] : mean[l];
 }
 
+// BoT-SORT's xywh filter (the `botsort` variant of the BYTE tracker, docs/BYTETRACK.md B-03): the same constant-velocity model
+// with every noise term scaled by the box width (x, w rows) or height (y, h rows) and no NSA.  Same operation order as the xyah
+// forms above; tests/bytetrack_ref.py restates both line by line.
+__device__ inline void ss_kf_initiate_xywh(const double z[4], double wp, double wv, double* mean, double* cov)
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { mean[i] = z[i]; mean[4 + i] = 0.0; }
+    const double w = z[2], h = z[3];
+    const double sd[8] = { 2.0 * wp * w, 2.0 * wp * h, 2.0 * wp * w, 2.0 * wp * h,
+                           10.0 * wv * w, 10.0 * wv * h, 10.0 * wv * w, 10.0 * wv * h };
+    for (int i = 0; i < 64; ++i) cov[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) cov[i * 8 + i] = sd[i] * sd[i];
+}
+
+__device__ inline void ss_kf_predict_xywh(double* mean, double* cov, double wp, double wv)
+{
+    const double w = mean[2], h = mean[3];
+    const double sd[8] = { wp * w, wp * h, wp * w, wp * h, wv * w, wv * h, wv * w, wv * h };
+    double P[64];
+#pragma unroll
+    for (int i = 0; i < 64; ++i) P[i] = cov[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) P[i * 8 + j] = P[i * 8 + j] + P[i * 8 + j + 4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) P[i * 8 + j] = P[i * 8 + j] + P[(i + 4) * 8 + j];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) P[i * 8 + i] = P[i * 8 + i] + sd[i] * sd[i];
+#pragma unroll
+    for (int i = 0; i < 64; ++i) cov[i] = P[i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) mean[i] = mean[i] + mean[i + 4];
+}
+
+__device__ inline void ss_kf_project_xywh(const double* mean, const double* cov, double wp, double m4[4], double S[16])
+{
+    const double w = mean[2], h = mean[3];
+    const double sd[4] = { wp * w, wp * h, wp * w, wp * h };
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        m4[i] = mean[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) S[i * 4 + j] = cov[i * 8 + j];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) S[i * 4 + i] = S[i * 4 + i] + sd[i] * sd[i];
+}
+
+// the correction half of ss_kf_update (gain by Cholesky solves, mean and covariance) for a projection m4 / S made by the caller
+__device__ inline void ss_kf_correct(double* mean, double* cov, const double z[4], const double m4[4], const double S[16])
+{
+    double L[16], K[32], M[32], y[4];
+    ss_chol4(S, L);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        double w[4], x[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            double sum = cov[r * 8 + i];
+#pragma unroll
+            for (int k = 0; k < i; ++k) sum = fma(-L[i * 4 + k], w[k], sum);
+            w[i] = sum / L[i * 4 + i];
+        }
+#pragma unroll
+        for (int i = 3; i >= 0; --i) {
+            double sum = w[i];
+#pragma unroll
+            for (int k = 3; k > i; --k) sum = fma(-L[k * 4 + i], x[k], sum);
+            x[i] = sum / L[i * 4 + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) K[r * 4 + i] = x[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = z[i] - m4[i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc = fma(S[i * 4 + k], K[c * 4 + k], acc);
+            M[i * 8 + c] = acc;
+        }
+    double nm[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc = fma(y[k], K[r * 4 + k], acc);
+        nm[r] = mean[r] + acc;
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc = fma(K[r * 4 + k], M[k * 8 + c], acc);
+            cov[r * 8 + c] = cov[r * 8 + c] - acc;
+        }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) mean[r] = nm[r];
+}
+
+__device__ inline void ss_kf_update_xywh(double* mean, double* cov, const double z[4], double wp)
+{
+    double m4[4], S[16];
+    ss_kf_project_xywh(mean, cov, wp, m4, S);
+    ss_kf_correct(mean, cov, z, m4, S);
+}
+
+// Device state of the BYTE tracker family (csrc/ss_byte.hip), hung off a context by ss_byte_create.  Per stream: two ordered
+// lists of slots (tracked = activated and unconfirmed tracks, lost), per slot the track's fields; all pointers device memory.
+#define SS_BYTE_TRACKED 1
+#define SS_BYTE_LOST 2
+#define SS_BYTE_REMOVED 3
+struct SSByteDev {
+    int S;
+    int xywh, fuse, max_time_lost, max_tracks, max_dets;
+    float high, low, new_thresh;        // score thresholds, compared in float32 (B-04)
+    double match, wp, wv;
+    int *frame, *next_id, *err;         // [S]
+    int *n_trk, *n_lost;                // [S]
+    int *trk, *lost;                    // [S][MAXT] slots in list order
+    int *state, *act, *tid, *start, *end, *len, *det;    // [S][MAXT] by slot
+    float *score, *cls;                 // [S][MAXT]
+    double *mean, *cov;                 // [S][MAXT][8], [S][MAXT][64]
+    double* spill;                      // [S][MAXT * MAXD] cost matrices that do not fit the LDS
+};
+
 // camera-motion warp m (2x3, full-frame pixels) applied to a track's box (oracle so_camera_update, D-18)
 __device__ inline void ss_camera_update(double* mean, const double* m)
 {

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from .config import StrongSortConfig, DetectConfig
+from .config import StrongSortConfig, DetectConfig, ByteTrackConfig
 from .lib import MAX_TRACKS, MAX_DETS, FEAT_DIM, OUT_COLS
 
 
@@ -489,3 +489,74 @@ class TrackerEngine:
         self._ck(self.L.ss_crop_norm(self.ctx, _ptr(frame), H, W, frame.stride(0), _ptr(dets), dets.stride(0), n,
                                      _ptr(count), _ptr(out), int(half)))
         return out
+
+
+class ByteTrackEngine:
+    """The BYTE tracker family (csrc/ss_byte.hip, docs/BYTETRACK.md) on the context of a TrackerEngine: the same
+    update_device / update_group / reset / check_errors shape as TrackerEngine, without features.  `engine`: share the
+    context of an existing TrackerEngine (a pipeline's: its NMS, streams and error words); None: a context of its own."""
+
+    def __init__(self, cfg: ByteTrackConfig | None = None, n_streams: int = 1, device: int = 0, engine: TrackerEngine | None = None):
+        self.cfg = cfg or ByteTrackConfig()
+        self._own = engine is None
+        self.base = TrackerEngine(StrongSortConfig(), n_streams, device) if engine is None else engine
+        self.S, self.device, self.L = self.base.S, self.base.device, self.base.L
+        c = _lib.make_byte_config(self.cfg)
+        self._ck(self.L.ss_byte_create(self.base.ctx, C.byref(c)))
+        self.out = torch.zeros(self.S, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=self.device)
+        self.nout = torch.zeros(self.S, dtype=torch.int32, device=self.device)
+
+    @property
+    def ctx(self):
+        return self.base.ctx
+
+    def _ck(self, rc):
+        _lib.check(self.base.ctx, rc)
+
+    def close(self):
+        if self._own:
+            self.base.close()
+        elif getattr(self.base, "ctx", None) and self.base.ctx.value:
+            torch.cuda.synchronize(self.device)
+            self._ck(self.L.ss_byte_destroy(self.base.ctx))
+
+    def use_current_stream(self):
+        self.base.use_current_stream()
+
+    def reset(self, stream: int = -1):
+        self._ck(self.L.ss_byte_reset(self.base.ctx, stream))
+
+    def check_errors(self):
+        self.base.check_errors()
+
+    @property
+    def max_group_frames(self) -> int:
+        return int(self.L.ss_max_group_frames())
+
+    def update_device(self, dets, ndets, feats=None, img_hw=None, out=None, nout=None):
+        """All streams, one frame: dets [S,128,6] f32, ndets [S] i32 (device) -> (rows [S,256,8], counts [S]) device tensors,
+        asynchronous.  feats / img_hw are accepted for TrackerEngine's call shape and unused (no appearance, no clipping)."""
+        out = self.out if out is None else out
+        nout = self.nout if nout is None else nout
+        self._ck(self.L.ss_byte_update(self.base.ctx, _ptr(dets), _ptr(ndets), _ptr(out), _ptr(nout)))
+        return out, nout
+
+    def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout):
+        """A group of n_frames (<= 32) frames of all streams in ONE launch: dets [F,S,128,6] f32, ndets [F,S] i32 -> rows
+        out [F,S,256,8], counts nout [F,S] (device tensors, asynchronous); frames are associated in order.  feats / img_hw
+        unused (TrackerEngine's call shape)."""
+        self._ck(self.L.ss_byte_update_group(self.base.ctx, int(n_frames), _ptr(dets), _ptr(ndets), _ptr(out), _ptr(nout)))
+        return out, nout
+
+    def tracks(self, stream: int = 0) -> dict:
+        """The table of one stream in list order (tracked, then lost): track_id, state (1 tracked, 2 lost), activated, mean."""
+        T = MAX_TRACKS
+        nt, nl, nid, fr = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        ids, st, act = np.zeros(T, np.int32), np.zeros(T, np.int32), np.zeros(T, np.int32)
+        mean = np.zeros((T, 8))
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        self._ck(self.L.ss_byte_get_tracks(self.base.ctx, stream, T, C.byref(nt), C.byref(nl), C.byref(nid), C.byref(fr),
+                                           ids.ctypes.data_as(ip), st.ctypes.data_as(ip), act.ctypes.data_as(ip), mean.ctypes.data_as(dp)))
+        k = nt.value + nl.value
+        return dict(track_id=ids[:k].copy(), state=st[:k].copy(), activated=act[:k].copy(), mean=mean[:k].copy(),
+                    n_tracked=nt.value, n_lost=nl.value, next_id=nid.value, frame_id=fr.value)

@@ -27,6 +27,7 @@ EXPORTS = [
     "ss_get_gallery", "ss_max_group_frames", "ss_track_join", "ss_stream_create", "ss_stream_destroy", "ss_assoc_timing", "ss_assoc_timing_values", "ss_assoc_inkernel_timing", "ss_assoc_timeline", "ss_op_bias_act_f16", "ss_op_bias_act_place_f16", "ss_op_pointwise_f16", "ss_op_conv3x3_f16", "ss_op_bottleneck_f16", "ss_op_conv_group_f16", "ss_op_head_f16", "ss_op_v8_decode_f16", "ss_op_v8_decode_ext_f16", "ss_op_dwconv3x3_f16", "ss_op_lightconv_f16", "ss_op_osnet_stem_f16", "ss_op_conv0_f16", "ss_op_osnet_streams_f16", "ss_op_osnet_streams_bands", "ss_op_dwtab_bytes", "ss_op_dwtab_f16", "ss_op_gate_apply_f16", "ss_op_osnet_tail_f16", "ss_op_gate_sum_f16", "ss_op_avgpool2_f16", "ss_op_upcat_f16", "ss_op_sppf_pools_f16", "ss_op_psa_attention_f16", "ss_op_osnet_head_f16", "ss_op_maxpool_f16",
     "ss_op32_pointwise", "ss_op32_chains_bands", "ss_op32_chains", "ss_op32_tail", "ss_op32_stem", "ss_op32_stem_u8", "ss_op32_stem_conv1", "ss_op32_head", "ss_op32_set_option", "ss_op32_conv", "ss_op32_conv0", "ss_op32_upcat", "ss_op32_v8_decode", "ss_op32_sppf_pools",
     "ss_mask_assemble", "ss_mask_outline",
+    "ss_byte_create", "ss_byte_destroy", "ss_byte_update_group", "ss_byte_update", "ss_byte_reset", "ss_byte_get_tracks",
 ]
 
 
@@ -43,6 +44,15 @@ class ss_config(C.Structure):
         ("std_weight_position", C.c_double), ("std_weight_velocity", C.c_double),
         ("ema_alpha", C.c_double), ("max_age", C.c_int), ("n_init", C.c_int), ("nn_budget", C.c_int),
         ("n_streams", C.c_int), ("debug", C.c_int),
+    ]
+
+
+class ss_byte_config(C.Structure):              # mirrors `typedef struct ss_byte_config`
+    _fields_ = [
+        ("track_high_thresh", C.c_double), ("track_low_thresh", C.c_double), ("new_track_thresh", C.c_double),
+        ("match_thresh", C.c_double), ("std_weight_position", C.c_double), ("std_weight_velocity", C.c_double),
+        ("track_buffer", C.c_int), ("frame_rate", C.c_int), ("fuse_score", C.c_int), ("kalman_xywh", C.c_int),
+        ("max_tracks", C.c_int), ("max_dets", C.c_int),
     ]
 
 
@@ -175,6 +185,12 @@ def load():
     L.ss_op32_v8_decode.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), i, i, i, vp]
     L.ss_mask_assemble.argtypes = [vp, vp, vp, i, ll, i, i, i, fp, ll, i, i, ip, i, i, fp, ll, i, i, vp, ll]
     L.ss_mask_outline.argtypes = [vp, vp, vp, ll, ip, i, i, i, i, i, ip, ll, ip, ll, vp, ll, vp, ll]
+    L.ss_byte_create.argtypes = [vp, C.POINTER(ss_byte_config)]
+    L.ss_byte_destroy.argtypes = [vp]
+    L.ss_byte_update_group.argtypes = [vp, i, fp, ip, fp, ip]
+    L.ss_byte_update.argtypes = [vp, fp, ip, fp, ip]
+    L.ss_byte_reset.argtypes = [vp, i]
+    L.ss_byte_get_tracks.argtypes = [vp, i, i, hi, hi, hi, hi, hi, hi, hi, hd]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("ss_destroy", "ss_last_error"):
@@ -193,3 +209,9 @@ def make_config(cfg, n_streams=1, debug=False) -> ss_config:
     return ss_config(cfg.max_dist, cfg.max_iou_distance, cfg.mc_lambda, cfg.gating_threshold, cfg.gated_cost,
                      cfg.std_weight_position, cfg.std_weight_velocity, cfg.ema_alpha, cfg.max_age, cfg.n_init,
                      cfg.nn_budget, n_streams, int(debug))
+
+
+def make_byte_config(cfg) -> ss_byte_config:
+    return ss_byte_config(cfg.track_high_thresh, cfg.track_low_thresh, cfg.new_track_thresh, cfg.match_thresh,
+                          cfg.std_weight_position, cfg.std_weight_velocity, cfg.track_buffer, cfg.frame_rate, int(cfg.fuse_score),
+                          int(cfg.kalman == "xywh"), cfg.max_tracks, cfg.max_dets)

@@ -39,10 +39,21 @@ class FramePipeline:
                  half: bool = True, reid_batch: int = 32, cfg: Optional[StrongSortConfig] = None,
                  dcfg: Optional[DetectConfig] = None, det_source: str = "detector", feat_source: str = "reid",
                  graph: str = "all", debug: bool = False, run_nets: bool = True, seed: int = 0, detect_only_rows: int = 0, cmc: bool = False,
-                 reid_half: Optional[bool] = None, crops_u8: bool = True):
+                 reid_half: Optional[bool] = None, crops_u8: bool = True, tracker: str = "strongsort"):
         self.cfg, self.dcfg = cfg or StrongSortConfig(), dcfg or DetectConfig()
         self.S, (self.H, self.W) = n_streams, frame_hw
+        # tracker = "bytetrack" / "botsort": the BYTE tracker family (csrc/ss_byte.hip) on IoU and scores — no OSNet is built, no
+        # crops are cut, the ReID stages drop out of the graphs; the tracker keeps the NMS rows' order (det_idx)
+        from .config import byte_config
+        self.byte_cfg = byte_config(tracker)
+        self.tracker = tracker
+        if self.byte_cfg is not None and cmc:
+            raise ValueError("camera-motion compensation is a StrongSORT option (BoT-SORT's GMC is not implemented)")
         self.eng = TrackerEngine(self.cfg, n_streams, device, debug=debug)
+        self.byte = None
+        if self.byte_cfg is not None:
+            from .engine import ByteTrackEngine
+            self.byte = ByteTrackEngine(self.byte_cfg, engine=self.eng)
         dev = self.dev = self.eng.device
         self.half, self.dtype = half, torch.float16 if half else torch.float32
         # reid_half=False: the ReID crops and OSNet in fp32 on the hand-written fp32 kernels (fused32.py, csrc/ss_ops32.hip:
@@ -61,7 +72,7 @@ class FramePipeline:
             raise ValueError("reid_batch <= 128")
         # Only the first reid_batch detections of a frame are cropped and embedded: with OSNet features feeding the
         # tracker, NMS keeps at most that many (highest scores first), so no detection reaches it without a feature.
-        self.max_det = min(self.dcfg.max_det, MAX_DETS, reid_batch if (feat_source == "reid" and run_nets) else MAX_DETS)
+        self.max_det = min(self.dcfg.max_det, MAX_DETS, reid_batch if (feat_source == "reid" and run_nets and self.byte is None) else MAX_DETS)
         # detect_only_rows > 0: a detection-only pipeline (model.predict, yolo_multi_model.py:173) whose NMS keeps up to
         # that many rows (<= 1024, the reference's max_det is 1000) — it never feeds the tracker (128 detections per frame)
         self.det_rows = MAX_DETS
@@ -73,7 +84,8 @@ class FramePipeline:
         self.detector = self.reid = None
         if run_nets:
             self.detector = nets.build_detector(detector, seed).to(dev, self.dtype).to(memory_format=torch.channels_last)
-            self.reid = nets.build_reid(seed + 1).to(dev, self.reid_dtype).to(memory_format=torch.channels_last)
+            if self.byte is None:
+                self.reid = nets.build_reid(seed + 1).to(dev, self.reid_dtype).to(memory_format=torch.channels_last)
             self.nc, self.nk = self.detector.nc, self.detector.nk
             self.nm = getattr(self.detector, "nm", 0)           # mask coefficients of a segmentation head (after the keypoints' place)
         else:
@@ -93,7 +105,8 @@ class FramePipeline:
         self.proto = torch.zeros(S, self.nm, g.out_h // 4, g.out_w // 4, dtype=self.dtype, device=dev) if self.nm else None
         self.keep = torch.zeros(S, self.det_rows, dtype=torch.int32, device=dev)
         self.ndets = torch.zeros(S, dtype=torch.int32, device=dev)
-        self.crops = torch.zeros(S * self.RB, 3, 256, 128, dtype=self.crops_dtype, device=dev).contiguous(memory_format=torch.channels_last)
+        self.crops = torch.zeros(S * self.RB if self.byte is None else 0, 3, 256, 128, dtype=self.crops_dtype,
+                                 device=dev).contiguous(memory_format=torch.channels_last)
         self.feats_in = torch.zeros(S, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=dev)
         self.img_hw = torch.tensor([[self.H, self.W]] * S, dtype=torch.int32, device=dev)
         self.out, self.nout = self.eng.out, self.eng.nout
@@ -144,6 +157,8 @@ class FramePipeline:
 
     def _reid_impl(self):
         e, S = self.eng, self.S
+        if self.byte is not None:
+            return
         if self.run_nets:
             e.crop_norm_batch(self.frames, self.dets6, self.RB, counts=self.ndets, half=self.reid_half, out=self.crops,
                               channels_last=True)
@@ -159,7 +174,16 @@ class FramePipeline:
         self._reid_impl()
 
     def _track(self):
+        if self.byte is not None:
+            self.byte.update_device(self.dets6, self.ndets, out=self.out, nout=self.nout)
+            return
         self.eng.update_device(self.dets6, self.ndets, self.feats_in, self.img_hw)
+
+    def reset_tracker(self, stream: int = -1):
+        """Restart the tracker of one stream (all: -1), whichever family runs."""
+        self.eng.reset(stream)
+        if self.byte is not None:
+            self.byte.reset(stream)
 
     @torch.no_grad()
     def step(self, track: bool = True):
@@ -205,7 +229,7 @@ class FramePipeline:
                     # three graphs on the same static buffers: detection | ReID | tracker, so a detection-only call
                     # (model.predict, yolo_multi_model.py:173) replays just the first
                     self.graph = []
-                    for fn in (self._detect_impl, self._reid_impl, self._track):
+                    for fn in ((self._detect_impl, self._track) if self.byte is not None else (self._detect_impl, self._reid_impl, self._track)):
                         gph = torch.cuda.CUDAGraph()
                         with torch.cuda.graph(gph, stream=st):
                             fn()
@@ -236,7 +260,7 @@ class FramePipeline:
     # the warm-up iterations must not advance the tracker: reset it (callers start streams fresh)
     def _restore_tracker(self):
         torch.cuda.synchronize(self.dev)
-        self.eng.reset(-1)
+        self.reset_tracker(-1)
 
     # ---- convenience ----------------------------------------------------------------------------------
     def results(self):
@@ -278,7 +302,8 @@ class _Bufs:
         self.proto = torch.zeros(S, p.nm, p.geom.out_h // 4, p.geom.out_w // 4, dtype=p.dtype, device=dev) if p.nm else None
         self.keep = torch.zeros(S, MAX_DETS, dtype=torch.int32, device=dev)
         self.ndets = torch.zeros(S, dtype=torch.int32, device=dev)
-        self.crops = torch.zeros(S * p.RB, 3, 256, 128, dtype=p.crops_dtype, device=dev).contiguous(memory_format=torch.channels_last)
+        self.crops = torch.zeros(S * p.RB if p.byte is None else 0, 3, 256, 128, dtype=p.crops_dtype,
+                                 device=dev).contiguous(memory_format=torch.channels_last)
         self.anchor_gt = torch.zeros(S, p.n_anchors, dtype=torch.int64, device=dev)
         self.gt_feats = torch.zeros(S, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=dev)
         self.feats_v = torch.zeros(S, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=dev)    # what the tracker reads
@@ -331,12 +356,14 @@ class OverlappedPipeline(FramePipeline):
         self.Sv = self.S * self.F
         # packed ReID batches: the group's valid crops contiguous, the OSNet kernels skip the unused slots of the fixed batch
         # (~28 of 32 slots per frame are used at configs[1]); pack_crops=False: A/B switch
-        self.pack = bool(self.run_nets and pack_crops)
+        self.pack = bool(self.run_nets and pack_crops and self.byte is None)
+        if self.byte is not None:                # BYTE: no ReID stage to cut or balance, no association launch to gate on
+            reid_split, assoc_gate = None, False
         self.geom_dev = self.geom_dev[:1].repeat(self.Sv, 1).contiguous()
         self.outs = torch.zeros(self.F, self.S, MAX_TRACKS, 8, dtype=torch.float32, device=self.dev)
         self.nouts = torch.zeros(self.F, self.S, dtype=torch.int32, device=self.dev)
         split_det = self.run_nets and n_stages >= 4 and hasattr(self.detector, "forward_backbone")
-        split_reid = self.run_nets and n_stages >= 4 and hasattr(self.reid, "forward_a")
+        split_reid = self.run_nets and n_stages >= 4 and self.reid is not None and hasattr(self.reid, "forward_a")
         # two stages can also be cut INSIDE the ReID network to balance them: stage 0 = letterbox, detector, NMS,
         # crops and OSNet parts [0, reid_split); stage 1 = the remaining parts, feature select and the tracker
         self.reid_split = None
@@ -474,7 +501,7 @@ class OverlappedPipeline(FramePipeline):
                     count=b.ndets, max_det=self.max_det)
         if self.nx:
             b.dets6.copy_(b.dets[:, :, :6])
-        if self.run_nets:
+        if self.run_nets and self.reid is not None:
             if self.pack:        # the group's valid crops contiguous; the ReID kernels skip the rest of the fixed-size batch
                 e.crop_norm_packed(b.frames, b.dets6, self.RB, b.ndets, b.crop_off, b.crops, half=self.reid_half)
             else:
@@ -513,7 +540,7 @@ class OverlappedPipeline(FramePipeline):
     def _s_nms_crop_reid_select(self, b):
         self._nms_crop(b)
         emb = None
-        if self.run_nets:
+        if self.run_nets and self.reid is not None:
             with self._valid(b):
                 emb = self.reid(b.crops)
         self._select(b, emb)
@@ -538,7 +565,7 @@ class OverlappedPipeline(FramePipeline):
         """Tracker update of the group's frames in ONE call: the library associates them strictly in order (frame f =
         virtual streams f*S..) and reads the galleries once for all of them; `group` = index of the group's first
         frame (None while warming up / capturing: no callbacks)."""
-        e = self.eng
+        e = self.eng if self.byte is None else self.byte
         nv = self.F if n_valid is None else n_valid
         G, S = self.eng.max_group_frames, self.S             # frames per library call (SS_FMAX)
         if self.sR is not None and self._res_ev is not None:
@@ -549,7 +576,7 @@ class OverlappedPipeline(FramePipeline):
                 e.set_cmc(b.warps[f0:f0 + n])
             e.update_group(n, b.dets6[v0:v1], b.ndets[v0:v1], b.feats_v[v0:v1], self.img_hw, self.outs[f0:f0 + n], self.nouts[f0:f0 + n])
         if self.sR is not None:                                 # detached chain: the rows exist once the chain's stream is done
-            e.track_join(self.sR)
+            self.eng.track_join(self.sR)
         if group is not None and self.on_result is not None:
             self.cur_bufs, self.cur_valid = b, nv               # the buffer set / real-frame count the callbacks below refer to
             with torch.cuda.stream(self.sR if self.sR is not None else torch.cuda.current_stream(self.dev)):
@@ -587,7 +614,7 @@ class OverlappedPipeline(FramePipeline):
                     self.graphs[j][i] = g
         torch.cuda.synchronize(self.dev)
         self._ss_stream(self.sB)                                 # the tracker lives on the last stage's stream
-        self.eng.reset(-1)
+        self.reset_tracker(-1)
         self._captured = True
 
     # ---- driver API --------------------------------------------------------------------------------------

@@ -13,8 +13,8 @@ import numpy as np
 import torch
 
 from . import nets
-from .config import StrongSortConfig
-from .engine import TrackerEngine
+from .config import StrongSortConfig, ByteTrackConfig
+from .engine import TrackerEngine, ByteTrackEngine
 from .lib import MAX_DETS, FEAT_DIM
 
 
@@ -61,6 +61,40 @@ class StrongSORT:
             crops = self.eng.crop_norm(frame_t, self._dets[0], n, half=self.dtype == torch.float16)
             self._feats[0, :n].copy_(self.reid(crops.contiguous(memory_format=torch.channels_last)))
         out, nout = self.eng.update_device(self._dets, self._n, self._feats, self._hw)
+        torch.cuda.synchronize(self.dev)
+        self.eng.check_errors()
+        return out[0, : int(nout[0])].cpu().numpy()
+
+    def reset(self):
+        self.eng.reset(-1)
+
+    def close(self):
+        self.eng.close()
+
+
+class BYTETracker:
+    """The BYTE tracker family for one video stream (docs/BYTETRACK.md): `update(dets)` needs no frame and no ReID weights.
+         dets  [N,6] float  x1,y1,x2,y2,conf,cls in frame pixels (numpy or torch), N <= 128
+       returns float32 [M,8]: x1,y1,x2,y2,track_id,class_id,conf,det_idx for every activated tracked track (det_idx = row of
+       `dets` matched this frame, always >= 0).  cfg.kalman = "xyah": ByteTrack; "xywh": BoT-SORT without GMC / ReID."""
+
+    def __init__(self, cfg: Optional[ByteTrackConfig] = None, device: int = 0):
+        self.cfg = cfg or ByteTrackConfig()
+        self.eng = ByteTrackEngine(self.cfg, 1, device)
+        self.dev = self.eng.device
+        self._dets = torch.zeros(1, MAX_DETS, 6, dtype=torch.float32, device=self.dev)
+        self._n = torch.zeros(1, dtype=torch.int32, device=self.dev)
+
+    @torch.no_grad()
+    def update(self, dets) -> np.ndarray:
+        self.eng.use_current_stream()
+        dets = torch.as_tensor(dets, dtype=torch.float32).reshape(-1, 6)
+        n = dets.shape[0]
+        if n > self.cfg.max_dets:
+            raise ValueError(f"at most {self.cfg.max_dets} detections per frame (got {n})")
+        self._dets[0, :n].copy_(dets, non_blocking=True)
+        self._n.fill_(n)
+        out, nout = self.eng.update_device(self._dets, self._n)
         torch.cuda.synchronize(self.dev)
         self.eng.check_errors()
         return out[0, : int(nout[0])].cpu().numpy()

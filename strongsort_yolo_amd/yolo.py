@@ -18,7 +18,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .config import DetectConfig, StrongSortConfig
+from .config import DetectConfig, StrongSortConfig, byte_config
 
 COCO_NAMES = ("person bicycle car motorcycle airplane bus train truck boat traffic_light fire_hydrant stop_sign "
               "parking_meter bench bird cat dog horse sheep cow elephant bear zebra giraffe backpack umbrella handbag tie "
@@ -237,14 +237,24 @@ class YOLO:
 
     def __init__(self, weights: str = "yolov8n.pt", seed: int = 0, random_init_ok: bool = False, reid_batch: int = 128,
                  camera_motion: bool = False, reid_weights: Optional[str] = None, reid_fp32: bool = True, half: bool = True,
-                 device_masks: bool = False):
+                 device_masks: bool = False, tracker_type: str = "strongsort"):
         """reid_fp32 (default since round 6): ReID crops + OSNet-x0.25 in fp32 on the fp32 kernels — appearance distances within 1e-4 of a CPU fp32
         network, which f16 activations miss by 330x (reid_fp32=False: the f16 throughput mode, ~1.2x the per-frame rate, 1.7x the stream rate).
         half=False: the DETECTOR in fp32 as well (the reference's own precision: it passes no half=, yolo_multi_model.py:41) on the
         fp32 convolution kernels (csrc/ss_ops32.hip k32_conv) — NMS keep lists then equal the CPU fp32 network's; implies reid_fp32.
         device_masks (segmentation models): every call also assembles the kept rows' masks and traces their polygons on the device
         (csrc/ss_mask.hip) and downloads bits and points instead of the prototypes; `Results.masks` then needs no host arithmetic
-        beyond unpacking and scale_coords.  Default False: masks are built on the host when first read (assemble_masks / mask_polygon)."""
+        beyond unpacking and scale_coords.  Default False: masks are built on the host when first read (assemble_masks / mask_polygon).
+        tracker_type: "strongsort" (default: OSNet appearance + NSA Kalman), or the BYTE family on the device (docs/BYTETRACK.md) —
+        "bytetrack" (xyah Kalman) / "botsort" (xywh Kalman, no GMC, no ReID): IoU and scores only, no ReID network or weights;
+        track() then runs NMS at conf 0.1 unless track(conf=...) says otherwise (Ultralytics' Model.track), predict() keeps
+        overrides['conf']."""
+        byte_config(tracker_type)                 # ValueError on anything else
+        self.tracker_type = tracker_type
+        self._byte = tracker_type != "strongsort"
+        if self._byte and camera_motion:
+            raise ValueError("camera_motion is a StrongSORT option (BoT-SORT's GMC is not implemented)")
+        self._conf_track = None                   # BYTE: the NMS threshold of the tracking pipelines (set while track / track_stream build)
         self.weights = weights
         self.reid_weights = reid_weights          # OSNet-x0.25 state_dict; same policy as the detector's (raise unless random init is asked for)
         self.random_init_ok = random_init_ok
@@ -267,13 +277,16 @@ class YOLO:
             self._pipe_kw["reid_half"] = False
         if not half:
             self._pipe_kw["half"] = False
+        if self._byte:
+            self._pipe_kw["tracker"] = tracker_type
         self.device_masks = bool(device_masks)
         self._fill = None
         self._frame_index = 0
 
     def _dcfg(self):
         o = self.overrides
-        return DetectConfig(conf=float(o["conf"]), iou=float(o["iou"]), agnostic_nms=bool(o["agnostic_nms"]),
+        conf = o["conf"] if self._conf_track is None else self._conf_track
+        return DetectConfig(conf=float(conf), iou=float(o["iou"]), agnostic_nms=bool(o["agnostic_nms"]),
                             max_det=int(o["max_det"]))
 
     def _state_key(self, shape, device):
@@ -292,8 +305,8 @@ class YOLO:
         # The ReID weights are needed only once the TRACKER consumes OSNet embeddings: model.predict (yolo_multi_model.py:173)
         # works with detector weights alone; the first model.track on such a pipeline rebuilds it with the ReID weights.
         nets.load_weights(pipe.detector, self.weights, f"detector {self.arch}", self.random_init_ok)
-        pipe.reid_loaded = False
-        if need_reid and pipe.feat_source == "reid" and pipe.det_rows == 128:
+        pipe.reid_loaded = pipe.reid is None and pipe.det_rows == 128        # BYTE: nothing to load, the pipeline tracks as built
+        if need_reid and pipe.reid is not None and pipe.feat_source == "reid" and pipe.det_rows == 128:
             nets.load_weights(pipe.reid, self.reid_weights, "OSNet-x0.25 ReID", self.random_init_ok)
             pipe.reid_loaded = True
         pipe.eng.nms_set_classes(self.overrides.get("classes"))
@@ -322,7 +335,9 @@ class YOLO:
         return self._pipe
 
     def _run(self, image, device, track):
-        if not track and int(self.overrides["max_det"]) > 128:
+        # BYTE models: predict() has a detection-only pipeline of its own (its NMS threshold is overrides['conf'], the tracking
+        # pipeline's is track's), so that predict calls between track calls do not restart the tracker
+        if not track and (int(self.overrides["max_det"]) > 128 or self._byte):
             return self._run_predict_wide(image, device)
         pipe = self._pipeline(image, device, need_reid=track)
         pipe.eng.upload(pipe.frames[0], image)
@@ -449,12 +464,20 @@ class YOLO:
     TRACKERS = ("strongsort.yaml", "strongsort", "botsort.yaml", "bytetrack.yaml")
 
     def _check_tracker(self, tracker):
-        """`tracker=`: this library has ONE tracker, StrongSORT (BASELINE north_star).  The reference passes "botsort.yaml"
-        (yolo_multi_model.py:41) — the Ultralytics tracker configurations are accepted and answered by StrongSORT, once with a
-        warning that says so; any other value is an error instead of being ignored."""
+        """`tracker=`: the tracker is chosen when the model is built (`tracker_type`), StrongSORT by default (BASELINE north_star).
+        The reference passes "botsort.yaml" (yolo_multi_model.py:41) — the Ultralytics tracker configurations are accepted and
+        answered by the model's tracker, once with a warning that says so; any other value is an error instead of being ignored."""
         name = os.path.basename(str(tracker))
         if name not in self.TRACKERS:
             raise ValueError(f"tracker={tracker!r}: this library tracks with StrongSORT only (accepted: {', '.join(self.TRACKERS)})")
+        if self._byte:
+            family = name.split(".")[0]
+            if family != self.tracker_type and not getattr(self, "_tracker_warned", False):
+                import warnings
+                self._tracker_warned = True
+                warnings.warn(f"tracker={tracker!r}: this model was built with tracker_type={self.tracker_type!r}, which rules; "
+                              f"its parameters are strongsort_yolo_amd.config.ByteTrackConfig", RuntimeWarning, stacklevel=3)
+            return
         if not name.startswith("strongsort") and not getattr(self, "_tracker_warned", False):
             import warnings
             self._tracker_warned = True
@@ -465,7 +488,13 @@ class YOLO:
     def track(self, image, verbose=False, device=0, persist=True, tracker="strongsort.yaml", **kw) -> List[Results]:
         self._check_tracker(tracker)
         if not persist and self._pipe is not None:
-            self._pipe.eng.reset(-1)
+            self._pipe.reset_tracker(-1)
+        if self._byte:                            # Ultralytics' Model.track: conf = kwargs.get("conf") or 0.1
+            self._conf_track = float(kw.get("conf") or 0.1)
+            try:
+                return self._run(image, device, True)
+            finally:
+                self._conf_track = None
         return self._run(image, device, True)
 
     @torch.no_grad()
@@ -476,25 +505,30 @@ class YOLO:
 
     # ---- throughput path ------------------------------------------------------------------------------------
     @torch.no_grad()
-    def track_stream(self, frames, batch: int = 16, device=0, keep_device_frames: bool = False):
+    def track_stream(self, frames, batch: int = 16, device=0, keep_device_frames: bool = False, conf: Optional[float] = None):
         """Generator over `frames` (BGR uint8 arrays of one size): yields the same [Results] `track(frame)` would, in
         order, `batch` frames at a time through the overlapped two-stream pipeline (stateless stages of group k+1 run
         while the tracker consumes group k; the tracker reads its galleries once per group).
         keep_device_frames: every Results also carries `orig_img_device`, the frame as a device tensor (a device-to-device copy
         of the group's input buffer taken on the tracker's stream), so that an annotated output needs no second upload
-        (`Overlay.draw_resident`); valid until the generator has yielded `ring` more groups."""
+        (`Overlay.draw_resident`); valid until the generator has yielded `ring` more groups.
+        conf (BYTE models): the NMS threshold, as track(conf=...) (default 0.1)."""
         from .pipeline import OverlappedPipeline
         it = iter(frames)
         first = next(it, None)
         if first is None:
             return
-        key = self._state_key(first.shape[:2], device) + (batch,)
-        if self._stream_pipe is None or key != self._stream_key:
-            if self._stream_pipe is not None:
-                self._stream_pipe.close()
-            self._stream_pipe = self._build(OverlappedPipeline, first.shape[:2], device, graph="front", frame_batch=batch,
-                                            reid_split=(5 if self.arch == "yolov8n" else 2) if batch > 1 else None, defer_track=batch > 1)     # stage cut: bench.REID_SPLIT's sweep
-            self._stream_key = key
+        self._conf_track = float(conf or 0.1) if self._byte else None
+        try:
+            key = self._state_key(first.shape[:2], device) + (batch,)
+            if self._stream_pipe is None or key != self._stream_key:
+                if self._stream_pipe is not None:
+                    self._stream_pipe.close()
+                self._stream_pipe = self._build(OverlappedPipeline, first.shape[:2], device, graph="front", frame_batch=batch,
+                                                reid_split=(5 if self.arch == "yolov8n" else 2) if batch > 1 else None, defer_track=batch > 1)     # stage cut: bench.REID_SPLIT's sweep
+                self._stream_key = key
+        finally:
+            self._conf_track = None
         pipe = self._stream_pipe
         pipe.on_result = None
         pipe.flush()                                                      # groups an abandoned generator left in flight: tracked, results dropped
