@@ -205,7 +205,7 @@ int ss_track_update_group(ss_ctx* ctx, int n_frames, const float* d_dets, const 
 int ss_track_update(ss_ctx* ctx, const float* d_dets, const int* d_ndets, const float* d_feats,
                     const int* d_img_hw, float* d_out, int* d_nout);
 
-/* ---- BYTE tracker family (docs/BYTETRACK.md): ByteTrack (xyah Kalman) and BoT-SORT without GMC / ReID (xywh Kalman) ------
+/* ---- BYTE tracker family (docs/BYTETRACK.md): ByteTrack (xyah Kalman) and BoT-SORT without ReID (xywh Kalman, optional GMC) -
  * Opt-in, IoU-only association on detection scores (no ReID features).  The state is hung off an existing context (its streams,
  * its HIP stream, its error words); ss_byte_create on a context that already has one replaces it. */
 typedef struct ss_byte_config {
@@ -232,7 +232,13 @@ int ss_byte_destroy(ss_ctx* ctx);
  * (set until ss_byte_reset). */
 int ss_byte_update_group(ss_ctx* ctx, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
 int ss_byte_update(ss_ctx* ctx, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
-int ss_byte_reset(ss_ctx* ctx, int stream);                /* stream < 0: all streams; ids restart at 1, frame_id at 1 */
+int ss_byte_reset(ss_ctx* ctx, int stream);                /* stream < 0: all streams; ids restart at 1, frame_id at 1; the
+                                                              stream's previous ss_cmc_estimate frame is forgotten (no warp next) */
+/* BoT-SORT GMC (docs/BYTETRACK.md §1b): the following ss_byte_update(_group) calls move every track's Kalman mean and covariance
+ * by d_warps[f][s][8] (ss_cmc_estimate's layout; [6] < 0: no warp) after predicting frame f.  The caller keeps at least
+ * n_frames rows alive; the pointer is read at launch (capturable).  NULL switches it off (the default).  SS_ERR_INVALID without
+ * BYTE state or on an xyah (ByteTrack) state. */
+int ss_byte_set_gmc(ss_ctx* ctx, const double* d_warps);
 /* Synchronous: the table of one stream in list order (tracked list, then lost list); any array may be NULL.
  * state 1 tracked, 2 lost; mean [n][8] (xyah or xywh state). */
 int ss_byte_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracked, int* n_lost, int* next_id, int* frame_id,

@@ -1097,6 +1097,7 @@ extern "C" int ss_byte_reset(ss_ctx* c, int stream)
     HIPCHK(c, hipMemsetAsync(b.n_trk + s0, 0, (s1 - s0) * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(b.n_lost + s0, 0, (s1 - s0) * 4, c->stream));
     HIPCHK(c, hipMemcpyAsync(b.next_id + s0, ones.data(), (s1 - s0) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->cmc_prev_valid + s0, 0, (s1 - s0) * 4, c->stream));     // G-04: the next frame gets no warp
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SS_OK;
 }
@@ -1147,6 +1148,16 @@ extern "C" int ss_byte_update_group(ss_ctx* c, int n_frames, const float* d_dets
     if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: 1 <= n_frames <= SS_FMAX");
     ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, d_out, d_nout, c->stream);
     HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+// BoT-SORT GMC (docs/BYTETRACK.md §1b): the following update calls read d_warps[f][s][8] (ss_cmc_estimate's layout) for frame f;
+// the pointer goes into the launch arguments, so the call is capturable.  NULL: off.  xyah (ByteTrack) has no GMC (G-05).
+extern "C" int ss_byte_set_gmc(ss_ctx* c, const double* d_warps)
+{
+    if (!c || !c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_set_gmc: no BYTE state (ss_byte_create)");
+    if (d_warps && !c->byte->dev.xywh) return fail(c, SS_ERR_INVALID, "ss_byte_set_gmc: GMC needs the xywh (BoT-SORT) state");
+    c->byte->dev.gmc = d_warps;
     return SS_OK;
 }
 

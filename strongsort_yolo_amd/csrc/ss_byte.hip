@@ -1,8 +1,9 @@
 // ss_byte.hip — the BYTE tracker family on the device (docs/BYTETRACK.md): ByteTrack (xyah Kalman) and BoT-SORT without
-// GMC / ReID (xywh Kalman), S independent streams, a GROUP of F <= SS_FMAX frames per call.
+// ReID (xywh Kalman, optional GMC), S independent streams, a GROUP of F <= SS_FMAX frames per call.
 //
 //   k_byte_group  one workgroup (256 threads) per stream walks the group's frames in order inside the launch: score split,
-//                 Kalman predict of the pool, three IoU associations (fused high / plain low / unconfirmed) each solved by
+//                 Kalman predict of the pool, BoT-SORT's GMC (§1b, the GMC variant only: the warps of ss_cmc_estimate
+//                 applied to the predicted pool and the unconfirmed tracks), three IoU associations (fused high / plain low / unconfirmed) each solved by
 //                 the one-wave LSAP (SciPy's optimum of the raw matrix, then the threshold), births, lost-track expiry, the
 //                 list rebuild with duplicate removal, output rows.  One launch per call, no host round trip: capturable.
 //
@@ -39,6 +40,38 @@ __device__ inline void byte_tlwh(const double* m, bool xywh, double* t)
     else { const double w = m[2] * m[3]; t[0] = m[0] - w / 2; t[1] = m[1] - m[3] / 2; t[2] = w; t[3] = m[3]; }
 }
 
+// step 3b (docs/BYTETRACK.md §1b, G-02): Ultralytics' STrack.multi_gmc with warp w (R = [[w0, w1], [w3, w4]], t = (w2, w5)):
+// mean <- R8 mean + (t, 0, ...), cov <- R8 cov R8^T, R8 = kron(I4, R) as 2x2 blocks.  Every entry is two products and one add
+// (the library is built with -ffp-contract=off); tests/botsort_gmc_ref.py restates this order.
+__device__ inline void byte_gmc(double* mean, double* cov, const double* w)
+{
+    const double r00 = w[0], r01 = w[1], r10 = w[3], r11 = w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double u = mean[2 * k], v = mean[2 * k + 1];
+        mean[2 * k] = r00 * u + r01 * v;
+        mean[2 * k + 1] = r10 * u + r11 * v;
+    }
+    mean[0] += w[2];
+    mean[1] += w[5];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)                  // X = R8 P: block rows
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const double a = cov[(2 * i) * 8 + c], e = cov[(2 * i + 1) * 8 + c];
+            cov[(2 * i) * 8 + c] = r00 * a + r01 * e;
+            cov[(2 * i + 1) * 8 + c] = r10 * a + r11 * e;
+        }
+#pragma unroll
+    for (int r = 0; r < 8; ++r)                  // P' = X R8^T: block columns
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double a = cov[r * 8 + 2 * j], e = cov[r * 8 + 2 * j + 1];
+            cov[r * 8 + 2 * j] = a * r00 + e * r01;
+            cov[r * 8 + 2 * j + 1] = a * r10 + e * r11;
+        }
+}
+
 // cost of (row r, column c) as stored for the LSAP: rows = the smaller side (transposed when there are fewer columns)
 __device__ inline size_t byte_cidx(int r, int c, int n_rows, int n_cols)
 {
@@ -64,7 +97,8 @@ __device__ inline void byte_assign(int n_rows, int n_cols, const double* cost, b
     __syncthreads();
 }
 
-template <bool XYWH>
+// GMC: BoT-SORT's camera-motion step 3b from b.gmc (only instantiated with XYWH; without it the code is the plain tracker's)
+template <bool XYWH, bool GMC>
 __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const float* __restrict__ dets, const int* __restrict__ ndets,
                                                     float* __restrict__ out, int* __restrict__ nout)
 {
@@ -121,6 +155,9 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
         const int nP = nPT + nL;
         __syncthreads();
         // ---- 3. predict the pool (thread = pool index); the unconfirmed tracks keep their mean ----
+        // ---- 3b. GMC (w6 >= 0: a warp, G-03): the predicted pool in registers, then the unconfirmed tracks ----
+        const double* gw = GMC ? b.gmc + fs * 8 : nullptr;
+        const bool warp = GMC && gw[6] >= 0.0;
         if (tid < nP) {
             const int slot = m.pool[tid];
             double mean[8], cov[64];
@@ -131,6 +168,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             for (int i = 0; i < 64; ++i) cov[i] = b.cov[g * 64 + i];
             if (m.state[slot] != SS_BYTE_TRACKED) { mean[7] = 0.0; if (XYWH) mean[6] = 0.0; }
             if (XYWH) ss_kf_predict_xywh(mean, cov, b.wp, b.wv); else ss_kf_predict(mean, cov, b.wp, b.wv);
+            if (warp) byte_gmc(mean, cov, gw);
 #pragma unroll
             for (int i = 0; i < 8; ++i) b.mean[g * 8 + i] = mean[i];
 #pragma unroll
@@ -139,9 +177,20 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
         }
         if (tid < nU) {
             const int slot = m.unc[tid];
+            const size_t g = sb + slot;
             double mean[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) mean[i] = b.mean[(sb + slot) * 8 + i];
+            for (int i = 0; i < 8; ++i) mean[i] = b.mean[g * 8 + i];
+            if (warp) {
+                double cov[64];
+#pragma unroll
+                for (int i = 0; i < 64; ++i) cov[i] = b.cov[g * 64 + i];
+                byte_gmc(mean, cov, gw);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) b.mean[g * 8 + i] = mean[i];
+#pragma unroll
+                for (int i = 0; i < 64; ++i) b.cov[g * 64 + i] = cov[i];
+            }
             byte_tlwh(mean, XYWH, m.tl[slot]);
         }
         __syncthreads();
@@ -350,6 +399,7 @@ size_t ss_byte_lds_bytes() { return sizeof(ByteLds); }
 
 void ss_launch_byte_group(const SSByteDev& b, int F, const float* dets, const int* ndets, float* out, int* nout, hipStream_t st)
 {
-    if (b.xywh) hipLaunchKernelGGL(k_byte_group<true>, dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
-    else hipLaunchKernelGGL(k_byte_group<false>, dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    if (b.xywh && b.gmc) hipLaunchKernelGGL((k_byte_group<true, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    else if (b.xywh) hipLaunchKernelGGL((k_byte_group<true, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    else hipLaunchKernelGGL((k_byte_group<false, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
 }

@@ -527,6 +527,7 @@ struct SSByteDev {
     float *score, *cls;                 // [S][MAXT]
     double *mean, *cov;                 // [S][MAXT][8], [S][MAXT][64]
     double* spill;                      // [S][MAXT * MAXD] cost matrices that do not fit the LDS
+    const double* gmc;                  // [F][S][8] BoT-SORT GMC warps (ss_byte_set_gmc, xywh only), NULL: off
 };
 
 // camera-motion warp m (2x3, full-frame pixels) applied to a track's box (oracle so_camera_update, D-18)

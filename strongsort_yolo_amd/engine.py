@@ -524,7 +524,18 @@ class ByteTrackEngine:
         self.base.use_current_stream()
 
     def reset(self, stream: int = -1):
+        """Restart the stream(s): ids from 1, and the next cmc_estimate frame gets no warp (G-04)."""
         self._ck(self.L.ss_byte_reset(self.base.ctx, stream))
+
+    def cmc_estimate(self, frames: torch.Tensor, n_frames: int, warps: torch.Tensor = None, stream=None, n_valid: torch.Tensor = None):
+        """N4's ECC warps of a group (TrackerEngine.cmc_estimate on the shared context): frames uint8 [F*S,H,W,3] -> [F,S,8]."""
+        return self.base.cmc_estimate(frames, n_frames, warps, stream=stream, n_valid=n_valid)
+
+    def set_cmc(self, warps):
+        """BoT-SORT GMC (docs/BYTETRACK.md §1b): the following update calls move every track by these warps ([F,S,8] float64,
+        ss_cmc_estimate's layout, at least as many rows as the calls' frames) after predicting; None: off.  xywh only."""
+        self._ck(self.L.ss_byte_set_gmc(self.base.ctx, _ptr(warps)))
+        self._cmc_keep = warps
 
     def check_errors(self):
         self.base.check_errors()

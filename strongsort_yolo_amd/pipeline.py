@@ -47,8 +47,8 @@ class FramePipeline:
         from .config import byte_config
         self.byte_cfg = byte_config(tracker)
         self.tracker = tracker
-        if self.byte_cfg is not None and cmc:
-            raise ValueError("camera-motion compensation is a StrongSORT option (BoT-SORT's GMC is not implemented)")
+        if self.byte_cfg is not None and cmc and self.byte_cfg.kalman != "xywh":
+            raise ValueError("camera-motion compensation needs tracker 'strongsort' or 'botsort' (ByteTrack has no GMC)")
         self.eng = TrackerEngine(self.cfg, n_streams, device, debug=debug)
         self.byte = None
         if self.byte_cfg is not None:
@@ -120,8 +120,8 @@ class FramePipeline:
         self.warps = torch.zeros(1, S, 8, dtype=torch.float64, device=dev) if self.cmc else None
         if self.cmc:
             self.eng.cmc_estimate(self.frames, 1, self.warps)            # sizes the small-frame buffer outside any capture
-            self.eng.reset(-1)
-            self.eng.set_cmc(self.warps)
+            self.reset_tracker(-1)
+            (self.eng if self.byte is None else self.byte).set_cmc(self.warps)    # BoT-SORT: GMC on the BYTE state (§1b)
 
     # ---- one frame for every stream, from the static buffers ----------------------------------------
     def _detect_impl(self):

@@ -73,25 +73,39 @@ class StrongSORT:
 
 
 class BYTETracker:
-    """The BYTE tracker family for one video stream (docs/BYTETRACK.md): `update(dets)` needs no frame and no ReID weights.
+    """The BYTE tracker family for one video stream (docs/BYTETRACK.md): `update(dets)` needs no ReID weights.
          dets  [N,6] float  x1,y1,x2,y2,conf,cls in frame pixels (numpy or torch), N <= 128
+         frame uint8 [H,W,3] BGR (numpy, or a torch tensor on the device): only with camera_motion=True
        returns float32 [M,8]: x1,y1,x2,y2,track_id,class_id,conf,det_idx for every activated tracked track (det_idx = row of
-       `dets` matched this frame, always >= 0).  cfg.kalman = "xyah": ByteTrack; "xywh": BoT-SORT without GMC / ReID."""
+       `dets` matched this frame, always >= 0).  cfg.kalman = "xyah": ByteTrack; "xywh": BoT-SORT without ReID.
+       camera_motion=True (xywh only): BoT-SORT's GMC (§1b) with the ECC warp between the previous frame and this one,
+       estimated on the device; `update(dets, frame)` then needs the frame."""
 
-    def __init__(self, cfg: Optional[ByteTrackConfig] = None, device: int = 0):
+    def __init__(self, cfg: Optional[ByteTrackConfig] = None, device: int = 0, camera_motion: bool = False):
         self.cfg = cfg or ByteTrackConfig()
+        if camera_motion and self.cfg.kalman != "xywh":
+            raise ValueError("camera_motion needs the xywh (BoT-SORT) filter: ByteTrack has no GMC")
         self.eng = ByteTrackEngine(self.cfg, 1, device)
         self.dev = self.eng.device
+        self.camera_motion = bool(camera_motion)
         self._dets = torch.zeros(1, MAX_DETS, 6, dtype=torch.float32, device=self.dev)
         self._n = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self._warps = torch.zeros(1, 1, 8, dtype=torch.float64, device=self.dev) if self.camera_motion else None
 
     @torch.no_grad()
-    def update(self, dets) -> np.ndarray:
+    def update(self, dets, frame=None) -> np.ndarray:
         self.eng.use_current_stream()
         dets = torch.as_tensor(dets, dtype=torch.float32).reshape(-1, 6)
         n = dets.shape[0]
         if n > self.cfg.max_dets:
             raise ValueError(f"at most {self.cfg.max_dets} detections per frame (got {n})")
+        if self.camera_motion:
+            if frame is None:
+                raise ValueError("camera_motion=True: update(dets, frame) needs the BGR frame")
+            frame_t = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame))
+            frame_t = frame_t.to(self.dev, non_blocking=True).contiguous()
+            self.eng.cmc_estimate(frame_t[None], 1, self._warps)
+            self.eng.set_cmc(self._warps)
         self._dets[0, :n].copy_(dets, non_blocking=True)
         self._n.fill_(n)
         out, nout = self.eng.update_device(self._dets, self._n)

@@ -246,14 +246,17 @@ class YOLO:
         (csrc/ss_mask.hip) and downloads bits and points instead of the prototypes; `Results.masks` then needs no host arithmetic
         beyond unpacking and scale_coords.  Default False: masks are built on the host when first read (assemble_masks / mask_polygon).
         tracker_type: "strongsort" (default: OSNet appearance + NSA Kalman), or the BYTE family on the device (docs/BYTETRACK.md) —
-        "bytetrack" (xyah Kalman) / "botsort" (xywh Kalman, no GMC, no ReID): IoU and scores only, no ReID network or weights;
+        "bytetrack" (xyah Kalman) / "botsort" (xywh Kalman, no ReID): IoU and scores only, no ReID network or weights;
         track() then runs NMS at conf 0.1 unless track(conf=...) says otherwise (Ultralytics' Model.track), predict() keeps
-        overrides['conf']."""
+        overrides['conf'].
+        camera_motion: ECC camera-motion warps estimated on the device beside the detector (N4). StrongSORT moves its track
+        boxes by them (D-18); "botsort" applies them as BoT-SORT's GMC to every track's Kalman mean and covariance
+        (docs/BYTETRACK.md §1b) in track() and track_stream(). "bytetrack" has no GMC: a ValueError."""
         byte_config(tracker_type)                 # ValueError on anything else
         self.tracker_type = tracker_type
         self._byte = tracker_type != "strongsort"
-        if self._byte and camera_motion:
-            raise ValueError("camera_motion is a StrongSORT option (BoT-SORT's GMC is not implemented)")
+        if tracker_type == "bytetrack" and camera_motion:
+            raise ValueError("camera_motion needs tracker_type 'strongsort' or 'botsort' (ByteTrack has no GMC, G-05)")
         self._conf_track = None                   # BYTE: the NMS threshold of the tracking pipelines (set while track / track_stream build)
         self.weights = weights
         self.reid_weights = reid_weights          # OSNet-x0.25 state_dict; same policy as the detector's (raise unless random init is asked for)

@@ -5,6 +5,11 @@
                               For the kernel's own time run it under `rocprofv3 --kernel-trace --stats -- python tools/byte_time.py ...`.
   --mode rates                YOLO.track() calls/s and track_stream frames/s, yolov8n (seeded random-init weights), bytetrack
                               mode beside the default StrongSORT (fp32 ReID) in the same process.
+  --gmc                       BoT-SORT's camera-motion step (docs/BYTETRACK.md §1b).  kernel mode: two xywh engines on the same
+                              streams, one with seeded synthetic warps installed (the GMC variant of k_byte_group) and one
+                              without, called alternately; each group also runs ss_cmc_estimate on 32 panning 1280x720 frames
+                              per stream (k_gray_small + k_ecc).  rates mode: botsort with and without camera_motion, one leg
+                              per fresh process, the legs interleaved (--rounds each).
 """
 import argparse
 import json
@@ -17,6 +22,68 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+
+def _pan_frames(G, S, H=720, W=1280, seed=0):
+    """G x S BGR frames cut from one seeded texture, panning 3 px right and 1 px down a frame ([F][S] order)."""
+    rng = np.random.default_rng(seed)
+    small = rng.integers(0, 256, ((H + 200) // 40, (W + 200) // 40, 3), dtype=np.uint8)
+    canvas = np.repeat(np.repeat(small, 40, 0), 40, 1)          # 40 px blocks: 4 px in the 0.1x grey images ECC aligns
+    out = np.zeros((G * S, H, W, 3), np.uint8)
+    for f in range(G):
+        for s in range(S):
+            out[f * S + s] = canvas[f + 4 * s:f + 4 * s + H, 3 * f:3 * f + W]
+    return out
+
+
+def kernel_gmc(S, groups, warmup):
+    from strongsort_yolo_amd.config import ByteTrackConfig
+    from strongsort_yolo_amd.engine import ByteTrackEngine
+    from tests.test_bytetrack_cpu import byte_stream
+    G = 32
+    n = (groups + warmup) * G
+    streams = [byte_stream(100 + s, n) for s in range(S)]
+    dev = torch.device("cuda", 0)
+    hd, hn = np.zeros((n, S, 128, 6), np.float32), np.zeros((n, S), np.int32)
+    for f in range(n):
+        for s in range(S):
+            d = streams[s][f]
+            hd[f, s, :len(d)], hn[f, s] = d, len(d)
+    rng = np.random.default_rng(7)                       # small seeded camera motions: tracks keep their detections
+    th = rng.uniform(-2e-3, 2e-3, (n, S))
+    w = np.zeros((n, S, 8))
+    w[..., 0], w[..., 1], w[..., 3], w[..., 4] = np.cos(th), -np.sin(th), np.sin(th), np.cos(th)
+    w[..., 2], w[..., 5], w[..., 6] = rng.uniform(-3, 3, (n, S)), rng.uniform(-3, 3, (n, S)), 5.0
+    dets, nd, warps = torch.from_numpy(hd).to(dev), torch.from_numpy(hn).to(dev), torch.from_numpy(w).to(dev)
+    frames = torch.from_numpy(_pan_frames(G, S)).to(dev)
+    out = torch.zeros(G, S, 256, 8, device=dev)
+    nout = torch.zeros(G, S, dtype=torch.int32, device=dev)
+    cfg = ByteTrackConfig(kalman="xywh")
+    plain, gmc = ByteTrackEngine(cfg, S, 0), ByteTrackEngine(cfg, S, 0)
+    plain.use_current_stream()
+    gmc.use_current_stream()
+    ecc_warps = gmc.cmc_estimate(frames, G)              # sizes the small-frame buffer
+    ms = {"plain": [], "gmc": [], "ecc": []}
+    for g in range(groups + warmup):
+        sl = slice(g * G, (g + 1) * G)
+        gmc.set_cmc(warps[sl])
+        for leg, fn in (("plain", lambda: plain.update_group(G, dets[sl], nd[sl], None, None, out, nout)),
+                        ("gmc", lambda: gmc.update_group(G, dets[sl], nd[sl], None, None, out, nout)),
+                        ("ecc", lambda: gmc.cmc_estimate(frames, G, ecc_warps))):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if g >= warmup:
+                ms[leg].append(a.elapsed_time(b))
+    plain.check_errors()
+    gmc.check_errors()
+    med = {k: float(np.median(v)) * 1e3 for k, v in ms.items()}
+    return {"mode": "kernel_gmc", "streams": S, "group_frames": G, "groups": groups, "dets_per_frame": float(hn.mean()),
+            "plain_us_per_group_median": med["plain"], "gmc_us_per_group_median": med["gmc"], "gmc_over_plain": med["gmc"] / med["plain"],
+            "ecc_us_per_group_median": med["ecc"], "ecc_frame": "1280x720", "ecc_iterations_mean": float(ecc_warps[..., 6].float().mean()),
+            "note": "host event pair around one call (includes launch latency); kernel times: rocprofv3 --kernel-trace --stats"}
 
 
 def kernel(S, groups, warmup):
@@ -80,6 +147,50 @@ def rates(n_frames, batch):
     return res
 
 
+def rate_leg(leg, n_frames, batch):
+    """One leg in this process: botsort with (leg "botsort_cmc") or without camera_motion, 1280x720 frames panning 3 px a frame."""
+    os.environ["SS_RANDOM_INIT"] = "1"
+    from strongsort_yolo_amd.yolo import YOLO
+    pan = _pan_frames(16, 1)
+    frames = [pan[k].copy() for k in range(16)]
+    frames += frames[::-1]                                  # back and forth: the sequence can repeat without a jump
+    m = YOLO("yolov8n.pt", random_init_ok=True, tracker_type="botsort", camera_motion=leg == "botsort_cmc")
+    for k in range(10):
+        m.track(frames[k % 32], persist=True)
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for k in range(n_frames):
+        m.track(frames[k % 32], persist=True)
+    res = {"leg": leg, "track_calls_per_s": n_frames / (time.perf_counter() - t)}
+    src = [frames[k % 32] for k in range(n_frames)]
+    for _ in m.track_stream(src[:2 * batch], batch=batch):
+        pass
+    t = time.perf_counter()
+    for _ in m.track_stream(src, batch=batch):
+        pass
+    res["track_stream_frames_per_s"] = n_frames / (time.perf_counter() - t)
+    m.close()
+    return res
+
+
+def rates_gmc(n_frames, batch, rounds):
+    import subprocess
+    legs = {"botsort": [], "botsort_cmc": []}
+    for r in range(rounds):
+        for leg in (("botsort", "botsort_cmc") if r % 2 == 0 else ("botsort_cmc", "botsort")):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", "rates", "--leg", leg, "--frames", str(n_frames),
+                                "--batch", str(batch)], capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                raise RuntimeError(f"leg {leg} failed ({p.returncode}): {p.stderr[-2000:]}")
+            legs[leg].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    res = {"mode": "rates_gmc", "weights": "yolov8n (seeded random init)", "frame": "1280x720", "batch": batch, "rounds": rounds}
+    for leg, rs in legs.items():
+        for k in ("track_calls_per_s", "track_stream_frames_per_s"):
+            res[f"{leg}_{k}_median"] = float(np.median([r[k] for r in rs]))
+            res[f"{leg}_{k}_all"] = [round(r[k], 1) for r in rs]
+    return res
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--mode", choices=("kernel", "rates"), default="kernel")
@@ -88,6 +199,14 @@ if __name__ == "__main__":
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--frames", type=int, default=256)
     p.add_argument("--batch", type=int, default=32)
+    p.add_argument("--gmc", action="store_true", help="BoT-SORT GMC legs (see the module docstring)")
+    p.add_argument("--rounds", type=int, default=3, help="rates --gmc: processes per leg")
+    p.add_argument("--leg", choices=("botsort", "botsort_cmc"), default=None, help=argparse.SUPPRESS)
     a = p.parse_args()
-    r = kernel(a.streams, a.groups, a.warmup) if a.mode == "kernel" else rates(a.frames, a.batch)
+    if a.leg is not None:
+        r = rate_leg(a.leg, a.frames, a.batch)
+    elif a.mode == "kernel":
+        r = kernel_gmc(a.streams, a.groups, a.warmup) if a.gmc else kernel(a.streams, a.groups, a.warmup)
+    else:
+        r = rates_gmc(a.frames, a.batch, a.rounds) if a.gmc else rates(a.frames, a.batch)
     print(json.dumps(r))
