@@ -3,6 +3,12 @@
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
     python bench.py ... --dump-outputs DIR                   (+ the last timed step's outputs as DIR/<name>.npy: dump_outputs)
+    python bench.py ... --full                               (+ every check and side measurement listed below)
+
+A plain run does only what the headline needs: set up, prefill, warm up, time the K steps, dump the outputs if asked, and
+print the line (`value`, `ms_per_step`, the step distribution and the association kernel's `roofline`, which are read off
+the timed steps themselves).  `--full` adds, after the timed steps, the checks against the exact-order oracle and every
+side measurement that takes runs of its own; the `--no-*` switches drop single ones of them.
 
 One "step" = one batch of `frames_per_step` consecutive frames (default one frame-batch group of 32 frames) of
 every stream owned by the rank through the whole hot path (letterbox -> detector -> NMS -> ReID crops -> OSNet ->
@@ -31,11 +37,14 @@ The JSON line also carries
                 measured with HIP start/stop events on the kernel's own dispatches inside the timed
                 region; traffic = HBM bytes per launch from the rocprofv3 PMC summary committed
                 under profiles/ (null until that file exists)
+and with --full (null in a plain run):
   roofline_batched  the same kernel family at 32 streams per launch (tracker path only), the regime where the
                 HBM roofline is meaningful (one stream moves 6 MB per launch, below a kernel boundary)
   cpu_baseline  the oracle ("port": NumPy/SciPy tracker + C-oracle frame stages + CPU-torch nets)
                 timed on this box's host cores on a bounded sample (rank 0, N=1 only)
   id_match_rate fraction of output rows identical to the exact-order C oracle on the same input
+  ...           roofline_front, net_outputs_check, api_path, tracker_only, reid_f16_vs_f32, det_f16_vs_f32,
+                throughput_mode / accuracy_mode, all_fp32
 """
 import argparse
 import json
@@ -857,6 +866,9 @@ def main():
     ap.add_argument("--pipe", action="append", default=[], help="A/B switch of the frame pipeline name=0|1: pack_crops, assoc_gate, track_priority; chain_cus=N (compute units reserved for the detached tracker chain)")
     ap.add_argument("--overlap", type=int, default=2, help="N>1: N-stage frame pipeline on N HIP streams (2 or 4; stateless detector / OSNet stages of later frames overlap the tracker of earlier ones); 0/1: strictly sequential")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last timed step computed to DIR/<name>.npy (float32, rank 0's streams; see dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also check every frame against the oracle and run the side measurements "
+                    "(network output check, front rooflines, API path, batched association, tracker only, precision checks, other-precision runs, "
+                    "CPU baseline); a plain run only times the steps")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -1180,25 +1192,28 @@ def main():
                     "frac_inkernel": (round((flops / t_ik / 1e12 / 157.3) if fp32_bound else (alg_bytes / t_ik / 1e9 / 8000.0), 4) if t_ik > 0 else None),
                     "tracks_confirmed_per_stream": [t for t, _ in T_conf], "gallery_rows": [round(b, 1) for _, b in T_conf]}
 
-    nets_check = net_outputs_check(pipe) if (rank == 0 and not args.no_nets and overlap) else None      # before anything touches the buffers again
-    roofline_front = front_rooflines(pipe, FB * S, Dm) if (rank == 0 and not args.no_nets and overlap) else None
+    nets_check = net_outputs_check(pipe) if (args.full and rank == 0 and not args.no_nets and overlap) else None      # before anything touches the buffers again
+    roofline_front = front_rooflines(pipe, FB * S, Dm) if (args.full and rank == 0 and not args.no_nets and overlap) else None
 
-    # ---- identical-ID rate vs the exact-order oracle: every rank checks ITS stream 0 over the WHOLE run (prefill, warm-up
+    # ---- identical-ID rate vs the exact-order oracle (--full): every rank checks ITS stream 0 over the WHOLE run (prefill, warm-up
     # and every timed frame: the oracle is a recurrence, so it has to see all of them anyway), rank 0 reports the minimum ----
-    nchk = total if args.check_frames < 0 else min(args.check_frames, total)
-    same, tot, exact_frames, exact_timed, n_timed = id_check(R, nchk)
-    out_host, nout_host = R.out_host, R.nout_host
-    id_rate = same / max(tot, 1)
+    if args.full:
+        nchk = total if args.check_frames < 0 else min(args.check_frames, total)
+        same, tot, exact_frames, exact_timed, n_timed = id_check(R, nchk)
+        id_min = torch.tensor([same / max(tot, 1), float(exact_frames), float(exact_timed)], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
+        if world > 1:
+            dist.all_reduce(id_min, op=dist.ReduceOp.MIN)
+        id_rate_min, exact_min, exact_timed_min = float(id_min[0].item()), int(id_min[1].item()), int(id_min[2].item())
+        ids = {"id_match_rate": round(id_rate_min, 6), "frames_bit_exact": f"{exact_min}/{nchk}", "frames_bit_exact_timed": f"{exact_timed_min}/{n_timed}",
+               "id_check": "every rank vs the oracle on its own stream 0 over prefill + warm-up + ALL timed frames, minimum over ranks"}
+    else:
+        ids = dict.fromkeys(("id_match_rate", "frames_bit_exact", "frames_bit_exact_timed", "id_check"))
     per_rank_enq = [round(t_enq_cpu / KF * 1e3, 4)]
     if world > 1:
         te = torch.tensor([t_enq_cpu / KF * 1e3], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         ge = [torch.zeros_like(te) for _ in range(world)]
         dist.all_gather(ge, te)
         per_rank_enq = [round(float(t.item()), 4) for t in ge]
-    id_min = torch.tensor([id_rate, float(exact_frames), float(exact_timed)], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
-    if world > 1:
-        dist.all_reduce(id_min, op=dist.ReduceOp.MIN)
-    id_rate_min, exact_min, exact_timed_min = float(id_min[0].item()), int(id_min[1].item()), int(id_min[2].item())
     if rank == 0:
         res = {
             "metric": f"tracked frames/sec (whole node), {W}x{H}@{n_ids}det",
@@ -1216,8 +1231,7 @@ def main():
             "backend": (backend + ("=RCCL" if backend == "nccl" else "")) if world > 1 else None,
             "devices": "one GPU shared by all ranks (SS_BENCH_SINGLE_DEVICE=1: control-flow run)" if (one_dev and world > 1) else "one GPU per rank",
             "cpu_affinity_rank0": affinity, "per_rank_host_enqueue_cpu_ms_per_frame": per_rank_enq,
-            "host_enqueue_ms_per_frame": round(t_enq / KF * 1e3, 4), "host_enqueue_cpu_ms_per_frame": round(t_enq_cpu / KF * 1e3, 4), "id_match_rate": round(id_rate_min, 6), "frames_bit_exact": f"{exact_min}/{nchk}", "frames_bit_exact_timed": f"{exact_timed_min}/{n_timed}",
-            "id_check": "every rank vs the oracle on its own stream 0 over prefill + warm-up + ALL timed frames, minimum over ranks",
+            "host_enqueue_ms_per_frame": round(t_enq / KF * 1e3, 4), "host_enqueue_cpu_ms_per_frame": round(t_enq_cpu / KF * 1e3, 4), **ids, "full": args.full,
             "roofline": roofline, "roofline_front": roofline_front, "net_outputs_check": nets_check,
         }
         res["roofline_batched"] = None
@@ -1233,22 +1247,23 @@ def main():
             print("bench.py: side measurement failed:\n" + traceback.format_exc(), file=sys.stderr)
             return {"error": f"{type(e).__name__}: {e}"[:300]}
 
+    legs = args.full and world == 1                     # the side measurements: rank 0 of a one-rank --full run
     if rank == 0:
-        if world == 1 and not args.no_api_path and not args.no_nets and args.preset in ("c2", "c3"):
+        if legs and not args.no_api_path and not args.no_nets and args.preset in ("c2", "c3"):
             res["api_path"] = leg(api_path, detector, W, H, n_ids, gs, nc, A, cfg, dcfg, device=dev_index, reid_fp32=args.reid_fp32)
             if args.reid_fp32:                           # ... and the same calls in the f16 throughput mode
                 res["api_path_f16"] = leg(api_path, detector, W, H, n_ids, gs, nc, A, cfg, dcfg, device=dev_index, reid_fp32=False)
-        if world == 1 and not args.no_batched:
+        if legs and not args.no_batched:
             bkw = dict(device=dev_index, n_ids=n_ids, W=W, H=H, preset=args.preset, n_streams=32 if n_ids <= 30 else 8, opts=tuple(args.opt))
             res["roofline_batched"] = leg(batched_association, cfg, frames=160, timed=32, frame_batch=FB if FB in (1, 2, 4, 8, 16, 32) else (32 if FB > 32 else 8), **bkw)
             res["roofline_batched_frame_at_a_time"] = leg(batched_association, cfg, frames=160, timed=32, frame_batch=1, check=False, **bkw)
             res["tracker_only"] = leg(tracker_only, cfg, n_ids=n_ids, W=W, H=H, device=dev_index, opts=tuple(args.opt))
-        if world == 1 and not args.no_reid_check and not args.no_nets:
+        if legs and not args.no_reid_check and not args.no_nets:
             res["reid_f16_vs_f32"] = leg(reid_f16_vs_f32, detector, W, H, n_ids, cfg, dcfg, device=dev_index)
             res["reid_f16_vs_f32"]["fp32_reid_mode"] = leg(reid_f16_vs_f32, detector, W, H, n_ids, cfg, dcfg, device=dev_index, reid_half=False)
-        if world == 1 and not args.no_reid_check and not args.no_nets and args.preset in ("c2", "c3", "c5"):
+        if legs and not args.no_reid_check and not args.no_nets and args.preset in ("c2", "c3", "c5"):
             res["det_f16_vs_f32"] = leg(det_f16_vs_f32, detector, W, H, n_ids, dcfg, device=dev_index)
-        if world == 1 and overlap and not args.no_nets and not args.no_accuracy_mode:
+        if legs and overlap and not args.no_nets and not args.no_accuracy_mode:
             # the OTHER ReID precision, measured the same way on fewer steps.  Default line (fp32 ReID, the configuration that meets
             # north_star's float bound): `throughput_mode` = f16 ReID kernels; with --reid-f16: `accuracy_mode` = fp32 ReID kernels.
             # `all_fp32`: the detector in fp32 as well (no f16 arithmetic left on the path).
@@ -1263,7 +1278,7 @@ def main():
                 import subprocess
                 cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(max(2, args.accuracy_steps)), "--warmup", "2", "--preset", args.preset,
                        "--streams", str(args.streams), "--graph", args.graph, "--frame-batch", str(args.frame_batch), "--overlap", str(args.overlap),
-                       "--groups-per-step", str(args.groups_per_step), "--defer-track", str(args.defer_track), "--no-cpu-baseline", "--no-batched", "--no-api-path",
+                       "--groups-per-step", str(args.groups_per_step), "--defer-track", str(args.defer_track), "--full", "--no-cpu-baseline", "--no-batched", "--no-api-path",
                        "--no-reid-check", "--no-accuracy-mode"] + extra
                 for kv in args.pipe: cmd += ["--pipe", kv]
                 for kv in args.opt: cmd += ["--opt", kv]
@@ -1329,7 +1344,7 @@ def main():
             res["fp32_reid_true_path"] = {"distance_err": tp32.get("cost_matrix_cosine_max_abs_err"), "embedding_err": tp32.get("embedding_unit_max_abs_err"),
                                           "id_match_rate": tp32.get("id_match_rate"), "within_north_star_bound_1e-4": tp32.get("within_bound"),
                                           "what": "the default line's ReID precision on the true ReID data path (150 rendered frames, CPU fp32 network + C-oracle tracker as the checker)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if legs and not args.no_cpu_baseline:
             res["cpu_baseline"] = leg(cpu_baseline, W, H, n_ids, nc, A, detector)
         print(json.dumps(res), flush=True)
     if world > 1:

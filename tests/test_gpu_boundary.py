@@ -399,7 +399,7 @@ def test_two_ranks_on_one_gpu_each_identical_to_its_oracle():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SS_BENCH_BACKEND="gloo", SS_BENCH_SINGLE_DEVICE="1", SS_RANDOM_INIT="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                           "--no-api-path", "--no-batched"], env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
@@ -409,6 +409,25 @@ def test_two_ranks_on_one_gpu_each_identical_to_its_oracle():
     n, m = d["frames_bit_exact_timed"].split("/")
     assert n == m and int(m) == 2 * 32
     assert abs(d["value"] - 2 * min(d["per_rank_value"])) <= 0.03                       # whole job = ranks x frames / max-rank time (each rounded to 2 decimals)
+
+
+def test_plain_bench_run_times_the_steps_and_nothing_else(tmp_path):
+    """`python bench.py` without --full: the headline and the last step's outputs, no oracle check and no side measurement."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, SS_RANDOM_INIT="1")
+    env.pop("WORLD_SIZE", None); env.pop("RANK", None)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         env=env, capture_output=True, text=True, timeout=600)
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["value"] > 0 and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - d["frames_per_step"] * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+    assert d["roofline"]["launches_timed"] > 0
+    assert all(d[k] is None for k in ("id_match_rate", "frames_bit_exact", "frames_bit_exact_timed", "roofline_front", "net_outputs_check", "roofline_batched", "cpu_baseline"))
+    assert not {"api_path", "tracker_only", "reid_f16_vs_f32", "det_f16_vs_f32", "throughput_mode", "all_fp32"} & set(d)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["embeddings.npy", "head_sample.npy", "track_counts.npy", "track_rows.npy"]
 
 
 def test_yolo_segmentation_masks_follow_the_boxes():
