@@ -205,8 +205,8 @@ int ss_track_update_group(ss_ctx* ctx, int n_frames, const float* d_dets, const 
 int ss_track_update(ss_ctx* ctx, const float* d_dets, const int* d_ndets, const float* d_feats,
                     const int* d_img_hw, float* d_out, int* d_nout);
 
-/* ---- BYTE tracker family (docs/BYTETRACK.md): ByteTrack (xyah Kalman) and BoT-SORT without ReID (xywh Kalman, optional GMC) -
- * Opt-in, IoU-only association on detection scores (no ReID features).  The state is hung off an existing context (its streams,
+/* ---- BYTE tracker family (docs/BYTETRACK.md): ByteTrack (xyah Kalman) and BoT-SORT (xywh Kalman, optional GMC and ReID) -----
+ * Opt-in association on IoU and detection scores; BoT-SORT can add an appearance term (ss_byte_set_reid).  The state is hung off an existing context (its streams,
  * its HIP stream, its error words); ss_byte_create on a context that already has one replaces it. */
 typedef struct ss_byte_config {
     double track_high_thresh;    /* 0.25  first-association rows: score >= this                   */
@@ -233,12 +233,25 @@ int ss_byte_destroy(ss_ctx* ctx);
 int ss_byte_update_group(ss_ctx* ctx, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
 int ss_byte_update(ss_ctx* ctx, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
 int ss_byte_reset(ss_ctx* ctx, int stream);                /* stream < 0: all streams; ids restart at 1, frame_id at 1; the
-                                                              stream's previous ss_cmc_estimate frame is forgotten (no warp next) */
+                                                              stream's previous ss_cmc_estimate frame is forgotten (no warp next)
+                                                              and its ReID track features are cleared */
 /* BoT-SORT GMC (docs/BYTETRACK.md §1b): the following ss_byte_update(_group) calls move every track's Kalman mean and covariance
  * by d_warps[f][s][8] (ss_cmc_estimate's layout; [6] < 0: no warp) after predicting frame f.  The caller keeps at least
  * n_frames rows alive; the pointer is read at launch (capturable).  NULL switches it off (the default).  SS_ERR_INVALID without
  * BYTE state or on an xyah (ByteTrack) state. */
 int ss_byte_set_gmc(ss_ctx* ctx, const double* d_warps);
+/* BoT-SORT's ReID branch (docs/BYTETRACK.md §1c): on != 0 adds the appearance term to the first and third associations, with
+ * proximity_thresh (0.5, on 1 - IoU), appearance_thresh (0.25, on the halved cosine distance) and the feature EMA weight alpha
+ * (0.9: (float)alpha, (float)(1 - alpha)).  Switching (on or off) resets every stream.  The first switch-on allocates the track
+ * features (512 KiB per stream) and the group's unit features (8 MiB per stream).  SS_ERR_INVALID without BYTE state or on an
+ * xyah (ByteTrack) state.  While ReID is on, ss_byte_update(_group) are refused: use ss_byte_update_group_feats. */
+int ss_byte_set_reid(ss_ctx* ctx, int on, double proximity_thresh, double appearance_thresh, double alpha);
+/* ss_byte_update_group with the group's raw detection features d_feats [n_frames][n_streams][SS_MAX_DETS][512] f32 (ReID on;
+ * ignored and may be NULL when it is off).  Asynchronous, capturable. */
+int ss_byte_update_group_feats(ss_ctx* ctx, int n_frames, const float* d_dets, const int* d_ndets, const float* d_feats,
+                               float* d_out, int* d_nout);
+/* Synchronous: the unit track features [n][512] of one stream in ss_byte_get_tracks' list order (after ss_byte_set_reid). */
+int ss_byte_get_features(ss_ctx* ctx, int stream, int cap, float* smooth);
 /* Synchronous: the table of one stream in list order (tracked list, then lost list); any array may be NULL.
  * state 1 tracked, 2 lost; mean [n][8] (xyah or xywh state). */
 int ss_byte_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracked, int* n_lost, int* next_id, int* frame_id,

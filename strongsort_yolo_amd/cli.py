@@ -197,7 +197,7 @@ def process_video(args: dict, model=None) -> dict:
         model = YOLO(args.get("weights", DEFAULT_WEIGHTS), random_init_ok=args.get("random_init", False), reid_weights=args.get("reid_weights"),
                      reid_fp32=not args.get("reid_f16", False), half=not args.get("fp32", False),
                      device_masks=args.get("device_masks", False), tracker_type=args.get("tracker", "strongsort"),
-                     camera_motion=args.get("camera_motion", False))
+                     camera_motion=args.get("camera_motion", False), with_reid=args.get("with_reid", False))
         model.overrides.update(conf=0.3, iou=0.4, agnostic_nms=False, max_det=1000)      # :18-21
     name = os.path.splitext(os.path.basename(str(source)))[0] or "stream"
     writer = LabelsWriter(os.path.join(args.get("outdir", "output"), f"{name}_labels.txt"), args.get("compat", False))
@@ -263,12 +263,14 @@ def main(argv=None):
     p.add_argument("--reid-f16", action="store_true", help="throughput mode: ReID crops + OSNet with f16 activations (1.7x the stream rate; appearance distances off by up to 3e-2)")
     p.add_argument("--fp32", action="store_true", help="every network operation in fp32 (the reference passes no half=): detector on the fp32 convolution kernels too — NMS keep lists equal the CPU fp32 network's; about 0.39x the f16 throughput")
     p.add_argument("--reid-weights", default=None, help="OSNet-x0.25 state_dict for the tracker's appearance features (required with --track unless --random-init; "
-                                                          "not used by --tracker bytetrack / botsort)")
+                                                          "used by --tracker botsort only with --with-reid, not by bytetrack)")
     p.add_argument("--tracker", choices=("strongsort", "bytetrack", "botsort"), default="strongsort",
                    help="strongsort (default): OSNet appearance + NSA Kalman; bytetrack / botsort: the BYTE family on IoU and scores, no ReID network (docs/BYTETRACK.md)")
     p.add_argument("--camera-motion", action="store_true",
                    help="ECC camera-motion compensation on the device: StrongSORT moves its track boxes, botsort applies BoT-SORT's GMC "
                         "(docs/BYTETRACK.md §1b); not with --tracker bytetrack")
+    p.add_argument("--with-reid", action="store_true",
+                   help="--tracker botsort only: BoT-SORT's ReID branch, OSNet-x0.25 appearance beside IoU (docs/BYTETRACK.md §1c; needs --reid-weights or --random-init)")
     p.add_argument("--limit", type=int, default=None)
     p.add_argument("--save", default=None, help="write annotated frames: stack.npy | video.bgr (raw BGR24 + .json) | directory of PNGs | video.mp4 (needs OpenCV)")
     p.add_argument("--batch", type=int, default=16, help="frames per group on the throughput path (1: per-frame model.track calls as in the reference)")
@@ -277,7 +279,9 @@ def main(argv=None):
     a = p.parse_args(argv)
     if a.camera_motion and a.tracker == "bytetrack":
         p.error("--camera-motion needs --tracker strongsort or botsort (ByteTrack has no GMC)")
-    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion,
+    if a.with_reid and a.tracker != "botsort":
+        p.error("--with-reid is BoT-SORT's ReID branch: it needs --tracker botsort")
+    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid,
              "save": (a.save if len(a.source) == 1 else f"{os.path.splitext(a.save)[0]}_{i}{os.path.splitext(a.save)[1]}") if a.save else None}
             for i, s in enumerate(a.source)]
     import torch

@@ -57,7 +57,9 @@ class DetectConfig:
 @dataclass(frozen=True)
 class ByteTrackConfig:
     """The BYTE tracker family (docs/BYTETRACK.md, decisions B-01..): Ultralytics' bytetrack.yaml / botsort.yaml defaults
-    (recalled from Ultralytics 8.3.x; botsort without GMC and ReID).  kalman = "xyah" (ByteTrack) or "xywh" (BoT-SORT)."""
+    (recalled from Ultralytics 8.3.x).  kalman = "xyah" (ByteTrack) or "xywh" (BoT-SORT).  with_reid (xywh only): BoT-SORT's
+    appearance term (§1c, decisions R-01..) with proximity_thresh on 1 - IoU, appearance_thresh on the halved cosine
+    distance and the feature EMA weight feat_alpha."""
     track_high_thresh: float = 0.25
     track_low_thresh: float = 0.1
     new_track_thresh: float = 0.25
@@ -71,10 +73,17 @@ class ByteTrackConfig:
     # capacities of the device-resident track table (per stream: tracked + lost + unconfirmed) and of a frame
     max_tracks: int = 256
     max_dets: int = 128
+    # BoT-SORT's ReID branch (§1c); appearance_thresh: older botsort.yaml files have 0.25, later 8.3.x ones 0.8 (R-03)
+    with_reid: bool = False
+    proximity_thresh: float = 0.5
+    appearance_thresh: float = 0.25
+    feat_alpha: float = 0.9
 
     def __post_init__(self):
         if self.kalman not in ("xyah", "xywh"):
             raise ValueError(f"ByteTrackConfig.kalman: 'xyah' or 'xywh', not {self.kalman!r}")
+        if self.with_reid and self.kalman != "xywh":
+            raise ValueError("ByteTrackConfig.with_reid needs kalman='xywh' (BoT-SORT): ByteTrack has no ReID")
         if not (0 < self.max_tracks <= 256 and 0 < self.max_dets <= 128):
             raise ValueError("ByteTrackConfig: max_tracks <= 256 and max_dets <= 128 (the device table's capacity)")
 
@@ -90,7 +99,11 @@ class ByteTrackConfig:
 TRACKER_TYPES = ("strongsort", "bytetrack", "botsort")
 
 
-def byte_config(tracker_type: str):
+def byte_config(tracker_type: str, with_reid: bool = False):
     if tracker_type not in TRACKER_TYPES:
         raise ValueError(f"tracker_type must be one of {TRACKER_TYPES}, not {tracker_type!r}")
-    return None if tracker_type == "strongsort" else ByteTrackConfig(kalman="xywh" if tracker_type == "botsort" else "xyah")
+    if with_reid and tracker_type != "botsort":
+        raise ValueError(f"with_reid is BoT-SORT's ReID branch: tracker_type 'botsort', not {tracker_type!r}")
+    if tracker_type == "strongsort":
+        return None
+    return ByteTrackConfig(kalman="xywh" if tracker_type == "botsort" else "xyah", with_reid=bool(with_reid))

@@ -43,7 +43,7 @@ void ss_launch_mask_assemble(const void*, int, long long, int, int, int, const f
 void ss_launch_mask_outline(const uint32_t*, long long, const int*, int, int, int, int, int, int*, long long, int*, long long, uint32_t*,
                             long long, int*, int, hipStream_t);
 extern "C" void ss_step_kernel_attr();
-void ss_launch_byte_group(const SSByteDev&, int, const float*, const int*, float*, int*, hipStream_t);
+void ss_launch_byte_group(const SSByteDev&, int, const float*, const int*, const float*, float*, int*, hipStream_t);
 
 static std::string g_last_error;
 
@@ -1098,6 +1098,8 @@ extern "C" int ss_byte_reset(ss_ctx* c, int stream)
     HIPCHK(c, hipMemsetAsync(b.n_lost + s0, 0, (s1 - s0) * 4, c->stream));
     HIPCHK(c, hipMemcpyAsync(b.next_id + s0, ones.data(), (s1 - s0) * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->cmc_prev_valid + s0, 0, (s1 - s0) * 4, c->stream));     // G-04: the next frame gets no warp
+    if (b.smooth)                                                                        // §1c: the streams' track features
+        HIPCHK(c, hipMemsetAsync(b.smooth + (size_t)s0 * SS_MAXT * SS_F, 0, (size_t)(s1 - s0) * SS_MAXT * SS_F * 4, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SS_OK;
 }
@@ -1146,8 +1148,71 @@ extern "C" int ss_byte_update_group(ss_ctx* c, int n_frames, const float* d_dets
     if (!c || !d_dets || !d_ndets || !d_out || !d_nout) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: null argument");
     if (!c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: no BYTE state (ss_byte_create)");
     if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: 1 <= n_frames <= SS_FMAX");
-    ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, d_out, d_nout, c->stream);
+    if (c->byte->dev.reid) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: ReID is on, the features go through ss_byte_update_group_feats");
+    ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, nullptr, d_out, d_nout, c->stream);
     HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+// §1c: ss_byte_update_group with the group's raw detection features d_feats [n_frames][S][SS_MAXD][512] f32 (read only while ReID
+// is on; NULL allowed when it is off).  Two launches on the context's stream (unit features, then the group): capturable.
+extern "C" int ss_byte_update_group_feats(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, const float* d_feats,
+                                          float* d_out, int* d_nout)
+{
+    if (!c || !d_dets || !d_ndets || !d_out || !d_nout) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: null argument");
+    if (!c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: no BYTE state (ss_byte_create)");
+    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: 1 <= n_frames <= SS_FMAX");
+    if (c->byte->dev.reid && !d_feats) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: ReID is on and d_feats is NULL");
+    ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, d_feats, d_out, d_nout, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+// §1c: BoT-SORT's ReID branch on (on != 0) or off.  Either way every stream restarts (ss_byte_reset).  The feature tables are
+// allocated on the first switch-on and kept.  xyah (ByteTrack) has no ReID.
+extern "C" int ss_byte_set_reid(ss_ctx* c, int on, double proximity_thresh, double appearance_thresh, double alpha)
+{
+    if (!c || !c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: no BYTE state (ss_byte_create)");
+    SSByteDev& b = c->byte->dev;
+    if (on && !b.xywh) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: ReID needs the xywh (BoT-SORT) state");
+    if (on && !b.smooth) {
+        const size_t ns = (size_t)b.S * SS_MAXT * SS_F, nu = (size_t)SS_FMAX * b.S * SS_MAXD * SS_F;
+        void *p = nullptr, *q = nullptr;
+        HIPCHK(c, hipMalloc(&p, ns * 4));
+        c->byte->allocs.push_back(p);
+        HIPCHK(c, hipMalloc(&q, nu * 4));
+        c->byte->allocs.push_back(q);
+        HIPCHK(c, hipMemsetAsync(q, 0, nu * 4, c->stream));
+        b.smooth = (float*)p; b.ufeat = (float*)q;
+    }
+    b.reid = on != 0;
+    b.prox = proximity_thresh; b.appear = appearance_thresh;
+    b.alpha = (float)alpha; b.one_minus_alpha = (float)(1.0 - alpha);
+    return ss_byte_reset(c, -1);
+}
+
+// Synchronous: the smoothed features [n][512] of one stream in ss_byte_get_tracks' list order.
+extern "C" int ss_byte_get_features(ss_ctx* c, int s, int cap, float* smooth)
+{
+    if (!c || !c->byte || s < 0 || s >= c->dev.S || cap < 0 || !smooth) return fail(c, SS_ERR_INVALID, "ss_byte_get_features: no BYTE state, bad stream or NULL");
+    const SSByteDev& b = c->byte->dev;
+    if (!b.smooth) return fail(c, SS_ERR_INVALID, "ss_byte_get_features: ReID was never switched on (ss_byte_set_reid)");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int nt = 0, nl = 0;
+    HIPCHK(c, hipMemcpy(&nt, b.n_trk + s, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&nl, b.n_lost + s, 4, hipMemcpyDeviceToHost));
+    if (nt + nl > cap) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_features: cap too small");
+    const size_t T = SS_MAXT, sb = (size_t)s * T;
+    std::vector<int> trk(T), lost(T);
+    std::vector<float> sm(T * SS_F);
+    HIPCHK(c, hipMemcpy(trk.data(), b.trk + sb, T * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(lost.data(), b.lost + sb, T * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(sm.data(), b.smooth + sb * SS_F, T * SS_F * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < nt + nl; ++i) {
+        const int slot = i < nt ? trk[i] : lost[i - nt];
+        if (slot < 0 || slot >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_features: corrupt list");
+        memcpy(smooth + (size_t)i * SS_F, sm.data() + (size_t)slot * SS_F, SS_F * 4);
+    }
     return SS_OK;
 }
 

@@ -1,11 +1,14 @@
-// ss_byte.hip — the BYTE tracker family on the device (docs/BYTETRACK.md): ByteTrack (xyah Kalman) and BoT-SORT without
-// ReID (xywh Kalman, optional GMC), S independent streams, a GROUP of F <= SS_FMAX frames per call.
+// ss_byte.hip — the BYTE tracker family on the device (docs/BYTETRACK.md): ByteTrack (xyah Kalman) and BoT-SORT (xywh Kalman,
+// optional GMC, optional ReID), S independent streams, a GROUP of F <= SS_FMAX frames per call.
 //
+//   k_byte_feats  (ReID only, before k_byte_group in the same call) one wave per detection row of the group: so_normalize of
+//                 the raw 512-float feature into b.ufeat.
 //   k_byte_group  one workgroup (256 threads) per stream walks the group's frames in order inside the launch: score split,
 //                 Kalman predict of the pool, BoT-SORT's GMC (§1b, the GMC variant only: the warps of ss_cmc_estimate
 //                 applied to the predicted pool and the unconfirmed tracks), three IoU associations (fused high / plain low / unconfirmed) each solved by
 //                 the one-wave LSAP (SciPy's optimum of the raw matrix, then the threshold), births, lost-track expiry, the
 //                 list rebuild with duplicate removal, output rows.  One launch per call, no host round trip: capturable.
+//                 The REID variant (§1c) adds the appearance entries of stages 4 and 6 and the tracks' smoothed features.
 //
 // The list logic lives in LDS (slot fields, list orders); means / covariances stay in global memory, one thread per track
 // for the f64 Kalman work.  tests/bytetrack_ref.py restates every step in the same order (rows are compared bit for bit).
@@ -97,8 +100,129 @@ __device__ inline void byte_assign(int n_rows, int n_cols, const double* cost, b
     __syncthreads();
 }
 
-// GMC: BoT-SORT's camera-motion step 3b from b.gmc (only instantiated with XYWH; without it the code is the plain tracker's)
-template <bool XYWH, bool GMC>
+// §1c: the unit feature of every detection row of the group, so_normalize order (lane l chains k = l, l+64, ...; the xor
+// butterfly of so_sumsq); an all-zero row stays zero (D-17).  Block = 4 rows (one wave each) of one (frame, stream).
+__global__ __launch_bounds__(256) void k_byte_feats(SSByteDev b, const float* __restrict__ feats, const int* __restrict__ ndets)
+{
+    const int s = blockIdx.y, f = blockIdx.z, r = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+    const size_t fs = (size_t)f * b.S + s;
+    const int N = min(max(ndets[fs], 0), b.max_dets);
+    if (r >= N) return;                                           // whole waves
+    const float* in = feats + (fs * SS_MAXD + r) * SS_F;
+    float* out = b.ufeat + (fs * SS_MAXD + r) * SS_F;
+    float v[8], acc = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { v[j] = in[l + 64 * j]; acc = fmaf(v[j], v[j], acc); }
+    const float n = sqrtf(ss_wave_sumsq_reduce(acc));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[l + 64 * j] = n > 0.0f ? v[j] / n : 0.0f;
+}
+
+// §1c get_dists with ReID on rows (track slots rs[r]) x columns (detections cd[k]) of frame fs, stored by byte_cidx:
+//   iou = 1 - IoU;  c = fused(iou) if fuse;  e = 1 if iou > prox, else max(0, 1 - so_dot(smooth, curr)) / 2 -> 1 if > appear;
+//   cost = min(c, e).
+// A masked entry is c (c <= 1, or NaN, which np.minimum keeps), so only the pairs with iou <= prox — overlapping boxes, about
+// one per track — get a dot product.  The entries go by chunks of 256: each thread one entry, the unmasked ones compacted
+// in LDS, then eight lanes per pair run so_dot's eight 64-long fmaf chains (lane = segment) and lane 0 of the eight adds
+// them in segment order.  A dense MFMA matrix (k_cosine_kat's form) would compute the whole rows x columns product for the
+// few unmasked pairs (docs/BYTETRACK.md §3).
+__device__ inline void byte_reid_cost(int nR, int nC, const int* rs, const int* cd, double* cost, const SSByteDev& b,
+                                            size_t sb, size_t fs, ByteLds& m)
+{
+    __shared__ int ae[256];
+    __shared__ double ac[256];
+    const int tid = threadIdx.x, seg = tid & 7, base = (tid & 63) & ~7, n = nR * nC;
+    for (int e0 = 0; e0 < n; e0 += 256) {
+        const int e = e0 + tid;
+        int need = 0;
+        double c = 0.0;
+        if (e < n) {
+            const int r = e / nC, k = e - r * nC, d = cd[k];
+            const double iou = ss_iou_cost(m.tl[rs[r]], m.dtl[d], 2.0);
+            c = b.fuse ? 1.0 - (1.0 - iou) * (double)m.dsc[d] : iou;
+            need = !(iou > b.prox);
+            if (!need) cost[byte_cidx(r, k, nR, nC)] = c;
+        }
+        int pos, nA;
+        block_scan256(need, m.wtot, pos, nA);
+        if (need) { ae[pos] = e; ac[pos] = c; }
+        __syncthreads();
+        for (int j0 = 0; j0 < nA; j0 += 32) {
+            const int j = j0 + (tid >> 3);
+            int r = 0, k = 0;
+            float p = 0.0f;
+            if (j < nA) {
+                r = ae[j] / nC; k = ae[j] - r * nC;
+                const float4* g = reinterpret_cast<const float4*>(b.smooth + (sb + rs[r]) * SS_F + SS_SEG * seg);
+                const float4* q = reinterpret_cast<const float4*>(b.ufeat + (fs * SS_MAXD + cd[k]) * SS_F + SS_SEG * seg);
+#pragma unroll 8
+                for (int i = 0; i < SS_SEG / 4; ++i) {
+                    const float4 x = g[i], y = q[i];
+                    p = fmaf(x.x, y.x, p); p = fmaf(x.y, y.y, p); p = fmaf(x.z, y.z, p); p = fmaf(x.w, y.w, p);
+                }
+            }
+            float tot = __shfl(p, base);
+#pragma unroll
+            for (int i = 1; i < SS_NSEG; ++i) tot = tot + __shfl(p, base + i);
+            if (j < nA && seg == 0) {
+                double a = (double)fmaxf(0.0f, 1.0f - tot) / 2.0;
+                if (a > b.appear) a = 1.0;
+                const double cf = ac[j];
+                cost[byte_cidx(r, k, nR, nC)] = a < cf ? a : cf;
+            }
+        }
+        __syncthreads();                                           // ae / ac: the next chunk's
+    }
+}
+
+// the smoothed features after the frame's Kalman updates (§1c): a birth copies its unit feature; a match of stages 4-6 takes
+// so_ema(smooth, curr, alpha, 1 - alpha) — the EMA, then so_normalize's order.  One wave per slot, in place (a lane reads and
+// writes the same elements); the updated slots are compacted into m.freel (free after the births) and every wave takes two
+// at a time, so that both slots' loads are in flight together.
+__device__ inline void byte_reid_smooth(const SSByteDev& b, size_t sb, size_t fs, int nB, ByteLds& m)
+{
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+    for (int i = w; i < nB; i += 4) {
+        const int slot = m.born[i];
+        const float* cu = b.ufeat + (fs * SS_MAXD + m.det[slot]) * SS_F;
+        float* sm = b.smooth + (sb + slot) * SS_F;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sm[l + 64 * j] = cu[l + 64 * j];
+    }
+    int pos, nU;
+    block_scan256(m.upd[tid] >= 0, m.wtot, pos, nU);
+    if (m.upd[tid] >= 0) m.freel[pos] = tid;
+    __syncthreads();
+    for (int i = 2 * w; i < nU; i += 8) {
+        const int two = i + 1 < nU;
+        float* sm[2];
+        float v[2][8], acc[2] = {0.0f, 0.0f};
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int slot = m.freel[two ? i + u : i];
+            sm[u] = b.smooth + (sb + slot) * SS_F;
+            const float* cu = b.ufeat + (fs * SS_MAXD + m.upd[slot]) * SS_F;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float t1 = b.alpha * sm[u][l + 64 * j];
+                const float t2 = b.one_minus_alpha * cu[l + 64 * j];
+                v[u][j] = t1 + t2;
+                acc[u] = fmaf(v[u][j], v[u][j], acc[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const float n = sqrtf(ss_wave_sumsq_reduce(acc[u]));
+            if (u == 0 || two)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) sm[u][l + 64 * j] = n > 0.0f ? v[u][j] / n : 0.0f;
+        }
+    }
+}
+
+// GMC: BoT-SORT's camera-motion step 3b from b.gmc; REID: §1c's appearance term and smoothed features from b.smooth / b.ufeat
+// (both only instantiated with XYWH; without them the code is the plain tracker's)
+template <bool XYWH, bool GMC, bool REID>
 __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const float* __restrict__ dets, const int* __restrict__ ndets,
                                                     float* __restrict__ out, int* __restrict__ nout)
 {
@@ -198,6 +322,8 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
         {
             const bool glb = nP * nHi > SS_BYTE_COST_CAP;
             double* cost = glb ? spill : m.cost;
+            if constexpr (REID) byte_reid_cost(nP, nHi, m.pool, m.hi, cost, b, sb, fs, m);
+            else
             for (int e = tid; e < nP * nHi; e += 256) {
                 const int r = e / nHi, k = e - r * nHi, d = m.hi[k];
                 double c = ss_iou_cost(m.tl[m.pool[r]], m.dtl[d], 2.0);
@@ -247,6 +373,8 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             __syncthreads();
             const bool glb = nU * nLeft > SS_BYTE_COST_CAP;
             double* cost = glb ? spill : m.cost;
+            if constexpr (REID) byte_reid_cost(nU, nLeft, m.unc, m.left, cost, b, sb, fs, m);
+            else
             for (int e = tid; e < nU * nLeft; e += 256) {
                 const int r = e / nLeft, k = e - r * nLeft, d = m.left[k];
                 double c = ss_iou_cost(m.tl[m.unc[r]], m.dtl[d], 2.0);
@@ -317,6 +445,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             }
         }
         __syncthreads();
+        if constexpr (REID) byte_reid_smooth(b, sb, fs, nB, m);
         // ---- 8. lost tracks past max_time_lost ----
         if (tid < nL) {
             const int slot = m.lost[tid];
@@ -397,9 +526,16 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
 
 size_t ss_byte_lds_bytes() { return sizeof(ByteLds); }
 
-void ss_launch_byte_group(const SSByteDev& b, int F, const float* dets, const int* ndets, float* out, int* nout, hipStream_t st)
+// feats [F][S][MAXD][F] raw detection features, read when ReID is on (b.reid: xywh only, ss_byte_set_reid)
+void ss_launch_byte_group(const SSByteDev& b, int F, const float* dets, const int* ndets, const float* feats, float* out, int* nout,
+                          hipStream_t st)
 {
-    if (b.xywh && b.gmc) hipLaunchKernelGGL((k_byte_group<true, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
-    else if (b.xywh) hipLaunchKernelGGL((k_byte_group<true, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
-    else hipLaunchKernelGGL((k_byte_group<false, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    if (b.reid) {
+        hipLaunchKernelGGL(k_byte_feats, dim3(SS_MAXD / 4, b.S, F), dim3(256), 0, st, b, feats, ndets);
+        if (b.gmc) hipLaunchKernelGGL((k_byte_group<true, true, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+        else hipLaunchKernelGGL((k_byte_group<true, false, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    }
+    else if (b.xywh && b.gmc) hipLaunchKernelGGL((k_byte_group<true, true, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    else if (b.xywh) hipLaunchKernelGGL((k_byte_group<true, false, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    else hipLaunchKernelGGL((k_byte_group<false, false, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
 }

@@ -528,6 +528,12 @@ struct SSByteDev {
     double *mean, *cov;                 // [S][MAXT][8], [S][MAXT][64]
     double* spill;                      // [S][MAXT * MAXD] cost matrices that do not fit the LDS
     const double* gmc;                  // [F][S][8] BoT-SORT GMC warps (ss_byte_set_gmc, xywh only), NULL: off
+    // BoT-SORT's ReID branch (docs/BYTETRACK.md §1c, ss_byte_set_reid; xywh only), allocated when first switched on
+    int reid;
+    float alpha, one_minus_alpha;       // so_ema weights: (float)alpha, (float)(1 - alpha)
+    double prox, appear;                // proximity_thresh (on 1 - IoU), appearance_thresh (on the halved cosine distance)
+    float* smooth;                      // [S][MAXT][F] unit track features by slot
+    float* ufeat;                       // [FMAX][S][MAXD][F] unit detection features of the group (k_byte_feats)
 };
 
 // camera-motion warp m (2x3, full-frame pixels) applied to a track's box (oracle so_camera_update, D-18)

@@ -493,7 +493,8 @@ class TrackerEngine:
 
 class ByteTrackEngine:
     """The BYTE tracker family (csrc/ss_byte.hip, docs/BYTETRACK.md) on the context of a TrackerEngine: the same
-    update_device / update_group / reset / check_errors shape as TrackerEngine, without features.  `engine`: share the
+    update_device / update_group / reset / check_errors shape as TrackerEngine; features only with cfg.with_reid (§1c, BoT-SORT's
+    ReID branch, switched on at construction).  `engine`: share the
     context of an existing TrackerEngine (a pipeline's: its NMS, streams and error words); None: a context of its own."""
 
     def __init__(self, cfg: ByteTrackConfig | None = None, n_streams: int = 1, device: int = 0, engine: TrackerEngine | None = None):
@@ -503,6 +504,10 @@ class ByteTrackEngine:
         self.S, self.device, self.L = self.base.S, self.base.device, self.base.L
         c = _lib.make_byte_config(self.cfg)
         self._ck(self.L.ss_byte_create(self.base.ctx, C.byref(c)))
+        self.reid = bool(self.cfg.with_reid)
+        if self.reid:                               # §1c: BoT-SORT's appearance term (resets the streams)
+            self._ck(self.L.ss_byte_set_reid(self.base.ctx, 1, float(self.cfg.proximity_thresh), float(self.cfg.appearance_thresh),
+                                             float(self.cfg.feat_alpha)))
         self.out = torch.zeros(self.S, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=self.device)
         self.nout = torch.zeros(self.S, dtype=torch.int32, device=self.device)
 
@@ -544,20 +549,42 @@ class ByteTrackEngine:
     def max_group_frames(self) -> int:
         return int(self.L.ss_max_group_frames())
 
+    def _feats(self, feats, rows):
+        if not self.reid:
+            return None
+        if feats is None:
+            raise ValueError("ByteTrackEngine: with_reid needs the detections' features [.., 128, 512] f32")
+        if feats.dtype != torch.float32 or not feats.is_contiguous() or feats.numel() != rows * MAX_DETS * FEAT_DIM:
+            raise ValueError(f"ByteTrackEngine: feats must be contiguous float32 [{rows} x {MAX_DETS} x {FEAT_DIM}]")
+        return feats
+
     def update_device(self, dets, ndets, feats=None, img_hw=None, out=None, nout=None):
-        """All streams, one frame: dets [S,128,6] f32, ndets [S] i32 (device) -> (rows [S,256,8], counts [S]) device tensors,
-        asynchronous.  feats / img_hw are accepted for TrackerEngine's call shape and unused (no appearance, no clipping)."""
+        """All streams, one frame: dets [S,128,6] f32, ndets [S] i32, with ReID feats [S,128,512] f32 (raw, device) ->
+        (rows [S,256,8], counts [S]) device tensors, asynchronous.  img_hw is accepted for TrackerEngine's call shape and
+        unused (no clipping); feats is unused without ReID."""
         out = self.out if out is None else out
         nout = self.nout if nout is None else nout
-        self._ck(self.L.ss_byte_update(self.base.ctx, _ptr(dets), _ptr(ndets), _ptr(out), _ptr(nout)))
-        return out, nout
+        return self.update_group(1, dets, ndets, feats, img_hw, out, nout)
 
     def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout):
-        """A group of n_frames (<= 32) frames of all streams in ONE launch: dets [F,S,128,6] f32, ndets [F,S] i32 -> rows
-        out [F,S,256,8], counts nout [F,S] (device tensors, asynchronous); frames are associated in order.  feats / img_hw
-        unused (TrackerEngine's call shape)."""
-        self._ck(self.L.ss_byte_update_group(self.base.ctx, int(n_frames), _ptr(dets), _ptr(ndets), _ptr(out), _ptr(nout)))
+        """A group of n_frames (<= 32) frames of all streams in ONE launch: dets [F,S,128,6] f32, ndets [F,S] i32, with ReID
+        feats [F,S,128,512] f32 -> rows out [F,S,256,8], counts nout [F,S] (device tensors, asynchronous); frames are
+        associated in order.  img_hw unused (TrackerEngine's call shape), feats unused without ReID."""
+        if self.reid:
+            f = self._feats(feats, int(n_frames) * self.S)
+            self._ck(self.L.ss_byte_update_group_feats(self.base.ctx, int(n_frames), _ptr(dets), _ptr(ndets), _ptr(f), _ptr(out), _ptr(nout)))
+        else:
+            self._ck(self.L.ss_byte_update_group(self.base.ctx, int(n_frames), _ptr(dets), _ptr(ndets), _ptr(out), _ptr(nout)))
         return out, nout
+
+    def features(self, stream: int = 0) -> np.ndarray:
+        """§1c: the unit track features [n,512] f32 of one stream in tracks()' list order (ReID only)."""
+        if not self.reid:
+            raise RuntimeError("ByteTrackEngine.features: with_reid is off")
+        sm = np.zeros((MAX_TRACKS, FEAT_DIM), np.float32)
+        self._ck(self.L.ss_byte_get_features(self.base.ctx, stream, MAX_TRACKS, sm.ctypes.data_as(C.POINTER(C.c_float))))
+        t = self.tracks(stream)
+        return sm[:t["n_tracked"] + t["n_lost"]].copy()
 
     def tracks(self, stream: int = 0) -> dict:
         """The table of one stream in list order (tracked, then lost): track_id, state (1 tracked, 2 lost), activated, mean."""

@@ -28,7 +28,7 @@ EXPORTS = [
     "ss_op32_pointwise", "ss_op32_chains_bands", "ss_op32_chains", "ss_op32_tail", "ss_op32_stem", "ss_op32_stem_u8", "ss_op32_stem_conv1", "ss_op32_head", "ss_op32_set_option", "ss_op32_conv", "ss_op32_conv0", "ss_op32_upcat", "ss_op32_v8_decode", "ss_op32_sppf_pools",
     "ss_mask_assemble", "ss_mask_outline",
     "ss_byte_create", "ss_byte_destroy", "ss_byte_update_group", "ss_byte_update", "ss_byte_reset", "ss_byte_get_tracks",
-    "ss_byte_set_gmc",
+    "ss_byte_set_gmc", "ss_byte_set_reid", "ss_byte_update_group_feats", "ss_byte_get_features",
 ]
 
 
@@ -193,6 +193,9 @@ def load():
     L.ss_byte_reset.argtypes = [vp, i]
     L.ss_byte_get_tracks.argtypes = [vp, i, i, hi, hi, hi, hi, hi, hi, hi, hd]
     L.ss_byte_set_gmc.argtypes = [vp, vp]
+    L.ss_byte_set_reid.argtypes = [vp, i, C.c_double, C.c_double, C.c_double]
+    L.ss_byte_update_group_feats.argtypes = [vp, i, fp, ip, fp, fp, ip]
+    L.ss_byte_get_features.argtypes = [vp, i, i, C.POINTER(C.c_float)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("ss_destroy", "ss_last_error"):

@@ -39,14 +39,17 @@ class FramePipeline:
                  half: bool = True, reid_batch: int = 32, cfg: Optional[StrongSortConfig] = None,
                  dcfg: Optional[DetectConfig] = None, det_source: str = "detector", feat_source: str = "reid",
                  graph: str = "all", debug: bool = False, run_nets: bool = True, seed: int = 0, detect_only_rows: int = 0, cmc: bool = False,
-                 reid_half: Optional[bool] = None, crops_u8: bool = True, tracker: str = "strongsort"):
+                 reid_half: Optional[bool] = None, crops_u8: bool = True, tracker: str = "strongsort", with_reid: bool = False):
         self.cfg, self.dcfg = cfg or StrongSortConfig(), dcfg or DetectConfig()
         self.S, (self.H, self.W) = n_streams, frame_hw
         # tracker = "bytetrack" / "botsort": the BYTE tracker family (csrc/ss_byte.hip) on IoU and scores — no OSNet is built, no
-        # crops are cut, the ReID stages drop out of the graphs; the tracker keeps the NMS rows' order (det_idx)
+        # crops are cut, the ReID stages drop out of the graphs; the tracker keeps the NMS rows' order (det_idx).
+        # with_reid (botsort only): BoT-SORT's ReID branch (docs/BYTETRACK.md §1c) — OSNet, crops and ReID stages stay as for
+        # StrongSORT and the BYTE tracker reads the same features
         from .config import byte_config
-        self.byte_cfg = byte_config(tracker)
+        self.byte_cfg = byte_config(tracker, with_reid)
         self.tracker = tracker
+        self.need_reid = self.byte_cfg is None or self.byte_cfg.with_reid
         if self.byte_cfg is not None and cmc and self.byte_cfg.kalman != "xywh":
             raise ValueError("camera-motion compensation needs tracker 'strongsort' or 'botsort' (ByteTrack has no GMC)")
         self.eng = TrackerEngine(self.cfg, n_streams, device, debug=debug)
@@ -72,7 +75,7 @@ class FramePipeline:
             raise ValueError("reid_batch <= 128")
         # Only the first reid_batch detections of a frame are cropped and embedded: with OSNet features feeding the
         # tracker, NMS keeps at most that many (highest scores first), so no detection reaches it without a feature.
-        self.max_det = min(self.dcfg.max_det, MAX_DETS, reid_batch if (feat_source == "reid" and run_nets and self.byte is None) else MAX_DETS)
+        self.max_det = min(self.dcfg.max_det, MAX_DETS, reid_batch if (feat_source == "reid" and run_nets and self.need_reid) else MAX_DETS)
         # detect_only_rows > 0: a detection-only pipeline (model.predict, yolo_multi_model.py:173) whose NMS keeps up to
         # that many rows (<= 1024, the reference's max_det is 1000) — it never feeds the tracker (128 detections per frame)
         self.det_rows = MAX_DETS
@@ -84,7 +87,7 @@ class FramePipeline:
         self.detector = self.reid = None
         if run_nets:
             self.detector = nets.build_detector(detector, seed).to(dev, self.dtype).to(memory_format=torch.channels_last)
-            if self.byte is None:
+            if self.need_reid:
                 self.reid = nets.build_reid(seed + 1).to(dev, self.reid_dtype).to(memory_format=torch.channels_last)
             self.nc, self.nk = self.detector.nc, self.detector.nk
             self.nm = getattr(self.detector, "nm", 0)           # mask coefficients of a segmentation head (after the keypoints' place)
@@ -105,7 +108,7 @@ class FramePipeline:
         self.proto = torch.zeros(S, self.nm, g.out_h // 4, g.out_w // 4, dtype=self.dtype, device=dev) if self.nm else None
         self.keep = torch.zeros(S, self.det_rows, dtype=torch.int32, device=dev)
         self.ndets = torch.zeros(S, dtype=torch.int32, device=dev)
-        self.crops = torch.zeros(S * self.RB if self.byte is None else 0, 3, 256, 128, dtype=self.crops_dtype,
+        self.crops = torch.zeros(S * self.RB if self.need_reid else 0, 3, 256, 128, dtype=self.crops_dtype,
                                  device=dev).contiguous(memory_format=torch.channels_last)
         self.feats_in = torch.zeros(S, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=dev)
         self.img_hw = torch.tensor([[self.H, self.W]] * S, dtype=torch.int32, device=dev)
@@ -157,7 +160,7 @@ class FramePipeline:
 
     def _reid_impl(self):
         e, S = self.eng, self.S
-        if self.byte is not None:
+        if not self.need_reid:
             return
         if self.run_nets:
             e.crop_norm_batch(self.frames, self.dets6, self.RB, counts=self.ndets, half=self.reid_half, out=self.crops,
@@ -175,7 +178,7 @@ class FramePipeline:
 
     def _track(self):
         if self.byte is not None:
-            self.byte.update_device(self.dets6, self.ndets, out=self.out, nout=self.nout)
+            self.byte.update_device(self.dets6, self.ndets, self.feats_in, out=self.out, nout=self.nout)
             return
         self.eng.update_device(self.dets6, self.ndets, self.feats_in, self.img_hw)
 
@@ -229,7 +232,7 @@ class FramePipeline:
                     # three graphs on the same static buffers: detection | ReID | tracker, so a detection-only call
                     # (model.predict, yolo_multi_model.py:173) replays just the first
                     self.graph = []
-                    for fn in ((self._detect_impl, self._track) if self.byte is not None else (self._detect_impl, self._reid_impl, self._track)):
+                    for fn in ((self._detect_impl, self._track) if not self.need_reid else (self._detect_impl, self._reid_impl, self._track)):
                         gph = torch.cuda.CUDAGraph()
                         with torch.cuda.graph(gph, stream=st):
                             fn()
@@ -302,7 +305,7 @@ class _Bufs:
         self.proto = torch.zeros(S, p.nm, p.geom.out_h // 4, p.geom.out_w // 4, dtype=p.dtype, device=dev) if p.nm else None
         self.keep = torch.zeros(S, MAX_DETS, dtype=torch.int32, device=dev)
         self.ndets = torch.zeros(S, dtype=torch.int32, device=dev)
-        self.crops = torch.zeros(S * p.RB if p.byte is None else 0, 3, 256, 128, dtype=p.crops_dtype,
+        self.crops = torch.zeros(S * p.RB if p.need_reid else 0, 3, 256, 128, dtype=p.crops_dtype,
                                  device=dev).contiguous(memory_format=torch.channels_last)
         self.anchor_gt = torch.zeros(S, p.n_anchors, dtype=torch.int64, device=dev)
         self.gt_feats = torch.zeros(S, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=dev)
@@ -356,9 +359,11 @@ class OverlappedPipeline(FramePipeline):
         self.Sv = self.S * self.F
         # packed ReID batches: the group's valid crops contiguous, the OSNet kernels skip the unused slots of the fixed batch
         # (~28 of 32 slots per frame are used at configs[1]); pack_crops=False: A/B switch
-        self.pack = bool(self.run_nets and pack_crops and self.byte is None)
-        if self.byte is not None:                # BYTE: no ReID stage to cut or balance, no association launch to gate on
-            reid_split, assoc_gate = None, False
+        self.pack = bool(self.run_nets and pack_crops and self.need_reid)
+        if self.byte is not None:                # BYTE: no association launch to gate on; without ReID no ReID stage to cut or balance
+            assoc_gate = False
+            if not self.need_reid:
+                reid_split = None
         self.geom_dev = self.geom_dev[:1].repeat(self.Sv, 1).contiguous()
         self.outs = torch.zeros(self.F, self.S, MAX_TRACKS, 8, dtype=torch.float32, device=self.dev)
         self.nouts = torch.zeros(self.F, self.S, dtype=torch.int32, device=self.dev)

@@ -79,36 +79,61 @@ class BYTETracker:
        returns float32 [M,8]: x1,y1,x2,y2,track_id,class_id,conf,det_idx for every activated tracked track (det_idx = row of
        `dets` matched this frame, always >= 0).  cfg.kalman = "xyah": ByteTrack; "xywh": BoT-SORT without ReID.
        camera_motion=True (xywh only): BoT-SORT's GMC (§1b) with the ECC warp between the previous frame and this one,
-       estimated on the device; `update(dets, frame)` then needs the frame."""
+       estimated on the device; `update(dets, frame)` then needs the frame.
+       cfg.with_reid=True (xywh only): BoT-SORT's ReID branch (§1c).  `update(dets, frame, features)` takes the rows' raw
+       features [N,512], or cuts the crops from `frame` and runs OSNet-x0.25 (reid_weights, loaded as StrongSORT loads them;
+       fp16 selects half activations) when `features` is None."""
 
-    def __init__(self, cfg: Optional[ByteTrackConfig] = None, device: int = 0, camera_motion: bool = False):
+    def __init__(self, cfg: Optional[ByteTrackConfig] = None, device: int = 0, camera_motion: bool = False,
+                 reid_weights: Optional[str] = None, fp16: bool = False, random_init_ok: bool = False, reid_seed: int = 1):
         self.cfg = cfg or ByteTrackConfig()
         if camera_motion and self.cfg.kalman != "xywh":
             raise ValueError("camera_motion needs the xywh (BoT-SORT) filter: ByteTrack has no GMC")
         self.eng = ByteTrackEngine(self.cfg, 1, device)
         self.dev = self.eng.device
         self.camera_motion = bool(camera_motion)
+        self.reid = None
+        if self.cfg.with_reid:
+            self.dtype = torch.float16 if fp16 else torch.float32
+            self._feats = torch.zeros(1, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=self.dev)
+            self.reid = nets.build_reid(reid_seed)           # the same loading policy as StrongSORT's (raise unless random init is asked for)
+            nets.load_weights(self.reid, reid_weights, "OSNet-x0.25 ReID", random_init_ok)
+            self.reid = self.reid.to(self.dev, self.dtype).to(memory_format=torch.channels_last)
         self._dets = torch.zeros(1, MAX_DETS, 6, dtype=torch.float32, device=self.dev)
         self._n = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self._warps = torch.zeros(1, 1, 8, dtype=torch.float64, device=self.dev) if self.camera_motion else None
 
     @torch.no_grad()
-    def update(self, dets, frame=None) -> np.ndarray:
+    def update(self, dets, frame=None, features=None) -> np.ndarray:
         self.eng.use_current_stream()
         dets = torch.as_tensor(dets, dtype=torch.float32).reshape(-1, 6)
         n = dets.shape[0]
         if n > self.cfg.max_dets:
             raise ValueError(f"at most {self.cfg.max_dets} detections per frame (got {n})")
-        if self.camera_motion:
-            if frame is None:
-                raise ValueError("camera_motion=True: update(dets, frame) needs the BGR frame")
+        frame_t = None
+        if frame is not None and (self.camera_motion or (self.cfg.with_reid and features is None)):
             frame_t = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame))
             frame_t = frame_t.to(self.dev, non_blocking=True).contiguous()
+        if self.camera_motion:
+            if frame_t is None:
+                raise ValueError("camera_motion=True: update(dets, frame) needs the BGR frame")
             self.eng.cmc_estimate(frame_t[None], 1, self._warps)
             self.eng.set_cmc(self._warps)
         self._dets[0, :n].copy_(dets, non_blocking=True)
         self._n.fill_(n)
-        out, nout = self.eng.update_device(self._dets, self._n)
+        feats = None
+        if self.cfg.with_reid:
+            feats = self._feats
+            if features is not None:
+                self._feats[0, :n].copy_(torch.as_tensor(features, dtype=torch.float32).reshape(n, FEAT_DIM))
+            elif frame_t is None:
+                raise ValueError("with_reid: update(dets, frame) needs the BGR frame or features [N,512]")
+            elif n:
+                crops = self.eng.base.crop_norm(frame_t, self._dets[0], n, half=self.dtype == torch.float16)
+                self._feats[0, :n].copy_(self.reid(crops.contiguous(memory_format=torch.channels_last)))
+        elif features is not None:
+            raise ValueError("features given, but cfg.with_reid is off")
+        out, nout = self.eng.update_device(self._dets, self._n, feats)
         torch.cuda.synchronize(self.dev)
         self.eng.check_errors()
         return out[0, : int(nout[0])].cpu().numpy()

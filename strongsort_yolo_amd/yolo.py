@@ -237,7 +237,7 @@ class YOLO:
 
     def __init__(self, weights: str = "yolov8n.pt", seed: int = 0, random_init_ok: bool = False, reid_batch: int = 128,
                  camera_motion: bool = False, reid_weights: Optional[str] = None, reid_fp32: bool = True, half: bool = True,
-                 device_masks: bool = False, tracker_type: str = "strongsort"):
+                 device_masks: bool = False, tracker_type: str = "strongsort", with_reid: bool = False):
         """reid_fp32 (default since round 6): ReID crops + OSNet-x0.25 in fp32 on the fp32 kernels — appearance distances within 1e-4 of a CPU fp32
         network, which f16 activations miss by 330x (reid_fp32=False: the f16 throughput mode, ~1.2x the per-frame rate, 1.7x the stream rate).
         half=False: the DETECTOR in fp32 as well (the reference's own precision: it passes no half=, yolo_multi_model.py:41) on the
@@ -251,9 +251,12 @@ class YOLO:
         overrides['conf'].
         camera_motion: ECC camera-motion warps estimated on the device beside the detector (N4). StrongSORT moves its track
         boxes by them (D-18); "botsort" applies them as BoT-SORT's GMC to every track's Kalman mean and covariance
-        (docs/BYTETRACK.md §1b) in track() and track_stream(). "bytetrack" has no GMC: a ValueError."""
-        byte_config(tracker_type)                 # ValueError on anything else
+        (docs/BYTETRACK.md §1b) in track() and track_stream(). "bytetrack" has no GMC: a ValueError.
+        with_reid ("botsort" only, else a ValueError): BoT-SORT's ReID branch (docs/BYTETRACK.md §1c) — OSNet-x0.25 features of
+        every tracked row (reid_weights, reid_fp32 and half as for StrongSORT) add an appearance term to the IoU association."""
+        byte_config(tracker_type, with_reid)      # ValueError on anything else
         self.tracker_type = tracker_type
+        self.with_reid = bool(with_reid)
         self._byte = tracker_type != "strongsort"
         if tracker_type == "bytetrack" and camera_motion:
             raise ValueError("camera_motion needs tracker_type 'strongsort' or 'botsort' (ByteTrack has no GMC, G-05)")
@@ -282,6 +285,8 @@ class YOLO:
             self._pipe_kw["half"] = False
         if self._byte:
             self._pipe_kw["tracker"] = tracker_type
+            if self.with_reid:
+                self._pipe_kw["with_reid"] = True
         self.device_masks = bool(device_masks)
         self._fill = None
         self._frame_index = 0

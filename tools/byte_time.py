@@ -10,6 +10,10 @@
                               without, called alternately; each group also runs ss_cmc_estimate on 32 panning 1280x720 frames
                               per stream (k_gray_small + k_ecc).  rates mode: botsort with and without camera_motion, one leg
                               per fresh process, the legs interleaved (--rounds each).
+  --reid                      BoT-SORT's ReID branch (docs/BYTETRACK.md §1c).  kernel mode: two xywh engines on the same streams
+                              with per-identity raw features (tests/test_gpu_botsort_reid.reid_stream), one with ReID (k_byte_feats +
+                              the REID variant of k_byte_group) and one without, called alternately.  rates mode: botsort,
+                              botsort with ReID and StrongSORT (fp32 ReID), one leg per fresh process, interleaved (--rounds each).
 """
 import argparse
 import json
@@ -120,6 +124,47 @@ def kernel(S, groups, warmup):
             "us_per_group_min": float(np.min(ms)) * 1e3, "note": "host event pair around one launch (includes launch latency)"}
 
 
+def kernel_reid(S, groups, warmup):
+    from strongsort_yolo_amd.config import ByteTrackConfig
+    from strongsort_yolo_amd.engine import ByteTrackEngine
+    from tests.test_gpu_botsort_reid import reid_stream
+    G = 32
+    n = (groups + warmup) * G
+    streams = [reid_stream(100 + s, n) for s in range(S)]
+    dev = torch.device("cuda", 0)
+    hd, hn = np.zeros((n, S, 128, 6), np.float32), np.zeros((n, S), np.int32)
+    hf = np.zeros((n, S, 128, 512), np.float32)
+    for f in range(n):
+        for s in range(S):
+            d, ft = streams[s][f]
+            hd[f, s, :len(d)], hf[f, s, :len(d)], hn[f, s] = d, ft, len(d)
+    dets, nd, feats = torch.from_numpy(hd).to(dev), torch.from_numpy(hn).to(dev), torch.from_numpy(hf).to(dev)
+    out = torch.zeros(G, S, 256, 8, device=dev)
+    nout = torch.zeros(G, S, dtype=torch.int32, device=dev)
+    plain = ByteTrackEngine(ByteTrackConfig(kalman="xywh"), S, 0)
+    reid = ByteTrackEngine(ByteTrackConfig(kalman="xywh", with_reid=True), S, 0)
+    plain.use_current_stream()
+    reid.use_current_stream()
+    ms = {"plain": [], "reid": []}
+    for g in range(groups + warmup):
+        sl = slice(g * G, (g + 1) * G)
+        for leg, eng in (("plain", plain), ("reid", reid)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            eng.update_group(G, dets[sl], nd[sl], feats[sl], None, out, nout)
+            b.record()
+            b.synchronize()
+            if g >= warmup:
+                ms[leg].append(a.elapsed_time(b))
+    plain.check_errors()
+    reid.check_errors()
+    med = {k: float(np.median(v)) * 1e3 for k, v in ms.items()}
+    return {"mode": "kernel_reid", "streams": S, "group_frames": G, "groups": groups, "dets_per_frame": float(hn.mean()),
+            "plain_us_per_group_median": med["plain"], "reid_us_per_group_median": med["reid"], "reid_over_plain": med["reid"] / med["plain"],
+            "note": "host event pair around one call (reid: k_byte_feats + k_byte_group, includes launch latency); kernel times: "
+                    "rocprofv3 --kernel-trace --stats"}
+
+
 def rates(n_frames, batch):
     os.environ["SS_RANDOM_INIT"] = "1"
     from strongsort_yolo_amd.synth import make_stream
@@ -148,13 +193,18 @@ def rates(n_frames, batch):
 
 
 def rate_leg(leg, n_frames, batch):
-    """One leg in this process: botsort with (leg "botsort_cmc") or without camera_motion, 1280x720 frames panning 3 px a frame."""
+    """One leg in this process: botsort with (leg "botsort_cmc") or without camera_motion, botsort with ReID ("botsort_reid"),
+    StrongSORT with fp32 ReID ("strongsort"); 1280x720 frames panning 3 px a frame."""
     os.environ["SS_RANDOM_INIT"] = "1"
     from strongsort_yolo_amd.yolo import YOLO
     pan = _pan_frames(16, 1)
     frames = [pan[k].copy() for k in range(16)]
     frames += frames[::-1]                                  # back and forth: the sequence can repeat without a jump
-    m = YOLO("yolov8n.pt", random_init_ok=True, tracker_type="botsort", camera_motion=leg == "botsort_cmc")
+    if leg == "strongsort":
+        m = YOLO("yolov8n.pt", random_init_ok=True)
+    else:
+        m = YOLO("yolov8n.pt", random_init_ok=True, tracker_type="botsort", camera_motion=leg == "botsort_cmc",
+                 with_reid=leg == "botsort_reid")
     for k in range(10):
         m.track(frames[k % 32], persist=True)
     torch.cuda.synchronize()
@@ -173,17 +223,17 @@ def rate_leg(leg, n_frames, batch):
     return res
 
 
-def rates_gmc(n_frames, batch, rounds):
+def rates_legs(n_frames, batch, rounds, names, mode):
     import subprocess
-    legs = {"botsort": [], "botsort_cmc": []}
+    legs = {k: [] for k in names}
     for r in range(rounds):
-        for leg in (("botsort", "botsort_cmc") if r % 2 == 0 else ("botsort_cmc", "botsort")):
+        for leg in (names if r % 2 == 0 else names[::-1]):
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", "rates", "--leg", leg, "--frames", str(n_frames),
                                 "--batch", str(batch)], capture_output=True, text=True, timeout=900)
             if p.returncode != 0:
                 raise RuntimeError(f"leg {leg} failed ({p.returncode}): {p.stderr[-2000:]}")
             legs[leg].append(json.loads(p.stdout.strip().splitlines()[-1]))
-    res = {"mode": "rates_gmc", "weights": "yolov8n (seeded random init)", "frame": "1280x720", "batch": batch, "rounds": rounds}
+    res = {"mode": mode, "weights": "yolov8n (seeded random init)", "frame": "1280x720", "batch": batch, "rounds": rounds}
     for leg, rs in legs.items():
         for k in ("track_calls_per_s", "track_stream_frames_per_s"):
             res[f"{leg}_{k}_median"] = float(np.median([r[k] for r in rs]))
@@ -201,12 +251,17 @@ if __name__ == "__main__":
     p.add_argument("--batch", type=int, default=32)
     p.add_argument("--gmc", action="store_true", help="BoT-SORT GMC legs (see the module docstring)")
     p.add_argument("--rounds", type=int, default=3, help="rates --gmc: processes per leg")
-    p.add_argument("--leg", choices=("botsort", "botsort_cmc"), default=None, help=argparse.SUPPRESS)
+    p.add_argument("--reid", action="store_true", help="BoT-SORT ReID legs (see the module docstring)")
+    p.add_argument("--leg", choices=("botsort", "botsort_cmc", "botsort_reid", "strongsort"), default=None, help=argparse.SUPPRESS)
     a = p.parse_args()
     if a.leg is not None:
         r = rate_leg(a.leg, a.frames, a.batch)
     elif a.mode == "kernel":
-        r = kernel_gmc(a.streams, a.groups, a.warmup) if a.gmc else kernel(a.streams, a.groups, a.warmup)
+        r = kernel_reid(a.streams, a.groups, a.warmup) if a.reid else kernel_gmc(a.streams, a.groups, a.warmup) if a.gmc else kernel(a.streams, a.groups, a.warmup)
+    elif a.reid:
+        r = rates_legs(a.frames, a.batch, a.rounds, ("botsort", "botsort_reid", "strongsort"), "rates_reid")
+    elif a.gmc:
+        r = rates_legs(a.frames, a.batch, a.rounds, ("botsort", "botsort_cmc"), "rates_gmc")
     else:
-        r = rates_gmc(a.frames, a.batch, a.rounds) if a.gmc else rates(a.frames, a.batch)
+        r = rates(a.frames, a.batch)
     print(json.dumps(r))
