@@ -252,6 +252,21 @@ int ss_byte_update_group_feats(ss_ctx* ctx, int n_frames, const float* d_dets, c
                                float* d_out, int* d_nout);
 /* Synchronous: the unit track features [n][512] of one stream in ss_byte_get_tracks' list order (after ss_byte_set_reid). */
 int ss_byte_get_features(ss_ctx* ctx, int stream, int cap, float* smooth);
+/* BoT-SORT's `model: auto` ReID features (docs/BYTETRACK.md §1d): the raw features of kept detections read from the detector's
+ * own head inputs.  maps[3]: the levels P3, P4, P5 of n_img images (f16 if half, else f32), channel stride 1, element (i, c, y, x)
+ * at data + i*img_stride + y*row_stride + x*pix_stride + c (strides in elements; a channel slice of a wider map is fine).
+ * d_keep [n_img][keep_stride] (>= SS_MAX_DETS): NMS anchor indices (level by level, row-major inside a level), d_counts [n_img].
+ * d_out [n_img][SS_MAX_DETS][512] f32: for r < min(count, SS_MAX_DETS), columns j < s hold the mean of channels [j*g, (j+1)*g)
+ * of every level (g = channels / s; f32 sum in channel order, then / g) and columns s..511 zeros; rows past the count are not
+ * written.  1 <= s <= 512 and channels % s == 0 on every level.  Asynchronous on the context's stream, capturable; every
+ * argument is checked first (SS_ERR_INVALID without touching the device). */
+typedef struct ss_native_map {
+    const void* data;
+    long long img_stride, row_stride, pix_stride;
+    int channels, height, width;
+} ss_native_map;
+int ss_native_feats(ss_ctx* ctx, int n_img, int half, const ss_native_map* maps, int s, const int* d_keep, long long keep_stride,
+                    const int* d_counts, float* d_out);
 /* Synchronous: the table of one stream in list order (tracked list, then lost list); any array may be NULL.
  * state 1 tracked, 2 lost; mean [n][8] (xyah or xywh state). */
 int ss_byte_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracked, int* n_lost, int* next_id, int* frame_id,

@@ -107,3 +107,18 @@ def byte_config(tracker_type: str, with_reid: bool = False):
     if tracker_type == "strongsort":
         return None
     return ByteTrackConfig(kalman="xywh" if tracker_type == "botsort" else "xyah", with_reid=bool(with_reid))
+
+
+# BoT-SORT's ReID model (docs/BYTETRACK.md §1d): "osnet" — OSNet-x0.25 on the detections' crops (§1c, the default); "auto" —
+# Ultralytics' `model: auto`, the detections' features read from the detector's own head inputs (no second network or weights file)
+REID_MODELS = ("osnet", "auto")
+
+
+def check_reid_model(reid_model: str, with_reid: bool, reid_weights=None) -> str:
+    if reid_model not in REID_MODELS:
+        raise ValueError(f"reid_model must be one of {REID_MODELS}, not {reid_model!r}")
+    if reid_model == "auto" and not with_reid:
+        raise ValueError("reid_model='auto' is a model for BoT-SORT's ReID branch: it needs with_reid=True (tracker_type 'botsort')")
+    if reid_model == "auto" and reid_weights:
+        raise ValueError("reid_model='auto' reads the detector's own features: reid_weights (OSNet) does not apply")
+    return reid_model

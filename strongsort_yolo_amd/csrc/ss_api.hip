@@ -44,6 +44,8 @@ void ss_launch_mask_outline(const uint32_t*, long long, const int*, int, int, in
                             long long, int*, int, hipStream_t);
 extern "C" void ss_step_kernel_attr();
 void ss_launch_byte_group(const SSByteDev&, int, const float*, const int*, const float*, float*, int*, hipStream_t);
+void ss_launch_native_feats(int, int, const void* const*, const long long*, const long long*, const long long*, const int*, const int*,
+                            const int*, int, const int*, long long, const int*, float*, hipStream_t);
 
 static std::string g_last_error;
 
@@ -1189,6 +1191,36 @@ extern "C" int ss_byte_set_reid(ss_ctx* c, int on, double proximity_thresh, doub
     b.prox = proximity_thresh; b.appear = appearance_thresh;
     b.alpha = (float)alpha; b.one_minus_alpha = (float)(1.0 - alpha);
     return ss_byte_reset(c, -1);
+}
+
+// §1d: BoT-SORT's `model: auto` features of the kept rows from the detector's head inputs (ss_native.hip k_native_feats).  Every
+// argument is checked before the device is touched; one launch on the context's stream (capturable).
+extern "C" int ss_native_feats(ss_ctx* c, int n_img, int half, const ss_native_map* maps, int s, const int* d_keep, long long keep_stride,
+                               const int* d_counts, float* d_out)
+{
+    if (!c || !maps || !d_keep || !d_counts || !d_out) return fail(c, SS_ERR_INVALID, "ss_native_feats: null argument");
+    if (n_img < 1 || n_img > 65535 || (half != 0 && half != 1) || s < 1 || s > SS_F || keep_stride < SS_MAXD)
+        return fail(c, SS_ERR_INVALID, "ss_native_feats: 1 <= n_img <= 65535, half 0 / 1, 1 <= s <= 512, keep_stride >= 128");
+    const void* p[3];
+    long long is[3], rs[3], ps[3];
+    int ch[3], h[3], w[3];
+    long long anchors = 0;
+    const size_t esz = half ? 2 : 4;
+    for (int l = 0; l < 3; ++l) {
+        const ss_native_map& m = maps[l];
+        p[l] = m.data; is[l] = m.img_stride; rs[l] = m.row_stride; ps[l] = m.pix_stride;
+        ch[l] = m.channels; h[l] = m.height; w[l] = m.width;
+        if (!m.data || ((uintptr_t)m.data % esz) != 0) return fail(c, SS_ERR_INVALID, "ss_native_feats: a map is NULL or misaligned");
+        if (m.channels < s || m.channels % s != 0) return fail(c, SS_ERR_INVALID, "ss_native_feats: every level's channels must be a multiple of s");
+        if (m.height < 1 || m.width < 1 || m.pix_stride < m.channels || m.row_stride < (long long)m.width * m.pix_stride
+            || (n_img > 1 && m.img_stride < (long long)m.height * m.row_stride))
+            return fail(c, SS_ERR_INVALID, "ss_native_feats: bad map shape or strides (channel stride 1, maps must not overlap)");
+        anchors += (long long)m.height * m.width;
+    }
+    if (anchors > 0x7fffffffLL) return fail(c, SS_ERR_INVALID, "ss_native_feats: too many anchors");
+    ss_launch_native_feats(n_img, half, p, is, rs, ps, ch, h, w, s, d_keep, keep_stride, d_counts, d_out, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
 }
 
 // Synchronous: the smoothed features [n][512] of one stream in ss_byte_get_tracks' list order.

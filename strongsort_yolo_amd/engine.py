@@ -426,6 +426,33 @@ class TrackerEngine:
         self._ck(self.L.ss_unpack_feats(self.ctx, _ptr(emb), int(emb.dtype == torch.float16), _ptr(offsets), _ptr(counts),
                                         feats.shape[0], n, _ptr(feats), feats.stride(0)))
 
+    def native_feats(self, maps, keep: torch.Tensor, counts: torch.Tensor, out: torch.Tensor, s: int | None = None):
+        """docs/BYTETRACK.md §1d (csrc/ss_native.hip k_native_feats): BoT-SORT's `model: auto` raw features of the kept rows from the
+        detector's head inputs.  maps: the three levels [B, C_l, H_l, W_l], all f16 or all f32 (any strides; a map whose channel
+        stride is not 1 is copied channels-last first); keep [B, >=128] int32 anchor indices, counts [B] int32 -> out [B, 128, 512]
+        f32: rows r < count hold the s = min(C_l) group means, then zeros.  Asynchronous on the engine's stream (capturable when
+        no copy is needed)."""
+        if len(maps) != 3:
+            raise ValueError("native_feats: three head inputs (P3, P4, P5)")
+        dt = maps[0].dtype
+        if dt not in (torch.float16, torch.float32) or any(m.dtype != dt or m.dim() != 4 for m in maps):
+            raise ValueError("native_feats: the maps must all be float16 or all float32 [B, C, H, W]")
+        B = maps[0].shape[0]
+        if any(m.shape[0] != B for m in maps) or keep.dtype != torch.int32 or counts.dtype != torch.int32:
+            raise ValueError("native_feats: maps of one batch, int32 keep / counts")
+        if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (B, MAX_DETS, FEAT_DIM):
+            raise ValueError(f"native_feats: out must be contiguous float32 [{B}, {MAX_DETS}, {FEAT_DIM}]")
+        if keep.dim() != 2 or keep.shape[0] != B or keep.stride(1) != 1 or counts.numel() != B or not counts.is_contiguous():
+            raise ValueError("native_feats: keep [B, >=128] with unit column stride, counts [B]")
+        maps = [m if m.stride(1) == 1 else m.contiguous(memory_format=torch.channels_last) for m in maps]
+        s = min(m.shape[1] for m in maps) if s is None else int(s)
+        desc = (_lib.ss_native_map * 3)()
+        for d, m in zip(desc, maps):
+            d.data, d.img_stride, d.row_stride, d.pix_stride = m.data_ptr(), m.stride(0), m.stride(2), m.stride(3)
+            d.channels, d.height, d.width = m.shape[1], m.shape[2], m.shape[3]
+        self._ck(self.L.ss_native_feats(self.ctx, B, int(dt == torch.float16), desc, s, _ptr(keep), keep.stride(0), _ptr(counts), _ptr(out)))
+        return out
+
     def pack_results(self, n_dets: torch.Tensor, dets: torch.Tensor, n_out, out, dst: torch.Tensor):
         """One frame's counts, detection rows and track rows into `dst` (float32, device or PINNED host memory) on the engine's stream:
         dst[0:2] = the two counts as int32 bits, then dets rows, then (from 2 + dets.numel()) track rows (csrc ss_pack_results)."""

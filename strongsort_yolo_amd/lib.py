@@ -29,6 +29,7 @@ EXPORTS = [
     "ss_mask_assemble", "ss_mask_outline",
     "ss_byte_create", "ss_byte_destroy", "ss_byte_update_group", "ss_byte_update", "ss_byte_reset", "ss_byte_get_tracks",
     "ss_byte_set_gmc", "ss_byte_set_reid", "ss_byte_update_group_feats", "ss_byte_get_features",
+    "ss_native_feats",
 ]
 
 
@@ -60,6 +61,11 @@ class ss_byte_config(C.Structure):              # mirrors `typedef struct ss_byt
 class ss_conv_desc(C.Structure):                 # mirrors `typedef struct ss_conv_desc`
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int), ("H", C.c_int),
                 ("W", C.c_int), ("Cin", C.c_int), ("N", C.c_int), ("ksize", C.c_int), ("stride", C.c_int), ("act", C.c_int)]
+
+
+class ss_native_map(C.Structure):                # mirrors `typedef struct ss_native_map`
+    _fields_ = [("data", C.c_void_p), ("img_stride", C.c_longlong), ("row_stride", C.c_longlong), ("pix_stride", C.c_longlong),
+                ("channels", C.c_int), ("height", C.c_int), ("width", C.c_int)]
 
 
 def build(force: bool = False) -> str:
@@ -196,6 +202,7 @@ def load():
     L.ss_byte_set_reid.argtypes = [vp, i, C.c_double, C.c_double, C.c_double]
     L.ss_byte_update_group_feats.argtypes = [vp, i, fp, ip, fp, fp, ip]
     L.ss_byte_get_features.argtypes = [vp, i, i, C.POINTER(C.c_float)]
+    L.ss_native_feats.argtypes = [vp, i, i, C.POINTER(ss_native_map), i, ip, ll, ip, fp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("ss_destroy", "ss_last_error"):

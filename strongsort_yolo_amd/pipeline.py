@@ -39,17 +39,23 @@ class FramePipeline:
                  half: bool = True, reid_batch: int = 32, cfg: Optional[StrongSortConfig] = None,
                  dcfg: Optional[DetectConfig] = None, det_source: str = "detector", feat_source: str = "reid",
                  graph: str = "all", debug: bool = False, run_nets: bool = True, seed: int = 0, detect_only_rows: int = 0, cmc: bool = False,
-                 reid_half: Optional[bool] = None, crops_u8: bool = True, tracker: str = "strongsort", with_reid: bool = False):
+                 reid_half: Optional[bool] = None, crops_u8: bool = True, tracker: str = "strongsort", with_reid: bool = False,
+                 reid_model: str = "osnet"):
         self.cfg, self.dcfg = cfg or StrongSortConfig(), dcfg or DetectConfig()
         self.S, (self.H, self.W) = n_streams, frame_hw
         # tracker = "bytetrack" / "botsort": the BYTE tracker family (csrc/ss_byte.hip) on IoU and scores — no OSNet is built, no
         # crops are cut, the ReID stages drop out of the graphs; the tracker keeps the NMS rows' order (det_idx).
         # with_reid (botsort only): BoT-SORT's ReID branch (docs/BYTETRACK.md §1c) — OSNet, crops and ReID stages stay as for
-        # StrongSORT and the BYTE tracker reads the same features
-        from .config import byte_config
+        # StrongSORT and the BYTE tracker reads the same features.
+        # reid_model = "auto" (with_reid only): Ultralytics' `model: auto` (docs/BYTETRACK.md §1d) — no OSNet is built, no crops are
+        # cut; one launch after NMS reads the kept rows' features from the detector's own head inputs (a forward pre-hook on
+        # detector.detect keeps them until that launch is enqueued)
+        from .config import byte_config, check_reid_model
         self.byte_cfg = byte_config(tracker, with_reid)
+        self.reid_model = check_reid_model(reid_model, with_reid)
         self.tracker = tracker
-        self.need_reid = self.byte_cfg is None or self.byte_cfg.with_reid
+        self.native = self.reid_model == "auto" and not detect_only_rows
+        self.need_reid = self.byte_cfg is None or (self.byte_cfg.with_reid and self.reid_model == "osnet")
         if self.byte_cfg is not None and cmc and self.byte_cfg.kalman != "xywh":
             raise ValueError("camera-motion compensation needs tracker 'strongsort' or 'botsort' (ByteTrack has no GMC)")
         self.eng = TrackerEngine(self.cfg, n_streams, device, debug=debug)
@@ -91,6 +97,8 @@ class FramePipeline:
                 self.reid = nets.build_reid(seed + 1).to(dev, self.reid_dtype).to(memory_format=torch.channels_last)
             self.nc, self.nk = self.detector.nc, self.detector.nk
             self.nm = getattr(self.detector, "nm", 0)           # mask coefficients of a segmentation head (after the keypoints' place)
+            if self.native:
+                self.detector.detect.register_forward_pre_hook(self._take_head_inputs)
         else:
             self.nc, self.nk, self.nm = 80, 0, 0
         self.nx = self.nk + self.nm                             # extra columns NMS carries along with every kept row
@@ -115,6 +123,7 @@ class FramePipeline:
         self.out, self.nout = self.eng.out, self.eng.nout
         self.anchor_gt = torch.zeros(S, self.n_anchors, dtype=torch.int64, device=dev)
         self.gt_feats = torch.zeros(S, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=dev)
+        self._maps = None                   # reid_model "auto": the head inputs of the detector call in flight
         self.graph = None
         self.graph_all = None
         self.graph_mode = graph
@@ -143,6 +152,13 @@ class FramePipeline:
                     count=self.ndets, max_det=self.max_det)
         if self.nx:
             self.dets6.copy_(self.dets[:, :, :6])
+        maps, self._maps = self._maps, None
+        if self.native and self.run_nets and self.feat_source == "reid":
+            e.native_feats(maps, self.keep, self.ndets, self.feats_in)
+
+    def _take_head_inputs(self, module, args):
+        """Forward pre-hook on detector.detect (reid_model "auto"): its input list [P3, P4, P5], as Ultralytics' hook keeps it."""
+        self._maps = list(args[0])
 
     def _decode_into(self, buf):
         """The head's decode launch writes the NMS input in place (fused.decode_into) when the detector feeds the NMS."""
@@ -160,9 +176,9 @@ class FramePipeline:
 
     def _reid_impl(self):
         e, S = self.eng, self.S
-        if not self.need_reid:
+        if not (self.need_reid or self.native):
             return
-        if self.run_nets:
+        if self.run_nets and self.reid is not None:
             e.crop_norm_batch(self.frames, self.dets6, self.RB, counts=self.ndets, half=self.reid_half, out=self.crops,
                               channels_last=True)
             emb = self.reid(self.crops)                         # [S*RB, 512]
@@ -485,6 +501,7 @@ class OverlappedPipeline(FramePipeline):
     def _s_head(self, b):
         with self._decode_into(b.pred_in):
             pred = self._pred(self.detector.forward_head(*b.pyr), b.proto)
+        self._hold_maps(b)
         if self.keep_net_outputs:
             b.head_out = pred
         if self.det_source == "detector" and pred.data_ptr() != b.pred_in.data_ptr():
@@ -495,10 +512,18 @@ class OverlappedPipeline(FramePipeline):
             self._letterbox(b)
             with self._decode_into(b.pred_in):
                 pred = self._pred(self.detector(b.lb), b.proto)
+            self._hold_maps(b)
             if self.keep_net_outputs:
                 b.head_out = pred
             if self.det_source == "detector" and pred.data_ptr() != b.pred_in.data_ptr():
                 b.pred_in.copy_(pred)
+
+    def _hold_maps(self, b):
+        """reid_model "auto": the head inputs stay referenced by the buffer set until the NMS stage's launch reads them.  No copy
+        across the stage boundary (as b.mid in _s_front_split): the maps live in this graph's private pool, keep their
+        addresses over replays, and the NMS stage's graph (captured after this one, for the same buffer set) reads them there."""
+        if self.native:
+            b.maps, self._maps = self._maps, None
 
     def _nms_crop(self, b):
         e = self.eng                       # one launch set over all S*F virtual streams
@@ -506,6 +531,8 @@ class OverlappedPipeline(FramePipeline):
                     count=b.ndets, max_det=self.max_det)
         if self.nx:
             b.dets6.copy_(b.dets[:, :, :6])
+        if self.native and self.run_nets and self.feat_source == "reid":
+            e.native_feats(b.maps, b.keep, b.ndets, b.feats_v)
         if self.run_nets and self.reid is not None:
             if self.pack:        # the group's valid crops contiguous; the ReID kernels skip the rest of the fixed-size batch
                 e.crop_norm_packed(b.frames, b.dets6, self.RB, b.ndets, b.crop_off, b.crops, half=self.reid_half)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import nets
-from .config import StrongSortConfig, ByteTrackConfig
+from .config import StrongSortConfig, ByteTrackConfig, check_reid_model
 from .engine import TrackerEngine, ByteTrackEngine
 from .lib import MAX_DETS, FEAT_DIM
 
@@ -81,12 +81,15 @@ class BYTETracker:
        camera_motion=True (xywh only): BoT-SORT's GMC (§1b) with the ECC warp between the previous frame and this one,
        estimated on the device; `update(dets, frame)` then needs the frame.
        cfg.with_reid=True (xywh only): BoT-SORT's ReID branch (§1c).  `update(dets, frame, features)` takes the rows' raw
-       features [N,512], or cuts the crops from `frame` and runs OSNet-x0.25 (reid_weights, loaded as StrongSORT loads them;
-       fp16 selects half activations) when `features` is None."""
+       features [N,k] (k <= 512, zero-padded to 512: the §1d features of a `model: auto` detector have k = min(C_l)), or cuts
+       the crops from `frame` and runs OSNet-x0.25 (reid_weights, loaded as StrongSORT loads them; fp16 selects half
+       activations) when `features` is None.  reid_model="auto" (§1d): no OSNet is built; update needs `features`."""
 
     def __init__(self, cfg: Optional[ByteTrackConfig] = None, device: int = 0, camera_motion: bool = False,
-                 reid_weights: Optional[str] = None, fp16: bool = False, random_init_ok: bool = False, reid_seed: int = 1):
+                 reid_weights: Optional[str] = None, fp16: bool = False, random_init_ok: bool = False, reid_seed: int = 1,
+                 reid_model: str = "osnet"):
         self.cfg = cfg or ByteTrackConfig()
+        self.reid_model = check_reid_model(reid_model, self.cfg.with_reid, reid_weights)
         if camera_motion and self.cfg.kalman != "xywh":
             raise ValueError("camera_motion needs the xywh (BoT-SORT) filter: ByteTrack has no GMC")
         self.eng = ByteTrackEngine(self.cfg, 1, device)
@@ -96,6 +99,7 @@ class BYTETracker:
         if self.cfg.with_reid:
             self.dtype = torch.float16 if fp16 else torch.float32
             self._feats = torch.zeros(1, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=self.dev)
+        if self.cfg.with_reid and self.reid_model == "osnet":
             self.reid = nets.build_reid(reid_seed)           # the same loading policy as StrongSORT's (raise unless random init is asked for)
             nets.load_weights(self.reid, reid_weights, "OSNet-x0.25 ReID", random_init_ok)
             self.reid = self.reid.to(self.dev, self.dtype).to(memory_format=torch.channels_last)
@@ -125,7 +129,15 @@ class BYTETracker:
         if self.cfg.with_reid:
             feats = self._feats
             if features is not None:
-                self._feats[0, :n].copy_(torch.as_tensor(features, dtype=torch.float32).reshape(n, FEAT_DIM))
+                ft = torch.as_tensor(features, dtype=torch.float32)
+                ft = ft.reshape(n, -1) if n else ft.reshape(0, ft.shape[-1] if ft.dim() else 0)
+                k = ft.shape[1]
+                if k > FEAT_DIM:
+                    raise ValueError(f"features [N,k]: k <= {FEAT_DIM} (got {k})")
+                self._feats[0, :n, :k].copy_(ft)
+                self._feats[0, :n, k:].zero_()                          # §1d: a shorter vector is zero-padded to 512
+            elif self.reid is None:
+                raise ValueError("reid_model='auto': update(dets, frame, features) needs the rows' features [N,k]")
             elif frame_t is None:
                 raise ValueError("with_reid: update(dets, frame) needs the BGR frame or features [N,512]")
             elif n:

@@ -18,7 +18,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .config import DetectConfig, StrongSortConfig, byte_config
+from .config import DetectConfig, StrongSortConfig, byte_config, check_reid_model
 
 COCO_NAMES = ("person bicycle car motorcycle airplane bus train truck boat traffic_light fire_hydrant stop_sign "
               "parking_meter bench bird cat dog horse sheep cow elephant bear zebra giraffe backpack umbrella handbag tie "
@@ -237,7 +237,7 @@ class YOLO:
 
     def __init__(self, weights: str = "yolov8n.pt", seed: int = 0, random_init_ok: bool = False, reid_batch: int = 128,
                  camera_motion: bool = False, reid_weights: Optional[str] = None, reid_fp32: bool = True, half: bool = True,
-                 device_masks: bool = False, tracker_type: str = "strongsort", with_reid: bool = False):
+                 device_masks: bool = False, tracker_type: str = "strongsort", with_reid: bool = False, reid_model: str = "osnet"):
         """reid_fp32 (default since round 6): ReID crops + OSNet-x0.25 in fp32 on the fp32 kernels — appearance distances within 1e-4 of a CPU fp32
         network, which f16 activations miss by 330x (reid_fp32=False: the f16 throughput mode, ~1.2x the per-frame rate, 1.7x the stream rate).
         half=False: the DETECTOR in fp32 as well (the reference's own precision: it passes no half=, yolo_multi_model.py:41) on the
@@ -253,8 +253,13 @@ class YOLO:
         boxes by them (D-18); "botsort" applies them as BoT-SORT's GMC to every track's Kalman mean and covariance
         (docs/BYTETRACK.md §1b) in track() and track_stream(). "bytetrack" has no GMC: a ValueError.
         with_reid ("botsort" only, else a ValueError): BoT-SORT's ReID branch (docs/BYTETRACK.md §1c) — OSNet-x0.25 features of
-        every tracked row (reid_weights, reid_fp32 and half as for StrongSORT) add an appearance term to the IoU association."""
+        every tracked row (reid_weights, reid_fp32 and half as for StrongSORT) add an appearance term to the IoU association.
+        reid_model (with_reid only): "osnet" (default, as above) or "auto" — Ultralytics' `model: auto` (docs/BYTETRACK.md §1d): the
+        rows' features are read from the detector's own head inputs, so the detector weights are the only file; no OSNet, no
+        crops, no reid_weights (a ValueError), and reid_fp32 does not apply (the features follow `half`)."""
         byte_config(tracker_type, with_reid)      # ValueError on anything else
+        check_reid_model(reid_model, with_reid, reid_weights)
+        self.reid_model = reid_model
         self.tracker_type = tracker_type
         self.with_reid = bool(with_reid)
         self._byte = tracker_type != "strongsort"
@@ -287,6 +292,8 @@ class YOLO:
             self._pipe_kw["tracker"] = tracker_type
             if self.with_reid:
                 self._pipe_kw["with_reid"] = True
+                if reid_model != "osnet":
+                    self._pipe_kw["reid_model"] = reid_model
         self.device_masks = bool(device_masks)
         self._fill = None
         self._frame_index = 0

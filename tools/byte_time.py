@@ -14,6 +14,10 @@
                               with per-identity raw features (tests/test_gpu_botsort_reid.reid_stream), one with ReID (k_byte_feats +
                               the REID variant of k_byte_group) and one without, called alternately.  rates mode: botsort,
                               botsort with ReID and StrongSORT (fp32 ReID), one leg per fresh process, interleaved (--rounds each).
+  --auto                      BoT-SORT's ReID with `model: auto` (docs/BYTETRACK.md §1d).  kernel mode: ss_native_feats alone on a
+                              32-frame group of yolov8n head inputs at 1280x720 (f16 [32, 64|128|256, 48|24|12, 80|40|20],
+                              --rows kept rows a frame); wall time per call (events), kernel time under rocprofv3.  rates mode:
+                              botsort, botsort + OSNet fp32 ReID and botsort + `auto`, one leg per fresh process, interleaved.
 """
 import argparse
 import json
@@ -165,6 +169,32 @@ def kernel_reid(S, groups, warmup):
                     "rocprofv3 --kernel-trace --stats"}
 
 
+def kernel_auto(groups, warmup, rows):
+    from strongsort_yolo_amd.engine import TrackerEngine
+    dev = torch.device("cuda", 0)
+    eng = TrackerEngine(n_streams=1)
+    g = torch.Generator().manual_seed(0)
+    shapes = ((64, 48, 80), (128, 24, 40), (256, 12, 20))
+    maps = [torch.randn(32, c, h, w, generator=g).half().to(dev).contiguous(memory_format=torch.channels_last) for c, h, w in shapes]
+    A = sum(h * w for _, h, w in shapes)
+    keep = torch.randint(0, A, (32, 128), generator=g, dtype=torch.int32).to(dev)
+    cnt = torch.full((32,), rows, dtype=torch.int32, device=dev)
+    out = torch.zeros(32, 128, 512, device=dev)
+    ms = []
+    for k in range(groups + warmup):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        eng.native_feats(maps, keep, cnt, out)
+        b.record()
+        b.synchronize()
+        if k >= warmup:
+            ms.append(a.elapsed_time(b))
+    eng.check_errors()
+    eng.close()
+    return {"mode": "kernel_auto", "group_frames": 32, "rows_per_frame": rows, "groups": groups, "us_per_group_median": float(np.median(ms)) * 1e3,
+            "note": "host event pair around one ss_native_feats call (includes launch latency); kernel time: rocprofv3 --kernel-trace --stats"}
+
+
 def rates(n_frames, batch):
     os.environ["SS_RANDOM_INIT"] = "1"
     from strongsort_yolo_amd.synth import make_stream
@@ -193,8 +223,8 @@ def rates(n_frames, batch):
 
 
 def rate_leg(leg, n_frames, batch):
-    """One leg in this process: botsort with (leg "botsort_cmc") or without camera_motion, botsort with ReID ("botsort_reid"),
-    StrongSORT with fp32 ReID ("strongsort"); 1280x720 frames panning 3 px a frame."""
+    """One leg in this process: botsort with (leg "botsort_cmc") or without camera_motion, botsort with ReID ("botsort_reid": OSNet
+    fp32, "botsort_auto": `model: auto`), StrongSORT with fp32 ReID ("strongsort"); 1280x720 frames panning 3 px a frame."""
     os.environ["SS_RANDOM_INIT"] = "1"
     from strongsort_yolo_amd.yolo import YOLO
     pan = _pan_frames(16, 1)
@@ -204,7 +234,7 @@ def rate_leg(leg, n_frames, batch):
         m = YOLO("yolov8n.pt", random_init_ok=True)
     else:
         m = YOLO("yolov8n.pt", random_init_ok=True, tracker_type="botsort", camera_motion=leg == "botsort_cmc",
-                 with_reid=leg == "botsort_reid")
+                 with_reid=leg in ("botsort_reid", "botsort_auto"), reid_model="auto" if leg == "botsort_auto" else "osnet")
     for k in range(10):
         m.track(frames[k % 32], persist=True)
     torch.cuda.synchronize()
@@ -252,12 +282,16 @@ if __name__ == "__main__":
     p.add_argument("--gmc", action="store_true", help="BoT-SORT GMC legs (see the module docstring)")
     p.add_argument("--rounds", type=int, default=3, help="rates --gmc: processes per leg")
     p.add_argument("--reid", action="store_true", help="BoT-SORT ReID legs (see the module docstring)")
-    p.add_argument("--leg", choices=("botsort", "botsort_cmc", "botsort_reid", "strongsort"), default=None, help=argparse.SUPPRESS)
+    p.add_argument("--auto", action="store_true", help="BoT-SORT ReID with model: auto (see the module docstring)")
+    p.add_argument("--rows", type=int, default=28, help="kernel --auto: kept rows a frame")
+    p.add_argument("--leg", choices=("botsort", "botsort_cmc", "botsort_reid", "botsort_auto", "strongsort"), default=None, help=argparse.SUPPRESS)
     a = p.parse_args()
     if a.leg is not None:
         r = rate_leg(a.leg, a.frames, a.batch)
     elif a.mode == "kernel":
-        r = kernel_reid(a.streams, a.groups, a.warmup) if a.reid else kernel_gmc(a.streams, a.groups, a.warmup) if a.gmc else kernel(a.streams, a.groups, a.warmup)
+        r = kernel_auto(a.groups, a.warmup, a.rows) if a.auto else kernel_reid(a.streams, a.groups, a.warmup) if a.reid else kernel_gmc(a.streams, a.groups, a.warmup) if a.gmc else kernel(a.streams, a.groups, a.warmup)
+    elif a.auto:
+        r = rates_legs(a.frames, a.batch, a.rounds, ("botsort", "botsort_reid", "botsort_auto"), "rates_auto")
     elif a.reid:
         r = rates_legs(a.frames, a.batch, a.rounds, ("botsort", "botsort_reid", "strongsort"), "rates_reid")
     elif a.gmc:
