@@ -66,6 +66,8 @@ class TrackerEngine:
         c = _lib.make_config(self.cfg, n_streams, debug)
         _lib.check(None, self.L.ss_create(C.byref(c), device, C.byref(self.ctx)))
         self.debug_enabled = debug
+        self._streams_keep = []                          # handles of create_stream(): destroyed with the context
+        self._cmc_keep = self._assoc_ev_keep = None      # set_cmc / set_assoc_event: the library keeps their addresses
         self.use_current_stream()
         dev = self.device
         self.out = torch.zeros(n_streams, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=dev)
@@ -74,7 +76,7 @@ class TrackerEngine:
     def close(self):
         if getattr(self, "ctx", None) and self.ctx.value:
             torch.cuda.synchronize(self.device)          # nothing of ours may still be in flight on any stream
-            for h in getattr(self, "_streams_keep", []):
+            for h in self._streams_keep:
                 self.L.ss_stream_destroy(self.ctx, C.c_void_p(h))
             self._streams_keep = []
             self.L.ss_destroy(self.ctx)
@@ -91,8 +93,16 @@ class TrackerEngine:
     def _ck(self, rc):
         _lib.check(self.ctx, rc)
 
+    def _st(self, stream=None):
+        """`stream` (torch.cuda.Stream), or the current torch stream, as the library takes it."""
+        return C.c_void_p((torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream)
+
+    def use_stream(self, stream=None):
+        """The tracker's and the front end's launches go to `stream` (default: the current torch stream) from here on."""
+        self._ck(self.L.ss_set_hip_stream(self.ctx, self._st(stream)))
+
     def use_current_stream(self):
-        self._ck(self.L.ss_set_hip_stream(self.ctx, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self.use_stream()
 
     def reset(self, stream: int = -1):
         self._ck(self.L.ss_reset(self.ctx, stream))
@@ -110,8 +120,7 @@ class TrackerEngine:
         src = np.ascontiguousarray(src)
         if src.nbytes != dst.numel() * dst.element_size() or not dst.is_contiguous():
             raise ValueError("upload: size / layout mismatch")
-        st = torch.cuda.current_stream(self.device) if stream is None else stream
-        self._ck(self.L.ss_upload(self.ctx, C.c_void_p(st.cuda_stream), _ptr(dst), src.ctypes.data_as(C.c_void_p), src.nbytes))
+        self._ck(self.L.ss_upload(self.ctx, self._st(stream), _ptr(dst), src.ctypes.data_as(C.c_void_p), src.nbytes))
 
     def upload_batch(self, dst: torch.Tensor, srcs, stream=None, threads: int = 4):
         """len(srcs) host arrays of one size -> dst[0 .. len(srcs)) (device, contiguous) in ONE asynchronous copy: the arrays are staged
@@ -125,24 +134,23 @@ class TrackerEngine:
         if (any(a.nbytes != each or a.shape != srcs[0].shape for a in srcs) or not dst.is_contiguous() or dst[0].numel() * dst.element_size() != each
                 or dst.shape[0] < n or tuple(dst.shape[1:]) != tuple(srcs[0].shape)):
             raise ValueError("upload_batch: size / shape / layout mismatch")
-        st = torch.cuda.current_stream(self.device) if stream is None else stream
         arr = (C.c_void_p * n)(*[a.ctypes.data for a in srcs])
-        self._ck(self.L.ss_upload_batch(self.ctx, C.c_void_p(st.cuda_stream), _ptr(dst), arr, n, each, int(threads)))
+        self._ck(self.L.ss_upload_batch(self.ctx, self._st(stream), _ptr(dst), arr, n, each, int(threads)))
 
     def download(self, dst: np.ndarray, src: torch.Tensor, stream=None):
         """Device tensor -> host array (synchronous)."""
         if dst.nbytes != src.numel() * src.element_size() or not src.is_contiguous() or not dst.flags["C_CONTIGUOUS"]:
             raise ValueError("download: size / layout mismatch")
-        st = torch.cuda.current_stream(self.device) if stream is None else stream
-        self._ck(self.L.ss_download(self.ctx, C.c_void_p(st.cuda_stream), dst.ctypes.data_as(C.c_void_p), _ptr(src), dst.nbytes))
+        self._ck(self.L.ss_download(self.ctx, self._st(stream), dst.ctypes.data_as(C.c_void_p), _ptr(src), dst.nbytes))
 
     # ---- tracker --------------------------------------------------------------------------------
-    def update_device(self, dets, ndets, feats, img_hw):
+    def update_device(self, dets, ndets, feats, img_hw, out=None, nout=None):
         """All streams, one frame; tensors live on the device ([S,128,6] f32, [S] i32, [S,128,512] f32,
-        [S,2] i32).  Asynchronous; returns (rows [S,256,8], counts [S]) device tensors."""
-        self._ck(self.L.ss_track_update(self.ctx, _ptr(dets), _ptr(ndets), _ptr(feats), _ptr(img_hw),
-                                        _ptr(self.out), _ptr(self.nout)))
-        return self.out, self.nout
+        [S,2] i32).  Asynchronous; returns (rows [S,256,8], counts [S]) device tensors (default: self.out, self.nout)."""
+        out = self.out if out is None else out
+        nout = self.nout if nout is None else nout
+        self._ck(self.L.ss_track_update(self.ctx, _ptr(dets), _ptr(ndets), _ptr(feats), _ptr(img_hw), _ptr(out), _ptr(nout)))
+        return out, nout
 
     @property
     def max_group_frames(self) -> int:
@@ -162,8 +170,7 @@ class TrackerEngine:
         frames of a partial group (the rest of the buffer is stale)."""
         if warps is None:
             warps = torch.zeros(n_frames, self.S, 8, dtype=torch.float64, device=self.device)
-        st = torch.cuda.current_stream(self.device) if stream is None else stream
-        self._ck(self.L.ss_cmc_estimate(self.ctx, C.c_void_p(st.cuda_stream), _ptr(frames), int(n_frames), frames.stride(0),
+        self._ck(self.L.ss_cmc_estimate(self.ctx, self._st(stream), _ptr(frames), int(n_frames), frames.stride(0),
                                         frames.shape[1], frames.shape[2], frames.stride(1), _ptr(n_valid), _ptr(warps)))
         return warps
 
@@ -180,16 +187,13 @@ class TrackerEngine:
 
     def track_join(self, stream):
         """`stream` (torch.cuda.Stream) waits for the detached per-frame chain of the last update_group (option "chain_cus")."""
-        self._ck(self.L.ss_track_join(self.ctx, C.c_void_p(stream.cuda_stream)))
+        self._ck(self.L.ss_track_join(self.ctx, self._st(stream)))
 
     def create_stream(self, skip_cus: int = 0):
         """A stream whose queue leaves the first `skip_cus` compute units of the CU mask alone (ss_stream_create) as a
         torch.cuda.ExternalStream; the handle lives as long as the engine."""
-        import torch
         h = C.c_void_p()
         self._ck(self.L.ss_stream_create(self.ctx, int(skip_cus), C.byref(h)))
-        if not hasattr(self, "_streams_keep"):
-            self._streams_keep = []
         self._streams_keep.append(h.value)
         return torch.cuda.ExternalStream(h.value, device=self.device)
 
@@ -474,8 +478,7 @@ class TrackerEngine:
         assert proto.is_contiguous() and dets.is_contiguous() and bits.is_contiguous() and geom.is_contiguous()
         assert dets.dtype == torch.float32 and geom.dtype == torch.float32 and counts.dtype == torch.int32
         assert proto.dtype in (torch.float16, torch.float32) and dets.shape[0] == F and bits.shape[:2] == dets.shape[:2]
-        st = torch.cuda.current_stream(self.device) if stream is None else stream
-        self._ck(self.L.ss_mask_assemble(self.ctx, C.c_void_p(st.cuda_stream), _ptr(proto), int(proto.dtype == torch.float16), proto.stride(0),
+        self._ck(self.L.ss_mask_assemble(self.ctx, self._st(stream), _ptr(proto), int(proto.dtype == torch.float16), proto.stride(0),
                                          nm, mh, mw, _ptr(dets), dets.stride(0), dets.shape[2], coef_off, _ptr(counts), F, dets.shape[1],
                                          _ptr(geom), geom.stride(0) if F > 1 else 0, 4 * mh, 4 * mw, _ptr(bits), bits.stride(0)))
 
@@ -489,8 +492,7 @@ class TrackerEngine:
         assert pts.shape[:2] == (F, R) and npts.shape == (F, R) and counts.dtype == torch.int32
         if bits_copy is not None:
             assert bits_copy.is_contiguous() and bits_copy.shape[1:] == bits.shape[1:] and (bits_copy.is_cuda or bits_copy.is_pinned())
-        st = torch.cuda.current_stream(self.device) if stream is None else stream
-        self._ck(self.L.ss_mask_outline(self.ctx, C.c_void_p(st.cuda_stream), _ptr(bits), bits.stride(0), _ptr(counts), F, R, ih, iw,
+        self._ck(self.L.ss_mask_outline(self.ctx, self._st(stream), _ptr(bits), bits.stride(0), _ptr(counts), F, R, ih, iw,
                                         pts.shape[2], _ptr(pts), pts.stride(0), _ptr(npts), npts.stride(0), _ptr(bits_copy),
                                         bits_copy.stride(0) if bits_copy is not None else 0, _ptr(scratch), scratch.numel() * scratch.element_size()))
 
@@ -535,8 +537,12 @@ class ByteTrackEngine:
         if self.reid:                               # §1c: BoT-SORT's appearance term (resets the streams)
             self._ck(self.L.ss_byte_set_reid(self.base.ctx, 1, float(self.cfg.proximity_thresh), float(self.cfg.appearance_thresh),
                                              float(self.cfg.feat_alpha)))
+        self._cmc_keep = None
         self.out = torch.zeros(self.S, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=self.device)
         self.nout = torch.zeros(self.S, dtype=torch.int32, device=self.device)
+        # the context's own: streams, error words, group size, the ECC warps of a group (N4: frames uint8 [F*S,H,W,3] -> [F,S,8])
+        self.use_stream, self.use_current_stream = self.base.use_stream, self.base.use_current_stream
+        self.check_errors, self.cmc_estimate = self.base.check_errors, self.base.cmc_estimate
 
     @property
     def ctx(self):
@@ -552,16 +558,9 @@ class ByteTrackEngine:
             torch.cuda.synchronize(self.device)
             self._ck(self.L.ss_byte_destroy(self.base.ctx))
 
-    def use_current_stream(self):
-        self.base.use_current_stream()
-
     def reset(self, stream: int = -1):
         """Restart the stream(s): ids from 1, and the next cmc_estimate frame gets no warp (G-04)."""
         self._ck(self.L.ss_byte_reset(self.base.ctx, stream))
-
-    def cmc_estimate(self, frames: torch.Tensor, n_frames: int, warps: torch.Tensor = None, stream=None, n_valid: torch.Tensor = None):
-        """N4's ECC warps of a group (TrackerEngine.cmc_estimate on the shared context): frames uint8 [F*S,H,W,3] -> [F,S,8]."""
-        return self.base.cmc_estimate(frames, n_frames, warps, stream=stream, n_valid=n_valid)
 
     def set_cmc(self, warps):
         """BoT-SORT GMC (docs/BYTETRACK.md §1b): the following update calls move every track by these warps ([F,S,8] float64,
@@ -569,12 +568,9 @@ class ByteTrackEngine:
         self._ck(self.L.ss_byte_set_gmc(self.base.ctx, _ptr(warps)))
         self._cmc_keep = warps
 
-    def check_errors(self):
-        self.base.check_errors()
-
     @property
     def max_group_frames(self) -> int:
-        return int(self.L.ss_max_group_frames())
+        return self.base.max_group_frames
 
     def _feats(self, feats, rows):
         if not self.reid:

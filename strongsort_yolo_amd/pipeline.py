@@ -59,10 +59,11 @@ class FramePipeline:
         if self.byte_cfg is not None and cmc and self.byte_cfg.kalman != "xywh":
             raise ValueError("camera-motion compensation needs tracker 'strongsort' or 'botsort' (ByteTrack has no GMC)")
         self.eng = TrackerEngine(self.cfg, n_streams, device, debug=debug)
-        self.byte = None
+        # trk: the tracker whose update_device / update_group / set_cmc the pipeline calls (BoT-SORT: GMC on the BYTE state, §1b)
+        self.byte, self.trk = None, self.eng
         if self.byte_cfg is not None:
             from .engine import ByteTrackEngine
-            self.byte = ByteTrackEngine(self.byte_cfg, engine=self.eng)
+            self.byte = self.trk = ByteTrackEngine(self.byte_cfg, engine=self.eng)
         dev = self.dev = self.eng.device
         self.half, self.dtype = half, torch.float16 if half else torch.float32
         # reid_half=False: the ReID crops and OSNet in fp32 on the hand-written fp32 kernels (fused32.py, csrc/ss_ops32.hip:
@@ -104,57 +105,132 @@ class FramePipeline:
         self.nx = self.nk + self.nm                             # extra columns NMS carries along with every kept row
         g, S = self.geom, n_streams
         self.n_anchors = sum((g.out_h // s) * (g.out_w // s) for s in (8, 16, 32))
-        # ---- static buffers (addresses are baked into the graph) ----
-        self.frames = torch.zeros(S, self.H, self.W, 3, dtype=torch.uint8, device=dev)
-        self.lb = torch.zeros(S, 3, g.out_h, g.out_w, dtype=self.dtype, device=dev).contiguous(memory_format=torch.channels_last)
+        # how the stage bodies below differ between this class and OverlappedPipeline, as data: one frame per buffer set,
+        # crops at one slot range per stream, net outputs not kept (OverlappedPipeline sets its own after this constructor)
+        self.F, self.Sv, self.pack, self.keep_net_outputs = 1, S, False, False
+        # N4 (optional): ECC camera-motion warps estimated beside the detector, applied by the tracker before predicting
+        self.cmc = bool(cmc)
+        # ---- static buffers (addresses are baked into the graph): ONE set, under the names callers fill and read ----
+        b = self.b = _Bufs(self, S, self.det_rows, 1, self.cmc)
+        for name in ("frames", "lb", "pred_in", "dets", "dets6", "proto", "keep", "ndets", "crops", "anchor_gt", "gt_feats", "warps"):
+            setattr(self, name, getattr(b, name))
+        self.feats_in = b.feats_v
         self.geom_dev = torch.tensor([[self.gain, self.pad_x, self.pad_y, float(self.W), float(self.H)]] * S,
                                      dtype=torch.float32, device=dev)      # per-image scale_boxes geometry for ss_nms_batch
-        self.pred_in = torch.zeros(S, 4 + self.nc + self.nx, self.n_anchors, dtype=torch.float32, device=dev)
-        self.dets = torch.zeros(S, self.det_rows, 6 + self.nx, dtype=torch.float32, device=dev)
-        self.dets6 = self.dets if self.nx == 0 else torch.zeros(S, self.det_rows, 6, dtype=torch.float32, device=dev)
-        # segmentation: the frame's mask prototypes [nm, out_h/4, out_w/4] stay here until the caller has built its Results
-        self.proto = torch.zeros(S, self.nm, g.out_h // 4, g.out_w // 4, dtype=self.dtype, device=dev) if self.nm else None
-        self.keep = torch.zeros(S, self.det_rows, dtype=torch.int32, device=dev)
-        self.ndets = torch.zeros(S, dtype=torch.int32, device=dev)
-        self.crops = torch.zeros(S * self.RB if self.need_reid else 0, 3, 256, 128, dtype=self.crops_dtype,
-                                 device=dev).contiguous(memory_format=torch.channels_last)
-        self.feats_in = torch.zeros(S, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=dev)
         self.img_hw = torch.tensor([[self.H, self.W]] * S, dtype=torch.int32, device=dev)
         self.out, self.nout = self.eng.out, self.eng.nout
-        self.anchor_gt = torch.zeros(S, self.n_anchors, dtype=torch.int64, device=dev)
-        self.gt_feats = torch.zeros(S, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=dev)
         self._maps = None                   # reid_model "auto": the head inputs of the detector call in flight
         self.graph = None
         self.graph_all = None
         self.graph_mode = graph
-        # N4 (optional): ECC camera-motion warps estimated beside the detector, applied by the tracker before predicting
-        self.cmc = bool(cmc)
-        self.warps = torch.zeros(1, S, 8, dtype=torch.float64, device=dev) if self.cmc else None
         if self.cmc:
             self.eng.cmc_estimate(self.frames, 1, self.warps)            # sizes the small-frame buffer outside any capture
             self.reset_tracker(-1)
-            (self.eng if self.byte is None else self.byte).set_cmc(self.warps)    # BoT-SORT: GMC on the BYTE state (§1b)
+            self.trk.set_cmc(self.warps)
 
-    # ---- one frame for every stream, from the static buffers ----------------------------------------
-    def _detect_impl(self):
-        # every frame-side stage is ONE launch (set) over all S streams, written straight in the NHWC layout the
-        # convolutions read
-        e, g = self.eng, self.geom
-        if self.cmc:
-            e.cmc_estimate(self.frames, 1, self.warps)
+    # ---- stage bodies (b = a buffer set) ---------------------------------------------------------------
+    # Every frame-side stage is ONE launch (set) over all virtual streams of the set, written straight in the NHWC layout the
+    # convolutions read.  FramePipeline's detect | reid | track stages and OverlappedPipeline's stage lists are compositions of
+    # these bodies; where the two classes launch differently, the condition is here (`grouped`, `pack`, `keep_net_outputs`).
+    grouped = False                         # OverlappedPipeline: the buffer sets hold frame groups and cross graph boundaries
+
+    def _letterbox(self, b):
+        if self.cmc:                                           # the group's F warps, beside the detector (stateless stage)
+            self.eng.cmc_estimate(b.frames, self.F, b.warps, n_valid=b.nvalid)    # a partial group: the last REAL frame becomes "previous"
         if self.run_nets:
-            e.letterbox_batch(self.frames, g, half=self.half, pad_value=self.dcfg.pad_value, out=self.lb, channels_last=True)
-            with self._decode_into(self.pred_in):
-                pred = self._pred(self.detector(self.lb), self.proto)    # [S, 4+nc+nk+nm, A]
-            if self.det_source == "detector" and pred.data_ptr() != self.pred_in.data_ptr():
-                self.pred_in.copy_(pred)
-        e.nms_batch(self.pred_in, self.nc, self.dcfg, self.geom_dev, n_extra=self.nx, rows=self.dets, keep=self.keep,
-                    count=self.ndets, max_det=self.max_det)
+            self.eng.letterbox_batch(b.frames, self.geom, half=self.half, pad_value=self.dcfg.pad_value, out=b.lb,
+                                     channels_last=True)
+
+    @staticmethod
+    def _keep(b, name, tensors):
+        """Stage outputs that cross a graph boundary live in per-set static buffers."""
+        cur = getattr(b, name, None)
+        if cur is None:
+            cur = [torch.empty_like(t) for t in tensors]
+            setattr(b, name, cur)
+        for d, t in zip(cur, tensors):
+            d.copy_(t)
+
+    def _s_backbone(self, b):
+        if self.run_nets:
+            self._letterbox(b)
+            self._keep(b, "pyr", self.detector.forward_backbone(b.lb))
+
+    def _s_head(self, b):
+        self._forward(b, lambda: self.detector.forward_head(*b.pyr))
+
+    def _s_detector(self, b):
+        if self.run_nets:
+            self._letterbox(b)
+            self._forward(b, lambda: self.detector(b.lb))
+        elif self.cmc and not self.grouped:                    # FramePipeline estimates the warps without the networks too
+            self._letterbox(b)
+
+    def _forward(self, b, head):
+        """The detector call that ends in the head, and what follows it: [Sv, 4+nc+nk+nm, A] into the NMS input."""
+        with self._decode_into(b.pred_in):
+            pred = self._pred(head(), b.proto)
+        if self.native:
+            # reid_model "auto": the head inputs stay referenced by the buffer set until the NMS body's launch reads them.  No
+            # copy across a stage boundary (as b.mid in _reid_a): the maps live in this graph's private pool, keep their addresses
+            # over replays, and the NMS stage's graph (captured after this one, for the same buffer set) reads them there.
+            b.maps, self._maps = self._maps, None
+        if self.keep_net_outputs:
+            b.head_out = pred
+        if self.det_source == "detector" and pred.data_ptr() != b.pred_in.data_ptr():
+            b.pred_in.copy_(pred)
+
+    def _nms(self, b):
+        e = self.eng
+        e.nms_batch(b.pred_in, self.nc, self.dcfg, self.geom_dev, n_extra=self.nx, rows=b.dets, keep=b.keep,
+                    count=b.ndets, max_det=self.max_det)
         if self.nx:
-            self.dets6.copy_(self.dets[:, :, :6])
-        maps, self._maps = self._maps, None
+            b.dets6.copy_(b.dets[:, :, :6])
         if self.native and self.run_nets and self.feat_source == "reid":
-            e.native_feats(maps, self.keep, self.ndets, self.feats_in)
+            e.native_feats(b.maps, b.keep, b.ndets, b.feats_v)
+        if not self.grouped:
+            b.maps = None                   # FramePipeline: detector and NMS are one stage, the maps are let go once the launch is enqueued
+
+    def _crops(self, b):
+        if self.run_nets and self.reid is not None:
+            if self.pack:        # the group's valid crops contiguous; the ReID kernels skip the rest of the fixed-size batch
+                self.eng.crop_norm_packed(b.frames, b.dets6, self.RB, b.ndets, b.crop_off, b.crops, half=self.reid_half)
+            else:
+                self.eng.crop_norm_batch(b.frames, b.dets6, self.RB, counts=b.ndets, half=self.reid_half, out=b.crops, channels_last=True)
+
+    def _valid(self, b):
+        from . import fused, fused32
+        if not self.reid_half:                               # fp32 kernels take the count as a launch argument
+            return fused32.valid_images(b.crop_off[self.Sv:] if self.pack else None)
+        return fused.valid_images(b.crop_off[self.Sv:] if self.pack else None, self.Sv * self.RB)
+
+    def _select(self, b, emb):
+        if emb is not None and self.keep_net_outputs:
+            b.emb_out = emb
+        if emb is not None and self.feat_source == "reid":
+            if self.pack:
+                self.eng.unpack_feats(emb.contiguous(), b.crop_off, b.ndets, self.RB, b.feats_v)
+            else:
+                b.feats_v[:, :self.RB].copy_(emb.view(self.Sv, self.RB, FEAT_DIM))
+        if self.feat_source == "by_anchor":
+            idx = b.anchor_gt.gather(1, b.keep.long().clamp_(0, self.n_anchors - 1))
+            torch.gather(b.gt_feats, 1, idx.clamp_(min=0).unsqueeze(-1).expand(-1, -1, FEAT_DIM), out=b.feats_v)
+
+    def _s_reid_select(self, b):
+        """Crops, the whole OSNet, feature select."""
+        if not (self.grouped or self.need_reid or self.native):
+            return                          # FramePipeline without ReID: no stage at all (not even the by_anchor gather)
+        self._crops(b)
+        emb = None
+        if self.run_nets and self.reid is not None:
+            with self._valid(b):
+                emb = self.reid(b.crops)                        # [Sv*RB, 512]
+        self._select(b, emb)
+
+    # ---- one frame for every stream, from the one buffer set --------------------------------------------
+    def _detect(self):
+        self._s_detector(self.b)
+        self._nms(self.b)
 
     def _take_head_inputs(self, module, args):
         """Forward pre-hook on detector.detect (reid_model "auto"): its input list [P3, P4, P5], as Ultralytics' hook keeps it."""
@@ -174,35 +250,45 @@ class FramePipeline:
             proto_dst.copy_(proto)
         return out
 
-    def _reid_impl(self):
-        e, S = self.eng, self.S
-        if not (self.need_reid or self.native):
-            return
-        if self.run_nets and self.reid is not None:
-            e.crop_norm_batch(self.frames, self.dets6, self.RB, counts=self.ndets, half=self.reid_half, out=self.crops,
-                              channels_last=True)
-            emb = self.reid(self.crops)                         # [S*RB, 512]
-            if self.feat_source == "reid":
-                self.feats_in[:, :self.RB].copy_(emb.view(S, self.RB, FEAT_DIM))
-        if self.feat_source == "by_anchor":
-            idx = self.anchor_gt.gather(1, self.keep.long().clamp_(0, self.n_anchors - 1))      # [S,128]
-            torch.gather(self.gt_feats, 1, idx.clamp_(min=0).unsqueeze(-1).expand(-1, -1, FEAT_DIM), out=self.feats_in)
-
-    def _step_impl(self):
-        self._detect_impl()
-        self._reid_impl()
+    def _reid(self):
+        self._s_reid_select(self.b)
 
     def _track(self):
-        if self.byte is not None:
-            self.byte.update_device(self.dets6, self.ndets, self.feats_in, out=self.out, nout=self.nout)
-            return
-        self.eng.update_device(self.dets6, self.ndets, self.feats_in, self.img_hw)
+        b = self.b
+        self.trk.update_device(b.dets6, b.ndets, b.feats_v, self.img_hw, out=self.out, nout=self.nout)
 
     def reset_tracker(self, stream: int = -1):
         """Restart the tracker of one stream (all: -1), whichever family runs."""
         self.eng.reset(stream)
         if self.byte is not None:
             self.byte.reset(stream)
+
+    def _warm_and_capture(self, warm, captures, tracks: bool = True):
+        """Warm `warm` (callables) up on a side stream (MIOpen find, allocator), three eager passes, then capture one HIP graph per
+        entry of `captures` (each a list of callables) there.  tracks: the warm-up frames must not count, the tracker is reset
+        before the capture and after it (streams start fresh)."""
+        st = torch.cuda.Stream(self.dev)
+        st.wait_stream(torch.cuda.current_stream(self.dev))
+        graphs = []
+        with torch.cuda.stream(st):
+            self.eng.use_current_stream()
+            for _ in range(3):
+                for fn in warm:
+                    fn()
+            st.synchronize()
+            if tracks:
+                self._restore_tracker()
+            for fns in captures:
+                gph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gph, stream=st):
+                    for fn in fns:
+                        fn()
+                graphs.append(gph)
+        torch.cuda.current_stream(self.dev).wait_stream(st)
+        self.eng.use_current_stream()
+        if tracks:
+            self._restore_tracker()
+        return graphs
 
     @torch.no_grad()
     def step(self, track: bool = True):
@@ -213,62 +299,24 @@ class FramePipeline:
                 raise RuntimeError("a detect_only_rows pipeline cannot track")
             if self.graph_mode != "none":
                 if self.graph is None:                       # one graph: letterbox, detector, NMS
-                    st = torch.cuda.Stream(self.dev)
-                    st.wait_stream(torch.cuda.current_stream(self.dev))
-                    with torch.cuda.stream(st):
-                        self.eng.use_current_stream()
-                        for _ in range(3):
-                            self._detect_impl()
-                        st.synchronize()
-                        self.graph = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(self.graph, stream=st):
-                            self._detect_impl()
-                    torch.cuda.current_stream(self.dev).wait_stream(st)
-                    self.eng.use_current_stream()
+                    self.graph, = self._warm_and_capture([self._detect], [[self._detect]], tracks=False)
                 self.graph.replay()
                 return
+        whole = [self._detect, self._reid, self._track]
         if self.graph_mode == "none":
-            self._detect_impl()
-            if track:
-                self._reid_impl()
-                self._track()
+            for fn in (whole if track else whole[:1]):
+                fn()
             return
         if self.graph is None:
-            # warm up on a side stream (MIOpen find, allocator), then capture
-            st = torch.cuda.Stream(self.dev)
-            st.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(st):
-                self.eng.use_current_stream()
-                for _ in range(3):
-                    self._step_impl()
-                    self._track()
-                st.synchronize()
-                self._restore_tracker()
-                if self.graph_mode == "split":
-                    # three graphs on the same static buffers: detection | ReID | tracker, so a detection-only call
-                    # (model.predict, yolo_multi_model.py:173) replays just the first
-                    self.graph = []
-                    for fn in ((self._detect_impl, self._track) if not self.need_reid else (self._detect_impl, self._reid_impl, self._track)):
-                        gph = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(gph, stream=st):
-                            fn()
-                        self.graph.append(gph)
-                    # ... and the three stages once more as ONE graph for the tracking call (model.track, yolo_multi_model.py:41 / :278: the
-                    # only call the reference makes per frame): one replay instead of three, no launch boundary between the stages
-                    self.graph_all = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self.graph_all, stream=st):
-                        self._detect_impl()
-                        self._reid_impl()
-                        self._track()
-                else:
-                    self.graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self.graph, stream=st):
-                        self._step_impl()
-                        if self.graph_mode == "all":
-                            self._track()
-            torch.cuda.current_stream(self.dev).wait_stream(st)
-            self.eng.use_current_stream()
-            self._restore_tracker()          # warm-up frames must not count: streams start fresh
+            if self.graph_mode == "split":
+                # three graphs on the same static buffers: detection | ReID | tracker, so a detection-only call
+                # (model.predict, yolo_multi_model.py:173) replays just the first
+                # ... and the three stages once more as ONE graph for the tracking call (model.track, yolo_multi_model.py:41 / :278: the
+                # only call the reference makes per frame): one replay instead of three, no launch boundary between the stages
+                stages = whole if self.need_reid else [self._detect, self._track]
+                *self.graph, self.graph_all = self._warm_and_capture(whole, [[fn] for fn in stages] + [whole])
+            else:
+                self.graph, = self._warm_and_capture(whole, [whole if self.graph_mode == "all" else whole[:2]])
         if self.graph_mode == "split":
             (self.graph_all if track else self.graph[0]).replay()
             return
@@ -298,37 +346,36 @@ class FramePipeline:
         torch.cuda.synchronize(self.dev)
         self.graph = None
         self.graph_all = None
-        if hasattr(self, "graphs"):
-            self.graphs = None                           # captured graphs reference the context's buffers: drop them first
         self.eng.close()
 
 
-def _p(t):
-    import ctypes as C
-    return C.c_void_p(t.data_ptr())
-
-
 class _Bufs:
-    """One set of per-frame buffers (static addresses, baked into that set's HIP graphs)."""
+    """One set of per-frame buffers (static addresses, baked into that set's HIP graphs): S virtual streams, `rows` detection rows
+    each, F frames per group; cmc: the group's camera-motion warps.  group: a frame group of OverlappedPipeline, which also
+    carries the packed ReID batch's offsets and the count of its real frames."""
 
-    def __init__(self, p: "FramePipeline"):
-        dev, S, g = p.dev, getattr(p, "Sv", p.S), p.geom
+    def __init__(self, p: "FramePipeline", S: int, rows: int = MAX_DETS, F: int = 1, cmc: bool = False, group: bool = False):
+        dev, g = p.dev, p.geom
         self.frames = torch.zeros(S, p.H, p.W, 3, dtype=torch.uint8, device=dev)
         self.lb = torch.zeros(S, 3, g.out_h, g.out_w, dtype=p.dtype, device=dev).contiguous(memory_format=torch.channels_last)
         self.pred_in = torch.zeros(S, 4 + p.nc + p.nx, p.n_anchors, dtype=torch.float32, device=dev)
-        self.dets = torch.zeros(S, MAX_DETS, 6 + p.nx, dtype=torch.float32, device=dev)
-        self.dets6 = self.dets if p.nx == 0 else torch.zeros(S, MAX_DETS, 6, dtype=torch.float32, device=dev)
-        self.proto = torch.zeros(S, p.nm, p.geom.out_h // 4, p.geom.out_w // 4, dtype=p.dtype, device=dev) if p.nm else None
-        self.keep = torch.zeros(S, MAX_DETS, dtype=torch.int32, device=dev)
+        self.dets = torch.zeros(S, rows, 6 + p.nx, dtype=torch.float32, device=dev)
+        self.dets6 = self.dets if p.nx == 0 else torch.zeros(S, rows, 6, dtype=torch.float32, device=dev)
+        # segmentation: the frame's mask prototypes [nm, out_h/4, out_w/4] stay here until the caller has built its Results
+        self.proto = torch.zeros(S, p.nm, g.out_h // 4, g.out_w // 4, dtype=p.dtype, device=dev) if p.nm else None
+        self.keep = torch.zeros(S, rows, dtype=torch.int32, device=dev)
         self.ndets = torch.zeros(S, dtype=torch.int32, device=dev)
         self.crops = torch.zeros(S * p.RB if p.need_reid else 0, 3, 256, 128, dtype=p.crops_dtype,
                                  device=dev).contiguous(memory_format=torch.channels_last)
         self.anchor_gt = torch.zeros(S, p.n_anchors, dtype=torch.int64, device=dev)
         self.gt_feats = torch.zeros(S, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=dev)
-        self.feats_v = torch.zeros(S, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=dev)    # what the tracker reads
-        self.crop_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)                     # packed ReID batch: first crop of every image, total
-        self.warps = torch.zeros(getattr(p, "F", 1), p.S, 8, dtype=torch.float64, device=dev) if getattr(p, "cmc", False) else None
-        self.nvalid = torch.full((1,), getattr(p, "F", 1), dtype=torch.int32, device=dev)    # real frames of the group in this set (device side: read by captured kernels)
+        self.feats_v = torch.zeros(S, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=dev)    # what the tracker reads (FramePipeline.feats_in)
+        self.warps = torch.zeros(F, p.S, 8, dtype=torch.float64, device=dev) if cmc else None
+        self.maps = None                    # reid_model "auto": the detector's head inputs, between the head and the NMS body
+        self.crop_off = self.nvalid = None
+        if group:
+            self.crop_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)                 # packed ReID batch: first crop of every image, total
+            self.nvalid = torch.full((1,), F, dtype=torch.int32, device=dev)                  # real frames of the group in this set (device side: read by captured kernels)
 
 
 class OverlappedPipeline(FramePipeline):
@@ -356,15 +403,15 @@ class OverlappedPipeline(FramePipeline):
                  tracker_stream: bool = False, defer_track: bool = False, keep_net_outputs: bool = False, pack_crops: bool = True,
                  assoc_gate: bool = True, track_priority: bool = False, skip_tracker: bool = False, chain_cus: int = 0, **kw):
         kw = dict(kw)
+        kw["graph"] = kw.get("graph", "front")
+        if kw["graph"] == "none":
+            raise ValueError("OverlappedPipeline needs graph='front' or 'all'")
+        super().__init__(*a, **kw)
         # keep_net_outputs: every buffer set keeps a reference to the head tensor and the embeddings its graphs produce
         # (b.head_out / b.emb_out: tensors of the graph's private pool, same address at every replay) even when the synthetic
         # workload does not consume them — bench.py compares them with an eager re-run after the timed region
         self.keep_net_outputs = bool(keep_net_outputs)
         self.skip_tracker = bool(skip_tracker)      # MEASUREMENT ONLY: no tracker calls (rows stay empty) — what the stateless stages alone cost
-        kw["graph"] = kw.get("graph", "front")
-        if kw["graph"] == "none":
-            raise ValueError("OverlappedPipeline needs graph='front' or 'all'")
-        super().__init__(*a, **kw)
         # frame batching: F consecutive frames of every stream travel through the stateless stages together as
         # S*F "virtual streams" (index f*S + s); the tracker then consumes them one frame at a time, in order.
         self.F = int(frame_batch)
@@ -392,19 +439,12 @@ class OverlappedPipeline(FramePipeline):
             self.reid_split = int(reid_split) if (self.run_nets and hasattr(self.reid, "N_PARTS")) else 0
             if not 0 <= self.reid_split <= getattr(self.reid, "N_PARTS", 0):
                 raise ValueError("reid_split out of range")
-        st = []
+        # every stage is a list of the stage bodies, run in order on the frame group's buffer set
         if self.reid_split is not None:
-            st += [self._s_front_split, self._s_back_split]
-        elif split_det:
-            st += [self._s_backbone, self._s_head]
+            st = [[self._s_detector, self._nms, self._crops, self._reid_a], [self._reid_b]]
         else:
-            st += [self._s_detector]
-        if self.reid_split is not None:
-            pass
-        elif split_reid:
-            st += [self._s_nms_crop_reid_a, self._s_reid_b_select]
-        else:
-            st += [self._s_nms_crop_reid_select]
+            st = [[self._s_backbone], [self._s_head]] if split_det else [[self._s_detector]]
+            st += [[self._nms, self._crops, self._reid_a], [self._reid_b]] if split_reid else [[self._nms, self._s_reid_select]]
         self.stages = st
         self.n = len(st)
         # track_priority=True gives the last stage's stream (the tracker's short dependent launches, the association kernel) high
@@ -456,7 +496,7 @@ class OverlappedPipeline(FramePipeline):
             self.eng.set_assoc_event(self.assoc_ev)
         self._gate = False
         self.nb = self.n + (1 if (self.sT is not None or self.defer) else 0)              # buffer sets
-        self.bufs = [_Bufs(self) for _ in range(self.nb)]
+        self.bufs = [_Bufs(self, self.Sv, MAX_DETS, self.F, self.cmc, group=True) for _ in range(self.nb)]
         self.ev = [[torch.cuda.Event() for _ in range(self.nb)] for _ in range(self.n)]   # ev[stage][set]
         self.ev_graph = [torch.cuda.Event() for _ in range(self.nb)]                      # last stage's graph done (tracker may start)
         self.graphs = [[None] * self.nb for _ in range(self.n)]                           # graphs[stage][set]
@@ -476,119 +516,29 @@ class OverlappedPipeline(FramePipeline):
         self.frames_in = 0
         self._captured = False
 
-    # ---- stage bodies (b = the frame's buffer set) -------------------------------------------------------
-    def _letterbox(self, b):
-        if self.cmc:                                           # the group's F warps, beside the detector (stateless stage)
-            self.eng.cmc_estimate(b.frames, self.F, b.warps, n_valid=b.nvalid)    # a partial group: the last REAL frame becomes "previous"
-        self.eng.letterbox_batch(b.frames, self.geom, half=self.half, pad_value=self.dcfg.pad_value, out=b.lb,
-                                 channels_last=True)
+    grouped = True
 
-    @staticmethod
-    def _keep(b, name, tensors):
-        """Stage outputs that cross a graph boundary live in per-set static buffers."""
-        cur = getattr(b, name, None)
-        if cur is None:
-            cur = [torch.empty_like(t) for t in tensors]
-            setattr(b, name, cur)
-        for d, t in zip(cur, tensors):
-            d.copy_(t)
-
-    def _s_backbone(self, b):
-        if self.run_nets:
-            self._letterbox(b)
-            self._keep(b, "pyr", self.detector.forward_backbone(b.lb))
-
-    def _s_head(self, b):
-        with self._decode_into(b.pred_in):
-            pred = self._pred(self.detector.forward_head(*b.pyr), b.proto)
-        self._hold_maps(b)
-        if self.keep_net_outputs:
-            b.head_out = pred
-        if self.det_source == "detector" and pred.data_ptr() != b.pred_in.data_ptr():
-            b.pred_in.copy_(pred)
-
-    def _s_detector(self, b):
-        if self.run_nets:
-            self._letterbox(b)
-            with self._decode_into(b.pred_in):
-                pred = self._pred(self.detector(b.lb), b.proto)
-            self._hold_maps(b)
-            if self.keep_net_outputs:
-                b.head_out = pred
-            if self.det_source == "detector" and pred.data_ptr() != b.pred_in.data_ptr():
-                b.pred_in.copy_(pred)
-
-    def _hold_maps(self, b):
-        """reid_model "auto": the head inputs stay referenced by the buffer set until the NMS stage's launch reads them.  No copy
-        across the stage boundary (as b.mid in _s_front_split): the maps live in this graph's private pool, keep their
-        addresses over replays, and the NMS stage's graph (captured after this one, for the same buffer set) reads them there."""
-        if self.native:
-            b.maps, self._maps = self._maps, None
-
-    def _nms_crop(self, b):
-        e = self.eng                       # one launch set over all S*F virtual streams
-        e.nms_batch(b.pred_in, self.nc, self.dcfg, self.geom_dev, n_extra=self.nx, rows=b.dets, keep=b.keep,
-                    count=b.ndets, max_det=self.max_det)
-        if self.nx:
-            b.dets6.copy_(b.dets[:, :, :6])
-        if self.native and self.run_nets and self.feat_source == "reid":
-            e.native_feats(b.maps, b.keep, b.ndets, b.feats_v)
-        if self.run_nets and self.reid is not None:
-            if self.pack:        # the group's valid crops contiguous; the ReID kernels skip the rest of the fixed-size batch
-                e.crop_norm_packed(b.frames, b.dets6, self.RB, b.ndets, b.crop_off, b.crops, half=self.reid_half)
-            else:
-                e.crop_norm_batch(b.frames, b.dets6, self.RB, counts=b.ndets, half=self.reid_half, out=b.crops, channels_last=True)
-
-    def _valid(self, b):
-        from . import fused, fused32
-        if not self.reid_half:                               # fp32 kernels take the count as a launch argument
-            return fused32.valid_images(b.crop_off[self.Sv:] if self.pack else None)
-        return fused.valid_images(b.crop_off[self.Sv:] if self.pack else None, self.Sv * self.RB)
-
-    def _select(self, b, emb):
-        if emb is not None and self.keep_net_outputs:
-            b.emb_out = emb
-        if emb is not None and self.feat_source == "reid":
-            if self.pack:
-                self.eng.unpack_feats(emb.contiguous(), b.crop_off, b.ndets, self.RB, b.feats_v)
-            else:
-                b.feats_v[:, :self.RB].copy_(emb.view(self.Sv, self.RB, FEAT_DIM))
-        if self.feat_source == "by_anchor":
-            idx = b.anchor_gt.gather(1, b.keep.long().clamp_(0, self.n_anchors - 1))
-            torch.gather(b.gt_feats, 1, idx.clamp_(min=0).unsqueeze(-1).expand(-1, -1, FEAT_DIM), out=b.feats_v)
-
-    def _s_nms_crop_reid_a(self, b):
-        self._nms_crop(b)
-        with self._valid(b):
-            st = self.reid.forward_a(b.crops)                # a tensor or a tuple of tensors (nets.OSNet._block_part)
-        b.mid_tuple = isinstance(st, tuple)
-        self._keep(b, "mid", list(st) if b.mid_tuple else [st])
-
-    def _s_reid_b_select(self, b):
-        with self._valid(b):
-            emb = self.reid.forward_b(tuple(b.mid) if b.mid_tuple else b.mid[0])
-        self._select(b, emb)
-
-    def _s_nms_crop_reid_select(self, b):
-        self._nms_crop(b)
-        emb = None
-        if self.run_nets and self.reid is not None:
+    # ---- the ReID network cut in two (b = the frame group's buffer set) ----------------------------------
+    def _reid_a(self, b):
+        """OSNet up to the cut: the network's own (four stages, reid_split None) or before part reid_split."""
+        if self.reid_split is None:
             with self._valid(b):
-                emb = self.reid(b.crops)
-        self._select(b, emb)
-
-    def _s_front_split(self, b):
-        self._s_detector(b)
-        self._nms_crop(b)
-        if self.run_nets and self.reid_split > 0:
+                st = self.reid.forward_a(b.crops)                # a tensor or a tuple of tensors (nets.OSNet._block_part)
+            b.mid_tuple = isinstance(st, tuple)
+            self._keep(b, "mid", list(st) if b.mid_tuple else [st])
+        elif self.run_nets and self.reid_split > 0:
             # no copy across the stage boundary: the tensor lives in this graph's private pool, keeps its address over
             # replays, and the next stage's graph (captured after this one, for the same buffer set) reads it there
             with self._valid(b):
                 b.mid = [self.reid.forward_a(b.crops, self.reid_split)]
 
-    def _s_back_split(self, b):
+    def _reid_b(self, b):
+        """The rest of OSNet, feature select."""
         emb = None
-        if self.run_nets:
+        if self.reid_split is None:
+            with self._valid(b):
+                emb = self.reid.forward_b(tuple(b.mid) if b.mid_tuple else b.mid[0])
+        elif self.run_nets:
             with self._valid(b):
                 emb = self.reid.forward_b(b.mid[0] if self.reid_split > 0 else b.crops, self.reid_split)
         self._select(b, emb)
@@ -597,7 +547,7 @@ class OverlappedPipeline(FramePipeline):
         """Tracker update of the group's frames in ONE call: the library associates them strictly in order (frame f =
         virtual streams f*S..) and reads the galleries once for all of them; `group` = index of the group's first
         frame (None while warming up / capturing: no callbacks)."""
-        e = self.eng if self.byte is None else self.byte
+        e = self.trk
         nv = self.F if n_valid is None else n_valid
         G, S = self.eng.max_group_frames, self.S             # frames per library call (SS_FMAX)
         if self.sR is not None and self._res_ev is not None:
@@ -615,10 +565,6 @@ class OverlappedPipeline(FramePipeline):
                 for f in range(nv):
                     self.on_result(group + f, f)       # e.g. enqueue the D2H copy of self.outs[f] on this stream
 
-    def _ss_stream(self, st):
-        import ctypes as C
-        self.eng._ck(self.eng.L.ss_set_hip_stream(self.eng.ctx, C.c_void_p(st.cuda_stream)))
-
     @torch.no_grad()
     def _capture(self):
         cur = torch.cuda.current_stream(self.dev)
@@ -626,26 +572,28 @@ class OverlappedPipeline(FramePipeline):
             st.wait_stream(cur)
         last = self.n - 1
         for i, b in enumerate(self.bufs):                       # eager warm-up in stage order (MIOpen find, allocator)
-            for j, fn in enumerate(self.stages):
+            for j, bodies in enumerate(self.stages):
                 with torch.cuda.stream(self.streams[j]):
-                    self._ss_stream(self.streams[j])
+                    self.eng.use_stream(self.streams[j])
                     for _ in range(2):
-                        fn(b)
+                        for fn in bodies:
+                            fn(b)
                         if j == last:
                             self._track_b(b)
                 self.streams[j].synchronize()
         for i, b in enumerate(self.bufs):
-            for j, fn in enumerate(self.stages):
+            for j, bodies in enumerate(self.stages):
                 with torch.cuda.stream(self.streams[j]):
-                    self._ss_stream(self.streams[j])
+                    self.eng.use_stream(self.streams[j])
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, stream=self.streams[j]):
-                        fn(b)
+                        for fn in bodies:
+                            fn(b)
                         if j == last and self.graph_mode == "all":
                             self._track_b(b)
                     self.graphs[j][i] = g
         torch.cuda.synchronize(self.dev)
-        self._ss_stream(self.sB)                                 # the tracker lives on the last stage's stream
+        self.eng.use_stream(self.sB)                                 # the tracker lives on the last stage's stream
         self.reset_tracker(-1)
         self._captured = True
 
@@ -750,3 +698,8 @@ class OverlappedPipeline(FramePipeline):
 
     def step(self, track: bool = True):
         raise RuntimeError("use begin_frame()/submit()/flush() on an OverlappedPipeline")
+
+    def close(self):
+        torch.cuda.synchronize(self.dev)
+        self.graphs = None                               # captured graphs reference the context's buffers: drop them first
+        super().close()

@@ -225,6 +225,58 @@ class Results:
         return 0 if self.boxes is None else len(self.boxes)
 
 
+class _HostResults:
+    """The pinned host side of F frames' results: counts, detection rows and (n_track_rows > 0) track rows in ONE pinned buffer
+    `res` — laid out as csrc ss_pack_results writes one frame: [2, F] counts (detections, tracks; int32 bits), dets [F, R, ld],
+    rows [F, n_track_rows, 8] — the prototypes or, from a YOLO(device_masks=True), the mask buffers, with keep_frames a device copy
+    of the frames, and the event after which a group handed over on a side stream may be read (`done`).  It lives on the model
+    (or in track_stream's ring) and refers to the pipeline, never the other way round: a pipeline that is dropped must be freed
+    at once, not by a later garbage collection (which may run inside a graph capture)."""
+
+    def __init__(self, model, pipe, b, F, n_track_rows=0, keep_frames=False):
+        self.pipe = pipe
+        R, ld = b.dets.shape[1:]
+        nd, no = F * R * ld, F * n_track_rows * 8
+        self.res = torch.zeros(2 * F + nd + no).pin_memory()
+        self.cnt = self.res[:2 * F].view(torch.int32).view(2, F)
+        self.dets = self.res[2 * F:2 * F + nd].view(F, R, ld)
+        self.rows = self.res[2 * F + nd:].view(F, n_track_rows, 8) if n_track_rows else None
+        dmask = pipe.nm and model.device_masks
+        self.proto = torch.empty((F,) + tuple(b.proto.shape[1:]), dtype=b.proto.dtype).pin_memory() if pipe.nm and not dmask else None
+        self.masks = model._mask_host(pipe, F, R) if dmask else None          # in place of proto
+        self.frames = torch.empty((F,) + tuple(b.frames.shape[1:]), dtype=torch.uint8, device=pipe.dev) if keep_frames else None
+        self.done = torch.cuda.Event()
+
+    def fetch(self, model, b, nv=1, outs=None, nouts=None, packed=False):
+        """Enqueue, on the current stream, the hand-over of buffer set b's first nv frames and their track rows outs [nv, 256, 8] /
+        counts nouts [nv] (None: detection only).  packed (one frame): counts and rows in one launch (ss_pack_results)."""
+        pipe = self.pipe
+        if packed:
+            pipe.eng.pack_results(b.ndets, b.dets[0], nouts, None if outs is None else outs[0], self.res)
+        else:
+            if outs is not None:
+                self.rows[:nv].copy_(outs, non_blocking=True)
+                self.cnt[1, :nv].copy_(nouts, non_blocking=True)
+            self.cnt[0, :nv].copy_(b.ndets[:nv], non_blocking=True)
+            self.dets[:nv].copy_(b.dets[:nv], non_blocking=True)
+        if self.masks is not None:
+            model._mask_launch(pipe, b.proto[:nv], b.dets[:nv], b.ndets[:nv], self.masks)
+        elif self.proto is not None:
+            self.proto[:nv].copy_(b.proto[:nv], non_blocking=True)
+        if self.frames is not None:
+            self.frames[:nv].copy_(b.frames[:nv], non_blocking=True)          # the set's frames, before the set is refilled
+
+    def results(self, model, f, image, track):
+        """Frame f as [Results], once the stream (or `done`) is synchronised."""
+        n, m = int(self.cnt[0, f]), int(self.cnt[1, f])
+        model._warn_if_capped(self.pipe, n, track)
+        res = model._results(image, self.pipe, self.dets[f, :n].clone(), self.rows[f, :m].clone() if track else None,
+                             None if self.proto is None else self.proto[f].clone(), model._mask_rows(self.masks, f, n))
+        if self.frames is not None:
+            res[0].orig_img_device = self.frames[f]
+        return res
+
+
 class YOLO:
     """`model = YOLO("yolo11n-pose.pt")` (yolo_multi_model.py:17).  `.track(frame)` / `.predict(frame)` replay HIP graphs
     captured once per (frame shape, overrides): the frame goes through a pinned host buffer, every stage runs on the
@@ -275,12 +327,11 @@ class YOLO:
         self.reid_batch = reid_batch
         pose = "pose" in self.arch
         self.names = {0: "person"} if pose else dict(enumerate(COCO_NAMES))
-        self._pipe = None
-        self._key = None
-        self._stream_pipe = None
-        self._stream_key = None
-        self._pred_pipe = None          # detection-only pipeline for predict() when max_det exceeds the tracker's 128 rows
-        self._pred_key = None
+        self._host = {}                 # slot name -> the _HostResults of a per-frame pipeline
+        self._pipe = None               # the cached pipelines (each with its .key): track() / predict(),
+        self._stream_pipe = None        # track_stream(),
+        self._pred_pipe = None          # and the detection-only one for predict() when max_det exceeds the tracker's 128 rows
+        self._cap_warned = self._tracker_warned = False           # warnings said once
         # test / bench hooks (synthetic head tensors, no weights exist offline): extra pipeline keywords and a callable
         # fill(buffers, virtual_stream, frame_index) that writes pred_in / anchor_gt / gt_feats before a frame runs
         self._pipe_kw = {"cmc": True} if camera_motion else {}    # N4: ECC camera-motion compensation (off by default)
@@ -327,92 +378,63 @@ class YOLO:
         pipe.eng.nms_set_classes(self.overrides.get("classes"))
         return pipe
 
-    # ---- per-frame path -------------------------------------------------------------------------------------
-    def _pipeline(self, image, device, need_reid=True):
-        from .pipeline import FramePipeline
-        key = self._state_key(image.shape[:2], device)
-        if self._pipe is None or key != self._key or (need_reid and not self._pipe.reid_loaded and self._pipe.feat_source == "reid"):
-            if self._pipe is not None:
-                self._pipe.close()
-            p = self._pipe = self._build(FramePipeline, image.shape[:2], device, need_reid=need_reid, graph="split")
-            self._key = key
-            self._frame_index = 0
-            H, W = image.shape[:2]
-            # one pinned buffer the device writes the frame's counts, detection rows and track rows into (csrc ss_pack_results): the host
-            # reads it after the call's one synchronisation, no copies in between
-            nd, no = p.dets.shape[1] * p.dets.shape[2], p.out.shape[1] * p.out.shape[2]
-            self._h_res = torch.zeros(2 + nd + no).pin_memory()
-            self._h_cnt = self._h_res[:2].view(torch.int32)
-            self._h_dets = self._h_res[2:2 + nd].view(p.dets.shape[1], p.dets.shape[2])
-            self._h_rows = self._h_res[2 + nd:].view(p.out.shape[1], p.out.shape[2])
-            self._h_proto = torch.empty(p.proto.shape[1:], dtype=p.proto.dtype).pin_memory() if p.nm and not self.device_masks else None
-            self._h_masks = self._mask_host(p, 1, p.dets.shape[1]) if p.nm and self.device_masks else None
-        return self._pipe
+    def _cached(self, slot, cls, shape, device, key=(), stale=None, **kw):
+        """The pipeline in `slot` (_pipe / _pred_pipe / _stream_pipe) for this frame shape, device and overrides (+ key): the one
+        built for them, else the old one closed and a new one built -> (pipeline, whether it is new)."""
+        key = self._state_key(shape, device) + key
+        pipe = getattr(self, slot)
+        if pipe is not None and pipe.key == key and not (stale and stale(pipe)):
+            return pipe, False
+        if pipe is not None:
+            pipe.close()
+        pipe = self._build(cls, shape, device, **kw)
+        pipe.key = key
+        setattr(self, slot, pipe)
+        return pipe, True
 
+    # ---- per-frame path -------------------------------------------------------------------------------------
     def _run(self, image, device, track):
-        # BYTE models: predict() has a detection-only pipeline of its own (its NMS threshold is overrides['conf'], the tracking
-        # pipeline's is track's), so that predict calls between track calls do not restart the tracker
-        if not track and (int(self.overrides["max_det"]) > 128 or self._byte):
-            return self._run_predict_wide(image, device)
-        pipe = self._pipeline(image, device, need_reid=track)
+        """One frame through a cached FramePipeline: upload, step, results through pinned memory, ONE synchronisation.
+        model.predict with max_det > 128 (the reference sets 1000, yolo_multi_model.py:21) has a detection-only pipeline whose NMS
+        keeps up to 1024 rows (`_pred_pipe`); the tracking pipeline (128 detections per frame) is not involved.  BYTE models' predict()
+        uses it too (its NMS threshold is overrides['conf'], the tracking pipeline's is track's), so that predict calls between track
+        calls do not restart the tracker."""
+        from .pipeline import FramePipeline
+        wide = not track and (int(self.overrides["max_det"]) > 128 or self._byte)
+        slot = "_pred_pipe" if wide else "_pipe"
+        if wide:
+            pipe, new = self._cached(slot, FramePipeline, image.shape[:2], device, graph="split", detect_only_rows=1024)
+        else:
+            pipe, new = self._cached(slot, FramePipeline, image.shape[:2], device, graph="split", need_reid=track,
+                                     stale=lambda p: track and not p.reid_loaded and p.feat_source == "reid")
+        if new:
+            # the tracking pipeline: one pinned buffer the device writes the frame's counts, detection rows and track rows into (csrc
+            # ss_pack_results), the host reads it after the call's one synchronisation, no copies in between; the wide one: two copies
+            self._host[slot] = _HostResults(self, pipe, pipe, 1, 0 if wide else pipe.out.shape[1])
+            if not wide:
+                self._frame_index = 0
         pipe.eng.upload(pipe.frames[0], image)
         if self._fill is not None:
             self._fill(pipe, 0, self._frame_index)
         pipe.step(track=track)
-        pipe.eng.pack_results(pipe.ndets, pipe.dets[0], pipe.nout if track else None, pipe.out[0] if track else None, self._h_res)
-        if self._h_masks is not None:
-            self._mask_launch(pipe, pipe.proto, pipe.dets, pipe.ndets, self._h_masks)
-        elif pipe.nm:
-            self._h_proto.copy_(pipe.proto[0], non_blocking=True)
+        h = self._host[slot]
+        h.fetch(self, pipe, 1, pipe.out if track else None, pipe.nout if track else None, packed=not wide)
         torch.cuda.current_stream(pipe.dev).synchronize()            # the one synchronisation of the call
         pipe.eng.check_errors()
-        self._frame_index += 1
-        n, m = int(self._h_cnt[0]), int(self._h_cnt[1])
-        self._warn_if_capped(pipe, n, track)
-        return self._results(image, pipe, self._h_dets[:n].clone(), self._h_rows[:m].clone() if track else None,
-                             self._h_proto.clone() if self._h_proto is not None else None, self._mask_rows(self._h_masks, 0, n))
+        if not wide:
+            self._frame_index += 1
+        return h.results(self, 0, image, track)
 
     def _warn_if_capped(self, pipe, n_kept, track):
         """The tracking pipeline carries at most pipe.max_det (<= 128, <= reid_batch) detections per frame, highest scores first;
         the reference's max_det = 1000 (yolo_multi_model.py:21) applies to its tracker too.  A frame that fills the cap may have
         lost lower-scored detections: say so once (capacity errors elsewhere are loud; this truncation used to be silent)."""
-        if track and n_kept >= pipe.max_det and pipe.max_det < int(self.overrides["max_det"]) and not getattr(self, "_cap_warned", False):
+        if track and n_kept >= pipe.max_det and pipe.max_det < int(self.overrides["max_det"]) and not self._cap_warned:
             import warnings
             self._cap_warned = True
             warnings.warn(f"a frame filled the tracker's per-frame limit of {pipe.max_det} detections (overrides['max_det'] = "
                           f"{self.overrides['max_det']}): lower-scored detections beyond it are not tracked "
-                          f"(limit = min(max_det, 128, reid_batch = {self.reid_batch}))", RuntimeWarning, stacklevel=3)
-
-    def _run_predict_wide(self, image, device):
-        """model.predict with max_det > 128 (the reference sets 1000, yolo_multi_model.py:21): a detection-only pipeline
-        whose NMS keeps up to 1024 rows; the tracking pipeline (128 detections per frame) is not involved."""
-        from .pipeline import FramePipeline
-        key = self._state_key(image.shape[:2], device)
-        if self._pred_pipe is None or key != self._pred_key:
-            if self._pred_pipe is not None:
-                self._pred_pipe.close()
-            p = self._pred_pipe = self._build(FramePipeline, image.shape[:2], device, graph="split", detect_only_rows=1024)
-            self._pred_key = key
-            self._hp_dets = torch.empty(p.dets.shape[1], p.dets.shape[2]).pin_memory()
-            self._hp_cnt = torch.zeros(1, dtype=torch.int32).pin_memory()
-            self._hp_proto = torch.empty(p.proto.shape[1:], dtype=p.proto.dtype).pin_memory() if p.nm and not self.device_masks else None
-            self._hp_masks = self._mask_host(p, 1, p.dets.shape[1]) if p.nm and self.device_masks else None
-        pipe = self._pred_pipe
-        pipe.eng.upload(pipe.frames[0], image)
-        if self._fill is not None:
-            self._fill(pipe, 0, self._frame_index)
-        pipe.step(track=False)
-        self._hp_dets.copy_(pipe.dets[0], non_blocking=True)
-        self._hp_cnt.copy_(pipe.ndets, non_blocking=True)
-        if self._hp_masks is not None:
-            self._mask_launch(pipe, pipe.proto, pipe.dets, pipe.ndets, self._hp_masks)
-        elif pipe.nm:
-            self._hp_proto.copy_(pipe.proto[0], non_blocking=True)
-        torch.cuda.current_stream(pipe.dev).synchronize()
-        pipe.eng.check_errors()
-        n = int(self._hp_cnt[0])
-        return self._results(image, pipe, self._hp_dets[:n].clone(), None,
-                             self._hp_proto.clone() if self._hp_proto is not None else None, self._mask_rows(self._hp_masks, 0, n))
+                          f"(limit = min(max_det, 128, reid_batch = {self.reid_batch}))", RuntimeWarning, stacklevel=4)
 
     # ---- device masks (device_masks=True) ---------------------------------------------------------------------
     MASK_CAP = 2048            # points per device polygon; a longer one is traced on the host (DESIGN.md: instance masks on the device)
@@ -487,13 +509,13 @@ class YOLO:
             raise ValueError(f"tracker={tracker!r}: this library tracks with StrongSORT only (accepted: {', '.join(self.TRACKERS)})")
         if self._byte:
             family = name.split(".")[0]
-            if family != self.tracker_type and not getattr(self, "_tracker_warned", False):
+            if family != self.tracker_type and not self._tracker_warned:
                 import warnings
                 self._tracker_warned = True
                 warnings.warn(f"tracker={tracker!r}: this model was built with tracker_type={self.tracker_type!r}, which rules; "
                               f"its parameters are strongsort_yolo_amd.config.ByteTrackConfig", RuntimeWarning, stacklevel=3)
             return
-        if not name.startswith("strongsort") and not getattr(self, "_tracker_warned", False):
+        if not name.startswith("strongsort") and not self._tracker_warned:
             import warnings
             self._tracker_warned = True
             warnings.warn(f"tracker={tracker!r} is an Ultralytics configuration; tracking runs StrongSORT (OSNet-x0.25 appearance + NSA Kalman), "
@@ -535,28 +557,15 @@ class YOLO:
             return
         self._conf_track = float(conf or 0.1) if self._byte else None
         try:
-            key = self._state_key(first.shape[:2], device) + (batch,)
-            if self._stream_pipe is None or key != self._stream_key:
-                if self._stream_pipe is not None:
-                    self._stream_pipe.close()
-                self._stream_pipe = self._build(OverlappedPipeline, first.shape[:2], device, graph="front", frame_batch=batch,
-                                                reid_split=(5 if self.arch == "yolov8n" else 2) if batch > 1 else None, defer_track=batch > 1)     # stage cut: bench.REID_SPLIT's sweep
-                self._stream_key = key
+            pipe, _ = self._cached("_stream_pipe", OverlappedPipeline, first.shape[:2], device, key=(batch,), graph="front", frame_batch=batch,
+                                   reid_split=(5 if self.arch == "yolov8n" else 2) if batch > 1 else None, defer_track=batch > 1)     # stage cut: bench.REID_SPLIT's sweep
         finally:
             self._conf_track = None
-        pipe = self._stream_pipe
         pipe.on_result = None
         pipe.flush()                                                      # groups an abandoned generator left in flight: tracked, results dropped
-        F, H, W = batch, first.shape[0], first.shape[1]
-        ring = 5                                                          # result slots: groups in flight (<= 3) + margin
-        h_rows = torch.empty(ring, F, pipe.outs.shape[2], 8).pin_memory()
-        h_dets = torch.empty(ring, F, pipe.bufs[0].dets.shape[1], pipe.bufs[0].dets.shape[2]).pin_memory()
-        h_cnt = torch.zeros(ring, 2, F, dtype=torch.int32).pin_memory()
-        dmask = pipe.nm and self.device_masks
-        h_proto = torch.empty((ring, F) + tuple(pipe.bufs[0].proto.shape[1:]), dtype=pipe.bufs[0].proto.dtype).pin_memory() if pipe.nm and not dmask else None
-        h_masks = [self._mask_host(pipe, F, pipe.bufs[0].dets.shape[1]) for _ in range(ring)] if dmask else None     # in place of h_proto
-        d_frames = torch.empty((ring, F, H, W, 3), dtype=torch.uint8, device=pipe.dev) if keep_device_frames else None
-        done = [torch.cuda.Event() for _ in range(ring)]
+        F = batch
+        # result slots: groups in flight (<= 3) + margin
+        ring = [_HostResults(self, pipe, pipe.bufs[0], F, pipe.outs.shape[2], keep_device_frames) for _ in range(5)]
         pending = []                                                      # (group index, frames of the group)
         state = {"group": 0, "first": {}, "enqueued": -1}                 # first frame index of a group -> group index
 
@@ -567,35 +576,19 @@ class YOLO:
             b, nv = pipe.cur_bufs, pipe.cur_valid                         # the set this tracker call read (the pipeline's own index, not g)
             if f != nv - 1:
                 return
-            slot = g % ring
-            h_rows[slot, :nv].copy_(pipe.outs[:nv, 0], non_blocking=True)
-            h_cnt[slot, 1, :nv].copy_(pipe.nouts[:nv, 0], non_blocking=True)
-            h_cnt[slot, 0, :nv].copy_(b.ndets[:nv], non_blocking=True)
-            h_dets[slot, :nv].copy_(b.dets[:nv], non_blocking=True)
-            if h_proto is not None:
-                h_proto[slot, :nv].copy_(b.proto[:nv], non_blocking=True)
-            if h_masks is not None:
-                self._mask_launch(pipe, b.proto[:nv], b.dets[:nv], b.ndets[:nv], h_masks[slot])
-            if d_frames is not None:
-                d_frames[slot, :nv].copy_(b.frames[:nv], non_blocking=True)       # the set's frames, before the set is refilled
-            done[slot].record(torch.cuda.current_stream(pipe.dev))
+            h = ring[g % len(ring)]
+            h.fetch(self, b, nv, pipe.outs[:nv, 0], pipe.nouts[:nv, 0])
+            h.done.record(torch.cuda.current_stream(pipe.dev))
             state["enqueued"] = g
             del state["first"][frame_idx - f]
 
         pipe.on_result = on_result
 
         def finish(g, imgs):
-            slot = g % ring
-            done[slot].synchronize()
+            h = ring[g % len(ring)]
+            h.done.synchronize()
             for f, img in enumerate(imgs):
-                n, m = int(h_cnt[slot, 0, f]), int(h_cnt[slot, 1, f])
-                self._warn_if_capped(pipe, n, True)
-                res = self._results(img, pipe, h_dets[slot, f, :n].clone(), h_rows[slot, f, :m].clone(),
-                                    None if h_proto is None else h_proto[slot, f].clone(),
-                                    None if h_masks is None else self._mask_rows(h_masks[slot], f, n))
-                if d_frames is not None:
-                    res[0].orig_img_device = d_frames[slot, f]
-                yield res
+                yield h.results(self, f, img, True)
 
         try:
             chunk = [first]
@@ -641,3 +634,4 @@ class YOLO:
             if p is not None:
                 p.close()
         self._pipe = self._stream_pipe = self._pred_pipe = None
+        self._host = {}

@@ -24,6 +24,6 @@ for i, nm in enumerate(("detect", "reid", "tracker")):
     print(f"{nm} graph + sync: %.3f ms" % t(lambda: (p.graph[i].replay(), sync())))
 def body():
     p.eng.upload(p.frames[0], img); p.step(track=True)
-    p.eng.pack_results(p.ndets, p.dets[0], p.nout, p.out[0], m._h_res); sync()
+    p.eng.pack_results(p.ndets, p.dets[0], p.nout, p.out[0], m._host["_pipe"].res); sync()
 print("_run body without check_errors / Results: %.3f ms" % t(body))
 print("check_errors: %.3f ms" % t(lambda: p.eng.check_errors()))

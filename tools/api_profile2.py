@@ -13,7 +13,7 @@ p = m._pipe
 steps = [
  ("upload", lambda i: p.eng.upload(p.frames[0], imgs[i % 8])),
  ("step", lambda i: p.step(track=True)),
- ("results", lambda i: p.eng.pack_results(p.ndets, p.dets[0], p.nout, p.out[0], m._h_res)),
+ ("results", lambda i: p.eng.pack_results(p.ndets, p.dets[0], p.nout, p.out[0], m._host["_pipe"].res)),
  ("sync", lambda i: torch.cuda.current_stream().synchronize()),
 ]
 acc = {k: 0.0 for k, _ in steps}
