@@ -71,6 +71,28 @@ def _ck(rc):
         raise _lib.SSError(rc, "fused op failed")
 
 
+def new_cl(x, c, hw=None):
+    """An uninitialised channels-last tensor with x's batch, dtype and device, `c` channels and x's (or the given) height and width."""
+    h, w = x.shape[2:] if hw is None else hw
+    return torch.empty((x.shape[0], c, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+
+
+def silu_conv(cv) -> bool:
+    """`cv` is a convolution + activation pair (nets.Conv) whose activation is SiLU."""
+    return isinstance(getattr(cv, "act", None), torch.nn.SiLU)
+
+
+def _cached(mod, name, like, build):
+    """The prepared copy `name` of a module's weights (a tensor, or nested tuples of them), kept in the module's __dict__ and built
+    again when the weights `like` moved to another device or dtype; clear_prepared drops it."""
+    t = first = mod.__dict__.get(name)
+    while isinstance(first, tuple):
+        first = first[0]
+    if t is None or first.device != like.device or first.dtype != like.dtype:
+        t = mod.__dict__[name] = build()
+    return t
+
+
 class valid_images:
     """`with valid_images(n_dev, batch):` — the OSNet-side launches of `batch` images made inside, on the current torch stream,
     compute only the first n_dev[0] (device int32) of them (packed ReID batches; csrc ss_op_set_valid_images: the setting
@@ -137,11 +159,7 @@ def pointwise_ok(conv) -> bool:
 
 def weight_nk(mod, conv):
     """[Cout, Cin] view of a 1x1 conv weight (already the layout k_pw stages), cached on the module."""
-    w = getattr(mod, "_w_nk", None)
-    if w is None or w.device != conv.weight.device or w.dtype != conv.weight.dtype:
-        w = conv.weight.detach().reshape(conv.weight.shape[0], -1).contiguous()
-        mod._w_nk = w
-    return w
+    return _cached(mod, "_w_nk", conv.weight, lambda: conv.weight.detach().reshape(conv.weight.shape[0], -1).contiguous())
 
 
 def pointwise(x, w_nk, bias, act="none", res=None, res_after=False, out=None, c_off=0, out2=None, c0=0):
@@ -155,7 +173,7 @@ def pointwise(x, w_nk, bias, act="none", res=None, res_after=False, out=None, c_
         res = _cl(res)
     ret = out
     if out is None:
-        ret = out = torch.empty((b, n, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        ret = out = new_cl(x, n)
     dst = C.c_void_p(out.data_ptr() + 2 * c_off)
     _ck(_lib.load().ss_op_pointwise_f16(_st(x), _p(x), _p(w_nk), _p(bias), _p(res), b * h * w, k, n, ACT[act], int(res_after),
                                         dst, out.shape[1], _p(out2), c0, 0 if out2 is None else out2.shape[1]))
@@ -173,11 +191,7 @@ def conv3x3_ok(conv) -> bool:
 
 def weight_n9k(mod, conv):
     """[Cout, 3*3*Cin] (tap-major, channel-minor) copy of a 3x3 conv weight, cached on the module."""
-    w = getattr(mod, "_w_n9k", None)
-    if w is None or w.device != conv.weight.device or w.dtype != conv.weight.dtype:
-        w = conv.weight.detach().permute(0, 2, 3, 1).reshape(conv.weight.shape[0], -1).contiguous()
-        mod._w_n9k = w
-    return w
+    return _cached(mod, "_w_n9k", conv.weight, lambda: conv.weight.detach().permute(0, 2, 3, 1).reshape(conv.weight.shape[0], -1).contiguous())
 
 
 def conv3x3(x, w_n9k, bias, stride=1, act="none", res=None, res_after=False, out=None, c_off=0, out2=None, c0=0):
@@ -190,7 +204,7 @@ def conv3x3(x, w_n9k, bias, stride=1, act="none", res=None, res_after=False, out
         res = _cl(res)
     ret = out
     if out is None:
-        ret = out = torch.empty((b, n, oh, ow), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        ret = out = new_cl(x, n, (oh, ow))
     dst = C.c_void_p(out.data_ptr() + 2 * c_off)
     _ck(_lib.load().ss_op_conv3x3_f16(_st(x), _p(x), _p(w_n9k), _p(bias), _p(res), b, h, w, k, n, stride, ACT[act], int(res_after),
                                       dst, out.shape[1], _p(out2), c0, 0 if out2 is None else out2.shape[1]))
@@ -203,7 +217,7 @@ BNECK = _flag("BNECK")                  # a C2f bottleneck (3x3 + 3x3 + shortcut
 
 def bottleneck_ok(m) -> bool:
     a, b = m.cv1.conv, m.cv2.conv
-    silu = all(type(cv.act).__name__ == "SiLU" for cv in (m.cv1, m.cv2))
+    silu = silu_conv(m.cv1) and silu_conv(m.cv2)
     return (BNECK and silu and conv3x3_ok(a) and conv3x3_ok(b) and a.stride == (1, 1) and b.stride == (1, 1)
             and a.in_channels == a.out_channels == b.out_channels and a.in_channels in BNECK_C)
 
@@ -221,7 +235,7 @@ def bottleneck(x, m, out, c_off, out2=None):
 def bottleneck_padded_ok(m) -> bool:
     """A Bottleneck c -> c/2 -> c (v11's e = 0.5) can run on k_bneck with its hidden width zero-padded to c."""
     a, b = m.cv1.conv, m.cv2.conv
-    silu = all(type(cv.act).__name__ == "SiLU" for cv in (m.cv1, m.cv2))
+    silu = silu_conv(m.cv1) and silu_conv(m.cv2)
     return (BNECK and silu and conv3x3_ok(a) and conv3x3_ok(b) and a.stride == (1, 1) and b.stride == (1, 1) and a.in_channels == b.out_channels
             and a.out_channels == b.in_channels and a.out_channels < a.in_channels and a.in_channels in BNECK_C)
 
@@ -233,8 +247,7 @@ def bottleneck_padded(x, m, out, c_off, out2=None):
     x = _cl(x)
     b, c, h, w = x.shape
     a, bb = m.cv1.conv, m.cv2.conv
-    p = getattr(m, "_padded", None)
-    if p is None or p[0].device != a.weight.device or p[0].dtype != a.weight.dtype:
+    def build():
         hid = a.out_channels
         w1 = torch.zeros(c, 3, 3, c, device=a.weight.device, dtype=a.weight.dtype)
         w1[:hid] = a.weight.detach().permute(0, 2, 3, 1)
@@ -242,7 +255,8 @@ def bottleneck_padded(x, m, out, c_off, out2=None):
         b1[:hid] = a.bias.detach()
         w2 = torch.zeros(c, 3, 3, c, device=a.weight.device, dtype=a.weight.dtype)
         w2[:, :, :, :hid] = bb.weight.detach().permute(0, 2, 3, 1)
-        p = m._padded = (w1.reshape(c, -1).contiguous(), b1, w2.reshape(c, -1).contiguous())
+        return w1.reshape(c, -1).contiguous(), b1, w2.reshape(c, -1).contiguous()
+    p = _cached(m, "_padded", a.weight, build)
     _ck(_lib.load().ss_op_bottleneck_f16(_st(x), _p(x), _p(p[0]), _p(p[1]), _p(p[2]), _p(bb.bias), b, h, w, c, int(m.add),
                                          C.c_void_p(out.data_ptr() + 2 * c_off), out.shape[1], _p(out2)))
     return out
@@ -262,7 +276,7 @@ def conv_group(items):
         b, cin, h, wd = x.shape
         N = w.shape[0]
         oh, ow = (h - 1) // stride + 1, (wd - 1) // stride + 1
-        y = torch.empty((b, N, oh, ow), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        y = new_cl(x, N, (oh, ow))
         d.x, d.w, d.bias, d.out = x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr()
         d.B, d.H, d.W, d.Cin, d.N, d.ksize, d.stride, d.act = b, h, wd, cin, N, ksize, stride, ACT[act]
         outs.append(y); keep.append(x)
@@ -285,7 +299,7 @@ def head_level_ok(x, box_seq, cls_seq) -> bool:
     for seq, cm in ((box_seq, 64), (cls_seq, 80)):
         a, b, c = seq[0], seq[1], seq[2]
         if not (hasattr(a, "conv") and hasattr(b, "conv") and conv3x3_ok(a.conv) and conv3x3_ok(b.conv) and a.conv.stride == (1, 1)
-                and b.conv.stride == (1, 1) and type(a.act).__name__ == "SiLU" and type(b.act).__name__ == "SiLU"
+                and b.conv.stride == (1, 1) and silu_conv(a) and silu_conv(b)
                 and a.conv.in_channels == x.shape[1] and a.conv.out_channels == cm and b.conv.in_channels == cm and b.conv.out_channels == cm
                 and pointwise_ok(c) and c.in_channels == cm and c.out_channels <= cm):
             return False
@@ -303,7 +317,7 @@ def head_level(x, box_seq, cls_seq, tile16=None):
         w1.append(weight_n9k(seq[0], seq[0].conv)); b1.append(seq[0].conv.bias)
         w2.append(weight_n9k(seq[1], seq[1].conv)); b2.append(seq[1].conv.bias)
         w3.append(weight_nk(seq[2], seq[2])); b3.append(seq[2].bias)
-        outs.append(torch.empty((b, seq[2].out_channels, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last))
+        outs.append(new_cl(x, seq[2].out_channels))
     nout = (C.c_int * 2)(*[o.shape[1] for o in outs])
     t16 = HEAD_TILE16 if tile16 is None else bool(tile16)
     _ck(_lib.load().ss_op_head_f16(_st(x), _p(x), arr(w1), arr(b1), arr(w2), arr(b2), arr(w3), arr(b3), arr(outs), nout, b, h, w, cin, int(t16)))
@@ -372,11 +386,7 @@ def dw3x3_ok(conv) -> bool:
 
 def weight_dw9(mod, conv):
     """[9, C] (tap-major) copy of a depthwise 3x3 weight, cached on the module."""
-    w = getattr(mod, "_w_dw9", None)
-    if w is None or w.device != conv.weight.device or w.dtype != conv.weight.dtype:
-        w = conv.weight.detach().reshape(conv.weight.shape[0], 9).t().contiguous()
-        mod._w_dw9 = w
-    return w
+    return _cached(mod, "_w_dw9", conv.weight, lambda: conv.weight.detach().reshape(conv.weight.shape[0], 9).t().contiguous())
 
 
 PREPARED = ("_w_nk", "_w_n9k", "_w_dw9", "_w_t", "_w_c0", "_w_stem", "_w1", "_w9", "_padded", "_padded_last", "_w12_", "_w_pair_", "_sw", "_gw",
@@ -396,24 +406,23 @@ def clear_prepared(module):
 def padded_last(mod, conv):
     """A 1x1 Conv2d whose output count is not a multiple of 8 (the class branch of a one-class head) as (w_nk, bias) zero-padded to 8
     rows, cached on `mod`; conv.in_channels % 8 == 0."""
-    p = getattr(mod, "_padded_last", None)
-    if p is None or p[0].device != conv.weight.device or p[0].dtype != conv.weight.dtype:
+    def build():
         n, np_ = conv.out_channels, (conv.out_channels + 7) // 8 * 8
         w = torch.zeros(np_, conv.in_channels, device=conv.weight.device, dtype=conv.weight.dtype)
         w[:n] = conv.weight.detach().reshape(n, -1)
         b = torch.zeros(np_, device=conv.weight.device, dtype=conv.weight.dtype)
         b[:n] = conv.bias.detach()
-        p = mod._padded_last = (w, b)
-    return p
+        return w, b
+    return _cached(mod, "_padded_last", conv.weight, build)
 
 
 def padded_branch(mod, seq, mult=16):
     """A head branch Conv 3x3 -> Conv 3x3 -> Conv2d 1x1 whose hidden width is not a multiple of 8 (the pose branch: 51 channels) as
     zero-padded weights the convolution kernels take: [(w_n9k, bias)] x 2 + (w_nk, bias) with the hidden width rounded up to `mult`
     and the output rows to 8; the padded channels carry exact zeros (SiLU(0) = 0).  Cached on `mod`."""
-    p = getattr(mod, "_padded", None)
     c0 = seq[0].conv
-    if p is None or p[0][0].device != c0.weight.device or p[0][0].dtype != c0.weight.dtype:
+
+    def build():
         up = lambda v, m: (v + m - 1) // m * m
         h, hp = c0.out_channels, up(c0.out_channels, mult)
         n, np_ = seq[2].out_channels, up(seq[2].out_channels, 8)
@@ -427,10 +436,9 @@ def padded_branch(mod, seq, mult=16):
             o = torch.zeros(rows, device=dev, dtype=dt)
             o[:b.shape[0]] = b.detach()
             return o
-        p = mod._padded = ((pad(c0.weight, hp, c0.in_channels), padb(c0.bias, hp)),
-                           (pad(seq[1].conv.weight, hp, hp), padb(seq[1].conv.bias, hp)),
-                           (pad(seq[2].weight, np_, hp), padb(seq[2].bias, np_)))
-    return p
+        return ((pad(c0.weight, hp, c0.in_channels), padb(c0.bias, hp)), (pad(seq[1].conv.weight, hp, hp), padb(seq[1].conv.bias, hp)),
+                (pad(seq[2].weight, np_, hp), padb(seq[2].bias, np_)))
+    return _cached(mod, "_padded", c0.weight, build)
 
 
 def dwconv3x3(x, w9, bias, act="relu"):
@@ -471,23 +479,22 @@ def conv0_ok(x, conv) -> bool:
 def conv0_weight(mod, conv):
     """[4][3][Cout][16]: for conv columns c = 4n + r, per (ky, out channel) the 9 (kx, ch) taps in the order they lie in an
     NHWC input row, placed (6r + 5) % 8 halfs into a 16-wide K window of two aligned 8-half blocks (k_conv0)."""
-    w = getattr(mod, "_w_c0", None)
-    if w is None or w.device != conv.weight.device or w.dtype != conv.weight.dtype:
+    def build():
         co = conv.out_channels
         taps = conv.weight.detach().permute(2, 0, 3, 1).reshape(3, co, 9)           # [ky][oc][3*kx + ch]
         w = torch.zeros(4, 3, co, 16, dtype=conv.weight.dtype, device=conv.weight.device)
         for r in range(4):
             sh = (6 * r + 5) % 8
             w[r, :, :, sh:sh + 9] = taps
-        mod._w_c0 = w
-    return w
+        return w
+    return _cached(mod, "_w_c0", conv.weight, build)
 
 
 def conv0(x, w_prep, bias, act="silu"):
     x = _cl(x)
     n, c, h, w = x.shape
     co = w_prep.shape[2]
-    y = torch.empty((n, co, (h - 1) // 2 + 1, w // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    y = new_cl(x, co, ((h - 1) // 2 + 1, w // 2))
     _ck(_lib.load().ss_op_conv0_f16(_st(x), _p(x), _p(w_prep), _p(bias), _p(y), n, h, w, co, ACT[act]))
     return y
 
@@ -504,15 +511,14 @@ def stem_ok(x, conv) -> bool:
 def stem_weight(mod, conv):
     """[4][7][16][32]: for conv columns c = 4n + r (r = 0..3), per (ky, out channel) the 21 (kx, ch) taps in the order they lie
     in an NHWC input row, placed (6r + 7) % 8 halfs into a 32-wide K window of aligned 8-half blocks (k_osnet_stem)."""
-    w = getattr(mod, "_w_stem", None)
-    if w is None or w.device != conv.weight.device or w.dtype != conv.weight.dtype:
+    def build():
         taps = conv.weight.detach().permute(2, 0, 3, 1).reshape(7, 16, 21)          # [ky][oc][3*kx + ch]
         w = torch.zeros(4, 7, 16, 32, dtype=conv.weight.dtype, device=conv.weight.device)
         for r in range(4):
             sh = (6 * r + 7) % 8
             w[r, :, :, sh:sh + 21] = taps
-        mod._w_stem = w
-    return w
+        return w
+    return _cached(mod, "_w_stem", conv.weight, build)
 
 
 STEM_CONV1 = _flag("STEM_CONV1")        # the first OSBlock's conv1 (16 -> 16) on the stem's pooled tile
@@ -522,7 +528,7 @@ def osnet_stem(x, w_prep, bias, conv1=None):
     """conv1 = (w [16,16], b [16]): also returns relu(conv1x1(y, w) + b) (the first OSBlock's conv1) from the same launch."""
     x = _cl(x)
     n, c, h, w = x.shape
-    y = torch.empty((n, 16, h // 4, w // 4), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    y = new_cl(x, 16, (h // 4, w // 4))
     y1 = torch.empty_like(y, memory_format=torch.channels_last) if conv1 is not None else None
     w1, b1 = conv1 if conv1 is not None else (None, None)
     _ck(_lib.load().ss_op_osnet_stem_f16(_st(x), _p(x), _p(w_prep), _p(bias), _p(y), n, h, w, _p(w1), _p(b1), _p(y1)))
@@ -596,9 +602,9 @@ def osnet_tail(ys, psum, gate_w, w3, b3, idn, want_out, w4, b4, pool, down=None)
     idn = _cl(idn)
     c2, n2 = w3.shape[0], w4.shape[0]
     c1, wd, bd = (idn.shape[1], down[0], down[1]) if down is not None else (0, None, None)       # down: shortcut = conv1x1(idn, wd) + bd
-    out = torch.empty((n, c2, h, w), dtype=idn.dtype, device=idn.device, memory_format=torch.channels_last) if want_out else None
+    out = new_cl(idn, c2, (h, w)) if want_out else None
     oh, ow = (h // 2, w // 2) if pool else (h, w)
-    out2 = torch.empty((n, n2, oh, ow), dtype=idn.dtype, device=idn.device, memory_format=torch.channels_last)
+    out2 = new_cl(idn, n2, (oh, ow))
     arr = (C.c_void_p * 4)(*[y.data_ptr() for y in ys])
     gw1, gb1, gw2, gb2 = gate_w
     gates = torch.empty((n, 4, 32), dtype=torch.float32, device=idn.device)
@@ -625,7 +631,7 @@ def maxpool(x, k, stride, pad):
     if c % 8:
         return torch.nn.functional.max_pool2d(x, k, stride, pad)
     oh, ow = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-    y = torch.empty((n, c, oh, ow), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    y = new_cl(x, c, (oh, ow))
     _ck(_lib.load().ss_op_maxpool_f16(_st(x), _p(x), _p(y), n, h, w, c, k, stride, pad))
     return y
 
@@ -643,7 +649,7 @@ def upcat(lo, hi, lo_first=True):
     lo, hi = _cl(lo), _cl(hi)
     b, c1, h, w = lo.shape
     c2 = hi.shape[1]
-    out = torch.empty((b, c1 + c2, 2 * h, 2 * w), dtype=lo.dtype, device=lo.device, memory_format=torch.channels_last)
+    out = new_cl(lo, c1 + c2, (2 * h, 2 * w))
     _ck(_lib.load().ss_op_upcat_f16(_st(lo), _p(lo), _p(hi), _p(out), b, h, w, c1, c2, int(lo_first)))
     return out
 
@@ -656,7 +662,7 @@ def sppf_pools(x):
     """cat(x, m(x), m(m(x)), m(m(m(x)))) with m = max_pool2d(5, 1, 2), one launch."""
     x = _cl(x)
     b, c, h, w = x.shape
-    out = torch.empty((b, 4 * c, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    out = new_cl(x, 4 * c)
     _ck(_lib.load().ss_op_sppf_pools_f16(_st(x), _p(x), _p(out), b, h, w, c))
     return out
 
@@ -689,7 +695,7 @@ def psa_attention(qkv, pe, heads, scale):
     softmax(scale q^T k) applied to v, + pe: [B, heads*64, H, W] channels-last."""
     qkv = _cl(qkv)
     b, _, h, w = qkv.shape
-    out = torch.empty((b, heads * 64, h, w), dtype=qkv.dtype, device=qkv.device, memory_format=torch.channels_last)
+    out = new_cl(qkv, heads * 64)
     _ck(_lib.load().ss_op_psa_attention_f16(_st(qkv), _p(qkv), _p(_cl(pe) if pe is not None else None), _p(out), b, h * w, heads, float(scale)))
     return out
 
@@ -700,7 +706,7 @@ def avgpool2(x):
     n, c, h, w = x.shape
     if c % 8 or h % 2 or w % 2:
         return torch.nn.functional.avg_pool2d(x, 2, 2)
-    y = torch.empty((n, c, h // 2, w // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    y = new_cl(x, c, (h // 2, w // 2))
     _ck(_lib.load().ss_op_avgpool2_f16(_st(x), _p(x), _p(y), n, h, w, c))
     return y
 
@@ -721,8 +727,4 @@ def is_pointwise(conv) -> bool:
 
 def weight_t(mod, conv):
     """[Cin, Cout] contiguous copy of a 1x1 conv weight, cached on the module (inference: weights are static)."""
-    wt = getattr(mod, "_w_t", None)
-    if wt is None or wt.device != conv.weight.device or wt.dtype != conv.weight.dtype:
-        wt = conv.weight.detach().reshape(conv.weight.shape[0], -1).t().contiguous()
-        mod._w_t = wt
-    return wt
+    return _cached(mod, "_w_t", conv.weight, lambda: conv.weight.detach().reshape(conv.weight.shape[0], -1).t().contiguous())

@@ -21,6 +21,8 @@ import torch.nn.functional as F
 
 from . import fused, fused32
 
+_new, _silu = fused.new_cl, fused.silu_conv       # a channels-last tensor like x with c channels; "is this a SiLU Conv"
+
 
 # --------------------------------------------------------------------------------------------------
 # YOLO building blocks
@@ -33,7 +35,7 @@ class Conv(nn.Module):
 
     def forward(self, x, out=None, res=None):
         """out / res (fp32 kernels only): write into this channels-last tensor / channel slice; add `res` after the activation."""
-        act = "silu" if isinstance(self.act, nn.SiLU) else ("none" if isinstance(self.act, nn.Identity) else None)
+        act = "silu" if _silu(self) else ("none" if isinstance(self.act, nn.Identity) else None)
         if act is not None and fused32.conv_ok(x, self.conv):       # fp32: one implicit-GEMM launch, bias + SiLU (+ shortcut) in its epilogue
             return fused32.conv(x, self, self.conv, act, out=out, res=res)
         if act is not None and fused32.conv0_ok(x, self.conv):
@@ -45,21 +47,35 @@ class Conv(nn.Module):
                 return y
             out.copy_(y)
             return out
-        if fused.usable(x):
-            c = self.conv
-            act = "silu" if isinstance(self.act, nn.SiLU) else "none"
-            if fused.pointwise_ok(c):        # 1x1: own MFMA kernel, bias + SiLU in its epilogue (one launch)
-                return fused.pointwise(x, fused.weight_nk(self, c), c.bias, act)
-            if fused.conv3x3_ok(c):          # 3x3: the same kernel as an implicit GEMM
-                return fused.conv3x3(x, fused.weight_n9k(self, c), c.bias, c.stride[0], act)
+        return self.place(x) if fused.usable(x) else self.act(self.conv(x))
+
+    def place(self, x, out=None, c_off=0, out2=None, c0=0, res=None, res_after=False):
+        """The one way to say "this convolution writes there": act(conv(x) + bias) (+ res; res_after: after the activation and its
+        rounding to half) in one launch on this module's own prepared weight, into channels [c_off, c_off + c2) of the channels-last
+        tensor `out` (none: a fresh dense tensor), channels [c0, c0 + out2.C) of the result mirrored into the dense tensor `out2`.
+        Returns `out`.  Tensors the f16 kernels do not take (fp32, CPU) go through forward with that channel slice: the fp32 kernels
+        write, and read, a strided slice, so nobody needs a mirror there."""
+        c = self.conv
+        if not fused.usable(x):
+            return self(x, out=None if out is None else out[:, c_off:c_off + c.out_channels], res=res)
+        act = "silu" if _silu(self) else "none"
+        where = dict(res=res, res_after=res_after, out=out, c_off=c_off, out2=out2, c0=c0)
+        if fused.pointwise_ok(c):            # 1x1: own MFMA kernel, bias + SiLU in its epilogue (one launch)
+            return fused.pointwise(x, fused.weight_nk(self, c), c.bias, act, **where)
+        if fused.conv3x3_ok(c):              # 3x3: the same kernel as an implicit GEMM
+            return fused.conv3x3(x, fused.weight_n9k(self, c), c.bias, c.stride[0], act, **where)
+        if out is None and res is None:
             if fused.conv0_ok(x, c):         # the first convolution (3 input channels, stride 2)
                 return fused.conv0(x, fused.conv0_weight(self, c), c.bias, act)
             if fused.dw3x3_ok(c):            # depthwise 3x3 (v11 head): MIOpen has only its naive kernel for these (55 us a launch)
                 return fused.dwconv3x3(x, fused.weight_dw9(self, c), c.bias, act)
-            # k x k: conv without bias (MIOpen) + one fused bias+SiLU pass
-            y = F.conv2d(x, c.weight, None, c.stride, c.padding, c.dilation, c.groups)
+        # k x k: conv without bias (MIOpen) + one fused bias+SiLU pass, which places the result
+        y = F.conv2d(x, c.weight, None, c.stride, c.padding, c.dilation, c.groups)
+        if out is None and res is None:
             return fused.bias_act_(y, c.bias, act)
-        return self.act(self.conv(x))
+        out = _new(y, c.out_channels) if out is None else out
+        fused.bias_act_place(y, c.bias, act, out, c_off, res=res, res_after=res_after, out2=out2, c0=c0)
+        return out
 
 
 class Bottleneck(nn.Module):
@@ -75,6 +91,53 @@ class Bottleneck(nn.Module):
         return x + self.cv2(self.cv1(x)) if self.add else self.cv2(self.cv1(x))
 
 
+def _place_bneck(m, x, out, c_off, out2=None):
+    """Bottleneck `m` of x (shortcut included) into channels [c_off, c_off + c) of `out` (+ the dense copy `out2`): one launch where
+    k_bneck covers the block, else its first convolution and a second one that adds the shortcut and places the sum."""
+    if fused.usable(x) and fused.bottleneck_ok(m):      # both convolutions + shortcut + placement in one launch (csrc k_bneck)
+        fused.bottleneck(x, m, out, c_off, out2=out2)
+    else:
+        m.cv2.place(m.cv1(x), out, c_off, out2, 0, res=x if m.add else None, res_after=True)
+
+
+def _c2f_placed(blk, x, inner, also=None, c_off=0):
+    """C2f / C3k2 without chunk / add / cat launches: every producer's epilogue writes straight into its channel slice of the concat
+    buffer; `inner(m, x, cat, c_off, out2)` places inner block m.  The f16 3x3 kernels read dense inputs, so there every producer
+    also mirrors the half the next block reads; the fp32 kernel reads the strided slice itself.
+    also / c_off: the last 1x1 also writes the block's output into channels [c_off, c_off + c2) of `also` (a later concat's buffer)."""
+    c, n, half = blk.c, len(blk.m), fused.usable(x)
+    cat = _new(x, (2 + n) * c)
+    cur = _new(x, c) if half else None
+    blk.cv1.place(x, cat, 0, cur, c)
+    for i, m in enumerate(blk.m):
+        nxt = _new(x, c) if half and i + 1 < n else None
+        inner(m, cur if half else cat[:, (1 + i) * c:(2 + i) * c], cat, (2 + i) * c, nxt)
+        cur = nxt
+    cv2 = blk.cv2
+    if also is None:
+        return cv2(cat)
+    if not half:                         # the block's output is its slice of `also`
+        return cv2.place(cat, also, c_off)
+    if fused.pointwise_ok(cv2.conv) and _silu(cv2):
+        y = _new(x, cv2.conv.out_channels)
+        cv2.place(cat, also, c_off, y, 0)
+        return y
+    return _put(also, c_off, cv2(cat))
+
+
+def _c2f_torch(blk, x, also=None, c_off=0):
+    y = list(blk.cv1(x).chunk(2, 1))
+    for m in blk.m:
+        y.append(m(y[-1]))
+    y = blk.cv2(torch.cat(y, 1))
+    return y if also is None else _put(also, c_off, y)
+
+
+def _put(buf, c_off, y):
+    buf[:, c_off:c_off + y.shape[1]] = y
+    return y
+
+
 class C2f(nn.Module):
     def __init__(self, c1, c2, n=1, shortcut=False):
         super().__init__()
@@ -84,76 +147,31 @@ class C2f(nn.Module):
         self.m = nn.ModuleList(Bottleneck(self.c, self.c, shortcut, e=1.0) for _ in range(n))
 
     def placed_ok(self, x) -> bool:
-        return fused.usable(x) and fused.place_ok(self.c, (2 + len(self.m)) * self.c) and all(type(m) is Bottleneck for m in self.m)
+        """The f16 kernels place this block; or the fp32 one does (every producer writes its slice, every consumer reads one)."""
+        if not all(type(m) is Bottleneck for m in self.m):
+            return False
+        return (fused.usable(x) and fused.place_ok(self.c, (2 + len(self.m)) * self.c)) or fused32.conv_ok(x, self.cv1.conv)
 
     def forward(self, x, also=None, c_off=0):
         """also / c_off: the block's output is ALSO written into channels [c_off, c_off + c2) of the channels-last tensor `also` (a
-        later concat's buffer) by the last 1x1's epilogue — only with the placed path (placed_ok) and a pointwise-capable cv2."""
-        if self.placed_ok(x):
-            return self._forward_placed(x, also, c_off)
-        if fused32.conv_ok(x, self.cv1.conv) and all(type(m) is Bottleneck for m in self.m):
-            # fp32 kernels: every producer writes its channel slice of the concat buffer, every consumer reads a slice — no chunk / add / cat pass
-            c, n = self.c, len(self.m)
-            B, _, H, W = x.shape
-            cat = torch.empty((B, (2 + n) * c, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            self.cv1(x, out=cat[:, :2 * c])
-            for i, m in enumerate(self.m):
-                m(cat[:, (1 + i) * c:(2 + i) * c], out=cat[:, (2 + i) * c:(3 + i) * c])
-            if also is not None:         # the last 1x1 writes its slice of a later concat's buffer; the block's output is that slice
-                return self.cv2(cat, out=also[:, c_off:c_off + self.cv2.conv.out_channels])
-            return self.cv2(cat)
-        y = list(self.cv1(x).chunk(2, 1))
-        for m in self.m:
-            y.append(m(y[-1]))
-        y = self.cv2(torch.cat(y, 1))
-        if also is not None:
-            also[:, c_off:c_off + y.shape[1]] = y
-        return y
-
-    def _forward_placed(self, x, also=None, c_off=0):
-        """Same arithmetic, no chunk / add / cat launches: every producer's bias+SiLU epilogue writes straight into
-        its channel slice of the concat buffer (and a dense copy of the half the next 3x3 conv reads)."""
-        c, n = self.c, len(self.m)
-        B, _, H, W = x.shape
-        cat = torch.empty((B, (2 + n) * c, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        dense = lambda: torch.empty((B, c, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        cv = self.cv1.conv
-        cur = dense()
-        if fused.pointwise_ok(cv):
-            fused.pointwise(x, fused.weight_nk(self.cv1, cv), cv.bias, "silu", out=cat, c_off=0, out2=cur, c0=c)
-        else:
-            fused.bias_act_place(F.conv2d(x, cv.weight, None, cv.stride, cv.padding), cv.bias, "silu", cat, 0, out2=cur, c0=c)
-        for i, m in enumerate(self.m):
-            cv = m.cv2.conv
-            nxt = dense() if i + 1 < n else None
-            if fused.bottleneck_ok(m):       # both convolutions + shortcut + placement in one launch (csrc k_bneck)
-                fused.bottleneck(cur, m, cat, (2 + i) * c, out2=nxt)
-            elif fused.conv3x3_ok(cv):       # conv + bias + SiLU + shortcut + placement in one launch
-                fused.conv3x3(m.cv1(cur), fused.weight_n9k(m.cv2, cv), cv.bias, cv.stride[0], "silu", res=cur if m.add else None,
-                              res_after=True, out=cat, c_off=(2 + i) * c, out2=nxt, c0=0)
-            else:
-                t = F.conv2d(m.cv1(cur), cv.weight, None, cv.stride, cv.padding)
-                fused.bias_act_place(t, cv.bias, "silu", cat, (2 + i) * c, res=cur if m.add else None, res_after=True,
-                                     out2=nxt, c0=0)
-            cur = nxt
-        cv = self.cv2.conv
-        if also is not None and fused.pointwise_ok(cv) and isinstance(self.cv2.act, nn.SiLU):
-            y = torch.empty((B, cv.out_channels, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            fused.pointwise(cat, fused.weight_nk(self.cv2, cv), cv.bias, "silu", out=also, c_off=c_off, out2=y, c0=0)
-            return y
-        y = self.cv2(cat)
-        if also is not None:
-            also[:, c_off:c_off + y.shape[1]] = y
-        return y
+        later concat's buffer), by the last 1x1's epilogue where the block is placed (_c2f_placed)."""
+        return (_c2f_placed(self, x, _place_bneck, also, c_off) if self.placed_ok(x) else _c2f_torch(self, x, also, c_off))
 
 
 def _w_pair(mod, a, b):
     """Two 1x1 convolutions on the same input as one: (weights [Ca + Cb, Cin], bias), cached on `mod`."""
-    w = getattr(mod, "_w_pair_", None)
-    if w is None or w[0].device != a.weight.device or w[0].dtype != a.weight.dtype:
-        w = mod._w_pair_ = (torch.cat((a.weight.detach().reshape(a.out_channels, -1), b.weight.detach().reshape(b.out_channels, -1)), 0).contiguous(),
-                            torch.cat((a.bias.detach(), b.bias.detach())).contiguous())
-    return w
+    return fused._cached(mod, "_w_pair_", a.weight, lambda: (
+        torch.cat((a.weight.detach().reshape(a.out_channels, -1), b.weight.detach().reshape(b.out_channels, -1)), 0).contiguous(),
+        torch.cat((a.bias.detach(), b.bias.detach())).contiguous()))
+
+
+def _open_pair(mod, x, ctot, c0):
+    """[cv1 | cv2] of `mod` in one pointwise launch into channels [0, 2 c_) of a fresh concat buffer of `ctot` channels, the half at
+    channel c0 mirrored densely for the 3x3 convolutions that follow -> (buffer, mirror)."""
+    buf, cur = _new(x, ctot), _new(x, mod.cv1.conv.out_channels)
+    w12, b12 = _w_pair(mod, mod.cv1.conv, mod.cv2.conv)
+    fused.pointwise(x, w12, b12, "silu", out=buf, c_off=0, out2=cur, c0=c0)
+    return buf, cur
 
 
 class C3(nn.Module):
@@ -165,16 +183,15 @@ class C3(nn.Module):
 
     def forward(self, x):
         if fused.C3K2 and fused.usable(x) and self.placed_ok():
-            B, _, H, W = x.shape
-            out = torch.empty((B, self.cv3.conv.out_channels, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+            out = _new(x, self.cv3.conv.out_channels)
             self.forward_placed(x, out, 0)
             return out
         return self.cv3(torch.cat((self.m(self.cv1(x)), self.cv2(x)), 1))
 
     def placed_ok(self) -> bool:
         a, b, c3 = self.cv1.conv, self.cv2.conv, self.cv3.conv
-        silu = all(isinstance(cv.act, nn.SiLU) for cv in (self.cv1, self.cv2, self.cv3))
-        inner = all(type(m) is Bottleneck and isinstance(m.cv1.act, nn.SiLU) and isinstance(m.cv2.act, nn.SiLU) and
+        silu = _silu(self.cv1) and _silu(self.cv2) and _silu(self.cv3)
+        inner = all(type(m) is Bottleneck and _silu(m.cv1) and _silu(m.cv2) and
                     (fused.bottleneck_ok(m) or ((fused.conv3x3_ok(m.cv1.conv) or fused.pointwise_ok(m.cv1.conv)) and fused.conv3x3_ok(m.cv2.conv)
                                                 and m.cv2.conv.stride == (1, 1)))
                     for m in self.m)
@@ -189,24 +206,12 @@ class C3(nn.Module):
         """The same arithmetic with every producer writing where its consumer reads: [cv1 | cv2] in one pointwise launch into the
         inner concat buffer (cv1's half mirrored densely for the first bottleneck), the bottlenecks' results (shortcut in the second
         convolution's epilogue) into cv1's slot, cv3's output into channels [c_off, c_off + c2) of `out` (+ the dense copy `out2`)."""
-        c_ = self.cv1.conv.out_channels
-        B, _, H, W = x.shape
-        inner = torch.empty((B, 2 * c_, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        dense = lambda: torch.empty((B, c_, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        cur = dense()
-        w12, b12 = self._w12()
-        fused.pointwise(x, w12, b12, "silu", out=inner, c_off=0, out2=cur, c0=0)
+        inner, cur = _open_pair(self, x, 2 * self.cv1.conv.out_channels, 0)
         for j, m in enumerate(self.m):
-            nxt = dense() if j + 1 < len(self.m) else None
-            if fused.bottleneck_ok(m):
-                fused.bottleneck(cur, m, inner, 0, out2=nxt)
-            else:
-                cv = m.cv2.conv
-                fused.conv3x3(m.cv1(cur), fused.weight_n9k(m.cv2, cv), cv.bias, 1, "silu", res=cur if m.add else None, res_after=True,
-                              out=inner, c_off=0, out2=nxt, c0=0)
+            nxt = _new(x, cur.shape[1]) if j + 1 < len(self.m) else None
+            _place_bneck(m, cur, inner, 0, nxt)
             cur = nxt
-        c3 = self.cv3.conv
-        fused.pointwise(inner, fused.weight_nk(self.cv3, c3), c3.bias, "silu", out=out, c_off=c_off, out2=out2, c0=0)
+        self.cv3.place(inner, out, c_off, out2, 0)
 
 
 class SPPF(nn.Module):
@@ -290,7 +295,7 @@ class Detect(nn.Module):
 
     def _ext_ok(self):
         """The third branch (keypoints / mask coefficients) can run on the convolution kernels with zero-padded widths."""
-        return fused.HEAD_EXT and all(s[0].conv.in_channels % 8 == 0 and isinstance(s[0].act, nn.SiLU) and s[0].conv.kernel_size == (3, 3)
+        return fused.HEAD_EXT and all(s[0].conv.in_channels % 8 == 0 and _silu(s[0]) and s[0].conv.kernel_size == (3, 3)
                                       and s[0].conv.out_channels <= 80 for s in self.cv4)
 
     def _decode(self, feats, box, cls, bb, cb, ext=None):
@@ -299,46 +304,55 @@ class Detect(nn.Module):
         pred = fused.v8_decode(box, cls, bb, cb, self.strides, self.nc, ext, n_ext, 1 if self.nk else 0)
         return (pred, self.proto(feats[0])) if self.nm else pred
 
+    def _pads(self, ext_head):
+        return [fused.padded_branch(s, s) for s in self.cv4] if ext_head else []
+
+    def _grouped_ok(self, seqs) -> bool:
+        return fused.GROUP and all(fused.conv3x3_ok(s[0].conv) and fused.conv3x3_ok(s[1].conv) and _silu(s[0]) and s[0].conv.out_channels <= 80
+                                   for s in seqs)
+
+    def _grouped(self, seqs, pads, feats):
+        """The 3x3 -> 3x3 -> 1x1 chains `seqs` (+ the zero-padded third branches `pads`), three levels each, are independent: one
+        grouped launch per depth instead of one per layer -> the last layers' outputs, in the order of seqs + pads."""
+        w = [[(fused.weight_n9k(s[d], s[d].conv), s[d].conv.bias) for s in seqs] + [p[d] for p in pads] for d in (0, 1)]
+        w.append([self._last_wb(s[2]) for s in seqs] + [p[2] for p in pads])
+        t = list(feats) * ((len(seqs) + len(pads)) // 3)
+        for d, (k, act) in enumerate(((3, "silu"), (3, "silu"), (1, "none"))):
+            t = fused.conv_group([(x, wd, b, k, 1, act) for (wd, b), x in zip(w[d], t)])
+        return t
+
+    @staticmethod
+    def _ext_layers(pads, feats):
+        """The third branch layer by layer on the convolution kernels (padded widths); None without one."""
+        return [fused.pointwise(fused.conv3x3(fused.conv3x3(f, *p[0], 1, "silu"), *p[1], 1, "silu"), *p[2]) for p, f in zip(pads, feats)] or None
+
+    def _last_pw(self, seq, f):
+        """A branch whose final 1x1 runs on the pointwise kernel (bias in its epilogue; the decode adds zeros)."""
+        return fused.pointwise(seq[1](seq[0](f)), *self._last_wb(seq[2]))
+
     def forward(self, feats):
-        B = feats[0].shape[0]
         ext_head = bool(self.nk or self.nm)
         if fused.usable(feats[0]) and (not ext_head or self._ext_ok()):    # branch tensors -> [B, 4+nc(+nk|nm), A] float in one launch
             seqs = list(self.cv2) + list(self.cv3)
-            pads = [fused.padded_branch(self.cv4[i], self.cv4[i]) for i in range(len(feats))] if ext_head else []
+            pads = self._pads(ext_head)
             if not ext_head and len(feats) == 3 and all(fused.head_level_ok(f, self.cv2[i], self.cv3[i]) for i, f in enumerate(feats)):
                 # a level's two branches, three layers each, in ONE launch with the intermediates in LDS (csrc k_head): 3 launches
                 # instead of the 3 grouped ones per depth, without the round trips of the 64- / 80-channel intermediates
                 t = [fused.head_level(f, self.cv2[i], self.cv3[i]) for i, f in enumerate(feats)]
                 z = self._zero_bias(feats[0])
                 return self._decode(feats, [a for a, _ in t], [b for _, b in t], z, z)
-            if (fused.GROUP and len(feats) == 3 and all(self._last_ok(s[2]) and fused.conv3x3_ok(s[0].conv) and
-                                                         fused.conv3x3_ok(s[1].conv) and isinstance(s[0].act, nn.SiLU) and
-                                                         s[2].out_channels <= 80 and s[0].conv.out_channels <= 80 for s in seqs)):
-                # the branches are independent: one grouped launch per depth instead of 18 (27 with a third branch) small ones
-                xs = list(feats) * (3 if ext_head else 2)
-                w = [[(fused.weight_n9k(s[d], s[d].conv), s[d].conv.bias) for s in seqs] + [p[d] for p in pads] for d in (0, 1)]
-                w.append([self._last_wb(s[2]) for s in seqs] + [p[2] for p in pads])
-                t = fused.conv_group([(x, wd, b, 3, 1, "silu") for (wd, b), x in zip(w[0], xs)])
-                t = fused.conv_group([(x, wd, b, 3, 1, "silu") for (wd, b), x in zip(w[1], t)])
-                t = fused.conv_group([(x, wd, b, 1, 1, "none") for (wd, b), x in zip(w[2], t)])
+            if len(feats) == 3 and self._grouped_ok(seqs) and all(self._last_ok(s[2]) and s[2].out_channels <= 80 for s in seqs):
+                t = self._grouped(seqs, pads, feats)          # 3 launches instead of 18 (27 with a third branch) small ones
                 z = self._zero_bias(feats[0])
                 return self._decode(feats, t[:3], t[3:6], z, z, t[6:] if ext_head else None)
-            ext = None
-            if ext_head:                     # the third branch layer by layer on the convolution kernels (padded widths)
-                ext = []
-                for p, f in zip(pads, feats):
-                    u = fused.conv3x3(f, p[0][0], p[0][1], 1, "silu")
-                    u = fused.conv3x3(u, p[1][0], p[1][1], 1, "silu")
-                    ext.append(fused.pointwise(u, p[2][0], p[2][1]))
-            if all(self._last_ok(s[2]) for s in list(self.cv2) + list(self.cv3)):
-                # final 1x1 of every branch on the pointwise kernel (bias in its epilogue; the decode adds zeros)
-                last = lambda seq, f: fused.pointwise(seq[1](seq[0](f)), *self._last_wb(seq[2]))
-                bb = cb = self._zero_bias(feats[0])
+            ext = self._ext_layers(pads, feats)
+            if all(self._last_ok(s[2]) for s in seqs):
+                last, bb = self._last_pw, self._zero_bias(feats[0])
+                cb = bb
             else:
                 last = lambda seq, f: F.conv2d(seq[1](seq[0](f)), seq[2].weight)
                 bb, cb = [s[2].bias for s in self.cv2], [s[2].bias for s in self.cv3]
-            return self._decode(feats, [last(self.cv2[i], f) for i, f in enumerate(feats)],
-                                [last(self.cv3[i], f) for i, f in enumerate(feats)], bb, cb, ext)
+            return self._decode(feats, [last(s, f) for s, f in zip(self.cv2, feats)], [last(s, f) for s, f in zip(self.cv3, feats)], bb, cb, ext)
         return self._forward_torch(feats)
 
     @staticmethod
@@ -409,34 +423,18 @@ class YOLOv8(nn.Module):
 
     def forward_head(self, p3, p4, p5):
         c16, c19 = self.h16.conv, self.h19.conv
-        if (fused.C3K2 and fused.usable(p3) and fused.conv3x3_ok(c16) and fused.conv3x3_ok(c19) and isinstance(self.h16.act, nn.SiLU)
-                and isinstance(self.h19.act, nn.SiLU) and c16.out_channels % 8 == 0 and c19.out_channels % 8 == 0):
-            # the two down-path concats as placement: h12 lands in h18's input from its own last 1x1, the stride-2 convolutions write
-            # their slices; only p5 (made in the backbone half, which may be another captured graph) is copied
-            B = p3.shape[0]
-            x18 = torch.empty((B, c16.out_channels + self.h12.cv2.conv.out_channels, p4.shape[2], p4.shape[3]), dtype=p3.dtype, device=p3.device,
-                              memory_format=torch.channels_last)
+        half = (fused.C3K2 and fused.usable(p3) and fused.conv3x3_ok(c16) and fused.conv3x3_ok(c19) and _silu(self.h16) and _silu(self.h19)
+                and c16.out_channels % 8 == 0 and c19.out_channels % 8 == 0)
+        if half or (fused32.conv_ok(p3, c16) and fused32.conv_ok(p4, c19)):
+            # the two down-path concats as placement, in both precisions: h12 lands in h18's input from its own last 1x1, the stride-2
+            # convolutions write their slices; only p5 (made in the backbone half, which may be another captured graph) is copied
+            x18 = _new(p4, c16.out_channels + self.h12.cv2.conv.out_channels)
             h12 = self.h12(_upcat(p5, p4), also=x18, c_off=c16.out_channels)
             h15 = self.h15(_upcat(h12, p3))
-            fused.conv3x3(h15, fused.weight_n9k(self.h16, c16), c16.bias, 2, "silu", out=x18, c_off=0)
+            self.h16.place(h15, x18, 0)
             h18 = self.h18(x18)
-            x21 = torch.empty((B, c19.out_channels + p5.shape[1], p5.shape[2], p5.shape[3]), dtype=p3.dtype, device=p3.device,
-                              memory_format=torch.channels_last)
-            fused.conv3x3(h18, fused.weight_n9k(self.h19, c19), c19.bias, 2, "silu", out=x21, c_off=0)
-            x21[:, c19.out_channels:] = p5
-            return self.detect([h15, h18, self.h21(x21)])
-        if fused32.conv_ok(p3, c16) and fused32.conv_ok(p4, c19):
-            # fp32 kernels: the two down-path concats as placement — h12 lands in h18's input from its own last 1x1, the stride-2
-            # convolutions write their slices; only p5 is copied
-            B = p3.shape[0]
-            new = lambda c, like: torch.empty((B, c, like.shape[2], like.shape[3]), dtype=p3.dtype, device=p3.device, memory_format=torch.channels_last)
-            x18 = new(c16.out_channels + self.h12.cv2.conv.out_channels, p4)
-            h12 = self.h12(_upcat(p5, p4), also=x18, c_off=c16.out_channels)
-            h15 = self.h15(_upcat(h12, p3))
-            self.h16(h15, out=x18[:, :c16.out_channels])
-            h18 = self.h18(x18)
-            x21 = new(c19.out_channels + p5.shape[1], p5)
-            self.h19(h18, out=x21[:, :c19.out_channels])
+            x21 = _new(p5, c19.out_channels + p5.shape[1])
+            self.h19.place(h18, x21, 0)
             x21[:, c19.out_channels:] = p5
             return self.detect([h15, h18, self.h21(x21)])
         h12 = self.h12(_upcat(p5, p4))
@@ -478,41 +476,24 @@ class C3k2(nn.Module):
         def inner_ok(m):
             if type(m) is C3k:
                 return m.placed_ok()
-            return (type(m) is Bottleneck and isinstance(m.cv1.act, nn.SiLU) and isinstance(m.cv2.act, nn.SiLU) and
+            return (type(m) is Bottleneck and _silu(m.cv1) and _silu(m.cv2) and
                     fused.conv3x3_ok(m.cv1.conv) and fused.conv3x3_ok(m.cv2.conv) and m.cv2.conv.stride == (1, 1))
         return (fused.C3K2 and fused.usable(x) and fused.place_ok(self.c, (2 + len(self.m)) * self.c) and fused.pointwise_ok(self.cv1.conv)
-                and isinstance(self.cv1.act, nn.SiLU) and all(inner_ok(m) for m in self.m))
+                and _silu(self.cv1) and all(inner_ok(m) for m in self.m))
+
+    @staticmethod
+    def _place_inner(m, x, out, c_off, out2):
+        """A C3k block places its output itself; a Bottleneck c -> c/2 -> c takes one launch of the equal-width kernel on zero-padded
+        weights, else its second convolution adds the shortcut and writes the slice."""
+        if type(m) is C3k:
+            m.forward_placed(x, out, c_off, out2)
+        elif fused.bottleneck_padded_ok(m):
+            fused.bottleneck_padded(x, m, out, c_off, out2=out2)
+        else:
+            m.cv2.place(m.cv1(x), out, c_off, out2, 0, res=x if m.add else None, res_after=True)
 
     def forward(self, x):
-        if self._placed_ok(x):
-            return self._forward_placed(x)
-        y = list(self.cv1(x).chunk(2, 1))
-        for m in self.m:
-            y.append(m(y[-1]))
-        return self.cv2(torch.cat(y, 1))
-
-    def _forward_placed(self, x):
-        """C2f._forward_placed for v11's inner blocks: no chunk / cat / add launches; a Bottleneck's second convolution adds the
-        shortcut and writes its slice of the concat buffer, a C3k block places its output itself."""
-        c, n = self.c, len(self.m)
-        B, _, H, W = x.shape
-        cat = torch.empty((B, (2 + n) * c, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        dense = lambda: torch.empty((B, c, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        cv = self.cv1.conv
-        cur = dense()
-        fused.pointwise(x, fused.weight_nk(self.cv1, cv), cv.bias, "silu", out=cat, c_off=0, out2=cur, c0=c)
-        for i, m in enumerate(self.m):
-            nxt = dense() if i + 1 < n else None
-            if type(m) is C3k:
-                m.forward_placed(cur, cat, (2 + i) * c, nxt)
-            elif fused.bottleneck_padded_ok(m):      # c -> c/2 -> c: one launch of the equal-width kernel on zero-padded weights
-                fused.bottleneck_padded(cur, m, cat, (2 + i) * c, out2=nxt)
-            else:
-                cv = m.cv2.conv
-                fused.conv3x3(m.cv1(cur), fused.weight_n9k(m.cv2, cv), cv.bias, 1, "silu", res=cur if m.add else None, res_after=True,
-                              out=cat, c_off=(2 + i) * c, out2=nxt, c0=0)
-            cur = nxt
-        return self.cv2(cat)
+        return _c2f_placed(self, x, self._place_inner) if self._placed_ok(x) else _c2f_torch(self, x)
 
 
 class Attention(nn.Module):
@@ -538,10 +519,9 @@ class Attention(nn.Module):
             per = 2 * self.key_dim + self.head_dim
             v = qkv.permute(0, 2, 3, 1).reshape(B, H, W, self.num_heads, per)[..., 2 * self.key_dim:].reshape(B, H, W, C).permute(0, 3, 1, 2)
             y = fused.psa_attention(qkv, self.pe(v), self.num_heads, self.scale)
-            pc = self.proj.conv
-            if res is not None and fused.pointwise_ok(pc):                               # PSABlock's x + attn(x) in the projection's epilogue
+            if res is not None and fused.pointwise_ok(self.proj.conv):                   # PSABlock's x + attn(x) in the projection's epilogue
                 # res_after: the projection is rounded to half BEFORE the shortcut is added, as `res + self.proj(y)` rounds it
-                return fused.pointwise(y, fused.weight_nk(self.proj, pc), pc.bias, "none", res=res, res_after=True)
+                return self.proj.place(y, res=res, res_after=True)
             return self.proj(y) if res is None else res + self.proj(y)
         qkv = self.qkv(x).contiguous().view(B, self.num_heads, self.key_dim * 2 + self.head_dim, N)
         q, k, v = qkv.split([self.key_dim, self.key_dim, self.head_dim], dim=2)
@@ -563,12 +543,9 @@ class PSABlock(nn.Module):
     def forward(self, x, out=None, c_off=0):
         """out / c_off: the result also goes to channels [c_off, c_off + c) of `out` (C2PSA's concat buffer) when the fused path runs."""
         x = self.attn(x, res=x)
-        f1 = self.ffn[1].conv
-        if fused.usable(x) and fused.pointwise_ok(f1):                                   # x + ffn(x) in the second 1x1's epilogue
-            if out is not None:
-                fused.pointwise(self.ffn[0](x), fused.weight_nk(self.ffn[1], f1), f1.bias, "none", res=x, res_after=True, out=out, c_off=c_off)
-                return None
-            return fused.pointwise(self.ffn[0](x), fused.weight_nk(self.ffn[1], f1), f1.bias, "none", res=x, res_after=True)   # (two roundings, as x + ffn(x))
+        if fused.usable(x) and fused.pointwise_ok(self.ffn[1].conv):                     # x + ffn(x) in the second 1x1's epilogue
+            y = self.ffn[1].place(self.ffn[0](x), out, c_off, res=x, res_after=True)     # (two roundings, as x + ffn(x))
+            return y if out is None else None
         y = x + self.ffn(x)
         if out is not None:
             out[:, c_off:c_off + y.shape[1]] = y
@@ -585,14 +562,12 @@ class C2PSA(nn.Module):
 
     def forward(self, x):
         cv = self.cv1.conv
-        if (fused.C3K2 and fused.usable(x) and fused.pointwise_ok(cv) and isinstance(self.cv1.act, nn.SiLU) and fused.place_ok(self.c, 2 * self.c)
+        if (fused.C3K2 and fused.usable(x) and fused.pointwise_ok(cv) and _silu(self.cv1) and fused.place_ok(self.c, 2 * self.c)
                 and len(self.m) >= 1 and all(fused.pointwise_ok(blk.ffn[1].conv) for blk in self.m)):
             # cv1 writes [a | b] into cv2's input and mirrors b densely for the attention blocks; the last block's shortcut epilogue
             # writes its result over b's slot: no split / contiguous / cat launches
-            B, _, H, W = x.shape
-            cat = torch.empty((B, 2 * self.c, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            b = torch.empty((B, self.c, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            fused.pointwise(x, fused.weight_nk(self.cv1, cv), cv.bias, "silu", out=cat, c_off=0, out2=b, c0=self.c)
+            cat, b = _new(x, 2 * self.c), _new(x, self.c)
+            self.cv1.place(x, cat, 0, b, self.c)
             for i, blk in enumerate(self.m):
                 b = blk(b) if i + 1 < len(self.m) else blk(b, out=cat, c_off=self.c)
             return self.cv2(cat)
@@ -617,29 +592,13 @@ class Detect11(Detect):
                 and all(self._last_ok(s[2]) for s in list(self.cv2) + list(self.cv3))):
             z = self._zero_bias(feats[0])
             # class branch: DWConv 3x3 -> 1x1, twice, -> 1x1 (each layer one launch of its own kernel)
-            cls = [fused.pointwise(s[1](s[0](f)), *self._last_wb(s[2])) for s, f in zip(self.cv3, feats)]
-            grp = list(self.cv2)
-            pads = [fused.padded_branch(self.cv4[i], self.cv4[i]) for i in range(3)] if ext_head else []
-            if fused.GROUP and all(fused.conv3x3_ok(s[0].conv) and fused.conv3x3_ok(s[1].conv) and isinstance(s[0].act, nn.SiLU)
-                                   and s[0].conv.out_channels <= 80 for s in grp):
-                # the box branches (and the keypoint / coefficient branches) are independent 3x3 -> 3x3 -> 1x1 chains: one grouped
-                # launch per depth
-                xs = list(feats) * (2 if ext_head else 1)
-                w = [[(fused.weight_n9k(s[d], s[d].conv), s[d].conv.bias) for s in grp] + [p[d] for p in pads] for d in (0, 1)]
-                w.append([self._last_wb(s[2]) for s in grp] + [p[2] for p in pads])
-                t = fused.conv_group([(x, wd, b, 3, 1, "silu") for (wd, b), x in zip(w[0], xs)])
-                t = fused.conv_group([(x, wd, b, 3, 1, "silu") for (wd, b), x in zip(w[1], t)])
-                t = fused.conv_group([(x, wd, b, 1, 1, "none") for (wd, b), x in zip(w[2], t)])
+            cls = [self._last_pw(s, f) for s, f in zip(self.cv3, feats)]
+            pads = self._pads(ext_head)
+            if self._grouped_ok(self.cv2):       # the box branches (and the keypoint / coefficient branches) as grouped launches
+                t = self._grouped(list(self.cv2), pads, feats)
                 return self._decode(feats, t[:3], cls, z, z, t[3:] if ext_head else None)
-            box = [fused.pointwise(s[1](s[0](f)), *self._last_wb(s[2])) for s, f in zip(self.cv2, feats)]
-            ext = None
-            if ext_head:
-                ext = []
-                for p, f in zip(pads, feats):
-                    u = fused.conv3x3(f, p[0][0], p[0][1], 1, "silu")
-                    u = fused.conv3x3(u, p[1][0], p[1][1], 1, "silu")
-                    ext.append(fused.pointwise(u, p[2][0], p[2][1]))
-            return self._decode(feats, box, cls, z, z, ext)
+            box = [self._last_pw(s, f) for s, f in zip(self.cv2, feats)]
+            return self._decode(feats, box, cls, z, z, self._ext_layers(pads, feats))
         return self._forward_torch(feats)
 
 
@@ -721,7 +680,7 @@ class ELAN(nn.Module):
     def _placed_ok(self, x) -> bool:
         a, b = self.cv1.conv, self.cv2.conv
         return (fused.C3K2 and fused.usable(x) and fused.pointwise_ok(a) and fused.pointwise_ok(b) and fused.place_ok(a.out_channels, self.out.conv.in_channels)
-                and all(isinstance(c.act, nn.SiLU) for c in [self.cv1, self.cv2] + list(self.m))
+                and all(_silu(c) for c in [self.cv1, self.cv2] + list(self.m))
                 and all(fused.conv3x3_ok(m.conv) and m.conv.stride == (1, 1) for m in self.m))
 
     def forward(self, x):
@@ -739,21 +698,15 @@ class ELAN(nn.Module):
         """The same arithmetic without the concat copy: [cv1 | cv2] as one 1x1 launch into the concat buffer (cv2's half mirrored
         densely for the 3x3 chain), every second 3x3 writes its slice (and a dense copy for the next one)."""
         c_ = self.cv1.conv.out_channels
-        B, _, H, W = x.shape
-        cat = torch.empty((B, self.out.conv.in_channels, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        dense = lambda: torch.empty((B, c_, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        cur = dense()
-        w12, b12 = _w_pair(self, self.cv1.conv, self.cv2.conv)
-        fused.pointwise(x, w12, b12, "silu", out=cat, c_off=0, out2=cur, c0=c_)
+        cat, cur = _open_pair(self, x, self.out.conv.in_channels, c_)
         n = len(self.m)
         for i, m in enumerate(self.m):
-            cv = m.conv
             if i % 2 == 1:
-                nxt = dense() if i + 1 < n else None
-                fused.conv3x3(cur, fused.weight_n9k(m, cv), cv.bias, 1, "silu", out=cat, c_off=(2 + i // 2) * c_, out2=nxt, c0=0)
+                nxt = _new(x, c_) if i + 1 < n else None
+                m.place(cur, cat, (2 + i // 2) * c_, nxt, 0)
                 cur = nxt
             else:
-                cur = fused.conv3x3(cur, fused.weight_n9k(m, cv), cv.bias, 1, "silu")
+                cur = m.place(cur)
         return self.out(cat)
 
 
@@ -764,13 +717,12 @@ class MP(nn.Module):
 
     def forward(self, x):
         a, c3 = self.cv1.conv, self.cv3.conv
-        if (fused.C3K2 and fused.usable(x) and fused.pointwise_ok(a) and fused.conv3x3_ok(c3) and isinstance(self.cv1.act, nn.SiLU)
-                and isinstance(self.cv3.act, nn.SiLU) and fused.place_ok(a.out_channels, 2 * a.out_channels) and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0):
+        if (fused.C3K2 and fused.usable(x) and fused.pointwise_ok(a) and fused.conv3x3_ok(c3) and _silu(self.cv1)
+                and _silu(self.cv3) and fused.place_ok(a.out_channels, 2 * a.out_channels) and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0):
             h = a.out_channels                           # both branches write their half of the output
-            B, _, H, W = x.shape
-            out = torch.empty((B, 2 * h, H // 2, W // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            fused.conv3x3(self.cv2(x), fused.weight_n9k(self.cv3, c3), c3.bias, 2, "silu", out=out, c_off=0)
-            fused.pointwise(F.max_pool2d(x, 2, 2), fused.weight_nk(self.cv1, a), a.bias, "silu", out=out, c_off=h)
+            out = _new(x, 2 * h, (x.shape[2] // 2, x.shape[3] // 2))
+            self.cv3.place(self.cv2(x), out, 0)
+            self.cv1.place(F.max_pool2d(x, 2, 2), out, h)
             return out
         return torch.cat((self.cv3(self.cv2(x)), self.cv1(F.max_pool2d(x, 2, 2))), 1)
 
@@ -786,16 +738,15 @@ class SPPCSPC(nn.Module):
     def forward(self, x):
         x1 = self.cv4(self.cv3(self.cv1(x)))
         c2, c6 = self.cv2.conv, self.cv6.conv
-        if (fused.C3K2 and fused.sppf_pools_ok(x1) and fused.pointwise_ok(c2) and fused.conv3x3_ok(c6) and isinstance(self.cv2.act, nn.SiLU)
-                and isinstance(self.cv6.act, nn.SiLU) and fused.place_ok(c6.out_channels, 2 * c6.out_channels)):
+        if (fused.C3K2 and fused.sppf_pools_ok(x1) and fused.pointwise_ok(c2) and fused.conv3x3_ok(c6) and _silu(self.cv2)
+                and _silu(self.cv6) and fused.place_ok(c6.out_channels, 2 * c6.out_channels)):
             # max pools of 5, 9, 13 = the cascade of three 5-pools (max over nested windows): the SPPF launch gives cat(x1, p5, p9, p13);
             # cv6 and cv2 write their halves of cv7's input
             t = self.cv5(fused.sppf_pools(x1))
             c_ = c6.out_channels
-            B, _, H, W = x.shape
-            cat = torch.empty((B, 2 * c_, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            fused.conv3x3(t, fused.weight_n9k(self.cv6, c6), c6.bias, 1, "silu", out=cat, c_off=0)
-            fused.pointwise(x, fused.weight_nk(self.cv2, c2), c2.bias, "silu", out=cat, c_off=c_)
+            cat = _new(x, 2 * c_)
+            self.cv6.place(t, cat, 0)
+            self.cv2.place(x, cat, c_)
             return self.cv7(cat)
         y1 = self.cv6(self.cv5(torch.cat([x1] + [F.max_pool2d(x1, k, 1, k // 2) for k in (5, 9, 13)], 1)))
         return self.cv7(torch.cat((y1, self.cv2(x)), 1))
@@ -964,12 +915,20 @@ class OSNet(nn.Module):
 
     N_PARTS = 10
 
+    @staticmethod
+    def _state(s):
+        """(x, x1) of the state between two parts: a tensor, (block output, the next block's conv1 of it), or a 1-tuple when the
+        previous block's tail already ran the following part."""
+        if not isinstance(s, tuple):
+            return s, None
+        return s if len(s) == 2 else (s[0], None)
+
     def _block_part(self, k, s):
         """Parts 1, 2, 4, 5, 7, 8: an OSBlock.  On the GPU the block's tail also runs the 1x1 convolution that follows it —
         the next block's conv1 (state becomes (block output, that conv1's output)) or the stage's ConvBR (+ average pool;
         state becomes a 1-tuple: the following part is already applied)."""
         blk, nxt, pool = self._blocks(k)
-        x, x1 = s if isinstance(s, tuple) else (s, None)
+        x, x1 = self._state(s)
         if blk.tail_ok(x, nxt, pool):
             want_out = k in (1, 4, 7)
             out, o2 = blk.forward_tail(x, x1, nxt, pool, want_out)
@@ -990,7 +949,7 @@ class OSNet(nn.Module):
             return f.stem(s, self.conv1, self.conv2[0].conv1)      # (x0, the first block's conv1 of x0) from one launch
         if k in (1, 2, 4, 5, 7, 8):
             blk, nxt, pool = self._blocks(k)
-            x, x1 = s if (isinstance(s, tuple) and len(s) == 2) else (s[0] if isinstance(s, tuple) else s, None)
+            x, x1 = self._state(s)
             if x1 is None:
                 x1 = f.pointwise(x, blk.conv1, blk.conv1.conv, relu=True)
             ys, psum = f.chains(x1, blk)
@@ -1000,9 +959,10 @@ class OSNet(nn.Module):
         assert isinstance(s, tuple) and len(s) == 1           # the previous block's tail already ran this part
         return s[0]
 
-    def _fp32_kernels(self, x) -> bool:
-        first = x[0] if isinstance(x, tuple) else x
-        if not fused32.usable(first):
+    def _fp32_kernels(self, x, u8=False) -> bool:
+        """The one place that decides whether the fp32 kernels take this state (u8: byte crops, which only the fp32 stem reads)."""
+        first = self._state(x)[0]
+        if not (fused32.usable_u8(first) if u8 else fused32.usable(first)):
             return False
         if getattr(self, "_ok32", None) is None:
             self._ok32 = fused32.osnet_ok(self, torch.empty(1, 3, 256, 128, device=first.device))
@@ -1012,16 +972,12 @@ class OSNet(nn.Module):
         """The backbone as 10 consecutive parts, so a frame pipeline can cut it anywhere to balance its stages.  The state
         between parts is a tensor or a tuple of tensors (see _block_part)."""
         if k == 0 and isinstance(x, torch.Tensor) and x.dtype == torch.uint8:      # byte crops (a4 with SS_DST_U8): the fp32 stem normalises them itself
-            if fused32.usable_u8(x):
-                if getattr(self, "_ok32", None) is None:
-                    self._ok32 = fused32.osnet_ok(self, torch.empty(1, 3, 256, 128, device=x.device))
-                if self._ok32:
-                    return self._part32(0, x)
+            if self._fp32_kernels(x, u8=True):
+                return self._part32(0, x)
             x = fused32.crops_from_u8(x).to(self.conv1.conv.weight.dtype)
         if self._fp32_kernels(x):
-            first = x[0] if isinstance(x, tuple) else x
             want = {0: (256, 128), 1: (64, 32), 2: (64, 32), 4: (32, 16), 5: (32, 16), 7: (16, 8), 8: (16, 8)}.get(k)
-            if (want is None and isinstance(x, tuple) and len(x) == 1) or (want is not None and tuple(first.shape[2:]) == want):
+            if (want is None and isinstance(x, tuple) and len(x) == 1) or (want is not None and tuple(self._state(x)[0].shape[2:]) == want):
                 return self._part32(k, x)
         if k == 0:
             if fused.usable(x) and fused.stem_ok(x, self.conv1.conv) and self.conv1.relu:      # conv + bias + ReLU + pool, one launch
@@ -1038,12 +994,10 @@ class OSNet(nn.Module):
         if isinstance(x, tuple):                            # the previous block's tail already ran this part
             assert len(x) == 1
             return x[0]
-        if k == 3:
-            t = self.conv2[2](x)
-            return fused.avgpool2(t) if fused.usable(t) else self.conv2[3](t)
-        if k == 6:
-            t = self.conv3[2](x)
-            return fused.avgpool2(t) if fused.usable(t) else self.conv3[3](t)
+        if k in (3, 6):                                     # the stage's ConvBR + 2x2 average
+            stage = self.conv2 if k == 3 else self.conv3
+            t = stage[2](x)
+            return fused.avgpool2(t) if fused.usable(t) else stage[3](t)
         return self.conv5(x)
 
     def forward_a(self, x, upto: int = 5):
