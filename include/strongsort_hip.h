@@ -234,7 +234,7 @@ int ss_byte_update_group(ss_ctx* ctx, int n_frames, const float* d_dets, const i
 int ss_byte_update(ss_ctx* ctx, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
 int ss_byte_reset(ss_ctx* ctx, int stream);                /* stream < 0: all streams; ids restart at 1, frame_id at 1; the
                                                               stream's previous ss_cmc_estimate frame is forgotten (no warp next)
-                                                              and its ReID track features are cleared */
+                                                              and its ReID track features and stored poses are cleared */
 /* BoT-SORT GMC (docs/BYTETRACK.md §1b): the following ss_byte_update(_group) calls move every track's Kalman mean and covariance
  * by d_warps[f][s][8] (ss_cmc_estimate's layout; [6] < 0: no warp) after predicting frame f.  The caller keeps at least
  * n_frames rows alive; the pointer is read at launch (capturable).  NULL switches it off (the default).  SS_ERR_INVALID without
@@ -252,6 +252,27 @@ int ss_byte_update_group_feats(ss_ctx* ctx, int n_frames, const float* d_dets, c
                                float* d_out, int* d_nout);
 /* Synchronous: the unit track features [n][512] of one stream in ss_byte_get_tracks' list order (after ss_byte_set_reid). */
 int ss_byte_get_features(ss_ctx* ctx, int stream, int cap, float* smooth);
+/* The keypoint (OKS) term of BoT-SORT (docs/BYTETRACK.md §1e, this project's own definition): on != 0 adds an OKS entry to the first
+ * and third associations for the pairs with 1 - IoU <= proximity_thresh (0.5), kept when (1 - OKS) / 2 <= pose_thresh (0.25); a
+ * keypoint counts when its visibility >= (float)vis_thresh (0.5), a pair when at least min_common (3) count on both sides; sigmas:
+ * n_kpt (1..32) host doubles (COCO's 17).  Switching (on or off) resets every stream.  The first switch-on allocates the pose tables.
+ * SS_ERR_INVALID without BYTE state, on an xyah (ByteTrack) state, while ReID is on, or with n_kpt outside 1..32.  While it is on,
+ * ss_byte_update(_group) and ss_byte_update_group_feats are refused (use ss_byte_update_group_kpts), and so is ss_byte_set_reid(on). */
+int ss_byte_set_pose(ss_ctx* ctx, int on, int n_kpt, const double* sigmas, double proximity_thresh, double pose_thresh,
+                     double vis_thresh, int min_common);
+/* ss_byte_update_group with the group's keypoints: row r of image i = f * n_streams + s at d_kpts + (i * SS_MAX_DETS + r) *
+ * kpt_row_stride + kpt_col_offset floats, n_kpt triplets (x, y, visibility) f32 (NMS rows carry them at column 6).  d_geom
+ * [n_frames * n_streams][5] = ss_nms_batch's geometry rows {gain, pad_x, pad_y, ..}: the keypoints are network-input pixels and are
+ * brought to original pixels, (x - pad) / gain in float32; NULL: they are original pixels already.  Asynchronous, capturable. */
+int ss_byte_update_group_kpts(ss_ctx* ctx, int n_frames, const float* d_dets, const int* d_ndets, const float* d_kpts,
+                              long long kpt_row_stride, int kpt_col_offset, const float* d_geom, float* d_out, int* d_nout);
+/* Synchronous: the stored poses of one stream in ss_byte_get_tracks' list order: offsets [n][n_kpt][2] f64 (from the box centre, in
+ * box widths / heights) and one visibility word per track (bit k = keypoint k); either may be NULL. */
+int ss_byte_get_keypoints(ss_ctx* ctx, int stream, int cap, double* offsets, unsigned* visible);
+/* Synchronous inspection call, a permanent part of this ABI like ss_get_debug (the tests compare k_byte_kpts' output through it bit
+ * for bit): the detection keypoints of image (frame, stream) as the last ss_byte_update_group_kpts call prepared them:
+ * xy [SS_MAX_DETS][n_kpt][2] f32 in original pixels, visibility words [SS_MAX_DETS]; rows past the image's count are not written. */
+int ss_byte_get_det_keypoints(ss_ctx* ctx, int frame, int stream, float* xy, unsigned* visible);
 /* BoT-SORT's `model: auto` ReID features (docs/BYTETRACK.md §1d): the raw features of kept detections read from the detector's
  * own head inputs.  maps[3]: the levels P3, P4, P5 of n_img images (f16 if half, else f32), channel stride 1, element (i, c, y, x)
  * at data + i*img_stride + y*row_stride + x*pix_stride + c (strides in elements; a channel slice of a wider map is fine).

@@ -198,7 +198,7 @@ def process_video(args: dict, model=None) -> dict:
                      reid_fp32=not args.get("reid_f16", False), half=not args.get("fp32", False),
                      device_masks=args.get("device_masks", False), tracker_type=args.get("tracker", "strongsort"),
                      camera_motion=args.get("camera_motion", False), with_reid=args.get("with_reid", False),
-                     reid_model=args.get("reid_model", "osnet"))
+                     reid_model=args.get("reid_model", "osnet"), with_pose=args.get("with_pose", False))
         model.overrides.update(conf=0.3, iou=0.4, agnostic_nms=False, max_det=1000)      # :18-21
     name = os.path.splitext(os.path.basename(str(source)))[0] or "stream"
     writer = LabelsWriter(os.path.join(args.get("outdir", "output"), f"{name}_labels.txt"), args.get("compat", False))
@@ -275,6 +275,8 @@ def main(argv=None):
     p.add_argument("--reid-model", choices=("osnet", "auto"), default="osnet",
                    help="--with-reid only: osnet (default) runs OSNet-x0.25 on the crops; auto reads the features from the detector's own "
                         "head inputs (Ultralytics' model: auto, docs/BYTETRACK.md §1d) — no second weights file, not with --reid-weights")
+    p.add_argument("--with-pose", action="store_true",
+                   help="--tracker botsort on a pose model only: the keypoint (OKS) term beside IoU (docs/BYTETRACK.md §1e); not with --with-reid")
     p.add_argument("--limit", type=int, default=None)
     p.add_argument("--save", default=None, help="write annotated frames: stack.npy | video.bgr (raw BGR24 + .json) | directory of PNGs | video.mp4 (needs OpenCV)")
     p.add_argument("--batch", type=int, default=16, help="frames per group on the throughput path (1: per-frame model.track calls as in the reference)")
@@ -285,11 +287,17 @@ def main(argv=None):
         p.error("--camera-motion needs --tracker strongsort or botsort (ByteTrack has no GMC)")
     if a.with_reid and a.tracker != "botsort":
         p.error("--with-reid is BoT-SORT's ReID branch: it needs --tracker botsort")
+    if a.with_pose and a.tracker != "botsort":
+        p.error("--with-pose is BoT-SORT's keypoint term: it needs --tracker botsort")
+    if a.with_pose and a.with_reid:
+        p.error("--with-pose and --with-reid cannot be combined")
+    if a.with_pose and "pose" not in os.path.basename(a.weights):
+        p.error("--with-pose needs a pose model (--weights ...-pose.pt): this detector has no keypoint columns")
     if a.reid_model != "osnet" and not a.with_reid:
         p.error("--reid-model is a model for BoT-SORT's ReID branch: it needs --with-reid")
     if a.reid_model == "auto" and a.reid_weights:
         p.error("--reid-model auto reads the detector's own features: --reid-weights does not apply")
-    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model,
+    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose,
              "save": (a.save if len(a.source) == 1 else f"{os.path.splitext(a.save)[0]}_{i}{os.path.splitext(a.save)[1]}") if a.save else None}
             for i, s in enumerate(a.source)]
     import torch

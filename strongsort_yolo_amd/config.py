@@ -54,12 +54,17 @@ class DetectConfig:
     max_nms: int = 8192               # candidate cap after the confidence filter (LDS sort capacity)
 
 
+COCO_KPT_SIGMAS = (.026, .025, .025, .035, .035, .079, .079, .072, .072, .062, .062, .107, .107, .087, .087, .089, .089)
+
+
 @dataclass(frozen=True)
 class ByteTrackConfig:
     """The BYTE tracker family (docs/BYTETRACK.md, decisions B-01..): Ultralytics' bytetrack.yaml / botsort.yaml defaults
     (recalled from Ultralytics 8.3.x).  kalman = "xyah" (ByteTrack) or "xywh" (BoT-SORT).  with_reid (xywh only): BoT-SORT's
     appearance term (§1c, decisions R-01..) with proximity_thresh on 1 - IoU, appearance_thresh on the halved cosine
-    distance and the feature EMA weight feat_alpha."""
+    distance and the feature EMA weight feat_alpha.  with_pose (xywh only, not with with_reid): this project's keypoint term (§1e,
+    decisions K-01..) — an OKS entry beside the fused IoU for the pairs within proximity_thresh, kept when (1 - OKS) / 2 <= pose_thresh;
+    a keypoint counts when its visibility >= kpt_vis_thresh (float32), a pair when at least min_common_kpts count on both sides."""
     track_high_thresh: float = 0.25
     track_low_thresh: float = 0.1
     new_track_thresh: float = 0.25
@@ -78,12 +83,24 @@ class ByteTrackConfig:
     proximity_thresh: float = 0.5
     appearance_thresh: float = 0.25
     feat_alpha: float = 0.9
+    # the keypoint (OKS) term (§1e); kpt_sigmas: the COCO-17 per-keypoint constants
+    with_pose: bool = False
+    pose_thresh: float = 0.25
+    kpt_vis_thresh: float = 0.5
+    min_common_kpts: int = 3
+    kpt_sigmas: tuple = COCO_KPT_SIGMAS
 
     def __post_init__(self):
         if self.kalman not in ("xyah", "xywh"):
             raise ValueError(f"ByteTrackConfig.kalman: 'xyah' or 'xywh', not {self.kalman!r}")
         if self.with_reid and self.kalman != "xywh":
             raise ValueError("ByteTrackConfig.with_reid needs kalman='xywh' (BoT-SORT): ByteTrack has no ReID")
+        if self.with_pose and self.kalman != "xywh":
+            raise ValueError("ByteTrackConfig.with_pose needs kalman='xywh' (BoT-SORT): ByteTrack has no keypoint term")
+        if self.with_pose and self.with_reid:
+            raise ValueError("ByteTrackConfig: with_pose and with_reid cannot be combined")
+        if self.with_pose and not 1 <= len(self.kpt_sigmas) <= 32:
+            raise ValueError("ByteTrackConfig.kpt_sigmas: 1..32 keypoints")
         if not (0 < self.max_tracks <= 256 and 0 < self.max_dets <= 128):
             raise ValueError("ByteTrackConfig: max_tracks <= 256 and max_dets <= 128 (the device table's capacity)")
 
@@ -99,14 +116,26 @@ class ByteTrackConfig:
 TRACKER_TYPES = ("strongsort", "bytetrack", "botsort")
 
 
-def byte_config(tracker_type: str, with_reid: bool = False):
+def byte_config(tracker_type: str, with_reid: bool = False, with_pose: bool = False):
     if tracker_type not in TRACKER_TYPES:
         raise ValueError(f"tracker_type must be one of {TRACKER_TYPES}, not {tracker_type!r}")
     if with_reid and tracker_type != "botsort":
         raise ValueError(f"with_reid is BoT-SORT's ReID branch: tracker_type 'botsort', not {tracker_type!r}")
+    if with_pose and tracker_type != "botsort":
+        raise ValueError(f"with_pose is BoT-SORT's keypoint term: tracker_type 'botsort', not {tracker_type!r}")
     if tracker_type == "strongsort":
         return None
-    return ByteTrackConfig(kalman="xywh" if tracker_type == "botsort" else "xyah", with_reid=bool(with_reid))
+    return ByteTrackConfig(kalman="xywh" if tracker_type == "botsort" else "xyah", with_reid=bool(with_reid), with_pose=bool(with_pose))
+
+
+def check_pose(cfg, nk: int):
+    """with_pose against the detector's keypoint columns nk (3 per keypoint): a pose head whose keypoint count has sigmas."""
+    if cfg is None or not cfg.with_pose:
+        return
+    if nk == 0:
+        raise ValueError("with_pose needs a pose detector (this one has no keypoint columns)")
+    if nk // 3 != len(cfg.kpt_sigmas):
+        raise ValueError(f"with_pose: the detector has {nk // 3} keypoints, kpt_sigmas {len(cfg.kpt_sigmas)}")
 
 
 # BoT-SORT's ReID model (docs/BYTETRACK.md §1d): "osnet" — OSNet-x0.25 on the detections' crops (§1c, the default); "auto" —

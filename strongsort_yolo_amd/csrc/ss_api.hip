@@ -44,6 +44,7 @@ void ss_launch_mask_outline(const uint32_t*, long long, const int*, int, int, in
                             long long, int*, int, hipStream_t);
 extern "C" void ss_step_kernel_attr();
 void ss_launch_byte_group(const SSByteDev&, int, const float*, const int*, const float*, float*, int*, hipStream_t);
+void ss_launch_byte_group_kpts(const SSByteDev&, int, const float*, const int*, const float*, long long, int, const float*, float*, int*, hipStream_t);
 void ss_launch_native_feats(int, int, const void* const*, const long long*, const long long*, const long long*, const int*, const int*,
                             const int*, int, const int*, long long, const int*, float*, hipStream_t);
 
@@ -1102,6 +1103,10 @@ extern "C" int ss_byte_reset(ss_ctx* c, int stream)
     HIPCHK(c, hipMemsetAsync(c->cmc_prev_valid + s0, 0, (s1 - s0) * 4, c->stream));     // G-04: the next frame gets no warp
     if (b.smooth)                                                                        // §1c: the streams' track features
         HIPCHK(c, hipMemsetAsync(b.smooth + (size_t)s0 * SS_MAXT * SS_F, 0, (size_t)(s1 - s0) * SS_MAXT * SS_F * 4, c->stream));
+    if (b.tpose) {                                                                       // §1e: the streams' track poses
+        HIPCHK(c, hipMemsetAsync(b.tpose + (size_t)s0 * SS_MAXT * b.nk * 2, 0, (size_t)(s1 - s0) * SS_MAXT * b.nk * 2 * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(b.tvis + (size_t)s0 * SS_MAXT, 0, (size_t)(s1 - s0) * SS_MAXT * 4, c->stream));
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SS_OK;
 }
@@ -1151,6 +1156,7 @@ extern "C" int ss_byte_update_group(ss_ctx* c, int n_frames, const float* d_dets
     if (!c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: no BYTE state (ss_byte_create)");
     if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: 1 <= n_frames <= SS_FMAX");
     if (c->byte->dev.reid) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: ReID is on, the features go through ss_byte_update_group_feats");
+    if (c->byte->dev.pose) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: the keypoint term is on, the keypoints go through ss_byte_update_group_kpts");
     ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, nullptr, d_out, d_nout, c->stream);
     HIPCHK(c, hipGetLastError());
     return SS_OK;
@@ -1165,6 +1171,7 @@ extern "C" int ss_byte_update_group_feats(ss_ctx* c, int n_frames, const float* 
     if (!c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: no BYTE state (ss_byte_create)");
     if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: 1 <= n_frames <= SS_FMAX");
     if (c->byte->dev.reid && !d_feats) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: ReID is on and d_feats is NULL");
+    if (c->byte->dev.pose) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: the keypoint term is on, the keypoints go through ss_byte_update_group_kpts");
     ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, d_feats, d_out, d_nout, c->stream);
     HIPCHK(c, hipGetLastError());
     return SS_OK;
@@ -1177,6 +1184,7 @@ extern "C" int ss_byte_set_reid(ss_ctx* c, int on, double proximity_thresh, doub
     if (!c || !c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: no BYTE state (ss_byte_create)");
     SSByteDev& b = c->byte->dev;
     if (on && !b.xywh) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: ReID needs the xywh (BoT-SORT) state");
+    if (on && b.pose) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: the keypoint term is on (ss_byte_set_pose): the two are not combined");
     if (on && !b.smooth) {
         const size_t ns = (size_t)b.S * SS_MAXT * SS_F, nu = (size_t)SS_FMAX * b.S * SS_MAXD * SS_F;
         void *p = nullptr, *q = nullptr;
@@ -1191,6 +1199,109 @@ extern "C" int ss_byte_set_reid(ss_ctx* c, int on, double proximity_thresh, doub
     b.prox = proximity_thresh; b.appear = appearance_thresh;
     b.alpha = (float)alpha; b.one_minus_alpha = (float)(1.0 - alpha);
     return ss_byte_reset(c, -1);
+}
+
+// §1e: the keypoint (OKS) term of BoT-SORT on (on != 0) or off.  Either way every stream restarts (ss_byte_reset).  The pose tables
+// are allocated on the first switch-on for n_kpt keypoints and kept (a later switch-on with another n_kpt allocates again).
+extern "C" int ss_byte_set_pose(ss_ctx* c, int on, int n_kpt, const double* sigmas, double proximity_thresh, double pose_thresh,
+                                double vis_thresh, int min_common)
+{
+    if (!c || !c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: no BYTE state (ss_byte_create)");
+    SSByteDev& b = c->byte->dev;
+    if (on) {
+        if (!b.xywh) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: the keypoint term needs the xywh (BoT-SORT) state");
+        if (b.reid) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: ReID is on (ss_byte_set_reid): the two are not combined");
+        if (n_kpt < 1 || n_kpt > SS_BYTE_MAXK) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: 1 <= n_kpt <= 32");
+        if (!sigmas) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: sigmas is NULL");
+        b.pose = 0;                                                // a failure below leaves the term off, never half set up
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (!b.ks2) {
+            void* q = nullptr;
+            HIPCHK(c, hipMalloc(&q, SS_BYTE_MAXK * 8));
+            c->byte->allocs.push_back(q);
+            b.ks2 = (const double*)q;
+        }
+        if (!b.tpose || b.nk != n_kpt) {
+            const size_t nt = (size_t)b.S * SS_MAXT, nd = (size_t)SS_FMAX * b.S * SS_MAXD;
+            void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+            const size_t bytes[4] = {nt * n_kpt * 2 * 8, nt * 4, nd * n_kpt * 2 * 4, nd * 4};
+            for (int i = 0; i < 4; ++i) {                          // the old tables (another n_kpt) stay in allocs until the state goes
+                HIPCHK(c, hipMalloc(&p[i], bytes[i]));
+                c->byte->allocs.push_back(p[i]);
+                HIPCHK(c, hipMemsetAsync(p[i], 0, bytes[i], c->stream));
+            }
+            b.nk = n_kpt;                                          // all four exist: commit them together
+            b.tpose = (double*)p[0]; b.tvis = (unsigned*)p[1]; b.kp = (float*)p[2]; b.kvis = (unsigned*)p[3];
+        }
+        double s2[SS_BYTE_MAXK] = {0.0};
+        for (int k = 0; k < n_kpt; ++k) s2[k] = 2.0 * sigmas[k];
+        HIPCHK(c, hipMemcpy((void*)b.ks2, s2, sizeof s2, hipMemcpyHostToDevice));
+        b.prox = proximity_thresh; b.pose_thresh = pose_thresh; b.vis = (float)vis_thresh; b.min_common = min_common;
+    }
+    b.pose = on != 0;
+    return ss_byte_reset(c, -1);
+}
+
+// §1e: ss_byte_update_group with the group's keypoints: row r of image fs = f * n_streams + s at d_kpts + (fs * SS_MAX_DETS + r) *
+// kpt_row_stride + kpt_col_offset, n_kpt triplets (x, y, v) f32.  d_geom [n_frames * n_streams][5] (ss_nms_batch's rows {gain, pad_x,
+// pad_y, ..}): the keypoints are network-input pixels; NULL: original pixels.  Two launches on the context's stream: capturable.
+extern "C" int ss_byte_update_group_kpts(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, const float* d_kpts,
+                                         long long kpt_row_stride, int kpt_col_offset, const float* d_geom, float* d_out, int* d_nout)
+{
+    if (!c || !d_dets || !d_ndets || !d_kpts || !d_out || !d_nout) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_kpts: null argument");
+    if (!c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_kpts: no BYTE state (ss_byte_create)");
+    const SSByteDev& b = c->byte->dev;
+    if (!b.pose) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_kpts: the keypoint term is off (ss_byte_set_pose)");
+    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_kpts: 1 <= n_frames <= SS_FMAX");
+    if (kpt_col_offset < 0 || kpt_row_stride < (long long)kpt_col_offset + 3 * b.nk)
+        return fail(c, SS_ERR_INVALID, "ss_byte_update_group_kpts: kpt_col_offset >= 0, kpt_row_stride >= kpt_col_offset + 3 n_kpt");
+    ss_launch_byte_group_kpts(b, n_frames, d_dets, d_ndets, d_kpts, kpt_row_stride, kpt_col_offset, d_geom, d_out, d_nout, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+// Synchronous: the stored poses of one stream in ss_byte_get_tracks' list order: offsets [n][n_kpt][2] f64 and a visibility word
+// per track (bit k = keypoint k); either may be NULL.
+extern "C" int ss_byte_get_keypoints(ss_ctx* c, int s, int cap, double* offsets, unsigned* visible)
+{
+    if (!c || !c->byte || s < 0 || s >= c->dev.S || cap < 0) return fail(c, SS_ERR_INVALID, "ss_byte_get_keypoints: no BYTE state or bad stream");
+    const SSByteDev& b = c->byte->dev;
+    if (!b.tpose) return fail(c, SS_ERR_INVALID, "ss_byte_get_keypoints: the keypoint term was never switched on (ss_byte_set_pose)");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int nt = 0, nl = 0;
+    HIPCHK(c, hipMemcpy(&nt, b.n_trk + s, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&nl, b.n_lost + s, 4, hipMemcpyDeviceToHost));
+    if (nt + nl > cap) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_keypoints: cap too small");
+    const size_t T = SS_MAXT, sb = (size_t)s * T, K2 = (size_t)b.nk * 2;
+    std::vector<int> trk(T), lost(T);
+    std::vector<double> po(T * K2);
+    std::vector<unsigned> vi(T);
+    HIPCHK(c, hipMemcpy(trk.data(), b.trk + sb, T * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(lost.data(), b.lost + sb, T * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(po.data(), b.tpose + sb * K2, T * K2 * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(vi.data(), b.tvis + sb, T * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < nt + nl; ++i) {
+        const int slot = i < nt ? trk[i] : lost[i - nt];
+        if (slot < 0 || slot >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_keypoints: corrupt list");
+        if (offsets) memcpy(offsets + (size_t)i * K2, po.data() + (size_t)slot * K2, K2 * 8);
+        if (visible) visible[i] = vi[slot];
+    }
+    return SS_OK;
+}
+
+// Synchronous: what k_byte_kpts wrote for image (frame, stream) of the last ss_byte_update_group_kpts call: xy [SS_MAX_DETS][n_kpt][2]
+// f32 in original pixels and the rows' visibility words [SS_MAX_DETS] (rows past the image's count keep older values).
+extern "C" int ss_byte_get_det_keypoints(ss_ctx* c, int frame, int s, float* xy, unsigned* visible)
+{
+    if (!c || !c->byte || s < 0 || s >= c->dev.S || frame < 0 || frame >= SS_FMAX || !xy || !visible)
+        return fail(c, SS_ERR_INVALID, "ss_byte_get_det_keypoints: no BYTE state, bad frame / stream or NULL");
+    const SSByteDev& b = c->byte->dev;
+    if (!b.kp) return fail(c, SS_ERR_INVALID, "ss_byte_get_det_keypoints: the keypoint term was never switched on (ss_byte_set_pose)");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t fs = (size_t)frame * b.S + s;
+    HIPCHK(c, hipMemcpy(xy, b.kp + fs * SS_MAXD * b.nk * 2, (size_t)SS_MAXD * b.nk * 2 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(visible, b.kvis + fs * SS_MAXD, (size_t)SS_MAXD * 4, hipMemcpyDeviceToHost));
+    return SS_OK;
 }
 
 // §1d: BoT-SORT's `model: auto` features of the kept rows from the detector's head inputs (ss_native.hip k_native_feats).  Every

@@ -3,12 +3,15 @@
 //
 //   k_byte_feats  (ReID only, before k_byte_group in the same call) one wave per detection row of the group: so_normalize of
 //                 the raw 512-float feature into b.ufeat.
+//   k_byte_kpts   (pose only, before k_byte_group in the same call) one half wave per detection row of the group: the row's
+//                 keypoints in original pixels and their visibility word into b.kp / b.kvis.
 //   k_byte_group  one workgroup (256 threads) per stream walks the group's frames in order inside the launch: score split,
 //                 Kalman predict of the pool, BoT-SORT's GMC (§1b, the GMC variant only: the warps of ss_cmc_estimate
 //                 applied to the predicted pool and the unconfirmed tracks), three IoU associations (fused high / plain low / unconfirmed) each solved by
 //                 the one-wave LSAP (SciPy's optimum of the raw matrix, then the threshold), births, lost-track expiry, the
 //                 list rebuild with duplicate removal, output rows.  One launch per call, no host round trip: capturable.
 //                 The REID variant (§1c) adds the appearance entries of stages 4 and 6 and the tracks' smoothed features.
+//                 The POSE variant (§1e) adds the OKS entries of stages 4 and 6 and the tracks' stored poses.
 //
 // The list logic lives in LDS (slot fields, list orders); means / covariances stay in global memory, one thread per track
 // for the f64 Kalman work.  tests/bytetrack_ref.py restates every step in the same order (rows are compared bit for bit).
@@ -220,9 +223,156 @@ __device__ inline void byte_reid_smooth(const SSByteDev& b, size_t sb, size_t fs
     }
 }
 
+// §1e: exp(-x), x >= 0, as ONE fixed sequence of f64 operations (tests/botsort_pose_ref.ss_expneg runs the same one with the same
+// constants; the file is built with -ffp-contract=off): k = floor(-x log2(e) + 1/2), r = (-x - k LN2_HI) - k LN2_LO with
+// |r| <= ln2 / 2, the degree-12 Taylor polynomial by Horner, ldexp.  Above the cut-off (and for a NaN) the result is 0.
+__device__ inline double ss_expneg(double x)
+{
+    if (!(x <= 700.0)) return 0.0;
+    const double y = -x;
+    const double k = floor(y * 0x1.71547652b82fep+0 + 0.5);
+    const double r = (y - k * 0x1.62e42feep-1) - k * 0x1.a39ef35793c76p-33;
+    double p = 0x1.1eed8eff8d898p-29;             // 1 / 12!
+    p = p * r + 0x1.ae64567f544e4p-26;            // 1 / 11!
+    p = p * r + 0x1.27e4fb7789f5cp-22;
+    p = p * r + 0x1.71de3a556c734p-19;
+    p = p * r + 0x1.a01a01a01a01ap-16;
+    p = p * r + 0x1.a01a01a01a01ap-13;
+    p = p * r + 0x1.6c16c16c16c17p-10;
+    p = p * r + 0x1.1111111111111p-7;
+    p = p * r + 0x1.5555555555555p-5;
+    p = p * r + 0x1.5555555555555p-3;
+    p = p * r + 0.5;
+    p = p * r + 1.0;
+    p = p * r + 1.0;
+    return ldexp(p, (int)k);
+}
+
+// §1e: the keypoints of every detection row of the group.  kpts: row (fs, r) at kpts + (fs * MAXD + r) * stride + off, nk triplets
+// (x, y, v); geom [F * S][5] = {gain, pad_x, pad_y, ..} (ss_nms_batch's rows): x, y are network-input pixels and become
+// (x - pad) / gain in float32, the floats Results.keypoints shows; NULL: they are original pixels already.  Half a wave per
+// row, lane = keypoint; the visibility word is the half's ballot.  Block = 8 rows of one (frame, stream).
+__global__ __launch_bounds__(256) void k_byte_kpts(SSByteDev b, const float* __restrict__ kpts, long long stride, int off,
+                                                   const float* __restrict__ geom, const int* __restrict__ ndets)
+{
+    const int s = blockIdx.y, f = blockIdx.z, r = blockIdx.x * 8 + (threadIdx.x >> 5), k = threadIdx.x & 31;
+    const size_t fs = (size_t)f * b.S + s;
+    const int N = min(max(ndets[fs], 0), b.max_dets);
+    const bool on = r < N && k < b.nk;
+    int v = 0;
+    if (on) {
+        const float* in = kpts + (fs * SS_MAXD + r) * stride + off + 3 * k;
+        float x = in[0], y = in[1];
+        if (geom) { const float* g = geom + fs * 5; x = (x - g[1]) / g[0]; y = (y - g[2]) / g[0]; }
+        v = in[2] >= b.vis;
+        float* o = b.kp + ((fs * SS_MAXD + r) * b.nk + k) * 2;
+        o[0] = x; o[1] = y;
+    }
+    const unsigned long long w = __ballot(v);
+    if (on && k == 0) b.kvis[fs * SS_MAXD + r] = (unsigned)(w >> (threadIdx.x & 32));
+}
+
+// §1e get_dists with the keypoint term on rows (track slots rs[r]) x columns (detections cd[k]) of frame fs, stored by byte_cidx:
+//   iou = 1 - IoU;  c = fused(iou) if fuse;  e = 1 if iou > prox, else the pair's OKS entry;  cost = min(c, e).
+// byte_reid_cost's chunked shape: each thread one entry, the unmasked ones (overlapping boxes, about one per track) compacted
+// in LDS; then half a wave per surviving pair, lane = keypoint: the track's stored offset on its predicted mean (b.mean, moved
+// by GMC already) against the row's keypoint, t_k = ss_expneg(d2 / (2 area (2 sigma_k)^2)).  Every lane of the half then adds
+// the common keypoints' terms in keypoint order (shuffles within the half) and lane 0 stores.
+__device__ inline void byte_pose_cost(int nR, int nC, const int* rs, const int* cd, double* cost, const SSByteDev& b,
+                                      size_t sb, size_t fs, ByteLds& m)
+{
+    __shared__ int pe[256];
+    __shared__ double pc[256];
+    const int tid = threadIdx.x, kk = tid & 31, base = tid & 32, n = nR * nC, K = b.nk;
+    for (int e0 = 0; e0 < n; e0 += 256) {
+        const int e = e0 + tid;
+        int need = 0;
+        double c = 0.0;
+        if (e < n) {
+            const int r = e / nC, k = e - r * nC, d = cd[k];
+            const double iou = ss_iou_cost(m.tl[rs[r]], m.dtl[d], 2.0);
+            c = b.fuse ? 1.0 - (1.0 - iou) * (double)m.dsc[d] : iou;
+            need = !(iou > b.prox);
+            if (!need) cost[byte_cidx(r, k, nR, nC)] = 1.0 < c ? 1.0 : c;
+        }
+        int pos, nA;
+        block_scan256(need, m.wtot, pos, nA);
+        if (need) { pe[pos] = e; pc[pos] = c; }
+        __syncthreads();
+        for (int j0 = 0; j0 < nA; j0 += 8) {
+            const int j = j0 + (tid >> 5);
+            const bool act = j < nA;
+            int r = 0, k = 0;
+            unsigned common = 0;
+            double t = 0.0, area = 0.0;
+            if (act) {
+                r = pe[j] / nC; k = pe[j] - r * nC;
+                const int slot = rs[r], d = cd[k];
+                common = b.tvis[sb + slot] & b.kvis[fs * SS_MAXD + d];
+                area = m.dtl[d][2] * m.dtl[d][3];
+                if (kk < K && ((common >> kk) & 1u)) {
+                    const double* mn = b.mean + (sb + slot) * 8;
+                    const double* po = b.tpose + ((sb + slot) * K + kk) * 2;
+                    const float* kp = b.kp + ((fs * SS_MAXD + d) * K + kk) * 2;
+                    const double px = mn[0] + po[0] * mn[2], py = mn[1] + po[1] * mn[3];
+                    const double dx = px - (double)kp[0], dy = py - (double)kp[1];
+                    const double d2 = dx * dx + dy * dy, s2 = b.ks2[kk];
+                    t = ss_expneg(d2 / (2.0 * area * s2 * s2));
+                }
+            }
+            double acc = 0.0;
+            for (int i = 0; i < K; ++i) {                              // every lane of the wave takes part in the shuffles
+                const double ti = __shfl(t, base + i);
+                if ((common >> i) & 1u) acc = acc + ti;
+            }
+            if (act && kk == 0) {
+                const int nc = __popc(common);
+                double a = 1.0;
+                if (nc >= b.min_common && area > 0.0) {
+                    a = (1.0 - acc / (double)nc) / 2.0;
+                    if (a > b.pose_thresh) a = 1.0;
+                }
+                const double cf = pc[j];
+                cost[byte_cidx(r, k, nR, nC)] = a < cf ? a : cf;
+            }
+        }
+        __syncthreads();                                           // pe / pc: the next chunk's
+    }
+}
+
+// the stored poses after the frame's Kalman updates (§1e, K-03: the last observation, no smoothing): the slots updated in stages
+// 4-6 compacted into m.freel (free after the births), the births behind them; m.det[slot] is the row either way.  Half a wave
+// per slot, lane = keypoint: offsets from the row's box centre in widths / heights (m.dz, the measurement), all invisible when
+// the box has no extent.
+__device__ inline void byte_pose_store(const SSByteDev& b, size_t sb, size_t fs, int nB, ByteLds& m)
+{
+    const int tid = threadIdx.x, kk = tid & 31, K = b.nk;
+    int pos, nU;
+    block_scan256(m.upd[tid] >= 0, m.wtot, pos, nU);
+    if (m.upd[tid] >= 0) m.freel[pos] = tid;
+    if (tid < nB) m.freel[nU + tid] = m.born[tid];
+    __syncthreads();
+    for (int i0 = 0; i0 < nU + nB; i0 += 8) {
+        const int i = i0 + (tid >> 5);
+        if (i >= nU + nB) continue;
+        const int slot = m.freel[i], d = m.det[slot];
+        const double* z = m.dz[d];
+        const bool box = z[2] > 0.0 && z[3] > 0.0;
+        if (kk < K) {
+            const float* kp = b.kp + ((fs * SS_MAXD + d) * K + kk) * 2;
+            double* po = b.tpose + ((sb + slot) * K + kk) * 2;
+            po[0] = box ? ((double)kp[0] - z[0]) / z[2] : 0.0;
+            po[1] = box ? ((double)kp[1] - z[1]) / z[3] : 0.0;
+        }
+        if (kk == 0) b.tvis[sb + slot] = box ? b.kvis[fs * SS_MAXD + d] : 0u;
+    }
+    __syncthreads();
+}
+
 // GMC: BoT-SORT's camera-motion step 3b from b.gmc; REID: §1c's appearance term and smoothed features from b.smooth / b.ufeat
-// (both only instantiated with XYWH; without them the code is the plain tracker's)
-template <bool XYWH, bool GMC, bool REID>
+// POSE: §1e's keypoint term and stored poses from b.tpose / b.kp (all three only instantiated with XYWH, REID and POSE never
+// together; without them the code is the plain tracker's)
+template <bool XYWH, bool GMC, bool REID, bool POSE>
 __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const float* __restrict__ dets, const int* __restrict__ ndets,
                                                     float* __restrict__ out, int* __restrict__ nout)
 {
@@ -323,6 +473,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             const bool glb = nP * nHi > SS_BYTE_COST_CAP;
             double* cost = glb ? spill : m.cost;
             if constexpr (REID) byte_reid_cost(nP, nHi, m.pool, m.hi, cost, b, sb, fs, m);
+            else if constexpr (POSE) byte_pose_cost(nP, nHi, m.pool, m.hi, cost, b, sb, fs, m);
             else
             for (int e = tid; e < nP * nHi; e += 256) {
                 const int r = e / nHi, k = e - r * nHi, d = m.hi[k];
@@ -374,6 +525,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             const bool glb = nU * nLeft > SS_BYTE_COST_CAP;
             double* cost = glb ? spill : m.cost;
             if constexpr (REID) byte_reid_cost(nU, nLeft, m.unc, m.left, cost, b, sb, fs, m);
+            else if constexpr (POSE) byte_pose_cost(nU, nLeft, m.unc, m.left, cost, b, sb, fs, m);
             else
             for (int e = tid; e < nU * nLeft; e += 256) {
                 const int r = e / nLeft, k = e - r * nLeft, d = m.left[k];
@@ -446,6 +598,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
         }
         __syncthreads();
         if constexpr (REID) byte_reid_smooth(b, sb, fs, nB, m);
+        if constexpr (POSE) byte_pose_store(b, sb, fs, nB, m);
         // ---- 8. lost tracks past max_time_lost ----
         if (tid < nL) {
             const int slot = m.lost[tid];
@@ -532,10 +685,19 @@ void ss_launch_byte_group(const SSByteDev& b, int F, const float* dets, const in
 {
     if (b.reid) {
         hipLaunchKernelGGL(k_byte_feats, dim3(SS_MAXD / 4, b.S, F), dim3(256), 0, st, b, feats, ndets);
-        if (b.gmc) hipLaunchKernelGGL((k_byte_group<true, true, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
-        else hipLaunchKernelGGL((k_byte_group<true, false, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+        if (b.gmc) hipLaunchKernelGGL((k_byte_group<true, true, true, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+        else hipLaunchKernelGGL((k_byte_group<true, false, true, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
     }
-    else if (b.xywh && b.gmc) hipLaunchKernelGGL((k_byte_group<true, true, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
-    else if (b.xywh) hipLaunchKernelGGL((k_byte_group<true, false, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
-    else hipLaunchKernelGGL((k_byte_group<false, false, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    else if (b.xywh && b.gmc) hipLaunchKernelGGL((k_byte_group<true, true, false, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    else if (b.xywh) hipLaunchKernelGGL((k_byte_group<true, false, false, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    else hipLaunchKernelGGL((k_byte_group<false, false, false, false>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+}
+
+// §1e: the group with the rows' keypoints (b.pose: xywh only, ss_byte_set_pose); kpts / stride / off / geom as k_byte_kpts
+void ss_launch_byte_group_kpts(const SSByteDev& b, int F, const float* dets, const int* ndets, const float* kpts, long long stride, int off,
+                               const float* geom, float* out, int* nout, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_byte_kpts, dim3(SS_MAXD / 8, b.S, F), dim3(256), 0, st, b, kpts, stride, off, geom, ndets);
+    if (b.gmc) hipLaunchKernelGGL((k_byte_group<true, true, false, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    else hipLaunchKernelGGL((k_byte_group<true, false, false, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
 }

@@ -515,6 +515,7 @@ __device__ inline void ss_kf_update_xywh(double* mean, double* cov, const double
 #define SS_BYTE_TRACKED 1
 #define SS_BYTE_LOST 2
 #define SS_BYTE_REMOVED 3
+#define SS_BYTE_MAXK 32                 // keypoints per row: one visibility word, one lane of a half wave each
 struct SSByteDev {
     int S;
     int xywh, fuse, max_time_lost, max_tracks, max_dets;
@@ -528,6 +529,15 @@ struct SSByteDev {
     double *mean, *cov;                 // [S][MAXT][8], [S][MAXT][64]
     double* spill;                      // [S][MAXT * MAXD] cost matrices that do not fit the LDS
     const double* gmc;                  // [F][S][8] BoT-SORT GMC warps (ss_byte_set_gmc, xywh only), NULL: off
+    // the keypoint term (docs/BYTETRACK.md §1e, ss_byte_set_pose; xywh only, not with ReID), allocated when first switched on
+    int pose, nk, min_common;           // on / keypoints per row (1..SS_BYTE_MAXK) / fewest keypoints visible on both sides
+    float vis;                          // (float)kpt_vis_thresh, compared in float32
+    double pose_thresh;                 // on (1 - OKS) / 2; the proximity mask is `prox` above
+    const double* ks2;                  // [SS_BYTE_MAXK] 2 sigma_k (device memory: the argument struct stays small)
+    double* tpose;                      // [S][MAXT][nk][2] track poses by slot: offsets from the box centre in box widths / heights
+    unsigned* tvis;                     // [S][MAXT] bit k: keypoint k of the track's pose is visible
+    float* kp;                          // [FMAX][S][MAXD][nk][2] the group's detection keypoints in original pixels (k_byte_kpts)
+    unsigned* kvis;                     // [FMAX][S][MAXD] bit k: keypoint k of the row is visible
     // BoT-SORT's ReID branch (docs/BYTETRACK.md §1c, ss_byte_set_reid; xywh only), allocated when first switched on
     int reid;
     float alpha, one_minus_alpha;       // so_ema weights: (float)alpha, (float)(1 - alpha)

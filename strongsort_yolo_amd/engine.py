@@ -523,7 +523,7 @@ class TrackerEngine:
 class ByteTrackEngine:
     """The BYTE tracker family (csrc/ss_byte.hip, docs/BYTETRACK.md) on the context of a TrackerEngine: the same
     update_device / update_group / reset / check_errors shape as TrackerEngine; features only with cfg.with_reid (§1c, BoT-SORT's
-    ReID branch, switched on at construction).  `engine`: share the
+    ReID branch, switched on at construction), keypoints only with cfg.with_pose (§1e, the OKS term, likewise).  `engine`: share the
     context of an existing TrackerEngine (a pipeline's: its NMS, streams and error words); None: a context of its own."""
 
     def __init__(self, cfg: ByteTrackConfig | None = None, n_streams: int = 1, device: int = 0, engine: TrackerEngine | None = None):
@@ -537,6 +537,12 @@ class ByteTrackEngine:
         if self.reid:                               # §1c: BoT-SORT's appearance term (resets the streams)
             self._ck(self.L.ss_byte_set_reid(self.base.ctx, 1, float(self.cfg.proximity_thresh), float(self.cfg.appearance_thresh),
                                              float(self.cfg.feat_alpha)))
+        self.pose = bool(self.cfg.with_pose)
+        self.K = len(self.cfg.kpt_sigmas)
+        if self.pose:                               # §1e: the keypoint term (resets the streams)
+            sg = (C.c_double * self.K)(*[float(v) for v in self.cfg.kpt_sigmas])
+            self._ck(self.L.ss_byte_set_pose(self.base.ctx, 1, self.K, sg, float(self.cfg.proximity_thresh), float(self.cfg.pose_thresh),
+                                             float(self.cfg.kpt_vis_thresh), int(self.cfg.min_common_kpts)))
         self._cmc_keep = None
         self.out = torch.zeros(self.S, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=self.device)
         self.nout = torch.zeros(self.S, dtype=torch.int32, device=self.device)
@@ -581,19 +587,40 @@ class ByteTrackEngine:
             raise ValueError(f"ByteTrackEngine: feats must be contiguous float32 [{rows} x {MAX_DETS} x {FEAT_DIM}]")
         return feats
 
-    def update_device(self, dets, ndets, feats=None, img_hw=None, out=None, nout=None):
-        """All streams, one frame: dets [S,128,6] f32, ndets [S] i32, with ReID feats [S,128,512] f32 (raw, device) ->
-        (rows [S,256,8], counts [S]) device tensors, asynchronous.  img_hw is accepted for TrackerEngine's call shape and
-        unused (no clipping); feats is unused without ReID."""
+    def _kpts(self, kpts, rows, kpt_col, geom):
+        """with_pose: the rows' keypoints as (tensor, row stride, column, geometry) for ss_byte_update_group_kpts.  kpts: float32,
+        [rows x 128 x C] with unit column stride — [.., K, 3] triplets (kpt_col 0) or whole NMS rows with the triplets from column
+        kpt_col; geom [rows, 5] f32 (ss_nms_batch's rows): the keypoints are network-input pixels, None: original pixels."""
+        if kpts is None:
+            raise ValueError("ByteTrackEngine: with_pose needs the detections' keypoints [.., 128, K, 3] f32")
+        if kpts.dim() >= 3 and kpts.shape[-1] == 3 and kpts.shape[-2] == self.K and kpt_col == 0:
+            kpts = kpts.reshape(-1, MAX_DETS, 3 * self.K) if kpts.is_contiguous() else kpts
+        C_ = kpts.shape[-1]
+        if kpts.dtype != torch.float32 or not kpts.is_contiguous() or kpts.numel() != rows * MAX_DETS * C_ or kpt_col < 0 or C_ < kpt_col + 3 * self.K:
+            raise ValueError(f"ByteTrackEngine: kpts must be contiguous float32 [{rows} x {MAX_DETS} x C], C >= kpt_col + {3 * self.K}")
+        if geom is not None and (geom.dtype != torch.float32 or not geom.is_contiguous() or geom.numel() != rows * 5):
+            raise ValueError(f"ByteTrackEngine: geom must be contiguous float32 [{rows} x 5]")
+        return kpts, C_, int(kpt_col), geom
+
+    def update_device(self, dets, ndets, feats=None, img_hw=None, out=None, nout=None, kpts=None, kpt_col=0, geom=None):
+        """All streams, one frame: dets [S,128,6] f32, ndets [S] i32, with ReID feats [S,128,512] f32 (raw, device), with the
+        keypoint term kpts (see update_group) -> (rows [S,256,8], counts [S]) device tensors, asynchronous.  img_hw is accepted
+        for TrackerEngine's call shape and unused (no clipping); feats is unused without ReID."""
         out = self.out if out is None else out
         nout = self.nout if nout is None else nout
-        return self.update_group(1, dets, ndets, feats, img_hw, out, nout)
+        return self.update_group(1, dets, ndets, feats, img_hw, out, nout, kpts=kpts, kpt_col=kpt_col, geom=geom)
 
-    def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout):
+    def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout, kpts=None, kpt_col=0, geom=None):
         """A group of n_frames (<= 32) frames of all streams in ONE launch: dets [F,S,128,6] f32, ndets [F,S] i32, with ReID
         feats [F,S,128,512] f32 -> rows out [F,S,256,8], counts nout [F,S] (device tensors, asynchronous); frames are
-        associated in order.  img_hw unused (TrackerEngine's call shape), feats unused without ReID."""
-        if self.reid:
+        associated in order.  img_hw unused (TrackerEngine's call shape), feats unused without ReID.  With the keypoint term (§1e):
+        kpts [F,S,128,K,3] f32 triplets (x, y, v) in the dets' pixels — or the NMS rows themselves [F*S,128,C] with the triplets
+        from column kpt_col in network-input pixels and geom [F*S,5] (the NMS geometry rows) to bring them to the dets' pixels."""
+        if self.pose:
+            k, stride, col, g = self._kpts(kpts, int(n_frames) * self.S, kpt_col, geom)
+            self._ck(self.L.ss_byte_update_group_kpts(self.base.ctx, int(n_frames), _ptr(dets), _ptr(ndets), _ptr(k), stride, col,
+                                                      _ptr(g), _ptr(out), _ptr(nout)))
+        elif self.reid:
             f = self._feats(feats, int(n_frames) * self.S)
             self._ck(self.L.ss_byte_update_group_feats(self.base.ctx, int(n_frames), _ptr(dets), _ptr(ndets), _ptr(f), _ptr(out), _ptr(nout)))
         else:
@@ -608,6 +635,26 @@ class ByteTrackEngine:
         self._ck(self.L.ss_byte_get_features(self.base.ctx, stream, MAX_TRACKS, sm.ctypes.data_as(C.POINTER(C.c_float))))
         t = self.tracks(stream)
         return sm[:t["n_tracked"] + t["n_lost"]].copy()
+
+    def keypoints(self, stream: int = 0):
+        """§1e: the stored poses of one stream in tracks()' list order (with_pose only): (offsets [n,K,2] float64 from the box centre
+        in box widths / heights, visibility words [n] uint32, bit k = keypoint k)."""
+        if not self.pose:
+            raise RuntimeError("ByteTrackEngine.keypoints: with_pose is off")
+        off, vis = np.zeros((MAX_TRACKS, self.K, 2)), np.zeros(MAX_TRACKS, np.uint32)
+        self._ck(self.L.ss_byte_get_keypoints(self.base.ctx, stream, MAX_TRACKS, off.ctypes.data_as(C.POINTER(C.c_double)),
+                                              vis.ctypes.data_as(C.POINTER(C.c_uint32))))
+        t = self.tracks(stream)
+        n = t["n_tracked"] + t["n_lost"]
+        return off[:n].copy(), vis[:n].copy()
+
+    def det_keypoints(self, frame: int = 0, stream: int = 0):
+        """§1e (tests): what the last update call's first launch prepared for image (frame, stream): (xy [128,K,2] float32 in
+        original pixels, visibility words [128] uint32); rows past the image's count are not written."""
+        xy, vis = np.zeros((MAX_DETS, self.K, 2), np.float32), np.zeros(MAX_DETS, np.uint32)
+        self._ck(self.L.ss_byte_get_det_keypoints(self.base.ctx, frame, stream, xy.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  vis.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return xy, vis
 
     def tracks(self, stream: int = 0) -> dict:
         """The table of one stream in list order (tracked, then lost): track_id, state (1 tracked, 2 lost), activated, mean."""

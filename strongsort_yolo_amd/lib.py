@@ -30,6 +30,7 @@ EXPORTS = [
     "ss_byte_create", "ss_byte_destroy", "ss_byte_update_group", "ss_byte_update", "ss_byte_reset", "ss_byte_get_tracks",
     "ss_byte_set_gmc", "ss_byte_set_reid", "ss_byte_update_group_feats", "ss_byte_get_features",
     "ss_native_feats",
+    "ss_byte_set_pose", "ss_byte_update_group_kpts", "ss_byte_get_keypoints", "ss_byte_get_det_keypoints",
 ]
 
 
@@ -202,6 +203,10 @@ def load():
     L.ss_byte_set_reid.argtypes = [vp, i, C.c_double, C.c_double, C.c_double]
     L.ss_byte_update_group_feats.argtypes = [vp, i, fp, ip, fp, fp, ip]
     L.ss_byte_get_features.argtypes = [vp, i, i, C.POINTER(C.c_float)]
+    L.ss_byte_set_pose.argtypes = [vp, i, i, hd, d, d, d, i]
+    L.ss_byte_update_group_kpts.argtypes = [vp, i, fp, ip, fp, ll, i, fp, fp, ip]
+    L.ss_byte_get_keypoints.argtypes = [vp, i, i, hd, C.POINTER(C.c_uint32)]
+    L.ss_byte_get_det_keypoints.argtypes = [vp, i, i, hf, C.POINTER(C.c_uint32)]
     L.ss_native_feats.argtypes = [vp, i, i, C.POINTER(ss_native_map), i, ip, ll, ip, fp]
     for name in EXPORTS:
         fn = getattr(L, name)

@@ -40,7 +40,7 @@ class FramePipeline:
                  dcfg: Optional[DetectConfig] = None, det_source: str = "detector", feat_source: str = "reid",
                  graph: str = "all", debug: bool = False, run_nets: bool = True, seed: int = 0, detect_only_rows: int = 0, cmc: bool = False,
                  reid_half: Optional[bool] = None, crops_u8: bool = True, tracker: str = "strongsort", with_reid: bool = False,
-                 reid_model: str = "osnet"):
+                 reid_model: str = "osnet", with_pose: bool = False):
         self.cfg, self.dcfg = cfg or StrongSortConfig(), dcfg or DetectConfig()
         self.S, (self.H, self.W) = n_streams, frame_hw
         # tracker = "bytetrack" / "botsort": the BYTE tracker family (csrc/ss_byte.hip) on IoU and scores — no OSNet is built, no
@@ -50,8 +50,10 @@ class FramePipeline:
         # reid_model = "auto" (with_reid only): Ultralytics' `model: auto` (docs/BYTETRACK.md §1d) — no OSNet is built, no crops are
         # cut; one launch after NMS reads the kept rows' features from the detector's own head inputs (a forward pre-hook on
         # detector.detect keeps them until that launch is enqueued)
-        from .config import byte_config, check_reid_model
-        self.byte_cfg = byte_config(tracker, with_reid)
+        # with_pose (botsort only, not with with_reid): the keypoint term (docs/BYTETRACK.md §1e) — the tracker call reads the
+        # keypoint columns of the NMS rows in place (b.dets, row stride 6 + nk + nm, column 6) with the NMS geometry; no copy, no stage.
+        from .config import byte_config, check_reid_model, check_pose
+        self.byte_cfg = byte_config(tracker, with_reid, with_pose)
         self.reid_model = check_reid_model(reid_model, with_reid)
         self.tracker = tracker
         self.native = self.reid_model == "auto" and not detect_only_rows
@@ -103,6 +105,11 @@ class FramePipeline:
         else:
             self.nc, self.nk, self.nm = 80, 0, 0
         self.nx = self.nk + self.nm                             # extra columns NMS carries along with every kept row
+        try:
+            check_pose(self.byte_cfg, self.nk)
+        except ValueError:
+            self.eng.close()                                    # (the tracker context exists already: do not leak it)
+            raise
         g, S = self.geom, n_streams
         self.n_anchors = sum((g.out_h // s) * (g.out_w // s) for s in (8, 16, 32))
         # how the stage bodies below differ between this class and OverlappedPipeline, as data: one frame per buffer set,
@@ -255,7 +262,14 @@ class FramePipeline:
 
     def _track(self):
         b = self.b
-        self.trk.update_device(b.dets6, b.ndets, b.feats_v, self.img_hw, out=self.out, nout=self.nout)
+        self.trk.update_device(b.dets6, b.ndets, b.feats_v, self.img_hw, out=self.out, nout=self.nout, **self._pose_kw(b, 0, self.Sv))
+
+    def _pose_kw(self, b, v0, v1):
+        """with_pose: the NMS rows of virtual streams [v0, v1) as the tracker call's keypoints (their columns from 6, network-input
+        pixels, and the images' NMS geometry)."""
+        if self.byte is None or not self.byte.pose:
+            return {}
+        return dict(kpts=b.dets[v0:v1], kpt_col=6, geom=self.geom_dev[v0:v1])
 
     def reset_tracker(self, stream: int = -1):
         """Restart the tracker of one stream (all: -1), whichever family runs."""
@@ -556,7 +570,8 @@ class OverlappedPipeline(FramePipeline):
             n, v0, v1 = min(G, nv - f0), f0 * S, min(nv, f0 + G) * S
             if self.cmc:
                 e.set_cmc(b.warps[f0:f0 + n])
-            e.update_group(n, b.dets6[v0:v1], b.ndets[v0:v1], b.feats_v[v0:v1], self.img_hw, self.outs[f0:f0 + n], self.nouts[f0:f0 + n])
+            e.update_group(n, b.dets6[v0:v1], b.ndets[v0:v1], b.feats_v[v0:v1], self.img_hw, self.outs[f0:f0 + n], self.nouts[f0:f0 + n],
+                           **self._pose_kw(b, v0, v1))
         if self.sR is not None:                                 # detached chain: the rows exist once the chain's stream is done
             self.eng.track_join(self.sR)
         if group is not None and self.on_result is not None:

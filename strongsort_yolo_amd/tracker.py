@@ -83,7 +83,9 @@ class BYTETracker:
        cfg.with_reid=True (xywh only): BoT-SORT's ReID branch (§1c).  `update(dets, frame, features)` takes the rows' raw
        features [N,k] (k <= 512, zero-padded to 512: the §1d features of a `model: auto` detector have k = min(C_l)), or cuts
        the crops from `frame` and runs OSNet-x0.25 (reid_weights, loaded as StrongSORT loads them; fp16 selects half
-       activations) when `features` is None.  reid_model="auto" (§1d): no OSNet is built; update needs `features`."""
+       activations) when `features` is None.  reid_model="auto" (§1d): no OSNet is built; update needs `features`.
+       cfg.with_pose=True (xywh only, not with with_reid): the keypoint term (§1e).  `update(dets, keypoints=...)` takes the rows'
+       keypoints [N,K,3] (x, y, visibility) in the same frame pixels as `dets`."""
 
     def __init__(self, cfg: Optional[ByteTrackConfig] = None, device: int = 0, camera_motion: bool = False,
                  reid_weights: Optional[str] = None, fp16: bool = False, random_init_ok: bool = False, reid_seed: int = 1,
@@ -105,10 +107,11 @@ class BYTETracker:
             self.reid = self.reid.to(self.dev, self.dtype).to(memory_format=torch.channels_last)
         self._dets = torch.zeros(1, MAX_DETS, 6, dtype=torch.float32, device=self.dev)
         self._n = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self._kpts = torch.zeros(1, MAX_DETS, len(self.cfg.kpt_sigmas), 3, dtype=torch.float32, device=self.dev) if self.cfg.with_pose else None
         self._warps = torch.zeros(1, 1, 8, dtype=torch.float64, device=self.dev) if self.camera_motion else None
 
     @torch.no_grad()
-    def update(self, dets, frame=None, features=None) -> np.ndarray:
+    def update(self, dets, frame=None, features=None, keypoints=None) -> np.ndarray:
         self.eng.use_current_stream()
         dets = torch.as_tensor(dets, dtype=torch.float32).reshape(-1, 6)
         n = dets.shape[0]
@@ -145,7 +148,16 @@ class BYTETracker:
                 self._feats[0, :n].copy_(self.reid(crops.contiguous(memory_format=torch.channels_last)))
         elif features is not None:
             raise ValueError("features given, but cfg.with_reid is off")
-        out, nout = self.eng.update_device(self._dets, self._n, feats)
+        if self.cfg.with_pose:
+            if keypoints is None:
+                raise ValueError("with_pose: update(dets, keypoints=...) needs the rows' keypoints [N,K,3]")
+            kp = torch.as_tensor(keypoints, dtype=torch.float32).reshape(-1, self._kpts.shape[2], 3)
+            if kp.shape[0] != n:
+                raise ValueError(f"keypoints [N,K,3]: one row per detection ({n}), got {kp.shape[0]}")
+            self._kpts[0, :n].copy_(kp)
+        elif keypoints is not None:
+            raise ValueError("keypoints given, but cfg.with_pose is off")
+        out, nout = self.eng.update_device(self._dets, self._n, feats, kpts=self._kpts)
         torch.cuda.synchronize(self.dev)
         self.eng.check_errors()
         return out[0, : int(nout[0])].cpu().numpy()

@@ -289,7 +289,8 @@ class YOLO:
 
     def __init__(self, weights: str = "yolov8n.pt", seed: int = 0, random_init_ok: bool = False, reid_batch: int = 128,
                  camera_motion: bool = False, reid_weights: Optional[str] = None, reid_fp32: bool = True, half: bool = True,
-                 device_masks: bool = False, tracker_type: str = "strongsort", with_reid: bool = False, reid_model: str = "osnet"):
+                 device_masks: bool = False, tracker_type: str = "strongsort", with_reid: bool = False, reid_model: str = "osnet",
+                 with_pose: bool = False):
         """reid_fp32 (default since round 6): ReID crops + OSNet-x0.25 in fp32 on the fp32 kernels — appearance distances within 1e-4 of a CPU fp32
         network, which f16 activations miss by 330x (reid_fp32=False: the f16 throughput mode, ~1.2x the per-frame rate, 1.7x the stream rate).
         half=False: the DETECTOR in fp32 as well (the reference's own precision: it passes no half=, yolo_multi_model.py:41) on the
@@ -308,12 +309,15 @@ class YOLO:
         every tracked row (reid_weights, reid_fp32 and half as for StrongSORT) add an appearance term to the IoU association.
         reid_model (with_reid only): "osnet" (default, as above) or "auto" — Ultralytics' `model: auto` (docs/BYTETRACK.md §1d): the
         rows' features are read from the detector's own head inputs, so the detector weights are the only file; no OSNet, no
-        crops, no reid_weights (a ValueError), and reid_fp32 does not apply (the features follow `half`)."""
-        byte_config(tracker_type, with_reid)      # ValueError on anything else
+        crops, no reid_weights (a ValueError), and reid_fp32 does not apply (the features follow `half`).
+        with_pose ("botsort" on a pose model only, not with with_reid, else a ValueError): the keypoint term (docs/BYTETRACK.md §1e) —
+        the rows' own keypoints add an OKS entry to the IoU association; no second network."""
+        byte_config(tracker_type, with_reid, with_pose)      # ValueError on anything else
         check_reid_model(reid_model, with_reid, reid_weights)
         self.reid_model = reid_model
         self.tracker_type = tracker_type
         self.with_reid = bool(with_reid)
+        self.with_pose = bool(with_pose)
         self._byte = tracker_type != "strongsort"
         if tracker_type == "bytetrack" and camera_motion:
             raise ValueError("camera_motion needs tracker_type 'strongsort' or 'botsort' (ByteTrack has no GMC, G-05)")
@@ -326,6 +330,8 @@ class YOLO:
         self.seed = seed
         self.reid_batch = reid_batch
         pose = "pose" in self.arch
+        if self.with_pose and not pose:
+            raise ValueError(f"with_pose needs a pose model (keypoint columns): {weights!r} has none")
         self.names = {0: "person"} if pose else dict(enumerate(COCO_NAMES))
         self._host = {}                 # slot name -> the _HostResults of a per-frame pipeline
         self._pipe = None               # the cached pipelines (each with its .key): track() / predict(),
@@ -345,6 +351,8 @@ class YOLO:
                 self._pipe_kw["with_reid"] = True
                 if reid_model != "osnet":
                     self._pipe_kw["reid_model"] = reid_model
+            if self.with_pose:
+                self._pipe_kw["with_pose"] = True
         self.device_masks = bool(device_masks)
         self._fill = None
         self._frame_index = 0

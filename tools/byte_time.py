@@ -18,6 +18,11 @@
                               32-frame group of yolov8n head inputs at 1280x720 (f16 [32, 64|128|256, 48|24|12, 80|40|20],
                               --rows kept rows a frame); wall time per call (events), kernel time under rocprofv3.  rates mode:
                               botsort, botsort + OSNet fp32 ReID and botsort + `auto`, one leg per fresh process, interleaved.
+  --pose                      BoT-SORT's keypoint term (docs/BYTETRACK.md §1e).  kernel mode: three xywh engines on the same seeded pose
+                              streams (tests/test_botsort_pose_cpu.pose_stream), one with the term (k_byte_kpts + the POSE variant of
+                              k_byte_group), one plain and one with ReID on seeded random features (the yardstick of the other opt-in
+                              term), called alternately.  rates mode: yolo11n-pose with botsort and with botsort + with_pose, one leg
+                              per fresh process, interleaved (--rounds each).
 """
 import argparse
 import json
@@ -169,6 +174,48 @@ def kernel_reid(S, groups, warmup):
                     "rocprofv3 --kernel-trace --stats"}
 
 
+def kernel_pose(S, groups, warmup):
+    from strongsort_yolo_amd.config import ByteTrackConfig
+    from strongsort_yolo_amd.engine import ByteTrackEngine
+    from tests.test_botsort_pose_cpu import K, pose_stream
+    G = 32
+    n = (groups + warmup) * G
+    streams = [pose_stream(100 + s, n) for s in range(S)]
+    dev = torch.device("cuda", 0)
+    hd, hn, hk = np.zeros((n, S, 128, 6), np.float32), np.zeros((n, S), np.int32), np.zeros((n, S, 128, K, 3), np.float32)
+    for f in range(n):
+        for s in range(S):
+            d, kp = streams[s][f]
+            hd[f, s, :len(d)], hk[f, s, :len(d)], hn[f, s] = d, kp, len(d)
+    dets, nd, kpts = torch.from_numpy(hd).to(dev), torch.from_numpy(hn).to(dev), torch.from_numpy(hk).to(dev)
+    feats = torch.randn(G, S, 128, 512, generator=torch.Generator().manual_seed(0)).to(dev)
+    out = torch.zeros(G, S, 256, 8, device=dev)
+    nout = torch.zeros(G, S, dtype=torch.int32, device=dev)
+    engs = {"plain": ByteTrackEngine(ByteTrackConfig(kalman="xywh"), S, 0), "pose": ByteTrackEngine(ByteTrackConfig(kalman="xywh", with_pose=True), S, 0),
+            "reid": ByteTrackEngine(ByteTrackConfig(kalman="xywh", with_reid=True), S, 0)}
+    ms = {k: [] for k in engs}
+    for e in engs.values():
+        e.use_current_stream()
+    for g in range(groups + warmup):
+        sl = slice(g * G, (g + 1) * G)
+        for leg, eng in engs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            eng.update_group(G, dets[sl], nd[sl], feats, None, out, nout, kpts=kpts[sl])
+            b.record()
+            b.synchronize()
+            if g >= warmup:
+                ms[leg].append(a.elapsed_time(b))
+    for e in engs.values():
+        e.check_errors()
+    med = {k: float(np.median(v)) * 1e3 for k, v in ms.items()}
+    return {"mode": "kernel_pose", "streams": S, "group_frames": G, "groups": groups, "dets_per_frame": float(hn.mean()),
+            "plain_us_per_group_median": med["plain"], "pose_us_per_group_median": med["pose"], "reid_us_per_group_median": med["reid"],
+            "pose_over_plain": med["pose"] / med["plain"], "reid_over_plain": med["reid"] / med["plain"],
+            "note": "host event pair around one call (pose: k_byte_kpts + k_byte_group, reid: k_byte_feats + k_byte_group, includes launch "
+                    "latency); kernel times: rocprofv3 --kernel-trace --stats"}
+
+
 def kernel_auto(groups, warmup, rows):
     from strongsort_yolo_amd.engine import TrackerEngine
     dev = torch.device("cuda", 0)
@@ -224,7 +271,8 @@ def rates(n_frames, batch):
 
 def rate_leg(leg, n_frames, batch):
     """One leg in this process: botsort with (leg "botsort_cmc") or without camera_motion, botsort with ReID ("botsort_reid": OSNet
-    fp32, "botsort_auto": `model: auto`), StrongSORT with fp32 ReID ("strongsort"); 1280x720 frames panning 3 px a frame."""
+    fp32, "botsort_auto": `model: auto`), StrongSORT with fp32 ReID ("strongsort"), yolo11n-pose with botsort ("pose_botsort") and with
+    the keypoint term ("pose_botsort_pose"); 1280x720 frames panning 3 px a frame."""
     os.environ["SS_RANDOM_INIT"] = "1"
     from strongsort_yolo_amd.yolo import YOLO
     pan = _pan_frames(16, 1)
@@ -232,6 +280,8 @@ def rate_leg(leg, n_frames, batch):
     frames += frames[::-1]                                  # back and forth: the sequence can repeat without a jump
     if leg == "strongsort":
         m = YOLO("yolov8n.pt", random_init_ok=True)
+    elif leg in ("pose_botsort", "pose_botsort_pose"):      # the pose model under both legs: only the term differs
+        m = YOLO("yolo11n-pose.pt", random_init_ok=True, tracker_type="botsort", with_pose=leg == "pose_botsort_pose")
     else:
         m = YOLO("yolov8n.pt", random_init_ok=True, tracker_type="botsort", camera_motion=leg == "botsort_cmc",
                  with_reid=leg in ("botsort_reid", "botsort_auto"), reid_model="auto" if leg == "botsort_auto" else "osnet")
@@ -263,7 +313,7 @@ def rates_legs(n_frames, batch, rounds, names, mode):
             if p.returncode != 0:
                 raise RuntimeError(f"leg {leg} failed ({p.returncode}): {p.stderr[-2000:]}")
             legs[leg].append(json.loads(p.stdout.strip().splitlines()[-1]))
-    res = {"mode": mode, "weights": "yolov8n (seeded random init)", "frame": "1280x720", "batch": batch, "rounds": rounds}
+    res = {"mode": mode, "weights": ("yolo11n-pose" if mode == "rates_pose" else "yolov8n") + " (seeded random init)", "frame": "1280x720", "batch": batch, "rounds": rounds}
     for leg, rs in legs.items():
         for k in ("track_calls_per_s", "track_stream_frames_per_s"):
             res[f"{leg}_{k}_median"] = float(np.median([r[k] for r in rs]))
@@ -284,12 +334,15 @@ if __name__ == "__main__":
     p.add_argument("--reid", action="store_true", help="BoT-SORT ReID legs (see the module docstring)")
     p.add_argument("--auto", action="store_true", help="BoT-SORT ReID with model: auto (see the module docstring)")
     p.add_argument("--rows", type=int, default=28, help="kernel --auto: kept rows a frame")
-    p.add_argument("--leg", choices=("botsort", "botsort_cmc", "botsort_reid", "botsort_auto", "strongsort"), default=None, help=argparse.SUPPRESS)
+    p.add_argument("--pose", action="store_true", help="BoT-SORT keypoint-term legs (see the module docstring)")
+    p.add_argument("--leg", choices=("botsort", "botsort_cmc", "botsort_reid", "botsort_auto", "strongsort", "pose_botsort", "pose_botsort_pose"), default=None, help=argparse.SUPPRESS)
     a = p.parse_args()
     if a.leg is not None:
         r = rate_leg(a.leg, a.frames, a.batch)
     elif a.mode == "kernel":
-        r = kernel_auto(a.groups, a.warmup, a.rows) if a.auto else kernel_reid(a.streams, a.groups, a.warmup) if a.reid else kernel_gmc(a.streams, a.groups, a.warmup) if a.gmc else kernel(a.streams, a.groups, a.warmup)
+        r = kernel_pose(a.streams, a.groups, a.warmup) if a.pose else kernel_auto(a.groups, a.warmup, a.rows) if a.auto else kernel_reid(a.streams, a.groups, a.warmup) if a.reid else kernel_gmc(a.streams, a.groups, a.warmup) if a.gmc else kernel(a.streams, a.groups, a.warmup)
+    elif a.pose:
+        r = rates_legs(a.frames, a.batch, a.rounds, ("pose_botsort", "pose_botsort_pose"), "rates_pose")
     elif a.auto:
         r = rates_legs(a.frames, a.batch, a.rounds, ("botsort", "botsort_reid", "botsort_auto"), "rates_auto")
     elif a.reid:
