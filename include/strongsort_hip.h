@@ -233,7 +233,7 @@ int ss_byte_destroy(ss_ctx* ctx);
 int ss_byte_update_group(ss_ctx* ctx, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
 int ss_byte_update(ss_ctx* ctx, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
 int ss_byte_reset(ss_ctx* ctx, int stream);                /* stream < 0: all streams; ids restart at 1, frame_id at 1; the
-                                                              stream's previous ss_cmc_estimate frame is forgotten (no warp next)
+                                                              stream's previous ss_cmc_estimate / ss_gmc_sparse_estimate frame is forgotten (no warp next)
                                                               and its ReID track features and stored poses are cleared */
 /* BoT-SORT GMC (docs/BYTETRACK.md §1b): the following ss_byte_update(_group) calls move every track's Kalman mean and covariance
  * by d_warps[f][s][8] (ss_cmc_estimate's layout; [6] < 0: no warp) after predicting frame f.  The caller keeps at least
@@ -307,6 +307,28 @@ int ss_byte_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracked, int* n_
 int ss_cmc_estimate(ss_ctx* ctx, void* hip_stream, const uint8_t* d_frames, int n_frames, long long frame_stride, int h, int w,
                     int row_stride, const int* d_n_valid, double* d_warps);
 int ss_track_set_cmc(ss_ctx* ctx, const double* d_warps);
+
+/* ---- BoT-SORT GMC by sparse optical flow (docs/BYTETRACK.md §1f, decisions S-01..; Ultralytics' gmc_method: sparseOptFlow,
+ * restated) ----------------------------------------------------------------------------------------------------------
+ * ss_gmc_sparse_estimate: ss_cmc_estimate's contract and output layout with another estimator.  For the n_frames x n_streams BGR
+ * u8 frames at d_frames ([F][S] order, frame_stride bytes apart): the half-size grey image and three pyrDown levels, up to 1000
+ * Shi-Tomasi corners per image (computed once, they serve the pair with the next frame), pyramidal Lucas-Kanade (21 x 21 window,
+ * levels 3..0, <= 30 iterations) from each frame's predecessor (the stream's last real frame of the previous call for f = 0), and a
+ * similarity fit (1024 two-point hypotheses, 3 px inlier bound, closed-form refit).  d_warps[f][s][8] = 2x3 matrix previous ->
+ * current in full-frame pixels, [6] = inliers (>= 2) or -1 with the identity stored (no predecessor: first frame or after
+ * ss_reset / ss_byte_reset; fewer than 5 tracked corners; an image of the pair without a corner; a frame past *d_n_valid),
+ * [7] = tracked corners.  Asynchronous on hip_stream and capturable once the first call for a frame size has been made outside a
+ * capture (it allocates).  d_n_valid: as ss_cmc_estimate.  64 <= h, w <= 16384 (level 3 of the half image is at least 4 x 4),
+ * row_stride >= 3 * w; every argument is checked before the context and the device: SS_ERR_INVALID, even with ctx NULL.
+ * ss_gmc_sparse_get: synchronous inspection call, a permanent part of this ABI like ss_get_debug (the tests compare every stage
+ * through it bit for bit).  For the pair (frame, stream) of the last estimate: the current image's half-size grey image and its
+ * three lower levels (sizes: w/2 x h/2, then (n + 1) / 2 per level); the previous image's corners [n][2] (x, y) in selection
+ * order, their count and the number of candidates before the cut to 1000; the corners' tracked positions [1000][2] (half-size
+ * pixels), status bytes [1000] and inlier mask [1000].  Any pointer may be NULL. */
+int ss_gmc_sparse_estimate(ss_ctx* ctx, void* hip_stream, const uint8_t* d_frames, int n_frames, long long frame_stride, int h, int w,
+                           int row_stride, const int* d_n_valid, double* d_warps);
+int ss_gmc_sparse_get(ss_ctx* ctx, int frame, int stream, uint8_t* half, uint8_t* level1, uint8_t* level2, uint8_t* level3,
+                      int* corners_xy, int* n_corners, int* n_candidates, double* points, uint8_t* status, uint8_t* inliers);
 
 /* Synchronous convenience for one stream with host buffers (used by StrongSORT.update). */
 int ss_track_update_host(ss_ctx* ctx, int stream, const float* h_dets, int n, const float* h_feats,

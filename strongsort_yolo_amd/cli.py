@@ -198,7 +198,8 @@ def process_video(args: dict, model=None) -> dict:
                      reid_fp32=not args.get("reid_f16", False), half=not args.get("fp32", False),
                      device_masks=args.get("device_masks", False), tracker_type=args.get("tracker", "strongsort"),
                      camera_motion=args.get("camera_motion", False), with_reid=args.get("with_reid", False),
-                     reid_model=args.get("reid_model", "osnet"), with_pose=args.get("with_pose", False))
+                     reid_model=args.get("reid_model", "osnet"), with_pose=args.get("with_pose", False),
+                     gmc_method=args.get("gmc_method", "ecc"))
         model.overrides.update(conf=0.3, iou=0.4, agnostic_nms=False, max_det=1000)      # :18-21
     name = os.path.splitext(os.path.basename(str(source)))[0] or "stream"
     writer = LabelsWriter(os.path.join(args.get("outdir", "output"), f"{name}_labels.txt"), args.get("compat", False))
@@ -270,6 +271,9 @@ def main(argv=None):
     p.add_argument("--camera-motion", action="store_true",
                    help="ECC camera-motion compensation on the device: StrongSORT moves its track boxes, botsort applies BoT-SORT's GMC "
                         "(docs/BYTETRACK.md §1b); not with --tracker bytetrack")
+    p.add_argument("--gmc-method", choices=("ecc", "sparseOptFlow"), default="ecc",
+                   help="--camera-motion with --tracker botsort only: ecc (default) or sparseOptFlow, the estimator Ultralytics' botsort.yaml "
+                        "names (corners, pyramidal Lucas-Kanade, RANSAC similarity on the device; docs/BYTETRACK.md §1f)")
     p.add_argument("--with-reid", action="store_true",
                    help="--tracker botsort only: BoT-SORT's ReID branch, OSNet-x0.25 appearance beside IoU (docs/BYTETRACK.md §1c; needs --reid-weights or --random-init)")
     p.add_argument("--reid-model", choices=("osnet", "auto"), default="osnet",
@@ -285,6 +289,10 @@ def main(argv=None):
     a = p.parse_args(argv)
     if a.camera_motion and a.tracker == "bytetrack":
         p.error("--camera-motion needs --tracker strongsort or botsort (ByteTrack has no GMC)")
+    if a.gmc_method != "ecc" and not a.camera_motion:
+        p.error("--gmc-method is a camera-motion estimator: it needs --camera-motion")
+    if a.gmc_method != "ecc" and a.tracker != "botsort":
+        p.error("--gmc-method sparseOptFlow is BoT-SORT's GMC: it needs --tracker botsort")
     if a.with_reid and a.tracker != "botsort":
         p.error("--with-reid is BoT-SORT's ReID branch: it needs --tracker botsort")
     if a.with_pose and a.tracker != "botsort":
@@ -297,7 +305,7 @@ def main(argv=None):
         p.error("--reid-model is a model for BoT-SORT's ReID branch: it needs --with-reid")
     if a.reid_model == "auto" and a.reid_weights:
         p.error("--reid-model auto reads the detector's own features: --reid-weights does not apply")
-    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose,
+    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method,
              "save": (a.save if len(a.source) == 1 else f"{os.path.splitext(a.save)[0]}_{i}{os.path.splitext(a.save)[1]}") if a.save else None}
             for i, s in enumerate(a.source)]
     import torch

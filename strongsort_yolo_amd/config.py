@@ -151,3 +151,19 @@ def check_reid_model(reid_model: str, with_reid: bool, reid_weights=None) -> str
     if reid_model == "auto" and reid_weights:
         raise ValueError("reid_model='auto' reads the detector's own features: reid_weights (OSNet) does not apply")
     return reid_model
+
+
+# BoT-SORT's camera-motion estimator: "ecc" — the 0.1x euclidean ECC of csrc/ss_cmc.hip (G-01, the default: what camera_motion=True
+# has always meant); "sparseOptFlow" — Ultralytics' botsort.yaml default, restated in docs/BYTETRACK.md §1f (csrc/ss_gmc.hip)
+GMC_METHODS = ("ecc", "sparseOptFlow")
+
+
+def check_gmc_method(gmc_method: str, camera_motion: bool, tracker_type: str) -> str:
+    if gmc_method not in GMC_METHODS:
+        raise ValueError(f"gmc_method must be one of {GMC_METHODS}, not {gmc_method!r}")
+    if gmc_method == "sparseOptFlow" and not camera_motion:
+        raise ValueError("gmc_method='sparseOptFlow' is a camera-motion estimator: it needs camera_motion=True")
+    if gmc_method == "sparseOptFlow" and tracker_type != "botsort":
+        raise ValueError(f"gmc_method='sparseOptFlow' is BoT-SORT's GMC: tracker_type 'botsort', not {tracker_type!r} "
+                         "(StrongSORT's compensation is ECC, ByteTrack has none, G-05)")
+    return gmc_method

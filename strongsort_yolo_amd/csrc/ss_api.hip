@@ -37,6 +37,7 @@ void ss_launch_unpack_feats(const void*, int, const int*, const int*, int, int, 
 void ss_launch_pack_results(const int*, const float*, int, int, const int*, const float*, int, int, float*, hipStream_t);
 void ss_launch_overlay(uint8_t*, int, long long, int, int, int, const void*, const int*, const uint8_t*, const uint8_t*, hipStream_t);
 void ss_launch_cmc(const uint8_t*, int, long long, int, int, int, uint8_t*, long long, int, int, int, int, int, double, int*, const int*, double*, hipStream_t);
+void ss_launch_gmc_sparse(const SSGmcDev&, const uint8_t*, int, long long, int, const int*, double*, hipStream_t);
 int  ss_mask_max_words();
 void ss_launch_mask_assemble(const void*, int, long long, int, int, int, const float*, long long, int, int, const int*, int, int, const float*,
                              long long, int, int, uint32_t*, long long, hipStream_t);
@@ -81,6 +82,7 @@ struct ss_ctx {
     int cmc_hw[2];              // frame size the buffer was made for
     int* cmc_prev_valid;        // [S]
     const double* cmc_warps;    // what ss_track_set_cmc installed
+    SSGmcDev gmc;               // sparse-optical-flow estimator (ss_gmc.hip); gmc.h == 0 until the first ss_gmc_sparse_estimate
     hipEvent_t assoc_event;     // what ss_track_set_assoc_event installed (recorded after every association launch)
     struct Back { void* p = nullptr; size_t cap = 0; } back;      // device -> host staging (ss_download)
     int cos_grid;               // persistent workgroups of the association kernel
@@ -178,6 +180,7 @@ extern "C" int ss_create(const ss_config* cfg, int device, ss_ctx** out)
     c->chain_cus = 0; c->chain_stream = nullptr; c->ev_head = c->ev_chain = nullptr; c->chain_pending = false;
     c->inkernel = 0;
     c->cls_mask[0] = c->cls_mask[1] = ~0ull;
+    memset(&c->gmc, 0, sizeof c->gmc);
     c->cmc_small = nullptr; c->cmc_stride = 0; c->cmc_hw[0] = c->cmc_hw[1] = 0; c->cmc_warps = nullptr; c->assoc_event = nullptr;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) { int r = fail(nullptr, SS_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e)); delete c; return r; }
@@ -228,6 +231,8 @@ extern "C" int ss_create(const ss_config* cfg, int device, ss_ctx** out)
     if (rc == SS_OK) rc = dalloc(c, &c->kat_err, 4);
     if (rc == SS_OK) rc = dalloc(c, &c->font, 95 * 5);
     if (rc == SS_OK) rc = dalloc(c, &c->cmc_prev_valid, S);
+    if (rc == SS_OK) rc = dalloc(c, &c->gmc.prev_valid, S);
+    if (rc == SS_OK) rc = dalloc(c, &c->gmc.last, 1);
     c->nms_ws_bytes = ss_nms_workspace_bytes();
     c->nms_units = 1;
     if (rc == SS_OK) { char* w; rc = dalloc(c, &w, c->nms_ws_bytes); c->nms_ws = w; }
@@ -388,6 +393,82 @@ extern "C" int ss_track_set_cmc(ss_ctx* c, const double* d_warps)
     return SS_OK;
 }
 
+// ---- sparse-optical-flow camera motion (ss_gmc.hip, docs/BYTETRACK.md §1f) -----------------------------------------------------
+// Arguments are checked before the context: a bad call returns SS_ERR_INVALID without touching the device, context or not.
+extern "C" int ss_gmc_sparse_estimate(ss_ctx* c, void* hip_stream, const uint8_t* d_frames, int n_frames, long long frame_stride, int h,
+                                      int w, int row_stride, const int* d_n_valid, double* d_warps)
+{
+    const char* bad = nullptr;
+    if (!d_frames || !d_warps) bad = "null pointer";
+    else if (n_frames < 1 || n_frames > SS_FMAX) bad = "n_frames outside 1..32";
+    else if (h < SS_GMC_MIN_SIDE || w < SS_GMC_MIN_SIDE || h > 16384 || w > 16384) bad = "frame sides outside 64..16384 (level 3 of the half image must be at least 4 x 4)";
+    else if (row_stride < 3 * w) bad = "row_stride below 3 * w";
+    if (bad) return fail(c, SS_ERR_INVALID, std::string("ss_gmc_sparse_estimate: ") + bad);
+    if (!c) return fail(c, SS_ERR_INVALID, "ss_gmc_sparse_estimate: null context");
+    SSGmcDev& g = c->gmc;
+    if (g.h != h || g.w != w) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hip_stream) HIPCHK(c, hipStreamIsCapturing((hipStream_t)hip_stream, &cs));
+        if (cs != hipStreamCaptureStatusNone)
+            return fail(c, SS_ERR_INVALID, "ss_gmc_sparse_estimate: first call for a frame size must not be inside a graph capture");
+        const size_t S = c->dev.S, FM = SS_FMAX;
+        g.S = (int)S;
+        long long off = 0;
+        for (int L = 0; L < SS_GMC_LEVELS; ++L) {
+            g.lw[L] = L ? (g.lw[L - 1] + 1) / 2 : w / 2;
+            g.lh[L] = L ? (g.lh[L - 1] + 1) / 2 : h / 2;
+            g.loff[L] = off;
+            off += (long long)g.lw[L] * g.lh[L];
+        }
+        g.pyr_stride = (off + 15) / 16 * 16;
+        const size_t npix = (size_t)g.lw[0] * g.lh[0];
+        int rc = dalloc(c, &g.pyr, (FM + 1) * S * (size_t)g.pyr_stride);
+        if (rc == SS_OK) rc = dalloc(c, &g.eig, FM * S * npix);
+        if (rc == SS_OK) rc = dalloc(c, &g.cand, FM * S * npix);
+        if (rc == SS_OK) rc = dalloc(c, &g.emax, FM * S);
+        if (rc == SS_OK) rc = dalloc(c, &g.corners, (FM + 1) * S * SS_GMC_MAXC);
+        if (rc == SS_OK) rc = dalloc(c, &g.ncorner, (FM + 1) * S);
+        if (rc == SS_OK) rc = dalloc(c, &g.ncand, (FM + 1) * S);
+        if (rc == SS_OK) rc = dalloc(c, &g.pts, FM * S * SS_GMC_MAXC * 2);
+        if (rc == SS_OK) rc = dalloc(c, &g.status, FM * S * SS_GMC_MAXC);
+        if (rc == SS_OK) rc = dalloc(c, &g.inlier, FM * S * SS_GMC_MAXC);
+        if (rc) { g.h = g.w = 0; return rc; }
+        g.h = h; g.w = w;
+        HIPCHK(c, hipMemsetAsync(g.prev_valid, 0, S * 4, c->stream));
+        HIPCHK(c, hipMemsetAsync(g.last, 0, 4, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    ss_launch_gmc_sparse(g, d_frames, n_frames, frame_stride, row_stride, d_n_valid, d_warps, (hipStream_t)hip_stream);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+extern "C" int ss_gmc_sparse_get(ss_ctx* c, int frame, int stream, uint8_t* half, uint8_t* level1, uint8_t* level2, uint8_t* level3,
+                                 int* corners_xy, int* n_corners, int* n_candidates, double* points, uint8_t* status, uint8_t* inliers)
+{
+    if (!c || !c->gmc.h || frame < 0 || frame >= SS_FMAX || stream < 0 || stream >= c->dev.S)
+        return fail(c, SS_ERR_INVALID, "ss_gmc_sparse_get: no estimate yet, or frame / stream out of range");
+    const SSGmcDev& g = c->gmc;
+    HIPCHK(c, hipDeviceSynchronize());
+    const size_t prev = (size_t)frame * g.S + stream, cur = prev + g.S;
+    uint8_t* lv[SS_GMC_LEVELS] = { half, level1, level2, level3 };
+    for (int L = 0; L < SS_GMC_LEVELS; ++L)
+        if (lv[L]) HIPCHK(c, hipMemcpy(lv[L], g.pyr + cur * g.pyr_stride + g.loff[L], (size_t)g.lw[L] * g.lh[L], hipMemcpyDeviceToHost));
+    int n = 0;
+    HIPCHK(c, hipMemcpy(&n, g.ncorner + prev, 4, hipMemcpyDeviceToHost));
+    if (n_corners) *n_corners = n;
+    if (n_candidates) HIPCHK(c, hipMemcpy(n_candidates, g.ncand + prev, 4, hipMemcpyDeviceToHost));
+    if (corners_xy) {
+        std::vector<int> idx(SS_GMC_MAXC);
+        HIPCHK(c, hipMemcpy(idx.data(), g.corners + prev * SS_GMC_MAXC, SS_GMC_MAXC * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) { corners_xy[2 * i] = idx[i] % g.lw[0]; corners_xy[2 * i + 1] = idx[i] / g.lw[0]; }
+    }
+    if (points) HIPCHK(c, hipMemcpy(points, g.pts + prev * SS_GMC_MAXC * 2, SS_GMC_MAXC * 16, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(c, hipMemcpy(status, g.status + prev * SS_GMC_MAXC, SS_GMC_MAXC, hipMemcpyDeviceToHost));
+    if (inliers) HIPCHK(c, hipMemcpy(inliers, g.inlier + prev * SS_GMC_MAXC, SS_GMC_MAXC, hipMemcpyDeviceToHost));
+    return SS_OK;
+}
+
 // ---- N2 overlay -----------------------------------------------------------------------------------------
 extern "C" int ss_overlay_set_font(ss_ctx* c, const uint8_t* h_font_95x5)
 {
@@ -483,6 +564,7 @@ extern "C" int ss_reset(ss_ctx* c, int stream)
     }
     HIPCHK(c, hipMemsetAsync(d.n_items, 0, 32, c->stream));
     for (int s = s0; s < s1; ++s) HIPCHK(c, hipMemsetAsync(c->cmc_prev_valid + s, 0, 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->gmc.prev_valid + s0, 0, (size_t)(s1 - s0) * 4, c->stream));
     if (stream < 0)
         for (int u = 0; u < c->nms_units; ++u) HIPCHK(c, hipMemsetAsync(ss_nms_error_flag(c->nms_ws, u), 0, 4, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1101,6 +1183,7 @@ extern "C" int ss_byte_reset(ss_ctx* c, int stream)
     HIPCHK(c, hipMemsetAsync(b.n_lost + s0, 0, (s1 - s0) * 4, c->stream));
     HIPCHK(c, hipMemcpyAsync(b.next_id + s0, ones.data(), (s1 - s0) * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->cmc_prev_valid + s0, 0, (s1 - s0) * 4, c->stream));     // G-04: the next frame gets no warp
+    HIPCHK(c, hipMemsetAsync(c->gmc.prev_valid + s0, 0, (s1 - s0) * 4, c->stream));     // ... from either estimator
     if (b.smooth)                                                                        // §1c: the streams' track features
         HIPCHK(c, hipMemsetAsync(b.smooth + (size_t)s0 * SS_MAXT * SS_F, 0, (size_t)(s1 - s0) * SS_MAXT * SS_F * 4, c->stream));
     if (b.tpose) {                                                                       // §1e: the streams' track poses

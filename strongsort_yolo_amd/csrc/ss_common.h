@@ -546,6 +546,27 @@ struct SSByteDev {
     float* ufeat;                       // [FMAX][S][MAXD][F] unit detection features of the group (k_byte_feats)
 };
 
+// Device state of the sparse-optical-flow camera-motion estimator (csrc/ss_gmc.hip, docs/BYTETRACK.md §1f), hung off a context by
+// the first ss_gmc_sparse_estimate call for a frame size.  Image slot 0 of a stream is the remembered frame, slots 1..F the group's.
+#define SS_GMC_MAXC 1000                // corners per image (S-05)
+#define SS_GMC_LEVELS 4                 // pyramid levels 0..3 (S-03)
+#define SS_GMC_MIN_SIDE 64              // smallest frame side: level 3 is at least 4 x 4
+struct SSGmcDev {
+    int S, h, w;                        // streams, frame size
+    int lw[SS_GMC_LEVELS], lh[SS_GMC_LEVELS];
+    long long loff[SS_GMC_LEVELS];      // byte offset of a level inside an image's pyramid
+    long long pyr_stride;               // bytes per pyramid (multiple of 16)
+    uint8_t* pyr;                       // [FMAX+1][S][pyr_stride] grey half image and its three lower levels
+    float* eig;                         // [FMAX][S][lw0*lh0] smaller eigenvalue per pixel
+    unsigned* cand;                     // [FMAX][S][lw0*lh0] its bits where the pixel is a corner candidate, else 0
+    unsigned* emax;                     // [FMAX][S] bits of the image's largest eigenvalue
+    int *corners, *ncorner, *ncand;     // [FMAX+1][S][MAXC] pixel indices in order, [FMAX+1][S] kept, [FMAX+1][S] candidates
+    double* pts;                        // [FMAX][S][MAXC][2] tracked corners of the previous image, half-size pixels
+    uint8_t *status, *inlier;           // [FMAX][S][MAXC]
+    int* prev_valid;                    // [S] the stream has a remembered frame
+    int* last;                          // slot of the last real frame of the previous call (0: none new)
+};
+
 // camera-motion warp m (2x3, full-frame pixels) applied to a track's box (oracle so_camera_update, D-18)
 __device__ inline void ss_camera_update(double* mean, const double* m)
 {

@@ -174,6 +174,38 @@ class TrackerEngine:
                                         frames.shape[1], frames.shape[2], frames.stride(1), _ptr(n_valid), _ptr(warps)))
         return warps
 
+    def gmc_sparse_estimate(self, frames: torch.Tensor, n_frames: int, warps: torch.Tensor = None, stream=None, n_valid: torch.Tensor = None):
+        """Sparse-optical-flow camera-motion warps of a group (docs/BYTETRACK.md §1f): cmc_estimate's arguments and layout;
+        [6] = inliers or -1, [7] = tracked corners.  Frame sides >= 64."""
+        if warps is None:
+            warps = torch.zeros(n_frames, self.S, 8, dtype=torch.float64, device=self.device)
+        self._gmc_hw = (int(frames.shape[1]), int(frames.shape[2]))
+        self._ck(self.L.ss_gmc_sparse_estimate(self.ctx, self._st(stream), _ptr(frames), int(n_frames), frames.stride(0),
+                                               frames.shape[1], frames.shape[2], frames.stride(1), _ptr(n_valid), _ptr(warps)))
+        return warps
+
+    def estimate_warps(self, method: str, *args, **kw):
+        """cmc_estimate ("ecc") or gmc_sparse_estimate ("sparseOptFlow")."""
+        return (self.gmc_sparse_estimate if method == "sparseOptFlow" else self.cmc_estimate)(*args, **kw)
+
+    def gmc_sparse_stages(self, frame: int, stream: int = 0) -> dict:
+        """Synchronous: the stages of pair (frame, stream) of the last gmc_sparse_estimate call (ss_gmc_sparse_get): the current
+        image's pyramid (4 uint8 arrays), the previous image's corners [n,2] and candidate count, the tracked points [n,2],
+        status [n] and inlier mask [n]."""
+        g = self._gmc_hw
+        sizes = [(g[0] // 2, g[1] // 2)]
+        for _ in range(3):
+            sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+        lv = [np.zeros(sz, np.uint8) for sz in sizes]
+        cxy, pts = np.zeros((1000, 2), np.int32), np.zeros((1000, 2), np.float64)
+        st, inl = np.zeros(1000, np.uint8), np.zeros(1000, np.uint8)
+        n, nc = C.c_int(0), C.c_int(0)
+        u8p, ip, dp = C.POINTER(C.c_uint8), C.POINTER(C.c_int), C.POINTER(C.c_double)
+        self._ck(self.L.ss_gmc_sparse_get(self.ctx, int(frame), int(stream), *[a.ctypes.data_as(u8p) for a in lv], cxy.ctypes.data_as(ip),
+                                          C.byref(n), C.byref(nc), pts.ctypes.data_as(dp), st.ctypes.data_as(u8p), inl.ctypes.data_as(u8p)))
+        k = n.value
+        return dict(pyramid=lv, corners=cxy[:k], n_candidates=nc.value, points=pts[:k], status=st[:k], inliers=inl[:k])
+
     def set_cmc(self, warps):
         """The following tracker calls compensate camera motion with these warps ([F,S,8] float64); None: off."""
         self._cmc_keep = warps
@@ -549,6 +581,8 @@ class ByteTrackEngine:
         # the context's own: streams, error words, group size, the ECC warps of a group (N4: frames uint8 [F*S,H,W,3] -> [F,S,8])
         self.use_stream, self.use_current_stream = self.base.use_stream, self.base.use_current_stream
         self.check_errors, self.cmc_estimate = self.base.check_errors, self.base.cmc_estimate
+        self.gmc_sparse_estimate, self.estimate_warps = self.base.gmc_sparse_estimate, self.base.estimate_warps
+        self.gmc_sparse_stages = self.base.gmc_sparse_stages
 
     @property
     def ctx(self):

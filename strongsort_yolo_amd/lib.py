@@ -31,6 +31,7 @@ EXPORTS = [
     "ss_byte_set_gmc", "ss_byte_set_reid", "ss_byte_update_group_feats", "ss_byte_get_features",
     "ss_native_feats",
     "ss_byte_set_pose", "ss_byte_update_group_kpts", "ss_byte_get_keypoints", "ss_byte_get_det_keypoints",
+    "ss_gmc_sparse_estimate", "ss_gmc_sparse_get",
 ]
 
 
@@ -207,6 +208,8 @@ def load():
     L.ss_byte_update_group_kpts.argtypes = [vp, i, fp, ip, fp, ll, i, fp, fp, ip]
     L.ss_byte_get_keypoints.argtypes = [vp, i, i, hd, C.POINTER(C.c_uint32)]
     L.ss_byte_get_det_keypoints.argtypes = [vp, i, i, hf, C.POINTER(C.c_uint32)]
+    L.ss_gmc_sparse_estimate.argtypes = [vp, vp, vp, i, ll, i, i, i, ip, vp]
+    L.ss_gmc_sparse_get.argtypes = [vp, i, i, hu8, hu8, hu8, hu8, hi, hi, hi, hd, hu8, hu8]
     L.ss_native_feats.argtypes = [vp, i, i, C.POINTER(ss_native_map), i, ip, ll, ip, fp]
     for name in EXPORTS:
         fn = getattr(L, name)

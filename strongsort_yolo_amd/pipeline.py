@@ -40,7 +40,7 @@ class FramePipeline:
                  dcfg: Optional[DetectConfig] = None, det_source: str = "detector", feat_source: str = "reid",
                  graph: str = "all", debug: bool = False, run_nets: bool = True, seed: int = 0, detect_only_rows: int = 0, cmc: bool = False,
                  reid_half: Optional[bool] = None, crops_u8: bool = True, tracker: str = "strongsort", with_reid: bool = False,
-                 reid_model: str = "osnet", with_pose: bool = False):
+                 reid_model: str = "osnet", with_pose: bool = False, gmc_method: str = "ecc"):
         self.cfg, self.dcfg = cfg or StrongSortConfig(), dcfg or DetectConfig()
         self.S, (self.H, self.W) = n_streams, frame_hw
         # tracker = "bytetrack" / "botsort": the BYTE tracker family (csrc/ss_byte.hip) on IoU and scores — no OSNet is built, no
@@ -52,8 +52,11 @@ class FramePipeline:
         # detector.detect keeps them until that launch is enqueued)
         # with_pose (botsort only, not with with_reid): the keypoint term (docs/BYTETRACK.md §1e) — the tracker call reads the
         # keypoint columns of the NMS rows in place (b.dets, row stride 6 + nk + nm, column 6) with the NMS geometry; no copy, no stage.
-        from .config import byte_config, check_reid_model, check_pose
+        # gmc_method (cmc only): "ecc" (csrc/ss_cmc.hip) or, for botsort, "sparseOptFlow" (docs/BYTETRACK.md §1f, csrc/ss_gmc.hip):
+        # which estimator fills the group's warps; the tracker call reads either the same way.
+        from .config import byte_config, check_reid_model, check_pose, check_gmc_method
         self.byte_cfg = byte_config(tracker, with_reid, with_pose)
+        self.gmc_method = check_gmc_method(gmc_method, cmc, tracker)
         self.reid_model = check_reid_model(reid_model, with_reid)
         self.tracker = tracker
         self.native = self.reid_model == "auto" and not detect_only_rows
@@ -115,7 +118,7 @@ class FramePipeline:
         # how the stage bodies below differ between this class and OverlappedPipeline, as data: one frame per buffer set,
         # crops at one slot range per stream, net outputs not kept (OverlappedPipeline sets its own after this constructor)
         self.F, self.Sv, self.pack, self.keep_net_outputs = 1, S, False, False
-        # N4 (optional): ECC camera-motion warps estimated beside the detector, applied by the tracker before predicting
+        # N4 (optional): camera-motion warps (gmc_method) estimated beside the detector, applied by the tracker before predicting
         self.cmc = bool(cmc)
         # ---- static buffers (addresses are baked into the graph): ONE set, under the names callers fill and read ----
         b = self.b = _Bufs(self, S, self.det_rows, 1, self.cmc)
@@ -131,7 +134,7 @@ class FramePipeline:
         self.graph_all = None
         self.graph_mode = graph
         if self.cmc:
-            self.eng.cmc_estimate(self.frames, 1, self.warps)            # sizes the small-frame buffer outside any capture
+            self.eng.estimate_warps(self.gmc_method, self.frames, 1, self.warps)   # sizes the estimator's buffers outside any capture
             self.reset_tracker(-1)
             self.trk.set_cmc(self.warps)
 
@@ -143,7 +146,7 @@ class FramePipeline:
 
     def _letterbox(self, b):
         if self.cmc:                                           # the group's F warps, beside the detector (stateless stage)
-            self.eng.cmc_estimate(b.frames, self.F, b.warps, n_valid=b.nvalid)    # a partial group: the last REAL frame becomes "previous"
+            self.eng.estimate_warps(self.gmc_method, b.frames, self.F, b.warps, n_valid=b.nvalid)    # a partial group: the last REAL frame becomes "previous"
         if self.run_nets:
             self.eng.letterbox_batch(b.frames, self.geom, half=self.half, pad_value=self.dcfg.pad_value, out=b.lb,
                                      channels_last=True)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import nets
-from .config import StrongSortConfig, ByteTrackConfig, check_reid_model
+from .config import StrongSortConfig, ByteTrackConfig, check_reid_model, check_gmc_method
 from .engine import TrackerEngine, ByteTrackEngine
 from .lib import MAX_DETS, FEAT_DIM
 
@@ -79,7 +79,8 @@ class BYTETracker:
        returns float32 [M,8]: x1,y1,x2,y2,track_id,class_id,conf,det_idx for every activated tracked track (det_idx = row of
        `dets` matched this frame, always >= 0).  cfg.kalman = "xyah": ByteTrack; "xywh": BoT-SORT without ReID.
        camera_motion=True (xywh only): BoT-SORT's GMC (§1b) with the ECC warp between the previous frame and this one,
-       estimated on the device; `update(dets, frame)` then needs the frame.
+       estimated on the device; `update(dets, frame)` then needs the frame.  gmc_method="sparseOptFlow": the sparse-optical-flow
+       estimator (§1f, Ultralytics' botsort.yaml default) instead of ECC; frame sides >= 64.
        cfg.with_reid=True (xywh only): BoT-SORT's ReID branch (§1c).  `update(dets, frame, features)` takes the rows' raw
        features [N,k] (k <= 512, zero-padded to 512: the §1d features of a `model: auto` detector have k = min(C_l)), or cuts
        the crops from `frame` and runs OSNet-x0.25 (reid_weights, loaded as StrongSORT loads them; fp16 selects half
@@ -89,9 +90,10 @@ class BYTETracker:
 
     def __init__(self, cfg: Optional[ByteTrackConfig] = None, device: int = 0, camera_motion: bool = False,
                  reid_weights: Optional[str] = None, fp16: bool = False, random_init_ok: bool = False, reid_seed: int = 1,
-                 reid_model: str = "osnet"):
+                 reid_model: str = "osnet", gmc_method: str = "ecc"):
         self.cfg = cfg or ByteTrackConfig()
         self.reid_model = check_reid_model(reid_model, self.cfg.with_reid, reid_weights)
+        self.gmc_method = check_gmc_method(gmc_method, camera_motion, "botsort" if self.cfg.kalman == "xywh" else "bytetrack")
         if camera_motion and self.cfg.kalman != "xywh":
             raise ValueError("camera_motion needs the xywh (BoT-SORT) filter: ByteTrack has no GMC")
         self.eng = ByteTrackEngine(self.cfg, 1, device)
@@ -124,7 +126,7 @@ class BYTETracker:
         if self.camera_motion:
             if frame_t is None:
                 raise ValueError("camera_motion=True: update(dets, frame) needs the BGR frame")
-            self.eng.cmc_estimate(frame_t[None], 1, self._warps)
+            self.eng.estimate_warps(self.gmc_method, frame_t[None], 1, self._warps)
             self.eng.set_cmc(self._warps)
         self._dets[0, :n].copy_(dets, non_blocking=True)
         self._n.fill_(n)

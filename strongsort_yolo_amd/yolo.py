@@ -18,7 +18,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .config import DetectConfig, StrongSortConfig, byte_config, check_reid_model
+from .config import DetectConfig, StrongSortConfig, byte_config, check_reid_model, check_gmc_method
 
 COCO_NAMES = ("person bicycle car motorcycle airplane bus train truck boat traffic_light fire_hydrant stop_sign "
               "parking_meter bench bird cat dog horse sheep cow elephant bear zebra giraffe backpack umbrella handbag tie "
@@ -290,7 +290,7 @@ class YOLO:
     def __init__(self, weights: str = "yolov8n.pt", seed: int = 0, random_init_ok: bool = False, reid_batch: int = 128,
                  camera_motion: bool = False, reid_weights: Optional[str] = None, reid_fp32: bool = True, half: bool = True,
                  device_masks: bool = False, tracker_type: str = "strongsort", with_reid: bool = False, reid_model: str = "osnet",
-                 with_pose: bool = False):
+                 with_pose: bool = False, gmc_method: str = "ecc"):
         """reid_fp32 (default since round 6): ReID crops + OSNet-x0.25 in fp32 on the fp32 kernels — appearance distances within 1e-4 of a CPU fp32
         network, which f16 activations miss by 330x (reid_fp32=False: the f16 throughput mode, ~1.2x the per-frame rate, 1.7x the stream rate).
         half=False: the DETECTOR in fp32 as well (the reference's own precision: it passes no half=, yolo_multi_model.py:41) on the
@@ -305,6 +305,9 @@ class YOLO:
         camera_motion: ECC camera-motion warps estimated on the device beside the detector (N4). StrongSORT moves its track
         boxes by them (D-18); "botsort" applies them as BoT-SORT's GMC to every track's Kalman mean and covariance
         (docs/BYTETRACK.md §1b) in track() and track_stream(). "bytetrack" has no GMC: a ValueError.
+        gmc_method (camera_motion with "botsort" only, else a ValueError): "ecc" (default, as above) or "sparseOptFlow" — the
+        estimator Ultralytics' botsort.yaml names: corners on the half-size grey frame, pyramidal Lucas-Kanade, a RANSAC similarity
+        fit, all on the device (docs/BYTETRACK.md §1f); frame sides >= 64.
         with_reid ("botsort" only, else a ValueError): BoT-SORT's ReID branch (docs/BYTETRACK.md §1c) — OSNet-x0.25 features of
         every tracked row (reid_weights, reid_fp32 and half as for StrongSORT) add an appearance term to the IoU association.
         reid_model (with_reid only): "osnet" (default, as above) or "auto" — Ultralytics' `model: auto` (docs/BYTETRACK.md §1d): the
@@ -321,6 +324,7 @@ class YOLO:
         self._byte = tracker_type != "strongsort"
         if tracker_type == "bytetrack" and camera_motion:
             raise ValueError("camera_motion needs tracker_type 'strongsort' or 'botsort' (ByteTrack has no GMC, G-05)")
+        self.gmc_method = check_gmc_method(gmc_method, camera_motion, tracker_type)
         self._conf_track = None                   # BYTE: the NMS threshold of the tracking pipelines (set while track / track_stream build)
         self.weights = weights
         self.reid_weights = reid_weights          # OSNet-x0.25 state_dict; same policy as the detector's (raise unless random init is asked for)
@@ -341,6 +345,8 @@ class YOLO:
         # test / bench hooks (synthetic head tensors, no weights exist offline): extra pipeline keywords and a callable
         # fill(buffers, virtual_stream, frame_index) that writes pred_in / anchor_gt / gt_feats before a frame runs
         self._pipe_kw = {"cmc": True} if camera_motion else {}    # N4: ECC camera-motion compensation (off by default)
+        if gmc_method != "ecc":
+            self._pipe_kw["gmc_method"] = gmc_method
         if reid_fp32 or not half:                                  # OSNet in fp32 (pipeline.FramePipeline reid_half): float distances within 1e-4
             self._pipe_kw["reid_half"] = False
         if not half:
