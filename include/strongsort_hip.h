@@ -602,6 +602,24 @@ int ss_op32_v8_decode(void* stream, const void* const* d_box, const void* const*
 int ss_op32_sppf_pools(void* stream, const void* d_x, int xs, void* d_out, int N, int H, int W, int C);
 int ss_op32_upcat(void* stream, const void* d_lo, int ls, int Cl, const void* d_hi, int hs, int Ch, void* d_out, int N, int H, int W, int lo_first);
 
+/* ---- baseline JPEG frames decoded on the device (csrc/ss_jpeg.hip, docs/JPEG.md) ---------------- */
+/* Accepted: SOF0, 8-bit, 1 component or 3 (YCbCr), luma sampling 1x1 / 2x1 / 2x2 with 1x1 chroma, one interleaved scan, 8-bit
+ * quantisation tables, any Huffman tables, restart intervals; sides 1 .. 8192.  Everything else returns SS_ERR_INVALID with the
+ * cause in ss_last_error().  The pixels equal libjpeg-turbo's defaults (JDCT_ISLOW, fancy upsampling) bit for bit.
+ * ss_jpeg_probe: host only (no GPU, no context; the message of a refusal is in ss_last_error(NULL)): the frame's size, its
+ * component count and the luma sampling factors. */
+int ss_jpeg_probe(const unsigned char* data, size_t size, int* width, int* height, int* components, int* h_samp, int* v_samp);
+/* Host only: the quantised coefficients as dense natural-order int16 blocks, component after component, each component's blocks
+ * in raster order over its whole-MCU grid (coef_cap: capacity in values), and the four quantisation tables quant [4][64] in
+ * natural order (absent tables zero).  For tests of the entropy stage. */
+int ss_jpeg_coefficients(const unsigned char* data, size_t size, short* coef, size_t coef_cap, unsigned short* quant);
+/* n (1 .. 64) encoded frames of one size height x width -> d_out + i * out_frame_stride, HWC uint8, BGR (rgb = 0) or RGB.  The
+ * entropy stage runs inside the call on `threads` (1 .. 16) host threads; the coefficients leave in one asynchronous copy and two
+ * launches on hip_stream do the rest.  The caller's buffers may be reused on return.  When a frame is refused nothing is launched
+ * and the message names its index.  Not capturable (host work): never call it while hip_stream is capturing. */
+int ss_jpeg_decode_batch(ss_ctx* ctx, void* hip_stream, const unsigned char* const* data, const size_t* sizes, int n, int height,
+                         int width, void* d_out, long long out_frame_stride, int rgb, int threads);
+
 /* ---- profiling support ----------------------------------------------------------------------- */
 /* Mean duration (ms) of the association (cosine gallery) kernel over the launches since the last
  * call, measured with HIP events on the context stream; also returns the launch count. */

@@ -5,7 +5,8 @@ What is kept is the per-stream loop (:244-339), the labels file (:34-39, :165-16
  — and, with `--save`, the annotated output (:58-162, :311-331): the drawing runs as an overlay kernel
 on the device (overlay.py, N2) on the frame that is ALREADY there (the throughput path keeps a device copy of every frame
 of a group: one upload and one download per frame) and the frames go to a sink (N3).  Frame sources (N3): `synthetic[:N]`,
-a `.npy` stack [T,H,W,3], a directory of images (Pillow) and — when OpenCV is importable — a video file or a camera index
+a `.npy` stack [T,H,W,3], a directory of images (Pillow; with `--device-decode` a JPEG directory or a raw `.mjpeg` file stays encoded and is decoded on the
+device, docs/JPEG.md) and — when OpenCV is importable — a video file or a camera index
 through `cv2.VideoCapture` (:252); sinks: `.npy`, raw BGR24, a PNG directory and — with OpenCV — `cv2.VideoWriter` (:256-260).
 OpenCV is optional: this environment has none, there the video branches raise a clear error (no GUI: imshow is out of scope).
 """
@@ -21,8 +22,66 @@ import numpy as np
 
 
 # ---- frame sources (N3) --------------------------------------------------------------------------------
-def frame_source(spec: str, limit: Optional[int] = None) -> Iterator[np.ndarray]:
-    if spec.startswith("synthetic"):
+JPEG_EXT, MJPEG_EXT = (".jpg", ".jpeg"), (".mjpeg", ".mjpg")
+
+
+def _image_names(spec: str):
+    return sorted(f for f in os.listdir(spec) if f.lower().endswith((".jpg", ".jpeg", ".png", ".bmp")))
+
+
+def _pil():
+    """Pillow's Image module, if this interpreter has it."""
+    try:
+        from PIL import Image
+        return Image
+    except ImportError:
+        return None
+
+
+def encoded_source_error(spec: str) -> Optional[str]:
+    """Why `spec` cannot feed --device-decode (None: it can): a directory of .jpg / .jpeg files or a raw .mjpeg / .mjpg file whose
+    first frame the device decoder accepts (baseline JPEG, docs/JPEG.md)."""
+    from .jpeg import probe, split_mjpeg
+    if os.path.isdir(spec):
+        names = _image_names(spec)
+        if not names or not all(f.lower().endswith(JPEG_EXT) for f in names):
+            return f"--device-decode: '{spec}' must hold .jpg / .jpeg images only"
+        first = os.path.join(spec, names[0])
+        try:
+            with open(first, "rb") as f:
+                probe(f.read())
+        except ValueError as e:
+            return f"--device-decode: '{first}': {e}"
+        return None
+    if spec.lower().endswith(MJPEG_EXT) and os.path.isfile(spec):
+        try:
+            if next(split_mjpeg(spec), None) is None:
+                return f"--device-decode: '{spec}' holds no JPEG frame"
+        except ValueError as e:
+            return f"--device-decode: '{spec}': {e}"
+        return None
+    return f"--device-decode: '{spec}' is neither a directory of .jpg / .jpeg images nor a .mjpeg / .mjpg file"
+
+
+def frame_source(spec: str, limit: Optional[int] = None, encoded: bool = False) -> Iterator[np.ndarray]:
+    """BGR uint8 frames of a source; encoded=True (JPEG directories and raw MJPEG files only): jpeg.EncodedFrames, still encoded."""
+    if encoded:
+        from .jpeg import EncodedFrame, split_mjpeg
+        why = encoded_source_error(spec)
+        if why:
+            raise ValueError(why)
+        if os.path.isdir(spec):
+            for k, f in enumerate(_image_names(spec)):
+                if limit is not None and k >= limit:
+                    break
+                with open(os.path.join(spec, f), "rb") as fh:
+                    yield EncodedFrame(fh.read())
+        else:
+            for k, fr in enumerate(split_mjpeg(spec)):
+                if limit is not None and k >= limit:
+                    break
+                yield fr
+    elif spec.startswith("synthetic"):
         from .synth import make_stream
         n = int(spec.split(":")[1]) if ":" in spec else 100
         st = make_stream(0, 640, 480, 8)
@@ -34,11 +93,19 @@ def frame_source(spec: str, limit: Optional[int] = None) -> Iterator[np.ndarray]
             yield np.ascontiguousarray(arr[k])
     elif os.path.isdir(spec):
         from PIL import Image
-        names = sorted(f for f in os.listdir(spec) if f.lower().endswith((".jpg", ".jpeg", ".png", ".bmp")))
-        for k, f in enumerate(names):
+        for k, f in enumerate(_image_names(spec)):
             if limit is not None and k >= limit:
                 break
             yield np.asarray(Image.open(os.path.join(spec, f)).convert("RGB"))[:, :, ::-1].copy()   # BGR like cv2
+    elif spec.lower().endswith(MJPEG_EXT) and os.path.isfile(spec) and _pil() is not None:
+        import io
+        from .jpeg import split_bytes
+        with open(spec, "rb") as fh:
+            buf = fh.read()
+        for k, seg in enumerate(split_bytes(buf)):
+            if limit is not None and k >= limit:
+                break
+            yield np.asarray(_pil().open(io.BytesIO(seg)).convert("RGB"))[:, :, ::-1].copy()
     else:
         yield from _video_source(spec, limit)
 
@@ -206,7 +273,7 @@ def process_video(args: dict, model=None) -> dict:
     counter = ClassCounter(model.names)
     frames, t0, fps = 0, time.time(), 0.0
     batch = int(args.get("batch", 16))
-    src = frame_source(str(source), args.get("limit"))
+    src = frame_source(str(source), args.get("limit"), encoded=bool(args.get("device_decode", False)))
     sink = FrameSink(args["save"]) if args.get("save") else None       # annotated output (N2 + N3), off by default
     overlay, fps_str = None, ""
 
@@ -285,6 +352,9 @@ def main(argv=None):
     p.add_argument("--save", default=None, help="write annotated frames: stack.npy | video.bgr (raw BGR24 + .json) | directory of PNGs | video.mp4 (needs OpenCV)")
     p.add_argument("--batch", type=int, default=16, help="frames per group on the throughput path (1: per-frame model.track calls as in the reference)")
     p.add_argument("--random-init", action="store_true", help="run seeded random-init networks when the weights file is missing")
+    p.add_argument("--device-decode", action="store_true",
+                   help="JPEG directories and raw .mjpeg files: decode baseline JPEG on the device (Huffman on host threads, the rest in "
+                        "csrc/ss_jpeg.hip; same pixels as Pillow, docs/JPEG.md); needs --track and --batch > 1")
     p.add_argument("--device-masks", action="store_true", help="segmentation models: assemble masks and trace their outlines on the device (csrc/ss_mask.hip) instead of on the host")
     a = p.parse_args(argv)
     if a.camera_motion and a.tracker == "bytetrack":
@@ -305,7 +375,14 @@ def main(argv=None):
         p.error("--reid-model is a model for BoT-SORT's ReID branch: it needs --with-reid")
     if a.reid_model == "auto" and a.reid_weights:
         p.error("--reid-model auto reads the detector's own features: --reid-weights does not apply")
-    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method,
+    if a.device_decode:
+        if not a.track or a.batch <= 1:
+            p.error("--device-decode feeds the grouped tracking path: it needs --track and --batch > 1")
+        for src in a.source:
+            why = encoded_source_error(src)
+            if why:
+                p.error(why)
+    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "device_decode": a.device_decode,
              "save": (a.save if len(a.source) == 1 else f"{os.path.splitext(a.save)[0]}_{i}{os.path.splitext(a.save)[1]}") if a.save else None}
             for i, s in enumerate(a.source)]
     import torch

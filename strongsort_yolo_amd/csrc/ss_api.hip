@@ -49,6 +49,12 @@ void ss_launch_byte_group_kpts(const SSByteDev&, int, const float*, const int*, 
 void ss_launch_native_feats(int, int, const void* const*, const long long*, const long long*, const long long*, const int*, const int*,
                             const int*, int, const int*, long long, const int*, float*, hipStream_t);
 
+struct SSJpeg;                          // ss_jpeg.hip
+int  ss_jpeg_probe_impl(const unsigned char*, size_t, int*, int*, int*, int*, int*, std::string&);
+int  ss_jpeg_coefficients_impl(const unsigned char*, size_t, short*, size_t, unsigned short*, std::string&);
+int  ss_jpeg_decode_impl(SSJpeg**, hipStream_t, const unsigned char* const*, const size_t*, int, int, int, void*, long long, int, int, std::string&);
+void ss_jpeg_free(SSJpeg*);
+
 static std::string g_last_error;
 
 struct ss_ctx {
@@ -111,6 +117,7 @@ struct ss_ctx {
     // the BYTE tracker family (ss_byte_create), NULL until attached
     struct Byte { SSByteDev dev; ss_byte_config cfg; std::vector<void*> allocs; };
     Byte* byte = nullptr;
+    SSJpeg* jpeg = nullptr;     // ss_jpeg_decode_batch's staging areas and planes, made by its first call
 };
 
 static int fail(ss_ctx* c, int code, const std::string& msg)
@@ -264,6 +271,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     for (auto& st : c->stage) { if (st.ev) (void)hipEventDestroy(st.ev); if (st.p) (void)hipHostFree(st.p); }
     for (auto& st : c->bstage) { if (st.ev) (void)hipEventDestroy(st.ev); if (st.p) (void)hipHostFree(st.p); }
     if (c->back.p) (void)hipHostFree(c->back.p);
+    ss_jpeg_free(c->jpeg);
     delete c;
 }
 
@@ -342,6 +350,36 @@ extern "C" int ss_upload_batch(ss_ctx* c, void* hip_stream, void* d_dst, const v
     st.busy = true;
     c->bstage_next ^= 1;
     return SS_OK;
+}
+
+// ---- N3 frame source: baseline JPEG (ss_jpeg.hip) ----------------------------------------------------------
+extern "C" int ss_jpeg_probe(const unsigned char* data, size_t size, int* width, int* height, int* components, int* h_samp, int* v_samp)
+{
+    if (!data || !size || !width || !height || !components || !h_samp || !v_samp) return fail(nullptr, SS_ERR_INVALID, "ss_jpeg_probe: null argument");
+    std::string err;
+    const int rc = ss_jpeg_probe_impl(data, size, width, height, components, h_samp, v_samp, err);
+    return rc == SS_OK ? rc : fail(nullptr, rc, "ss_jpeg_probe: " + err);
+}
+
+extern "C" int ss_jpeg_coefficients(const unsigned char* data, size_t size, short* coef, size_t coef_cap, unsigned short* quant)
+{
+    if (!data || !size || !coef || !quant) return fail(nullptr, SS_ERR_INVALID, "ss_jpeg_coefficients: null argument");
+    std::string err;
+    const int rc = ss_jpeg_coefficients_impl(data, size, coef, coef_cap, quant, err);
+    return rc == SS_OK ? rc : fail(nullptr, rc, "ss_jpeg_coefficients: " + err);
+}
+
+extern "C" int ss_jpeg_decode_batch(ss_ctx* c, void* hip_stream, const unsigned char* const* data, const size_t* sizes, int n, int height,
+                                    int width, void* d_out, long long out_frame_stride, int rgb, int threads)
+{
+    if (!c || !data || !sizes || !d_out) return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch: null argument");
+    if (n < 1 || n > 64 || threads < 1 || threads > 16 || height < 1 || height > 8192 || width < 1 || width > 8192 || (rgb != 0 && rgb != 1) ||
+        out_frame_stride < (long long)height * width * 3)
+        return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch: 1 <= n <= 64, 1 <= threads <= 16, sides 1 .. 8192, rgb 0 / 1, out_frame_stride >= height * width * 3");
+    for (int i = 0; i < n; ++i) if (!data[i] || !sizes[i]) return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch: image " + std::to_string(i) + ": no data");
+    std::string err;
+    const int rc = ss_jpeg_decode_impl(&c->jpeg, (hipStream_t)hip_stream, data, sizes, n, height, width, d_out, out_frame_stride, rgb, threads, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
 }
 
 // Device -> host through a pinned staging buffer; synchronous (returns when h_dst holds the bytes).

@@ -1,0 +1,620 @@
+// ss_jpeg.hip — baseline JPEG frames decoded into the pipeline's frame buffer (docs/JPEG.md).
+//
+// The host does the serial part only: headers, Huffman tables and the entropy-coded scan, whole images dealt out to the call's
+// host threads.  What leaves the host is a SPARSE coefficient stream (a 32-bit offset per block, a 32-bit entry per non-zero
+// coefficient), packed into a write-combined staging area and sent in one asynchronous copy.  Two kernels do the rest for all
+// images of the call at once:
+//   k_jpeg_idct    eight lanes per 8x8 block: expand the block's entries into LDS (dequantised), ISLOW pass 1 with lane = column,
+//                  pass 2 with lane = row, range limit, 8 bytes per lane into the component planes
+//   k_jpeg_pixels  a lane makes 4 consecutive pixels of the flat HWC image (12 bytes = 3 dwords): fancy chroma upsampling from
+//                  the planes (neighbours across block borders included), YCbCr -> BGR / RGB, the store
+// Every value is an integer; the results equal libjpeg-turbo's defaults (JDCT_ISLOW, fancy upsampling) bit for bit.
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+#include "ss_common.h"
+
+#define JPEG_HDR 160                    // dwords of an image's header in the stream (see docs/JPEG.md "staging layout")
+#define JPEG_WS_PITCH 72                // LDS dwords per block, rows of 9 (8 + 1 pad): the 32 lanes of a ds_read_b32 / ds_write_b32 group (4 blocks)
+                                        // hit 32 different banks in pass 1 (lane = column) and in pass 2 (lane = row)
+
+static const uint8_t kZigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                                    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// ---- host: headers ---------------------------------------------------------------------------------------------------------
+struct JHuff {
+    bool present = false;
+    uint16_t fast[512];                 // 9 leading bits -> (length << 8) | symbol, 0: the code is longer (or does not exist)
+    int mincode[17], maxcode[17], valptr[17];
+    uint8_t vals[256];
+};
+
+struct JInfo {
+    int width = 0, height = 0, ncomp = 0;
+    int cid[3], h[3], v[3], tq[3], td[3], ta[3];
+    uint16_t quant[4][64];              // natural order
+    bool have_q[4] = {false, false, false, false};
+    JHuff dc[4], ac[4];
+    int ri = 0;
+    size_t scan = 0;                    // first byte of the entropy-coded data
+    int mcux = 0, mcuy = 0;
+};
+
+static bool jfail(std::string& err, const std::string& msg) { err = msg; return false; }
+
+static bool build_huff(JHuff& t, const uint8_t* counts, const uint8_t* syms, int tot)
+{
+    memset(t.fast, 0, sizeof t.fast);
+    memcpy(t.vals, syms, tot);
+    int code = 0, k = 0;
+    for (int ln = 1; ln <= 16; ++ln) {
+        t.valptr[ln] = k;
+        t.mincode[ln] = code;
+        if (counts[ln - 1] > (1 << ln) - code) return false;    // more codes of this length than the code space has left
+        for (int i = 0; i < counts[ln - 1]; ++i, ++code, ++k)
+            if (ln <= 9)
+                for (int f = 0; f < (1 << (9 - ln)); ++f) t.fast[(code << (9 - ln)) | f] = (uint16_t)((ln << 8) | syms[k]);
+        t.maxcode[ln] = counts[ln - 1] ? code - 1 : -1;
+        code <<= 1;
+    }
+    t.present = true;
+    return true;
+}
+
+static bool parse_headers(const uint8_t* d, size_t n, JInfo& J, std::string& err)
+{
+    if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return jfail(err, "no SOI marker");
+    size_t p = 2;
+    bool sof = false, jfif = false;
+    int adobe = -1;
+    const uint8_t* seg = nullptr;
+    size_t L = 0;
+    for (;;) {
+        while (p < n && d[p] != 0xFF) ++p;
+        while (p < n && d[p] == 0xFF) ++p;
+        if (p >= n) return jfail(err, "no scan");
+        const int m = d[p++];
+        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
+        if (m == 0xD9) return jfail(err, "no scan");
+        if (p + 2 > n) return jfail(err, "truncated header");
+        L = ((size_t)d[p] << 8) | d[p + 1];
+        if (L < 2 || p + L > n) return jfail(err, "truncated header");
+        seg = d + p + 2;
+        const size_t sl = L - 2;
+        if (m == 0xC0) {
+            if (sof) return jfail(err, "two frame headers");
+            if (sl < 6 || sl != 6 + 3 * (size_t)seg[5]) return jfail(err, "bad frame header");
+            if (seg[0] != 8) return jfail(err, "12-bit samples");
+            J.height = (seg[1] << 8) | seg[2];
+            J.width = (seg[3] << 8) | seg[4];
+            J.ncomp = seg[5];
+            for (int i = 0; i < J.ncomp && i < 3; ++i) { J.cid[i] = seg[6 + 3 * i]; J.h[i] = seg[7 + 3 * i] >> 4; J.v[i] = seg[7 + 3 * i] & 15; J.tq[i] = seg[8 + 3 * i]; }
+            sof = true;
+        } else if (m >= 0xC1 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+            const char* kind = m == 0xC1 ? "extended sequential" : m == 0xC2 ? "progressive" : m == 0xC3 ? "lossless" : "arithmetic or differential";
+            return jfail(err, std::string(kind) + " JPEG (SOF" + std::to_string(m - 0xC0) + ")");
+        } else if (m == 0xCC) {
+            return jfail(err, "arithmetic coding");
+        } else if (m == 0xDB) {
+            for (size_t q = 0; q < sl; q += 65) {
+                const int pq = seg[q] >> 4, tq = seg[q] & 15;
+                if (pq != 0) return jfail(err, "16-bit quantisation table");
+                if (tq > 3 || q + 65 > sl) return jfail(err, "bad quantisation table");
+                for (int k = 0; k < 64; ++k) J.quant[tq][kZigzag[k]] = seg[q + 1 + k];
+                J.have_q[tq] = true;
+            }
+        } else if (m == 0xC4) {
+            size_t q = 0;
+            while (q < sl) {
+                if (q + 17 > sl) return jfail(err, "bad Huffman table");
+                const int tc = seg[q] >> 4, th = seg[q] & 15;
+                int tot = 0;
+                for (int i = 0; i < 16; ++i) tot += seg[q + 1 + i];
+                if (tc > 1 || th > 3 || tot > 256 || q + 17 + tot > sl) return jfail(err, "bad Huffman table");
+                if (!build_huff(tc ? J.ac[th] : J.dc[th], seg + q + 1, seg + q + 17, tot)) return jfail(err, "bad Huffman table");
+                q += 17 + tot;
+            }
+        } else if (m == 0xDD) {
+            if (sl != 2) return jfail(err, "bad restart interval");
+            J.ri = (seg[0] << 8) | seg[1];
+        } else if (m == 0xE0 && sl >= 5 && !memcmp(seg, "JFIF\0", 5)) {
+            jfif = true;
+        } else if (m == 0xEE && sl >= 12 && !memcmp(seg, "Adobe", 5)) {
+            adobe = seg[11];
+        } else if (m == 0xDA) {
+            if (!sof) return jfail(err, "scan before the frame header");
+            break;
+        }
+        p += L;
+    }
+    const size_t sl = L - 2;
+    if (J.height < 1 || J.height > 8192 || J.width < 1 || J.width > 8192) return jfail(err, "sides must be 1 ... 8192");
+    if (J.ncomp != 1 && J.ncomp != 3) return jfail(err, std::to_string(J.ncomp) + " components (1 or 3 are decoded)");
+    if (adobe == 0 && J.ncomp == 3) return jfail(err, "Adobe marker with transform 0 (RGB)");
+    if (J.ncomp == 3 && !jfif && adobe < 0 && J.cid[0] == 'R' && J.cid[1] == 'G' && J.cid[2] == 'B') return jfail(err, "component ids R, G, B (RGB)");
+    if (J.ncomp == 1) {
+        J.h[0] = J.v[0] = 1;                                   // a one-component scan is not interleaved: the factors do not matter
+    } else {
+        const bool luma = (J.h[0] == 1 && J.v[0] == 1) || (J.h[0] == 2 && J.v[0] == 1) || (J.h[0] == 2 && J.v[0] == 2);
+        if (!luma || J.h[1] != 1 || J.v[1] != 1 || J.h[2] != 1 || J.v[2] != 1) {
+            std::string s = "sampling factors";
+            for (int i = 0; i < 3; ++i) s += " " + std::to_string(J.h[i]) + "x" + std::to_string(J.v[i]);
+            return jfail(err, s + " (4:4:4, 4:2:2 and 4:2:0 are decoded)");
+        }
+    }
+    if (sl < 1 || seg[0] != J.ncomp || sl != 4 + 2 * (size_t)seg[0]) return jfail(err, "several scans");
+    if (seg[sl - 3] != 0 || seg[sl - 2] != 63 || seg[sl - 1] != 0) return jfail(err, "scan header is not a baseline one (Ss 0, Se 63, Ah / Al 0)");
+    for (int i = 0; i < J.ncomp; ++i) {
+        if (seg[1 + 2 * i] != J.cid[i]) return jfail(err, "scan components out of order");
+        J.td[i] = seg[2 + 2 * i] >> 4;
+        J.ta[i] = seg[2 + 2 * i] & 15;
+    }
+    for (int i = 0; i < J.ncomp; ++i) {
+        if (J.tq[i] > 3 || !J.have_q[J.tq[i]]) return jfail(err, "missing quantisation table " + std::to_string(J.tq[i]));
+        if (J.td[i] > 3 || !J.dc[J.td[i]].present) return jfail(err, "missing DC Huffman table " + std::to_string(J.td[i]));
+        if (J.ta[i] > 3 || !J.ac[J.ta[i]].present) return jfail(err, "missing AC Huffman table " + std::to_string(J.ta[i]));
+    }
+    J.scan = p + L;
+    J.mcux = (J.width + 8 * J.h[0] - 1) / (8 * J.h[0]);
+    J.mcuy = (J.height + 8 * J.v[0] - 1) / (8 * J.v[0]);
+    return true;
+}
+
+// ---- host: the entropy-coded scan ------------------------------------------------------------------------------------------
+// Bits are held left-aligned in a 64-bit word.  At a marker (or the end of the data) the reader stops advancing and supplies zero
+// bits, counted in `fake`: they are always the last bits of the word, so real data has run out exactly when cnt < fake.
+struct JBits {
+    const uint8_t* d;
+    size_t pos, n;
+    uint64_t buf = 0;
+    int cnt = 0, fake = 0;
+    bool marker = false;
+    inline void fill()
+    {
+        if (cnt <= 32 && !marker && pos + 8 <= n) {              // eight bytes without an FF: whole bytes straight into the word
+            uint64_t w;
+            memcpy(&w, d + pos, 8);
+            const uint64_t x = ~w;
+            if (!((x - 0x0101010101010101ull) & ~x & 0x8080808080808080ull)) {
+                const int k = (64 - cnt) >> 3;
+                buf |= (__builtin_bswap64(w) >> cnt) & ~(((uint64_t)1 << (64 - cnt - 8 * k)) - 1);
+                pos += k;
+                cnt += 8 * k;
+                return;
+            }
+        }
+        while (cnt <= 56) {
+            unsigned x = 0;
+            if (!marker && pos < n) {
+                x = d[pos];
+                if (x != 0xFF) ++pos;
+                else if (pos + 1 < n && d[pos + 1] == 0) pos += 2;
+                else { marker = true; x = 0; }
+            } else marker = true;
+            if (marker) fake += 8;
+            buf |= (uint64_t)x << (56 - cnt);
+            cnt += 8;
+        }
+    }
+    inline unsigned peek(int k) const { return (unsigned)(buf >> (64 - k)); }
+    inline void skip(int k) { buf <<= k; cnt -= k; }
+};
+
+static inline int huff_sym(JBits& b, const JHuff& t)            // after fill(); -1: no such code
+{
+    const unsigned f = t.fast[b.peek(9)];
+    if (f) { b.skip(f >> 8); return f & 255; }
+    for (int ln = 10; ln <= 16; ++ln) {
+        const int code = (int)b.peek(ln);
+        if (t.maxcode[ln] >= 0 && code <= t.maxcode[ln] && code >= t.mincode[ln]) { b.skip(ln); return t.vals[t.valptr[ln] + code - t.mincode[ln]]; }
+    }
+    return -1;
+}
+
+static inline int receive_extend(JBits& b, int s)               // 1 <= s <= 15
+{
+    const int v = (int)b.peek(s);
+    b.skip(s);
+    return v >= (1 << (s - 1)) ? v : v - (1 << s) + 1;
+}
+
+// Sink: begin(ci, by, bx) opens the next block in scan order, coef(k_natural, value) adds one of its non-zero coefficients.
+template <class Sink>
+static bool decode_scan(const uint8_t* d, size_t n, const JInfo& J, Sink& sink, std::string& err)
+{
+    JBits b{d, J.scan, n};
+    int pred[3] = {0, 0, 0};
+    const int nm = J.mcux * J.mcuy;
+    int rst = 0;
+    for (int m = 0; m < nm; ++m) {
+        if (J.ri && m && m % J.ri == 0) {
+            b.fill();
+            if (b.cnt - b.fake >= 8 || !b.marker) return jfail(err, "bad restart marker");
+            size_t q = b.pos;
+            while (q < n && d[q] == 0xFF) ++q;
+            if (q >= n || q == b.pos || d[q] != 0xD0 + (rst & 7)) return jfail(err, "bad restart marker");
+            ++rst;
+            b = JBits{d, q + 1, n};
+            pred[0] = pred[1] = pred[2] = 0;
+        }
+        const int my = m / J.mcux, mx = m % J.mcux;
+        for (int ci = 0; ci < J.ncomp; ++ci) {
+            const JHuff &dc = J.dc[J.td[ci]], &ac = J.ac[J.ta[ci]];
+            for (int by = 0; by < J.v[ci]; ++by)
+                for (int bx = 0; bx < J.h[ci]; ++bx) {
+                    sink.begin(ci, my * J.v[ci] + by, mx * J.h[ci] + bx);
+                    b.fill();
+                    int s = huff_sym(b, dc);
+                    if (s < 0) return jfail(err, b.cnt - b.fake < 16 ? "data ends before the last MCU" : "Huffman code that does not exist");
+                    if (s > 15) return jfail(err, "bad DC category");
+                    if (s) pred[ci] += receive_extend(b, s);
+                    pred[ci] = (int16_t)pred[ci];
+                    if (pred[ci]) sink.coef(0, pred[ci]);
+                    for (int k = 1; k < 64;) {
+                        b.fill();
+                        const int rs = huff_sym(b, ac);
+                        if (rs < 0) return jfail(err, b.cnt - b.fake < 16 ? "data ends before the last MCU" : "Huffman code that does not exist");
+                        const int r = rs >> 4;
+                        s = rs & 15;
+                        if (!s) {
+                            if (r != 15) break;
+                            k += 16;
+                            continue;
+                        }
+                        k += r;
+                        if (k > 63) return jfail(err, "coefficient index beyond 63");
+                        const int v = receive_extend(b, s);
+                        if (v) sink.coef(kZigzag[k], v);
+                        ++k;
+                    }
+                    if (b.cnt < b.fake) return jfail(err, "data ends before the last MCU");
+                }
+        }
+    }
+    return true;
+}
+
+int ss_jpeg_probe_impl(const unsigned char* data, size_t size, int* width, int* height, int* components, int* h_samp, int* v_samp, std::string& err)
+{
+    JInfo* J = new (std::nothrow) JInfo();
+    if (!J) { err = "out of memory"; return SS_ERR_INVALID; }
+    const bool ok = parse_headers(data, size, *J, err);
+    if (ok) { *width = J->width; *height = J->height; *components = J->ncomp; *h_samp = J->h[0]; *v_samp = J->v[0]; }
+    delete J;
+    return ok ? SS_OK : SS_ERR_INVALID;
+}
+
+struct DenseSink {
+    short* coef_out;
+    size_t base[3];
+    int bw[3];
+    short* cur = nullptr;
+    void begin(int ci, int by, int bx) { cur = coef_out + base[ci] + ((size_t)by * bw[ci] + bx) * 64; }
+    void coef(int k, int v) { cur[k] = (short)v; }
+};
+
+int ss_jpeg_coefficients_impl(const unsigned char* data, size_t size, short* coef, size_t coef_cap, unsigned short* quant, std::string& err)
+{
+    JInfo* J = new (std::nothrow) JInfo();
+    if (!J) { err = "out of memory"; return SS_ERR_INVALID; }
+    int rc = SS_ERR_INVALID;
+    if (parse_headers(data, size, *J, err)) {
+        DenseSink sink{coef, {0, 0, 0}, {0, 0, 0}};
+        size_t tot = 0;
+        for (int c = 0; c < J->ncomp; ++c) { sink.base[c] = tot; sink.bw[c] = J->mcux * J->h[c]; tot += (size_t)J->mcux * J->h[c] * J->mcuy * J->v[c] * 64; }
+        if (tot > coef_cap) err = "coefficient buffer too small: " + std::to_string(tot) + " values needed";
+        else {
+            memset(coef, 0, tot * sizeof(short));
+            memset(quant, 0, 4 * 64 * sizeof(unsigned short));
+            for (int t = 0; t < 4; ++t) if (J->have_q[t]) memcpy(quant + 64 * t, J->quant[t], 64 * sizeof(unsigned short));
+            if (decode_scan(data, size, *J, sink, err)) rc = SS_OK;
+        }
+    }
+    delete J;
+    return rc;
+}
+
+// ---- device ----------------------------------------------------------------------------------------------------------------
+// The stream (dwords; every image's header first, then per image its block table and its entries):
+//   header i at JPEG_HDR * i:  [0] components  [1] h  [2] v (luma factors)  [3] MCUs per row  [4] blocks  [5] block table (dword index)
+//                              [6] entries (dword index)  [8 + c] quantisation table of component c  [11 + c] plane offset (bytes)
+//                              [14 + c] plane pitch  [32 .. 160) the four quantisation tables, uint16 [4][64], natural order
+//   block table:  blocks + 1 dwords in SCAN order; block b's entries are entries[table[b] .. table[b + 1])
+//   entry:        (natural-order index << 16) | (uint16) value
+__device__ __forceinline__ void jpeg_pass(uint32_t (&x)[8], int s)
+{
+    const uint32_t a = 2446, b = 3196, c = 4433, dd = 6270, e = 7373, f = 9633, g = 12299, h = 15137, i = 16069, j = 16819, k = 20995, l = 25172;
+    const uint32_t r = 1u << (s - 1);
+    uint32_t z1 = (x[2] + x[6]) * c;
+    const uint32_t t2 = z1 - x[6] * h, t3 = z1 + x[2] * dd, t0 = (x[0] + x[4]) << 13, t1 = (x[0] - x[4]) << 13;
+    const uint32_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    uint32_t o0 = x[7], o1 = x[5], o2 = x[3], o3 = x[1];
+    z1 = o0 + o3;
+    uint32_t z2 = o1 + o2, z3 = o0 + o2, z4 = o1 + o3;
+    const uint32_t z5 = (z3 + z4) * f;
+    o0 *= a; o1 *= j; o2 *= l; o3 *= g;
+    z1 = 0u - z1 * e; z2 = 0u - z2 * k; z3 = z5 - z3 * i; z4 = z5 - z4 * b;
+    o0 += z1 + z3; o1 += z2 + z4; o2 += z2 + z3; o3 += z1 + z4;
+    x[0] = (uint32_t)((int32_t)(t10 + o3 + r) >> s); x[7] = (uint32_t)((int32_t)(t10 - o3 + r) >> s);
+    x[1] = (uint32_t)((int32_t)(t11 + o2 + r) >> s); x[6] = (uint32_t)((int32_t)(t11 - o2 + r) >> s);
+    x[2] = (uint32_t)((int32_t)(t12 + o1 + r) >> s); x[5] = (uint32_t)((int32_t)(t12 - o1 + r) >> s);
+    x[3] = (uint32_t)((int32_t)(t13 + o0 + r) >> s); x[4] = (uint32_t)((int32_t)(t13 - o0 + r) >> s);
+}
+
+__device__ __forceinline__ uint32_t jpeg_limit(uint32_t y)
+{
+    const uint32_t v = y & 1023u;
+    return v < 128u ? v + 128u : v < 512u ? 255u : v < 896u ? 0u : v - 896u;
+}
+
+// grid (ceil(max blocks / 32), images), 256 threads: 8 lanes per block, 32 blocks per workgroup
+__global__ __launch_bounds__(256) void k_jpeg_idct(const uint32_t* __restrict__ s, uint8_t* __restrict__ planes, long long plane_slot)
+{
+    __shared__ uint32_t ws[32 * JPEG_WS_PITCH];
+    const uint32_t* hdr = s + (size_t)blockIdx.y * JPEG_HDR;
+    const int nblk = (int)hdr[4], lb = threadIdx.x >> 3, l = threadIdx.x & 7, blk = blockIdx.x * 32 + lb;
+    const bool on = blk < nblk;
+    uint32_t* w = ws + lb * JPEG_WS_PITCH;
+    // the block's place: scan order -> (component, block row, block column)
+    const int h = (int)hdr[1], v = (int)hdr[2], mcux = (int)hdr[3], ncomp = (int)hdr[0];
+    const int bpm = ncomp == 1 ? 1 : h * v + 2, mcu = blk / bpm, jj = blk - mcu * bpm, my = mcu / mcux, mx = mcu - my * mcux;
+    int comp = 0, by = my, bx = mx;
+    if (jj < h * v) { by = my * v + jj / h; bx = mx * h + jj % h; }
+    else comp = 1 + jj - h * v;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[l * 9 + i] = 0u;
+    __syncthreads();
+    if (on) {
+        const uint32_t* tab = s + hdr[5];
+        const uint32_t* ent = s + hdr[6];
+        const uint16_t* q = (const uint16_t*)(hdr + 32) + 64 * hdr[8 + comp];
+        const uint32_t e1 = tab[blk + 1];
+        for (uint32_t e = tab[blk] + l; e < e1; e += 8) {
+            const uint32_t u = ent[e], k = (u >> 16) & 63u;
+            w[(k >> 3) * 9 + (k & 7)] = (uint32_t)(int32_t)(int16_t)(u & 0xffffu) * (uint32_t)q[k];
+        }
+    }
+    __syncthreads();
+    uint32_t x[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = w[i * 9 + l];             // lane = column
+    jpeg_pass(x, 11);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i * 9 + l] = x[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = w[l * 9 + i];             // lane = row
+    jpeg_pass(x, 18);
+    if (on) {
+        uint2 o;
+        o.x = jpeg_limit(x[0]) | jpeg_limit(x[1]) << 8 | jpeg_limit(x[2]) << 16 | jpeg_limit(x[3]) << 24;
+        o.y = jpeg_limit(x[4]) | jpeg_limit(x[5]) << 8 | jpeg_limit(x[6]) << 16 | jpeg_limit(x[7]) << 24;
+        uint8_t* p = planes + (size_t)blockIdx.y * plane_slot + hdr[11 + comp] + (size_t)(by * 8 + l) * hdr[14 + comp] + (size_t)bx * 8;
+        *(uint2*)p = o;                                          // plane offsets and pitches are multiples of 8
+    }
+}
+
+// One chroma sample of the full-size image at (x, y): libjpeg's fancy (triangle) upsampling, replication for planes at most 2 wide
+__device__ __forceinline__ int jpeg_chroma(const uint8_t* __restrict__ p, int pitch, int cw, int ch, int x, int y, int hs, int vs)
+{
+    if (hs == 1) return p[y * pitch + x];
+    const int cx = x >> 1, cy = vs == 2 ? y >> 1 : y;
+    if (cw <= 2) return p[cy * pitch + cx];
+    const int xn = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0);
+    if (vs == 1) return (3 * p[cy * pitch + cx] + p[cy * pitch + xn] + ((x & 1) ? 2 : 1)) >> 2;
+    const int oy = (y & 1) ? min(cy + 1, ch - 1) : max(cy - 1, 0);
+    const int c0 = 3 * p[cy * pitch + cx] + p[oy * pitch + cx], c1 = 3 * p[cy * pitch + xn] + p[oy * pitch + xn];
+    return (3 * c0 + c1 + ((x & 1) ? 7 : 8)) >> 4;
+}
+
+__device__ __forceinline__ uint32_t jpeg_clamp(int v) { return (uint32_t)min(max(v, 0), 255); }
+
+// grid (ceil(ceil(H W / 4) / 256), images), 256 threads: a lane makes pixels 4 g .. 4 g + 3 of the flat image (rows are contiguous
+// in HWC, so the 12 bytes are three aligned dwords whenever the image's base is; otherwise, and at the ragged end, bytes)
+__global__ __launch_bounds__(256) void k_jpeg_pixels(const uint32_t* __restrict__ s, const uint8_t* __restrict__ planes, long long plane_slot,
+                                                     int H, int W, uint8_t* __restrict__ out, long long out_stride, int rgb, int dwords)
+{
+    const uint32_t* hdr = s + (size_t)blockIdx.y * JPEG_HDR;
+    const int g = blockIdx.x * 256 + threadIdx.x, npix = H * W, p0 = 4 * g;
+    if (p0 >= npix) return;
+    const int ncomp = (int)hdr[0], hs = (int)hdr[1], vs = (int)hdr[2];
+    const uint8_t* base = planes + (size_t)blockIdx.y * plane_slot;
+    const uint8_t *py = base + hdr[11], *pb = base + hdr[12], *pr = base + hdr[13];
+    const int ypitch = (int)hdr[14], cpitch = (int)hdr[15], cw = (W + hs - 1) / hs, ch = (H + vs - 1) / vs;
+    uint32_t px[4];
+    int y = p0 / W, x = p0 - y * W;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        px[i] = 0;
+        if (p0 + i < npix) {
+            const int Y = py[y * ypitch + x];
+            if (ncomp == 1) px[i] = (uint32_t)Y * 0x010101u;
+            else {
+                const int cb = jpeg_chroma(pb, cpitch, cw, ch, x, y, hs, vs) - 128, cr = jpeg_chroma(pr, cpitch, cw, ch, x, y, hs, vs) - 128;
+                const uint32_t R = jpeg_clamp(Y + ((91881 * cr + 32768) >> 16)), G = jpeg_clamp(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16)),
+                               B = jpeg_clamp(Y + ((116130 * cb + 32768) >> 16));
+                px[i] = rgb ? (R | G << 8 | B << 16) : (B | G << 8 | R << 16);
+            }
+        }
+        if (++x == W) { x = 0; ++y; }
+    }
+    uint8_t* o = out + (size_t)blockIdx.y * out_stride + (size_t)p0 * 3;
+    if (dwords && p0 + 4 <= npix) {
+        uint32_t* o4 = (uint32_t*)o;
+        o4[0] = px[0] | px[1] << 24;
+        o4[1] = px[1] >> 8 | px[2] << 16;
+        o4[2] = px[2] >> 16 | px[3] << 8;
+    } else {
+        for (int i = 0; i < 4 && p0 + i < npix; ++i) { o[3 * i] = (uint8_t)px[i]; o[3 * i + 1] = (uint8_t)(px[i] >> 8); o[3 * i + 2] = (uint8_t)(px[i] >> 16); }
+    }
+}
+
+// ---- host: the batch call --------------------------------------------------------------------------------------------------
+struct SparseSink {
+    std::vector<uint32_t>*tab, *ent;
+    void begin(int, int, int) { tab->push_back((uint32_t)ent->size()); }
+    void coef(int k, int v) { ent->push_back((uint32_t)k << 16 | (uint32_t)(uint16_t)(int16_t)v); }
+};
+
+struct SSJpeg {
+    struct Slot {
+        void* host = nullptr; size_t host_cap = 0;              // write-combined staging
+        uint32_t* dev = nullptr; size_t dev_cap = 0;            // its device mirror
+        uint8_t* planes = nullptr; size_t planes_cap = 0;       // component planes of the call's images
+        hipEvent_t ev = nullptr; bool busy = false;
+    } slot[2];
+    int next = 0;
+    struct Image { JInfo J; std::vector<uint32_t> tab, ent; std::string err; bool ok = false; size_t tab_at = 0, ent_at = 0; };
+    std::vector<Image> img;
+};
+
+// ss_upload_batch's rules: threads that cannot be started have their share done by the caller; nothing thrown crosses the C boundary
+template <class Work>
+static bool run_threads(int T, Work work)
+{
+    try {
+        std::vector<std::thread> pool;
+        pool.reserve(T > 1 ? T - 1 : 0);
+        int started = 1;
+        try {
+            for (int t = 1; t < T; ++t) { pool.emplace_back(work, t, T); ++started; }
+        } catch (...) {
+            for (auto& th : pool) th.join();
+            for (int t = started; t < T; ++t) work(t, T);
+            pool.clear();
+        }
+        work(0, T);
+        for (auto& th : pool) th.join();
+    } catch (...) {
+        return false;
+    }
+    return true;
+}
+
+void ss_jpeg_free(SSJpeg* j)
+{
+    if (!j) return;
+    for (auto& st : j->slot) {
+        if (st.ev) (void)hipEventDestroy(st.ev);
+        if (st.host) (void)hipHostFree(st.host);
+        if (st.dev) (void)hipFree(st.dev);
+        if (st.planes) (void)hipFree(st.planes);
+    }
+    delete j;
+}
+
+#define JCHK(x)                                                                                              \
+    do {                                                                                                     \
+        hipError_t e_ = (x);                                                                                 \
+        if (e_ != hipSuccess) { err = std::string("ss_jpeg_decode_batch: " #x ": ") + hipGetErrorString(e_); return SS_ERR_HIP; } \
+    } while (0)
+
+// The arguments have been checked (ss_api.hip).  Returns an SS_* code, the message in err.
+int ss_jpeg_decode_impl(SSJpeg** state, hipStream_t stream, const unsigned char* const* data, const size_t* sizes, int n, int height, int width,
+                        void* d_out, long long out_frame_stride, int rgb, int threads, std::string& err)
+{
+    try {
+        if (!*state) *state = new SSJpeg();
+        SSJpeg& S = **state;
+        if ((int)S.img.size() < n) S.img.resize(n);
+        // ---- 1. headers + entropy decoding, whole images per thread ----
+        auto decode = [&S, data, sizes, n, height, width](int t, int nt) {
+            for (int i = t; i < n; i += nt) {
+                SSJpeg::Image& im = S.img[i];
+                im.ok = false;
+                im.err.clear();
+                im.tab.clear();
+                im.ent.clear();
+                try {
+                    im.J = JInfo();
+                    if (!parse_headers(data[i], sizes[i], im.J, im.err)) continue;
+                    if (im.J.width != width || im.J.height != height) {
+                        im.err = "size " + std::to_string(im.J.width) + "x" + std::to_string(im.J.height) + " differs from the batch's " + std::to_string(width) + "x" + std::to_string(height);
+                        continue;
+                    }
+                    SparseSink sink{&im.tab, &im.ent};
+                    if (!decode_scan(data[i], sizes[i], im.J, sink, im.err)) continue;
+                    im.tab.push_back((uint32_t)im.ent.size());
+                    im.ok = true;
+                } catch (...) {
+                    im.err = "out of memory";
+                }
+            }
+        };
+        const int T = threads < n ? threads : n;
+        if (!run_threads(T, decode)) { err = "ss_jpeg_decode_batch: host decoding failed"; return SS_ERR_INVALID; }
+        for (int i = 0; i < n; ++i)
+            if (!S.img[i].ok) { err = "ss_jpeg_decode_batch: image " + std::to_string(i) + ": " + S.img[i].err; return SS_ERR_INVALID; }
+        // ---- 2. layout ----
+        size_t at = (size_t)n * JPEG_HDR;
+        int max_blk = 0;
+        for (int i = 0; i < n; ++i) {
+            SSJpeg::Image& im = S.img[i];
+            im.tab_at = at; at += im.tab.size();
+            im.ent_at = at; at += im.ent.size();
+            if ((int)im.tab.size() - 1 > max_blk) max_blk = (int)im.tab.size() - 1;
+        }
+        if (at >= ((size_t)1 << 32)) { err = "ss_jpeg_decode_batch: coefficient stream beyond 2^32 entries"; return SS_ERR_CAPACITY; }
+        const size_t bytes = at * 4;
+        const size_t plane_slot = 3 * (size_t)((width + 15) / 16 * 16) * ((height + 15) / 16 * 16), planes_bytes = plane_slot * n;
+        SSJpeg::Slot& st = S.slot[S.next];
+        if (st.busy) { JCHK(hipEventSynchronize(st.ev)); st.busy = false; }
+        if (!st.ev) JCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+        if (st.host_cap < bytes) {
+            if (st.host) { JCHK(hipHostFree(st.host)); st.host = nullptr; st.host_cap = 0; }
+            const size_t cap = bytes + bytes / 4;
+            JCHK(hipHostMalloc(&st.host, cap, hipHostMallocWriteCombined));
+            st.host_cap = cap;
+        }
+        if (st.dev_cap < bytes) {
+            if (st.dev) { JCHK(hipFree(st.dev)); st.dev = nullptr; st.dev_cap = 0; }
+            const size_t cap = bytes + bytes / 4;
+            JCHK(hipMalloc((void**)&st.dev, cap));
+            st.dev_cap = cap;
+        }
+        if (st.planes_cap < planes_bytes) {
+            if (st.planes) { JCHK(hipFree(st.planes)); st.planes = nullptr; st.planes_cap = 0; }
+            JCHK(hipMalloc((void**)&st.planes, planes_bytes));
+            st.planes_cap = planes_bytes;
+        }
+        // ---- 3. pack into the write-combined area (sequential stores only) ----
+        uint32_t* base = (uint32_t*)st.host;
+        auto pack = [&S, base, n](int t, int nt) {
+            for (int i = t; i < n; i += nt) {
+                const SSJpeg::Image& im = S.img[i];
+                const JInfo& J = im.J;
+                uint32_t hdr[JPEG_HDR];
+                memset(hdr, 0, sizeof hdr);
+                hdr[0] = J.ncomp; hdr[1] = J.h[0]; hdr[2] = J.v[0]; hdr[3] = J.mcux; hdr[4] = (uint32_t)im.tab.size() - 1;
+                hdr[5] = (uint32_t)im.tab_at; hdr[6] = (uint32_t)im.ent_at;
+                uint32_t off = 0;
+                for (int c = 0; c < J.ncomp; ++c) {
+                    const uint32_t pitch = J.mcux * J.h[c] * 8, rows = J.mcuy * J.v[c] * 8;
+                    hdr[8 + c] = J.tq[c]; hdr[11 + c] = off; hdr[14 + c] = pitch;
+                    off += pitch * rows;
+                }
+                memcpy(hdr + 32, J.quant, sizeof J.quant);
+                memcpy(base + (size_t)i * JPEG_HDR, hdr, sizeof hdr);
+                memcpy(base + im.tab_at, im.tab.data(), im.tab.size() * 4);
+                if (!im.ent.empty()) memcpy(base + im.ent_at, im.ent.data(), im.ent.size() * 4);
+            }
+        };
+        if (!run_threads(bytes < ((size_t)1 << 20) ? 1 : T, pack)) { err = "ss_jpeg_decode_batch: host staging failed"; return SS_ERR_INVALID; }
+        // ---- 4. one copy, two launches ----
+        JCHK(hipMemcpyAsync(st.dev, st.host, bytes, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_jpeg_idct, dim3((max_blk + 31) / 32, n), dim3(256), 0, stream, st.dev, st.planes, (long long)plane_slot);
+        const int groups = (height * width + 3) / 4;
+        const int dwords = (((uintptr_t)d_out | (uintptr_t)out_frame_stride) & 3) == 0;
+        hipLaunchKernelGGL(k_jpeg_pixels, dim3((groups + 255) / 256, n), dim3(256), 0, stream, st.dev, st.planes, (long long)plane_slot, height, width,
+                           (uint8_t*)d_out, out_frame_stride, rgb, dwords);
+        JCHK(hipGetLastError());
+        JCHK(hipEventRecord(st.ev, stream));
+        st.busy = true;
+        S.next ^= 1;
+        return SS_OK;
+    } catch (...) {
+        err = "ss_jpeg_decode_batch: out of memory";
+        return SS_ERR_INVALID;
+    }
+}

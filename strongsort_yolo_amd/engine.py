@@ -137,6 +137,23 @@ class TrackerEngine:
         arr = (C.c_void_p * n)(*[a.ctypes.data for a in srcs])
         self._ck(self.L.ss_upload_batch(self.ctx, self._st(stream), _ptr(dst), arr, n, each, int(threads)))
 
+    def jpeg_decode_batch(self, dst: torch.Tensor, frames, stream=None, threads: int = 4, rgb: bool = False):
+        """len(frames) (1 .. 64) jpeg.EncodedFrames of one size -> dst[0 .. len(frames)) (device uint8 [.., H, W, 3], every frame
+        contiguous), BGR or RGB: Huffman decoding on `threads` host threads inside the call, then one asynchronous copy of the
+        coefficients and two launches (csrc/ss_jpeg.hip).  The frames' bytes may be reused immediately."""
+        n = len(frames)
+        if n == 0:
+            return
+        shape = tuple(frames[0].shape)
+        if (any(tuple(f.shape) != shape for f in frames) or dst.dtype != torch.uint8 or dst.dim() != 4 or not dst[0].is_contiguous()
+                or dst.shape[0] < n or tuple(dst.shape[1:]) != shape or (dst.shape[0] > 1 and dst.stride(0) < dst[0].numel())):
+            raise ValueError("jpeg_decode_batch: size / shape / layout mismatch")
+        data = (C.c_char_p * n)(*[f.data for f in frames])
+        sizes = (C.c_size_t * n)(*[len(f.data) for f in frames])
+        stride = dst.stride(0) if dst.shape[0] > 1 else dst[0].numel()
+        self._ck(self.L.ss_jpeg_decode_batch(self.ctx, self._st(stream), data, sizes, n, shape[0], shape[1], _ptr(dst), stride, int(bool(rgb)),
+                                             int(threads)))
+
     def download(self, dst: np.ndarray, src: torch.Tensor, stream=None):
         """Device tensor -> host array (synchronous)."""
         if dst.nbytes != src.numel() * src.element_size() or not src.is_contiguous() or not dst.flags["C_CONTIGUOUS"]:

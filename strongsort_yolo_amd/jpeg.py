@@ -1,0 +1,110 @@
+"""Encoded frames: baseline JPEG decoded on the device (csrc/ss_jpeg.hip, docs/JPEG.md).
+
+    H, W, components, (h, v) = probe(data)          host only
+    f = EncodedFrame(data)                          .shape == (H, W, 3); ValueError with the library's message when refused
+    for f in split_mjpeg("clip.mjpeg"): ...         a raw concatenated MJPEG file, no container parsing
+    for b in split_bytes(buf): ...                  the same cut on bytes, yielding each frame's bytes unprobed
+    t = decode(engine, frames)                      uint8 device tensor [n, H, W, 3], BGR (rgb=True: RGB)
+
+`YOLO.track_stream` takes EncodedFrames in place of arrays: the group is decoded straight into the buffer the detector reads.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Iterator, Union
+
+from . import lib
+
+MAX_BATCH = 64
+
+
+def probe(data):
+    """(H, W, components, (h, v)) of a JPEG the decoder accepts; ValueError with the library's message otherwise."""
+    data = bytes(data)
+    L = lib.load()
+    w, h, nc, hs, vs = (C.c_int() for _ in range(5))
+    rc = L.ss_jpeg_probe(data, len(data), C.byref(w), C.byref(h), C.byref(nc), C.byref(hs), C.byref(vs))
+    if rc != lib.SS_OK:
+        msg = L.ss_last_error(None)
+        raise ValueError(msg.decode() if msg else "ss_jpeg_probe failed")
+    return h.value, w.value, nc.value, (hs.value, vs.value)
+
+
+class EncodedFrame:
+    """One baseline JPEG, still encoded.  `shape` is what the decoded frame will have."""
+    __slots__ = ("data", "shape", "components", "sampling")
+
+    def __init__(self, data):
+        self.data = bytes(data)
+        h, w, self.components, self.sampling = probe(self.data)
+        self.shape = (h, w, 3)
+
+    def __len__(self):
+        return len(self.data)
+
+    def __repr__(self):
+        return f"EncodedFrame({self.shape[1]}x{self.shape[0]}, {len(self.data)} bytes)"
+
+
+def split_bytes(buf: bytes) -> Iterator[bytes]:
+    """The SOI .. EOI runs of a concatenated stream, as bytes (nothing is probed).  Marker segments are skipped by their length (an FFD9 inside APPn / COM data
+    ends nothing); inside entropy-coded data FF is followed by 00 or RSTn, so the first other marker there ends the scan."""
+    n, p = len(buf), 0
+    while True:
+        p = buf.find(b"\xff\xd8", p)
+        if p < 0:
+            return
+        start, p = p, p + 2
+        while p + 1 < n:
+            if buf[p] != 0xFF:
+                p += 1                                             # between segments (not expected in a clean stream)
+                continue
+            m = buf[p + 1]
+            if m == 0xFF:
+                p += 1
+            elif m == 0xD9:
+                p += 2
+                yield buf[start:p]
+                break
+            elif m == 0xD8 or m == 0x01 or 0xD0 <= m <= 0xD7:
+                p += 2
+            else:
+                if p + 3 >= n:
+                    return
+                p += 2 + ((buf[p + 2] << 8) | buf[p + 3])
+                if m == 0xDA:                                      # the scan: to the next marker that is neither stuffing nor a restart
+                    while True:
+                        p = buf.find(b"\xff", p)
+                        if p < 0 or p + 1 >= n:
+                            return
+                        if buf[p + 1] == 0 or 0xD0 <= buf[p + 1] <= 0xD7 or buf[p + 1] == 0xFF:
+                            p += 1 if buf[p + 1] == 0xFF else 2
+                            continue
+                        break
+        else:
+            return
+
+
+def split_mjpeg(src: Union[str, bytes, bytearray, memoryview, "os.PathLike"]) -> Iterator[EncodedFrame]:
+    """EncodedFrames of a raw concatenated MJPEG file (a path) or of its bytes."""
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        buf = bytes(src)
+    else:
+        with open(src, "rb") as f:
+            buf = f.read()
+    for seg in split_bytes(buf):
+        yield EncodedFrame(seg)
+
+
+def decode(engine, frames, out=None, rgb: bool = False, stream=None, threads: int = 4):
+    """EncodedFrames (or bytes) of one size -> uint8 device tensor [n, H, W, 3]; asynchronous on `stream` after the host stage."""
+    import torch
+    frames = [f if isinstance(f, EncodedFrame) else EncodedFrame(f) for f in frames]
+    if not frames:
+        raise ValueError("jpeg.decode: no frames")
+    if out is None:
+        out = torch.empty((len(frames),) + frames[0].shape, dtype=torch.uint8, device=engine.device)
+    for k in range(0, len(frames), MAX_BATCH):
+        engine.jpeg_decode_batch(out[k:k + MAX_BATCH], frames[k:k + MAX_BATCH], stream, threads, rgb)
+    return out

@@ -32,6 +32,7 @@ EXPORTS = [
     "ss_native_feats",
     "ss_byte_set_pose", "ss_byte_update_group_kpts", "ss_byte_get_keypoints", "ss_byte_get_det_keypoints",
     "ss_gmc_sparse_estimate", "ss_gmc_sparse_get",
+    "ss_jpeg_probe", "ss_jpeg_coefficients", "ss_jpeg_decode_batch",
 ]
 
 
@@ -211,6 +212,9 @@ def load():
     L.ss_gmc_sparse_estimate.argtypes = [vp, vp, vp, i, ll, i, i, i, ip, vp]
     L.ss_gmc_sparse_get.argtypes = [vp, i, i, hu8, hu8, hu8, hu8, hi, hi, hi, hd, hu8, hu8]
     L.ss_native_feats.argtypes = [vp, i, i, C.POINTER(ss_native_map), i, ip, ll, ip, fp]
+    L.ss_jpeg_probe.argtypes = [C.c_char_p, C.c_size_t, hi, hi, hi, hi, hi]
+    L.ss_jpeg_coefficients.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_short), C.c_size_t, C.POINTER(C.c_ushort)]
+    L.ss_jpeg_decode_batch.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), i, i, i, vp, ll, i, i]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("ss_destroy", "ss_last_error"):

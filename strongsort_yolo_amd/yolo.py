@@ -414,6 +414,10 @@ class YOLO:
         uses it too (its NMS threshold is overrides['conf'], the tracking pipeline's is track's), so that predict calls between track
         calls do not restart the tracker."""
         from .pipeline import FramePipeline
+        from .jpeg import EncodedFrame
+        if isinstance(image, EncodedFrame):
+            raise TypeError("track() / predict() take decoded frames (BGR uint8 arrays): pass EncodedFrames to track_stream(), "
+                            "or decode them first with strongsort_yolo_amd.jpeg.decode()")
         wide = not track and (int(self.overrides["max_det"]) > 128 or self._byte)
         slot = "_pred_pipe" if wide else "_pipe"
         if wide:
@@ -557,7 +561,8 @@ class YOLO:
     # ---- throughput path ------------------------------------------------------------------------------------
     @torch.no_grad()
     def track_stream(self, frames, batch: int = 16, device=0, keep_device_frames: bool = False, conf: Optional[float] = None):
-        """Generator over `frames` (BGR uint8 arrays of one size): yields the same [Results] `track(frame)` would, in
+        """Generator over `frames` (BGR uint8 arrays of one size, or jpeg.EncodedFrames of one size: baseline JPEGs decoded on the
+        device, `Results.orig_img` is then the EncodedFrame): yields the same [Results] `track(frame)` would, in
         order, `batch` frames at a time through the overlapped two-stream pipeline (stateless stages of group k+1 run
         while the tracker consumes group k; the tracker reads its galleries once per group).
         keep_device_frames: every Results also carries `orig_img_device`, the frame as a device tensor (a device-to-device copy
@@ -565,10 +570,22 @@ class YOLO:
         (`Overlay.draw_resident`); valid until the generator has yielded `ring` more groups.
         conf (BYTE models): the NMS threshold, as track(conf=...) (default 0.1)."""
         from .pipeline import OverlappedPipeline
+        from .jpeg import EncodedFrame
         it = iter(frames)
         first = next(it, None)
         if first is None:
             return
+        encoded = isinstance(first, EncodedFrame)
+
+        def take():
+            """the next frame; an encoded stream holds EncodedFrames of the first one's shape only"""
+            nxt = next(it, None)
+            if encoded and nxt is not None:
+                if not isinstance(nxt, EncodedFrame):
+                    raise TypeError("track_stream: the first frame is an EncodedFrame, so every frame must be one")
+                if nxt.shape != first.shape:
+                    raise ValueError(f"track_stream: EncodedFrame of shape {nxt.shape} in a stream of {first.shape}")
+            return nxt
         self._conf_track = float(conf or 0.1) if self._byte else None
         try:
             pipe, _ = self._cached("_stream_pipe", OverlappedPipeline, first.shape[:2], device, key=(batch,), graph="front", frame_batch=batch,
@@ -608,14 +625,17 @@ class YOLO:
             chunk = [first]
             while chunk:
                 while len(chunk) < F:
-                    nxt = next(it, None)
+                    nxt = take()
                     if nxt is None:
                         break
                     chunk.append(nxt)
                 g = state["group"]
                 b = pipe.begin_frame()                                    # waits until this buffer set's last group left the tracker
                 with torch.cuda.stream(pipe.s_in):
-                    pipe.eng.upload_batch(b.frames, chunk, pipe.s_in)      # the group's frames: staged by several host threads, one copy
+                    if encoded:                                           # Huffman decoding on host threads, the rest on the device (jpeg.py)
+                        pipe.eng.jpeg_decode_batch(b.frames, chunk, pipe.s_in)
+                    else:
+                        pipe.eng.upload_batch(b.frames, chunk, pipe.s_in)  # the group's frames: staged by several host threads, one copy
                     if self._fill is not None:
                         for f in range(len(chunk)):
                             self._fill(b, f, self._frame_index + f)
@@ -626,7 +646,7 @@ class YOLO:
                 state["group"] = g + 1
                 while pending and pending[0][0] <= state["enqueued"] - 1:  # its results are enqueued, and so is a group after it
                     yield from finish(*pending.pop(0))
-                nxt = next(it, None)
+                nxt = take()
                 chunk = [nxt] if nxt is not None else []
             pipe.flush()
             while pending:
