@@ -620,6 +620,25 @@ int ss_jpeg_coefficients(const unsigned char* data, size_t size, short* coef, si
 int ss_jpeg_decode_batch(ss_ctx* ctx, void* hip_stream, const unsigned char* const* data, const size_t* sizes, int n, int height,
                          int width, void* d_out, long long out_frame_stride, int rgb, int threads);
 
+/* ---- frames on the device written as baseline JPEG files (csrc/ss_jpeg_enc.hip, docs/JPEG.md "Encoding") ---- */
+/* The files equal what libjpeg-turbo's defaults write (JDCT_ISLOW, the Annex K Huffman tables, JFIF header) byte for byte: YCbCr
+ * with luma sampling h_samp x v_samp = 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4), quality 1 .. 100, sides 1 .. 8192.
+ * Host only: a capacity no file of that shape can exceed (negative: SS_ERR_INVALID, the cause in ss_last_error(NULL)). */
+long long ss_jpeg_encode_bound(int width, int height, int h_samp, int v_samp);
+/* Host only: the entropy stage and the header alone.  coef: quantised coefficients as dense natural-order int16 blocks in the
+ * layout ss_jpeg_coefficients returns (blocks outside a component's real blocks are not read: the writer fills them in itself);
+ * out receives the whole file (out_cap >= ss_jpeg_encode_bound), *out_size its length.  For tests of the entropy stage. */
+int ss_jpeg_entropy_encode(const short* coef, int quality, int width, int height, int h_samp, int v_samp, unsigned char* out, size_t out_cap,
+                           size_t* out_size);
+/* n (1 .. 64) frames of one size on the device, HWC uint8, BGR (rgb = 0) or RGB, frame i at d_in + i * in_frame_stride -> n files
+ * in the host buffers out[i] (out_cap[i] >= ss_jpeg_encode_bound), lengths in out_size[i].  Colour conversion, downsampling,
+ * forward DCT, quantisation and the compaction of the non-zero coefficients are two launches on hip_stream; the sparse
+ * coefficients come back in one copy, the call waits for it on an event of its own (no device-wide synchronisation) and Huffman-
+ * codes the images on `threads` (1 .. 16) host threads.  Every argument is checked before the device is touched.  Not capturable
+ * (host work, waits): never call it while hip_stream is capturing. */
+int ss_jpeg_encode_batch(ss_ctx* ctx, void* hip_stream, const void* d_in, long long in_frame_stride, int n, int height, int width, int rgb,
+                         int quality, int h_samp, int v_samp, int threads, unsigned char* const* out, const size_t* out_cap, size_t* out_size);
+
 /* ---- profiling support ----------------------------------------------------------------------- */
 /* Mean duration (ms) of the association (cosine gallery) kernel over the launches since the last
  * call, measured with HIP events on the context stream; also returns the launch count. */

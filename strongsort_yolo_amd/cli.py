@@ -7,7 +7,8 @@ on the device (overlay.py, N2) on the frame that is ALREADY there (the throughpu
 of a group: one upload and one download per frame) and the frames go to a sink (N3).  Frame sources (N3): `synthetic[:N]`,
 a `.npy` stack [T,H,W,3], a directory of images (Pillow; with `--device-decode` a JPEG directory or a raw `.mjpeg` file stays encoded and is decoded on the
 device, docs/JPEG.md) and — when OpenCV is importable — a video file or a camera index
-through `cv2.VideoCapture` (:252); sinks: `.npy`, raw BGR24, a PNG directory and — with OpenCV — `cv2.VideoWriter` (:256-260).
+through `cv2.VideoCapture` (:252); sinks: `.npy`, raw BGR24, a PNG directory, with `--device-encode` a raw `.mjpeg` file or a JPEG directory whose frames
+are encoded on the device (docs/JPEG.md "Encoding") and — with OpenCV — `cv2.VideoWriter` (:256-260).
 OpenCV is optional: this environment has none, there the video branches raise a clear error (no GUI: imshow is out of scope).
 """
 from __future__ import annotations
@@ -155,24 +156,84 @@ class FrameSink:
       *.npy      one uint8 stack [T,H,W,3] (BGR), saved at close
       *.bgr      raw BGR24 frames appended as they arrive + `<path>.json` {width, height, fps, frames} (ffmpeg -f rawvideo
                  -pix_fmt bgr24 -s WxH -r fps turns it into the reference's mp4)
-      directory  frame_000000.png ... (Pillow)."""
+      directory  frame_000000.png ... (Pillow)
+    and, with device_encode=True (the CLI's --device-encode), baseline JPEG encoded on the device (jpeg.encode, docs/JPEG.md):
+      *.mjpeg / *.mjpg   the frames' files concatenated (jpeg.split_mjpeg and --device-decode read it back)       kind "mjpeg"
+      directory          frame_000000.jpg ... (the path ends in a separator or is an existing directory)          kind "jpgdir"
+    These two take frames that are still on the device (`write_device`); `write` uploads a host frame into the same path.  Frames
+    are collected in a device buffer and encoded a group (up to GROUP) at a time, on flush() and close()."""
+    GROUP = 32
 
-    def __init__(self, path: str, fps: int = 15):
+    @staticmethod
+    def encoded_kind(path: str) -> Optional[str]:
+        """The device-encoded kind a --save path selects, None when it selects neither."""
+        if path.lower().endswith(MJPEG_EXT):
+            return "mjpeg"
+        if path.endswith(("/", os.sep)) or os.path.isdir(path):
+            return "jpgdir"
+        return None
+
+    def __init__(self, path: str, fps: int = 15, device_encode: bool = False, engine=None, quality: int = 85, subsampling: str = "4:2:0"):
         self.path, self.fps, self.n, self.shape = path, fps, 0, None
-        self.kind = ("npy" if path.endswith(".npy") else "bgr" if path.endswith((".bgr", ".raw")) else
-                     "video" if path.lower().endswith(VIDEO_EXT) else "dir")
+        self.engine, self.quality, self.subsampling = engine, quality, subsampling
+        self._buf, self._held = None, 0                      # device frames waiting for their group's encode
+        if device_encode:
+            self.kind = self.encoded_kind(path)
+            if self.kind is None:
+                raise ValueError(f"sink '{path}': device encoding writes a .mjpeg / .mjpg file or a directory of .jpg files")
+        else:
+            self.kind = ("npy" if path.endswith(".npy") else "bgr" if path.endswith((".bgr", ".raw")) else
+                         "video" if path.lower().endswith(VIDEO_EXT) else "dir")
         self._writer = None
         if self.kind == "video" and _cv2() is None:
             raise RuntimeError(f"sink '{path}' is a video file: that needs OpenCV (`import cv2` failed); use .bgr (raw BGR24 + .json), .npy or a directory")
-        if self.kind == "dir":
+        if self.kind in ("dir", "jpgdir"):
             os.makedirs(path, exist_ok=True)
         else:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         self._frames = []
-        self._f = open(path, "wb") if self.kind == "bgr" else None
+        self._f = open(path, "wb") if self.kind in ("bgr", "mjpeg") else None
+
+    def _slot(self, shape):
+        """The next free frame of the device buffer (encoding what it holds first when it is full or of another size)."""
+        import torch
+        if self.engine is None:
+            raise RuntimeError(f"sink '{self.path}' encodes on the device: it needs an engine (FrameSink(..., engine=...))")
+        if self._buf is not None and (self._held == self.GROUP or tuple(self._buf.shape[1:]) != tuple(shape)):
+            self.flush()
+        if self._buf is None or tuple(self._buf.shape[1:]) != tuple(shape):
+            self._buf = torch.empty((self.GROUP,) + tuple(shape), dtype=torch.uint8, device=self.engine.device)
+        self._held += 1
+        self.n += 1
+        self.shape = tuple(shape)
+        return self._buf[self._held - 1]
+
+    def write_device(self, dev_frame):
+        """A frame on the device (uint8 [H,W,3], BGR): copied into the sink's buffer there — the caller may reuse its tensor."""
+        if self.kind not in ("mjpeg", "jpgdir"):
+            raise ValueError(f"sink '{self.path}' ({self.kind}) takes host frames: write()")
+        self._slot(dev_frame.shape).copy_(dev_frame)
+
+    def flush(self):
+        """Encode and write the device frames collected so far (the device-encoded kinds; nothing to do for the others)."""
+        if not self._held:
+            return
+        from .jpeg import encode
+        files = encode(self.engine, self._buf[:self._held], self.quality, self.subsampling)
+        first, self._held = self.n - self._held, 0
+        for k, data in enumerate(files):
+            if self.kind == "mjpeg":
+                self._f.write(data)
+            else:
+                with open(os.path.join(self.path, f"frame_{first + k:06d}.jpg"), "wb") as f:
+                    f.write(data)
 
     def write(self, frame: np.ndarray):
         frame = np.ascontiguousarray(frame, dtype=np.uint8)
+        if self.kind in ("mjpeg", "jpgdir"):
+            slot = self._slot(frame.shape)
+            self.engine.upload(slot, frame)
+            return
         self.shape = frame.shape
         if self.kind == "npy":
             self._frames.append(frame.copy())
@@ -189,6 +250,9 @@ class FrameSink:
         self.n += 1
 
     def close(self):
+        self.flush()
+        if self.kind == "mjpeg":
+            self._f.close()
         if self.kind == "video" and self._writer is not None:
             self._writer.release()
         if self.kind == "npy":
@@ -274,7 +338,9 @@ def process_video(args: dict, model=None) -> dict:
     frames, t0, fps = 0, time.time(), 0.0
     batch = int(args.get("batch", 16))
     src = frame_source(str(source), args.get("limit"), encoded=bool(args.get("device_decode", False)))
-    sink = FrameSink(args["save"]) if args.get("save") else None       # annotated output (N2 + N3), off by default
+    sink = (FrameSink(args["save"], device_encode=bool(args.get("device_encode", False)), quality=int(args.get("save_quality", 85)),
+                      subsampling=args.get("save_subsampling", "4:2:0")) if args.get("save") else None)       # annotated output (N2 + N3), off by default
+    on_device = sink is not None and sink.kind in ("mjpeg", "jpgdir")
     overlay, fps_str = None, ""
 
     def emit(frame, res):
@@ -292,9 +358,12 @@ def process_video(args: dict, model=None) -> dict:
         if sink is not None:
             if overlay is None:
                 overlay = model.overlay()
+                sink.engine = overlay.eng
             cnt = counter.counts() if (count and track) else None
             dev_frame = getattr(res[0], "orig_img_device", None) if res else None
-            if dev_frame is not None:                # the frame is still on the device: draw there, ONE download, no second upload
+            if dev_frame is not None and on_device:  # drawn and encoded where it is: only the sparse coefficients of its JPEG come back
+                sink.write_device(overlay.annotate_resident(dev_frame, res, cnt, fps_str))
+            elif dev_frame is not None:              # the frame is still on the device: draw there, ONE download, no second upload
                 sink.write(overlay.draw_resident(dev_frame, res, cnt, fps_str))
             else:
                 sink.write(overlay.draw(frame, res, cnt, fps_str))
@@ -320,6 +389,16 @@ def process_video(args: dict, model=None) -> dict:
         sink.close()
     writer.close()
     return {"source": str(source), "frames": frames, "fps": fps, "counts": counter.counts() if count and track else {}}
+
+
+def _save_path(a, i: int) -> Optional[str]:
+    """--save of source i: the path itself for one source, `<root>_<i><ext>` for several (a JPEG directory: `<directory>/stream_<i>/`)."""
+    if not a.save or len(a.source) == 1:
+        return a.save
+    if a.device_encode and FrameSink.encoded_kind(a.save) == "jpgdir":
+        return os.path.join(a.save, f"stream_{i}", "")
+    root, ext = os.path.splitext(a.save)
+    return f"{root}_{i}{ext}"
 
 
 def main(argv=None):
@@ -349,7 +428,13 @@ def main(argv=None):
     p.add_argument("--with-pose", action="store_true",
                    help="--tracker botsort on a pose model only: the keypoint (OKS) term beside IoU (docs/BYTETRACK.md §1e); not with --with-reid")
     p.add_argument("--limit", type=int, default=None)
-    p.add_argument("--save", default=None, help="write annotated frames: stack.npy | video.bgr (raw BGR24 + .json) | directory of PNGs | video.mp4 (needs OpenCV)")
+    p.add_argument("--save", default=None, help="write annotated frames: stack.npy | video.bgr (raw BGR24 + .json) | directory of PNGs | video.mp4 (needs OpenCV) | "
+                                                "with --device-encode: clip.mjpeg (raw concatenated JPEG) or a directory of .jpg files")
+    p.add_argument("--device-encode", action="store_true",
+                   help="encode the annotated frames as baseline JPEG on the device (colour, DCT and quantisation in csrc/ss_jpeg_enc.hip, Huffman on host "
+                        "threads; the same bytes as Pillow, docs/JPEG.md); needs --save clip.mjpeg / clip.mjpg or --save <directory>/")
+    p.add_argument("--save-quality", type=int, default=85, help="--device-encode: JPEG quality 1 .. 100")
+    p.add_argument("--save-subsampling", choices=("4:2:0", "4:2:2", "4:4:4"), default="4:2:0", help="--device-encode: chroma subsampling")
     p.add_argument("--batch", type=int, default=16, help="frames per group on the throughput path (1: per-frame model.track calls as in the reference)")
     p.add_argument("--random-init", action="store_true", help="run seeded random-init networks when the weights file is missing")
     p.add_argument("--device-decode", action="store_true",
@@ -382,8 +467,16 @@ def main(argv=None):
             why = encoded_source_error(src)
             if why:
                 p.error(why)
+    if a.device_encode:
+        if not a.save:
+            p.error("--device-encode encodes the annotated output: it needs --save")
+        if FrameSink.encoded_kind(a.save) is None:
+            p.error(f"--device-encode: --save '{a.save}' must be a .mjpeg / .mjpg file or a directory (a path ending in '/' or an existing directory)")
+        if not 1 <= a.save_quality <= 100:
+            p.error("--save-quality must be 1 .. 100")
     jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "device_decode": a.device_decode,
-             "save": (a.save if len(a.source) == 1 else f"{os.path.splitext(a.save)[0]}_{i}{os.path.splitext(a.save)[1]}") if a.save else None}
+             "device_encode": a.device_encode, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
+             "save": _save_path(a, i)}
             for i, s in enumerate(a.source)]
     import torch
     ngpu = max(torch.cuda.device_count(), 1)

@@ -54,6 +54,11 @@ int  ss_jpeg_probe_impl(const unsigned char*, size_t, int*, int*, int*, int*, in
 int  ss_jpeg_coefficients_impl(const unsigned char*, size_t, short*, size_t, unsigned short*, std::string&);
 int  ss_jpeg_decode_impl(SSJpeg**, hipStream_t, const unsigned char* const*, const size_t*, int, int, int, void*, long long, int, int, std::string&);
 void ss_jpeg_free(SSJpeg*);
+struct SSJpegEnc;                       // ss_jpeg_enc.hip
+size_t ss_jpeg_encode_bound_impl(int, int, int, int);
+int  ss_jpeg_entropy_encode_impl(const short*, int, int, int, int, int, unsigned char*, size_t*, std::string&);
+int  ss_jpeg_encode_impl(SSJpegEnc**, hipStream_t, const void*, long long, int, int, int, int, int, int, int, int, unsigned char* const*, size_t*, std::string&);
+void ss_jpeg_enc_free(SSJpegEnc*);
 
 static std::string g_last_error;
 
@@ -118,6 +123,7 @@ struct ss_ctx {
     struct Byte { SSByteDev dev; ss_byte_config cfg; std::vector<void*> allocs; };
     Byte* byte = nullptr;
     SSJpeg* jpeg = nullptr;     // ss_jpeg_decode_batch's staging areas and planes, made by its first call
+    SSJpegEnc* jpeg_enc = nullptr;   // ss_jpeg_encode_batch's buffers, made by its first call
 };
 
 static int fail(ss_ctx* c, int code, const std::string& msg)
@@ -272,6 +278,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     for (auto& st : c->bstage) { if (st.ev) (void)hipEventDestroy(st.ev); if (st.p) (void)hipHostFree(st.p); }
     if (c->back.p) (void)hipHostFree(c->back.p);
     ss_jpeg_free(c->jpeg);
+    ss_jpeg_enc_free(c->jpeg_enc);
     delete c;
 }
 
@@ -379,6 +386,54 @@ extern "C" int ss_jpeg_decode_batch(ss_ctx* c, void* hip_stream, const unsigned 
     for (int i = 0; i < n; ++i) if (!data[i] || !sizes[i]) return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch: image " + std::to_string(i) + ": no data");
     std::string err;
     const int rc = ss_jpeg_decode_impl(&c->jpeg, (hipStream_t)hip_stream, data, sizes, n, height, width, d_out, out_frame_stride, rgb, threads, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+// ---- N3 frame sink: baseline JPEG (ss_jpeg_enc.hip) --------------------------------------------------------
+static const char* jpeg_enc_shape_error(int width, int height, int quality, int h_samp, int v_samp)
+{
+    if (width < 1 || width > 8192 || height < 1 || height > 8192) return "sides must be 1 .. 8192";
+    if (quality < 1 || quality > 100) return "quality must be 1 .. 100";
+    if (!((h_samp == 2 && v_samp == 2) || (h_samp == 2 && v_samp == 1) || (h_samp == 1 && v_samp == 1))) return "luma sampling must be 2x2, 2x1 or 1x1";
+    return nullptr;
+}
+
+extern "C" long long ss_jpeg_encode_bound(int width, int height, int h_samp, int v_samp)
+{
+    if (const char* why = jpeg_enc_shape_error(width, height, 50, h_samp, v_samp)) return fail(nullptr, SS_ERR_INVALID, std::string("ss_jpeg_encode_bound: ") + why);
+    return (long long)ss_jpeg_encode_bound_impl(width, height, h_samp, v_samp);
+}
+
+extern "C" int ss_jpeg_entropy_encode(const short* coef, int quality, int width, int height, int h_samp, int v_samp, unsigned char* out, size_t out_cap,
+                                      size_t* out_size)
+{
+    if (!coef || !out || !out_size) return fail(nullptr, SS_ERR_INVALID, "ss_jpeg_entropy_encode: null argument");
+    if (const char* why = jpeg_enc_shape_error(width, height, quality, h_samp, v_samp)) return fail(nullptr, SS_ERR_INVALID, std::string("ss_jpeg_entropy_encode: ") + why);
+    const size_t bound = ss_jpeg_encode_bound_impl(width, height, h_samp, v_samp);
+    if (out_cap < bound) return fail(nullptr, SS_ERR_INVALID, "ss_jpeg_entropy_encode: out_cap " + std::to_string(out_cap) + " is below the bound " + std::to_string(bound));
+    std::string err;
+    const int rc = ss_jpeg_entropy_encode_impl(coef, quality, width, height, h_samp, v_samp, out, out_size, err);
+    return rc == SS_OK ? rc : fail(nullptr, rc, "ss_jpeg_entropy_encode: " + err);
+}
+
+extern "C" int ss_jpeg_encode_batch(ss_ctx* c, void* hip_stream, const void* d_in, long long in_frame_stride, int n, int height, int width, int rgb,
+                                    int quality, int h_samp, int v_samp, int threads, unsigned char* const* out, const size_t* out_cap, size_t* out_size)
+{
+    if (!c || !d_in || !out || !out_cap || !out_size) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: null argument");
+    if (n < 1 || n > 64) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: 1 <= n <= 64");
+    if (threads < 1 || threads > 16) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: 1 <= threads <= 16");
+    if (rgb != 0 && rgb != 1) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: rgb 0 / 1");
+    if (const char* why = jpeg_enc_shape_error(width, height, quality, h_samp, v_samp)) return fail(c, SS_ERR_INVALID, std::string("ss_jpeg_encode_batch: ") + why);
+    if (n > 1 && in_frame_stride < (long long)height * width * 3) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: in_frame_stride >= height * width * 3");
+    const size_t bound = ss_jpeg_encode_bound_impl(width, height, h_samp, v_samp);
+    for (int i = 0; i < n; ++i) {
+        if (!out[i]) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: image " + std::to_string(i) + ": null buffer");
+        if (out_cap[i] < bound)
+            return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: image " + std::to_string(i) + ": out_cap " + std::to_string(out_cap[i]) + " is below the bound " + std::to_string(bound));
+    }
+    std::string err;
+    const int rc = ss_jpeg_encode_impl(&c->jpeg_enc, (hipStream_t)hip_stream, d_in, in_frame_stride, n, height, width, rgb, quality, h_samp, v_samp, threads, out,
+                                       out_size, err);
     return rc == SS_OK ? rc : fail(c, rc, err);
 }
 

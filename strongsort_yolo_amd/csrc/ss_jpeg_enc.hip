@@ -1,0 +1,515 @@
+// ss_jpeg_enc.hip — frames on the device written as baseline JPEG files (docs/JPEG.md "Encoding"): the mirror of ss_jpeg.hip.
+//
+// Two kernels do everything that is independent per 8x8 block, for all images of the call at once:
+//   k_jpegenc_fdct  eight lanes per block: gather the block's 64 samples from the HWC frame (colour conversion and chroma
+//                   downsampling on the fly, clamped indices), ISLOW forward DCT (pass 1 on the lane's row in registers, pass 2 on
+//                   its column through LDS), quantisation, the 64 values in zig-zag order as int16 into a dense device-only
+//                   buffer, the block's non-zero count into a table in SCAN order
+//   k_jpegenc_pack  exclusive scan of the counts per image, then the compaction: a wave per block, a lane per coefficient
+// What crosses to the host is the SPARSE stream (a 32-bit offset per block, a 32-bit entry per non-zero coefficient).  The serial
+// part, Huffman coding with the Annex K tables, runs on the call's host threads, whole images per thread.
+// Every value is an integer; the files equal libjpeg-turbo's defaults (JDCT_ISLOW, standard tables) byte for byte.
+#include <cstring>
+#include <string>
+#include <vector>
+#include "ss_common.h"
+#include "ss_jpeg_host.h"
+
+#define JENC_WS_PITCH 72                // LDS dwords per block, rows of 9 (8 + 1 pad), as in k_jpeg_idct
+#define JENC_PACK_THREADS 1024
+#define JENC_HEADER_BYTES 625           // SOI, APP0, 2 DQT, SOF0, 4 DHT, SOS, EOI
+#define JENC_BLOCK_BYTES 416            // 20 bits of DC + 63 * 26 bits of AC = 208 bytes, every one of them stuffed
+
+// ---- tables ----------------------------------------------------------------------------------------------------------------
+// Annex K.1 / K.2, natural order
+static const uint8_t kBaseQuant[2][64] = {
+    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+
+// Annex K.3.3 - K.3.6: code counts per length 1 .. 16, then the symbols; order DC 0, AC 0, DC 1, AC 1 (the order of the DHT segments)
+static const uint8_t kDcCounts[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+static const uint8_t kDcSyms[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+static const uint8_t kAcCounts[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
+static const uint8_t kAcSyms[2][162] = {
+    {1, 2, 3, 0, 4, 17, 5, 18, 33, 49, 65, 6, 19, 81, 97, 7, 34, 113, 20, 50, 129, 145, 161, 8, 35, 66, 177, 193, 21, 82, 209, 240, 36, 51, 98, 114, 130, 9, 10,
+     22, 23, 24, 25, 26, 37, 38, 39, 40, 41, 42, 52, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72, 73, 74, 83, 84, 85, 86, 87, 88, 89, 90, 99, 100, 101, 102,
+     103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163,
+     164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215,
+     216, 217, 218, 225, 226, 227, 228, 229, 230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250},
+    {0, 1, 2, 3, 17, 4, 5, 33, 49, 6, 18, 65, 81, 7, 97, 113, 19, 34, 50, 129, 8, 20, 66, 145, 161, 177, 193, 9, 35, 51, 82, 240, 21, 98, 114, 209, 10, 22, 36,
+     52, 225, 37, 241, 23, 24, 25, 26, 38, 39, 40, 41, 42, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72, 73, 74, 83, 84, 85, 86, 87, 88, 89, 90, 99, 100, 101,
+     102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 130, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154,
+     162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213,
+     214, 215, 216, 217, 218, 226, 227, 228, 229, 230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249, 250}};
+
+// q[k] = clamp((base[k] * s + 50) / 100, 1, 255) with s = 5000 / Q below 50 and 200 - 2 Q from there; natural order, [0] luma [1] chroma
+static void jenc_quant(int quality, uint16_t (&q)[2][64])
+{
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int t = 0; t < 2; ++t)
+        for (int k = 0; k < 64; ++k) {
+            const int v = (kBaseQuant[t][k] * s + 50) / 100;
+            q[t][k] = (uint16_t)(v < 1 ? 1 : v > 255 ? 255 : v);
+        }
+}
+
+// ---- host: the entropy stage -----------------------------------------------------------------------------------------------
+struct JEncHuff { uint16_t code[256]; uint8_t len[256]; };      // len 0: the table has no such symbol
+
+static void jenc_build(JEncHuff& t, const uint8_t* counts, const uint8_t* syms)
+{
+    memset(&t, 0, sizeof t);
+    int code = 0, k = 0;
+    for (int ln = 1; ln <= 16; ++ln) {
+        for (int i = 0; i < counts[ln - 1]; ++i, ++code, ++k) { t.code[syms[k]] = (uint16_t)code; t.len[syms[k]] = (uint8_t)ln; }
+        code <<= 1;
+    }
+}
+
+struct JEncTables {
+    JEncHuff dc[2], ac[2];
+    JEncTables() { for (int t = 0; t < 2; ++t) { jenc_build(dc[t], kDcCounts[t], kDcSyms); jenc_build(ac[t], kAcCounts[t], kAcSyms[t]); } }
+};
+static const JEncTables kEnc;
+
+struct JEncBits {
+    uint8_t* p;
+    uint64_t acc = 0;
+    int n = 0;                          // bits waiting in acc (below 32 between calls)
+    inline void bytes(int k)
+    {
+        for (; k > 0; --k, n -= 8) {
+            const uint8_t b = (uint8_t)(acc >> (n - 8));
+            *p++ = b;
+            if (b == 0xFF) *p++ = 0;
+        }
+    }
+    inline void put(uint32_t bits, int len)                         // len <= 27
+    {
+        acc = (acc << len) | bits;
+        n += len;
+        if (n >= 32) {
+            uint32_t w = (uint32_t)(acc >> (n - 32));
+            const uint32_t x = ~w;
+            if (!((x - 0x01010101u) & ~x & 0x80808080u)) {          // four bytes without an FF: stored at once
+                w = __builtin_bswap32(w);
+                memcpy(p, &w, 4);
+                p += 4;
+                n -= 32;
+            } else bytes(4);
+        }
+    }
+    inline void finish()                                            // the last byte is padded with 1-bits
+    {
+        bytes(n >> 3);
+        if (n) { acc = (acc << (8 - n)) | ((1u << (8 - n)) - 1); n = 8; bytes(1); }
+    }
+};
+
+static inline int jenc_category(int v) { return v ? 32 - __builtin_clz((unsigned)(v < 0 ? -v : v)) : 0; }
+
+// One block: its non-zero coefficients as entries (zig-zag index << 16 | uint16 value) in rising zig-zag order
+static inline bool jenc_block(JEncBits& b, const uint32_t* ent, int cnt, int& pred, const JEncHuff& dc, const JEncHuff& ac)
+{
+    int i = 0, v = 0;
+    if (cnt && (ent[0] >> 16) == 0) { v = (int16_t)(ent[0] & 0xffffu); i = 1; }
+    const int diff = v - pred;
+    pred = v;
+    int s = jenc_category(diff);
+    if (s > 11) return false;
+    b.put(((uint32_t)dc.code[s] << s) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1)), dc.len[s] + s);
+    int k = 1;                                                      // the next zig-zag index to be coded
+    for (; i < cnt; ++i) {
+        const int zz = (int)(ent[i] >> 16);
+        v = (int16_t)(ent[i] & 0xffffu);
+        int run = zz - k;
+        if (run < 0 || zz > 63) return false;
+        for (; run > 15; run -= 16) b.put(ac.code[0xF0], ac.len[0xF0]);
+        s = jenc_category(v);
+        if (s > 10) return false;
+        const int sym = (run << 4) | s;
+        b.put(((uint32_t)ac.code[sym] << s) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1)), ac.len[sym] + s);
+        k = zz + 1;
+    }
+    if (k < 64) b.put(ac.code[0], ac.len[0]);
+    return true;
+}
+
+// A dummy block (outside the component's real blocks): all AC zero, the DC of the block before it, so its difference is 0
+static inline void jenc_dummy(JEncBits& b, const JEncHuff& dc, const JEncHuff& ac)
+{
+    b.put(dc.code[0], dc.len[0]);
+    b.put(ac.code[0], ac.len[0]);
+}
+
+struct JEncShape {
+    int W, H, hm, vm, mcux, mcuy, bpm, nscan;
+    int bw[2], bh[2];                   // real blocks of luma [0] and of a chroma component [1]
+    JEncShape(int width, int height, int h, int v) : W(width), H(height), hm(h), vm(v)
+    {
+        mcux = (W + 8 * hm - 1) / (8 * hm);
+        mcuy = (H + 8 * vm - 1) / (8 * vm);
+        bpm = hm * vm + 2;
+        nscan = mcux * mcuy * bpm;
+        bw[0] = (W + 7) / 8; bh[0] = (H + 7) / 8;
+        bw[1] = ((W + hm - 1) / hm + 7) / 8; bh[1] = ((H + vm - 1) / vm + 7) / 8;
+    }
+};
+
+size_t ss_jpeg_encode_bound_impl(int width, int height, int h_samp, int v_samp)
+{
+    const JEncShape S(width, height, h_samp, v_samp);
+    return JENC_HEADER_BYTES + 15 + (size_t)S.nscan * JENC_BLOCK_BYTES;
+}
+
+static uint8_t* jenc_header(uint8_t* p, const JEncShape& S, const uint16_t (&q)[2][64])
+{
+    auto put16 = [&p](int v) { *p++ = (uint8_t)(v >> 8); *p++ = (uint8_t)v; };
+    put16(0xFFD8);
+    put16(0xFFE0); put16(16); memcpy(p, "JFIF\0\1\1\0\0\1\0\1\0\0", 14); p += 14;
+    for (int t = 0; t < 2; ++t) {
+        put16(0xFFDB); put16(67); *p++ = (uint8_t)t;
+        for (int k = 0; k < 64; ++k) *p++ = (uint8_t)q[t][kZigzag[k]];
+    }
+    put16(0xFFC0); put16(17); *p++ = 8; put16(S.H); put16(S.W); *p++ = 3;
+    *p++ = 1; *p++ = (uint8_t)(S.hm << 4 | S.vm); *p++ = 0;
+    *p++ = 2; *p++ = 0x11; *p++ = 1;
+    *p++ = 3; *p++ = 0x11; *p++ = 1;
+    for (int t = 0; t < 2; ++t) {
+        put16(0xFFC4); put16(31); *p++ = (uint8_t)t; memcpy(p, kDcCounts[t], 16); p += 16; memcpy(p, kDcSyms, 12); p += 12;
+        put16(0xFFC4); put16(181); *p++ = (uint8_t)(0x10 | t); memcpy(p, kAcCounts[t], 16); p += 16; memcpy(p, kAcSyms[t], 162); p += 162;
+    }
+    put16(0xFFDA); put16(12); *p++ = 3; *p++ = 1; *p++ = 0x00; *p++ = 2; *p++ = 0x11; *p++ = 3; *p++ = 0x11; *p++ = 0; *p++ = 63; *p++ = 0;
+    return p;
+}
+
+// The whole file of one image.  Block(s, comp, by, bx, ent) -> the entry count of the real block at scan position s, its entries in ent
+// (a pointer it may redirect).  out holds at least ss_jpeg_encode_bound bytes.
+template <class Block>
+static bool jenc_file(const JEncShape& S, const uint16_t (&q)[2][64], Block block, uint8_t* out, size_t* out_size)
+{
+    JEncBits b{jenc_header(out, S, q)};
+    int pred[3] = {0, 0, 0};
+    int s = 0;
+    for (int my = 0; my < S.mcuy; ++my)
+        for (int mx = 0; mx < S.mcux; ++mx)
+            for (int j = 0; j < S.bpm; ++j, ++s) {
+                const int comp = j < S.hm * S.vm ? 0 : 1 + j - S.hm * S.vm, t = comp ? 1 : 0;
+                const int by = comp ? my : my * S.vm + j / S.hm, bx = comp ? mx : mx * S.hm + j % S.hm;
+                if (by >= S.bh[t] || bx >= S.bw[t]) { jenc_dummy(b, kEnc.dc[t], kEnc.ac[t]); continue; }
+                uint32_t tmp[64];
+                const uint32_t* ent = tmp;
+                const int cnt = block(s, comp, by, bx, tmp, ent);
+                if (!jenc_block(b, ent, cnt, pred[comp], kEnc.dc[t], kEnc.ac[t])) return false;
+            }
+    b.finish();
+    *b.p++ = 0xFF; *b.p++ = 0xD9;
+    *out_size = (size_t)(b.p - out);
+    return true;
+}
+
+// The arguments have been checked (ss_api.hip)
+int ss_jpeg_entropy_encode_impl(const short* coef, int quality, int width, int height, int h_samp, int v_samp, unsigned char* out, size_t* out_size,
+                                std::string& err)
+{
+    const JEncShape S(width, height, h_samp, v_samp);
+    uint16_t q[2][64];
+    jenc_quant(quality, q);
+    // ss_jpeg_coefficients' layout: component after component, each one's blocks in raster order over its whole-MCU grid
+    const size_t ybl = (size_t)S.mcux * S.hm * S.mcuy * S.vm, cbl = (size_t)S.mcux * S.mcuy;
+    auto block = [&](int, int comp, int by, int bx, uint32_t* tmp, const uint32_t*&) {
+        const short* c = coef + (comp == 0 ? ((size_t)by * S.mcux * S.hm + bx) : ybl + (comp - 1) * cbl + (size_t)by * S.mcux + bx) * 64;
+        int n = 0;
+        for (int k = 0; k < 64; ++k)
+            if (c[kZigzag[k]]) tmp[n++] = (uint32_t)k << 16 | (uint16_t)c[kZigzag[k]];
+        return n;
+    };
+    if (!jenc_file(S, q, block, out, out_size)) { err = "a coefficient beyond the baseline categories (DC difference 11 bits, AC 10 bits)"; return SS_ERR_INVALID; }
+    return SS_OK;
+}
+
+// ---- device ----------------------------------------------------------------------------------------------------------------
+struct JEncParams {
+    uint16_t q[2][64];                  // natural order
+    uint32_t recip[2][64];              // floor(2^32 / (8 q)) + 1: (a * recip) >> 32 == a / (8 q) for every a the transform can give (tests/test_jpeg_encode_cpu.py)
+    uint8_t zz[64];                     // natural index -> zig-zag position
+};
+
+// One 1-D pass of jfdctint's ISLOW on d[0..7] (docs/JPEG.md "Encoding"); int32 with wrap-around like the decoder's passes
+template <bool FIRST>
+__device__ __forceinline__ void jenc_pass(uint32_t (&d)[8])
+{
+    constexpr int s = FIRST ? 11 : 15;
+    constexpr uint32_t r = 1u << (s - 1);
+    const uint32_t t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6], t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
+    const uint32_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    if (FIRST) { d[0] = (t10 + t11) << 2; d[4] = (t10 - t11) << 2; }
+    else { d[0] = (uint32_t)((int32_t)(t10 + t11 + 2u) >> 2); d[4] = (uint32_t)((int32_t)(t10 - t11 + 2u) >> 2); }
+    uint32_t z1 = (t12 + t13) * 4433u;
+    d[2] = (uint32_t)((int32_t)(z1 + t13 * 6270u + r) >> s);
+    d[6] = (uint32_t)((int32_t)(z1 - t12 * 15137u + r) >> s);
+    z1 = t4 + t7;
+    uint32_t z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+    const uint32_t z5 = (z3 + z4) * 9633u;
+    const uint32_t u4 = t4 * 2446u, u5 = t5 * 16819u, u6 = t6 * 25172u, u7 = t7 * 12299u;
+    z1 = 0u - z1 * 7373u; z2 = 0u - z2 * 20995u; z3 = z5 - z3 * 16069u; z4 = z5 - z4 * 3196u;
+    d[7] = (uint32_t)((int32_t)(u4 + z1 + z3 + r) >> s);
+    d[5] = (uint32_t)((int32_t)(u5 + z2 + z4 + r) >> s);
+    d[3] = (uint32_t)((int32_t)(u6 + z2 + z3 + r) >> s);
+    d[1] = (uint32_t)((int32_t)(u7 + z1 + z4 + r) >> s);
+}
+
+// grid (ceil(scan positions / 32), images), 256 threads: 8 lanes per block, 32 blocks per workgroup.  A block is named by its scan
+// position (MCU after MCU; inside an MCU the hm * vm luma blocks row by row, then Cb, then Cr); positions outside the component's real
+// blocks (the dummies that complete an MCU) only write a count of 0.
+__global__ __launch_bounds__(256) void k_jpegenc_fdct(const uint8_t* __restrict__ in, long long in_stride, int H, int W, int rgb, int hm, int vm, int mcux,
+                                                      int nscan, int16_t* __restrict__ dense, uint32_t* __restrict__ cnt, uint32_t* __restrict__ totals,
+                                                      const JEncParams P)
+{
+    __shared__ uint32_t ws[32 * JENC_WS_PITCH];
+    const int img = blockIdx.y, lb = threadIdx.x >> 3, l = threadIdx.x & 7, s = blockIdx.x * 32 + lb;
+    uint32_t* w = ws + lb * JENC_WS_PITCH;
+    const int bpm = hm * vm + 2, mcu = s / bpm, jj = s - mcu * bpm, my = mcu / mcux, mx = mcu - my * mcux;
+    int comp = 0, by = my, bx = mx;
+    if (jj < hm * vm) { by = my * vm + jj / hm; bx = mx * hm + jj % hm; }
+    else comp = 1 + jj - hm * vm;
+    const int cw = comp ? (W + hm - 1) / hm : W, ch = comp ? (H + vm - 1) / vm : H;        // the component's plane
+    const bool on = s < nscan && by * 8 < ch && bx * 8 < cw;
+    const uint8_t* src = in + (size_t)img * in_stride;
+    const int ir = rgb ? 0 : 2, ib = 2 - ir;
+    uint32_t x[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = 0u;
+    if (on && comp == 0) {
+        const uint8_t* row = src + (size_t)min(by * 8 + l, H - 1) * W * 3;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const uint8_t* p = row + min(bx * 8 + i, W - 1) * 3;
+            x[i] = (uint32_t)(((19595 * p[ir] + 38470 * p[1] + 7471 * p[ib] + 32768) >> 16) - 128);
+        }
+    } else if (on) {
+        // chroma sample (cy, cx): vertically the DOWNSAMPLED last row is replicated (cy clamped), horizontally the full-size last
+        // column (cx is not clamped, the pixel columns are); the rounding bias alternates with cx, in the padded columns too
+        const int kr = comp == 1 ? -11059 : 32768, kg = comp == 1 ? -21709 : -27439, kb = comp == 1 ? 32768 : -5329;
+        const int cy = min(by * 8 + l, ch - 1);
+        const uint8_t* row0 = src + (size_t)min(vm * cy, H - 1) * W * 3;
+        const uint8_t* row1 = src + (size_t)min(vm * cy + vm - 1, H - 1) * W * 3;
+        auto chroma = [=](const uint8_t* p) { return (kr * p[ir] + kg * p[1] + kb * p[ib] + 8388608 + 32767) >> 16; };
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int cx = bx * 8 + i, x0 = min(hm * cx, W - 1) * 3, x1 = min(hm * cx + hm - 1, W - 1) * 3;
+            int v = chroma(row0 + x0);
+            if (hm == 2) {
+                v += chroma(row0 + x1);
+                if (vm == 2) v = (v + chroma(row1 + x0) + chroma(row1 + x1) + 1 + (cx & 1)) >> 2;
+                else v = (v + (cx & 1)) >> 1;
+            }
+            x[i] = (uint32_t)(v - 128);
+        }
+    }
+    jenc_pass<true>(x);                                          // the lane's row
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[l * 9 + i] = x[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = w[i * 9 + l];             // lane = column
+    jenc_pass<false>(x);
+    __syncthreads();
+    const int t = comp ? 1 : 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {                                // x[i] is coefficient (row i, column l), 8 x its true value
+        const int k = i * 8 + l, c = (int32_t)x[i];
+        const uint32_t qv = (uint32_t)P.q[t][k] << 3, a = (uint32_t)(c < 0 ? -c : c) + (qv >> 1);
+        const int m = (int)__umulhi(a, P.recip[t][k]);
+        const int z = P.zz[k];
+        w[(z >> 3) * 9 + (z & 7)] = (uint32_t)(c < 0 ? -m : m);
+    }
+    __syncthreads();
+    uint32_t v[8];
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { v[i] = w[l * 9 + i]; c += v[i] != 0u; }
+    c += __shfl_xor(c, 1); c += __shfl_xor(c, 2); c += __shfl_xor(c, 4);                  // the block's count, in its eight lanes
+    if (on) {
+        uint4 o;
+        o.x = (v[0] & 0xffffu) | v[1] << 16; o.y = (v[2] & 0xffffu) | v[3] << 16; o.z = (v[4] & 0xffffu) | v[5] << 16; o.w = (v[6] & 0xffffu) | v[7] << 16;
+        *(uint4*)(dense + ((size_t)img * nscan + s) * 64 + l * 8) = o;
+    }
+    if (l == 0 && s < nscan) cnt[(size_t)img * nscan + s] = (uint32_t)c;                  // (a block that is not `on` transformed zeros: 0)
+    int tot = l == 0 ? c : 0;                                    // one atomic per wave for the image's entry total
+    tot += __shfl_xor(tot, 8); tot += __shfl_xor(tot, 16); tot += __shfl_xor(tot, 32);
+    if ((threadIdx.x & 63) == 0 && tot) atomicAdd(totals + img, (uint32_t)tot);
+}
+
+__device__ __forceinline__ uint32_t jenc_wave_scan(uint32_t v, int lane)                  // inclusive
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t u = __shfl_up(v, d);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+
+// grid (chunks, images), 1024 threads.  A workgroup owns the scan positions [chunk * blockIdx.x, chunk * (blockIdx.x + 1)) of its image:
+// it sums the counts before them, scans its own into the image's block table (table[b] .. table[b + 1] are block b's entries, relative to
+// the image's first entry; blocks + 1 words) and compacts its blocks: a wave per block, a lane per coefficient, the entry's place from
+// the ballot of the non-zero lanes.  The images' entries follow each other: image i starts at the sum of the totals before it.
+__global__ __launch_bounds__(JENC_PACK_THREADS) void k_jpegenc_pack(const int16_t* __restrict__ dense, const uint32_t* __restrict__ cnt,
+                                                                    const uint32_t* __restrict__ totals, uint32_t* table,
+                                                                    uint32_t* __restrict__ entries, int nscan, int chunk)
+{
+    __shared__ uint32_t red[JENC_PACK_THREADS / 64];
+    const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s0 = blockIdx.x * chunk, s1 = min(s0 + chunk, nscan);
+    const uint32_t* c = cnt + (size_t)img * nscan;
+    uint32_t* tab = table + (size_t)img * (nscan + 1);
+    size_t base = 0;
+    for (int j = 0; j < img; ++j) base += totals[j];
+    uint32_t acc = 0;
+    for (int i = tid; i < s0; i += JENC_PACK_THREADS) acc += c[i];
+    acc = jenc_wave_scan(acc, lane);
+    if (lane == 63) red[wave] = acc;
+    __syncthreads();
+    uint32_t run = 0;
+    for (int k = 0; k < JENC_PACK_THREADS / 64; ++k) run += red[k];
+    __syncthreads();
+    for (int t0 = s0; t0 < s1; t0 += JENC_PACK_THREADS) {
+        const int i = t0 + tid;
+        const uint32_t v = i < s1 ? c[i] : 0u, incl = jenc_wave_scan(v, lane);
+        if (lane == 63) red[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, tile = 0;
+        for (int k = 0; k < JENC_PACK_THREADS / 64; ++k) { before += k < wave ? red[k] : 0u; tile += red[k]; }
+        if (i < s1) tab[i] = run + before + incl - v;
+        run += tile;
+        __syncthreads();
+    }
+    if (s1 == nscan && tid == 0) tab[nscan] = run;
+    __syncthreads();                                             // the table words of this chunk are read back below by their own workgroup (`table` is not __restrict__)
+    uint32_t* ent = entries + base;
+    const uint32_t room = totals[img];                           // what the host sized the image's entries by
+    for (int s = s0 + wave; s < s1; s += JENC_PACK_THREADS / 64) {
+        if (c[s] == 0u) continue;
+        const int v = dense[((size_t)img * nscan + s) * 64 + lane];
+        const unsigned long long nz = __ballot(v != 0);
+        const uint32_t at = tab[s] + __popcll(nz & ((1ull << lane) - 1ull));
+        if (v != 0 && at < room) ent[at] = (uint32_t)lane << 16 | (uint32_t)(uint16_t)v;
+    }
+}
+
+// ---- host: the batch call --------------------------------------------------------------------------------------------------
+struct SSJpegEnc {
+    struct Slot {
+        int16_t* dense = nullptr; size_t dense_cap = 0;         // device only: every block's 64 values
+        uint32_t* cnt = nullptr; size_t cnt_cap = 0;            // device only: every block's count
+        uint32_t* totals = nullptr;                             // [64] entries per image
+        uint32_t* h_totals = nullptr;                           // pinned
+        uint32_t* dev = nullptr; size_t dev_cap = 0;            // the stream: every image's block table, then every image's entries
+        void* host = nullptr; size_t host_cap = 0;              // its pinned host mirror (cacheable: the host threads read it)
+        hipEvent_t ev = nullptr;
+    } slot[2];
+    int next = 0;
+};
+
+void ss_jpeg_enc_free(SSJpegEnc* j)
+{
+    if (!j) return;
+    for (auto& st : j->slot) {
+        if (st.ev) (void)hipEventDestroy(st.ev);
+        if (st.host) (void)hipHostFree(st.host);
+        if (st.h_totals) (void)hipHostFree(st.h_totals);
+        if (st.dev) (void)hipFree(st.dev);
+        if (st.totals) (void)hipFree(st.totals);
+        if (st.cnt) (void)hipFree(st.cnt);
+        if (st.dense) (void)hipFree(st.dense);
+    }
+    delete j;
+}
+
+#define JECHK(x)                                                                                             \
+    do {                                                                                                     \
+        hipError_t e_ = (x);                                                                                 \
+        if (e_ != hipSuccess) { err = std::string("ss_jpeg_encode_batch: " #x ": ") + hipGetErrorString(e_); return SS_ERR_HIP; } \
+    } while (0)
+
+template <class T>
+static hipError_t jenc_grow(T*& p, size_t& cap, size_t bytes)
+{
+    if (cap >= bytes) return hipSuccess;
+    if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
+    const size_t want = bytes + bytes / 4;
+    hipError_t e = hipMalloc((void**)&p, want);
+    if (e == hipSuccess) cap = want;
+    return e;
+}
+
+// The arguments have been checked (ss_api.hip).  Returns an SS_* code, the message in err.
+int ss_jpeg_encode_impl(SSJpegEnc** state, hipStream_t stream, const void* d_in, long long in_frame_stride, int n, int height, int width, int rgb,
+                        int quality, int h_samp, int v_samp, int threads, unsigned char* const* out, size_t* out_size, std::string& err)
+{
+    try {
+        if (!*state) *state = new SSJpegEnc();
+        SSJpegEnc& S = **state;
+        const JEncShape shape(width, height, h_samp, v_samp);
+        const int nscan = shape.nscan;
+        JEncParams P;
+        jenc_quant(quality, P.q);
+        for (int t = 0; t < 2; ++t)
+            for (int k = 0; k < 64; ++k) P.recip[t][k] = (uint32_t)((1ull << 32) / ((uint32_t)P.q[t][k] << 3)) + 1u;
+        for (int k = 0; k < 64; ++k) P.zz[kZigzag[k]] = (uint8_t)k;
+        SSJpegEnc::Slot& st = S.slot[S.next];
+        if (!st.ev) JECHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+        if (!st.totals) JECHK(hipMalloc((void**)&st.totals, 64 * sizeof(uint32_t)));
+        if (!st.h_totals) JECHK(hipHostMalloc((void**)&st.h_totals, 64 * sizeof(uint32_t), hipHostMallocDefault));
+        JECHK(jenc_grow(st.dense, st.dense_cap, (size_t)n * nscan * 64 * sizeof(int16_t)));
+        JECHK(jenc_grow(st.cnt, st.cnt_cap, (size_t)n * nscan * sizeof(uint32_t)));
+        // ---- 1. transform; the entry totals decide the size of everything that follows ----
+        JECHK(hipMemsetAsync(st.totals, 0, n * sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(k_jpegenc_fdct, dim3((nscan + 31) / 32, n), dim3(256), 0, stream, (const uint8_t*)d_in, in_frame_stride, height, width, rgb, h_samp,
+                           v_samp, shape.mcux, nscan, st.dense, st.cnt, st.totals, P);
+        JECHK(hipGetLastError());
+        JECHK(hipMemcpyAsync(st.h_totals, st.totals, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        JECHK(hipEventRecord(st.ev, stream));
+        JECHK(hipEventSynchronize(st.ev));
+        size_t entries = 0;
+        std::vector<size_t> ent_at(n);
+        for (int i = 0; i < n; ++i) { ent_at[i] = entries; entries += st.h_totals[i]; }
+        const size_t tab_words = (size_t)n * (nscan + 1), bytes = (tab_words + entries) * 4;
+        JECHK(jenc_grow(st.dev, st.dev_cap, bytes));
+        if (st.host_cap < bytes) {
+            if (st.host) { JECHK(hipHostFree(st.host)); st.host = nullptr; st.host_cap = 0; }
+            const size_t cap = bytes + bytes / 4;
+            JECHK(hipHostMalloc(&st.host, cap, hipHostMallocDefault));
+            st.host_cap = cap;
+        }
+        // ---- 2. scan + compaction, ONE copy of exactly the used size ----
+        const int chunks = nscan < 16 * 2048 ? (nscan + 2047) / 2048 : 16, chunk = (nscan + chunks - 1) / chunks;
+        hipLaunchKernelGGL(k_jpegenc_pack, dim3(chunks, n), dim3(JENC_PACK_THREADS), 0, stream, st.dense, st.cnt, st.totals, st.dev, st.dev + tab_words, nscan,
+                           chunk);
+        JECHK(hipGetLastError());
+        JECHK(hipMemcpyAsync(st.host, st.dev, bytes, hipMemcpyDeviceToHost, stream));
+        JECHK(hipEventRecord(st.ev, stream));
+        JECHK(hipEventSynchronize(st.ev));
+        S.next ^= 1;
+        // ---- 3. the entropy stage, whole images per thread ----
+        const uint32_t* base = (const uint32_t*)st.host;
+        std::vector<char> bad(n, 0);
+        auto encode = [&](int t, int nt) {
+            for (int i = t; i < n; i += nt) {
+                const uint32_t* tab = base + (size_t)i * (nscan + 1);
+                const uint32_t* ent = base + tab_words + ent_at[i];
+                auto block = [tab, ent](int s, int, int, int, uint32_t*, const uint32_t*& e) { e = ent + tab[s]; return (int)(tab[s + 1] - tab[s]); };
+                if (!jenc_file(shape, P.q, block, out[i], &out_size[i])) bad[i] = 1;
+            }
+        };
+        if (!run_threads(threads < n ? threads : n, encode)) { err = "ss_jpeg_encode_batch: host encoding failed"; return SS_ERR_INVALID; }
+        for (int i = 0; i < n; ++i)
+            if (bad[i]) { err = "ss_jpeg_encode_batch: image " + std::to_string(i) + ": a coefficient beyond the baseline categories"; return SS_ERR_INVALID; }
+        return SS_OK;
+    } catch (...) {
+        err = "ss_jpeg_encode_batch: out of memory";
+        return SS_ERR_INVALID;
+    }
+}

@@ -154,6 +154,32 @@ class TrackerEngine:
         self._ck(self.L.ss_jpeg_decode_batch(self.ctx, self._st(stream), data, sizes, n, shape[0], shape[1], _ptr(dst), stride, int(bool(rgb)),
                                              int(threads)))
 
+    def jpeg_encode_batch(self, src: torch.Tensor, quality: int = 85, subsampling: str = "4:2:0", stream=None, threads: int = 4, rgb: bool = False):
+        """src: device uint8 [n, H, W, 3] (n 1 .. 64, every frame contiguous) or [H, W, 3], BGR (rgb=True: RGB) -> n baseline JPEG
+        files as bytes, equal to what Pillow writes at that quality and subsampling ("4:2:0" | "4:2:2" | "4:4:4"): colour
+        conversion, downsampling, forward DCT, quantisation and compaction on the device (csrc/ss_jpeg_enc.hip), the sparse
+        coefficients back in one copy, Huffman coding on `threads` host threads.  Returns when the files are written."""
+        from .jpeg import SUBSAMPLING
+        if subsampling not in SUBSAMPLING:
+            raise ValueError(f"jpeg_encode_batch: subsampling {subsampling!r} (one of {', '.join(SUBSAMPLING)})")
+        hs, vs = SUBSAMPLING[subsampling]
+        fr = src if src.dim() == 4 else src.unsqueeze(0)
+        if (fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.device != self.device or not fr[0].is_contiguous()
+                or (fr.shape[0] > 1 and fr.stride(0) < fr[0].numel())):
+            raise ValueError("jpeg_encode_batch: a uint8 [n, H, W, 3] tensor on the engine's device, every frame contiguous")
+        n, H, W = (int(v) for v in fr.shape[:3])
+        bound = int(self.L.ss_jpeg_encode_bound(W, H, hs, vs))
+        if bound < 0:
+            _lib.check(None, bound)                                       # (a host-only entry point: its message is the library's, not the context's)
+        files = np.empty((max(n, 1), bound), np.uint8)                    # (untouched pages cost nothing: a file fills a small part of its bound)
+        out = (C.c_void_p * max(n, 1))(*[files[i].ctypes.data for i in range(n)])
+        cap = (C.c_size_t * max(n, 1))(*([bound] * n))
+        size = (C.c_size_t * max(n, 1))()
+        stride = fr.stride(0) if n > 1 else H * W * 3
+        self._ck(self.L.ss_jpeg_encode_batch(self.ctx, self._st(stream), _ptr(fr), stride, n, H, W, int(bool(rgb)), int(quality), hs, vs, int(threads),
+                                             out, cap, size))
+        return [files[i, :size[i]].tobytes() for i in range(n)]
+
     def download(self, dst: np.ndarray, src: torch.Tensor, stream=None):
         """Device tensor -> host array (synchronous)."""
         if dst.nbytes != src.numel() * src.element_size() or not src.is_contiguous() or not dst.flags["C_CONTIGUOUS"]:

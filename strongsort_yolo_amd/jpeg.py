@@ -1,10 +1,11 @@
-"""Encoded frames: baseline JPEG decoded on the device (csrc/ss_jpeg.hip, docs/JPEG.md).
+"""Encoded frames: baseline JPEG decoded on the device (csrc/ss_jpeg.hip) and written from frames on the device (csrc/ss_jpeg_enc.hip); docs/JPEG.md.
 
     H, W, components, (h, v) = probe(data)          host only
     f = EncodedFrame(data)                          .shape == (H, W, 3); ValueError with the library's message when refused
     for f in split_mjpeg("clip.mjpeg"): ...         a raw concatenated MJPEG file, no container parsing
     for b in split_bytes(buf): ...                  the same cut on bytes, yielding each frame's bytes unprobed
     t = decode(engine, frames)                      uint8 device tensor [n, H, W, 3], BGR (rgb=True: RGB)
+    files = encode(engine, frames, quality=85)      frames on the device (or host arrays) -> baseline JPEG files as bytes (csrc/ss_jpeg_enc.hip)
 
 `YOLO.track_stream` takes EncodedFrames in place of arrays: the group is decoded straight into the buffer the detector reads.
 """
@@ -17,6 +18,7 @@ from typing import Iterator, Union
 from . import lib
 
 MAX_BATCH = 64
+SUBSAMPLING = {"4:2:0": (2, 2), "4:2:2": (2, 1), "4:4:4": (1, 1)}       # luma sampling factors (h, v); chroma is 1 x 1
 
 
 def probe(data):
@@ -107,4 +109,28 @@ def decode(engine, frames, out=None, rgb: bool = False, stream=None, threads: in
         out = torch.empty((len(frames),) + frames[0].shape, dtype=torch.uint8, device=engine.device)
     for k in range(0, len(frames), MAX_BATCH):
         engine.jpeg_decode_batch(out[k:k + MAX_BATCH], frames[k:k + MAX_BATCH], stream, threads, rgb)
+    return out
+
+
+def encode(engine, frames, quality: int = 85, subsampling: str = "4:2:0", stream=None, threads: int = 4, rgb: bool = False):
+    """Any number of frames of one size -> list of baseline JPEG files (bytes), byte for byte what Pillow writes with
+    `quality=quality, subsampling=subsampling`.  `frames`: a uint8 tensor [n, H, W, 3] (or a sequence of [H, W, 3] tensors / arrays),
+    BGR unless rgb=True; what is not on the engine's device yet is uploaded first.  Encoded in chunks of MAX_BATCH."""
+    import numpy as np
+    import torch
+    if not isinstance(frames, (torch.Tensor, np.ndarray)):
+        frames = list(frames)
+        if not frames:
+            raise ValueError("jpeg.encode: no frames")
+        frames = torch.stack(list(frames)) if isinstance(frames[0], torch.Tensor) else np.stack(frames)
+    if isinstance(frames, np.ndarray):
+        frames = torch.from_numpy(np.ascontiguousarray(frames))
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.shape[0] == 0:
+        raise ValueError("jpeg.encode: no frames")
+    frames = frames.to(engine.device).contiguous()
+    out = []
+    for k in range(0, frames.shape[0], MAX_BATCH):
+        out += engine.jpeg_encode_batch(frames[k:k + MAX_BATCH], quality, subsampling, stream, threads, rgb)
     return out

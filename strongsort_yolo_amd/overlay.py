@@ -222,10 +222,15 @@ class Overlay:
         self._keep.append((d_prims, d_off, d_chars))
         return frames
 
+    def annotate_resident(self, dev_frame: torch.Tensor, results, counts: Optional[dict] = None, fps_text: str = "", stream=None) -> torch.Tensor:
+        """A frame that is ALREADY on the device (uint8 [H,W,3]) annotated in place and returned still on the device: what a
+        device-side consumer (the JPEG sink, cli.FrameSink.write_device) takes; no transfer of the frame in either direction."""
+        return self.draw_device(dev_frame, [self.commands(results, counts, fps_text)], stream)
+
     def draw_resident(self, dev_frame: torch.Tensor, results, counts: Optional[dict] = None, fps_text: str = "") -> np.ndarray:
         """A frame that is ALREADY on the device (uint8 [H,W,3], e.g. `Results.orig_img_device` of track_stream) -> annotated
         host frame: ss_overlay in place, one download, no upload of the frame."""
-        self.draw_device(dev_frame, [self.commands(results, counts, fps_text)])
+        self.annotate_resident(dev_frame, results, counts, fps_text)
         out = np.empty(tuple(dev_frame.shape), np.uint8)
         self.eng.download(out, dev_frame)
         return out
