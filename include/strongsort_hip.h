@@ -620,6 +620,26 @@ int ss_jpeg_coefficients(const unsigned char* data, size_t size, short* coef, si
 int ss_jpeg_decode_batch(ss_ctx* ctx, void* hip_stream, const unsigned char* const* data, const size_t* sizes, int n, int height,
                          int width, void* d_out, long long out_frame_stride, int rgb, int threads);
 
+/* The same call with the entropy stage on the device (docs/JPEG.md section 12): the host parses the headers and copies the scan's
+ * bytes (stuffing dropped, cut at the restart markers); two more kernels decode the Huffman code.  Same arguments, same checks,
+ * same pixels.  The one difference: damage that only the scan shows (a code that does not exist, a bad DC category, an index beyond
+ * 63, data that ends early, bytes left over before a restart marker) is found on the device: the frame is written as if all its
+ * blocks were empty and SS_ERR_INVALID, naming the image and the cause, is returned by the next ss_check_errors or by the next
+ * decode call that reuses the call's staging slot (there are two), whichever comes first.  Not capturable. */
+int ss_jpeg_decode_batch_device(ss_ctx* ctx, void* hip_stream, const unsigned char* const* data, const size_t* sizes, int n, int height,
+                                int width, void* d_out, long long out_frame_stride, int rgb, int threads);
+/* Host only (no GPU, no context): the host's share of that call for one file.  bytes: the scan without the 00 after every FF, cut
+ * at the RSTn markers into segments, each padded with zeros to 4 bytes; segments: per segment {byte offset, byte length, first
+ * block in scan order, blocks}; header: the 160 words of section 3 (the call's offsets zero; may be NULL).  With bytes == NULL only
+ * *bytes_used (the capacity to bring) and *n_segments are written.  Header refusals and "bad restart marker" as ss_jpeg_decode_batch. */
+int ss_jpeg_scan_segments(const unsigned char* data, size_t size, unsigned char* bytes, size_t bytes_cap, size_t* bytes_used, unsigned int* segments,
+                          size_t seg_cap, int* n_segments, unsigned int* header);
+/* The device entropy stage alone on one image, for known-answer tests: dense blocks in ss_jpeg_coefficients' layout (synchronous;
+ * the stream is expanded on the host).  ss_jpeg_device_rounds: the speculation rounds each 1024-lane tile of that image took
+ * (returns the number of tiles, writes at most cap). */
+int ss_jpeg_device_coefficients(ss_ctx* ctx, const unsigned char* data, size_t size, short* coef, size_t coef_cap);
+int ss_jpeg_device_rounds(ss_ctx* ctx, int* rounds, int cap);
+
 /* ---- frames on the device written as baseline JPEG files (csrc/ss_jpeg_enc.hip, docs/JPEG.md "Encoding") ---- */
 /* The files equal what libjpeg-turbo's defaults write (JDCT_ISLOW, the Annex K Huffman tables, JFIF header) byte for byte: YCbCr
  * with luma sampling h_samp x v_samp = 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4), quality 1 .. 100, sides 1 .. 8192.

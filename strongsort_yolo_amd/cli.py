@@ -372,6 +372,8 @@ def process_video(args: dict, model=None) -> dict:
         # a file / synthetic source can supply frames ahead: groups of `batch` frames through the overlapped pipeline
         # (same rows as frame-by-frame model.track; --batch 1 keeps the reference's per-frame call, :41)
         kw = {"keep_device_frames": True} if sink is not None else {}
+        if args.get("device_entropy", False):
+            kw["jpeg_entropy"] = "device"
         for res in model.track_stream(src, batch=batch, device=args.get("device", 0), **kw):
             emit(res[0].orig_img, res)
         src = ()
@@ -440,6 +442,8 @@ def main(argv=None):
     p.add_argument("--device-decode", action="store_true",
                    help="JPEG directories and raw .mjpeg files: decode baseline JPEG on the device (Huffman on host threads, the rest in "
                         "csrc/ss_jpeg.hip; same pixels as Pillow, docs/JPEG.md); needs --track and --batch > 1")
+    p.add_argument("--device-entropy", action="store_true",
+                   help="--device-decode: decode the Huffman code on the device too (docs/JPEG.md §12); the host only parses headers and copies the scans")
     p.add_argument("--device-masks", action="store_true", help="segmentation models: assemble masks and trace their outlines on the device (csrc/ss_mask.hip) instead of on the host")
     a = p.parse_args(argv)
     if a.camera_motion and a.tracker == "bytetrack":
@@ -460,6 +464,8 @@ def main(argv=None):
         p.error("--reid-model is a model for BoT-SORT's ReID branch: it needs --with-reid")
     if a.reid_model == "auto" and a.reid_weights:
         p.error("--reid-model auto reads the detector's own features: --reid-weights does not apply")
+    if a.device_entropy and not a.device_decode:
+        p.error("--device-entropy is a stage of the device JPEG decoder: it needs --device-decode")
     if a.device_decode:
         if not a.track or a.batch <= 1:
             p.error("--device-decode feeds the grouped tracking path: it needs --track and --batch > 1")
@@ -474,7 +480,7 @@ def main(argv=None):
             p.error(f"--device-encode: --save '{a.save}' must be a .mjpeg / .mjpg file or a directory (a path ending in '/' or an existing directory)")
         if not 1 <= a.save_quality <= 100:
             p.error("--save-quality must be 1 .. 100")
-    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "device_decode": a.device_decode,
+    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "device_decode": a.device_decode, "device_entropy": a.device_entropy,
              "device_encode": a.device_encode, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
              "save": _save_path(a, i)}
             for i, s in enumerate(a.source)]

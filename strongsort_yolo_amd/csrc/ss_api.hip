@@ -54,6 +54,10 @@ int  ss_jpeg_probe_impl(const unsigned char*, size_t, int*, int*, int*, int*, in
 int  ss_jpeg_coefficients_impl(const unsigned char*, size_t, short*, size_t, unsigned short*, std::string&);
 int  ss_jpeg_decode_impl(SSJpeg**, hipStream_t, const unsigned char* const*, const size_t*, int, int, int, void*, long long, int, int, std::string&);
 void ss_jpeg_free(SSJpeg*);
+int  ss_jpeg_scan_segments_impl(const unsigned char*, size_t, unsigned char*, size_t, size_t*, unsigned int*, size_t, int*, unsigned int*, std::string&);
+int  ss_jpeg_decode_device_impl(SSJpeg**, hipStream_t, const unsigned char* const*, const size_t*, int, int, int, void*, long long, int, int, short*, size_t, std::string&);
+int  ss_jpeg_pending_impl(SSJpeg*, std::string&);
+int  ss_jpeg_device_rounds_impl(SSJpeg*, int*, int);
 struct SSJpegEnc;                       // ss_jpeg_enc.hip
 size_t ss_jpeg_encode_bound_impl(int, int, int, int);
 int  ss_jpeg_entropy_encode_impl(const short*, int, int, int, int, int, unsigned char*, size_t*, std::string&);
@@ -387,6 +391,43 @@ extern "C" int ss_jpeg_decode_batch(ss_ctx* c, void* hip_stream, const unsigned 
     std::string err;
     const int rc = ss_jpeg_decode_impl(&c->jpeg, (hipStream_t)hip_stream, data, sizes, n, height, width, d_out, out_frame_stride, rgb, threads, err);
     return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+// The entropy stage on the device (docs/JPEG.md section 12): ss_jpeg_decode_batch's arguments and checks
+extern "C" int ss_jpeg_decode_batch_device(ss_ctx* c, void* hip_stream, const unsigned char* const* data, const size_t* sizes, int n, int height,
+                                           int width, void* d_out, long long out_frame_stride, int rgb, int threads)
+{
+    if (!c || !data || !sizes || !d_out) return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch_device: null argument");
+    if (n < 1 || n > 64 || threads < 1 || threads > 16 || height < 1 || height > 8192 || width < 1 || width > 8192 || (rgb != 0 && rgb != 1) ||
+        out_frame_stride < (long long)height * width * 3)
+        return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch_device: 1 <= n <= 64, 1 <= threads <= 16, sides 1 .. 8192, rgb 0 / 1, out_frame_stride >= height * width * 3");
+    for (int i = 0; i < n; ++i) if (!data[i] || !sizes[i]) return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch_device: image " + std::to_string(i) + ": no data");
+    std::string err;
+    const int rc = ss_jpeg_decode_device_impl(&c->jpeg, (hipStream_t)hip_stream, data, sizes, n, height, width, d_out, out_frame_stride, rgb, threads, nullptr, 0, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+extern "C" int ss_jpeg_scan_segments(const unsigned char* data, size_t size, unsigned char* bytes, size_t bytes_cap, size_t* bytes_used, unsigned int* segments,
+                                     size_t seg_cap, int* n_segments, unsigned int* header)
+{
+    if (!data || !size || !bytes_used || !n_segments || (bytes && !segments)) return fail(nullptr, SS_ERR_INVALID, "ss_jpeg_scan_segments: null argument");
+    std::string err;
+    const int rc = ss_jpeg_scan_segments_impl(data, size, bytes, bytes_cap, bytes_used, segments, seg_cap, n_segments, header, err);
+    return rc == SS_OK ? rc : fail(nullptr, rc, "ss_jpeg_scan_segments: " + err);
+}
+
+extern "C" int ss_jpeg_device_coefficients(ss_ctx* c, const unsigned char* data, size_t size, short* coef, size_t coef_cap)
+{
+    if (!c || !data || !size || !coef) return fail(c, SS_ERR_INVALID, "ss_jpeg_device_coefficients: null argument");
+    std::string err;
+    const int rc = ss_jpeg_decode_device_impl(&c->jpeg, c->stream, &data, &size, 1, 0, 0, nullptr, 0, 0, 1, coef, coef_cap, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+extern "C" int ss_jpeg_device_rounds(ss_ctx* c, int* rounds, int cap)
+{
+    if (!c || (!rounds && cap > 0) || cap < 0) return fail(c, SS_ERR_INVALID, "ss_jpeg_device_rounds: bad argument");
+    return ss_jpeg_device_rounds_impl(c->jpeg, rounds, cap);
 }
 
 // ---- N3 frame sink: baseline JPEG (ss_jpeg_enc.hip) --------------------------------------------------------
@@ -911,6 +952,10 @@ extern "C" int ss_check_errors(ss_ctx* c)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (size_t s = 0; s < e.size(); ++s)
             if (e[s]) return fail(c, e[s], "BYTE tracker: device error flag on stream " + std::to_string(s));
+    }
+    {                                                        // images a device-entropy JPEG call refused (docs/JPEG.md section 12)
+        std::string err;
+        if (int rcj = ss_jpeg_pending_impl(c->jpeg, err)) return fail(c, rcj, err);
     }
     for (int u = 0; u < c->nms_units; ++u) {                 // NMS candidate overflow (flag stays set until ss_reset)
         int f = 0;

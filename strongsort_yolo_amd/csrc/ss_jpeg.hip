@@ -9,6 +9,7 @@
 //   k_jpeg_pixels  a lane makes 4 consecutive pixels of the flat HWC image (12 bytes = 3 dwords): fancy chroma upsampling from
 //                  the planes (neighbours across block borders included), YCbCr -> BGR / RGB, the store
 // Every value is an integer; the results equal libjpeg-turbo's defaults (JDCT_ISLOW, fancy upsampling) bit for bit.
+// On request the entropy-coded scan is decoded on the device as well (ss_jpeg_decode_batch_device: the second half of this file).
 #include <cstring>
 #include <string>
 #include <vector>
@@ -460,8 +461,11 @@ struct SSJpeg {
         uint32_t* dev = nullptr; size_t dev_cap = 0;            // its device mirror
         uint8_t* planes = nullptr; size_t planes_cap = 0;       // component planes of the call's images
         hipEvent_t ev = nullptr; bool busy = false;
+        uint32_t *status_dev = nullptr, *status_host = nullptr;  // device entropy stage: a status word per image and its pinned copy
+        int pending = 0;                                        // images whose status arrives with `ev` (0: the call was a host-stage one)
     } slot[2];
     int next = 0;
+    std::vector<int> rounds;                                    // ss_jpeg_device_coefficients: rounds each tile of its image took
     struct Image { JInfo J; std::vector<uint32_t> tab, ent; std::string err; bool ok = false; size_t tab_at = 0, ent_at = 0; };
     std::vector<Image> img;
 };
@@ -474,6 +478,8 @@ void ss_jpeg_free(SSJpeg* j)
         if (st.host) (void)hipHostFree(st.host);
         if (st.dev) (void)hipFree(st.dev);
         if (st.planes) (void)hipFree(st.planes);
+        if (st.status_dev) (void)hipFree(st.status_dev);
+        if (st.status_host) (void)hipHostFree(st.status_host);
     }
     delete j;
 }
@@ -483,6 +489,8 @@ void ss_jpeg_free(SSJpeg* j)
         hipError_t e_ = (x);                                                                                 \
         if (e_ != hipSuccess) { err = std::string("ss_jpeg_decode_batch: " #x ": ") + hipGetErrorString(e_); return SS_ERR_HIP; } \
     } while (0)
+
+static int jpeg_slot_wait(SSJpeg::Slot& st, std::string& err);
 
 // The arguments have been checked (ss_api.hip).  Returns an SS_* code, the message in err.
 int ss_jpeg_decode_impl(SSJpeg** state, hipStream_t stream, const unsigned char* const* data, const size_t* sizes, int n, int height, int width,
@@ -533,7 +541,7 @@ int ss_jpeg_decode_impl(SSJpeg** state, hipStream_t stream, const unsigned char*
         const size_t bytes = at * 4;
         const size_t plane_slot = 3 * (size_t)((width + 15) / 16 * 16) * ((height + 15) / 16 * 16), planes_bytes = plane_slot * n;
         SSJpeg::Slot& st = S.slot[S.next];
-        if (st.busy) { JCHK(hipEventSynchronize(st.ev)); st.busy = false; }
+        if (int rcw = jpeg_slot_wait(st, err)) return rcw;       // (a device-entropy call that used this slot may have refused an image)
         if (!st.ev) JCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
         if (st.host_cap < bytes) {
             if (st.host) { JCHK(hipHostFree(st.host)); st.host = nullptr; st.host_cap = 0; }
@@ -591,4 +599,624 @@ int ss_jpeg_decode_impl(SSJpeg** state, hipStream_t stream, const unsigned char*
         err = "ss_jpeg_decode_batch: out of memory";
         return SS_ERR_INVALID;
     }
+}
+
+// ============================================================================================================================
+// The entropy stage on the device (docs/JPEG.md section 12; tests/jpeg_huff_ref.py is the same algorithm in NumPy).
+//
+// The host keeps what is serial and cheap per file: the headers, the Huffman look-up tables and ONE pass over the scan that drops
+// the stuffing bytes and cuts the scan at its restart markers into segments.  The entropy-coded bytes cross PCIe; two kernels make
+// section 3's stream (block table + entries) in device memory, k_jpeg_idct and k_jpeg_pixels read it unchanged.
+//   k_jpeg_huff   a workgroup per image, 1024 lanes, a lane per subsequence of W dwords of a segment: speculative decoding until
+//                 every lane's entry state equals its left neighbour's exit state, a scan of the block and entry counts, then the
+//                 pass that stores the block table and the entries (the DC slot of a block holds the raw DC difference)
+//   k_jpeg_dc     per image and component the running sum of the DC differences, restarted at every segment; a refused image
+//                 gets a block table of zeros instead (every block empty)
+// Header words of the device stage (beside section 3's, which end at [16], the third component's pitch):  [17] segments  [18] scan
+// bytes (dword index)  [19] Huffman tables (dword index; component c: DC at 2 c, AC at 2 c + 1)  [20] lanes  [21] entry capacity
+// [22] rounds read-out (dword index, one per tile)  [23] W  [24] MCUs per segment  [25] segment table (dword index)
+#define JH_TAB 344                      // dwords of a Huffman table: fast[512] uint16 | maxcode, mincode, valptr of the lengths 10 .. 16 (8 dwords each) | vals[256] uint8
+#define JH_SEG 5                        // dwords of a segment: byte offset in the image's scan bytes, byte length, first block, blocks, first lane
+#define JH_LANES 1024
+#define JH_OK 0xffffffffu
+enum { JE_CODE = 1, JE_DCCAT = 2, JE_INDEX = 3, JE_ENDS = 4, JE_RST = 5, JE_CAP = 6 };
+static const char* const kJpegCause[7] = {"", "Huffman code that does not exist", "bad DC category", "coefficient index beyond 63", "data ends before the last MCU",
+                                          "bad restart marker", "more entries than the scan's length allows"};
+
+int g_opt_jpeg_subseq_words = 32;       // ss_op_set_option "jpeg_subseq_words": 4, 8, 16 or 32 dwords of scan per lane
+
+__constant__ uint8_t d_jpeg_zigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                                          35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+struct JhLane {                          // what a lane knows about its subsequence
+    const uint32_t* w;                  // the segment's bytes (dwords, bytes in stream order)
+    uint32_t nw;                        // dwords of the segment (padded length / 4): reads beyond supply zero bits
+    uint32_t bits;                      // 8 * byte length: real data ends here
+    uint32_t end;                       // symbols that start before this bit are the lane's
+    int hv, bpm;                        // luma blocks per MCU, blocks per MCU
+};
+
+struct JhSink {                          // the storing pass
+    uint32_t *tab, *ent;
+    uint32_t e, cap;                    // next entry, capacity
+    uint32_t blk, bend;                 // next block to begin (image-wide scan index), the segment's end
+    bool last_seg;
+    uint32_t err;
+};
+
+// Decodes from (p, bi, k) every symbol that starts before L.end, beginning at most `maxbegin` blocks.  Total: a code that does not
+// exist consumes one bit, a DC category above 15 keeps its low four bits, a run beyond index 63 closes the block.
+template <bool WRITE>
+__device__ __forceinline__ void jh_decode(const uint32_t* tabs, const JhLane& L, uint32_t& p, uint32_t& bi, uint32_t& k, int maxbegin, uint32_t& nb, uint32_t& ne,
+                                          uint32_t& nel, JhSink& S)
+{
+    nb = 0; ne = 0; nel = 0;
+    uint32_t ci = 0xffffffffu, ca = 0, cb = 0;
+    while (p < L.end) {
+        if (k == 0 && (int)nb >= maxbegin) break;
+        const uint32_t i = p >> 5, sh = p & 31u;
+        if (i != ci) {
+            ci = i;
+            ca = i < L.nw ? __builtin_bswap32(L.w[i]) : 0u;
+            cb = i + 1 < L.nw ? __builtin_bswap32(L.w[i + 1]) : 0u;
+        }
+        const uint32_t win = sh ? (ca << sh) | (cb >> (32u - sh)) : ca;
+        const uint32_t comp = (int)bi < L.hv ? 0u : bi - (uint32_t)L.hv + 1u;
+        const uint32_t* T = tabs + (2u * comp + (k ? 1u : 0u)) * JH_TAB;
+        const uint32_t f = ((const uint16_t*)T)[win >> 23];
+        uint32_t len = f >> 8, sym = f & 255u;
+        if (!f) {
+#pragma unroll
+            for (int ln = 10; ln <= 16; ++ln) {
+                const uint32_t code = win >> (32 - ln), mn = T[264 + ln - 10];
+                if (!len && (int)code <= (int)T[256 + ln - 10] && code >= mn) { len = ln; sym = ((const uint8_t*)(T + 280))[(T[272 + ln - 10] + code - mn) & 255u]; }
+            }
+            if (!len) {
+                if (WRITE && !S.err) S.err = L.bits - p < 16u ? JE_ENDS : JE_CODE;
+                ++p;
+                continue;
+            }
+        }
+        bool close = false;
+        if (k == 0) {
+            uint32_t s = sym;
+            if (s > 15u) { if (WRITE && !S.err) S.err = JE_DCCAT; s &= 15u; }
+            uint32_t v = 0;
+            if (s) { v = (win << len) >> (32u - s); if (v < (1u << (s - 1u))) v = v - (1u << s) + 1u; }
+            nel = ne;
+            if (WRITE) {
+                if (S.e < S.cap) { S.tab[S.blk] = S.e; S.ent[S.e] = v & 0xffffu; }
+                else if (!S.err) S.err = JE_CAP;
+                ++S.blk; ++S.e;
+            }
+            ++nb; ++ne;
+            p += len + s;
+            k = 1;
+        } else {
+            const uint32_t r = sym >> 4, s = sym & 15u;
+            if (!s) {
+                p += len;
+                if (r == 15u) { k += 16u; close = k > 63u; }
+                else close = true;
+            } else {
+                k += r;
+                if (k > 63u) {
+                    if (WRITE && !S.err) S.err = JE_INDEX;
+                    p += len;
+                    close = true;
+                } else {
+                    uint32_t v = (win << len) >> (32u - s);
+                    if (v < (1u << (s - 1u))) v = v - (1u << s) + 1u;
+                    if (WRITE) {
+                        if (S.e < S.cap) S.ent[S.e] = (uint32_t)d_jpeg_zigzag[k] << 16 | (v & 0xffffu);
+                        else if (!S.err) S.err = JE_CAP;
+                        ++S.e;
+                    }
+                    ++ne;
+                    p += len + s;
+                    close = ++k == 64u;
+                }
+            }
+        }
+        if (close) {
+            k = 0;
+            bi = (int)bi + 1 == L.bpm ? 0u : bi + 1u;
+            if (WRITE && S.blk == S.bend) {                      // the segment's last block: what is left over?
+                if (p > L.bits) { if (!S.err) S.err = JE_ENDS; }
+                else if (!S.last_seg && L.bits - p >= 8u) { if (!S.err) S.err = JE_RST; }
+                break;
+            }
+        }
+    }
+}
+
+// inclusive sum over the workgroup's 1024 lanes (two barriers)
+__device__ __forceinline__ uint32_t jh_scan(uint32_t v, uint32_t* wsum, uint32_t& total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(v, d, 64);
+        if (lane >= d) v += t;
+    }
+    if (lane == 63) wsum[wv] = v;
+    __syncthreads();
+    uint32_t off = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { const uint32_t t = wsum[i]; if (i < wv) off += t; tot += t; }
+    __syncthreads();
+    total = tot;
+    return v + off;
+}
+
+// grid (images), 1024 threads
+__global__ __launch_bounds__(JH_LANES) void k_jpeg_huff(uint32_t* __restrict__ s, uint32_t* __restrict__ status)
+{
+    __shared__ uint32_t tabs[6 * JH_TAB];
+    __shared__ uint32_t xp[JH_LANES], xs[JH_LANES], sc[JH_LANES];
+    __shared__ uint32_t wsum[16], bc[1];
+    const uint32_t* hdr = s + (size_t)blockIdx.x * JPEG_HDR;
+    const int tid = threadIdx.x, ncomp = (int)hdr[0];
+    const uint32_t blocks = hdr[4], nseg = hdr[17], lanes = hdr[20], W = hdr[23];
+    const uint32_t* segs = s + hdr[25];
+    const uint32_t* scan = s + hdr[18];
+    uint32_t* rounds_out = s + hdr[22];
+    for (int i = tid; i < ncomp * 2 * JH_TAB; i += JH_LANES) tabs[i] = s[hdr[19] + i];
+    JhLane L;
+    L.hv = ncomp == 1 ? 1 : (int)(hdr[1] * hdr[2]);
+    L.bpm = ncomp == 1 ? 1 : L.hv + 2;
+    JhSink S;
+    S.tab = s + hdr[5]; S.ent = s + hdr[6]; S.cap = hdr[21];
+    uint32_t cp = 0, cbk = 0, cblk = 0, cent = 0;               // carried from tile to tile: exit state, blocks begun in the open segment, entries
+    __syncthreads();
+    for (uint32_t tile0 = 0, t = 0; tile0 < lanes; tile0 += JH_LANES, ++t) {
+        const uint32_t g = tile0 + tid, nl = lanes - tile0 < JH_LANES ? lanes - tile0 : JH_LANES;
+        const bool active = g < lanes;
+        uint32_t lane0 = 0, seg_blk0 = 0, seg_nblk = 0, j = 0;
+        bool lastlane = false;
+        L.w = scan; L.nw = 0; L.bits = 0; L.end = 0;
+        if (active) {
+            uint32_t lo = 0, hi = nseg - 1;
+            for (int it = 0; it < 32 && lo < hi; ++it) {         // the last segment whose first lane is <= g
+                const uint32_t mid = (lo + hi + 1) >> 1;
+                if (segs[mid * JH_SEG + 4] <= g) lo = mid; else hi = mid - 1;
+            }
+            const uint32_t* sg = segs + lo * JH_SEG;
+            const uint32_t len = sg[1];
+            lane0 = sg[4]; seg_blk0 = sg[2]; seg_nblk = sg[3];
+            j = g - lane0;
+            L.w = scan + (sg[0] >> 2);
+            L.nw = (len + 3) >> 2;
+            L.bits = len << 3;
+            const uint32_t e1 = (j + 1) * 32u * W;
+            L.end = e1 < L.bits ? e1 : L.bits;
+            lastlane = (lo + 1 == nseg ? lanes : sg[JH_SEG + 4]) == g + 1;
+            S.last_seg = lo + 1 == nseg;
+        }
+        // ---- speculation: round 0 from the guess, then from the left neighbour's exit state while it differs ----
+        const bool exact = j == 0 || tid == 0;
+        uint32_t ep = j * 32u * W, ebk = 0;
+        if (j != 0 && tid == 0) { ep = cp; ebk = cbk; }
+        uint32_t p = ep, bi = ebk >> 8, k = ebk & 255u, nb = 0, ne = 0, nel = 0;
+        if (active) jh_decode<false>(tabs, L, p, bi, k, 0x7fffffff, nb, ne, nel, S);
+        xp[tid] = p; xs[tid] = bi << 8 | k;
+        __syncthreads();
+        uint32_t rounds = 1;
+        for (uint32_t r = 1; r < nl; ++r) {                      // counted: lane i is final after i rounds
+            uint32_t np = 0, nbk = 0;
+            bool redo = false;
+            if (active && !exact) { np = xp[tid - 1]; nbk = xs[tid - 1]; redo = np != ep || nbk != ebk; }
+            if (!__syncthreads_or(redo)) break;
+            ++rounds;
+            if (redo) {
+                ep = np; ebk = nbk;
+                p = ep; bi = ebk >> 8; k = ebk & 255u;
+                jh_decode<false>(tabs, L, p, bi, k, 0x7fffffff, nb, ne, nel, S);
+                xp[tid] = p; xs[tid] = bi << 8 | k;
+            }
+            __syncthreads();
+        }
+        if (tid == 0) rounds_out[t] = rounds;
+        // ---- where the lane's blocks and entries go ----
+        uint32_t total;
+        const uint32_t bex = jh_scan(nb, wsum, total) - nb;
+        sc[tid] = bex;
+        __syncthreads();
+        const uint32_t b0 = bex - sc[lane0 > tile0 ? lane0 - tile0 : 0] + (lane0 < tile0 ? cblk : 0u);
+        if (tid == JH_LANES - 1) bc[0] = b0 + nb;
+        const int maxbegin = b0 > seg_nblk ? -1 : (int)(seg_nblk - b0);
+        if (!active || maxbegin < 0) { nb = 0; ne = 0; }
+        else if ((int)nb > maxbegin) {                           // the segment's blocks end inside this lane
+            if ((int)nb == maxbegin + 1) { nb = (uint32_t)maxbegin; ne = nel; }
+            else {
+                p = ep; bi = ebk >> 8; k = ebk & 255u;
+                jh_decode<false>(tabs, L, p, bi, k, maxbegin, nb, ne, nel, S);
+            }
+        }
+        const uint32_t e0 = cent + jh_scan(ne, wsum, total) - ne;
+        // ---- the storing pass ----
+        if (active && maxbegin >= 0) {
+            S.e = e0; S.blk = seg_blk0 + b0; S.bend = seg_blk0 + seg_nblk; S.err = 0;
+            p = ep; bi = ebk >> 8; k = ebk & 255u;
+            uint32_t wb, we, wl;
+            jh_decode<true>(tabs, L, p, bi, k, maxbegin, wb, we, wl, S);
+            if (lastlane && !S.err && !(S.blk == S.bend && k == 0)) S.err = JE_ENDS;
+            if (S.err) atomicMin(status + blockIdx.x, (g + 1u) << 3 | S.err);
+        }
+        __syncthreads();
+        cp = xp[JH_LANES - 1]; cbk = xs[JH_LANES - 1]; cblk = bc[0]; cent += total;
+        __syncthreads();
+    }
+    if (tid == 0) S.tab[blocks] = cent;
+}
+
+// grid (images), 1024 threads: a lane per MCU, 1024 MCUs at a time
+__global__ __launch_bounds__(JH_LANES) void k_jpeg_dc(uint32_t* __restrict__ s, const uint32_t* __restrict__ status)
+{
+    __shared__ uint32_t wv_v[3][16], wv_f[16];
+    const uint32_t* hdr = s + (size_t)blockIdx.x * JPEG_HDR;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, ncomp = (int)hdr[0];
+    const uint32_t blocks = hdr[4], cap = hdr[21];
+    uint32_t* tab = s + hdr[5];
+    uint32_t* ent = s + hdr[6];
+    if (status[blockIdx.x] != JH_OK) {                           // refused: every block empty
+        for (uint32_t i = tid; i <= blocks; i += JH_LANES) tab[i] = 0u;
+        return;
+    }
+    const int hv = ncomp == 1 ? 1 : (int)(hdr[1] * hdr[2]), bpm = ncomp == 1 ? 1 : hv + 2;
+    const uint32_t nm = blocks / (uint32_t)bpm, ri = hdr[24];
+    uint32_t carry[3] = {0u, 0u, 0u};
+    for (uint32_t m0 = 0; m0 < nm; m0 += JH_LANES) {
+        const uint32_t m = m0 + tid;
+        const bool active = m < nm;
+        uint32_t f = active && m % ri == 0u ? 1u : 0u, v[3] = {0u, 0u, 0u}, d[4] = {0u, 0u, 0u, 0u}, at[6] = {cap, cap, cap, cap, cap, cap};
+#pragma unroll
+        for (int q = 0; q < 6; ++q)
+            if (active && q < bpm) {
+                const uint32_t e = tab[m * (uint32_t)bpm + q];
+                at[q] = e < cap ? e : cap;
+                const uint32_t x = e < cap ? ent[e] & 0xffffu : 0u;
+                if (q < hv) { if (q < 4) d[q] = x; v[0] += x; }
+                else if (q == hv) v[1] = x;
+                else v[2] = x;
+            }
+        const uint32_t own[3] = {v[0], v[1], v[2]};
+#pragma unroll
+        for (int dd = 1; dd < 64; dd <<= 1) {                    // segmented inclusive scan inside the wave
+            const uint32_t tf = __shfl_up(f, dd, 64);
+            uint32_t tv[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) tv[c] = __shfl_up(v[c], dd, 64);
+            if (lane >= dd) {
+                if (!f) { v[0] += tv[0]; v[1] += tv[1]; v[2] += tv[2]; }
+                f |= tf;
+            }
+        }
+        if (lane == 63) { wv_v[0][wv] = v[0]; wv_v[1][wv] = v[1]; wv_v[2][wv] = v[2]; wv_f[wv] = f; }
+        __syncthreads();
+        uint32_t in[3] = {carry[0], carry[1], carry[2]};
+        for (int i = 0; i < 16; ++i) {
+            if (i == wv && !f) { v[0] += in[0]; v[1] += in[1]; v[2] += in[2]; }
+            const bool fl = wv_f[i] != 0u;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) in[c] = fl ? wv_v[c][i] : in[c] + wv_v[c][i];
+        }
+        carry[0] = in[0]; carry[1] = in[1]; carry[2] = in[2];
+        __syncthreads();
+        uint32_t pred = v[0] - own[0];
+#pragma unroll
+        for (int q = 0; q < 6; ++q)
+            if (active && q < bpm) {
+                uint32_t x;
+                if (q < hv) { if (q < 4) pred += d[q]; x = pred; }
+                else x = q == hv ? v[1] : v[2];
+                if (at[q] < cap) ent[at[q]] = x & 0xffffu;
+            }
+    }
+}
+
+// ---- host: the scan cut ----------------------------------------------------------------------------------------------------
+struct JSeg { uint32_t off, len, blk0, nblk; };
+
+static inline int jpeg_bpm(const JInfo& J) { return J.ncomp == 1 ? 1 : J.h[0] * J.v[0] + 2; }
+static inline int jpeg_nseg(const JInfo& J) { const int nm = J.mcux * J.mcuy; return J.ri ? (nm + J.ri - 1) / J.ri : 1; }
+static inline size_t jpeg_scan_bound(const JInfo& J, size_t n) { return ((n - J.scan + 3) & ~(size_t)3) + 4 * (size_t)jpeg_nseg(J); }
+
+// One pass: the scan's bytes without the 00 after every FF, cut at the RSTn markers, every segment padded with zeros to 4 bytes.
+// dst holds jpeg_scan_bound bytes and may be write-combined: it is written front to back and never read.
+static bool cut_scan(const uint8_t* d, size_t n, const JInfo& J, uint8_t* dst, std::vector<JSeg>& segs, size_t& used, std::string& err)
+{
+    const int bpm = jpeg_bpm(J), nm = J.mcux * J.mcuy, ri = J.ri ? J.ri : nm, nseg = jpeg_nseg(J);
+    size_t p = J.scan, o = 0;
+    segs.clear();
+    for (int sg = 0; sg < nseg; ++sg) {
+        const size_t start = o;
+        for (;;) {
+            const uint8_t* q = p < n ? (const uint8_t*)memchr(d + p, 0xFF, n - p) : nullptr;
+            const size_t run = (q ? (size_t)(q - d) : n) - p;
+            memcpy(dst + o, d + p, run);
+            o += run; p += run;
+            if (q && p + 1 < n && d[p + 1] == 0) { dst[o++] = 0xFF; p += 2; continue; }
+            break;                                               // a marker, or the data ends
+        }
+        const size_t len = o - start;
+        while (o & 3) dst[o++] = 0;
+        const int m0 = sg * ri, mn = nm - m0 < ri ? nm - m0 : ri;
+        segs.push_back(JSeg{(uint32_t)start, (uint32_t)len, (uint32_t)(m0 * bpm), (uint32_t)(mn * bpm)});
+        if (sg + 1 < nseg) {
+            size_t q = p;
+            while (q < n && d[q] == 0xFF) ++q;
+            if (q >= n || q == p || d[q] != 0xD0 + (sg & 7)) return jfail(err, "bad restart marker");
+            p = q + 1;
+        }
+    }
+    used = o;
+    return true;
+}
+
+static void jpeg_header_words(const JInfo& J, uint32_t* hdr)
+{
+    memset(hdr, 0, JPEG_HDR * sizeof(uint32_t));
+    hdr[0] = J.ncomp; hdr[1] = J.h[0]; hdr[2] = J.v[0]; hdr[3] = J.mcux; hdr[4] = (uint32_t)(J.mcux * J.mcuy * jpeg_bpm(J));
+    uint32_t off = 0;
+    for (int c = 0; c < J.ncomp; ++c) {
+        const uint32_t pitch = J.mcux * J.h[c] * 8, rows = J.mcuy * J.v[c] * 8;
+        hdr[8 + c] = J.tq[c]; hdr[11 + c] = off; hdr[14 + c] = pitch;
+        off += pitch * rows;
+    }
+    hdr[17] = (uint32_t)jpeg_nseg(J);
+    hdr[24] = (uint32_t)(J.ri ? J.ri : J.mcux * J.mcuy);
+    memcpy(hdr + 32, J.quant, sizeof J.quant);
+}
+
+// bytes == NULL: only the sizes (*bytes_used: the capacity to bring, *n_segments)
+int ss_jpeg_scan_segments_impl(const unsigned char* data, size_t size, unsigned char* bytes, size_t bytes_cap, size_t* bytes_used, unsigned int* segments,
+                               size_t seg_cap, int* n_segments, unsigned int* header, std::string& err)
+{
+    JInfo* J = new (std::nothrow) JInfo();
+    if (!J) { err = "out of memory"; return SS_ERR_INVALID; }
+    int rc = SS_ERR_INVALID;
+    try {
+        if (parse_headers(data, size, *J, err)) {
+            const size_t bound = jpeg_scan_bound(*J, size);
+            const int nseg = jpeg_nseg(*J);
+            if (!bytes) { *bytes_used = bound; *n_segments = nseg; rc = SS_OK; }
+            else if (bytes_cap < bound || seg_cap < (size_t)nseg) err = "buffers too small: " + std::to_string(bound) + " bytes and " + std::to_string(nseg) + " segments needed";
+            else {
+                std::vector<JSeg> segs;
+                size_t used = 0;
+                if (cut_scan(data, size, *J, bytes, segs, used, err)) {
+                    for (int i = 0; i < nseg; ++i) { segments[4 * i] = segs[i].off; segments[4 * i + 1] = segs[i].len; segments[4 * i + 2] = segs[i].blk0; segments[4 * i + 3] = segs[i].nblk; }
+                    *bytes_used = used; *n_segments = nseg;
+                    if (header) jpeg_header_words(*J, header);
+                    rc = SS_OK;
+                }
+            }
+        }
+    } catch (...) { err = "out of memory"; }
+    delete J;
+    return rc;
+}
+
+// ---- host: the batch call with the entropy stage on the device -------------------------------------------------------------
+static int jpeg_slot_wait(SSJpeg::Slot& st, std::string& err)
+{
+    if (st.busy) {
+        const hipError_t e = hipEventSynchronize(st.ev);
+        st.busy = false;
+        if (e != hipSuccess) { st.pending = 0; err = std::string("ss_jpeg_decode_batch: hipEventSynchronize: ") + hipGetErrorString(e); return SS_ERR_HIP; }
+    }
+    const int n = st.pending;
+    st.pending = 0;
+    for (int i = 0; i < n; ++i)
+        if (st.status_host[i] != JH_OK) {
+            const uint32_t code = st.status_host[i] & 7u;
+            err = "ss_jpeg_decode_batch_device: image " + std::to_string(i) + ": " + kJpegCause[code < 7 ? code : 0];
+            return SS_ERR_INVALID;
+        }
+    return SS_OK;
+}
+
+// ss_check_errors: the status words of device-entropy calls still in flight
+int ss_jpeg_pending_impl(SSJpeg* j, std::string& err)
+{
+    if (!j) return SS_OK;
+    int rc = SS_OK;
+    for (auto& st : j->slot) {
+        std::string e;
+        const int r = jpeg_slot_wait(st, e);
+        if (r != SS_OK && rc == SS_OK) { rc = r; err = e; }
+    }
+    return rc;
+}
+
+static void pack_huff(const JHuff& t, uint32_t* o)
+{
+    memset(o, 0, JH_TAB * sizeof(uint32_t));
+    memcpy(o, t.fast, sizeof t.fast);
+    for (int ln = 10; ln <= 16; ++ln) { o[256 + ln - 10] = (uint32_t)t.maxcode[ln]; o[264 + ln - 10] = (uint32_t)t.mincode[ln]; o[272 + ln - 10] = (uint32_t)t.valptr[ln]; }
+    memcpy(o + 280, t.vals, sizeof t.vals);
+}
+
+struct JDevImage { JInfo J; std::vector<JSeg> segs; std::string err; bool ok = false; size_t at = 0, bound = 0, used = 0, tab_at = 0, ent_at = 0, rounds_at = 0, cap = 0, lanes = 0; };
+
+// coef != NULL: the stage alone on one image (ss_jpeg_device_coefficients): no size check, no IDCT, the stream comes back and is expanded here.
+int ss_jpeg_decode_device_impl(SSJpeg** state, hipStream_t stream, const unsigned char* const* data, const size_t* sizes, int n, int height, int width,
+                               void* d_out, long long out_frame_stride, int rgb, int threads, short* coef, size_t coef_cap, std::string& err)
+{
+    try {
+        if (!*state) *state = new SSJpeg();
+        SSJpeg& S = **state;
+        std::vector<JDevImage> img(n);
+        const uint32_t W = (uint32_t)g_opt_jpeg_subseq_words;
+        // ---- 1. headers ----
+        auto heads = [&img, data, sizes, n, height, width, coef](int t, int nt) {
+            for (int i = t; i < n; i += nt) {
+                JDevImage& im = img[i];
+                try {
+                    if (!parse_headers(data[i], sizes[i], im.J, im.err)) continue;
+                    if (!coef && (im.J.width != width || im.J.height != height)) {
+                        im.err = "size " + std::to_string(im.J.width) + "x" + std::to_string(im.J.height) + " differs from the batch's " + std::to_string(width) + "x" + std::to_string(height);
+                        continue;
+                    }
+                    im.bound = jpeg_scan_bound(im.J, sizes[i]);
+                    im.ok = true;
+                } catch (...) { im.err = "out of memory"; }
+            }
+        };
+        const int T = threads < n ? threads : n;
+        if (!run_threads(T, heads)) { err = "ss_jpeg_decode_batch_device: host stage failed"; return SS_ERR_INVALID; }
+        for (int i = 0; i < n; ++i)
+            if (!img[i].ok) { err = "ss_jpeg_decode_batch_device: image " + std::to_string(i) + ": " + img[i].err; return SS_ERR_INVALID; }
+        // ---- 2. layout of what crosses PCIe: headers, then per image its Huffman tables, segment table and scan bytes ----
+        size_t at = (size_t)n * JPEG_HDR;
+        for (int i = 0; i < n; ++i) {
+            JDevImage& im = img[i];
+            im.at = at;
+            at += (size_t)im.J.ncomp * 2 * JH_TAB + (size_t)jpeg_nseg(im.J) * JH_SEG + im.bound / 4;
+        }
+        if (at >= ((size_t)1 << 30)) { err = "ss_jpeg_decode_batch_device: scans beyond 4 GiB"; return SS_ERR_CAPACITY; }
+        const size_t in_words = at;
+        SSJpeg::Slot& st = S.slot[S.next];
+        if (int rcw = jpeg_slot_wait(st, err)) return rcw;
+        if (!st.ev) JCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+        if (!st.status_dev) {
+            JCHK(hipMalloc((void**)&st.status_dev, 64 * sizeof(uint32_t)));
+            JCHK(hipHostMalloc((void**)&st.status_host, 64 * sizeof(uint32_t), hipHostMallocDefault));
+        }
+        if (st.host_cap < in_words * 4) {
+            if (st.host) { JCHK(hipHostFree(st.host)); st.host = nullptr; st.host_cap = 0; }
+            const size_t cap = in_words * 4 + in_words;
+            JCHK(hipHostMalloc(&st.host, cap, hipHostMallocWriteCombined));
+            st.host_cap = cap;
+        }
+        // ---- 3. the scan cut and the tables, straight into the staging area ----
+        uint32_t* base = (uint32_t*)st.host;
+        auto cut = [&img, base, data, sizes, n, W](int t, int nt) {
+            for (int i = t; i < n; i += nt) {
+                JDevImage& im = img[i];
+                im.ok = false;
+                try {
+                    const JInfo& J = im.J;
+                    uint32_t* o = base + im.at;
+                    uint32_t tb[JH_TAB];
+                    for (int c = 0; c < J.ncomp; ++c) {
+                        pack_huff(J.dc[J.td[c]], tb); memcpy(o, tb, sizeof tb); o += JH_TAB;
+                        pack_huff(J.ac[J.ta[c]], tb); memcpy(o, tb, sizeof tb); o += JH_TAB;
+                    }
+                    const size_t nseg = (size_t)jpeg_nseg(J);
+                    if (!cut_scan(data[i], sizes[i], J, (uint8_t*)(o + nseg * JH_SEG), im.segs, im.used, im.err)) continue;
+                    std::vector<uint32_t> rec(nseg * JH_SEG);
+                    size_t lanes = 0, bytes = 0;
+                    for (size_t k = 0; k < nseg; ++k) {
+                        const JSeg& sg = im.segs[k];
+                        rec[k * JH_SEG] = sg.off; rec[k * JH_SEG + 1] = sg.len; rec[k * JH_SEG + 2] = sg.blk0; rec[k * JH_SEG + 3] = sg.nblk; rec[k * JH_SEG + 4] = (uint32_t)lanes;
+                        const size_t sub = ((size_t)sg.len + 4 * W - 1) / (4 * W);
+                        lanes += sub ? sub : 1;
+                        bytes += sg.len;
+                    }
+                    memcpy(o, rec.data(), rec.size() * 4);
+                    im.lanes = lanes;
+                    im.cap = (size_t)J.mcux * J.mcuy * jpeg_bpm(J) + 4 * bytes;
+                    im.ok = true;
+                } catch (...) { im.err = "out of memory"; }
+            }
+        };
+        if (!run_threads(T, cut)) { err = "ss_jpeg_decode_batch_device: host stage failed"; return SS_ERR_INVALID; }
+        for (int i = 0; i < n; ++i)
+            if (!img[i].ok) { err = "ss_jpeg_decode_batch_device: image " + std::to_string(i) + ": " + img[i].err; return SS_ERR_INVALID; }
+        // ---- 4. layout of what stays on the device: block tables (zeroed), rounds, entries; then the headers ----
+        int max_blk = 0;
+        const size_t tabs_at = at;
+        for (int i = 0; i < n; ++i) { img[i].tab_at = at; at += (size_t)img[i].J.mcux * img[i].J.mcuy * jpeg_bpm(img[i].J) + 1; }
+        const size_t tabs_words = at - tabs_at;
+        for (int i = 0; i < n; ++i) { img[i].rounds_at = at; at += (img[i].lanes + JH_LANES - 1) / JH_LANES; }
+        for (int i = 0; i < n; ++i) { img[i].ent_at = at; at += img[i].cap; }
+        if (at >= ((size_t)1 << 32)) { err = "ss_jpeg_decode_batch_device: coefficient stream beyond 2^32 entries"; return SS_ERR_CAPACITY; }
+        for (int i = 0; i < n; ++i) {
+            const JDevImage& im = img[i];
+            uint32_t hdr[JPEG_HDR];
+            jpeg_header_words(im.J, hdr);
+            if ((int)hdr[4] > max_blk) max_blk = (int)hdr[4];
+            hdr[5] = (uint32_t)im.tab_at; hdr[6] = (uint32_t)im.ent_at;
+            hdr[19] = (uint32_t)im.at;
+            hdr[25] = hdr[19] + (uint32_t)im.J.ncomp * 2 * JH_TAB;
+            hdr[18] = hdr[25] + hdr[17] * JH_SEG;
+            hdr[20] = (uint32_t)im.lanes; hdr[21] = (uint32_t)im.cap; hdr[22] = (uint32_t)im.rounds_at; hdr[23] = W;
+            memcpy(base + (size_t)i * JPEG_HDR, hdr, sizeof hdr);
+        }
+        const size_t bytes = at * 4;
+        const size_t plane_slot = 3 * (size_t)((width + 15) / 16 * 16) * ((height + 15) / 16 * 16), planes_bytes = coef ? 0 : plane_slot * n;
+        if (st.dev_cap < bytes) {
+            if (st.dev) { JCHK(hipFree(st.dev)); st.dev = nullptr; st.dev_cap = 0; }
+            const size_t cap = bytes + bytes / 4;
+            JCHK(hipMalloc((void**)&st.dev, cap));
+            st.dev_cap = cap;
+        }
+        if (st.planes_cap < planes_bytes) {
+            if (st.planes) { JCHK(hipFree(st.planes)); st.planes = nullptr; st.planes_cap = 0; }
+            JCHK(hipMalloc((void**)&st.planes, planes_bytes));
+            st.planes_cap = planes_bytes;
+        }
+        // ---- 5. one copy, the two entropy kernels, the two kernels of the host stage's path, the status ----
+        JCHK(hipMemcpyAsync(st.dev, st.host, in_words * 4, hipMemcpyHostToDevice, stream));
+        JCHK(hipMemsetAsync(st.dev + tabs_at, 0, tabs_words * 4, stream));
+        JCHK(hipMemsetAsync(st.status_dev, 0xff, (size_t)n * 4, stream));
+        hipLaunchKernelGGL(k_jpeg_huff, dim3(n), dim3(JH_LANES), 0, stream, st.dev, st.status_dev);
+        hipLaunchKernelGGL(k_jpeg_dc, dim3(n), dim3(JH_LANES), 0, stream, st.dev, st.status_dev);
+        if (!coef) {
+            hipLaunchKernelGGL(k_jpeg_idct, dim3((max_blk + 31) / 32, n), dim3(256), 0, stream, st.dev, st.planes, (long long)plane_slot);
+            const int groups = (height * width + 3) / 4;
+            const int dwords = (((uintptr_t)d_out | (uintptr_t)out_frame_stride) & 3) == 0;
+            hipLaunchKernelGGL(k_jpeg_pixels, dim3((groups + 255) / 256, n), dim3(256), 0, stream, st.dev, st.planes, (long long)plane_slot, height, width,
+                               (uint8_t*)d_out, out_frame_stride, rgb, dwords);
+        }
+        JCHK(hipGetLastError());
+        JCHK(hipMemcpyAsync(st.status_host, st.status_dev, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+        JCHK(hipEventRecord(st.ev, stream));
+        st.busy = true;
+        st.pending = n;
+        S.next ^= 1;
+        if (!coef) return SS_OK;
+        // ---- the stage alone: wait, read the stream back, expand ----
+        if (int rcw = jpeg_slot_wait(st, err)) return rcw;
+        const JDevImage& im = img[0];
+        const JInfo& J = im.J;
+        const size_t blocks = (size_t)J.mcux * J.mcuy * jpeg_bpm(J), tiles = (im.lanes + JH_LANES - 1) / JH_LANES;
+        size_t cbase[3] = {0, 0, 0}, tot = 0;
+        for (int c = 0; c < J.ncomp; ++c) { cbase[c] = tot; tot += (size_t)J.mcux * J.h[c] * J.mcuy * J.v[c] * 64; }
+        if (tot > coef_cap) { err = "coefficient buffer too small: " + std::to_string(tot) + " values needed"; return SS_ERR_INVALID; }
+        std::vector<uint32_t> tab(blocks + 1), rnd(tiles);
+        JCHK(hipMemcpy(tab.data(), st.dev + im.tab_at, tab.size() * 4, hipMemcpyDeviceToHost));
+        JCHK(hipMemcpy(rnd.data(), st.dev + im.rounds_at, rnd.size() * 4, hipMemcpyDeviceToHost));
+        const size_t ne = tab[blocks];
+        if (ne > im.cap) { err = "ss_jpeg_device_coefficients: entry total beyond the capacity"; return SS_ERR_INVALID; }
+        std::vector<uint32_t> ent(ne ? ne : 1);
+        if (ne) JCHK(hipMemcpy(ent.data(), st.dev + im.ent_at, ne * 4, hipMemcpyDeviceToHost));
+        S.rounds.assign(rnd.begin(), rnd.end());
+        memset(coef, 0, tot * sizeof(short));
+        const int bpm = jpeg_bpm(J), hv = J.ncomp == 1 ? 1 : J.h[0] * J.v[0];
+        for (size_t b = 0; b < blocks; ++b) {
+            const size_t m = b / bpm;
+            const int jj = (int)(b % bpm), my = (int)(m / J.mcux), mx = (int)(m % J.mcux);
+            int c = 0, by = my, bx = mx;
+            if (jj < hv) { by = my * J.v[0] + jj / J.h[0]; bx = mx * J.h[0] + jj % J.h[0]; }
+            else c = 1 + jj - hv;
+            short* o = coef + cbase[c] + ((size_t)by * (J.mcux * J.h[c]) + bx) * 64;
+            if (tab[b] > tab[b + 1] || tab[b + 1] > ne) { err = "ss_jpeg_device_coefficients: block table out of order"; return SS_ERR_INVALID; }
+            for (size_t e = tab[b]; e < tab[b + 1]; ++e) o[(ent[e] >> 16) & 63u] = (short)(uint16_t)(ent[e] & 0xffffu);
+        }
+        return SS_OK;
+    } catch (...) {
+        err = "ss_jpeg_decode_batch_device: out of memory";
+        return SS_ERR_INVALID;
+    }
+}
+
+int ss_jpeg_device_rounds_impl(SSJpeg* j, int* rounds, int cap)
+{
+    if (!j) return 0;
+    const int n = (int)j->rounds.size();
+    for (int i = 0; i < n && i < cap; ++i) rounds[i] = j->rounds[i];
+    return n;
 }

@@ -137,10 +137,14 @@ class TrackerEngine:
         arr = (C.c_void_p * n)(*[a.ctypes.data for a in srcs])
         self._ck(self.L.ss_upload_batch(self.ctx, self._st(stream), _ptr(dst), arr, n, each, int(threads)))
 
-    def jpeg_decode_batch(self, dst: torch.Tensor, frames, stream=None, threads: int = 4, rgb: bool = False):
+    def jpeg_decode_batch(self, dst: torch.Tensor, frames, stream=None, threads: int = 4, rgb: bool = False, entropy: str = "host"):
         """len(frames) (1 .. 64) jpeg.EncodedFrames of one size -> dst[0 .. len(frames)) (device uint8 [.., H, W, 3], every frame
         contiguous), BGR or RGB: Huffman decoding on `threads` host threads inside the call, then one asynchronous copy of the
-        coefficients and two launches (csrc/ss_jpeg.hip).  The frames' bytes may be reused immediately."""
+        coefficients and two launches (csrc/ss_jpeg.hip).  The frames' bytes may be reused immediately.
+        entropy="device": the host only parses the headers and copies the scans; Huffman decoding runs on the device too (docs/JPEG.md
+        §12).  Same pixels; a scan that turns out damaged is reported by the next check_errors() or a later decode call."""
+        if entropy not in ("host", "device"):
+            raise ValueError(f"jpeg_decode_batch: entropy {entropy!r} (\"host\" or \"device\")")
         n = len(frames)
         if n == 0:
             return
@@ -151,8 +155,8 @@ class TrackerEngine:
         data = (C.c_char_p * n)(*[f.data for f in frames])
         sizes = (C.c_size_t * n)(*[len(f.data) for f in frames])
         stride = dst.stride(0) if dst.shape[0] > 1 else dst[0].numel()
-        self._ck(self.L.ss_jpeg_decode_batch(self.ctx, self._st(stream), data, sizes, n, shape[0], shape[1], _ptr(dst), stride, int(bool(rgb)),
-                                             int(threads)))
+        call = self.L.ss_jpeg_decode_batch_device if entropy == "device" else self.L.ss_jpeg_decode_batch
+        self._ck(call(self.ctx, self._st(stream), data, sizes, n, shape[0], shape[1], _ptr(dst), stride, int(bool(rgb)), int(threads)))
 
     def jpeg_encode_batch(self, src: torch.Tensor, quality: int = 85, subsampling: str = "4:2:0", stream=None, threads: int = 4, rgb: bool = False):
         """src: device uint8 [n, H, W, 3] (n 1 .. 64, every frame contiguous) or [H, W, 3], BGR (rgb=True: RGB) -> n baseline JPEG

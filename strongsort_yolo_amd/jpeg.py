@@ -4,7 +4,9 @@
     f = EncodedFrame(data)                          .shape == (H, W, 3); ValueError with the library's message when refused
     for f in split_mjpeg("clip.mjpeg"): ...         a raw concatenated MJPEG file, no container parsing
     for b in split_bytes(buf): ...                  the same cut on bytes, yielding each frame's bytes unprobed
-    t = decode(engine, frames)                      uint8 device tensor [n, H, W, 3], BGR (rgb=True: RGB)
+    t = decode(engine, frames)                      uint8 device tensor [n, H, W, 3], BGR (rgb=True: RGB); entropy="device": Huffman
+                                                    decoding on the device too (docs/JPEG.md §12)
+    raw, segs, hdr = scan_segments(data)            host only: the host's share of that stage (unstuffed scan cut at its restart markers)
     files = encode(engine, frames, quality=85)      frames on the device (or host arrays) -> baseline JPEG files as bytes (csrc/ss_jpeg_enc.hip)
 
 `YOLO.track_stream` takes EncodedFrames in place of arrays: the group is decoded straight into the buffer the detector reads.
@@ -99,17 +101,51 @@ def split_mjpeg(src: Union[str, bytes, bytearray, memoryview, "os.PathLike"]) ->
         yield EncodedFrame(seg)
 
 
-def decode(engine, frames, out=None, rgb: bool = False, stream=None, threads: int = 4):
-    """EncodedFrames (or bytes) of one size -> uint8 device tensor [n, H, W, 3]; asynchronous on `stream` after the host stage."""
+def decode(engine, frames, out=None, rgb: bool = False, stream=None, threads: int = 4, entropy: str = "host"):
+    """EncodedFrames (or bytes) of one size -> uint8 device tensor [n, H, W, 3]; asynchronous on `stream` after the host stage.
+    entropy: "host" (Huffman decoding on the host threads) or "device" (on the device too, docs/JPEG.md §12)."""
     import torch
+    if entropy not in ("host", "device"):
+        raise ValueError(f"jpeg.decode: entropy {entropy!r} (\"host\" or \"device\")")
     frames = [f if isinstance(f, EncodedFrame) else EncodedFrame(f) for f in frames]
     if not frames:
         raise ValueError("jpeg.decode: no frames")
     if out is None:
         out = torch.empty((len(frames),) + frames[0].shape, dtype=torch.uint8, device=engine.device)
     for k in range(0, len(frames), MAX_BATCH):
-        engine.jpeg_decode_batch(out[k:k + MAX_BATCH], frames[k:k + MAX_BATCH], stream, threads, rgb)
+        engine.jpeg_decode_batch(out[k:k + MAX_BATCH], frames[k:k + MAX_BATCH], stream, threads, rgb, entropy)
     return out
+
+
+def scan_segments(data):
+    """The host's share of the device entropy stage for one file (host only): (unstuffed scan bytes, segments [n, 4] uint32 of
+    byte offset / byte length / first block / blocks, the 160 header words); ValueError with the library's message when refused."""
+    import numpy as np
+    data = bytes(data)
+    L = lib.load()
+    used, nseg = C.c_size_t(), C.c_int()
+
+    def ck(rc):
+        if rc != lib.SS_OK:
+            msg = L.ss_last_error(None)
+            raise ValueError(msg.decode() if msg else "ss_jpeg_scan_segments failed")
+    ck(L.ss_jpeg_scan_segments(data, len(data), None, 0, C.byref(used), None, 0, C.byref(nseg), None))
+    raw, segs, hdr = np.zeros(used.value, np.uint8), np.zeros((nseg.value, 4), np.uint32), np.zeros(160, np.uint32)
+    ck(L.ss_jpeg_scan_segments(data, len(data), raw.ctypes.data, raw.size, C.byref(used), segs.ctypes.data, nseg.value, C.byref(nseg), hdr.ctypes.data))
+    return raw[:used.value].tobytes(), segs, hdr
+
+
+def device_coefficients(engine, data):
+    """The device entropy stage alone on one file: (dense int16 blocks in ss_jpeg_coefficients' layout, the rounds each tile took)."""
+    import numpy as np
+    data = bytes(data)
+    h, w, nc, (hs, vs) = probe(data)
+    mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
+    coef = np.zeros(mx * my * 64 * (1 if nc == 1 else hs * vs + 2), np.int16)
+    engine._ck(engine.L.ss_jpeg_device_coefficients(engine.ctx, data, len(data), coef.ctypes.data_as(C.POINTER(C.c_short)), coef.size))
+    rounds = (C.c_int * 4096)()
+    n = engine.L.ss_jpeg_device_rounds(engine.ctx, rounds, 4096)
+    return coef, list(rounds[:min(n, 4096)])
 
 
 def encode(engine, frames, quality: int = 85, subsampling: str = "4:2:0", stream=None, threads: int = 4, rgb: bool = False):

@@ -33,6 +33,7 @@ EXPORTS = [
     "ss_byte_set_pose", "ss_byte_update_group_kpts", "ss_byte_get_keypoints", "ss_byte_get_det_keypoints",
     "ss_gmc_sparse_estimate", "ss_gmc_sparse_get",
     "ss_jpeg_probe", "ss_jpeg_coefficients", "ss_jpeg_decode_batch",
+    "ss_jpeg_decode_batch_device", "ss_jpeg_scan_segments", "ss_jpeg_device_coefficients", "ss_jpeg_device_rounds",
     "ss_jpeg_encode_bound", "ss_jpeg_entropy_encode", "ss_jpeg_encode_batch",
 ]
 
@@ -216,6 +217,10 @@ def load():
     L.ss_jpeg_probe.argtypes = [C.c_char_p, C.c_size_t, hi, hi, hi, hi, hi]
     L.ss_jpeg_coefficients.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_short), C.c_size_t, C.POINTER(C.c_ushort)]
     L.ss_jpeg_decode_batch.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), i, i, i, vp, ll, i, i]
+    L.ss_jpeg_decode_batch_device.argtypes = L.ss_jpeg_decode_batch.argtypes
+    L.ss_jpeg_scan_segments.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, hi, vp]
+    L.ss_jpeg_device_coefficients.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_short), C.c_size_t]
+    L.ss_jpeg_device_rounds.argtypes = [vp, hi, i]
     L.ss_jpeg_encode_bound.argtypes = [i, i, i, i]
     L.ss_jpeg_entropy_encode.argtypes = [C.POINTER(C.c_short), i, i, i, i, i, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ss_jpeg_encode_batch.argtypes = [vp, vp, vp, ll, i, i, i, i, i, i, i, i, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]

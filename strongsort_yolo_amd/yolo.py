@@ -560,7 +560,8 @@ class YOLO:
 
     # ---- throughput path ------------------------------------------------------------------------------------
     @torch.no_grad()
-    def track_stream(self, frames, batch: int = 16, device=0, keep_device_frames: bool = False, conf: Optional[float] = None):
+    def track_stream(self, frames, batch: int = 16, device=0, keep_device_frames: bool = False, conf: Optional[float] = None,
+                     jpeg_entropy: str = "host"):
         """Generator over `frames` (BGR uint8 arrays of one size, or jpeg.EncodedFrames of one size: baseline JPEGs decoded on the
         device, `Results.orig_img` is then the EncodedFrame): yields the same [Results] `track(frame)` would, in
         order, `batch` frames at a time through the overlapped two-stream pipeline (stateless stages of group k+1 run
@@ -568,7 +569,10 @@ class YOLO:
         keep_device_frames: every Results also carries `orig_img_device`, the frame as a device tensor (a device-to-device copy
         of the group's input buffer taken on the tracker's stream), so that an annotated output needs no second upload
         (`Overlay.draw_resident`); valid until the generator has yielded `ring` more groups.
-        conf (BYTE models): the NMS threshold, as track(conf=...) (default 0.1)."""
+        conf (BYTE models): the NMS threshold, as track(conf=...) (default 0.1).
+        jpeg_entropy (EncodedFrames): "host" (default) decodes the Huffman code on host threads, "device" on the device (docs/JPEG.md §12)."""
+        if jpeg_entropy not in ("host", "device"):
+            raise ValueError(f"track_stream: jpeg_entropy {jpeg_entropy!r} (\"host\" or \"device\")")
         from .pipeline import OverlappedPipeline
         from .jpeg import EncodedFrame
         it = iter(frames)
@@ -633,7 +637,7 @@ class YOLO:
                 b = pipe.begin_frame()                                    # waits until this buffer set's last group left the tracker
                 with torch.cuda.stream(pipe.s_in):
                     if encoded:                                           # Huffman decoding on host threads, the rest on the device (jpeg.py)
-                        pipe.eng.jpeg_decode_batch(b.frames, chunk, pipe.s_in)
+                        pipe.eng.jpeg_decode_batch(b.frames, chunk, pipe.s_in, entropy=jpeg_entropy)
                     else:
                         pipe.eng.upload_batch(b.frames, chunk, pipe.s_in)  # the group's frames: staged by several host threads, one copy
                     if self._fill is not None:
