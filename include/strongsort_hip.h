@@ -658,6 +658,21 @@ int ss_jpeg_entropy_encode(const short* coef, int quality, int width, int height
  * (host work, waits): never call it while hip_stream is capturing. */
 int ss_jpeg_encode_batch(ss_ctx* ctx, void* hip_stream, const void* d_in, long long in_frame_stride, int n, int height, int width, int rgb,
                          int quality, int h_samp, int v_samp, int threads, unsigned char* const* out, const size_t* out_cap, size_t* out_size);
+/* The same call with the entropy stage on the device too (docs/JPEG.md section 13): same arguments, same checks, same refusals,
+ * same return codes, the same files byte for byte.  Four more kernels on hip_stream turn the dense coefficients into the stuffed
+ * scan (bit length per block, 64-bit scan of the lengths + write into a zeroed stream, FF count, stuffing); only the scans' own
+ * bytes come back, and `threads` (1 .. 16) host threads write the headers and copy.  The call waits three times on an event of its
+ * own (bit totals, FF totals, the copy); no device-wide synchronisation.  Not capturable (waits, allocations that follow the
+ * totals): never call it while hip_stream is capturing. */
+int ss_jpeg_encode_batch_device(ss_ctx* ctx, void* hip_stream, const void* d_in, long long in_frame_stride, int n, int height, int width,
+                                int rgb, int quality, int h_samp, int v_samp, int threads, unsigned char* const* out, const size_t* out_cap,
+                                size_t* out_size);
+/* For tests: the device twin of ss_jpeg_entropy_encode.  The same coefficient layout (ss_jpeg_coefficients'), uploaded as dense
+ * blocks; the device entropy stage alone writes the scan, the host the header; out receives the whole file.  Synchronous, on the
+ * context's stream.  Coefficients beyond the baseline categories (DC difference 11 bits, AC 10 bits), which no frame produces, are
+ * refused on the host before anything is launched, with ss_jpeg_entropy_encode's message. */
+int ss_jpeg_entropy_encode_device(ss_ctx* ctx, const short* coef, int quality, int width, int height, int h_samp, int v_samp,
+                                  unsigned char* out, size_t out_cap, size_t* out_size);
 
 /* ---- profiling support ----------------------------------------------------------------------- */
 /* Mean duration (ms) of the association (cosine gallery) kernel over the launches since the last

@@ -157,7 +157,8 @@ class FrameSink:
       *.bgr      raw BGR24 frames appended as they arrive + `<path>.json` {width, height, fps, frames} (ffmpeg -f rawvideo
                  -pix_fmt bgr24 -s WxH -r fps turns it into the reference's mp4)
       directory  frame_000000.png ... (Pillow)
-    and, with device_encode=True (the CLI's --device-encode), baseline JPEG encoded on the device (jpeg.encode, docs/JPEG.md):
+    and, with device_encode=True (the CLI's --device-encode), baseline JPEG encoded on the device (jpeg.encode, docs/JPEG.md; with
+    device_entropy=True, --device-encode-entropy, its Huffman coding too):
       *.mjpeg / *.mjpg   the frames' files concatenated (jpeg.split_mjpeg and --device-decode read it back)       kind "mjpeg"
       directory          frame_000000.jpg ... (the path ends in a separator or is an existing directory)          kind "jpgdir"
     These two take frames that are still on the device (`write_device`); `write` uploads a host frame into the same path.  Frames
@@ -173,9 +174,11 @@ class FrameSink:
             return "jpgdir"
         return None
 
-    def __init__(self, path: str, fps: int = 15, device_encode: bool = False, engine=None, quality: int = 85, subsampling: str = "4:2:0"):
+    def __init__(self, path: str, fps: int = 15, device_encode: bool = False, engine=None, quality: int = 85, subsampling: str = "4:2:0",
+                 device_entropy: bool = False):
         self.path, self.fps, self.n, self.shape = path, fps, 0, None
         self.engine, self.quality, self.subsampling = engine, quality, subsampling
+        self.entropy = "device" if device_entropy else "host"   # jpeg.encode's entropy: Huffman coding on the device too (docs/JPEG.md §13)
         self._buf, self._held = None, 0                      # device frames waiting for their group's encode
         if device_encode:
             self.kind = self.encoded_kind(path)
@@ -219,7 +222,7 @@ class FrameSink:
         if not self._held:
             return
         from .jpeg import encode
-        files = encode(self.engine, self._buf[:self._held], self.quality, self.subsampling)
+        files = encode(self.engine, self._buf[:self._held], self.quality, self.subsampling, entropy=self.entropy)
         first, self._held = self.n - self._held, 0
         for k, data in enumerate(files):
             if self.kind == "mjpeg":
@@ -339,7 +342,8 @@ def process_video(args: dict, model=None) -> dict:
     batch = int(args.get("batch", 16))
     src = frame_source(str(source), args.get("limit"), encoded=bool(args.get("device_decode", False)))
     sink = (FrameSink(args["save"], device_encode=bool(args.get("device_encode", False)), quality=int(args.get("save_quality", 85)),
-                      subsampling=args.get("save_subsampling", "4:2:0")) if args.get("save") else None)       # annotated output (N2 + N3), off by default
+                      subsampling=args.get("save_subsampling", "4:2:0"), device_entropy=bool(args.get("device_encode_entropy", False)))
+            if args.get("save") else None)       # annotated output (N2 + N3), off by default
     on_device = sink is not None and sink.kind in ("mjpeg", "jpgdir")
     overlay, fps_str = None, ""
 
@@ -435,6 +439,8 @@ def main(argv=None):
     p.add_argument("--device-encode", action="store_true",
                    help="encode the annotated frames as baseline JPEG on the device (colour, DCT and quantisation in csrc/ss_jpeg_enc.hip, Huffman on host "
                         "threads; the same bytes as Pillow, docs/JPEG.md); needs --save clip.mjpeg / clip.mjpg or --save <directory>/")
+    p.add_argument("--device-encode-entropy", action="store_true",
+                   help="--device-encode: Huffman-code the frames on the device too (docs/JPEG.md §13); only the files' own bytes come back, the same bytes")
     p.add_argument("--save-quality", type=int, default=85, help="--device-encode: JPEG quality 1 .. 100")
     p.add_argument("--save-subsampling", choices=("4:2:0", "4:2:2", "4:4:4"), default="4:2:0", help="--device-encode: chroma subsampling")
     p.add_argument("--batch", type=int, default=16, help="frames per group on the throughput path (1: per-frame model.track calls as in the reference)")
@@ -473,6 +479,8 @@ def main(argv=None):
             why = encoded_source_error(src)
             if why:
                 p.error(why)
+    if a.device_encode_entropy and not a.device_encode:
+        p.error("--device-encode-entropy is a stage of the device JPEG encoder: it needs --device-encode")
     if a.device_encode:
         if not a.save:
             p.error("--device-encode encodes the annotated output: it needs --save")
@@ -481,7 +489,7 @@ def main(argv=None):
         if not 1 <= a.save_quality <= 100:
             p.error("--save-quality must be 1 .. 100")
     jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "device_decode": a.device_decode, "device_entropy": a.device_entropy,
-             "device_encode": a.device_encode, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
+             "device_encode": a.device_encode, "device_encode_entropy": a.device_encode_entropy, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
              "save": _save_path(a, i)}
             for i, s in enumerate(a.source)]
     import torch

@@ -62,6 +62,8 @@ struct SSJpegEnc;                       // ss_jpeg_enc.hip
 size_t ss_jpeg_encode_bound_impl(int, int, int, int);
 int  ss_jpeg_entropy_encode_impl(const short*, int, int, int, int, int, unsigned char*, size_t*, std::string&);
 int  ss_jpeg_encode_impl(SSJpegEnc**, hipStream_t, const void*, long long, int, int, int, int, int, int, int, int, unsigned char* const*, size_t*, std::string&);
+int  ss_jpeg_encode_device_impl(SSJpegEnc**, hipStream_t, const void*, long long, int, int, int, int, int, int, int, int, unsigned char* const*, size_t*, std::string&);
+int  ss_jpeg_entropy_encode_device_impl(SSJpegEnc**, hipStream_t, const short*, int, int, int, int, int, unsigned char*, size_t*, std::string&);
 void ss_jpeg_enc_free(SSJpegEnc*);
 
 static std::string g_last_error;
@@ -457,24 +459,60 @@ extern "C" int ss_jpeg_entropy_encode(const short* coef, int quality, int width,
     return rc == SS_OK ? rc : fail(nullptr, rc, "ss_jpeg_entropy_encode: " + err);
 }
 
+// ss_jpeg_encode_batch and ss_jpeg_encode_batch_device: one set of checks, the messages under the caller's name
+static int jpeg_encode_checks(ss_ctx* c, const std::string& who, const void* d_in, long long in_frame_stride, int n, int height, int width, int rgb, int quality,
+                              int h_samp, int v_samp, int threads, unsigned char* const* out, const size_t* out_cap, size_t* out_size)
+{
+    if (!c || !d_in || !out || !out_cap || !out_size) return fail(c, SS_ERR_INVALID, who + ": null argument");
+    if (n < 1 || n > 64) return fail(c, SS_ERR_INVALID, who + ": 1 <= n <= 64");
+    if (threads < 1 || threads > 16) return fail(c, SS_ERR_INVALID, who + ": 1 <= threads <= 16");
+    if (rgb != 0 && rgb != 1) return fail(c, SS_ERR_INVALID, who + ": rgb 0 / 1");
+    if (const char* why = jpeg_enc_shape_error(width, height, quality, h_samp, v_samp)) return fail(c, SS_ERR_INVALID, who + ": " + why);
+    if (n > 1 && in_frame_stride < (long long)height * width * 3) return fail(c, SS_ERR_INVALID, who + ": in_frame_stride >= height * width * 3");
+    const size_t bound = ss_jpeg_encode_bound_impl(width, height, h_samp, v_samp);
+    for (int i = 0; i < n; ++i) {
+        if (!out[i]) return fail(c, SS_ERR_INVALID, who + ": image " + std::to_string(i) + ": null buffer");
+        if (out_cap[i] < bound)
+            return fail(c, SS_ERR_INVALID, who + ": image " + std::to_string(i) + ": out_cap " + std::to_string(out_cap[i]) + " is below the bound " + std::to_string(bound));
+    }
+    return SS_OK;
+}
+
 extern "C" int ss_jpeg_encode_batch(ss_ctx* c, void* hip_stream, const void* d_in, long long in_frame_stride, int n, int height, int width, int rgb,
                                     int quality, int h_samp, int v_samp, int threads, unsigned char* const* out, const size_t* out_cap, size_t* out_size)
 {
-    if (!c || !d_in || !out || !out_cap || !out_size) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: null argument");
-    if (n < 1 || n > 64) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: 1 <= n <= 64");
-    if (threads < 1 || threads > 16) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: 1 <= threads <= 16");
-    if (rgb != 0 && rgb != 1) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: rgb 0 / 1");
-    if (const char* why = jpeg_enc_shape_error(width, height, quality, h_samp, v_samp)) return fail(c, SS_ERR_INVALID, std::string("ss_jpeg_encode_batch: ") + why);
-    if (n > 1 && in_frame_stride < (long long)height * width * 3) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: in_frame_stride >= height * width * 3");
-    const size_t bound = ss_jpeg_encode_bound_impl(width, height, h_samp, v_samp);
-    for (int i = 0; i < n; ++i) {
-        if (!out[i]) return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: image " + std::to_string(i) + ": null buffer");
-        if (out_cap[i] < bound)
-            return fail(c, SS_ERR_INVALID, "ss_jpeg_encode_batch: image " + std::to_string(i) + ": out_cap " + std::to_string(out_cap[i]) + " is below the bound " + std::to_string(bound));
-    }
+    if (const int bad = jpeg_encode_checks(c, "ss_jpeg_encode_batch", d_in, in_frame_stride, n, height, width, rgb, quality, h_samp, v_samp, threads, out, out_cap, out_size))
+        return bad;
     std::string err;
     const int rc = ss_jpeg_encode_impl(&c->jpeg_enc, (hipStream_t)hip_stream, d_in, in_frame_stride, n, height, width, rgb, quality, h_samp, v_samp, threads, out,
                                        out_size, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+// The same call with the entropy stage on the device (docs/JPEG.md section 13): same arguments, same checks, same files
+extern "C" int ss_jpeg_encode_batch_device(ss_ctx* c, void* hip_stream, const void* d_in, long long in_frame_stride, int n, int height, int width, int rgb,
+                                           int quality, int h_samp, int v_samp, int threads, unsigned char* const* out, const size_t* out_cap, size_t* out_size)
+{
+    if (const int bad = jpeg_encode_checks(c, "ss_jpeg_encode_batch_device", d_in, in_frame_stride, n, height, width, rgb, quality, h_samp, v_samp, threads, out, out_cap,
+                                           out_size))
+        return bad;
+    std::string err;
+    const int rc = ss_jpeg_encode_device_impl(&c->jpeg_enc, (hipStream_t)hip_stream, d_in, in_frame_stride, n, height, width, rgb, quality, h_samp, v_samp, threads, out,
+                                              out_size, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+// The device entropy stage alone on one image's coefficients, for tests: ss_jpeg_entropy_encode's arguments and checks
+extern "C" int ss_jpeg_entropy_encode_device(ss_ctx* c, const short* coef, int quality, int width, int height, int h_samp, int v_samp, unsigned char* out,
+                                             size_t out_cap, size_t* out_size)
+{
+    if (!c || !coef || !out || !out_size) return fail(c, SS_ERR_INVALID, "ss_jpeg_entropy_encode_device: null argument");
+    if (const char* why = jpeg_enc_shape_error(width, height, quality, h_samp, v_samp)) return fail(c, SS_ERR_INVALID, std::string("ss_jpeg_entropy_encode_device: ") + why);
+    const size_t bound = ss_jpeg_encode_bound_impl(width, height, h_samp, v_samp);
+    if (out_cap < bound)
+        return fail(c, SS_ERR_INVALID, "ss_jpeg_entropy_encode_device: out_cap " + std::to_string(out_cap) + " is below the bound " + std::to_string(bound));
+    std::string err;
+    const int rc = ss_jpeg_entropy_encode_device_impl(&c->jpeg_enc, c->stream, coef, quality, width, height, h_samp, v_samp, out, out_size, err);
     return rc == SS_OK ? rc : fail(c, rc, err);
 }
 

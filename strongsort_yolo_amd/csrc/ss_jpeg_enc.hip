@@ -9,6 +9,12 @@
 // What crosses to the host is the SPARSE stream (a 32-bit offset per block, a 32-bit entry per non-zero coefficient).  The serial
 // part, Huffman coding with the Annex K tables, runs on the call's host threads, whole images per thread.
 // Every value is an integer; the files equal libjpeg-turbo's defaults (JDCT_ISLOW, standard tables) byte for byte.
+//
+// ss_jpeg_encode_batch_device (docs/JPEG.md section 13) keeps the entropy stage on the device as well: from k_jpegenc_fdct's dense blocks
+//   k_jpegenc_hlen   a wave per block: the block's bit length (DC difference against the nearest earlier real block of its component)
+//   k_jpegenc_hwrite exclusive scan of the lengths per image (64-bit positions), every block's bits ORed into the zeroed unstuffed stream
+//   k_jpegenc_ffcount / k_jpegenc_stuff   the FF bytes counted per chunk, then every byte moved to its place with a 00 behind each FF
+// and only the files' own bytes cross to the host.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -399,6 +405,272 @@ __global__ __launch_bounds__(JENC_PACK_THREADS) void k_jpegenc_pack(const int16_
     }
 }
 
+// ---- device: the entropy stage (docs/JPEG.md section 13) -------------------------------------------------------------------
+#define JENC_HLEN_THREADS 256
+#define JENC_HLEN_BLOCKS 16             // scan positions per workgroup of k_jpegenc_hlen: four per wave
+#define JENC_HW_THREADS 1024
+#define JENC_HW_TILE 2048               // k_jpegenc_hwrite's chunks, as k_jpegenc_pack's: ceil(positions / 2048) of them, 16 at the most
+#define JENC_HW_CHUNKS 16
+#define JENC_HW_WORDS 56                // 31 bits of offset + 1658 bits of block end in word 52; a code's third word may be two further
+#define JENC_STUFF_THREADS 256
+#define JENC_STUFF_TILE 2048            // bytes per step of a workgroup of k_jpegenc_ffcount / k_jpegenc_stuff: eight per thread
+#define JENC_STUFF_CHUNKS 64            // chunks per image at the most (whole tiles each)
+#define JENC_HUFF_WORDS (2 * 256 + 2 * 12)
+
+struct JEncHuffDev { uint32_t w[JENC_HUFF_WORDS]; };              // code << 8 | length: AC luma [0, 256), AC chroma [256, 512), DC luma, DC chroma (12 each)
+struct JEncGrid { int hm, vm, mcux, nscan, bw, bh; };             // bw, bh: the real luma blocks
+
+// Words of an image's unstuffed stream: whole 8-byte units, so that every image starts 8-byte aligned and the bytes behind its last one are zero
+__device__ __host__ __forceinline__ size_t jenc_image_words(unsigned long long bits) { return (size_t)((bits + 63) >> 6) * 2; }
+// Bytes of an image's stuffed scan in the stuffed stream (16-byte aligned starts)
+__device__ __host__ __forceinline__ size_t jenc_image_room(unsigned long long bits, uint32_t ff) { return (((size_t)((bits + 7) >> 3) + ff) + 15) & ~(size_t)15; }
+
+// Scan position s: is it a real block; t its table (0 luma, 1 chroma); prev the scan position of the nearest earlier REAL block of its component
+// (-1: it is the first).  Chroma has no dummies (ceil(ceil(W / hm) / 8) == ceil(W / (8 hm))); of an MCU's hm x vm luma blocks the left
+// rw x rh are real, rw = min(hm, bw - mx hm), rh = min(vm, bh - my vm), both at least 1.
+__device__ __forceinline__ bool jenc_real(const JEncGrid& g, int s, int& t, int& prev)
+{
+    const int nl = g.hm * g.vm, bpm = nl + 2, mcu = s / bpm, j = s - mcu * bpm;
+    prev = -1;
+    if (j >= nl) { t = 1; if (mcu) prev = s - bpm; return true; }
+    t = 0;
+    const int my = mcu / g.mcux, mx = mcu - my * g.mcux, jy = j / g.hm, jx = j - jy * g.hm;
+    const int rw = min(g.hm, g.bw - mx * g.hm), rh = min(g.vm, g.bh - my * g.vm);
+    if (jx >= rw || jy >= rh) return false;
+    if (jx > 0) prev = s - 1;
+    else if (jy > 0) prev = mcu * bpm + (jy - 1) * g.hm + rw - 1;
+    else if (mcu > 0) {                                          // the last real block of the MCU before
+        const int pm = mcu - 1, pmy = pm / g.mcux, pmx = pm - pmy * g.mcux;
+        prev = pm * bpm + (min(g.vm, g.bh - pmy * g.vm) - 1) * g.hm + min(g.hm, g.bw - pmx * g.hm) - 1;
+    }
+    return true;
+}
+
+// The bits lane `lane` contributes to its block: lane 0 the DC difference v, lane k a non-zero AC coefficient v at zig-zag k with the ZRLs of
+// the zero run in front of it (nz: the lanes 1 .. 63 with a non-zero value), lane 63 with a zero the EOB.  len <= 3 * 11 + 16 + 10 = 59.
+// A category beyond baseline cannot reach this point (section 7, and the host check of the test entry); it is clamped to stay inside the tables.
+__device__ __forceinline__ void jenc_lane_code(const uint32_t* hac, const uint32_t* hdc, int lane, int v, unsigned long long nz, uint64_t& bits, int& len)
+{
+    bits = 0;
+    len = 0;
+    const int a = v < 0 ? -v : v, mag = v < 0 ? v - 1 : v;
+    int s = 32 - __clz(a);
+    if (lane == 0) {
+        s = min(s, 11);
+        const uint32_t e = hdc[s];
+        bits = ((uint64_t)(e >> 8) << s) | ((uint32_t)mag & ((1u << s) - 1u));
+        len = (int)(e & 0xffu) + s;
+    } else if (v != 0) {
+        s = min(s, 10);
+        const unsigned long long below = nz & ((1ull << lane) - 1ull);
+        const int run = lane - 1 - (below ? 63 - __clzll(below) : 0);
+        const uint32_t z = hac[0xF0], e = hac[(run & 15) << 4 | s];
+        for (int i = 0; i < (run >> 4); ++i) { bits = bits << (z & 0xffu) | (z >> 8); len += (int)(z & 0xffu); }
+        const int el = (int)(e & 0xffu) + s;
+        bits = bits << el | (uint64_t)(e >> 8) << s | ((uint32_t)mag & ((1u << s) - 1u));
+        len += el;
+    } else if (lane == 63) {
+        const uint32_t e = hac[0];
+        bits = e >> 8;
+        len = (int)(e & 0xffu);
+    }
+}
+
+// The block at scan position s of the image whose dense blocks start at d, by one wave: every lane's code; returns the block's bit length.
+// A dummy position (never written by k_jpegenc_fdct, never read here) is DC difference 0 and EOB.
+__device__ __forceinline__ uint32_t jenc_wave_block(const int16_t* __restrict__ d, const JEncGrid& g, const uint32_t* tab, int s, int lane, uint64_t& bits,
+                                                    int& len)
+{
+    int t, prev, v = 0;
+    if (jenc_real(g, s, t, prev)) {
+        v = d[(size_t)s * 64 + lane];
+        if (lane == 0 && prev >= 0) v -= d[(size_t)prev * 64];
+    }
+    const unsigned long long nz = __ballot(lane > 0 && v != 0);
+    jenc_lane_code(tab + t * 256, tab + 512 + t * 12, lane, v, nz, bits, len);
+    uint32_t total = (uint32_t)len;
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) total += __shfl_xor(total, m);
+    return total;
+}
+
+// grid (ceil(scan positions / 16), images), 256 threads: a wave per block, four blocks per wave.  lens[image][position] = the block's bits;
+// bits[image] += them (an integer sum: the same whatever order the atomics land in).
+__global__ __launch_bounds__(JENC_HLEN_THREADS) void k_jpegenc_hlen(const int16_t* __restrict__ dense, const JEncGrid g, uint32_t* __restrict__ lens,
+                                                                    unsigned long long* __restrict__ bits, const JEncHuffDev T)
+{
+    __shared__ uint32_t tab[JENC_HUFF_WORDS];
+    for (int i = threadIdx.x; i < JENC_HUFF_WORDS; i += JENC_HLEN_THREADS) tab[i] = T.w[i];
+    __syncthreads();
+    const int img = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int16_t* d = dense + (size_t)img * g.nscan * 64;
+    unsigned long long sum = 0;
+    for (int b = 0; b < JENC_HLEN_BLOCKS / 4; ++b) {
+        const int s = blockIdx.x * JENC_HLEN_BLOCKS + wave * (JENC_HLEN_BLOCKS / 4) + b;
+        if (s >= g.nscan) break;                                 // (the same in every lane of the wave)
+        uint64_t cb;
+        int cl;
+        const uint32_t L = jenc_wave_block(d, g, tab, s, lane, cb, cl);
+        if (lane == 0) lens[(size_t)img * g.nscan + s] = L;
+        sum += L;
+    }
+    if (lane == 0 && sum) atomicAdd(bits + img, sum);
+}
+
+__device__ __forceinline__ void jenc_wave_sync()                 // orders one wave's LDS accesses among its lanes (the hardware serves them in order)
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// grid (chunks, images), 1024 threads.  A workgroup owns the scan positions [chunk * blockIdx.x, chunk * (blockIdx.x + 1)) of its image: it sums the
+// lengths before them (64 bits: 3.1 M positions x 1658 bits pass 2^32), scans its own 1024 at a time into LDS and writes its blocks: a wave per
+// block, a lane per code, the block's bits merged in the wave's LDS words and every non-zero word ORed into the image's zeroed, big-endian
+// stream (atomicOr: the first and the last word are shared with the neighbours; OR does not care in which order they arrive).  The images'
+// streams follow each other, jenc_image_words(bits[j]) each.  The workgroup of the last chunk pads the last byte with 1-bits.
+__global__ __launch_bounds__(JENC_HW_THREADS) void k_jpegenc_hwrite(const int16_t* __restrict__ dense, const uint32_t* __restrict__ lens,
+                                                                    const unsigned long long* __restrict__ bits, uint32_t* ustream, const JEncGrid g, int chunk,
+                                                                    const JEncHuffDev T)
+{
+    __shared__ uint32_t tab[JENC_HUFF_WORDS];
+    __shared__ uint32_t red[JENC_HW_THREADS / 64];
+    __shared__ unsigned long long tpos[JENC_HW_THREADS];
+    __shared__ uint32_t wbuf[JENC_HW_THREADS / 64][JENC_HW_WORDS];
+    const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nscan = g.nscan, s0 = blockIdx.x * chunk, s1 = min(s0 + chunk, nscan);
+    for (int i = tid; i < JENC_HUFF_WORDS; i += JENC_HW_THREADS) tab[i] = T.w[i];
+    const int16_t* d = dense + (size_t)img * nscan * 64;
+    const uint32_t* l = lens + (size_t)img * nscan;
+    size_t base = 0;
+    for (int j = 0; j < img; ++j) base += jenc_image_words(bits[j]);
+    const unsigned long long total = bits[img];
+    const size_t room = jenc_image_words(total);                 // what the host sized the image's words by
+    uint32_t* out = ustream + base;
+    uint32_t acc = 0;                                            // at most 3072 lengths per thread, 64 threads per wave: below 2^32
+    for (int i = tid; i < s0; i += JENC_HW_THREADS) acc += l[i];
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) acc += __shfl_xor(acc, m);
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    unsigned long long run = 0;
+    for (int k = 0; k < JENC_HW_THREADS / 64; ++k) run += red[k];
+    __syncthreads();
+    for (int t0 = s0; t0 < s1; t0 += JENC_HW_THREADS) {
+        const int i = t0 + tid;
+        const uint32_t v = i < s1 ? l[i] : 0u, incl = jenc_wave_scan(v, lane);
+        if (lane == 63) red[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, tile = 0;
+        for (int k = 0; k < JENC_HW_THREADS / 64; ++k) { before += k < wave ? red[k] : 0u; tile += red[k]; }
+        tpos[tid] = run + before + incl - v;
+        run += tile;
+        __syncthreads();
+        for (int b = 0; b < 64; ++b) {
+            const int s = t0 + wave * 64 + b;
+            if (s >= s1) break;                                  // (the same in every lane of the wave; no workgroup barrier inside)
+            const unsigned long long pos = tpos[wave * 64 + b];
+            uint64_t cb;
+            int cl;
+            (void)jenc_wave_block(d, g, tab, s, lane, cb, cl);
+            const uint32_t r = (uint32_t)(pos & 31u) + jenc_wave_scan((uint32_t)cl, lane) - (uint32_t)cl;     // the code's first bit, from the word of `pos`
+            if (lane < JENC_HW_WORDS) wbuf[wave][lane] = 0u;
+            jenc_wave_sync();
+            if (cl) {
+                const uint64_t x = cb << (64 - cl);              // top-aligned; the 96-bit window that starts at word r / 32 holds x << (32 - r % 32)
+                const uint32_t w0 = r >> 5, sh = r & 31u;
+                const uint32_t a0 = (uint32_t)(x >> (32 + sh)), a1 = (uint32_t)(x >> sh), a2 = (uint32_t)((x << (32 - sh)) & 0xffffffffull);
+                if (a0) atomicOr(&wbuf[wave][w0], a0);
+                if (a1) atomicOr(&wbuf[wave][w0 + 1], a1);
+                if (a2) atomicOr(&wbuf[wave][w0 + 2], a2);
+            }
+            jenc_wave_sync();
+            if (lane < JENC_HW_WORDS) {
+                const uint32_t w = wbuf[wave][lane];
+                const size_t at = (size_t)(pos >> 5) + lane;
+                if (w && at < room) atomicOr(out + at, __builtin_bswap32(w));
+            }
+            jenc_wave_sync();
+        }
+        __syncthreads();
+    }
+    if (s1 == nscan && tid == 0 && (total & 7u)) {
+        const uint32_t pad = 8u - (uint32_t)(total & 7u), sh = (uint32_t)(total & 31u);
+        atomicOr(out + (size_t)(total >> 5), __builtin_bswap32(((1u << pad) - 1u) << (32u - sh - pad)));
+    }
+}
+
+__device__ __forceinline__ uint32_t jenc_ff_bytes(uint32_t w)
+{
+    return (uint32_t)((w & 0xffu) == 0xffu) + (uint32_t)((w & 0xff00u) == 0xff00u) + (uint32_t)((w & 0xff0000u) == 0xff0000u) + (uint32_t)(w >= 0xff000000u);
+}
+
+// grid (chunks, images), 256 threads.  A workgroup counts the FF bytes in the unstuffed bytes [chunk * blockIdx.x, chunk * (blockIdx.x + 1)) of
+// its image (chunk: whole tiles of 2048 bytes): ffc[image][chunk], and fft[image] += it.  The bytes behind an image's last one are zero.
+__global__ __launch_bounds__(JENC_STUFF_THREADS) void k_jpegenc_ffcount(const uint32_t* __restrict__ ustream, const unsigned long long* __restrict__ bits,
+                                                                        uint32_t* __restrict__ ffc, uint32_t* __restrict__ fft, uint32_t chunk)
+{
+    __shared__ uint32_t red[JENC_STUFF_THREADS / 64];
+    const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    size_t base = 0;
+    for (int j = 0; j < img; ++j) base += jenc_image_words(bits[j]);
+    const uint32_t nbytes = (uint32_t)((bits[img] + 7) >> 3);
+    const unsigned long long b0 = (unsigned long long)blockIdx.x * chunk, b1 = b0 + chunk < nbytes ? b0 + chunk : nbytes;
+    const uint8_t* src = (const uint8_t*)(ustream + base);
+    uint32_t c = 0;
+    for (unsigned long long o = b0 + (unsigned long long)tid * 8; o < b1; o += JENC_STUFF_TILE) {
+        const uint2 w = *(const uint2*)(src + o);
+        c += jenc_ff_bytes(w.x) + jenc_ff_bytes(w.y);
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m);
+    if (lane == 0) red[wave] = c;
+    __syncthreads();
+    if (tid == 0) {
+        c = 0;
+        for (int k = 0; k < JENC_STUFF_THREADS / 64; ++k) c += red[k];
+        ffc[img * JENC_STUFF_CHUNKS + blockIdx.x] = c;
+        if (c) atomicAdd(fft + img, c);
+    }
+}
+
+// The same grid.  Byte i of the image goes to i + (the FF bytes before i), a 00 behind every FF: the counts of the chunks before, then a scan of
+// the threads' own counts per tile.  The images' stuffed scans follow each other, jenc_image_room(bits[j], fft[j]) bytes each.
+__global__ __launch_bounds__(JENC_STUFF_THREADS) void k_jpegenc_stuff(const uint32_t* __restrict__ ustream, const unsigned long long* __restrict__ bits,
+                                                                      const uint32_t* __restrict__ ffc, const uint32_t* __restrict__ fft,
+                                                                      uint8_t* __restrict__ stuffed, uint32_t chunk)
+{
+    __shared__ uint32_t red[JENC_STUFF_THREADS / 64];
+    const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    size_t base = 0, sbase = 0;
+    for (int j = 0; j < img; ++j) { base += jenc_image_words(bits[j]); sbase += jenc_image_room(bits[j], fft[j]); }
+    const uint32_t nbytes = (uint32_t)((bits[img] + 7) >> 3);
+    const unsigned long long room = (unsigned long long)nbytes + fft[img];          // what the host sized the image's bytes by
+    const unsigned long long b0 = (unsigned long long)blockIdx.x * chunk, b1 = b0 + chunk < nbytes ? b0 + chunk : nbytes;
+    const uint8_t* src = (const uint8_t*)(ustream + base);
+    uint8_t* dst = stuffed + sbase;
+    unsigned long long pre = 0;
+    for (int k = 0; k < (int)blockIdx.x; ++k) pre += ffc[img * JENC_STUFF_CHUNKS + k];
+    for (unsigned long long t0 = b0; t0 < b1; t0 += JENC_STUFF_TILE) {
+        const unsigned long long o = t0 + (unsigned long long)tid * 8;
+        uint2 w = make_uint2(0u, 0u);
+        if (o < b1) w = *(const uint2*)(src + o);
+        const uint32_t c = jenc_ff_bytes(w.x) + jenc_ff_bytes(w.y), incl = jenc_wave_scan(c, lane);
+        if (lane == 63) red[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, tile = 0;
+        for (int k = 0; k < JENC_STUFF_THREADS / 64; ++k) { before += k < wave ? red[k] : 0u; tile += red[k]; }
+        unsigned long long at = o + pre + before + incl - c;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t v = ((k < 4 ? w.x : w.y) >> (8 * (k & 3))) & 0xffu;
+            if (o + k < b1 && at < room) dst[at++] = (uint8_t)v;
+            if (o + k < b1 && v == 0xffu && at < room) dst[at++] = 0;
+        }
+        pre += tile;
+        __syncthreads();
+    }
+}
+
 // ---- host: the batch call --------------------------------------------------------------------------------------------------
 struct SSJpegEnc {
     struct Slot {
@@ -411,11 +683,34 @@ struct SSJpegEnc {
         hipEvent_t ev = nullptr;
     } slot[2];
     int next = 0;
+    struct DSlot {                                              // ss_jpeg_encode_batch_device's own two slots (section 13)
+        int16_t* dense = nullptr; size_t dense_cap = 0;
+        uint32_t* cnt = nullptr; size_t cnt_cap = 0;            // k_jpegenc_fdct's counts (written, not used on this path)
+        uint32_t* lens = nullptr; size_t lens_cap = 0;          // every block's bit length
+        uint32_t* small = nullptr;                              // device: bits [64] (64-bit), totals [64], fft [64], ffc [64][64]
+        uint32_t* h_small = nullptr;                            // pinned: bits [64] (64-bit), fft [64]
+        uint32_t* ustream = nullptr; size_t ustream_cap = 0;    // the unstuffed streams, zeroed by every call
+        uint8_t* stuffed = nullptr; size_t stuffed_cap = 0;     // the stuffed scans
+        void* host = nullptr; size_t host_cap = 0;              // their pinned mirror
+        hipEvent_t ev = nullptr;
+    } dslot[2];
+    int dnext = 0;
 };
 
 void ss_jpeg_enc_free(SSJpegEnc* j)
 {
     if (!j) return;
+    for (auto& st : j->dslot) {
+        if (st.ev) (void)hipEventDestroy(st.ev);
+        if (st.host) (void)hipHostFree(st.host);
+        if (st.h_small) (void)hipHostFree(st.h_small);
+        if (st.stuffed) (void)hipFree(st.stuffed);
+        if (st.ustream) (void)hipFree(st.ustream);
+        if (st.small) (void)hipFree(st.small);
+        if (st.lens) (void)hipFree(st.lens);
+        if (st.cnt) (void)hipFree(st.cnt);
+        if (st.dense) (void)hipFree(st.dense);
+    }
     for (auto& st : j->slot) {
         if (st.ev) (void)hipEventDestroy(st.ev);
         if (st.host) (void)hipHostFree(st.host);
@@ -510,6 +805,174 @@ int ss_jpeg_encode_impl(SSJpegEnc** state, hipStream_t stream, const void* d_in,
         return SS_OK;
     } catch (...) {
         err = "ss_jpeg_encode_batch: out of memory";
+        return SS_ERR_INVALID;
+    }
+}
+
+// ---- host: the batch call with the entropy stage on the device (docs/JPEG.md section 13) -------------------------------------
+static const JEncHuffDev kEncDev = [] {
+    JEncHuffDev d;
+    for (int t = 0; t < 2; ++t) {
+        for (int s = 0; s < 256; ++s) d.w[t * 256 + s] = (uint32_t)kEnc.ac[t].code[s] << 8 | kEnc.ac[t].len[s];
+        for (int s = 0; s < 12; ++s) d.w[512 + t * 12 + s] = (uint32_t)kEnc.dc[t].code[s] << 8 | kEnc.dc[t].len[s];
+    }
+    return d;
+}();
+
+#define JDCHK(x)                                                                                             \
+    do {                                                                                                     \
+        hipError_t e_ = (x);                                                                                 \
+        if (e_ != hipSuccess) { err = std::string(who) + ": " #x ": " + hipGetErrorString(e_); return SS_ERR_HIP; } \
+    } while (0)
+
+static int jenc_dslot(SSJpegEnc::DSlot& st, const char* who, size_t blocks, std::string& err)
+{
+    if (!st.ev) JDCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    if (!st.small) JDCHK(hipMalloc((void**)&st.small, (256 + 64 * JENC_STUFF_CHUNKS) * sizeof(uint32_t)));
+    if (!st.h_small) JDCHK(hipHostMalloc((void**)&st.h_small, 192 * sizeof(uint32_t), hipHostMallocDefault));
+    JDCHK(jenc_grow(st.dense, st.dense_cap, blocks * 64 * sizeof(int16_t)));
+    JDCHK(jenc_grow(st.lens, st.lens_cap, blocks * sizeof(uint32_t)));
+    return SS_OK;
+}
+
+// Steps 1 .. 6 of section 13 on the n images whose dense blocks are in st.dense.  Three waits on the slot's event: the bit totals size the
+// unstuffed stream, the FF totals size the stuffed one, its pinned mirror and the copy, and the copy has to arrive.
+static int jenc_entropy_device(SSJpegEnc::DSlot& st, hipStream_t stream, const char* who, int n, const JEncShape& shape, const uint16_t (&q)[2][64], int threads,
+                               unsigned char* const* out, size_t* out_size, std::string& err)
+{
+    const int nscan = shape.nscan;
+    const JEncGrid g{shape.hm, shape.vm, shape.mcux, nscan, shape.bw[0], shape.bh[0]};
+    unsigned long long* d_bits = (unsigned long long*)st.small;
+    uint32_t *d_fft = st.small + 192, *d_ffc = st.small + 256;
+    const unsigned long long* h_bits = (const unsigned long long*)st.h_small;
+    const uint32_t* h_fft = st.h_small + 128;
+    // ---- 1. every block's bit length; the images' bit totals decide the size of the unstuffed stream ----
+    JDCHK(hipMemsetAsync(d_bits, 0, n * sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(k_jpegenc_hlen, dim3((nscan + JENC_HLEN_BLOCKS - 1) / JENC_HLEN_BLOCKS, n), dim3(JENC_HLEN_THREADS), 0, stream, st.dense, g, st.lens, d_bits,
+                       kEncDev);
+    JDCHK(hipGetLastError());
+    JDCHK(hipMemcpyAsync(st.h_small, d_bits, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    JDCHK(hipEventRecord(st.ev, stream));
+    JDCHK(hipEventSynchronize(st.ev));
+    size_t words = 0, most = 0;
+    for (int i = 0; i < n; ++i) {
+        words += jenc_image_words(h_bits[i]);
+        const size_t b = (size_t)((h_bits[i] + 7) >> 3);
+        if (b > most) most = b;
+    }
+    JDCHK(jenc_grow(st.ustream, st.ustream_cap, words * 4));
+    // ---- 2. scan + write into the zeroed stream, the FF bytes counted; their totals decide the size of everything that follows ----
+    JDCHK(hipMemsetAsync(st.ustream, 0, words * 4, stream));
+    JDCHK(hipMemsetAsync(d_fft, 0, n * sizeof(uint32_t), stream));
+    const int chunks = nscan < JENC_HW_CHUNKS * JENC_HW_TILE ? (nscan + JENC_HW_TILE - 1) / JENC_HW_TILE : JENC_HW_CHUNKS, chunk = (nscan + chunks - 1) / chunks;
+    hipLaunchKernelGGL(k_jpegenc_hwrite, dim3(chunks, n), dim3(JENC_HW_THREADS), 0, stream, st.dense, st.lens, d_bits, st.ustream, g, chunk, kEncDev);
+    JDCHK(hipGetLastError());
+    const size_t tiles = (most + JENC_STUFF_TILE - 1) / JENC_STUFF_TILE, per = (tiles + JENC_STUFF_CHUNKS - 1) / JENC_STUFF_CHUNKS;
+    const uint32_t bchunk = (uint32_t)(per * JENC_STUFF_TILE);
+    const int bchunks = (int)((most + bchunk - 1) / bchunk);
+    hipLaunchKernelGGL(k_jpegenc_ffcount, dim3(bchunks, n), dim3(JENC_STUFF_THREADS), 0, stream, st.ustream, d_bits, d_ffc, d_fft, bchunk);
+    JDCHK(hipGetLastError());
+    JDCHK(hipMemcpyAsync(st.h_small + 128, d_fft, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    JDCHK(hipEventRecord(st.ev, stream));
+    JDCHK(hipEventSynchronize(st.ev));
+    size_t bytes = 0;
+    std::vector<size_t> at(n);
+    for (int i = 0; i < n; ++i) { at[i] = bytes; bytes += jenc_image_room(h_bits[i], h_fft[i]); }
+    JDCHK(jenc_grow(st.stuffed, st.stuffed_cap, bytes));
+    if (st.host_cap < bytes) {
+        if (st.host) { JDCHK(hipHostFree(st.host)); st.host = nullptr; st.host_cap = 0; }
+        const size_t cap = bytes + bytes / 4;
+        JDCHK(hipHostMalloc(&st.host, cap, hipHostMallocDefault));
+        st.host_cap = cap;
+    }
+    // ---- 3. stuffing, ONE copy of exactly the used size ----
+    hipLaunchKernelGGL(k_jpegenc_stuff, dim3(bchunks, n), dim3(JENC_STUFF_THREADS), 0, stream, st.ustream, d_bits, d_ffc, d_fft, st.stuffed, bchunk);
+    JDCHK(hipGetLastError());
+    JDCHK(hipMemcpyAsync(st.host, st.stuffed, bytes, hipMemcpyDeviceToHost, stream));
+    JDCHK(hipEventRecord(st.ev, stream));
+    JDCHK(hipEventSynchronize(st.ev));
+    // ---- 4. header, scan, EOI: whole images per thread ----
+    const uint8_t* base = (const uint8_t*)st.host;
+    auto write = [&](int t, int nt) {
+        for (int i = t; i < n; i += nt) {
+            const size_t len = (size_t)((h_bits[i] + 7) >> 3) + h_fft[i];
+            uint8_t* p = jenc_header(out[i], shape, q);
+            memcpy(p, base + at[i], len);
+            p += len;
+            *p++ = 0xFF; *p++ = 0xD9;
+            out_size[i] = (size_t)(p - out[i]);
+        }
+    };
+    if (!run_threads(threads < n ? threads : n, write)) { err = std::string(who) + ": host copy failed"; return SS_ERR_INVALID; }
+    return SS_OK;
+}
+
+// The arguments have been checked (ss_api.hip).  Returns an SS_* code, the message in err.
+int ss_jpeg_encode_device_impl(SSJpegEnc** state, hipStream_t stream, const void* d_in, long long in_frame_stride, int n, int height, int width, int rgb,
+                               int quality, int h_samp, int v_samp, int threads, unsigned char* const* out, size_t* out_size, std::string& err)
+{
+    const char* who = "ss_jpeg_encode_batch_device";
+    try {
+        if (!*state) *state = new SSJpegEnc();
+        SSJpegEnc& S = **state;
+        const JEncShape shape(width, height, h_samp, v_samp);
+        const int nscan = shape.nscan;
+        JEncParams P;
+        jenc_quant(quality, P.q);
+        for (int t = 0; t < 2; ++t)
+            for (int k = 0; k < 64; ++k) P.recip[t][k] = (uint32_t)((1ull << 32) / ((uint32_t)P.q[t][k] << 3)) + 1u;
+        for (int k = 0; k < 64; ++k) P.zz[kZigzag[k]] = (uint8_t)k;
+        SSJpegEnc::DSlot& st = S.dslot[S.dnext];
+        if (const int rc = jenc_dslot(st, who, (size_t)n * nscan, err)) return rc;
+        JDCHK(jenc_grow(st.cnt, st.cnt_cap, (size_t)n * nscan * sizeof(uint32_t)));
+        uint32_t* totals = st.small + 128;                       // (k_jpegenc_fdct's entry totals: written, not used on this path)
+        JDCHK(hipMemsetAsync(totals, 0, n * sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(k_jpegenc_fdct, dim3((nscan + 31) / 32, n), dim3(256), 0, stream, (const uint8_t*)d_in, in_frame_stride, height, width, rgb, h_samp,
+                           v_samp, shape.mcux, nscan, st.dense, st.cnt, totals, P);
+        JDCHK(hipGetLastError());
+        S.dnext ^= 1;
+        return jenc_entropy_device(st, stream, who, n, shape, P.q, threads, out, out_size, err);
+    } catch (...) {
+        err = std::string(who) + ": out of memory";
+        return SS_ERR_INVALID;
+    }
+}
+
+// The entropy stage alone on one image's coefficients (ss_jpeg_coefficients' layout), for tests.  Categories beyond baseline are refused here,
+// before anything is launched, with the host writer's message.
+int ss_jpeg_entropy_encode_device_impl(SSJpegEnc** state, hipStream_t stream, const short* coef, int quality, int width, int height, int h_samp, int v_samp,
+                                       unsigned char* out, size_t* out_size, std::string& err)
+{
+    const char* who = "ss_jpeg_entropy_encode_device";
+    try {
+        if (!*state) *state = new SSJpegEnc();
+        SSJpegEnc& S = **state;
+        const JEncShape shape(width, height, h_samp, v_samp);
+        uint16_t q[2][64];
+        jenc_quant(quality, q);
+        std::vector<int16_t> dense((size_t)shape.nscan * 64, 0);  // scan order, zig-zag order: what k_jpegenc_fdct leaves
+        const size_t ybl = (size_t)shape.mcux * shape.hm * shape.mcuy * shape.vm, cbl = (size_t)shape.mcux * shape.mcuy;
+        int pred[3] = {0, 0, 0}, s = 0;
+        for (int my = 0; my < shape.mcuy; ++my)
+            for (int mx = 0; mx < shape.mcux; ++mx)
+                for (int j = 0; j < shape.bpm; ++j, ++s) {
+                    const int comp = j < shape.hm * shape.vm ? 0 : 1 + j - shape.hm * shape.vm, t = comp ? 1 : 0;
+                    const int by = comp ? my : my * shape.vm + j / shape.hm, bx = comp ? mx : mx * shape.hm + j % shape.hm;
+                    if (by >= shape.bh[t] || bx >= shape.bw[t]) continue;
+                    const short* c = coef + (comp == 0 ? ((size_t)by * shape.mcux * shape.hm + bx) : ybl + (comp - 1) * cbl + (size_t)by * shape.mcux + bx) * 64;
+                    int16_t* o = dense.data() + (size_t)s * 64;
+                    bool ok = jenc_category(c[0] - pred[comp]) <= 11;
+                    pred[comp] = c[0];
+                    for (int k = 0; k < 64; ++k) { o[k] = c[kZigzag[k]]; if (k && jenc_category(o[k]) > 10) ok = false; }
+                    if (!ok) { err = std::string(who) + ": a coefficient beyond the baseline categories (DC difference 11 bits, AC 10 bits)"; return SS_ERR_INVALID; }
+                }
+        SSJpegEnc::DSlot& st = S.dslot[S.dnext];
+        if (const int rc = jenc_dslot(st, who, (size_t)shape.nscan, err)) return rc;
+        JDCHK(hipMemcpyAsync(st.dense, dense.data(), dense.size() * sizeof(int16_t), hipMemcpyHostToDevice, stream));
+        S.dnext ^= 1;
+        return jenc_entropy_device(st, stream, who, 1, shape, q, 1, &out, out_size, err);      // (its first wait is behind the upload: `dense` outlives it)
+    } catch (...) {
+        err = std::string(who) + ": out of memory";
         return SS_ERR_INVALID;
     }
 }

@@ -158,12 +158,17 @@ class TrackerEngine:
         call = self.L.ss_jpeg_decode_batch_device if entropy == "device" else self.L.ss_jpeg_decode_batch
         self._ck(call(self.ctx, self._st(stream), data, sizes, n, shape[0], shape[1], _ptr(dst), stride, int(bool(rgb)), int(threads)))
 
-    def jpeg_encode_batch(self, src: torch.Tensor, quality: int = 85, subsampling: str = "4:2:0", stream=None, threads: int = 4, rgb: bool = False):
+    def jpeg_encode_batch(self, src: torch.Tensor, quality: int = 85, subsampling: str = "4:2:0", stream=None, threads: int = 4, rgb: bool = False,
+                          entropy: str = "host"):
         """src: device uint8 [n, H, W, 3] (n 1 .. 64, every frame contiguous) or [H, W, 3], BGR (rgb=True: RGB) -> n baseline JPEG
         files as bytes, equal to what Pillow writes at that quality and subsampling ("4:2:0" | "4:2:2" | "4:4:4"): colour
         conversion, downsampling, forward DCT, quantisation and compaction on the device (csrc/ss_jpeg_enc.hip), the sparse
-        coefficients back in one copy, Huffman coding on `threads` host threads.  Returns when the files are written."""
+        coefficients back in one copy, Huffman coding on `threads` host threads.  Returns when the files are written.
+        entropy="device": Huffman coding and byte stuffing run on the device too (docs/JPEG.md §13); only the scans' own bytes come
+        back and the host threads write the headers and copy.  The same files."""
         from .jpeg import SUBSAMPLING
+        if entropy not in ("host", "device"):
+            raise ValueError(f"jpeg_encode_batch: entropy {entropy!r} (\"host\" or \"device\")")
         if subsampling not in SUBSAMPLING:
             raise ValueError(f"jpeg_encode_batch: subsampling {subsampling!r} (one of {', '.join(SUBSAMPLING)})")
         hs, vs = SUBSAMPLING[subsampling]
@@ -180,8 +185,8 @@ class TrackerEngine:
         cap = (C.c_size_t * max(n, 1))(*([bound] * n))
         size = (C.c_size_t * max(n, 1))()
         stride = fr.stride(0) if n > 1 else H * W * 3
-        self._ck(self.L.ss_jpeg_encode_batch(self.ctx, self._st(stream), _ptr(fr), stride, n, H, W, int(bool(rgb)), int(quality), hs, vs, int(threads),
-                                             out, cap, size))
+        call = self.L.ss_jpeg_encode_batch_device if entropy == "device" else self.L.ss_jpeg_encode_batch
+        self._ck(call(self.ctx, self._st(stream), _ptr(fr), stride, n, H, W, int(bool(rgb)), int(quality), hs, vs, int(threads), out, cap, size))
         return [files[i, :size[i]].tobytes() for i in range(n)]
 
     def download(self, dst: np.ndarray, src: torch.Tensor, stream=None):

@@ -7,7 +7,8 @@
     t = decode(engine, frames)                      uint8 device tensor [n, H, W, 3], BGR (rgb=True: RGB); entropy="device": Huffman
                                                     decoding on the device too (docs/JPEG.md §12)
     raw, segs, hdr = scan_segments(data)            host only: the host's share of that stage (unstuffed scan cut at its restart markers)
-    files = encode(engine, frames, quality=85)      frames on the device (or host arrays) -> baseline JPEG files as bytes (csrc/ss_jpeg_enc.hip)
+    files = encode(engine, frames, quality=85)      frames on the device (or host arrays) -> baseline JPEG files as bytes (csrc/ss_jpeg_enc.hip);
+                                                    entropy="device": Huffman coding on the device too (docs/JPEG.md §13)
 
 `YOLO.track_stream` takes EncodedFrames in place of arrays: the group is decoded straight into the buffer the detector reads.
 """
@@ -148,10 +149,13 @@ def device_coefficients(engine, data):
     return coef, list(rounds[:min(n, 4096)])
 
 
-def encode(engine, frames, quality: int = 85, subsampling: str = "4:2:0", stream=None, threads: int = 4, rgb: bool = False):
+def encode(engine, frames, quality: int = 85, subsampling: str = "4:2:0", stream=None, threads: int = 4, rgb: bool = False, entropy: str = "host"):
     """Any number of frames of one size -> list of baseline JPEG files (bytes), byte for byte what Pillow writes with
     `quality=quality, subsampling=subsampling`.  `frames`: a uint8 tensor [n, H, W, 3] (or a sequence of [H, W, 3] tensors / arrays),
-    BGR unless rgb=True; what is not on the engine's device yet is uploaded first.  Encoded in chunks of MAX_BATCH."""
+    BGR unless rgb=True; what is not on the engine's device yet is uploaded first.  Encoded in chunks of MAX_BATCH.
+    entropy: "host" (Huffman coding on the host threads) or "device" (on the device too, docs/JPEG.md §13); the same bytes."""
+    if entropy not in ("host", "device"):
+        raise ValueError(f"jpeg.encode: entropy {entropy!r} (\"host\" or \"device\")")
     import numpy as np
     import torch
     if not isinstance(frames, (torch.Tensor, np.ndarray)):
@@ -168,5 +172,26 @@ def encode(engine, frames, quality: int = 85, subsampling: str = "4:2:0", stream
     frames = frames.to(engine.device).contiguous()
     out = []
     for k in range(0, frames.shape[0], MAX_BATCH):
-        out += engine.jpeg_encode_batch(frames[k:k + MAX_BATCH], quality, subsampling, stream, threads, rgb)
+        out += engine.jpeg_encode_batch(frames[k:k + MAX_BATCH], quality, subsampling, stream, threads, rgb, entropy)
     return out
+
+
+def entropy_encode_device(engine, coef, quality: int, width: int, height: int, subsampling: str = "4:2:0") -> bytes:
+    """The device entropy stage alone, for tests: dense natural-order int16 blocks in ss_jpeg_coefficients' layout (component after
+    component, each over its whole-MCU grid) -> the whole file.  The device twin of the library's host-only ss_jpeg_entropy_encode;
+    coefficients beyond the baseline categories are refused (engine's error) before anything is launched."""
+    import numpy as np
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"jpeg.entropy_encode_device: subsampling {subsampling!r} (one of {', '.join(SUBSAMPLING)})")
+    hs, vs = SUBSAMPLING[subsampling]
+    coef = np.ascontiguousarray(coef, dtype=np.int16).reshape(-1)
+    blocks = -(-int(width) // (8 * hs)) * -(-int(height) // (8 * vs)) * (hs * vs + 2)
+    if coef.size != blocks * 64:
+        raise ValueError(f"jpeg.entropy_encode_device: {coef.size} values, the shape has {blocks} blocks of 64")
+    bound = int(engine.L.ss_jpeg_encode_bound(int(width), int(height), hs, vs))
+    if bound < 0:
+        lib.check(None, bound)
+    out, size = np.empty(bound, np.uint8), C.c_size_t()
+    engine._ck(engine.L.ss_jpeg_entropy_encode_device(engine.ctx, coef.ctypes.data_as(C.POINTER(C.c_short)), int(quality), int(width), int(height), hs, vs,
+                                                      out.ctypes.data, bound, C.byref(size)))
+    return out[:size.value].tobytes()

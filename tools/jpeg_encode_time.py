@@ -2,15 +2,18 @@
 
 The frames: the 32 rendered synthetic 1280x720 frames of tools/jpeg_time.py (its decoded arrays), on the device; 4:2:0, quality 85.
 
-  --mode host     wall time of engine.jpeg_encode_batch on groups of 32 at threads 1, 4 and 16 (the call returns when the files are
-                  written: two launches, the copy of the sparse coefficients, Huffman coding), the time of the same call's device part
-                  alone (threads do not matter there: measured as the call on 32 flat frames, whose entropy stage is a few EOBs), the
-                  bytes that cross PCIe per frame, and — when Pillow is importable — whether the files equal Pillow's
-  --mode kernel   the same call in a loop and nothing else; for the kernels' own times run it under
+  --mode host     wall time of engine.jpeg_encode_batch on groups of 32: the host entropy stage at threads 1, 4 and 16 (the call returns
+                  when the files are written: two launches, the copy of the sparse coefficients, Huffman coding) and the device entropy
+                  stage (entropy="device", docs/JPEG.md §13) at threads 1 and 4, the five legs interleaved group by group in one
+                  process; the same two calls on 32 flat frames (next to no entropy coding: launches, waits, copies and the wrapper);
+                  the bytes that cross PCIe per frame for both stages, and — when Pillow is importable — whether the files equal Pillow's
+  --mode kernel   both calls in a loop and nothing else; for the kernels' own times (k_jpegenc_fdct, k_jpegenc_pack and the entropy
+                  stage's k_jpegenc_hlen, k_jpegenc_hwrite, k_jpegenc_ffcount, k_jpegenc_stuff) run it under
                   `rocprofv3 --kernel-trace --stats -- python tools/jpeg_encode_time.py --mode kernel` (no counters in that run)
-  --mode rates    cli.process_video frames/s (bytetrack, yolov8n with seeded random-init weights, batch 32) with three sinks in ONE
-                  process, the legs interleaved over --rounds: --save x.bgr (the raw download), --save x.mjpeg --device-encode, and the
-                  raw download followed by Pillow's encoder on the host at the same quality (needs Pillow)
+  --mode rates    cli.process_video frames/s (bytetrack, yolov8n with seeded random-init weights, batch 32) with four sinks in ONE
+                  process, the legs interleaved over --rounds: (a) --save x.bgr (the raw download), (b) --save x.mjpeg --device-encode,
+                  (c) the raw download followed by Pillow's encoder on the host at the same quality (needs Pillow), (d) --save x.mjpeg
+                  --device-encode --device-encode-entropy
 """
 import argparse
 import ctypes as C
@@ -57,26 +60,35 @@ def host(groups, warmup):
     res = {"mode": "host", "frame": f"1280x720 {SUB} q{Q}", "group_frames": G, "raw_frame_bytes": 3 * 720 * 1280}
     files = None
 
-    def timed(src, th):
-        ms = []
+    def timed(src, legs):
+        """legs: (entropy, threads); interleaved group by group -> {leg: [ms]}, {leg: the last files}."""
+        ms, out = {leg: [] for leg in legs}, {}
         for g in range(groups + warmup):
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            out = eng.jpeg_encode_batch(src, Q, SUB, threads=th)
-            dt = time.perf_counter() - t
-            if g >= warmup:
-                ms.append(dt * 1e3)
+            for leg in (legs if g % 2 == 0 else legs[::-1]):
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                out[leg] = eng.jpeg_encode_batch(src, Q, SUB, threads=leg[1], entropy=leg[0])
+                dt = time.perf_counter() - t
+                if g >= warmup:
+                    ms[leg].append(dt * 1e3)
         return ms, out
-    for th in (1, 4, 16):
-        ms, files = timed(x, th)
-        res[f"threads_{th}_ms_per_group"] = _spread(ms)
-        res[f"threads_{th}_frames_per_s_median"] = G / (float(np.median(ms)) * 1e-3)
-    ms, _ = timed(flat, 16)
-    res["flat_frames_ms_per_group"] = _spread(ms)             # launches, waits, copies and the Python wrapper; next to no entropy coding
+    legs = [("host", 1), ("host", 4), ("host", 16), ("device", 1), ("device", 4)]
+    ms, out = timed(x, legs)
+    files = out[("host", 16)]
+    for leg in legs:
+        name = f"threads_{leg[1]}" if leg[0] == "host" else f"device_entropy_threads_{leg[1]}"      # (the host legs keep their earlier names)
+        res[f"{name}_ms_per_group"] = _spread(ms[leg])
+        res[f"{name}_frames_per_s_median"] = G / (float(np.median(ms[leg])) * 1e-3)
+    res["device_entropy_equal_to_host"] = bool(all(out[leg] == files for leg in legs))
+    ms, _ = timed(flat, [("host", 16), ("device", 4)])
+    res["flat_frames_ms_per_group"] = _spread(ms[("host", 16)])   # launches, waits, copies and the Python wrapper; next to no entropy coding
+    res["device_entropy_flat_frames_ms_per_group"] = _spread(ms[("device", 4)])
     blocks = 80 * 45 * 6
     sb = [_stream_bytes(eng.L, f, blocks) for f in files]
     res["file_bytes_per_frame_mean"] = float(np.mean([len(f) for f in files]))
     res["downloaded_bytes_per_frame_mean"] = float(np.mean([b for b, _ in sb]))
+    # the device entropy stage copies the stuffed scan (the file without its 625 bytes of header and EOI, rounded up to 16) and 12 bytes of totals
+    res["device_entropy_downloaded_bytes_per_frame_mean"] = float(np.mean([(len(f) - 625 + 15) // 16 * 16 + 12 for f in files]))
     res["nonzero_coefficients_per_frame_mean"] = float(np.mean([n for _, n in sb]))
     try:
         res["equal_to_pillow"] = bool(all(_pillow(dec[k]) == files[k] for k in range(G)))
@@ -93,9 +105,10 @@ def kernel(groups):
     x = torch.from_numpy(np.stack(dec)).to(eng.device)
     for _ in range(groups):
         eng.jpeg_encode_batch(x, Q, SUB, threads=16)
+        eng.jpeg_encode_batch(x, Q, SUB, threads=4, entropy="device")
     torch.cuda.synchronize()
     eng.close()
-    return {"mode": "kernel", "groups": groups, "group_frames": G, "frame": f"1280x720 {SUB} q{Q}"}
+    return {"mode": "kernel", "groups": groups, "group_frames": G, "frame": f"1280x720 {SUB} q{Q}", "calls_per_group": ["entropy=host", "entropy=device"]}
 
 
 def rates(n_frames, batch, rounds):
@@ -120,7 +133,9 @@ def rates(n_frames, batch, rounds):
     plain = cli.FrameSink
     legs = {"raw_bgr_download": ({"save": os.path.join(tmp, "a.bgr")}, plain),
             "device_encode_mjpeg": ({"save": os.path.join(tmp, "b.mjpeg"), "device_encode": True, "save_quality": Q, "save_subsampling": SUB}, plain),
-            "download_then_pillow": ({"save": os.path.join(tmp, "c.pil")}, PillowSink)}
+            "download_then_pillow": ({"save": os.path.join(tmp, "c.pil")}, PillowSink),
+            "device_encode_entropy_mjpeg": ({"save": os.path.join(tmp, "d.mjpeg"), "device_encode": True, "device_encode_entropy": True, "save_quality": Q,
+                                             "save_subsampling": SUB}, plain)}
     model = YOLO("yolov8n.pt", random_init_ok=True, tracker_type="bytetrack")
 
     def run(name, limit=None):
