@@ -243,14 +243,16 @@ static bool decode_scan(const uint8_t* d, size_t n, const JInfo& J, Sink& sink, 
                 for (int bx = 0; bx < J.h[ci]; ++bx) {
                     sink.begin(ci, my * J.v[ci] + by, mx * J.h[ci] + bx);
                     b.fill();
+                    int c0 = b.cnt;                               // c0 <= b.fake: the symbol starts beyond the last real bit; it is not judged, the data has ended
                     int s = huff_sym(b, dc);
                     if (s < 0) return jfail(err, b.cnt - b.fake < 16 ? "data ends before the last MCU" : "Huffman code that does not exist");
-                    if (s > 15) return jfail(err, "bad DC category");
+                    if (s > 15) return jfail(err, c0 <= b.fake ? "data ends before the last MCU" : "bad DC category");
                     if (s) pred[ci] += receive_extend(b, s);
                     pred[ci] = (int16_t)pred[ci];
                     if (pred[ci]) sink.coef(0, pred[ci]);
                     for (int k = 1; k < 64;) {
                         b.fill();
+                        c0 = b.cnt;
                         const int rs = huff_sym(b, ac);
                         if (rs < 0) return jfail(err, b.cnt - b.fake < 16 ? "data ends before the last MCU" : "Huffman code that does not exist");
                         const int r = rs >> 4;
@@ -261,7 +263,7 @@ static bool decode_scan(const uint8_t* d, size_t n, const JInfo& J, Sink& sink, 
                             continue;
                         }
                         k += r;
-                        if (k > 63) return jfail(err, "coefficient index beyond 63");
+                        if (k > 63) return jfail(err, c0 <= b.fake ? "data ends before the last MCU" : "coefficient index beyond 63");
                         const int v = receive_extend(b, s);
                         if (v) sink.coef(kZigzag[k], v);
                         ++k;

@@ -110,6 +110,7 @@ def _decode(luts, w, bits, end, hv, bpm, state, maxbegin, sink=None):
                     v = v - (1 << s) + 1
             nel = ne
             if sink is not None:
+                assert sink.blk < sink.bend                     # `maxbegin` keeps every table store inside the lane's segment, whatever the bits say
                 if sink.e < sink.cap:
                     sink.tab[sink.blk] = sink.e
                     sink.ent[sink.e] = v & 0xFFFF
@@ -163,8 +164,9 @@ def _decode(luts, w, bits, end, hv, bpm, state, maxbegin, sink=None):
     return (p, bi, k), nb, ne, nel
 
 
-def stream(data, W=32, lanes_per_tile=LANES):
-    """The device stream of one image: (info, block table [blocks + 1], entries, rounds per tile, status word or None, capacity)."""
+def stream(data, W=32, lanes_per_tile=LANES, errors=None):
+    """The device stream of one image: (info, block table [blocks + 1], entries, rounds per tile, status word or None, capacity).
+    The status word is `(lane + 1) << 3 | cause` of the smallest lane that reports; `errors` (a list) receives every lane's word."""
     d = bytes(data)
     info = parse(d)
     raw, segs = cut(d, info)
@@ -239,6 +241,8 @@ def stream(data, W=32, lanes_per_tile=LANES):
                 s.err = 4
             if s.err:
                 key = ((tile0 + t + 1) << 3) | s.err
+                if errors is not None:
+                    errors.append(key)
                 status = key if status is None else min(status, key)
         carry_state, carry_blk, carry_ent = res[-1][0], L[-1]["b0"] + res[-1][1], carry_ent + eex[-1]
     tab[blocks] = carry_ent

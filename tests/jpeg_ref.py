@@ -4,6 +4,7 @@ upsampling).  The specification in executable form; not a test module.
     info = parse(data)                       headers: width, height, components, tables, where the scan starts
     coefs, quant, info = coefficients(data)  per component [bh, bw, 64] int16 natural-order blocks; quant [4, 64] uint16 natural order
     rgb = decode(data)                       uint8 [H, W, 3] (RGB; rgb=False: BGR); dtype=np.int64 runs the same arithmetic without wrap
+    y = prelimit(data)                       every IDCT result before the range limit (which zones of the limit does the file reach?)
 
 Everything the device refuses raises Refused with the same cause.
 """
@@ -162,25 +163,26 @@ class _Bits:
         self.i = 0
 
     def sym(self, table):
+        """The next code.  One that starts inside the data and reaches beyond it is completed with zero bits and judged like any
+        other, as the host decoder's bit reader does; one that starts beyond the data is read the same way, but `past` tells the
+        caller not to judge its symbol.  Whoever consumed such bits finds `i` beyond the data at the end of the block."""
         code, bits, i = 0, self.bits, self.i
+        self.past = i >= len(bits)
         for ln in range(1, 17):
-            if i >= len(bits):
-                raise Refused("data ends before the last MCU")
-            code = (code << 1) | bits[i]
+            code = (code << 1) | (bits[i] if i < len(bits) else 0)
             i += 1
             s = table.get((ln, code))
             if s is not None:
                 self.i = i
                 return s
-        raise Refused("Huffman code that does not exist")
+        raise Refused("data ends before the last MCU" if len(bits) - self.i < 16 else "Huffman code that does not exist")
 
     def receive_extend(self, s):
         if s == 0:
             return 0
-        if self.i + s > len(self.bits):
-            raise Refused("data ends before the last MCU")
         v = 0
-        for b in self.bits[self.i:self.i + s]:
+        got = self.bits[self.i:self.i + s]
+        for b in got + [0] * (s - len(got)):                      # (zero bits beyond the data, as in sym)
             v = (v << 1) | b
         self.i += s
         return v if v >= (1 << (s - 1)) else v - (1 << s) + 1
@@ -210,7 +212,7 @@ def coefficients(data: bytes):
                     blk = coefs[ci][my * v + by, mx * h + bx]
                     s = br.sym(dc)
                     if s > 15:
-                        raise Refused("bad DC category")
+                        raise Refused("data ends before the last MCU" if br.past else "bad DC category")
                     pred[ci] = (pred[ci] + br.receive_extend(s) + 32768) % 65536 - 32768
                     blk[0] = pred[ci]
                     k = 1
@@ -224,9 +226,11 @@ def coefficients(data: bytes):
                             continue
                         k += r
                         if k > 63:
-                            raise Refused("coefficient index beyond 63")
+                            raise Refused("data ends before the last MCU" if br.past else "coefficient index beyond 63")
                         blk[ZIGZAG[k]] = br.receive_extend(s)
                         k += 1
+                    if br.i > len(br.bits):                       # the block took bits that are not there
+                        raise Refused("data ends before the last MCU")
     return coefs, info["quant"].copy(), info
 
 
@@ -253,13 +257,23 @@ def _pass(x, s):
             (t13 - o0 + r) >> s, (t12 - o1 + r) >> s, (t11 - o2 + r) >> s, (t10 - o3 + r) >> s]
 
 
-def idct_blocks(coef, q, dtype=np.int32):
-    """coef [..., 64] int16 natural order, q [64] -> samples [..., 8, 8] uint8."""
+def idct_prelimit(coef, q, dtype=np.int32):
+    """coef [..., 64] int16 natural order, q [64] -> the second pass's results [..., 8, 8] before the range limit."""
     d = (coef.astype(dtype) * q.astype(dtype)).reshape(coef.shape[:-1] + (8, 8))
     ws = np.stack(_pass([d[..., i, :] for i in range(8)], 11), axis=-2)          # down the columns
-    y = np.stack(_pass([ws[..., :, j] for j in range(8)], 18), axis=-1)          # along the rows
-    v = y & 1023
+    return np.stack(_pass([ws[..., :, j] for j in range(8)], 18), axis=-1)       # along the rows
+
+
+def idct_blocks(coef, q, dtype=np.int32):
+    """coef [..., 64] int16 natural order, q [64] -> samples [..., 8, 8] uint8."""
+    v = idct_prelimit(coef, q, dtype) & 1023
     return np.where(v < 128, v + 128, np.where(v < 512, 255, np.where(v < 896, 0, v - 896))).astype(np.uint8)
+
+
+def prelimit(data: bytes, dtype=np.int32):
+    """Every sample of every block of the file before the range limit (padding blocks included), as one flat array."""
+    coefs, quant, info = coefficients(data)
+    return np.concatenate([idct_prelimit(c, quant[tq], dtype).reshape(-1) for c, (_, _, _, tq) in zip(coefs, info["comps"])])
 
 
 def planes(data: bytes, dtype=np.int32):
