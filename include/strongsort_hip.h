@@ -674,6 +674,22 @@ int ss_jpeg_encode_batch_device(ss_ctx* ctx, void* hip_stream, const void* d_in,
 int ss_jpeg_entropy_encode_device(ss_ctx* ctx, const short* coef, int quality, int width, int height, int h_samp, int v_samp,
                                   unsigned char* out, size_t out_cap, size_t* out_size);
 
+/* ---- GSI post-processing: Gaussian-process smoothing of finished tracks (csrc/ss_gsi.hip, docs/GSI.md) ---- */
+/* n_tracks (1 .. 65 536) tracks, all host pointers: track t owns rows offsets[t] .. offsets[t+1]-1 (offsets[0] = 0, non-decreasing;
+ * an empty track is allowed and produces nothing) of frames (strictly increasing inside a track) and of vals [rows][4] = x1, y1, w,
+ * h; len_scale[t] (finite, > 0) is its RBF length scale, alpha (finite, >= 0) is added on the kernel matrix's diagonal.  out
+ * [rows][4] receives the posterior mean of each column, status[t] 0 (smoothed), 1 (a pivot was not > 0: the track's vals copied
+ * through) or 2 (more than ss_gsi_max_len() rows: copied through, never sent to the device).  One upload, the launches on the
+ * context's stream (one workgroup per track, the long tracks first) and one download; the call waits on an event of its own, not
+ * on the device.  Every argument is checked before the context or the device is touched: a refusal returns SS_ERR_INVALID with a
+ * message naming the track (ss_last_error; with ctx NULL in ss_last_error(NULL)) and leaves the context usable; a call whose
+ * tracks are all empty or over the cap is settled on the host and needs no context.  The results are
+ * the bits tests/gsi_ref.py computes (docs/GSI.md section 3).  Not capturable (waits, allocations that follow the call's size). */
+int ss_gsi_smooth(ss_ctx* ctx, int n_tracks, const int* offsets, const int* frames, const double* vals, const double* len_scale, double alpha,
+                  double* out, int* status);
+/* Host only: the longest track ss_gsi_smooth sends to the device (1024). */
+int ss_gsi_max_len(void);
+
 /* ---- profiling support ----------------------------------------------------------------------- */
 /* Mean duration (ms) of the association (cosine gallery) kernel over the launches since the last
  * call, measured with HIP events on the context stream; also returns the launch count. */

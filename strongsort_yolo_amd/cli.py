@@ -346,12 +346,17 @@ def process_video(args: dict, model=None) -> dict:
             if args.get("save") else None)       # annotated output (N2 + N3), off by default
     on_device = sink is not None and sink.kind in ("mjpeg", "jpgdir")
     overlay, fps_str = None, ""
+    gsi_on, gsi_rows = bool(args.get("gsi", False)) and track, []         # --gsi: every frame's tracked rows, smoothed after the stream (docs/GSI.md)
+    if gsi_on:
+        from .gsi import rows_of
 
     def emit(frame, res):
         """labels, counts and (with --save) the annotated frame of one processed frame; reference :284-331"""
         nonlocal frames, t0, fps, overlay, fps_str
         if track:
             writer.write(frames, res)
+            if gsi_on:
+                gsi_rows.append(rows_of(res, frames))
             if count:
                 counter.update(res)
         frames += 1
@@ -394,7 +399,16 @@ def process_video(args: dict, model=None) -> dict:
     if sink is not None:
         sink.close()
     writer.close()
-    return {"source": str(source), "frames": frames, "fps": fps, "counts": counter.counts() if count and track else {}}
+    summary = {"source": str(source), "frames": frames, "fps": fps, "counts": counter.counts() if count and track else {}}
+    if gsi_on:
+        # GSI post-processing of the whole run on the device context the overlay uses; the labels file above stays as it is
+        from . import gsi
+        eng = (overlay or model.overlay()).eng
+        rows = np.concatenate(gsi_rows, 0) if gsi_rows else np.zeros((0, 8))
+        rows, status = gsi.gsi(rows, eng, interval=int(args.get("gsi_interval", gsi.INTERVAL)), tau=float(args.get("gsi_tau", gsi.TAU)))
+        summary["gsi_rows"] = gsi.write_labels(os.path.join(args.get("outdir", "output"), f"{name}_labels_gsi.txt"), rows)
+        summary["gsi_status"] = {k: sum(1 for v in status.values() if v == k) for k in (0, 1, 2)}
+    return summary
 
 
 def _save_path(a, i: int) -> Optional[str]:
@@ -451,7 +465,16 @@ def main(argv=None):
     p.add_argument("--device-entropy", action="store_true",
                    help="--device-decode: decode the Huffman code on the device too (docs/JPEG.md §12); the host only parses headers and copies the scans")
     p.add_argument("--device-masks", action="store_true", help="segmentation models: assemble masks and trace their outlines on the device (csrc/ss_mask.hip) instead of on the host")
+    p.add_argument("--gsi", action="store_true",
+                   help="--track only: after the stream, GSI post-processing (StrongSORT++'s gap interpolation + Gaussian-process smoothing on the "
+                        "device, docs/GSI.md) of the tracked rows into <name>_labels_gsi.txt beside the labels file; any --tracker")
+    p.add_argument("--gsi-interval", type=int, default=20, help="--gsi: gaps shorter than this many frames are filled")
+    p.add_argument("--gsi-tau", type=float, default=10.0, help="--gsi: the length scale adapts as tau ln(tau^3 / track length)")
     a = p.parse_args(argv)
+    if a.gsi and not a.track:
+        p.error("--gsi post-processes tracked rows: it needs --track")
+    if a.gsi and (a.gsi_interval < 1 or not a.gsi_tau > 0):
+        p.error("--gsi-interval must be >= 1 and --gsi-tau > 0")
     if a.camera_motion and a.tracker == "bytetrack":
         p.error("--camera-motion needs --tracker strongsort or botsort (ByteTrack has no GMC)")
     if a.gmc_method != "ecc" and not a.camera_motion:
@@ -490,6 +513,7 @@ def main(argv=None):
             p.error("--save-quality must be 1 .. 100")
     jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "device_decode": a.device_decode, "device_entropy": a.device_entropy,
              "device_encode": a.device_encode, "device_encode_entropy": a.device_encode_entropy, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
+             "gsi": a.gsi, "gsi_interval": a.gsi_interval, "gsi_tau": a.gsi_tau,
              "save": _save_path(a, i)}
             for i, s in enumerate(a.source)]
     import torch

@@ -65,6 +65,11 @@ int  ss_jpeg_encode_impl(SSJpegEnc**, hipStream_t, const void*, long long, int, 
 int  ss_jpeg_encode_device_impl(SSJpegEnc**, hipStream_t, const void*, long long, int, int, int, int, int, int, int, int, unsigned char* const*, size_t*, std::string&);
 int  ss_jpeg_entropy_encode_device_impl(SSJpegEnc**, hipStream_t, const short*, int, int, int, int, int, unsigned char*, size_t*, std::string&);
 void ss_jpeg_enc_free(SSJpegEnc*);
+struct SSGsi;                           // ss_gsi.hip
+int  ss_gsi_max_len_impl();
+int  ss_gsi_check_impl(int, const int*, const int*, const double*, const double*, double, const double*, const int*, std::string&);
+int  ss_gsi_smooth_impl(SSGsi**, hipStream_t, int, const int*, const int*, const double*, const double*, double, double*, int*, std::string&);
+void ss_gsi_free(SSGsi*);
 
 static std::string g_last_error;
 
@@ -130,6 +135,7 @@ struct ss_ctx {
     Byte* byte = nullptr;
     SSJpeg* jpeg = nullptr;     // ss_jpeg_decode_batch's staging areas and planes, made by its first call
     SSJpegEnc* jpeg_enc = nullptr;   // ss_jpeg_encode_batch's buffers, made by its first call
+    SSGsi* gsi = nullptr;       // ss_gsi_smooth's staging and scratch slots, made by its first call
 };
 
 static int fail(ss_ctx* c, int code, const std::string& msg)
@@ -285,6 +291,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     if (c->back.p) (void)hipHostFree(c->back.p);
     ss_jpeg_free(c->jpeg);
     ss_jpeg_enc_free(c->jpeg_enc);
+    ss_gsi_free(c->gsi);
     delete c;
 }
 
@@ -513,6 +520,20 @@ extern "C" int ss_jpeg_entropy_encode_device(ss_ctx* c, const short* coef, int q
         return fail(c, SS_ERR_INVALID, "ss_jpeg_entropy_encode_device: out_cap " + std::to_string(out_cap) + " is below the bound " + std::to_string(bound));
     std::string err;
     const int rc = ss_jpeg_entropy_encode_device_impl(&c->jpeg_enc, c->stream, coef, quality, width, height, h_samp, v_samp, out, out_size, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+// ---- GSI post-processing (ss_gsi.hip, docs/GSI.md) ------------------------------------------------------------
+extern "C" int ss_gsi_max_len(void) { return ss_gsi_max_len_impl(); }
+
+extern "C" int ss_gsi_smooth(ss_ctx* c, int n_tracks, const int* offsets, const int* frames, const double* vals, const double* len_scale, double alpha,
+                             double* out, int* status)
+{
+    std::string err;
+    int rc = ss_gsi_check_impl(n_tracks, offsets, frames, vals, len_scale, alpha, out, status, err);      // the arguments first: no context needed
+    if (rc != SS_OK) return fail(c, rc, err);
+    // (tracks over the cap and empty tracks are settled on the host: a call that holds nothing else needs no context)
+    rc = ss_gsi_smooth_impl(c ? &c->gsi : nullptr, c ? c->stream : nullptr, n_tracks, offsets, frames, vals, len_scale, alpha, out, status, err);
     return rc == SS_OK ? rc : fail(c, rc, err);
 }
 

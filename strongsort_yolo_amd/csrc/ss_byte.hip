@@ -17,6 +17,7 @@
 // for the f64 Kalman work.  tests/bytetrack_ref.py restates every step in the same order (rows are compared bit for bit).
 #include "ss_common.h"
 #include "ss_lsap.h"
+#include "ss_expneg.h"
 
 #define SS_BYTE_COST_CAP 2048          // LDS-resident cost entries (f64); a larger matrix lives in the stream's global spill area
 
@@ -221,31 +222,6 @@ __device__ inline void byte_reid_smooth(const SSByteDev& b, size_t sb, size_t fs
                 for (int j = 0; j < 8; ++j) sm[u][l + 64 * j] = n > 0.0f ? v[u][j] / n : 0.0f;
         }
     }
-}
-
-// §1e: exp(-x), x >= 0, as ONE fixed sequence of f64 operations (tests/botsort_pose_ref.ss_expneg runs the same one with the same
-// constants; the file is built with -ffp-contract=off): k = floor(-x log2(e) + 1/2), r = (-x - k LN2_HI) - k LN2_LO with
-// |r| <= ln2 / 2, the degree-12 Taylor polynomial by Horner, ldexp.  Above the cut-off (and for a NaN) the result is 0.
-__device__ inline double ss_expneg(double x)
-{
-    if (!(x <= 700.0)) return 0.0;
-    const double y = -x;
-    const double k = floor(y * 0x1.71547652b82fep+0 + 0.5);
-    const double r = (y - k * 0x1.62e42feep-1) - k * 0x1.a39ef35793c76p-33;
-    double p = 0x1.1eed8eff8d898p-29;             // 1 / 12!
-    p = p * r + 0x1.ae64567f544e4p-26;            // 1 / 11!
-    p = p * r + 0x1.27e4fb7789f5cp-22;
-    p = p * r + 0x1.71de3a556c734p-19;
-    p = p * r + 0x1.a01a01a01a01ap-16;
-    p = p * r + 0x1.a01a01a01a01ap-13;
-    p = p * r + 0x1.6c16c16c16c17p-10;
-    p = p * r + 0x1.1111111111111p-7;
-    p = p * r + 0x1.5555555555555p-5;
-    p = p * r + 0x1.5555555555555p-3;
-    p = p * r + 0.5;
-    p = p * r + 1.0;
-    p = p * r + 1.0;
-    return ldexp(p, (int)k);
 }
 
 // §1e: the keypoints of every detection row of the group.  kpts: row (fs, r) at kpts + (fs * MAXD + r) * stride + off, nk triplets

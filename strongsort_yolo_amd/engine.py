@@ -195,6 +195,24 @@ class TrackerEngine:
             raise ValueError("download: size / layout mismatch")
         self._ck(self.L.ss_download(self.ctx, self._st(stream), dst.ctypes.data_as(C.c_void_p), _ptr(src), dst.nbytes))
 
+    def gsi_smooth(self, offsets, frames, vals, len_scale, alpha: float = 1e-10):
+        """GSI's Gaussian-process smoothing of finished tracks (csrc/ss_gsi.hip, docs/GSI.md), host arrays in and out: track t owns
+        rows offsets[t] .. offsets[t+1]-1 of frames (int, strictly increasing inside a track) and vals [rows, 4] (x1, y1, w, h);
+        len_scale [tracks] is each track's RBF length scale.  -> (out [rows, 4] float64, status [tracks] int32: 0 smoothed, 1 a pivot
+        was not positive, 2 longer than ss_gsi_max_len(); the rows of 1 and 2 pass through).  Synchronous, on the engine's stream."""
+        offsets = np.ascontiguousarray(offsets, np.int32)
+        frames = np.ascontiguousarray(frames, np.int32)
+        vals = np.ascontiguousarray(vals, np.float64)
+        len_scale = np.ascontiguousarray(len_scale, np.float64)
+        nt = len(offsets) - 1
+        if offsets.ndim != 1 or nt < 0 or len_scale.shape != (nt,) or frames.ndim != 1 or vals.shape != (len(frames), 4) or (nt >= 0 and len(offsets) and offsets[-1] != len(frames)):
+            raise ValueError("gsi_smooth: offsets [tracks + 1], frames [rows], vals [rows, 4], len_scale [tracks] with offsets[-1] == rows")
+        out, status = np.empty((max(len(frames), 1), 4), np.float64), np.zeros(max(nt, 1), np.int32)
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        self._ck(self.L.ss_gsi_smooth(self.ctx, nt, offsets.ctypes.data_as(pi), frames.ctypes.data_as(pi), vals.ctypes.data_as(pd),
+                                      len_scale.ctypes.data_as(pd), float(alpha), out.ctypes.data_as(pd), status.ctypes.data_as(pi)))
+        return out[:len(frames)], status[:nt]
+
     # ---- tracker --------------------------------------------------------------------------------
     def update_device(self, dets, ndets, feats, img_hw, out=None, nout=None):
         """All streams, one frame; tensors live on the device ([S,128,6] f32, [S] i32, [S,128,512] f32,

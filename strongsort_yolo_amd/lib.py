@@ -35,6 +35,7 @@ EXPORTS = [
     "ss_jpeg_probe", "ss_jpeg_coefficients", "ss_jpeg_decode_batch",
     "ss_jpeg_decode_batch_device", "ss_jpeg_scan_segments", "ss_jpeg_device_coefficients", "ss_jpeg_device_rounds",
     "ss_jpeg_encode_bound", "ss_jpeg_entropy_encode", "ss_jpeg_encode_batch", "ss_jpeg_encode_batch_device", "ss_jpeg_entropy_encode_device",
+    "ss_gsi_smooth", "ss_gsi_max_len",
 ]
 
 
@@ -226,6 +227,8 @@ def load():
     L.ss_jpeg_encode_batch.argtypes = [vp, vp, vp, ll, i, i, i, i, i, i, i, i, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.ss_jpeg_encode_batch_device.argtypes = L.ss_jpeg_encode_batch.argtypes
     L.ss_jpeg_entropy_encode_device.argtypes = [vp, C.POINTER(C.c_short), i, i, i, i, i, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.ss_gsi_smooth.argtypes = [vp, i, hi, hi, hd, hd, d, hd, hi]
+    L.ss_gsi_max_len.argtypes = []
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("ss_destroy", "ss_last_error"):
