@@ -690,6 +690,26 @@ int ss_gsi_smooth(ss_ctx* ctx, int n_tracks, const int* offsets, const int* fram
 /* Host only: the longest track ss_gsi_smooth sends to the device (1024). */
 int ss_gsi_max_len(void);
 
+/* ---- scoring tracks against ground truth: HOTA and CLEAR MOT (csrc/ss_mot.hip, docs/MOTEVAL.md) ---- */
+/* n_pairs (1 .. 64) pairs of one ground-truth and one tracker row set, all host pointers.  Pair p owns the evaluated frames
+ * frame_off[p] .. frame_off[p+1]-1 (at most 65 536); frame f owns the ground-truth rows gt_off[f] .. gt_off[f+1]-1 and the tracker
+ * rows tr_off[f] .. tr_off[f+1]-1 (at most ss_mot_max_boxes() each; every offset array starts at 0 and does not decrease).  gt_ids /
+ * tr_ids are the rows' dense ids, 0 .. n_gt_ids[p]-1 and 0 .. n_tr_ids[p]-1, unique within a frame; gt_boxes / tr_boxes [rows][4]
+ * are x1, y1, x2, y2, finite with x2 > x1 and y2 > y1; thr in (0, 1] is CLEAR's similarity threshold.  Per ground-truth row the
+ * call returns HOTA's match (hota_match: the tracker row's index within its frame or -1, hota_s: that pair's similarity or 0) and
+ * CLEAR's (clear_match, clear_s); ga, unless NULL, receives the global alignment scores, per pair [n_gt_ids][n_tr_ids], pair after
+ * pair.  One upload, the launches (CLEAR's walkers, one wave per pair, on a second stream of the context beside the alignment and
+ * the HOTA matching) and one download; the call waits on an event of its own.  Every argument is checked before the context or the
+ * device is touched: a refusal is SS_ERR_INVALID, a call over a cap (boxes a frame, pairs, frames a pair, 2^26 ground-truth id x
+ * tracker id cells, 2^27 box x box cells) SS_ERR_CAPACITY, both with a message naming the pair and frame (with ctx NULL in
+ * ss_last_error(NULL)), and the context stays usable.  The results are the bits tests/moteval_ref.py computes (docs/MOTEVAL.md
+ * section 1).  Not capturable. */
+int ss_mot_eval(ss_ctx* ctx, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_ids, const int* tr_ids,
+                const double* gt_boxes, const double* tr_boxes, const int* n_gt_ids, const int* n_tr_ids, double thr,
+                int* hota_match, double* hota_s, int* clear_match, double* clear_s, double* ga);
+/* Host only: the most boxes one side of a frame may hold (256: the one-wave assignment solver's columns). */
+int ss_mot_max_boxes(void);
+
 /* ---- profiling support ----------------------------------------------------------------------- */
 /* Mean duration (ms) of the association (cosine gallery) kernel over the launches since the last
  * call, measured with HIP events on the context stream; also returns the launch count. */

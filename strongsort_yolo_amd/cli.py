@@ -408,6 +408,19 @@ def process_video(args: dict, model=None) -> dict:
         rows, status = gsi.gsi(rows, eng, interval=int(args.get("gsi_interval", gsi.INTERVAL)), tau=float(args.get("gsi_tau", gsi.TAU)))
         summary["gsi_rows"] = gsi.write_labels(os.path.join(args.get("outdir", "output"), f"{name}_labels_gsi.txt"), rows)
         summary["gsi_status"] = {k: sum(1 for v in status.values() if v == k) for k in (0, 1, 2)}
+    if args.get("eval_gt") and track:
+        # HOTA and CLEAR MOT of the files just written against the ground truth (docs/MOTEVAL.md): the labels file holds int()
+        # corners, so the file is what is scored; with --gsi its file is a second pair of the same device call
+        from . import moteval
+        eng = (overlay or model.overlay()).eng
+        outdir = args.get("outdir", "output")
+        names = ["labels"] + (["labels_gsi"] if gsi_on else [])
+        scored = moteval.evaluate(moteval.read_labels(args["eval_gt"]), [moteval.read_labels(os.path.join(outdir, f"{name}_{k}.txt")) for k in names],
+                                  eng, thr=float(args.get("eval_thr", 0.5)))
+        moteval.write_metrics(os.path.join(outdir, f"{name}_metrics.json"), dict(zip(names, scored)) if gsi_on else scored[0])
+        for k, m in zip(names, scored):
+            for fig in ("HOTA", "MOTA", "IDSW"):
+                summary[fig + k[len("labels"):]] = m[fig]
     return summary
 
 
@@ -470,7 +483,21 @@ def main(argv=None):
                         "device, docs/GSI.md) of the tracked rows into <name>_labels_gsi.txt beside the labels file; any --tracker")
     p.add_argument("--gsi-interval", type=int, default=20, help="--gsi: gaps shorter than this many frames are filled")
     p.add_argument("--gsi-tau", type=float, default=10.0, help="--gsi: the length scale adapts as tau ln(tau^3 / track length)")
+    p.add_argument("--eval-gt", nargs="+", default=None, metavar="PATH",
+                   help="--track only: ground-truth labels files (the labels file's line format), one per source; after the stream "
+                        "<name>_labels.txt (with --gsi also <name>_labels_gsi.txt) is scored against it on the device, HOTA and CLEAR MOT "
+                        "(docs/MOTEVAL.md), into <name>_metrics.json")
+    p.add_argument("--eval-thr", type=float, default=0.5, help="--eval-gt: CLEAR MOT's similarity threshold, in (0, 1]")
     a = p.parse_args(argv)
+    if a.eval_gt and not a.track:
+        p.error("--eval-gt scores tracked rows: it needs --track")
+    if a.eval_gt and len(a.eval_gt) != len(a.source):
+        p.error("--eval-gt takes one ground-truth file per --source")
+    for path in a.eval_gt or ():
+        if not os.path.isfile(path):
+            p.error(f"--eval-gt: no such file: {path}")
+    if a.eval_gt and not 0.0 < a.eval_thr <= 1.0:
+        p.error("--eval-thr must be in (0, 1]")
     if a.gsi and not a.track:
         p.error("--gsi post-processes tracked rows: it needs --track")
     if a.gsi and (a.gsi_interval < 1 or not a.gsi_tau > 0):
@@ -513,7 +540,7 @@ def main(argv=None):
             p.error("--save-quality must be 1 .. 100")
     jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "device_decode": a.device_decode, "device_entropy": a.device_entropy,
              "device_encode": a.device_encode, "device_encode_entropy": a.device_encode_entropy, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
-             "gsi": a.gsi, "gsi_interval": a.gsi_interval, "gsi_tau": a.gsi_tau,
+             "gsi": a.gsi, "gsi_interval": a.gsi_interval, "gsi_tau": a.gsi_tau, "eval_gt": a.eval_gt[i] if a.eval_gt else None, "eval_thr": a.eval_thr,
              "save": _save_path(a, i)}
             for i, s in enumerate(a.source)]
     import torch

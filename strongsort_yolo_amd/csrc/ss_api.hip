@@ -70,6 +70,13 @@ int  ss_gsi_max_len_impl();
 int  ss_gsi_check_impl(int, const int*, const int*, const double*, const double*, double, const double*, const int*, std::string&);
 int  ss_gsi_smooth_impl(SSGsi**, hipStream_t, int, const int*, const int*, const double*, const double*, double, double*, int*, std::string&);
 void ss_gsi_free(SSGsi*);
+struct SSMot;                           // ss_mot.hip
+int  ss_mot_max_boxes_impl();
+int  ss_mot_check_impl(int, const int*, const int*, const int*, const int*, const int*, const double*, const double*, const int*, const int*, double,
+                       const int*, const double*, const int*, const double*, std::string&);
+int  ss_mot_eval_impl(SSMot**, hipStream_t, int, const int*, const int*, const int*, const int*, const int*, const double*, const double*, const int*,
+                      const int*, double, int*, double*, int*, double*, double*, std::string&);
+void ss_mot_free(SSMot*);
 
 static std::string g_last_error;
 
@@ -136,6 +143,7 @@ struct ss_ctx {
     SSJpeg* jpeg = nullptr;     // ss_jpeg_decode_batch's staging areas and planes, made by its first call
     SSJpegEnc* jpeg_enc = nullptr;   // ss_jpeg_encode_batch's buffers, made by its first call
     SSGsi* gsi = nullptr;       // ss_gsi_smooth's staging and scratch slots, made by its first call
+    SSMot* mot = nullptr;       // ss_mot_eval's staging, scratch and second stream, made by its first call
 };
 
 static int fail(ss_ctx* c, int code, const std::string& msg)
@@ -292,6 +300,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     ss_jpeg_free(c->jpeg);
     ss_jpeg_enc_free(c->jpeg_enc);
     ss_gsi_free(c->gsi);
+    ss_mot_free(c->mot);
     delete c;
 }
 
@@ -534,6 +543,22 @@ extern "C" int ss_gsi_smooth(ss_ctx* c, int n_tracks, const int* offsets, const 
     if (rc != SS_OK) return fail(c, rc, err);
     // (tracks over the cap and empty tracks are settled on the host: a call that holds nothing else needs no context)
     rc = ss_gsi_smooth_impl(c ? &c->gsi : nullptr, c ? c->stream : nullptr, n_tracks, offsets, frames, vals, len_scale, alpha, out, status, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+// ---- HOTA and CLEAR MOT against ground truth (ss_mot.hip, docs/MOTEVAL.md) --------------------------------------------------
+extern "C" int ss_mot_max_boxes(void) { return ss_mot_max_boxes_impl(); }
+
+extern "C" int ss_mot_eval(ss_ctx* c, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_ids, const int* tr_ids,
+                           const double* gt_boxes, const double* tr_boxes, const int* n_gt_ids, const int* n_tr_ids, double thr,
+                           int* hota_match, double* hota_s, int* clear_match, double* clear_s, double* ga)
+{
+    std::string err;
+    int rc = ss_mot_check_impl(n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids, thr,
+                               hota_match, hota_s, clear_match, clear_s, err);                            // the arguments first: no context needed
+    if (rc != SS_OK) return fail(c, rc, err);
+    rc = ss_mot_eval_impl(c ? &c->mot : nullptr, c ? c->stream : nullptr, n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes,
+                          n_gt_ids, n_tr_ids, thr, hota_match, hota_s, clear_match, clear_s, ga, err);
     return rc == SS_OK ? rc : fail(c, rc, err);
 }
 

@@ -213,6 +213,34 @@ class TrackerEngine:
                                       len_scale.ctypes.data_as(pd), float(alpha), out.ctypes.data_as(pd), status.ctypes.data_as(pi)))
         return out[:len(frames)], status[:nt]
 
+    def mot_eval(self, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids, thr: float = 0.5, want_ga: bool = False):
+        """HOTA's and CLEAR MOT's matching of ground-truth / tracker pairs (csrc/ss_mot.hip, docs/MOTEVAL.md), host arrays in and out:
+        pair p owns frames frame_off[p] .. frame_off[p+1]-1, frame f the rows gt_off[f] .. gt_off[f+1]-1 of gt_ids (dense, per pair) and
+        gt_boxes [rows, 4] (x1, y1, x2, y2) and likewise on the tracker side.  -> (hota_match, hota_s, clear_match, clear_s) per
+        ground-truth row (a match is the tracker row's index within its frame, -1 none) and, with want_ga, the alignment scores of
+        all pairs in one flat array.  Synchronous; one device call for all pairs."""
+        ai = lambda v: np.ascontiguousarray(v, np.int32).reshape(-1)
+        frame_off, gt_off, tr_off, gt_ids, tr_ids, n_gt_ids, n_tr_ids = (ai(v) for v in (frame_off, gt_off, tr_off, gt_ids, tr_ids, n_gt_ids, n_tr_ids))
+        gt_boxes, tr_boxes = (np.ascontiguousarray(v, np.float64).reshape(-1, 4) for v in (gt_boxes, tr_boxes))
+        n_pairs = len(frame_off) - 1
+        if (n_pairs < 1 or len(n_gt_ids) != n_pairs or len(n_tr_ids) != n_pairs or len(gt_off) != len(tr_off) or len(gt_off) != frame_off[-1] + 1
+                or gt_off[-1] != len(gt_ids) or tr_off[-1] != len(tr_ids) or len(gt_boxes) != len(gt_ids) or len(tr_boxes) != len(tr_ids)):
+            raise ValueError("mot_eval: frame_off [pairs + 1], gt_off / tr_off [frames + 1], ids [rows], boxes [rows, 4], id counts [pairs]")
+        n = max(len(gt_ids), 1)
+        hm, cm, hs, cs = np.full(n, -1, np.int32), np.full(n, -1, np.int32), np.zeros(n), np.zeros(n)
+        ga = np.zeros(max(int((n_gt_ids.astype(np.int64) * n_tr_ids).sum()), 1)) if want_ga else None
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        k = len(gt_ids)
+        if not len(gt_ids):                                               # (a side without rows still passes a pointer)
+            gt_ids, gt_boxes = np.zeros(1, np.int32), np.zeros((1, 4))
+        if not len(tr_ids):
+            tr_ids, tr_boxes = np.zeros(1, np.int32), np.zeros((1, 4))
+        self._ck(self.L.ss_mot_eval(self.ctx, n_pairs, frame_off.ctypes.data_as(pi), gt_off.ctypes.data_as(pi), tr_off.ctypes.data_as(pi),
+                                    gt_ids.ctypes.data_as(pi), tr_ids.ctypes.data_as(pi), gt_boxes.ctypes.data_as(pd), tr_boxes.ctypes.data_as(pd),
+                                    n_gt_ids.ctypes.data_as(pi), n_tr_ids.ctypes.data_as(pi), float(thr), hm.ctypes.data_as(pi), hs.ctypes.data_as(pd),
+                                    cm.ctypes.data_as(pi), cs.ctypes.data_as(pd), ga.ctypes.data_as(pd) if want_ga else None))
+        return (hm[:k], hs[:k], cm[:k], cs[:k]) + ((ga,) if want_ga else ())
+
     # ---- tracker --------------------------------------------------------------------------------
     def update_device(self, dets, ndets, feats, img_hw, out=None, nout=None):
         """All streams, one frame; tensors live on the device ([S,128,6] f32, [S] i32, [S,128,512] f32,

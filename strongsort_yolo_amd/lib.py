@@ -36,6 +36,7 @@ EXPORTS = [
     "ss_jpeg_decode_batch_device", "ss_jpeg_scan_segments", "ss_jpeg_device_coefficients", "ss_jpeg_device_rounds",
     "ss_jpeg_encode_bound", "ss_jpeg_entropy_encode", "ss_jpeg_encode_batch", "ss_jpeg_encode_batch_device", "ss_jpeg_entropy_encode_device",
     "ss_gsi_smooth", "ss_gsi_max_len",
+    "ss_mot_eval", "ss_mot_max_boxes",
 ]
 
 
@@ -229,6 +230,8 @@ def load():
     L.ss_jpeg_entropy_encode_device.argtypes = [vp, C.POINTER(C.c_short), i, i, i, i, i, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ss_gsi_smooth.argtypes = [vp, i, hi, hi, hd, hd, d, hd, hi]
     L.ss_gsi_max_len.argtypes = []
+    L.ss_mot_eval.argtypes = [vp, i, hi, hi, hi, hi, hi, hd, hd, hi, hi, d, hi, hd, hi, hd, hd]
+    L.ss_mot_max_boxes.argtypes = []
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("ss_destroy", "ss_last_error"):
