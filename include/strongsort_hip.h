@@ -13,6 +13,9 @@
  * Conventions: plain pointers and sizes; `d_` = device memory owned by the caller; every call is
  * asynchronous on the context's HIP stream unless it says "synchronous"; return 0 or a negative
  * SS_ERR_* code, never a C++ exception; one context is not thread safe.
+ *
+ * The Python binding is derived from this file (strongsort_yolo_amd/cheader.py): keep to flat declarations, structs of scalars
+ * and pointers, integer #defines; a `d_` pointer binds as an address, any other non-void pointer as a typed host pointer.
  */
 #ifndef STRONGSORT_HIP_H
 #define STRONGSORT_HIP_H
@@ -150,12 +153,12 @@ int ss_unpack_feats(ss_ctx* ctx, const void* d_emb, int emb_half, const int* d_o
                     float* d_feats, long long feats_image_stride);
 
 /* One frame's results gathered into ONE buffer on the context's stream (the per-frame call of yolo_multi_model.py:41 / :278 reads boxes and
- * track rows on the host after every frame): dst[0] = n = min(*d_n_dets, det_cap) and dst[1] = m = min(*d_n_out, out_cap) as int32 bit
- * patterns, n rows of det_ld floats from dst + 2, m rows of out_ld floats from dst + 2 + det_cap * det_ld.  dst: 2 + det_cap * det_ld +
+ * track rows on the host after every frame): d_dst[0] = n = min(*d_n_dets, det_cap) and d_dst[1] = m = min(*d_n_out, out_cap) as int32 bit
+ * patterns, n rows of det_ld floats from d_dst + 2, m rows of out_ld floats from d_dst + 2 + det_cap * det_ld.  d_dst: 2 + det_cap * det_ld +
  * out_cap * out_ld floats of device memory or of pinned (device-accessible) host memory - then the host reads it after synchronising the
  * stream, with no copy in between.  d_n_out / d_out may both be NULL (detection only: m = 0). */
 int ss_pack_results(ss_ctx* ctx, const int* d_n_dets, const float* d_dets, int det_ld, int det_cap, const int* d_n_out, const float* d_out,
-                    int out_ld, int out_cap, float* dst);
+                    int out_ld, int out_cap, float* d_dst);
 
 /* ---- instance masks of a segmentation head (yolo.py assemble_masks / mask_polygon on the device; YOLO(device_masks=True)) --------
  * ss_mask_assemble: frame f's prototypes at d_proto + f*proto_frame_stride elements ([nm][mh][mw], IEEE half when proto_f16, else

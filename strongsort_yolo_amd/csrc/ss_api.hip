@@ -8,75 +8,7 @@
 #include <type_traits>
 #include <vector>
 #include "ss_common.h"
-
-// launchers implemented in ss_track.hip / ss_front.hip
-size_t ss_lsap_lds_bytes();
-size_t ss_frame_lds_bytes(int, int, int);
-void ss_launch_group_head(const SSDev&, const SSParams&, hipStream_t, hipEvent_t, hipEvent_t, hipEvent_t);
-void ss_launch_group_chain(const SSDev&, const SSParams&, hipStream_t);
-void ss_launch_normalize(const float*, int, float*, hipStream_t);
-void ss_launch_ema(const float*, const float*, int, float, float, float*, hipStream_t);
-void ss_launch_kf(int, double*, double*, const double*, const double*, int, double, double, hipStream_t);
-void ss_launch_pack(const float*, int, int, float*, hipStream_t);
-void ss_launch_assoc(const float*, const int*, int, const float*, int, const double*, const double*,
-                     const double*, const SSParams&, float*, float*, double*, float*, double*, uint8_t*, hipStream_t);
-void ss_launch_iou(const double*, int, const double*, int, double, double*, hipStream_t);
-void ss_launch_lsap(const double*, int, int, int*, double*, int*, hipStream_t);
-int  ss_front_init();
-void ss_launch_letterbox(const uint8_t*, int, long long, int, int, int, void*, int, int, int, int, int, int, int, int, hipStream_t);
-int  ss_launch_nms(const float*, int, long long, int, int, int, float, float, int, float, int, float, float, float, float,
-                   float, const float*, float*, int, long long, int*, long long, int*, void*, size_t, unsigned long long,
-                   unsigned long long, hipStream_t);
-int* ss_nms_error_flag(void*, int);
-size_t ss_nms_workspace_bytes();
-void ss_launch_crop(const uint8_t*, int, long long, int, int, int, const float*, int, long long, int, const int*, void*, int, hipStream_t, const int*);
-void ss_launch_crop_offsets(const int*, int, int, int*, hipStream_t);
-void ss_launch_project(const double*, const double*, const double*, int, double, double*, double*, hipStream_t);
-extern int ss_nms_fused;
-void ss_launch_unpack_feats(const void*, int, const int*, const int*, int, int, float*, long long, hipStream_t);
-void ss_launch_pack_results(const int*, const float*, int, int, const int*, const float*, int, int, float*, hipStream_t);
-void ss_launch_overlay(uint8_t*, int, long long, int, int, int, const void*, const int*, const uint8_t*, const uint8_t*, hipStream_t);
-void ss_launch_cmc(const uint8_t*, int, long long, int, int, int, uint8_t*, long long, int, int, int, int, int, double, int*, const int*, double*, hipStream_t);
-void ss_launch_gmc_sparse(const SSGmcDev&, const uint8_t*, int, long long, int, const int*, double*, hipStream_t);
-int  ss_mask_max_words();
-void ss_launch_mask_assemble(const void*, int, long long, int, int, int, const float*, long long, int, int, const int*, int, int, const float*,
-                             long long, int, int, uint32_t*, long long, hipStream_t);
-void ss_launch_mask_outline(const uint32_t*, long long, const int*, int, int, int, int, int, int*, long long, int*, long long, uint32_t*,
-                            long long, int*, int, hipStream_t);
-extern "C" void ss_step_kernel_attr();
-void ss_launch_byte_group(const SSByteDev&, int, const float*, const int*, const float*, float*, int*, hipStream_t);
-void ss_launch_byte_group_kpts(const SSByteDev&, int, const float*, const int*, const float*, long long, int, const float*, float*, int*, hipStream_t);
-void ss_launch_native_feats(int, int, const void* const*, const long long*, const long long*, const long long*, const int*, const int*,
-                            const int*, int, const int*, long long, const int*, float*, hipStream_t);
-
-struct SSJpeg;                          // ss_jpeg.hip
-int  ss_jpeg_probe_impl(const unsigned char*, size_t, int*, int*, int*, int*, int*, std::string&);
-int  ss_jpeg_coefficients_impl(const unsigned char*, size_t, short*, size_t, unsigned short*, std::string&);
-int  ss_jpeg_decode_impl(SSJpeg**, hipStream_t, const unsigned char* const*, const size_t*, int, int, int, void*, long long, int, int, std::string&);
-void ss_jpeg_free(SSJpeg*);
-int  ss_jpeg_scan_segments_impl(const unsigned char*, size_t, unsigned char*, size_t, size_t*, unsigned int*, size_t, int*, unsigned int*, std::string&);
-int  ss_jpeg_decode_device_impl(SSJpeg**, hipStream_t, const unsigned char* const*, const size_t*, int, int, int, void*, long long, int, int, short*, size_t, std::string&);
-int  ss_jpeg_pending_impl(SSJpeg*, std::string&);
-int  ss_jpeg_device_rounds_impl(SSJpeg*, int*, int);
-struct SSJpegEnc;                       // ss_jpeg_enc.hip
-size_t ss_jpeg_encode_bound_impl(int, int, int, int);
-int  ss_jpeg_entropy_encode_impl(const short*, int, int, int, int, int, unsigned char*, size_t*, std::string&);
-int  ss_jpeg_encode_impl(SSJpegEnc**, hipStream_t, const void*, long long, int, int, int, int, int, int, int, int, unsigned char* const*, size_t*, std::string&);
-int  ss_jpeg_encode_device_impl(SSJpegEnc**, hipStream_t, const void*, long long, int, int, int, int, int, int, int, int, unsigned char* const*, size_t*, std::string&);
-int  ss_jpeg_entropy_encode_device_impl(SSJpegEnc**, hipStream_t, const short*, int, int, int, int, int, unsigned char*, size_t*, std::string&);
-void ss_jpeg_enc_free(SSJpegEnc*);
-struct SSGsi;                           // ss_gsi.hip
-int  ss_gsi_max_len_impl();
-int  ss_gsi_check_impl(int, const int*, const int*, const double*, const double*, double, const double*, const int*, std::string&);
-int  ss_gsi_smooth_impl(SSGsi**, hipStream_t, int, const int*, const int*, const double*, const double*, double, double*, int*, std::string&);
-void ss_gsi_free(SSGsi*);
-struct SSMot;                           // ss_mot.hip
-int  ss_mot_max_boxes_impl();
-int  ss_mot_check_impl(int, const int*, const int*, const int*, const int*, const int*, const double*, const double*, const int*, const int*, double,
-                       const int*, const double*, const int*, const double*, std::string&);
-int  ss_mot_eval_impl(SSMot**, hipStream_t, int, const int*, const int*, const int*, const int*, const int*, const double*, const double*, const int*,
-                      const int*, double, int*, double*, int*, double*, double*, std::string&);
-void ss_mot_free(SSMot*);
+#include "ss_launch.h"
 
 static std::string g_last_error;
 
@@ -1228,11 +1160,11 @@ extern "C" int ss_unpack_feats(ss_ctx* c, const void* d_emb, int emb_half, const
 }
 
 extern "C" int ss_pack_results(ss_ctx* c, const int* d_n_dets, const float* d_dets, int det_ld, int det_cap, const int* d_n_out,
-                               const float* d_out, int out_ld, int out_cap, float* dst)
+                               const float* d_out, int out_ld, int out_cap, float* d_dst)
 {
-    if (!c || !d_n_dets || !d_dets || !dst || det_ld < 1 || det_cap < 1 || ((d_n_out || d_out) && (!d_n_out || !d_out || out_ld < 1 || out_cap < 1)))
+    if (!c || !d_n_dets || !d_dets || !d_dst || det_ld < 1 || det_cap < 1 || ((d_n_out || d_out) && (!d_n_out || !d_out || out_ld < 1 || out_cap < 1)))
         return fail(c, SS_ERR_INVALID, "ss_pack_results: bad argument");
-    ss_launch_pack_results(d_n_dets, d_dets, det_ld, det_cap, d_n_out, d_out, out_ld, out_cap, dst, c->stream);
+    ss_launch_pack_results(d_n_dets, d_dets, det_ld, det_cap, d_n_out, d_out, out_ld, out_cap, d_dst, c->stream);
     HIPCHK(c, hipGetLastError());
     return SS_OK;
 }

@@ -16,6 +16,7 @@
 // The list logic lives in LDS (slot fields, list orders); means / covariances stay in global memory, one thread per track
 // for the f64 Kalman work.  tests/bytetrack_ref.py restates every step in the same order (rows are compared bit for bit).
 #include "ss_common.h"
+#include "ss_launch.h"
 #include "ss_lsap.h"
 #include "ss_expneg.h"
 

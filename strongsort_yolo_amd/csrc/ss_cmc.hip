@@ -5,6 +5,7 @@
 // warps.  The warps are stateless per frame pair, so a whole frame group is estimated in one launch (one 1024-thread
 // workgroup per pair) beside the detector; k_frame applies warp f to the track boxes before predicting frame f.
 #include "ss_common.h"
+#include "ss_launch.h"
 
 __device__ inline void cm_axis(int d, float scale, int n_src, int& i0, int& i1, float& frac)
 {

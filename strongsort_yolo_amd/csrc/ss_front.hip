@@ -3,6 +3,7 @@
 // operation for operation; results are bit-identical (tests/test_gpu_front.py).
 #include <hip/hip_fp16.h>
 #include "ss_common.h"
+#include "ss_launch.h"
 
 // ---- shared bilinear helpers (oracle so_axis / so_bilerp_u8) ---------------------------------------
 __device__ inline void ss_axis(int d, float scale, int n_src, int& i0, int& i1, float& frac)

@@ -5,6 +5,7 @@
 // with -ffp-contract=off) -> bit-identical warps.  Like ECC (ss_cmc.hip) the estimate is stateless per frame pair: a whole group is
 // one batch of launches beside the detector, and the warps go to k_byte_group's GMC variant in ss_cmc_estimate's layout.
 #include "ss_common.h"
+#include "ss_launch.h"
 
 #define GMC_WIN 21
 #define GMC_WIN_N (GMC_WIN * GMC_WIN)

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 #include "ss_common.h"
+#include "ss_launch.h"
 #include "ss_expneg.h"
 
 #define GSI_MAX_LEN 1024

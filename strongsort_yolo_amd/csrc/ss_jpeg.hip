@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 #include "ss_common.h"
+#include "ss_launch.h"
 #include "ss_jpeg_host.h"
 
 #define JPEG_HDR 160                    // dwords of an image's header in the stream (see docs/JPEG.md "staging layout")

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "ss_common.h"
+#include "ss_launch.h"
 #include "ss_jpeg_host.h"
 
 #define JENC_WS_PITCH 72                // LDS dwords per block, rows of 9 (8 + 1 pad), as in k_jpeg_idct

@@ -1,0 +1,114 @@
+// ss_launch.h — what ss_api.hip calls in the other translation units, declared once with the definitions' parameter names:
+// the kernel launchers and the host-side state of the JPEG, GSI and MOT stages.  ss_api.hip and every file that defines one of
+// these include it, so each definition is compiled next to its declaration.  C++ linkage: none of this is part of the C ABI.
+#pragma once
+#include <string>
+#include "ss_common.h"
+
+// ---- ss_track.hip: StrongSORT tracker chain and the stage kernels behind the known-answer entry points
+void   ss_step_kernel_attr();
+size_t ss_lsap_lds_bytes();
+size_t ss_frame_lds_bytes(int cap_cost, int cap_t, int cap_d);
+void ss_launch_group_head(const SSDev& dev, const SSParams& prm, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev_assoc);
+void ss_launch_group_chain(const SSDev& dev, const SSParams& prm, hipStream_t st);
+void ss_launch_normalize(const float* raw, int n, float* unit, hipStream_t st);
+void ss_launch_ema(const float* s, const float* f, int n, float a, float b, float* o, hipStream_t st);
+void ss_launch_kf(int op, double* mean, double* cov, const double* z, const double* conf, int n, double wp, double wv, hipStream_t st);
+void ss_launch_project(const double* mean, const double* cov, const double* conf, int n, double wp, double* zmean, double* S, hipStream_t st);
+void ss_launch_pack(const float* nat, int T, int B, float* frag, hipStream_t st);
+void ss_launch_assoc(const float* gal_frag, const int* counts, int T, const float* feats, int D, const double* mean, const double* cov,
+                     const double* xyah, const SSParams& prm, float* feat_frag_scratch, float* part_min_scratch, double* cost, float* cosd,
+                     double* maha, uint8_t* gated, hipStream_t st);
+void ss_launch_iou(const double* t, int T, const double* d, int D, double md, double* cost, hipStream_t st);
+void ss_launch_lsap(const double* cost, int nr, int nc, int* r2c, double* scratch, int* err, hipStream_t st);
+
+// ---- ss_front.hip: letterbox, NMS, ReID crops, result hand-over
+int    ss_front_init();
+extern __attribute__((visibility("hidden"))) int ss_nms_fused;     // a variable's name is not mangled: hidden keeps it out of the exported ss_* names
+size_t ss_nms_workspace_bytes();
+int*   ss_nms_error_flag(void* ws, int unit);
+void ss_launch_letterbox(const uint8_t* src, int batch, long long src_batch_stride, int h, int w, int stride, void* dst, int flags, int out_h,
+                         int out_w, int new_h, int new_w, int pad_top, int pad_left, int pad_value, hipStream_t st);
+int  ss_launch_nms(const float* pred, int batch, long long pred_stride, int N, int nc, int n_extra, float conf, float iou, int agnostic,
+                   float max_wh, int max_det, float gain, float pad_x, float pad_y, float w0, float h0, const float* geom, float* rows,
+                   int row_stride, long long rows_batch_stride, int* keep, long long keep_batch_stride, int* count, void* ws, size_t ws_bytes,
+                   unsigned long long cm0, unsigned long long cm1, hipStream_t st);
+void ss_launch_crop(const uint8_t* frame, int batch, long long frame_batch_stride, int h, int w, int stride, const float* dets, int det_stride,
+                    long long dets_batch_stride, int n, const int* d_count, void* out, int flags, hipStream_t st, const int* d_off);
+void ss_launch_crop_offsets(const int* counts, int batch, int n, int* off, hipStream_t st);
+void ss_launch_unpack_feats(const void* emb, int half, const int* off, const int* counts, int batch, int n, float* feats,
+                            long long feats_img_stride, hipStream_t st);
+void ss_launch_pack_results(const int* n_dets, const float* dets, int det_ld, int det_cap, const int* n_out, const float* out, int out_ld,
+                            int out_cap, float* dst, hipStream_t st);
+
+// ---- ss_overlay.hip, ss_cmc.hip, ss_gmc.hip, ss_mask.hip, ss_byte.hip, ss_native.hip
+void ss_launch_overlay(uint8_t* frames, int batch, long long frame_stride, int h, int w, int row_stride, const void* prims,
+                       const int* prim_off, const uint8_t* chars, const uint8_t* font, hipStream_t st);
+void ss_launch_cmc(const uint8_t* frames, int n_images, long long frame_stride, int h, int w, int row_stride, uint8_t* smalls,
+                   long long img_stride, int S, int n_frames, int hs, int ws, int max_iter, double eps, int* prev_valid,
+                   const int* n_valid, double* warps, hipStream_t st);
+void ss_launch_gmc_sparse(const SSGmcDev& g, const uint8_t* frames, int n_frames, long long frame_stride, int row_stride,
+                          const int* n_valid, double* warps, hipStream_t st);
+int  ss_mask_max_words();
+void ss_launch_mask_assemble(const void* proto, int f16, long long proto_fs, int nm, int mh, int mw, const float* dets, long long dets_fs,
+                             int ld, int coef_off, const int* counts, int S, int R, const float* geom, long long geom_fs, int ih, int iw,
+                             uint32_t* bits, long long bits_fs, hipStream_t st);
+void ss_launch_mask_outline(const uint32_t* bits, long long bits_fs, const int* counts, int S, int R, int ih, int iw, int cap, int* pts,
+                            long long pts_fs, int* npts, long long npts_fs, uint32_t* copy, long long copy_fs, int* scratch, int slots,
+                            hipStream_t st);
+void ss_launch_byte_group(const SSByteDev& b, int F, const float* dets, const int* ndets, const float* feats, float* out, int* nout,
+                          hipStream_t st);
+void ss_launch_byte_group_kpts(const SSByteDev& b, int F, const float* dets, const int* ndets, const float* kpts, long long stride, int off,
+                               const float* geom, float* out, int* nout, hipStream_t st);
+void ss_launch_native_feats(int n_img, int half, const void* const* p, const long long* img_stride, const long long* row_stride,
+                            const long long* pix_stride, const int* channels, const int* height, const int* width, int s,
+                            const int* keep, long long keep_stride, const int* counts, float* out, hipStream_t st);
+
+// ---- ss_jpeg.hip: decoder state of a context (created on first use)
+struct SSJpeg;
+int  ss_jpeg_probe_impl(const unsigned char* data, size_t size, int* width, int* height, int* components, int* h_samp, int* v_samp, std::string& err);
+int  ss_jpeg_coefficients_impl(const unsigned char* data, size_t size, short* coef, size_t coef_cap, unsigned short* quant, std::string& err);
+int  ss_jpeg_decode_impl(SSJpeg** state, hipStream_t stream, const unsigned char* const* data, const size_t* sizes, int n, int height, int width,
+                         void* d_out, long long out_frame_stride, int rgb, int threads, std::string& err);
+void ss_jpeg_free(SSJpeg* j);
+int  ss_jpeg_scan_segments_impl(const unsigned char* data, size_t size, unsigned char* bytes, size_t bytes_cap, size_t* bytes_used,
+                                unsigned int* segments, size_t seg_cap, int* n_segments, unsigned int* header, std::string& err);
+int  ss_jpeg_decode_device_impl(SSJpeg** state, hipStream_t stream, const unsigned char* const* data, const size_t* sizes, int n, int height,
+                                int width, void* d_out, long long out_frame_stride, int rgb, int threads, short* coef, size_t coef_cap,
+                                std::string& err);
+int  ss_jpeg_pending_impl(SSJpeg* j, std::string& err);
+int  ss_jpeg_device_rounds_impl(SSJpeg* j, int* rounds, int cap);
+
+// ---- ss_jpeg_enc.hip: encoder state of a context
+struct SSJpegEnc;
+size_t ss_jpeg_encode_bound_impl(int width, int height, int h_samp, int v_samp);
+int  ss_jpeg_entropy_encode_impl(const short* coef, int quality, int width, int height, int h_samp, int v_samp, unsigned char* out,
+                                 size_t* out_size, std::string& err);
+int  ss_jpeg_encode_impl(SSJpegEnc** state, hipStream_t stream, const void* d_in, long long in_frame_stride, int n, int height, int width,
+                         int rgb, int quality, int h_samp, int v_samp, int threads, unsigned char* const* out, size_t* out_size, std::string& err);
+int  ss_jpeg_encode_device_impl(SSJpegEnc** state, hipStream_t stream, const void* d_in, long long in_frame_stride, int n, int height, int width,
+                                int rgb, int quality, int h_samp, int v_samp, int threads, unsigned char* const* out, size_t* out_size,
+                                std::string& err);
+int  ss_jpeg_entropy_encode_device_impl(SSJpegEnc** state, hipStream_t stream, const short* coef, int quality, int width, int height, int h_samp,
+                                        int v_samp, unsigned char* out, size_t* out_size, std::string& err);
+void ss_jpeg_enc_free(SSJpegEnc* j);
+
+// ---- ss_gsi.hip
+struct SSGsi;
+int  ss_gsi_max_len_impl();
+int  ss_gsi_check_impl(int n_tracks, const int* offsets, const int* frames, const double* vals, const double* len_scale, double alpha,
+                       const double* out, const int* status, std::string& err);
+int  ss_gsi_smooth_impl(SSGsi** pg, hipStream_t stream, int n_tracks, const int* offsets, const int* frames, const double* vals,
+                        const double* len_scale, double alpha, double* out, int* status, std::string& err);
+void ss_gsi_free(SSGsi* g);
+
+// ---- ss_mot.hip
+struct SSMot;
+int  ss_mot_max_boxes_impl();
+int  ss_mot_check_impl(int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id, const int* tr_id,
+                       const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
+                       const int* hota_idx, const double* hota_s, const int* clear_idx, const double* clear_s, std::string& err);
+int  ss_mot_eval_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id,
+                      const int* tr_id, const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
+                      int* hota_idx, double* hota_s, int* clear_idx, double* clear_s, double* ga, std::string& err);
+void ss_mot_free(SSMot* m);

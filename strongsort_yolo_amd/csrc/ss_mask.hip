@@ -10,6 +10,7 @@
 // yolo.trace_outline's Moore walk over the bits held in LDS, the first outline of maximal length kept.  Points are int32 (x, y).
 #include <hip/hip_fp16.h>
 #include "ss_common.h"
+#include "ss_launch.h"
 
 #define MK_BAND 32            // output rows per assembly workgroup
 #define MK_BAND_PROTO 12      // prototype rows a band reads at most (MK_BAND / 4 + 2, rounded up)

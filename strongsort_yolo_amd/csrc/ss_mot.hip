@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 #include "ss_common.h"
+#include "ss_launch.h"
 #include "ss_lsap.h"
 
 #define MOT_MAX_BOXES 256

@@ -10,6 +10,7 @@
 //                   (its g channels are contiguous in the channels-last map) and writes the columns l, l+64, ...; rows at or
 //                   past the image's count are not touched.
 #include "ss_common.h"
+#include "ss_launch.h"
 #include <hip/hip_fp16.h>
 
 struct SSNativeMaps {

@@ -9,6 +9,7 @@
 // order into LDS, and every pixel walks the hits in order with exact integer coverage tests (no floating point, so the
 // NumPy rasteriser used as the oracle reproduces every pixel).  Pixels no primitive covers are not touched.
 #include "ss_common.h"
+#include "ss_launch.h"
 
 #define OV_RECT 0      // outline of box (x0,y0)-(x1,y1), thickness a centred on the box edge
 #define OV_FILL 1      // filled rectangle, corners in any order

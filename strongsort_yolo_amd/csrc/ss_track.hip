@@ -14,6 +14,7 @@
 // No host round trip anywhere in the group.
 #include <hip/hip_ext.h>
 #include "ss_common.h"
+#include "ss_launch.h"
 #include "ss_lsap.h"
 
 // Memory operations without a return value as inline assembly: the compiler's wait-count pass does not see them, so they do
@@ -1539,7 +1540,7 @@ __global__ void k_kat_iou(const double* ttlwh, int T, const double* dtlwh, int D
 size_t ss_lsap_lds_bytes() { return 256 * 4; }
 size_t ss_assoc_lds_bytes() { return 2 * SS_TILE_FLOATS * 4 + 7 * 2048 + 64 + 256; }       // B pair, hand-over slots, flags, column map
 
-extern "C" void ss_step_kernel_attr()
+void ss_step_kernel_attr()
 {
     // a failure here surfaces as a launch error on first use (checked with hipGetLastError after every launch)
     (void)hipFuncSetAttribute((const void*)k_frame, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ss_frame_lds_bytes(SS_COST_CAP, SS_MAXT, SS_MAXD));

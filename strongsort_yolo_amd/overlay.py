@@ -124,7 +124,7 @@ class Overlay:
         self._scratch = None
         if engine is not None:
             t = np.ascontiguousarray(font_table())
-            engine._ck(engine.L.ss_overlay_set_font(engine.ctx, t.ctypes.data_as(C.c_void_p)))
+            engine._ck(engine.L.ss_overlay_set_font(engine.ctx, t.ctypes.data_as(C.POINTER(C.c_uint8))))
 
     # ---- the reference's drawing sequence as data ---------------------------------------------------------
     def commands(self, results, counts: Optional[dict] = None, fps_text: str = "") -> CommandList:

@@ -2,8 +2,12 @@
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
-from strongsort_yolo_amd import lib
+import pytest
+
+from strongsort_yolo_amd import cheader, lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -22,6 +26,16 @@ def test_library_exports_every_declared_symbol():
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, missing
     assert sorted(names) == sorted(lib.EXPORTS)          # the ctypes binding covers the whole header
+
+
+def test_library_exports_only_declared_symbols():
+    """Nothing under the ss_ prefix leaves the library that the header does not declare."""
+    if shutil.which("nm") is None:
+        pytest.skip("nm is not installed: the library's symbol table cannot be listed")
+    lib.build()
+    out = subprocess.run(["nm", "-D", "--defined-only", lib.SO_PATH], check=True, capture_output=True, text=True).stdout
+    defined = sorted({line.split()[-1].split("@")[0] for line in out.splitlines() if line.split()[-1].startswith("ss_")})
+    assert defined == _declared()
 
 
 def test_config_struct_matches_header():
@@ -65,3 +79,93 @@ def test_host_side_entry_points_without_a_gpu():
     assert L.ss_op_upcat_f16(None, None, None, None, 1, 4, 4, 8, 8, 1) < 0
     assert L.ss_op_sppf_pools_f16(None, None, None, 1, 40, 40, 8) < 0   # H*W > 1024 (and null tensors)
     assert L.ss_op_conv0_f16(None, None, None, None, None, 1, 8, 100, 16, 2) < 0
+
+
+# ---- the binding is derived from the header (strongsort_yolo_amd/cheader.py): checked here with regular expressions of the test's own
+
+_CTYPE = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong, "void": None,
+          "const char*": ctypes.c_char_p, "const void*": ctypes.c_void_p, "void*": ctypes.c_void_p}
+
+
+def _header_code():
+    src = open(os.path.join(ROOT, "include", "strongsort_hip.h")).read()
+    return re.sub(r"/\*.*?\*/|//[^\n]*", "", src, flags=re.S)
+
+
+def _prototypes():
+    """name -> (return type, parameter texts) of every function declaration."""
+    protos = {m.group(2): (" ".join(m.group(1).split()).replace(" *", "*"), [] if m.group(3).strip() == "void" else m.group(3).split(","))
+              for m in re.finditer(r"^([A-Za-z][\w \t*]*?)\s*\b(ss_\w+)\s*\(([^()]*)\)\s*;", _header_code(), flags=re.M)}
+    assert len(protos) >= 127
+    return protos
+
+
+def test_every_function_has_the_declared_argument_count_and_return_type():
+    lib.build()
+    L = lib.load()
+    protos = _prototypes()
+    assert sorted(protos) == sorted(lib.EXPORTS)
+    for name, (ret, params) in protos.items():
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), name
+        assert fn.restype is _CTYPE[ret], (name, ret, fn.restype)
+    assert ctypes.sizeof(L.ss_op_dwtab_bytes.restype) == 8 and ctypes.sizeof(L.ss_jpeg_encode_bound.restype) == 8
+
+
+# sizes by natural alignment: ss_config 8 doubles + 5 ints = 84, padded to its 8-byte alignment; ss_byte_config 6 doubles + 6 ints;
+# ss_conv_desc 4 pointers + 8 ints; ss_native_map 1 pointer + 3 long long + 3 ints = 44, padded to 48
+@pytest.mark.parametrize("name,size", [("ss_config", 88), ("ss_byte_config", 72), ("ss_conv_desc", 64), ("ss_native_map", 48)])
+def test_struct_matches_header_field_by_field(name, size):
+    m = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), _header_code(), flags=re.S)
+    fields = []
+    for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
+        t, names = re.fullmatch(r"((?:const )?(?:long long|\w+)\*?)\s+(\w+(?:\s*,\s*\w+)*)", decl).groups()
+        fields += [(n.strip(), _CTYPE[t]) for n in names.split(",")]
+    struct = getattr(lib, name)
+    assert issubclass(struct, ctypes.Structure) and struct.__name__ == name
+    assert fields == [(n, t) for n, t in struct._fields_]
+    assert ctypes.sizeof(struct) == size
+
+
+def test_constants_come_from_the_header():
+    defines = {n: int(v) for n, v in re.findall(r"^#define (SS_\w+) \(?(-?\d+)\)?", _header_code(), flags=re.M)}
+    assert len(defines) == 12
+    for n, v in defines.items():
+        assert getattr(lib, n if n == "SS_OK" or n.startswith("SS_ERR_") else n[3:]) == v, n
+
+
+@pytest.mark.parametrize("text", [
+    "int ss_f(ss_ctx* ctx, __half* d_x);",                 # a type the header does not use
+    "int ss_f(wchar_t n);",
+    "int ss_f(int a, int (*cb)(int));",                    # not flat
+    "int ss_f(int a;",                                     # unbalanced parenthesis
+    "int ss_f(int a));",
+    "int ss_f(int);",                                      # a parameter without a name
+    "int ss_f(ss_config cfg);",                            # a struct by value
+    "int ss_f(int*** p);",
+    "int ss_f(int a)",                                     # no semicolon
+    "#define SS_X (1 << 3)",
+    "typedef struct ss_s { int a[4]; } ss_s;",
+    "typedef int ss_int;",
+    "static int ss_x = 3;",
+    "int ss_f(int a); int ss_f(int a);",                   # declared twice
+])
+def test_parser_raises_on_what_it_cannot_classify(text):
+    prefix = "typedef struct ss_ctx ss_ctx;\ntypedef struct ss_config { int a; } ss_config;\n"
+    assert cheader.Header(prefix + "int ss_f(ss_ctx* ctx, const ss_config* cfg, const float* d_x);").functions["ss_f"][1][2] is ctypes.c_void_p
+    with pytest.raises(cheader.HeaderError):
+        cheader.Header(prefix + text)
+
+
+def test_typed_host_pointers_reject_the_wrong_array():
+    """Host scalar pointers stay typed: ctypes refuses the call before the library sees it (no GPU call is made)."""
+    lib.build()
+    L = lib.load()
+    assert L.ss_nms_set_classes.argtypes[1] == ctypes.POINTER(ctypes.c_int)
+    with pytest.raises(ctypes.ArgumentError):
+        L.ss_nms_set_classes(None, (ctypes.c_float * 4)(), 4)
+    with pytest.raises(ctypes.ArgumentError):
+        L.ss_gsi_smooth(None, 1, (ctypes.c_int * 2)(0, 1), (ctypes.c_int * 1)(), (ctypes.c_float * 4)(), None, 0.0, None, None)
+    with pytest.raises(ctypes.ArgumentError):
+        L.ss_op_conv_group_f16(None, 1, (lib.ss_native_map * 1)())
+    assert L.ss_nms_set_classes(None, (ctypes.c_int * 4)(), 4) == lib.SS_ERR_INVALID      # the right type reaches the library: null context
