@@ -1387,11 +1387,41 @@ extern "C" int ss_byte_create(ss_ctx* c, const ss_byte_config* cfg)
     return SS_OK;
 }
 
+// Synchronous: the slots of one stream's BYTE lists in list order (tracked, then lost) -> slots, after the stream has drained.
+// nt / nl: the lists' lengths; fn: the caller's name for the message.  More than cap entries or a slot out of range is an error.
+static int byte_read_lists(ss_ctx* c, const char* fn, int s, int cap, int& nt, int& nl, std::vector<int>& slots)
+{
+    const SSByteDev& b = c->byte->dev;
+    HIPCHK(c, hipMemcpy(&nt, b.n_trk + s, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&nl, b.n_lost + s, 4, hipMemcpyDeviceToHost));
+    if (nt + nl > cap) return fail(c, SS_ERR_CAPACITY, std::string(fn) + ": cap too small");
+    const size_t T = SS_MAXT, sb = (size_t)s * T;
+    std::vector<int> trk(T), lost(T);
+    HIPCHK(c, hipMemcpy(trk.data(), b.trk + sb, T * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(lost.data(), b.lost + sb, T * 4, hipMemcpyDeviceToHost));
+    slots.resize(nt + nl);
+    for (int i = 0; i < nt + nl; ++i) {
+        slots[i] = i < nt ? trk[i] : lost[i - nt];
+        if (slots[i] < 0 || slots[i] >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, std::string(fn) + ": corrupt list");
+    }
+    return SS_OK;
+}
+
+// the checks every ss_byte_update_group* entry point makes first (ok: its pointer arguments are all there; need_pose: it is the one
+// that needs the keypoint term on); fn: its name for the message
+static int byte_update_check(ss_ctx* c, const char* fn, bool ok, int n_frames, bool need_pose = false)
+{
+    const std::string f = fn;
+    if (!c || !ok) return fail(c, SS_ERR_INVALID, f + ": null argument");
+    if (!c->byte) return fail(c, SS_ERR_INVALID, f + ": no BYTE state (ss_byte_create)");
+    if (need_pose && !c->byte->dev.pose) return fail(c, SS_ERR_INVALID, f + ": the keypoint term is off (ss_byte_set_pose)");
+    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, f + ": 1 <= n_frames <= SS_FMAX");
+    return SS_OK;
+}
+
 extern "C" int ss_byte_update_group(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout)
 {
-    if (!c || !d_dets || !d_ndets || !d_out || !d_nout) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: null argument");
-    if (!c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: no BYTE state (ss_byte_create)");
-    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: 1 <= n_frames <= SS_FMAX");
+    if (const int rc = byte_update_check(c, "ss_byte_update_group", d_dets && d_ndets && d_out && d_nout, n_frames)) return rc;
     if (c->byte->dev.reid) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: ReID is on, the features go through ss_byte_update_group_feats");
     if (c->byte->dev.pose) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: the keypoint term is on, the keypoints go through ss_byte_update_group_kpts");
     ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, nullptr, d_out, d_nout, c->stream);
@@ -1404,9 +1434,7 @@ extern "C" int ss_byte_update_group(ss_ctx* c, int n_frames, const float* d_dets
 extern "C" int ss_byte_update_group_feats(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, const float* d_feats,
                                           float* d_out, int* d_nout)
 {
-    if (!c || !d_dets || !d_ndets || !d_out || !d_nout) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: null argument");
-    if (!c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: no BYTE state (ss_byte_create)");
-    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: 1 <= n_frames <= SS_FMAX");
+    if (const int rc = byte_update_check(c, "ss_byte_update_group_feats", d_dets && d_ndets && d_out && d_nout, n_frames)) return rc;
     if (c->byte->dev.reid && !d_feats) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: ReID is on and d_feats is NULL");
     if (c->byte->dev.pose) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: the keypoint term is on, the keypoints go through ss_byte_update_group_kpts");
     ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, d_feats, d_out, d_nout, c->stream);
@@ -1485,11 +1513,8 @@ extern "C" int ss_byte_set_pose(ss_ctx* c, int on, int n_kpt, const double* sigm
 extern "C" int ss_byte_update_group_kpts(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, const float* d_kpts,
                                          long long kpt_row_stride, int kpt_col_offset, const float* d_geom, float* d_out, int* d_nout)
 {
-    if (!c || !d_dets || !d_ndets || !d_kpts || !d_out || !d_nout) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_kpts: null argument");
-    if (!c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_kpts: no BYTE state (ss_byte_create)");
+    if (const int rc = byte_update_check(c, "ss_byte_update_group_kpts", d_dets && d_ndets && d_kpts && d_out && d_nout, n_frames, true)) return rc;
     const SSByteDev& b = c->byte->dev;
-    if (!b.pose) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_kpts: the keypoint term is off (ss_byte_set_pose)");
-    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_kpts: 1 <= n_frames <= SS_FMAX");
     if (kpt_col_offset < 0 || kpt_row_stride < (long long)kpt_col_offset + 3 * b.nk)
         return fail(c, SS_ERR_INVALID, "ss_byte_update_group_kpts: kpt_col_offset >= 0, kpt_row_stride >= kpt_col_offset + 3 n_kpt");
     ss_launch_byte_group_kpts(b, n_frames, d_dets, d_ndets, d_kpts, kpt_row_stride, kpt_col_offset, d_geom, d_out, d_nout, c->stream);
@@ -1506,22 +1531,16 @@ extern "C" int ss_byte_get_keypoints(ss_ctx* c, int s, int cap, double* offsets,
     if (!b.tpose) return fail(c, SS_ERR_INVALID, "ss_byte_get_keypoints: the keypoint term was never switched on (ss_byte_set_pose)");
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int nt = 0, nl = 0;
-    HIPCHK(c, hipMemcpy(&nt, b.n_trk + s, 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&nl, b.n_lost + s, 4, hipMemcpyDeviceToHost));
-    if (nt + nl > cap) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_keypoints: cap too small");
+    std::vector<int> slots;
+    if (const int rc = byte_read_lists(c, "ss_byte_get_keypoints", s, cap, nt, nl, slots)) return rc;
     const size_t T = SS_MAXT, sb = (size_t)s * T, K2 = (size_t)b.nk * 2;
-    std::vector<int> trk(T), lost(T);
     std::vector<double> po(T * K2);
     std::vector<unsigned> vi(T);
-    HIPCHK(c, hipMemcpy(trk.data(), b.trk + sb, T * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(lost.data(), b.lost + sb, T * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(po.data(), b.tpose + sb * K2, T * K2 * 8, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(vi.data(), b.tvis + sb, T * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < nt + nl; ++i) {
-        const int slot = i < nt ? trk[i] : lost[i - nt];
-        if (slot < 0 || slot >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_keypoints: corrupt list");
-        if (offsets) memcpy(offsets + (size_t)i * K2, po.data() + (size_t)slot * K2, K2 * 8);
-        if (visible) visible[i] = vi[slot];
+    for (size_t i = 0; i < slots.size(); ++i) {
+        if (offsets) memcpy(offsets + i * K2, po.data() + (size_t)slots[i] * K2, K2 * 8);
+        if (visible) visible[i] = vi[slots[i]];
     }
     return SS_OK;
 }
@@ -1579,20 +1598,12 @@ extern "C" int ss_byte_get_features(ss_ctx* c, int s, int cap, float* smooth)
     if (!b.smooth) return fail(c, SS_ERR_INVALID, "ss_byte_get_features: ReID was never switched on (ss_byte_set_reid)");
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int nt = 0, nl = 0;
-    HIPCHK(c, hipMemcpy(&nt, b.n_trk + s, 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&nl, b.n_lost + s, 4, hipMemcpyDeviceToHost));
-    if (nt + nl > cap) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_features: cap too small");
+    std::vector<int> slots;
+    if (const int rc = byte_read_lists(c, "ss_byte_get_features", s, cap, nt, nl, slots)) return rc;
     const size_t T = SS_MAXT, sb = (size_t)s * T;
-    std::vector<int> trk(T), lost(T);
     std::vector<float> sm(T * SS_F);
-    HIPCHK(c, hipMemcpy(trk.data(), b.trk + sb, T * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(lost.data(), b.lost + sb, T * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(sm.data(), b.smooth + sb * SS_F, T * SS_F * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < nt + nl; ++i) {
-        const int slot = i < nt ? trk[i] : lost[i - nt];
-        if (slot < 0 || slot >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_features: corrupt list");
-        memcpy(smooth + (size_t)i * SS_F, sm.data() + (size_t)slot * SS_F, SS_F * 4);
-    }
+    for (size_t i = 0; i < slots.size(); ++i) memcpy(smooth + i * SS_F, sm.data() + (size_t)slots[i] * SS_F, SS_F * 4);
     return SS_OK;
 }
 
@@ -1618,27 +1629,24 @@ extern "C" int ss_byte_get_tracks(ss_ctx* c, int s, int cap, int* n_tracked, int
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const SSByteDev& b = c->byte->dev;
     int nt = 0, nl = 0, nid = 0, fr = 0;
-    HIPCHK(c, hipMemcpy(&nt, b.n_trk + s, 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&nl, b.n_lost + s, 4, hipMemcpyDeviceToHost));
+    std::vector<int> slots;
     HIPCHK(c, hipMemcpy(&nid, b.next_id + s, 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(&fr, b.frame + s, 4, hipMemcpyDeviceToHost));
-    if (n_tracked) *n_tracked = nt;
+    const int rc = byte_read_lists(c, "ss_byte_get_tracks", s, cap, nt, nl, slots);
+    if (n_tracked) *n_tracked = nt;                                  // the counts also when cap is too small: the caller sizes by them
     if (n_lost) *n_lost = nl;
     if (next_id) *next_id = nid;
     if (frame_id) *frame_id = fr;
-    if (nt + nl > cap) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_tracks: cap too small");
+    if (rc) return rc;
     const size_t T = SS_MAXT, sb = (size_t)s * T;
-    std::vector<int> trk(T), lost(T), st(T), act(T), id(T);
+    std::vector<int> st(T), act(T), id(T);
     std::vector<double> mn(T * 8);
-    HIPCHK(c, hipMemcpy(trk.data(), b.trk + sb, T * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(lost.data(), b.lost + sb, T * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(st.data(), b.state + sb, T * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(act.data(), b.act + sb, T * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(id.data(), b.tid + sb, T * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(mn.data(), b.mean + sb * 8, T * 64, hipMemcpyDeviceToHost));
     for (int i = 0; i < nt + nl; ++i) {
-        const int slot = i < nt ? trk[i] : lost[i - nt];
-        if (slot < 0 || slot >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, "ss_byte_get_tracks: corrupt list");
+        const int slot = slots[i];
         if (track_id) track_id[i] = id[slot];
         if (state) state[i] = st[slot];
         if (activated) activated[i] = act[slot];

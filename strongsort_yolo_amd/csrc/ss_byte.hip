@@ -80,13 +80,7 @@ __device__ inline void byte_gmc(double* mean, double* cov, const double* w)
         }
 }
 
-// cost of (row r, column c) as stored for the LSAP: rows = the smaller side (transposed when there are fewer columns)
-__device__ inline size_t byte_cidx(int r, int c, int n_rows, int n_cols)
-{
-    return n_cols < n_rows ? (size_t)c * n_rows + r : (size_t)r * n_cols + c;
-}
-
-// LSAP of an n_rows x n_cols matrix already stored by byte_cidx -> m.asg[row] = column or -1 (all threads call it).
+// LSAP of an n_rows x n_cols matrix already stored by lsap_cidx -> m.asg[row] = column or -1 (all threads call it).
 __device__ inline void byte_assign(int n_rows, int n_cols, const double* cost, bool glb, ByteLds& m, int* err)
 {
     const int tid = threadIdx.x;
@@ -94,19 +88,15 @@ __device__ inline void byte_assign(int n_rows, int n_cols, const double* cost, b
     if (glb) __threadfence();                     // the spilled matrix is read back by wave 0
     __syncthreads();
     if (n_rows > 0 && n_cols > 0 && (tid >> 6) == 0) {
-        const bool tr = n_cols < n_rows;
-        const int nr = tr ? n_cols : n_rows, nc = tr ? n_rows : n_cols;
         LsapLds L;
         L.col4row = m.col4row;
-        const int rc = lsap_wave(nr, nc, cost, L);
-        if (rc) { if (tid == 0) *err = SS_ERR_INFEASIBLE; }
-        else for (int i = tid; i < nr; i += 64) { if (tr) m.asg[L.col4row[i]] = i; else m.asg[i] = L.col4row[i]; }
+        if (lsap_wave_assign(n_rows, n_cols, cost, L, m.asg) && tid == 0) *err = SS_ERR_INFEASIBLE;
     }
     __syncthreads();
 }
 
-// §1c: the unit feature of every detection row of the group, so_normalize order (lane l chains k = l, l+64, ...; the xor
-// butterfly of so_sumsq); an all-zero row stays zero (D-17).  Block = 4 rows (one wave each) of one (frame, stream).
+// §1c: the unit feature of every detection row of the group (ss_unit8: so_normalize order).  Block = 4 rows (one wave each) of one
+// (frame, stream).
 __global__ __launch_bounds__(256) void k_byte_feats(SSByteDev b, const float* __restrict__ feats, const int* __restrict__ ndets)
 {
     const int s = blockIdx.y, f = blockIdx.z, r = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
@@ -115,43 +105,56 @@ __global__ __launch_bounds__(256) void k_byte_feats(SSByteDev b, const float* __
     if (r >= N) return;                                           // whole waves
     const float* in = feats + (fs * SS_MAXD + r) * SS_F;
     float* out = b.ufeat + (fs * SS_MAXD + r) * SS_F;
-    float v[8], acc = 0.0f;
+    float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { v[j] = in[l + 64 * j]; acc = fmaf(v[j], v[j], acc); }
-    const float n = sqrtf(ss_wave_sumsq_reduce(acc));
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[l + 64 * j] = n > 0.0f ? v[j] / n : 0.0f;
+    for (int j = 0; j < 8; ++j) v[j] = in[l + 64 * j];
+    ss_unit8(v, out);
 }
 
-// §1c get_dists with ReID on rows (track slots rs[r]) x columns (detections cd[k]) of frame fs, stored by byte_cidx:
+// First half of a 256-entry chunk of BoT-SORT's get_dists with a second term (§1c ReID, §1e keypoints), each thread one entry e0 + tid
+// of rows (track slots rs[r]) x columns (detections cd[k]), stored by lsap_cidx:  iou = 1 - IoU;  c = fused(iou) if fuse.  An entry
+// with iou > prox is masked: its second term is 1, so it stores min(c, 1) — c itself for ReID (pose = false: c <= 1, or NaN, which
+// np.minimum keeps), the clamped value for the keypoint term.  The others — overlapping boxes, about one per track — are compacted
+// into ae / ac (entry, c; one pair of LDS arrays for both terms: they are never instantiated together) for the caller's second
+// half.  Returns their number.
+__device__ inline int byte_cost_chunk(int e0, int nR, int nC, const int* rs, const int* cd, double* cost, const SSByteDev& b, bool pose,
+                                      ByteLds& m, int*& ae, double*& ac)
+{
+    __shared__ int s_ae[256];
+    __shared__ double s_ac[256];
+    ae = s_ae; ac = s_ac;
+    const int e = e0 + threadIdx.x;
+    int need = 0;
+    double c = 0.0;
+    if (e < nR * nC) {
+        const int r = e / nC, k = e - r * nC, d = cd[k];
+        const double iou = ss_iou_cost(m.tl[rs[r]], m.dtl[d], 2.0);
+        c = b.fuse ? 1.0 - (1.0 - iou) * (double)m.dsc[d] : iou;
+        need = !(iou > b.prox);
+        if (!need) cost[lsap_cidx(r, k, nR, nC)] = pose && 1.0 < c ? 1.0 : c;
+    }
+    int pos, nA;
+    block_scan256(need, m.wtot, pos, nA);
+    if (need) { s_ae[pos] = e; s_ac[pos] = c; }
+    __syncthreads();
+    return nA;
+}
+
+// §1c get_dists with ReID on rows (track slots rs[r]) x columns (detections cd[k]) of frame fs, stored by lsap_cidx:
 //   iou = 1 - IoU;  c = fused(iou) if fuse;  e = 1 if iou > prox, else max(0, 1 - so_dot(smooth, curr)) / 2 -> 1 if > appear;
 //   cost = min(c, e).
-// A masked entry is c (c <= 1, or NaN, which np.minimum keeps), so only the pairs with iou <= prox — overlapping boxes, about
-// one per track — get a dot product.  The entries go by chunks of 256: each thread one entry, the unmasked ones compacted
-// in LDS, then eight lanes per pair run so_dot's eight 64-long fmaf chains (lane = segment) and lane 0 of the eight adds
+// Only the unmasked pairs get a dot product.  The entries go by chunks of 256 (byte_cost_chunk), then eight lanes per pair run
+// so_dot's eight 64-long fmaf chains (lane = segment) and lane 0 of the eight adds
 // them in segment order.  A dense MFMA matrix (k_cosine_kat's form) would compute the whole rows x columns product for the
 // few unmasked pairs (docs/BYTETRACK.md §3).
 __device__ inline void byte_reid_cost(int nR, int nC, const int* rs, const int* cd, double* cost, const SSByteDev& b,
                                             size_t sb, size_t fs, ByteLds& m)
 {
-    __shared__ int ae[256];
-    __shared__ double ac[256];
     const int tid = threadIdx.x, seg = tid & 7, base = (tid & 63) & ~7, n = nR * nC;
+    int* ae;
+    double* ac;
     for (int e0 = 0; e0 < n; e0 += 256) {
-        const int e = e0 + tid;
-        int need = 0;
-        double c = 0.0;
-        if (e < n) {
-            const int r = e / nC, k = e - r * nC, d = cd[k];
-            const double iou = ss_iou_cost(m.tl[rs[r]], m.dtl[d], 2.0);
-            c = b.fuse ? 1.0 - (1.0 - iou) * (double)m.dsc[d] : iou;
-            need = !(iou > b.prox);
-            if (!need) cost[byte_cidx(r, k, nR, nC)] = c;
-        }
-        int pos, nA;
-        block_scan256(need, m.wtot, pos, nA);
-        if (need) { ae[pos] = e; ac[pos] = c; }
-        __syncthreads();
+        const int nA = byte_cost_chunk(e0, nR, nC, rs, cd, cost, b, false, m, ae, ac);
         for (int j0 = 0; j0 < nA; j0 += 32) {
             const int j = j0 + (tid >> 3);
             int r = 0, k = 0;
@@ -173,7 +176,7 @@ __device__ inline void byte_reid_cost(int nR, int nC, const int* rs, const int* 
                 double a = (double)fmaxf(0.0f, 1.0f - tot) / 2.0;
                 if (a > b.appear) a = 1.0;
                 const double cf = ac[j];
-                cost[byte_cidx(r, k, nR, nC)] = a < cf ? a : cf;
+                cost[lsap_cidx(r, k, nR, nC)] = a < cf ? a : cf;
             }
         }
         __syncthreads();                                           // ae / ac: the next chunk's
@@ -201,27 +204,17 @@ __device__ inline void byte_reid_smooth(const SSByteDev& b, size_t sb, size_t fs
     for (int i = 2 * w; i < nU; i += 8) {
         const int two = i + 1 < nU;
         float* sm[2];
-        float v[2][8], acc[2] = {0.0f, 0.0f};
+        float sv[2][8], cv[2][8];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int slot = m.freel[two ? i + u : i];
             sm[u] = b.smooth + (sb + slot) * SS_F;
             const float* cu = b.ufeat + (fs * SS_MAXD + m.upd[slot]) * SS_F;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float t1 = b.alpha * sm[u][l + 64 * j];
-                const float t2 = b.one_minus_alpha * cu[l + 64 * j];
-                v[u][j] = t1 + t2;
-                acc[u] = fmaf(v[u][j], v[u][j], acc[u]);
-            }
+            for (int j = 0; j < 8; ++j) { sv[u][j] = sm[u][l + 64 * j]; cv[u][j] = cu[l + 64 * j]; }
         }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const float n = sqrtf(ss_wave_sumsq_reduce(acc[u]));
-            if (u == 0 || two)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) sm[u][l + 64 * j] = n > 0.0f ? v[u][j] / n : 0.0f;
-        }
+        ss_ema_regs(sv[0], cv[0], b.alpha, b.one_minus_alpha, sm[0]);
+        if (two) ss_ema_regs(sv[1], cv[1], b.alpha, b.one_minus_alpha, sm[1]);
     }
 }
 
@@ -249,33 +242,20 @@ __global__ __launch_bounds__(256) void k_byte_kpts(SSByteDev b, const float* __r
     if (on && k == 0) b.kvis[fs * SS_MAXD + r] = (unsigned)(w >> (threadIdx.x & 32));
 }
 
-// §1e get_dists with the keypoint term on rows (track slots rs[r]) x columns (detections cd[k]) of frame fs, stored by byte_cidx:
+// §1e get_dists with the keypoint term on rows (track slots rs[r]) x columns (detections cd[k]) of frame fs, stored by lsap_cidx:
 //   iou = 1 - IoU;  c = fused(iou) if fuse;  e = 1 if iou > prox, else the pair's OKS entry;  cost = min(c, e).
-// byte_reid_cost's chunked shape: each thread one entry, the unmasked ones (overlapping boxes, about one per track) compacted
-// in LDS; then half a wave per surviving pair, lane = keypoint: the track's stored offset on its predicted mean (b.mean, moved
+// byte_reid_cost's chunked shape (byte_cost_chunk); then half a wave per surviving pair, lane = keypoint: the track's stored offset
+// on its predicted mean (b.mean, moved
 // by GMC already) against the row's keypoint, t_k = ss_expneg(d2 / (2 area (2 sigma_k)^2)).  Every lane of the half then adds
 // the common keypoints' terms in keypoint order (shuffles within the half) and lane 0 stores.
 __device__ inline void byte_pose_cost(int nR, int nC, const int* rs, const int* cd, double* cost, const SSByteDev& b,
                                       size_t sb, size_t fs, ByteLds& m)
 {
-    __shared__ int pe[256];
-    __shared__ double pc[256];
     const int tid = threadIdx.x, kk = tid & 31, base = tid & 32, n = nR * nC, K = b.nk;
+    int* pe;
+    double* pc;
     for (int e0 = 0; e0 < n; e0 += 256) {
-        const int e = e0 + tid;
-        int need = 0;
-        double c = 0.0;
-        if (e < n) {
-            const int r = e / nC, k = e - r * nC, d = cd[k];
-            const double iou = ss_iou_cost(m.tl[rs[r]], m.dtl[d], 2.0);
-            c = b.fuse ? 1.0 - (1.0 - iou) * (double)m.dsc[d] : iou;
-            need = !(iou > b.prox);
-            if (!need) cost[byte_cidx(r, k, nR, nC)] = 1.0 < c ? 1.0 : c;
-        }
-        int pos, nA;
-        block_scan256(need, m.wtot, pos, nA);
-        if (need) { pe[pos] = e; pc[pos] = c; }
-        __syncthreads();
+        const int nA = byte_cost_chunk(e0, nR, nC, rs, cd, cost, b, true, m, pe, pc);
         for (int j0 = 0; j0 < nA; j0 += 8) {
             const int j = j0 + (tid >> 5);
             const bool act = j < nA;
@@ -310,7 +290,7 @@ __device__ inline void byte_pose_cost(int nR, int nC, const int* rs, const int* 
                     if (a > b.pose_thresh) a = 1.0;
                 }
                 const double cf = pc[j];
-                cost[byte_cidx(r, k, nR, nC)] = a < cf ? a : cf;
+                cost[lsap_cidx(r, k, nR, nC)] = a < cf ? a : cf;
             }
         }
         __syncthreads();                                           // pe / pc: the next chunk's
@@ -418,7 +398,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
 #pragma unroll
             for (int i = 0; i < 64; ++i) cov[i] = b.cov[g * 64 + i];
             if (m.state[slot] != SS_BYTE_TRACKED) { mean[7] = 0.0; if (XYWH) mean[6] = 0.0; }
-            if (XYWH) ss_kf_predict_xywh(mean, cov, b.wp, b.wv); else ss_kf_predict(mean, cov, b.wp, b.wv);
+            ss_kf_predict<XYWH>(mean, cov, b.wp, b.wv);
             if (warp) byte_gmc(mean, cov, gw);
 #pragma unroll
             for (int i = 0; i < 8; ++i) b.mean[g * 8 + i] = mean[i];
@@ -456,12 +436,12 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
                 const int r = e / nHi, k = e - r * nHi, d = m.hi[k];
                 double c = ss_iou_cost(m.tl[m.pool[r]], m.dtl[d], 2.0);
                 if (b.fuse) c = 1.0 - (1.0 - c) * (double)m.dsc[d];
-                cost[byte_cidx(r, k, nP, nHi)] = c;
+                cost[lsap_cidx(r, k, nP, nHi)] = c;
             }
             byte_assign(nP, nHi, cost, glb, m, err);
             if (tid < nP) {
                 const int k = m.asg[tid];
-                if (k >= 0 && cost[byte_cidx(tid, k, nP, nHi)] <= b.match) {
+                if (k >= 0 && cost[lsap_cidx(tid, k, nP, nHi)] <= b.match) {
                     const int slot = m.pool[tid], d = m.hi[k];
                     m.hused[k] = 1;
                     m.upd[slot] = d;
@@ -482,12 +462,12 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             double* cost = glb ? spill : m.cost;
             for (int e = tid; e < nR2 * nLo; e += 256) {
                 const int r = e / nLo, k = e - r * nLo;
-                cost[byte_cidx(r, k, nR2, nLo)] = ss_iou_cost(m.tl[m.r2[r]], m.dtl[m.lo[k]], 2.0);
+                cost[lsap_cidx(r, k, nR2, nLo)] = ss_iou_cost(m.tl[m.r2[r]], m.dtl[m.lo[k]], 2.0);
             }
             byte_assign(nR2, nLo, cost, glb, m, err);
             if (tid < nR2) {
                 const int k = m.asg[tid], slot = m.r2[tid];
-                if (k >= 0 && cost[byte_cidx(tid, k, nR2, nLo)] <= 0.5) { m.upd[slot] = m.lo[k]; m.len[slot] += 1; }
+                if (k >= 0 && cost[lsap_cidx(tid, k, nR2, nLo)] <= 0.5) { m.upd[slot] = m.lo[k]; m.len[slot] += 1; }
                 else m.state[slot] = SS_BYTE_LOST;                       // new lost (r2 index tid)
             }
         }
@@ -508,12 +488,12 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
                 const int r = e / nLeft, k = e - r * nLeft, d = m.left[k];
                 double c = ss_iou_cost(m.tl[m.unc[r]], m.dtl[d], 2.0);
                 if (b.fuse) c = 1.0 - (1.0 - c) * (double)m.dsc[d];
-                cost[byte_cidx(r, k, nU, nLeft)] = c;
+                cost[lsap_cidx(r, k, nU, nLeft)] = c;
             }
             byte_assign(nU, nLeft, cost, glb, m, err);
             if (tid < nU) {
                 const int k = m.asg[tid], slot = m.unc[tid];
-                if (k >= 0 && cost[byte_cidx(tid, k, nU, nLeft)] <= 0.7) { m.upd[slot] = m.left[k]; m.len[slot] += 1; m.lused[k] = 1; }
+                if (k >= 0 && cost[lsap_cidx(tid, k, nU, nLeft)] <= 0.7) { m.upd[slot] = m.left[k]; m.len[slot] += 1; m.lused[k] = 1; }
                 else m.state[slot] = SS_BYTE_REMOVED;
             }
         }
@@ -540,7 +520,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             if (isB && rank < nB) {
                 const int slot = m.freel[rank], d = m.left[tid];
                 double mean[8], cov[64];
-                if (XYWH) ss_kf_initiate_xywh(m.dz[d], b.wp, b.wv, mean, cov); else ss_kf_initiate(m.dz[d], b.wp, b.wv, mean, cov);
+                ss_kf_initiate<XYWH>(m.dz[d], b.wp, b.wv, mean, cov);
                 const size_t g = sb + slot;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) b.mean[g * 8 + i] = mean[i];
@@ -563,7 +543,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
                 for (int i = 0; i < 8; ++i) mean[i] = b.mean[g * 8 + i];
 #pragma unroll
                 for (int i = 0; i < 64; ++i) cov[i] = b.cov[g * 64 + i];
-                if (XYWH) ss_kf_update_xywh(mean, cov, m.dz[d], b.wp); else ss_kf_update(mean, cov, m.dz[d], 0.0, b.wp);
+                ss_kf_update<XYWH>(mean, cov, m.dz[d], 0.0, b.wp);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) b.mean[g * 8 + i] = mean[i];
 #pragma unroll

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/strongsort_hip.h"
+#include "ss_kalman.h"
 
 #define SS_F 512              // feature width (OSNet)
 #define SS_SEG 64             // dot-product segment (one wave of the cosine kernel per segment)
@@ -160,157 +161,113 @@ __device__ inline float ss_wave_sumsq_reduce(float p)
     return p;
 }
 
+// Unit feature of a 512-float row held by a wave, lane l = elements l + 64 j (oracle so_normalize): every lane chains fmaf over its
+// eight elements, the xor butterfly adds the lanes, sqrtf (ss_norm8); then every element is divided — or zero for an all-zero row,
+// D-17 (ss_unit_elem).  ss_unit8 -> out[l + 64 j] (LDS or global); a caller that stores an element more than once uses the two parts.
+__device__ __forceinline__ float ss_norm8(const float v[8])
+{
+    float acc = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc = fmaf(v[j], v[j], acc);
+    return sqrtf(ss_wave_sumsq_reduce(acc));
+}
+__device__ __forceinline__ float ss_unit_elem(float v, float n) { return n > 0.0f ? v / n : 0.0f; }
+__device__ __forceinline__ void ss_unit8(const float v[8], float* out)
+{
+    const int l = threadIdx.x & 63;
+    const float n = ss_norm8(v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[l + 64 * j] = ss_unit_elem(v[j], n);
+}
+
+// oracle so_ema of a smoothed row sv and a unit feature fv in registers (lane l = elements l + 64 j): a * sv + b * fv, then its unit row
+__device__ __forceinline__ void ss_ema_regs(const float sv[8], const float fv[8], float a, float b, float* out)
+{
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float t1 = a * sv[j];
+        const float t2 = b * fv[j];
+        v[j] = t1 + t2;
+    }
+    ss_unit8(v, out);
+}
+
 // ---------------------------------------------------------------------------------------------
-// Kalman filter (float64), mirrors oracle so_kf_* line by line
+// block helpers (256 threads)
 // ---------------------------------------------------------------------------------------------
-__device__ inline void ss_kf_initiate(const double z[4], double wp, double wv, double* mean, double* cov)
+// Flag scans: position of a thread's flag among the set ones, and their number.  block_scan256_3 is three independent scans for the
+// price of one (two barriers; k_frame ran ten scans of two barriers each: 20 of its ~30 barriers); block_scan256 is the same code
+// for one flag, with 4 instead of 12 ints of LDS.
+__device__ inline void block_scan256(int flag, int* wtot /*LDS[4]*/, int& pos, int& total)
 {
+    unsigned long long m = __ballot(flag);
+    int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inwave = __popcll(m & ((1ull << lane) - 1ull));
+    __syncthreads();                       // protect wtot from the previous scan's readers
+    if (lane == 0) wtot[w] = __popcll(m);
+    __syncthreads();
+    int off = 0, tot = 0;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { mean[i] = z[i]; mean[4 + i] = 0.0; }
-    double h = z[3];
-    double sd[8] = { 2.0 * wp * h, 2.0 * wp * h, 1e-2, 2.0 * wp * h,
-                     10.0 * wv * h, 10.0 * wv * h, 1e-5, 10.0 * wv * h };
-    for (int i = 0; i < 64; ++i) cov[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) cov[i * 8 + i] = sd[i] * sd[i];
+    for (int i = 0; i < 4; ++i) { int c = wtot[i]; if (i < w) off += c; tot += c; }
+    pos = off + inwave;
+    total = tot;
 }
 
-__device__ inline void ss_kf_predict(double* mean, double* cov, double wp, double wv)
+__device__ inline void block_scan256_3(int f0, int f1, int f2, int* wtot /*LDS[12]*/, int& p0, int& p1, int& p2, int& t0, int& t1, int& t2)
 {
-    double h = mean[3];
-    double sp = wp * h, sv = wv * h;
-    double sd[8] = { sp, sp, 1e-2, sp, sv, sv, 1e-5, sv };
-    double P[64];
-#pragma unroll
-    for (int i = 0; i < 64; ++i) P[i] = cov[i];
-    // A = P F^T (in place on the left half), B = F A (in place on the top half)
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) P[i * 8 + j] = P[i * 8 + j] + P[i * 8 + j + 4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) P[i * 8 + j] = P[i * 8 + j] + P[(i + 4) * 8 + j];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) P[i * 8 + i] = P[i * 8 + i] + sd[i] * sd[i];
-#pragma unroll
-    for (int i = 0; i < 64; ++i) cov[i] = P[i];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mean[i] = mean[i] + mean[i + 4];
-}
-
-__device__ inline void ss_kf_project(const double* mean, const double* cov, double conf, double wp,
-                                     double m4[4], double S[16])
-{
-    double h = mean[3];
-    double sd[4] = { wp * h, wp * h, 1e-1, wp * h };
+    const unsigned long long m0 = __ballot(f0), m1 = __ballot(f1), m2 = __ballot(f2);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int i0 = __popcll(m0 & below), i1 = __popcll(m1 & below), i2 = __popcll(m2 & below);
+    __syncthreads();                       // protect wtot from the previous scan's readers
+    if (lane == 0) { wtot[w] = __popcll(m0); wtot[4 + w] = __popcll(m1); wtot[8 + w] = __popcll(m2); }
+    __syncthreads();
+    int o0 = 0, o1 = 0, o2 = 0, s0 = 0, s1 = 0, s2 = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        m4[i] = mean[i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) S[i * 4 + j] = cov[i * 8 + j];
+        const int c0 = wtot[i], c1 = wtot[4 + i], c2 = wtot[8 + i];
+        if (i < w) { o0 += c0; o1 += c1; o2 += c2; }
+        s0 += c0; s1 += c1; s2 += c2;
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        double s = (1.0 - conf) * sd[i];
-        S[i * 4 + i] = S[i * 4 + i] + s * s;
-    }
+    p0 = o0 + i0; p1 = o1 + i1; p2 = o2 + i2;
+    t0 = s0; t1 = s1; t2 = s2;
 }
 
-__device__ inline void ss_chol4(const double S[16], double L[16])
+// exclusive prefix sum of small non-negative ints over the 256 threads of a block
+__device__ inline void block_scan_sum256(int v, int* wtot /*LDS[4]*/, int& excl, int& total)
 {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) L[i] = 0.0;
+    for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
+    __syncthreads();
+    if (lane == 63) wtot[w] = inc;
+    __syncthreads();
+    int off = 0, tot = 0;
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            double sum = S[i * 4 + j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) sum = fma(-L[i * 4 + k], L[j * 4 + k], sum);
-            L[i * 4 + j] = (i == j) ? sqrt(sum) : sum / L[j * 4 + j];
-        }
+    for (int i = 0; i < 4; ++i) { int c = wtot[i]; if (i < w) off += c; tot += c; }
+    excl = off + inc - v;
+    total = tot;
 }
 
-// squared Mahalanobis distance given L (lower Cholesky of the projected covariance) and m4
-__device__ inline double ss_maha(const double L[16], const double m4[4], const double z[4])
+// ---------------------------------------------------------------------------------------------
+// Kalman filter (float64): the thread forms, the noise model and the gain row are in ss_kalman.h; here the wave-cooperative
+// forms of the xyah filter (StrongSORT's post_track), lane l = covariance entry (r, c) = (l >> 3, l & 7).  Every lane performs
+// exactly the operations the thread form performs for its entry, so every result bit equals the one-thread form.
+// ---------------------------------------------------------------------------------------------
+// ss_kf_initiate<false>: -> gmean / gcov (global) and ws = 72 doubles of per-wave LDS (covariance, then mean)
+__device__ inline void ss_kf_initiate_wave(const double* z, double wp, double wv, double* gmean, double* gcov, double* ws)
 {
-    double y[4], acc = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        double sum = z[i] - m4[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) sum = fma(-L[i * 4 + k], y[k], sum);
-        y[i] = sum / L[i * 4 + i];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc = fma(y[i], y[i], acc);
-    return acc;
+    const int l = threadIdx.x & 63, r = l >> 3, c = l & 7;
+    const double sd = ss_kf_sd_initiate<false>(r, wp, wv, z);
+    const double c0 = (r == c) ? sd * sd : 0.0;
+    gcov[l] = c0; ws[l] = c0;
+    if (l < 8) { const double m0 = (l < 4) ? z[l] : 0.0; gmean[l] = m0; ws[64 + l] = m0; }
 }
 
-__device__ inline void ss_kf_update(double* mean, double* cov, const double z[4], double conf, double wp)
-{
-    double m4[4], S[16], L[16], K[32], M[32], y[4];
-    ss_kf_project(mean, cov, conf, wp, m4, S);
-    ss_chol4(S, L);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        double w[4], x[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            double sum = cov[r * 8 + i];
-#pragma unroll
-            for (int k = 0; k < i; ++k) sum = fma(-L[i * 4 + k], w[k], sum);
-            w[i] = sum / L[i * 4 + i];
-        }
-#pragma unroll
-        for (int i = 3; i >= 0; --i) {
-            double sum = w[i];
-#pragma unroll
-            for (int k = 3; k > i; --k) sum = fma(-L[k * 4 + i], x[k], sum);
-            x[i] = sum / L[i * 4 + i];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) K[r * 4 + i] = x[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) y[i] = z[i] - m4[i];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc = fma(S[i * 4 + k], K[c * 4 + k], acc);
-            M[i * 8 + c] = acc;
-        }
-    double nm[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc = fma(y[k], K[r * 4 + k], acc);
-        nm[r] = mean[r] + acc;
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc = fma(K[r * 4 + k], M[k * 8 + c], acc);
-            cov[r * 8 + c] = cov[r * 8 + c] - acc;
-        }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) mean[r] = nm[r];
-}
-
-// Wave-cooperative form of ss_kf_update: lane l owns covariance entry (r, c) = (l >> 3, l & 7) and computes exactly
-// the operations the oracle performs for that entry (the gain rows r and c, column c of S K^T), so every result bit
-// equals the one-thread form.  ws = 72 doubles of per-wave LDS (covariance, then mean; the new mean is left in
-// ws[64..71]).  gmean / gcov are updated in place.
-// (imean / icov: the state it starts from — the same arrays, or the predicted copies; the new covariance is ALSO left in ws[0..63])
+// ss_kf_update<false>: the gain rows r and c, column c of S K^T.  The new state goes to gmean / gcov and is left in ws
+// (covariance in ws[0..63], mean in ws[64..71]).  imean / icov: the state it starts from — gmean / gcov, or the predicted copies.
 __device__ inline void ss_kf_update_wave(const double* imean, const double* icov, double* gmean, double* gcov, const double z[4], double conf,
                                          double wp, double* ws)
 {
@@ -322,30 +279,11 @@ __device__ inline void ss_kf_update_wave(const double* imean, const double* icov
     const double* cov = ws;
     const double* mean = ws + 64;
     double m4[4], S[16], L[16];
-    ss_kf_project(mean, cov, conf, wp, m4, S);
+    ss_kf_project<false>(mean, cov, conf, wp, m4, S);
     ss_chol4(S, L);
     double Kr[4], Kc[4];
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        const int row = pass == 0 ? r : c;
-        double w[4], x[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            double sum = cov[row * 8 + i];
-#pragma unroll
-            for (int k = 0; k < i; ++k) sum = fma(-L[i * 4 + k], w[k], sum);
-            w[i] = sum / L[i * 4 + i];
-        }
-#pragma unroll
-        for (int i = 3; i >= 0; --i) {
-            double sum = w[i];
-#pragma unroll
-            for (int k = 3; k > i; --k) sum = fma(-L[k * 4 + i], x[k], sum);
-            x[i] = sum / L[i * 4 + i];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { if (pass == 0) Kr[i] = x[i]; else Kc[i] = x[i]; }
-    }
+    ss_kf_gain_row(L, cov + r * 8, Kr);
+    ss_kf_gain_row(L, cov + c * 8, Kc);
     double Mc[4];                                   // column c of M = S K^T
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -369,16 +307,13 @@ __device__ inline void ss_kf_update_wave(const double* imean, const double* icov
     SS_WAVE_SYNC();
 }
 
-// Kalman prediction of a state held in ws (covariance [64], mean [8]) by the 64 lanes of a wave, lane l = entry (l >> 3, l & 7):
-// exactly the operations ss_kf_predict performs for that entry (A = P F^T on the left half, B = F A on the top half, + Q on the
-// diagonal; h = the mean's height BEFORE the step).  -> pmean[8], pcov[64] (global).
+// ss_kf_predict<false> of the state in ws (A = P F^T on the left half, B = F A on the top half, + Q on the diagonal; the noise from
+// the mean BEFORE the step).  -> pmean[8], pcov[64] (global).
 __device__ inline void ss_kf_predict_wave(const double* ws, double wp, double wv, double* pmean, double* pcov)
 {
     const int l = threadIdx.x & 63, i = l >> 3, j = l & 7;
     const double* P = ws;
     const double* mean = ws + 64;
-    const double h = mean[3];
-    const double sp = wp * h, sv = wv * h;
     double a = P[i * 8 + j];
     if (j < 4) a = a + P[i * 8 + j + 4];
     if (i < 4) {
@@ -387,127 +322,11 @@ __device__ inline void ss_kf_predict_wave(const double* ws, double wp, double wv
         a = a + a4;
     }
     if (i == j) {
-        const double sd = (i == 2) ? 1e-2 : (i == 6) ? 1e-5 : (i < 4) ? sp : sv;
+        const double sd = ss_kf_sd_predict<false>(i, wp, wv, mean);
         a = a + sd * sd;
     }
     pcov[l] = a;
     if (l < 8) pmean[l] = l < 4 ? mean[l] + mean[l + 4] : mean[l];
-}
-
-// BoT-SORT's xywh filter (the `botsort` variant of the BYTE tracker, docs/BYTETRACK.md B-03): the same constant-velocity model
-// with every noise term scaled by the box width (x, w rows) or height (y, h rows) and no NSA.  Same operation order as the xyah
-// forms above; tests/bytetrack_ref.py restates both line by line.
-__device__ inline void ss_kf_initiate_xywh(const double z[4], double wp, double wv, double* mean, double* cov)
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { mean[i] = z[i]; mean[4 + i] = 0.0; }
-    const double w = z[2], h = z[3];
-    const double sd[8] = { 2.0 * wp * w, 2.0 * wp * h, 2.0 * wp * w, 2.0 * wp * h,
-                           10.0 * wv * w, 10.0 * wv * h, 10.0 * wv * w, 10.0 * wv * h };
-    for (int i = 0; i < 64; ++i) cov[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) cov[i * 8 + i] = sd[i] * sd[i];
-}
-
-__device__ inline void ss_kf_predict_xywh(double* mean, double* cov, double wp, double wv)
-{
-    const double w = mean[2], h = mean[3];
-    const double sd[8] = { wp * w, wp * h, wp * w, wp * h, wv * w, wv * h, wv * w, wv * h };
-    double P[64];
-#pragma unroll
-    for (int i = 0; i < 64; ++i) P[i] = cov[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) P[i * 8 + j] = P[i * 8 + j] + P[i * 8 + j + 4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) P[i * 8 + j] = P[i * 8 + j] + P[(i + 4) * 8 + j];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) P[i * 8 + i] = P[i * 8 + i] + sd[i] * sd[i];
-#pragma unroll
-    for (int i = 0; i < 64; ++i) cov[i] = P[i];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mean[i] = mean[i] + mean[i + 4];
-}
-
-__device__ inline void ss_kf_project_xywh(const double* mean, const double* cov, double wp, double m4[4], double S[16])
-{
-    const double w = mean[2], h = mean[3];
-    const double sd[4] = { wp * w, wp * h, wp * w, wp * h };
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        m4[i] = mean[i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) S[i * 4 + j] = cov[i * 8 + j];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) S[i * 4 + i] = S[i * 4 + i] + sd[i] * sd[i];
-}
-
-// the correction half of ss_kf_update (gain by Cholesky solves, mean and covariance) for a projection m4 / S made by the caller
-__device__ inline void ss_kf_correct(double* mean, double* cov, const double z[4], const double m4[4], const double S[16])
-{
-    double L[16], K[32], M[32], y[4];
-    ss_chol4(S, L);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        double w[4], x[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            double sum = cov[r * 8 + i];
-#pragma unroll
-            for (int k = 0; k < i; ++k) sum = fma(-L[i * 4 + k], w[k], sum);
-            w[i] = sum / L[i * 4 + i];
-        }
-#pragma unroll
-        for (int i = 3; i >= 0; --i) {
-            double sum = w[i];
-#pragma unroll
-            for (int k = 3; k > i; --k) sum = fma(-L[k * 4 + i], x[k], sum);
-            x[i] = sum / L[i * 4 + i];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) K[r * 4 + i] = x[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) y[i] = z[i] - m4[i];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc = fma(S[i * 4 + k], K[c * 4 + k], acc);
-            M[i * 8 + c] = acc;
-        }
-    double nm[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc = fma(y[k], K[r * 4 + k], acc);
-        nm[r] = mean[r] + acc;
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc = fma(K[r * 4 + k], M[k * 8 + c], acc);
-            cov[r * 8 + c] = cov[r * 8 + c] - acc;
-        }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) mean[r] = nm[r];
-}
-
-__device__ inline void ss_kf_update_xywh(double* mean, double* cov, const double z[4], double wp)
-{
-    double m4[4], S[16];
-    ss_kf_project_xywh(mean, cov, wp, m4, S);
-    ss_kf_correct(mean, cov, z, m4, S);
 }
 
 // Device state of the BYTE tracker family (csrc/ss_byte.hip), hung off a context by ss_byte_create.  Per stream: two ordered

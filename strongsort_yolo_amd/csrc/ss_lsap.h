@@ -1,22 +1,7 @@
-// ss_lsap.h — device helpers shared by the StrongSORT kernels (ss_track.hip) and the BYTE tracker (ss_byte.hip):
-// the 256-thread flag scan and the one-wave LSAP in SciPy's scan order (moved here unchanged from ss_track.hip).
+// ss_lsap.h — the one-wave LSAP in SciPy's scan order and the assignment wrapper around it (rows = the smaller side), shared by the
+// StrongSORT kernels (ss_track.hip), the BYTE tracker (ss_byte.hip) and the MOT scorer (ss_mot.hip).
 #pragma once
 #include "ss_common.h"
-
-__device__ inline void block_scan256(int flag, int* wtot /*LDS[4]*/, int& pos, int& total)
-{
-    unsigned long long m = __ballot(flag);
-    int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inwave = __popcll(m & ((1ull << lane) - 1ull));
-    __syncthreads();                       // protect wtot from the previous scan's readers
-    if (lane == 0) wtot[w] = __popcll(m);
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { int c = wtot[i]; if (i < w) off += c; tot += c; }
-    pos = off + inwave;
-    total = tot;
-}
 
 // =================================================================================================
 // LSAP on one wave — shortest augmenting path in SciPy's scan order (oracle so_lsap)
@@ -272,10 +257,33 @@ __device__ inline int lsap_wave_regs(int nr, int nc, const double* cost, const L
 }
 
 // cost: [nr][nc] (nr <= nc <= 256) in LDS or global.  Result col4row[0..nr).  Returns 0 / -1.
-__device__ inline int lsap_wave(int nr, int nc, const double* cost, const LsapLds& L)
+#ifndef SS_LSAP_WAVE_INLINE
+#define SS_LSAP_WAVE_INLINE inline                // a file may ask for __noinline__ before it includes this header (ss_track.hip)
+#endif
+__device__ SS_LSAP_WAVE_INLINE int lsap_wave(int nr, int nc, const double* cost, const LsapLds& L)
 {
     if (nc <= 64) return lsap_wave_small(nr, nc, cost, L);
     if (nc <= 128) return lsap_wave_regs<2>(nr, nc, cost, L);
     if (nc <= 256) return lsap_wave_regs<4>(nr, nc, cost, L);
     return -1;                       // callers cap both dimensions at 256 (SS_MAX_TRACKS)
+}
+
+// ---- assignment of an n_rows x n_cols matrix in its natural orientation (rows = tracks) -----------------------------------------
+// SciPy transposes a tall matrix: the LSAP's rows are the smaller side.  Entry (r, c) is stored at lsap_cidx.
+__device__ inline int lsap_cidx(int r, int c, int n_rows, int n_cols)
+{
+    return n_cols < n_rows ? c * n_rows + r : r * n_cols + c;
+}
+
+// One wave: lsap_wave of the matrix stored by lsap_cidx, then asg[row] = its column, back through the transposition (rows without
+// a column keep what asg held: the caller presets -1).  Returns lsap_wave's status; asg is untouched when it is not 0.
+__device__ inline int lsap_wave_assign(int n_rows, int n_cols, const double* cost, const LsapLds& L, int* asg)
+{
+    const int l = threadIdx.x & 63;
+    const bool tr = n_cols < n_rows;
+    const int nr = tr ? n_cols : n_rows, nc = tr ? n_rows : n_cols;
+    const int rc = lsap_wave(nr, nc, cost, L);
+    if (rc) return rc;
+    for (int i = l; i < nr; i += 64) { if (tr) asg[L.col4row[i]] = i; else asg[i] = L.col4row[i]; }
+    return 0;
 }

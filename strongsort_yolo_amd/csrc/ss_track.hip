@@ -15,6 +15,9 @@
 #include <hip/hip_ext.h>
 #include "ss_common.h"
 #include "ss_launch.h"
+// k_frame's two stages call the solver out of line: inlined, its three register forms are in the kernel once per stage (three times
+// the code of a latency-bound kernel: measured 0.5 us slower per frame)
+#define SS_LSAP_WAVE_INLINE __noinline__
 #include "ss_lsap.h"
 
 // Memory operations without a return value as inline assembly: the compiler's wait-count pass does not see them, so they do
@@ -53,44 +56,6 @@ __device__ __forceinline__ void frag_write_row(float4* tile, int i, const float*
     }
     tile[(q * 4 + ks0) * 16 + i] = make_float4(r[ks0], r[4 + ks0], r[8 + ks0], r[12 + ks0]);
     tile[(q * 4 + ks0 + 1) * 16 + i] = make_float4(r[ks0 + 1], r[5 + ks0], r[9 + ks0], r[13 + ks0]);
-}
-
-// three independent flag scans for the price of one (k_frame ran ten scans of two barriers each: 20 of its ~30 barriers)
-__device__ inline void block_scan256_3(int f0, int f1, int f2, int* wtot /*LDS[12]*/, int& p0, int& p1, int& p2, int& t0, int& t1, int& t2)
-{
-    const unsigned long long m0 = __ballot(f0), m1 = __ballot(f1), m2 = __ballot(f2);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const int i0 = __popcll(m0 & below), i1 = __popcll(m1 & below), i2 = __popcll(m2 & below);
-    __syncthreads();                       // protect wtot from the previous scan's readers
-    if (lane == 0) { wtot[w] = __popcll(m0); wtot[4 + w] = __popcll(m1); wtot[8 + w] = __popcll(m2); }
-    __syncthreads();
-    int o0 = 0, o1 = 0, o2 = 0, s0 = 0, s1 = 0, s2 = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c0 = wtot[i], c1 = wtot[4 + i], c2 = wtot[8 + i];
-        if (i < w) { o0 += c0; o1 += c1; o2 += c2; }
-        s0 += c0; s1 += c1; s2 += c2;
-    }
-    p0 = o0 + i0; p1 = o1 + i1; p2 = o2 + i2;
-    t0 = s0; t1 = s1; t2 = s2;
-}
-
-// exclusive prefix sum of small non-negative ints over the 256 threads of a block
-__device__ inline void block_scan_sum256(int v, int* wtot /*LDS[4]*/, int& excl, int& total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
-    __syncthreads();
-    if (lane == 63) wtot[w] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { int c = wtot[i]; if (i < w) off += c; tot += c; }
-    excl = off + inc - v;
-    total = tot;
 }
 
 // =================================================================================================
@@ -225,9 +190,8 @@ __global__ __launch_bounds__(64) void k_lsap_kat(const double* cost, int nr0, in
     LsapLds L = carve_lsap(p);
     const int l = threadIdx.x;
     const bool tr = nc0 < nr0;
-    const int nr = tr ? nc0 : nr0, nc = tr ? nr0 : nc0;
     for (int i = l; i < nr0; i += 64) row_to_col[i] = -1;
-    if (nr == 0) return;
+    if (nr0 == 0 || nc0 == 0) return;
     const double* c = cost;
     if (tr) {
         for (int idx = l; idx < nr0 * nc0; idx += 64) { int i = idx / nc0, j = idx % nc0; scratch_t[j * nr0 + i] = cost[idx]; }
@@ -235,11 +199,7 @@ __global__ __launch_bounds__(64) void k_lsap_kat(const double* cost, int nr0, in
         __syncthreads();
         c = scratch_t;
     }
-    int rc = lsap_wave(nr, nc, c, L);
-    if (rc) { if (l == 0) *err = SS_ERR_INFEASIBLE; return; }
-    for (int i = l; i < nr; i += 64) {
-        if (tr) row_to_col[L.col4row[i]] = i; else row_to_col[i] = L.col4row[i];
-    }
+    if (lsap_wave_assign(nr0, nc0, c, L, row_to_col) && l == 0) *err = SS_ERR_INFEASIBLE;
 }
 
 // =================================================================================================
@@ -248,34 +208,10 @@ __global__ __launch_bounds__(64) void k_lsap_kat(const double* cost, int nr0, in
 __device__ inline void ema_wave(const float* smooth_in, const float* feat, float a, float b, float* out)
 {
     const int l = threadIdx.x & 63;
-    float v[8], acc = 0.0f;
+    float sv[8], fv[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float t1 = a * smooth_in[l + 64 * j];
-        float t2 = b * feat[l + 64 * j];
-        v[j] = t1 + t2;
-        acc = fmaf(v[j], v[j], acc);
-    }
-    float n = sqrtf(ss_wave_sumsq_reduce(acc));
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[l + 64 * j] = n > 0.0f ? v[j] / n : 0.0f;
-}
-
-// the same from registers (lane l holds elements l + 64 j)
-__device__ inline void ema_regs(const float sv[8], const float fv[8], float a, float b, float* out)
-{
-    const int l = threadIdx.x & 63;
-    float v[8], acc = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float t1 = a * sv[j];
-        float t2 = b * fv[j];
-        v[j] = t1 + t2;
-        acc = fmaf(v[j], v[j], acc);
-    }
-    float n = sqrtf(ss_wave_sumsq_reduce(acc));
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[l + 64 * j] = n > 0.0f ? v[j] / n : 0.0f;
+    for (int j = 0; j < 8; ++j) { sv[j] = smooth_in[l + 64 * j]; fv[j] = feat[l + 64 * j]; }
+    ss_ema_regs(sv, fv, a, b, out);
 }
 
 // append row-major unit row `src` (global) as gallery row b of a track (fragment-major tiles)
@@ -463,13 +399,13 @@ __global__ __launch_bounds__(256) void k_group_prep(SSDev dev)
     const int jj = d % SS_TILE;
     if (d < D) {
         const float* raw = dev.feats_raw + (fs * SS_MAXD + d) * SS_F;
-        float v[8], a = 0.0f;
+        float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { v[j] = raw[l + 64 * j]; a = fmaf(v[j], v[j], a); }
-        float n = sqrtf(ss_wave_sumsq_reduce(a));
+        for (int j = 0; j < 8; ++j) v[j] = raw[l + 64 * j];
+        const float n = ss_norm8(v);
         float* unit = dev.feat_unit + (fs * SS_MAXD + d) * SS_F;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { float u = n > 0.0f ? v[j] / n : 0.0f; unit[l + 64 * j] = u; rowbuf[w][l + 64 * j] = u; }   // all-zero row stays zero (D-17)
+        for (int j = 0; j < 8; ++j) { const float u = ss_unit_elem(v[j], n); unit[l + 64 * j] = u; rowbuf[w][l + 64 * j] = u; }
         SS_WAVE_SYNC();
         frag_write_row(frag, jj, rowbuf[w], false);
         if (dev.assoc_pack) {                                           // the same row as column g of the group's packed detections
@@ -892,7 +828,7 @@ __device__ inline FrameLds carve_frame(char* p, const SSDev& dev, int s, int nT,
 size_t ss_frame_lds_bytes(int cap_cost, int cap_t, int cap_d) { return (size_t)cap_cost * 8 + (size_t)cap_t * 18 * 8 + 2 * (size_t)cap_d * 4 * 8 + 15 * 256 * 4 + 64; }
 
 // Assignment of one stage.  n_rows x n_cols is the matrix in its natural orientation (rows = tracks); cost is stored
-// [nr][nc] after the transposition rule (rows = the smaller side).  Result: m.asg[row] = column or -1.
+// by lsap_cidx (rows = the smaller side).  Result: m.asg[row] = column or -1.
 // Shortcut: rcnt / ccnt count the entries <= threshold per natural row / column (filled while the matrix is built,
 // rsel[row] = such a column).  Every other entry equals the replacement value threshold + 1e-5, so if no row and no
 // column holds more than one entry <= threshold, the optimal assignment is unique on those entries (swapping any of
@@ -903,8 +839,6 @@ __device__ inline int frame_assign(int n_rows, int n_cols, bool big, const doubl
                                    const FrameLds& m, int* err)
 {
     const int tid = threadIdx.x;
-    const bool tr = n_cols < n_rows;
-    const int nr = tr ? n_cols : n_rows, nc = tr ? n_rows : n_cols;
     const int multi = __syncthreads_or((tid < n_rows && m.rcnt[tid] > 1) || (tid < n_cols && m.ccnt[tid] > 1));
     if (!multi) {
         if (tid < n_rows) m.asg[tid] = m.rcnt[tid] == 1 ? m.rsel[tid] : -1;
@@ -912,9 +846,8 @@ __device__ inline int frame_assign(int n_rows, int n_cols, bool big, const doubl
         return 1;
     }
     if ((tid >> 6) == 0) {
-        const int rc = big ? lsap_wave(nr, nc, cost_glb, m.L) : lsap_wave(nr, nc, cost_lds, m.L);
-        if (rc) { if (tid == 0) *err = SS_ERR_INFEASIBLE; }
-        else for (int i = tid; i < nr; i += 64) { if (tr) m.asg[m.L.col4row[i]] = i; else m.asg[i] = m.L.col4row[i]; }
+        const int rc = lsap_wave_assign(n_rows, n_cols, big ? cost_glb : cost_lds, m.L, m.asg);
+        if (rc && tid == 0) *err = SS_ERR_INFEASIBLE;
     }
     __syncthreads();
     return 2;
@@ -993,7 +926,7 @@ __global__ __launch_bounds__(256) void k_frame(SSDev dev, SSParams prm, int f)
                 const double* wm = dev.cmc + fs * 8;
                 if (wm[6] >= 1.0) { const double m6[6] = { wm[0], wm[1], wm[2], wm[3], wm[4], wm[5] }; ss_camera_update(mean, m6); }
             }
-            ss_kf_predict(mean, cov, prm.wp, prm.wv);
+            ss_kf_predict<false>(mean, cov, prm.wp, prm.wv);
 #pragma unroll
             for (int i = 0; i < 8; ++i) dev.mean[g * 8 + i] = mean[i];
 #pragma unroll
@@ -1008,7 +941,7 @@ __global__ __launch_bounds__(256) void k_frame(SSDev dev, SSParams prm, int f)
         dev.det_idx[g] = -1;
         // gate factorisation (projection with conf = 0) and predicted box
         double m4[4], Sm[16], L[16];
-        ss_kf_project(mean, cov, 0.0, prm.wp, m4, Sm);
+        ss_kf_project<false>(mean, cov, 0.0, prm.wp, m4, Sm);
         ss_chol4(Sm, L);
         double* ch = m.chol + tid * 14;
         ch[0] = L[0]; ch[1] = L[4]; ch[2] = L[5]; ch[3] = L[8]; ch[4] = L[9]; ch[5] = L[10];
@@ -1038,9 +971,7 @@ __global__ __launch_bounds__(256) void k_frame(SSDev dev, SSParams prm, int f)
     // ---------------- stage A: appearance + motion cost, LSAP --------------------------------
     double* spill = dev.cost_spill + (size_t)s * SS_MAXT * SS_MAXD;
     if (nC > 0 && D > 0) {
-        const bool tr = D < nC;
-        const int nr = tr ? D : nC, nc = tr ? nC : D;
-        const bool big = nr * nc > dev.cap_cost;
+        const bool big = nC * D > dev.cap_cost;
         double* cost = big ? spill : m.cost;
         // the appearance distances of a thread's next four entries are requested together: one exposed round trip to the association
         // kernel's output per 1 024 entries instead of one per 256 (at 30 x 30: 4 -> 1; each was ~0.6 us of this ~2.7 us phase)
@@ -1067,7 +998,7 @@ __global__ __launch_bounds__(256) void k_frame(SSDev dev, SSParams prm, int f)
             const double maha = ss_maha(Lm, m4, z);
             int gt;
             const double v = ss_blend(c, maha, prm, &gt);
-            cost[tr ? d * nc + r : r * nc + d] = v;
+            cost[lsap_cidx(r, d, nC, D)] = v;
             if (!(v > prm.max_dist)) { atomicAdd(&m.rcnt[r], 1); atomicAdd(&m.ccnt[d], 1); m.rsel[r] = d; }
             if (prm.debug) {
                 const size_t o = (dbg + r) * SS_MAXD + d;
@@ -1083,7 +1014,7 @@ __global__ __launch_bounds__(256) void k_frame(SSDev dev, SSParams prm, int f)
         if (tid < nC) {
             int d = m.asg[tid];
             if (d >= 0) {
-                const double v = cost[tr ? d * nc + tid : tid * nc + d];
+                const double v = cost[lsap_cidx(tid, d, nC, D)];
                 if (!(v > prm.max_dist)) { m.matchdet[m.conf_l[tid]] = d; m.dettrk[d] = m.conf_l[tid]; }
                 else d = -1;
             }
@@ -1113,9 +1044,7 @@ __global__ __launch_bounds__(256) void k_frame(SSDev dev, SSParams prm, int f)
     }
     SS_FS(4);
     if (nCand > 0 && nCols > 0) {
-        const bool tr = nCols < nCand;
-        const int nr = tr ? nCols : nCand, nc = tr ? nCand : nCols;
-        const bool big = nr * nc > dev.cap_cost;
+        const bool big = nCand * nCols > dev.cap_cost;
         double* cost = big ? spill : m.cost;
         for (int idx = tid; idx < nCand * nCols; idx += 256) {
             const int r = idx / nCols, c = idx % nCols;
@@ -1124,7 +1053,7 @@ __global__ __launch_bounds__(256) void k_frame(SSDev dev, SSParams prm, int f)
             const double* cb = m.dtl + m.cols[c] * 4;
             double t[4] = { tb[0], tb[1], tb[2], tb[3] }, cc[4] = { cb[0], cb[1], cb[2], cb[3] };
             const double v = (m.tsu_l[ti] > 1) ? prm.max_iou_distance + 1e-5 : ss_iou_cost(t, cc, prm.max_iou_distance);
-            cost[tr ? c * nc + r : r * nc + c] = v;
+            cost[lsap_cidx(r, c, nCand, nCols)] = v;
             if (!(v > prm.max_iou_distance)) { atomicAdd(&m.rcnt[r], 1); atomicAdd(&m.ccnt[c], 1); m.rsel[r] = c; }
             if (prm.debug) dev.dbg_cost_b[(dbg + r) * SS_MAXD + c] = v;
         }
@@ -1135,7 +1064,7 @@ __global__ __launch_bounds__(256) void k_frame(SSDev dev, SSParams prm, int f)
         if (tid < nCand) {
             int c = m.asg[tid];
             if (c >= 0) {
-                const double v = cost[tr ? c * nc + tid : tid * nc + c];
+                const double v = cost[lsap_cidx(tid, c, nCand, nCols)];
                 if (!(v > prm.max_iou_distance)) { m.matchdet[m.cand[tid]] = m.cols[c]; m.dettrk[m.cols[c]] = m.cand[tid]; }
                 else c = -1;
             }
@@ -1252,7 +1181,7 @@ __device__ __forceinline__ void post_track(const SSDev& dev, const SSParams& prm
 #pragma unroll
         for (int j = 0; j < 8; ++j) { sv[j] = sm[l + 64 * j]; fv[j] = fu[l + 64 * j]; }
         ss_kf_update_wave(imean, icov, dev.mean + g * 8, dev.cov + g * 64, z, (double)dev.dets[(fb + d) * 6 + 4], prm.wp, ws);
-        ema_regs(sv, fv, prm.ema_alpha, prm.ema_one_minus_alpha, rowbuf);
+        ss_ema_regs(sv, fv, prm.ema_alpha, prm.ema_one_minus_alpha, rowbuf);
         SS_WAVE_SYNC();
         // the new row goes to the OTHER half: new-row units of this launch (k_postnew) may still be reading the old one
         float* sn = dev.smooth + (g * 2 + (sel ^ 1)) * SS_F;
@@ -1261,14 +1190,7 @@ __device__ __forceinline__ void post_track(const SSDev& dev, const SSParams& prm
         if (l == 0) dev.smooth_sel[g] = sel ^ 1;
         src = rowbuf;
     } else if (fl & SS_P_BIRTH) {
-        const double* zz = dev.xyah + (fb + d) * 4;
-        const double h = zz[3];
-        const int r = l >> 3, c = l & 7;
-        // ss_kf_initiate, one covariance entry per lane
-        const double sd = (r == 2) ? 1e-2 : (r == 6) ? 1e-5 : (r < 4) ? 2.0 * prm.wp * h : 10.0 * prm.wv * h;
-        const double c0 = (r == c) ? sd * sd : 0.0;
-        dev.cov[g * 64 + l] = c0; ws[l] = c0;
-        if (l < 8) { const double m0 = (l < 4) ? zz[l] : 0.0; dev.mean[g * 8 + l] = m0; ws[64 + l] = m0; }
+        ss_kf_initiate_wave(dev.xyah + (fb + d) * 4, prm.wp, prm.wv, dev.mean + g * 8, dev.cov + g * 64, ws);
         const float* fu = dev.feat_unit + (fb + d) * SS_F;
         float* sw = dev.smooth + (g * 2 + sel) * SS_F;
 #pragma unroll
@@ -1315,7 +1237,7 @@ __global__ __launch_bounds__(256) void k_post(SSDev dev, SSParams prm, int f)
 // (cosine_dots), A gathered from the 16 rows' EMA features.  Every (track, detection) entry is kept:
 // M[slot][f2][d] = min(M, 1 - dot), or just 1 - dot for a gallery's first row.
 // OWN_ROWS (k_postnew: the update of the same frame runs beside this unit): the 16 rows are computed HERE, from the row list's
-// (smooth half at frame start, matched detection) — the same ema_regs arithmetic on the same operands as post_track — into LDS;
+// (smooth half at frame start, matched detection) — the same ss_ema_regs arithmetic on the same operands as post_track — into LDS;
 // !OWN_ROWS (k_newrow after k_post): they are read from the half post_track wrote.
 template <bool OWN_ROWS>
 __device__ __forceinline__ void newrow_units(const SSDev& dev, const SSParams& prm, int s, int f, int u0, int ustep, float* lds_part /*[2*8*4*64]*/,
@@ -1350,7 +1272,7 @@ __device__ __forceinline__ void newrow_units(const SSDev& dev, const SSParams& p
                         float fv[8];
 #pragma unroll
                         for (int j = 0; j < 8; ++j) fv[j] = fu[l + 64 * j];
-                        ema_regs(sv, fv, prm.ema_alpha, prm.ema_one_minus_alpha, out);
+                        ss_ema_regs(sv, fv, prm.ema_alpha, prm.ema_one_minus_alpha, out);
                     } else {
 #pragma unroll
                         for (int j = 0; j < 8; ++j) out[l + 64 * j] = sv[j];
@@ -1435,12 +1357,10 @@ __global__ void k_kat_normalize(const float* raw, int n, float* unit)
 {
     const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, l = threadIdx.x & 63;
     if (w >= n) return;
-    float v[8], a = 0.0f;
+    float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { v[j] = raw[(size_t)w * SS_F + l + 64 * j]; a = fmaf(v[j], v[j], a); }
-    float nn = sqrtf(ss_wave_sumsq_reduce(a));
-#pragma unroll
-    for (int j = 0; j < 8; ++j) unit[(size_t)w * SS_F + l + 64 * j] = nn > 0.0f ? v[j] / nn : 0.0f;
+    for (int j = 0; j < 8; ++j) v[j] = raw[(size_t)w * SS_F + l + 64 * j];
+    ss_unit8(v, unit + (size_t)w * SS_F);
 }
 
 __global__ void k_kat_ema(const float* smooth, const float* feat, int n, float a, float b, float* out)
@@ -1458,14 +1378,14 @@ __global__ void k_kat_kf(int op, double* mean, double* cov, const double* z, con
     double m[8], c[64];
     if (op == 2) {
         double zz[4] = { z[i * 4], z[i * 4 + 1], z[i * 4 + 2], z[i * 4 + 3] };
-        ss_kf_initiate(zz, wp, wv, m, c);
+        ss_kf_initiate<false>(zz, wp, wv, m, c);
     } else {
         for (int k = 0; k < 8; ++k) m[k] = mean[(size_t)i * 8 + k];
         for (int k = 0; k < 64; ++k) c[k] = cov[(size_t)i * 64 + k];
-        if (op == 0) ss_kf_predict(m, c, wp, wv);
+        if (op == 0) ss_kf_predict<false>(m, c, wp, wv);
         else {
             double zz[4] = { z[i * 4], z[i * 4 + 1], z[i * 4 + 2], z[i * 4 + 3] };
-            ss_kf_update(m, c, zz, conf[i], wp);
+            ss_kf_update<false>(m, c, zz, conf[i], wp);
         }
     }
     for (int k = 0; k < 8; ++k) mean[(size_t)i * 8 + k] = m[k];
@@ -1480,7 +1400,7 @@ __global__ void k_kat_project(const double* mean, const double* cov, const doubl
     double m[8], c[64], m4[4], s16[16];
     for (int k = 0; k < 8; ++k) m[k] = mean[(size_t)i * 8 + k];
     for (int k = 0; k < 64; ++k) c[k] = cov[(size_t)i * 64 + k];
-    ss_kf_project(m, c, conf ? conf[i] : 0.0, wp, m4, s16);
+    ss_kf_project<false>(m, c, conf ? conf[i] : 0.0, wp, m4, s16);
     for (int k = 0; k < 4; ++k) zmean[(size_t)i * 4 + k] = m4[k];
     for (int k = 0; k < 16; ++k) S[(size_t)i * 16 + k] = s16[k];
 }
@@ -1517,7 +1437,7 @@ __global__ void k_kat_gate(const float* part_min, const int* counts, int T, int 
     double m[8], cv[64], m4[4], S[16], L[16];
     for (int k = 0; k < 8; ++k) m[k] = mean[(size_t)r * 8 + k];
     for (int k = 0; k < 64; ++k) cv[k] = cov[(size_t)r * 64 + k];
-    ss_kf_project(m, cv, 0.0, prm.wp, m4, S);
+    ss_kf_project<false>(m, cv, 0.0, prm.wp, m4, S);
     ss_chol4(S, L);
     double z[4] = { xyah[d * 4], xyah[d * 4 + 1], xyah[d * 4 + 2], xyah[d * 4 + 3] };
     double mh = ss_maha(L, m4, z);

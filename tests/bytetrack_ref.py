@@ -6,8 +6,8 @@ Not a conftest and not a test module: imported by tests/test_bytetrack_cpu.py an
     ref = ByteTrackRef(ByteTrackConfig(kalman="xyah"))
     rows = ref.update(dets)      # dets [N,6] float32 x1,y1,x2,y2,score,cls -> float32 [M,8] x1,y1,x2,y2,id,cls,score,det_idx
 
-The Kalman arithmetic mirrors ss_kf_initiate / ss_kf_predict / ss_kf_update (csrc/ss_common.h, conf = 0) for "xyah" and their
-xywh twins for "xywh" line by line; every fused multiply-add of the device is an exactly rounded fma here (`_fma`).
+The Kalman arithmetic mirrors ss_kf_initiate / ss_kf_predict / ss_kf_update (csrc/ss_kalman.h) with conf = 0 for "xyah" and with
+the xywh noise model for "xywh" line by line; every fused multiply-add of the device is an exactly rounded fma here (`_fma`).
 """
 from __future__ import annotations
 
