@@ -133,3 +133,57 @@ def test_lsap_identical_to_oracle_and_scipy(eng, seed):
     assert np.array_equal(r2c, ref)
     sr, sc = linear_sum_assignment(cost)
     assert np.array_equal(rows, sr) and np.array_equal(cols, sc)
+
+
+LSAP_KINDS = ("uniform", "integers", "constant", "tracker", "tracker_dup", "signed_zeros", "magnitudes")
+
+
+def lsap_cost(kind, nr, nc, rng):
+    """One cost matrix of the kinds that decide SciPy's pairs by its tie order rather than by the values."""
+    if kind == "uniform":
+        return rng.random((nr, nc))
+    if kind == "integers":
+        return rng.integers(0, 4, (nr, nc)).astype(np.float64)
+    if kind == "constant":
+        return np.full((nr, nc), 0.75)
+    if kind in ("tracker", "tracker_dup"):                              # the BYTE family's shape: 1.0 where boxes do not overlap
+        cost = np.ones((nr, nc))
+        for r in range(nr):
+            k = min(nc, int(rng.integers(2, 5)))
+            cost[r, rng.choice(nc, k, replace=False)] = rng.uniform(0.05, 0.95, k)
+        if kind == "tracker_dup" and nc > 1:                            # a tenth of the columns copies another one: exact ties
+            dst = rng.choice(nc, max(1, nc // 10), replace=False)
+            cost[:, dst] = cost[:, (dst + 1 + rng.integers(0, nc - 1, len(dst))) % nc]
+        return cost
+    if kind == "signed_zeros":                                          # -0.0 and +0.0 compare equal: ss_f64_key folds them
+        cost = rng.integers(-2, 3, (nr, nc)).astype(np.float64)
+        cost[cost == 0] = np.where(rng.random(int((cost == 0).sum())) < 0.5, -0.0, 0.0)
+        cost.reshape(-1)[:2] = (-0.0, 0.0)
+        return cost
+    if kind == "magnitudes":
+        return np.where(rng.random((nr, nc)) < 0.5, 1e300, 1e-300) * rng.uniform(0.5, 1.5, (nr, nc))
+    raise ValueError(kind)
+
+
+def lsap_shapes(big):
+    """larger side `big`, smaller side 1, 2, big - 1, big, both orientations."""
+    return sorted({s for small in (1, 2, big - 1, big) for s in ((small, big), (big, small))})
+
+
+@pytest.mark.parametrize("big", [63, 64, 65, 127, 128, 129, 255, 256])
+def test_lsap_at_the_edges_of_the_solver_forms(eng, big):
+    """The sizes next to 64, 128 and 256 columns, where lsap_wave changes its form (one column per lane, two, four), wide and tall
+    (transposed through lsap_cidx / lsap_wave_assign), every cost kind on every size: the pairs are SciPy's and the oracle's."""
+    from scipy.optimize import linear_sum_assignment
+    for nr, nc in lsap_shapes(big):
+        for ki, kind in enumerate(LSAP_KINDS):
+            cost = lsap_cost(kind, nr, nc, np.random.default_rng([big, nr, nc, ki]))
+            if kind == "signed_zeros":
+                assert np.signbit(cost[cost == 0]).any() and not np.signbit(cost[cost == 0]).all()
+            r2c = eng.lsap(cost).cpu().numpy()
+            sr, sc = linear_sum_assignment(cost)
+            ref = np.full(nr, -1, np.int32)
+            ref[sr] = sc
+            assert np.array_equal(r2c, ref), f"{kind} {nr} x {nc}: device != SciPy at rows {np.nonzero(r2c != ref)[0][:8]}"
+            rows, cols = cexact.lsap(cost)
+            assert np.array_equal(rows, sr) and np.array_equal(cols, sc), f"{kind} {nr} x {nc}: oracle != SciPy"
