@@ -712,6 +712,21 @@ int ss_mot_eval(ss_ctx* ctx, int n_pairs, const int* frame_off, const int* gt_of
                 int* hota_match, double* hota_s, int* clear_match, double* clear_s, double* ga);
 /* Host only: the most boxes one side of a frame may hold (256: the one-wave assignment solver's columns). */
 int ss_mot_max_boxes(void);
+/* The identity metrics of the same pairs (docs/MOTEVAL.md section 1, "Identity"): the arguments up to thr are ss_mot_eval's and are
+ * checked by the same body, before the context or the device is touched, except that a pair may have at most ss_mot_max_ids()
+ * ground-truth ids and as many tracker ids (more: SS_ERR_CAPACITY naming the pair) and that the box x box cap does not apply (no
+ * similarity is stored).  pot[g][t] counts the frames in which both ids have a box with S >= thr - 2^-52; idtp[p] is the weight of
+ * a maximum-weight one-to-one matching of pair p's ground-truth ids to its tracker ids under pot, gt_to_tr (one entry per
+ * ground-truth id, pair after pair) one such matching: the dense tracker id, or -1 where the id is unmatched or its pair has
+ * pot = 0.  The weight is unique; of several matchings that reach it the call returns the same one every time.  pot, unless
+ * NULL, receives the counts, per pair [n_gt_ids][n_tr_ids], pair after pair.  One upload, two launches (the counts, one workgroup
+ * per frame; the matching, one workgroup per pair) and one download; pot is zeroed by every call, the scratch is the context's and
+ * is reused, and the call waits on an event of its own.  Not capturable. */
+int ss_mot_identity(ss_ctx* ctx, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_ids, const int* tr_ids,
+                    const double* gt_boxes, const double* tr_boxes, const int* n_gt_ids, const int* n_tr_ids, double thr,
+                    int* idtp, int* gt_to_tr, int* pot);
+/* Host only: the most ids one side of a pair may have in ss_mot_identity (4096: the workgroup-wide assignment solver's columns). */
+int ss_mot_max_ids(void);
 
 /* ---- profiling support ----------------------------------------------------------------------- */
 /* Mean duration (ms) of the association (cosine gallery) kernel over the launches since the last

@@ -415,11 +415,12 @@ def process_video(args: dict, model=None) -> dict:
         eng = (overlay or model.overlay()).eng
         outdir = args.get("outdir", "output")
         names = ["labels"] + (["labels_gsi"] if gsi_on else [])
+        with_identity = bool(args.get("eval_identity"))            # IDF1, IDP, IDR: a second device call for the same pairs
         scored = moteval.evaluate(moteval.read_labels(args["eval_gt"]), [moteval.read_labels(os.path.join(outdir, f"{name}_{k}.txt")) for k in names],
-                                  eng, thr=float(args.get("eval_thr", 0.5)))
+                                  eng, thr=float(args.get("eval_thr", 0.5)), **({"identity": True} if with_identity else {}))
         moteval.write_metrics(os.path.join(outdir, f"{name}_metrics.json"), dict(zip(names, scored)) if gsi_on else scored[0])
         for k, m in zip(names, scored):
-            for fig in ("HOTA", "MOTA", "IDSW"):
+            for fig in ("HOTA", "MOTA", "IDSW") + (("IDF1",) if with_identity else ()):
                 summary[fig + k[len("labels"):]] = m[fig]
     return summary
 
@@ -488,7 +489,11 @@ def main(argv=None):
                         "<name>_labels.txt (with --gsi also <name>_labels_gsi.txt) is scored against it on the device, HOTA and CLEAR MOT "
                         "(docs/MOTEVAL.md), into <name>_metrics.json")
     p.add_argument("--eval-thr", type=float, default=0.5, help="--eval-gt: CLEAR MOT's similarity threshold, in (0, 1]")
+    p.add_argument("--eval-identity", action="store_true",
+                   help="--eval-gt only: also the identity metrics IDTP, IDFN, IDFP, IDF1, IDP, IDR at --eval-thr, into the same <name>_metrics.json")
     a = p.parse_args(argv)
+    if a.eval_identity and not a.eval_gt:
+        p.error("--eval-identity adds to what --eval-gt scores: it needs --eval-gt")
     if a.eval_gt and not a.track:
         p.error("--eval-gt scores tracked rows: it needs --track")
     if a.eval_gt and len(a.eval_gt) != len(a.source):
@@ -540,7 +545,7 @@ def main(argv=None):
             p.error("--save-quality must be 1 .. 100")
     jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "device_decode": a.device_decode, "device_entropy": a.device_entropy,
              "device_encode": a.device_encode, "device_encode_entropy": a.device_encode_entropy, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
-             "gsi": a.gsi, "gsi_interval": a.gsi_interval, "gsi_tau": a.gsi_tau, "eval_gt": a.eval_gt[i] if a.eval_gt else None, "eval_thr": a.eval_thr,
+             "gsi": a.gsi, "gsi_interval": a.gsi_interval, "gsi_tau": a.gsi_tau, "eval_gt": a.eval_gt[i] if a.eval_gt else None, "eval_thr": a.eval_thr, "eval_identity": a.eval_identity,
              "save": _save_path(a, i)}
             for i, s in enumerate(a.source)]
     import torch

@@ -75,7 +75,7 @@ struct ss_ctx {
     SSJpeg* jpeg = nullptr;     // ss_jpeg_decode_batch's staging areas and planes, made by its first call
     SSJpegEnc* jpeg_enc = nullptr;   // ss_jpeg_encode_batch's buffers, made by its first call
     SSGsi* gsi = nullptr;       // ss_gsi_smooth's staging and scratch slots, made by its first call
-    SSMot* mot = nullptr;       // ss_mot_eval's staging, scratch and second stream, made by its first call
+    SSMot* mot = nullptr;       // ss_mot_eval's and ss_mot_identity's staging, scratch and second stream, made by its first call
 };
 
 static int fail(ss_ctx* c, int code, const std::string& msg)
@@ -491,6 +491,21 @@ extern "C" int ss_mot_eval(ss_ctx* c, int n_pairs, const int* frame_off, const i
     if (rc != SS_OK) return fail(c, rc, err);
     rc = ss_mot_eval_impl(c ? &c->mot : nullptr, c ? c->stream : nullptr, n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes,
                           n_gt_ids, n_tr_ids, thr, hota_match, hota_s, clear_match, clear_s, ga, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+// ---- the identity metrics IDF1, IDP, IDR (ss_mot.hip, docs/MOTEVAL.md) ----------------------------------------------------------
+extern "C" int ss_mot_max_ids(void) { return ss_mot_max_ids_impl(); }
+
+extern "C" int ss_mot_identity(ss_ctx* c, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_ids, const int* tr_ids,
+                               const double* gt_boxes, const double* tr_boxes, const int* n_gt_ids, const int* n_tr_ids, double thr,
+                               int* idtp, int* gt_to_tr, int* pot)
+{
+    std::string err;
+    int rc = ss_mot_identity_check_impl(n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids, thr, idtp, gt_to_tr, err);
+    if (rc != SS_OK) return fail(c, rc, err);                                                            // the arguments first: no context needed
+    rc = ss_mot_identity_impl(c ? &c->mot : nullptr, c ? c->stream : nullptr, n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes,
+                              n_gt_ids, n_tr_ids, thr, idtp, gt_to_tr, pot, err);
     return rc == SS_OK ? rc : fail(c, rc, err);
 }
 

@@ -111,4 +111,11 @@ int  ss_mot_check_impl(int n_pairs, const int* frame_off, const int* gt_off, con
 int  ss_mot_eval_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id,
                       const int* tr_id, const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
                       int* hota_idx, double* hota_s, int* clear_idx, double* clear_s, double* ga, std::string& err);
+int  ss_mot_max_ids_impl();
+int  ss_mot_identity_check_impl(int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id, const int* tr_id,
+                                const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
+                                const int* idtp, const int* gt_to_tr, std::string& err);
+int  ss_mot_identity_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id,
+                          const int* tr_id, const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
+                          int* idtp, int* gt_to_tr, int* pot, std::string& err);
 void ss_mot_free(SSMot* m);

@@ -9,6 +9,9 @@
 //   k_mot_clear  one wave per pair, persistent over the pair's frames: needs only S, so it runs on the context's second stream
 //                beside k_mot_align and k_mot_hota.  prev_t lives in device memory as {tracker id, number of the processed frame
 //                that set it}: "reset everywhere" is the frame number moving on.
+//   k_id_count   one workgroup per frame: the identity metrics' counts, pot[g][t] += 1 where S >= thr - eps (integer atomics).
+//   k_id_solve   one workgroup of 1024 threads per pair: the maximum-weight matching of ground-truth ids to tracker ids under
+//                those counts, shortest augmenting paths with the columns spread over the workgroup, integer arithmetic.
 // A matrix is solved with the smaller side as rows (SciPy transposes a tall matrix): lsap_wave wants nr <= nc.
 #include <cmath>
 #include <cstring>
@@ -25,6 +28,9 @@
 #define MOT_MAX_SIM_CELLS (1ll << 27)       // ground-truth boxes x tracker boxes summed over the frames of a call: 1 GB each of S and si
 #define MOT_LDS_CELLS 20000                 // cost entries a wave keeps in LDS: 160 000 of the 163 840 bytes a workgroup may declare
 #define MOT_EPS 0x1p-52
+#define MOT_MAX_IDS 4096                    // ids of one side of a pair in ss_mot_identity: k_id_solve's columns
+#define MOT_ID_THREADS 1024                 // k_id_solve's workgroup; thread t owns columns t, t + 1024, ...
+#define MOT_ID_Q 4                          // MOT_MAX_IDS / MOT_ID_THREADS columns a thread
 
 struct MotArgs {
     // upload image
@@ -56,7 +62,22 @@ struct MotArgs {
     int lds_cells;                          // cost entries of the launch's dynamic LDS
     int n_gids;
     double thr;
+    // the identity metrics (ss_mot_identity): pot_off, gbase and the upload image's boxes, offsets and ids as above
+    const int* n_gid;                       // [pairs]
+    unsigned* id_pot;                       // per pair [rows][columns], the side with fewer ids as rows (ground truth when equal)
+    int* id_match;                          // [all ground-truth ids] dense tracker id or -1
+    int* id_tp;                             // [pairs]
 };
+
+// S of docs/MOTEVAL.md section 1 by its four written steps
+__device__ __forceinline__ double mot_sim(const double* __restrict__ A, const double* __restrict__ B)
+{
+    const double ax1 = A[0], ay1 = A[1], ax2 = A[2], ay2 = A[3], bx1 = B[0], by1 = B[1], bx2 = B[2], by2 = B[3];
+    const double w = fmax(0.0, fmin(ax2, bx2) - fmax(ax1, bx1)), h = fmax(0.0, fmin(ay2, by2) - fmax(ay1, by1));
+    const double inter = w * h;
+    const double uni = ((ax2 - ax1) * (ay2 - ay1) + (bx2 - bx1) * (by2 - by1)) - inter;
+    return inter / uni;
+}
 
 __global__ __launch_bounds__(256) void k_mot_sim(const MotArgs a)
 {
@@ -69,13 +90,7 @@ __global__ __launch_bounds__(256) void k_mot_sim(const MotArgs a)
     const int cells = ng * nt;
     for (int e = tid; e < cells; e += 256) {
         const int i = e / nt, j = e - i * nt;
-        const double* A = a.gt_box + (size_t)(g0 + i) * 4;
-        const double* B = a.tr_box + (size_t)(t0 + j) * 4;
-        const double ax1 = A[0], ay1 = A[1], ax2 = A[2], ay2 = A[3], bx1 = B[0], by1 = B[1], bx2 = B[2], by2 = B[3];
-        const double w = fmax(0.0, fmin(ax2, bx2) - fmax(ax1, bx1)), h = fmax(0.0, fmin(ay2, by2) - fmax(ay1, by1));
-        const double inter = w * h;
-        const double uni = ((ax2 - ax1) * (ay2 - ay1) + (bx2 - bx1) * (by2 - by1)) - inter;
-        S[e] = inter / uni;
+        S[e] = mot_sim(a.gt_box + (size_t)(g0 + i) * 4, a.tr_box + (size_t)(t0 + j) * 4);
     }
     __syncthreads();
     if (tid < ng) {
@@ -229,6 +244,151 @@ __global__ __launch_bounds__(64) void k_mot_clear(const MotArgs a)
     }
 }
 
+// ---- the identity metrics: IDTP is the weight of a maximum-weight matching of ground-truth ids to tracker ids -----------------
+// One workgroup per frame.  A cell of pot gets at most one addend per frame (ids are unique within a frame) and integer addition
+// does not depend on the order, so the counts are deterministic.  S is not stored.
+__global__ __launch_bounds__(256) void k_id_count(const MotArgs a)
+{
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const int g0 = a.gt_off[f], ng = a.gt_off[f + 1] - g0, t0 = a.tr_off[f], nt = a.tr_off[f + 1] - t0;
+    if (ng <= 0 || nt <= 0) return;
+    const int p = a.pair_of[f], nG = a.n_gid[p], nT = a.n_tid[p];
+    const bool tall = nT < nG;              // fewer tracker ids: they are the solver's rows
+    unsigned* pot = a.id_pot + a.pot_off[p];
+    const double lim = a.thr - MOT_EPS;
+    const int cells = ng * nt;
+    for (int e = tid; e < cells; e += 256) {
+        const int i = e / nt, j = e - i * nt;
+        const double s = mot_sim(a.gt_box + (size_t)(g0 + i) * 4, a.tr_box + (size_t)(t0 + j) * 4);
+        if (s >= lim) {
+            const int g = a.gt_id[g0 + i], t = a.tr_id[t0 + j];
+            atomicAdd(pot + (tall ? (size_t)t * nG + g : (size_t)g * nT + t), 1u);
+        }
+    }
+}
+
+// One workgroup per pair: shortest augmenting paths on the cost -pot (the algorithm of so_lsap / lsap_wave) with nr <= nc <= 4096,
+// thread t owning columns t, t + 1024, ...  Per column the path cost and the dual v sit in registers, the predecessor and row4col
+// in LDS (the augmentation walks them), the rows' dual u and col4row in LDS.  One scan step is a coalesced read of the current
+// row's counts, the relaxations, a wave minimum (the DPP reduction of ss_lsap.h) and a 16-slot minimum through LDS, with one
+// barrier: the slots alternate between two sets, so a wave that writes the next step's slot cannot overtake a reader of this one.
+// The minimum is taken of the key {path cost, column assigned?, column}: among equal path costs an unassigned column wins (the
+// path ends there), then the lowest column.  That is the fixed tie rule; it is not SciPy's, and the optimum value does not depend
+// on it.  A row without a positive count is skipped: it can add nothing to the weight.
+// Integer width.  A count is at most 65 536 = 2^16 (the frames a pair may have) and an alternating path has at most 4096 forward
+// and 4095 matched edges, so every path length is below 8191 * 2^16 < 2^29 in magnitude.  The duals v and the scan's minVal are such
+// path lengths, u = cost - v of a matched cell is below 2^29 + 2^16, a reduced cost cost - u - v is below 2^30 + 2^17, and
+// a path cost minVal + reduced cost is below 2^29 + 2^30 + 2^17 < 2^31: int holds all of them.  A row's u starts at -2^16, at
+// most every cost, so reduced costs and with them path costs are never negative, and the key
+// {path cost << 13 | assigned << 12 | column} is below 2^44 and orders as the triple does.
+__global__ __launch_bounds__(MOT_ID_THREADS) void k_id_solve(const MotArgs a)
+{
+    __shared__ int u[MOT_MAX_IDS], col4row[MOT_MAX_IDS], row4col[MOT_MAX_IDS], pred[MOT_MAX_IDS];
+    __shared__ unsigned long long slot[2][MOT_ID_THREADS / 64];
+    __shared__ unsigned weight;
+    const int p = blockIdx.x, t = threadIdx.x, wave = t >> 6;
+    const int nG = a.n_gid[p], nT = a.n_tid[p];
+    const bool tall = nT < nG;
+    const int nr = tall ? nT : nG, nc = tall ? nG : nT;
+    int* match = a.id_match + a.gbase[p];
+    for (int g = t; g < nG; g += MOT_ID_THREADS) match[g] = -1;
+    if (nr <= 0) {
+        if (t == 0) a.id_tp[p] = 0;
+        return;
+    }
+    const unsigned* __restrict__ pot = a.id_pot + a.pot_off[p];
+    for (int k = t; k < nc; k += MOT_ID_THREADS) row4col[k] = -1;
+    for (int k = t; k < nr; k += MOT_ID_THREADS) { u[k] = -MOT_MAX_FRAMES; col4row[k] = -1; }      // cost - u - v >= 0 from the start
+    if (t == 0) weight = 0u;
+    int v[MOT_ID_Q], r4c[MOT_ID_Q];
+#pragma unroll
+    for (int q = 0; q < MOT_ID_Q; ++q) { v[q] = 0; r4c[q] = -1; }
+    unsigned mine = 0u;                     // bit q: column t + 1024 q exists
+#pragma unroll
+    for (int q = 0; q < MOT_ID_Q; ++q) if (t + MOT_ID_THREADS * q < nc) mine |= 1u << q;
+    int par = 0;
+    __syncthreads();
+    for (int cur = 0; cur < nr; ++cur) {
+        {
+            const unsigned* __restrict__ row = pot + (size_t)cur * nc;
+            int any = 0;
+#pragma unroll
+            for (int q = 0; q < MOT_ID_Q; ++q) if (mine >> q & 1u) any |= row[t + MOT_ID_THREADS * q] != 0u;
+            if (!__syncthreads_or(any)) continue;
+        }
+        int sp[MOT_ID_Q];
+#pragma unroll
+        for (int q = 0; q < MOT_ID_Q; ++q) sp[q] = 0x7fffffff;
+        unsigned active = mine, scanned = 0u;
+        int minVal = 0, i = cur, sink = -1;
+        for (;;) {
+            const unsigned* __restrict__ row = pot + (size_t)i * nc;
+            unsigned c[MOT_ID_Q];
+#pragma unroll
+            for (int q = 0; q < MOT_ID_Q; ++q) c[q] = (active >> q & 1u) ? row[t + MOT_ID_THREADS * q] : 0u;
+            const int base = minVal - u[i];
+            unsigned long long key = ~0ull;
+#pragma unroll
+            for (int q = 0; q < MOT_ID_Q; ++q)
+                if (active >> q & 1u) {
+                    const int j = t + MOT_ID_THREADS * q;
+                    const int r = base - (int)c[q] - v[q];
+                    if (r < sp[q]) { sp[q] = r; pred[j] = i; }
+                    const unsigned long long k = ((unsigned long long)(unsigned)sp[q] << 13) | (r4c[q] >= 0 ? 4096ull : 0ull) | (unsigned)j;
+                    key = k < key ? k : key;
+                }
+            key = wave_min_u64(key);
+            if ((t & 63) == 0) slot[par][wave] = key;
+            __syncthreads();
+            unsigned long long m = slot[par][0];
+#pragma unroll
+            for (int w = 1; w < MOT_ID_THREADS / 64; ++w) { const unsigned long long o = slot[par][w]; m = o < m ? o : m; }
+            par ^= 1;
+            const int w = (int)(m & 4095ull);
+            minVal = (int)(m >> 13);
+            if ((w & (MOT_ID_THREADS - 1)) == t) { active &= ~(1u << (w >> 10)); scanned |= 1u << (w >> 10); }
+            if (!(m & 4096ull)) { sink = w; break; }
+            i = row4col[w];
+        }
+        // the duals: v[j] -= minVal - sp[j] for the scanned columns, u[r] += minVal - sp[col4row[r]] for the rows reached through
+        // them (every visited row but `cur`, each from its own column), u[cur] += minVal
+#pragma unroll
+        for (int q = 0; q < MOT_ID_Q; ++q)
+            if (scanned >> q & 1u) {
+                const int d = minVal - sp[q];
+                v[q] -= d;
+                if (r4c[q] >= 0) u[r4c[q]] += d;
+            }
+        if (t == 0) u[cur] += minVal;
+        __syncthreads();
+        if (t == 0) {                       // augment along the predecessors
+            int j = sink;
+            for (;;) {
+                const int r = pred[j];
+                row4col[j] = r;
+                const int next = col4row[r];
+                col4row[r] = j;
+                j = next;
+                if (r == cur) break;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < MOT_ID_Q; ++q) if (mine >> q & 1u) r4c[q] = row4col[t + MOT_ID_THREADS * q];
+    }
+    // a solved pair of count 0 is no match: the id stays -1
+    for (int r = t; r < nr; r += MOT_ID_THREADS) {
+        const int j = col4row[r];
+        if (j < 0) continue;
+        const unsigned w = pot[(size_t)r * nc + j];
+        if (w == 0u) continue;
+        atomicAdd(&weight, w);
+        if (tall) match[j] = r; else match[r] = j;
+    }
+    __syncthreads();
+    if (t == 0) a.id_tp[p] = (int)weight;
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------
 struct SSMot {
     void* host = nullptr; size_t host_cap = 0;          // pinned: the upload image, then the download image
@@ -255,15 +415,16 @@ void ss_mot_free(SSMot* m)
 }
 
 int ss_mot_max_boxes_impl() { return MOT_MAX_BOXES; }
+int ss_mot_max_ids_impl() { return MOT_MAX_IDS; }
 
-// Every refusal of ss_mot_eval that needs neither a context nor the device: SS_ERR_INVALID for arguments that make no sense,
-// SS_ERR_CAPACITY for a call that is too large.
-int ss_mot_check_impl(int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id, const int* tr_id,
-                      const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
-                      const int* hota_idx, const double* hota_s, const int* clear_idx, const double* clear_s, std::string& err)
+// Every refusal of ss_mot_eval and ss_mot_identity that needs neither a context nor the device: SS_ERR_INVALID for arguments
+// that make no sense, SS_ERR_CAPACITY for a call that is too large.  `identity`: at most MOT_MAX_IDS ids a side of a pair, and no
+// cap on the box x box cells (S is not stored).  any_null: one of the call's own output pointers is NULL.
+static int mot_check(const std::string& who, bool identity, bool any_null, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off,
+                     const int* gt_id, const int* tr_id, const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids,
+                     double thr, std::string& err)
 {
-    const std::string who = "ss_mot_eval: ";
-    if (!frame_off || !gt_off || !tr_off || !gt_id || !tr_id || !gt_box || !tr_box || !n_gt_ids || !n_tr_ids || !hota_idx || !hota_s || !clear_idx || !clear_s) {
+    if (!frame_off || !gt_off || !tr_off || !gt_id || !tr_id || !gt_box || !tr_box || !n_gt_ids || !n_tr_ids || any_null) {
         err = who + "null argument"; return SS_ERR_INVALID;
     }
     if (n_pairs < 1) { err = who + "n_pairs must be at least 1"; return SS_ERR_INVALID; }
@@ -276,6 +437,11 @@ int ss_mot_check_impl(int n_pairs, const int* frame_off, const int* gt_off, cons
         if (n_gt_ids[p] < 0 || n_tr_ids[p] < 0) { err = who + pr + "an id count is negative"; return SS_ERR_INVALID; }
         if (frame_off[p + 1] - frame_off[p] > MOT_MAX_FRAMES) {
             err = who + pr + std::to_string(frame_off[p + 1] - frame_off[p]) + " frames: at most " + std::to_string(MOT_MAX_FRAMES) + " a pair"; return SS_ERR_CAPACITY;
+        }
+        if (identity && (n_gt_ids[p] > MOT_MAX_IDS || n_tr_ids[p] > MOT_MAX_IDS)) {
+            const bool g = n_gt_ids[p] > MOT_MAX_IDS;
+            err = who + pr + std::to_string(g ? n_gt_ids[p] : n_tr_ids[p]) + (g ? " ground-truth" : " tracker") + " ids: at most " + std::to_string(MOT_MAX_IDS) + " a side";
+            return SS_ERR_CAPACITY;
         }
     }
     for (int p = 0; p < n_pairs; ++p) {               // (every frame offset is sound by now)
@@ -321,16 +487,33 @@ int ss_mot_check_impl(int n_pairs, const int* frame_off, const int* gt_off, cons
         }
     }
     if (id_cells > MOT_MAX_ID_CELLS) { err = who + std::to_string(id_cells) + " ground-truth id x tracker id cells: at most " + std::to_string(MOT_MAX_ID_CELLS) + " a call"; return SS_ERR_CAPACITY; }
-    if (sim_cells > MOT_MAX_SIM_CELLS) { err = who + std::to_string(sim_cells) + " box x box cells: at most " + std::to_string(MOT_MAX_SIM_CELLS) + " a call"; return SS_ERR_CAPACITY; }
+    if (!identity && sim_cells > MOT_MAX_SIM_CELLS) { err = who + std::to_string(sim_cells) + " box x box cells: at most " + std::to_string(MOT_MAX_SIM_CELLS) + " a call"; return SS_ERR_CAPACITY; }
     return SS_OK;
+}
+
+int ss_mot_check_impl(int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id, const int* tr_id,
+                      const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
+                      const int* hota_idx, const double* hota_s, const int* clear_idx, const double* clear_s, std::string& err)
+{
+    return mot_check("ss_mot_eval: ", false, !hota_idx || !hota_s || !clear_idx || !clear_s, n_pairs, frame_off, gt_off, tr_off, gt_id, tr_id, gt_box,
+                     tr_box, n_gt_ids, n_tr_ids, thr, err);
+}
+
+int ss_mot_identity_check_impl(int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id, const int* tr_id,
+                               const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
+                               const int* idtp, const int* gt_to_tr, std::string& err)
+{
+    return mot_check("ss_mot_identity: ", true, !idtp || !gt_to_tr, n_pairs, frame_off, gt_off, tr_off, gt_id, tr_id, gt_box, tr_box, n_gt_ids,
+                     n_tr_ids, thr, err);
 }
 
 #define MCHK(x)                                                                                     \
     do {                                                                                            \
         hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) { err = std::string("ss_mot_eval: " #x ": ") + hipGetErrorString(e_); return SS_ERR_HIP; } \
+        if (e_ != hipSuccess) { err = std::string(MOT_WHO #x ": ") + hipGetErrorString(e_); return SS_ERR_HIP; } \
     } while (0)
 
+#define MOT_WHO "ss_mot_eval: "
 static size_t mot_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 int ss_mot_eval_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id,
@@ -493,5 +676,110 @@ int ss_mot_eval_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int* fra
     memcpy(hota_idx, hd + o_hi, Ng * sizeof(int));
     memcpy(clear_idx, hd + o_ci, Ng * sizeof(int));
     if (ga) memcpy(ga, hd + o_pot, id_cells * sizeof(double));
+    return SS_OK;
+}
+
+#undef MOT_WHO
+#define MOT_WHO "ss_mot_identity: "
+
+// The identity metrics' counts and matching.  The staging areas are the context's, shared with ss_mot_eval (a call owns them until
+// its event has passed): upload image | pot | download image (gt_to_tr, idtp), pot downloaded with it when the caller wants it.
+int ss_mot_identity_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id,
+                         const int* tr_id, const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
+                         int* idtp, int* gt_to_tr, int* pot, std::string& err)
+{
+    if (!pm) { err = MOT_WHO "null context"; return SS_ERR_INVALID; }
+    const int F = frame_off[n_pairs];
+    const size_t Ng = (size_t)gt_off[F], Nt = (size_t)tr_off[F];
+    size_t nG = 0, id_cells = 0;
+    for (int p = 0; p < n_pairs; ++p) { nG += n_gt_ids[p]; id_cells += (size_t)n_gt_ids[p] * n_tr_ids[p]; }
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at = mot_up16(at + bytes); return o; };
+    const size_t o_gbox = take(Ng * 4 * sizeof(double)), o_tbox = take(Nt * 4 * sizeof(double));
+    const size_t o_poff = take((size_t)(n_pairs + 1) * sizeof(long long));
+    const size_t o_goff = take((size_t)(F + 1) * sizeof(int)), o_toff = take((size_t)(F + 1) * sizeof(int));
+    const size_t o_gid = take(Ng * sizeof(int)), o_tid = take(Nt * sizeof(int));
+    const size_t o_pairof = take((size_t)F * sizeof(int)), o_ngid = take((size_t)n_pairs * sizeof(int)), o_ntid = take((size_t)n_pairs * sizeof(int));
+    const size_t o_gbase = take((size_t)(n_pairs + 1) * sizeof(int));
+    const size_t up = at;
+    const size_t o_pot = take(id_cells * sizeof(unsigned));
+    const size_t o_match = take(nG * sizeof(int)), o_tp = take((size_t)n_pairs * sizeof(int));
+    const size_t total = at;
+    const size_t down_from = pot ? o_pot : o_match, down = total - down_from;
+    const size_t host_need = up + down;
+
+    if (!*pm) *pm = new SSMot();
+    SSMot& m = **pm;
+    if (!m.ev) MCHK(hipEventCreateWithFlags(&m.ev, hipEventDisableTiming));
+    if (m.host_cap < host_need) {
+        if (m.host) { MCHK(hipHostFree(m.host)); m.host = nullptr; m.host_cap = 0; }
+        const size_t cap = host_need + host_need / 4;
+        MCHK(hipHostMalloc(&m.host, cap, hipHostMallocDefault));
+        m.host_cap = cap;
+    }
+    if (m.dev_cap < total) {
+        if (m.dev) { MCHK(hipFree(m.dev)); m.dev = nullptr; m.dev_cap = 0; }
+        const size_t cap = total + total / 4;
+        MCHK(hipMalloc(&m.dev, cap));
+        m.dev_cap = cap;
+    }
+    char* h = (char*)m.host;
+    memcpy(h + o_gbox, gt_box, Ng * 4 * sizeof(double));
+    memcpy(h + o_tbox, tr_box, Nt * 4 * sizeof(double));
+    memcpy(h + o_goff, gt_off, (size_t)(F + 1) * sizeof(int));
+    memcpy(h + o_toff, tr_off, (size_t)(F + 1) * sizeof(int));
+    memcpy(h + o_gid, gt_id, Ng * sizeof(int));
+    memcpy(h + o_tid, tr_id, Nt * sizeof(int));
+    memcpy(h + o_ngid, n_gt_ids, (size_t)n_pairs * sizeof(int));
+    memcpy(h + o_ntid, n_tr_ids, (size_t)n_pairs * sizeof(int));
+    long long* h_poff = (long long*)(h + o_poff);
+    int* h_pairof = (int*)(h + o_pairof); int* h_gbase = (int*)(h + o_gbase);
+    h_poff[0] = 0; h_gbase[0] = 0;
+    bool cells = false;                                  // some frame has boxes on both sides
+    for (int p = 0; p < n_pairs; ++p) {
+        h_poff[p + 1] = h_poff[p] + (long long)n_gt_ids[p] * n_tr_ids[p];
+        h_gbase[p + 1] = h_gbase[p] + n_gt_ids[p];
+        for (int f = frame_off[p]; f < frame_off[p + 1]; ++f) {
+            h_pairof[f] = p;
+            cells = cells || (gt_off[f + 1] > gt_off[f] && tr_off[f + 1] > tr_off[f]);
+        }
+    }
+    char* d = (char*)m.dev;
+    MotArgs a;
+    memset(&a, 0, sizeof a);
+    a.gt_box = (const double*)(d + o_gbox); a.tr_box = (const double*)(d + o_tbox);
+    a.pot_off = (const long long*)(d + o_poff);
+    a.gt_off = (const int*)(d + o_goff); a.tr_off = (const int*)(d + o_toff); a.gt_id = (const int*)(d + o_gid); a.tr_id = (const int*)(d + o_tid);
+    a.pair_of = (const int*)(d + o_pairof); a.n_gid = (const int*)(d + o_ngid); a.n_tid = (const int*)(d + o_ntid);
+    a.gbase = (const int*)(d + o_gbase);
+    a.id_pot = (unsigned*)(d + o_pot); a.id_match = (int*)(d + o_match); a.id_tp = (int*)(d + o_tp);
+    a.thr = thr;
+
+    MCHK(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
+    if (id_cells) MCHK(hipMemsetAsync(d + o_pot, 0, id_cells * sizeof(unsigned), stream));       // every call
+    if (cells) {
+        hipLaunchKernelGGL(k_id_count, dim3((unsigned)F), dim3(256), 0, stream, a);
+        MCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_id_solve, dim3((unsigned)n_pairs), dim3(MOT_ID_THREADS), 0, stream, a);
+    MCHK(hipGetLastError());
+    MCHK(hipMemcpyAsync(h + up, d + down_from, down, hipMemcpyDeviceToHost, stream));
+    MCHK(hipEventRecord(m.ev, stream));
+    MCHK(hipEventSynchronize(m.ev));
+    const char* hd = h + up - down_from;                 // hd + o_x is field x of the download image
+    memcpy(idtp, hd + o_tp, (size_t)n_pairs * sizeof(int));
+    memcpy(gt_to_tr, hd + o_match, nG * sizeof(int));
+    if (pot) {                                           // the device's rows are the side with fewer ids: hand out [n_gt_ids][n_tr_ids]
+        const unsigned* src = (const unsigned*)(hd + o_pot);
+        for (int p = 0; p < n_pairs; ++p) {
+            const int G = n_gt_ids[p], T = n_tr_ids[p];
+            const unsigned* s = src + h_poff[p];
+            int* o = pot + h_poff[p];
+            if (T < G) {
+                for (int g = 0; g < G; ++g)
+                    for (int t = 0; t < T; ++t) o[(size_t)g * T + t] = (int)s[(size_t)t * G + g];
+            } else memcpy(o, s, (size_t)G * T * sizeof(int));
+        }
+    }
     return SS_OK;
 }

@@ -219,27 +219,51 @@ class TrackerEngine:
         gt_boxes [rows, 4] (x1, y1, x2, y2) and likewise on the tracker side.  -> (hota_match, hota_s, clear_match, clear_s) per
         ground-truth row (a match is the tracker row's index within its frame, -1 none) and, with want_ga, the alignment scores of
         all pairs in one flat array.  Synchronous; one device call for all pairs."""
+        n_pairs, k, n_gt_ids, n_tr_ids, ptrs, keep = self._mot_args("mot_eval", frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids)
+        n = max(k, 1)
+        hm, cm, hs, cs = np.full(n, -1, np.int32), np.full(n, -1, np.int32), np.zeros(n), np.zeros(n)
+        ga = np.zeros(max(int((n_gt_ids.astype(np.int64) * n_tr_ids).sum()), 1)) if want_ga else None
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        self._ck(self.L.ss_mot_eval(self.ctx, n_pairs, *ptrs, float(thr), hm.ctypes.data_as(pi), hs.ctypes.data_as(pd),
+                                    cm.ctypes.data_as(pi), cs.ctypes.data_as(pd), ga.ctypes.data_as(pd) if want_ga else None))
+        return (hm[:k], hs[:k], cm[:k], cs[:k]) + ((ga,) if want_ga else ())
+
+    @staticmethod
+    def _mot_args(who, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids):
+        """The host arrays of mot_eval / mot_identity, checked for shape -> (pairs, ground-truth rows, id counts of both sides, the
+        nine pointers in the C order, the arrays behind them)."""
         ai = lambda v: np.ascontiguousarray(v, np.int32).reshape(-1)
         frame_off, gt_off, tr_off, gt_ids, tr_ids, n_gt_ids, n_tr_ids = (ai(v) for v in (frame_off, gt_off, tr_off, gt_ids, tr_ids, n_gt_ids, n_tr_ids))
         gt_boxes, tr_boxes = (np.ascontiguousarray(v, np.float64).reshape(-1, 4) for v in (gt_boxes, tr_boxes))
         n_pairs = len(frame_off) - 1
         if (n_pairs < 1 or len(n_gt_ids) != n_pairs or len(n_tr_ids) != n_pairs or len(gt_off) != len(tr_off) or len(gt_off) != frame_off[-1] + 1
                 or gt_off[-1] != len(gt_ids) or tr_off[-1] != len(tr_ids) or len(gt_boxes) != len(gt_ids) or len(tr_boxes) != len(tr_ids)):
-            raise ValueError("mot_eval: frame_off [pairs + 1], gt_off / tr_off [frames + 1], ids [rows], boxes [rows, 4], id counts [pairs]")
-        n = max(len(gt_ids), 1)
-        hm, cm, hs, cs = np.full(n, -1, np.int32), np.full(n, -1, np.int32), np.zeros(n), np.zeros(n)
-        ga = np.zeros(max(int((n_gt_ids.astype(np.int64) * n_tr_ids).sum()), 1)) if want_ga else None
-        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+            raise ValueError(f"{who}: frame_off [pairs + 1], gt_off / tr_off [frames + 1], ids [rows], boxes [rows, 4], id counts [pairs]")
         k = len(gt_ids)
         if not len(gt_ids):                                               # (a side without rows still passes a pointer)
             gt_ids, gt_boxes = np.zeros(1, np.int32), np.zeros((1, 4))
         if not len(tr_ids):
             tr_ids, tr_boxes = np.zeros(1, np.int32), np.zeros((1, 4))
-        self._ck(self.L.ss_mot_eval(self.ctx, n_pairs, frame_off.ctypes.data_as(pi), gt_off.ctypes.data_as(pi), tr_off.ctypes.data_as(pi),
-                                    gt_ids.ctypes.data_as(pi), tr_ids.ctypes.data_as(pi), gt_boxes.ctypes.data_as(pd), tr_boxes.ctypes.data_as(pd),
-                                    n_gt_ids.ctypes.data_as(pi), n_tr_ids.ctypes.data_as(pi), float(thr), hm.ctypes.data_as(pi), hs.ctypes.data_as(pd),
-                                    cm.ctypes.data_as(pi), cs.ctypes.data_as(pd), ga.ctypes.data_as(pd) if want_ga else None))
-        return (hm[:k], hs[:k], cm[:k], cs[:k]) + ((ga,) if want_ga else ())
+        keep = (frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids)
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        return n_pairs, k, n_gt_ids, n_tr_ids, [v.ctypes.data_as(pd if v.dtype == np.float64 else pi) for v in keep], keep
+
+    def mot_identity(self, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids, thr: float = 0.5, want_pot: bool = False):
+        """The identity metrics' device half (csrc/ss_mot.hip, docs/MOTEVAL.md §1 "Identity"), the packing of mot_eval: -> (idtp [pairs]
+        int32, the weight of a maximum-weight matching of each pair's ground-truth ids to its tracker ids under the counts pot;
+        gt_to_tr [all ground-truth ids] int32, one such matching as dense tracker ids, -1 none) and, with want_pot, the counts of all
+        pairs in one flat int32 array, per pair [n_gt_ids, n_tr_ids].  At most ss_mot_max_ids() ids a side of a pair.  Synchronous;
+        one device call for all pairs."""
+        n_pairs, _, n_gt_ids, n_tr_ids, ptrs, keep = self._mot_args("mot_identity", frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids)
+        cap = int(self.L.ss_mot_max_ids())                                # (a call over the cap is the library's to refuse: its outputs stay small)
+        g, t = np.clip(n_gt_ids, 0, cap).astype(np.int64), np.clip(n_tr_ids, 0, cap).astype(np.int64)
+        n_g = int(g.sum())
+        idtp, match = np.zeros(n_pairs, np.int32), np.full(max(n_g, 1), -1, np.int32)
+        pot = np.zeros(max(int((g * t).sum()), 1), np.int32) if want_pot else None
+        pi = C.POINTER(C.c_int)
+        self._ck(self.L.ss_mot_identity(self.ctx, n_pairs, *ptrs, float(thr), idtp.ctypes.data_as(pi), match.ctypes.data_as(pi),
+                                        pot.ctypes.data_as(pi) if pot is not None else None))
+        return (idtp, match[:n_g]) + ((pot,) if want_pot else ())
 
     # ---- tracker --------------------------------------------------------------------------------
     def update_device(self, dets, ndets, feats, img_hw, out=None, nout=None):

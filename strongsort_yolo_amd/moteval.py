@@ -7,8 +7,10 @@ ids to dense indices, packs the call and turns the per-row record that comes bac
 no CPU fallback: without the library or a device `evaluate` raises as the rest of the package does.  tests/moteval_ref.py restates
 the whole of it; the device's record and every figure equal it bit for bit.  Parity with TrackEval or motmetrics is unpinned.
 
-Identity metrics (IDF1, IDP, IDR) are not computed: they need one assignment over (ground-truth ids + tracker ids) squared, beyond
-the 256-column solver.  `evaluate(..., metrics=("IDF1",))` refuses by name."""
+The identity metrics IDF1, IDP and IDR (docs/MOTEVAL.md §1 "Identity") are a device call of their own, `identity` /
+`identity_full`, or `evaluate(..., identity=True)`, which adds their six keys to every dict: the counts of the id pairs and one
+maximum-weight matching of ground-truth ids to tracker ids, solved by a workgroup for up to 4096 ids a side.  They are not part of
+the default call: `evaluate(..., metrics=("IDF1",))` still refuses by name and says which switch to use."""
 from __future__ import annotations
 
 import json
@@ -22,7 +24,8 @@ ALPHAS = [0.05 + k * 0.05 for k in range(19)]
 MAX_BOXES = 256                                         # ss_mot_max_boxes(); the other caps are the library's to refuse (docs/MOTEVAL.md §2)
 LDS_CELLS = 20000                                       # a frame's matrix of up to this many cells is solved from LDS
 HOTA_FIELDS = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA")
-REFUSED = ("IDF1", "IDP", "IDR")
+REFUSED = ("IDF1", "IDP", "IDR")                        # not in `metrics=`: they come from identity=True or moteval.identity
+IDENTITY_FIELDS = ("IDTP", "IDFN", "IDFP", "IDF1", "IDP", "IDR")
 
 
 def _seq(x) -> float:
@@ -130,20 +133,65 @@ def pack(pairs):
             np.asarray([p.n_gid for p in pairs], np.int32), np.asarray([p.n_tid for p in pairs], np.int32))
 
 
-def evaluate_full(gt_rows, tracker_rows, engine, thr: float = 0.5, classes=None, metrics=None, want_ga: bool = False):
-    """-> (one dict of metrics per pair, one record dict per pair: hota_idx, hota_s, clear_idx, clear_s per ground-truth row by
-    (frame, id), and GA with want_ga).  tracker_rows: one row set or a list of them, each scored against gt_rows."""
-    for name in metrics or ():
-        if name in REFUSED:
-            raise ValueError(f"{name}: identity metrics are not computed (docs/MOTEVAL.md: one assignment over all ids of both sides, beyond the 256-column solver)")
+def _pairs(gt_rows, tracker_rows, thr, classes):
+    """-> the list of _Pair of a call: tracker_rows is one row set or a list of them, each scored against gt_rows"""
     if not (0.0 < float(thr) <= 1.0):
         raise ValueError("thr must be in (0, 1]")
     many = isinstance(tracker_rows, (list, tuple)) and (len(tracker_rows) == 0 or np.ndim(tracker_rows[0]) >= 2)
     sets = list(tracker_rows) if many else [tracker_rows]
     if not sets:
-        return [], []
+        return []
     gt = _rows(gt_rows, "ground truth", classes)
-    pairs = [_Pair(gt, _rows(t, f"tracker rows {k}", classes)) for k, t in enumerate(sets)]
+    return [_Pair(gt, _rows(t, f"tracker rows {k}", classes)) for k, t in enumerate(sets)]
+
+
+def _identity_figures(idtp: int, n_gt: int, n_tr: int) -> dict:
+    idfn, idfp = n_gt - idtp, n_tr - idtp
+    return {"IDTP": int(idtp), "IDFN": int(idfn), "IDFP": int(idfp), "IDF1": idtp / max(1, idtp + 0.5 * idfp + 0.5 * idfn),
+            "IDP": idtp / max(1, idtp + idfp), "IDR": idtp / max(1, idtp + idfn)}
+
+
+def _identity(pairs, engine, thr, want_pot):
+    """one engine call for all pairs -> (one dict of the six figures per pair, one record dict per pair or None)"""
+    out = engine.mot_identity(*pack(pairs), thr=float(thr), want_pot=want_pot)
+    idtp, match = out[:2]
+    res, rec, g_at, c_at = [], [], 0, 0
+    for k, p in enumerate(pairs):
+        res.append(_identity_figures(int(idtp[k]), len(p.gt), len(p.tr)))
+        if want_pot:
+            m = np.asarray(match[g_at:g_at + p.n_gid])
+            gid, tid = np.unique(p.gt[:, 1]), np.unique(p.tr[:, 1])
+            rec.append({"gt_to_tr": {float(gid[g]): float(tid[m[g]]) for g in np.nonzero(m >= 0)[0]},
+                        "pot": np.asarray(out[2][c_at:c_at + p.n_gid * p.n_tid]).reshape(p.n_gid, p.n_tid)})
+        g_at, c_at = g_at + p.n_gid, c_at + p.n_gid * p.n_tid
+    return res, rec
+
+
+def identity_full(gt_rows, tracker_rows_or_list, engine, thr: float = 0.5, classes=None):
+    """-> (one dict per pair as `identity` returns it, one record dict per pair: `gt_to_tr`, the reported matching as a dict
+    original ground-truth id -> original tracker id (the matched ids only; ids whose pair never passes `thr` are left out), and
+    `pot` [ground-truth ids, tracker ids] int32 in np.unique order of the ids)."""
+    pairs = _pairs(gt_rows, tracker_rows_or_list, thr, classes)
+    return _identity(pairs, engine, thr, True) if pairs else ([], [])
+
+
+def identity(gt_rows, tracker_rows_or_list, engine, thr: float = 0.5, classes=None):
+    """The identity metrics (docs/MOTEVAL.md §1 "Identity"): one dict per pair with IDTP, IDFN, IDFP (ints) and IDF1, IDP, IDR
+    (floats), through a single device call.  A box pair counts where its similarity is at least `thr`."""
+    pairs = _pairs(gt_rows, tracker_rows_or_list, thr, classes)
+    return _identity(pairs, engine, thr, False)[0] if pairs else []
+
+
+def evaluate_full(gt_rows, tracker_rows, engine, thr: float = 0.5, classes=None, metrics=None, want_ga: bool = False, identity: bool = False):
+    """-> (one dict of metrics per pair, one record dict per pair: hota_idx, hota_s, clear_idx, clear_s per ground-truth row by
+    (frame, id), and GA with want_ga).  tracker_rows: one row set or a list of them, each scored against gt_rows.  identity: a
+    second engine call adds IDTP, IDFN, IDFP, IDF1, IDP, IDR to every dict."""
+    for name in metrics or ():
+        if name in REFUSED:
+            raise ValueError(f"{name}: identity metrics are not selected with metrics=; pass identity=True or call moteval.identity (docs/MOTEVAL.md)")
+    pairs = _pairs(gt_rows, tracker_rows, thr, classes)
+    if not pairs:
+        return [], []
     out = engine.mot_eval(*pack(pairs), thr=float(thr), want_ga=want_ga)
     hi, hs, ci, cs = out[:4]
     res, rec, at, ga_at = [], [], 0, 0
@@ -159,14 +207,18 @@ def evaluate_full(gt_rows, tracker_rows, engine, thr: float = 0.5, classes=None,
             r["GA"] = out[4][ga_at:ga_at + p.n_gid * p.n_tid].reshape(p.n_gid, p.n_tid)
             ga_at += p.n_gid * p.n_tid
         rec.append(r)
+    if identity:
+        for m, more in zip(res, _identity(pairs, engine, thr, False)[0]):
+            m.update(more)
     return res, rec
 
 
-def evaluate(gt_rows, tracker_rows_or_list, engine, thr: float = 0.5, classes=None, metrics=None):
+def evaluate(gt_rows, tracker_rows_or_list, engine, thr: float = 0.5, classes=None, metrics=None, identity: bool = False):
     """One dict of metrics per pair (a list, also for a single tracker row set), through a single device call: the 19-vectors
     `<name>_alpha` as lists, their means HOTA, DetA, AssA, DetRe, DetPr, AssRe, AssPr, LocA, HOTA(0), LocA(0), and CLEAR's TP, FN,
-    FP, IDSW, MOTA, MOTP, MT, PT, ML, Frag at the similarity threshold `thr`.  classes: keep only the rows of these classes."""
-    return evaluate_full(gt_rows, tracker_rows_or_list, engine, thr, classes, metrics)[0]
+    FP, IDSW, MOTA, MOTP, MT, PT, ML, Frag at the similarity threshold `thr`.  classes: keep only the rows of these classes.
+    identity: a second device call adds the identity metrics IDTP, IDFN, IDFP, IDF1, IDP, IDR at the same `thr`."""
+    return evaluate_full(gt_rows, tracker_rows_or_list, engine, thr, classes, metrics, identity=identity)[0]
 
 
 def read_labels(path: str) -> np.ndarray:
@@ -191,3 +243,8 @@ def write_metrics(path: str, metrics) -> None:
 
 def max_boxes() -> int:
     return int(_lib.load().ss_mot_max_boxes())
+
+
+def max_ids() -> int:
+    """the most ids one side of a pair may have in `identity`"""
+    return int(_lib.load().ss_mot_max_ids())

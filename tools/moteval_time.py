@@ -7,6 +7,12 @@
                   4 px jitter, one false positive a frame), and --pairs such pairs (different seeds of the perturbation) in one call.
   --mode kernel   a loop of --calls calls of the single large pair and of the --pairs-pair call and nothing else, for
                   `rocprofv3 --kernel-trace --stats -- python tools/moteval_time.py --mode kernel`.
+  --mode identity per leg wall ms of one moteval.identity call (IDF1, IDP, IDR: host packing, the device call, the figures), the same
+                  statistics, the share inside TrackerEngine.mot_identity, and in the same process tests/identity_ref.py on the host:
+                  the counts (pot_of), SciPy's linear_sum_assignment on the G x T reduction, and on the full (G+T)^2 matrix where
+                  G + T < 1500.  Legs: those of --mode time, one dense tie-heavy pair of 1100 x 1030 ids (identity_ref.crowd, 24 frames
+                  of 256 boxes a side), and two at the ids cap (4096 x 3072 ids in 40 frames, 4096 x 4096 in 20).
+  --mode identity-kernel   --calls calls of the 1100 x 1030 pair, then of the 4096 x 3072 pair, and nothing else, for rocprofv3.
 """
 import argparse
 import json
@@ -57,6 +63,58 @@ def host_leg(gt, trs):
     return out, 1e3 * (time.perf_counter() - t0)
 
 
+def identity_leg(eng, gt, trs, calls, warmup):
+    from strongsort_yolo_amd import moteval
+    inner = []
+    real = eng.mot_identity
+
+    def timed(*a, **k):
+        t0 = time.perf_counter()
+        out = real(*a, **k)
+        inner.append(1e3 * (time.perf_counter() - t0))
+        return out
+
+    eng.mot_identity = timed
+    try:
+        for _ in range(warmup):
+            out = moteval.identity(gt, trs, eng)
+        del inner[:]
+        ms = []
+        for _ in range(calls):
+            t0 = time.perf_counter()
+            out = moteval.identity(gt, trs, eng)
+            ms.append(1e3 * (time.perf_counter() - t0))
+    finally:
+        del eng.mot_identity
+    return out, stats(ms, calls), stats(inner, calls)
+
+
+def identity_host_leg(gt, trs):
+    """-> (figures per pair, ms of the counts, ms of SciPy on the reduction, ms of SciPy on the full matrix or None)"""
+    from tests import identity_ref
+    out, t_pot, t_red, t_full = [], 0.0, 0.0, 0.0
+    for t in trs:
+        t0 = time.perf_counter()
+        pot, p = identity_ref.pot_of(gt, t)
+        t1 = time.perf_counter()
+        w = identity_ref.reduced(pot)
+        t2 = time.perf_counter()
+        t_pot, t_red = t_pot + 1e3 * (t1 - t0), t_red + 1e3 * (t2 - t1)
+        if t_full is not None and p.n_gid + p.n_tid < 1500:
+            assert identity_ref.full(pot, p.cnt_g, p.cnt_t)[0] == w
+            t_full += 1e3 * (time.perf_counter() - t2)
+        else:
+            t_full = None
+        out.append(identity_ref.figures(w, len(p.gt), len(p.tr)))
+    return out, t_pot, t_red, t_full
+
+
+def crowds():
+    from tests import identity_ref
+    return [(f"crowd {g} x {t} ids, {f} frames",) + identity_ref.crowd(np.random.default_rng(g + f), g, t, f)
+            for g, t, f in ((1100, 1030, 24), (4096, 3072, 40), (4096, 4096, 20))]
+
+
 def large(frames, ids, pairs):
     from tests import moteval_ref
     gt = moteval_ref.synth_gt(1000, ids, frames)
@@ -65,7 +123,7 @@ def large(frames, ids, pairs):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--mode", choices=("time", "kernel"), default="time")
+    p.add_argument("--mode", choices=("time", "kernel", "identity", "identity-kernel"), default="time")
     p.add_argument("--frames", type=int, default=1000)
     p.add_argument("--ids", type=int, default=100)
     p.add_argument("--pairs", type=int, default=8)
@@ -76,6 +134,14 @@ def main():
     from strongsort_yolo_amd.engine import TrackerEngine
     from tests.golden.make_moteval_golden import case_rows
     eng = TrackerEngine()
+    if a.mode == "identity-kernel":
+        legs = crowds()[:2]
+        for _, g, t in legs:
+            for _ in range(a.calls):
+                moteval.identity(g, t, eng)
+        print(json.dumps({"leg": "identity kernel loop", "legs": [n for n, _, _ in legs], "calls": a.calls}))
+        eng.close()
+        return
     gt, trs = large(a.frames, a.ids, a.pairs)
     if a.mode == "kernel":
         for sets in (trs[:1], trs):
@@ -87,6 +153,15 @@ def main():
     z = np.load(os.path.join(ROOT, "tests", "golden", "moteval_cases.npz"))
     legs = [(name, case_rows(z[f"{name}_gt"]), [case_rows(z[f"{name}_tr"])]) for name in ("id30", "id100")]
     legs += [(f"1 pair of {a.frames} frames x {a.ids} ids", gt, trs[:1]), (f"{a.pairs} such pairs in one call", gt, trs)]
+    if a.mode == "identity":
+        for name, g, t in legs + [(n, cg, [ct]) for n, cg, ct in crowds()]:
+            got, whole, inner = identity_leg(eng, g, t, a.calls, a.warmup)
+            want, pot_ms, red_ms, full_ms = identity_host_leg(g, t)
+            print(json.dumps({"leg": name, "pairs": len(t), "gt_rows": len(g), "tracker_rows": [len(x) for x in t], "identity": whole, "of_which_mot_identity": inner,
+                              "host_counts_ms": round(pot_ms, 1), "scipy_reduction_ms": round(red_ms, 1), "scipy_full_ms": None if full_ms is None else round(full_ms, 1),
+                              "equal": json.dumps(got) == json.dumps(want), "IDF1": got[0]["IDF1"], "IDTP": got[0]["IDTP"]}), flush=True)
+        eng.close()
+        return
     for name, g, t in legs:
         got, whole, inner = device_leg(eng, g, t, a.calls, a.warmup)
         want, host_ms = host_leg(g, t)
