@@ -304,11 +304,19 @@ int ss_byte_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracked, int* n_
  * [6] = iterations (>= 1) or -1 (no usable alignment / no predecessor: identity), [7] = 0.  Asynchronous on hip_stream;
  * stateless apart from the remembered last frames, so it can run beside the detector.  d_n_valid (device int, may be NULL =
  * n_frames): only the first *d_n_valid frames of the buffer are real (a partial last group behind a captured graph): the
- * others get -1 warps and the last REAL frame is what the next call aligns its first frame with.
+ * others get -1 warps and the last REAL frame is what the next call aligns its first frame with.  20 <= h, w; row_stride >= 3 * w;
+ * n_frames <= ss_max_group_frames(); the first call for a frame size allocates (not inside a graph capture) and forgets every
+ * stream's predecessor.
+ * ss_cmc_get_small: synchronous inspection call, a permanent part of this ABI like ss_gmc_sparse_get (the tests compare the small
+ * images through it byte for byte).  The hs x ws grey image (hs = (int)(h * 0.1), ws = (int)(w * 0.1), rows ws bytes apart) of
+ * `stream`: frame 0 = the remembered predecessor (after a call: the call's last real frame), frame 1..n_frames = the frames of the
+ * last ss_cmc_estimate.  out may be NULL (only *hs, *ws are written; either may be NULL); otherwise cap >= hs * ws bytes.
+ * SS_ERR_INVALID before the first ss_cmc_estimate, for a frame / stream out of range and for a cap too small.
  * ss_track_set_cmc: the following tracker calls move every track's box by warp [f][s] before predicting frame f
  * (NULL switches compensation off, the default). */
 int ss_cmc_estimate(ss_ctx* ctx, void* hip_stream, const uint8_t* d_frames, int n_frames, long long frame_stride, int h, int w,
                     int row_stride, const int* d_n_valid, double* d_warps);
+int ss_cmc_get_small(ss_ctx* ctx, int frame, int stream, uint8_t* out, int cap, int* hs, int* ws);
 int ss_track_set_cmc(ss_ctx* ctx, const double* d_warps);
 
 /* ---- BoT-SORT GMC by sparse optical flow (docs/BYTETRACK.md §1f, decisions S-01..; Ultralytics' gmc_method: sparseOptFlow,

@@ -41,6 +41,7 @@ struct ss_ctx {
     uint8_t* cmc_small;         // [FMAX+1][S][cmc_stride] down-scaled grey frames (index 0 = last frame of the previous group)
     size_t cmc_stride;          // bytes per small image (multiple of 16), 0 until the first ss_cmc_estimate
     int cmc_hw[2];              // frame size the buffer was made for
+    int cmc_frames;             // n_frames of the last ss_cmc_estimate (what ss_cmc_get_small may read)
     int* cmc_prev_valid;        // [S]
     const double* cmc_warps;    // what ss_track_set_cmc installed
     SSGmcDev gmc;               // sparse-optical-flow estimator (ss_gmc.hip); gmc.h == 0 until the first ss_gmc_sparse_estimate
@@ -146,7 +147,7 @@ extern "C" int ss_create(const ss_config* cfg, int device, ss_ctx** out)
     c->inkernel = 0;
     c->cls_mask[0] = c->cls_mask[1] = ~0ull;
     memset(&c->gmc, 0, sizeof c->gmc);
-    c->cmc_small = nullptr; c->cmc_stride = 0; c->cmc_hw[0] = c->cmc_hw[1] = 0; c->cmc_warps = nullptr; c->assoc_event = nullptr;
+    c->cmc_small = nullptr; c->cmc_stride = 0; c->cmc_hw[0] = c->cmc_hw[1] = 0; c->cmc_frames = 0; c->cmc_warps = nullptr; c->assoc_event = nullptr;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) { int r = fail(nullptr, SS_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e)); delete c; return r; }
     SSParams& p = c->prm;
@@ -548,6 +549,21 @@ extern "C" int ss_cmc_estimate(ss_ctx* c, void* hip_stream, const uint8_t* d_fra
     ss_launch_cmc(d_frames, n_frames * c->dev.S, frame_stride, h, w, row_stride, c->cmc_small, (long long)c->cmc_stride, c->dev.S,
                   n_frames, hs, ws, 100, 1e-5, c->cmc_prev_valid, d_n_valid, d_warps, (hipStream_t)hip_stream);
     HIPCHK(c, hipGetLastError());
+    c->cmc_frames = n_frames;
+    return SS_OK;
+}
+
+extern "C" int ss_cmc_get_small(ss_ctx* c, int frame, int stream, uint8_t* out, int cap, int* hs, int* ws)
+{
+    if (!c || !c->cmc_stride || frame < 0 || frame > c->cmc_frames || stream < 0 || stream >= c->dev.S)
+        return fail(c, SS_ERR_INVALID, "ss_cmc_get_small: no estimate yet, or frame / stream out of range");
+    const int h = (int)(c->cmc_hw[0] * 0.1), w = (int)(c->cmc_hw[1] * 0.1);
+    if (hs) *hs = h;
+    if (ws) *ws = w;
+    if (!out) return SS_OK;                                            // a size query
+    if (cap < h * w) return fail(c, SS_ERR_INVALID, "ss_cmc_get_small: cap below hs * ws");
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemcpy(out, c->cmc_small + ((size_t)frame * c->dev.S + stream) * c->cmc_stride, (size_t)h * w, hipMemcpyDeviceToHost));
     return SS_OK;
 }
 

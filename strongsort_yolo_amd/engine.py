@@ -296,6 +296,15 @@ class TrackerEngine:
                                         frames.shape[1], frames.shape[2], frames.stride(1), _ptr(n_valid), _ptr(warps)))
         return warps
 
+    def cmc_small(self, frame: int, stream: int = 0) -> np.ndarray:
+        """Synchronous: a 0.1x grey image of `stream` as cmc_estimate keeps it (ss_cmc_get_small), uint8 [hs, ws]: frame 0 is the
+        remembered predecessor, frame 1..F are the frames of the last call."""
+        hs, ws = C.c_int(0), C.c_int(0)
+        self._ck(self.L.ss_cmc_get_small(self.ctx, int(frame), int(stream), None, 0, C.byref(hs), C.byref(ws)))
+        out = np.zeros((hs.value, ws.value), np.uint8)
+        self._ck(self.L.ss_cmc_get_small(self.ctx, int(frame), int(stream), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size, None, None))
+        return out
+
     def gmc_sparse_estimate(self, frames: torch.Tensor, n_frames: int, warps: torch.Tensor = None, stream=None, n_valid: torch.Tensor = None):
         """Sparse-optical-flow camera-motion warps of a group (docs/BYTETRACK.md §1f): cmc_estimate's arguments and layout;
         [6] = inliers or -1, [7] = tracked corners.  Frame sides >= 64."""
@@ -704,7 +713,7 @@ class ByteTrackEngine:
         self.use_stream, self.use_current_stream = self.base.use_stream, self.base.use_current_stream
         self.check_errors, self.cmc_estimate = self.base.check_errors, self.base.cmc_estimate
         self.gmc_sparse_estimate, self.estimate_warps = self.base.gmc_sparse_estimate, self.base.estimate_warps
-        self.gmc_sparse_stages = self.base.gmc_sparse_stages
+        self.gmc_sparse_stages, self.cmc_small = self.base.gmc_sparse_stages, self.base.cmc_small
 
     @property
     def ctx(self):

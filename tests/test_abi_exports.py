@@ -26,6 +26,7 @@ def test_library_exports_every_declared_symbol():
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, missing
     assert sorted(names) == sorted(lib.EXPORTS)          # the ctypes binding covers the whole header
+    assert "ss_cmc_estimate" in names and "ss_cmc_get_small" in names
 
 
 def test_library_exports_only_declared_symbols():
@@ -61,6 +62,7 @@ def test_host_side_entry_points_without_a_gpu():
     lib.build()
     L = lib.load()
     assert L.ss_max_group_frames() == 32
+    assert L.ss_cmc_get_small(None, 0, 0, None, 0, None, None) == lib.SS_ERR_INVALID                        # null context
     # band count of the LightConv chain launches: LDS form (16-row bands) below 96 images, the row-stream form sizes its bands
     # for one round of waves (32-wide: 3072 waves = images x bands x 2 chain groups), at least 8 rows per band
     assert L.ss_op_osnet_streams_bands(32, 64, 32, 16) == 4
@@ -96,7 +98,7 @@ def _prototypes():
     """name -> (return type, parameter texts) of every function declaration."""
     protos = {m.group(2): (" ".join(m.group(1).split()).replace(" *", "*"), [] if m.group(3).strip() == "void" else m.group(3).split(","))
               for m in re.finditer(r"^([A-Za-z][\w \t*]*?)\s*\b(ss_\w+)\s*\(([^()]*)\)\s*;", _header_code(), flags=re.M)}
-    assert len(protos) >= 127
+    assert len(protos) >= 130 and "ss_cmc_get_small" in protos
     return protos
 
 

@@ -32,6 +32,16 @@ def test_ecc_recovers_translation_and_rotation():
     warp, it = cexact.ecc(T, I)
     assert 1 <= it <= 100
     assert abs(warp[0, 2] + 3) < 0.05 and abs(warp[1, 2] - 2) < 0.05 and abs(warp[0, 0] - 1) < 1e-3 and abs(warp[1, 0]) < 1e-3
+    # the camera turned by 0.04 rad about the image origin and moved by (2.5, -1.5): I(R p + t) = T(p)
+    from scipy.ndimage import affine_transform
+    th, tx, ty = 0.04, 2.5, -1.5
+    c, s = np.cos(th), np.sin(th)
+    I = affine_transform(big, np.array([[c, -s], [s, c]]), offset=[12 - c * ty + s * tx, 12 - s * ty - c * tx], output_shape=(72, 128),
+                         order=1, mode="nearest").astype(np.uint8)
+    warp, it = cexact.ecc(T, I)
+    assert 2 <= it <= 20
+    assert abs(np.arctan2(warp[1, 0], warp[0, 0]) - th) < 2e-3 and abs(warp[0, 2] - tx) < 0.05 and abs(warp[1, 2] - ty) < 0.05
+    assert warp[0, 0] == warp[1, 1] and warp[0, 1] == -warp[1, 0]
     # identical frames: identity after the first check
     warp, it = cexact.ecc(T, T)
     assert np.allclose(warp, [[1, 0, 0], [0, 1, 0]], atol=1e-6) and it >= 1
