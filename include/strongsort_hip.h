@@ -491,7 +491,8 @@ int ss_op_conv0_f16(void* stream, const void* d_x, const void* d_w_prep, const v
  * see each other's setting.  At most 8 streams of a thread hold a setting at once (SS_ERR_CAPACITY). */
 int ss_op_set_valid_images(void* stream, const int* d_n, int batch);
 /* Process-wide A/B switches of the stateless operators, for measurements (default 1 each): "pw_epilogue" (16-byte vector
- * epilogue), "pw_splitk" (split-K form of small 3x3 layers), "osnet_chains" (register-resident LightConv row streams). */
+ * epilogue), "pw_splitk" (split-K form of small 3x3 layers), "osnet_chains" (register-resident LightConv row streams).  Sizes: "jpeg_subseq_words" (4, 8, 16 or 32), "aflink_chunk" (candidate
+ * pairs per pass of the AFLink network, 1 .. 65536, default 1024). */
 int ss_op_set_option(const char* name, int value);
 /* OSNet stem in one pass: conv 7x7/2 pad 3 (3 -> 16) + bias + ReLU + max pool 3x3/2 pad 1 on crops [N][H][128][3]
  * half -> [N][H/4][32][16]; d_w_prep [4][7][16][32] = for conv columns c = 4n + r, per (ky, out channel) the taps 3*kx+ch
@@ -735,6 +736,37 @@ int ss_mot_identity(ss_ctx* ctx, int n_pairs, const int* frame_off, const int* g
                     int* idtp, int* gt_to_tr, int* pot);
 /* Host only: the most ids one side of a pair may have in ss_mot_identity (4096: the workgroup-wide assignment solver's columns). */
 int ss_mot_max_ids(void);
+
+/* ---- AFLink: linking of finished tracklets by a small convolutional network (csrc/ss_aflink.hip, docs/AFLINK.md) ---- */
+/* Host only: the floats of the weight blob (docs/AFLINK.md section 3), and the most tracklets a side one connected component of
+ * surviving pairs may have in ss_aflink_match (256: the one-wave assignment solver's side). */
+long long ss_aflink_weight_floats(void);
+int ss_aflink_max_component(void);
+/* The network's weights, BatchNorms folded: blob = n = ss_aflink_weight_floats() finite floats in the layout of docs/AFLINK.md
+ * section 3.  Checked before the context is looked at; copied to the device, where they stay until the next call. */
+int ss_aflink_set_weights(ss_ctx* ctx, const float* blob, long long n);
+/* Host arrays in and out.  Tracklet t owns rows offsets[t] .. offsets[t+1]-1 (at least one; offsets[0] == 0) of feats [rows][3] =
+ * frame (an integer, strictly increasing inside a tracklet), x1, y1.  Tracklet i (the earlier) and j (the later) are a candidate
+ * if i != j, thr_t0 <= first frame of j - last frame of i < thr_t1 and sqrt(dx dx + dy dy) <= thr_s from i's last (x1, y1) to j's
+ * first (f64, no fma), and i starts first: (first frame of i, i) < (first frame of j, j), so the links of any matching of the candidates
+ * have no cycle.  *n_pairs receives the number of candidates.  cap == 0: nothing else is written (the caller sizes its arrays
+ * by the count and calls again).  cap >= the count: pair_i, pair_j (row-major: i rising, then j rising) and cost [count] = 1 -
+ * p[1] of the network for every candidate; inputs, when not NULL, receives the normalised network inputs [count][2][30][3].
+ * 0 < cap < the count: SS_ERR_CAPACITY, the message names the count (a sized call makes room for min(cap, n (n - 1) / 2) candidates before it counts).  Every argument is checked before the context or the device
+ * is looked at (SS_ERR_INVALID, also with a NULL context); without weights SS_ERR_INVALID.  The candidates pass the network in
+ * chunks (ss_op_set_option "aflink_chunk", default 1024) through scratch that belongs to the context and grows on demand.  Two
+ * identical calls give the same bytes.  Not capturable (waits, allocations that follow the call's size). */
+int ss_aflink_cost(ss_ctx* ctx, int n_tracklets, const int* offsets, const double* feats, int thr_t0, int thr_t1, double thr_s, long long cap,
+                   int* pair_i, int* pair_j, double* cost, float* inputs, long long* n_pairs);
+/* The matching of the pairs whose cost < thr_p (a cost equal to thr_p is left out): maximum cardinality, then minimum cost sum,
+ * solved per connected component of the surviving pairs by the one-wave solver in SciPy's scan order on the component's matrix
+ * (1e5 where a cell is no surviving pair), one launch for all components.  pair_i / pair_j [n_pairs] must be row-major and
+ * distinct, as ss_aflink_cost gives them; the costs are the caller's.  successor [n_tracklets] receives per tracklet the tracklet
+ * linked behind it, or -1.  A component with more than ss_aflink_max_component() tracklets a side is SS_ERR_CAPACITY (the message
+ * names its size; successor is all -1, nothing is truncated).  Pairs a caller made up may link in a circle; aflink.merge refuses
+ * such a successor array.  Arguments are checked first, as above. */
+int ss_aflink_match(ss_ctx* ctx, int n_tracklets, long long n_pairs, const int* pair_i, const int* pair_j, const double* cost, double thr_p,
+                    int* successor);
 
 /* ---- profiling support ----------------------------------------------------------------------- */
 /* Mean duration (ms) of the association (cosine gallery) kernel over the launches since the last

@@ -347,7 +347,9 @@ def process_video(args: dict, model=None) -> dict:
     on_device = sink is not None and sink.kind in ("mjpeg", "jpgdir")
     overlay, fps_str = None, ""
     gsi_on, gsi_rows = bool(args.get("gsi", False)) and track, []         # --gsi: every frame's tracked rows, smoothed after the stream (docs/GSI.md)
-    if gsi_on:
+    aflink_on = bool(args.get("aflink")) and track                        # --aflink: the same rows, linked after the stream (docs/AFLINK.md)
+    keep_rows = gsi_on or aflink_on
+    if keep_rows:
         from .gsi import rows_of
 
     def emit(frame, res):
@@ -355,7 +357,7 @@ def process_video(args: dict, model=None) -> dict:
         nonlocal frames, t0, fps, overlay, fps_str
         if track:
             writer.write(frames, res)
-            if gsi_on:
+            if keep_rows:
                 gsi_rows.append(rows_of(res, frames))
             if count:
                 counter.update(res)
@@ -408,21 +410,42 @@ def process_video(args: dict, model=None) -> dict:
         rows, status = gsi.gsi(rows, eng, interval=int(args.get("gsi_interval", gsi.INTERVAL)), tau=float(args.get("gsi_tau", gsi.TAU)))
         summary["gsi_rows"] = gsi.write_labels(os.path.join(args.get("outdir", "output"), f"{name}_labels_gsi.txt"), rows)
         summary["gsi_status"] = {k: sum(1 for v in status.values() if v == k) for k in (0, 1, 2)}
+    if aflink_on:
+        eng = (overlay or model.overlay()).eng
+        rows = np.concatenate(gsi_rows, 0) if gsi_rows else np.zeros((0, 8))
+        aflink_post(rows, eng, args, args.get("outdir", "output"), name, summary)
     if args.get("eval_gt") and track:
         # HOTA and CLEAR MOT of the files just written against the ground truth (docs/MOTEVAL.md): the labels file holds int()
         # corners, so the file is what is scored; with --gsi its file is a second pair of the same device call
         from . import moteval
         eng = (overlay or model.overlay()).eng
         outdir = args.get("outdir", "output")
-        names = ["labels"] + (["labels_gsi"] if gsi_on else [])
+        names = ["labels"] + (["labels_gsi"] if gsi_on else []) + (["labels_aflink"] if aflink_on else []) + (["labels_aflink_gsi"] if aflink_on and gsi_on else [])
         with_identity = bool(args.get("eval_identity"))            # IDF1, IDP, IDR: a second device call for the same pairs
         scored = moteval.evaluate(moteval.read_labels(args["eval_gt"]), [moteval.read_labels(os.path.join(outdir, f"{name}_{k}.txt")) for k in names],
                                   eng, thr=float(args.get("eval_thr", 0.5)), **({"identity": True} if with_identity else {}))
-        moteval.write_metrics(os.path.join(outdir, f"{name}_metrics.json"), dict(zip(names, scored)) if gsi_on else scored[0])
+        moteval.write_metrics(os.path.join(outdir, f"{name}_metrics.json"), dict(zip(names, scored)) if len(names) > 1 else scored[0])
         for k, m in zip(names, scored):
             for fig in ("HOTA", "MOTA", "IDSW") + (("IDF1",) if with_identity else ()):
                 summary[fig + k[len("labels"):]] = m[fig]
     return summary
+
+
+def aflink_post(rows, eng, args: dict, outdir: str, name: str, summary: dict):
+    """--aflink: the tracked rows of a finished run linked on the device (docs/AFLINK.md) into <name>_labels_aflink.txt; with --gsi
+    the StrongSORT++ order, AFLink then GSI, into <name>_labels_aflink_gsi.txt.  The other labels files stay as they are."""
+    from . import aflink, gsi
+    model = args["aflink"] if isinstance(args["aflink"], aflink.PostLinker) else aflink.load(args["aflink"])
+    info = {}
+    linked, _ = aflink.link(rows, eng, model, thr_t=tuple(args.get("aflink_thr_t", aflink.THR_T)), thr_s=float(args.get("aflink_thr_s", aflink.THR_S)),
+                            thr_p=float(args.get("aflink_thr_p", aflink.THR_P)), info=info)
+    os.makedirs(outdir, exist_ok=True)
+    gsi.write_labels(os.path.join(outdir, f"{name}_labels_aflink.txt"), linked)
+    summary["aflink_candidates"], summary["aflink_links"] = info["candidates"], info["links"]
+    if args.get("gsi", False):
+        both, _ = gsi.gsi(linked, eng, interval=int(args.get("gsi_interval", gsi.INTERVAL)), tau=float(args.get("gsi_tau", gsi.TAU)))
+        gsi.write_labels(os.path.join(outdir, f"{name}_labels_aflink_gsi.txt"), both)
+    return linked
 
 
 def _save_path(a, i: int) -> Optional[str]:
@@ -484,9 +507,16 @@ def main(argv=None):
                         "device, docs/GSI.md) of the tracked rows into <name>_labels_gsi.txt beside the labels file; any --tracker")
     p.add_argument("--gsi-interval", type=int, default=20, help="--gsi: gaps shorter than this many frames are filled")
     p.add_argument("--gsi-tau", type=float, default=10.0, help="--gsi: the length scale adapts as tau ln(tau^3 / track length)")
+    p.add_argument("--aflink", default=None, metavar="WEIGHTS",
+                   help="--track only: after the stream, AFLink (StrongSORT++'s tracklet linking, docs/AFLINK.md) of the tracked rows on the device "
+                        "with the PostLinker checkpoint WEIGHTS, into <name>_labels_aflink.txt; with --gsi also AFLink then GSI into "
+                        "<name>_labels_aflink_gsi.txt; any --tracker")
+    p.add_argument("--aflink-thr-t", type=int, nargs=2, default=[0, 30], metavar=("A", "B"), help="--aflink: a pair needs A <= frame gap < B")
+    p.add_argument("--aflink-thr-s", type=float, default=75.0, help="--aflink: a pair needs at most this distance between the tracklet ends")
+    p.add_argument("--aflink-thr-p", type=float, default=0.05, help="--aflink: a pair is linked only if its cost is below this, in (0, 1]")
     p.add_argument("--eval-gt", nargs="+", default=None, metavar="PATH",
                    help="--track only: ground-truth labels files (the labels file's line format), one per source; after the stream "
-                        "<name>_labels.txt (with --gsi also <name>_labels_gsi.txt) is scored against it on the device, HOTA and CLEAR MOT "
+                        "<name>_labels.txt (with --gsi / --aflink also their files) is scored against it on the device, HOTA and CLEAR MOT "
                         "(docs/MOTEVAL.md), into <name>_metrics.json")
     p.add_argument("--eval-thr", type=float, default=0.5, help="--eval-gt: CLEAR MOT's similarity threshold, in (0, 1]")
     p.add_argument("--eval-identity", action="store_true",
@@ -507,6 +537,16 @@ def main(argv=None):
         p.error("--gsi post-processes tracked rows: it needs --track")
     if a.gsi and (a.gsi_interval < 1 or not a.gsi_tau > 0):
         p.error("--gsi-interval must be >= 1 and --gsi-tau > 0")
+    if a.aflink and not a.track:
+        p.error("--aflink post-processes tracked rows: it needs --track")
+    if a.aflink and not os.path.isfile(a.aflink):
+        p.error(f"--aflink: no such file: {a.aflink}")
+    if a.aflink and not 0 <= a.aflink_thr_t[0] < a.aflink_thr_t[1]:
+        p.error("--aflink-thr-t A B must satisfy 0 <= A < B")
+    if a.aflink and not (a.aflink_thr_s >= 0 and a.aflink_thr_s < float("inf")):
+        p.error("--aflink-thr-s must be finite and >= 0")
+    if a.aflink and not 0.0 < a.aflink_thr_p <= 1.0:
+        p.error("--aflink-thr-p must be in (0, 1]")
     if a.camera_motion and a.tracker == "bytetrack":
         p.error("--camera-motion needs --tracker strongsort or botsort (ByteTrack has no GMC)")
     if a.gmc_method != "ecc" and not a.camera_motion:
@@ -546,6 +586,7 @@ def main(argv=None):
     jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "device_decode": a.device_decode, "device_entropy": a.device_entropy,
              "device_encode": a.device_encode, "device_encode_entropy": a.device_encode_entropy, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
              "gsi": a.gsi, "gsi_interval": a.gsi_interval, "gsi_tau": a.gsi_tau, "eval_gt": a.eval_gt[i] if a.eval_gt else None, "eval_thr": a.eval_thr, "eval_identity": a.eval_identity,
+             "aflink": a.aflink, "aflink_thr_t": tuple(a.aflink_thr_t), "aflink_thr_s": a.aflink_thr_s, "aflink_thr_p": a.aflink_thr_p,
              "save": _save_path(a, i)}
             for i, s in enumerate(a.source)]
     import torch

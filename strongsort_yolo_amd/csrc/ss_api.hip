@@ -77,6 +77,7 @@ struct ss_ctx {
     SSJpegEnc* jpeg_enc = nullptr;   // ss_jpeg_encode_batch's buffers, made by its first call
     SSGsi* gsi = nullptr;       // ss_gsi_smooth's staging and scratch slots, made by its first call
     SSMot* mot = nullptr;       // ss_mot_eval's and ss_mot_identity's staging, scratch and second stream, made by its first call
+    SSAflink* aflink = nullptr; // ss_aflink_*'s weights, staging and activation scratch, made by its first call
 };
 
 static int fail(ss_ctx* c, int code, const std::string& msg)
@@ -234,6 +235,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     ss_jpeg_enc_free(c->jpeg_enc);
     ss_gsi_free(c->gsi);
     ss_mot_free(c->mot);
+    ss_aflink_free(c->aflink);
     delete c;
 }
 
@@ -507,6 +509,41 @@ extern "C" int ss_mot_identity(ss_ctx* c, int n_pairs, const int* frame_off, con
     if (rc != SS_OK) return fail(c, rc, err);                                                            // the arguments first: no context needed
     rc = ss_mot_identity_impl(c ? &c->mot : nullptr, c ? c->stream : nullptr, n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes,
                               n_gt_ids, n_tr_ids, thr, idtp, gt_to_tr, pot, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+// ---- AFLink tracklet linking (ss_aflink.hip, docs/AFLINK.md) ---------------------------------------------------------------------
+extern "C" long long ss_aflink_weight_floats(void) { return ss_aflink_weight_floats_impl(); }
+extern "C" int ss_aflink_max_component(void) { return ss_aflink_max_component_impl(); }
+
+extern "C" int ss_aflink_set_weights(ss_ctx* c, const float* blob, long long n)
+{
+    std::string err;
+    int rc = ss_aflink_set_weights_check_impl(blob, n, err);                                              // the arguments first: no context needed
+    if (rc != SS_OK) return fail(c, rc, err);
+    rc = ss_aflink_set_weights_impl(c ? &c->aflink : nullptr, c ? c->stream : nullptr, blob, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+extern "C" int ss_aflink_cost(ss_ctx* c, int n_tracklets, const int* offsets, const double* feats, int thr_t0, int thr_t1, double thr_s, long long cap,
+                              int* pair_i, int* pair_j, double* cost, float* inputs, long long* n_pairs)
+{
+    std::string err;
+    int rc = ss_aflink_cost_check_impl(n_tracklets, offsets, feats, thr_t0, thr_t1, thr_s, cap, pair_i, pair_j, cost, n_pairs, err);
+    if (rc != SS_OK) return fail(c, rc, err);
+    rc = ss_aflink_cost_impl(c ? &c->aflink : nullptr, c ? c->stream : nullptr, n_tracklets, offsets, feats, thr_t0, thr_t1, thr_s, cap, pair_i, pair_j,
+                             cost, inputs, n_pairs, err);
+    return rc == SS_OK ? rc : fail(c, rc, err);
+}
+
+extern "C" int ss_aflink_match(ss_ctx* c, int n_tracklets, long long n_pairs, const int* pair_i, const int* pair_j, const double* cost, double thr_p,
+                               int* successor)
+{
+    std::string err;
+    int rc = ss_aflink_match_check_impl(n_tracklets, n_pairs, pair_i, pair_j, cost, thr_p, successor, err);
+    if (rc != SS_OK) return fail(c, rc, err);
+    // (a call without a surviving pair is settled on the host and needs no context)
+    rc = ss_aflink_match_impl(c ? &c->aflink : nullptr, c ? c->stream : nullptr, n_tracklets, n_pairs, pair_i, pair_j, cost, thr_p, successor, err);
     return rc == SS_OK ? rc : fail(c, rc, err);
 }
 

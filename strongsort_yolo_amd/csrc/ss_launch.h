@@ -119,3 +119,20 @@ int  ss_mot_identity_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int
                           const int* tr_id, const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
                           int* idtp, int* gt_to_tr, int* pot, std::string& err);
 void ss_mot_free(SSMot* m);
+
+// ---- ss_aflink.hip
+struct SSAflink;
+long long ss_aflink_weight_floats_impl();
+int  ss_aflink_max_component_impl();
+int  ss_aflink_chunk_option(int value);
+int  ss_aflink_set_weights_check_impl(const float* blob, long long n, std::string& err);
+int  ss_aflink_set_weights_impl(SSAflink** pg, hipStream_t stream, const float* blob, std::string& err);
+int  ss_aflink_cost_check_impl(int n, const int* offsets, const double* feats, int t0, int t1, double thr_s, long long cap, const int* pair_i,
+                               const int* pair_j, const double* cost, const long long* n_pairs, std::string& err);
+int  ss_aflink_cost_impl(SSAflink** pg, hipStream_t stream, int n, const int* offsets, const double* feats, int t0, int t1, double thr_s, long long cap,
+                         int* pair_i, int* pair_j, double* cost, float* inputs, long long* n_pairs, std::string& err);
+int  ss_aflink_match_check_impl(int n, long long n_pairs, const int* pair_i, const int* pair_j, const double* cost, double thr_p, const int* successor,
+                                std::string& err);
+int  ss_aflink_match_impl(SSAflink** pg, hipStream_t stream, int n, long long n_pairs, const int* pair_i, const int* pair_j, const double* cost,
+                          double thr_p, int* successor, std::string& err);
+void ss_aflink_free(SSAflink* g);

@@ -3024,7 +3024,9 @@ extern "C" int ss_op_set_valid_images(void* stream, const int* d_n, int batch)
 //   "pw_splitk"     split-K form for 3x3 layers with few pixels and a long K walk
 //   "osnet_chains"  register-resident row-stream form of the OSNet LightConv chains (0: the LDS form)
 //   "jpeg_subseq_words"  dwords of scan a lane of the device JPEG entropy stage owns: 4, 8, 16 or 32 (default; csrc/ss_jpeg.hip)
+//   "aflink_chunk"  candidate pairs per pass of the AFLink network, 1 .. 65536 (default 1024; csrc/ss_aflink.hip)
 extern int g_opt_jpeg_subseq_words;
+int ss_aflink_chunk_option(int value);
 extern "C" int ss_op_set_option(const char* name, int value)
 {
     if (!name) return SS_ERR_INVALID;
@@ -3033,6 +3035,7 @@ extern "C" int ss_op_set_option(const char* name, int value)
     else if (n == "pw_splitk") g_opt_pw_splitk = value;
     else if (n == "osnet_chains") g_opt_osnet_chains = value;
     else if (n == "jpeg_subseq_words") { if (value != 4 && value != 8 && value != 16 && value != 32) return SS_ERR_INVALID; g_opt_jpeg_subseq_words = value; }
+    else if (n == "aflink_chunk") return ss_aflink_chunk_option(value);
     else return SS_ERR_INVALID;
     return SS_OK;
 }

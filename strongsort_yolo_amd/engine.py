@@ -213,6 +213,51 @@ class TrackerEngine:
                                       len_scale.ctypes.data_as(pd), float(alpha), out.ctypes.data_as(pd), status.ctypes.data_as(pi)))
         return out[:len(frames)], status[:nt]
 
+    def aflink_set_weights(self, blob):
+        """AFLink's network weights (csrc/ss_aflink.hip, docs/AFLINK.md §3): the float32 blob of aflink.pack, ss_aflink_weight_floats()
+        long.  They stay on the device until the next call."""
+        blob = np.ascontiguousarray(blob, np.float32)
+        if blob.ndim != 1:
+            raise ValueError("aflink_set_weights: a flat float32 blob")
+        self._ck(self.L.ss_aflink_set_weights(self.ctx, blob.ctypes.data_as(C.POINTER(C.c_float)), len(blob)))
+
+    def aflink_cost(self, offsets, feats, thr_t=(0, 30), thr_s: float = 75.0, want_inputs: bool = False):
+        """AFLink's gate, input transform and network, host arrays in and out: tracklet t owns rows offsets[t] .. offsets[t+1]-1 of
+        feats [rows, 3] (frame, x1, y1).  -> (pair_i, pair_j int32 [pairs], row-major; cost float64 [pairs]) and, with want_inputs,
+        the normalised float32 inputs [pairs, 2, 30, 3].  The library counts the candidates first; the arrays are sized by its
+        answer.  Synchronous, on the engine's stream."""
+        offsets = np.ascontiguousarray(offsets, np.int32)
+        feats = np.ascontiguousarray(feats, np.float64)
+        n = len(offsets) - 1
+        if offsets.ndim != 1 or n < 0 or feats.ndim != 2 or feats.shape[1] != 3 or (len(offsets) and offsets[-1] != len(feats)) or len(thr_t) != 2:
+            raise ValueError("aflink_cost: offsets [tracklets + 1], feats [rows, 3] with offsets[-1] == rows, thr_t (t0, t1)")
+        pi, pd, pf, pl = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_longlong)
+        head = (self.ctx, n, offsets.ctypes.data_as(pi), feats.ctypes.data_as(pd), int(thr_t[0]), int(thr_t[1]), float(thr_s))
+        count = C.c_longlong(0)
+        self._ck(self.L.ss_aflink_cost(*head, 0, None, None, None, None, C.byref(count)))
+        m = int(count.value)
+        pair_i, pair_j, cost = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float64)
+        inputs = np.zeros((m, 2, 30, 3), np.float32) if want_inputs else None
+        if m:
+            self._ck(self.L.ss_aflink_cost(*head, m, pair_i.ctypes.data_as(pi), pair_j.ctypes.data_as(pi), cost.ctypes.data_as(pd),
+                                           inputs.ctypes.data_as(pf) if want_inputs else None, C.byref(count)))
+            if int(count.value) != m:
+                raise _lib.SSError(_lib.SS_ERR_INVALID, f"aflink_cost: {m} candidates counted, {int(count.value)} written")
+        return (pair_i, pair_j, cost, inputs) if want_inputs else (pair_i, pair_j, cost)
+
+    def aflink_match(self, n_tracklets: int, pair_i, pair_j, cost, thr_p: float = 0.05):
+        """AFLink's matching of the pairs with cost < thr_p (csrc/ss_aflink.hip: one wave per connected component) -> successor
+        [n_tracklets] int32, the tracklet linked behind each or -1.  The costs are the caller's."""
+        pair_i, pair_j = np.ascontiguousarray(pair_i, np.int32), np.ascontiguousarray(pair_j, np.int32)
+        cost = np.ascontiguousarray(cost, np.float64)
+        if pair_i.ndim != 1 or pair_j.shape != pair_i.shape or cost.shape != pair_i.shape:
+            raise ValueError("aflink_match: pair_i, pair_j, cost [pairs]")
+        succ = np.full(max(int(n_tracklets), 1), -1, np.int32)
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        self._ck(self.L.ss_aflink_match(self.ctx, int(n_tracklets), len(pair_i), pair_i.ctypes.data_as(pi), pair_j.ctypes.data_as(pi),
+                                        cost.ctypes.data_as(pd), float(thr_p), succ.ctypes.data_as(pi)))
+        return succ[:max(int(n_tracklets), 0)]
+
     def mot_eval(self, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids, thr: float = 0.5, want_ga: bool = False):
         """HOTA's and CLEAR MOT's matching of ground-truth / tracker pairs (csrc/ss_mot.hip, docs/MOTEVAL.md), host arrays in and out:
         pair p owns frames frame_off[p] .. frame_off[p+1]-1, frame f the rows gt_off[f] .. gt_off[f+1]-1 of gt_ids (dense, per pair) and

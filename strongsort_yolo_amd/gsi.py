@@ -6,7 +6,7 @@ track by the posterior mean of a Gaussian process over the frame number, on the 
 There is no CPU fallback: without the library or a device `smooth` raises as the rest of the package does.  tests/gsi_ref.py restates
 both steps; the device's results equal it bit for bit.
 
-AFLink, the other half of StrongSORT++, needs a trained network and is not part of this package.
+AFLink, the other half of StrongSORT++, is strongsort_yolo_amd.aflink (docs/AFLINK.md).
 """
 from __future__ import annotations
 
