@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 #include "ss_common.h"
+#include "ss_host.h"
 #include "ss_launch.h"
 #include "ss_lsap.h"
 
@@ -338,21 +339,13 @@ __global__ __launch_bounds__(64) void k_afl_match(const int4* __restrict__ desc,
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 struct SSAflink {
-    float* blob = nullptr;                              // the weights (ss_aflink_set_weights)
-    char* dev = nullptr; size_t dev_cap = 0;            // the call's uploads and results
-    float* scratch = nullptr; size_t scratch_cap = 0;   // floats: a chunk's x and the two activation buffers, grown when a call needs more
-    hipEvent_t ev = nullptr;
+    SsBuf<SS_DEVICE> blob;                              // the weights (ss_aflink_set_weights)
+    SsBuf<SS_DEVICE> dev;                               // the call's uploads and results
+    SsBuf<SS_DEVICE> scratch;                           // a chunk's x and the two activation buffers, grown when a call needs more
+    SsEvent ev;
 };
 
-void ss_aflink_free(SSAflink* g)
-{
-    if (!g) return;
-    if (g->ev) (void)hipEventDestroy(g->ev);
-    if (g->blob) (void)hipFree(g->blob);
-    if (g->dev) (void)hipFree(g->dev);
-    if (g->scratch) (void)hipFree(g->scratch);
-    delete g;
-}
+void ss_aflink_free(SSAflink* g) { delete g; }
 
 long long ss_aflink_weight_floats_impl() { return AFL_FLOATS; }
 int ss_aflink_max_component_impl() { return AFL_MAX_COMPONENT; }
@@ -363,30 +356,12 @@ int ss_aflink_chunk_option(int value)
     return SS_OK;
 }
 
-#define ACHK(x)                                                                                     \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) { err = who + #x ": " + hipGetErrorString(e_); return SS_ERR_HIP; }   \
-    } while (0)
-
-static size_t afl_up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 static int afl_state(SSAflink** pg, SSAflink*& g, const std::string& who, std::string& err)
 {
     if (!pg) { err = who + "null context"; return SS_ERR_INVALID; }
     if (!*pg) *pg = new SSAflink();
     g = *pg;
-    if (!g->ev) ACHK(hipEventCreateWithFlags(&g->ev, hipEventDisableTiming));
-    return SS_OK;
-}
-
-static int afl_grow(SSAflink& g, size_t bytes, const std::string& who, std::string& err)
-{
-    if (g.dev_cap >= bytes) return SS_OK;
-    if (g.dev) { ACHK(hipFree(g.dev)); g.dev = nullptr; g.dev_cap = 0; }
-    const size_t cap = bytes + bytes / 4;
-    ACHK(hipMalloc((void**)&g.dev, cap));
-    g.dev_cap = cap;
+    SS_HIPCHK(who, g->ev.ensure());
     return SS_OK;
 }
 
@@ -405,9 +380,9 @@ int ss_aflink_set_weights_impl(SSAflink** pg, hipStream_t stream, const float* b
     const std::string who = "ss_aflink_set_weights: ";
     SSAflink* g = nullptr;
     if (int rc = afl_state(pg, g, who, err)) return rc;
-    if (!g->blob) ACHK(hipMalloc((void**)&g->blob, (size_t)AFL_FLOATS * sizeof(float)));
-    ACHK(hipMemcpyAsync(g->blob, blob, (size_t)AFL_FLOATS * sizeof(float), hipMemcpyHostToDevice, stream));
-    ACHK(hipStreamSynchronize(stream));
+    SS_HIPCHK(who, g->blob.reserve((size_t)AFL_FLOATS * sizeof(float), SS_EXACT));
+    SS_HIPCHK(who, hipMemcpyAsync(g->blob.as(), blob, (size_t)AFL_FLOATS * sizeof(float), hipMemcpyHostToDevice, stream));
+    SS_HIPCHK(who, hipStreamSynchronize(stream));
     return SS_OK;
 }
 
@@ -450,63 +425,62 @@ int ss_aflink_cost_impl(SSAflink** pg, hipStream_t stream, int n, const int* off
     SSAflink* gp = nullptr;
     if (int rc = afl_state(pg, gp, who, err)) return rc;
     SSAflink& g = *gp;
-    if (!g.blob) { err = who + "no weights (ss_aflink_set_weights)"; return SS_ERR_INVALID; }
+    const float* const w = g.blob.as<float>();
+    if (!w) { err = who + "no weights (ss_aflink_set_weights)"; return SS_ERR_INVALID; }
     const size_t rows = (size_t)offsets[n];
     // device image: feats | row_off | offsets, then (a sized call) pair_i | pair_j | cost
-    const size_t o_ro = afl_up16(rows * 3 * sizeof(double)), o_off = o_ro + afl_up16((size_t)(n + 1) * sizeof(long long));
-    const size_t head = o_off + afl_up16((size_t)(n + 1) * sizeof(int));
+    SsLayout lay;
+    lay.take(rows * 3 * sizeof(double));                // feats at 0
+    const size_t o_ro = lay.take((size_t)(n + 1) * sizeof(long long)), o_off = lay.take((size_t)(n + 1) * sizeof(int));
+    const size_t head = lay.at;
     // a sized call makes room before the gate runs, so the gate is counted once per call: for `cap` candidates, or for the n (n - 1) / 2
     // pairs that n tracklets can give at most (one direction of every pair), whichever is less
     const size_t room = (size_t)std::min<long long>(cap, (long long)n * (n - 1) / 2);
     if (room > 0x7fffffffull / 256) { err = who + "room for " + std::to_string(room) + " candidates asked: more than one call takes"; return SS_ERR_CAPACITY; }
-    const size_t o_pi = head, o_pj = o_pi + afl_up16(room * sizeof(int)), o_cost = o_pj + afl_up16(room * sizeof(int));
-    const size_t all = o_cost + afl_up16(room * sizeof(double));
-    if (int rc = afl_grow(g, room ? all : head, who, err)) return rc;
-    ACHK(hipMemcpyAsync(g.dev, feats, rows * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-    ACHK(hipMemcpyAsync(g.dev + o_off, offsets, (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+    const size_t o_pi = lay.take(room * sizeof(int)), o_pj = lay.take(room * sizeof(int)), o_cost = lay.take(room * sizeof(double));
+    SS_HIPCHK(who, g.dev.reserve(room ? lay.at : head, SS_QUARTER));
+    char* const d = g.dev.as();
+    SS_HIPCHK(who, hipMemcpyAsync(d, feats, rows * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
+    SS_HIPCHK(who, hipMemcpyAsync(d + o_off, offsets, (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
     AflGate a;
-    a.offsets = (const int*)(g.dev + o_off); a.feats = (const double*)g.dev; a.row_off = (long long*)(g.dev + o_ro);
+    a.offsets = (const int*)(d + o_off); a.feats = (const double*)d; a.row_off = (long long*)(d + o_ro);
     a.pair_i = a.pair_j = nullptr; a.thr_s = thr_s; a.t0 = t0; a.t1 = t1; a.n = n;
     hipLaunchKernelGGL((k_afl_gate<false>), dim3(n), dim3(64), 0, stream, a);
     hipLaunchKernelGGL(k_afl_scan, dim3(1), dim3(64), 0, stream, a.row_off, n);
-    ACHK(hipGetLastError());
+    SS_HIPCHK(who, hipGetLastError());
     long long total = 0;
-    ACHK(hipMemcpyAsync(&total, a.row_off + n, sizeof(long long), hipMemcpyDeviceToHost, stream));
-    ACHK(hipStreamSynchronize(stream));
+    SS_HIPCHK(who, hipMemcpyAsync(&total, a.row_off + n, sizeof(long long), hipMemcpyDeviceToHost, stream));
+    SS_HIPCHK(who, hipStreamSynchronize(stream));
     *n_pairs = total;
     if (cap == 0 || total == 0) return SS_OK;           // the count alone: the caller sizes its arrays by it
     if (total > cap) { err = who + std::to_string(total) + " candidates, cap " + std::to_string(cap); return SS_ERR_CAPACITY; }
-    a.pair_i = (int*)(g.dev + o_pi); a.pair_j = (int*)(g.dev + o_pj);
-    double* d_cost = (double*)(g.dev + o_cost);
+    a.pair_i = (int*)(d + o_pi); a.pair_j = (int*)(d + o_pj);
+    double* d_cost = (double*)(d + o_cost);
     hipLaunchKernelGGL((k_afl_gate<true>), dim3(n), dim3(64), 0, stream, a);
-    ACHK(hipGetLastError());
+    SS_HIPCHK(who, hipGetLastError());
     const int chunk = (int)std::min<long long>(g_opt_aflink_chunk, total);
     const size_t need = (size_t)chunk * (AFL_X_FLOATS + 2 * AFL_BUF_FLOATS);
-    if (g.scratch_cap < need) {
-        if (g.scratch) { ACHK(hipFree(g.scratch)); g.scratch = nullptr; g.scratch_cap = 0; }
-        ACHK(hipMalloc((void**)&g.scratch, need * sizeof(float)));
-        g.scratch_cap = need;
-    }
-    float* x = g.scratch;
+    SS_HIPCHK(who, g.scratch.reserve(need * sizeof(float), SS_EXACT));
+    float* x = g.scratch.as<float>();
     float* bufA = x + (size_t)chunk * AFL_X_FLOATS;
     float* bufB = bufA + (size_t)chunk * AFL_BUF_FLOATS;
     for (long long c0 = 0; c0 < total; c0 += chunk) {
         const int P = (int)std::min<long long>(chunk, total - c0);
         hipLaunchKernelGGL(k_afl_prep, dim3((P * 3 + 255) / 256), dim3(256), 0, stream, a.offsets, a.feats, a.pair_i + c0, a.pair_j + c0, x, P);
-        hipLaunchKernelGGL(k_afl_l1, dim3((unsigned)(((long long)P * 2 * 3 * 24 * 8 + 255) / 256)), dim3(256), 0, stream, x, g.blob, bufA, P);
-        afl_launch_gemm<32, 64, 64, 24, 18, 0>(bufA, g.blob, bufB, P, AFL_O_W2, AFL_O_SB2, stream);
-        afl_launch_gemm<64, 128, 128, 18, 12, 0>(bufB, g.blob, bufA, P, AFL_O_W3, AFL_O_SB3, stream);
-        afl_launch_gemm<128, 256, 128, 12, 6, 1>(bufA, g.blob, bufB, P, AFL_O_W4, AFL_O_SB4, stream);
-        afl_launch_gemm<256, 256, 128, 6, 6, 2>(bufB, g.blob, bufA, P, AFL_O_WF, AFL_O_SBF, stream);
-        hipLaunchKernelGGL(k_afl_head, dim3(P), dim3(128), 0, stream, bufA, g.blob, d_cost + c0, P);
-        ACHK(hipGetLastError());
-        if (inputs) ACHK(hipMemcpyAsync(inputs + (size_t)c0 * AFL_X_FLOATS, x, (size_t)P * AFL_X_FLOATS * sizeof(float), hipMemcpyDeviceToHost, stream));
+        hipLaunchKernelGGL(k_afl_l1, dim3((unsigned)(((long long)P * 2 * 3 * 24 * 8 + 255) / 256)), dim3(256), 0, stream, x, w, bufA, P);
+        afl_launch_gemm<32, 64, 64, 24, 18, 0>(bufA, w, bufB, P, AFL_O_W2, AFL_O_SB2, stream);
+        afl_launch_gemm<64, 128, 128, 18, 12, 0>(bufB, w, bufA, P, AFL_O_W3, AFL_O_SB3, stream);
+        afl_launch_gemm<128, 256, 128, 12, 6, 1>(bufA, w, bufB, P, AFL_O_W4, AFL_O_SB4, stream);
+        afl_launch_gemm<256, 256, 128, 6, 6, 2>(bufB, w, bufA, P, AFL_O_WF, AFL_O_SBF, stream);
+        hipLaunchKernelGGL(k_afl_head, dim3(P), dim3(128), 0, stream, bufA, w, d_cost + c0, P);
+        SS_HIPCHK(who, hipGetLastError());
+        if (inputs) SS_HIPCHK(who, hipMemcpyAsync(inputs + (size_t)c0 * AFL_X_FLOATS, x, (size_t)P * AFL_X_FLOATS * sizeof(float), hipMemcpyDeviceToHost, stream));
     }
-    ACHK(hipMemcpyAsync(pair_i, a.pair_i, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, stream));
-    ACHK(hipMemcpyAsync(pair_j, a.pair_j, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, stream));
-    ACHK(hipMemcpyAsync(cost, d_cost, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, stream));
-    ACHK(hipEventRecord(g.ev, stream));
-    ACHK(hipEventSynchronize(g.ev));
+    SS_HIPCHK(who, hipMemcpyAsync(pair_i, a.pair_i, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, stream));
+    SS_HIPCHK(who, hipMemcpyAsync(pair_j, a.pair_j, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, stream));
+    SS_HIPCHK(who, hipMemcpyAsync(cost, d_cost, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, stream));
+    SS_HIPCHK(who, hipEventRecord(g.ev, stream));
+    SS_HIPCHK(who, hipEventSynchronize(g.ev));
     return SS_OK;
 }
 
@@ -573,9 +547,11 @@ int ss_aflink_match_impl(SSAflink** pg, hipStream_t stream, int n, long long n_p
     if (int rc = afl_state(pg, gp, who, err)) return rc;
     SSAflink& g = *gp;
     // image: matrices | desc | err | results
-    const size_t nc = comps.size(), o_desc = afl_up16(cells * sizeof(double)), o_err = o_desc + afl_up16(nc * sizeof(int4)), o_res = o_err + 16;
-    const size_t all = o_res + afl_up16(res * sizeof(int));
-    if (int rc = afl_grow(g, all, who, err)) return rc;
+    SsLayout lay;
+    lay.take(cells * sizeof(double));                   // matrices at 0
+    const size_t nc = comps.size(), o_desc = lay.take(nc * sizeof(int4)), o_err = lay.take(sizeof(int)), o_res = lay.take(res * sizeof(int));
+    SS_HIPCHK(who, g.dev.reserve(lay.at, SS_QUARTER));
+    char* const dev = g.dev.as();
     std::vector<char> h(o_res, 0);
     double* mats = (double*)h.data();
     int4* desc = (int4*)(h.data() + o_desc);
@@ -593,15 +569,15 @@ int ss_aflink_match_impl(SSAflink** pg, hipStream_t stream, int n, long long n_p
         at += (size_t)R * Cn;
         rat += std::min(R, Cn);
     }
-    ACHK(hipMemcpyAsync(g.dev, h.data(), o_res, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_afl_match, dim3((unsigned)nc), dim3(64), 0, stream, (const int4*)(g.dev + o_desc), (const double*)g.dev, (int*)(g.dev + o_res),
-                       (int*)(g.dev + o_err));
-    ACHK(hipGetLastError());
+    SS_HIPCHK(who, hipMemcpyAsync(dev, h.data(), o_res, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_afl_match, dim3((unsigned)nc), dim3(64), 0, stream, (const int4*)(dev + o_desc), (const double*)dev, (int*)(dev + o_res),
+                       (int*)(dev + o_err));
+    SS_HIPCHK(who, hipGetLastError());
     std::vector<int> out(res + 4);
-    ACHK(hipMemcpyAsync(out.data() + res, g.dev + o_err, sizeof(int), hipMemcpyDeviceToHost, stream));
-    if (res) ACHK(hipMemcpyAsync(out.data(), g.dev + o_res, res * sizeof(int), hipMemcpyDeviceToHost, stream));
-    ACHK(hipEventRecord(g.ev, stream));
-    ACHK(hipEventSynchronize(g.ev));
+    SS_HIPCHK(who, hipMemcpyAsync(out.data() + res, dev + o_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (res) SS_HIPCHK(who, hipMemcpyAsync(out.data(), dev + o_res, res * sizeof(int), hipMemcpyDeviceToHost, stream));
+    SS_HIPCHK(who, hipEventRecord(g.ev, stream));
+    SS_HIPCHK(who, hipEventSynchronize(g.ev));
     if (out[res] != 0) { err = who + "component " + std::to_string(out[res] - 1) + " has no assignment"; return SS_ERR_INFEASIBLE; }
     for (size_t q = 0; q < nc; ++q) {
         const Comp& c = comps[q];

@@ -4,10 +4,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <type_traits>
 #include <vector>
 #include "ss_common.h"
+#include "ss_host.h"
 #include "ss_launch.h"
 
 static std::string g_last_error;
@@ -32,7 +32,7 @@ struct ss_ctx {
     int nms_units;
     unsigned long long cls_mask[2];   // classes the NMS keeps (ss_nms_set_classes); all ones = every class
     // host -> device upload staging (ss_upload): write-combined pinned buffers, used round robin
-    struct Stage { void* p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool busy = false; } stage[4];
+    struct Stage { SsBuf<SS_PINNED_WC> buf; SsEvent ev; bool busy = false; int acquire(ss_ctx* c, size_t bytes); } stage[4];
     int stage_next = 0;
     Stage bstage[2];            // ss_upload_batch: a whole frame group per staging area
     int bstage_next = 0;
@@ -46,7 +46,7 @@ struct ss_ctx {
     const double* cmc_warps;    // what ss_track_set_cmc installed
     SSGmcDev gmc;               // sparse-optical-flow estimator (ss_gmc.hip); gmc.h == 0 until the first ss_gmc_sparse_estimate
     hipEvent_t assoc_event;     // what ss_track_set_assoc_event installed (recorded after every association launch)
-    struct Back { void* p = nullptr; size_t cap = 0; } back;      // device -> host staging (ss_download)
+    SsBuf<SS_PINNED> back;      // device -> host staging (ss_download)
     int cos_grid;               // persistent workgroups of the association kernel
     int comp_rows;              // ragged last tiles with at most this many rows travel as 4-row groups of composite tiles (0: never)
     int assoc_stage;            // staging of the association kernel's detection operand (SSDev.assoc_stage)
@@ -228,21 +228,27 @@ extern "C" void ss_destroy(ss_ctx* c)
     if (c->ev_chain) (void)hipEventDestroy(c->ev_chain);
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->byte) { for (void* p : c->byte->allocs) (void)hipFree(p); delete c->byte; }
-    for (auto& st : c->stage) { if (st.ev) (void)hipEventDestroy(st.ev); if (st.p) (void)hipHostFree(st.p); }
-    for (auto& st : c->bstage) { if (st.ev) (void)hipEventDestroy(st.ev); if (st.p) (void)hipHostFree(st.p); }
-    if (c->back.p) (void)hipHostFree(c->back.p);
     ss_jpeg_free(c->jpeg);
     ss_jpeg_enc_free(c->jpeg_enc);
     ss_gsi_free(c->gsi);
     ss_mot_free(c->mot);
     ss_aflink_free(c->aflink);
-    delete c;
+    delete c;                   // (the staging areas of ss_upload, ss_upload_batch and ss_download go with it)
 }
 
 extern "C" int ss_set_hip_stream(ss_ctx* c, void* s)
 {
     if (!c) return SS_ERR_INVALID;
     c->stream = (hipStream_t)s;
+    return SS_OK;
+}
+
+// What an upload does before it fills a staging area: the area's previous upload has left it, it holds `bytes`, its event exists
+int ss_ctx::Stage::acquire(ss_ctx* c, size_t bytes)
+{
+    if (busy) { HIPCHK(c, hipEventSynchronize(ev)); busy = false; }
+    HIPCHK(c, buf.reserve(bytes, SS_EXACT));
+    HIPCHK(c, ev.ensure());
     return SS_OK;
 }
 
@@ -255,15 +261,9 @@ extern "C" int ss_upload(ss_ctx* c, void* hip_stream, void* d_dst, const void* h
     if (bytes == 0) return SS_OK;
     ss_ctx::Stage& st = c->stage[c->stage_next];
     c->stage_next = (c->stage_next + 1) & 3;
-    if (st.busy) { HIPCHK(c, hipEventSynchronize(st.ev)); st.busy = false; }        // its previous upload has left the buffer
-    if (st.cap < bytes) {
-        if (st.p) { HIPCHK(c, hipHostFree(st.p)); st.p = nullptr; st.cap = 0; }
-        HIPCHK(c, hipHostMalloc(&st.p, bytes, hipHostMallocWriteCombined));
-        st.cap = bytes;
-    }
-    if (!st.ev) HIPCHK(c, hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
-    memcpy(st.p, h_src, bytes);
-    HIPCHK(c, hipMemcpyAsync(d_dst, st.p, bytes, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
+    if (int rc = st.acquire(c, bytes)) return rc;
+    memcpy(st.buf.as(), h_src, bytes);
+    HIPCHK(c, hipMemcpyAsync(d_dst, st.buf.as(), bytes, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
     HIPCHK(c, hipEventRecord(st.ev, (hipStream_t)hip_stream));
     st.busy = true;
     return SS_OK;
@@ -279,37 +279,16 @@ extern "C" int ss_upload_batch(ss_ctx* c, void* hip_stream, void* d_dst, const v
     if (n == 0 || bytes_each == 0) return SS_OK;
     for (int i = 0; i < n; ++i) if (!h_srcs[i]) return fail(c, SS_ERR_INVALID, "ss_upload_batch: null frame");
     ss_ctx::Stage& st = c->bstage[c->bstage_next];                  // (the area is taken for good only when the copy has been enqueued)
-    if (st.busy) { HIPCHK(c, hipEventSynchronize(st.ev)); st.busy = false; }
     const size_t bytes = (size_t)n * bytes_each;
-    if (st.cap < bytes) {
-        if (st.p) { HIPCHK(c, hipHostFree(st.p)); st.p = nullptr; st.cap = 0; }
-        HIPCHK(c, hipHostMalloc(&st.p, bytes, hipHostMallocWriteCombined));
-        st.cap = bytes;
-    }
-    if (!st.ev) HIPCHK(c, hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    if (int rc = st.acquire(c, bytes)) return rc;
     // small groups are not worth the threads' start + join (tens of microseconds); nothing the standard library throws
-    // (std::system_error when no thread can be started, bad_alloc) may cross the C boundary
+    // (std::system_error when no thread can be started, bad_alloc) may cross the C boundary: run_threads sees to that
     int T = threads < n ? threads : n;
     if (bytes < (size_t)4 << 20) T = 1;
-    char* base = (char*)st.p;
+    char* base = st.buf.as();
     auto work = [=](int t, int nt) { for (int i = t; i < n; i += nt) memcpy(base + (size_t)i * bytes_each, h_srcs[i], bytes_each); };
-    try {
-        std::vector<std::thread> pool;
-        pool.reserve(T > 1 ? T - 1 : 0);
-        int started = 1;
-        try {
-            for (int t = 1; t < T; ++t) { pool.emplace_back(work, t, T); ++started; }
-        } catch (...) {
-            for (auto& th : pool) th.join();                       // the frames of the threads that never started are copied here
-            for (int t = started; t < T; ++t) work(t, T);
-            pool.clear();
-        }
-        work(0, T);
-        for (auto& th : pool) th.join();
-    } catch (...) {
-        return fail(c, SS_ERR_INVALID, "ss_upload_batch: host staging failed");
-    }
-    HIPCHK(c, hipMemcpyAsync(d_dst, st.p, bytes, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
+    if (!run_threads(T, work)) return fail(c, SS_ERR_INVALID, "ss_upload_batch: host staging failed");
+    HIPCHK(c, hipMemcpyAsync(d_dst, base, bytes, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
     HIPCHK(c, hipEventRecord(st.ev, (hipStream_t)hip_stream));
     st.busy = true;
     c->bstage_next ^= 1;
@@ -333,14 +312,22 @@ extern "C" int ss_jpeg_coefficients(const unsigned char* data, size_t size, shor
     return rc == SS_OK ? rc : fail(nullptr, rc, "ss_jpeg_coefficients: " + err);
 }
 
+// ss_jpeg_decode_batch and ss_jpeg_decode_batch_device: one set of checks, the messages under the caller's name
+static int jpeg_decode_checks(ss_ctx* c, const std::string& who, const unsigned char* const* data, const size_t* sizes, int n, int height, int width,
+                              const void* d_out, long long out_frame_stride, int rgb, int threads)
+{
+    if (!c || !data || !sizes || !d_out) return fail(c, SS_ERR_INVALID, who + ": null argument");
+    if (n < 1 || n > 64 || threads < 1 || threads > 16 || height < 1 || height > 8192 || width < 1 || width > 8192 || (rgb != 0 && rgb != 1) ||
+        out_frame_stride < (long long)height * width * 3)
+        return fail(c, SS_ERR_INVALID, who + ": 1 <= n <= 64, 1 <= threads <= 16, sides 1 .. 8192, rgb 0 / 1, out_frame_stride >= height * width * 3");
+    for (int i = 0; i < n; ++i) if (!data[i] || !sizes[i]) return fail(c, SS_ERR_INVALID, who + ": image " + std::to_string(i) + ": no data");
+    return SS_OK;
+}
+
 extern "C" int ss_jpeg_decode_batch(ss_ctx* c, void* hip_stream, const unsigned char* const* data, const size_t* sizes, int n, int height,
                                     int width, void* d_out, long long out_frame_stride, int rgb, int threads)
 {
-    if (!c || !data || !sizes || !d_out) return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch: null argument");
-    if (n < 1 || n > 64 || threads < 1 || threads > 16 || height < 1 || height > 8192 || width < 1 || width > 8192 || (rgb != 0 && rgb != 1) ||
-        out_frame_stride < (long long)height * width * 3)
-        return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch: 1 <= n <= 64, 1 <= threads <= 16, sides 1 .. 8192, rgb 0 / 1, out_frame_stride >= height * width * 3");
-    for (int i = 0; i < n; ++i) if (!data[i] || !sizes[i]) return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch: image " + std::to_string(i) + ": no data");
+    if (const int bad = jpeg_decode_checks(c, "ss_jpeg_decode_batch", data, sizes, n, height, width, d_out, out_frame_stride, rgb, threads)) return bad;
     std::string err;
     const int rc = ss_jpeg_decode_impl(&c->jpeg, (hipStream_t)hip_stream, data, sizes, n, height, width, d_out, out_frame_stride, rgb, threads, err);
     return rc == SS_OK ? rc : fail(c, rc, err);
@@ -350,11 +337,7 @@ extern "C" int ss_jpeg_decode_batch(ss_ctx* c, void* hip_stream, const unsigned 
 extern "C" int ss_jpeg_decode_batch_device(ss_ctx* c, void* hip_stream, const unsigned char* const* data, const size_t* sizes, int n, int height,
                                            int width, void* d_out, long long out_frame_stride, int rgb, int threads)
 {
-    if (!c || !data || !sizes || !d_out) return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch_device: null argument");
-    if (n < 1 || n > 64 || threads < 1 || threads > 16 || height < 1 || height > 8192 || width < 1 || width > 8192 || (rgb != 0 && rgb != 1) ||
-        out_frame_stride < (long long)height * width * 3)
-        return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch_device: 1 <= n <= 64, 1 <= threads <= 16, sides 1 .. 8192, rgb 0 / 1, out_frame_stride >= height * width * 3");
-    for (int i = 0; i < n; ++i) if (!data[i] || !sizes[i]) return fail(c, SS_ERR_INVALID, "ss_jpeg_decode_batch_device: image " + std::to_string(i) + ": no data");
+    if (const int bad = jpeg_decode_checks(c, "ss_jpeg_decode_batch_device", data, sizes, n, height, width, d_out, out_frame_stride, rgb, threads)) return bad;
     std::string err;
     const int rc = ss_jpeg_decode_device_impl(&c->jpeg, (hipStream_t)hip_stream, data, sizes, n, height, width, d_out, out_frame_stride, rgb, threads, nullptr, 0, err);
     return rc == SS_OK ? rc : fail(c, rc, err);
@@ -467,18 +450,34 @@ extern "C" int ss_jpeg_entropy_encode_device(ss_ctx* c, const short* coef, int q
     return rc == SS_OK ? rc : fail(c, rc, err);
 }
 
+// ---- the post-run entries: GSI, HOTA / CLEAR MOT, identity metrics, AFLink ------------------------------------------------
+// check(err) looks at the arguments first and needs no context; work(err) runs when it found nothing.  Both build vectors and strings
+// sized by the caller's input and `work` makes the stage's state on first use: nothing they throw may cross the C boundary.
+template <class Check, class Work>
+static int post_run(ss_ctx* c, const char* entry, Check check, Work work)
+{
+    try {
+        std::string err;
+        int rc = check(err);
+        if (rc != SS_OK) return fail(c, rc, err);
+        rc = work(err);
+        return rc == SS_OK ? rc : fail(c, rc, err);
+    } catch (...) {
+        return fail(c, SS_ERR_INVALID, std::string(entry) + ": out of memory");
+    }
+}
+
 // ---- GSI post-processing (ss_gsi.hip, docs/GSI.md) ------------------------------------------------------------
 extern "C" int ss_gsi_max_len(void) { return ss_gsi_max_len_impl(); }
 
 extern "C" int ss_gsi_smooth(ss_ctx* c, int n_tracks, const int* offsets, const int* frames, const double* vals, const double* len_scale, double alpha,
                              double* out, int* status)
 {
-    std::string err;
-    int rc = ss_gsi_check_impl(n_tracks, offsets, frames, vals, len_scale, alpha, out, status, err);      // the arguments first: no context needed
-    if (rc != SS_OK) return fail(c, rc, err);
     // (tracks over the cap and empty tracks are settled on the host: a call that holds nothing else needs no context)
-    rc = ss_gsi_smooth_impl(c ? &c->gsi : nullptr, c ? c->stream : nullptr, n_tracks, offsets, frames, vals, len_scale, alpha, out, status, err);
-    return rc == SS_OK ? rc : fail(c, rc, err);
+    return post_run(c, "ss_gsi_smooth",
+        [&](std::string& err) { return ss_gsi_check_impl(n_tracks, offsets, frames, vals, len_scale, alpha, out, status, err); },
+        [&](std::string& err) { return ss_gsi_smooth_impl(c ? &c->gsi : nullptr, c ? c->stream : nullptr, n_tracks, offsets, frames, vals, len_scale, alpha, out,
+                                                          status, err); });
 }
 
 // ---- HOTA and CLEAR MOT against ground truth (ss_mot.hip, docs/MOTEVAL.md) --------------------------------------------------
@@ -488,13 +487,11 @@ extern "C" int ss_mot_eval(ss_ctx* c, int n_pairs, const int* frame_off, const i
                            const double* gt_boxes, const double* tr_boxes, const int* n_gt_ids, const int* n_tr_ids, double thr,
                            int* hota_match, double* hota_s, int* clear_match, double* clear_s, double* ga)
 {
-    std::string err;
-    int rc = ss_mot_check_impl(n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids, thr,
-                               hota_match, hota_s, clear_match, clear_s, err);                            // the arguments first: no context needed
-    if (rc != SS_OK) return fail(c, rc, err);
-    rc = ss_mot_eval_impl(c ? &c->mot : nullptr, c ? c->stream : nullptr, n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes,
-                          n_gt_ids, n_tr_ids, thr, hota_match, hota_s, clear_match, clear_s, ga, err);
-    return rc == SS_OK ? rc : fail(c, rc, err);
+    return post_run(c, "ss_mot_eval",
+        [&](std::string& err) { return ss_mot_check_impl(n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids, thr,
+                                                         hota_match, hota_s, clear_match, clear_s, err); },
+        [&](std::string& err) { return ss_mot_eval_impl(c ? &c->mot : nullptr, c ? c->stream : nullptr, n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes,
+                                                        tr_boxes, n_gt_ids, n_tr_ids, thr, hota_match, hota_s, clear_match, clear_s, ga, err); });
 }
 
 // ---- the identity metrics IDF1, IDP, IDR (ss_mot.hip, docs/MOTEVAL.md) ----------------------------------------------------------
@@ -504,12 +501,11 @@ extern "C" int ss_mot_identity(ss_ctx* c, int n_pairs, const int* frame_off, con
                                const double* gt_boxes, const double* tr_boxes, const int* n_gt_ids, const int* n_tr_ids, double thr,
                                int* idtp, int* gt_to_tr, int* pot)
 {
-    std::string err;
-    int rc = ss_mot_identity_check_impl(n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids, thr, idtp, gt_to_tr, err);
-    if (rc != SS_OK) return fail(c, rc, err);                                                            // the arguments first: no context needed
-    rc = ss_mot_identity_impl(c ? &c->mot : nullptr, c ? c->stream : nullptr, n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes,
-                              n_gt_ids, n_tr_ids, thr, idtp, gt_to_tr, pot, err);
-    return rc == SS_OK ? rc : fail(c, rc, err);
+    return post_run(c, "ss_mot_identity",
+        [&](std::string& err) { return ss_mot_identity_check_impl(n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes, tr_boxes, n_gt_ids, n_tr_ids, thr,
+                                                                  idtp, gt_to_tr, err); },
+        [&](std::string& err) { return ss_mot_identity_impl(c ? &c->mot : nullptr, c ? c->stream : nullptr, n_pairs, frame_off, gt_off, tr_off, gt_ids, tr_ids, gt_boxes,
+                                                            tr_boxes, n_gt_ids, n_tr_ids, thr, idtp, gt_to_tr, pot, err); });
 }
 
 // ---- AFLink tracklet linking (ss_aflink.hip, docs/AFLINK.md) ---------------------------------------------------------------------
@@ -518,33 +514,28 @@ extern "C" int ss_aflink_max_component(void) { return ss_aflink_max_component_im
 
 extern "C" int ss_aflink_set_weights(ss_ctx* c, const float* blob, long long n)
 {
-    std::string err;
-    int rc = ss_aflink_set_weights_check_impl(blob, n, err);                                              // the arguments first: no context needed
-    if (rc != SS_OK) return fail(c, rc, err);
-    rc = ss_aflink_set_weights_impl(c ? &c->aflink : nullptr, c ? c->stream : nullptr, blob, err);
-    return rc == SS_OK ? rc : fail(c, rc, err);
+    return post_run(c, "ss_aflink_set_weights",
+        [&](std::string& err) { return ss_aflink_set_weights_check_impl(blob, n, err); },
+        [&](std::string& err) { return ss_aflink_set_weights_impl(c ? &c->aflink : nullptr, c ? c->stream : nullptr, blob, err); });
 }
 
 extern "C" int ss_aflink_cost(ss_ctx* c, int n_tracklets, const int* offsets, const double* feats, int thr_t0, int thr_t1, double thr_s, long long cap,
                               int* pair_i, int* pair_j, double* cost, float* inputs, long long* n_pairs)
 {
-    std::string err;
-    int rc = ss_aflink_cost_check_impl(n_tracklets, offsets, feats, thr_t0, thr_t1, thr_s, cap, pair_i, pair_j, cost, n_pairs, err);
-    if (rc != SS_OK) return fail(c, rc, err);
-    rc = ss_aflink_cost_impl(c ? &c->aflink : nullptr, c ? c->stream : nullptr, n_tracklets, offsets, feats, thr_t0, thr_t1, thr_s, cap, pair_i, pair_j,
-                             cost, inputs, n_pairs, err);
-    return rc == SS_OK ? rc : fail(c, rc, err);
+    return post_run(c, "ss_aflink_cost",
+        [&](std::string& err) { return ss_aflink_cost_check_impl(n_tracklets, offsets, feats, thr_t0, thr_t1, thr_s, cap, pair_i, pair_j, cost, n_pairs, err); },
+        [&](std::string& err) { return ss_aflink_cost_impl(c ? &c->aflink : nullptr, c ? c->stream : nullptr, n_tracklets, offsets, feats, thr_t0, thr_t1, thr_s, cap,
+                                                           pair_i, pair_j, cost, inputs, n_pairs, err); });
 }
 
 extern "C" int ss_aflink_match(ss_ctx* c, int n_tracklets, long long n_pairs, const int* pair_i, const int* pair_j, const double* cost, double thr_p,
                                int* successor)
 {
-    std::string err;
-    int rc = ss_aflink_match_check_impl(n_tracklets, n_pairs, pair_i, pair_j, cost, thr_p, successor, err);
-    if (rc != SS_OK) return fail(c, rc, err);
     // (a call without a surviving pair is settled on the host and needs no context)
-    rc = ss_aflink_match_impl(c ? &c->aflink : nullptr, c ? c->stream : nullptr, n_tracklets, n_pairs, pair_i, pair_j, cost, thr_p, successor, err);
-    return rc == SS_OK ? rc : fail(c, rc, err);
+    return post_run(c, "ss_aflink_match",
+        [&](std::string& err) { return ss_aflink_match_check_impl(n_tracklets, n_pairs, pair_i, pair_j, cost, thr_p, successor, err); },
+        [&](std::string& err) { return ss_aflink_match_impl(c ? &c->aflink : nullptr, c ? c->stream : nullptr, n_tracklets, n_pairs, pair_i, pair_j, cost, thr_p,
+                                                            successor, err); });
 }
 
 // Device -> host through a pinned staging buffer; synchronous (returns when h_dst holds the bytes).
@@ -552,14 +543,10 @@ extern "C" int ss_download(ss_ctx* c, void* hip_stream, void* h_dst, const void*
 {
     if (!c || !h_dst || !d_src) return fail(c, SS_ERR_INVALID, "ss_download: null argument");
     if (bytes == 0) return SS_OK;
-    if (c->back.cap < bytes) {
-        if (c->back.p) { HIPCHK(c, hipHostFree(c->back.p)); c->back.p = nullptr; c->back.cap = 0; }
-        HIPCHK(c, hipHostMalloc(&c->back.p, bytes, hipHostMallocDefault));
-        c->back.cap = bytes;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->back.p, d_src, bytes, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
+    HIPCHK(c, c->back.reserve(bytes, SS_EXACT));
+    HIPCHK(c, hipMemcpyAsync(c->back.as(), d_src, bytes, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
     HIPCHK(c, hipStreamSynchronize((hipStream_t)hip_stream));
-    memcpy(h_dst, c->back.p, bytes);
+    memcpy(h_dst, c->back.as(), bytes);
     return SS_OK;
 }
 

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 #include "ss_common.h"
+#include "ss_host.h"
 #include "ss_launch.h"
 #include "ss_expneg.h"
 
@@ -206,22 +207,14 @@ __global__ __launch_bounds__(NT) void k_gsi_smooth(const GsiArgs a)
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
 struct SSGsi {
-    void* host = nullptr; size_t host_cap = 0;          // pinned: the upload image, then the download image
-    void* dev = nullptr; size_t dev_cap = 0;
-    double* scratch = nullptr; size_t scratch_cap = 0;  // doubles: the long tracks' slots, grown when a call needs more
-    hipEvent_t ev = nullptr;
+    SsBuf<SS_PINNED> host;                              // the upload image, then the download image
+    SsBuf<SS_DEVICE> dev;
+    SsBuf<SS_DEVICE> scratch;                           // the long tracks' slots, grown when a call needs more
+    SsEvent ev;
     bool attr = false;
 };
 
-void ss_gsi_free(SSGsi* g)
-{
-    if (!g) return;
-    if (g->ev) (void)hipEventDestroy(g->ev);
-    if (g->host) (void)hipHostFree(g->host);
-    if (g->dev) (void)hipFree(g->dev);
-    if (g->scratch) (void)hipFree(g->scratch);
-    delete g;
-}
+void ss_gsi_free(SSGsi* g) { delete g; }
 
 int ss_gsi_max_len_impl() { return GSI_MAX_LEN; }
 
@@ -247,14 +240,7 @@ int ss_gsi_check_impl(int n_tracks, const int* offsets, const int* frames, const
     return SS_OK;
 }
 
-#define GCHK(x)                                                                                     \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) { err = std::string("ss_gsi_smooth: " #x ": ") + hipGetErrorString(e_); return SS_ERR_HIP; } \
-    } while (0)
-
 static size_t gsi_image_doubles(int n) { return (size_t)n * (n + 1) / 2 + (size_t)4 * n; }
-static size_t gsi_up8(size_t b) { return (b + 7) & ~(size_t)7; }
 
 int ss_gsi_smooth_impl(SSGsi** pg, hipStream_t stream, int n_tracks, const int* offsets, const int* frames, const double* vals,
                        const double* len_scale, double alpha, double* out, int* status, std::string& err)
@@ -276,37 +262,26 @@ int ss_gsi_smooth_impl(SSGsi** pg, hipStream_t stream, int n_tracks, const int* 
     size_t rows = 0, n_glb = 0;
     for (int t : order) { const int n = offsets[t + 1] - offsets[t]; rows += n; n_glb += n > GSI_LDS_MAX; }
     // upload image: vals | len | desc | frames;  download image: out | status
-    const size_t o_len = rows * 4 * sizeof(double), o_desc = o_len + nd * sizeof(double), o_fr = o_desc + nd * sizeof(int2);
-    const size_t up = gsi_up8(o_fr + rows * sizeof(int));
-    const size_t o_stat = rows * 4 * sizeof(double), down = gsi_up8(o_stat + nd * sizeof(int));
+    SsLayout lay{0, 8};
+    lay.take(rows * 4 * sizeof(double));                // vals at 0
+    const size_t o_len = lay.take(nd * sizeof(double)), o_desc = lay.take(nd * sizeof(int2)), o_fr = lay.take(rows * sizeof(int));
+    const size_t up = lay.at;
+    const size_t o_stat = rows * 4 * sizeof(double), down = ss_align_up(o_stat + nd * sizeof(int), 8);
     if (!*pg) *pg = new SSGsi();
     SSGsi& g = **pg;
-    if (!g.ev) GCHK(hipEventCreateWithFlags(&g.ev, hipEventDisableTiming));
-    if (g.host_cap < up + down) {
-        if (g.host) { GCHK(hipHostFree(g.host)); g.host = nullptr; g.host_cap = 0; }
-        const size_t cap = (up + down) + (up + down) / 4;
-        GCHK(hipHostMalloc(&g.host, cap, hipHostMallocDefault));
-        g.host_cap = cap;
-    }
-    if (g.dev_cap < up + down) {
-        if (g.dev) { GCHK(hipFree(g.dev)); g.dev = nullptr; g.dev_cap = 0; }
-        const size_t cap = (up + down) + (up + down) / 4;
-        GCHK(hipMalloc(&g.dev, cap));
-        g.dev_cap = cap;
-    }
+    const char* const who = "ss_gsi_smooth: ";
+    SS_HIPCHK(who, g.ev.ensure());
+    SS_HIPCHK(who, g.host.reserve(up + down, SS_QUARTER));
+    SS_HIPCHK(who, g.dev.reserve(up + down, SS_QUARTER));
     const int slots = (int)std::min<size_t>(n_glb, GSI_SLOTS);
     const size_t slot_doubles = n_glb ? gsi_image_doubles(offsets[order[0] + 1] - offsets[order[0]]) : 0;
-    if (g.scratch_cap < slot_doubles * slots) {
-        if (g.scratch) { GCHK(hipFree(g.scratch)); g.scratch = nullptr; g.scratch_cap = 0; }
-        GCHK(hipMalloc((void**)&g.scratch, slot_doubles * slots * sizeof(double)));
-        g.scratch_cap = slot_doubles * slots;
-    }
+    SS_HIPCHK(who, g.scratch.reserve(slot_doubles * slots * sizeof(double), SS_EXACT));
     if (!g.attr) {
-        GCHK(hipFuncSetAttribute((const void*)k_gsi_smooth<false, GSI_NT_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        GCHK(hipFuncSetAttribute((const void*)k_gsi_smooth<true, GSI_NT_GLB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        SS_HIPCHK(who, hipFuncSetAttribute((const void*)k_gsi_smooth<false, GSI_NT_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        SS_HIPCHK(who, hipFuncSetAttribute((const void*)k_gsi_smooth<true, GSI_NT_GLB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         g.attr = true;
     }
-    char* h = (char*)g.host;
+    char* h = g.host.as();
     double* h_vals = (double*)h; double* h_len = (double*)(h + o_len); int2* h_desc = (int2*)(h + o_desc); int* h_fr = (int*)(h + o_fr);
     size_t at = 0;
     for (size_t k = 0; k < nd; ++k) {
@@ -317,15 +292,15 @@ int ss_gsi_smooth_impl(SSGsi** pg, hipStream_t stream, int n_tracks, const int* 
         h_desc[k] = make_int2((int)at, n);
         at += n;
     }
-    char* d = (char*)g.dev;
-    GCHK(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
+    char* d = g.dev.as();
+    SS_HIPCHK(who, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
     GsiArgs a;
     a.frames = (const int*)(d + o_fr); a.vals = (const double*)d; a.out = (double*)(d + up); a.alpha = alpha;
-    a.scratch = g.scratch; a.slot_doubles = slot_doubles;
+    a.scratch = g.scratch.as<double>(); a.slot_doubles = slot_doubles;
     if (n_glb) {                                        // the long tracks first
         a.desc = (const int2*)(d + o_desc); a.len = (const double*)(d + o_len); a.status = (int*)(d + up + o_stat); a.n_tracks = (int)n_glb;
         hipLaunchKernelGGL((k_gsi_smooth<true, GSI_NT_GLB>), dim3(slots), dim3(GSI_NT_GLB), GSI_PANEL * GSI_RS * sizeof(double), stream, a);
-        GCHK(hipGetLastError());
+        SS_HIPCHK(who, hipGetLastError());
     }
     if (nd > n_glb) {
         const int nmax = offsets[order[n_glb] + 1] - offsets[order[n_glb]];
@@ -333,11 +308,11 @@ int ss_gsi_smooth_impl(SSGsi** pg, hipStream_t stream, int n_tracks, const int* 
         a.n_tracks = (int)(nd - n_glb);
         hipLaunchKernelGGL((k_gsi_smooth<false, GSI_NT_LDS>), dim3((unsigned)(nd - n_glb)), dim3(GSI_NT_LDS), (gsi_image_doubles(nmax) + (size_t)4 * nmax) * sizeof(double),
                            stream, a);
-        GCHK(hipGetLastError());
+        SS_HIPCHK(who, hipGetLastError());
     }
-    GCHK(hipMemcpyAsync(h + up, d + up, down, hipMemcpyDeviceToHost, stream));
-    GCHK(hipEventRecord(g.ev, stream));
-    GCHK(hipEventSynchronize(g.ev));
+    SS_HIPCHK(who, hipMemcpyAsync(h + up, d + up, down, hipMemcpyDeviceToHost, stream));
+    SS_HIPCHK(who, hipEventRecord(g.ev, stream));
+    SS_HIPCHK(who, hipEventSynchronize(g.ev));
     const double* h_out = (const double*)(h + up); const int* h_stat = (const int*)(h + up + o_stat);
     at = 0;
     for (size_t k = 0; k < nd; ++k) {

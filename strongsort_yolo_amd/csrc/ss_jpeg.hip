@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 #include "ss_common.h"
+#include "ss_host.h"
 #include "ss_launch.h"
 #include "ss_jpeg_host.h"
 
@@ -460,11 +461,12 @@ struct SparseSink {
 
 struct SSJpeg {
     struct Slot {
-        void* host = nullptr; size_t host_cap = 0;              // write-combined staging
-        uint32_t* dev = nullptr; size_t dev_cap = 0;            // its device mirror
-        uint8_t* planes = nullptr; size_t planes_cap = 0;       // component planes of the call's images
-        hipEvent_t ev = nullptr; bool busy = false;
-        uint32_t *status_dev = nullptr, *status_host = nullptr;  // device entropy stage: a status word per image and its pinned copy
+        SsBuf<SS_PINNED_WC> host;                               // staging
+        SsBuf<SS_DEVICE> dev;                                   // its device mirror
+        SsBuf<SS_DEVICE> planes;                                // component planes of the call's images
+        SsEvent ev; bool busy = false;
+        SsBuf<SS_DEVICE> status_dev;                            // device entropy stage: a status word per image
+        SsBuf<SS_PINNED> status_host;                           // and its pinned copy
         int pending = 0;                                        // images whose status arrives with `ev` (0: the call was a host-stage one)
     } slot[2];
     int next = 0;
@@ -473,27 +475,20 @@ struct SSJpeg {
     std::vector<Image> img;
 };
 
-void ss_jpeg_free(SSJpeg* j)
-{
-    if (!j) return;
-    for (auto& st : j->slot) {
-        if (st.ev) (void)hipEventDestroy(st.ev);
-        if (st.host) (void)hipHostFree(st.host);
-        if (st.dev) (void)hipFree(st.dev);
-        if (st.planes) (void)hipFree(st.planes);
-        if (st.status_dev) (void)hipFree(st.status_dev);
-        if (st.status_host) (void)hipHostFree(st.status_host);
-    }
-    delete j;
-}
+void ss_jpeg_free(SSJpeg* j) { delete j; }
 
-#define JCHK(x)                                                                                              \
-    do {                                                                                                     \
-        hipError_t e_ = (x);                                                                                 \
-        if (e_ != hipSuccess) { err = std::string("ss_jpeg_decode_batch: " #x ": ") + hipGetErrorString(e_); return SS_ERR_HIP; } \
-    } while (0)
+static const char* const kJpegWho = "ss_jpeg_decode_batch: ";      // HIP failures of both batch paths are reported under this name
 
 static int jpeg_slot_wait(SSJpeg::Slot& st, std::string& err);
+
+// what both batch paths keep in a slot: the staging area and its mirror with a quarter to spare, the planes exact
+static int jpeg_slot_reserve(SSJpeg::Slot& st, size_t host_bytes, size_t dev_bytes, size_t planes_bytes, std::string& err)
+{
+    SS_HIPCHK(kJpegWho, st.host.reserve(host_bytes, SS_QUARTER));
+    SS_HIPCHK(kJpegWho, st.dev.reserve(dev_bytes, SS_QUARTER));
+    SS_HIPCHK(kJpegWho, st.planes.reserve(planes_bytes, SS_EXACT));
+    return SS_OK;
+}
 
 // The arguments have been checked (ss_api.hip).  Returns an SS_* code, the message in err.
 int ss_jpeg_decode_impl(SSJpeg** state, hipStream_t stream, const unsigned char* const* data, const size_t* sizes, int n, int height, int width,
@@ -545,26 +540,10 @@ int ss_jpeg_decode_impl(SSJpeg** state, hipStream_t stream, const unsigned char*
         const size_t plane_slot = 3 * (size_t)((width + 15) / 16 * 16) * ((height + 15) / 16 * 16), planes_bytes = plane_slot * n;
         SSJpeg::Slot& st = S.slot[S.next];
         if (int rcw = jpeg_slot_wait(st, err)) return rcw;       // (a device-entropy call that used this slot may have refused an image)
-        if (!st.ev) JCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
-        if (st.host_cap < bytes) {
-            if (st.host) { JCHK(hipHostFree(st.host)); st.host = nullptr; st.host_cap = 0; }
-            const size_t cap = bytes + bytes / 4;
-            JCHK(hipHostMalloc(&st.host, cap, hipHostMallocWriteCombined));
-            st.host_cap = cap;
-        }
-        if (st.dev_cap < bytes) {
-            if (st.dev) { JCHK(hipFree(st.dev)); st.dev = nullptr; st.dev_cap = 0; }
-            const size_t cap = bytes + bytes / 4;
-            JCHK(hipMalloc((void**)&st.dev, cap));
-            st.dev_cap = cap;
-        }
-        if (st.planes_cap < planes_bytes) {
-            if (st.planes) { JCHK(hipFree(st.planes)); st.planes = nullptr; st.planes_cap = 0; }
-            JCHK(hipMalloc((void**)&st.planes, planes_bytes));
-            st.planes_cap = planes_bytes;
-        }
+        SS_HIPCHK(kJpegWho, st.ev.ensure());
+        if (int rcr = jpeg_slot_reserve(st, bytes, bytes, planes_bytes, err)) return rcr;
         // ---- 3. pack into the write-combined area (sequential stores only) ----
-        uint32_t* base = (uint32_t*)st.host;
+        uint32_t* base = st.host.as<uint32_t>();
         auto pack = [&S, base, n](int t, int nt) {
             for (int i = t; i < n; i += nt) {
                 const SSJpeg::Image& im = S.img[i];
@@ -587,14 +566,16 @@ int ss_jpeg_decode_impl(SSJpeg** state, hipStream_t stream, const unsigned char*
         };
         if (!run_threads(bytes < ((size_t)1 << 20) ? 1 : T, pack)) { err = "ss_jpeg_decode_batch: host staging failed"; return SS_ERR_INVALID; }
         // ---- 4. one copy, two launches ----
-        JCHK(hipMemcpyAsync(st.dev, st.host, bytes, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(k_jpeg_idct, dim3((max_blk + 31) / 32, n), dim3(256), 0, stream, st.dev, st.planes, (long long)plane_slot);
+        uint32_t* dev = st.dev.as<uint32_t>();
+        uint8_t* planes = st.planes.as<uint8_t>();
+        SS_HIPCHK(kJpegWho, hipMemcpyAsync(dev, base, bytes, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_jpeg_idct, dim3((max_blk + 31) / 32, n), dim3(256), 0, stream, dev, planes, (long long)plane_slot);
         const int groups = (height * width + 3) / 4;
         const int dwords = (((uintptr_t)d_out | (uintptr_t)out_frame_stride) & 3) == 0;
-        hipLaunchKernelGGL(k_jpeg_pixels, dim3((groups + 255) / 256, n), dim3(256), 0, stream, st.dev, st.planes, (long long)plane_slot, height, width,
+        hipLaunchKernelGGL(k_jpeg_pixels, dim3((groups + 255) / 256, n), dim3(256), 0, stream, dev, planes, (long long)plane_slot, height, width,
                            (uint8_t*)d_out, out_frame_stride, rgb, dwords);
-        JCHK(hipGetLastError());
-        JCHK(hipEventRecord(st.ev, stream));
+        SS_HIPCHK(kJpegWho, hipGetLastError());
+        SS_HIPCHK(kJpegWho, hipEventRecord(st.ev, stream));
         st.busy = true;
         S.next ^= 1;
         return SS_OK;
@@ -1011,9 +992,10 @@ static int jpeg_slot_wait(SSJpeg::Slot& st, std::string& err)
     }
     const int n = st.pending;
     st.pending = 0;
+    const uint32_t* status = st.status_host.as<uint32_t>();
     for (int i = 0; i < n; ++i)
-        if (st.status_host[i] != JH_OK) {
-            const uint32_t code = st.status_host[i] & 7u;
+        if (status[i] != JH_OK) {
+            const uint32_t code = status[i] & 7u;
             err = "ss_jpeg_decode_batch_device: image " + std::to_string(i) + ": " + kJpegCause[code < 7 ? code : 0];
             return SS_ERR_INVALID;
         }
@@ -1082,19 +1064,12 @@ int ss_jpeg_decode_device_impl(SSJpeg** state, hipStream_t stream, const unsigne
         const size_t in_words = at;
         SSJpeg::Slot& st = S.slot[S.next];
         if (int rcw = jpeg_slot_wait(st, err)) return rcw;
-        if (!st.ev) JCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
-        if (!st.status_dev) {
-            JCHK(hipMalloc((void**)&st.status_dev, 64 * sizeof(uint32_t)));
-            JCHK(hipHostMalloc((void**)&st.status_host, 64 * sizeof(uint32_t), hipHostMallocDefault));
-        }
-        if (st.host_cap < in_words * 4) {
-            if (st.host) { JCHK(hipHostFree(st.host)); st.host = nullptr; st.host_cap = 0; }
-            const size_t cap = in_words * 4 + in_words;
-            JCHK(hipHostMalloc(&st.host, cap, hipHostMallocWriteCombined));
-            st.host_cap = cap;
-        }
+        SS_HIPCHK(kJpegWho, st.ev.ensure());
+        SS_HIPCHK(kJpegWho, st.status_dev.reserve(64 * sizeof(uint32_t), SS_EXACT));
+        SS_HIPCHK(kJpegWho, st.status_host.reserve(64 * sizeof(uint32_t), SS_EXACT));
+        if (int rcr = jpeg_slot_reserve(st, in_words * 4, 0, 0, err)) return rcr;       // (the device's share is known after the cut)
         // ---- 3. the scan cut and the tables, straight into the staging area ----
-        uint32_t* base = (uint32_t*)st.host;
+        uint32_t* base = st.host.as<uint32_t>();
         auto cut = [&img, base, data, sizes, n, W](int t, int nt) {
             for (int i = t; i < n; i += nt) {
                 JDevImage& im = img[i];
@@ -1150,33 +1125,26 @@ int ss_jpeg_decode_device_impl(SSJpeg** state, hipStream_t stream, const unsigne
         }
         const size_t bytes = at * 4;
         const size_t plane_slot = 3 * (size_t)((width + 15) / 16 * 16) * ((height + 15) / 16 * 16), planes_bytes = coef ? 0 : plane_slot * n;
-        if (st.dev_cap < bytes) {
-            if (st.dev) { JCHK(hipFree(st.dev)); st.dev = nullptr; st.dev_cap = 0; }
-            const size_t cap = bytes + bytes / 4;
-            JCHK(hipMalloc((void**)&st.dev, cap));
-            st.dev_cap = cap;
-        }
-        if (st.planes_cap < planes_bytes) {
-            if (st.planes) { JCHK(hipFree(st.planes)); st.planes = nullptr; st.planes_cap = 0; }
-            JCHK(hipMalloc((void**)&st.planes, planes_bytes));
-            st.planes_cap = planes_bytes;
-        }
+        if (int rcr = jpeg_slot_reserve(st, in_words * 4, bytes, planes_bytes, err)) return rcr;
+        uint32_t* dev = st.dev.as<uint32_t>();
+        uint32_t* status = st.status_dev.as<uint32_t>();
+        uint8_t* planes = st.planes.as<uint8_t>();
         // ---- 5. one copy, the two entropy kernels, the two kernels of the host stage's path, the status ----
-        JCHK(hipMemcpyAsync(st.dev, st.host, in_words * 4, hipMemcpyHostToDevice, stream));
-        JCHK(hipMemsetAsync(st.dev + tabs_at, 0, tabs_words * 4, stream));
-        JCHK(hipMemsetAsync(st.status_dev, 0xff, (size_t)n * 4, stream));
-        hipLaunchKernelGGL(k_jpeg_huff, dim3(n), dim3(JH_LANES), 0, stream, st.dev, st.status_dev);
-        hipLaunchKernelGGL(k_jpeg_dc, dim3(n), dim3(JH_LANES), 0, stream, st.dev, st.status_dev);
+        SS_HIPCHK(kJpegWho, hipMemcpyAsync(dev, base, in_words * 4, hipMemcpyHostToDevice, stream));
+        SS_HIPCHK(kJpegWho, hipMemsetAsync(dev + tabs_at, 0, tabs_words * 4, stream));
+        SS_HIPCHK(kJpegWho, hipMemsetAsync(status, 0xff, (size_t)n * 4, stream));
+        hipLaunchKernelGGL(k_jpeg_huff, dim3(n), dim3(JH_LANES), 0, stream, dev, status);
+        hipLaunchKernelGGL(k_jpeg_dc, dim3(n), dim3(JH_LANES), 0, stream, dev, status);
         if (!coef) {
-            hipLaunchKernelGGL(k_jpeg_idct, dim3((max_blk + 31) / 32, n), dim3(256), 0, stream, st.dev, st.planes, (long long)plane_slot);
+            hipLaunchKernelGGL(k_jpeg_idct, dim3((max_blk + 31) / 32, n), dim3(256), 0, stream, dev, planes, (long long)plane_slot);
             const int groups = (height * width + 3) / 4;
             const int dwords = (((uintptr_t)d_out | (uintptr_t)out_frame_stride) & 3) == 0;
-            hipLaunchKernelGGL(k_jpeg_pixels, dim3((groups + 255) / 256, n), dim3(256), 0, stream, st.dev, st.planes, (long long)plane_slot, height, width,
+            hipLaunchKernelGGL(k_jpeg_pixels, dim3((groups + 255) / 256, n), dim3(256), 0, stream, dev, planes, (long long)plane_slot, height, width,
                                (uint8_t*)d_out, out_frame_stride, rgb, dwords);
         }
-        JCHK(hipGetLastError());
-        JCHK(hipMemcpyAsync(st.status_host, st.status_dev, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-        JCHK(hipEventRecord(st.ev, stream));
+        SS_HIPCHK(kJpegWho, hipGetLastError());
+        SS_HIPCHK(kJpegWho, hipMemcpyAsync(st.status_host.as(), status, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+        SS_HIPCHK(kJpegWho, hipEventRecord(st.ev, stream));
         st.busy = true;
         st.pending = n;
         S.next ^= 1;
@@ -1190,12 +1158,12 @@ int ss_jpeg_decode_device_impl(SSJpeg** state, hipStream_t stream, const unsigne
         for (int c = 0; c < J.ncomp; ++c) { cbase[c] = tot; tot += (size_t)J.mcux * J.h[c] * J.mcuy * J.v[c] * 64; }
         if (tot > coef_cap) { err = "coefficient buffer too small: " + std::to_string(tot) + " values needed"; return SS_ERR_INVALID; }
         std::vector<uint32_t> tab(blocks + 1), rnd(tiles);
-        JCHK(hipMemcpy(tab.data(), st.dev + im.tab_at, tab.size() * 4, hipMemcpyDeviceToHost));
-        JCHK(hipMemcpy(rnd.data(), st.dev + im.rounds_at, rnd.size() * 4, hipMemcpyDeviceToHost));
+        SS_HIPCHK(kJpegWho, hipMemcpy(tab.data(), dev + im.tab_at, tab.size() * 4, hipMemcpyDeviceToHost));
+        SS_HIPCHK(kJpegWho, hipMemcpy(rnd.data(), dev + im.rounds_at, rnd.size() * 4, hipMemcpyDeviceToHost));
         const size_t ne = tab[blocks];
         if (ne > im.cap) { err = "ss_jpeg_device_coefficients: entry total beyond the capacity"; return SS_ERR_INVALID; }
         std::vector<uint32_t> ent(ne ? ne : 1);
-        if (ne) JCHK(hipMemcpy(ent.data(), st.dev + im.ent_at, ne * 4, hipMemcpyDeviceToHost));
+        if (ne) SS_HIPCHK(kJpegWho, hipMemcpy(ent.data(), dev + im.ent_at, ne * 4, hipMemcpyDeviceToHost));
         S.rounds.assign(rnd.begin(), rnd.end());
         memset(coef, 0, tot * sizeof(short));
         const int bpm = jpeg_bpm(J), hv = J.ncomp == 1 ? 1 : J.h[0] * J.v[0];

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "ss_common.h"
+#include "ss_host.h"
 #include "ss_launch.h"
 #include "ss_jpeg_host.h"
 
@@ -675,71 +676,30 @@ __global__ __launch_bounds__(JENC_STUFF_THREADS) void k_jpegenc_stuff(const uint
 // ---- host: the batch call --------------------------------------------------------------------------------------------------
 struct SSJpegEnc {
     struct Slot {
-        int16_t* dense = nullptr; size_t dense_cap = 0;         // device only: every block's 64 values
-        uint32_t* cnt = nullptr; size_t cnt_cap = 0;            // device only: every block's count
-        uint32_t* totals = nullptr;                             // [64] entries per image
-        uint32_t* h_totals = nullptr;                           // pinned
-        uint32_t* dev = nullptr; size_t dev_cap = 0;            // the stream: every image's block table, then every image's entries
-        void* host = nullptr; size_t host_cap = 0;              // its pinned host mirror (cacheable: the host threads read it)
-        hipEvent_t ev = nullptr;
+        SsBuf<SS_DEVICE> dense;                                 // device only: every block's 64 values
+        SsBuf<SS_DEVICE> cnt;                                   // device only: every block's count
+        SsBuf<SS_DEVICE> totals;                                // [64] entries per image
+        SsBuf<SS_PINNED> h_totals;
+        SsBuf<SS_DEVICE> dev;                                   // the stream: every image's block table, then every image's entries
+        SsBuf<SS_PINNED> host;                                  // its pinned host mirror (cacheable: the host threads read it)
+        SsEvent ev;
     } slot[2];
     int next = 0;
     struct DSlot {                                              // ss_jpeg_encode_batch_device's own two slots (section 13)
-        int16_t* dense = nullptr; size_t dense_cap = 0;
-        uint32_t* cnt = nullptr; size_t cnt_cap = 0;            // k_jpegenc_fdct's counts (written, not used on this path)
-        uint32_t* lens = nullptr; size_t lens_cap = 0;          // every block's bit length
-        uint32_t* small = nullptr;                              // device: bits [64] (64-bit), totals [64], fft [64], ffc [64][64]
-        uint32_t* h_small = nullptr;                            // pinned: bits [64] (64-bit), fft [64]
-        uint32_t* ustream = nullptr; size_t ustream_cap = 0;    // the unstuffed streams, zeroed by every call
-        uint8_t* stuffed = nullptr; size_t stuffed_cap = 0;     // the stuffed scans
-        void* host = nullptr; size_t host_cap = 0;              // their pinned mirror
-        hipEvent_t ev = nullptr;
+        SsBuf<SS_DEVICE> dense;
+        SsBuf<SS_DEVICE> cnt;                                   // k_jpegenc_fdct's counts (written, not used on this path)
+        SsBuf<SS_DEVICE> lens;                                  // every block's bit length
+        SsBuf<SS_DEVICE> small;                                 // bits [64] (64-bit), totals [64], fft [64], ffc [64][64]
+        SsBuf<SS_PINNED> h_small;                               // bits [64] (64-bit), fft [64]
+        SsBuf<SS_DEVICE> ustream;                               // the unstuffed streams, zeroed by every call
+        SsBuf<SS_DEVICE> stuffed;                               // the stuffed scans
+        SsBuf<SS_PINNED> host;                                  // their pinned mirror
+        SsEvent ev;
     } dslot[2];
     int dnext = 0;
 };
 
-void ss_jpeg_enc_free(SSJpegEnc* j)
-{
-    if (!j) return;
-    for (auto& st : j->dslot) {
-        if (st.ev) (void)hipEventDestroy(st.ev);
-        if (st.host) (void)hipHostFree(st.host);
-        if (st.h_small) (void)hipHostFree(st.h_small);
-        if (st.stuffed) (void)hipFree(st.stuffed);
-        if (st.ustream) (void)hipFree(st.ustream);
-        if (st.small) (void)hipFree(st.small);
-        if (st.lens) (void)hipFree(st.lens);
-        if (st.cnt) (void)hipFree(st.cnt);
-        if (st.dense) (void)hipFree(st.dense);
-    }
-    for (auto& st : j->slot) {
-        if (st.ev) (void)hipEventDestroy(st.ev);
-        if (st.host) (void)hipHostFree(st.host);
-        if (st.h_totals) (void)hipHostFree(st.h_totals);
-        if (st.dev) (void)hipFree(st.dev);
-        if (st.totals) (void)hipFree(st.totals);
-        if (st.cnt) (void)hipFree(st.cnt);
-        if (st.dense) (void)hipFree(st.dense);
-    }
-    delete j;
-}
-
-#define JECHK(x)                                                                                             \
-    do {                                                                                                     \
-        hipError_t e_ = (x);                                                                                 \
-        if (e_ != hipSuccess) { err = std::string("ss_jpeg_encode_batch: " #x ": ") + hipGetErrorString(e_); return SS_ERR_HIP; } \
-    } while (0)
-
-template <class T>
-static hipError_t jenc_grow(T*& p, size_t& cap, size_t bytes)
-{
-    if (cap >= bytes) return hipSuccess;
-    if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
-    const size_t want = bytes + bytes / 4;
-    hipError_t e = hipMalloc((void**)&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-}
+void ss_jpeg_enc_free(SSJpegEnc* j) { delete j; }
 
 // The arguments have been checked (ss_api.hip).  Returns an SS_* code, the message in err.
 int ss_jpeg_encode_impl(SSJpegEnc** state, hipStream_t stream, const void* d_in, long long in_frame_stride, int n, int height, int width, int rgb,
@@ -756,41 +716,39 @@ int ss_jpeg_encode_impl(SSJpegEnc** state, hipStream_t stream, const void* d_in,
             for (int k = 0; k < 64; ++k) P.recip[t][k] = (uint32_t)((1ull << 32) / ((uint32_t)P.q[t][k] << 3)) + 1u;
         for (int k = 0; k < 64; ++k) P.zz[kZigzag[k]] = (uint8_t)k;
         SSJpegEnc::Slot& st = S.slot[S.next];
-        if (!st.ev) JECHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
-        if (!st.totals) JECHK(hipMalloc((void**)&st.totals, 64 * sizeof(uint32_t)));
-        if (!st.h_totals) JECHK(hipHostMalloc((void**)&st.h_totals, 64 * sizeof(uint32_t), hipHostMallocDefault));
-        JECHK(jenc_grow(st.dense, st.dense_cap, (size_t)n * nscan * 64 * sizeof(int16_t)));
-        JECHK(jenc_grow(st.cnt, st.cnt_cap, (size_t)n * nscan * sizeof(uint32_t)));
+        const char* const who = "ss_jpeg_encode_batch: ";
+        SS_HIPCHK(who, st.ev.ensure());
+        SS_HIPCHK(who, st.totals.reserve(64 * sizeof(uint32_t), SS_EXACT));
+        SS_HIPCHK(who, st.h_totals.reserve(64 * sizeof(uint32_t), SS_EXACT));
+        SS_HIPCHK(who, st.dense.reserve((size_t)n * nscan * 64 * sizeof(int16_t), SS_QUARTER));
+        SS_HIPCHK(who, st.cnt.reserve((size_t)n * nscan * sizeof(uint32_t), SS_QUARTER));
+        int16_t* dense = st.dense.as<int16_t>();
+        uint32_t *cnt = st.cnt.as<uint32_t>(), *totals = st.totals.as<uint32_t>(), *h_totals = st.h_totals.as<uint32_t>();
         // ---- 1. transform; the entry totals decide the size of everything that follows ----
-        JECHK(hipMemsetAsync(st.totals, 0, n * sizeof(uint32_t), stream));
+        SS_HIPCHK(who, hipMemsetAsync(totals, 0, n * sizeof(uint32_t), stream));
         hipLaunchKernelGGL(k_jpegenc_fdct, dim3((nscan + 31) / 32, n), dim3(256), 0, stream, (const uint8_t*)d_in, in_frame_stride, height, width, rgb, h_samp,
-                           v_samp, shape.mcux, nscan, st.dense, st.cnt, st.totals, P);
-        JECHK(hipGetLastError());
-        JECHK(hipMemcpyAsync(st.h_totals, st.totals, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        JECHK(hipEventRecord(st.ev, stream));
-        JECHK(hipEventSynchronize(st.ev));
+                           v_samp, shape.mcux, nscan, dense, cnt, totals, P);
+        SS_HIPCHK(who, hipGetLastError());
+        SS_HIPCHK(who, hipMemcpyAsync(h_totals, totals, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        SS_HIPCHK(who, hipEventRecord(st.ev, stream));
+        SS_HIPCHK(who, hipEventSynchronize(st.ev));
         size_t entries = 0;
         std::vector<size_t> ent_at(n);
-        for (int i = 0; i < n; ++i) { ent_at[i] = entries; entries += st.h_totals[i]; }
+        for (int i = 0; i < n; ++i) { ent_at[i] = entries; entries += h_totals[i]; }
         const size_t tab_words = (size_t)n * (nscan + 1), bytes = (tab_words + entries) * 4;
-        JECHK(jenc_grow(st.dev, st.dev_cap, bytes));
-        if (st.host_cap < bytes) {
-            if (st.host) { JECHK(hipHostFree(st.host)); st.host = nullptr; st.host_cap = 0; }
-            const size_t cap = bytes + bytes / 4;
-            JECHK(hipHostMalloc(&st.host, cap, hipHostMallocDefault));
-            st.host_cap = cap;
-        }
+        SS_HIPCHK(who, st.dev.reserve(bytes, SS_QUARTER));
+        SS_HIPCHK(who, st.host.reserve(bytes, SS_QUARTER));
+        uint32_t* dev = st.dev.as<uint32_t>();
+        uint32_t* base = st.host.as<uint32_t>();
         // ---- 2. scan + compaction, ONE copy of exactly the used size ----
         const int chunks = nscan < 16 * 2048 ? (nscan + 2047) / 2048 : 16, chunk = (nscan + chunks - 1) / chunks;
-        hipLaunchKernelGGL(k_jpegenc_pack, dim3(chunks, n), dim3(JENC_PACK_THREADS), 0, stream, st.dense, st.cnt, st.totals, st.dev, st.dev + tab_words, nscan,
-                           chunk);
-        JECHK(hipGetLastError());
-        JECHK(hipMemcpyAsync(st.host, st.dev, bytes, hipMemcpyDeviceToHost, stream));
-        JECHK(hipEventRecord(st.ev, stream));
-        JECHK(hipEventSynchronize(st.ev));
+        hipLaunchKernelGGL(k_jpegenc_pack, dim3(chunks, n), dim3(JENC_PACK_THREADS), 0, stream, dense, cnt, totals, dev, dev + tab_words, nscan, chunk);
+        SS_HIPCHK(who, hipGetLastError());
+        SS_HIPCHK(who, hipMemcpyAsync(base, dev, bytes, hipMemcpyDeviceToHost, stream));
+        SS_HIPCHK(who, hipEventRecord(st.ev, stream));
+        SS_HIPCHK(who, hipEventSynchronize(st.ev));
         S.next ^= 1;
         // ---- 3. the entropy stage, whole images per thread ----
-        const uint32_t* base = (const uint32_t*)st.host;
         std::vector<char> bad(n, 0);
         auto encode = [&](int t, int nt) {
             for (int i = t; i < n; i += nt) {
@@ -820,19 +778,14 @@ static const JEncHuffDev kEncDev = [] {
     return d;
 }();
 
-#define JDCHK(x)                                                                                             \
-    do {                                                                                                     \
-        hipError_t e_ = (x);                                                                                 \
-        if (e_ != hipSuccess) { err = std::string(who) + ": " #x ": " + hipGetErrorString(e_); return SS_ERR_HIP; } \
-    } while (0)
-
+// (`who` in what follows: the entry's name with its ": ")
 static int jenc_dslot(SSJpegEnc::DSlot& st, const char* who, size_t blocks, std::string& err)
 {
-    if (!st.ev) JDCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
-    if (!st.small) JDCHK(hipMalloc((void**)&st.small, (256 + 64 * JENC_STUFF_CHUNKS) * sizeof(uint32_t)));
-    if (!st.h_small) JDCHK(hipHostMalloc((void**)&st.h_small, 192 * sizeof(uint32_t), hipHostMallocDefault));
-    JDCHK(jenc_grow(st.dense, st.dense_cap, blocks * 64 * sizeof(int16_t)));
-    JDCHK(jenc_grow(st.lens, st.lens_cap, blocks * sizeof(uint32_t)));
+    SS_HIPCHK(who, st.ev.ensure());
+    SS_HIPCHK(who, st.small.reserve((256 + 64 * JENC_STUFF_CHUNKS) * sizeof(uint32_t), SS_EXACT));
+    SS_HIPCHK(who, st.h_small.reserve(192 * sizeof(uint32_t), SS_EXACT));
+    SS_HIPCHK(who, st.dense.reserve(blocks * 64 * sizeof(int16_t), SS_QUARTER));
+    SS_HIPCHK(who, st.lens.reserve(blocks * sizeof(uint32_t), SS_QUARTER));
     return SS_OK;
 }
 
@@ -843,57 +796,55 @@ static int jenc_entropy_device(SSJpegEnc::DSlot& st, hipStream_t stream, const c
 {
     const int nscan = shape.nscan;
     const JEncGrid g{shape.hm, shape.vm, shape.mcux, nscan, shape.bw[0], shape.bh[0]};
-    unsigned long long* d_bits = (unsigned long long*)st.small;
-    uint32_t *d_fft = st.small + 192, *d_ffc = st.small + 256;
-    const unsigned long long* h_bits = (const unsigned long long*)st.h_small;
-    const uint32_t* h_fft = st.h_small + 128;
+    unsigned long long* d_bits = st.small.as<unsigned long long>();
+    uint32_t *d_fft = st.small.as<uint32_t>() + 192, *d_ffc = st.small.as<uint32_t>() + 256;
+    const unsigned long long* h_bits = st.h_small.as<unsigned long long>();
+    uint32_t* h_fft = st.h_small.as<uint32_t>() + 128;
+    const int16_t* dense = st.dense.as<int16_t>();
+    uint32_t* lens = st.lens.as<uint32_t>();
     // ---- 1. every block's bit length; the images' bit totals decide the size of the unstuffed stream ----
-    JDCHK(hipMemsetAsync(d_bits, 0, n * sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(k_jpegenc_hlen, dim3((nscan + JENC_HLEN_BLOCKS - 1) / JENC_HLEN_BLOCKS, n), dim3(JENC_HLEN_THREADS), 0, stream, st.dense, g, st.lens, d_bits,
-                       kEncDev);
-    JDCHK(hipGetLastError());
-    JDCHK(hipMemcpyAsync(st.h_small, d_bits, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    JDCHK(hipEventRecord(st.ev, stream));
-    JDCHK(hipEventSynchronize(st.ev));
+    SS_HIPCHK(who, hipMemsetAsync(d_bits, 0, n * sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(k_jpegenc_hlen, dim3((nscan + JENC_HLEN_BLOCKS - 1) / JENC_HLEN_BLOCKS, n), dim3(JENC_HLEN_THREADS), 0, stream, dense, g, lens, d_bits, kEncDev);
+    SS_HIPCHK(who, hipGetLastError());
+    SS_HIPCHK(who, hipMemcpyAsync(st.h_small.as(), d_bits, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    SS_HIPCHK(who, hipEventRecord(st.ev, stream));
+    SS_HIPCHK(who, hipEventSynchronize(st.ev));
     size_t words = 0, most = 0;
     for (int i = 0; i < n; ++i) {
         words += jenc_image_words(h_bits[i]);
         const size_t b = (size_t)((h_bits[i] + 7) >> 3);
         if (b > most) most = b;
     }
-    JDCHK(jenc_grow(st.ustream, st.ustream_cap, words * 4));
+    SS_HIPCHK(who, st.ustream.reserve(words * 4, SS_QUARTER));
+    uint32_t* ustream = st.ustream.as<uint32_t>();
     // ---- 2. scan + write into the zeroed stream, the FF bytes counted; their totals decide the size of everything that follows ----
-    JDCHK(hipMemsetAsync(st.ustream, 0, words * 4, stream));
-    JDCHK(hipMemsetAsync(d_fft, 0, n * sizeof(uint32_t), stream));
+    SS_HIPCHK(who, hipMemsetAsync(ustream, 0, words * 4, stream));
+    SS_HIPCHK(who, hipMemsetAsync(d_fft, 0, n * sizeof(uint32_t), stream));
     const int chunks = nscan < JENC_HW_CHUNKS * JENC_HW_TILE ? (nscan + JENC_HW_TILE - 1) / JENC_HW_TILE : JENC_HW_CHUNKS, chunk = (nscan + chunks - 1) / chunks;
-    hipLaunchKernelGGL(k_jpegenc_hwrite, dim3(chunks, n), dim3(JENC_HW_THREADS), 0, stream, st.dense, st.lens, d_bits, st.ustream, g, chunk, kEncDev);
-    JDCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_jpegenc_hwrite, dim3(chunks, n), dim3(JENC_HW_THREADS), 0, stream, dense, lens, d_bits, ustream, g, chunk, kEncDev);
+    SS_HIPCHK(who, hipGetLastError());
     const size_t tiles = (most + JENC_STUFF_TILE - 1) / JENC_STUFF_TILE, per = (tiles + JENC_STUFF_CHUNKS - 1) / JENC_STUFF_CHUNKS;
     const uint32_t bchunk = (uint32_t)(per * JENC_STUFF_TILE);
     const int bchunks = (int)((most + bchunk - 1) / bchunk);
-    hipLaunchKernelGGL(k_jpegenc_ffcount, dim3(bchunks, n), dim3(JENC_STUFF_THREADS), 0, stream, st.ustream, d_bits, d_ffc, d_fft, bchunk);
-    JDCHK(hipGetLastError());
-    JDCHK(hipMemcpyAsync(st.h_small + 128, d_fft, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    JDCHK(hipEventRecord(st.ev, stream));
-    JDCHK(hipEventSynchronize(st.ev));
+    hipLaunchKernelGGL(k_jpegenc_ffcount, dim3(bchunks, n), dim3(JENC_STUFF_THREADS), 0, stream, ustream, d_bits, d_ffc, d_fft, bchunk);
+    SS_HIPCHK(who, hipGetLastError());
+    SS_HIPCHK(who, hipMemcpyAsync(h_fft, d_fft, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    SS_HIPCHK(who, hipEventRecord(st.ev, stream));
+    SS_HIPCHK(who, hipEventSynchronize(st.ev));
     size_t bytes = 0;
     std::vector<size_t> at(n);
     for (int i = 0; i < n; ++i) { at[i] = bytes; bytes += jenc_image_room(h_bits[i], h_fft[i]); }
-    JDCHK(jenc_grow(st.stuffed, st.stuffed_cap, bytes));
-    if (st.host_cap < bytes) {
-        if (st.host) { JDCHK(hipHostFree(st.host)); st.host = nullptr; st.host_cap = 0; }
-        const size_t cap = bytes + bytes / 4;
-        JDCHK(hipHostMalloc(&st.host, cap, hipHostMallocDefault));
-        st.host_cap = cap;
-    }
+    SS_HIPCHK(who, st.stuffed.reserve(bytes, SS_QUARTER));
+    SS_HIPCHK(who, st.host.reserve(bytes, SS_QUARTER));
+    uint8_t* stuffed = st.stuffed.as<uint8_t>();
+    uint8_t* base = st.host.as<uint8_t>();
     // ---- 3. stuffing, ONE copy of exactly the used size ----
-    hipLaunchKernelGGL(k_jpegenc_stuff, dim3(bchunks, n), dim3(JENC_STUFF_THREADS), 0, stream, st.ustream, d_bits, d_ffc, d_fft, st.stuffed, bchunk);
-    JDCHK(hipGetLastError());
-    JDCHK(hipMemcpyAsync(st.host, st.stuffed, bytes, hipMemcpyDeviceToHost, stream));
-    JDCHK(hipEventRecord(st.ev, stream));
-    JDCHK(hipEventSynchronize(st.ev));
+    hipLaunchKernelGGL(k_jpegenc_stuff, dim3(bchunks, n), dim3(JENC_STUFF_THREADS), 0, stream, ustream, d_bits, d_ffc, d_fft, stuffed, bchunk);
+    SS_HIPCHK(who, hipGetLastError());
+    SS_HIPCHK(who, hipMemcpyAsync(base, stuffed, bytes, hipMemcpyDeviceToHost, stream));
+    SS_HIPCHK(who, hipEventRecord(st.ev, stream));
+    SS_HIPCHK(who, hipEventSynchronize(st.ev));
     // ---- 4. header, scan, EOI: whole images per thread ----
-    const uint8_t* base = (const uint8_t*)st.host;
     auto write = [&](int t, int nt) {
         for (int i = t; i < n; i += nt) {
             const size_t len = (size_t)((h_bits[i] + 7) >> 3) + h_fft[i];
@@ -904,7 +855,7 @@ static int jenc_entropy_device(SSJpegEnc::DSlot& st, hipStream_t stream, const c
             out_size[i] = (size_t)(p - out[i]);
         }
     };
-    if (!run_threads(threads < n ? threads : n, write)) { err = std::string(who) + ": host copy failed"; return SS_ERR_INVALID; }
+    if (!run_threads(threads < n ? threads : n, write)) { err = std::string(who) + "host copy failed"; return SS_ERR_INVALID; }
     return SS_OK;
 }
 
@@ -912,7 +863,7 @@ static int jenc_entropy_device(SSJpegEnc::DSlot& st, hipStream_t stream, const c
 int ss_jpeg_encode_device_impl(SSJpegEnc** state, hipStream_t stream, const void* d_in, long long in_frame_stride, int n, int height, int width, int rgb,
                                int quality, int h_samp, int v_samp, int threads, unsigned char* const* out, size_t* out_size, std::string& err)
 {
-    const char* who = "ss_jpeg_encode_batch_device";
+    const char* who = "ss_jpeg_encode_batch_device: ";
     try {
         if (!*state) *state = new SSJpegEnc();
         SSJpegEnc& S = **state;
@@ -925,16 +876,16 @@ int ss_jpeg_encode_device_impl(SSJpegEnc** state, hipStream_t stream, const void
         for (int k = 0; k < 64; ++k) P.zz[kZigzag[k]] = (uint8_t)k;
         SSJpegEnc::DSlot& st = S.dslot[S.dnext];
         if (const int rc = jenc_dslot(st, who, (size_t)n * nscan, err)) return rc;
-        JDCHK(jenc_grow(st.cnt, st.cnt_cap, (size_t)n * nscan * sizeof(uint32_t)));
-        uint32_t* totals = st.small + 128;                       // (k_jpegenc_fdct's entry totals: written, not used on this path)
-        JDCHK(hipMemsetAsync(totals, 0, n * sizeof(uint32_t), stream));
+        SS_HIPCHK(who, st.cnt.reserve((size_t)n * nscan * sizeof(uint32_t), SS_QUARTER));
+        uint32_t* totals = st.small.as<uint32_t>() + 128;        // (k_jpegenc_fdct's entry totals: written, not used on this path)
+        SS_HIPCHK(who, hipMemsetAsync(totals, 0, n * sizeof(uint32_t), stream));
         hipLaunchKernelGGL(k_jpegenc_fdct, dim3((nscan + 31) / 32, n), dim3(256), 0, stream, (const uint8_t*)d_in, in_frame_stride, height, width, rgb, h_samp,
-                           v_samp, shape.mcux, nscan, st.dense, st.cnt, totals, P);
-        JDCHK(hipGetLastError());
+                           v_samp, shape.mcux, nscan, st.dense.as<int16_t>(), st.cnt.as<uint32_t>(), totals, P);
+        SS_HIPCHK(who, hipGetLastError());
         S.dnext ^= 1;
         return jenc_entropy_device(st, stream, who, n, shape, P.q, threads, out, out_size, err);
     } catch (...) {
-        err = std::string(who) + ": out of memory";
+        err = std::string(who) + "out of memory";
         return SS_ERR_INVALID;
     }
 }
@@ -944,7 +895,7 @@ int ss_jpeg_encode_device_impl(SSJpegEnc** state, hipStream_t stream, const void
 int ss_jpeg_entropy_encode_device_impl(SSJpegEnc** state, hipStream_t stream, const short* coef, int quality, int width, int height, int h_samp, int v_samp,
                                        unsigned char* out, size_t* out_size, std::string& err)
 {
-    const char* who = "ss_jpeg_entropy_encode_device";
+    const char* who = "ss_jpeg_entropy_encode_device: ";
     try {
         if (!*state) *state = new SSJpegEnc();
         SSJpegEnc& S = **state;
@@ -965,15 +916,15 @@ int ss_jpeg_entropy_encode_device_impl(SSJpegEnc** state, hipStream_t stream, co
                     bool ok = jenc_category(c[0] - pred[comp]) <= 11;
                     pred[comp] = c[0];
                     for (int k = 0; k < 64; ++k) { o[k] = c[kZigzag[k]]; if (k && jenc_category(o[k]) > 10) ok = false; }
-                    if (!ok) { err = std::string(who) + ": a coefficient beyond the baseline categories (DC difference 11 bits, AC 10 bits)"; return SS_ERR_INVALID; }
+                    if (!ok) { err = std::string(who) + "a coefficient beyond the baseline categories (DC difference 11 bits, AC 10 bits)"; return SS_ERR_INVALID; }
                 }
         SSJpegEnc::DSlot& st = S.dslot[S.dnext];
         if (const int rc = jenc_dslot(st, who, (size_t)shape.nscan, err)) return rc;
-        JDCHK(hipMemcpyAsync(st.dense, dense.data(), dense.size() * sizeof(int16_t), hipMemcpyHostToDevice, stream));
+        SS_HIPCHK(who, hipMemcpyAsync(st.dense.as(), dense.data(), dense.size() * sizeof(int16_t), hipMemcpyHostToDevice, stream));
         S.dnext ^= 1;
         return jenc_entropy_device(st, stream, who, 1, shape, q, 1, &out, out_size, err);      // (its first wait is behind the upload: `dense` outlives it)
     } catch (...) {
-        err = std::string(who) + ": out of memory";
+        err = std::string(who) + "out of memory";
         return SS_ERR_INVALID;
     }
 }

@@ -1,6 +1,7 @@
 // ss_launch.h — what ss_api.hip calls in the other translation units, declared once with the definitions' parameter names:
-// the kernel launchers and the host-side state of the JPEG, GSI and MOT stages.  ss_api.hip and every file that defines one of
+// the kernel launchers and the host-side state of the JPEG, GSI, MOT and AFLink stages.  ss_api.hip and every file that defines one of
 // these include it, so each definition is compiled next to its declaration.  C++ linkage: none of this is part of the C ABI.
+// (What those states are made of, the owning buffers and the HIP check of the *_impl functions, is in ss_host.h.)
 #pragma once
 #include <string>
 #include "ss_common.h"

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 #include "ss_common.h"
+#include "ss_host.h"
 #include "ss_launch.h"
 #include "ss_lsap.h"
 
@@ -391,26 +392,18 @@ __global__ __launch_bounds__(MOT_ID_THREADS) void k_id_solve(const MotArgs a)
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
 struct SSMot {
-    void* host = nullptr; size_t host_cap = 0;          // pinned: the upload image, then the download image
-    void* dev = nullptr; size_t dev_cap = 0;            // upload image | prev_t | pot | download image
-    double* sim = nullptr; size_t sim_cap = 0;          // doubles: S and si, grown when a call needs more
-    double* spill = nullptr; size_t spill_cap = 0;      // doubles: k_mot_clear's matrices that do not fit the LDS
+    SsBuf<SS_PINNED> host;                              // the upload image, then the download image
+    SsBuf<SS_DEVICE> dev;                               // upload image | prev_t | pot | download image
+    SsBuf<SS_DEVICE> sim;                               // S and si, grown when a call needs more
+    SsBuf<SS_DEVICE> spill;                             // k_mot_clear's matrices that do not fit the LDS
     hipStream_t side = nullptr;                         // k_mot_clear's stream
-    hipEvent_t ev = nullptr, ev_sim = nullptr, ev_clear = nullptr;
+    SsEvent ev, ev_sim, ev_clear;
     bool attr = false;
 };
 
 void ss_mot_free(SSMot* m)
 {
-    if (!m) return;
-    if (m->ev) (void)hipEventDestroy(m->ev);
-    if (m->ev_sim) (void)hipEventDestroy(m->ev_sim);
-    if (m->ev_clear) (void)hipEventDestroy(m->ev_clear);
-    if (m->side) (void)hipStreamDestroy(m->side);
-    if (m->host) (void)hipHostFree(m->host);
-    if (m->dev) (void)hipFree(m->dev);
-    if (m->sim) (void)hipFree(m->sim);
-    if (m->spill) (void)hipFree(m->spill);
+    if (m && m->side) (void)hipStreamDestroy(m->side);
     delete m;
 }
 
@@ -507,66 +500,47 @@ int ss_mot_identity_check_impl(int n_pairs, const int* frame_off, const int* gt_
                      n_tr_ids, thr, err);
 }
 
-#define MCHK(x)                                                                                     \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) { err = std::string(MOT_WHO #x ": ") + hipGetErrorString(e_); return SS_ERR_HIP; } \
-    } while (0)
-
-#define MOT_WHO "ss_mot_eval: "
-static size_t mot_up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 int ss_mot_eval_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id,
                      const int* tr_id, const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
                      int* hota_idx, double* hota_s, int* clear_idx, double* clear_s, double* ga, std::string& err)
 {
+    const char* const who = "ss_mot_eval: ";
     if (!pm) { err = "ss_mot_eval: null context"; return SS_ERR_INVALID; }
     const int F = frame_off[n_pairs];
     const size_t Ng = (size_t)gt_off[F], Nt = (size_t)tr_off[F];
     size_t nG = 0, nT = 0;
     for (int p = 0; p < n_pairs; ++p) { nG += n_gt_ids[p]; nT += n_tr_ids[p]; }
     // ---- the layout of the upload image, the work area and the download image ----
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at = mot_up16(at + bytes); return o; };
-    const size_t o_gbox = take(Ng * 4 * sizeof(double)), o_tbox = take(Nt * 4 * sizeof(double));
-    const size_t o_soff = take((size_t)(F + 1) * sizeof(long long)), o_poff = take((size_t)(n_pairs + 1) * sizeof(long long));
-    const size_t o_goff = take((size_t)(F + 1) * sizeof(int)), o_toff = take((size_t)(F + 1) * sizeof(int));
-    const size_t o_gid = take(Ng * sizeof(int)), o_tid = take(Nt * sizeof(int));
-    const size_t o_foff = take((size_t)(n_pairs + 1) * sizeof(int)), o_pairof = take((size_t)F * sizeof(int)), o_ntid = take((size_t)n_pairs * sizeof(int));
-    const size_t o_gbase = take((size_t)(n_pairs + 1) * sizeof(int)), o_tbase = take((size_t)(n_pairs + 1) * sizeof(int));
-    const size_t o_gidoff = take((nG + 1) * sizeof(int)), o_gidrows = take(Ng * sizeof(int)), o_gidpair = take(nG * sizeof(int));
-    const size_t o_rowframe = take(Ng * sizeof(int)), o_cntt = take(nT * sizeof(int));
-    const size_t up = at;
-    const size_t o_prev = take(nG * sizeof(int2));
+    SsLayout lay;
+    const size_t o_gbox = lay.take(Ng * 4 * sizeof(double)), o_tbox = lay.take(Nt * 4 * sizeof(double));
+    const size_t o_soff = lay.take((size_t)(F + 1) * sizeof(long long)), o_poff = lay.take((size_t)(n_pairs + 1) * sizeof(long long));
+    const size_t o_goff = lay.take((size_t)(F + 1) * sizeof(int)), o_toff = lay.take((size_t)(F + 1) * sizeof(int));
+    const size_t o_gid = lay.take(Ng * sizeof(int)), o_tid = lay.take(Nt * sizeof(int));
+    const size_t o_foff = lay.take((size_t)(n_pairs + 1) * sizeof(int)), o_pairof = lay.take((size_t)F * sizeof(int)), o_ntid = lay.take((size_t)n_pairs * sizeof(int));
+    const size_t o_gbase = lay.take((size_t)(n_pairs + 1) * sizeof(int)), o_tbase = lay.take((size_t)(n_pairs + 1) * sizeof(int));
+    const size_t o_gidoff = lay.take((nG + 1) * sizeof(int)), o_gidrows = lay.take(Ng * sizeof(int)), o_gidpair = lay.take(nG * sizeof(int));
+    const size_t o_rowframe = lay.take(Ng * sizeof(int)), o_cntt = lay.take(nT * sizeof(int));
+    const size_t up = lay.at;
+    const size_t o_prev = lay.take(nG * sizeof(int2));
     size_t id_cells = 0;
     for (int p = 0; p < n_pairs; ++p) id_cells += (size_t)n_gt_ids[p] * n_tr_ids[p];
-    const size_t o_pot = take(id_cells * sizeof(double));
-    const size_t o_hs = take(Ng * sizeof(double)), o_cs = take(Ng * sizeof(double));
-    const size_t o_hi = take(Ng * sizeof(int)), o_ci = take(Ng * sizeof(int)), o_err = take(sizeof(int));
-    const size_t total = at;
+    const size_t o_pot = lay.take(id_cells * sizeof(double));
+    const size_t o_hs = lay.take(Ng * sizeof(double)), o_cs = lay.take(Ng * sizeof(double));
+    const size_t o_hi = lay.take(Ng * sizeof(int)), o_ci = lay.take(Ng * sizeof(int)), o_err = lay.take(sizeof(int));
+    const size_t total = lay.at;
     const size_t down_from = ga ? o_pot : o_hs, down = total - down_from;
     const size_t host_need = up + down;
 
     if (!*pm) *pm = new SSMot();
     SSMot& m = **pm;
-    if (!m.ev) MCHK(hipEventCreateWithFlags(&m.ev, hipEventDisableTiming));
-    if (!m.ev_sim) MCHK(hipEventCreateWithFlags(&m.ev_sim, hipEventDisableTiming));
-    if (!m.ev_clear) MCHK(hipEventCreateWithFlags(&m.ev_clear, hipEventDisableTiming));
-    if (!m.side) MCHK(hipStreamCreateWithFlags(&m.side, hipStreamNonBlocking));
-    if (m.host_cap < host_need) {
-        if (m.host) { MCHK(hipHostFree(m.host)); m.host = nullptr; m.host_cap = 0; }
-        const size_t cap = host_need + host_need / 4;
-        MCHK(hipHostMalloc(&m.host, cap, hipHostMallocDefault));
-        m.host_cap = cap;
-    }
-    if (m.dev_cap < total) {
-        if (m.dev) { MCHK(hipFree(m.dev)); m.dev = nullptr; m.dev_cap = 0; }
-        const size_t cap = total + total / 4;
-        MCHK(hipMalloc(&m.dev, cap));
-        m.dev_cap = cap;
-    }
+    SS_HIPCHK(who, m.ev.ensure());
+    SS_HIPCHK(who, m.ev_sim.ensure());
+    SS_HIPCHK(who, m.ev_clear.ensure());
+    if (!m.side) SS_HIPCHK(who, hipStreamCreateWithFlags(&m.side, hipStreamNonBlocking));
+    SS_HIPCHK(who, m.host.reserve(host_need, SS_QUARTER));
+    SS_HIPCHK(who, m.dev.reserve(total, SS_QUARTER));
     // ---- the upload image ----
-    char* h = (char*)m.host;
+    char* h = m.host.as();
     memcpy(h + o_gbox, gt_box, Ng * 4 * sizeof(double));
     memcpy(h + o_tbox, tr_box, Nt * 4 * sizeof(double));
     memcpy(h + o_goff, gt_off, (size_t)(F + 1) * sizeof(int));
@@ -607,24 +581,16 @@ int ss_mot_eval_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int* fra
             for (int r = gt_off[frame_off[p]]; r < gt_off[frame_off[p + 1]]; ++r) h_gidrows[fill[h_gbase[p] + gt_id[r]]++] = r;      // rows come by frame
     }
     // ---- scratch of the context ----
-    if (m.sim_cap < (size_t)sim_cells * 2) {
-        if (m.sim) { MCHK(hipFree(m.sim)); m.sim = nullptr; m.sim_cap = 0; }
-        MCHK(hipMalloc((void**)&m.sim, (size_t)sim_cells * 2 * sizeof(double)));
-        m.sim_cap = (size_t)sim_cells * 2;
-    }
+    SS_HIPCHK(who, m.sim.reserve((size_t)sim_cells * 2 * sizeof(double), SS_EXACT));
     const int lds_cells = (int)std::min<long long>(max_cells, MOT_LDS_CELLS);
     const long long spill_cells = max_cells > MOT_LDS_CELLS ? max_cells : 0;
-    if (m.spill_cap < (size_t)spill_cells * n_pairs) {
-        if (m.spill) { MCHK(hipFree(m.spill)); m.spill = nullptr; m.spill_cap = 0; }
-        MCHK(hipMalloc((void**)&m.spill, (size_t)spill_cells * n_pairs * sizeof(double)));
-        m.spill_cap = (size_t)spill_cells * n_pairs;
-    }
+    SS_HIPCHK(who, m.spill.reserve((size_t)spill_cells * n_pairs * sizeof(double), SS_EXACT));
     if (!m.attr) {
-        MCHK(hipFuncSetAttribute((const void*)k_mot_hota, hipFuncAttributeMaxDynamicSharedMemorySize, MOT_LDS_CELLS * (int)sizeof(double)));
-        MCHK(hipFuncSetAttribute((const void*)k_mot_clear, hipFuncAttributeMaxDynamicSharedMemorySize, MOT_LDS_CELLS * (int)sizeof(double)));
+        SS_HIPCHK(who, hipFuncSetAttribute((const void*)k_mot_hota, hipFuncAttributeMaxDynamicSharedMemorySize, MOT_LDS_CELLS * (int)sizeof(double)));
+        SS_HIPCHK(who, hipFuncSetAttribute((const void*)k_mot_clear, hipFuncAttributeMaxDynamicSharedMemorySize, MOT_LDS_CELLS * (int)sizeof(double)));
         m.attr = true;
     }
-    char* d = (char*)m.dev;
+    char* d = m.dev.as();
     MotArgs a;
     a.gt_box = (const double*)(d + o_gbox); a.tr_box = (const double*)(d + o_tbox);
     a.s_off = (const long long*)(d + o_soff); a.pot_off = (const long long*)(d + o_poff);
@@ -633,37 +599,37 @@ int ss_mot_eval_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int* fra
     a.gbase = (const int*)(d + o_gbase); a.tbase = (const int*)(d + o_tbase);
     a.gid_off = (const int*)(d + o_gidoff); a.gid_rows = (const int*)(d + o_gidrows); a.gid_pair = (const int*)(d + o_gidpair);
     a.row_frame = (const int*)(d + o_rowframe); a.cnt_t = (const int*)(d + o_cntt);
-    a.S = m.sim; a.si = m.sim + sim_cells;
+    a.S = m.sim.as<double>(); a.si = a.S + sim_cells;
     a.pot = (double*)(d + o_pot); a.prev_t = (int2*)(d + o_prev);
-    a.clear_spill = spill_cells ? m.spill : nullptr; a.spill_cells = spill_cells;
+    a.clear_spill = spill_cells ? m.spill.as<double>() : nullptr; a.spill_cells = spill_cells;
     a.hota_idx = (int*)(d + o_hi); a.clear_idx = (int*)(d + o_ci); a.hota_s = (double*)(d + o_hs); a.clear_s = (double*)(d + o_cs);
     a.err = (int*)(d + o_err);
     a.lds_cells = lds_cells; a.n_gids = (int)nG; a.thr = thr;
 
-    MCHK(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
-    if (o_hs > o_prev) MCHK(hipMemsetAsync(d + o_prev, 0, o_hs - o_prev, stream));        // prev_t (stamp 0: none) and pot
-    MCHK(hipMemsetAsync(d + o_err, 0, sizeof(int), stream));
+    SS_HIPCHK(who, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
+    if (o_hs > o_prev) SS_HIPCHK(who, hipMemsetAsync(d + o_prev, 0, o_hs - o_prev, stream));        // prev_t (stamp 0: none) and pot
+    SS_HIPCHK(who, hipMemsetAsync(d + o_err, 0, sizeof(int), stream));
     if (F > 0 && Ng > 0) {
         if (sim_cells > 0) {
             hipLaunchKernelGGL(k_mot_sim, dim3((unsigned)F), dim3(256), 0, stream, a);
-            MCHK(hipGetLastError());
+            SS_HIPCHK(who, hipGetLastError());
         }
-        MCHK(hipEventRecord(m.ev_sim, stream));
-        MCHK(hipStreamWaitEvent(m.side, m.ev_sim, 0));
+        SS_HIPCHK(who, hipEventRecord(m.ev_sim, stream));
+        SS_HIPCHK(who, hipStreamWaitEvent(m.side, m.ev_sim, 0));
         hipLaunchKernelGGL(k_mot_clear, dim3((unsigned)n_pairs), dim3(64), (size_t)lds_cells * sizeof(double), m.side, a);
-        MCHK(hipGetLastError());
-        MCHK(hipEventRecord(m.ev_clear, m.side));
+        SS_HIPCHK(who, hipGetLastError());
+        SS_HIPCHK(who, hipEventRecord(m.ev_clear, m.side));
         if (sim_cells > 0 && nG > 0) {
             hipLaunchKernelGGL(k_mot_align, dim3((unsigned)((nG + 3) / 4)), dim3(256), 0, stream, a);
-            MCHK(hipGetLastError());
+            SS_HIPCHK(who, hipGetLastError());
         }
         hipLaunchKernelGGL(k_mot_hota, dim3((unsigned)F), dim3(64), (size_t)lds_cells * sizeof(double), stream, a);
-        MCHK(hipGetLastError());
-        MCHK(hipStreamWaitEvent(stream, m.ev_clear, 0));
+        SS_HIPCHK(who, hipGetLastError());
+        SS_HIPCHK(who, hipStreamWaitEvent(stream, m.ev_clear, 0));
     }
-    MCHK(hipMemcpyAsync(h + up, d + down_from, down, hipMemcpyDeviceToHost, stream));
-    MCHK(hipEventRecord(m.ev, stream));
-    MCHK(hipEventSynchronize(m.ev));
+    SS_HIPCHK(who, hipMemcpyAsync(h + up, d + down_from, down, hipMemcpyDeviceToHost, stream));
+    SS_HIPCHK(who, hipEventRecord(m.ev, stream));
+    SS_HIPCHK(who, hipEventSynchronize(m.ev));
     const char* hd = h + up - down_from;                 // hd + o_x is field x of the download image
     const int bad = *(const int*)(hd + o_err);
     if (bad) {
@@ -679,51 +645,38 @@ int ss_mot_eval_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int* fra
     return SS_OK;
 }
 
-#undef MOT_WHO
-#define MOT_WHO "ss_mot_identity: "
-
 // The identity metrics' counts and matching.  The staging areas are the context's, shared with ss_mot_eval (a call owns them until
 // its event has passed): upload image | pot | download image (gt_to_tr, idtp), pot downloaded with it when the caller wants it.
 int ss_mot_identity_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int* frame_off, const int* gt_off, const int* tr_off, const int* gt_id,
                          const int* tr_id, const double* gt_box, const double* tr_box, const int* n_gt_ids, const int* n_tr_ids, double thr,
                          int* idtp, int* gt_to_tr, int* pot, std::string& err)
 {
-    if (!pm) { err = MOT_WHO "null context"; return SS_ERR_INVALID; }
+    const char* const who = "ss_mot_identity: ";
+    if (!pm) { err = "ss_mot_identity: null context"; return SS_ERR_INVALID; }
     const int F = frame_off[n_pairs];
     const size_t Ng = (size_t)gt_off[F], Nt = (size_t)tr_off[F];
     size_t nG = 0, id_cells = 0;
     for (int p = 0; p < n_pairs; ++p) { nG += n_gt_ids[p]; id_cells += (size_t)n_gt_ids[p] * n_tr_ids[p]; }
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at = mot_up16(at + bytes); return o; };
-    const size_t o_gbox = take(Ng * 4 * sizeof(double)), o_tbox = take(Nt * 4 * sizeof(double));
-    const size_t o_poff = take((size_t)(n_pairs + 1) * sizeof(long long));
-    const size_t o_goff = take((size_t)(F + 1) * sizeof(int)), o_toff = take((size_t)(F + 1) * sizeof(int));
-    const size_t o_gid = take(Ng * sizeof(int)), o_tid = take(Nt * sizeof(int));
-    const size_t o_pairof = take((size_t)F * sizeof(int)), o_ngid = take((size_t)n_pairs * sizeof(int)), o_ntid = take((size_t)n_pairs * sizeof(int));
-    const size_t o_gbase = take((size_t)(n_pairs + 1) * sizeof(int));
-    const size_t up = at;
-    const size_t o_pot = take(id_cells * sizeof(unsigned));
-    const size_t o_match = take(nG * sizeof(int)), o_tp = take((size_t)n_pairs * sizeof(int));
-    const size_t total = at;
+    SsLayout lay;
+    const size_t o_gbox = lay.take(Ng * 4 * sizeof(double)), o_tbox = lay.take(Nt * 4 * sizeof(double));
+    const size_t o_poff = lay.take((size_t)(n_pairs + 1) * sizeof(long long));
+    const size_t o_goff = lay.take((size_t)(F + 1) * sizeof(int)), o_toff = lay.take((size_t)(F + 1) * sizeof(int));
+    const size_t o_gid = lay.take(Ng * sizeof(int)), o_tid = lay.take(Nt * sizeof(int));
+    const size_t o_pairof = lay.take((size_t)F * sizeof(int)), o_ngid = lay.take((size_t)n_pairs * sizeof(int)), o_ntid = lay.take((size_t)n_pairs * sizeof(int));
+    const size_t o_gbase = lay.take((size_t)(n_pairs + 1) * sizeof(int));
+    const size_t up = lay.at;
+    const size_t o_pot = lay.take(id_cells * sizeof(unsigned));
+    const size_t o_match = lay.take(nG * sizeof(int)), o_tp = lay.take((size_t)n_pairs * sizeof(int));
+    const size_t total = lay.at;
     const size_t down_from = pot ? o_pot : o_match, down = total - down_from;
     const size_t host_need = up + down;
 
     if (!*pm) *pm = new SSMot();
     SSMot& m = **pm;
-    if (!m.ev) MCHK(hipEventCreateWithFlags(&m.ev, hipEventDisableTiming));
-    if (m.host_cap < host_need) {
-        if (m.host) { MCHK(hipHostFree(m.host)); m.host = nullptr; m.host_cap = 0; }
-        const size_t cap = host_need + host_need / 4;
-        MCHK(hipHostMalloc(&m.host, cap, hipHostMallocDefault));
-        m.host_cap = cap;
-    }
-    if (m.dev_cap < total) {
-        if (m.dev) { MCHK(hipFree(m.dev)); m.dev = nullptr; m.dev_cap = 0; }
-        const size_t cap = total + total / 4;
-        MCHK(hipMalloc(&m.dev, cap));
-        m.dev_cap = cap;
-    }
-    char* h = (char*)m.host;
+    SS_HIPCHK(who, m.ev.ensure());
+    SS_HIPCHK(who, m.host.reserve(host_need, SS_QUARTER));
+    SS_HIPCHK(who, m.dev.reserve(total, SS_QUARTER));
+    char* h = m.host.as();
     memcpy(h + o_gbox, gt_box, Ng * 4 * sizeof(double));
     memcpy(h + o_tbox, tr_box, Nt * 4 * sizeof(double));
     memcpy(h + o_goff, gt_off, (size_t)(F + 1) * sizeof(int));
@@ -744,7 +697,7 @@ int ss_mot_identity_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int*
             cells = cells || (gt_off[f + 1] > gt_off[f] && tr_off[f + 1] > tr_off[f]);
         }
     }
-    char* d = (char*)m.dev;
+    char* d = m.dev.as();
     MotArgs a;
     memset(&a, 0, sizeof a);
     a.gt_box = (const double*)(d + o_gbox); a.tr_box = (const double*)(d + o_tbox);
@@ -755,17 +708,17 @@ int ss_mot_identity_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int*
     a.id_pot = (unsigned*)(d + o_pot); a.id_match = (int*)(d + o_match); a.id_tp = (int*)(d + o_tp);
     a.thr = thr;
 
-    MCHK(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
-    if (id_cells) MCHK(hipMemsetAsync(d + o_pot, 0, id_cells * sizeof(unsigned), stream));       // every call
+    SS_HIPCHK(who, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
+    if (id_cells) SS_HIPCHK(who, hipMemsetAsync(d + o_pot, 0, id_cells * sizeof(unsigned), stream));       // every call
     if (cells) {
         hipLaunchKernelGGL(k_id_count, dim3((unsigned)F), dim3(256), 0, stream, a);
-        MCHK(hipGetLastError());
+        SS_HIPCHK(who, hipGetLastError());
     }
     hipLaunchKernelGGL(k_id_solve, dim3((unsigned)n_pairs), dim3(MOT_ID_THREADS), 0, stream, a);
-    MCHK(hipGetLastError());
-    MCHK(hipMemcpyAsync(h + up, d + down_from, down, hipMemcpyDeviceToHost, stream));
-    MCHK(hipEventRecord(m.ev, stream));
-    MCHK(hipEventSynchronize(m.ev));
+    SS_HIPCHK(who, hipGetLastError());
+    SS_HIPCHK(who, hipMemcpyAsync(h + up, d + down_from, down, hipMemcpyDeviceToHost, stream));
+    SS_HIPCHK(who, hipEventRecord(m.ev, stream));
+    SS_HIPCHK(who, hipEventSynchronize(m.ev));
     const char* hd = h + up - down_from;                 // hd + o_x is field x of the download image
     memcpy(idtp, hd + o_tp, (size_t)n_pairs * sizeof(int));
     memcpy(gt_to_tr, hd + o_match, nG * sizeof(int));

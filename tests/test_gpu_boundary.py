@@ -503,3 +503,19 @@ def test_pack_results_writes_counts_and_rows_into_one_buffer(pinned):
         assert torch.equal(h[2 + 128 * 6:2 + 128 * 6 + cm * 8].view(cm, 8), out.cpu()[:cm])
         assert (h[2 + 128 * 6 + cm * 8:] == -7.0).all()
     eng.close()
+
+
+def test_upload_download_round_trips_grow_and_under_fill_the_staging_slots():
+    """Six uploads go once round the four upload slots and revisit two of them: slot 0 grows to 1 KiB and is then under-filled
+    with 16 B, slot 1 holds 1 MiB twice, slot 3 grows to 3 MiB; the download area grows, shrinks in use and grows again."""
+    from tests.gpu_util import engine
+    eng = engine(StrongSortConfig())
+    rng = np.random.default_rng(6)
+    for n in (1 << 10, 1 << 20, 4 << 10, 3 << 20, 16, 1 << 20):
+        src = rng.integers(0, 256, n, dtype=np.uint8)
+        dev = torch.empty(n, dtype=torch.uint8, device=eng.device)
+        back = np.zeros(n, np.uint8)
+        eng.upload(dev, src)
+        eng.download(back, dev)
+        assert back.tobytes() == src.tobytes(), f"{n} bytes came back changed"
+    eng.close()

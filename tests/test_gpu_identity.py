@@ -186,6 +186,31 @@ def test_four_pairs_in_one_call_equal_four_calls_and_scratch_is_reused(eng, gold
     assert whole[0].tobytes() == again[0].tobytes() and whole[0][3] == len(g30)
 
 
+def test_mot_eval_and_mot_identity_alternate_on_one_engine_across_a_growth(eng, golden):
+    """The two calls share the context's pinned and device images, lay them out differently and size them by different totals:
+    small eval, large identity (grows both), large eval (grows both again), small identity (under-fills them).  Every result
+    equals, bit for bit, the same call on a fresh engine."""
+    rng = np.random.default_rng(44)
+    g6, t6 = case_rows(golden["id6_gt"]), case_rows(golden["id6_tr"])                    # the smallest golden pair
+    g30, t30 = case_rows(golden["id30_gt"]), case_rows(golden["id30_tr"])
+    small = [_pair(g6, t6)]
+    four = [_pair(*iref.crowd(rng, 300, 280, 24)), _pair(g30, t30), _pair(*iref.crowd(rng, 40, 70, 6)), _pair(g30, g30)]
+    calls = [("mot_eval", small, {"want_ga": True}), ("mot_identity", four, {"want_pot": True}), ("mot_eval", four, {"want_ga": True}),
+             ("mot_identity", small, {"want_pot": True})]
+    own = engine(debug=False)                            # not the module's engine: its images have grown already
+    got = [getattr(own, name)(*moteval.pack(pairs), **kw) for name, pairs, kw in calls]
+    own.close()
+    for k, (name, pairs, kw) in enumerate(calls):
+        if k == 0:
+            continue                                     # (the first call ran on a fresh engine)
+        fresh = engine(debug=False)
+        want = getattr(fresh, name)(*moteval.pack(pairs), **kw)
+        fresh.close()
+        assert len(got[k]) == len(want) and len(want) == (5 if name == "mot_eval" else 3)
+        for a, b in zip(got[k], want):
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), f"call {k} ({name}) differs from a fresh engine's"
+
+
 # ---- evaluate ------------------------------------------------------------------------------------------------------------------------
 def test_evaluate_with_identity_is_evaluate_plus_six_keys(eng, golden):
     gt, trs = case_rows(golden["id30_gt"]), [case_rows(golden["id30_tr"]), case_rows(golden["id30_gt"])[::2]]
