@@ -296,6 +296,42 @@ int ss_native_feats(ss_ctx* ctx, int n_img, int half, const ss_native_map* maps,
 int ss_byte_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracked, int* n_lost, int* next_id, int* frame_id,
                        int* track_id, int* state, int* activated, double* mean);
 
+/* ---- OC-SORT (docs/OCSORT.md): the motion-only tracker with observation-centric re-update, momentum and recovery ----------------
+ * A 7-state SORT Kalman filter per track and IoU association with a direction-consistency term; no weights, no frames.  The state
+ * is hung off an existing context like the BYTE state (the two may coexist); ss_ocsort_create on a context that already has one
+ * replaces it.  SS_ERR_INVALID unless 1 <= max_tracks <= SS_MAX_TRACKS, 1 <= max_dets <= SS_MAX_DETS, 1 <= delta_t <= 8,
+ * max_age >= 1, min_hits >= 0, 0 < iou_threshold <= 1, inertia >= 0 and use_byte is 0 or 1. */
+typedef struct ss_ocsort_config {
+    double det_thresh;           /* 0.25  first association and births: score > this                          */
+    double low_thresh;           /* 0.1   BYTE stage rows: low < score < det_thresh                            */
+    double iou_threshold;        /* 0.3   a pair is kept when its IoU >= this                                  */
+    double inertia;              /* 0.2   weight of the direction-consistency term                             */
+    int    max_age;              /* 30    a track is removed when time_since_update > this                     */
+    int    min_hits;             /* 3     rows need hit_streak >= this (or frame_count <= this)                */
+    int    delta_t;              /* 3     observations this many ages back give the directions (1..8)          */
+    int    use_byte;             /* 0     1: the second association on the low-score rows                      */
+    int    max_tracks;           /* <= SS_MAX_TRACKS per stream                                                */
+    int    max_dets;             /* <= SS_MAX_DETS per frame                                                   */
+} ss_ocsort_config;
+int ss_ocsort_create(ss_ctx* ctx, const ss_ocsort_config* cfg);
+int ss_ocsort_destroy(ss_ctx* ctx);
+/* A group of n_frames (1..32) frames of every stream in ONE launch, associated strictly in order; the layouts of
+ * ss_byte_update_group: d_dets [n_frames][n_streams][SS_MAX_DETS][6], d_ndets [n_frames][n_streams] ->
+ * d_out [n_frames][n_streams][SS_MAX_TRACKS][8] (x1,y1,x2,y2,track_id,class_id,conf,det_idx; the box is the track's last
+ * observation, newest track first; det_idx >= 0 always), d_nout [n_frames][n_streams].  Every argument is checked first
+ * (SS_ERR_INVALID without touching the device).  Asynchronous on the context's stream, capturable.  A frame with more than
+ * max_dets rows is tracked on its first max_dets; births beyond max_tracks are dropped; either raises SS_ERR_CAPACITY at
+ * ss_check_errors (set until ss_ocsort_reset). */
+int ss_ocsort_update_group(ss_ctx* ctx, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
+int ss_ocsort_update(ss_ctx* ctx, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
+int ss_ocsort_reset(ss_ctx* ctx, int stream);              /* stream < 0: all streams; ids restart at 1, frame_count at 0 */
+/* Synchronous: the table of one stream in list order (oldest track first); any array may be NULL.  x [n][7] (x, y, s, r, vx, vy,
+ * vs), P [n][49], frozen: 1 while the filter holds a copy frozen at the first miss after an observation, last_obs [n][4] xyxy
+ * (-1 four times while the track has none), velocity [n][2] unit direction (x, y; zeros while none). */
+int ss_ocsort_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracks, int* next_id, int* frame_count, int* track_id, int* age,
+                         int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
+                         double* velocity);
+
 /* ---- N4  camera-motion compensation (upstream StrongSORT: tracker.camera_update(prev, cur) before tracker.predict();
  * not in the reference snapshot; optional) ----------------------------------------------------------
  * ss_cmc_estimate: for the n_frames x n_streams BGR u8 frames at d_frames ([F][S] order, frame_stride bytes apart) build

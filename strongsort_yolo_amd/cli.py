@@ -333,7 +333,7 @@ def process_video(args: dict, model=None) -> dict:
                      device_masks=args.get("device_masks", False), tracker_type=args.get("tracker", "strongsort"),
                      camera_motion=args.get("camera_motion", False), with_reid=args.get("with_reid", False),
                      reid_model=args.get("reid_model", "osnet"), with_pose=args.get("with_pose", False),
-                     gmc_method=args.get("gmc_method", "ecc"))
+                     gmc_method=args.get("gmc_method", "ecc"), ocsort_use_byte=args.get("ocsort_use_byte", False))
         model.overrides.update(conf=0.3, iou=0.4, agnostic_nms=False, max_det=1000)      # :18-21
     name = os.path.splitext(os.path.basename(str(source)))[0] or "stream"
     writer = LabelsWriter(os.path.join(args.get("outdir", "output"), f"{name}_labels.txt"), args.get("compat", False))
@@ -469,8 +469,11 @@ def main(argv=None):
     p.add_argument("--fp32", action="store_true", help="every network operation in fp32 (the reference passes no half=): detector on the fp32 convolution kernels too — NMS keep lists equal the CPU fp32 network's; about 0.39x the f16 throughput")
     p.add_argument("--reid-weights", default=None, help="OSNet-x0.25 state_dict for the tracker's appearance features (required with --track unless --random-init; "
                                                           "used by --tracker botsort only with --with-reid, not by bytetrack)")
-    p.add_argument("--tracker", choices=("strongsort", "bytetrack", "botsort"), default="strongsort",
-                   help="strongsort (default): OSNet appearance + NSA Kalman; bytetrack / botsort: the BYTE family on IoU and scores, no ReID network (docs/BYTETRACK.md)")
+    p.add_argument("--tracker", choices=("strongsort", "bytetrack", "botsort", "ocsort"), default="strongsort",
+                   help="strongsort (default): OSNet appearance + NSA Kalman; bytetrack / botsort: the BYTE family on IoU and scores, no ReID network (docs/BYTETRACK.md); "
+                        "ocsort: OC-SORT, motion only, no ReID network (docs/OCSORT.md)")
+    p.add_argument("--ocsort-use-byte", action="store_true",
+                   help="--tracker ocsort only: OC-SORT's BYTE stage, a second association on the rows scoring between 0.1 and 0.25")
     p.add_argument("--camera-motion", action="store_true",
                    help="ECC camera-motion compensation on the device: StrongSORT moves its track boxes, botsort applies BoT-SORT's GMC "
                         "(docs/BYTETRACK.md §1b); not with --tracker bytetrack")
@@ -547,6 +550,12 @@ def main(argv=None):
         p.error("--aflink-thr-s must be finite and >= 0")
     if a.aflink and not 0.0 < a.aflink_thr_p <= 1.0:
         p.error("--aflink-thr-p must be in (0, 1]")
+    if a.tracker == "ocsort":
+        for flag, on in (("--camera-motion", a.camera_motion), ("--with-reid", a.with_reid), ("--with-pose", a.with_pose)):
+            if on:
+                p.error(f"{flag} is not available with --tracker ocsort (OC-SORT is motion only, docs/OCSORT.md)")
+    if a.ocsort_use_byte and a.tracker != "ocsort":
+        p.error("--ocsort-use-byte is OC-SORT's BYTE stage: it needs --tracker ocsort")
     if a.camera_motion and a.tracker == "bytetrack":
         p.error("--camera-motion needs --tracker strongsort or botsort (ByteTrack has no GMC)")
     if a.gmc_method != "ecc" and not a.camera_motion:
@@ -583,7 +592,7 @@ def main(argv=None):
             p.error(f"--device-encode: --save '{a.save}' must be a .mjpeg / .mjpg file or a directory (a path ending in '/' or an existing directory)")
         if not 1 <= a.save_quality <= 100:
             p.error("--save-quality must be 1 .. 100")
-    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "device_decode": a.device_decode, "device_entropy": a.device_entropy,
+    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "ocsort_use_byte": a.ocsort_use_byte, "device_decode": a.device_decode, "device_entropy": a.device_entropy,
              "device_encode": a.device_encode, "device_encode_entropy": a.device_encode_entropy, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
              "gsi": a.gsi, "gsi_interval": a.gsi_interval, "gsi_tau": a.gsi_tau, "eval_gt": a.eval_gt[i] if a.eval_gt else None, "eval_thr": a.eval_thr, "eval_identity": a.eval_identity,
              "aflink": a.aflink, "aflink_thr_t": tuple(a.aflink_thr_t), "aflink_thr_s": a.aflink_thr_s, "aflink_thr_p": a.aflink_thr_p,

@@ -112,13 +112,67 @@ class ByteTrackConfig:
         return asdict(self)
 
 
-# tracker_type of YOLO / FramePipeline / the CLI -> the BYTE configuration it runs (None: StrongSORT)
-TRACKER_TYPES = ("strongsort", "bytetrack", "botsort")
+@dataclass(frozen=True)
+class OCSortConfig:
+    """OC-SORT (docs/OCSORT.md, decisions O-01..): the motion-only tracker with observation-centric re-update, momentum
+    (inertia, delta_t) and recovery; use_byte adds the second association on the rows between low_thresh and det_thresh.
+    det_thresh is ByteTrackConfig.track_high_thresh, so the three IoU trackers see the same high rows at default settings (O-01)."""
+    det_thresh: float = 0.25
+    low_thresh: float = 0.1
+    max_age: int = 30
+    min_hits: int = 3
+    iou_threshold: float = 0.3
+    delta_t: int = 3
+    inertia: float = 0.2
+    use_byte: bool = False
+    # capacities of the device-resident track table (per stream) and of a frame
+    max_tracks: int = 256
+    max_dets: int = 128
+
+    def __post_init__(self):
+        if not 1 <= self.delta_t <= 8:
+            raise ValueError(f"OCSortConfig.delta_t: 1..8, not {self.delta_t}")
+        if self.max_age < 1 or self.min_hits < 0:
+            raise ValueError("OCSortConfig: max_age >= 1 and min_hits >= 0")
+        if not 0.0 < self.iou_threshold <= 1.0:
+            raise ValueError(f"OCSortConfig.iou_threshold: in (0, 1], not {self.iou_threshold}")
+        if not self.inertia >= 0.0:
+            raise ValueError(f"OCSortConfig.inertia: >= 0, not {self.inertia}")
+        if not self.low_thresh <= self.det_thresh:
+            raise ValueError("OCSortConfig: low_thresh <= det_thresh")
+        if not (0 < self.max_tracks <= 256 and 0 < self.max_dets <= 128):
+            raise ValueError("OCSortConfig: max_tracks <= 256 and max_dets <= 128 (the device table's capacity)")
+
+    def as_dict(self):
+        return asdict(self)
+
+
+# tracker_type of YOLO / FramePipeline / the CLI -> the BYTE configuration it runs (None: StrongSORT and OC-SORT)
+TRACKER_TYPES = ("strongsort", "bytetrack", "botsort", "ocsort")
+
+
+def ocsort_config(tracker_type: str, use_byte: bool = False, camera_motion: bool = False, with_reid: bool = False, with_pose: bool = False):
+    """tracker_type -> the OC-SORT configuration it runs (None: another tracker).  OC-SORT is motion only: the BoT-SORT options
+    are refused by name."""
+    if tracker_type not in TRACKER_TYPES:
+        raise ValueError(f"tracker_type must be one of {TRACKER_TYPES}, not {tracker_type!r}")
+    if tracker_type != "ocsort":
+        if use_byte:
+            raise ValueError(f"use_byte is OC-SORT's BYTE stage: tracker_type 'ocsort', not {tracker_type!r}")
+        return None
+    for name, on in (("camera_motion", camera_motion), ("with_reid", with_reid), ("with_pose", with_pose)):
+        if on:
+            raise ValueError(f"{name} is not available with tracker_type 'ocsort' (OC-SORT is motion only, docs/OCSORT.md)")
+    return OCSortConfig(use_byte=bool(use_byte))
 
 
 def byte_config(tracker_type: str, with_reid: bool = False, with_pose: bool = False):
     if tracker_type not in TRACKER_TYPES:
         raise ValueError(f"tracker_type must be one of {TRACKER_TYPES}, not {tracker_type!r}")
+    if tracker_type == "ocsort":
+        if with_reid or with_pose:
+            raise ValueError(f"{'with_reid' if with_reid else 'with_pose'} is not available with tracker_type 'ocsort' (OC-SORT is motion only)")
+        return None
     if with_reid and tracker_type != "botsort":
         raise ValueError(f"with_reid is BoT-SORT's ReID branch: tracker_type 'botsort', not {tracker_type!r}")
     if with_pose and tracker_type != "botsort":

@@ -73,6 +73,9 @@ struct ss_ctx {
     // the BYTE tracker family (ss_byte_create), NULL until attached
     struct Byte { SSByteDev dev; ss_byte_config cfg; std::vector<void*> allocs; };
     Byte* byte = nullptr;
+    // the OC-SORT tracker (ss_ocsort_create), NULL until attached
+    struct Oc { SSOcDev dev; std::vector<void*> allocs; };
+    Oc* oc = nullptr;
     SSJpeg* jpeg = nullptr;     // ss_jpeg_decode_batch's staging areas and planes, made by its first call
     SSJpegEnc* jpeg_enc = nullptr;   // ss_jpeg_encode_batch's buffers, made by its first call
     SSGsi* gsi = nullptr;       // ss_gsi_smooth's staging and scratch slots, made by its first call
@@ -228,6 +231,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     if (c->ev_chain) (void)hipEventDestroy(c->ev_chain);
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->byte) { for (void* p : c->byte->allocs) (void)hipFree(p); delete c->byte; }
+    if (c->oc) { for (void* p : c->oc->allocs) (void)hipFree(p); delete c->oc; }
     ss_jpeg_free(c->jpeg);
     ss_jpeg_enc_free(c->jpeg_enc);
     ss_gsi_free(c->gsi);
@@ -1024,6 +1028,12 @@ extern "C" int ss_check_errors(ss_ctx* c)
         for (size_t s = 0; s < e.size(); ++s)
             if (e[s]) return fail(c, e[s], "BYTE tracker: device error flag on stream " + std::to_string(s));
     }
+    if (c->oc) {                                             // OC-SORT's flags (capacity, infeasible)
+        HIPCHK(c, hipMemcpyAsync(e.data(), c->oc->dev.err, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (size_t s = 0; s < e.size(); ++s)
+            if (e[s]) return fail(c, e[s], "OC-SORT tracker: device error flag on stream " + std::to_string(s));
+    }
     {                                                        // images a device-entropy JPEG call refused (docs/JPEG.md section 12)
         std::string err;
         if (int rcj = ss_jpeg_pending_impl(c->jpeg, err)) return fail(c, rcj, err);
@@ -1365,6 +1375,140 @@ extern "C" int ss_assoc_timing_values(ss_ctx* c, float* out_ms, int cap, int* n)
     if (!c || !n || cap < 0 || (cap > 0 && !out_ms)) return SS_ERR_INVALID;
     *n = (int)c->ev_ms.size();
     for (int i = 0; i < cap && i < *n; ++i) out_ms[i] = c->ev_ms[i];
+    return SS_OK;
+}
+
+// ---- OC-SORT (ss_ocsort.hip, docs/OCSORT.md) ---------------------------------------------------------------------------------------
+extern "C" int ss_ocsort_destroy(ss_ctx* c)
+{
+    if (!c) return fail(nullptr, SS_ERR_INVALID, "ss_ocsort_destroy: null context");
+    if (!c->oc) return SS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (void* p : c->oc->allocs) HIPCHK(c, hipFree(p));
+    delete c->oc;
+    c->oc = nullptr;
+    return SS_OK;
+}
+
+extern "C" int ss_ocsort_reset(ss_ctx* c, int stream)
+{
+    if (!c || !c->oc || stream >= c->dev.S) return fail(c, SS_ERR_INVALID, "ss_ocsort_reset: no OC-SORT state or bad stream");
+    SSOcDev& o = c->oc->dev;
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? o.S : stream + 1;
+    std::vector<int> ones(o.S, 1);
+    HIPCHK(c, hipMemsetAsync(o.frame + s0, 0, (s1 - s0) * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(o.err + s0, 0, (s1 - s0) * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(o.n_trk + s0, 0, (s1 - s0) * 4, c->stream));
+    HIPCHK(c, hipMemcpyAsync(o.next_id + s0, ones.data(), (s1 - s0) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SS_OK;
+}
+
+extern "C" int ss_ocsort_create(ss_ctx* c, const ss_ocsort_config* cfg)
+{
+    if (!c || !cfg) return fail(c, SS_ERR_INVALID, "ss_ocsort_create: null argument");
+    if (cfg->max_tracks < 1 || cfg->max_tracks > SS_MAXT || cfg->max_dets < 1 || cfg->max_dets > SS_MAXD || cfg->delta_t < 1 ||
+        cfg->delta_t > SS_OC_MAXDT || cfg->max_age < 1 || cfg->min_hits < 0 || !(cfg->iou_threshold > 0.0 && cfg->iou_threshold <= 1.0) ||
+        !(cfg->inertia >= 0.0) || !(cfg->low_thresh <= cfg->det_thresh) || (cfg->use_byte != 0 && cfg->use_byte != 1))
+        return fail(c, SS_ERR_INVALID, "ss_ocsort_create: 1 <= max_tracks <= 256, 1 <= max_dets <= 128, 1 <= delta_t <= 8, max_age >= 1, "
+                                       "min_hits >= 0, 0 < iou_threshold <= 1, inertia >= 0, low_thresh <= det_thresh, use_byte 0 / 1");
+    if (int rc = ss_ocsort_destroy(c)) return rc;
+    ss_ctx::Oc* O = new ss_ctx::Oc();
+    SSOcDev& o = O->dev;
+    memset(&o, 0, sizeof o);
+    o.S = c->dev.S;
+    o.max_age = cfg->max_age; o.min_hits = cfg->min_hits; o.delta_t = cfg->delta_t; o.use_byte = cfg->use_byte;
+    o.max_tracks = cfg->max_tracks; o.max_dets = cfg->max_dets;
+    o.det_thresh = (float)cfg->det_thresh; o.low_thresh = (float)cfg->low_thresh;
+    o.iou_thr = cfg->iou_threshold; o.inertia = cfg->inertia;
+    const size_t S = o.S, T = SS_MAXT;
+    int rc = SS_OK;
+    auto al = [&](auto** p, size_t n) {
+        if (rc != SS_OK) return;
+        void* q = nullptr;
+        const size_t bytes = n * sizeof(**p);
+        hipError_t e = hipMalloc(&q, bytes);
+        if (e == hipSuccess) { O->allocs.push_back(q); e = hipMemsetAsync(q, 0, bytes, c->stream); }
+        if (e != hipSuccess) rc = fail(c, SS_ERR_HIP, std::string("ss_ocsort_create: ") + hipGetErrorString(e));
+        *p = (std::remove_reference_t<decltype(**p)>*)q;
+    };
+    al(&o.frame, S); al(&o.next_id, S); al(&o.err, S); al(&o.n_trk, S);
+    al(&o.trk, S * T);
+    al(&o.tid, S * T); al(&o.age, S * T); al(&o.tsu, S * T); al(&o.hits, S * T); al(&o.streak, S * T); al(&o.hasobs, S * T);
+    al(&o.obsd, S * T); al(&o.frozen, S * T); al(&o.det, S * T);
+    al(&o.score, S * T); al(&o.cls, S * T); al(&o.lobs, S * T * 4);
+    al(&o.ring, S * T * SS_OC_MAXDT * 4); al(&o.rage, S * T * SS_OC_MAXDT); al(&o.vel, S * T * 2);
+    al(&o.x, S * T * 7); al(&o.P, S * T * 49); al(&o.xf, S * T * 7); al(&o.Pf, S * T * 49); al(&o.spill, S * T * SS_MAXD);
+    c->oc = O;
+    if (rc == SS_OK) rc = ss_ocsort_reset(c, -1);
+    if (rc != SS_OK) { std::string m = c->err; (void)ss_ocsort_destroy(c); c->err = m; return rc; }
+    return SS_OK;
+}
+
+extern "C" int ss_ocsort_update_group(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout)
+{
+    if (!c || !d_dets || !d_ndets || !d_out || !d_nout) return fail(c, SS_ERR_INVALID, "ss_ocsort_update_group: null argument");
+    if (!c->oc) return fail(c, SS_ERR_INVALID, "ss_ocsort_update_group: no OC-SORT state (ss_ocsort_create)");
+    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_ocsort_update_group: 1 <= n_frames <= SS_FMAX");
+    ss_launch_ocsort_group(c->oc->dev, n_frames, d_dets, d_ndets, d_out, d_nout, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+extern "C" int ss_ocsort_update(ss_ctx* c, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout)
+{
+    return ss_ocsort_update_group(c, 1, d_dets, d_ndets, d_out, d_nout);
+}
+
+extern "C" int ss_ocsort_get_tracks(ss_ctx* c, int s, int cap, int* n_tracks, int* next_id, int* frame_count, int* track_id, int* age,
+                                    int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
+                                    double* velocity)
+{
+    if (!c || !c->oc || s < 0 || s >= c->dev.S || cap < 0) return fail(c, SS_ERR_INVALID, "ss_ocsort_get_tracks: no OC-SORT state or bad stream");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const SSOcDev& o = c->oc->dev;
+    int nt = 0, nid = 0, fr = 0;
+    HIPCHK(c, hipMemcpy(&nt, o.n_trk + s, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&nid, o.next_id + s, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&fr, o.frame + s, 4, hipMemcpyDeviceToHost));
+    if (n_tracks) *n_tracks = nt;                                    // the counts also when cap is too small: the caller sizes by them
+    if (next_id) *next_id = nid;
+    if (frame_count) *frame_count = fr;
+    if (nt < 0 || nt > SS_MAXT) return fail(c, SS_ERR_CAPACITY, "ss_ocsort_get_tracks: corrupt list");
+    if (nt > cap) return fail(c, SS_ERR_CAPACITY, "ss_ocsort_get_tracks: cap too small");
+    const size_t T = SS_MAXT, sb = (size_t)s * T;
+    std::vector<int> trk(T), iv(T);
+    HIPCHK(c, hipMemcpy(trk.data(), o.trk + sb, T * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < nt; ++i)
+        if (trk[i] < 0 || trk[i] >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, "ss_ocsort_get_tracks: corrupt list");
+    auto ints = [&](const int* src, int* dst) -> int {
+        if (!dst) return SS_OK;
+        HIPCHK(c, hipMemcpy(iv.data(), src + sb, T * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < nt; ++i) dst[i] = iv[trk[i]];
+        return SS_OK;
+    };
+    auto dbls = [&](const double* src, double* dst, int n) -> int {
+        if (!dst) return SS_OK;
+        std::vector<double> dv(T * n);
+        HIPCHK(c, hipMemcpy(dv.data(), src + sb * n, T * n * 8, hipMemcpyDeviceToHost));
+        for (int i = 0; i < nt; ++i) for (int k = 0; k < n; ++k) dst[i * n + k] = dv[(size_t)trk[i] * n + k];
+        return SS_OK;
+    };
+    if (int rc = ints(o.tid, track_id)) return rc;
+    if (int rc = ints(o.age, age)) return rc;
+    if (int rc = ints(o.tsu, time_since_update)) return rc;
+    if (int rc = ints(o.hits, hits)) return rc;
+    if (int rc = ints(o.streak, hit_streak)) return rc;
+    if (int rc = ints(o.frozen, frozen)) return rc;
+    if (int rc = dbls(o.x, x, 7)) return rc;
+    if (int rc = dbls(o.P, P, 49)) return rc;
+    if (int rc = dbls(o.vel, velocity, 2)) return rc;
+    if (last_obs) {
+        std::vector<float> lv(T * 4);
+        HIPCHK(c, hipMemcpy(lv.data(), o.lobs + sb * 4, T * 16, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(iv.data(), o.hasobs + sb, T * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < nt; ++i) for (int k = 0; k < 4; ++k) last_obs[i * 4 + k] = iv[trk[i]] ? lv[(size_t)trk[i] * 4 + k] : -1.0f;
+    }
     return SS_OK;
 }
 

@@ -365,6 +365,26 @@ struct SSByteDev {
     float* ufeat;                       // [FMAX][S][MAXD][F] unit detection features of the group (k_byte_feats)
 };
 
+// Device state of the OC-SORT tracker (csrc/ss_ocsort.hip, docs/OCSORT.md), hung off a context by ss_ocsort_create.  Per stream: one
+// ordered list of slots, per slot the track's fields; all pointers device memory.
+#define SS_OC_MAXDT 8                   // largest delta_t: the depth of a track's ring of observations
+struct SSOcDev {
+    int S;
+    int max_age, min_hits, delta_t, use_byte, max_tracks, max_dets;
+    float det_thresh, low_thresh;       // score thresholds, compared in float32
+    double iou_thr, inertia;
+    int *frame, *next_id, *err, *n_trk; // [S]
+    int* trk;                           // [S][MAXT] slots in list order
+    int *tid, *age, *tsu, *hits, *streak, *hasobs, *obsd, *frozen, *det;     // [S][MAXT] by slot
+    float *score, *cls;                 // [S][MAXT]
+    float* lobs;                        // [S][MAXT][4] last observation (the birth row while hasobs is 0)
+    float* ring;                        // [S][MAXT][SS_OC_MAXDT][4] observations, entry age % delta_t
+    int* rage;                          // [S][MAXT][SS_OC_MAXDT] the age an entry was stored at, -1: empty
+    double* vel;                        // [S][MAXT][2] unit velocity (x, y); zero: none
+    double *x, *P, *xf, *Pf;            // [S][MAXT][7], [S][MAXT][49]: the filter and its frozen copy
+    double* spill;                      // [S][MAXT * MAXD] cost matrices that do not fit the LDS
+};
+
 // Device state of the sparse-optical-flow camera-motion estimator (csrc/ss_gmc.hip, docs/BYTETRACK.md §1f), hung off a context by
 // the first ss_gmc_sparse_estimate call for a frame size.  Image slot 0 of a stream is the remembered frame, slots 1..F the group's.
 #define SS_GMC_MAXC 1000                // corners per image (S-05)

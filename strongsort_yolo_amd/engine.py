@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from .config import StrongSortConfig, DetectConfig, ByteTrackConfig
+from .config import StrongSortConfig, DetectConfig, ByteTrackConfig, OCSortConfig
 from .lib import MAX_TRACKS, MAX_DETS, FEAT_DIM, OUT_COLS
 
 
@@ -878,3 +878,73 @@ class ByteTrackEngine:
         k = nt.value + nl.value
         return dict(track_id=ids[:k].copy(), state=st[:k].copy(), activated=act[:k].copy(), mean=mean[:k].copy(),
                     n_tracked=nt.value, n_lost=nl.value, next_id=nid.value, frame_id=fr.value)
+
+
+class OCSortEngine:
+    """OC-SORT (csrc/ss_ocsort.hip, docs/OCSORT.md) on the context of a TrackerEngine: the same update_device / update_group /
+    reset / check_errors shape as ByteTrackEngine, without features, keypoints or warps.  `engine`: share the context of an
+    existing TrackerEngine (a pipeline's: its NMS, streams and error words); None: a context of its own."""
+
+    reid = pose = False
+
+    def __init__(self, cfg: OCSortConfig | None = None, n_streams: int = 1, device: int = 0, engine: TrackerEngine | None = None):
+        self.cfg = cfg or OCSortConfig()
+        self._own = engine is None
+        self.base = TrackerEngine(StrongSortConfig(), n_streams, device) if engine is None else engine
+        self.S, self.device, self.L = self.base.S, self.base.device, self.base.L
+        c = _lib.make_ocsort_config(self.cfg)
+        self._ck(self.L.ss_ocsort_create(self.base.ctx, C.byref(c)))
+        self.out = torch.zeros(self.S, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=self.device)
+        self.nout = torch.zeros(self.S, dtype=torch.int32, device=self.device)
+        self.use_stream, self.use_current_stream = self.base.use_stream, self.base.use_current_stream
+        self.check_errors = self.base.check_errors
+
+    @property
+    def ctx(self):
+        return self.base.ctx
+
+    @property
+    def max_group_frames(self) -> int:
+        return self.base.max_group_frames
+
+    def _ck(self, rc):
+        _lib.check(self.base.ctx, rc)
+
+    def close(self):
+        if self._own:
+            self.base.close()
+        elif getattr(self.base, "ctx", None) and self.base.ctx.value:
+            torch.cuda.synchronize(self.device)
+            self._ck(self.L.ss_ocsort_destroy(self.base.ctx))
+
+    def reset(self, stream: int = -1):
+        """Restart the stream(s): ids from 1, frame_count from 0."""
+        self._ck(self.L.ss_ocsort_reset(self.base.ctx, stream))
+
+    def update_device(self, dets, ndets, feats=None, img_hw=None, out=None, nout=None):
+        """All streams, one frame: dets [S,128,6] f32, ndets [S] i32 -> (rows [S,256,8], counts [S]) device tensors, asynchronous.
+        feats and img_hw are accepted for TrackerEngine's call shape and unused."""
+        out = self.out if out is None else out
+        nout = self.nout if nout is None else nout
+        return self.update_group(1, dets, ndets, feats, img_hw, out, nout)
+
+    def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout):
+        """A group of n_frames (<= 32) frames of all streams in ONE launch: dets [F,S,128,6] f32, ndets [F,S] i32 -> rows out
+        [F,S,256,8], counts nout [F,S] (device tensors, asynchronous); frames are associated in order.  feats, img_hw unused."""
+        self._ck(self.L.ss_ocsort_update_group(self.base.ctx, int(n_frames), _ptr(dets), _ptr(ndets), _ptr(out), _ptr(nout)))
+        return out, nout
+
+    def tracks(self, stream: int = 0) -> dict:
+        """The table of one stream in list order (oldest track first): what tests/ocsort_ref.py's tracks() returns."""
+        T = MAX_TRACKS
+        nt, nid, fr = C.c_int(), C.c_int(), C.c_int()
+        names = ("track_id", "age", "time_since_update", "hits", "hit_streak", "frozen")
+        iv = {n: np.zeros(T, np.int32) for n in names}
+        x, P, lo, vel = np.zeros((T, 7)), np.zeros((T, 49)), np.zeros((T, 4), np.float32), np.zeros((T, 2))
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        self._ck(self.L.ss_ocsort_get_tracks(self.base.ctx, stream, T, C.byref(nt), C.byref(nid), C.byref(fr),
+                                             *[iv[n].ctypes.data_as(ip) for n in names], x.ctypes.data_as(dp), P.ctypes.data_as(dp),
+                                             lo.ctypes.data_as(C.POINTER(C.c_float)), vel.ctypes.data_as(dp)))
+        k = nt.value
+        return dict({n: iv[n][:k].copy() for n in names}, x=x[:k].copy(), P=P[:k].copy(), last_obs=lo[:k].copy(), velocity=vel[:k].copy(),
+                    n_tracks=k, next_id=nid.value, frame_count=fr.value)

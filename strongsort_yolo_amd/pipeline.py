@@ -40,7 +40,7 @@ class FramePipeline:
                  dcfg: Optional[DetectConfig] = None, det_source: str = "detector", feat_source: str = "reid",
                  graph: str = "all", debug: bool = False, run_nets: bool = True, seed: int = 0, detect_only_rows: int = 0, cmc: bool = False,
                  reid_half: Optional[bool] = None, crops_u8: bool = True, tracker: str = "strongsort", with_reid: bool = False,
-                 reid_model: str = "osnet", with_pose: bool = False, gmc_method: str = "ecc"):
+                 reid_model: str = "osnet", with_pose: bool = False, gmc_method: str = "ecc", ocsort_use_byte: bool = False):
         self.cfg, self.dcfg = cfg or StrongSortConfig(), dcfg or DetectConfig()
         self.S, (self.H, self.W) = n_streams, frame_hw
         # tracker = "bytetrack" / "botsort": the BYTE tracker family (csrc/ss_byte.hip) on IoU and scores — no OSNet is built, no
@@ -54,13 +54,16 @@ class FramePipeline:
         # keypoint columns of the NMS rows in place (b.dets, row stride 6 + nk + nm, column 6) with the NMS geometry; no copy, no stage.
         # gmc_method (cmc only): "ecc" (csrc/ss_cmc.hip) or, for botsort, "sparseOptFlow" (docs/BYTETRACK.md §1f, csrc/ss_gmc.hip):
         # which estimator fills the group's warps; the tracker call reads either the same way.
-        from .config import byte_config, check_reid_model, check_pose, check_gmc_method
+        # tracker = "ocsort": OC-SORT (csrc/ss_ocsort.hip, docs/OCSORT.md) — motion only: like the BYTE family without ReID it builds no
+        # OSNet and cuts no crops, and its engine stands where the BYTE engine stands (self.byte / self.trk: the same stage bodies).
+        from .config import byte_config, ocsort_config, check_reid_model, check_pose, check_gmc_method
+        self.oc_cfg = ocsort_config(tracker, ocsort_use_byte, cmc, with_reid, with_pose)
         self.byte_cfg = byte_config(tracker, with_reid, with_pose)
         self.gmc_method = check_gmc_method(gmc_method, cmc, tracker)
         self.reid_model = check_reid_model(reid_model, with_reid)
         self.tracker = tracker
         self.native = self.reid_model == "auto" and not detect_only_rows
-        self.need_reid = self.byte_cfg is None or (self.byte_cfg.with_reid and self.reid_model == "osnet")
+        self.need_reid = (self.byte_cfg is None and self.oc_cfg is None) or (self.byte_cfg is not None and self.byte_cfg.with_reid and self.reid_model == "osnet")
         if self.byte_cfg is not None and cmc and self.byte_cfg.kalman != "xywh":
             raise ValueError("camera-motion compensation needs tracker 'strongsort' or 'botsort' (ByteTrack has no GMC)")
         self.eng = TrackerEngine(self.cfg, n_streams, device, debug=debug)
@@ -69,6 +72,9 @@ class FramePipeline:
         if self.byte_cfg is not None:
             from .engine import ByteTrackEngine
             self.byte = self.trk = ByteTrackEngine(self.byte_cfg, engine=self.eng)
+        elif self.oc_cfg is not None:
+            from .engine import OCSortEngine
+            self.byte = self.trk = OCSortEngine(self.oc_cfg, engine=self.eng)
         dev = self.dev = self.eng.device
         self.half, self.dtype = half, torch.float16 if half else torch.float32
         # reid_half=False: the ReID crops and OSNet in fp32 on the hand-written fp32 kernels (fused32.py, csrc/ss_ops32.hip:

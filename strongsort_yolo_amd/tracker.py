@@ -13,8 +13,8 @@ import numpy as np
 import torch
 
 from . import nets
-from .config import StrongSortConfig, ByteTrackConfig, check_reid_model, check_gmc_method
-from .engine import TrackerEngine, ByteTrackEngine
+from .config import StrongSortConfig, ByteTrackConfig, OCSortConfig, check_reid_model, check_gmc_method
+from .engine import TrackerEngine, ByteTrackEngine, OCSortEngine
 from .lib import MAX_DETS, FEAT_DIM
 
 
@@ -160,6 +160,41 @@ class BYTETracker:
         elif keypoints is not None:
             raise ValueError("keypoints given, but cfg.with_pose is off")
         out, nout = self.eng.update_device(self._dets, self._n, feats, kpts=self._kpts)
+        torch.cuda.synchronize(self.dev)
+        self.eng.check_errors()
+        return out[0, : int(nout[0])].cpu().numpy()
+
+    def reset(self):
+        self.eng.reset(-1)
+
+    def close(self):
+        self.eng.close()
+
+
+class OCSORTTracker:
+    """OC-SORT for one video stream (docs/OCSORT.md): `update(dets)` needs no weights and no frame.
+         dets  [N,6] float  x1,y1,x2,y2,conf,cls in frame pixels (numpy or torch), N <= cfg.max_dets
+       returns float32 [M,8]: x1,y1,x2,y2,track_id,class_id,conf,det_idx for every track matched this frame with
+       hit_streak >= min_hits (or within the first min_hits frames), newest track first; the box is the matched row's
+       (det_idx = its row in `dets`, always >= 0)."""
+
+    def __init__(self, cfg: Optional[OCSortConfig] = None, device: int = 0):
+        self.cfg = cfg or OCSortConfig()
+        self.eng = OCSortEngine(self.cfg, 1, device)
+        self.dev = self.eng.device
+        self._dets = torch.zeros(1, MAX_DETS, 6, dtype=torch.float32, device=self.dev)
+        self._n = torch.zeros(1, dtype=torch.int32, device=self.dev)
+
+    @torch.no_grad()
+    def update(self, dets, frame=None) -> np.ndarray:
+        self.eng.use_current_stream()
+        dets = torch.as_tensor(dets, dtype=torch.float32).reshape(-1, 6)
+        n = dets.shape[0]
+        if n > self.cfg.max_dets:
+            raise ValueError(f"at most {self.cfg.max_dets} detections per frame (got {n})")
+        self._dets[0, :n].copy_(dets, non_blocking=True)
+        self._n.fill_(n)
+        out, nout = self.eng.update_device(self._dets, self._n)
         torch.cuda.synchronize(self.dev)
         self.eng.check_errors()
         return out[0, : int(nout[0])].cpu().numpy()

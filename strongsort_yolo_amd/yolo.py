@@ -18,7 +18,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .config import DetectConfig, StrongSortConfig, byte_config, check_reid_model, check_gmc_method
+from .config import DetectConfig, StrongSortConfig, byte_config, ocsort_config, check_reid_model, check_gmc_method
 
 COCO_NAMES = ("person bicycle car motorcycle airplane bus train truck boat traffic_light fire_hydrant stop_sign "
               "parking_meter bench bird cat dog horse sheep cow elephant bear zebra giraffe backpack umbrella handbag tie "
@@ -290,7 +290,7 @@ class YOLO:
     def __init__(self, weights: str = "yolov8n.pt", seed: int = 0, random_init_ok: bool = False, reid_batch: int = 128,
                  camera_motion: bool = False, reid_weights: Optional[str] = None, reid_fp32: bool = True, half: bool = True,
                  device_masks: bool = False, tracker_type: str = "strongsort", with_reid: bool = False, reid_model: str = "osnet",
-                 with_pose: bool = False, gmc_method: str = "ecc"):
+                 with_pose: bool = False, gmc_method: str = "ecc", ocsort_use_byte: bool = False):
         """reid_fp32 (default since round 6): ReID crops + OSNet-x0.25 in fp32 on the fp32 kernels — appearance distances within 1e-4 of a CPU fp32
         network, which f16 activations miss by 330x (reid_fp32=False: the f16 throughput mode, ~1.2x the per-frame rate, 1.7x the stream rate).
         half=False: the DETECTOR in fp32 as well (the reference's own precision: it passes no half=, yolo_multi_model.py:41) on the
@@ -314,8 +314,13 @@ class YOLO:
         rows' features are read from the detector's own head inputs, so the detector weights are the only file; no OSNet, no
         crops, no reid_weights (a ValueError), and reid_fp32 does not apply (the features follow `half`).
         with_pose ("botsort" on a pose model only, not with with_reid, else a ValueError): the keypoint term (docs/BYTETRACK.md §1e) —
-        the rows' own keypoints add an OKS entry to the IoU association; no second network."""
-        byte_config(tracker_type, with_reid, with_pose)      # ValueError on anything else
+        the rows' own keypoints add an OKS entry to the IoU association; no second network.
+        tracker_type "ocsort": OC-SORT on the device (docs/OCSORT.md) — a 7-state SORT filter with observation-centric re-update,
+        momentum and recovery; motion only, so no ReID network or weights, NMS at conf 0.1 in track() as for the BYTE family, and
+        camera_motion, with_reid and with_pose are ValueErrors.  ocsort_use_byte ("ocsort" only): its BYTE stage on the rows between
+        0.1 and 0.25."""
+        ocsort_config(tracker_type, ocsort_use_byte, camera_motion, with_reid, with_pose)      # ValueError on anything else
+        byte_config(tracker_type, with_reid, with_pose)
         check_reid_model(reid_model, with_reid, reid_weights)
         self.reid_model = reid_model
         self.tracker_type = tracker_type
@@ -359,6 +364,8 @@ class YOLO:
                     self._pipe_kw["reid_model"] = reid_model
             if self.with_pose:
                 self._pipe_kw["with_pose"] = True
+            if ocsort_use_byte:
+                self._pipe_kw["ocsort_use_byte"] = True
         self.device_masks = bool(device_masks)
         self._fill = None
         self._frame_index = 0
@@ -516,7 +523,7 @@ class YOLO:
         return [Results(image, self.names, Boxes(rows[:, :4], rows[:, 6], rows[:, 5], rows[:, 4]),
                         None if kpts is None else Keypoints(kpts[di]), None if masks is None else masks[di])]
 
-    TRACKERS = ("strongsort.yaml", "strongsort", "botsort.yaml", "bytetrack.yaml")
+    TRACKERS = ("strongsort.yaml", "strongsort", "botsort.yaml", "bytetrack.yaml", "ocsort.yaml")
 
     def _check_tracker(self, tracker):
         """`tracker=`: the tracker is chosen when the model is built (`tracker_type`), StrongSORT by default (BASELINE north_star).
@@ -531,7 +538,8 @@ class YOLO:
                 import warnings
                 self._tracker_warned = True
                 warnings.warn(f"tracker={tracker!r}: this model was built with tracker_type={self.tracker_type!r}, which rules; "
-                              f"its parameters are strongsort_yolo_amd.config.ByteTrackConfig", RuntimeWarning, stacklevel=3)
+                              f"its parameters are strongsort_yolo_amd.config.{'OCSortConfig' if self.tracker_type == 'ocsort' else 'ByteTrackConfig'}",
+                              RuntimeWarning, stacklevel=3)
             return
         if not name.startswith("strongsort") and not self._tracker_warned:
             import warnings
