@@ -640,6 +640,9 @@ int ss_op32_head(void* stream, const void* d_x, const void* d_w, const void* d_b
 int ss_op32_conv(void* stream, const void* d_x, int xs, const void* d_w, const void* d_bias, const void* d_res, int rs, void* d_out,
                  int os, int N, int H, int W, int Cin, int Cout, int ks, int stride, int act);
 int ss_op32_conv0(void* stream, const void* d_x, const void* d_w, const void* d_bias, void* d_out, int os, int N, int H, int W, int act);
+/* The launch ss_op32_conv makes for this problem under the current option state, computed on the host (no HIP call): *mt = 16-channel
+ * output tiles per workgroup (1 | 2 | 4 | 5), *waves = waves per workgroup (4 | 8), the grid.  Same argument checks as ss_op32_conv. */
+int ss_op32_conv_plan(int N, int H, int W, int Cin, int Cout, int ks, int stride, int* mt, int* waves, int* grid_x, int* grid_y);
 /* cat(upsample2x_nearest(lo), hi) (lo_first != 0) or cat(hi, upsample2x_nearest(lo)) along channels in one pass (the neck's two
  * upsample + concat pairs), fp32 NHWC: d_lo [N][H/2][W/2][.] pixel stride ls, d_hi [N][H][W][.] pixel stride hs, d_out dense. */
 /* YOLOv8 head decode in fp32 (DFL expectation, dist2bbox, stride scale, class sigmoid, level concat; the third branch as keypoint

@@ -1469,7 +1469,7 @@ static bool lds_attr_once(const void* fn, unsigned long long& done)
 }
 static int g_chains_pre = -1;         // k32_chains3: x1 tiles of a chain's first 1x1 requested a phase ahead: -1 = where it was measured faster (16 channels:
                                       // 618 -> 572 us per launch; 24 channels: 218 -> 330 us, the 32 extra registers spill), 0 / 1 = A/B
-static int g_chains_form = 2;        // 2: k32_chainsR (register row stream; 64 x 32 x 16 and 32 x 16 x 24 maps), 1: k32_chains3, 0: k32_chains (the 16 x 8 maps always take k32_chains)
+static int g_chains_form = 2;        // 2: k32_chainsR (register row stream; 64 x 32 x 16 and 32 x 16 x 24 maps), 1: k32_chains3 (the 16 x 8 maps have no such form: k32_chains), 0: k32_chains
 static int g_conv_mt = 0, g_conv_min = 0;      // k32_conv: 16-channel output tiles per workgroup forced (A/B) / the workgroup count below which fewer are taken (0: never; measured: 768 -> 3.64 vs 3.59 ms)
 static int g_conv_waves = 0, g_conv_wgs = 1024; // k32_conv: waves per workgroup (0 = 8 when that still leaves g_conv_wgs workgroups, else 4); A/B
 static int g_tail_wgs = 0;           // k32_tail: workgroups of the persistent grid (0 = two per CU where they fit); A/B
@@ -1708,20 +1708,17 @@ extern "C" int ss_op32_head(void* stream, const void* d_x, const void* d_w, cons
     return SS_OK;
 }
 
-/* fp32 convolution of the detector graphs (k32_conv): d_x NHWC [N][H][W][.] with pixel stride xs floats (>= Cin, a channel slice of a
- * wider tensor when larger), d_w [Cout][ks][ks][Cin], d_out NHWC [N][OH][OW][.] with pixel stride os, d_res (may be NULL, added AFTER
- * the activation) with pixel stride rs; ks 1 | 3, stride 1 | 2, pad ks / 2; act 1 = SiLU, 0 = none; Cin, Cout multiples of 16 and every
- * base pointer / stride a multiple of 4 floats. */
-extern "C" int ss_op32_conv(void* stream, const void* d_x, int xs, const void* d_w, const void* d_bias, const void* d_res, int rs, void* d_out,
-                            int os, int N, int H, int W, int Cin, int Cout, int ks, int stride, int act)
+// The launch of ss_op32_conv for a problem, computed on the host alone (no HIP call): argument checks, then the choice of mt (16-channel
+// output tiles per workgroup), waves per workgroup and grid, under the option state ss_op32_set_option holds.  ss_op32_conv launches
+// what this returns; ss_op32_conv_plan exports it (tests show from it which instantiation a case reaches).
+static int conv32_plan(int xs, int rs, int os, bool has_res, int N, int H, int W, int Cin, int Cout, int ks, int stride, int* mt_, int* wv_,
+                       unsigned* gx, unsigned* gy)
 {
-    if (!d_x || !d_w || !d_bias || !d_out || N < 1 || H < 1 || W < 1 || Cin < 16 || Cin % 16 || Cout < 16 || Cout % 16 || xs < Cin || os < Cout ||
-        (xs | os | rs) % 4 || (d_res && rs < Cout) || !(ks == 1 || ks == 3) || !(stride == 1 || stride == 2) || (ks == 1 && stride != 1) ||
-        (((uintptr_t)d_x | (uintptr_t)d_out | (uintptr_t)d_res | (uintptr_t)d_w | (uintptr_t)d_bias) & 15))
+    if (N < 1 || H < 1 || W < 1 || Cin < 16 || Cin % 16 || Cout < 16 || Cout % 16 || xs < Cin || os < Cout || (xs | os | rs) % 4 ||
+        (has_res && rs < Cout) || !(ks == 1 || ks == 3) || !(stride == 1 || stride == 2) || (ks == 1 && stride != 1))
         return SS_ERR_INVALID;
     const int OH = (H + 2 * (ks / 2) - ks) / stride + 1, OW = (W + 2 * (ks / 2) - ks) / stride + 1;
     const long long M = (long long)N * OH * OW, tiles = (M + 15) / 16;
-    hipStream_t st = (hipStream_t)stream;
     // output channels per workgroup: 64 (80 for the 80-wide head layers) on the large maps; on the small ones fewer, so that the launch
     // still has ~g_conv_min workgroups (a 12 x 20 map of 32 frames is 480 pixel tiles: 120 workgroups of 64 channels would leave the chip 7/8 idle)
     int mt = Cout % 80 == 0 && Cout <= 80 ? 5 : (Cout % 64 == 0 ? 4 : (Cout % 32 == 0 ? 2 : 1));
@@ -1730,7 +1727,38 @@ extern "C" int ss_op32_conv(void* stream, const void* d_x, int xs, const void* d
     // enough workgroups for the chip: one pixel tile per wave on the small maps
     const int pt = 1;                                          // (two pixel tiles per wave measured slower everywhere: 4.25 vs 3.68 ms per 32 frames)
     const int wv = g_conv_waves ? g_conv_waves : (tiles / 8 * ((Cout + 16 * mt - 1) / (16 * mt)) >= g_conv_wgs ? 8 : 4);
-    const dim3 grid((unsigned)((tiles + wv * pt - 1) / (wv * pt)), (unsigned)((Cout + 16 * mt - 1) / (16 * mt)));
+    *mt_ = mt; *wv_ = wv;
+    *gx = (unsigned)((tiles + wv * pt - 1) / (wv * pt)); *gy = (unsigned)((Cout + 16 * mt - 1) / (16 * mt));
+    return SS_OK;
+}
+
+extern "C" int ss_op32_conv_plan(int N, int H, int W, int Cin, int Cout, int ks, int stride, int* mt, int* waves, int* grid_x, int* grid_y)
+{
+    if (!mt || !waves || !grid_x || !grid_y) return SS_ERR_INVALID;
+    unsigned gx = 0, gy = 0;
+    const int rc = conv32_plan(Cin, 0, Cout, false, N, H, W, Cin, Cout, ks, stride, mt, waves, &gx, &gy);       // dense operands: the strides take no part in the choice
+    if (rc != SS_OK) return rc;
+    *grid_x = (int)gx; *grid_y = (int)gy;
+    return SS_OK;
+}
+
+/* fp32 convolution of the detector graphs (k32_conv): d_x NHWC [N][H][W][.] with pixel stride xs floats (>= Cin, a channel slice of a
+ * wider tensor when larger), d_w [Cout][ks][ks][Cin], d_out NHWC [N][OH][OW][.] with pixel stride os, d_res (may be NULL, added AFTER
+ * the activation) with pixel stride rs; ks 1 | 3, stride 1 | 2, pad ks / 2; act 1 = SiLU, 0 = none; Cin, Cout multiples of 16 and every
+ * base pointer / stride a multiple of 4 floats. */
+extern "C" int ss_op32_conv(void* stream, const void* d_x, int xs, const void* d_w, const void* d_bias, const void* d_res, int rs, void* d_out,
+                            int os, int N, int H, int W, int Cin, int Cout, int ks, int stride, int act)
+{
+    if (!d_x || !d_w || !d_bias || !d_out ||
+        (((uintptr_t)d_x | (uintptr_t)d_out | (uintptr_t)d_res | (uintptr_t)d_w | (uintptr_t)d_bias) & 15))
+        return SS_ERR_INVALID;
+    int mt = 0, wv = 0;
+    unsigned gx = 0, gy = 0;
+    const int rc = conv32_plan(xs, rs, os, d_res != nullptr, N, H, W, Cin, Cout, ks, stride, &mt, &wv, &gx, &gy);
+    if (rc != SS_OK) return rc;
+    const int OH = (H + 2 * (ks / 2) - ks) / stride + 1, OW = (W + 2 * (ks / 2) - ks) / stride + 1;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(gx, gy);
 #define CV32(KS_, ST_, MT_, WV_) if (ks == KS_ && stride == ST_ && mt == MT_ && wv == WV_) { \
         hipLaunchKernelGGL((k32_conv<KS_, ST_, MT_, 1, WV_>), grid, dim3(64 * WV_), 0, st, (const float*)d_x, xs, (const float*)d_w, (const float*)d_bias, \
                            (const float*)d_res, rs, (float*)d_out, os, N, H, W, OH, OW, Cin, Cout, act); \

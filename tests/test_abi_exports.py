@@ -81,6 +81,7 @@ def test_host_side_entry_points_without_a_gpu():
     assert L.ss_op_upcat_f16(None, None, None, None, 1, 4, 4, 8, 8, 1) < 0
     assert L.ss_op_sppf_pools_f16(None, None, None, 1, 40, 40, 8) < 0   # H*W > 1024 (and null tensors)
     assert L.ss_op_conv0_f16(None, None, None, None, None, 1, 8, 100, 16, 2) < 0
+    assert L.ss_op32_conv_plan(1, 8, 8, 16, 16, 3, 1, None, None, None, None) < 0      # null results; with them it plans on the host: test_f32_ref_cpu.py
 
 
 # ---- the binding is derived from the header (strongsort_yolo_amd/cheader.py): checked here with regular expressions of the test's own

@@ -154,8 +154,8 @@ def _block(c1, c2, seed):
 @pytest.mark.parametrize("c1,c2,n,h,w", [(16, 64, 3, 64, 32), (64, 96, 3, 32, 16), (96, 128, 5, 16, 8), (16, 64, 4, 64, 32), (64, 96, 1, 32, 16)])
 def test_chains_match_fp64(c1, c2, n, h, w, form):
     """Every kernel form: 2 = k32_chainsR (register-resident row stream, one chain per wave, two images per workgroup: odd and even
-    image counts; 64 x 32 and 32 x 16 maps — the default), 1 = k32_chains3 (LDS phases, conflict-free lane map), 0 = k32_chains
-    (always for 16 x 8)."""
+    image counts, four on the 16 x 8 maps; all three maps — chains_rowstream accepts C == 32 && W == 8 too), 1 = k32_chains3 (LDS phases,
+    conflict-free lane map; the 16 x 8 maps have no such instantiation and take k32_chains), 0 = k32_chains."""
     from strongsort_yolo_amd import fused32
     fused32.set_option("chains_form", form)
     fused32.set_option("chains_min_n", 1)              # (batches below 128 images would otherwise take the band forms: the per-frame call's batches)
