@@ -332,6 +332,56 @@ int ss_ocsort_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracks, int* n
                          int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
                          double* velocity);
 
+/* ---- Deep OC-SORT (docs/DEEPOCSORT.md): OC-SORT with camera-motion compensation, dynamic appearance and adaptive weighting -------
+ * OC-SORT's frame procedure without the BYTE stage; the first association adds w_association_emb x (adaptive weight) x the
+ * similarity of the row's unit feature and the track's feature, and every track keeps a feature whose EMA weight follows the
+ * detection score.  The state is hung off an existing context like the BYTE and OC-SORT states (they may coexist);
+ * ss_deepoc_create on a context that already has one replaces it.  SS_ERR_INVALID unless 1 <= max_tracks <= SS_MAX_TRACKS,
+ * 1 <= max_dets <= SS_MAX_DETS, 1 <= delta_t <= 8, max_age >= 1, min_hits >= 0, 0 < iou_threshold <= 1, inertia >= 0,
+ * det_thresh < 1, w_association_emb >= 0, 0 <= alpha_fixed_emb <= 1, 0 <= aw_param < 1 and the three flags are 0 or 1.  It
+ * allocates the track features (512 KiB per stream), the group's unit features (8 MiB per stream) and the similarities. */
+typedef struct ss_deepoc_config {
+    double det_thresh;           /* 0.25  first association and births: score > this; the zero of the score's trust */
+    double iou_threshold;        /* 0.3   a pair is kept when its IoU >= this                                  */
+    double inertia;              /* 0.2   weight of the direction-consistency term                             */
+    double w_association_emb;    /* 0.75  weight of the appearance cost                                        */
+    double alpha_fixed_emb;      /* 0.95  the feature EMA's weight at trust 1 (and always, without dynamic_appearance) */
+    double aw_param;             /* 0.5   adaptive weighting: second / first similarity above this lowers the weight */
+    int    max_age;              /* 30    a track is removed when time_since_update > this                     */
+    int    min_hits;             /* 3     rows need hit_streak >= this (or frame_count <= this)                */
+    int    delta_t;              /* 3     observations this many ages back give the directions (1..8)          */
+    int    appearance;           /* 1     0: no appearance cost and no features (d_feats is not read)          */
+    int    dynamic_appearance;   /* 1     the EMA weight follows the detection score                           */
+    int    adaptive_weighting;   /* 1     per-row and per-track factors on w_association_emb                   */
+    int    max_tracks;           /* <= SS_MAX_TRACKS per stream                                                */
+    int    max_dets;             /* <= SS_MAX_DETS per frame                                                   */
+} ss_deepoc_config;
+int ss_deepoc_create(ss_ctx* ctx, const ss_deepoc_config* cfg);
+int ss_deepoc_destroy(ss_ctx* ctx);
+/* A group of n_frames (1..32) frames of every stream, associated strictly in order; the layouts of ss_byte_update_group_feats:
+ * d_dets [n_frames][n_streams][SS_MAX_DETS][6], d_ndets [n_frames][n_streams], d_feats [n_frames][n_streams][SS_MAX_DETS][512] f32
+ * raw features (only the rows scoring above det_thresh are read; NULL allowed when appearance is 0) -> d_out
+ * [n_frames][n_streams][SS_MAX_TRACKS][8] and d_nout as ss_ocsort_update_group.  Every argument is checked first (SS_ERR_INVALID
+ * without touching the device).  Asynchronous on the context's stream, capturable.  Capacity errors as ss_ocsort_update_group
+ * (set until ss_deepoc_reset). */
+int ss_deepoc_update_group(ss_ctx* ctx, int n_frames, const float* d_dets, const int* d_ndets, const float* d_feats, float* d_out,
+                           int* d_nout);
+int ss_deepoc_update(ss_ctx* ctx, const float* d_dets, const int* d_ndets, const float* d_feats, float* d_out, int* d_nout);
+/* Camera-motion compensation (docs/DEEPOCSORT.md step 1b): the following update calls move every track's filter, frozen filter,
+ * last observation and recent observations by d_warps[f][s][8] (ss_cmc_estimate's layout; [6] < 0: no warp) before predicting
+ * frame f.  The caller keeps at least n_frames rows alive; the pointer is read at launch (capturable).  NULL switches it off
+ * (the default).  SS_ERR_INVALID without Deep OC-SORT state. */
+int ss_deepoc_set_gmc(ss_ctx* ctx, const double* d_warps);
+int ss_deepoc_reset(ss_ctx* ctx, int stream);              /* stream < 0: all streams; ids restart at 1, frame_count at 0; the stream's
+                                                              previous ss_cmc_estimate / ss_gmc_sparse_estimate frame is forgotten (no warp
+                                                              next) and its track features are cleared */
+/* Synchronous: the table of one stream in list order, the fields of ss_ocsort_get_tracks. */
+int ss_deepoc_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracks, int* next_id, int* frame_count, int* track_id, int* age,
+                         int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
+                         double* velocity);
+/* Synchronous: the tracks' unit features [n][512] of one stream in ss_deepoc_get_tracks' list order (zeros while appearance is 0). */
+int ss_deepoc_get_features(ss_ctx* ctx, int stream, int cap, float* emb);
+
 /* ---- N4  camera-motion compensation (upstream StrongSORT: tracker.camera_update(prev, cur) before tracker.predict();
  * not in the reference snapshot; optional) ----------------------------------------------------------
  * ss_cmc_estimate: for the n_frames x n_streams BGR u8 frames at d_frames ([F][S] order, frame_stride bytes apart) build

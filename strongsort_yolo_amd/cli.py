@@ -468,10 +468,11 @@ def main(argv=None):
     p.add_argument("--reid-f16", action="store_true", help="throughput mode: ReID crops + OSNet with f16 activations (1.7x the stream rate; appearance distances off by up to 3e-2)")
     p.add_argument("--fp32", action="store_true", help="every network operation in fp32 (the reference passes no half=): detector on the fp32 convolution kernels too — NMS keep lists equal the CPU fp32 network's; about 0.39x the f16 throughput")
     p.add_argument("--reid-weights", default=None, help="OSNet-x0.25 state_dict for the tracker's appearance features (required with --track unless --random-init; "
-                                                          "used by --tracker botsort only with --with-reid, not by bytetrack)")
-    p.add_argument("--tracker", choices=("strongsort", "bytetrack", "botsort", "ocsort"), default="strongsort",
+                                                          "used by --tracker botsort only with --with-reid, by deep_ocsort always, not by bytetrack or ocsort)")
+    p.add_argument("--tracker", choices=("strongsort", "bytetrack", "botsort", "ocsort", "deep_ocsort"), default="strongsort",
                    help="strongsort (default): OSNet appearance + NSA Kalman; bytetrack / botsort: the BYTE family on IoU and scores, no ReID network (docs/BYTETRACK.md); "
-                        "ocsort: OC-SORT, motion only, no ReID network (docs/OCSORT.md)")
+                        "ocsort: OC-SORT, motion only, no ReID network (docs/OCSORT.md); deep_ocsort: Deep OC-SORT, OC-SORT with OSNet appearance and, "
+                        "with --camera-motion, compensated filters and observations (docs/DEEPOCSORT.md; needs --reid-weights or --random-init)")
     p.add_argument("--ocsort-use-byte", action="store_true",
                    help="--tracker ocsort only: OC-SORT's BYTE stage, a second association on the rows scoring between 0.1 and 0.25")
     p.add_argument("--camera-motion", action="store_true",
@@ -554,13 +555,19 @@ def main(argv=None):
         for flag, on in (("--camera-motion", a.camera_motion), ("--with-reid", a.with_reid), ("--with-pose", a.with_pose)):
             if on:
                 p.error(f"{flag} is not available with --tracker ocsort (OC-SORT is motion only, docs/OCSORT.md)")
+    if a.tracker == "deep_ocsort":
+        for flag, on in (("--with-reid", a.with_reid), ("--with-pose", a.with_pose), ("--ocsort-use-byte", a.ocsort_use_byte)):
+            if on:
+                p.error(f"{flag} is not available with --tracker deep_ocsort (its appearance branch is its own and it has no BYTE stage, docs/DEEPOCSORT.md)")
+        if a.reid_model != "osnet":
+            p.error("--reid-model auto is BoT-SORT's: --tracker deep_ocsort reads OSNet features")
     if a.ocsort_use_byte and a.tracker != "ocsort":
         p.error("--ocsort-use-byte is OC-SORT's BYTE stage: it needs --tracker ocsort")
     if a.camera_motion and a.tracker == "bytetrack":
         p.error("--camera-motion needs --tracker strongsort or botsort (ByteTrack has no GMC)")
     if a.gmc_method != "ecc" and not a.camera_motion:
         p.error("--gmc-method is a camera-motion estimator: it needs --camera-motion")
-    if a.gmc_method != "ecc" and a.tracker != "botsort":
+    if a.gmc_method != "ecc" and a.tracker not in ("botsort", "deep_ocsort"):
         p.error("--gmc-method sparseOptFlow is BoT-SORT's GMC: it needs --tracker botsort")
     if a.with_reid and a.tracker != "botsort":
         p.error("--with-reid is BoT-SORT's ReID branch: it needs --tracker botsort")

@@ -147,8 +147,68 @@ class OCSortConfig:
         return asdict(self)
 
 
-# tracker_type of YOLO / FramePipeline / the CLI -> the BYTE configuration it runs (None: StrongSORT and OC-SORT)
-TRACKER_TYPES = ("strongsort", "bytetrack", "botsort", "ocsort")
+@dataclass(frozen=True)
+class DeepOCSortConfig:
+    """Deep OC-SORT (docs/DEEPOCSORT.md, decisions DO-01..): OC-SORT without the BYTE stage, plus camera-motion compensation of
+    filter and observations, a feature EMA whose weight follows the detection score (dynamic_appearance, alpha_fixed_emb) and an
+    appearance cost weighted by how clearly a row or track prefers one partner (adaptive_weighting, w_association_emb, aw_param)."""
+    det_thresh: float = 0.25
+    max_age: int = 30
+    min_hits: int = 3
+    iou_threshold: float = 0.3
+    delta_t: int = 3
+    inertia: float = 0.2
+    w_association_emb: float = 0.75
+    alpha_fixed_emb: float = 0.95
+    aw_param: float = 0.5
+    appearance: bool = True
+    dynamic_appearance: bool = True
+    adaptive_weighting: bool = True
+    # capacities of the device-resident track table (per stream) and of a frame
+    max_tracks: int = 256
+    max_dets: int = 128
+
+    def __post_init__(self):
+        if not 1 <= self.delta_t <= 8:
+            raise ValueError(f"DeepOCSortConfig.delta_t: 1..8, not {self.delta_t}")
+        if self.max_age < 1 or self.min_hits < 0:
+            raise ValueError("DeepOCSortConfig: max_age >= 1 and min_hits >= 0")
+        if not 0.0 < self.iou_threshold <= 1.0:
+            raise ValueError(f"DeepOCSortConfig.iou_threshold: in (0, 1], not {self.iou_threshold}")
+        if not self.inertia >= 0.0:
+            raise ValueError(f"DeepOCSortConfig.inertia: >= 0, not {self.inertia}")
+        if not self.det_thresh < 1.0:
+            raise ValueError(f"DeepOCSortConfig.det_thresh: < 1 (the trust of a score divides by 1 - det_thresh), not {self.det_thresh}")
+        if not self.w_association_emb >= 0.0:
+            raise ValueError(f"DeepOCSortConfig.w_association_emb: >= 0, not {self.w_association_emb}")
+        if not 0.0 <= self.alpha_fixed_emb <= 1.0:
+            raise ValueError(f"DeepOCSortConfig.alpha_fixed_emb: in [0, 1], not {self.alpha_fixed_emb}")
+        if not 0.0 <= self.aw_param < 1.0:
+            raise ValueError(f"DeepOCSortConfig.aw_param: in [0, 1), not {self.aw_param}")
+        if not (0 < self.max_tracks <= 256 and 0 < self.max_dets <= 128):
+            raise ValueError("DeepOCSortConfig: max_tracks <= 256 and max_dets <= 128 (the device table's capacity)")
+
+    def as_dict(self):
+        return asdict(self)
+
+
+# tracker_type of YOLO / FramePipeline / the CLI -> the BYTE configuration it runs (None: StrongSORT, OC-SORT and Deep OC-SORT)
+TRACKER_TYPES = ("strongsort", "bytetrack", "botsort", "ocsort", "deep_ocsort")
+
+
+def deep_ocsort_config(tracker_type: str, with_reid: bool = False, with_pose: bool = False, ocsort_use_byte: bool = False):
+    """tracker_type -> the Deep OC-SORT configuration it runs (None: another tracker).  Its appearance branch is its own: BoT-SORT's
+    options and OC-SORT's BYTE stage are refused by name.  camera_motion is accepted (docs/DEEPOCSORT.md step 1b)."""
+    if tracker_type not in TRACKER_TYPES:
+        raise ValueError(f"tracker_type must be one of {TRACKER_TYPES}, not {tracker_type!r}")
+    if tracker_type != "deep_ocsort":
+        return None
+    for name, on in (("with_reid", with_reid), ("with_pose", with_pose)):
+        if on:
+            raise ValueError(f"{name} is BoT-SORT's: it is not available with tracker_type 'deep_ocsort' (its appearance is always on, docs/DEEPOCSORT.md)")
+    if ocsort_use_byte:
+        raise ValueError("ocsort_use_byte is OC-SORT's BYTE stage: Deep OC-SORT has none (docs/DEEPOCSORT.md)")
+    return DeepOCSortConfig()
 
 
 def ocsort_config(tracker_type: str, use_byte: bool = False, camera_motion: bool = False, with_reid: bool = False, with_pose: bool = False):
@@ -177,7 +237,7 @@ def byte_config(tracker_type: str, with_reid: bool = False, with_pose: bool = Fa
         raise ValueError(f"with_reid is BoT-SORT's ReID branch: tracker_type 'botsort', not {tracker_type!r}")
     if with_pose and tracker_type != "botsort":
         raise ValueError(f"with_pose is BoT-SORT's keypoint term: tracker_type 'botsort', not {tracker_type!r}")
-    if tracker_type == "strongsort":
+    if tracker_type in ("strongsort", "deep_ocsort"):
         return None
     return ByteTrackConfig(kalman="xywh" if tracker_type == "botsort" else "xyah", with_reid=bool(with_reid), with_pose=bool(with_pose))
 
@@ -217,7 +277,7 @@ def check_gmc_method(gmc_method: str, camera_motion: bool, tracker_type: str) ->
         raise ValueError(f"gmc_method must be one of {GMC_METHODS}, not {gmc_method!r}")
     if gmc_method == "sparseOptFlow" and not camera_motion:
         raise ValueError("gmc_method='sparseOptFlow' is a camera-motion estimator: it needs camera_motion=True")
-    if gmc_method == "sparseOptFlow" and tracker_type != "botsort":
+    if gmc_method == "sparseOptFlow" and tracker_type not in ("botsort", "deep_ocsort"):
         raise ValueError(f"gmc_method='sparseOptFlow' is BoT-SORT's GMC: tracker_type 'botsort', not {tracker_type!r} "
                          "(StrongSORT's compensation is ECC, ByteTrack has none, G-05)")
     return gmc_method

@@ -76,6 +76,9 @@ struct ss_ctx {
     // the OC-SORT tracker (ss_ocsort_create), NULL until attached
     struct Oc { SSOcDev dev; std::vector<void*> allocs; };
     Oc* oc = nullptr;
+    // the Deep OC-SORT tracker (ss_deepoc_create), NULL until attached
+    struct DeepOc { SSDeepOcDev dev; std::vector<void*> allocs; };
+    DeepOc* deepoc = nullptr;
     SSJpeg* jpeg = nullptr;     // ss_jpeg_decode_batch's staging areas and planes, made by its first call
     SSJpegEnc* jpeg_enc = nullptr;   // ss_jpeg_encode_batch's buffers, made by its first call
     SSGsi* gsi = nullptr;       // ss_gsi_smooth's staging and scratch slots, made by its first call
@@ -232,6 +235,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->byte) { for (void* p : c->byte->allocs) (void)hipFree(p); delete c->byte; }
     if (c->oc) { for (void* p : c->oc->allocs) (void)hipFree(p); delete c->oc; }
+    if (c->deepoc) { for (void* p : c->deepoc->allocs) (void)hipFree(p); delete c->deepoc; }
     ss_jpeg_free(c->jpeg);
     ss_jpeg_enc_free(c->jpeg_enc);
     ss_gsi_free(c->gsi);
@@ -1034,6 +1038,12 @@ extern "C" int ss_check_errors(ss_ctx* c)
         for (size_t s = 0; s < e.size(); ++s)
             if (e[s]) return fail(c, e[s], "OC-SORT tracker: device error flag on stream " + std::to_string(s));
     }
+    if (c->deepoc) {                                             // Deep OC-SORT's flags
+        HIPCHK(c, hipMemcpyAsync(e.data(), c->deepoc->dev.oc.err, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (size_t s = 0; s < e.size(); ++s)
+            if (e[s]) return fail(c, e[s], "Deep OC-SORT tracker: device error flag on stream " + std::to_string(s));
+    }
     {                                                        // images a device-entropy JPEG call refused (docs/JPEG.md section 12)
         std::string err;
         if (int rcj = ss_jpeg_pending_impl(c->jpeg, err)) return fail(c, rcj, err);
@@ -1390,10 +1400,9 @@ extern "C" int ss_ocsort_destroy(ss_ctx* c)
     return SS_OK;
 }
 
-extern "C" int ss_ocsort_reset(ss_ctx* c, int stream)
+// the streams' lists, counters and error words of an OC-SORT state (OC-SORT's own or Deep OC-SORT's) restart
+static int oc_reset_state(ss_ctx* c, SSOcDev& o, int stream)
 {
-    if (!c || !c->oc || stream >= c->dev.S) return fail(c, SS_ERR_INVALID, "ss_ocsort_reset: no OC-SORT state or bad stream");
-    SSOcDev& o = c->oc->dev;
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? o.S : stream + 1;
     std::vector<int> ones(o.S, 1);
     HIPCHK(c, hipMemsetAsync(o.frame + s0, 0, (s1 - s0) * 4, c->stream));
@@ -1402,6 +1411,36 @@ extern "C" int ss_ocsort_reset(ss_ctx* c, int stream)
     HIPCHK(c, hipMemcpyAsync(o.next_id + s0, ones.data(), (s1 - s0) * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SS_OK;
+}
+
+extern "C" int ss_ocsort_reset(ss_ctx* c, int stream)
+{
+    if (!c || !c->oc || stream >= c->dev.S) return fail(c, SS_ERR_INVALID, "ss_ocsort_reset: no OC-SORT state or bad stream");
+    return oc_reset_state(c, c->oc->dev, stream);
+}
+
+// the tables of an OC-SORT state (o.S set), zeroed; every allocation is recorded in allocs, also when a later one fails
+static int oc_alloc_state(ss_ctx* c, SSOcDev& o, std::vector<void*>& allocs, const char* fn)
+{
+    const size_t S = o.S, T = SS_MAXT;
+    int rc = SS_OK;
+    auto al = [&](auto** p, size_t n) {
+        if (rc != SS_OK) return;
+        void* q = nullptr;
+        const size_t bytes = n * sizeof(**p);
+        hipError_t e = hipMalloc(&q, bytes);
+        if (e == hipSuccess) { allocs.push_back(q); e = hipMemsetAsync(q, 0, bytes, c->stream); }
+        if (e != hipSuccess) rc = fail(c, SS_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+        *p = (std::remove_reference_t<decltype(**p)>*)q;
+    };
+    al(&o.frame, S); al(&o.next_id, S); al(&o.err, S); al(&o.n_trk, S);
+    al(&o.trk, S * T);
+    al(&o.tid, S * T); al(&o.age, S * T); al(&o.tsu, S * T); al(&o.hits, S * T); al(&o.streak, S * T); al(&o.hasobs, S * T);
+    al(&o.obsd, S * T); al(&o.frozen, S * T); al(&o.det, S * T);
+    al(&o.score, S * T); al(&o.cls, S * T); al(&o.lobs, S * T * 4);
+    al(&o.ring, S * T * SS_OC_MAXDT * 4); al(&o.rage, S * T * SS_OC_MAXDT); al(&o.vel, S * T * 2);
+    al(&o.x, S * T * 7); al(&o.P, S * T * 49); al(&o.xf, S * T * 7); al(&o.Pf, S * T * 49); al(&o.spill, S * T * SS_MAXD);
+    return rc;
 }
 
 extern "C" int ss_ocsort_create(ss_ctx* c, const ss_ocsort_config* cfg)
@@ -1421,24 +1460,7 @@ extern "C" int ss_ocsort_create(ss_ctx* c, const ss_ocsort_config* cfg)
     o.max_tracks = cfg->max_tracks; o.max_dets = cfg->max_dets;
     o.det_thresh = (float)cfg->det_thresh; o.low_thresh = (float)cfg->low_thresh;
     o.iou_thr = cfg->iou_threshold; o.inertia = cfg->inertia;
-    const size_t S = o.S, T = SS_MAXT;
-    int rc = SS_OK;
-    auto al = [&](auto** p, size_t n) {
-        if (rc != SS_OK) return;
-        void* q = nullptr;
-        const size_t bytes = n * sizeof(**p);
-        hipError_t e = hipMalloc(&q, bytes);
-        if (e == hipSuccess) { O->allocs.push_back(q); e = hipMemsetAsync(q, 0, bytes, c->stream); }
-        if (e != hipSuccess) rc = fail(c, SS_ERR_HIP, std::string("ss_ocsort_create: ") + hipGetErrorString(e));
-        *p = (std::remove_reference_t<decltype(**p)>*)q;
-    };
-    al(&o.frame, S); al(&o.next_id, S); al(&o.err, S); al(&o.n_trk, S);
-    al(&o.trk, S * T);
-    al(&o.tid, S * T); al(&o.age, S * T); al(&o.tsu, S * T); al(&o.hits, S * T); al(&o.streak, S * T); al(&o.hasobs, S * T);
-    al(&o.obsd, S * T); al(&o.frozen, S * T); al(&o.det, S * T);
-    al(&o.score, S * T); al(&o.cls, S * T); al(&o.lobs, S * T * 4);
-    al(&o.ring, S * T * SS_OC_MAXDT * 4); al(&o.rage, S * T * SS_OC_MAXDT); al(&o.vel, S * T * 2);
-    al(&o.x, S * T * 7); al(&o.P, S * T * 49); al(&o.xf, S * T * 7); al(&o.Pf, S * T * 49); al(&o.spill, S * T * SS_MAXD);
+    int rc = oc_alloc_state(c, o, O->allocs, "ss_ocsort_create");
     c->oc = O;
     if (rc == SS_OK) rc = ss_ocsort_reset(c, -1);
     if (rc != SS_OK) { std::string m = c->err; (void)ss_ocsort_destroy(c); c->err = m; return rc; }
@@ -1460,13 +1482,13 @@ extern "C" int ss_ocsort_update(ss_ctx* c, const float* d_dets, const int* d_nde
     return ss_ocsort_update_group(c, 1, d_dets, d_ndets, d_out, d_nout);
 }
 
-extern "C" int ss_ocsort_get_tracks(ss_ctx* c, int s, int cap, int* n_tracks, int* next_id, int* frame_count, int* track_id, int* age,
-                                    int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
-                                    double* velocity)
+// Synchronous: the table of one stream of an OC-SORT state (OC-SORT's own or Deep OC-SORT's) in list order; fn: the caller's name
+// for the messages.  slots (may be NULL): the list's slots, for a caller that gathers more.
+static int oc_get_tracks(ss_ctx* c, const SSOcDev& o, const std::string& fn, int s, int cap, int* n_tracks, int* next_id, int* frame_count,
+                         int* track_id, int* age, int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P,
+                         float* last_obs, double* velocity, std::vector<int>* slots = nullptr)
 {
-    if (!c || !c->oc || s < 0 || s >= c->dev.S || cap < 0) return fail(c, SS_ERR_INVALID, "ss_ocsort_get_tracks: no OC-SORT state or bad stream");
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const SSOcDev& o = c->oc->dev;
     int nt = 0, nid = 0, fr = 0;
     HIPCHK(c, hipMemcpy(&nt, o.n_trk + s, 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(&nid, o.next_id + s, 4, hipMemcpyDeviceToHost));
@@ -1474,13 +1496,13 @@ extern "C" int ss_ocsort_get_tracks(ss_ctx* c, int s, int cap, int* n_tracks, in
     if (n_tracks) *n_tracks = nt;                                    // the counts also when cap is too small: the caller sizes by them
     if (next_id) *next_id = nid;
     if (frame_count) *frame_count = fr;
-    if (nt < 0 || nt > SS_MAXT) return fail(c, SS_ERR_CAPACITY, "ss_ocsort_get_tracks: corrupt list");
-    if (nt > cap) return fail(c, SS_ERR_CAPACITY, "ss_ocsort_get_tracks: cap too small");
+    if (nt < 0 || nt > SS_MAXT) return fail(c, SS_ERR_CAPACITY, fn + ": corrupt list");
+    if (nt > cap) return fail(c, SS_ERR_CAPACITY, fn + ": cap too small");
     const size_t T = SS_MAXT, sb = (size_t)s * T;
     std::vector<int> trk(T), iv(T);
     HIPCHK(c, hipMemcpy(trk.data(), o.trk + sb, T * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < nt; ++i)
-        if (trk[i] < 0 || trk[i] >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, "ss_ocsort_get_tracks: corrupt list");
+        if (trk[i] < 0 || trk[i] >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, fn + ": corrupt list");
     auto ints = [&](const int* src, int* dst) -> int {
         if (!dst) return SS_OK;
         HIPCHK(c, hipMemcpy(iv.data(), src + sb, T * 4, hipMemcpyDeviceToHost));
@@ -1509,6 +1531,129 @@ extern "C" int ss_ocsort_get_tracks(ss_ctx* c, int s, int cap, int* n_tracks, in
         HIPCHK(c, hipMemcpy(iv.data(), o.hasobs + sb, T * 4, hipMemcpyDeviceToHost));
         for (int i = 0; i < nt; ++i) for (int k = 0; k < 4; ++k) last_obs[i * 4 + k] = iv[trk[i]] ? lv[(size_t)trk[i] * 4 + k] : -1.0f;
     }
+    if (slots) slots->assign(trk.begin(), trk.begin() + nt);
+    return SS_OK;
+}
+
+extern "C" int ss_ocsort_get_tracks(ss_ctx* c, int s, int cap, int* n_tracks, int* next_id, int* frame_count, int* track_id, int* age,
+                                    int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
+                                    double* velocity)
+{
+    if (!c || !c->oc || s < 0 || s >= c->dev.S || cap < 0) return fail(c, SS_ERR_INVALID, "ss_ocsort_get_tracks: no OC-SORT state or bad stream");
+    return oc_get_tracks(c, c->oc->dev, "ss_ocsort_get_tracks", s, cap, n_tracks, next_id, frame_count, track_id, age, time_since_update, hits,
+                         hit_streak, frozen, x, P, last_obs, velocity);
+}
+
+// ---- Deep OC-SORT (ss_deepoc.hip, docs/DEEPOCSORT.md) -------------------------------------------------------------------------------
+extern "C" int ss_deepoc_destroy(ss_ctx* c)
+{
+    if (!c) return fail(nullptr, SS_ERR_INVALID, "ss_deepoc_destroy: null context");
+    if (!c->deepoc) return SS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (void* p : c->deepoc->allocs) HIPCHK(c, hipFree(p));
+    delete c->deepoc;
+    c->deepoc = nullptr;
+    return SS_OK;
+}
+
+extern "C" int ss_deepoc_reset(ss_ctx* c, int stream)
+{
+    if (!c || !c->deepoc || stream >= c->dev.S) return fail(c, SS_ERR_INVALID, "ss_deepoc_reset: no Deep OC-SORT state or bad stream");
+    SSDeepOcDev& d = c->deepoc->dev;
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? d.oc.S : stream + 1;
+    HIPCHK(c, hipMemsetAsync(c->cmc_prev_valid + s0, 0, (s1 - s0) * 4, c->stream));     // G-04: the next frame gets no warp
+    HIPCHK(c, hipMemsetAsync(c->gmc.prev_valid + s0, 0, (s1 - s0) * 4, c->stream));     // ... from either estimator
+    HIPCHK(c, hipMemsetAsync(d.emb + (size_t)s0 * SS_MAXT * SS_F, 0, (size_t)(s1 - s0) * SS_MAXT * SS_F * 4, c->stream));
+    return oc_reset_state(c, d.oc, stream);
+}
+
+extern "C" int ss_deepoc_create(ss_ctx* c, const ss_deepoc_config* cfg)
+{
+    if (!c || !cfg) return fail(c, SS_ERR_INVALID, "ss_deepoc_create: null argument");
+    auto flag = [](int v) { return v == 0 || v == 1; };
+    if (cfg->max_tracks < 1 || cfg->max_tracks > SS_MAXT || cfg->max_dets < 1 || cfg->max_dets > SS_MAXD || cfg->delta_t < 1 ||
+        cfg->delta_t > SS_OC_MAXDT || cfg->max_age < 1 || cfg->min_hits < 0 || !(cfg->iou_threshold > 0.0 && cfg->iou_threshold <= 1.0) ||
+        !(cfg->inertia >= 0.0) || !(cfg->det_thresh < 1.0) || !(cfg->w_association_emb >= 0.0) ||
+        !(cfg->alpha_fixed_emb >= 0.0 && cfg->alpha_fixed_emb <= 1.0) || !(cfg->aw_param >= 0.0 && cfg->aw_param < 1.0) ||
+        !flag(cfg->appearance) || !flag(cfg->dynamic_appearance) || !flag(cfg->adaptive_weighting))
+        return fail(c, SS_ERR_INVALID, "ss_deepoc_create: 1 <= max_tracks <= 256, 1 <= max_dets <= 128, 1 <= delta_t <= 8, max_age >= 1, "
+                                       "min_hits >= 0, 0 < iou_threshold <= 1, inertia >= 0, det_thresh < 1, w_association_emb >= 0, "
+                                       "0 <= alpha_fixed_emb <= 1, 0 <= aw_param < 1, flags 0 / 1");
+    if (int rc = ss_deepoc_destroy(c)) return rc;
+    ss_ctx::DeepOc* D = new ss_ctx::DeepOc();
+    SSDeepOcDev& d = D->dev;
+    memset(&d, 0, sizeof d);
+    SSOcDev& o = d.oc;
+    o.S = c->dev.S;
+    o.max_age = cfg->max_age; o.min_hits = cfg->min_hits; o.delta_t = cfg->delta_t; o.use_byte = 0;
+    o.max_tracks = cfg->max_tracks; o.max_dets = cfg->max_dets;
+    o.det_thresh = (float)cfg->det_thresh; o.low_thresh = (float)cfg->det_thresh;
+    o.iou_thr = cfg->iou_threshold; o.inertia = cfg->inertia;
+    d.appearance = cfg->appearance; d.dynamic = cfg->dynamic_appearance; d.adaptive = cfg->adaptive_weighting;
+    d.det_thresh = cfg->det_thresh; d.w_emb = cfg->w_association_emb; d.alpha_fixed = cfg->alpha_fixed_emb; d.aw = cfg->aw_param;
+    int rc = oc_alloc_state(c, o, D->allocs, "ss_deepoc_create");
+    const size_t S = o.S;
+    const size_t bytes[3] = {S * SS_MAXT * SS_F * 4, (size_t)SS_FMAX * S * SS_MAXD * SS_F * 4, S * SS_MAXT * SS_MAXD * 8};
+    void* q[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3 && rc == SS_OK; ++i) {
+        hipError_t e = hipMalloc(&q[i], bytes[i]);
+        if (e == hipSuccess) { D->allocs.push_back(q[i]); e = hipMemsetAsync(q[i], 0, bytes[i], c->stream); }
+        if (e != hipSuccess) rc = fail(c, SS_ERR_HIP, std::string("ss_deepoc_create: ") + hipGetErrorString(e));
+    }
+    d.emb = (float*)q[0]; d.ufeat = (float*)q[1]; d.E = (double*)q[2];
+    c->deepoc = D;
+    if (rc == SS_OK) rc = ss_deepoc_reset(c, -1);
+    if (rc != SS_OK) { std::string m = c->err; (void)ss_deepoc_destroy(c); c->err = m; return rc; }
+    return SS_OK;
+}
+
+// The following update calls read d_warps[f][s][8] (ss_cmc_estimate's layout) for frame f; the pointer goes into the launch
+// arguments, so the call is capturable.  NULL: off.
+extern "C" int ss_deepoc_set_gmc(ss_ctx* c, const double* d_warps)
+{
+    if (!c || !c->deepoc) return fail(c, SS_ERR_INVALID, "ss_deepoc_set_gmc: no Deep OC-SORT state (ss_deepoc_create)");
+    c->deepoc->dev.gmc = d_warps;
+    return SS_OK;
+}
+
+// Two launches on the context's stream (unit features, then the group): capturable.
+extern "C" int ss_deepoc_update_group(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, const float* d_feats, float* d_out,
+                                      int* d_nout)
+{
+    if (!c || !d_dets || !d_ndets || !d_out || !d_nout) return fail(c, SS_ERR_INVALID, "ss_deepoc_update_group: null argument");
+    if (!c->deepoc) return fail(c, SS_ERR_INVALID, "ss_deepoc_update_group: no Deep OC-SORT state (ss_deepoc_create)");
+    if (c->deepoc->dev.appearance && !d_feats) return fail(c, SS_ERR_INVALID, "ss_deepoc_update_group: appearance is on and d_feats is NULL");
+    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_deepoc_update_group: 1 <= n_frames <= SS_FMAX");
+    ss_launch_deepoc_group(c->deepoc->dev, n_frames, d_dets, d_ndets, d_feats, d_out, d_nout, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+extern "C" int ss_deepoc_update(ss_ctx* c, const float* d_dets, const int* d_ndets, const float* d_feats, float* d_out, int* d_nout)
+{
+    return ss_deepoc_update_group(c, 1, d_dets, d_ndets, d_feats, d_out, d_nout);
+}
+
+extern "C" int ss_deepoc_get_tracks(ss_ctx* c, int s, int cap, int* n_tracks, int* next_id, int* frame_count, int* track_id, int* age,
+                                    int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
+                                    double* velocity)
+{
+    if (!c || !c->deepoc || s < 0 || s >= c->dev.S || cap < 0) return fail(c, SS_ERR_INVALID, "ss_deepoc_get_tracks: no Deep OC-SORT state or bad stream");
+    return oc_get_tracks(c, c->deepoc->dev.oc, "ss_deepoc_get_tracks", s, cap, n_tracks, next_id, frame_count, track_id, age, time_since_update,
+                         hits, hit_streak, frozen, x, P, last_obs, velocity);
+}
+
+// Synchronous: the tracks' unit features [n][512] of one stream in ss_deepoc_get_tracks' list order.
+extern "C" int ss_deepoc_get_features(ss_ctx* c, int s, int cap, float* emb)
+{
+    if (!c || !c->deepoc || s < 0 || s >= c->dev.S || cap < 0 || !emb)
+        return fail(c, SS_ERR_INVALID, "ss_deepoc_get_features: no Deep OC-SORT state, bad stream or NULL");
+    std::vector<int> slots;
+    if (const int rc = oc_get_tracks(c, c->deepoc->dev.oc, "ss_deepoc_get_features", s, cap, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &slots)) return rc;
+    std::vector<float> em((size_t)SS_MAXT * SS_F);
+    HIPCHK(c, hipMemcpy(em.data(), c->deepoc->dev.emb + (size_t)s * SS_MAXT * SS_F, em.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < slots.size(); ++i) memcpy(emb + i * SS_F, em.data() + (size_t)slots[i] * SS_F, SS_F * 4);
     return SS_OK;
 }
 

@@ -385,6 +385,19 @@ struct SSOcDev {
     double* spill;                      // [S][MAXT * MAXD] cost matrices that do not fit the LDS
 };
 
+// Device state of the Deep OC-SORT tracker (csrc/ss_deepoc.hip, docs/DEEPOCSORT.md), hung off a context by ss_deepoc_create: an OC-SORT
+// state of its own (use_byte 0) and what the appearance and camera-motion steps add.
+struct SSDeepOcDev {
+    SSOcDev oc;
+    int appearance, dynamic, adaptive;  // 0 / 1
+    double det_thresh;                  // the f64 threshold of the score's trust (oc.det_thresh is its float32 value for the split)
+    double w_emb, alpha_fixed, aw;      // w_association_emb, alpha_fixed_emb, aw_param
+    float* emb;                         // [S][MAXT][F] unit track features by slot
+    float* ufeat;                       // [FMAX][S][MAXD][F] unit features of the group's high rows (k_deepoc_feats)
+    double* E;                          // [S][MAXD * MAXT] the first association's similarities, row-major rows x tracks
+    const double* gmc;                  // [F][S][8] warps (ss_deepoc_set_gmc), NULL: off
+};
+
 // Device state of the sparse-optical-flow camera-motion estimator (csrc/ss_gmc.hip, docs/BYTETRACK.md §1f), hung off a context by
 // the first ss_gmc_sparse_estimate call for a frame size.  Image slot 0 of a stream is the remembered frame, slots 1..F the group's.
 #define SS_GMC_MAXC 1000                // corners per image (S-05)

@@ -62,6 +62,8 @@ void ss_launch_byte_group(const SSByteDev& b, int F, const float* dets, const in
 void ss_launch_byte_group_kpts(const SSByteDev& b, int F, const float* dets, const int* ndets, const float* kpts, long long stride, int off,
                                const float* geom, float* out, int* nout, hipStream_t st);
 void ss_launch_ocsort_group(const SSOcDev& o, int F, const float* dets, const int* ndets, float* out, int* nout, hipStream_t st);
+void ss_launch_deepoc_group(const SSDeepOcDev& x, int F, const float* dets, const int* ndets, const float* feats, float* out, int* nout,
+                            hipStream_t st);
 void ss_launch_native_feats(int n_img, int half, const void* const* p, const long long* img_stride, const long long* row_stride,
                             const long long* pix_stride, const int* channels, const int* height, const int* width, int s,
                             const int* keep, long long keep_stride, const int* counts, float* out, hipStream_t st);

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from .config import StrongSortConfig, DetectConfig, ByteTrackConfig, OCSortConfig
+from .config import StrongSortConfig, DetectConfig, ByteTrackConfig, OCSortConfig, DeepOCSortConfig
 from .lib import MAX_TRACKS, MAX_DETS, FEAT_DIM, OUT_COLS
 
 
@@ -936,15 +936,91 @@ class OCSortEngine:
 
     def tracks(self, stream: int = 0) -> dict:
         """The table of one stream in list order (oldest track first): what tests/ocsort_ref.py's tracks() returns."""
+        return self._tracks(self.L.ss_ocsort_get_tracks, stream)
+
+    def _tracks(self, get, stream: int) -> dict:
         T = MAX_TRACKS
         nt, nid, fr = C.c_int(), C.c_int(), C.c_int()
         names = ("track_id", "age", "time_since_update", "hits", "hit_streak", "frozen")
         iv = {n: np.zeros(T, np.int32) for n in names}
         x, P, lo, vel = np.zeros((T, 7)), np.zeros((T, 49)), np.zeros((T, 4), np.float32), np.zeros((T, 2))
         ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
-        self._ck(self.L.ss_ocsort_get_tracks(self.base.ctx, stream, T, C.byref(nt), C.byref(nid), C.byref(fr),
-                                             *[iv[n].ctypes.data_as(ip) for n in names], x.ctypes.data_as(dp), P.ctypes.data_as(dp),
+        self._ck(get(self.base.ctx, stream, T, C.byref(nt), C.byref(nid), C.byref(fr),
+                 *[iv[n].ctypes.data_as(ip) for n in names], x.ctypes.data_as(dp), P.ctypes.data_as(dp),
                                              lo.ctypes.data_as(C.POINTER(C.c_float)), vel.ctypes.data_as(dp)))
         k = nt.value
         return dict({n: iv[n][:k].copy() for n in names}, x=x[:k].copy(), P=P[:k].copy(), last_obs=lo[:k].copy(), velocity=vel[:k].copy(),
                     n_tracks=k, next_id=nid.value, frame_count=fr.value)
+
+
+class DeepOCSortEngine(OCSortEngine):
+    """Deep OC-SORT (csrc/ss_deepoc.hip, docs/DEEPOCSORT.md) on the context of a TrackerEngine: OCSortEngine's shape with the
+    detections' raw features (read while cfg.appearance is on) and BoT-SORT's set_cmc.  It stands where the BYTE / OC-SORT engine
+    stands.  `engine`: share the context of an existing TrackerEngine; None: a context of its own."""
+
+    pose = False
+
+    def __init__(self, cfg: DeepOCSortConfig | None = None, n_streams: int = 1, device: int = 0, engine: TrackerEngine | None = None):
+        self.cfg = cfg or DeepOCSortConfig()
+        self._own = engine is None
+        self.base = TrackerEngine(StrongSortConfig(), n_streams, device) if engine is None else engine
+        self.S, self.device, self.L = self.base.S, self.base.device, self.base.L
+        c = _lib.make_deepoc_config(self.cfg)
+        self._ck(self.L.ss_deepoc_create(self.base.ctx, C.byref(c)))
+        self.reid = bool(self.cfg.appearance)
+        self._cmc_keep = None
+        self.out = torch.zeros(self.S, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=self.device)
+        self.nout = torch.zeros(self.S, dtype=torch.int32, device=self.device)
+        self.use_stream, self.use_current_stream = self.base.use_stream, self.base.use_current_stream
+        self.check_errors, self.cmc_estimate = self.base.check_errors, self.base.cmc_estimate
+        self.gmc_sparse_estimate, self.estimate_warps = self.base.gmc_sparse_estimate, self.base.estimate_warps
+
+    def close(self):
+        if self._own:
+            self.base.close()
+        elif getattr(self.base, "ctx", None) and self.base.ctx.value:
+            torch.cuda.synchronize(self.device)
+            self._ck(self.L.ss_deepoc_destroy(self.base.ctx))
+
+    def reset(self, stream: int = -1):
+        """Restart the stream(s): ids from 1, frame_count from 0, features cleared, and the next estimated frame gets no warp."""
+        self._ck(self.L.ss_deepoc_reset(self.base.ctx, stream))
+
+    def set_cmc(self, warps):
+        """Step 1b: the following update calls move every track by these warps ([F,S,8] float64, ss_cmc_estimate's layout, at least
+        as many rows as the calls' frames) before predicting; None: off."""
+        self._ck(self.L.ss_deepoc_set_gmc(self.base.ctx, _ptr(warps)))
+        self._cmc_keep = warps
+
+    def _feats(self, feats, rows):
+        if not self.reid:
+            return None
+        if feats is None:
+            raise ValueError("DeepOCSortEngine: appearance needs the detections' features [.., 128, 512] f32")
+        if feats.dtype != torch.float32 or not feats.is_contiguous() or feats.numel() != rows * MAX_DETS * FEAT_DIM:
+            raise ValueError(f"DeepOCSortEngine: feats must be contiguous float32 [{rows} x {MAX_DETS} x {FEAT_DIM}]")
+        return feats
+
+    def update_device(self, dets, ndets, feats=None, img_hw=None, out=None, nout=None):
+        """All streams, one frame: dets [S,128,6] f32, ndets [S] i32, feats [S,128,512] f32 (raw, device) -> (rows [S,256,8],
+        counts [S]) device tensors, asynchronous.  img_hw is accepted for TrackerEngine's call shape and unused."""
+        out = self.out if out is None else out
+        nout = self.nout if nout is None else nout
+        return self.update_group(1, dets, ndets, feats, img_hw, out, nout)
+
+    def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout):
+        """A group of n_frames (<= 32) frames of all streams in one call: dets [F,S,128,6] f32, ndets [F,S] i32, feats
+        [F,S,128,512] f32 -> rows out [F,S,256,8], counts nout [F,S] (device tensors, asynchronous); frames are associated in order."""
+        f = self._feats(feats, int(n_frames) * self.S)
+        self._ck(self.L.ss_deepoc_update_group(self.base.ctx, int(n_frames), _ptr(dets), _ptr(ndets), _ptr(f), _ptr(out), _ptr(nout)))
+        return out, nout
+
+    def tracks(self, stream: int = 0) -> dict:
+        """The table of one stream in list order (oldest track first): what tests/deepocsort_ref.py's tracks() returns."""
+        return self._tracks(self.L.ss_deepoc_get_tracks, stream)
+
+    def features(self, stream: int = 0) -> np.ndarray:
+        """The tracks' unit features [n,512] f32 of one stream in tracks()' list order."""
+        em = np.zeros((MAX_TRACKS, FEAT_DIM), np.float32)
+        self._ck(self.L.ss_deepoc_get_features(self.base.ctx, stream, MAX_TRACKS, em.ctypes.data_as(C.POINTER(C.c_float))))
+        return em[:self.tracks(stream)["n_tracks"]].copy()

@@ -22,8 +22,8 @@ SS_OK, SS_ERR_INVALID, SS_ERR_CAPACITY, SS_ERR_HIP, SS_ERR_INFEASIBLE = (
 MAX_TRACKS, MAX_DETS, FEAT_DIM, OUT_COLS, DST_F16, DST_HWC, DST_U8 = (
     _H.defines["SS_" + n] for n in ("MAX_TRACKS", "MAX_DETS", "FEAT_DIM", "OUT_COLS", "DST_F16", "DST_HWC", "DST_U8"))
 EXPORTS = list(_H.functions)
-ss_config, ss_byte_config, ss_ocsort_config, ss_conv_desc, ss_native_map = (
-    _H.structs[n] for n in ("ss_config", "ss_byte_config", "ss_ocsort_config", "ss_conv_desc", "ss_native_map"))
+ss_config, ss_byte_config, ss_ocsort_config, ss_deepoc_config, ss_conv_desc, ss_native_map = (
+    _H.structs[n] for n in ("ss_config", "ss_byte_config", "ss_ocsort_config", "ss_deepoc_config", "ss_conv_desc", "ss_native_map"))
 
 
 class SSError(RuntimeError):
@@ -84,3 +84,9 @@ def make_byte_config(cfg) -> ss_byte_config:
 def make_ocsort_config(cfg) -> ss_ocsort_config:
     return ss_ocsort_config(cfg.det_thresh, cfg.low_thresh, cfg.iou_threshold, cfg.inertia, cfg.max_age, cfg.min_hits, cfg.delta_t,
                             int(cfg.use_byte), cfg.max_tracks, cfg.max_dets)
+
+
+def make_deepoc_config(cfg) -> ss_deepoc_config:
+    return ss_deepoc_config(cfg.det_thresh, cfg.iou_threshold, cfg.inertia, cfg.w_association_emb, cfg.alpha_fixed_emb, cfg.aw_param,
+                            cfg.max_age, cfg.min_hits, cfg.delta_t, int(cfg.appearance), int(cfg.dynamic_appearance),
+                            int(cfg.adaptive_weighting), cfg.max_tracks, cfg.max_dets)

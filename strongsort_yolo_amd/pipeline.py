@@ -56,7 +56,10 @@ class FramePipeline:
         # which estimator fills the group's warps; the tracker call reads either the same way.
         # tracker = "ocsort": OC-SORT (csrc/ss_ocsort.hip, docs/OCSORT.md) — motion only: like the BYTE family without ReID it builds no
         # OSNet and cuts no crops, and its engine stands where the BYTE engine stands (self.byte / self.trk: the same stage bodies).
-        from .config import byte_config, ocsort_config, check_reid_model, check_pose, check_gmc_method
+        # tracker = "deep_ocsort": Deep OC-SORT (csrc/ss_deepoc.hip, docs/DEEPOCSORT.md) — OSNet, crops and ReID stages stay as for botsort
+        # with with_reid, the warps stage as for botsort; its engine stands where the BYTE engine stands.
+        from .config import byte_config, ocsort_config, deep_ocsort_config, check_reid_model, check_pose, check_gmc_method
+        self.deep_cfg = deep_ocsort_config(tracker, with_reid, with_pose, ocsort_use_byte)
         self.oc_cfg = ocsort_config(tracker, ocsort_use_byte, cmc, with_reid, with_pose)
         self.byte_cfg = byte_config(tracker, with_reid, with_pose)
         self.gmc_method = check_gmc_method(gmc_method, cmc, tracker)
@@ -75,6 +78,9 @@ class FramePipeline:
         elif self.oc_cfg is not None:
             from .engine import OCSortEngine
             self.byte = self.trk = OCSortEngine(self.oc_cfg, engine=self.eng)
+        elif self.deep_cfg is not None:
+            from .engine import DeepOCSortEngine
+            self.byte = self.trk = DeepOCSortEngine(self.deep_cfg, engine=self.eng)
         dev = self.dev = self.eng.device
         self.half, self.dtype = half, torch.float16 if half else torch.float32
         # reid_half=False: the ReID crops and OSNet in fp32 on the hand-written fp32 kernels (fused32.py, csrc/ss_ops32.hip:

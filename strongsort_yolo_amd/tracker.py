@@ -13,8 +13,8 @@ import numpy as np
 import torch
 
 from . import nets
-from .config import StrongSortConfig, ByteTrackConfig, OCSortConfig, check_reid_model, check_gmc_method
-from .engine import TrackerEngine, ByteTrackEngine, OCSortEngine
+from .config import StrongSortConfig, ByteTrackConfig, OCSortConfig, DeepOCSortConfig, check_reid_model, check_gmc_method
+from .engine import TrackerEngine, ByteTrackEngine, OCSortEngine, DeepOCSortEngine
 from .lib import MAX_DETS, FEAT_DIM
 
 
@@ -195,6 +195,84 @@ class OCSORTTracker:
         self._dets[0, :n].copy_(dets, non_blocking=True)
         self._n.fill_(n)
         out, nout = self.eng.update_device(self._dets, self._n)
+        torch.cuda.synchronize(self.dev)
+        self.eng.check_errors()
+        return out[0, : int(nout[0])].cpu().numpy()
+
+    def reset(self):
+        self.eng.reset(-1)
+
+    def close(self):
+        self.eng.close()
+
+
+class DeepOCSORTTracker:
+    """Deep OC-SORT for one video stream (docs/DEEPOCSORT.md), shaped like ByteTracker with with_reid.
+         dets     [N,6] float  x1,y1,x2,y2,conf,cls in frame pixels (numpy or torch), N <= cfg.max_dets
+         frame    uint8 [H,W,3] BGR (numpy, or a torch tensor on the device): with camera_motion=True, and for the crops when
+                  `features` is None
+         features [N,k] raw features of the rows (k <= 512, zero-padded); None: the crops go through OSNet-x0.25 (reid_weights,
+                  loaded as StrongSORT loads them; fp16 selects half activations)
+       returns float32 [M,8] as OCSORTTracker.update.  camera_motion=True: step 1b with the warp between the previous frame and this
+       one, estimated on the device (gmc_method "ecc" or "sparseOptFlow").  cfg.appearance=False: no network, no features."""
+
+    def __init__(self, cfg: Optional[DeepOCSortConfig] = None, device: int = 0, camera_motion: bool = False,
+                 reid_weights: Optional[str] = None, fp16: bool = False, random_init_ok: bool = False, gmc_method: str = "ecc",
+                 reid_seed: int = 1):
+        self.cfg = cfg or DeepOCSortConfig()
+        self.gmc_method = check_gmc_method(gmc_method, camera_motion, "deep_ocsort")
+        self.reid = None
+        if self.cfg.appearance and (reid_weights or random_init_ok):
+            self.reid = nets.build_reid(reid_seed)
+            nets.load_weights(self.reid, reid_weights, "OSNet-x0.25 ReID", random_init_ok)
+        self.eng = DeepOCSortEngine(self.cfg, 1, device)
+        self.dev = self.eng.device
+        self.camera_motion = bool(camera_motion)
+        self.dtype = torch.float16 if fp16 else torch.float32
+        if self.reid is not None:
+            self.reid = self.reid.to(self.dev, self.dtype).to(memory_format=torch.channels_last)
+        self._feats = torch.zeros(1, MAX_DETS, FEAT_DIM, dtype=torch.float32, device=self.dev) if self.cfg.appearance else None
+        self._dets = torch.zeros(1, MAX_DETS, 6, dtype=torch.float32, device=self.dev)
+        self._n = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self._warps = torch.zeros(1, 1, 8, dtype=torch.float64, device=self.dev) if self.camera_motion else None
+
+    @torch.no_grad()
+    def update(self, dets, frame=None, features=None) -> np.ndarray:
+        self.eng.use_current_stream()
+        dets = torch.as_tensor(dets, dtype=torch.float32).reshape(-1, 6)
+        n = dets.shape[0]
+        if n > self.cfg.max_dets:
+            raise ValueError(f"at most {self.cfg.max_dets} detections per frame (got {n})")
+        frame_t = None
+        if frame is not None and (self.camera_motion or (self.cfg.appearance and features is None)):
+            frame_t = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame))
+            frame_t = frame_t.to(self.dev, non_blocking=True).contiguous()
+        if self.camera_motion:
+            if frame_t is None:
+                raise ValueError("camera_motion=True: update(dets, frame) needs the BGR frame")
+            self.eng.estimate_warps(self.gmc_method, frame_t[None], 1, self._warps)
+            self.eng.set_cmc(self._warps)
+        self._dets[0, :n].copy_(dets, non_blocking=True)
+        self._n.fill_(n)
+        if not self.cfg.appearance:
+            if features is not None:
+                raise ValueError("features given, but cfg.appearance is off")
+        elif features is not None:
+            ft = torch.as_tensor(features, dtype=torch.float32)
+            ft = ft.reshape(n, -1) if n else ft.reshape(0, ft.shape[-1] if ft.dim() else 0)
+            k = ft.shape[1]
+            if k > FEAT_DIM:
+                raise ValueError(f"features [N,k]: k <= {FEAT_DIM} (got {k})")
+            self._feats[0, :n, :k].copy_(ft)
+            self._feats[0, :n, k:].zero_()
+        elif self.reid is None:
+            raise ValueError("no ReID network was loaded (reid_weights): update(dets, frame, features) needs the rows' features [N,k]")
+        elif frame_t is None:
+            raise ValueError("appearance: update(dets, frame) needs the BGR frame or features [N,512]")
+        elif n:
+            crops = self.eng.base.crop_norm(frame_t, self._dets[0], n, half=self.dtype == torch.float16)
+            self._feats[0, :n].copy_(self.reid(crops.contiguous(memory_format=torch.channels_last)))
+        out, nout = self.eng.update_device(self._dets, self._n, self._feats)
         torch.cuda.synchronize(self.dev)
         self.eng.check_errors()
         return out[0, : int(nout[0])].cpu().numpy()

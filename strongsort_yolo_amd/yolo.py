@@ -18,7 +18,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .config import DetectConfig, StrongSortConfig, byte_config, ocsort_config, check_reid_model, check_gmc_method
+from .config import DetectConfig, StrongSortConfig, byte_config, ocsort_config, deep_ocsort_config, check_reid_model, check_gmc_method
 
 COCO_NAMES = ("person bicycle car motorcycle airplane bus train truck boat traffic_light fire_hydrant stop_sign "
               "parking_meter bench bird cat dog horse sheep cow elephant bear zebra giraffe backpack umbrella handbag tie "
@@ -318,7 +318,12 @@ class YOLO:
         tracker_type "ocsort": OC-SORT on the device (docs/OCSORT.md) — a 7-state SORT filter with observation-centric re-update,
         momentum and recovery; motion only, so no ReID network or weights, NMS at conf 0.1 in track() as for the BYTE family, and
         camera_motion, with_reid and with_pose are ValueErrors.  ocsort_use_byte ("ocsort" only): its BYTE stage on the rows between
-        0.1 and 0.25."""
+        0.1 and 0.25.
+        tracker_type "deep_ocsort": Deep OC-SORT on the device (docs/DEEPOCSORT.md) — OC-SORT without the BYTE stage, with OSNet-x0.25
+        features of every tracked row (reid_weights, reid_fp32 and half as for StrongSORT) in an adaptively weighted appearance cost,
+        a feature EMA that follows the detection score, and, with camera_motion, the warps (gmc_method "ecc" or "sparseOptFlow")
+        applied to filters and observations.  with_reid, with_pose, ocsort_use_byte and reid_model="auto" are ValueErrors."""
+        deep_ocsort_config(tracker_type, with_reid, with_pose, ocsort_use_byte)               # ValueError on anything else
         ocsort_config(tracker_type, ocsort_use_byte, camera_motion, with_reid, with_pose)      # ValueError on anything else
         byte_config(tracker_type, with_reid, with_pose)
         check_reid_model(reid_model, with_reid, reid_weights)
@@ -523,7 +528,7 @@ class YOLO:
         return [Results(image, self.names, Boxes(rows[:, :4], rows[:, 6], rows[:, 5], rows[:, 4]),
                         None if kpts is None else Keypoints(kpts[di]), None if masks is None else masks[di])]
 
-    TRACKERS = ("strongsort.yaml", "strongsort", "botsort.yaml", "bytetrack.yaml", "ocsort.yaml")
+    TRACKERS = ("strongsort.yaml", "strongsort", "botsort.yaml", "bytetrack.yaml", "ocsort.yaml", "deep_ocsort.yaml")
 
     def _check_tracker(self, tracker):
         """`tracker=`: the tracker is chosen when the model is built (`tracker_type`), StrongSORT by default (BASELINE north_star).
@@ -538,7 +543,7 @@ class YOLO:
                 import warnings
                 self._tracker_warned = True
                 warnings.warn(f"tracker={tracker!r}: this model was built with tracker_type={self.tracker_type!r}, which rules; "
-                              f"its parameters are strongsort_yolo_amd.config.{'OCSortConfig' if self.tracker_type == 'ocsort' else 'ByteTrackConfig'}",
+                              f"its parameters are strongsort_yolo_amd.config.{ {'ocsort': 'OCSortConfig', 'deep_ocsort': 'DeepOCSortConfig'}.get(self.tracker_type, 'ByteTrackConfig') }",
                               RuntimeWarning, stacklevel=3)
             return
         if not name.startswith("strongsort") and not self._tracker_warned:
