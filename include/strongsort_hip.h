@@ -857,6 +857,56 @@ int ss_aflink_cost(ss_ctx* ctx, int n_tracklets, const int* offsets, const doubl
 int ss_aflink_match(ss_ctx* ctx, int n_tracklets, long long n_pairs, const int* pair_i, const int* pair_j, const double* cost, double thr_p,
                     int* successor);
 
+/* ---- analytics behind the trackers: line crossings, zones, dwell and a heat map (csrc/ss_zone.hip, docs/ZONES.md) ---- */
+/* Host only: the caps (16 lines, 16 zones, 32 vertices a zone, 1024 live tracks a stream). */
+int ss_zone_max_lines(void);
+int ss_zone_max_zones(void);
+int ss_zone_max_vertices(void);
+int ss_zone_max_live(void);
+typedef struct ss_zone_config {
+    int anchor;                  /* 1     0: centre of the box, 1: middle of its bottom edge                   */
+    int max_gap;                 /* 30    a track unseen for more frames than this has lost its state (1..32)  */
+    int n_classes;               /* 80    classes the line counts are kept for (1..128)                        */
+    int heat;                    /* 0     0: off, 1: +1 at the anchor's cell, 2: +1 in every cell under the box */
+    int heat_cell_log2;          /* 3     a heat cell is 2^k pixels a side (0..6)                              */
+    int frame_h, frame_w;        /*       frame size in pixels (read when heat is on)                          */
+} ss_zone_config;
+/* The state is hung off an existing context and shared by its streams; a second call replaces it.  lines [n_lines][4] = ax, ay, bx,
+ * by (directed a -> b); zone q owns the vertices poly_off[q] .. poly_off[q+1]-1 of poly_xy [..][2] (poly_off[0] == 0, 3 to 32 each);
+ * coordinates are integer pixels within +-32767.  With heat on the grid is ceil(frame_h / cell) x ceil(frame_w / cell), at most
+ * 65 536 cells.  Every argument is checked before the context or the device is touched: a refusal returns SS_ERR_INVALID with a
+ * message naming the line or zone (ss_last_error; with ctx NULL in ss_last_error(NULL)). */
+int ss_zone_create(ss_ctx* ctx, const ss_zone_config* cfg, const int* lines, int n_lines, const int* poly_xy, const int* poly_off, int n_zones);
+int ss_zone_destroy(ss_ctx* ctx);
+int ss_zone_reset(ss_ctx* ctx, int stream);                /* stream < 0: all streams; tables, totals, heat, frame counter and error word */
+/* A group of n_frames (1..32) frames of every stream in ONE launch, the frames in order: d_rows [n_frames][n_streams][SS_MAX_TRACKS][8]
+ * and d_nrows [n_frames][n_streams] as every tracker's update_group leaves them (16-byte aligned; a count above SS_MAX_TRACKS is
+ * read as SS_MAX_TRACKS; a NEGATIVE count: the stream sits that frame out, its frame counter does not move and nothing is written
+ * for it).  Outputs, each skipped when NULL: d_events [F][S][R] u32 (bit l: line l crossed inward, bit 16+l outward), d_inside
+ * [F][S][R] u32 zone bits, d_dwell [F][S][R] i32, d_line_totals [F][S][16][2] i32 cumulative in / out, d_occupancy [F][S][16] i32,
+ * d_heat_frames [F][S][gh][gw] i32 the grid after each frame, d_heat_max [F][S] i32 its maximum (R = SS_MAX_TRACKS).  Asynchronous
+ * on the context's stream, capturable.  With ss_zone_max_live() live tracks a new id counts as a first appearance, leaves no
+ * state, and SS_ERR_CAPACITY is reported by ss_check_errors until ss_zone_reset.  The bits are those of tests/zones_ref.py. */
+int ss_zone_update_group(ss_ctx* ctx, int n_frames, const float* d_rows, const int* d_nrows, uint32_t* d_events, uint32_t* d_inside,
+                         int* d_dwell, int* d_line_totals, int* d_occupancy, int* d_heat_frames, int* d_heat_max);
+/* Synchronous, host arrays, any may be NULL: frames seen, line_class [16][2][n_classes], line_totals [16][2] (in, out), per zone
+ * entries, exits, the dwell frames summed over the exits, the longest dwell among them, the peak occupancy; the heat grid's maximum. */
+int ss_zone_get_totals(ss_ctx* ctx, int stream, int* frames, int* line_class, int* line_totals, int* zone_entries, int* zone_exits,
+                       long long* zone_dwell_sum, int* zone_longest, int* zone_peak, int* heat_max);
+/* Synchronous: the stream's cumulative grid into grid [gh][gw] (cap: the ints it holds; gh, gw receive the grid's shape, also when cap is 0). */
+int ss_zone_get_heat(ss_ctx* ctx, int stream, int* grid, int cap, int* gh, int* gw);
+/* Where the stream's cumulative grid and its maximum live on the device (for ss_zone_heat_blend with heat_frame_stride 0). */
+int ss_zone_heat_device(ss_ctx* ctx, int stream, void** d_heat, void** d_max);
+/* The blend's colour table: 256 x 3 bytes, B G R. */
+int ss_zone_set_colormap(ss_ctx* ctx, const uint8_t* bgr_256x3);
+/* In place over batch BGR frames laid out as ss_overlay's: per pixel v = heat[y >> k][x >> k] of frame b's grid at d_heat + b *
+ * heat_frame_stride ints (0: one grid for all), m = max(d_max[b * max_stride], 1); v <= 0 leaves the pixel alone, otherwise
+ * t = (min(v, m) * 255 + m / 2) / m, col = table[t] and every channel becomes (pix * (256 - alpha) + col * alpha + 128) >> 8
+ * (alpha 0..256).  Asynchronous on hip_stream.  The arguments are checked before the context (SS_ERR_INVALID, also with ctx NULL);
+ * h, w must be the zone state's. */
+int ss_zone_heat_blend(ss_ctx* ctx, void* hip_stream, uint8_t* d_frames, int batch, long long frame_batch_stride, int h, int w, int row_stride,
+                       const int* d_heat, long long heat_frame_stride, const int* d_max, int max_stride, int alpha);
+
 /* ---- profiling support ----------------------------------------------------------------------- */
 /* Mean duration (ms) of the association (cosine gallery) kernel over the launches since the last
  * call, measured with HIP events on the context stream; also returns the launch count. */

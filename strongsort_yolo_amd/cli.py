@@ -351,16 +351,25 @@ def process_video(args: dict, model=None) -> dict:
     keep_rows = gsi_on or aflink_on
     if keep_rows:
         from .gsi import rows_of
+    # --line / --zone / --heatmap: crossings, occupancy, dwell and heat counted on the device, frame by frame, on the rows the labels file records (docs/ZONES.md)
+    zone_cfg, zc, zf = zone_config(args, len(model.names)) if track else None, None, None
+    zone_asked = bool(args.get("lines") or args.get("zones") or args.get("heatmap"))
 
     def emit(frame, res):
         """labels, counts and (with --save) the annotated frame of one processed frame; reference :284-331"""
-        nonlocal frames, t0, fps, overlay, fps_str
+        nonlocal frames, t0, fps, overlay, fps_str, zc, zf
         if track:
             writer.write(frames, res)
             if keep_rows:
                 gsi_rows.append(rows_of(res, frames))
             if count:
                 counter.update(res)
+            if zone_cfg is not None:
+                from . import zones
+                if zc is None:
+                    overlay = overlay or model.overlay()
+                    zc = zones.ZoneCounter(zone_cfg, overlay.eng, frame_hw=frame.shape[:2])
+                zf = zc.update(zones.label_rows(res))
         frames += 1
         if frames % 10 == 0:                     # reference :321-326 (10-frame window)
             fps = 10 / max(time.time() - t0, 1e-9)
@@ -369,15 +378,17 @@ def process_video(args: dict, model=None) -> dict:
         if sink is not None:
             if overlay is None:
                 overlay = model.overlay()
+            if sink.engine is None:
                 sink.engine = overlay.eng
             cnt = counter.counts() if (count and track) else None
+            zkw = {"zones": zf} if zf is not None else {}     # the heat blended on the resident frame, then the lines and zones drawn with the rest
             dev_frame = getattr(res[0], "orig_img_device", None) if res else None
             if dev_frame is not None and on_device:  # drawn and encoded where it is: only the sparse coefficients of its JPEG come back
-                sink.write_device(overlay.annotate_resident(dev_frame, res, cnt, fps_str))
+                sink.write_device(overlay.annotate_resident(dev_frame, res, cnt, fps_str, **zkw))
             elif dev_frame is not None:              # the frame is still on the device: draw there, ONE download, no second upload
-                sink.write(overlay.draw_resident(dev_frame, res, cnt, fps_str))
+                sink.write(overlay.draw_resident(dev_frame, res, cnt, fps_str, **zkw))
             else:
-                sink.write(overlay.draw(frame, res, cnt, fps_str))
+                sink.write(overlay.draw(frame, res, cnt, fps_str, **zkw))
 
     if track and batch > 1 and hasattr(model, "track_stream"):
         # a file / synthetic source can supply frames ahead: groups of `batch` frames through the overlapped pipeline
@@ -397,11 +408,23 @@ def process_video(args: dict, model=None) -> dict:
                 print("[INFO] count works only when objects are tracking.. so use both flags (--track --count)")
                 frames += 1
                 break
+            if zone_asked:
+                print("[INFO] lines, zones and the heat map work only when objects are tracking.. so use them with --track")
+                frames += 1
+                break
         emit(frame, res)
     if sink is not None:
         sink.close()
     writer.close()
     summary = {"source": str(source), "frames": frames, "fps": fps, "counts": counter.counts() if count and track else {}}
+    if zc is not None:
+        from . import zones
+        outdir = args.get("outdir", "output")
+        summary["zones"] = zones.write_summary(os.path.join(outdir, f"{name}_zones.json"), zc.totals(0), zone_cfg, model.names)
+        if zone_cfg.heat:
+            np.save(os.path.join(outdir, f"{name}_heat.npy"), zc.heatmap(0))
+        zone_hw = zc.frame_hw
+        zc.close()
     if gsi_on:
         # GSI post-processing of the whole run on the device context the overlay uses; the labels file above stays as it is
         from . import gsi
@@ -410,6 +433,10 @@ def process_video(args: dict, model=None) -> dict:
         rows, status = gsi.gsi(rows, eng, interval=int(args.get("gsi_interval", gsi.INTERVAL)), tau=float(args.get("gsi_tau", gsi.TAU)))
         summary["gsi_rows"] = gsi.write_labels(os.path.join(args.get("outdir", "output"), f"{name}_labels_gsi.txt"), rows)
         summary["gsi_status"] = {k: sum(1 for v in status.values() if v == k) for k in (0, 1, 2)}
+        if zc is not None:                       # the same counts over the smoothed rows as their file records them
+            from . import moteval, zones
+            tot, _ = zones.replay(moteval.read_labels(os.path.join(args.get("outdir", "output"), f"{name}_labels_gsi.txt")), zone_cfg, eng, zone_hw)
+            zones.write_summary(os.path.join(args.get("outdir", "output"), f"{name}_zones_gsi.json"), tot, zone_cfg, model.names)
     if aflink_on:
         eng = (overlay or model.overlay()).eng
         rows = np.concatenate(gsi_rows, 0) if gsi_rows else np.zeros((0, 8))
@@ -429,6 +456,18 @@ def process_video(args: dict, model=None) -> dict:
             for fig in ("HOTA", "MOTA", "IDSW") + (("IDF1",) if with_identity else ()):
                 summary[fig + k[len("labels"):]] = m[fig]
     return summary
+
+
+def zone_config(args: dict, n_names: int):
+    """The ZoneConfig the flags ask for (None: none of --line, --zone, --heatmap was given)."""
+    if not (args.get("lines") or args.get("zones") or args.get("heatmap")):
+        return None
+    from .zones import ZoneConfig
+    cfg = ZoneConfig(lines=list(args.get("lines") or []), zones=list(args.get("zones") or []), anchor=args.get("zone_anchor", "bottom"),
+                     max_gap=int(args.get("zone_gap", 30)), n_classes=min(max(int(n_names), 1), 128), heat=args.get("heatmap"),
+                     heat_cell=int(args.get("heat_cell", 8)), heat_alpha=int(round(float(args.get("heat_alpha", 0.5)) * 256)))
+    cfg.validate()
+    return cfg
 
 
 def aflink_post(rows, eng, args: dict, outdir: str, name: str, summary: dict):
@@ -525,7 +564,27 @@ def main(argv=None):
     p.add_argument("--eval-thr", type=float, default=0.5, help="--eval-gt: CLEAR MOT's similarity threshold, in (0, 1]")
     p.add_argument("--eval-identity", action="store_true",
                    help="--eval-gt only: also the identity metrics IDTP, IDFN, IDFP, IDF1, IDP, IDR at --eval-thr, into the same <name>_metrics.json")
+    p.add_argument("--line", action="append", default=[], metavar="X0,Y0,X1,Y1",
+                   help="--track only, repeatable (up to 16): count the tracks that cross the directed segment a -> b, inward (onto its s >= 0 side) "
+                        "and outward, by class, on the device (docs/ZONES.md) into <name>_zones.json; any --tracker")
+    p.add_argument("--zone", action="append", default=[], metavar="X0,Y0,X1,Y1,...",
+                   help="--track only, repeatable (up to 16): a polygon of 3 to 32 vertices; entries, exits, peak occupancy and dwell into <name>_zones.json")
+    p.add_argument("--zone-anchor", choices=("bottom", "centre"), default="bottom", help="--line / --zone: the point of a box that is tested")
+    p.add_argument("--zone-gap", type=int, default=30, help="--line / --zone: a track unseen for more frames than this starts anew (1 .. 32)")
+    p.add_argument("--heatmap", choices=("anchor", "box"), default=None,
+                   help="--track only: a cumulative heat map of the anchors or of the boxes on the device into <name>_heat.npy; with --save it is blended over the frames")
+    p.add_argument("--heat-cell", type=int, default=8, help="--heatmap: pixels a side of a heat cell, a power of two from 1 to 64")
+    p.add_argument("--heat-alpha", type=float, default=0.5, help="--heatmap with --save: weight of the heat colour, 0 .. 1")
     a = p.parse_args(argv)
+    from . import zones as _zones
+    try:
+        a.line, a.zone = [_zones.parse_line(t) for t in a.line], [_zones.parse_zone(t) for t in a.zone]
+        if not 0.0 <= a.heat_alpha <= 1.0:
+            raise ValueError("--heat-alpha must be 0 .. 1")
+        zone_config({"lines": a.line, "zones": a.zone, "heatmap": a.heatmap, "zone_anchor": a.zone_anchor, "zone_gap": a.zone_gap,
+                     "heat_cell": a.heat_cell, "heat_alpha": a.heat_alpha}, 80)
+    except ValueError as e:
+        p.error(str(e))
     if a.eval_identity and not a.eval_gt:
         p.error("--eval-identity adds to what --eval-gt scores: it needs --eval-gt")
     if a.eval_gt and not a.track:
@@ -603,6 +662,7 @@ def main(argv=None):
              "device_encode": a.device_encode, "device_encode_entropy": a.device_encode_entropy, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
              "gsi": a.gsi, "gsi_interval": a.gsi_interval, "gsi_tau": a.gsi_tau, "eval_gt": a.eval_gt[i] if a.eval_gt else None, "eval_thr": a.eval_thr, "eval_identity": a.eval_identity,
              "aflink": a.aflink, "aflink_thr_t": tuple(a.aflink_thr_t), "aflink_thr_s": a.aflink_thr_s, "aflink_thr_p": a.aflink_thr_p,
+             "lines": a.line, "zones": a.zone, "zone_anchor": a.zone_anchor, "zone_gap": a.zone_gap, "heatmap": a.heatmap, "heat_cell": a.heat_cell, "heat_alpha": a.heat_alpha,
              "save": _save_path(a, i)}
             for i, s in enumerate(a.source)]
     import torch

@@ -84,6 +84,7 @@ struct ss_ctx {
     SSGsi* gsi = nullptr;       // ss_gsi_smooth's staging and scratch slots, made by its first call
     SSMot* mot = nullptr;       // ss_mot_eval's and ss_mot_identity's staging, scratch and second stream, made by its first call
     SSAflink* aflink = nullptr; // ss_aflink_*'s weights, staging and activation scratch, made by its first call
+    SSZone* zone = nullptr;     // the analytics stage (ss_zone_create), NULL until attached
 };
 
 static int fail(ss_ctx* c, int code, const std::string& msg)
@@ -241,6 +242,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     ss_gsi_free(c->gsi);
     ss_mot_free(c->mot);
     ss_aflink_free(c->aflink);
+    ss_zone_free(c->zone);
     delete c;                   // (the staging areas of ss_upload, ss_upload_batch and ss_download go with it)
 }
 
@@ -1044,6 +1046,10 @@ extern "C" int ss_check_errors(ss_ctx* c)
         for (size_t s = 0; s < e.size(); ++s)
             if (e[s]) return fail(c, e[s], "Deep OC-SORT tracker: device error flag on stream " + std::to_string(s));
     }
+    {                                                        // the analytics stage's flags (more live tracks than its table holds)
+        std::string err;
+        if (int rcz = ss_zone_pending_impl(c->zone, c->stream, err)) return fail(c, rcz, err);
+    }
     {                                                        // images a device-entropy JPEG call refused (docs/JPEG.md section 12)
         std::string err;
         if (int rcj = ss_jpeg_pending_impl(c->jpeg, err)) return fail(c, rcj, err);
@@ -1386,6 +1392,127 @@ extern "C" int ss_assoc_timing_values(ss_ctx* c, float* out_ms, int cap, int* n)
     *n = (int)c->ev_ms.size();
     for (int i = 0; i < cap && i < *n; ++i) out_ms[i] = c->ev_ms[i];
     return SS_OK;
+}
+
+// ---- analytics behind the trackers: lines, zones, dwell, heat (ss_zone.hip, docs/ZONES.md) -----------------------------------
+extern "C" int ss_zone_max_lines(void) { return ss_zone_max_lines_impl(); }
+extern "C" int ss_zone_max_zones(void) { return ss_zone_max_zones_impl(); }
+extern "C" int ss_zone_max_vertices(void) { return ss_zone_max_vertices_impl(); }
+extern "C" int ss_zone_max_live(void) { return ss_zone_max_live_impl(); }
+
+// the checks every ss_zone_* entry makes after its own arguments: a context, its zone state, a stream of it
+static int zone_state(ss_ctx* c, const char* entry, int stream, bool need_stream, std::string& err)
+{
+    if (!c) { err = std::string(entry) + ": null context"; return SS_ERR_INVALID; }
+    if (!c->zone) { err = std::string(entry) + ": no zone state (ss_zone_create)"; return SS_ERR_INVALID; }
+    if (stream >= c->dev.S || (need_stream && stream < 0)) { err = std::string(entry) + ": stream " + std::to_string(stream) + " out of range"; return SS_ERR_INVALID; }
+    return SS_OK;
+}
+
+extern "C" int ss_zone_create(ss_ctx* c, const ss_zone_config* cfg, const int* lines, int n_lines, const int* poly_xy, const int* poly_off, int n_zones)
+{
+    return post_run(c, "ss_zone_create",
+        [&](std::string& err) { return ss_zone_create_check_impl(cfg, lines, n_lines, poly_xy, poly_off, n_zones, err); },
+        [&](std::string& err) {
+            if (!c) { err = "ss_zone_create: null context"; return (int)SS_ERR_INVALID; }
+            hipError_t e = hipStreamSynchronize(c->stream);          // nothing of a state this call replaces may still be in flight
+            if (e != hipSuccess) { err = std::string("ss_zone_create: ") + hipGetErrorString(e); return (int)SS_ERR_HIP; }
+            return ss_zone_create_impl(&c->zone, c->stream, c->dev.S, cfg, lines, n_lines, poly_xy, poly_off, n_zones, err);
+        });
+}
+
+extern "C" int ss_zone_destroy(ss_ctx* c)
+{
+    if (!c) return fail(nullptr, SS_ERR_INVALID, "ss_zone_destroy: null context");
+    if (!c->zone) return SS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ss_zone_free(c->zone);
+    c->zone = nullptr;
+    return SS_OK;
+}
+
+extern "C" int ss_zone_reset(ss_ctx* c, int stream)
+{
+    return post_run(c, "ss_zone_reset",
+        [&](std::string& err) { return zone_state(c, "ss_zone_reset", stream, false, err); },
+        [&](std::string& err) { return ss_zone_reset_impl(c->zone, c->stream, stream, err); });
+}
+
+extern "C" int ss_zone_update_group(ss_ctx* c, int n_frames, const float* d_rows, const int* d_nrows, uint32_t* d_events, uint32_t* d_inside,
+                                    int* d_dwell, int* d_line_totals, int* d_occupancy, int* d_heat_frames, int* d_heat_max)
+{
+    return post_run(c, "ss_zone_update_group",
+        [&](std::string& err) {
+            if (int rc = ss_zone_update_check_impl(n_frames, d_rows, d_nrows, err)) return rc;
+            return zone_state(c, "ss_zone_update_group", -1, false, err);
+        },
+        [&](std::string& err) {
+            return ss_zone_update_impl(c->zone, c->stream, n_frames, d_rows, d_nrows, d_events, d_inside, d_dwell, d_line_totals, d_occupancy,
+                                       d_heat_frames, d_heat_max, err);
+        });
+}
+
+extern "C" int ss_zone_get_totals(ss_ctx* c, int stream, int* frames, int* line_class, int* line_totals, int* zone_entries, int* zone_exits,
+                                  long long* zone_dwell_sum, int* zone_longest, int* zone_peak, int* heat_max)
+{
+    return post_run(c, "ss_zone_get_totals",
+        [&](std::string& err) { return zone_state(c, "ss_zone_get_totals", stream, true, err); },
+        [&](std::string& err) {
+            return ss_zone_get_totals_impl(c->zone, c->stream, stream, frames, line_class, line_totals, zone_entries, zone_exits, zone_dwell_sum,
+                                           zone_longest, zone_peak, heat_max, err);
+        });
+}
+
+extern "C" int ss_zone_get_heat(ss_ctx* c, int stream, int* grid, int cap, int* gh, int* gw)
+{
+    return post_run(c, "ss_zone_get_heat",
+        [&](std::string& err) {
+            if (!gh || !gw || cap < 0 || (cap > 0 && !grid)) { err = "ss_zone_get_heat: null argument or negative cap"; return (int)SS_ERR_INVALID; }
+            return zone_state(c, "ss_zone_get_heat", stream, true, err);
+        },
+        [&](std::string& err) {
+            int S, heat, h, w;
+            ss_zone_shape_impl(c->zone, &S, &heat, gh, gw, &h, &w);
+            if (!heat) { err = "ss_zone_get_heat: the zone state was made without a heat map"; return (int)SS_ERR_INVALID; }
+            if (cap == 0) return (int)SS_OK;
+            if (cap < *gh * *gw) { err = "ss_zone_get_heat: cap " + std::to_string(cap) + " is below the grid's " + std::to_string(*gh * *gw) + " cells"; return (int)SS_ERR_INVALID; }
+            return ss_zone_get_heat_impl(c->zone, c->stream, stream, grid, err);
+        });
+}
+
+extern "C" int ss_zone_heat_device(ss_ctx* c, int stream, void** d_heat, void** d_max)
+{
+    return post_run(c, "ss_zone_heat_device",
+        [&](std::string& err) {
+            if (!d_heat || !d_max) { err = "ss_zone_heat_device: null argument"; return (int)SS_ERR_INVALID; }
+            return zone_state(c, "ss_zone_heat_device", stream, true, err);
+        },
+        [&](std::string&) { ss_zone_heat_device_impl(c->zone, stream, d_heat, d_max); return (int)SS_OK; });
+}
+
+extern "C" int ss_zone_set_colormap(ss_ctx* c, const uint8_t* bgr_256x3)
+{
+    return post_run(c, "ss_zone_set_colormap",
+        [&](std::string& err) {
+            if (!bgr_256x3) { err = "ss_zone_set_colormap: null table"; return (int)SS_ERR_INVALID; }
+            return zone_state(c, "ss_zone_set_colormap", -1, false, err);
+        },
+        [&](std::string& err) { return ss_zone_set_colormap_impl(c->zone, bgr_256x3, err); });
+}
+
+extern "C" int ss_zone_heat_blend(ss_ctx* c, void* hip_stream, uint8_t* d_frames, int batch, long long frame_batch_stride, int h, int w, int row_stride,
+                                  const int* d_heat, long long heat_frame_stride, const int* d_max, int max_stride, int alpha)
+{
+    return post_run(c, "ss_zone_heat_blend",
+        [&](std::string& err) {
+            if (int rc = ss_zone_blend_check_impl(d_frames, batch, frame_batch_stride, h, w, row_stride, d_heat, heat_frame_stride, d_max, max_stride, alpha, err))
+                return rc;
+            return zone_state(c, "ss_zone_heat_blend", -1, false, err);
+        },
+        [&](std::string& err) {
+            return ss_zone_blend_impl(c->zone, (hipStream_t)hip_stream, d_frames, batch, frame_batch_stride, h, w, row_stride, d_heat, heat_frame_stride,
+                                      d_max, max_stride, alpha, err);
+        });
 }
 
 // ---- OC-SORT (ss_ocsort.hip, docs/OCSORT.md) ---------------------------------------------------------------------------------------

@@ -124,6 +124,33 @@ int  ss_mot_identity_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int
                           int* idtp, int* gt_to_tr, int* pot, std::string& err);
 void ss_mot_free(SSMot* m);
 
+// ---- ss_zone.hip
+struct SSZone;
+int  ss_zone_max_lines_impl();
+int  ss_zone_max_zones_impl();
+int  ss_zone_max_vertices_impl();
+int  ss_zone_max_live_impl();
+int  ss_zone_create_check_impl(const ss_zone_config* cfg, const int* lines, int n_lines, const int* poly_xy, const int* poly_off, int n_zones,
+                               std::string& err);
+int  ss_zone_create_impl(SSZone** pz, hipStream_t st, int S, const ss_zone_config* cfg, const int* lines, int n_lines, const int* poly_xy,
+                         const int* poly_off, int n_zones, std::string& err);
+int  ss_zone_reset_impl(SSZone* z, hipStream_t st, int stream, std::string& err);
+int  ss_zone_update_check_impl(int n_frames, const float* d_rows, const int* d_nrows, std::string& err);
+int  ss_zone_update_impl(SSZone* z, hipStream_t st, int n_frames, const float* d_rows, const int* d_nrows, uint32_t* d_events, uint32_t* d_inside,
+                         int* d_dwell, int* d_line_totals, int* d_occupancy, int* d_heat_frames, int* d_heat_max, std::string& err);
+int  ss_zone_pending_impl(SSZone* z, hipStream_t st, std::string& err);
+int  ss_zone_get_totals_impl(SSZone* z, hipStream_t st, int stream, int* frames, int* line_class, int* line_totals, int* zone_entries, int* zone_exits,
+                             long long* zone_dwell_sum, int* zone_longest, int* zone_peak, int* heat_max, std::string& err);
+int  ss_zone_get_heat_impl(SSZone* z, hipStream_t st, int stream, int* grid, std::string& err);
+void ss_zone_shape_impl(const SSZone* z, int* S, int* heat, int* gh, int* gw, int* h, int* w);
+void ss_zone_heat_device_impl(const SSZone* z, int stream, void** d_heat, void** d_max);
+int  ss_zone_set_colormap_impl(SSZone* z, const uint8_t* bgr, std::string& err);
+int  ss_zone_blend_check_impl(const uint8_t* d_frames, int batch, long long frame_batch_stride, int h, int w, int row_stride, const int* d_heat,
+                              long long heat_frame_stride, const int* d_max, int max_stride, int alpha, std::string& err);
+int  ss_zone_blend_impl(SSZone* z, hipStream_t st, uint8_t* d_frames, int batch, long long frame_batch_stride, int h, int w, int row_stride,
+                        const int* d_heat, long long heat_frame_stride, const int* d_max, int max_stride, int alpha, std::string& err);
+void ss_zone_free(SSZone* z);
+
 // ---- ss_aflink.hip
 struct SSAflink;
 long long ss_aflink_weight_floats_impl();

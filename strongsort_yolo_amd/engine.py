@@ -311,6 +311,69 @@ class TrackerEngine:
         return (idtp, match[:n_g]) + ((pot,) if want_pot else ())
 
     # ---- tracker --------------------------------------------------------------------------------
+    # ---- analytics behind the trackers (csrc/ss_zone.hip, docs/ZONES.md); zones.ZoneCounter is the front of these ----
+    def zone_create(self, cfg, lines, zones):
+        """cfg: lib.ss_zone_config; lines [[ax, ay, bx, by], ...]; zones [[[x, y], ...], ...] in integer pixels.  One state per
+        context, shared by its streams; a second call replaces it."""
+        ln = np.ascontiguousarray(np.asarray(lines, np.int32).reshape(-1, 4))
+        xy = np.ascontiguousarray(np.concatenate([np.asarray(z, np.int32).reshape(-1, 2) for z in zones], 0) if len(zones) else np.zeros((0, 2), np.int32))
+        off = np.concatenate([[0], np.cumsum([len(z) for z in zones])]).astype(np.int32)
+        pi = C.POINTER(C.c_int)
+        self._ck(self.L.ss_zone_create(self.ctx, C.byref(cfg), ln.ctypes.data_as(pi), len(ln), xy.ctypes.data_as(pi), off.ctypes.data_as(pi), len(zones)))
+
+    def zone_destroy(self):
+        self._ck(self.L.ss_zone_destroy(self.ctx))
+
+    def zone_reset(self, stream: int = -1):
+        self._ck(self.L.ss_zone_reset(self.ctx, int(stream)))
+
+    def zone_update_group(self, n_frames, rows, counts, events=None, inside=None, dwell=None, line_totals=None, occupancy=None, heat_frames=None,
+                          heat_max=None):
+        """One launch for n_frames (<= 32) frames of every stream: rows [F,S,256,8] f32 and counts [F,S] i32 as a tracker's
+        update_group leaves them (device tensors, read in place); every output is a device tensor or None.  Asynchronous."""
+        self._ck(self.L.ss_zone_update_group(self.ctx, int(n_frames), _ptr(rows), _ptr(counts), _ptr(events), _ptr(inside), _ptr(dwell), _ptr(line_totals),
+                                             _ptr(occupancy), _ptr(heat_frames), _ptr(heat_max)))
+
+    def zone_totals(self, stream: int, n_classes: int) -> dict:
+        """Synchronous: the running totals of one stream (the keys of tests/zones_ref.py's totals())."""
+        fr, hm = C.c_int(), C.c_int()
+        lc, lt = np.zeros((16, 2, n_classes), np.int32), np.zeros((16, 2), np.int32)
+        z = {k: np.zeros(16, np.int32) for k in ("entries", "exits", "longest", "peak")}
+        ds = np.zeros(16, np.int64)
+        pi = C.POINTER(C.c_int)
+        self._ck(self.L.ss_zone_get_totals(self.ctx, int(stream), C.byref(fr), lc.ctypes.data_as(pi), lt.ctypes.data_as(pi), z["entries"].ctypes.data_as(pi),
+                                           z["exits"].ctypes.data_as(pi), ds.ctypes.data_as(C.POINTER(C.c_longlong)), z["longest"].ctypes.data_as(pi),
+                                           z["peak"].ctypes.data_as(pi), C.byref(hm)))
+        return dict(z, frames=fr.value, heat_max=hm.value, line_class=lc, line_totals=lt, dwell_sum=ds)
+
+    def zone_heat(self, stream: int = 0) -> np.ndarray:
+        """Synchronous: the cumulative heat grid of one stream, int32 [gh, gw]."""
+        gh, gw = C.c_int(), C.c_int()
+        self._ck(self.L.ss_zone_get_heat(self.ctx, int(stream), None, 0, C.byref(gh), C.byref(gw)))
+        g = np.zeros((gh.value, gw.value), np.int32)
+        self._ck(self.L.ss_zone_get_heat(self.ctx, int(stream), g.ctypes.data_as(C.POINTER(C.c_int)), g.size, C.byref(gh), C.byref(gw)))
+        return g
+
+    def zone_heat_device(self, stream: int = 0):
+        """-> (address of the stream's cumulative grid, address of its maximum) on the device."""
+        a, b = C.c_void_p(), C.c_void_p()
+        self._ck(self.L.ss_zone_heat_device(self.ctx, int(stream), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def zone_set_colormap(self, table):
+        t = np.ascontiguousarray(table, np.uint8)
+        if t.shape != (256, 3):
+            raise ValueError("zone_set_colormap: a uint8 [256, 3] BGR table")
+        self._ck(self.L.ss_zone_set_colormap(self.ctx, t.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def zone_heat_blend(self, frames: torch.Tensor, heat, heat_frame_stride: int, maxes, max_stride: int, alpha: int, stream=None):
+        """frames uint8 [B,H,W,3] (or [H,W,3]) on the device, blended in place; heat / maxes: device tensors or addresses."""
+        fr = frames if frames.dim() == 4 else frames.unsqueeze(0)
+        addr = lambda t: C.c_void_p(t) if isinstance(t, int) else _ptr(t)
+        self._ck(self.L.ss_zone_heat_blend(self.ctx, self._st(stream), _ptr(fr), fr.shape[0], fr.stride(0), fr.shape[1], fr.shape[2], fr.stride(1),
+                                           addr(heat), int(heat_frame_stride), addr(maxes), int(max_stride), int(alpha)))
+        return frames
+
     def update_device(self, dets, ndets, feats, img_hw, out=None, nout=None):
         """All streams, one frame; tensors live on the device ([S,128,6] f32, [S] i32, [S,128,512] f32,
         [S,2] i32).  Asynchronous; returns (rows [S,256,8], counts [S]) device tensors (default: self.out, self.nout)."""

@@ -22,8 +22,8 @@ SS_OK, SS_ERR_INVALID, SS_ERR_CAPACITY, SS_ERR_HIP, SS_ERR_INFEASIBLE = (
 MAX_TRACKS, MAX_DETS, FEAT_DIM, OUT_COLS, DST_F16, DST_HWC, DST_U8 = (
     _H.defines["SS_" + n] for n in ("MAX_TRACKS", "MAX_DETS", "FEAT_DIM", "OUT_COLS", "DST_F16", "DST_HWC", "DST_U8"))
 EXPORTS = list(_H.functions)
-ss_config, ss_byte_config, ss_ocsort_config, ss_deepoc_config, ss_conv_desc, ss_native_map = (
-    _H.structs[n] for n in ("ss_config", "ss_byte_config", "ss_ocsort_config", "ss_deepoc_config", "ss_conv_desc", "ss_native_map"))
+ss_config, ss_byte_config, ss_ocsort_config, ss_deepoc_config, ss_conv_desc, ss_native_map, ss_zone_config = (
+    _H.structs[n] for n in ("ss_config", "ss_byte_config", "ss_ocsort_config", "ss_deepoc_config", "ss_conv_desc", "ss_native_map", "ss_zone_config"))
 
 
 class SSError(RuntimeError):

@@ -127,8 +127,12 @@ class Overlay:
             engine._ck(engine.L.ss_overlay_set_font(engine.ctx, t.ctypes.data_as(C.POINTER(C.c_uint8))))
 
     # ---- the reference's drawing sequence as data ---------------------------------------------------------
-    def commands(self, results, counts: Optional[dict] = None, fps_text: str = "") -> CommandList:
+    def commands(self, results, counts: Optional[dict] = None, fps_text: str = "", zones=None) -> CommandList:
+        """zones: a zones.ZoneFrame (docs/ZONES.md), drawn under the boxes: every counting line with its `in / out` totals, every
+        zone's outline with `n inside`.  None (the default) draws what was drawn before."""
         cl = CommandList()
+        if zones is not None:
+            self._zones(cl, zones)
         live = {int(i) for r in results if r is not None and r.boxes is not None and r.boxes.id is not None for i in r.boxes.id}
         for id_ in list(self.trails):                                   # yolo_multi_model.py:45-47
             if id_ not in live:
@@ -181,6 +185,16 @@ class Overlay:
         return cl
 
     @staticmethod
+    def _zones(cl, z):
+        for i, (ax, ay, qx, qy) in enumerate(z.cfg.lines):
+            cl.line(ax, ay, qx, qy, bgr(0, 255, 255), 2)
+            cl.circle(qx, qy, 4, bgr(0, 255, 255))                                                   # the b end: inward is on its left-hand side (s >= 0)
+            cl.text(f"L{i} in {int(z.line_totals[i][0])} out {int(z.line_totals[i][1])}", (ax + qx) // 2 + 4, (ay + qy) // 2 - 4, bgr(0, 255, 255))
+        for i, poly in enumerate(z.cfg.zones):
+            cl.polyline(poly, bgr(255, 128, 0), 2)
+            cl.text(f"Z{i} {int(z.occupancy[i])} inside", int(poly[0][0]) + 4, int(poly[0][1]) + 12, bgr(255, 128, 0))
+
+    @staticmethod
     def _box(cl, xyxy, label):
         x0, y0, x1, y1 = (int(v) for v in xyxy)
         cl.rect(x0, y0, x1, y1, bgr(0, 0, 225), 2)                                                   # :80 / :132
@@ -222,26 +236,30 @@ class Overlay:
         self._keep.append((d_prims, d_off, d_chars))
         return frames
 
-    def annotate_resident(self, dev_frame: torch.Tensor, results, counts: Optional[dict] = None, fps_text: str = "", stream=None) -> torch.Tensor:
+    def annotate_resident(self, dev_frame: torch.Tensor, results, counts: Optional[dict] = None, fps_text: str = "", stream=None, zones=None) -> torch.Tensor:
         """A frame that is ALREADY on the device (uint8 [H,W,3]) annotated in place and returned still on the device: what a
-        device-side consumer (the JPEG sink, cli.FrameSink.write_device) takes; no transfer of the frame in either direction."""
-        return self.draw_device(dev_frame, [self.commands(results, counts, fps_text)], stream)
+        device-side consumer (the JPEG sink, cli.FrameSink.write_device) takes; no transfer of the frame in either direction.
+        zones (a zones.ZoneFrame): its heat map is blended over the frame first, then its lines and zones are drawn with the rest."""
+        if zones is None:
+            return self.draw_device(dev_frame, [self.commands(results, counts, fps_text)], stream)
+        zones.blend_into(dev_frame, stream)
+        return self.draw_device(dev_frame, [self.commands(results, counts, fps_text, zones)], stream)
 
-    def draw_resident(self, dev_frame: torch.Tensor, results, counts: Optional[dict] = None, fps_text: str = "") -> np.ndarray:
+    def draw_resident(self, dev_frame: torch.Tensor, results, counts: Optional[dict] = None, fps_text: str = "", zones=None) -> np.ndarray:
         """A frame that is ALREADY on the device (uint8 [H,W,3], e.g. `Results.orig_img_device` of track_stream) -> annotated
         host frame: ss_overlay in place, one download, no upload of the frame."""
-        self.annotate_resident(dev_frame, results, counts, fps_text)
+        self.annotate_resident(dev_frame, results, counts, fps_text, zones=zones)
         out = np.empty(tuple(dev_frame.shape), np.uint8)
         self.eng.download(out, dev_frame)
         return out
 
-    def draw(self, frame: np.ndarray, results, counts: Optional[dict] = None, fps_text: str = "") -> np.ndarray:
+    def draw(self, frame: np.ndarray, results, counts: Optional[dict] = None, fps_text: str = "", zones=None) -> np.ndarray:
         """Host frame in, annotated host frame out (upload -> ss_overlay -> download)."""
         e = self.eng
         if self._scratch is None or self._scratch.shape != frame.shape:
             self._scratch = torch.empty(frame.shape, dtype=torch.uint8, device=e.device)
         e.upload(self._scratch, frame)
-        self.draw_device(self._scratch, [self.commands(results, counts, fps_text)])
+        self.annotate_resident(self._scratch, results, counts, fps_text, zones=zones)
         out = np.empty_like(frame)
         e.download(out, self._scratch)
         return out
