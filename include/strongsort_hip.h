@@ -907,6 +907,40 @@ int ss_zone_set_colormap(ss_ctx* ctx, const uint8_t* bgr_256x3);
 int ss_zone_heat_blend(ss_ctx* ctx, void* hip_stream, uint8_t* d_frames, int batch, long long frame_batch_stride, int h, int w, int row_stride,
                        const int* d_heat, long long heat_frame_stride, const int* d_max, int max_stride, int alpha);
 
+/* ---- sliced inference: the frame cut into overlapping tiles before the detector, the tiles' rows merged after it (csrc/ss_slice.hip,
+ * docs/SLICE.md; the bits are those of tests/slice_ref.py) ---- */
+/* Host only: the caps (64 tiles a frame, the full-frame tile included; 8192 candidates a frame = tiles x rows_per_tile). */
+int ss_slice_max_tiles(void);
+int ss_slice_max_candidates(void);
+/* The state is hung off an existing context; a second call replaces it.  h_tiles [n_tiles][8] = {x0, y0, tile_w, tile_h, new_w, new_h,
+ * pad_left, pad_top}: the tile's window in the frame_h x frame_w frame, the size it is resized to and where that lands in the
+ * canvas_h x canvas_w detector input all tiles share.  rows_per_tile: rows a tile's NMS may keep (the merge reads that many at most);
+ * n_extra: columns behind the six of a row; the first n_kpt triples of them are keypoints (x, y, conf), which the merge re-expresses as
+ * ((k - pad_t) / gain_t + origin) * kpt_gain + kpt_pad, the whole frame's letterbox.  Every argument is checked before the context or
+ * the device is touched (SS_ERR_INVALID and a message naming the tile, also with ctx NULL). */
+int ss_slice_config(ss_ctx* ctx, const int* h_tiles, int n_tiles, int frame_h, int frame_w, int canvas_h, int canvas_w, int rows_per_tile,
+                    int n_extra, int n_kpt, float kpt_gain, float kpt_pad_x, float kpt_pad_y);
+/* d_geom [batch][n_tiles][5]: ss_nms_batch's geometry rows {gain, pad_x, pad_y, tile_w, tile_h} of the configured tiles, repeated per
+ * frame (image = frame * n_tiles + tile).  Synchronous; not inside a capture. */
+int ss_slice_nms_geom(ss_ctx* ctx, float* d_geom, int batch);
+/* ss_letterbox_batch for every tile of `batch` resident frames in ONE launch: frame b at d_src + b * src_batch_stride bytes (frame_h x
+ * frame_w BGR u8, row_stride bytes a row), output image b * n_tiles + t at d_dst + (b * n_tiles + t) * 3 * canvas_h * canvas_w elements,
+ * dst_flags as ss_letterbox's.  A tile's image equals ss_letterbox_batch on a cropped copy of the tile, bit for bit.  Asynchronous on
+ * the context's stream, capturable; batch * n_tiles <= 65535. */
+int ss_slice_letterbox_batch(ss_ctx* ctx, const uint8_t* d_src, int batch, long long src_batch_stride, int row_stride, void* d_dst, int dst_flags,
+                             int pad_value);
+/* The tiles' NMS rows of `batch` frames into one row list per frame.  Tile t of frame b: rows at d_rows + b * frame_stride + t *
+ * tile_stride floats (row_stride floats a row, tile pixels, descending score), count d_counts[b * n_tiles + t] (read as
+ * min(max(count, 0), rows_per_tile)).  mode 0: greedy NMS across tiles, 1: SAHI's GREEDYNMM (a kept box grows to the union of the
+ * candidates it removed while metric(box so far, candidate) > thr); metric 0: IoU, 1: intersection over the smaller area; a candidate
+ * is removed when an earlier kept one matches it with metric >= thr (and, unless agnostic, the same class column).  Outputs: up to
+ * out_cap rows a frame in frame pixels at d_out + b * out_frame_stride (out_row_stride floats a row), d_out_count[b], and per row the
+ * source index tile * rows_per_tile + row at d_out_src + b * src_frame_stride.  Asynchronous on the context's stream, capturable; the
+ * first call with a larger batch than any before grows the workspace and must not be inside a capture. */
+int ss_slice_merge(ss_ctx* ctx, const float* d_rows, const int* d_counts, int batch, int row_stride, long long tile_stride, long long frame_stride,
+                   int mode, int metric, float thr, int agnostic, int out_cap, float* d_out, int out_row_stride, long long out_frame_stride,
+                   int* d_out_count, int* d_out_src, long long src_frame_stride);
+
 /* ---- profiling support ----------------------------------------------------------------------- */
 /* Mean duration (ms) of the association (cosine gallery) kernel over the launches since the last
  * call, measured with HIP events on the context stream; also returns the launch count. */

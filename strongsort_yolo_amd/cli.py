@@ -322,6 +322,26 @@ class ClassCounter:
 DEFAULT_WEIGHTS = "yolo11n-pose.pt"       # the model file the reference loads (/root/reference/yolo_multi_model.py:17)
 
 
+def slice_kwargs(args: dict) -> dict:
+    """--slice and its companions as YOLO(...)'s keywords ({} without --slice); a ValueError names what is wrong."""
+    hw = args.get("slice")
+    given = [f for f, d in (("slice_overlap", 0.2), ("slice_merge", "nmm"), ("slice_metric", "ios"), ("slice_thr", 0.5), ("no_slice_full", False))
+             if args.get(f, d) != d]
+    if hw is None:
+        if given:
+            raise ValueError(f"--{given[0].replace('_', '-')} is an option of sliced inference: it needs --slice H W")
+        return {}
+    from .slicing import SliceConfig
+    if "seg" in os.path.basename(str(args.get("weights", ""))):
+        raise ValueError("--slice cannot run a segmentation model (a row's mask coefficients belong to its tile's prototypes)")
+    if args.get("reid_model", "osnet") == "auto":
+        raise ValueError("--slice cannot feed --reid-model auto (the detector's anchor indices are per tile)")
+    kw = dict(slice_hw=tuple(hw), slice_overlap=args.get("slice_overlap", 0.2), slice_full=not args.get("no_slice_full", False),
+              slice_merge=args.get("slice_merge", "nmm"), slice_metric=args.get("slice_metric", "ios"), slice_thr=args.get("slice_thr", 0.5))
+    SliceConfig(kw["slice_hw"], kw["slice_overlap"], kw["slice_full"], kw["slice_merge"], kw["slice_metric"], kw["slice_thr"])
+    return kw
+
+
 # ---- per-stream loop ------------------------------------------------------------------------------------------
 def process_video(args: dict, model=None) -> dict:
     """One stream (yolo_multi_model.py:244-339).  Returns a summary instead of showing a window."""
@@ -333,7 +353,7 @@ def process_video(args: dict, model=None) -> dict:
                      device_masks=args.get("device_masks", False), tracker_type=args.get("tracker", "strongsort"),
                      camera_motion=args.get("camera_motion", False), with_reid=args.get("with_reid", False),
                      reid_model=args.get("reid_model", "osnet"), with_pose=args.get("with_pose", False),
-                     gmc_method=args.get("gmc_method", "ecc"), ocsort_use_byte=args.get("ocsort_use_byte", False))
+                     gmc_method=args.get("gmc_method", "ecc"), ocsort_use_byte=args.get("ocsort_use_byte", False), **slice_kwargs(args))
         model.overrides.update(conf=0.3, iou=0.4, agnostic_nms=False, max_det=1000)      # :18-21
     name = os.path.splitext(os.path.basename(str(source)))[0] or "stream"
     writer = LabelsWriter(os.path.join(args.get("outdir", "output"), f"{name}_labels.txt"), args.get("compat", False))
@@ -575,9 +595,17 @@ def main(argv=None):
                    help="--track only: a cumulative heat map of the anchors or of the boxes on the device into <name>_heat.npy; with --save it is blended over the frames")
     p.add_argument("--heat-cell", type=int, default=8, help="--heatmap: pixels a side of a heat cell, a power of two from 1 to 64")
     p.add_argument("--heat-alpha", type=float, default=0.5, help="--heatmap with --save: weight of the heat colour, 0 .. 1")
+    p.add_argument("--slice", type=int, nargs=2, default=None, metavar=("H", "W"),
+                   help="sliced inference (docs/SLICE.md): run the detector on overlapping H x W tiles of every frame and merge their rows on the device; the detector costs T times as much")
+    p.add_argument("--slice-overlap", type=float, default=0.2, help="--slice: overlap of neighbouring tiles as a ratio of the tile, in [0, 1)")
+    p.add_argument("--slice-merge", choices=("nmm", "nms"), default="nmm", help="--slice: merge duplicates into their union (SAHI's GREEDYNMM) or drop them")
+    p.add_argument("--slice-metric", choices=("ios", "iou"), default="ios", help="--slice: intersection over the smaller area, or over the union")
+    p.add_argument("--slice-thr", type=float, default=0.5, help="--slice: the match threshold")
+    p.add_argument("--no-slice-full", action="store_true", help="--slice: do not add the whole frame as one more tile")
     a = p.parse_args(argv)
     from . import zones as _zones
     try:
+        slice_kwargs(vars(a))
         a.line, a.zone = [_zones.parse_line(t) for t in a.line], [_zones.parse_zone(t) for t in a.zone]
         if not 0.0 <= a.heat_alpha <= 1.0:
             raise ValueError("--heat-alpha must be 0 .. 1")
@@ -663,6 +691,7 @@ def main(argv=None):
              "gsi": a.gsi, "gsi_interval": a.gsi_interval, "gsi_tau": a.gsi_tau, "eval_gt": a.eval_gt[i] if a.eval_gt else None, "eval_thr": a.eval_thr, "eval_identity": a.eval_identity,
              "aflink": a.aflink, "aflink_thr_t": tuple(a.aflink_thr_t), "aflink_thr_s": a.aflink_thr_s, "aflink_thr_p": a.aflink_thr_p,
              "lines": a.line, "zones": a.zone, "zone_anchor": a.zone_anchor, "zone_gap": a.zone_gap, "heatmap": a.heatmap, "heat_cell": a.heat_cell, "heat_alpha": a.heat_alpha,
+             "slice": a.slice, "slice_overlap": a.slice_overlap, "slice_merge": a.slice_merge, "slice_metric": a.slice_metric, "slice_thr": a.slice_thr, "no_slice_full": a.no_slice_full,
              "save": _save_path(a, i)}
             for i, s in enumerate(a.source)]
     import torch

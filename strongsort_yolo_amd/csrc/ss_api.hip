@@ -85,6 +85,7 @@ struct ss_ctx {
     SSMot* mot = nullptr;       // ss_mot_eval's and ss_mot_identity's staging, scratch and second stream, made by its first call
     SSAflink* aflink = nullptr; // ss_aflink_*'s weights, staging and activation scratch, made by its first call
     SSZone* zone = nullptr;     // the analytics stage (ss_zone_create), NULL until attached
+    SSSlice* slice = nullptr;   // sliced inference (ss_slice_config): tile table, NMS geometry, merge workspace; NULL until configured
 };
 
 static int fail(ss_ctx* c, int code, const std::string& msg)
@@ -243,6 +244,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     ss_mot_free(c->mot);
     ss_aflink_free(c->aflink);
     ss_zone_free(c->zone);
+    ss_slice_free(c->slice);
     delete c;                   // (the staging areas of ss_upload, ss_upload_batch and ss_download go with it)
 }
 
@@ -1365,6 +1367,72 @@ extern "C" int ss_assoc_timeline(ss_ctx* c, long long* out, int n_workgroups)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, c->dev.timeline, (size_t)n_workgroups * 16 * 8, hipMemcpyDeviceToHost));
     return SS_OK;
+}
+
+// ---- sliced inference: tiled letterbox, cross-tile merge (ss_slice.hip, docs/SLICE.md) -----------------------------------------
+extern "C" int ss_slice_max_tiles(void) { return ss_slice_max_tiles_impl(); }
+extern "C" int ss_slice_max_candidates(void) { return ss_slice_max_candidates_impl(); }
+
+static int slice_state(ss_ctx* c, const char* entry, std::string& err)
+{
+    if (!c) { err = std::string(entry) + ": null context"; return SS_ERR_INVALID; }
+    if (!c->slice) { err = std::string(entry) + ": no slice state (ss_slice_config)"; return SS_ERR_INVALID; }
+    return SS_OK;
+}
+
+extern "C" int ss_slice_config(ss_ctx* c, const int* h_tiles, int n_tiles, int frame_h, int frame_w, int canvas_h, int canvas_w, int rows_per_tile,
+                               int n_extra, int n_kpt, float kpt_gain, float kpt_pad_x, float kpt_pad_y)
+{
+    return post_run(c, "ss_slice_config",
+        [&](std::string& err) {
+            return ss_slice_config_check_impl(h_tiles, n_tiles, frame_h, frame_w, canvas_h, canvas_w, rows_per_tile, n_extra, n_kpt, kpt_gain, kpt_pad_x,
+                                              kpt_pad_y, err);
+        },
+        [&](std::string& err) {
+            if (!c) { err = "ss_slice_config: null context"; return (int)SS_ERR_INVALID; }
+            hipError_t e = hipStreamSynchronize(c->stream);          // nothing of a state this call replaces may still be in flight
+            if (e != hipSuccess) { err = std::string("ss_slice_config: ") + hipGetErrorString(e); return (int)SS_ERR_HIP; }
+            return ss_slice_config_impl(&c->slice, h_tiles, n_tiles, frame_h, frame_w, canvas_h, canvas_w, rows_per_tile, n_extra, n_kpt, kpt_gain,
+                                        kpt_pad_x, kpt_pad_y, err);
+        });
+}
+
+extern "C" int ss_slice_nms_geom(ss_ctx* c, float* d_geom, int batch)
+{
+    return post_run(c, "ss_slice_nms_geom",
+        [&](std::string& err) {
+            if (!d_geom || batch < 1 || batch > 65535) { err = "ss_slice_nms_geom: null output or batch outside 1..65535"; return (int)SS_ERR_INVALID; }
+            return slice_state(c, "ss_slice_nms_geom", err);
+        },
+        [&](std::string& err) { return ss_slice_nms_geom_impl(c->slice, d_geom, batch, err); });
+}
+
+extern "C" int ss_slice_letterbox_batch(ss_ctx* c, const uint8_t* d_src, int batch, long long src_batch_stride, int row_stride, void* d_dst, int dst_flags,
+                                        int pad_value)
+{
+    return post_run(c, "ss_slice_letterbox_batch",
+        [&](std::string& err) {
+            if (int rc = ss_slice_letterbox_check_impl(d_src, batch, src_batch_stride, row_stride, d_dst, dst_flags, pad_value, err)) return rc;
+            return slice_state(c, "ss_slice_letterbox_batch", err);
+        },
+        [&](std::string& err) { return ss_slice_letterbox_impl(c->slice, c->stream, d_src, batch, src_batch_stride, row_stride, d_dst, dst_flags, pad_value, err); });
+}
+
+extern "C" int ss_slice_merge(ss_ctx* c, const float* d_rows, const int* d_counts, int batch, int row_stride, long long tile_stride, long long frame_stride,
+                              int mode, int metric, float thr, int agnostic, int out_cap, float* d_out, int out_row_stride, long long out_frame_stride,
+                              int* d_out_count, int* d_out_src, long long src_frame_stride)
+{
+    return post_run(c, "ss_slice_merge",
+        [&](std::string& err) {
+            if (int rc = ss_slice_merge_check_impl(d_rows, d_counts, batch, row_stride, tile_stride, frame_stride, mode, metric, thr, agnostic, out_cap, d_out,
+                                                   out_row_stride, out_frame_stride, d_out_count, d_out_src, src_frame_stride, err))
+                return rc;
+            return slice_state(c, "ss_slice_merge", err);
+        },
+        [&](std::string& err) {
+            return ss_slice_merge_impl(c->slice, c->stream, d_rows, d_counts, batch, row_stride, tile_stride, frame_stride, mode, metric, thr, agnostic,
+                                       out_cap, d_out, out_row_stride, out_frame_stride, d_out_count, d_out_src, src_frame_stride, err);
+        });
 }
 
 extern "C" int ss_assoc_timing(ss_ctx* c, int enable, float* mean_ms, int* launches)

@@ -151,6 +151,27 @@ int  ss_zone_blend_impl(SSZone* z, hipStream_t st, uint8_t* d_frames, int batch,
                         const int* d_heat, long long heat_frame_stride, const int* d_max, int max_stride, int alpha, std::string& err);
 void ss_zone_free(SSZone* z);
 
+// ---- ss_slice.hip
+struct SSSlice;
+int  ss_slice_max_tiles_impl();
+int  ss_slice_max_candidates_impl();
+int  ss_slice_config_check_impl(const int* h_tiles, int n_tiles, int frame_h, int frame_w, int canvas_h, int canvas_w, int rows_per_tile, int n_extra,
+                                int n_kpt, float kpt_gain, float kpt_pad_x, float kpt_pad_y, std::string& err);
+int  ss_slice_config_impl(SSSlice** ps, const int* h_tiles, int n_tiles, int frame_h, int frame_w, int canvas_h, int canvas_w, int rows_per_tile,
+                          int n_extra, int n_kpt, float kpt_gain, float kpt_pad_x, float kpt_pad_y, std::string& err);
+int  ss_slice_nms_geom_impl(const SSSlice* s, float* d_geom, int batch, std::string& err);
+int  ss_slice_letterbox_check_impl(const uint8_t* d_src, int batch, long long src_batch_stride, int row_stride, const void* d_dst, int dst_flags,
+                                   int pad_value, std::string& err);
+int  ss_slice_letterbox_impl(SSSlice* s, hipStream_t st, const uint8_t* d_src, int batch, long long src_batch_stride, int row_stride, void* d_dst,
+                             int dst_flags, int pad_value, std::string& err);
+int  ss_slice_merge_check_impl(const float* d_rows, const int* d_counts, int batch, int row_stride, long long tile_stride, long long frame_stride,
+                               int mode, int metric, float thr, int agnostic, int out_cap, const float* d_out, int out_row_stride,
+                               long long out_frame_stride, const int* d_out_count, const int* d_out_src, long long src_frame_stride, std::string& err);
+int  ss_slice_merge_impl(SSSlice* s, hipStream_t st, const float* d_rows, const int* d_counts, int batch, int row_stride, long long tile_stride,
+                         long long frame_stride, int mode, int metric, float thr, int agnostic, int out_cap, float* d_out, int out_row_stride,
+                         long long out_frame_stride, int* d_out_count, int* d_out_src, long long src_frame_stride, std::string& err);
+void ss_slice_free(SSSlice* s);
+
 // ---- ss_aflink.hip
 struct SSAflink;
 long long ss_aflink_weight_floats_impl();

@@ -672,6 +672,51 @@ class TrackerEngine:
         arr = (C.c_int * max(len(cl), 1))(*cl)
         self._ck(self.L.ss_nms_set_classes(self.ctx, arr, len(cl)))
 
+    # ---- sliced inference (csrc/ss_slice.hip, docs/SLICE.md); slicing.py makes the table ----
+    def slice_config(self, table, frame_hw, canvas_hw, rows_per_tile: int, n_extra: int = 0, n_kpt: int = 0, kpt_geom=(1.0, 0.0, 0.0)):
+        """table: int32 [T][8] of slicing.canvas(); one state per context, a second call replaces it.  kpt_geom: (gain, pad_x, pad_y) of
+        the whole frame's letterbox, what the merged rows' keypoints are expressed in."""
+        t = np.ascontiguousarray(table, np.int32)
+        if t.ndim != 2 or t.shape[1] != 8:
+            raise ValueError("slice_config: an int32 [T, 8] table")
+        self._ck(self.L.ss_slice_config(self.ctx, t.ctypes.data_as(C.POINTER(C.c_int)), t.shape[0], int(frame_hw[0]), int(frame_hw[1]),
+                                        int(canvas_hw[0]), int(canvas_hw[1]), int(rows_per_tile), int(n_extra), int(n_kpt),
+                                        float(kpt_geom[0]), float(kpt_geom[1]), float(kpt_geom[2])))
+        self._slice = (t.shape[0], int(canvas_hw[0]), int(canvas_hw[1]), int(rows_per_tile), int(n_extra))
+
+    def slice_nms_geom(self, batch: int) -> torch.Tensor:
+        """float32 [batch * T, 5] on the device: ss_nms_batch's geometry rows of the tiles, image = frame * T + tile."""
+        g = torch.zeros(batch * self._slice[0], 5, dtype=torch.float32, device=self.device)
+        self._ck(self.L.ss_slice_nms_geom(self.ctx, _ptr(g), int(batch)))
+        return g
+
+    def slice_letterbox_batch(self, frames: torch.Tensor, half: bool = False, pad_value: int = 114, out=None, channels_last: bool = False):
+        """frames uint8 [B,H,W,3] BGR on the device -> [B*T,3,canvas_h,canvas_w] float/half, every tile of every frame in one launch."""
+        T, ch, cw = self._slice[:3]
+        B = frames.shape[0]
+        if out is None:
+            out = torch.empty(B * T, 3, ch, cw, dtype=torch.float16 if half else torch.float32, device=self.device,
+                              memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+        flags = (_lib.DST_F16 if half else 0) | (_lib.DST_HWC if channels_last else 0)
+        self._ck(self.L.ss_slice_letterbox_batch(self.ctx, _ptr(frames), B, frames.stride(0), frames.stride(1), _ptr(out), flags, int(pad_value)))
+        return out
+
+    def slice_merge(self, rows: torch.Tensor, counts: torch.Tensor, mode: str = "nmm", metric: str = "ios", thr: float = 0.5,
+                    agnostic: bool = False, out_cap: int = 128, out=None, count=None, src=None):
+        """rows [B,T,R',6+n_extra] f32 (R' >= rows_per_tile) and counts [B,T] i32 as ss_nms_batch leaves them on B*T images -> (rows
+        [B,out_cap,6+n_extra] in frame pixels, counts [B], source indices [B,out_cap] = tile * rows_per_tile + row).  One launch."""
+        B, ld = rows.shape[0], 6 + self._slice[4]
+        if out is None:
+            out = torch.zeros(B, out_cap, ld, dtype=torch.float32, device=self.device)
+        if count is None:
+            count = torch.zeros(B, dtype=torch.int32, device=self.device)
+        if src is None:
+            src = torch.zeros(B, out_cap, dtype=torch.int32, device=self.device)
+        self._ck(self.L.ss_slice_merge(self.ctx, _ptr(rows), _ptr(counts), B, rows.stride(2), rows.stride(1), rows.stride(0),
+                                       ("nms", "nmm").index(mode), ("iou", "ios").index(metric), float(thr), int(bool(agnostic)), int(out_cap),
+                                       _ptr(out), out.stride(1), out.stride(0), _ptr(count), _ptr(src), src.stride(0)))
+        return out, count, src
+
     def crop_norm_batch(self, frames: torch.Tensor, dets: torch.Tensor, n: int, counts=None, half: bool = False,
                         out=None, channels_last: bool = False):
         """frames uint8 [B,H,W,3], dets [B,cap,>=4] float32, counts [B] int32 -> crops [B*n,3,256,128]."""

@@ -40,7 +40,7 @@ class FramePipeline:
                  dcfg: Optional[DetectConfig] = None, det_source: str = "detector", feat_source: str = "reid",
                  graph: str = "all", debug: bool = False, run_nets: bool = True, seed: int = 0, detect_only_rows: int = 0, cmc: bool = False,
                  reid_half: Optional[bool] = None, crops_u8: bool = True, tracker: str = "strongsort", with_reid: bool = False,
-                 reid_model: str = "osnet", with_pose: bool = False, gmc_method: str = "ecc", ocsort_use_byte: bool = False):
+                 reid_model: str = "osnet", with_pose: bool = False, gmc_method: str = "ecc", ocsort_use_byte: bool = False, slice_cfg=None):
         self.cfg, self.dcfg = cfg or StrongSortConfig(), dcfg or DetectConfig()
         self.S, (self.H, self.W) = n_streams, frame_hw
         # tracker = "bytetrack" / "botsort": the BYTE tracker family (csrc/ss_byte.hip) on IoU and scores — no OSNet is built, no
@@ -58,7 +58,13 @@ class FramePipeline:
         # OSNet and cuts no crops, and its engine stands where the BYTE engine stands (self.byte / self.trk: the same stage bodies).
         # tracker = "deep_ocsort": Deep OC-SORT (csrc/ss_deepoc.hip, docs/DEEPOCSORT.md) — OSNet, crops and ReID stages stay as for botsort
         # with with_reid, the warps stage as for botsort; its engine stands where the BYTE engine stands.
+        # slice_cfg (slicing.SliceConfig): sliced inference (csrc/ss_slice.hip, docs/SLICE.md) — the detector sees T tiles of every frame
+        # (S * T images: lb, pred_in and the per-tile NMS rows carry that leading dimension), one launch letterboxes them, one launch
+        # merges the tiles' rows into b.dets / b.ndets; from there on nothing differs.  None: nothing of it is allocated or launched.
         from .config import byte_config, ocsort_config, deep_ocsort_config, check_reid_model, check_pose, check_gmc_method
+        self.slice = slice_cfg
+        if self.slice is not None and reid_model == "auto":
+            raise ValueError("sliced inference cannot feed reid_model='auto': the detector's anchor indices are per tile")
         self.deep_cfg = deep_ocsort_config(tracker, with_reid, with_pose, ocsort_use_byte)
         self.oc_cfg = ocsort_config(tracker, ocsort_use_byte, cmc, with_reid, with_pose)
         self.byte_cfg = byte_config(tracker, with_reid, with_pose)
@@ -108,6 +114,18 @@ class FramePipeline:
             self.max_det = min(self.dcfg.max_det, self.det_rows)
         self.geom = letterbox_geometry(self.H, self.W, self.dcfg.imgsz, self.dcfg.stride)
         self.gain, self.pad_x, self.pad_y = scale_geometry(self.geom, self.H, self.W)
+        # in_geom: the detector's input.  Sliced: the canvas every tile is letterboxed into; self.geom / gain / pad stay the whole frame's
+        # (the merged rows' keypoints are expressed in it, as an unsliced pipeline's are)
+        self.in_geom, self.T = self.geom, 1
+        if self.slice is not None:
+            from . import slicing
+            try:
+                self.in_geom, self.tile_table = slicing.canvas(self.H, self.W, self.slice, self.dcfg.imgsz, self.dcfg.stride)
+            except ValueError:
+                self.eng.close()
+                raise
+            self.T = len(self.tile_table)
+            self.tile_rows = slicing.rows_per_tile(self.det_rows, self.T)
         self.detector = self.reid = None
         if run_nets:
             self.detector = nets.build_detector(detector, seed).to(dev, self.dtype).to(memory_format=torch.channels_last)
@@ -122,10 +140,12 @@ class FramePipeline:
         self.nx = self.nk + self.nm                             # extra columns NMS carries along with every kept row
         try:
             check_pose(self.byte_cfg, self.nk)
+            if self.slice is not None and self.nm:
+                raise ValueError("sliced inference cannot run a segmentation model: a row's mask coefficients belong to its tile's prototypes")
         except ValueError:
             self.eng.close()                                    # (the tracker context exists already: do not leak it)
             raise
-        g, S = self.geom, n_streams
+        g, S = self.in_geom, n_streams
         self.n_anchors = sum((g.out_h // s) * (g.out_w // s) for s in (8, 16, 32))
         # how the stage bodies below differ between this class and OverlappedPipeline, as data: one frame per buffer set,
         # crops at one slot range per stream, net outputs not kept (OverlappedPipeline sets its own after this constructor)
@@ -140,6 +160,10 @@ class FramePipeline:
         self.geom_dev = torch.tensor([[self.gain, self.pad_x, self.pad_y, float(self.W), float(self.H)]] * S,
                                      dtype=torch.float32, device=dev)      # per-image scale_boxes geometry for ss_nms_batch
         self.img_hw = torch.tensor([[self.H, self.W]] * S, dtype=torch.int32, device=dev)
+        if self.slice is not None:
+            self.eng.slice_config(self.tile_table, (self.H, self.W), (g.out_h, g.out_w), self.tile_rows, n_extra=self.nx, n_kpt=self.nk // 3,
+                                  kpt_geom=(self.gain, self.pad_x, self.pad_y))
+            self.tile_geom_dev = self.eng.slice_nms_geom(S)        # per-image geometry of the S * T tile images
         self.out, self.nout = self.eng.out, self.eng.nout
         self._maps = None                   # reid_model "auto": the head inputs of the detector call in flight
         self.graph = None
@@ -159,7 +183,9 @@ class FramePipeline:
     def _letterbox(self, b):
         if self.cmc:                                           # the group's F warps, beside the detector (stateless stage)
             self.eng.estimate_warps(self.gmc_method, b.frames, self.F, b.warps, n_valid=b.nvalid)    # a partial group: the last REAL frame becomes "previous"
-        if self.run_nets:
+        if self.run_nets and self.slice is not None:           # every tile of every frame of the set, one launch
+            self.eng.slice_letterbox_batch(b.frames, half=self.half, pad_value=self.dcfg.pad_value, out=b.lb, channels_last=True)
+        elif self.run_nets:
             self.eng.letterbox_batch(b.frames, self.geom, half=self.half, pad_value=self.dcfg.pad_value, out=b.lb,
                                      channels_last=True)
 
@@ -204,8 +230,17 @@ class FramePipeline:
 
     def _nms(self, b):
         e = self.eng
-        e.nms_batch(b.pred_in, self.nc, self.dcfg, self.geom_dev, n_extra=self.nx, rows=b.dets, keep=b.keep,
-                    count=b.ndets, max_det=self.max_det)
+        if self.slice is not None:
+            # the tiles' NMS on S * T images (rows in tile pixels), then the merge: b.dets / b.ndets as an unsliced NMS leaves them,
+            # b.keep = the kept rows' source indices (tile * tile_rows + row) where an unsliced pipeline has anchors
+            sc = self.slice
+            e.nms_batch(b.pred_in, self.nc, self.dcfg, self.tile_geom_dev, n_extra=self.nx, rows=b.tile_dets, keep=b.tile_keep,
+                        count=b.tile_ndets, max_det=min(self.max_det, self.tile_rows))
+            e.slice_merge(b.tile_dets.view(-1, self.T, self.tile_rows, 6 + self.nx), b.tile_ndets.view(-1, self.T), sc.merge, sc.metric, sc.thr,
+                          self.dcfg.agnostic_nms, self.max_det, out=b.dets, count=b.ndets, src=b.keep)
+        else:
+            e.nms_batch(b.pred_in, self.nc, self.dcfg, self.geom_dev, n_extra=self.nx, rows=b.dets, keep=b.keep,
+                        count=b.ndets, max_det=self.max_det)
         if self.nx:
             b.dets6.copy_(b.dets[:, :, :6])
         if self.native and self.run_nets and self.feat_source == "reid":
@@ -384,10 +419,15 @@ class _Bufs:
     carries the packed ReID batch's offsets and the count of its real frames."""
 
     def __init__(self, p: "FramePipeline", S: int, rows: int = MAX_DETS, F: int = 1, cmc: bool = False, group: bool = False):
-        dev, g = p.dev, p.geom
+        dev, g = p.dev, p.in_geom
+        ST = S * p.T                        # images the detector sees: sliced, T tiles of every frame (tile-side buffers, leading dimension S * T)
         self.frames = torch.zeros(S, p.H, p.W, 3, dtype=torch.uint8, device=dev)
-        self.lb = torch.zeros(S, 3, g.out_h, g.out_w, dtype=p.dtype, device=dev).contiguous(memory_format=torch.channels_last)
-        self.pred_in = torch.zeros(S, 4 + p.nc + p.nx, p.n_anchors, dtype=torch.float32, device=dev)
+        self.lb = torch.zeros(ST, 3, g.out_h, g.out_w, dtype=p.dtype, device=dev).contiguous(memory_format=torch.channels_last)
+        self.pred_in = torch.zeros(ST, 4 + p.nc + p.nx, p.n_anchors, dtype=torch.float32, device=dev)
+        if p.slice is not None:             # the tiles' NMS rows, anchors and counts, which the merge reads
+            self.tile_dets = torch.zeros(ST, p.tile_rows, 6 + p.nx, dtype=torch.float32, device=dev)
+            self.tile_keep = torch.zeros(ST, p.tile_rows, dtype=torch.int32, device=dev)
+            self.tile_ndets = torch.zeros(ST, dtype=torch.int32, device=dev)
         self.dets = torch.zeros(S, rows, 6 + p.nx, dtype=torch.float32, device=dev)
         self.dets6 = self.dets if p.nx == 0 else torch.zeros(S, rows, 6, dtype=torch.float32, device=dev)
         # segmentation: the frame's mask prototypes [nm, out_h/4, out_w/4] stay here until the caller has built its Results
@@ -457,6 +497,8 @@ class OverlappedPipeline(FramePipeline):
             if not self.need_reid:
                 reid_split = None
         self.geom_dev = self.geom_dev[:1].repeat(self.Sv, 1).contiguous()
+        if self.slice is not None:
+            self.tile_geom_dev = self.eng.slice_nms_geom(self.Sv)
         self.outs = torch.zeros(self.F, self.S, MAX_TRACKS, 8, dtype=torch.float32, device=self.dev)
         self.nouts = torch.zeros(self.F, self.S, dtype=torch.int32, device=self.dev)
         split_det = self.run_nets and n_stages >= 4 and hasattr(self.detector, "forward_backbone")

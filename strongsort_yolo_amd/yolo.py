@@ -290,7 +290,8 @@ class YOLO:
     def __init__(self, weights: str = "yolov8n.pt", seed: int = 0, random_init_ok: bool = False, reid_batch: int = 128,
                  camera_motion: bool = False, reid_weights: Optional[str] = None, reid_fp32: bool = True, half: bool = True,
                  device_masks: bool = False, tracker_type: str = "strongsort", with_reid: bool = False, reid_model: str = "osnet",
-                 with_pose: bool = False, gmc_method: str = "ecc", ocsort_use_byte: bool = False):
+                 with_pose: bool = False, gmc_method: str = "ecc", ocsort_use_byte: bool = False, slice_hw=None, slice_overlap=0.2,
+                 slice_full: bool = True, slice_merge: str = "nmm", slice_metric: str = "ios", slice_thr: float = 0.5):
         """reid_fp32 (default since round 6): ReID crops + OSNet-x0.25 in fp32 on the fp32 kernels — appearance distances within 1e-4 of a CPU fp32
         network, which f16 activations miss by 330x (reid_fp32=False: the f16 throughput mode, ~1.2x the per-frame rate, 1.7x the stream rate).
         half=False: the DETECTOR in fp32 as well (the reference's own precision: it passes no half=, yolo_multi_model.py:41) on the
@@ -322,7 +323,20 @@ class YOLO:
         tracker_type "deep_ocsort": Deep OC-SORT on the device (docs/DEEPOCSORT.md) — OC-SORT without the BYTE stage, with OSNet-x0.25
         features of every tracked row (reid_weights, reid_fp32 and half as for StrongSORT) in an adaptively weighted appearance cost,
         a feature EMA that follows the detection score, and, with camera_motion, the warps (gmc_method "ecc" or "sparseOptFlow")
-        applied to filters and observations.  with_reid, with_pose, ocsort_use_byte and reid_model="auto" are ValueErrors."""
+        applied to filters and observations.  with_reid, with_pose, ocsort_use_byte and reid_model="auto" are ValueErrors.
+        slice_hw (sh, sw): sliced inference (SAHI; docs/SLICE.md) — the detector runs on overlapping sh x sw tiles of the frame as one
+        batch (slice_overlap: one ratio or (oh, ow); slice_full: the whole frame as one more tile) and the tiles' rows are merged on the
+        device (slice_merge "nmm" = GREEDYNMM or "nms", slice_metric "ios" or "iou", slice_thr); predict, track and track_stream then
+        see small objects at the tiles' scale.  The detector costs T times as much.  Segmentation models and reid_model="auto" are
+        ValueErrors, as are more than 64 tiles; the slice must fit the frame (checked when the first frame arrives)."""
+        self.slice = None
+        if slice_hw is not None:
+            from .slicing import SliceConfig
+            self.slice = SliceConfig(slice_hw, slice_overlap, slice_full, slice_merge, slice_metric, slice_thr)
+            if "seg" in os.path.basename(weights):
+                raise ValueError("sliced inference cannot run a segmentation model: a row's mask coefficients belong to its tile's prototypes")
+            if reid_model == "auto":
+                raise ValueError("sliced inference cannot feed reid_model='auto': the detector's anchor indices are per tile")
         deep_ocsort_config(tracker_type, with_reid, with_pose, ocsort_use_byte)               # ValueError on anything else
         ocsort_config(tracker_type, ocsort_use_byte, camera_motion, with_reid, with_pose)      # ValueError on anything else
         byte_config(tracker_type, with_reid, with_pose)
@@ -371,6 +385,8 @@ class YOLO:
                 self._pipe_kw["with_pose"] = True
             if ocsort_use_byte:
                 self._pipe_kw["ocsort_use_byte"] = True
+        if self.slice is not None:
+            self._pipe_kw["slice_cfg"] = self.slice
         self.device_masks = bool(device_masks)
         self._fill = None
         self._frame_index = 0
@@ -384,7 +400,7 @@ class YOLO:
     def _state_key(self, shape, device):
         cl = self.overrides.get("classes")
         cl = None if cl is None else tuple(int(c) for c in (cl if isinstance(cl, (list, tuple)) else [cl]))
-        return (tuple(shape), int(device or 0), self._dcfg(), cl)
+        return (tuple(shape), int(device or 0), self._dcfg(), cl, None if self.slice is None else self.slice.key())
 
     def _build(self, cls, shape, device, need_reid=True, **kw):
         from . import nets
