@@ -125,6 +125,23 @@ int ss_nms_batch(ss_ctx* ctx, const float* d_pred, int batch, long long pred_bat
                  int max_det, const float* d_geom, float* d_rows, int row_stride,
                  long long rows_batch_stride, int* d_keep, long long keep_batch_stride, int* d_count);
 
+/* ---- oriented boxes: rotated NMS on ProbIoU (docs/OBB.md) -----------------------------------------
+ * d_pred: OBB head layout [(4+nc+1)][n_anchors] float (xywh in network-input pixels, class scores, theta).  ss_nms_batch's
+ * arguments without max_wh: classes are separated by equality, not by an offset (R-03).  A candidate is removed when ANY
+ * higher-scored candidate has ProbIoU >= iou_thres with it (R-02, Ultralytics' nms_rotated; not a greedy scan).  Writes up to
+ * max_det rows [x1,y1,x2,y2,conf,cls, cx,cy,w,h,theta] (row_stride >= 11) in ORIGINAL-image pixels: the rotated box is
+ * scaled, not clipped, and regularised (w >= h, theta in [0, pi)); columns 0..3 are its axis-aligned envelope clipped to the
+ * image, so columns 0..5 read as a plain detection row.  Candidate filter, `classes` mask, d_keep, d_count, the workspace
+ * growth outside a capture and the 8192-candidate capacity are ss_nms_batch's.  Asynchronous and capturable. */
+int ss_nms_obb_batch(ss_ctx* ctx, const float* d_pred, int batch, long long pred_batch_stride, int n_anchors,
+                     int nc, float conf_thres, float iou_thres, int agnostic, int max_det, const float* d_geom,
+                     float* d_rows, int row_stride, long long rows_batch_stride, int* d_keep,
+                     long long keep_batch_stride, int* d_count);
+/* Known-answer entry, synchronous: ProbIoU of every pair of the HOST lists h_a [n][5] and h_b [m][5] (cx, cy, w, h, theta;
+ * n, m <= 4096) by the device function the rotated NMS uses, into the host matrix h_out [n][m].  A box with a non-finite
+ * field, w <= 0, h <= 0 or |theta| > 2^20 has ProbIoU 0 with everything (R-01). */
+int ss_probiou(ss_ctx* ctx, const float* h_a, int n, const float* h_b, int m, double* h_out);
+
 /* The `classes` override of the reference (yolo_multi_model.py:22, commented out there): keep only anchors whose best
  * class is in classes[0..n) (ids 0..127); n = 0 keeps every class (default).  Host state of the context, read by the
  * following ss_nms / ss_nms_batch calls (and baked into a HIP graph that captures them). */
@@ -272,6 +289,20 @@ int ss_byte_update_group_kpts(ss_ctx* ctx, int n_frames, const float* d_dets, co
 /* Synchronous: the stored poses of one stream in ss_byte_get_tracks' list order: offsets [n][n_kpt][2] f64 (from the box centre, in
  * box widths / heights) and one visibility word per track (bit k = keypoint k); either may be NULL. */
 int ss_byte_get_keypoints(ss_ctx* ctx, int stream, int cap, double* offsets, unsigned* visible);
+/* Oriented boxes (docs/OBB.md §4): on != 0 swaps the cost of the three associations and of the duplicate test for 1 - ProbIoU of the
+ * rotated boxes; every track remembers the angle of its last row (R-06), the Kalman filter is unchanged.  Resets every stream.
+ * Allocates the per-slot angles and the boxes' ProbIoU terms on the first switch-on.  SS_ERR_INVALID without BYTE state or while ReID,
+ * the keypoint term or GMC is on (and those refuse while this is on).  While it is on, ss_byte_update(_group) and
+ * ss_byte_update_group_feats are refused: use ss_byte_update_group_obb. */
+int ss_byte_set_obb(ss_ctx* ctx, int on);
+/* ss_byte_update_group on ss_nms_obb_batch's rows: d_dets [n_frames][n_streams][SS_MAX_DETS][11] = x1, y1, x2, y2, conf, cls, cx, cy,
+ * w, h, theta (columns 0..3 are not read).  d_out as ss_byte_update_group's, columns 0..3 the axis-aligned envelope (not clipped) of
+ * the track's rotated box; d_out_rbox [n_frames][n_streams][SS_MAX_TRACKS][5] = cx, cy, w, h, theta of the same rows.  One launch:
+ * capturable. */
+int ss_byte_update_group_obb(ss_ctx* ctx, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, float* d_out_rbox,
+                             int* d_nout);
+/* Synchronous: the angles [n] of one stream's tracks in ss_byte_get_tracks' list order (after ss_byte_set_obb). */
+int ss_byte_get_angles(ss_ctx* ctx, int stream, int cap, float* angles);
 /* Synchronous inspection call, a permanent part of this ABI like ss_get_debug (the tests compare k_byte_kpts' output through it bit
  * for bit): the detection keypoints of image (frame, stream) as the last ss_byte_update_group_kpts call prepared them:
  * xy [SS_MAX_DETS][n_kpt][2] f32 in original pixels, visibility words [SS_MAX_DETS]; rows past the image's count are not written. */
@@ -554,7 +585,9 @@ int ss_op_v8_decode_f16(void* stream, const void* const* d_box, const void* cons
 /* The same with the head's third branch as extra rows 4 + nc .. 4 + nc + n_ext of the prediction [B][4 + nc + n_ext][A]: d_ext[3]
  * [B][H][W][ext_ld] half with the bias already added (the branch's last 1x1 through ss_op_pointwise_f16); ext_mode 1: keypoint
  * triplets decoded as Ultralytics Pose.kpts_decode ((2 v + cell) * stride for x and y, sigmoid for the visibility), n_ext % 3 == 0;
- * ext_mode 0: raw values (Segment's mask coefficients).  cls_ld >= nc: channels per pixel of the class tensors (a one-class head
+ * ext_mode 0: raw values (Segment's mask coefficients); ext_mode 2 (n_ext == 1): an oriented box's angle, theta = (sigmoid(v) - 1/4) pi
+ * in row 4 + nc, and rows 0..3 become dist2rbox's (cx, cy, w, h): the centre's offset from the anchor turned by theta (docs/OBB.md §2).
+ * cls_ld >= nc: channels per pixel of the class tensors (a one-class head
  * zero-padded to 8 so that its last 1x1 runs on ss_op_pointwise_f16).  n_ext == 0 and cls_ld == nc: ss_op_v8_decode_f16. */
 int ss_op_v8_decode_ext_f16(void* stream, const void* const* d_box, const void* const* d_cls, const void* const* d_box_bias,
                             const void* const* d_cls_bias, const void* const* d_ext, int n_ext, int ext_ld, int ext_mode,
@@ -696,7 +729,7 @@ int ss_op32_conv_plan(int N, int H, int W, int Cin, int Cout, int ks, int stride
 /* cat(upsample2x_nearest(lo), hi) (lo_first != 0) or cat(hi, upsample2x_nearest(lo)) along channels in one pass (the neck's two
  * upsample + concat pairs), fp32 NHWC: d_lo [N][H/2][W/2][.] pixel stride ls, d_hi [N][H][W][.] pixel stride hs, d_out dense. */
 /* YOLOv8 head decode in fp32 (DFL expectation, dist2bbox, stride scale, class sigmoid, level concat; the third branch as keypoint
- * triplets (ext_mode 1) or raw (0)): dense NHWC float branch outputs with their bias -> d_pred [B][4 + nc + n_ext][A]. */
+ * triplets (ext_mode 1), raw (0) or an oriented box's angle (2, as ss_op_v8_decode_ext_f16)): dense NHWC float branch outputs with their bias -> d_pred [B][4 + nc + n_ext][A]. */
 int ss_op32_v8_decode(void* stream, const void* const* d_box, const void* const* d_cls, const void* const* d_ext, int n_ext, int ext_ld,
                       int ext_mode, const int* H, const int* W, const int* strides, int B, int nc, int cls_ld, float* d_pred);
 /* SPPF's three chained 5x5 max pools + concat in one pass, fp32: d_x NHWC [N][H][W][.] (pixel stride xs) -> d_out dense [N][H][W][4 C]. */

@@ -272,27 +272,38 @@ class LabelsWriter:
     """`frameId cls id conf x1 y1 x2 y2 -1 -1 -1 -1` per tracked box (yolo_multi_model.py:165-169).
     compat=True reproduces the reference's quirks (frameId always 0, :32; append mode, :39)."""
 
-    def __init__(self, path: str, compat: bool = False):
+    def __init__(self, path: str, compat: bool = False, obb: bool = False):
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         self.f = open(path, "a" if compat else "w")
         self.compat = compat
+        # an oriented-box model (docs/OBB.md §5): the labels file holds the envelopes, <name>_labels_obb.txt beside it the rotated boxes
+        self.f_obb = open(path[:-4] + "_obb.txt", "a" if compat else "w") if obb else None
 
     def write(self, frame_id: int, results) -> int:
         n = 0
         for r in results:
-            if r is None or r.boxes is None or r.boxes.id is None:
+            b = None if r is None else r.boxes if r.boxes is not None else getattr(r, "obb", None)
+            if b is None or b.id is None:
                 continue
-            for bbox in r.boxes:
+            if self.f_obb is not None and b is not r.boxes:                     # frame cls id conf cx cy w h theta
+                for conf, cls, id_, q in zip(b.conf, b.cls, b.id, b.xywhr.tolist()):
+                    self.f_obb.write(f"{0 if self.compat else frame_id} {int(cls)} {int(id_)} {round(float(conf), 3)} "
+                                     f"{q[0]:.2f} {q[1]:.2f} {q[2]:.2f} {q[3]:.2f} {q[4]:.5f}\n")
+            for bbox in b:
                 for conf, cls, xyxy, id_ in zip(bbox.conf, bbox.cls, bbox.xyxy, bbox.id):
                     x1, y1, x2, y2 = (int(v) for v in xyxy)                 # reference :166 int() box corners
                     fid = 0 if self.compat else frame_id
                     self.f.write(f"{fid} {int(cls)} {int(id_)} {round(float(conf), 3)} {x1} {y1} {x2} {y2} -1 -1 -1 -1\n")
                     n += 1
         self.f.flush()
+        if self.f_obb is not None:
+            self.f_obb.flush()
         return n
 
     def close(self):
         self.f.close()
+        if self.f_obb is not None:
+            self.f_obb.close()
 
 
 class ClassCounter:
@@ -305,9 +316,10 @@ class ClassCounter:
 
     def update(self, results):
         for r in results:
-            if r is None or r.boxes is None or r.boxes.id is None:
+            b = None if r is None else r.boxes if r.boxes is not None else getattr(r, "obb", None)
+            if b is None or b.id is None:
                 continue
-            for cls, id_ in zip(r.boxes.cls, r.boxes.id):
+            for cls, id_ in zip(b.cls, b.id):
                 self.votes[int(id_)][int(cls)] += 1
 
     def counts(self) -> dict:
@@ -356,7 +368,8 @@ def process_video(args: dict, model=None) -> dict:
                      gmc_method=args.get("gmc_method", "ecc"), ocsort_use_byte=args.get("ocsort_use_byte", False), **slice_kwargs(args))
         model.overrides.update(conf=0.3, iou=0.4, agnostic_nms=False, max_det=1000)      # :18-21
     name = os.path.splitext(os.path.basename(str(source)))[0] or "stream"
-    writer = LabelsWriter(os.path.join(args.get("outdir", "output"), f"{name}_labels.txt"), args.get("compat", False))
+    writer = LabelsWriter(os.path.join(args.get("outdir", "output"), f"{name}_labels.txt"), args.get("compat", False),
+                          obb=getattr(model, "_obb", False))
     counter = ClassCounter(model.names)
     frames, t0, fps = 0, time.time(), 0.0
     batch = int(args.get("batch", 16))

@@ -1176,6 +1176,41 @@ extern "C" int ss_nms_batch(ss_ctx* c, const float* pred, int batch, long long p
     return SS_OK;
 }
 
+extern "C" int ss_nms_obb_batch(ss_ctx* c, const float* pred, int batch, long long pred_batch_stride, int n_anchors, int nc,
+                                float conf_thres, float iou_thres, int agnostic, int max_det, const float* d_geom, float* rows,
+                                int row_stride, long long rows_batch_stride, int* keep, long long keep_batch_stride, int* count)
+{
+    if (!c || !pred || !d_geom || !rows || !keep || !count || row_stride < 11 || batch < 0 || batch > 65535 || nc < 1 || n_anchors < 0)
+        return fail(c, SS_ERR_INVALID, "ss_nms_obb_batch: bad argument");
+    int rc = nms_reserve(c, batch);
+    if (rc) return rc;
+    rc = ss_launch_nms_obb(pred, batch, pred_batch_stride, n_anchors, nc, conf_thres, iou_thres, agnostic, max_det, d_geom, rows, row_stride,
+                           rows_batch_stride, keep, keep_batch_stride, count, c->nms_ws, c->nms_ws_bytes * (size_t)c->nms_units,
+                           c->cls_mask[0], c->cls_mask[1], c->stream);
+    if (rc) return fail(c, rc, "ss_nms_obb_batch: anchors exceed the workspace (n_anchors <= 32768)");
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+// synchronous known-answer entry: host lists in, the device function on every pair, host matrix out
+extern "C" int ss_probiou(ss_ctx* c, const float* h_a, int n, const float* h_b, int m, double* h_out)
+{
+    if (!c || n < 0 || m < 0 || n > 4096 || m > 4096 || ((n > 0 && !h_a) || (m > 0 && !h_b) || (n > 0 && m > 0 && !h_out)))
+        return fail(c, SS_ERR_INVALID, "ss_probiou: null argument or a list outside 0..4096");
+    if (n == 0 || m == 0) return SS_OK;
+    SsBuf<SS_DEVICE> da, db, dout;
+    HIPCHK(c, da.reserve((size_t)n * 5 * sizeof(float), SS_EXACT));
+    HIPCHK(c, db.reserve((size_t)m * 5 * sizeof(float), SS_EXACT));
+    HIPCHK(c, dout.reserve((size_t)n * m * sizeof(double), SS_EXACT));
+    HIPCHK(c, hipMemcpyAsync(da.as(), h_a, (size_t)n * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(db.as(), h_b, (size_t)m * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    ss_launch_probiou(da.as<float>(), n, db.as<float>(), m, dout.as<double>(), c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_out, dout.as(), (size_t)n * m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SS_OK;
+}
+
 extern "C" int ss_nms_set_classes(ss_ctx* c, const int* classes, int n)
 {
     if (!c || n < 0 || (n > 0 && !classes)) return fail(c, SS_ERR_INVALID, "ss_nms_set_classes: bad argument");
@@ -1963,6 +1998,7 @@ extern "C" int ss_byte_update_group(ss_ctx* c, int n_frames, const float* d_dets
     if (const int rc = byte_update_check(c, "ss_byte_update_group", d_dets && d_ndets && d_out && d_nout, n_frames)) return rc;
     if (c->byte->dev.reid) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: ReID is on, the features go through ss_byte_update_group_feats");
     if (c->byte->dev.pose) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: the keypoint term is on, the keypoints go through ss_byte_update_group_kpts");
+    if (c->byte->dev.obb) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: oriented boxes are on, the 11-column rows go through ss_byte_update_group_obb");
     ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, nullptr, d_out, d_nout, c->stream);
     HIPCHK(c, hipGetLastError());
     return SS_OK;
@@ -1976,6 +2012,7 @@ extern "C" int ss_byte_update_group_feats(ss_ctx* c, int n_frames, const float* 
     if (const int rc = byte_update_check(c, "ss_byte_update_group_feats", d_dets && d_ndets && d_out && d_nout, n_frames)) return rc;
     if (c->byte->dev.reid && !d_feats) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: ReID is on and d_feats is NULL");
     if (c->byte->dev.pose) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: the keypoint term is on, the keypoints go through ss_byte_update_group_kpts");
+    if (c->byte->dev.obb) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: oriented boxes are on, the 11-column rows go through ss_byte_update_group_obb");
     ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, d_feats, d_out, d_nout, c->stream);
     HIPCHK(c, hipGetLastError());
     return SS_OK;
@@ -1989,6 +2026,7 @@ extern "C" int ss_byte_set_reid(ss_ctx* c, int on, double proximity_thresh, doub
     SSByteDev& b = c->byte->dev;
     if (on && !b.xywh) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: ReID needs the xywh (BoT-SORT) state");
     if (on && b.pose) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: the keypoint term is on (ss_byte_set_pose): the two are not combined");
+    if (on && b.obb) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: oriented boxes are on (ss_byte_set_obb): the two are not combined");
     if (on && !b.smooth) {
         const size_t ns = (size_t)b.S * SS_MAXT * SS_F, nu = (size_t)SS_FMAX * b.S * SS_MAXD * SS_F;
         void *p = nullptr, *q = nullptr;
@@ -2015,6 +2053,7 @@ extern "C" int ss_byte_set_pose(ss_ctx* c, int on, int n_kpt, const double* sigm
     if (on) {
         if (!b.xywh) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: the keypoint term needs the xywh (BoT-SORT) state");
         if (b.reid) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: ReID is on (ss_byte_set_reid): the two are not combined");
+        if (b.obb) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: oriented boxes are on (ss_byte_set_obb): the two are not combined");
         if (n_kpt < 1 || n_kpt > SS_BYTE_MAXK) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: 1 <= n_kpt <= 32");
         if (!sigmas) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: sigmas is NULL");
         b.pose = 0;                                                // a failure below leaves the term off, never half set up
@@ -2152,7 +2191,58 @@ extern "C" int ss_byte_set_gmc(ss_ctx* c, const double* d_warps)
 {
     if (!c || !c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_set_gmc: no BYTE state (ss_byte_create)");
     if (d_warps && !c->byte->dev.xywh) return fail(c, SS_ERR_INVALID, "ss_byte_set_gmc: GMC needs the xywh (BoT-SORT) state");
+    if (d_warps && c->byte->dev.obb) return fail(c, SS_ERR_INVALID, "ss_byte_set_gmc: oriented boxes are on (ss_byte_set_obb): GMC does not move rotated tracks");
     c->byte->dev.gmc = d_warps;
+    return SS_OK;
+}
+
+// docs/OBB.md §4: association on ProbIoU on (on != 0) or off.  Either way every stream restarts (ss_byte_reset).  The per-slot angles
+// and the boxes' ProbIoU terms are allocated on the first switch-on and kept.  Not with ReID, the keypoint term or GMC.
+extern "C" int ss_byte_set_obb(ss_ctx* c, int on)
+{
+    if (!c || !c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_set_obb: no BYTE state (ss_byte_create)");
+    SSByteDev& b = c->byte->dev;
+    if (on && (b.reid || b.pose || b.gmc))
+        return fail(c, SS_ERR_INVALID, "ss_byte_set_obb: ReID, the keypoint term or GMC is on: oriented boxes are not combined with them");
+    if (on && !b.angle) {
+        const size_t nt = (size_t)b.S * SS_MAXT, nd = (size_t)b.S * SS_MAXD;
+        void* p[3] = {nullptr, nullptr, nullptr};
+        const size_t bytes[3] = {nt * 4, nt * 6 * 8, nd * 6 * 8};
+        for (int i = 0; i < 3; ++i) {
+            HIPCHK(c, hipMalloc(&p[i], bytes[i]));
+            c->byte->allocs.push_back(p[i]);
+            HIPCHK(c, hipMemsetAsync(p[i], 0, bytes[i], c->stream));
+        }
+        b.angle = (float*)p[0]; b.tbox = (double*)p[1]; b.dbox = (double*)p[2];      // all three exist: commit them together
+    }
+    b.obb = on != 0;
+    return ss_byte_reset(c, -1);
+}
+
+// docs/OBB.md §4: ss_byte_update_group on the 11-column rows ss_nms_obb_batch writes; one launch on the context's stream: capturable.
+extern "C" int ss_byte_update_group_obb(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, float* d_out_rbox,
+                                        int* d_nout)
+{
+    if (const int rc = byte_update_check(c, "ss_byte_update_group_obb", d_dets && d_ndets && d_out && d_out_rbox && d_nout, n_frames)) return rc;
+    if (!c->byte->dev.obb) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_obb: oriented boxes are off (ss_byte_set_obb)");
+    ss_launch_byte_group_obb(c->byte->dev, n_frames, d_dets, d_ndets, d_out, d_out_rbox, d_nout, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
+// Synchronous: the angles [n] of one stream's tracks in ss_byte_get_tracks' list order.
+extern "C" int ss_byte_get_angles(ss_ctx* c, int s, int cap, float* angles)
+{
+    if (!c || !c->byte || s < 0 || s >= c->dev.S || cap < 0 || !angles) return fail(c, SS_ERR_INVALID, "ss_byte_get_angles: no BYTE state, bad stream or NULL");
+    const SSByteDev& b = c->byte->dev;
+    if (!b.angle) return fail(c, SS_ERR_INVALID, "ss_byte_get_angles: oriented boxes were never switched on (ss_byte_set_obb)");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int nt = 0, nl = 0;
+    std::vector<int> slots;
+    if (const int rc = byte_read_lists(c, "ss_byte_get_angles", s, cap, nt, nl, slots)) return rc;
+    std::vector<float> an(SS_MAXT);
+    HIPCHK(c, hipMemcpy(an.data(), b.angle + (size_t)s * SS_MAXT, SS_MAXT * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < slots.size(); ++i) angles[i] = an[slots[i]];
     return SS_OK;
 }
 

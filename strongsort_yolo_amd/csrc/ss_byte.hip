@@ -19,6 +19,7 @@
 #include "ss_launch.h"
 #include "ss_lsap.h"
 #include "ss_expneg.h"
+#include "ss_probiou.h"
 
 #define SS_BYTE_COST_CAP 2048          // LDS-resident cost entries (f64); a larger matrix lives in the stream's global spill area
 
@@ -28,7 +29,7 @@ struct ByteLds {
     float score[SS_MAXT], cls[SS_MAXT];
     int trk[SS_MAXT], lost[SS_MAXT];   // the lists, in order
     int upd[SS_MAXT];                  // per slot: detection to apply this frame (Kalman update) or -1
-    double tl[SS_MAXT][4];             // per slot: tlwh of the current mean (predicted / updated / initiated this frame)
+    double tl[SS_MAXT][4];             // per slot: tlwh of the current mean (predicted / updated / initiated this frame); OBB: cx, cy, w, h
     // the frame's detections
     double dtl[SS_MAXD][4], dz[SS_MAXD][4];
     float dsc[SS_MAXD], dcls[SS_MAXD];
@@ -46,6 +47,19 @@ __device__ inline void byte_tlwh(const double* m, bool xywh, double* t)
 {
     if (xywh) { t[0] = m[0] - m[2] / 2; t[1] = m[1] - m[3] / 2; t[2] = m[2]; t[3] = m[3]; }
     else { const double w = m[2] * m[3]; t[0] = m[0] - w / 2; t[1] = m[1] - m[3] / 2; t[2] = w; t[3] = m[3]; }
+}
+
+// The slot's box from its current mean.  OBB (docs/OBB.md §4): centre and size, the rotated box's own frame, and the ProbIoU terms of
+// the box rounded to float32 (the floats d_out_rbox shows) with the slot's angle th into b.tbox[g]; the terms live in global memory,
+// so the plain variants' LDS is what it was.
+template <bool XYWH, bool OBB>
+__device__ inline void byte_box(const SSByteDev& b, size_t g, const double* m, float th, double* t)
+{
+    if constexpr (OBB) {
+        t[0] = m[0]; t[1] = m[1]; t[2] = XYWH ? m[2] : m[2] * m[3]; t[3] = m[3];
+        *reinterpret_cast<ss_pbox*>(b.tbox + g * 6) = ss_probiou_box((float)t[0], (float)t[1], (float)t[2], (float)t[3], th);
+    }
+    else byte_tlwh(m, XYWH, t);
 }
 
 // step 3b (docs/BYTETRACK.md §1b, G-02): Ultralytics' STrack.multi_gmc with warp w (R = [[w0, w1], [w3, w4]], t = (w2, w5)):
@@ -328,8 +342,10 @@ __device__ inline void byte_pose_store(const SSByteDev& b, size_t sb, size_t fs,
 
 // GMC: BoT-SORT's camera-motion step 3b from b.gmc; REID: §1c's appearance term and smoothed features from b.smooth / b.ufeat
 // POSE: §1e's keypoint term and stored poses from b.tpose / b.kp (all three only instantiated with XYWH, REID and POSE never
-// together; without them the code is the plain tracker's)
-template <bool XYWH, bool GMC, bool REID, bool POSE>
+// together; without them the code is the plain tracker's).  OBB (docs/OBB.md §4, never with the other three): 11-column rows, the
+// cost of every association and of the duplicate test is 1 - ProbIoU of the rotated boxes, the slot carries its last row's angle
+// (R-06), rows carry the rotated box's envelope and b.rbox its xywh theta.
+template <bool XYWH, bool GMC, bool REID, bool POSE, bool OBB = false>
 __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const float* __restrict__ dets, const int* __restrict__ ndets,
                                                     float* __restrict__ out, int* __restrict__ nout)
 {
@@ -338,6 +354,18 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
     const size_t sb = (size_t)s * SS_MAXT;
     double* spill = b.spill + (size_t)s * SS_MAXT * SS_MAXD;
     int* err = b.err + s;
+    [[maybe_unused]] const size_t db = (size_t)s * SS_MAXD;
+    // 1 - IoU of a slot's box and a row's (OBB: 1 - ProbIoU from the two boxes' terms), and of two slots' boxes
+    auto cost_td = [&](int slot, int d) -> double {
+        if constexpr (OBB) return 1.0 - ss_probiou_pair(*reinterpret_cast<const ss_pbox*>(b.tbox + (sb + slot) * 6),
+                                                        *reinterpret_cast<const ss_pbox*>(b.dbox + (db + d) * 6));
+        else return ss_iou_cost(m.tl[slot], m.dtl[d], 2.0);
+    };
+    auto cost_tt = [&](int a, int c) -> double {
+        if constexpr (OBB) return 1.0 - ss_probiou_pair(*reinterpret_cast<const ss_pbox*>(b.tbox + (sb + a) * 6),
+                                                        *reinterpret_cast<const ss_pbox*>(b.tbox + (sb + c) * 6));
+        else return ss_iou_cost(m.tl[a], m.tl[c], 2.0);
+    };
     // ---- the stream's table into LDS ----
     m.state[tid] = b.state[sb + tid]; m.act[tid] = b.act[sb + tid]; m.id[tid] = b.tid[sb + tid]; m.start[tid] = b.start[sb + tid];
     m.end[tid] = b.end[sb + tid]; m.len[tid] = b.len[sb + tid]; m.det[tid] = b.det[sb + tid]; m.score[tid] = b.score[sb + tid];
@@ -355,13 +383,20 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
         // ---- 1. detections and the score split ----
         int isHi = 0, isLo = 0;
         if (tid < N) {
-            const float* d = dets + (fs * SS_MAXD + tid) * 6;
-            const double x1 = d[0], y1 = d[1], x2 = d[2], y2 = d[3];
+            const float* d = dets + (fs * SS_MAXD + tid) * (OBB ? 11 : 6);
             const float sc = d[4];
             double* t = m.dtl[tid];
             double* z = m.dz[tid];
-            t[0] = x1; t[1] = y1; t[2] = x2 - x1; t[3] = y2 - y1;
-            z[0] = t[0] + t[2] / 2; z[1] = t[1] + t[3] / 2;
+            if constexpr (OBB) {                                   // the rotated box's own centre and size; the envelope is not read
+                t[0] = d[6]; t[1] = d[7]; t[2] = d[8]; t[3] = d[9];
+                z[0] = t[0]; z[1] = t[1];
+                *reinterpret_cast<ss_pbox*>(b.dbox + (db + tid) * 6) = ss_probiou_box(d[6], d[7], d[8], d[9], d[10]);
+            }
+            else {
+                const double x1 = d[0], y1 = d[1], x2 = d[2], y2 = d[3];
+                t[0] = x1; t[1] = y1; t[2] = x2 - x1; t[3] = y2 - y1;
+                z[0] = t[0] + t[2] / 2; z[1] = t[1] + t[3] / 2;
+            }
             if (XYWH) { z[2] = t[2]; z[3] = t[3]; } else { z[2] = t[2] / t[3]; z[3] = t[3]; }
             m.dsc[tid] = sc; m.dcls[tid] = d[5];
             isHi = sc >= b.high;
@@ -404,7 +439,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             for (int i = 0; i < 8; ++i) b.mean[g * 8 + i] = mean[i];
 #pragma unroll
             for (int i = 0; i < 64; ++i) b.cov[g * 64 + i] = cov[i];
-            byte_tlwh(mean, XYWH, m.tl[slot]);
+            byte_box<XYWH, OBB>(b, g, mean, OBB ? b.angle[g] : 0.0f, m.tl[slot]);
         }
         if (tid < nU) {
             const int slot = m.unc[tid];
@@ -422,7 +457,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
 #pragma unroll
                 for (int i = 0; i < 64; ++i) b.cov[g * 64 + i] = cov[i];
             }
-            byte_tlwh(mean, XYWH, m.tl[slot]);
+            byte_box<XYWH, OBB>(b, g, mean, OBB ? b.angle[g] : 0.0f, m.tl[slot]);
         }
         __syncthreads();
         // ---- 4. first association: pool x high rows, fused 1 - IoU, match_thresh ----
@@ -434,7 +469,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             else
             for (int e = tid; e < nP * nHi; e += 256) {
                 const int r = e / nHi, k = e - r * nHi, d = m.hi[k];
-                double c = ss_iou_cost(m.tl[m.pool[r]], m.dtl[d], 2.0);
+                double c = cost_td(m.pool[r], d);
                 if (b.fuse) c = 1.0 - (1.0 - c) * (double)m.dsc[d];
                 cost[lsap_cidx(r, k, nP, nHi)] = c;
             }
@@ -462,7 +497,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             double* cost = glb ? spill : m.cost;
             for (int e = tid; e < nR2 * nLo; e += 256) {
                 const int r = e / nLo, k = e - r * nLo;
-                cost[lsap_cidx(r, k, nR2, nLo)] = ss_iou_cost(m.tl[m.r2[r]], m.dtl[m.lo[k]], 2.0);
+                cost[lsap_cidx(r, k, nR2, nLo)] = cost_td(m.r2[r], m.lo[k]);
             }
             byte_assign(nR2, nLo, cost, glb, m, err);
             if (tid < nR2) {
@@ -486,7 +521,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             else
             for (int e = tid; e < nU * nLeft; e += 256) {
                 const int r = e / nLeft, k = e - r * nLeft, d = m.left[k];
-                double c = ss_iou_cost(m.tl[m.unc[r]], m.dtl[d], 2.0);
+                double c = cost_td(m.unc[r], d);
                 if (b.fuse) c = 1.0 - (1.0 - c) * (double)m.dsc[d];
                 cost[lsap_cidx(r, k, nU, nLeft)] = c;
             }
@@ -525,7 +560,9 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
 #pragma unroll
                 for (int i = 0; i < 8; ++i) b.mean[g * 8 + i] = mean[i];
                 for (int i = 0; i < 64; ++i) b.cov[g * 64 + i] = cov[i];
-                byte_tlwh(mean, XYWH, m.tl[slot]);
+                float th = 0.0f;
+                if constexpr (OBB) { th = dets[(fs * SS_MAXD + d) * 11 + 10]; b.angle[g] = th; }       // R-06
+                byte_box<XYWH, OBB>(b, g, mean, th, m.tl[slot]);
                 m.id[slot] = m.next_id + rank;
                 m.len[slot] = 0; m.state[slot] = SS_BYTE_TRACKED; m.act[slot] = fid == 1;
                 m.start[slot] = fid; m.end[slot] = fid;
@@ -548,7 +585,9 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
                 for (int i = 0; i < 8; ++i) b.mean[g * 8 + i] = mean[i];
 #pragma unroll
                 for (int i = 0; i < 64; ++i) b.cov[g * 64 + i] = cov[i];
-                byte_tlwh(mean, XYWH, m.tl[tid]);
+                float th = 0.0f;
+                if constexpr (OBB) { th = dets[(fs * SS_MAXD + d) * 11 + 10]; b.angle[g] = th; }       // R-06
+                byte_box<XYWH, OBB>(b, g, mean, th, m.tl[tid]);
                 m.state[tid] = SS_BYTE_TRACKED; m.act[tid] = 1; m.end[tid] = fid;
                 m.score[tid] = m.dsc[d]; m.cls[tid] = m.dcls[d]; m.det[tid] = d;
             }
@@ -588,7 +627,7 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
         // ---- duplicates between the lists: 1 - IoU < 0.15, the shorter-lived track goes (the tracked one on a tie) ----
         for (int e = tid; e < nT2 * nL2; e += 256) {
             const int p = e / nL2, q = e - p * nL2, a = m.trk[p], c = m.lost[q];
-            if (ss_iou_cost(m.tl[a], m.tl[c], 2.0) < 0.15) {
+            if (cost_tt(a, c) < 0.15) {
                 if (m.end[a] - m.start[a] > m.end[c] - m.start[c]) m.dupb[q] = 1;
                 else m.dupa[p] = 1;
             }
@@ -617,7 +656,15 @@ __global__ __launch_bounds__(256) void k_byte_group(SSByteDev b, int F, const fl
             if (emit) {
                 const double* t = m.tl[slot];
                 float* o = out + (fs * SS_MAXT + row) * 8;
-                o[0] = (float)t[0]; o[1] = (float)t[1]; o[2] = (float)(t[0] + t[2]); o[3] = (float)(t[1] + t[3]);
+                if constexpr (OBB) {
+                    float* q = b.rbox + (fs * SS_MAXT + row) * 5;
+                    const float cx = (float)t[0], cy = (float)t[1], bw = (float)t[2], bh = (float)t[3], th = b.angle[sb + slot];
+                    double e[4];
+                    ss_rbox_envelope(cx, cy, bw, bh, th, e);
+                    o[0] = (float)e[0]; o[1] = (float)e[1]; o[2] = (float)e[2]; o[3] = (float)e[3];
+                    q[0] = cx; q[1] = cy; q[2] = bw; q[3] = bh; q[4] = th;
+                }
+                else { o[0] = (float)t[0]; o[1] = (float)t[1]; o[2] = (float)(t[0] + t[2]); o[3] = (float)(t[1] + t[3]); }
                 o[4] = (float)m.id[slot]; o[5] = m.cls[slot]; o[6] = m.score[slot]; o[7] = (float)m.det[slot];
             }
             if (tid == 0) {
@@ -657,4 +704,13 @@ void ss_launch_byte_group_kpts(const SSByteDev& b, int F, const float* dets, con
     hipLaunchKernelGGL(k_byte_kpts, dim3(SS_MAXD / 8, b.S, F), dim3(256), 0, st, b, kpts, stride, off, geom, ndets);
     if (b.gmc) hipLaunchKernelGGL((k_byte_group<true, true, false, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
     else hipLaunchKernelGGL((k_byte_group<true, false, false, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+}
+
+// docs/OBB.md §4: the group on 11-column rows (b.obb: ss_byte_set_obb); rbox [F][S][MAXT][5] goes with the launch arguments
+void ss_launch_byte_group_obb(const SSByteDev& b0, int F, const float* dets, const int* ndets, float* out, float* rbox, int* nout, hipStream_t st)
+{
+    SSByteDev b = b0;
+    b.rbox = rbox;
+    if (b.xywh) hipLaunchKernelGGL((k_byte_group<true, false, false, false, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
+    else hipLaunchKernelGGL((k_byte_group<false, false, false, false, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
 }

@@ -363,6 +363,12 @@ struct SSByteDev {
     double prox, appear;                // proximity_thresh (on 1 - IoU), appearance_thresh (on the halved cosine distance)
     float* smooth;                      // [S][MAXT][F] unit track features by slot
     float* ufeat;                       // [FMAX][S][MAXD][F] unit detection features of the group (k_byte_feats)
+    // oriented boxes (docs/OBB.md §4, ss_byte_set_obb; not with GMC, ReID or the keypoint term), allocated when first switched on
+    int obb;
+    float* angle;                       // [S][MAXT] by slot: the angle of the track's last detection (R-06)
+    double* tbox;                       // [S][MAXT][6] by slot: ProbIoU terms (x, y, A, B, C, D) of the track's current box
+    double* dbox;                       // [S][MAXD][6] the same of the frame's detection rows
+    float* rbox;                        // [F][S][MAXT][5] the call's d_out_rbox (set by the launcher on its copy of this struct)
 };
 
 // Device state of the OC-SORT tracker (csrc/ss_ocsort.hip, docs/OCSORT.md), hung off a context by ss_ocsort_create.  Per stream: one

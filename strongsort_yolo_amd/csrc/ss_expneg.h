@@ -1,12 +1,19 @@
-// ss_expneg.h — exp(-x) as one fixed sequence of f64 operations, shared by the BoT-SORT keypoint term (ss_byte.hip, docs/BYTETRACK.md §1e)
-// and the GSI kernel (ss_gsi.hip, docs/GSI.md §2): both CPU restatements run the same sequence with the same constants.
+// ss_expneg.h — exp(-x) as one fixed sequence of f64 operations, shared by the BoT-SORT keypoint term (ss_byte.hip, docs/BYTETRACK.md §1e),
+// the GSI kernel (ss_gsi.hip, docs/GSI.md §2) and ProbIoU (ss_probiou.h, docs/OBB.md §1): the CPU restatements run the same sequence with
+// the same constants.  A host compiler can include this header on its own.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define SS_EXPNEG_FN __host__ __device__ inline
+#else
+#include <math.h>
+#define SS_EXPNEG_FN inline
+#endif
 
 // §1e: exp(-x), x >= 0, as ONE fixed sequence of f64 operations (tests/botsort_pose_ref.ss_expneg runs the same one with the same
 // constants; the file is built with -ffp-contract=off): k = floor(-x log2(e) + 1/2), r = (-x - k LN2_HI) - k LN2_LO with
 // |r| <= ln2 / 2, the degree-12 Taylor polynomial by Horner, ldexp.  Above the cut-off (and for a NaN) the result is 0.
-__device__ inline double ss_expneg(double x)
+SS_EXPNEG_FN double ss_expneg(double x)
 {
     if (!(x <= 700.0)) return 0.0;
     const double y = -x;

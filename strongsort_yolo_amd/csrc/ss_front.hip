@@ -5,6 +5,7 @@
 #include "ss_common.h"
 #include "ss_launch.h"
 #include "ss_bilerp.h"       // ss_axis / ss_bilerp_u8 / ss_cvt (oracle so_axis / so_bilerp_u8), shared with ss_slice.hip
+#include "ss_probiou.h"      // ProbIoU of oriented boxes as one fixed f64 sequence (docs/OBB.md §1)
 
 // uint8_t output of the crop kernel: the rounded bilinear value itself (0..255), BEFORE the normalisation — the 256 x 3 possible outputs of
 // ((q / 255) - mean) / sd are applied by the consumer (k32_stemW's staging) from the same expression, so the crops travel as a quarter of the bytes
@@ -816,11 +817,169 @@ __global__ __launch_bounds__(1024) void k_nms_rest(NmsBatch nb, int N, int nc, i
 
 #define NMS_REST_LDS (NMS_MAX_CAND * 8 + 16 * 64 * 4 * 4 + 16 * 64 * 4 + 1024 * 4)
 
+// =================================================================================================
+// Rotated NMS on ProbIoU (docs/OBB.md §3): k_nms_filter, then ONE workgroup per image for the rest
+// =================================================================================================
+// The prediction tensor is [4 + nc + 1][N]: xywh, class scores, theta.  Phase A = k_nms_rest's sort, then the per-box ProbIoU terms
+// (x, y, A, B, C, D) and the class of every sorted candidate, once, into the workspace unit (the bit matrix's bytes: this rule has no
+// matrix).  Phase B walks the upper-triangle 64x64 block pairs, one WAVE per pair: the wave holds the 64 rows' terms in its LDS tile, a
+// lane holds one column j and ORs "some i < j has probiou(i, j) >= thr (and the same class)" into its removed bit (R-02: whether i is
+// itself removed does not matter, so there is no sequential pass).  Phase C keeps the first max_det unremoved candidates in order,
+// phase D writes the rows [x1, y1, x2, y2, conf, cls, cx, cy, w, h, theta]: float32 steps, the envelope from float64 corners.
+struct NmsObbWs { double* terms; int* cls; };
+__device__ inline NmsObbWs nms_obb_unit(const NmsWs& w) { return NmsObbWs{ (double*)w.mask, (int*)w.area }; }
+static_assert((size_t)NMS_MAX_CAND * 6 * 8 <= (size_t)NMS_MAX_CAND * NMS_WORDS * 8, "the ProbIoU terms fit the bit matrix's bytes");
+
+#define NMS_OBB_LDS (NMS_MAX_CAND * 8 + 16 * 64 * 6 * 8 + 16 * 64 * 4 + NMS_WORDS * 8 + 1024 * 4)
+
+__global__ __launch_bounds__(1024) void k_nms_obb_rest(NmsBatch nb, int N, int nc, int agnostic, float iou_thres, int max_det,
+                                                       const float* __restrict__ geom, float* __restrict__ rows, int row_stride,
+                                                       long long rows_batch_stride, int* __restrict__ keep, long long keep_batch_stride,
+                                                       int* __restrict__ count)
+{
+    const int img = blockIdx.x;
+    const float* __restrict__ pred = nb.pred + (size_t)img * nb.pred_stride;
+    const NmsWs w = nms_unit(nb, img);
+    const NmsObbWs ow = nms_obb_unit(w);
+    rows += (size_t)img * rows_batch_stride; keep += (size_t)img * keep_batch_stride; count += img;
+    const float gain = geom[img * 5], pad_x = geom[img * 5 + 1], pad_y = geom[img * 5 + 2], w0 = geom[img * 5 + 3], h0 = geom[img * 5 + 4];
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned long long* k = (unsigned long long*)smem;                                     // [NMS_MAX_CAND] sort keys
+    double* stw = (double*)(smem + (size_t)NMS_MAX_CAND * 8);                               // [16 waves][64][6] terms of a row block
+    int* scw = (int*)(stw + 16 * 64 * 6);                                                  // [16][64] classes of a row block
+    unsigned long long* rem = (unsigned long long*)(scw + 16 * 64);                        // [NMS_WORDS] removed bits
+    int* kept_sorted = (int*)(rem + NMS_WORDS);                                            // [1024]
+    __shared__ int s_kept;
+    const int tid = threadIdx.x, l = tid & 63, wv = tid >> 6;
+    // ---- phase A: sort, per-box terms ----
+    int n = w.counters[0];
+    __syncthreads();
+    if (n > NMS_MAX_CAND) {
+        if (tid == 0) { w.counters[1] = SS_ERR_CAPACITY; w.counters[0] = 0; }
+        n = 0;
+    }
+    int np = 1; while (np < n) np <<= 1;
+    for (int i = tid; i < np; i += 1024) k[i] = i < n ? w.keys[i] : ~0ull;
+    if (tid < NMS_WORDS) rem[tid] = 0ull;
+    __syncthreads();
+    for (int size = 2; size <= np; size <<= 1)
+        for (int strd = size >> 1; strd > 0; strd >>= 1) {
+            for (int i = tid; i < np / 2; i += 1024) {
+                int lo = 2 * i - (i & (strd - 1)), hi = lo + strd;
+                bool up = (lo & size) == 0;
+                unsigned long long a = k[lo], b = k[hi];
+                if ((a > b) == up) { k[lo] = b; k[hi] = a; }
+            }
+            __syncthreads();
+        }
+    for (int i = tid; i < n; i += 1024) {
+        const int a = (int)(k[i] & 0xffffffffu);
+        const ss_pbox p = ss_probiou_box(pred[a], pred[(size_t)N + a], pred[(size_t)2 * N + a], pred[(size_t)3 * N + a],
+                                         pred[(size_t)(4 + nc) * N + a]);
+        double* t = ow.terms + (size_t)i * 6;
+        t[0] = p.x; t[1] = p.y; t[2] = p.A; t[3] = p.B; t[4] = p.C; t[5] = p.D;
+        ow.cls[i] = w.cand_cls[a];
+    }
+    __threadfence_block();
+    __syncthreads();
+    // ---- phase B: removed bits, one wave per (ib <= jb) block pair ----
+    {
+        double* st = stw + wv * 64 * 6;
+        int* sc = scw + wv * 64;
+        const double thr = (double)iou_thres;
+        const int nblk = (n + 63) / 64, npair = nblk * (nblk + 1) / 2;
+        for (int pr = wv; pr < npair; pr += 16) {
+            int ib = 0, r = pr;
+            while (r >= nblk - ib) { r -= nblk - ib; ++ib; }
+            const int jb = ib + r;
+            const int i = ib * 64 + l, j = jb * 64 + l;
+            SS_WAVE_SYNC();                                          // the previous pair's reads of the tile are done
+            if (i < n) {
+#pragma unroll
+                for (int e = 0; e < 6; ++e) st[l * 6 + e] = ow.terms[(size_t)i * 6 + e];
+                sc[l] = ow.cls[i];
+            }
+            SS_WAVE_SYNC();
+            bool hit = false;
+            if (j < n) {
+                ss_pbox q;
+                q.x = ow.terms[(size_t)j * 6]; q.y = ow.terms[(size_t)j * 6 + 1]; q.A = ow.terms[(size_t)j * 6 + 2];
+                q.B = ow.terms[(size_t)j * 6 + 3]; q.C = ow.terms[(size_t)j * 6 + 4]; q.D = ow.terms[(size_t)j * 6 + 5];
+                const int cj = ow.cls[j];
+                const int in = min(64, ib == jb ? l : n - ib * 64);          // rows i < j of this block
+                for (int u = 0; u < in; ++u) {
+                    if (!agnostic && sc[u] != cj) continue;                    // R-03
+                    ss_pbox p;
+                    p.x = st[u * 6]; p.y = st[u * 6 + 1]; p.A = st[u * 6 + 2]; p.B = st[u * 6 + 3]; p.C = st[u * 6 + 4]; p.D = st[u * 6 + 5];
+                    if (ss_probiou_pair(p, q) >= thr) hit = true;
+                }
+            }
+            const unsigned long long word = __ballot(hit);
+            if (l == 0 && word) atomicOr(&rem[jb], word);
+        }
+    }
+    __syncthreads();
+    // ---- phase C: the first max_det unremoved candidates, in order, on wave 0 ----
+    if (wv == 0) {
+        const int nw = (n + 63) / 64, cap = min(max_det, 1024);
+        int kept = 0;
+        for (int ib = 0; ib < nw && kept < cap; ++ib) {
+            const int cnt = min(64, n - ib * 64);
+            const unsigned long long live = ~rem[ib] & (cnt == 64 ? ~0ull : (1ull << cnt) - 1ull);
+            const int rank = kept + __popcll(live & ((1ull << l) - 1ull));
+            if (((live >> l) & 1ull) && rank < cap) kept_sorted[rank] = ib * 64 + l;
+            kept = min(cap, kept + __popcll(live));
+        }
+        if (l == 0) { s_kept = kept; *count = kept; w.counters[0] = 0; }     // re-arm the candidate counter for the next call
+    }
+    __syncthreads();
+    // ---- phase D: rows ----
+    const int kept = s_kept;
+    for (int kk = tid; kk < kept; kk += 1024) {
+        const int i = kept_sorted[kk];
+        const unsigned long long key = k[i];
+        const int a = (int)(key & 0xffffffffu);
+        float cx = pred[a], cy = pred[(size_t)N + a], bw = pred[(size_t)2 * N + a], bh = pred[(size_t)3 * N + a];
+        float th = pred[(size_t)(4 + nc) * N + a];
+        cx = (cx - pad_x) / gain; cy = (cy - pad_y) / gain;                   // no clipping (R-04)
+        bw = bw / gain; bh = bh / gain;
+        if (!(bw > bh)) { const float t = bw; bw = bh; bh = t; th = th + 1.57079637050628662f; }       // R-05
+        if (th < 0.0f) th = th + 3.14159274101257324f;
+        else if (th >= 3.14159274101257324f) th = th - 3.14159274101257324f;
+        double e[4];
+        ss_rbox_envelope(cx, cy, bw, bh, th, e);
+        float* r = rows + (size_t)kk * row_stride;
+        r[0] = fminf(fmaxf((float)e[0], 0.0f), w0); r[1] = fminf(fmaxf((float)e[1], 0.0f), h0);
+        r[2] = fminf(fmaxf((float)e[2], 0.0f), w0); r[3] = fminf(fmaxf((float)e[3], 0.0f), h0);
+        r[4] = __uint_as_float(~(unsigned)(key >> 32)); r[5] = (float)w.cand_cls[a];
+        r[6] = cx; r[7] = cy; r[8] = bw; r[9] = bh; r[10] = th;
+        keep[kk] = a;
+    }
+}
+
+// test entry: the ProbIoU matrix of two box lists, the device function on every pair
+__global__ __launch_bounds__(256) void k_probiou_matrix(const float* __restrict__ a, int n, const float* __restrict__ b, int m,
+                                                        double* __restrict__ out)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)n * m) return;
+    const int i = (int)(idx / m), j = (int)(idx % m);
+    out[idx] = ss_probiou_xywhr(a + (size_t)i * 5, b + (size_t)j * 5);
+}
+
+void ss_launch_probiou(const float* a, int n, const float* b, int m, double* out, hipStream_t st)
+{
+    const long long total = (long long)n * m;
+    if (total <= 0) return;
+    hipLaunchKernelGGL(k_probiou_matrix, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, n, b, m, out);
+}
+
 int ss_front_init()
 {
     hipError_t e = hipFuncSetAttribute((const void*)k_nms_sort, hipFuncAttributeMaxDynamicSharedMemorySize, NMS_MAX_CAND * 8);
     hipError_t e2 = hipFuncSetAttribute((const void*)k_nms_rest, hipFuncAttributeMaxDynamicSharedMemorySize, NMS_REST_LDS);
-    return (e == hipSuccess && e2 == hipSuccess) ? 0 : 1;
+    hipError_t e3 = hipFuncSetAttribute((const void*)k_nms_obb_rest, hipFuncAttributeMaxDynamicSharedMemorySize, NMS_OBB_LDS);
+    return (e == hipSuccess && e2 == hipSuccess && e3 == hipSuccess) ? 0 : 1;
 }
 
 // error flags (counters[1]) of the first `units` workspace units, for ss_check_errors
@@ -848,5 +1007,18 @@ int ss_launch_nms(const float* pred, int batch, long long pred_stride, int N, in
         hipLaunchKernelGGL(k_nms_scan, dim3(batch), dim3(64), 0, st, nb, N, nc, n_extra, max_det, gain, pad_x, pad_y, w0, h0,
                            geom, rows, row_stride, rows_batch_stride, keep, keep_batch_stride, count);
     }
+    return 0;
+}
+
+int ss_launch_nms_obb(const float* pred, int batch, long long pred_stride, int N, int nc, float conf, float iou, int agnostic, int max_det,
+                      const float* geom, float* rows, int row_stride, long long rows_batch_stride, int* keep, long long keep_batch_stride,
+                      int* count, void* ws, size_t ws_bytes, unsigned long long cm0, unsigned long long cm1, hipStream_t st)
+{
+    if (batch <= 0) return 0;
+    if (N > NMS_MAX_ANCHORS || ws_bytes < ss_nms_workspace_bytes() * (size_t)batch) return SS_ERR_CAPACITY;
+    NmsBatch nb{ pred, pred_stride, (char*)ws, (long long)ss_nms_workspace_bytes() };
+    hipLaunchKernelGGL(k_nms_filter, dim3((N + 63) / 64, batch), dim3(512), 0, st, nb, N, nc, conf, cm0, cm1);
+    hipLaunchKernelGGL(k_nms_obb_rest, dim3(batch), dim3(1024), NMS_OBB_LDS, st, nb, N, nc, agnostic, iou, max_det, geom, rows, row_stride,
+                       rows_batch_stride, keep, keep_batch_stride, count);
     return 0;
 }

@@ -34,6 +34,10 @@ int  ss_launch_nms(const float* pred, int batch, long long pred_stride, int N, i
                    float max_wh, int max_det, float gain, float pad_x, float pad_y, float w0, float h0, const float* geom, float* rows,
                    int row_stride, long long rows_batch_stride, int* keep, long long keep_batch_stride, int* count, void* ws, size_t ws_bytes,
                    unsigned long long cm0, unsigned long long cm1, hipStream_t st);
+int  ss_launch_nms_obb(const float* pred, int batch, long long pred_stride, int N, int nc, float conf, float iou, int agnostic, int max_det,
+                       const float* geom, float* rows, int row_stride, long long rows_batch_stride, int* keep, long long keep_batch_stride,
+                       int* count, void* ws, size_t ws_bytes, unsigned long long cm0, unsigned long long cm1, hipStream_t st);
+void ss_launch_probiou(const float* a, int n, const float* b, int m, double* out, hipStream_t st);
 void ss_launch_crop(const uint8_t* frame, int batch, long long frame_batch_stride, int h, int w, int stride, const float* dets, int det_stride,
                     long long dets_batch_stride, int n, const int* d_count, void* out, int flags, hipStream_t st, const int* d_off);
 void ss_launch_crop_offsets(const int* counts, int batch, int n, int* off, hipStream_t st);
@@ -61,6 +65,7 @@ void ss_launch_byte_group(const SSByteDev& b, int F, const float* dets, const in
                           hipStream_t st);
 void ss_launch_byte_group_kpts(const SSByteDev& b, int F, const float* dets, const int* ndets, const float* kpts, long long stride, int off,
                                const float* geom, float* out, int* nout, hipStream_t st);
+void ss_launch_byte_group_obb(const SSByteDev& b, int F, const float* dets, const int* ndets, float* out, float* rbox, int* nout, hipStream_t st);
 void ss_launch_ocsort_group(const SSOcDev& o, int F, const float* dets, const int* ndets, float* out, int* nout, hipStream_t st);
 void ss_launch_deepoc_group(const SSDeepOcDev& x, int F, const float* dets, const int* ndets, const float* feats, float* out, int* nout,
                             hipStream_t st);

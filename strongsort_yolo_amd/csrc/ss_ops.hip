@@ -203,6 +203,16 @@ __global__ __launch_bounds__(128) void k_v8_decode(V8Levels L, int B, int nc, in
     const float ax = (float)px + 0.5f, ay = (float)py + 0.5f, st = (float)L.stride[l];
     const float x1 = ax - d[0], y1 = ay - d[1], x2 = ax + d[2], y2 = ay + d[3];
     float* o = pred + (size_t)b * (4 + nc + L.n_ext) * A + a;
+    if (L.n_ext && L.ext_mode == 2) {
+        // oriented box (docs/OBB.md §2): theta = (sigmoid(v) - 1/4) pi, dist2rbox: the centre's offset from the anchor turned by theta
+        const float v = __half2float(L.ext[l][((size_t)b * hw + p) * L.ext_ld]);
+        const float th = (1.0f / (1.0f + __expf(-v)) - 0.25f) * 3.14159274101257324f;
+        const float cs = cosf(th), sn = sinf(th);
+        const float xf = (d[2] - d[0]) * 0.5f, yf = (d[3] - d[1]) * 0.5f;
+        o[0] = (ax + (xf * cs - yf * sn)) * st; o[(size_t)A] = (ay + (xf * sn + yf * cs)) * st;
+        o[(size_t)2 * A] = (d[0] + d[2]) * st; o[(size_t)3 * A] = (d[1] + d[3]) * st;
+        o[(size_t)(4 + nc) * A] = th;
+    } else {
     o[0] = (x1 + x2) * 0.5f * st; o[(size_t)A] = (y1 + y2) * 0.5f * st;
     o[(size_t)2 * A] = (x2 - x1) * st; o[(size_t)3 * A] = (y2 - y1) * st;
     if (L.n_ext) {
@@ -212,6 +222,7 @@ __global__ __launch_bounds__(128) void k_v8_decode(V8Levels L, int B, int nc, in
             const float v = __half2float(e[k]);
             oe[(size_t)k * A] = L.ext_mode == 0 ? v : j == 0 ? (v * 2.0f + (float)px) * st : j == 1 ? (v * 2.0f + (float)py) * st : 1.0f / (1.0f + __expf(-v));
         }
+    }
     }
     const __half* cl = L.cls[l] + ((size_t)b * hw + p) * L.cls_ld;
     const __half* cb = L.cls_bias[l];
@@ -2561,7 +2572,7 @@ extern "C" int ss_op_v8_decode_ext_f16(void* stream, const void* const* box, con
                                        const int* H, const int* W, const int* strides, int B, int nc, int cls_ld, float* pred)
 {
     if (!box || !cls || !box_bias || !cls_bias || !H || !W || !strides || !pred || B < 1 || B > 65535 || nc < 1 || cls_ld < nc) return SS_ERR_INVALID;
-    if (n_ext < 0 || (n_ext && (!ext || ext_ld < n_ext || (ext_mode != 0 && ext_mode != 1) || (ext_mode == 1 && n_ext % 3)))) return SS_ERR_INVALID;
+    if (n_ext < 0 || (n_ext && (!ext || ext_ld < n_ext || ext_mode < 0 || ext_mode > 2 || (ext_mode == 1 && n_ext % 3) || (ext_mode == 2 && n_ext != 1)))) return SS_ERR_INVALID;
     V8Levels L;
     int A = 0;
     L.n_ext = n_ext; L.ext_ld = ext_ld; L.ext_mode = ext_mode; L.cls_ld = cls_ld;

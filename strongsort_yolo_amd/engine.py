@@ -666,6 +666,29 @@ class TrackerEngine:
                                      rows.stride(0), _ptr(keep), keep.stride(0), _ptr(count)))
         return rows, keep, count
 
+    def nms_obb_batch(self, pred: torch.Tensor, nc: int, dcfg: DetectConfig, geom: torch.Tensor, rows=None, keep=None, count=None,
+                      max_det: int | None = None):
+        """Rotated NMS on ProbIoU (docs/OBB.md).  pred: [B,(4+nc+1),N] float32 (xywh, class scores, theta); geom as nms_batch's.
+        rows [B,max_det,11]: the envelope, conf, cls, then cx, cy, w, h, theta in original-image pixels."""
+        B, N = pred.shape[0], pred.shape[2]
+        md = min(dcfg.max_det, 1024) if max_det is None else max_det
+        if rows is None:
+            rows = torch.zeros(B, md, 11, dtype=torch.float32, device=self.device)
+            keep = torch.zeros(B, md, dtype=torch.int32, device=self.device)
+            count = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self._ck(self.L.ss_nms_obb_batch(self.ctx, _ptr(pred), B, pred.stride(0), N, nc, dcfg.conf, dcfg.iou, int(dcfg.agnostic_nms), md,
+                                         _ptr(geom), _ptr(rows), rows.stride(1), rows.stride(0), _ptr(keep), keep.stride(0), _ptr(count)))
+        return rows, keep, count
+
+    def probiou(self, a, b) -> np.ndarray:
+        """float32 [n,5] x [m,5] host lists (cx, cy, w, h, theta) -> float64 [n,m], the device function on every pair (synchronous)."""
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 5)
+        b = np.ascontiguousarray(b, np.float32).reshape(-1, 5)
+        out = np.zeros((a.shape[0], b.shape[0]), np.float64)
+        fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+        self._ck(self.L.ss_probiou(self.ctx, a.ctypes.data_as(fp), a.shape[0], b.ctypes.data_as(fp), b.shape[0], out.ctypes.data_as(dp)))
+        return out
+
     def nms_set_classes(self, classes=None):
         """Keep only these class ids in the following NMS calls (None / empty: all) — overrides['classes']."""
         cl = [] if classes is None else ([int(classes)] if np.isscalar(classes) else [int(c) for c in classes])
@@ -842,8 +865,11 @@ class ByteTrackEngine:
     ReID branch, switched on at construction), keypoints only with cfg.with_pose (§1e, the OKS term, likewise).  `engine`: share the
     context of an existing TrackerEngine (a pipeline's: its NMS, streams and error words); None: a context of its own."""
 
-    def __init__(self, cfg: ByteTrackConfig | None = None, n_streams: int = 1, device: int = 0, engine: TrackerEngine | None = None):
+    def __init__(self, cfg: ByteTrackConfig | None = None, n_streams: int = 1, device: int = 0, engine: TrackerEngine | None = None,
+                 obb: bool = False):
         self.cfg = cfg or ByteTrackConfig()
+        if obb and (self.cfg.with_reid or self.cfg.with_pose):
+            raise ValueError("ByteTrackEngine: oriented boxes (obb=True) are not combined with with_reid or with_pose (docs/OBB.md §4)")
         self._own = engine is None
         self.base = TrackerEngine(StrongSortConfig(), n_streams, device) if engine is None else engine
         self.S, self.device, self.L = self.base.S, self.base.device, self.base.L
@@ -859,6 +885,9 @@ class ByteTrackEngine:
             sg = (C.c_double * self.K)(*[float(v) for v in self.cfg.kpt_sigmas])
             self._ck(self.L.ss_byte_set_pose(self.base.ctx, 1, self.K, sg, float(self.cfg.proximity_thresh), float(self.cfg.pose_thresh),
                                              float(self.cfg.kpt_vis_thresh), int(self.cfg.min_common_kpts)))
+        self.obb = False
+        if obb:                                     # docs/OBB.md §4: association on ProbIoU, 11-column rows (resets the streams)
+            self.set_obb(True)
         self._cmc_keep = None
         self.out = torch.zeros(self.S, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=self.device)
         self.nout = torch.zeros(self.S, dtype=torch.int32, device=self.device)
@@ -885,6 +914,21 @@ class ByteTrackEngine:
     def reset(self, stream: int = -1):
         """Restart the stream(s): ids from 1, and the next cmc_estimate frame gets no warp (G-04)."""
         self._ck(self.L.ss_byte_reset(self.base.ctx, stream))
+
+    def set_obb(self, on: bool):
+        """docs/OBB.md §4: association on ProbIoU of rotated boxes on or off; every stream restarts.  While on, update_group takes
+        ss_nms_obb_batch's 11-column rows and fills `rbox`."""
+        self._ck(self.L.ss_byte_set_obb(self.base.ctx, int(bool(on))))
+        self.obb = bool(on)
+        if self.obb and getattr(self, "rbox", None) is None:
+            self.rbox = torch.zeros(self.S, MAX_TRACKS, 5, dtype=torch.float32, device=self.device)
+
+    def angles(self, stream: int = 0) -> np.ndarray:
+        """docs/OBB.md §4: the tracks' angles [n] f32 of one stream in tracks()' list order (R-06: the last row's, not filtered)."""
+        an = np.zeros(MAX_TRACKS, np.float32)
+        self._ck(self.L.ss_byte_get_angles(self.base.ctx, stream, MAX_TRACKS, an.ctypes.data_as(C.POINTER(C.c_float))))
+        t = self.tracks(stream)
+        return an[:t["n_tracked"] + t["n_lost"]].copy()
 
     def set_cmc(self, warps):
         """BoT-SORT GMC (docs/BYTETRACK.md §1b): the following update calls move every track by these warps ([F,S,8] float64,
@@ -928,13 +972,22 @@ class ByteTrackEngine:
         nout = self.nout if nout is None else nout
         return self.update_group(1, dets, ndets, feats, img_hw, out, nout, kpts=kpts, kpt_col=kpt_col, geom=geom)
 
-    def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout, kpts=None, kpt_col=0, geom=None):
+    def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout, kpts=None, kpt_col=0, geom=None, rbox=None):
         """A group of n_frames (<= 32) frames of all streams in ONE launch: dets [F,S,128,6] f32, ndets [F,S] i32, with ReID
         feats [F,S,128,512] f32 -> rows out [F,S,256,8], counts nout [F,S] (device tensors, asynchronous); frames are
         associated in order.  img_hw unused (TrackerEngine's call shape), feats unused without ReID.  With the keypoint term (§1e):
         kpts [F,S,128,K,3] f32 triplets (x, y, v) in the dets' pixels — or the NMS rows themselves [F*S,128,C] with the triplets
-        from column kpt_col in network-input pixels and geom [F*S,5] (the NMS geometry rows) to bring them to the dets' pixels."""
-        if self.pose:
+        from column kpt_col in network-input pixels and geom [F*S,5] (the NMS geometry rows) to bring them to the dets' pixels.
+        With oriented boxes (set_obb): dets [F,S,128,11] f32 (ss_nms_obb_batch's rows), rows' columns 0..3 the envelope of the track's
+        rotated box, and rbox [F,S,256,5] f32 its cx, cy, w, h, theta (None: self.rbox, one frame's)."""
+        if self.obb:
+            rbox = self.rbox if rbox is None else rbox
+            if dets.dtype != torch.float32 or not dets.is_contiguous() or dets.numel() != int(n_frames) * self.S * MAX_DETS * 11:
+                raise ValueError(f"ByteTrackEngine: with oriented boxes dets must be contiguous float32 [{int(n_frames) * self.S} x {MAX_DETS} x 11]")
+            if rbox.dtype != torch.float32 or not rbox.is_contiguous() or rbox.numel() < int(n_frames) * self.S * MAX_TRACKS * 5:
+                raise ValueError(f"ByteTrackEngine: rbox must be contiguous float32 [{int(n_frames) * self.S} x {MAX_TRACKS} x 5]")
+            self._ck(self.L.ss_byte_update_group_obb(self.base.ctx, int(n_frames), _ptr(dets), _ptr(ndets), _ptr(out), _ptr(rbox), _ptr(nout)))
+        elif self.pose:
             k, stride, col, g = self._kpts(kpts, int(n_frames) * self.S, kpt_col, geom)
             self._ck(self.L.ss_byte_update_group_kpts(self.base.ctx, int(n_frames), _ptr(dets), _ptr(ndets), _ptr(k), stride, col,
                                                       _ptr(g), _ptr(out), _ptr(nout)))

@@ -96,9 +96,9 @@ def rows_of(results, frame_id: int) -> np.ndarray:
     """The tracked boxes of one frame's Results as rows [n, 8], corners as the floats the tracker gave (not truncated)."""
     out = []
     for r in results:
-        if r is None or r.boxes is None or r.boxes.id is None or len(r.boxes) == 0:
+        b = None if r is None else r.boxes if r.boxes is not None else getattr(r, "obb", None)    # an oriented-box result: its envelopes (docs/OBB.md §3)
+        if b is None or b.id is None or len(b) == 0:
             continue
-        b = r.boxes
         f = [np.asarray(v.cpu() if hasattr(v, "cpu") else v, np.float64).reshape(len(b), -1) for v in (b.id, b.xyxy, b.conf, b.cls)]
         out.append(np.concatenate([np.full((len(b), 1), float(frame_id)), f[0], f[1], f[2], f[3]], 1))
     return np.concatenate(out, 0) if out else np.zeros((0, 8))

@@ -250,17 +250,19 @@ class Detect(nn.Module):
     segmentation head, Ultralytics `Segment`: /root/reference/yolo_multi_model.py:14 names 'yolov8n-seg.pt') the rows end in
     the nm raw mask coefficients and forward returns (rows, prototypes [B, nm, H/4, W/4])."""
 
-    def __init__(self, nc, ch, nk=0, nm=0, npr=256):
+    def __init__(self, nc, ch, nk=0, nm=0, npr=256, ne=0):
         super().__init__()
-        if nk and nm:
-            raise ValueError("a head carries keypoints or mask coefficients, not both")
-        self.nc, self.nk, self.nm, self.reg_max = nc, nk, nm, 16
+        if bool(nk) + bool(nm) + bool(ne) > 1:
+            raise ValueError("a head carries keypoints, mask coefficients or an angle, not two of them")
+        if ne not in (0, 1):
+            raise ValueError("an oriented-box head carries one angle (ne = 1)")
+        self.nc, self.nk, self.nm, self.ne, self.reg_max = nc, nk, nm, ne, 16
         c2, c3 = max(16, ch[0] // 4, 64), max(ch[0], min(nc, 100))
         self.cv2 = nn.ModuleList(nn.Sequential(Conv(x, c2, 3), Conv(c2, c2, 3), nn.Conv2d(c2, 64, 1)) for x in ch)
         self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, nc, 1)) for x in ch)
-        if nk or nm:
-            c4 = max(ch[0] // 4, nk or nm)
-            self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, nk or nm, 1)) for x in ch)
+        if nk or nm or ne:
+            c4 = max(ch[0] // 4, nk or nm or ne)
+            self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, nk or nm or ne, 1)) for x in ch)
         if nm:
             self.proto = Proto(ch[0], npr, nm)
         self.strides = (8, 16, 32)
@@ -300,9 +302,13 @@ class Detect(nn.Module):
 
     def _decode(self, feats, box, cls, bb, cb, ext=None):
         """box / cls / ext: the branches' last-layer outputs per level -> the prediction tensor (+ prototypes for a mask head)."""
-        n_ext = (self.nk or self.nm) if ext is not None else 0
-        pred = fused.v8_decode(box, cls, bb, cb, self.strides, self.nc, ext, n_ext, 1 if self.nk else 0)
+        n_ext = (self.nk or self.nm or self.ne) if ext is not None else 0
+        pred = fused.v8_decode(box, cls, bb, cb, self.strides, self.nc, ext, n_ext, self._ext_mode())
         return (pred, self.proto(feats[0])) if self.nm else pred
+
+    def _ext_mode(self) -> int:
+        """the decode's treatment of the third branch: 1 keypoint triplets, 2 the oriented box's angle (docs/OBB.md §2), 0 raw"""
+        return 1 if self.nk else 2 if self.ne else 0
 
     def _pads(self, ext_head):
         return [fused.padded_branch(s, s) for s in self.cv4] if ext_head else []
@@ -331,7 +337,7 @@ class Detect(nn.Module):
         return fused.pointwise(seq[1](seq[0](f)), *self._last_wb(seq[2]))
 
     def forward(self, feats):
-        ext_head = bool(self.nk or self.nm)
+        ext_head = bool(self.nk or self.nm or self.ne)
         if fused.usable(feats[0]) and (not ext_head or self._ext_ok()):    # branch tensors -> [B, 4+nc(+nk|nm), A] float in one launch
             seqs = list(self.cv2) + list(self.cv3)
             pads = self._pads(ext_head)
@@ -367,8 +373,8 @@ class Detect(nn.Module):
             # fp32 kernels: the branches on k32_conv, the decode (DFL, dist2bbox, sigmoid, level concat, keypoints / coefficients) in one launch
             box = [self._branch(self.cv2[i], f) for i, f in enumerate(feats)]
             cls = [self._branch(self.cv3[i], f) for i, f in enumerate(feats)]
-            ext = [self._branch(self.cv4[i], f) for i, f in enumerate(feats)] if (self.nk or self.nm) else None
-            pred = fused32.v8_decode(box, cls, self.strides, self.nc, ext, self.nk or self.nm, 1 if self.nk else 0)
+            ext = [self._branch(self.cv4[i], f) for i, f in enumerate(feats)] if (self.nk or self.nm or self.ne) else None
+            pred = fused32.v8_decode(box, cls, self.strides, self.nc, ext, self.nk or self.nm or self.ne, self._ext_mode())
             return (pred, self.proto(feats[0])) if self.nm else pred
         box = torch.cat([self._branch(self.cv2[i], f).reshape(B, 64, -1) for i, f in enumerate(feats)], 2)
         cls = torch.cat([self._branch(self.cv3[i], f).reshape(B, self.nc, -1) for i, f in enumerate(feats)], 2)
@@ -380,6 +386,14 @@ class Detect(nn.Module):
         lt, rb = d[:, :2], d[:, 2:]
         x1y1, x2y2 = anchors - lt, anchors + rb
         out = [torch.cat(((x1y1 + x2y2) / 2, x2y2 - x1y1), 1) * strides, cls.sigmoid()]
+        if self.ne:
+            # oriented boxes (Ultralytics OBB): theta = (sigmoid - 1/4) pi in [-pi/4, 3pi/4); dist2rbox turns the offset of the box centre
+            # from the anchor by theta; the sizes are the sums of the opposite distances
+            theta = (torch.cat([self.cv4[i](f).reshape(B, 1, -1) for i, f in enumerate(feats)], 2).sigmoid() - 0.25) * math.pi
+            cos, sin = theta.cos(), theta.sin()
+            xf, yf = ((rb - lt) / 2).split(1, 1)
+            xy = torch.cat((xf * cos - yf * sin, xf * sin + yf * cos), 1) + anchors
+            out = [torch.cat((xy, lt + rb), 1) * strides, cls.sigmoid(), theta]
         if self.nk:
             # keypoint decode (Ultralytics Pose.kpts_decode): xy = (2 k + anchor - 0.5) * stride, visibility = sigmoid
             k = torch.cat([self.cv4[i](f).reshape(B, self.nk, -1) for i, f in enumerate(feats)], 2).view(B, self.nk // 3, 3, -1)
@@ -397,7 +411,7 @@ _V8_SCALES = {"n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024), "m": (0.67, 0.75
 
 
 class YOLOv8(nn.Module):
-    def __init__(self, scale="n", nc=80, nk=0, nm=0):
+    def __init__(self, scale="n", nc=80, nk=0, nm=0, ne=0):
         super().__init__()
         d, w, mc = _V8_SCALES[scale]
         c = lambda x: int(math.ceil(min(x, mc) * w / 8) * 8)
@@ -412,8 +426,8 @@ class YOLOv8(nn.Module):
         self.h15 = C2f(c(512) + c(256), c(256), n(3))
         self.h16, self.h18 = Conv(c(256), c(256), 3, 2), C2f(c(256) + c(512), c(512), n(3))
         self.h19, self.h21 = Conv(c(512), c(512), 3, 2), C2f(c(512) + c(1024), c(1024), n(3))
-        self.detect = Detect(nc, (c(256), c(512), c(1024)), nk, nm, c(256))
-        self.nc, self.nk, self.nm = nc, nk, nm
+        self.detect = Detect(nc, (c(256), c(512), c(1024)), nk, nm, c(256), ne)
+        self.nc, self.nk, self.nm, self.ne = nc, nk, nm, ne
 
     def forward_backbone(self, x):
         p3 = self.b4(self.b3(self.b2(self.b1(self.b0(x)))))
@@ -580,14 +594,14 @@ class C2PSA(nn.Module):
 class Detect11(Detect):
     """v11 head: the class branch is depthwise-separable (DWConv 3x3 -> Conv 1x1, twice) before the final 1x1."""
 
-    def __init__(self, nc, ch, nk=0, nm=0, npr=256):
-        super().__init__(nc, ch, nk, nm, npr)
+    def __init__(self, nc, ch, nk=0, nm=0, npr=256, ne=0):
+        super().__init__(nc, ch, nk, nm, npr, ne)
         c3 = max(ch[0], min(nc, 100))
         self.cv3 = nn.ModuleList(nn.Sequential(nn.Sequential(Conv(x, x, 3, g=x), Conv(x, c3, 1)),
                                                nn.Sequential(Conv(c3, c3, 3, g=c3), Conv(c3, c3, 1)), nn.Conv2d(c3, nc, 1)) for x in ch)
 
     def forward(self, feats):
-        ext_head = bool(self.nk or self.nm)
+        ext_head = bool(self.nk or self.nm or self.ne)
         if (fused.usable(feats[0]) and (not ext_head or self._ext_ok()) and len(feats) == 3
                 and all(self._last_ok(s[2]) for s in list(self.cv2) + list(self.cv3))):
             z = self._zero_bias(feats[0])
@@ -606,7 +620,7 @@ _V11_SCALES = {"n": (0.50, 0.25, 1024), "s": (0.50, 0.50, 1024), "m": (0.50, 1.0
 
 
 class YOLO11(nn.Module):
-    def __init__(self, scale="n", nc=80, nk=0, nm=0):
+    def __init__(self, scale="n", nc=80, nk=0, nm=0, ne=0):
         super().__init__()
         d, w, mc = _V11_SCALES[scale]
         c = lambda x: int(math.ceil(min(x, mc) * w / 8) * 8)
@@ -622,8 +636,8 @@ class YOLO11(nn.Module):
         self.h16 = C3k2(c(512) + c(512), c(256), n(2), k3)
         self.h17, self.h19 = Conv(c(256), c(256), 3, 2), C3k2(c(256) + c(512), c(512), n(2), k3)
         self.h20, self.h22 = Conv(c(512), c(512), 3, 2), C3k2(c(512) + c(1024), c(1024), n(2), True)
-        self.detect = Detect11(nc, (c(256), c(512), c(1024)), nk, nm, c(256))
-        self.nc, self.nk, self.nm = nc, nk, nm
+        self.detect = Detect11(nc, (c(256), c(512), c(1024)), nk, nm, c(256), ne)
+        self.nc, self.nk, self.nm, self.ne = nc, nk, nm, ne
 
     def forward(self, x):
         p3 = self.b4(self.b3(self.b2(self.b1(self.b0(x)))))
@@ -1044,16 +1058,25 @@ DETECTORS = {
 }
 
 
+# Oriented-box models (docs/OBB.md): DOTA's 15 classes and one angle per anchor.  A table of its own: DETECTORS is also the list of models
+# with a recorded launch plan.
+OBB_DETECTORS = {
+    "yolov8n-obb": lambda: YOLOv8("n", nc=15, ne=1), "yolov8s-obb": lambda: YOLOv8("s", nc=15, ne=1),
+    "yolo11n-obb": lambda: YOLO11("n", nc=15, ne=1),
+}
+
+
 def build_detector(name: str, seed: int = 0) -> nn.Module:
     """Seeded random-init detector named like the reference's weight files
     (yolo_multi_model.py:14-17: 'yolov8n-seg.pt', 'yolov5n.pt', 'yolo11n.pt', 'yolo11n-pose.pt')."""
     key = name.lower().replace(".pt", "")
-    if key not in DETECTORS:
-        raise ValueError(f"unknown detector '{name}'; known: {sorted(DETECTORS)}")
+    table = OBB_DETECTORS if key in OBB_DETECTORS else DETECTORS
+    if key not in table:
+        raise ValueError(f"unknown detector '{name}'; known: {sorted(DETECTORS) + sorted(OBB_DETECTORS)}")
     g = torch.random.fork_rng()
     with g:
         torch.manual_seed(seed)
-        m = DETECTORS[key]()
+        m = table[key]()
     return m.eval()
 
 

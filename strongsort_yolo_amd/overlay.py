@@ -134,10 +134,14 @@ class Overlay:
         if zones is not None:
             self._zones(cl, zones)
         live = {int(i) for r in results if r is not None and r.boxes is not None and r.boxes.id is not None for i in r.boxes.id}
+        live |= {int(i) for r in results if r is not None and getattr(r, "obb", None) is not None and r.obb.id is not None for i in r.obb.id}
         for id_ in list(self.trails):                                   # yolo_multi_model.py:45-47
             if id_ not in live:
                 del self.trails[id_]
         for r in results:
+            if r is not None and r.boxes is None and getattr(r, "obb", None) is not None:
+                self._obb(cl, r.obb)
+                continue
             if r is None or r.boxes is None:
                 continue
             tracked = r.boxes.id is not None
@@ -193,6 +197,25 @@ class Overlay:
         for i, poly in enumerate(z.cfg.zones):
             cl.polyline(poly, bgr(255, 128, 0), 2)
             cl.text(f"Z{i} {int(z.occupancy[i])} inside", int(poly[0][0]) + 4, int(poly[0][1]) + 12, bgr(255, 128, 0))
+
+    def _obb(self, cl, obb):
+        """An oriented-box result (docs/OBB.md): every box as a closed four-point polyline with its label at the top-most corner; a tracked
+        box leaves its trail through the rotated box's centre."""
+        tracked = obb.id is not None
+        ids = obb.id if tracked else [None] * len(obb)
+        for conf, cls, pts, ctr, id_ in zip(obb.conf, obb.cls, obb.xyxyxyxy.tolist(), obb.xywhr[:, :2].tolist(), ids):
+            name = f"{self.names.get(int(cls), int(cls))} {round(float(conf) * 100, 1)}%"
+            label = f" ID: {int(id_)} {name}" if tracked else f" {name}"
+            cl.polyline(np.int32(pts), bgr(0, 0, 225), 2)
+            x0, y0 = (int(v) for v in min(pts, key=lambda p: (p[1], p[0])))
+            cl.fill(x0, y0, x0 + ADVANCE * len(label) + 2, y0 - 12, bgr(30, 30, 30))
+            cl.text(label, x0, y0 - 3, bgr(255, 255, 255))
+            if tracked:
+                self.trails.setdefault(int(id_), deque(maxlen=self.trail_len)).append((float(ctr[0]), float(ctr[1])))
+        if tracked:
+            for t in self.trails.values():
+                for i in range(1, len(t)):
+                    cl.line(int(t[i - 1][0]), int(t[i - 1][1]), int(t[i][0]), int(t[i][1]), bgr(255, 255, 255), 2)
 
     @staticmethod
     def _box(cl, xyxy, label):

@@ -63,6 +63,17 @@ class FramePipeline:
         # merges the tiles' rows into b.dets / b.ndets; from there on nothing differs.  None: nothing of it is allocated or launched.
         from .config import byte_config, ocsort_config, deep_ocsort_config, check_reid_model, check_pose, check_gmc_method
         self.slice = slice_cfg
+        # an oriented-box model (docs/OBB.md §5): one angle row behind the class scores, the rotated NMS, 11-column rows (nx = 5), and
+        # the BYTE family on ProbIoU; what is not built for rotated boxes is refused by name before anything is allocated
+        self.ne = 1 if detector.lower().replace(".pt", "") in nets.OBB_DETECTORS else 0
+        if self.ne:
+            if tracker in ("ocsort", "deep_ocsort") or (tracker == "strongsort" and not detect_only_rows):
+                raise ValueError(f"'{detector}' is an oriented-box model: tracker '{tracker}' associates on axis-aligned boxes; use 'bytetrack' or "
+                                 "'botsort' (ProbIoU of the rotated boxes, docs/OBB.md §4)")
+            for on, what in ((with_reid, "with_reid"), (reid_model == "auto", "reid_model='auto'"), (with_pose, "with_pose"),
+                             (cmc, "camera_motion"), (slice_cfg is not None, "slice_hw")):
+                if on:
+                    raise ValueError(f"'{detector}' is an oriented-box model: {what} is not built for rotated boxes (docs/OBB.md §5)")
         if self.slice is not None and reid_model == "auto":
             raise ValueError("sliced inference cannot feed reid_model='auto': the detector's anchor indices are per tile")
         self.deep_cfg = deep_ocsort_config(tracker, with_reid, with_pose, ocsort_use_byte)
@@ -80,7 +91,7 @@ class FramePipeline:
         self.byte, self.trk = None, self.eng
         if self.byte_cfg is not None:
             from .engine import ByteTrackEngine
-            self.byte = self.trk = ByteTrackEngine(self.byte_cfg, engine=self.eng)
+            self.byte = self.trk = ByteTrackEngine(self.byte_cfg, engine=self.eng, obb=bool(self.ne))
         elif self.oc_cfg is not None:
             from .engine import OCSortEngine
             self.byte = self.trk = OCSortEngine(self.oc_cfg, engine=self.eng)
@@ -136,8 +147,8 @@ class FramePipeline:
             if self.native:
                 self.detector.detect.register_forward_pre_hook(self._take_head_inputs)
         else:
-            self.nc, self.nk, self.nm = 80, 0, 0
-        self.nx = self.nk + self.nm                             # extra columns NMS carries along with every kept row
+            self.nc, self.nk, self.nm = 15 if self.ne else 80, 0, 0
+        self.nx = 5 if self.ne else self.nk + self.nm           # extra columns NMS carries along with every kept row (OBB: cx, cy, w, h, theta)
         try:
             check_pose(self.byte_cfg, self.nk)
             if self.slice is not None and self.nm:
@@ -238,10 +249,12 @@ class FramePipeline:
                         count=b.tile_ndets, max_det=min(self.max_det, self.tile_rows))
             e.slice_merge(b.tile_dets.view(-1, self.T, self.tile_rows, 6 + self.nx), b.tile_ndets.view(-1, self.T), sc.merge, sc.metric, sc.thr,
                           self.dcfg.agnostic_nms, self.max_det, out=b.dets, count=b.ndets, src=b.keep)
+        elif self.ne:                       # rotated NMS on ProbIoU: rows = envelope, conf, cls, cx, cy, w, h, theta
+            e.nms_obb_batch(b.pred_in, self.nc, self.dcfg, self.geom_dev, rows=b.dets, keep=b.keep, count=b.ndets, max_det=self.max_det)
         else:
             e.nms_batch(b.pred_in, self.nc, self.dcfg, self.geom_dev, n_extra=self.nx, rows=b.dets, keep=b.keep,
                         count=b.ndets, max_det=self.max_det)
-        if self.nx:
+        if self.nx and not self.ne:         # (the OBB tracker call reads the 11-column rows themselves)
             b.dets6.copy_(b.dets[:, :, :6])
         if self.native and self.run_nets and self.feat_source == "reid":
             e.native_feats(b.maps, b.keep, b.ndets, b.feats_v)
@@ -312,7 +325,8 @@ class FramePipeline:
 
     def _track(self):
         b = self.b
-        self.trk.update_device(b.dets6, b.ndets, b.feats_v, self.img_hw, out=self.out, nout=self.nout, **self._pose_kw(b, 0, self.Sv))
+        self.trk.update_device(b.dets if self.ne else b.dets6, b.ndets, b.feats_v, self.img_hw, out=self.out, nout=self.nout,
+                               **self._pose_kw(b, 0, self.Sv))
 
     def _pose_kw(self, b, v0, v1):
         """with_pose: the NMS rows of virtual streams [v0, v1) as the tracker call's keypoints (their columns from 6, network-input
@@ -423,7 +437,7 @@ class _Bufs:
         ST = S * p.T                        # images the detector sees: sliced, T tiles of every frame (tile-side buffers, leading dimension S * T)
         self.frames = torch.zeros(S, p.H, p.W, 3, dtype=torch.uint8, device=dev)
         self.lb = torch.zeros(ST, 3, g.out_h, g.out_w, dtype=p.dtype, device=dev).contiguous(memory_format=torch.channels_last)
-        self.pred_in = torch.zeros(ST, 4 + p.nc + p.nx, p.n_anchors, dtype=torch.float32, device=dev)
+        self.pred_in = torch.zeros(ST, 4 + p.nc + (p.ne or p.nx), p.n_anchors, dtype=torch.float32, device=dev)
         if p.slice is not None:             # the tiles' NMS rows, anchors and counts, which the merge reads
             self.tile_dets = torch.zeros(ST, p.tile_rows, 6 + p.nx, dtype=torch.float32, device=dev)
             self.tile_keep = torch.zeros(ST, p.tile_rows, dtype=torch.int32, device=dev)
@@ -501,6 +515,7 @@ class OverlappedPipeline(FramePipeline):
             self.tile_geom_dev = self.eng.slice_nms_geom(self.Sv)
         self.outs = torch.zeros(self.F, self.S, MAX_TRACKS, 8, dtype=torch.float32, device=self.dev)
         self.nouts = torch.zeros(self.F, self.S, dtype=torch.int32, device=self.dev)
+        self.rboxs = torch.zeros(self.F, self.S, MAX_TRACKS, 5, dtype=torch.float32, device=self.dev) if self.ne else None   # OBB: the rows' cx, cy, w, h, theta
         split_det = self.run_nets and n_stages >= 4 and hasattr(self.detector, "forward_backbone")
         split_reid = self.run_nets and n_stages >= 4 and self.reid is not None and hasattr(self.reid, "forward_a")
         # two stages can also be cut INSIDE the ReID network to balance them: stage 0 = letterbox, detector, NMS,
@@ -627,6 +642,10 @@ class OverlappedPipeline(FramePipeline):
             n, v0, v1 = min(G, nv - f0), f0 * S, min(nv, f0 + G) * S
             if self.cmc:
                 e.set_cmc(b.warps[f0:f0 + n])
+            if self.ne:
+                e.update_group(n, b.dets[v0:v1], b.ndets[v0:v1], None, self.img_hw, self.outs[f0:f0 + n], self.nouts[f0:f0 + n],
+                               rbox=self.rboxs[f0:f0 + n])
+                continue
             e.update_group(n, b.dets6[v0:v1], b.ndets[v0:v1], b.feats_v[v0:v1], self.img_hw, self.outs[f0:f0 + n], self.nouts[f0:f0 + n],
                            **self._pose_kw(b, v0, v1))
         if self.sR is not None:                                 # detached chain: the rows exist once the chain's stream is done

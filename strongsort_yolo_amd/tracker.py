@@ -86,19 +86,26 @@ class BYTETracker:
        the crops from `frame` and runs OSNet-x0.25 (reid_weights, loaded as StrongSORT loads them; fp16 selects half
        activations) when `features` is None.  reid_model="auto" (§1d): no OSNet is built; update needs `features`.
        cfg.with_pose=True (xywh only, not with with_reid): the keypoint term (§1e).  `update(dets, keypoints=...)` takes the rows'
-       keypoints [N,K,3] (x, y, visibility) in the same frame pixels as `dets`."""
+       keypoints [N,K,3] (x, y, visibility) in the same frame pixels as `dets`.
+       obb=True (docs/OBB.md §4; not with camera_motion, with_reid or with_pose): oriented boxes, associated on ProbIoU.  `update(dets)`
+       takes [N,7+] rows cx, cy, w, h, theta, conf, cls (taken as they are: not regularised) and returns float32 [M,13]: the eight
+       columns above with the rotated box's axis-aligned envelope in front, then the track's cx, cy, w, h, theta."""
 
     def __init__(self, cfg: Optional[ByteTrackConfig] = None, device: int = 0, camera_motion: bool = False,
                  reid_weights: Optional[str] = None, fp16: bool = False, random_init_ok: bool = False, reid_seed: int = 1,
-                 reid_model: str = "osnet", gmc_method: str = "ecc"):
+                 reid_model: str = "osnet", gmc_method: str = "ecc", obb: bool = False):
         self.cfg = cfg or ByteTrackConfig()
+        self.obb = bool(obb)
+        if self.obb and (camera_motion or self.cfg.with_reid or self.cfg.with_pose):
+            raise ValueError("obb=True: oriented boxes are not combined with camera_motion, with_reid or with_pose (docs/OBB.md §4)")
         self.reid_model = check_reid_model(reid_model, self.cfg.with_reid, reid_weights)
         self.gmc_method = check_gmc_method(gmc_method, camera_motion, "botsort" if self.cfg.kalman == "xywh" else "bytetrack")
         if camera_motion and self.cfg.kalman != "xywh":
             raise ValueError("camera_motion needs the xywh (BoT-SORT) filter: ByteTrack has no GMC")
-        self.eng = ByteTrackEngine(self.cfg, 1, device)
+        self.eng = ByteTrackEngine(self.cfg, 1, device, obb=self.obb)
         self.dev = self.eng.device
         self.camera_motion = bool(camera_motion)
+        self._dets11 = torch.zeros(1, MAX_DETS, 11, dtype=torch.float32, device=self.dev) if self.obb else None
         self.reid = None
         if self.cfg.with_reid:
             self.dtype = torch.float16 if fp16 else torch.float32
@@ -115,6 +122,8 @@ class BYTETracker:
     @torch.no_grad()
     def update(self, dets, frame=None, features=None, keypoints=None) -> np.ndarray:
         self.eng.use_current_stream()
+        if self.obb:
+            return self._update_obb(dets)
         dets = torch.as_tensor(dets, dtype=torch.float32).reshape(-1, 6)
         n = dets.shape[0]
         if n > self.cfg.max_dets:
@@ -163,6 +172,24 @@ class BYTETracker:
         torch.cuda.synchronize(self.dev)
         self.eng.check_errors()
         return out[0, : int(nout[0])].cpu().numpy()
+
+    def _update_obb(self, dets) -> np.ndarray:
+        dets = torch.as_tensor(dets, dtype=torch.float32)
+        dets = dets.reshape(-1, dets.shape[-1] if dets.dim() > 1 else 7)
+        n = dets.shape[0]
+        if dets.shape[1] < 7:
+            raise ValueError("obb=True: dets [N,7+] = cx, cy, w, h, theta, conf, cls")
+        if n > self.cfg.max_dets:
+            raise ValueError(f"at most {self.cfg.max_dets} detections per frame (got {n})")
+        rows = torch.zeros(n, 11, dtype=torch.float32)               # the tracker call reads conf, cls and the rotated box, not the envelope
+        rows[:, 4:6], rows[:, 6:11] = dets[:, 5:7], dets[:, :5]
+        self._dets11[0, :n].copy_(rows, non_blocking=True)
+        self._n.fill_(n)
+        out, nout = self.eng.update_device(self._dets11, self._n)
+        torch.cuda.synchronize(self.dev)
+        self.eng.check_errors()
+        m = int(nout[0])
+        return torch.cat([out[0, :m], self.eng.rbox[0, :m]], 1).cpu().numpy()
 
     def reset(self):
         self.eng.reset(-1)

@@ -61,6 +61,50 @@ class Boxes:
         return self.id is not None
 
 
+# DOTA v1's 15 classes in the order of Ultralytics' DOTAv1.yaml (the -obb models), spelt with underscores like COCO_NAMES
+DOTA_NAMES = ("plane ship storage_tank baseball_diamond tennis_court basketball_court ground_track_field harbor bridge large_vehicle "
+              "small_vehicle helicopter roundabout soccer_ball_field swimming_pool").split()
+
+
+class OBB:
+    """Oriented boxes (docs/OBB.md): `xywhr` [n,5] = cx, cy, w, h, theta in original-image pixels (w >= h, theta in [0, pi)), `xyxy` [n,4]
+    the axis-aligned envelope, `conf`, `cls`, `id` (None unless tracked).  `OBB.from_rows` reads the rows ss_nms_obb_batch writes.
+    Length, indexing and iteration as Boxes."""
+
+    def __init__(self, xywhr, xyxy, conf, cls, ids=None):
+        self.xywhr, self.xyxy, self.conf, self.cls, self.id = xywhr, xyxy, conf, cls, ids
+
+    @classmethod
+    def from_rows(cls, rows, ids=None):
+        """rows [n, >= 11] = x1, y1, x2, y2, conf, cls, cx, cy, w, h, theta (TrackerEngine.nms_obb_batch, the first `count` rows of an image)"""
+        rows = torch.as_tensor(rows)
+        if rows.dim() != 2 or rows.shape[1] < 11:
+            raise ValueError("OBB.from_rows: rows [n, 11] = x1, y1, x2, y2, conf, cls, cx, cy, w, h, theta")
+        return cls(rows[:, 6:11], rows[:, :4], rows[:, 4], rows[:, 5], ids)
+
+    @property
+    def xyxyxyxy(self):
+        """[n,4,2]: the corners ctr + v1 + v2, ctr + v1 - v2, ctr - v1 - v2, ctr - v1 + v2 with v1 = (w/2)(cos, sin), v2 = (h/2)(-sin, cos)"""
+        ctr, w, h, t = self.xywhr[:, :2], self.xywhr[:, 2:3], self.xywhr[:, 3:4], self.xywhr[:, 4:5]
+        cos, sin = torch.cos(t), torch.sin(t)
+        v1, v2 = torch.cat((w / 2 * cos, w / 2 * sin), 1), torch.cat((-h / 2 * sin, h / 2 * cos), 1)
+        return torch.stack((ctr + v1 + v2, ctr + v1 - v2, ctr - v1 - v2, ctr - v1 + v2), 1)
+
+    def __len__(self):
+        return self.xywhr.shape[0]
+
+    def __getitem__(self, i):
+        i = _row(i, len(self))
+        return OBB(self.xywhr[i], self.xyxy[i], self.conf[i], self.cls[i], None if self.id is None else self.id[i])
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+    @property
+    def is_track(self):
+        return self.id is not None
+
+
 class Keypoints:
     def __init__(self, data):                    # [n,17,3]
         self.data = data
@@ -217,12 +261,16 @@ class Masks:
 
 
 class Results:
-    def __init__(self, orig_img, names, boxes: Optional[Boxes], keypoints: Optional[Keypoints] = None, masks: Optional[Masks] = None):
+    def __init__(self, orig_img, names, boxes: Optional[Boxes], keypoints: Optional[Keypoints] = None, masks: Optional[Masks] = None,
+                 obb: Optional[OBB] = None):
         self.orig_img, self.names, self.boxes, self.keypoints, self.masks = orig_img, names, boxes, keypoints, masks
+        self.obb = obb                   # an oriented-box result: boxes is then None, as upstream
         self.orig_img_device = None      # track_stream(keep_device_frames=True): the frame as a device tensor uint8 [H,W,3] (for Overlay.draw_resident)
 
     def __len__(self):
-        return 0 if self.boxes is None else len(self.boxes)
+        if self.boxes is None:
+            return 0 if self.obb is None else len(self.obb)
+        return len(self.boxes)
 
 
 class _HostResults:
@@ -245,9 +293,10 @@ class _HostResults:
         self.proto = torch.empty((F,) + tuple(b.proto.shape[1:]), dtype=b.proto.dtype).pin_memory() if pipe.nm and not dmask else None
         self.masks = model._mask_host(pipe, F, R) if dmask else None          # in place of proto
         self.frames = torch.empty((F,) + tuple(b.frames.shape[1:]), dtype=torch.uint8, device=pipe.dev) if keep_frames else None
+        self.rbox = torch.zeros(F, n_track_rows, 5).pin_memory() if pipe.ne and n_track_rows else None       # OBB: the track rows' xywh theta
         self.done = torch.cuda.Event()
 
-    def fetch(self, model, b, nv=1, outs=None, nouts=None, packed=False):
+    def fetch(self, model, b, nv=1, outs=None, nouts=None, packed=False, rbox=None):
         """Enqueue, on the current stream, the hand-over of buffer set b's first nv frames and their track rows outs [nv, 256, 8] /
         counts nouts [nv] (None: detection only).  packed (one frame): counts and rows in one launch (ss_pack_results)."""
         pipe = self.pipe
@@ -259,6 +308,8 @@ class _HostResults:
                 self.cnt[1, :nv].copy_(nouts, non_blocking=True)
             self.cnt[0, :nv].copy_(b.ndets[:nv], non_blocking=True)
             self.dets[:nv].copy_(b.dets[:nv], non_blocking=True)
+        if rbox is not None and outs is not None:
+            self.rbox[:nv].copy_(rbox, non_blocking=True)
         if self.masks is not None:
             model._mask_launch(pipe, b.proto[:nv], b.dets[:nv], b.ndets[:nv], self.masks)
         elif self.proto is not None:
@@ -271,7 +322,8 @@ class _HostResults:
         n, m = int(self.cnt[0, f]), int(self.cnt[1, f])
         model._warn_if_capped(self.pipe, n, track)
         res = model._results(image, self.pipe, self.dets[f, :n].clone(), self.rows[f, :m].clone() if track else None,
-                             None if self.proto is None else self.proto[f].clone(), model._mask_rows(self.masks, f, n))
+                             None if self.proto is None else self.proto[f].clone(), model._mask_rows(self.masks, f, n),
+                             rbox=self.rbox[f, :m].clone() if track and self.rbox is not None else None)
         if self.frames is not None:
             res[0].orig_img_device = self.frames[f]
         return res
@@ -346,6 +398,16 @@ class YOLO:
         self.with_reid = bool(with_reid)
         self.with_pose = bool(with_pose)
         self._byte = tracker_type != "strongsort"
+        from .nets import OBB_DETECTORS
+        self._obb = os.path.basename(weights).lower().replace(".pt", "") in OBB_DETECTORS
+        if self._obb:                             # docs/OBB.md §5: what is not built for rotated boxes is refused by name
+            if tracker_type in ("ocsort", "deep_ocsort"):
+                raise ValueError(f"{weights!r} is an oriented-box model: tracker_type {tracker_type!r} associates on axis-aligned boxes; use "
+                                 "'bytetrack' or 'botsort' (ProbIoU of the rotated boxes)")
+            for on, what in ((with_reid, "with_reid"), (reid_model == "auto", "reid_model='auto'"), (with_pose, "with_pose"),
+                             (camera_motion, "camera_motion"), (slice_hw is not None, "slice_hw"), (device_masks, "device_masks")):
+                if on:
+                    raise ValueError(f"{weights!r} is an oriented-box model: {what} is not built for rotated boxes (docs/OBB.md §5)")
         if tracker_type == "bytetrack" and camera_motion:
             raise ValueError("camera_motion needs tracker_type 'strongsort' or 'botsort' (ByteTrack has no GMC, G-05)")
         self.gmc_method = check_gmc_method(gmc_method, camera_motion, tracker_type)
@@ -360,7 +422,7 @@ class YOLO:
         pose = "pose" in self.arch
         if self.with_pose and not pose:
             raise ValueError(f"with_pose needs a pose model (keypoint columns): {weights!r} has none")
-        self.names = {0: "person"} if pose else dict(enumerate(COCO_NAMES))
+        self.names = {0: "person"} if pose else dict(enumerate(DOTA_NAMES if self._obb else COCO_NAMES))
         self._host = {}                 # slot name -> the _HostResults of a per-frame pipeline
         self._pipe = None               # the cached pipelines (each with its .key): track() / predict(),
         self._stream_pipe = None        # track_stream(),
@@ -446,7 +508,10 @@ class YOLO:
         if isinstance(image, EncodedFrame):
             raise TypeError("track() / predict() take decoded frames (BGR uint8 arrays): pass EncodedFrames to track_stream(), "
                             "or decode them first with strongsort_yolo_amd.jpeg.decode()")
-        wide = not track and (int(self.overrides["max_det"]) > 128 or self._byte)
+        if track and self._obb and not self._byte:
+            raise ValueError(f"{self.weights!r} is an oriented-box model: tracker_type 'strongsort' associates on axis-aligned boxes; build the "
+                             "model with tracker_type 'bytetrack' or 'botsort' (ProbIoU of the rotated boxes)")
+        wide = not track and (int(self.overrides["max_det"]) > 128 or self._byte or self._obb)
         slot = "_pred_pipe" if wide else "_pipe"
         if wide:
             pipe, new = self._cached(slot, FramePipeline, image.shape[:2], device, graph="split", detect_only_rows=1024)
@@ -464,7 +529,8 @@ class YOLO:
             self._fill(pipe, 0, self._frame_index)
         pipe.step(track=track)
         h = self._host[slot]
-        h.fetch(self, pipe, 1, pipe.out if track else None, pipe.nout if track else None, packed=not wide)
+        h.fetch(self, pipe, 1, pipe.out if track else None, pipe.nout if track else None, packed=not wide,
+                rbox=pipe.byte.rbox if track and pipe.ne else None)
         torch.cuda.current_stream(pipe.dev).synchronize()            # the one synchronisation of the call
         pipe.eng.check_errors()
         if not wide:
@@ -518,8 +584,14 @@ class YOLO:
         polys = [pts[r, :k].astype(np.float32) if k >= 0 else None for r, k in enumerate(npts.tolist())]
         return h["bits"][f, :n].numpy().copy(), polys
 
-    def _results(self, image, pipe, dets, rows, proto=None, dm=None):
+    def _results(self, image, pipe, dets, rows, proto=None, dm=None, rbox=None):
         kpts = masks = None
+        if getattr(pipe, "ne", 0):                      # oriented boxes: Results.obb, boxes None as upstream
+            if rows is None:
+                return [Results(image, self.names, None, obb=OBB.from_rows(dets))]
+            sel = rows[:, 7] >= 0
+            rows, rbox = rows[sel], rbox[sel]
+            return [Results(image, self.names, None, obb=OBB(rbox, rows[:, :4], rows[:, 6], rows[:, 5], rows[:, 4]))]
         if pipe.nk:
             k = dets[:, 6:6 + pipe.nk].reshape(dets.shape[0], pipe.nk // 3, 3).clone()
             k[..., 0] = (k[..., 0] - pipe.pad_x) / pipe.gain
@@ -619,6 +691,9 @@ class YOLO:
                 if nxt.shape != first.shape:
                     raise ValueError(f"track_stream: EncodedFrame of shape {nxt.shape} in a stream of {first.shape}")
             return nxt
+        if self._obb and not self._byte:
+            raise ValueError(f"{self.weights!r} is an oriented-box model: tracker_type 'strongsort' associates on axis-aligned boxes; build the "
+                             "model with tracker_type 'bytetrack' or 'botsort' (ProbIoU of the rotated boxes)")
         self._conf_track = float(conf or 0.1) if self._byte else None
         try:
             pipe, _ = self._cached("_stream_pipe", OverlappedPipeline, first.shape[:2], device, key=(batch,), graph="front", frame_batch=batch,
@@ -641,7 +716,7 @@ class YOLO:
             if f != nv - 1:
                 return
             h = ring[g % len(ring)]
-            h.fetch(self, b, nv, pipe.outs[:nv, 0], pipe.nouts[:nv, 0])
+            h.fetch(self, b, nv, pipe.outs[:nv, 0], pipe.nouts[:nv, 0], rbox=pipe.rboxs[:nv, 0] if pipe.ne else None)
             h.done.record(torch.cuda.current_stream(pipe.dev))
             state["enqueued"] = g
             del state["first"][frame_idx - f]

@@ -115,9 +115,9 @@ def rows_of(results) -> np.ndarray:
     """The tracked boxes of one frame's Results as device-layout rows [n, 8]: x1, y1, x2, y2, id, cls, conf, 0 (float32)."""
     out = []
     for r in results:
-        if r is None or r.boxes is None or r.boxes.id is None or len(r.boxes) == 0:
+        b = None if r is None else r.boxes if r.boxes is not None else getattr(r, "obb", None)    # an oriented-box result: its envelopes (docs/OBB.md §3)
+        if b is None or b.id is None or len(b) == 0:
             continue
-        b = r.boxes
         xyxy, tid, cls, conf = (np.asarray(v.cpu() if hasattr(v, "cpu") else v, np.float32).reshape(len(b), -1) for v in (b.xyxy, b.id, b.cls, b.conf))
         out.append(np.concatenate([xyxy, tid, cls, conf, np.zeros((len(b), 1), np.float32)], 1))
     return np.concatenate(out, 0) if out else np.zeros((0, 8), np.float32)
