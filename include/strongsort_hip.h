@@ -940,6 +940,38 @@ int ss_zone_set_colormap(ss_ctx* ctx, const uint8_t* bgr_256x3);
 int ss_zone_heat_blend(ss_ctx* ctx, void* hip_stream, uint8_t* d_frames, int batch, long long frame_batch_stride, int h, int w, int row_stride,
                        const int* d_heat, long long heat_frame_stride, const int* d_max, int max_stride, int alpha);
 
+/* ---- identities across cameras: a descriptor per track id kept beside a tracker, and the linking of the cameras' tracklets after
+ * the run (csrc/ss_mtmc.hip, docs/MTMC.md; the bits are those of tests/mtmc_ref.py) ---- */
+/* Host only: the most ids a bank may be made for (65 536) and the most tracklets of one ss_mtmc_link (2048). */
+int ss_bank_max_ids(void);
+int ss_mtmc_max_tracklets(void);
+/* The bank is hung off an existing context, one table per stream of it: per track id 1..max_ids the f64 sum of the unit features of
+ * its rows, their count, first and last frame and the last class (4 KiB an id and stream).  A second call replaces it.  Every
+ * argument of every ss_bank_* entry is checked before the device is touched (SS_ERR_INVALID, also with ctx NULL). */
+int ss_bank_create(ss_ctx* ctx, int max_ids);
+int ss_bank_destroy(ss_ctx* ctx);
+int ss_bank_reset(ss_ctx* ctx, int stream);                /* stream < 0: all streams; sums, counts, frame counter and error word */
+/* A group of n_frames (1..32) frames of every stream in ONE launch, the frames in order: d_rows [n_frames][n_streams][SS_MAX_TRACKS][8]
+ * and d_nrows [n_frames][n_streams] as every tracker's update_group leaves them, d_feats [n_frames][n_streams][SS_MAX_DETS][512] the
+ * raw features that tracker call read; all read in place.  A row contributes when 0 <= det_idx < SS_MAX_DETS, 1 <= track_id <=
+ * max_ids and its feature's squared norm is positive and finite; a NEGATIVE count: the stream sits that frame out and its frame
+ * counter does not move.  Asynchronous on the context's stream (behind a detached tracker chain), capturable, no allocation.  An id
+ * above max_ids contributes nothing and SS_ERR_CAPACITY is reported by ss_check_errors until ss_bank_reset. */
+int ss_bank_update_group(ss_ctx* ctx, int n_frames, const float* d_rows, const int* d_nrows, const float* d_feats);
+/* Synchronous, host arrays: the ids of the stream with a count > 0 in rising order, *n of them; ids, counts, first, last, cls [cap]
+ * and desc [cap][512], desc = (float)(sum / |sum|).  cap 0: only *n is written (the arrays may be NULL); a cap below *n is
+ * SS_ERR_INVALID. */
+int ss_bank_get(ss_ctx* ctx, int stream, int cap, int* n, int* ids, int* counts, int* first, int* last, int* cls, float* desc);
+/* Links T tracklets (host arrays: desc [T][512] unit descriptors, camera index, first and last frame, row count, each [T]):
+ * D[i][j] = 1 - desc_i . desc_j in f32 for i < j; i and j conflict when they share a camera and their [first, last] overlap, or when
+ * either has fewer than min_rows rows; then average-linkage clustering in f64, merging the smallest (d, a, b) with d < thr among the
+ * pairs without a conflict until none is left.  global_id [T]: 1.. in rising order of each cluster's smallest tracklet; merges
+ * [T - 1][3] = (a, b, height) in order, *n_merges of them; dist_out (may be NULL) [T][T]: D, zero where i >= j.  T above
+ * ss_mtmc_max_tracklets() is SS_ERR_CAPACITY, the message naming T, before anything runs.  Synchronous, not capturable, scratch of the
+ * context that grows on demand; two identical calls give the same bytes. */
+int ss_mtmc_link(ss_ctx* ctx, int T, const float* desc, const int* cam, const int* first, const int* last, const int* n, double thr, int min_rows,
+                 int* global_id, double* merges, int* n_merges, float* dist_out);
+
 /* ---- sliced inference: the frame cut into overlapping tiles before the detector, the tiles' rows merged after it (csrc/ss_slice.hip,
  * docs/SLICE.md; the bits are those of tests/slice_ref.py) ---- */
 /* Host only: the caps (64 tiles a frame, the full-frame tile included; 8192 candidates a frame = tiles x rows_per_tile). */

@@ -365,7 +365,8 @@ def process_video(args: dict, model=None) -> dict:
                      device_masks=args.get("device_masks", False), tracker_type=args.get("tracker", "strongsort"),
                      camera_motion=args.get("camera_motion", False), with_reid=args.get("with_reid", False),
                      reid_model=args.get("reid_model", "osnet"), with_pose=args.get("with_pose", False),
-                     gmc_method=args.get("gmc_method", "ecc"), ocsort_use_byte=args.get("ocsort_use_byte", False), **slice_kwargs(args))
+                     gmc_method=args.get("gmc_method", "ecc"), ocsort_use_byte=args.get("ocsort_use_byte", False), **slice_kwargs(args),
+                     **({"track_bank": True} if args.get("mtmc") and track else {}))
         model.overrides.update(conf=0.3, iou=0.4, agnostic_nms=False, max_det=1000)      # :18-21
     name = os.path.splitext(os.path.basename(str(source)))[0] or "stream"
     writer = LabelsWriter(os.path.join(args.get("outdir", "output"), f"{name}_labels.txt"), args.get("compat", False),
@@ -458,6 +459,10 @@ def process_video(args: dict, model=None) -> dict:
             np.save(os.path.join(outdir, f"{name}_heat.npy"), zc.heatmap(0))
         zone_hw = zc.frame_hw
         zc.close()
+    if args.get("mtmc") and track and frames:
+        # --mtmc: this stream's track bank beside its labels file; the parent links the streams' tables after all of them (docs/MTMC.md)
+        from . import mtmc
+        mtmc.save_table(os.path.join(args.get("outdir", "output"), f"{name}_bank.npz"), model.track_bank())
     if gsi_on:
         # GSI post-processing of the whole run on the device context the overlay uses; the labels file above stays as it is
         from . import gsi
@@ -518,6 +523,39 @@ def aflink_post(rows, eng, args: dict, outdir: str, name: str, summary: dict):
         both, _ = gsi.gsi(linked, eng, interval=int(args.get("gsi_interval", gsi.INTERVAL)), tau=float(args.get("gsi_tau", gsi.TAU)))
         gsi.write_labels(os.path.join(outdir, f"{name}_labels_aflink_gsi.txt"), both)
     return linked
+
+
+def source_name(source) -> str:
+    """The name a source's output files carry (process_video)."""
+    return os.path.splitext(os.path.basename(str(source)))[0] or "stream"
+
+
+def mtmc_refusal(track: bool, sources, tracker: str, with_reid: bool, reid_model: str, weights: str) -> Optional[str]:
+    """Why --mtmc cannot run with these flags (None: it can)."""
+    if not track:
+        return "--mtmc links tracked ids across sources: it needs --track"
+    if len(sources) < 2:
+        return "--mtmc links ids across cameras: it needs at least two --source"
+    names = [source_name(s) for s in sources]
+    if len(set(names)) != len(names):
+        return "--mtmc: two sources share the output name '" + next(n for n in names if names.count(n) > 1) + "'"
+    from .mtmc import bank_refusal
+    from .nets import OBB_DETECTORS
+    why = bank_refusal(tracker, with_reid, reid_model, os.path.basename(str(weights)).lower().replace(".pt", "") in OBB_DETECTORS)
+    return f"--mtmc: {why}" if why else None
+
+
+def mtmc_post(sources, outdir: str, engine, thr: float, min_rows: int = 1) -> dict:
+    """--mtmc, after every stream has finished: the streams' <name>_bank.npz tables linked on the device (docs/MTMC.md), per source
+    <name>_labels_mtmc.txt = the labels file with global ids in the id column, and mtmc.json.  Every other file stays as it is."""
+    from . import mtmc
+    names = [source_name(s) for s in sources]
+    tables = [mtmc.load_table(os.path.join(outdir, f"{n}_bank.npz")) for n in names]
+    info = {}
+    maps = mtmc.link(tables, engine, thr=thr, min_rows=min_rows, info=info)
+    for n, m in zip(names, maps):
+        mtmc.rewrite_labels(os.path.join(outdir, f"{n}_labels.txt"), os.path.join(outdir, f"{n}_labels_mtmc.txt"), m)
+    return mtmc.write_summary(os.path.join(outdir, "mtmc.json"), [str(s) for s in sources], tables, maps, info)
 
 
 def _save_path(a, i: int) -> Optional[str]:
@@ -608,6 +646,12 @@ def main(argv=None):
                    help="--track only: a cumulative heat map of the anchors or of the boxes on the device into <name>_heat.npy; with --save it is blended over the frames")
     p.add_argument("--heat-cell", type=int, default=8, help="--heatmap: pixels a side of a heat cell, a power of two from 1 to 64")
     p.add_argument("--heat-alpha", type=float, default=0.5, help="--heatmap with --save: weight of the heat colour, 0 .. 1")
+    p.add_argument("--mtmc", action="store_true",
+                   help="--track with two or more --source only: every stream keeps one pooled OSNet descriptor per track id on the device, and after "
+                        "all streams the tracklets are linked across the sources (docs/MTMC.md) into <name>_labels_mtmc.txt (the labels file with "
+                        "global ids) and mtmc.json; needs a tracker with OSNet features (strongsort, deep_ocsort, botsort --with-reid)")
+    p.add_argument("--mtmc-thr", type=float, default=0.2, help="--mtmc: clusters merge while their average cosine distance is below this")
+    p.add_argument("--mtmc-min-rows", type=int, default=1, help="--mtmc: a track with fewer rows than this keeps a global id of its own")
     p.add_argument("--slice", type=int, nargs=2, default=None, metavar=("H", "W"),
                    help="sliced inference (docs/SLICE.md): run the detector on overlapping H x W tiles of every frame and merge their rows on the device; the detector costs T times as much")
     p.add_argument("--slice-overlap", type=float, default=0.2, help="--slice: overlap of neighbouring tiles as a ratio of the tile, in [0, 1)")
@@ -626,6 +670,14 @@ def main(argv=None):
                      "heat_cell": a.heat_cell, "heat_alpha": a.heat_alpha}, 80)
     except ValueError as e:
         p.error(str(e))
+    if a.mtmc:
+        why = mtmc_refusal(a.track, a.source, a.tracker, a.with_reid, a.reid_model, a.weights)
+        if why:
+            p.error(why)
+        if not (a.mtmc_thr == a.mtmc_thr and abs(a.mtmc_thr) < float("inf")) or a.mtmc_min_rows < 0:
+            p.error("--mtmc-thr must be finite and --mtmc-min-rows >= 0")
+    elif a.mtmc_thr != 0.2 or a.mtmc_min_rows != 1:
+        p.error("--mtmc-thr and --mtmc-min-rows are options of --mtmc")
     if a.eval_identity and not a.eval_gt:
         p.error("--eval-identity adds to what --eval-gt scores: it needs --eval-gt")
     if a.eval_gt and not a.track:
@@ -705,7 +757,7 @@ def main(argv=None):
              "aflink": a.aflink, "aflink_thr_t": tuple(a.aflink_thr_t), "aflink_thr_s": a.aflink_thr_s, "aflink_thr_p": a.aflink_thr_p,
              "lines": a.line, "zones": a.zone, "zone_anchor": a.zone_anchor, "zone_gap": a.zone_gap, "heatmap": a.heatmap, "heat_cell": a.heat_cell, "heat_alpha": a.heat_alpha,
              "slice": a.slice, "slice_overlap": a.slice_overlap, "slice_merge": a.slice_merge, "slice_metric": a.slice_metric, "slice_thr": a.slice_thr, "no_slice_full": a.no_slice_full,
-             "save": _save_path(a, i)}
+             "mtmc": a.mtmc, "save": _save_path(a, i)}
             for i, s in enumerate(a.source)]
     import torch
     ngpu = max(torch.cuda.device_count(), 1)
@@ -717,6 +769,15 @@ def main(argv=None):
         import torch.multiprocessing as mp
         with mp.get_context("spawn").Pool(processes=len(jobs)) as pool:      # :353-354
             out = pool.map(process_video, jobs)
+        if a.mtmc:
+            # the workers have exited: one more process opens the device, links the tables and leaves
+            from .engine import TrackerEngine
+            eng = TrackerEngine(n_streams=1, device=0)
+            try:
+                s = mtmc_post(a.source, "output", eng, a.mtmc_thr, a.mtmc_min_rows)
+            finally:
+                eng.close()
+            out.append({"mtmc": {k: s[k] for k in ("cameras", "tracklets", "clusters")}})
     for o in out:
         print(o)
     return out

@@ -85,6 +85,8 @@ struct ss_ctx {
     SSMot* mot = nullptr;       // ss_mot_eval's and ss_mot_identity's staging, scratch and second stream, made by its first call
     SSAflink* aflink = nullptr; // ss_aflink_*'s weights, staging and activation scratch, made by its first call
     SSZone* zone = nullptr;     // the analytics stage (ss_zone_create), NULL until attached
+    SSBank* bank = nullptr;     // the track bank (ss_bank_create), NULL until attached
+    SSMtmc* mtmc = nullptr;     // ss_mtmc_link's scratch, made by its first call
     SSSlice* slice = nullptr;   // sliced inference (ss_slice_config): tile table, NMS geometry, merge workspace; NULL until configured
 };
 
@@ -244,6 +246,8 @@ extern "C" void ss_destroy(ss_ctx* c)
     ss_mot_free(c->mot);
     ss_aflink_free(c->aflink);
     ss_zone_free(c->zone);
+    ss_bank_free(c->bank);
+    ss_mtmc_free(c->mtmc);
     ss_slice_free(c->slice);
     delete c;                   // (the staging areas of ss_upload, ss_upload_batch and ss_download go with it)
 }
@@ -1052,6 +1056,10 @@ extern "C" int ss_check_errors(ss_ctx* c)
         std::string err;
         if (int rcz = ss_zone_pending_impl(c->zone, c->stream, err)) return fail(c, rcz, err);
     }
+    {                                                        // the track bank's flags (an id above its max_ids)
+        std::string err;
+        if (int rcb = ss_bank_pending_impl(c->bank, c->stream, err)) return fail(c, rcb, err);
+    }
     {                                                        // images a device-entropy JPEG call refused (docs/JPEG.md section 12)
         std::string err;
         if (int rcj = ss_jpeg_pending_impl(c->jpeg, err)) return fail(c, rcj, err);
@@ -1495,6 +1503,83 @@ extern "C" int ss_assoc_timing_values(ss_ctx* c, float* out_ms, int cap, int* n)
     *n = (int)c->ev_ms.size();
     for (int i = 0; i < cap && i < *n; ++i) out_ms[i] = c->ev_ms[i];
     return SS_OK;
+}
+
+// ---- identities across cameras: the track bank and the linking (ss_mtmc.hip, docs/MTMC.md) ----------------------------------------
+extern "C" int ss_bank_max_ids(void) { return ss_bank_max_ids_impl(); }
+extern "C" int ss_mtmc_max_tracklets(void) { return ss_mtmc_max_tracklets_impl(); }
+
+// the checks every ss_bank_* entry makes after its own arguments: a context, its bank, a stream of it
+static int bank_state(ss_ctx* c, const char* entry, int stream, bool need_stream, std::string& err)
+{
+    if (!c) { err = std::string(entry) + ": null context"; return SS_ERR_INVALID; }
+    if (!c->bank) { err = std::string(entry) + ": no bank (ss_bank_create)"; return SS_ERR_INVALID; }
+    if (stream >= c->dev.S || (need_stream && stream < 0)) { err = std::string(entry) + ": stream " + std::to_string(stream) + " out of range"; return SS_ERR_INVALID; }
+    return SS_OK;
+}
+
+extern "C" int ss_bank_create(ss_ctx* c, int max_ids)
+{
+    return post_run(c, "ss_bank_create",
+        [&](std::string& err) {
+            if (max_ids < 1 || max_ids > ss_bank_max_ids_impl()) { err = "ss_bank_create: max_ids " + std::to_string(max_ids) + " outside 1.." + std::to_string(ss_bank_max_ids_impl()); return (int)SS_ERR_INVALID; }
+            if (!c) { err = "ss_bank_create: null context"; return (int)SS_ERR_INVALID; }
+            return (int)SS_OK;
+        },
+        [&](std::string& err) {
+            hipError_t e = hipStreamSynchronize(c->stream);          // nothing of a bank this call replaces may still be in flight
+            if (e != hipSuccess) { err = std::string("ss_bank_create: ") + hipGetErrorString(e); return (int)SS_ERR_HIP; }
+            return ss_bank_create_impl(&c->bank, c->stream, c->dev.S, max_ids, err);
+        });
+}
+
+extern "C" int ss_bank_destroy(ss_ctx* c)
+{
+    if (!c) return fail(nullptr, SS_ERR_INVALID, "ss_bank_destroy: null context");
+    if (!c->bank) return SS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ss_bank_free(c->bank);
+    c->bank = nullptr;
+    return SS_OK;
+}
+
+extern "C" int ss_bank_reset(ss_ctx* c, int stream)
+{
+    return post_run(c, "ss_bank_reset",
+        [&](std::string& err) { return bank_state(c, "ss_bank_reset", stream, false, err); },
+        [&](std::string& err) { return ss_bank_reset_impl(c->bank, c->stream, stream, err); });
+}
+
+extern "C" int ss_bank_update_group(ss_ctx* c, int n_frames, const float* d_rows, const int* d_nrows, const float* d_feats)
+{
+    return post_run(c, "ss_bank_update_group",
+        [&](std::string& err) {
+            if (int rc = ss_bank_update_check_impl(n_frames, d_rows, d_nrows, d_feats, err)) return rc;
+            return bank_state(c, "ss_bank_update_group", -1, false, err);
+        },
+        [&](std::string& err) {
+            if (int rc = chain_join(c, c->stream)) { err = c->err; return rc; }     // the rows of a detached tracker chain exist first
+            return ss_bank_update_impl(c->bank, c->stream, n_frames, d_rows, d_nrows, d_feats, err);
+        });
+}
+
+extern "C" int ss_bank_get(ss_ctx* c, int stream, int cap, int* n, int* ids, int* counts, int* first, int* last, int* cls, float* desc)
+{
+    return post_run(c, "ss_bank_get",
+        [&](std::string& err) {
+            if (!n || cap < 0 || (cap > 0 && (!ids || !counts || !first || !last || !cls || !desc))) { err = "ss_bank_get: null argument or negative cap"; return (int)SS_ERR_INVALID; }
+            return bank_state(c, "ss_bank_get", stream, true, err);
+        },
+        [&](std::string& err) { return ss_bank_get_impl(c->bank, c->stream, stream, cap, n, ids, counts, first, last, cls, desc, err); });
+}
+
+extern "C" int ss_mtmc_link(ss_ctx* c, int T, const float* desc, const int* cam, const int* first, const int* last, const int* n, double thr, int min_rows,
+                            int* global_id, double* merges, int* n_merges, float* dist_out)
+{
+    return post_run(c, "ss_mtmc_link",
+        [&](std::string& err) { return ss_mtmc_link_check_impl(T, desc, cam, first, last, n, thr, min_rows, global_id, merges, n_merges, err); },
+        [&](std::string& err) { return ss_mtmc_link_impl(c ? &c->mtmc : nullptr, c ? c->stream : nullptr, T, desc, cam, first, last, n, thr, min_rows, global_id,
+                                                         merges, n_merges, dist_out, err); });
 }
 
 // ---- analytics behind the trackers: lines, zones, dwell, heat (ss_zone.hip, docs/ZONES.md) -----------------------------------

@@ -156,6 +156,25 @@ int  ss_zone_blend_impl(SSZone* z, hipStream_t st, uint8_t* d_frames, int batch,
                         const int* d_heat, long long heat_frame_stride, const int* d_max, int max_stride, int alpha, std::string& err);
 void ss_zone_free(SSZone* z);
 
+// ---- ss_mtmc.hip
+struct SSBank;
+struct SSMtmc;
+int  ss_bank_max_ids_impl();
+int  ss_mtmc_max_tracklets_impl();
+int  ss_bank_create_impl(SSBank** pb, hipStream_t st, int S, int max_ids, std::string& err);
+int  ss_bank_reset_impl(SSBank* b, hipStream_t st, int stream, std::string& err);
+int  ss_bank_update_check_impl(int n_frames, const float* d_rows, const int* d_nrows, const float* d_feats, std::string& err);
+int  ss_bank_update_impl(SSBank* b, hipStream_t st, int n_frames, const float* d_rows, const int* d_nrows, const float* d_feats, std::string& err);
+int  ss_bank_pending_impl(SSBank* b, hipStream_t st, std::string& err);
+int  ss_bank_get_impl(SSBank* b, hipStream_t st, int stream, int cap, int* n, int* ids, int* counts, int* first, int* last, int* cls, float* desc,
+                      std::string& err);
+void ss_bank_free(SSBank* b);
+int  ss_mtmc_link_check_impl(int T, const float* desc, const int* cam, const int* first, const int* last, const int* n, double thr, int min_rows,
+                             const int* global_id, const double* merges, const int* n_merges, std::string& err);
+int  ss_mtmc_link_impl(SSMtmc** pg, hipStream_t st, int T, const float* desc, const int* cam, const int* first, const int* last, const int* n, double thr,
+                       int min_rows, int* global_id, double* merges, int* n_merges, float* dist_out, std::string& err);
+void ss_mtmc_free(SSMtmc* g);
+
 // ---- ss_slice.hip
 struct SSSlice;
 int  ss_slice_max_tiles_impl();

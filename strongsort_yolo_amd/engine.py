@@ -374,6 +374,60 @@ class TrackerEngine:
                                            addr(heat), int(heat_frame_stride), addr(maxes), int(max_stride), int(alpha)))
         return frames
 
+    # ---- identities across cameras (csrc/ss_mtmc.hip, docs/MTMC.md); mtmc.TrackBank and mtmc.link are the front of these ----
+    def bank_create(self, max_ids: int = 4096):
+        """One descriptor table per stream of the context for the track ids 1..max_ids (4 KiB an id and stream); a second call
+        replaces it."""
+        self._ck(self.L.ss_bank_create(self.ctx, int(max_ids)))
+
+    def bank_destroy(self):
+        self._ck(self.L.ss_bank_destroy(self.ctx))
+
+    def bank_reset(self, stream: int = -1):
+        self._ck(self.L.ss_bank_reset(self.ctx, int(stream)))
+
+    def bank_update_group(self, n_frames, rows, counts, feats):
+        """One launch for n_frames (<= 32) frames of every stream: rows [F,S,256,8] f32 and counts [F,S] i32 as a tracker's
+        update_group leaves them and feats [F,S,128,512] f32, the raw features that call read (device tensors, read in place).
+        Asynchronous on the engine's stream, behind a detached tracker chain."""
+        self._ck(self.L.ss_bank_update_group(self.ctx, int(n_frames), _ptr(rows), _ptr(counts), _ptr(feats)))
+
+    def bank_get(self, stream: int = 0) -> dict:
+        """Synchronous: the stream's table (the keys of tests/mtmc_ref.py's Bank.table()): ids, n, first, last, cls int32 [m] in
+        rising id order and desc float32 [m, 512]."""
+        pi = C.POINTER(C.c_int)
+        m = C.c_int(0)
+        self._ck(self.L.ss_bank_get(self.ctx, int(stream), 0, C.byref(m), None, None, None, None, None, None))
+        k = m.value
+        t = {name: np.zeros(max(k, 1), np.int32) for name in ("ids", "n", "first", "last", "cls")}
+        desc = np.zeros((max(k, 1), FEAT_DIM), np.float32)
+        if k:
+            self._ck(self.L.ss_bank_get(self.ctx, int(stream), k, C.byref(m), *(t[name].ctypes.data_as(pi) for name in ("ids", "n", "first", "last", "cls")),
+                                        desc.ctypes.data_as(C.POINTER(C.c_float))))
+            if m.value != k:
+                raise _lib.SSError(_lib.SS_ERR_INVALID, f"bank_get: {k} ids counted, {m.value} written")
+        return dict({name: v[:k] for name, v in t.items()}, desc=desc[:k])
+
+    def mtmc_link(self, desc, cam, first, last, n, thr: float, min_rows: int = 1, want_dist: bool = False):
+        """Distances, constraints and constrained average-linkage clustering of T tracklets (host arrays: desc [T, 512] float32 unit
+        rows; cam, first, last, n [T]) -> (global_id int32 [T], merges float64 [m, 3] = (a, b, height)) and, with want_dist, the
+        float32 distances [T, T] (i < j; zero elsewhere).  Synchronous, on the engine's stream."""
+        desc = np.ascontiguousarray(desc, np.float32)
+        cam, first, last, n = (np.ascontiguousarray(v, np.int32).reshape(-1) for v in (cam, first, last, n))
+        T = len(cam)
+        if desc.shape != (T, FEAT_DIM) or len(first) != T or len(last) != T or len(n) != T:
+            raise ValueError(f"mtmc_link: desc [T, {FEAT_DIM}], cam, first, last, n [T]")
+        k = max(T, 1)
+        gid, merges, nm = np.zeros(k, np.int32), np.zeros((k, 3), np.float64), C.c_int(0)
+        dist = np.zeros((min(k, int(self.L.ss_mtmc_max_tracklets())),) * 2, np.float32) if want_dist else None
+        pi = C.POINTER(C.c_int)
+        self._ck(self.L.ss_mtmc_link(self.ctx, T, desc.ctypes.data_as(C.POINTER(C.c_float)), cam.ctypes.data_as(pi), first.ctypes.data_as(pi),
+                                     last.ctypes.data_as(pi), n.ctypes.data_as(pi), float(thr), int(min_rows), gid.ctypes.data_as(pi),
+                                     merges.ctypes.data_as(C.POINTER(C.c_double)), C.byref(nm),
+                                     dist.ctypes.data_as(C.POINTER(C.c_float)) if want_dist else None))
+        out = (gid[:T], merges[:nm.value].copy())
+        return out + (dist,) if want_dist else out
+
     def update_device(self, dets, ndets, feats, img_hw, out=None, nout=None):
         """All streams, one frame; tensors live on the device ([S,128,6] f32, [S] i32, [S,128,512] f32,
         [S,2] i32).  Asynchronous; returns (rows [S,256,8], counts [S]) device tensors (default: self.out, self.nout)."""

@@ -40,7 +40,8 @@ class FramePipeline:
                  dcfg: Optional[DetectConfig] = None, det_source: str = "detector", feat_source: str = "reid",
                  graph: str = "all", debug: bool = False, run_nets: bool = True, seed: int = 0, detect_only_rows: int = 0, cmc: bool = False,
                  reid_half: Optional[bool] = None, crops_u8: bool = True, tracker: str = "strongsort", with_reid: bool = False,
-                 reid_model: str = "osnet", with_pose: bool = False, gmc_method: str = "ecc", ocsort_use_byte: bool = False, slice_cfg=None):
+                 reid_model: str = "osnet", with_pose: bool = False, gmc_method: str = "ecc", ocsort_use_byte: bool = False, slice_cfg=None,
+                 track_bank: bool = False, bank_max_ids: int = 4096):
         self.cfg, self.dcfg = cfg or StrongSortConfig(), dcfg or DetectConfig()
         self.S, (self.H, self.W) = n_streams, frame_hw
         # tracker = "bytetrack" / "botsort": the BYTE tracker family (csrc/ss_byte.hip) on IoU and scores — no OSNet is built, no
@@ -61,8 +62,16 @@ class FramePipeline:
         # slice_cfg (slicing.SliceConfig): sliced inference (csrc/ss_slice.hip, docs/SLICE.md) — the detector sees T tiles of every frame
         # (S * T images: lb, pred_in and the per-tile NMS rows carry that leading dimension), one launch letterboxes them, one launch
         # merges the tiles' rows into b.dets / b.ndets; from there on nothing differs.  None: nothing of it is allocated or launched.
+        # track_bank: one pooled appearance descriptor per track id, kept on the device behind every tracker call (csrc/ss_mtmc.hip,
+        # docs/MTMC.md): one more launch per call that reads the rows and the features where they are.  Off: nothing is allocated or launched.
         from .config import byte_config, ocsort_config, deep_ocsort_config, check_reid_model, check_pose, check_gmc_method
         self.slice = slice_cfg
+        self.bank = None
+        if track_bank and not detect_only_rows:
+            from .mtmc import bank_refusal
+            why = bank_refusal(tracker, with_reid, reid_model, detector.lower().replace(".pt", "") in nets.OBB_DETECTORS)
+            if why:
+                raise ValueError(f"track_bank: {why}")
         # an oriented-box model (docs/OBB.md §5): one angle row behind the class scores, the rotated NMS, 11-column rows (nx = 5), and
         # the BYTE family on ProbIoU; what is not built for rotated boxes is refused by name before anything is allocated
         self.ne = 1 if detector.lower().replace(".pt", "") in nets.OBB_DETECTORS else 0
@@ -98,6 +107,9 @@ class FramePipeline:
         elif self.deep_cfg is not None:
             from .engine import DeepOCSortEngine
             self.byte = self.trk = DeepOCSortEngine(self.deep_cfg, engine=self.eng)
+        if track_bank and not detect_only_rows:
+            from .mtmc import TrackBank
+            self.bank = TrackBank(self.eng, bank_max_ids)
         dev = self.dev = self.eng.device
         self.half, self.dtype = half, torch.float16 if half else torch.float32
         # reid_half=False: the ReID crops and OSNet in fp32 on the hand-written fp32 kernels (fused32.py, csrc/ss_ops32.hip:
@@ -327,6 +339,8 @@ class FramePipeline:
         b = self.b
         self.trk.update_device(b.dets if self.ne else b.dets6, b.ndets, b.feats_v, self.img_hw, out=self.out, nout=self.nout,
                                **self._pose_kw(b, 0, self.Sv))
+        if self.bank is not None:
+            self.bank.update_group_device(self.out, self.nout, b.feats_v, 1)
 
     def _pose_kw(self, b, v0, v1):
         """with_pose: the NMS rows of virtual streams [v0, v1) as the tracker call's keypoints (their columns from 6, network-input
@@ -340,6 +354,8 @@ class FramePipeline:
         self.eng.reset(stream)
         if self.byte is not None:
             self.byte.reset(stream)
+        if self.bank is not None:
+            self.bank.reset(stream)
 
     def _warm_and_capture(self, warm, captures, tracks: bool = True):
         """Warm `warm` (callables) up on a side stream (MIOpen find, allocator), three eager passes, then capture one HIP graph per
@@ -648,8 +664,12 @@ class OverlappedPipeline(FramePipeline):
                 continue
             e.update_group(n, b.dets6[v0:v1], b.ndets[v0:v1], b.feats_v[v0:v1], self.img_hw, self.outs[f0:f0 + n], self.nouts[f0:f0 + n],
                            **self._pose_kw(b, v0, v1))
+            if self.bank is not None:                           # the same slices, behind the rows (the library joins a detached chain first)
+                self.bank.update_group_device(self.outs[f0:f0 + n], self.nouts[f0:f0 + n], b.feats_v[v0:v1], n)
         if self.sR is not None:                                 # detached chain: the rows exist once the chain's stream is done
             self.eng.track_join(self.sR)
+            if self.bank is not None:                           # the set is released on sR: not before the bank has read its features
+                self.sR.wait_stream(torch.cuda.current_stream(self.dev))
         if group is not None and self.on_result is not None:
             self.cur_bufs, self.cur_valid = b, nv               # the buffer set / real-frame count the callbacks below refer to
             with torch.cuda.stream(self.sR if self.sR is not None else torch.cuda.current_stream(self.dev)):

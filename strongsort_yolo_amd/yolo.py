@@ -343,7 +343,8 @@ class YOLO:
                  camera_motion: bool = False, reid_weights: Optional[str] = None, reid_fp32: bool = True, half: bool = True,
                  device_masks: bool = False, tracker_type: str = "strongsort", with_reid: bool = False, reid_model: str = "osnet",
                  with_pose: bool = False, gmc_method: str = "ecc", ocsort_use_byte: bool = False, slice_hw=None, slice_overlap=0.2,
-                 slice_full: bool = True, slice_merge: str = "nmm", slice_metric: str = "ios", slice_thr: float = 0.5):
+                 slice_full: bool = True, slice_merge: str = "nmm", slice_metric: str = "ios", slice_thr: float = 0.5,
+                 track_bank: bool = False):
         """reid_fp32 (default since round 6): ReID crops + OSNet-x0.25 in fp32 on the fp32 kernels — appearance distances within 1e-4 of a CPU fp32
         network, which f16 activations miss by 330x (reid_fp32=False: the f16 throughput mode, ~1.2x the per-frame rate, 1.7x the stream rate).
         half=False: the DETECTOR in fp32 as well (the reference's own precision: it passes no half=, yolo_multi_model.py:41) on the
@@ -380,7 +381,11 @@ class YOLO:
         batch (slice_overlap: one ratio or (oh, ow); slice_full: the whole frame as one more tile) and the tiles' rows are merged on the
         device (slice_merge "nmm" = GREEDYNMM or "nms", slice_metric "ios" or "iou", slice_thr); predict, track and track_stream then
         see small objects at the tiles' scale.  The detector costs T times as much.  Segmentation models and reid_model="auto" are
-        ValueErrors, as are more than 64 tiles; the slice must fit the frame (checked when the first frame arrives)."""
+        ValueErrors, as are more than 64 tiles; the slice must fit the frame (checked when the first frame arrives).
+        track_bank: track() and track_stream() also keep, on the device, one pooled OSNet descriptor per track id (docs/MTMC.md): the
+        table `model.track_bank()` returns and `mtmc.link` links across cameras.  It needs a tracker that reads OSNet features
+        ("strongsort", "deep_ocsort", or "botsort" with with_reid and reid_model "osnet"); anything else is a ValueError.  Default
+        False: nothing changes."""
         self.slice = None
         if slice_hw is not None:
             from .slicing import SliceConfig
@@ -449,6 +454,13 @@ class YOLO:
                 self._pipe_kw["ocsort_use_byte"] = True
         if self.slice is not None:
             self._pipe_kw["slice_cfg"] = self.slice
+        self._track_bank, self._bank_pipe = bool(track_bank), None
+        if self._track_bank:
+            from .mtmc import bank_refusal
+            why = bank_refusal(tracker_type, with_reid, reid_model, self._obb)
+            if why:
+                raise ValueError(f"track_bank=True: {why}")
+            self._pipe_kw["track_bank"] = True
         self.device_masks = bool(device_masks)
         self._fill = None
         self._frame_index = 0
@@ -528,6 +540,8 @@ class YOLO:
         if self._fill is not None:
             self._fill(pipe, 0, self._frame_index)
         pipe.step(track=track)
+        if track:
+            self._bank_pipe = pipe
         h = self._host[slot]
         h.fetch(self, pipe, 1, pipe.out if track else None, pipe.nout if track else None, packed=not wide,
                 rbox=pipe.byte.rbox if track and pipe.ne else None)
@@ -700,6 +714,7 @@ class YOLO:
                                    reid_split=(5 if self.arch == "yolov8n" else 2) if batch > 1 else None, defer_track=batch > 1)     # stage cut: bench.REID_SPLIT's sweep
         finally:
             self._conf_track = None
+        self._bank_pipe = pipe
         pipe.on_result = None
         pipe.flush()                                                      # groups an abandoned generator left in flight: tracked, results dropped
         F = batch
@@ -763,6 +778,17 @@ class YOLO:
         finally:
             pipe.on_result = None
 
+    def track_bank(self, stream: int = 0):
+        """The track bank's table of the pipeline that tracked last (track_bank=True): ids, n, first, last, cls int32 [m] in rising id
+        order and desc float32 [m, 512] (docs/MTMC.md).  Synchronous."""
+        if not self._track_bank:
+            raise RuntimeError("track_bank(): build the model with track_bank=True")
+        pipe = self._bank_pipe
+        if pipe is None or pipe.bank is None:
+            raise RuntimeError("track_bank(): run track() or track_stream() once first (the bank lives in the tracking pipeline)")
+        torch.cuda.synchronize(pipe.dev)
+        return pipe.bank.table(stream)
+
     def overlay(self):
         """Annotation overlay bound to this model's device context (drawing of yolo_multi_model.py:58-162 as a kernel)."""
         from .overlay import Overlay
@@ -775,5 +801,5 @@ class YOLO:
         for p in (self._pipe, self._stream_pipe, self._pred_pipe):
             if p is not None:
                 p.close()
-        self._pipe = self._stream_pipe = self._pred_pipe = None
+        self._pipe = self._stream_pipe = self._pred_pipe = self._bank_pipe = None
         self._host = {}
