@@ -4,7 +4,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <vector>
 #include "ss_common.h"
 #include "ss_host.h"
@@ -70,15 +69,9 @@ struct ss_ctx {
     hipStream_t chain_stream;
     hipEvent_t ev_head, ev_chain;
     bool chain_pending;
-    // the BYTE tracker family (ss_byte_create), NULL until attached
-    struct Byte { SSByteDev dev; ss_byte_config cfg; std::vector<void*> allocs; };
-    Byte* byte = nullptr;
-    // the OC-SORT tracker (ss_ocsort_create), NULL until attached
-    struct Oc { SSOcDev dev; std::vector<void*> allocs; };
-    Oc* oc = nullptr;
-    // the Deep OC-SORT tracker (ss_deepoc_create), NULL until attached
-    struct DeepOc { SSDeepOcDev dev; std::vector<void*> allocs; };
-    DeepOc* deepoc = nullptr;
+    SSByte* byte = nullptr;     // the BYTE tracker family (ss_byte_create), NULL until attached
+    SSOc* oc = nullptr;         // the OC-SORT tracker (ss_ocsort_create), NULL until attached
+    SSDeepOc* deepoc = nullptr; // the Deep OC-SORT tracker (ss_deepoc_create), NULL until attached
     SSJpeg* jpeg = nullptr;     // ss_jpeg_decode_batch's staging areas and planes, made by its first call
     SSJpegEnc* jpeg_enc = nullptr;   // ss_jpeg_encode_batch's buffers, made by its first call
     SSGsi* gsi = nullptr;       // ss_gsi_smooth's staging and scratch slots, made by its first call
@@ -237,9 +230,9 @@ extern "C" void ss_destroy(ss_ctx* c)
     if (c->ev_head) (void)hipEventDestroy(c->ev_head);
     if (c->ev_chain) (void)hipEventDestroy(c->ev_chain);
     for (void* p : c->allocs) (void)hipFree(p);
-    if (c->byte) { for (void* p : c->byte->allocs) (void)hipFree(p); delete c->byte; }
-    if (c->oc) { for (void* p : c->oc->allocs) (void)hipFree(p); delete c->oc; }
-    if (c->deepoc) { for (void* p : c->deepoc->allocs) (void)hipFree(p); delete c->deepoc; }
+    ss_byte_free(c->byte);
+    ss_ocsort_free(c->oc);
+    ss_deepoc_free(c->deepoc);
     ss_jpeg_free(c->jpeg);
     ss_jpeg_enc_free(c->jpeg_enc);
     ss_gsi_free(c->gsi);
@@ -481,6 +474,47 @@ static int post_run(ss_ctx* c, const char* entry, Check check, Work work)
     } catch (...) {
         return fail(c, SS_ERR_INVALID, std::string(entry) + ": out of memory");
     }
+}
+
+// The checks an entry of an attached stage (the zones, the bank, a tracker family) makes after its own arguments: a context, the
+// stage's state (have_state), a stream of it.  what: the state and the entry that makes it, said after "no ".  one_wording (the
+// trackers' reset and get entries): a missing context and a bad stream read "no <what>" as well.
+static int stage_state(ss_ctx* c, const char* entry, bool have_state, const char* what, int stream, bool need_stream, std::string& err,
+                       bool one_wording = false)
+{
+    const std::string who = std::string(entry) + ": ";
+    const bool bad_stream = c && (stream >= c->dev.S || (need_stream && stream < 0));
+    if (one_wording ? (!have_state || bad_stream) : (c && !have_state)) { err = who + "no " + what; return SS_ERR_INVALID; }
+    if (!c) { err = who + "null context"; return SS_ERR_INVALID; }
+    if (bad_stream) { err = who + "stream " + std::to_string(stream) + " out of range"; return SS_ERR_INVALID; }
+    return SS_OK;
+}
+
+// A create entry of an attached stage: check(err) on its arguments; then a context with nothing of the state the call replaces still
+// in flight, that state freed (a failure leaves none attached), and make(err)
+template <class State, class Check, class Make>
+static int create_run(ss_ctx* c, const char* entry, State* ss_ctx::*state, void (*release)(State*), Check check, Make make)
+{
+    return post_run(c, entry, check, [&](std::string& err) {
+        if (!c) { err = std::string(entry) + ": null context"; return (int)SS_ERR_INVALID; }
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { err = std::string(entry) + ": " + hipGetErrorString(e); return (int)SS_ERR_HIP; }
+        release(c->*state);
+        c->*state = nullptr;
+        return make(err);
+    });
+}
+
+// What a destroy entry of an attached stage does: the stream drains, the state goes
+template <class State>
+static int stage_destroy(ss_ctx* c, const char* entry, State* ss_ctx::*state, void (*release)(State*))
+{
+    if (!c) return fail(nullptr, SS_ERR_INVALID, std::string(entry) + ": null context");
+    if (!(c->*state)) return SS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    release(c->*state);
+    c->*state = nullptr;
+    return SS_OK;
 }
 
 // ---- GSI post-processing (ss_gsi.hip, docs/GSI.md) ------------------------------------------------------------
@@ -1034,36 +1068,14 @@ extern "C" int ss_check_errors(ss_ctx* c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (size_t s = 0; s < e.size(); ++s)
         if (e[s]) return fail(c, e[s], "device error flag on stream " + std::to_string(s));
-    if (c->byte) {                                           // the BYTE tracker's flags (capacity, infeasible)
-        HIPCHK(c, hipMemcpyAsync(e.data(), c->byte->dev.err, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (size_t s = 0; s < e.size(); ++s)
-            if (e[s]) return fail(c, e[s], "BYTE tracker: device error flag on stream " + std::to_string(s));
-    }
-    if (c->oc) {                                             // OC-SORT's flags (capacity, infeasible)
-        HIPCHK(c, hipMemcpyAsync(e.data(), c->oc->dev.err, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (size_t s = 0; s < e.size(); ++s)
-            if (e[s]) return fail(c, e[s], "OC-SORT tracker: device error flag on stream " + std::to_string(s));
-    }
-    if (c->deepoc) {                                             // Deep OC-SORT's flags
-        HIPCHK(c, hipMemcpyAsync(e.data(), c->deepoc->dev.oc.err, e.size() * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (size_t s = 0; s < e.size(); ++s)
-            if (e[s]) return fail(c, e[s], "Deep OC-SORT tracker: device error flag on stream " + std::to_string(s));
-    }
-    {                                                        // the analytics stage's flags (more live tracks than its table holds)
-        std::string err;
-        if (int rcz = ss_zone_pending_impl(c->zone, c->stream, err)) return fail(c, rcz, err);
-    }
-    {                                                        // the track bank's flags (an id above its max_ids)
-        std::string err;
-        if (int rcb = ss_bank_pending_impl(c->bank, c->stream, err)) return fail(c, rcb, err);
-    }
-    {                                                        // images a device-entropy JPEG call refused (docs/JPEG.md section 12)
-        std::string err;
-        if (int rcj = ss_jpeg_pending_impl(c->jpeg, err)) return fail(c, rcj, err);
-    }
+    std::string err;                                         // the attached stages' flags, each SS_OK without its state:
+    int rc = ss_byte_pending_impl(c->byte, c->stream, err);                     // the tracker families' (capacity, infeasible)
+    if (rc == SS_OK) rc = ss_ocsort_pending_impl(c->oc, c->stream, err);
+    if (rc == SS_OK) rc = ss_deepoc_pending_impl(c->deepoc, c->stream, err);
+    if (rc == SS_OK) rc = ss_zone_pending_impl(c->zone, c->stream, err);        // more live tracks than the analytics table holds
+    if (rc == SS_OK) rc = ss_bank_pending_impl(c->bank, c->stream, err);        // an id above the track bank's max_ids
+    if (rc == SS_OK) rc = ss_jpeg_pending_impl(c->jpeg, err);                   // images a device-entropy JPEG call refused (docs/JPEG.md section 12)
+    if (rc != SS_OK) return fail(c, rc, err);
     for (int u = 0; u < c->nms_units; ++u) {                 // NMS candidate overflow (flag stays set until ss_reset)
         int f = 0;
         HIPCHK(c, hipMemcpy(&f, ss_nms_error_flag(c->nms_ws, u), 4, hipMemcpyDeviceToHost));
@@ -1301,6 +1313,36 @@ extern "C" int ss_crop_norm(ss_ctx* c, const uint8_t* frame, int h, int w, int s
     return ss_crop_norm_batch(c, frame, 1, 0, h, w, stride, dets, det_stride, 0, n, d_count, out, out_flags);
 }
 
+// §1d: BoT-SORT's `model: auto` features of the kept rows from the detector's head inputs (ss_native.hip k_native_feats).  Every
+// argument is checked before the device is touched; one launch on the context's stream (capturable).
+extern "C" int ss_native_feats(ss_ctx* c, int n_img, int half, const ss_native_map* maps, int s, const int* d_keep, long long keep_stride,
+                               const int* d_counts, float* d_out)
+{
+    if (!c || !maps || !d_keep || !d_counts || !d_out) return fail(c, SS_ERR_INVALID, "ss_native_feats: null argument");
+    if (n_img < 1 || n_img > 65535 || (half != 0 && half != 1) || s < 1 || s > SS_F || keep_stride < SS_MAXD)
+        return fail(c, SS_ERR_INVALID, "ss_native_feats: 1 <= n_img <= 65535, half 0 / 1, 1 <= s <= 512, keep_stride >= 128");
+    const void* p[3];
+    long long is[3], rs[3], ps[3];
+    int ch[3], h[3], w[3];
+    long long anchors = 0;
+    const size_t esz = half ? 2 : 4;
+    for (int l = 0; l < 3; ++l) {
+        const ss_native_map& m = maps[l];
+        p[l] = m.data; is[l] = m.img_stride; rs[l] = m.row_stride; ps[l] = m.pix_stride;
+        ch[l] = m.channels; h[l] = m.height; w[l] = m.width;
+        if (!m.data || ((uintptr_t)m.data % esz) != 0) return fail(c, SS_ERR_INVALID, "ss_native_feats: a map is NULL or misaligned");
+        if (m.channels < s || m.channels % s != 0) return fail(c, SS_ERR_INVALID, "ss_native_feats: every level's channels must be a multiple of s");
+        if (m.height < 1 || m.width < 1 || m.pix_stride < m.channels || m.row_stride < (long long)m.width * m.pix_stride
+            || (n_img > 1 && m.img_stride < (long long)m.height * m.row_stride))
+            return fail(c, SS_ERR_INVALID, "ss_native_feats: bad map shape or strides (channel stride 1, maps must not overlap)");
+        anchors += (long long)m.height * m.width;
+    }
+    if (anchors > 0x7fffffffLL) return fail(c, SS_ERR_INVALID, "ss_native_feats: too many anchors");
+    ss_launch_native_feats(n_img, half, p, is, rs, ps, ch, h, w, s, d_keep, keep_stride, d_counts, d_out, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return SS_OK;
+}
+
 // ---- inspection ----------------------------------------------------------------------------------------
 extern "C" int ss_get_tracks(ss_ctx* c, int s, int cap, int* n_tracks, int* next_id, int* track_id, int* state,
                              int* hits, int* age, int* tsu, int* class_id, float* conf, double* mean,
@@ -1317,22 +1359,12 @@ extern "C" int ss_get_tracks(ss_ctx* c, int s, int cap, int* n_tracks, int* next
     if (next_id) *next_id = nid;
     if (nt > cap) return fail(c, SS_ERR_CAPACITY, "ss_get_tracks: cap too small");
     const size_t T = SS_MAXT, sb = (size_t)s * T;
-    std::vector<int> order(T), tmp(T);
+    std::vector<int> order(T);
     HIPCHK(c, hipMemcpy(order.data(), d.order + sb, T * 4, hipMemcpyDeviceToHost));
-    auto gather_i = [&](const int* src, int* dst) -> int {
-        if (!dst) return 0;
-        if (hipMemcpy(tmp.data(), src + sb, T * 4, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-        for (int i = 0; i < nt; ++i) dst[i] = tmp[order[i]];
-        return 0;
-    };
-    if (gather_i(d.track_id, track_id) || gather_i(d.state, state) || gather_i(d.hits, hits) || gather_i(d.age, age) ||
-        gather_i(d.tsu, tsu) || gather_i(d.class_id, class_id) || gather_i(d.gal_count, gal_count))
+    auto column = [&](const auto* src, auto* dst) { return ss_gather_device(order.data(), nt, src + sb, T, 1, dst) != hipSuccess; };
+    if (column(d.track_id, track_id) || column(d.state, state) || column(d.hits, hits) || column(d.age, age) || column(d.tsu, tsu) ||
+        column(d.class_id, class_id) || column(d.gal_count, gal_count) || column(d.conf, conf))
         return fail(c, SS_ERR_HIP, "ss_get_tracks: copy failed");
-    if (conf) {
-        std::vector<float> t(T);
-        HIPCHK(c, hipMemcpy(t.data(), d.conf + sb, T * 4, hipMemcpyDeviceToHost));
-        for (int i = 0; i < nt; ++i) conf[i] = t[order[i]];
-    }
     for (int i = 0; i < nt; ++i) {
         const size_t g = sb + order[i];
         if (mean) HIPCHK(c, hipMemcpy(mean + (size_t)i * 8, d.mean + g * 8, 64, hipMemcpyDeviceToHost));
@@ -1416,13 +1448,6 @@ extern "C" int ss_assoc_timeline(ss_ctx* c, long long* out, int n_workgroups)
 extern "C" int ss_slice_max_tiles(void) { return ss_slice_max_tiles_impl(); }
 extern "C" int ss_slice_max_candidates(void) { return ss_slice_max_candidates_impl(); }
 
-static int slice_state(ss_ctx* c, const char* entry, std::string& err)
-{
-    if (!c) { err = std::string(entry) + ": null context"; return SS_ERR_INVALID; }
-    if (!c->slice) { err = std::string(entry) + ": no slice state (ss_slice_config)"; return SS_ERR_INVALID; }
-    return SS_OK;
-}
-
 extern "C" int ss_slice_config(ss_ctx* c, const int* h_tiles, int n_tiles, int frame_h, int frame_w, int canvas_h, int canvas_w, int rows_per_tile,
                                int n_extra, int n_kpt, float kpt_gain, float kpt_pad_x, float kpt_pad_y)
 {
@@ -1445,7 +1470,7 @@ extern "C" int ss_slice_nms_geom(ss_ctx* c, float* d_geom, int batch)
     return post_run(c, "ss_slice_nms_geom",
         [&](std::string& err) {
             if (!d_geom || batch < 1 || batch > 65535) { err = "ss_slice_nms_geom: null output or batch outside 1..65535"; return (int)SS_ERR_INVALID; }
-            return slice_state(c, "ss_slice_nms_geom", err);
+            return stage_state(c, "ss_slice_nms_geom", c && c->slice, "slice state (ss_slice_config)", -1, false, err);
         },
         [&](std::string& err) { return ss_slice_nms_geom_impl(c->slice, d_geom, batch, err); });
 }
@@ -1456,7 +1481,7 @@ extern "C" int ss_slice_letterbox_batch(ss_ctx* c, const uint8_t* d_src, int bat
     return post_run(c, "ss_slice_letterbox_batch",
         [&](std::string& err) {
             if (int rc = ss_slice_letterbox_check_impl(d_src, batch, src_batch_stride, row_stride, d_dst, dst_flags, pad_value, err)) return rc;
-            return slice_state(c, "ss_slice_letterbox_batch", err);
+            return stage_state(c, "ss_slice_letterbox_batch", c && c->slice, "slice state (ss_slice_config)", -1, false, err);
         },
         [&](std::string& err) { return ss_slice_letterbox_impl(c->slice, c->stream, d_src, batch, src_batch_stride, row_stride, d_dst, dst_flags, pad_value, err); });
 }
@@ -1470,7 +1495,7 @@ extern "C" int ss_slice_merge(ss_ctx* c, const float* d_rows, const int* d_count
             if (int rc = ss_slice_merge_check_impl(d_rows, d_counts, batch, row_stride, tile_stride, frame_stride, mode, metric, thr, agnostic, out_cap, d_out,
                                                    out_row_stride, out_frame_stride, d_out_count, d_out_src, src_frame_stride, err))
                 return rc;
-            return slice_state(c, "ss_slice_merge", err);
+            return stage_state(c, "ss_slice_merge", c && c->slice, "slice state (ss_slice_config)", -1, false, err);
         },
         [&](std::string& err) {
             return ss_slice_merge_impl(c->slice, c->stream, d_rows, d_counts, batch, row_stride, tile_stride, frame_stride, mode, metric, thr, agnostic,
@@ -1509,44 +1534,22 @@ extern "C" int ss_assoc_timing_values(ss_ctx* c, float* out_ms, int cap, int* n)
 extern "C" int ss_bank_max_ids(void) { return ss_bank_max_ids_impl(); }
 extern "C" int ss_mtmc_max_tracklets(void) { return ss_mtmc_max_tracklets_impl(); }
 
-// the checks every ss_bank_* entry makes after its own arguments: a context, its bank, a stream of it
-static int bank_state(ss_ctx* c, const char* entry, int stream, bool need_stream, std::string& err)
-{
-    if (!c) { err = std::string(entry) + ": null context"; return SS_ERR_INVALID; }
-    if (!c->bank) { err = std::string(entry) + ": no bank (ss_bank_create)"; return SS_ERR_INVALID; }
-    if (stream >= c->dev.S || (need_stream && stream < 0)) { err = std::string(entry) + ": stream " + std::to_string(stream) + " out of range"; return SS_ERR_INVALID; }
-    return SS_OK;
-}
-
 extern "C" int ss_bank_create(ss_ctx* c, int max_ids)
 {
-    return post_run(c, "ss_bank_create",
+    return create_run(c, "ss_bank_create", &ss_ctx::bank, ss_bank_free,
         [&](std::string& err) {
             if (max_ids < 1 || max_ids > ss_bank_max_ids_impl()) { err = "ss_bank_create: max_ids " + std::to_string(max_ids) + " outside 1.." + std::to_string(ss_bank_max_ids_impl()); return (int)SS_ERR_INVALID; }
-            if (!c) { err = "ss_bank_create: null context"; return (int)SS_ERR_INVALID; }
             return (int)SS_OK;
         },
-        [&](std::string& err) {
-            hipError_t e = hipStreamSynchronize(c->stream);          // nothing of a bank this call replaces may still be in flight
-            if (e != hipSuccess) { err = std::string("ss_bank_create: ") + hipGetErrorString(e); return (int)SS_ERR_HIP; }
-            return ss_bank_create_impl(&c->bank, c->stream, c->dev.S, max_ids, err);
-        });
+        [&](std::string& err) { return ss_bank_create_impl(&c->bank, c->stream, c->dev.S, max_ids, err); });
 }
 
-extern "C" int ss_bank_destroy(ss_ctx* c)
-{
-    if (!c) return fail(nullptr, SS_ERR_INVALID, "ss_bank_destroy: null context");
-    if (!c->bank) return SS_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    ss_bank_free(c->bank);
-    c->bank = nullptr;
-    return SS_OK;
-}
+extern "C" int ss_bank_destroy(ss_ctx* c) { return stage_destroy(c, "ss_bank_destroy", &ss_ctx::bank, ss_bank_free); }
 
 extern "C" int ss_bank_reset(ss_ctx* c, int stream)
 {
     return post_run(c, "ss_bank_reset",
-        [&](std::string& err) { return bank_state(c, "ss_bank_reset", stream, false, err); },
+        [&](std::string& err) { return stage_state(c, "ss_bank_reset", c && c->bank, "bank (ss_bank_create)", stream, false, err); },
         [&](std::string& err) { return ss_bank_reset_impl(c->bank, c->stream, stream, err); });
 }
 
@@ -1555,7 +1558,7 @@ extern "C" int ss_bank_update_group(ss_ctx* c, int n_frames, const float* d_rows
     return post_run(c, "ss_bank_update_group",
         [&](std::string& err) {
             if (int rc = ss_bank_update_check_impl(n_frames, d_rows, d_nrows, d_feats, err)) return rc;
-            return bank_state(c, "ss_bank_update_group", -1, false, err);
+            return stage_state(c, "ss_bank_update_group", c && c->bank, "bank (ss_bank_create)", -1, false, err);
         },
         [&](std::string& err) {
             if (int rc = chain_join(c, c->stream)) { err = c->err; return rc; }     // the rows of a detached tracker chain exist first
@@ -1568,7 +1571,7 @@ extern "C" int ss_bank_get(ss_ctx* c, int stream, int cap, int* n, int* ids, int
     return post_run(c, "ss_bank_get",
         [&](std::string& err) {
             if (!n || cap < 0 || (cap > 0 && (!ids || !counts || !first || !last || !cls || !desc))) { err = "ss_bank_get: null argument or negative cap"; return (int)SS_ERR_INVALID; }
-            return bank_state(c, "ss_bank_get", stream, true, err);
+            return stage_state(c, "ss_bank_get", c && c->bank, "bank (ss_bank_create)", stream, true, err);
         },
         [&](std::string& err) { return ss_bank_get_impl(c->bank, c->stream, stream, cap, n, ids, counts, first, last, cls, desc, err); });
 }
@@ -1588,41 +1591,19 @@ extern "C" int ss_zone_max_zones(void) { return ss_zone_max_zones_impl(); }
 extern "C" int ss_zone_max_vertices(void) { return ss_zone_max_vertices_impl(); }
 extern "C" int ss_zone_max_live(void) { return ss_zone_max_live_impl(); }
 
-// the checks every ss_zone_* entry makes after its own arguments: a context, its zone state, a stream of it
-static int zone_state(ss_ctx* c, const char* entry, int stream, bool need_stream, std::string& err)
-{
-    if (!c) { err = std::string(entry) + ": null context"; return SS_ERR_INVALID; }
-    if (!c->zone) { err = std::string(entry) + ": no zone state (ss_zone_create)"; return SS_ERR_INVALID; }
-    if (stream >= c->dev.S || (need_stream && stream < 0)) { err = std::string(entry) + ": stream " + std::to_string(stream) + " out of range"; return SS_ERR_INVALID; }
-    return SS_OK;
-}
-
 extern "C" int ss_zone_create(ss_ctx* c, const ss_zone_config* cfg, const int* lines, int n_lines, const int* poly_xy, const int* poly_off, int n_zones)
 {
-    return post_run(c, "ss_zone_create",
+    return create_run(c, "ss_zone_create", &ss_ctx::zone, ss_zone_free,
         [&](std::string& err) { return ss_zone_create_check_impl(cfg, lines, n_lines, poly_xy, poly_off, n_zones, err); },
-        [&](std::string& err) {
-            if (!c) { err = "ss_zone_create: null context"; return (int)SS_ERR_INVALID; }
-            hipError_t e = hipStreamSynchronize(c->stream);          // nothing of a state this call replaces may still be in flight
-            if (e != hipSuccess) { err = std::string("ss_zone_create: ") + hipGetErrorString(e); return (int)SS_ERR_HIP; }
-            return ss_zone_create_impl(&c->zone, c->stream, c->dev.S, cfg, lines, n_lines, poly_xy, poly_off, n_zones, err);
-        });
+        [&](std::string& err) { return ss_zone_create_impl(&c->zone, c->stream, c->dev.S, cfg, lines, n_lines, poly_xy, poly_off, n_zones, err); });
 }
 
-extern "C" int ss_zone_destroy(ss_ctx* c)
-{
-    if (!c) return fail(nullptr, SS_ERR_INVALID, "ss_zone_destroy: null context");
-    if (!c->zone) return SS_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    ss_zone_free(c->zone);
-    c->zone = nullptr;
-    return SS_OK;
-}
+extern "C" int ss_zone_destroy(ss_ctx* c) { return stage_destroy(c, "ss_zone_destroy", &ss_ctx::zone, ss_zone_free); }
 
 extern "C" int ss_zone_reset(ss_ctx* c, int stream)
 {
     return post_run(c, "ss_zone_reset",
-        [&](std::string& err) { return zone_state(c, "ss_zone_reset", stream, false, err); },
+        [&](std::string& err) { return stage_state(c, "ss_zone_reset", c && c->zone, "zone state (ss_zone_create)", stream, false, err); },
         [&](std::string& err) { return ss_zone_reset_impl(c->zone, c->stream, stream, err); });
 }
 
@@ -1632,7 +1613,7 @@ extern "C" int ss_zone_update_group(ss_ctx* c, int n_frames, const float* d_rows
     return post_run(c, "ss_zone_update_group",
         [&](std::string& err) {
             if (int rc = ss_zone_update_check_impl(n_frames, d_rows, d_nrows, err)) return rc;
-            return zone_state(c, "ss_zone_update_group", -1, false, err);
+            return stage_state(c, "ss_zone_update_group", c && c->zone, "zone state (ss_zone_create)", -1, false, err);
         },
         [&](std::string& err) {
             return ss_zone_update_impl(c->zone, c->stream, n_frames, d_rows, d_nrows, d_events, d_inside, d_dwell, d_line_totals, d_occupancy,
@@ -1644,7 +1625,7 @@ extern "C" int ss_zone_get_totals(ss_ctx* c, int stream, int* frames, int* line_
                                   long long* zone_dwell_sum, int* zone_longest, int* zone_peak, int* heat_max)
 {
     return post_run(c, "ss_zone_get_totals",
-        [&](std::string& err) { return zone_state(c, "ss_zone_get_totals", stream, true, err); },
+        [&](std::string& err) { return stage_state(c, "ss_zone_get_totals", c && c->zone, "zone state (ss_zone_create)", stream, true, err); },
         [&](std::string& err) {
             return ss_zone_get_totals_impl(c->zone, c->stream, stream, frames, line_class, line_totals, zone_entries, zone_exits, zone_dwell_sum,
                                            zone_longest, zone_peak, heat_max, err);
@@ -1656,7 +1637,7 @@ extern "C" int ss_zone_get_heat(ss_ctx* c, int stream, int* grid, int cap, int* 
     return post_run(c, "ss_zone_get_heat",
         [&](std::string& err) {
             if (!gh || !gw || cap < 0 || (cap > 0 && !grid)) { err = "ss_zone_get_heat: null argument or negative cap"; return (int)SS_ERR_INVALID; }
-            return zone_state(c, "ss_zone_get_heat", stream, true, err);
+            return stage_state(c, "ss_zone_get_heat", c && c->zone, "zone state (ss_zone_create)", stream, true, err);
         },
         [&](std::string& err) {
             int S, heat, h, w;
@@ -1673,7 +1654,7 @@ extern "C" int ss_zone_heat_device(ss_ctx* c, int stream, void** d_heat, void** 
     return post_run(c, "ss_zone_heat_device",
         [&](std::string& err) {
             if (!d_heat || !d_max) { err = "ss_zone_heat_device: null argument"; return (int)SS_ERR_INVALID; }
-            return zone_state(c, "ss_zone_heat_device", stream, true, err);
+            return stage_state(c, "ss_zone_heat_device", c && c->zone, "zone state (ss_zone_create)", stream, true, err);
         },
         [&](std::string&) { ss_zone_heat_device_impl(c->zone, stream, d_heat, d_max); return (int)SS_OK; });
 }
@@ -1683,7 +1664,7 @@ extern "C" int ss_zone_set_colormap(ss_ctx* c, const uint8_t* bgr_256x3)
     return post_run(c, "ss_zone_set_colormap",
         [&](std::string& err) {
             if (!bgr_256x3) { err = "ss_zone_set_colormap: null table"; return (int)SS_ERR_INVALID; }
-            return zone_state(c, "ss_zone_set_colormap", -1, false, err);
+            return stage_state(c, "ss_zone_set_colormap", c && c->zone, "zone state (ss_zone_create)", -1, false, err);
         },
         [&](std::string& err) { return ss_zone_set_colormap_impl(c->zone, bgr_256x3, err); });
 }
@@ -1695,7 +1676,7 @@ extern "C" int ss_zone_heat_blend(ss_ctx* c, void* hip_stream, uint8_t* d_frames
         [&](std::string& err) {
             if (int rc = ss_zone_blend_check_impl(d_frames, batch, frame_batch_stride, h, w, row_stride, d_heat, heat_frame_stride, d_max, max_stride, alpha, err))
                 return rc;
-            return zone_state(c, "ss_zone_heat_blend", -1, false, err);
+            return stage_state(c, "ss_zone_heat_blend", c && c->zone, "zone state (ss_zone_create)", -1, false, err);
         },
         [&](std::string& err) {
             return ss_zone_blend_impl(c->zone, (hipStream_t)hip_stream, d_frames, batch, frame_batch_stride, h, w, row_stride, d_heat, heat_frame_stride,
@@ -1703,668 +1684,246 @@ extern "C" int ss_zone_heat_blend(ss_ctx* c, void* hip_stream, uint8_t* d_frames
         });
 }
 
-// ---- OC-SORT (ss_ocsort.hip, docs/OCSORT.md) ---------------------------------------------------------------------------------------
-extern "C" int ss_ocsort_destroy(ss_ctx* c)
+// ---- the tracker families: BYTE (ss_byte.hip), OC-SORT (ss_ocsort.hip), Deep OC-SORT (ss_deepoc.hip) --------------------------------
+// Each family's state, tables, reset and read-back live beside its kernels; include/strongsort_hip.h says what each entry does.
+// An entry that needs the state: ok (it is there and the entry's own arguments are sound) and the stream, all worded "no <what>".
+template <class Work>
+static int tracker_run(ss_ctx* c, const char* entry, bool ok, const char* what, int stream, bool need_stream, Work work)
 {
-    if (!c) return fail(nullptr, SS_ERR_INVALID, "ss_ocsort_destroy: null context");
-    if (!c->oc) return SS_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (void* p : c->oc->allocs) HIPCHK(c, hipFree(p));
-    delete c->oc;
-    c->oc = nullptr;
-    return SS_OK;
+    return post_run(c, entry, [&](std::string& err) { return stage_state(c, entry, ok, what, stream, need_stream, err, true); }, work);
 }
 
-// the streams' lists, counters and error words of an OC-SORT state (OC-SORT's own or Deep OC-SORT's) restart
-static int oc_reset_state(ss_ctx* c, SSOcDev& o, int stream)
+static int invalid(std::string& err, const char* entry, const char* why) { err = std::string(entry) + ": " + why; return SS_ERR_INVALID; }
+
+// An update entry: its arguments, a context that has the family's state, then launch(err): the mode's own checks and its launches on
+// the context's stream.  Nothing else touches the device: capturable.
+template <class Launch>
+static int update_run(ss_ctx* c, const char* entry, bool pointers, int n_frames, bool have_state, const char* what, Launch launch)
 {
-    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? o.S : stream + 1;
-    std::vector<int> ones(o.S, 1);
-    HIPCHK(c, hipMemsetAsync(o.frame + s0, 0, (s1 - s0) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(o.err + s0, 0, (s1 - s0) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(o.n_trk + s0, 0, (s1 - s0) * 4, c->stream));
-    HIPCHK(c, hipMemcpyAsync(o.next_id + s0, ones.data(), (s1 - s0) * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SS_OK;
+    return post_run(c, entry,
+        [&](std::string& err) {
+            if (!pointers) return invalid(err, entry, "null argument");
+            if (n_frames < 1 || n_frames > SS_FMAX) return invalid(err, entry, "1 <= n_frames <= SS_FMAX");
+            return stage_state(c, entry, have_state, what, -1, false, err);
+        },
+        [&](std::string& err) {
+            if (int rc = launch(err)) return rc;
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) { err = std::string(entry) + ": " + hipGetErrorString(e); return (int)SS_ERR_HIP; }
+            return (int)SS_OK;
+        });
+}
+
+static SsWarpFlags warp_flags(ss_ctx* c) { return {c->cmc_prev_valid, c->gmc.prev_valid}; }      // what a BYTE or Deep OC-SORT restart clears
+
+// ---- OC-SORT (docs/OCSORT.md)
+static const char *const OC_STATE = "OC-SORT state (ss_ocsort_create)", *const OC_OR_STREAM = "OC-SORT state or bad stream";
+
+extern "C" int ss_ocsort_destroy(ss_ctx* c) { return stage_destroy(c, "ss_ocsort_destroy", &ss_ctx::oc, ss_ocsort_free); }
+
+extern "C" int ss_ocsort_create(ss_ctx* c, const ss_ocsort_config* cfg)
+{
+    return create_run(c, "ss_ocsort_create", &ss_ctx::oc, ss_ocsort_free, [&](std::string& err) { return ss_ocsort_create_check_impl(cfg, err); },
+                      [&](std::string& err) { return ss_ocsort_create_impl(&c->oc, c->stream, c->dev.S, cfg, err); });
 }
 
 extern "C" int ss_ocsort_reset(ss_ctx* c, int stream)
 {
-    if (!c || !c->oc || stream >= c->dev.S) return fail(c, SS_ERR_INVALID, "ss_ocsort_reset: no OC-SORT state or bad stream");
-    return oc_reset_state(c, c->oc->dev, stream);
-}
-
-// the tables of an OC-SORT state (o.S set), zeroed; every allocation is recorded in allocs, also when a later one fails
-static int oc_alloc_state(ss_ctx* c, SSOcDev& o, std::vector<void*>& allocs, const char* fn)
-{
-    const size_t S = o.S, T = SS_MAXT;
-    int rc = SS_OK;
-    auto al = [&](auto** p, size_t n) {
-        if (rc != SS_OK) return;
-        void* q = nullptr;
-        const size_t bytes = n * sizeof(**p);
-        hipError_t e = hipMalloc(&q, bytes);
-        if (e == hipSuccess) { allocs.push_back(q); e = hipMemsetAsync(q, 0, bytes, c->stream); }
-        if (e != hipSuccess) rc = fail(c, SS_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
-        *p = (std::remove_reference_t<decltype(**p)>*)q;
-    };
-    al(&o.frame, S); al(&o.next_id, S); al(&o.err, S); al(&o.n_trk, S);
-    al(&o.trk, S * T);
-    al(&o.tid, S * T); al(&o.age, S * T); al(&o.tsu, S * T); al(&o.hits, S * T); al(&o.streak, S * T); al(&o.hasobs, S * T);
-    al(&o.obsd, S * T); al(&o.frozen, S * T); al(&o.det, S * T);
-    al(&o.score, S * T); al(&o.cls, S * T); al(&o.lobs, S * T * 4);
-    al(&o.ring, S * T * SS_OC_MAXDT * 4); al(&o.rage, S * T * SS_OC_MAXDT); al(&o.vel, S * T * 2);
-    al(&o.x, S * T * 7); al(&o.P, S * T * 49); al(&o.xf, S * T * 7); al(&o.Pf, S * T * 49); al(&o.spill, S * T * SS_MAXD);
-    return rc;
-}
-
-extern "C" int ss_ocsort_create(ss_ctx* c, const ss_ocsort_config* cfg)
-{
-    if (!c || !cfg) return fail(c, SS_ERR_INVALID, "ss_ocsort_create: null argument");
-    if (cfg->max_tracks < 1 || cfg->max_tracks > SS_MAXT || cfg->max_dets < 1 || cfg->max_dets > SS_MAXD || cfg->delta_t < 1 ||
-        cfg->delta_t > SS_OC_MAXDT || cfg->max_age < 1 || cfg->min_hits < 0 || !(cfg->iou_threshold > 0.0 && cfg->iou_threshold <= 1.0) ||
-        !(cfg->inertia >= 0.0) || !(cfg->low_thresh <= cfg->det_thresh) || (cfg->use_byte != 0 && cfg->use_byte != 1))
-        return fail(c, SS_ERR_INVALID, "ss_ocsort_create: 1 <= max_tracks <= 256, 1 <= max_dets <= 128, 1 <= delta_t <= 8, max_age >= 1, "
-                                       "min_hits >= 0, 0 < iou_threshold <= 1, inertia >= 0, low_thresh <= det_thresh, use_byte 0 / 1");
-    if (int rc = ss_ocsort_destroy(c)) return rc;
-    ss_ctx::Oc* O = new ss_ctx::Oc();
-    SSOcDev& o = O->dev;
-    memset(&o, 0, sizeof o);
-    o.S = c->dev.S;
-    o.max_age = cfg->max_age; o.min_hits = cfg->min_hits; o.delta_t = cfg->delta_t; o.use_byte = cfg->use_byte;
-    o.max_tracks = cfg->max_tracks; o.max_dets = cfg->max_dets;
-    o.det_thresh = (float)cfg->det_thresh; o.low_thresh = (float)cfg->low_thresh;
-    o.iou_thr = cfg->iou_threshold; o.inertia = cfg->inertia;
-    int rc = oc_alloc_state(c, o, O->allocs, "ss_ocsort_create");
-    c->oc = O;
-    if (rc == SS_OK) rc = ss_ocsort_reset(c, -1);
-    if (rc != SS_OK) { std::string m = c->err; (void)ss_ocsort_destroy(c); c->err = m; return rc; }
-    return SS_OK;
+    return tracker_run(c, "ss_ocsort_reset", c && c->oc, OC_OR_STREAM, stream, false,
+                       [&](std::string& err) { return ss_oc_reset_impl(ss_ocsort_dev(c->oc), c->stream, stream, "ss_ocsort_reset: ", err); });
 }
 
 extern "C" int ss_ocsort_update_group(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout)
 {
-    if (!c || !d_dets || !d_ndets || !d_out || !d_nout) return fail(c, SS_ERR_INVALID, "ss_ocsort_update_group: null argument");
-    if (!c->oc) return fail(c, SS_ERR_INVALID, "ss_ocsort_update_group: no OC-SORT state (ss_ocsort_create)");
-    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_ocsort_update_group: 1 <= n_frames <= SS_FMAX");
-    ss_launch_ocsort_group(c->oc->dev, n_frames, d_dets, d_ndets, d_out, d_nout, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return SS_OK;
+    return update_run(c, "ss_ocsort_update_group", d_dets && d_ndets && d_out && d_nout, n_frames, c && c->oc, OC_STATE,
+                      [&](std::string&) { ss_launch_ocsort_group(ss_ocsort_dev(c->oc), n_frames, d_dets, d_ndets, d_out, d_nout, c->stream); return (int)SS_OK; });
 }
 
-extern "C" int ss_ocsort_update(ss_ctx* c, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout)
-{
-    return ss_ocsort_update_group(c, 1, d_dets, d_ndets, d_out, d_nout);
-}
-
-// Synchronous: the table of one stream of an OC-SORT state (OC-SORT's own or Deep OC-SORT's) in list order; fn: the caller's name
-// for the messages.  slots (may be NULL): the list's slots, for a caller that gathers more.
-static int oc_get_tracks(ss_ctx* c, const SSOcDev& o, const std::string& fn, int s, int cap, int* n_tracks, int* next_id, int* frame_count,
-                         int* track_id, int* age, int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P,
-                         float* last_obs, double* velocity, std::vector<int>* slots = nullptr)
-{
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int nt = 0, nid = 0, fr = 0;
-    HIPCHK(c, hipMemcpy(&nt, o.n_trk + s, 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&nid, o.next_id + s, 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&fr, o.frame + s, 4, hipMemcpyDeviceToHost));
-    if (n_tracks) *n_tracks = nt;                                    // the counts also when cap is too small: the caller sizes by them
-    if (next_id) *next_id = nid;
-    if (frame_count) *frame_count = fr;
-    if (nt < 0 || nt > SS_MAXT) return fail(c, SS_ERR_CAPACITY, fn + ": corrupt list");
-    if (nt > cap) return fail(c, SS_ERR_CAPACITY, fn + ": cap too small");
-    const size_t T = SS_MAXT, sb = (size_t)s * T;
-    std::vector<int> trk(T), iv(T);
-    HIPCHK(c, hipMemcpy(trk.data(), o.trk + sb, T * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < nt; ++i)
-        if (trk[i] < 0 || trk[i] >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, fn + ": corrupt list");
-    auto ints = [&](const int* src, int* dst) -> int {
-        if (!dst) return SS_OK;
-        HIPCHK(c, hipMemcpy(iv.data(), src + sb, T * 4, hipMemcpyDeviceToHost));
-        for (int i = 0; i < nt; ++i) dst[i] = iv[trk[i]];
-        return SS_OK;
-    };
-    auto dbls = [&](const double* src, double* dst, int n) -> int {
-        if (!dst) return SS_OK;
-        std::vector<double> dv(T * n);
-        HIPCHK(c, hipMemcpy(dv.data(), src + sb * n, T * n * 8, hipMemcpyDeviceToHost));
-        for (int i = 0; i < nt; ++i) for (int k = 0; k < n; ++k) dst[i * n + k] = dv[(size_t)trk[i] * n + k];
-        return SS_OK;
-    };
-    if (int rc = ints(o.tid, track_id)) return rc;
-    if (int rc = ints(o.age, age)) return rc;
-    if (int rc = ints(o.tsu, time_since_update)) return rc;
-    if (int rc = ints(o.hits, hits)) return rc;
-    if (int rc = ints(o.streak, hit_streak)) return rc;
-    if (int rc = ints(o.frozen, frozen)) return rc;
-    if (int rc = dbls(o.x, x, 7)) return rc;
-    if (int rc = dbls(o.P, P, 49)) return rc;
-    if (int rc = dbls(o.vel, velocity, 2)) return rc;
-    if (last_obs) {
-        std::vector<float> lv(T * 4);
-        HIPCHK(c, hipMemcpy(lv.data(), o.lobs + sb * 4, T * 16, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(iv.data(), o.hasobs + sb, T * 4, hipMemcpyDeviceToHost));
-        for (int i = 0; i < nt; ++i) for (int k = 0; k < 4; ++k) last_obs[i * 4 + k] = iv[trk[i]] ? lv[(size_t)trk[i] * 4 + k] : -1.0f;
-    }
-    if (slots) slots->assign(trk.begin(), trk.begin() + nt);
-    return SS_OK;
-}
+extern "C" int ss_ocsort_update(ss_ctx* c, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout) { return ss_ocsort_update_group(c, 1, d_dets, d_ndets, d_out, d_nout); }
 
 extern "C" int ss_ocsort_get_tracks(ss_ctx* c, int s, int cap, int* n_tracks, int* next_id, int* frame_count, int* track_id, int* age,
                                     int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
                                     double* velocity)
 {
-    if (!c || !c->oc || s < 0 || s >= c->dev.S || cap < 0) return fail(c, SS_ERR_INVALID, "ss_ocsort_get_tracks: no OC-SORT state or bad stream");
-    return oc_get_tracks(c, c->oc->dev, "ss_ocsort_get_tracks", s, cap, n_tracks, next_id, frame_count, track_id, age, time_since_update, hits,
-                         hit_streak, frozen, x, P, last_obs, velocity);
+    return tracker_run(c, "ss_ocsort_get_tracks", c && c->oc && cap >= 0, OC_OR_STREAM, s, true, [&](std::string& err) {
+        return ss_oc_get_tracks_impl(ss_ocsort_dev(c->oc), c->stream, "ss_ocsort_get_tracks", s, cap, n_tracks, next_id, frame_count, track_id, age,
+                                     time_since_update, hits, hit_streak, frozen, x, P, last_obs, velocity, nullptr, err);
+    });
 }
 
-// ---- Deep OC-SORT (ss_deepoc.hip, docs/DEEPOCSORT.md) -------------------------------------------------------------------------------
-extern "C" int ss_deepoc_destroy(ss_ctx* c)
+// ---- Deep OC-SORT (docs/DEEPOCSORT.md)
+static const char *const DEEPOC_STATE = "Deep OC-SORT state (ss_deepoc_create)", *const DEEPOC_OR_STREAM = "Deep OC-SORT state or bad stream";
+
+extern "C" int ss_deepoc_destroy(ss_ctx* c) { return stage_destroy(c, "ss_deepoc_destroy", &ss_ctx::deepoc, ss_deepoc_free); }
+
+extern "C" int ss_deepoc_create(ss_ctx* c, const ss_deepoc_config* cfg)
 {
-    if (!c) return fail(nullptr, SS_ERR_INVALID, "ss_deepoc_destroy: null context");
-    if (!c->deepoc) return SS_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (void* p : c->deepoc->allocs) HIPCHK(c, hipFree(p));
-    delete c->deepoc;
-    c->deepoc = nullptr;
-    return SS_OK;
+    return create_run(c, "ss_deepoc_create", &ss_ctx::deepoc, ss_deepoc_free, [&](std::string& err) { return ss_deepoc_create_check_impl(cfg, err); },
+                      [&](std::string& err) { return ss_deepoc_create_impl(&c->deepoc, c->stream, warp_flags(c), c->dev.S, cfg, err); });
 }
 
 extern "C" int ss_deepoc_reset(ss_ctx* c, int stream)
 {
-    if (!c || !c->deepoc || stream >= c->dev.S) return fail(c, SS_ERR_INVALID, "ss_deepoc_reset: no Deep OC-SORT state or bad stream");
-    SSDeepOcDev& d = c->deepoc->dev;
-    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? d.oc.S : stream + 1;
-    HIPCHK(c, hipMemsetAsync(c->cmc_prev_valid + s0, 0, (s1 - s0) * 4, c->stream));     // G-04: the next frame gets no warp
-    HIPCHK(c, hipMemsetAsync(c->gmc.prev_valid + s0, 0, (s1 - s0) * 4, c->stream));     // ... from either estimator
-    HIPCHK(c, hipMemsetAsync(d.emb + (size_t)s0 * SS_MAXT * SS_F, 0, (size_t)(s1 - s0) * SS_MAXT * SS_F * 4, c->stream));
-    return oc_reset_state(c, d.oc, stream);
+    return tracker_run(c, "ss_deepoc_reset", c && c->deepoc, DEEPOC_OR_STREAM, stream, false,
+                       [&](std::string& err) { return ss_deepoc_reset_impl(c->deepoc, c->stream, warp_flags(c), stream, err); });
 }
 
-extern "C" int ss_deepoc_create(ss_ctx* c, const ss_deepoc_config* cfg)
-{
-    if (!c || !cfg) return fail(c, SS_ERR_INVALID, "ss_deepoc_create: null argument");
-    auto flag = [](int v) { return v == 0 || v == 1; };
-    if (cfg->max_tracks < 1 || cfg->max_tracks > SS_MAXT || cfg->max_dets < 1 || cfg->max_dets > SS_MAXD || cfg->delta_t < 1 ||
-        cfg->delta_t > SS_OC_MAXDT || cfg->max_age < 1 || cfg->min_hits < 0 || !(cfg->iou_threshold > 0.0 && cfg->iou_threshold <= 1.0) ||
-        !(cfg->inertia >= 0.0) || !(cfg->det_thresh < 1.0) || !(cfg->w_association_emb >= 0.0) ||
-        !(cfg->alpha_fixed_emb >= 0.0 && cfg->alpha_fixed_emb <= 1.0) || !(cfg->aw_param >= 0.0 && cfg->aw_param < 1.0) ||
-        !flag(cfg->appearance) || !flag(cfg->dynamic_appearance) || !flag(cfg->adaptive_weighting))
-        return fail(c, SS_ERR_INVALID, "ss_deepoc_create: 1 <= max_tracks <= 256, 1 <= max_dets <= 128, 1 <= delta_t <= 8, max_age >= 1, "
-                                       "min_hits >= 0, 0 < iou_threshold <= 1, inertia >= 0, det_thresh < 1, w_association_emb >= 0, "
-                                       "0 <= alpha_fixed_emb <= 1, 0 <= aw_param < 1, flags 0 / 1");
-    if (int rc = ss_deepoc_destroy(c)) return rc;
-    ss_ctx::DeepOc* D = new ss_ctx::DeepOc();
-    SSDeepOcDev& d = D->dev;
-    memset(&d, 0, sizeof d);
-    SSOcDev& o = d.oc;
-    o.S = c->dev.S;
-    o.max_age = cfg->max_age; o.min_hits = cfg->min_hits; o.delta_t = cfg->delta_t; o.use_byte = 0;
-    o.max_tracks = cfg->max_tracks; o.max_dets = cfg->max_dets;
-    o.det_thresh = (float)cfg->det_thresh; o.low_thresh = (float)cfg->det_thresh;
-    o.iou_thr = cfg->iou_threshold; o.inertia = cfg->inertia;
-    d.appearance = cfg->appearance; d.dynamic = cfg->dynamic_appearance; d.adaptive = cfg->adaptive_weighting;
-    d.det_thresh = cfg->det_thresh; d.w_emb = cfg->w_association_emb; d.alpha_fixed = cfg->alpha_fixed_emb; d.aw = cfg->aw_param;
-    int rc = oc_alloc_state(c, o, D->allocs, "ss_deepoc_create");
-    const size_t S = o.S;
-    const size_t bytes[3] = {S * SS_MAXT * SS_F * 4, (size_t)SS_FMAX * S * SS_MAXD * SS_F * 4, S * SS_MAXT * SS_MAXD * 8};
-    void* q[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < 3 && rc == SS_OK; ++i) {
-        hipError_t e = hipMalloc(&q[i], bytes[i]);
-        if (e == hipSuccess) { D->allocs.push_back(q[i]); e = hipMemsetAsync(q[i], 0, bytes[i], c->stream); }
-        if (e != hipSuccess) rc = fail(c, SS_ERR_HIP, std::string("ss_deepoc_create: ") + hipGetErrorString(e));
-    }
-    d.emb = (float*)q[0]; d.ufeat = (float*)q[1]; d.E = (double*)q[2];
-    c->deepoc = D;
-    if (rc == SS_OK) rc = ss_deepoc_reset(c, -1);
-    if (rc != SS_OK) { std::string m = c->err; (void)ss_deepoc_destroy(c); c->err = m; return rc; }
-    return SS_OK;
-}
-
-// The following update calls read d_warps[f][s][8] (ss_cmc_estimate's layout) for frame f; the pointer goes into the launch
-// arguments, so the call is capturable.  NULL: off.
 extern "C" int ss_deepoc_set_gmc(ss_ctx* c, const double* d_warps)
 {
-    if (!c || !c->deepoc) return fail(c, SS_ERR_INVALID, "ss_deepoc_set_gmc: no Deep OC-SORT state (ss_deepoc_create)");
-    c->deepoc->dev.gmc = d_warps;
-    return SS_OK;
+    return tracker_run(c, "ss_deepoc_set_gmc", c && c->deepoc, DEEPOC_STATE, -1, false,
+                       [&](std::string&) { ss_deepoc_set_gmc_impl(c->deepoc, d_warps); return (int)SS_OK; });
 }
 
-// Two launches on the context's stream (unit features, then the group): capturable.
 extern "C" int ss_deepoc_update_group(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, const float* d_feats, float* d_out,
                                       int* d_nout)
 {
-    if (!c || !d_dets || !d_ndets || !d_out || !d_nout) return fail(c, SS_ERR_INVALID, "ss_deepoc_update_group: null argument");
-    if (!c->deepoc) return fail(c, SS_ERR_INVALID, "ss_deepoc_update_group: no Deep OC-SORT state (ss_deepoc_create)");
-    if (c->deepoc->dev.appearance && !d_feats) return fail(c, SS_ERR_INVALID, "ss_deepoc_update_group: appearance is on and d_feats is NULL");
-    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, "ss_deepoc_update_group: 1 <= n_frames <= SS_FMAX");
-    ss_launch_deepoc_group(c->deepoc->dev, n_frames, d_dets, d_ndets, d_feats, d_out, d_nout, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return SS_OK;
+    const char* fn = "ss_deepoc_update_group";
+    return update_run(c, fn, d_dets && d_ndets && d_out && d_nout, n_frames, c && c->deepoc, DEEPOC_STATE, [&](std::string& err) {
+        const SSDeepOcDev& d = ss_deepoc_dev(c->deepoc);
+        if (d.appearance && !d_feats) return invalid(err, fn, "appearance is on and d_feats is NULL");
+        ss_launch_deepoc_group(d, n_frames, d_dets, d_ndets, d_feats, d_out, d_nout, c->stream);
+        return (int)SS_OK;
+    });
 }
 
-extern "C" int ss_deepoc_update(ss_ctx* c, const float* d_dets, const int* d_ndets, const float* d_feats, float* d_out, int* d_nout)
-{
-    return ss_deepoc_update_group(c, 1, d_dets, d_ndets, d_feats, d_out, d_nout);
-}
+extern "C" int ss_deepoc_update(ss_ctx* c, const float* d_dets, const int* d_ndets, const float* d_feats, float* d_out, int* d_nout) { return ss_deepoc_update_group(c, 1, d_dets, d_ndets, d_feats, d_out, d_nout); }
 
 extern "C" int ss_deepoc_get_tracks(ss_ctx* c, int s, int cap, int* n_tracks, int* next_id, int* frame_count, int* track_id, int* age,
                                     int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
                                     double* velocity)
 {
-    if (!c || !c->deepoc || s < 0 || s >= c->dev.S || cap < 0) return fail(c, SS_ERR_INVALID, "ss_deepoc_get_tracks: no Deep OC-SORT state or bad stream");
-    return oc_get_tracks(c, c->deepoc->dev.oc, "ss_deepoc_get_tracks", s, cap, n_tracks, next_id, frame_count, track_id, age, time_since_update,
-                         hits, hit_streak, frozen, x, P, last_obs, velocity);
+    return tracker_run(c, "ss_deepoc_get_tracks", c && c->deepoc && cap >= 0, DEEPOC_OR_STREAM, s, true, [&](std::string& err) {
+        return ss_oc_get_tracks_impl(ss_deepoc_dev(c->deepoc).oc, c->stream, "ss_deepoc_get_tracks", s, cap, n_tracks, next_id, frame_count, track_id,
+                                     age, time_since_update, hits, hit_streak, frozen, x, P, last_obs, velocity, nullptr, err);
+    });
 }
 
-// Synchronous: the tracks' unit features [n][512] of one stream in ss_deepoc_get_tracks' list order.
 extern "C" int ss_deepoc_get_features(ss_ctx* c, int s, int cap, float* emb)
 {
-    if (!c || !c->deepoc || s < 0 || s >= c->dev.S || cap < 0 || !emb)
-        return fail(c, SS_ERR_INVALID, "ss_deepoc_get_features: no Deep OC-SORT state, bad stream or NULL");
-    std::vector<int> slots;
-    if (const int rc = oc_get_tracks(c, c->deepoc->dev.oc, "ss_deepoc_get_features", s, cap, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &slots)) return rc;
-    std::vector<float> em((size_t)SS_MAXT * SS_F);
-    HIPCHK(c, hipMemcpy(em.data(), c->deepoc->dev.emb + (size_t)s * SS_MAXT * SS_F, em.size() * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < slots.size(); ++i) memcpy(emb + i * SS_F, em.data() + (size_t)slots[i] * SS_F, SS_F * 4);
-    return SS_OK;
+    return tracker_run(c, "ss_deepoc_get_features", c && c->deepoc && cap >= 0 && emb, "Deep OC-SORT state, bad stream or NULL", s, true,
+                       [&](std::string& err) { return ss_deepoc_get_features_impl(c->deepoc, c->stream, s, cap, emb, err); });
 }
 
-// ---- BYTE tracker family (ss_byte.hip) -----------------------------------------------------------------------------
-extern "C" int ss_byte_destroy(ss_ctx* c)
+// ---- BYTE tracker family (docs/BYTETRACK.md; oriented boxes: docs/OBB.md §4)
+static const char *const BYTE_STATE = "BYTE state (ss_byte_create)", *const BYTE_OR_STREAM = "BYTE state or bad stream",
+                  *const BYTE_OR_STREAM_NULL = "BYTE state, bad stream or NULL";
+
+extern "C" int ss_byte_destroy(ss_ctx* c) { return stage_destroy(c, "ss_byte_destroy", &ss_ctx::byte, ss_byte_free); }
+
+extern "C" int ss_byte_create(ss_ctx* c, const ss_byte_config* cfg)
 {
-    if (!c) return fail(nullptr, SS_ERR_INVALID, "ss_byte_destroy: null context");
-    if (!c->byte) return SS_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (void* p : c->byte->allocs) HIPCHK(c, hipFree(p));
-    delete c->byte;
-    c->byte = nullptr;
-    return SS_OK;
+    return create_run(c, "ss_byte_create", &ss_ctx::byte, ss_byte_free, [&](std::string& err) { return ss_byte_create_check_impl(cfg, err); },
+                      [&](std::string& err) { return ss_byte_create_impl(&c->byte, c->stream, warp_flags(c), c->dev.S, cfg, err); });
 }
 
 extern "C" int ss_byte_reset(ss_ctx* c, int stream)
 {
-    if (!c || !c->byte || stream >= c->dev.S) return fail(c, SS_ERR_INVALID, "ss_byte_reset: no BYTE state or bad stream");
-    SSByteDev& b = c->byte->dev;
-    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? b.S : stream + 1;
-    std::vector<int> ones(b.S, 1);
-    HIPCHK(c, hipMemsetAsync(b.frame + s0, 0, (s1 - s0) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.err + s0, 0, (s1 - s0) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.n_trk + s0, 0, (s1 - s0) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.n_lost + s0, 0, (s1 - s0) * 4, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.next_id + s0, ones.data(), (s1 - s0) * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->cmc_prev_valid + s0, 0, (s1 - s0) * 4, c->stream));     // G-04: the next frame gets no warp
-    HIPCHK(c, hipMemsetAsync(c->gmc.prev_valid + s0, 0, (s1 - s0) * 4, c->stream));     // ... from either estimator
-    if (b.smooth)                                                                        // §1c: the streams' track features
-        HIPCHK(c, hipMemsetAsync(b.smooth + (size_t)s0 * SS_MAXT * SS_F, 0, (size_t)(s1 - s0) * SS_MAXT * SS_F * 4, c->stream));
-    if (b.tpose) {                                                                       // §1e: the streams' track poses
-        HIPCHK(c, hipMemsetAsync(b.tpose + (size_t)s0 * SS_MAXT * b.nk * 2, 0, (size_t)(s1 - s0) * SS_MAXT * b.nk * 2 * 8, c->stream));
-        HIPCHK(c, hipMemsetAsync(b.tvis + (size_t)s0 * SS_MAXT, 0, (size_t)(s1 - s0) * SS_MAXT * 4, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SS_OK;
+    return tracker_run(c, "ss_byte_reset", c && c->byte, BYTE_OR_STREAM, stream, false,
+                       [&](std::string& err) { return ss_byte_reset_impl(c->byte, c->stream, warp_flags(c), stream, err); });
 }
 
-extern "C" int ss_byte_create(ss_ctx* c, const ss_byte_config* cfg)
+// ss_byte_update_group (d_feats NULL, feats_entry 0) and ss_byte_update_group_feats: up to two launches (unit features, then the group)
+static int byte_update(ss_ctx* c, const char* fn, int feats_entry, int n_frames, const float* d_dets, const int* d_ndets, const float* d_feats,
+                       float* d_out, int* d_nout)
 {
-    if (!c || !cfg) return fail(c, SS_ERR_INVALID, "ss_byte_create: null argument");
-    if (cfg->max_tracks < 1 || cfg->max_tracks > SS_MAXT || cfg->max_dets < 1 || cfg->max_dets > SS_MAXD || cfg->frame_rate < 1 ||
-        cfg->track_buffer < 0 || (cfg->kalman_xywh != 0 && cfg->kalman_xywh != 1))
-        return fail(c, SS_ERR_INVALID, "ss_byte_create: 1 <= max_tracks <= 256, 1 <= max_dets <= 128, frame_rate >= 1, kalman_xywh 0 / 1");
-    if (int rc = ss_byte_destroy(c)) return rc;
-    ss_ctx::Byte* B = new ss_ctx::Byte();
-    B->cfg = *cfg;
-    SSByteDev& b = B->dev;
-    memset(&b, 0, sizeof b);
-    b.S = c->dev.S;
-    b.xywh = cfg->kalman_xywh; b.fuse = cfg->fuse_score != 0;
-    b.max_time_lost = (int)(cfg->frame_rate / 30.0 * cfg->track_buffer);
-    b.max_tracks = cfg->max_tracks; b.max_dets = cfg->max_dets;
-    b.high = (float)cfg->track_high_thresh; b.low = (float)cfg->track_low_thresh; b.new_thresh = (float)cfg->new_track_thresh;
-    b.match = cfg->match_thresh; b.wp = cfg->std_weight_position; b.wv = cfg->std_weight_velocity;
-    const size_t S = b.S, T = SS_MAXT;
-    int rc = SS_OK;
-    auto al = [&](auto** p, size_t n) {
-        if (rc != SS_OK) return;
-        void* q = nullptr;
-        const size_t bytes = n * sizeof(**p);
-        hipError_t e = hipMalloc(&q, bytes);
-        if (e == hipSuccess) { B->allocs.push_back(q); e = hipMemsetAsync(q, 0, bytes, c->stream); }
-        if (e != hipSuccess) rc = fail(c, SS_ERR_HIP, std::string("ss_byte_create: ") + hipGetErrorString(e));
-        *p = (std::remove_reference_t<decltype(**p)>*)q;
-    };
-    al(&b.frame, S); al(&b.next_id, S); al(&b.err, S); al(&b.n_trk, S); al(&b.n_lost, S);
-    al(&b.trk, S * T); al(&b.lost, S * T);
-    al(&b.state, S * T); al(&b.act, S * T); al(&b.tid, S * T); al(&b.start, S * T); al(&b.end, S * T); al(&b.len, S * T); al(&b.det, S * T);
-    al(&b.score, S * T); al(&b.cls, S * T);
-    al(&b.mean, S * T * 8); al(&b.cov, S * T * 64); al(&b.spill, S * T * SS_MAXD);
-    c->byte = B;
-    if (rc == SS_OK) rc = ss_byte_reset(c, -1);
-    if (rc != SS_OK) { std::string m = c->err; (void)ss_byte_destroy(c); c->err = m; return rc; }
-    return SS_OK;
-}
-
-// Synchronous: the slots of one stream's BYTE lists in list order (tracked, then lost) -> slots, after the stream has drained.
-// nt / nl: the lists' lengths; fn: the caller's name for the message.  More than cap entries or a slot out of range is an error.
-static int byte_read_lists(ss_ctx* c, const char* fn, int s, int cap, int& nt, int& nl, std::vector<int>& slots)
-{
-    const SSByteDev& b = c->byte->dev;
-    HIPCHK(c, hipMemcpy(&nt, b.n_trk + s, 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&nl, b.n_lost + s, 4, hipMemcpyDeviceToHost));
-    if (nt + nl > cap) return fail(c, SS_ERR_CAPACITY, std::string(fn) + ": cap too small");
-    const size_t T = SS_MAXT, sb = (size_t)s * T;
-    std::vector<int> trk(T), lost(T);
-    HIPCHK(c, hipMemcpy(trk.data(), b.trk + sb, T * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(lost.data(), b.lost + sb, T * 4, hipMemcpyDeviceToHost));
-    slots.resize(nt + nl);
-    for (int i = 0; i < nt + nl; ++i) {
-        slots[i] = i < nt ? trk[i] : lost[i - nt];
-        if (slots[i] < 0 || slots[i] >= SS_MAXT) return fail(c, SS_ERR_CAPACITY, std::string(fn) + ": corrupt list");
-    }
-    return SS_OK;
-}
-
-// the checks every ss_byte_update_group* entry point makes first (ok: its pointer arguments are all there; need_pose: it is the one
-// that needs the keypoint term on); fn: its name for the message
-static int byte_update_check(ss_ctx* c, const char* fn, bool ok, int n_frames, bool need_pose = false)
-{
-    const std::string f = fn;
-    if (!c || !ok) return fail(c, SS_ERR_INVALID, f + ": null argument");
-    if (!c->byte) return fail(c, SS_ERR_INVALID, f + ": no BYTE state (ss_byte_create)");
-    if (need_pose && !c->byte->dev.pose) return fail(c, SS_ERR_INVALID, f + ": the keypoint term is off (ss_byte_set_pose)");
-    if (n_frames < 1 || n_frames > SS_FMAX) return fail(c, SS_ERR_INVALID, f + ": 1 <= n_frames <= SS_FMAX");
-    return SS_OK;
+    return update_run(c, fn, d_dets && d_ndets && d_out && d_nout, n_frames, c && c->byte, BYTE_STATE, [&](std::string& err) {
+        const SSByteDev& b = ss_byte_dev(c->byte);
+        if (!feats_entry && b.reid) return invalid(err, fn, "ReID is on, the features go through ss_byte_update_group_feats");
+        if (b.reid && !d_feats) return invalid(err, fn, "ReID is on and d_feats is NULL");
+        if (b.pose) return invalid(err, fn, "the keypoint term is on, the keypoints go through ss_byte_update_group_kpts");
+        if (b.obb) return invalid(err, fn, "oriented boxes are on, the 11-column rows go through ss_byte_update_group_obb");
+        ss_launch_byte_group(b, n_frames, d_dets, d_ndets, d_feats, d_out, d_nout, c->stream);
+        return (int)SS_OK;
+    });
 }
 
 extern "C" int ss_byte_update_group(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout)
-{
-    if (const int rc = byte_update_check(c, "ss_byte_update_group", d_dets && d_ndets && d_out && d_nout, n_frames)) return rc;
-    if (c->byte->dev.reid) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: ReID is on, the features go through ss_byte_update_group_feats");
-    if (c->byte->dev.pose) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: the keypoint term is on, the keypoints go through ss_byte_update_group_kpts");
-    if (c->byte->dev.obb) return fail(c, SS_ERR_INVALID, "ss_byte_update_group: oriented boxes are on, the 11-column rows go through ss_byte_update_group_obb");
-    ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, nullptr, d_out, d_nout, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return SS_OK;
-}
+{ return byte_update(c, "ss_byte_update_group", 0, n_frames, d_dets, d_ndets, nullptr, d_out, d_nout); }
 
-// §1c: ss_byte_update_group with the group's raw detection features d_feats [n_frames][S][SS_MAXD][512] f32 (read only while ReID
-// is on; NULL allowed when it is off).  Two launches on the context's stream (unit features, then the group): capturable.
+extern "C" int ss_byte_update(ss_ctx* c, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout) { return ss_byte_update_group(c, 1, d_dets, d_ndets, d_out, d_nout); }
+
 extern "C" int ss_byte_update_group_feats(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, const float* d_feats,
                                           float* d_out, int* d_nout)
-{
-    if (const int rc = byte_update_check(c, "ss_byte_update_group_feats", d_dets && d_ndets && d_out && d_nout, n_frames)) return rc;
-    if (c->byte->dev.reid && !d_feats) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: ReID is on and d_feats is NULL");
-    if (c->byte->dev.pose) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: the keypoint term is on, the keypoints go through ss_byte_update_group_kpts");
-    if (c->byte->dev.obb) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_feats: oriented boxes are on, the 11-column rows go through ss_byte_update_group_obb");
-    ss_launch_byte_group(c->byte->dev, n_frames, d_dets, d_ndets, d_feats, d_out, d_nout, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return SS_OK;
-}
+{ return byte_update(c, "ss_byte_update_group_feats", 1, n_frames, d_dets, d_ndets, d_feats, d_out, d_nout); }
 
-// §1c: BoT-SORT's ReID branch on (on != 0) or off.  Either way every stream restarts (ss_byte_reset).  The feature tables are
-// allocated on the first switch-on and kept.  xyah (ByteTrack) has no ReID.
-extern "C" int ss_byte_set_reid(ss_ctx* c, int on, double proximity_thresh, double appearance_thresh, double alpha)
-{
-    if (!c || !c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: no BYTE state (ss_byte_create)");
-    SSByteDev& b = c->byte->dev;
-    if (on && !b.xywh) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: ReID needs the xywh (BoT-SORT) state");
-    if (on && b.pose) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: the keypoint term is on (ss_byte_set_pose): the two are not combined");
-    if (on && b.obb) return fail(c, SS_ERR_INVALID, "ss_byte_set_reid: oriented boxes are on (ss_byte_set_obb): the two are not combined");
-    if (on && !b.smooth) {
-        const size_t ns = (size_t)b.S * SS_MAXT * SS_F, nu = (size_t)SS_FMAX * b.S * SS_MAXD * SS_F;
-        void *p = nullptr, *q = nullptr;
-        HIPCHK(c, hipMalloc(&p, ns * 4));
-        c->byte->allocs.push_back(p);
-        HIPCHK(c, hipMalloc(&q, nu * 4));
-        c->byte->allocs.push_back(q);
-        HIPCHK(c, hipMemsetAsync(q, 0, nu * 4, c->stream));
-        b.smooth = (float*)p; b.ufeat = (float*)q;
-    }
-    b.reid = on != 0;
-    b.prox = proximity_thresh; b.appear = appearance_thresh;
-    b.alpha = (float)alpha; b.one_minus_alpha = (float)(1.0 - alpha);
-    return ss_byte_reset(c, -1);
-}
-
-// §1e: the keypoint (OKS) term of BoT-SORT on (on != 0) or off.  Either way every stream restarts (ss_byte_reset).  The pose tables
-// are allocated on the first switch-on for n_kpt keypoints and kept (a later switch-on with another n_kpt allocates again).
-extern "C" int ss_byte_set_pose(ss_ctx* c, int on, int n_kpt, const double* sigmas, double proximity_thresh, double pose_thresh,
-                                double vis_thresh, int min_common)
-{
-    if (!c || !c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: no BYTE state (ss_byte_create)");
-    SSByteDev& b = c->byte->dev;
-    if (on) {
-        if (!b.xywh) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: the keypoint term needs the xywh (BoT-SORT) state");
-        if (b.reid) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: ReID is on (ss_byte_set_reid): the two are not combined");
-        if (b.obb) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: oriented boxes are on (ss_byte_set_obb): the two are not combined");
-        if (n_kpt < 1 || n_kpt > SS_BYTE_MAXK) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: 1 <= n_kpt <= 32");
-        if (!sigmas) return fail(c, SS_ERR_INVALID, "ss_byte_set_pose: sigmas is NULL");
-        b.pose = 0;                                                // a failure below leaves the term off, never half set up
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (!b.ks2) {
-            void* q = nullptr;
-            HIPCHK(c, hipMalloc(&q, SS_BYTE_MAXK * 8));
-            c->byte->allocs.push_back(q);
-            b.ks2 = (const double*)q;
-        }
-        if (!b.tpose || b.nk != n_kpt) {
-            const size_t nt = (size_t)b.S * SS_MAXT, nd = (size_t)SS_FMAX * b.S * SS_MAXD;
-            void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-            const size_t bytes[4] = {nt * n_kpt * 2 * 8, nt * 4, nd * n_kpt * 2 * 4, nd * 4};
-            for (int i = 0; i < 4; ++i) {                          // the old tables (another n_kpt) stay in allocs until the state goes
-                HIPCHK(c, hipMalloc(&p[i], bytes[i]));
-                c->byte->allocs.push_back(p[i]);
-                HIPCHK(c, hipMemsetAsync(p[i], 0, bytes[i], c->stream));
-            }
-            b.nk = n_kpt;                                          // all four exist: commit them together
-            b.tpose = (double*)p[0]; b.tvis = (unsigned*)p[1]; b.kp = (float*)p[2]; b.kvis = (unsigned*)p[3];
-        }
-        double s2[SS_BYTE_MAXK] = {0.0};
-        for (int k = 0; k < n_kpt; ++k) s2[k] = 2.0 * sigmas[k];
-        HIPCHK(c, hipMemcpy((void*)b.ks2, s2, sizeof s2, hipMemcpyHostToDevice));
-        b.prox = proximity_thresh; b.pose_thresh = pose_thresh; b.vis = (float)vis_thresh; b.min_common = min_common;
-    }
-    b.pose = on != 0;
-    return ss_byte_reset(c, -1);
-}
-
-// §1e: ss_byte_update_group with the group's keypoints: row r of image fs = f * n_streams + s at d_kpts + (fs * SS_MAX_DETS + r) *
-// kpt_row_stride + kpt_col_offset, n_kpt triplets (x, y, v) f32.  d_geom [n_frames * n_streams][5] (ss_nms_batch's rows {gain, pad_x,
-// pad_y, ..}): the keypoints are network-input pixels; NULL: original pixels.  Two launches on the context's stream: capturable.
 extern "C" int ss_byte_update_group_kpts(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, const float* d_kpts,
                                          long long kpt_row_stride, int kpt_col_offset, const float* d_geom, float* d_out, int* d_nout)
 {
-    if (const int rc = byte_update_check(c, "ss_byte_update_group_kpts", d_dets && d_ndets && d_kpts && d_out && d_nout, n_frames, true)) return rc;
-    const SSByteDev& b = c->byte->dev;
-    if (kpt_col_offset < 0 || kpt_row_stride < (long long)kpt_col_offset + 3 * b.nk)
-        return fail(c, SS_ERR_INVALID, "ss_byte_update_group_kpts: kpt_col_offset >= 0, kpt_row_stride >= kpt_col_offset + 3 n_kpt");
-    ss_launch_byte_group_kpts(b, n_frames, d_dets, d_ndets, d_kpts, kpt_row_stride, kpt_col_offset, d_geom, d_out, d_nout, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return SS_OK;
+    const char* fn = "ss_byte_update_group_kpts";
+    return update_run(c, fn, d_dets && d_ndets && d_kpts && d_out && d_nout, n_frames, c && c->byte, BYTE_STATE, [&](std::string& err) {
+        const SSByteDev& b = ss_byte_dev(c->byte);
+        if (!b.pose) return invalid(err, fn, "the keypoint term is off (ss_byte_set_pose)");
+        if (kpt_col_offset < 0 || kpt_row_stride < (long long)kpt_col_offset + 3 * b.nk)
+            return invalid(err, fn, "kpt_col_offset >= 0, kpt_row_stride >= kpt_col_offset + 3 n_kpt");
+        ss_launch_byte_group_kpts(b, n_frames, d_dets, d_ndets, d_kpts, kpt_row_stride, kpt_col_offset, d_geom, d_out, d_nout, c->stream);
+        return (int)SS_OK;
+    });
 }
 
-// Synchronous: the stored poses of one stream in ss_byte_get_tracks' list order: offsets [n][n_kpt][2] f64 and a visibility word
-// per track (bit k = keypoint k); either may be NULL.
-extern "C" int ss_byte_get_keypoints(ss_ctx* c, int s, int cap, double* offsets, unsigned* visible)
-{
-    if (!c || !c->byte || s < 0 || s >= c->dev.S || cap < 0) return fail(c, SS_ERR_INVALID, "ss_byte_get_keypoints: no BYTE state or bad stream");
-    const SSByteDev& b = c->byte->dev;
-    if (!b.tpose) return fail(c, SS_ERR_INVALID, "ss_byte_get_keypoints: the keypoint term was never switched on (ss_byte_set_pose)");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int nt = 0, nl = 0;
-    std::vector<int> slots;
-    if (const int rc = byte_read_lists(c, "ss_byte_get_keypoints", s, cap, nt, nl, slots)) return rc;
-    const size_t T = SS_MAXT, sb = (size_t)s * T, K2 = (size_t)b.nk * 2;
-    std::vector<double> po(T * K2);
-    std::vector<unsigned> vi(T);
-    HIPCHK(c, hipMemcpy(po.data(), b.tpose + sb * K2, T * K2 * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(vi.data(), b.tvis + sb, T * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < slots.size(); ++i) {
-        if (offsets) memcpy(offsets + i * K2, po.data() + (size_t)slots[i] * K2, K2 * 8);
-        if (visible) visible[i] = vi[slots[i]];
-    }
-    return SS_OK;
-}
-
-// Synchronous: what k_byte_kpts wrote for image (frame, stream) of the last ss_byte_update_group_kpts call: xy [SS_MAX_DETS][n_kpt][2]
-// f32 in original pixels and the rows' visibility words [SS_MAX_DETS] (rows past the image's count keep older values).
-extern "C" int ss_byte_get_det_keypoints(ss_ctx* c, int frame, int s, float* xy, unsigned* visible)
-{
-    if (!c || !c->byte || s < 0 || s >= c->dev.S || frame < 0 || frame >= SS_FMAX || !xy || !visible)
-        return fail(c, SS_ERR_INVALID, "ss_byte_get_det_keypoints: no BYTE state, bad frame / stream or NULL");
-    const SSByteDev& b = c->byte->dev;
-    if (!b.kp) return fail(c, SS_ERR_INVALID, "ss_byte_get_det_keypoints: the keypoint term was never switched on (ss_byte_set_pose)");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t fs = (size_t)frame * b.S + s;
-    HIPCHK(c, hipMemcpy(xy, b.kp + fs * SS_MAXD * b.nk * 2, (size_t)SS_MAXD * b.nk * 2 * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(visible, b.kvis + fs * SS_MAXD, (size_t)SS_MAXD * 4, hipMemcpyDeviceToHost));
-    return SS_OK;
-}
-
-// §1d: BoT-SORT's `model: auto` features of the kept rows from the detector's head inputs (ss_native.hip k_native_feats).  Every
-// argument is checked before the device is touched; one launch on the context's stream (capturable).
-extern "C" int ss_native_feats(ss_ctx* c, int n_img, int half, const ss_native_map* maps, int s, const int* d_keep, long long keep_stride,
-                               const int* d_counts, float* d_out)
-{
-    if (!c || !maps || !d_keep || !d_counts || !d_out) return fail(c, SS_ERR_INVALID, "ss_native_feats: null argument");
-    if (n_img < 1 || n_img > 65535 || (half != 0 && half != 1) || s < 1 || s > SS_F || keep_stride < SS_MAXD)
-        return fail(c, SS_ERR_INVALID, "ss_native_feats: 1 <= n_img <= 65535, half 0 / 1, 1 <= s <= 512, keep_stride >= 128");
-    const void* p[3];
-    long long is[3], rs[3], ps[3];
-    int ch[3], h[3], w[3];
-    long long anchors = 0;
-    const size_t esz = half ? 2 : 4;
-    for (int l = 0; l < 3; ++l) {
-        const ss_native_map& m = maps[l];
-        p[l] = m.data; is[l] = m.img_stride; rs[l] = m.row_stride; ps[l] = m.pix_stride;
-        ch[l] = m.channels; h[l] = m.height; w[l] = m.width;
-        if (!m.data || ((uintptr_t)m.data % esz) != 0) return fail(c, SS_ERR_INVALID, "ss_native_feats: a map is NULL or misaligned");
-        if (m.channels < s || m.channels % s != 0) return fail(c, SS_ERR_INVALID, "ss_native_feats: every level's channels must be a multiple of s");
-        if (m.height < 1 || m.width < 1 || m.pix_stride < m.channels || m.row_stride < (long long)m.width * m.pix_stride
-            || (n_img > 1 && m.img_stride < (long long)m.height * m.row_stride))
-            return fail(c, SS_ERR_INVALID, "ss_native_feats: bad map shape or strides (channel stride 1, maps must not overlap)");
-        anchors += (long long)m.height * m.width;
-    }
-    if (anchors > 0x7fffffffLL) return fail(c, SS_ERR_INVALID, "ss_native_feats: too many anchors");
-    ss_launch_native_feats(n_img, half, p, is, rs, ps, ch, h, w, s, d_keep, keep_stride, d_counts, d_out, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return SS_OK;
-}
-
-// Synchronous: the smoothed features [n][512] of one stream in ss_byte_get_tracks' list order.
-extern "C" int ss_byte_get_features(ss_ctx* c, int s, int cap, float* smooth)
-{
-    if (!c || !c->byte || s < 0 || s >= c->dev.S || cap < 0 || !smooth) return fail(c, SS_ERR_INVALID, "ss_byte_get_features: no BYTE state, bad stream or NULL");
-    const SSByteDev& b = c->byte->dev;
-    if (!b.smooth) return fail(c, SS_ERR_INVALID, "ss_byte_get_features: ReID was never switched on (ss_byte_set_reid)");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int nt = 0, nl = 0;
-    std::vector<int> slots;
-    if (const int rc = byte_read_lists(c, "ss_byte_get_features", s, cap, nt, nl, slots)) return rc;
-    const size_t T = SS_MAXT, sb = (size_t)s * T;
-    std::vector<float> sm(T * SS_F);
-    HIPCHK(c, hipMemcpy(sm.data(), b.smooth + sb * SS_F, T * SS_F * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < slots.size(); ++i) memcpy(smooth + i * SS_F, sm.data() + (size_t)slots[i] * SS_F, SS_F * 4);
-    return SS_OK;
-}
-
-// BoT-SORT GMC (docs/BYTETRACK.md §1b): the following update calls read d_warps[f][s][8] (ss_cmc_estimate's layout) for frame f;
-// the pointer goes into the launch arguments, so the call is capturable.  NULL: off.  xyah (ByteTrack) has no GMC (G-05).
-extern "C" int ss_byte_set_gmc(ss_ctx* c, const double* d_warps)
-{
-    if (!c || !c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_set_gmc: no BYTE state (ss_byte_create)");
-    if (d_warps && !c->byte->dev.xywh) return fail(c, SS_ERR_INVALID, "ss_byte_set_gmc: GMC needs the xywh (BoT-SORT) state");
-    if (d_warps && c->byte->dev.obb) return fail(c, SS_ERR_INVALID, "ss_byte_set_gmc: oriented boxes are on (ss_byte_set_obb): GMC does not move rotated tracks");
-    c->byte->dev.gmc = d_warps;
-    return SS_OK;
-}
-
-// docs/OBB.md §4: association on ProbIoU on (on != 0) or off.  Either way every stream restarts (ss_byte_reset).  The per-slot angles
-// and the boxes' ProbIoU terms are allocated on the first switch-on and kept.  Not with ReID, the keypoint term or GMC.
-extern "C" int ss_byte_set_obb(ss_ctx* c, int on)
-{
-    if (!c || !c->byte) return fail(c, SS_ERR_INVALID, "ss_byte_set_obb: no BYTE state (ss_byte_create)");
-    SSByteDev& b = c->byte->dev;
-    if (on && (b.reid || b.pose || b.gmc))
-        return fail(c, SS_ERR_INVALID, "ss_byte_set_obb: ReID, the keypoint term or GMC is on: oriented boxes are not combined with them");
-    if (on && !b.angle) {
-        const size_t nt = (size_t)b.S * SS_MAXT, nd = (size_t)b.S * SS_MAXD;
-        void* p[3] = {nullptr, nullptr, nullptr};
-        const size_t bytes[3] = {nt * 4, nt * 6 * 8, nd * 6 * 8};
-        for (int i = 0; i < 3; ++i) {
-            HIPCHK(c, hipMalloc(&p[i], bytes[i]));
-            c->byte->allocs.push_back(p[i]);
-            HIPCHK(c, hipMemsetAsync(p[i], 0, bytes[i], c->stream));
-        }
-        b.angle = (float*)p[0]; b.tbox = (double*)p[1]; b.dbox = (double*)p[2];      // all three exist: commit them together
-    }
-    b.obb = on != 0;
-    return ss_byte_reset(c, -1);
-}
-
-// docs/OBB.md §4: ss_byte_update_group on the 11-column rows ss_nms_obb_batch writes; one launch on the context's stream: capturable.
 extern "C" int ss_byte_update_group_obb(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, float* d_out_rbox,
                                         int* d_nout)
 {
-    if (const int rc = byte_update_check(c, "ss_byte_update_group_obb", d_dets && d_ndets && d_out && d_out_rbox && d_nout, n_frames)) return rc;
-    if (!c->byte->dev.obb) return fail(c, SS_ERR_INVALID, "ss_byte_update_group_obb: oriented boxes are off (ss_byte_set_obb)");
-    ss_launch_byte_group_obb(c->byte->dev, n_frames, d_dets, d_ndets, d_out, d_out_rbox, d_nout, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return SS_OK;
+    const char* fn = "ss_byte_update_group_obb";
+    return update_run(c, fn, d_dets && d_ndets && d_out && d_out_rbox && d_nout, n_frames, c && c->byte, BYTE_STATE, [&](std::string& err) {
+        if (!ss_byte_dev(c->byte).obb) return invalid(err, fn, "oriented boxes are off (ss_byte_set_obb)");
+        ss_launch_byte_group_obb(ss_byte_dev(c->byte), n_frames, d_dets, d_ndets, d_out, d_out_rbox, d_nout, c->stream);
+        return (int)SS_OK;
+    });
 }
 
-// Synchronous: the angles [n] of one stream's tracks in ss_byte_get_tracks' list order.
-extern "C" int ss_byte_get_angles(ss_ctx* c, int s, int cap, float* angles)
+extern "C" int ss_byte_set_reid(ss_ctx* c, int on, double proximity_thresh, double appearance_thresh, double alpha)
 {
-    if (!c || !c->byte || s < 0 || s >= c->dev.S || cap < 0 || !angles) return fail(c, SS_ERR_INVALID, "ss_byte_get_angles: no BYTE state, bad stream or NULL");
-    const SSByteDev& b = c->byte->dev;
-    if (!b.angle) return fail(c, SS_ERR_INVALID, "ss_byte_get_angles: oriented boxes were never switched on (ss_byte_set_obb)");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int nt = 0, nl = 0;
-    std::vector<int> slots;
-    if (const int rc = byte_read_lists(c, "ss_byte_get_angles", s, cap, nt, nl, slots)) return rc;
-    std::vector<float> an(SS_MAXT);
-    HIPCHK(c, hipMemcpy(an.data(), b.angle + (size_t)s * SS_MAXT, SS_MAXT * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < slots.size(); ++i) angles[i] = an[slots[i]];
-    return SS_OK;
+    return tracker_run(c, "ss_byte_set_reid", c && c->byte, BYTE_STATE, -1, false, [&](std::string& err) {
+        return ss_byte_set_reid_impl(c->byte, c->stream, warp_flags(c), on, proximity_thresh, appearance_thresh, alpha, err);
+    });
 }
 
-extern "C" int ss_byte_update(ss_ctx* c, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout)
+extern "C" int ss_byte_set_pose(ss_ctx* c, int on, int n_kpt, const double* sigmas, double proximity_thresh, double pose_thresh,
+                                double vis_thresh, int min_common)
 {
-    return ss_byte_update_group(c, 1, d_dets, d_ndets, d_out, d_nout);
+    return tracker_run(c, "ss_byte_set_pose", c && c->byte, BYTE_STATE, -1, false, [&](std::string& err) {
+        return ss_byte_set_pose_impl(c->byte, c->stream, warp_flags(c), on, n_kpt, sigmas, proximity_thresh, pose_thresh, vis_thresh, min_common, err);
+    });
+}
+
+extern "C" int ss_byte_set_obb(ss_ctx* c, int on)
+{
+    return tracker_run(c, "ss_byte_set_obb", c && c->byte, BYTE_STATE, -1, false,
+                       [&](std::string& err) { return ss_byte_set_obb_impl(c->byte, c->stream, warp_flags(c), on, err); });
+}
+
+extern "C" int ss_byte_set_gmc(ss_ctx* c, const double* d_warps)
+{
+    return tracker_run(c, "ss_byte_set_gmc", c && c->byte, BYTE_STATE, -1, false,
+                       [&](std::string& err) { return ss_byte_set_gmc_impl(c->byte, d_warps, err); });
+}
+
+// the read-backs of one stream, each in list order (tracked, then lost): ss_byte_get_impl fills the tables r names
+static int byte_get(ss_ctx* c, const char* fn, bool ok, const char* what, int s, int cap, const SsByteRows& r)
+{
+    return tracker_run(c, fn, c && c->byte && cap >= 0 && ok, what, s, true,
+                       [&](std::string& err) { return ss_byte_get_impl(c->byte, c->stream, fn, s, cap, r, err); });
 }
 
 extern "C" int ss_byte_get_tracks(ss_ctx* c, int s, int cap, int* n_tracked, int* n_lost, int* next_id, int* frame_id,
                                   int* track_id, int* state, int* activated, double* mean)
 {
-    if (!c || !c->byte || s < 0 || s >= c->dev.S || cap < 0) return fail(c, SS_ERR_INVALID, "ss_byte_get_tracks: no BYTE state or bad stream");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const SSByteDev& b = c->byte->dev;
-    int nt = 0, nl = 0, nid = 0, fr = 0;
-    std::vector<int> slots;
-    HIPCHK(c, hipMemcpy(&nid, b.next_id + s, 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&fr, b.frame + s, 4, hipMemcpyDeviceToHost));
-    const int rc = byte_read_lists(c, "ss_byte_get_tracks", s, cap, nt, nl, slots);
-    if (n_tracked) *n_tracked = nt;                                  // the counts also when cap is too small: the caller sizes by them
-    if (n_lost) *n_lost = nl;
-    if (next_id) *next_id = nid;
-    if (frame_id) *frame_id = fr;
-    if (rc) return rc;
-    const size_t T = SS_MAXT, sb = (size_t)s * T;
-    std::vector<int> st(T), act(T), id(T);
-    std::vector<double> mn(T * 8);
-    HIPCHK(c, hipMemcpy(st.data(), b.state + sb, T * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(act.data(), b.act + sb, T * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(id.data(), b.tid + sb, T * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(mn.data(), b.mean + sb * 8, T * 64, hipMemcpyDeviceToHost));
-    for (int i = 0; i < nt + nl; ++i) {
-        const int slot = slots[i];
-        if (track_id) track_id[i] = id[slot];
-        if (state) state[i] = st[slot];
-        if (activated) activated[i] = act[slot];
-        if (mean) for (int k = 0; k < 8; ++k) mean[i * 8 + k] = mn[slot * 8 + k];
-    }
-    return SS_OK;
+    SsByteRows r;
+    r.n_tracked = n_tracked; r.n_lost = n_lost; r.next_id = next_id; r.frame_id = frame_id; r.track_id = track_id; r.state = state; r.activated = activated; r.mean = mean;
+    return byte_get(c, "ss_byte_get_tracks", true, BYTE_OR_STREAM, s, cap, r);
+}
+
+extern "C" int ss_byte_get_features(ss_ctx* c, int s, int cap, float* smooth)
+{ SsByteRows r; r.smooth = smooth; return byte_get(c, "ss_byte_get_features", smooth, BYTE_OR_STREAM_NULL, s, cap, r); }
+
+extern "C" int ss_byte_get_keypoints(ss_ctx* c, int s, int cap, double* offsets, unsigned* visible)
+{ SsByteRows r; r.offsets = offsets; r.visible = visible; r.pose = true; return byte_get(c, "ss_byte_get_keypoints", true, BYTE_OR_STREAM, s, cap, r); }
+
+extern "C" int ss_byte_get_angles(ss_ctx* c, int s, int cap, float* angles)
+{ SsByteRows r; r.angles = angles; return byte_get(c, "ss_byte_get_angles", angles, BYTE_OR_STREAM_NULL, s, cap, r); }
+
+extern "C" int ss_byte_get_det_keypoints(ss_ctx* c, int frame, int s, float* xy, unsigned* visible)
+{
+    return tracker_run(c, "ss_byte_get_det_keypoints", c && c->byte && frame >= 0 && frame < SS_FMAX && xy && visible, "BYTE state, bad frame / stream or NULL", s, true,
+                       [&](std::string& err) { return ss_byte_get_det_keypoints_impl(c->byte, c->stream, frame, s, xy, visible, err); });
 }

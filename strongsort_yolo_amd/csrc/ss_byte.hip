@@ -714,3 +714,204 @@ void ss_launch_byte_group_obb(const SSByteDev& b0, int F, const float* dets, con
     if (b.xywh) hipLaunchKernelGGL((k_byte_group<true, false, false, false, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
     else hipLaunchKernelGGL((k_byte_group<false, false, false, false, true>), dim3(b.S), dim3(256), 0, st, b, F, dets, ndets, out, nout);
 }
+
+// ---- host side: the state of a context ------------------------------------------------------------------------------------------
+struct SSByte {
+    SSByteDev dev;
+    SsBuf<SS_DEVICE> base;              // the tables every mode has
+    SsBuf<SS_DEVICE> reid, pose, obb;   // a mode's own, carved when it is first switched on (pose: again for another n_kpt)
+};
+
+void ss_byte_free(SSByte* b) { delete b; }
+const SSByteDev& ss_byte_dev(const SSByte* b) { return b->dev; }
+int ss_byte_pending_impl(SSByte* B, hipStream_t st, std::string& err) { return B ? ss_tracker_pending_impl(B->dev.err, B->dev.S, st, "BYTE tracker", err) : (int)SS_OK; }
+
+int ss_byte_create_check_impl(const ss_byte_config* cfg, std::string& err)
+{
+    if (!cfg) { err = "ss_byte_create: null argument"; return SS_ERR_INVALID; }
+    if (cfg->max_tracks < 1 || cfg->max_tracks > SS_MAXT || cfg->max_dets < 1 || cfg->max_dets > SS_MAXD || cfg->frame_rate < 1 ||
+        cfg->track_buffer < 0 || (cfg->kalman_xywh != 0 && cfg->kalman_xywh != 1))
+        { err = "ss_byte_create: 1 <= max_tracks <= 256, 1 <= max_dets <= 128, frame_rate >= 1, kalman_xywh 0 / 1"; return SS_ERR_INVALID; }
+    return SS_OK;
+}
+
+// the streams' lists, counters, error words, warp flags and what the modes keep per track restart; synchronises
+static int byte_reset(const SSByteDev& b, hipStream_t st, SsWarpFlags wf, int stream, const char* who, std::string& err)
+{
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? b.S : stream + 1;
+    const std::vector<int> ones(b.S, 1);
+    SS_HIPCHK(who, hipMemsetAsync(b.frame + s0, 0, (s1 - s0) * 4, st));
+    SS_HIPCHK(who, hipMemsetAsync(b.err + s0, 0, (s1 - s0) * 4, st));
+    SS_HIPCHK(who, hipMemsetAsync(b.n_trk + s0, 0, (s1 - s0) * 4, st));
+    SS_HIPCHK(who, hipMemsetAsync(b.n_lost + s0, 0, (s1 - s0) * 4, st));
+    SS_HIPCHK(who, hipMemcpyAsync(b.next_id + s0, ones.data(), (s1 - s0) * 4, hipMemcpyHostToDevice, st));
+    SS_HIPCHK(who, hipMemsetAsync(wf.cmc + s0, 0, (s1 - s0) * 4, st));
+    SS_HIPCHK(who, hipMemsetAsync(wf.gmc + s0, 0, (s1 - s0) * 4, st));
+    if (b.smooth)                                                                        // §1c: the streams' track features
+        SS_HIPCHK(who, hipMemsetAsync(b.smooth + (size_t)s0 * SS_MAXT * SS_F, 0, (size_t)(s1 - s0) * SS_MAXT * SS_F * 4, st));
+    if (b.tpose) {                                                                       // §1e: the streams' track poses
+        SS_HIPCHK(who, hipMemsetAsync(b.tpose + (size_t)s0 * SS_MAXT * b.nk * 2, 0, (size_t)(s1 - s0) * SS_MAXT * b.nk * 2 * 8, st));
+        SS_HIPCHK(who, hipMemsetAsync(b.tvis + (size_t)s0 * SS_MAXT, 0, (size_t)(s1 - s0) * SS_MAXT * 4, st));
+    }
+    SS_HIPCHK(who, hipStreamSynchronize(st));
+    return SS_OK;
+}
+
+int ss_byte_reset_impl(SSByte* B, hipStream_t st, SsWarpFlags wf, int stream, std::string& err) { return byte_reset(B->dev, st, wf, stream, "ss_byte_reset: ", err); }
+
+// the caller has drained the stream and freed the state this one replaces: a failure leaves none attached
+int ss_byte_create_impl(SSByte** pb, hipStream_t st, SsWarpFlags wf, int n_streams, const ss_byte_config* cfg, std::string& err)
+{
+    std::unique_ptr<SSByte> B(new SSByte());
+    SSByteDev& b = B->dev;
+    memset(&b, 0, sizeof b);
+    b.S = n_streams;
+    b.xywh = cfg->kalman_xywh; b.fuse = cfg->fuse_score != 0;
+    b.max_time_lost = (int)(cfg->frame_rate / 30.0 * cfg->track_buffer);
+    b.max_tracks = cfg->max_tracks; b.max_dets = cfg->max_dets;
+    b.high = (float)cfg->track_high_thresh; b.low = (float)cfg->track_low_thresh; b.new_thresh = (float)cfg->new_track_thresh;
+    b.match = cfg->match_thresh; b.wp = cfg->std_weight_position; b.wv = cfg->std_weight_velocity;
+    const size_t S = b.S, T = SS_MAXT;
+    SsCarve c;
+    c.add(&b.frame, S); c.add(&b.next_id, S); c.add(&b.err, S); c.add(&b.n_trk, S); c.add(&b.n_lost, S);
+    c.add(&b.trk, S * T); c.add(&b.lost, S * T);
+    c.add(&b.state, S * T); c.add(&b.act, S * T); c.add(&b.tid, S * T); c.add(&b.start, S * T); c.add(&b.end, S * T); c.add(&b.len, S * T);
+    c.add(&b.det, S * T); c.add(&b.score, S * T); c.add(&b.cls, S * T);
+    c.add(&b.mean, S * T * 8); c.add(&b.cov, S * T * 64); c.add(&b.spill, S * T * SS_MAXD);
+    SS_HIPCHK("ss_byte_create: ", c.carve(B->base, st));
+    if (const int rc = byte_reset(b, st, wf, -1, "ss_byte_create: ", err)) return rc;
+    *pb = B.release();
+    return SS_OK;
+}
+
+// The mode switches (ReID §1c, the keypoint term §1e, oriented boxes docs/OBB.md §4), on != 0 or off; either way every stream restarts.
+// A mode's tables are carved when it is first switched on, and kept.  The modes are not combined, and xyah has none but obb.
+int ss_byte_set_reid_impl(SSByte* B, hipStream_t st, SsWarpFlags wf, int on, double proximity_thresh, double appearance_thresh, double alpha, std::string& err)
+{
+    const char* who = "ss_byte_set_reid: ";
+    SSByteDev& b = B->dev;
+    auto bad = [&](const char* why) { err = std::string(who) + why; return (int)SS_ERR_INVALID; };
+    if (on && !b.xywh) return bad("ReID needs the xywh (BoT-SORT) state");
+    if (on && b.pose) return bad("the keypoint term is on (ss_byte_set_pose): the two are not combined");
+    if (on && b.obb) return bad("oriented boxes are on (ss_byte_set_obb): the two are not combined");
+    if (on && !b.smooth) {
+        SsCarve c;
+        c.add(&b.smooth, (size_t)b.S * SS_MAXT * SS_F); c.add(&b.ufeat, (size_t)SS_FMAX * b.S * SS_MAXD * SS_F);
+        SS_HIPCHK(who, c.carve(B->reid, st));
+    }
+    b.reid = on != 0;
+    b.prox = proximity_thresh; b.appear = appearance_thresh;
+    b.alpha = (float)alpha; b.one_minus_alpha = (float)(1.0 - alpha);
+    return byte_reset(b, st, wf, -1, who, err);
+}
+
+// (another n_kpt carves the pose tables again out of the same buffer, which grows only when it has to; the stream is drained first,
+// so nothing reads the old tables any more)
+int ss_byte_set_pose_impl(SSByte* B, hipStream_t st, SsWarpFlags wf, int on, int n_kpt, const double* sigmas, double proximity_thresh, double pose_thresh,
+                          double vis_thresh, int min_common, std::string& err)
+{
+    const char* who = "ss_byte_set_pose: ";
+    SSByteDev& b = B->dev;
+    auto bad = [&](const char* why) { err = std::string(who) + why; return (int)SS_ERR_INVALID; };
+    if (on) {
+        if (!b.xywh) return bad("the keypoint term needs the xywh (BoT-SORT) state");
+        if (b.reid) return bad("ReID is on (ss_byte_set_reid): the two are not combined");
+        if (b.obb) return bad("oriented boxes are on (ss_byte_set_obb): the two are not combined");
+        if (n_kpt < 1 || n_kpt > SS_BYTE_MAXK) return bad("1 <= n_kpt <= 32");
+        if (!sigmas) return bad("sigmas is NULL");
+        b.pose = 0;                                                // a failure below leaves the term off, never half set up
+        SS_HIPCHK(who, hipStreamSynchronize(st));
+        if (!b.tpose || b.nk != n_kpt) {
+            const size_t nt = (size_t)b.S * SS_MAXT, nd = (size_t)SS_FMAX * b.S * SS_MAXD;
+            SsCarve c;
+            c.add(&b.tpose, nt * n_kpt * 2); c.add(&b.tvis, nt); c.add(&b.kp, nd * n_kpt * 2); c.add(&b.kvis, nd); c.add(&b.ks2, (size_t)SS_BYTE_MAXK);
+            b.tpose = nullptr; b.kp = nullptr;                     // a carve that fails may have released the old tables
+            SS_HIPCHK(who, c.carve(B->pose, st));
+            b.nk = n_kpt;
+        }
+        double s2[SS_BYTE_MAXK] = {0.0};
+        for (int k = 0; k < n_kpt; ++k) s2[k] = 2.0 * sigmas[k];
+        SS_HIPCHK(who, hipMemcpyAsync((void*)b.ks2, s2, sizeof s2, hipMemcpyHostToDevice, st));      // on st: behind the carve's memset of the range
+        SS_HIPCHK(who, hipStreamSynchronize(st));                  // s2 is this frame's
+        b.prox = proximity_thresh; b.pose_thresh = pose_thresh; b.vis = (float)vis_thresh; b.min_common = min_common;
+    }
+    b.pose = on != 0;
+    return byte_reset(b, st, wf, -1, who, err);
+}
+
+int ss_byte_set_obb_impl(SSByte* B, hipStream_t st, SsWarpFlags wf, int on, std::string& err)
+{
+    SSByteDev& b = B->dev;
+    if (on && (b.reid || b.pose || b.gmc)) { err = "ss_byte_set_obb: ReID, the keypoint term or GMC is on: oriented boxes are not combined with them"; return SS_ERR_INVALID; }
+    if (on && !b.angle) {
+        const size_t nt = (size_t)b.S * SS_MAXT, nd = (size_t)b.S * SS_MAXD;
+        SsCarve c;
+        c.add(&b.angle, nt); c.add(&b.tbox, nt * 6); c.add(&b.dbox, nd * 6);
+        SS_HIPCHK("ss_byte_set_obb: ", c.carve(B->obb, st));
+    }
+    b.obb = on != 0;
+    return byte_reset(b, st, wf, -1, "ss_byte_set_obb: ", err);
+}
+
+// BoT-SORT GMC (docs/BYTETRACK.md §1b): the pointer goes into the launch arguments.  NULL: off.  xyah (ByteTrack) has no GMC (G-05).
+int ss_byte_set_gmc_impl(SSByte* B, const double* d_warps, std::string& err)
+{
+    if (d_warps && !B->dev.xywh) { err = "ss_byte_set_gmc: GMC needs the xywh (BoT-SORT) state"; return SS_ERR_INVALID; }
+    if (d_warps && B->dev.obb) { err = "ss_byte_set_gmc: oriented boxes are on (ss_byte_set_obb): GMC does not move rotated tracks"; return SS_ERR_INVALID; }
+    B->dev.gmc = d_warps;
+    return SS_OK;
+}
+
+// Synchronous: one stream's lists and, in list order (tracked, then lost), the per-track tables r asks for (SsByteRows, ss_launch.h)
+int ss_byte_get_impl(SSByte* B, hipStream_t st, const char* entry, int s, int cap, const SsByteRows& r, std::string& err)
+{
+    const std::string who = std::string(entry) + ": ";
+    const SSByteDev& b = B->dev;
+    auto bad = [&](int rc, const char* why) { err = who + why; return rc; };
+    if (r.smooth && !b.smooth) return bad(SS_ERR_INVALID, "ReID was never switched on (ss_byte_set_reid)");
+    if ((r.pose || r.offsets || r.visible) && !b.tpose) return bad(SS_ERR_INVALID, "the keypoint term was never switched on (ss_byte_set_pose)");
+    if (r.angles && !b.angle) return bad(SS_ERR_INVALID, "oriented boxes were never switched on (ss_byte_set_obb)");
+    SS_HIPCHK(who, hipStreamSynchronize(st));
+    int nt = 0, nl = 0, nid = 0, fr = 0;
+    SS_HIPCHK(who, hipMemcpy(&nid, b.next_id + s, 4, hipMemcpyDeviceToHost));
+    SS_HIPCHK(who, hipMemcpy(&fr, b.frame + s, 4, hipMemcpyDeviceToHost));
+    SS_HIPCHK(who, hipMemcpy(&nt, b.n_trk + s, 4, hipMemcpyDeviceToHost));
+    SS_HIPCHK(who, hipMemcpy(&nl, b.n_lost + s, 4, hipMemcpyDeviceToHost));
+    if (r.n_tracked) *r.n_tracked = nt;
+    if (r.n_lost) *r.n_lost = nl;
+    if (r.next_id) *r.next_id = nid;
+    if (r.frame_id) *r.frame_id = fr;
+    if (nt < 0 || nl < 0) return bad(SS_ERR_CAPACITY, "corrupt list");
+    const int n = nt + nl;
+    if (n > cap) return bad(SS_ERR_CAPACITY, "cap too small");
+    const size_t T = SS_MAXT, sb = (size_t)s * T;
+    std::vector<int> trk(T), lost(T), slots(n);
+    SS_HIPCHK(who, hipMemcpy(trk.data(), b.trk + sb, T * 4, hipMemcpyDeviceToHost));
+    SS_HIPCHK(who, hipMemcpy(lost.data(), b.lost + sb, T * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {
+        slots[i] = i < nt ? trk[i] : lost[i - nt];
+        if (slots[i] < 0 || slots[i] >= SS_MAXT) return bad(SS_ERR_CAPACITY, "corrupt list");
+    }
+    SS_HIPCHK(who, ss_gather_device(slots.data(), n, b.tid + sb, T, 1, r.track_id));
+    SS_HIPCHK(who, ss_gather_device(slots.data(), n, b.state + sb, T, 1, r.state));
+    SS_HIPCHK(who, ss_gather_device(slots.data(), n, b.act + sb, T, 1, r.activated));
+    SS_HIPCHK(who, ss_gather_device(slots.data(), n, b.mean + sb * 8, T, 8, r.mean));
+    if (r.smooth) SS_HIPCHK(who, ss_gather_device(slots.data(), n, b.smooth + sb * SS_F, T, SS_F, r.smooth));
+    if (r.offsets) SS_HIPCHK(who, ss_gather_device(slots.data(), n, b.tpose + sb * b.nk * 2, T, b.nk * 2, r.offsets));
+    if (r.visible) SS_HIPCHK(who, ss_gather_device(slots.data(), n, b.tvis + sb, T, 1, r.visible));
+    if (r.angles) SS_HIPCHK(who, ss_gather_device(slots.data(), n, b.angle + sb, T, 1, r.angles));
+    return SS_OK;
+}
+
+// Synchronous: what k_byte_kpts wrote for image (frame, stream) of the last ss_byte_update_group_kpts call
+int ss_byte_get_det_keypoints_impl(SSByte* B, hipStream_t st, int frame, int s, float* xy, unsigned* visible, std::string& err)
+{
+    const char* who = "ss_byte_get_det_keypoints: ";
+    const SSByteDev& b = B->dev;
+    if (!b.kp) { err = std::string(who) + "the keypoint term was never switched on (ss_byte_set_pose)"; return SS_ERR_INVALID; }
+    SS_HIPCHK(who, hipStreamSynchronize(st));
+    const size_t fs = (size_t)frame * b.S + s;
+    SS_HIPCHK(who, hipMemcpy(xy, b.kp + fs * SS_MAXD * b.nk * 2, (size_t)SS_MAXD * b.nk * 2 * 4, hipMemcpyDeviceToHost));
+    SS_HIPCHK(who, hipMemcpy(visible, b.kvis + fs * SS_MAXD, (size_t)SS_MAXD * 4, hipMemcpyDeviceToHost));
+    return SS_OK;
+}

@@ -226,3 +226,78 @@ void ss_launch_deepoc_group(const SSDeepOcDev& x, int F, const float* dets, cons
     if (x.appearance) hipLaunchKernelGGL(k_deepoc_feats, dim3(SS_MAXD / 4, x.oc.S, F), dim3(256), 0, st, x, dets, feats, ndets);
     hipLaunchKernelGGL(k_deepoc_group, dim3(x.oc.S), dim3(256), 0, st, x, F, dets, ndets, out, nout);
 }
+
+// ---- host side: the state of a context; dev.oc's tables, reset and read-back are ss_ocsort.hip's (ss_oc_*) ---------------------------
+struct SSDeepOc {
+    SSDeepOcDev dev;
+    SsBuf<SS_DEVICE> base, feat;        // dev.oc's tables; emb, ufeat and E
+};
+
+void ss_deepoc_free(SSDeepOc* d) { delete d; }
+const SSDeepOcDev& ss_deepoc_dev(const SSDeepOc* d) { return d->dev; }
+void ss_deepoc_set_gmc_impl(SSDeepOc* d, const double* d_warps) { d->dev.gmc = d_warps; }
+int ss_deepoc_pending_impl(SSDeepOc* d, hipStream_t st, std::string& err) { return d ? ss_tracker_pending_impl(d->dev.oc.err, d->dev.oc.S, st, "Deep OC-SORT tracker", err) : (int)SS_OK; }
+
+int ss_deepoc_create_check_impl(const ss_deepoc_config* cfg, std::string& err)
+{
+    if (!cfg) { err = "ss_deepoc_create: null argument"; return SS_ERR_INVALID; }
+    auto flag = [](int v) { return v == 0 || v == 1; };
+    if (cfg->max_tracks < 1 || cfg->max_tracks > SS_MAXT || cfg->max_dets < 1 || cfg->max_dets > SS_MAXD || cfg->delta_t < 1 ||
+        cfg->delta_t > SS_OC_MAXDT || cfg->max_age < 1 || cfg->min_hits < 0 || !(cfg->iou_threshold > 0.0 && cfg->iou_threshold <= 1.0) ||
+        !(cfg->inertia >= 0.0) || !(cfg->det_thresh < 1.0) || !(cfg->w_association_emb >= 0.0) ||
+        !(cfg->alpha_fixed_emb >= 0.0 && cfg->alpha_fixed_emb <= 1.0) || !(cfg->aw_param >= 0.0 && cfg->aw_param < 1.0) ||
+        !flag(cfg->appearance) || !flag(cfg->dynamic_appearance) || !flag(cfg->adaptive_weighting)) {
+        err = "ss_deepoc_create: 1 <= max_tracks <= 256, 1 <= max_dets <= 128, 1 <= delta_t <= 8, max_age >= 1, "
+              "min_hits >= 0, 0 < iou_threshold <= 1, inertia >= 0, det_thresh < 1, w_association_emb >= 0, "
+              "0 <= alpha_fixed_emb <= 1, 0 <= aw_param < 1, flags 0 / 1";
+        return SS_ERR_INVALID;
+    }
+    return SS_OK;
+}
+
+// the streams restart: their warp flags and track features, then what an OC-SORT state resets; synchronises
+static int deepoc_reset(const SSDeepOcDev& d, hipStream_t st, SsWarpFlags wf, int stream, const char* who, std::string& err)
+{
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? d.oc.S : stream + 1;
+    SS_HIPCHK(who, hipMemsetAsync(wf.cmc + s0, 0, (s1 - s0) * 4, st));
+    SS_HIPCHK(who, hipMemsetAsync(wf.gmc + s0, 0, (s1 - s0) * 4, st));
+    SS_HIPCHK(who, hipMemsetAsync(d.emb + (size_t)s0 * SS_MAXT * SS_F, 0, (size_t)(s1 - s0) * SS_MAXT * SS_F * 4, st));
+    return ss_oc_reset_impl(d.oc, st, stream, who, err);
+}
+
+int ss_deepoc_reset_impl(SSDeepOc* d, hipStream_t st, SsWarpFlags wf, int stream, std::string& err) { return deepoc_reset(d->dev, st, wf, stream, "ss_deepoc_reset: ", err); }
+
+// the caller has drained the stream and freed the state this one replaces: a failure leaves none attached
+int ss_deepoc_create_impl(SSDeepOc** pd, hipStream_t st, SsWarpFlags wf, int S, const ss_deepoc_config* cfg, std::string& err)
+{
+    const char* who = "ss_deepoc_create: ";
+    std::unique_ptr<SSDeepOc> D(new SSDeepOc());
+    SSDeepOcDev& d = D->dev;
+    memset(&d, 0, sizeof d);
+    SSOcDev& o = d.oc;
+    o.S = S;
+    o.max_age = cfg->max_age; o.min_hits = cfg->min_hits; o.delta_t = cfg->delta_t; o.use_byte = 0;
+    o.max_tracks = cfg->max_tracks; o.max_dets = cfg->max_dets;
+    o.det_thresh = (float)cfg->det_thresh; o.low_thresh = (float)cfg->det_thresh;
+    o.iou_thr = cfg->iou_threshold; o.inertia = cfg->inertia;
+    d.appearance = cfg->appearance; d.dynamic = cfg->dynamic_appearance; d.adaptive = cfg->adaptive_weighting;
+    d.det_thresh = cfg->det_thresh; d.w_emb = cfg->w_association_emb; d.alpha_fixed = cfg->alpha_fixed_emb; d.aw = cfg->aw_param;
+    SsCarve c;
+    c.add(&d.emb, (size_t)S * SS_MAXT * SS_F); c.add(&d.ufeat, (size_t)SS_FMAX * S * SS_MAXD * SS_F); c.add(&d.E, (size_t)S * SS_MAXT * SS_MAXD);
+    if (const int rc = ss_oc_carve_impl(o, D->base, st, who, err)) return rc;
+    SS_HIPCHK(who, c.carve(D->feat, st));
+    if (const int rc = deepoc_reset(d, st, wf, -1, who, err)) return rc;
+    *pd = D.release();
+    return SS_OK;
+}
+
+// Synchronous: the tracks' unit features [n][512] of one stream in ss_deepoc_get_tracks' list order
+int ss_deepoc_get_features_impl(SSDeepOc* d, hipStream_t st, int s, int cap, float* emb, std::string& err)
+{
+    const auto none = nullptr;
+    std::vector<int> slots;
+    if (const int rc = ss_oc_get_tracks_impl(d->dev.oc, st, "ss_deepoc_get_features", s, cap, none, none, none, none, none, none, none, none, none, none,
+                                             none, none, none, &slots, err)) return rc;
+    SS_HIPCHK("ss_deepoc_get_features: ", ss_gather_device(slots.data(), (int)slots.size(), d->dev.emb + (size_t)s * SS_MAXT * SS_F, SS_MAXT, SS_F, emb));
+    return SS_OK;
+}

@@ -1,7 +1,10 @@
 // ss_host.h — host staging shared by every entry that moves data around a launch: an owning, growable buffer, an event owner,
-// the HIP check of the *_impl functions, image layout arithmetic and the small thread pool of the batch copies.  Host code only.
+// the HIP check of the *_impl functions, image layout arithmetic, the carve-out and list-order read-back of a state's tables and the
+// small thread pool of the batch copies.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -66,6 +69,52 @@ struct SsLayout {
     size_t at = 0, align = 16;
     size_t take(size_t bytes) { const size_t o = at; at = ss_align_up(at + bytes, align); return o; }
 };
+
+// Where tables of bytes[0..n) start in one buffer that holds them in this order, each on a 256-byte boundary (what an allocation of
+// its own gave it) -> off[0..n); returns the buffer's size
+static inline size_t ss_carve_plan(const size_t* bytes, size_t n, size_t* off)
+{
+    SsLayout l{0, 256};
+    for (size_t i = 0; i < n; ++i) off[i] = l.take(bytes[i]);
+    return l.at;
+}
+
+// The tables of one lifetime group out of one owned device buffer: add() registers a table's pointer field and element count; carve()
+// plans the offsets, reserves, zeroes the whole range on `st` and only then assigns the fields
+struct SsCarve {
+    std::vector<void*> field;                           // each the address of a T* of the state's argument struct
+    std::vector<size_t> bytes;
+    template <class T> void add(T** f, size_t n) { field.push_back((void*)f); bytes.push_back(n * sizeof(T)); }
+    hipError_t carve(SsBuf<SS_DEVICE>& buf, hipStream_t st) const
+    {
+        std::vector<size_t> off(bytes.size());
+        const size_t total = ss_carve_plan(bytes.data(), bytes.size(), off.data());
+        hipError_t e = buf.reserve(total, SS_EXACT);
+        if (e == hipSuccess) e = hipMemsetAsync(buf.as(), 0, total, st);
+        for (size_t i = 0; e == hipSuccess && i < field.size(); ++i) { void* p = buf.as() + off[i]; memcpy(field[i], &p, sizeof p); }
+        return e;
+    }
+};
+
+// Rows of a [rows][width] table in list order: dst[i * width + k] = src[slots[i] * width + k] for i < n; a NULL dst asks for nothing.
+// ss_gather_device is what the read-backs call: it fetches the table from the device first (the stream has been drained) and hands the
+// host copy to ss_gather_rows, which is apart so that a host program can check it without a device (tests/tracker_state_host_main.cpp).
+template <class T>
+static inline void ss_gather_rows(const int* slots, int n, const T* src, int width, T* dst)
+{
+    for (int i = 0; dst && i < n; ++i)
+        for (int k = 0; k < width; ++k) dst[(size_t)i * width + k] = src[(size_t)slots[i] * width + k];
+}
+
+template <class T>
+static hipError_t ss_gather_device(const int* slots, int n, const T* d_src, size_t rows, int width, T* dst)
+{
+    if (!dst) return hipSuccess;
+    std::vector<T> h(rows * width);
+    const hipError_t e = hipMemcpy(h.data(), d_src, h.size() * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) ss_gather_rows(slots, n, h.data(), width, dst);
+    return e;
+}
 
 // work(t, T) for t = 0 .. T - 1, t = 0 on the calling thread.  Threads that cannot be started have their share done by the
 // caller; false on any exception, since nothing thrown may cross the C boundary.

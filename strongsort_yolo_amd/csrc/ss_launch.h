@@ -1,10 +1,12 @@
 // ss_launch.h — what ss_api.hip calls in the other translation units, declared once with the definitions' parameter names:
-// the kernel launchers and the host-side state of the JPEG, GSI, MOT and AFLink stages.  ss_api.hip and every file that defines one of
+// the kernel launchers and the host-side state of the stages and the tracker families.  ss_api.hip and every file that defines one of
 // these include it, so each definition is compiled next to its declaration.  C++ linkage: none of this is part of the C ABI.
 // (What those states are made of, the owning buffers and the HIP check of the *_impl functions, is in ss_host.h.)
 #pragma once
 #include <string>
+#include <vector>
 #include "ss_common.h"
+#include "ss_host.h"
 
 // ---- ss_track.hip: StrongSORT tracker chain and the stage kernels behind the known-answer entry points
 void   ss_step_kernel_attr();
@@ -72,6 +74,54 @@ void ss_launch_deepoc_group(const SSDeepOcDev& x, int F, const float* dets, cons
 void ss_launch_native_feats(int n_img, int half, const void* const* p, const long long* img_stride, const long long* row_stride,
                             const long long* pix_stride, const int* channels, const int* height, const int* width, int s,
                             const int* keep, long long keep_stride, const int* counts, float* out, hipStream_t st);
+
+// ---- the tracker families' states of a context: BYTE (ss_byte.hip), OC-SORT (ss_ocsort.hip), Deep OC-SORT (ss_deepoc.hip).
+// `entry` is the C entry's name (`who`: with its ": ").  create replaces a state (the caller has drained the stream) and leaves none on
+// failure; create, reset and every get synchronise.  SsWarpFlags: the context's per-stream flags of the two warp estimators (G-04).
+struct SsWarpFlags { int *cmc, *gmc; };
+int  ss_tracker_pending_impl(const int* d_err, int S, hipStream_t st, const char* family, std::string& err);
+struct SSByte;
+const SSByteDev& ss_byte_dev(const SSByte* b);
+int  ss_byte_create_check_impl(const ss_byte_config* cfg, std::string& err);
+int  ss_byte_create_impl(SSByte** pb, hipStream_t st, SsWarpFlags wf, int n_streams, const ss_byte_config* cfg, std::string& err);
+int  ss_byte_reset_impl(SSByte* B, hipStream_t st, SsWarpFlags wf, int stream, std::string& err);
+int  ss_byte_set_reid_impl(SSByte* B, hipStream_t st, SsWarpFlags wf, int on, double proximity_thresh, double appearance_thresh, double alpha, std::string& err);
+int  ss_byte_set_pose_impl(SSByte* B, hipStream_t st, SsWarpFlags wf, int on, int n_kpt, const double* sigmas, double proximity_thresh, double pose_thresh,
+                           double vis_thresh, int min_common, std::string& err);
+int  ss_byte_set_obb_impl(SSByte* B, hipStream_t st, SsWarpFlags wf, int on, std::string& err);
+int  ss_byte_set_gmc_impl(SSByte* B, const double* d_warps, std::string& err);
+int  ss_byte_pending_impl(SSByte* B, hipStream_t st, std::string& err);
+// what a BYTE read-back fills: each NULL or room for cap rows (the counts: one int, written also when cap is too small)
+struct SsByteRows {
+    int *n_tracked = nullptr, *n_lost = nullptr, *next_id = nullptr, *frame_id = nullptr;
+    int *track_id = nullptr, *state = nullptr, *activated = nullptr;
+    double* mean = nullptr;
+    float *smooth = nullptr, *angles = nullptr;         // ReID's, oriented boxes': refused when the mode was never switched on, as are
+    double* offsets = nullptr; unsigned* visible = nullptr; bool pose = false;      // the keypoints' (pose: their entry; it may ask for neither)
+};
+int  ss_byte_get_impl(SSByte* B, hipStream_t st, const char* entry, int s, int cap, const SsByteRows& r, std::string& err);
+int  ss_byte_get_det_keypoints_impl(SSByte* B, hipStream_t st, int frame, int s, float* xy, unsigned* visible, std::string& err);
+void ss_byte_free(SSByte* b);
+struct SSOc;
+struct SSDeepOc;
+const SSOcDev& ss_ocsort_dev(const SSOc* o);            // the launch arguments: for the launchers, the entries' mode checks and the
+const SSDeepOcDev& ss_deepoc_dev(const SSDeepOc* d);    // ss_oc_* functions, which serve both OC-SORT families
+int  ss_oc_carve_impl(SSOcDev& o, SsBuf<SS_DEVICE>& buf, hipStream_t st, const char* who, std::string& err);
+int  ss_oc_reset_impl(const SSOcDev& o, hipStream_t st, int stream, const char* who, std::string& err);
+int  ss_oc_get_tracks_impl(const SSOcDev& o, hipStream_t st, const char* entry, int s, int cap, int* n_tracks, int* next_id, int* frame_count,
+                           int* track_id, int* age, int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P,
+                           float* last_obs, double* velocity, std::vector<int>* slots, std::string& err);
+int  ss_ocsort_create_check_impl(const ss_ocsort_config* cfg, std::string& err);
+int  ss_ocsort_create_impl(SSOc** po, hipStream_t st, int S, const ss_ocsort_config* cfg, std::string& err);
+int  ss_ocsort_pending_impl(SSOc* o, hipStream_t st, std::string& err);
+void ss_ocsort_free(SSOc* o);
+int  ss_deepoc_create_check_impl(const ss_deepoc_config* cfg, std::string& err);
+int  ss_deepoc_create_impl(SSDeepOc** pd, hipStream_t st, SsWarpFlags wf, int S, const ss_deepoc_config* cfg, std::string& err);
+int  ss_deepoc_reset_impl(SSDeepOc* d, hipStream_t st, SsWarpFlags wf, int stream, std::string& err);
+void ss_deepoc_set_gmc_impl(SSDeepOc* d, const double* d_warps);
+int  ss_deepoc_get_features_impl(SSDeepOc* d, hipStream_t st, int s, int cap, float* emb, std::string& err);
+int  ss_deepoc_pending_impl(SSDeepOc* d, hipStream_t st, std::string& err);
+void ss_deepoc_free(SSDeepOc* d);
 
 // ---- ss_jpeg.hip: decoder state of a context (created on first use)
 struct SSJpeg;

@@ -324,8 +324,6 @@ int ss_bank_reset_impl(SSBank* b, hipStream_t st, int stream, std::string& err)
 int ss_bank_create_impl(SSBank** pb, hipStream_t st, int S, int max_ids, std::string& err)
 {
     const char* who = "ss_bank_create: ";
-    ss_bank_free(*pb);
-    *pb = nullptr;
     SSBank* b = new SSBank();
     SSBankDev& d = b->dev;
     memset(&d, 0, sizeof d);

@@ -449,8 +449,6 @@ int ss_zone_create_impl(SSZone** pz, hipStream_t st, int S, const ss_zone_config
                         const int* poly_off, int n_zones, std::string& err)
 {
     const char* who = "ss_zone_create: ";
-    ss_zone_free(*pz);
-    *pz = nullptr;
     SSZone* z = new SSZone();
     z->cfg = *cfg;
     SSZoneDev& d = z->dev;

@@ -913,20 +913,78 @@ class TrackerEngine:
         return out
 
 
-class ByteTrackEngine:
+class _AttachedTracker:
+    """A tracker family attached to the context of a TrackerEngine: what ByteTrackEngine, OCSortEngine and DeepOCSortEngine share.
+    `engine`: the TrackerEngine whose context (NMS, streams, error words) the tracker shares; None: a context of its own."""
+    # the class's name in its messages; the family's destroy and reset entries; the setting that makes update calls read features
+    _name = _destroy = _reset = _feats_need = ""
+    _delegated = ("use_stream", "use_current_stream", "check_errors")      # the context's own, under the tracker's name too
+    reid = pose = False
+
+    def __init__(self, n_streams: int, device: int, engine):
+        self._own = engine is None
+        self.base = TrackerEngine(StrongSortConfig(), n_streams, device) if engine is None else engine
+        self.S, self.device, self.L = self.base.S, self.base.device, self.base.L
+        self.out = torch.zeros(self.S, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=self.device)
+        self.nout = torch.zeros(self.S, dtype=torch.int32, device=self.device)
+        for name in self._delegated:
+            setattr(self, name, getattr(self.base, name))
+
+    @property
+    def ctx(self):
+        return self.base.ctx
+
+    @property
+    def max_group_frames(self) -> int:
+        return self.base.max_group_frames
+
+    def _ck(self, rc):
+        _lib.check(self.base.ctx, rc)
+
+    def close(self):
+        if self._own:
+            self.base.close()
+        elif getattr(self.base, "ctx", None) and self.base.ctx.value:
+            torch.cuda.synchronize(self.device)
+            self._ck(getattr(self.L, self._destroy)(self.base.ctx))
+
+    def reset(self, stream: int = -1):
+        """Restart the stream(s) (-1: all): ids from 1, frame count 0, and whatever else the family keeps per stream (BYTE and Deep
+        OC-SORT: the tracks' features or poses, and the next estimated frame gets no warp, G-04)."""
+        self._ck(getattr(self.L, self._reset)(self.base.ctx, stream))
+
+    def _feats(self, feats, rows):
+        if not self.reid:
+            return None
+        if feats is None:
+            raise ValueError(f"{self._name}: {self._feats_need} needs the detections' features [.., 128, 512] f32")
+        if feats.dtype != torch.float32 or not feats.is_contiguous() or feats.numel() != rows * MAX_DETS * FEAT_DIM:
+            raise ValueError(f"{self._name}: feats must be contiguous float32 [{rows} x {MAX_DETS} x {FEAT_DIM}]")
+        return feats
+
+    def update_device(self, dets, ndets, feats=None, img_hw=None, out=None, nout=None):
+        """All streams, one frame: dets [S,128,6] f32, ndets [S] i32, feats [S,128,512] f32 (raw, device; read by the trackers that use
+        features) -> (rows [S,256,8], counts [S]) device tensors, asynchronous; the engine's own unless out / nout are given.  img_hw is
+        accepted for TrackerEngine's call shape and unused."""
+        return self.update_group(1, dets, ndets, feats, img_hw, self.out if out is None else out, self.nout if nout is None else nout)
+
+
+class ByteTrackEngine(_AttachedTracker):
     """The BYTE tracker family (csrc/ss_byte.hip, docs/BYTETRACK.md) on the context of a TrackerEngine: the same
     update_device / update_group / reset / check_errors shape as TrackerEngine; features only with cfg.with_reid (§1c, BoT-SORT's
     ReID branch, switched on at construction), keypoints only with cfg.with_pose (§1e, the OKS term, likewise).  `engine`: share the
     context of an existing TrackerEngine (a pipeline's: its NMS, streams and error words); None: a context of its own."""
+
+    _name, _destroy, _reset, _feats_need = "ByteTrackEngine", "ss_byte_destroy", "ss_byte_reset", "with_reid"
+    # the context's own: streams, error words, the warps of a group (N4: frames uint8 [F*S,H,W,3] -> [F,S,8]) and their stages
+    _delegated = _AttachedTracker._delegated + ("cmc_estimate", "gmc_sparse_estimate", "estimate_warps", "gmc_sparse_stages", "cmc_small")
 
     def __init__(self, cfg: ByteTrackConfig | None = None, n_streams: int = 1, device: int = 0, engine: TrackerEngine | None = None,
                  obb: bool = False):
         self.cfg = cfg or ByteTrackConfig()
         if obb and (self.cfg.with_reid or self.cfg.with_pose):
             raise ValueError("ByteTrackEngine: oriented boxes (obb=True) are not combined with with_reid or with_pose (docs/OBB.md §4)")
-        self._own = engine is None
-        self.base = TrackerEngine(StrongSortConfig(), n_streams, device) if engine is None else engine
-        self.S, self.device, self.L = self.base.S, self.base.device, self.base.L
+        super().__init__(n_streams, device, engine)
         c = _lib.make_byte_config(self.cfg)
         self._ck(self.L.ss_byte_create(self.base.ctx, C.byref(c)))
         self.reid = bool(self.cfg.with_reid)
@@ -943,31 +1001,6 @@ class ByteTrackEngine:
         if obb:                                     # docs/OBB.md §4: association on ProbIoU, 11-column rows (resets the streams)
             self.set_obb(True)
         self._cmc_keep = None
-        self.out = torch.zeros(self.S, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=self.device)
-        self.nout = torch.zeros(self.S, dtype=torch.int32, device=self.device)
-        # the context's own: streams, error words, group size, the ECC warps of a group (N4: frames uint8 [F*S,H,W,3] -> [F,S,8])
-        self.use_stream, self.use_current_stream = self.base.use_stream, self.base.use_current_stream
-        self.check_errors, self.cmc_estimate = self.base.check_errors, self.base.cmc_estimate
-        self.gmc_sparse_estimate, self.estimate_warps = self.base.gmc_sparse_estimate, self.base.estimate_warps
-        self.gmc_sparse_stages, self.cmc_small = self.base.gmc_sparse_stages, self.base.cmc_small
-
-    @property
-    def ctx(self):
-        return self.base.ctx
-
-    def _ck(self, rc):
-        _lib.check(self.base.ctx, rc)
-
-    def close(self):
-        if self._own:
-            self.base.close()
-        elif getattr(self.base, "ctx", None) and self.base.ctx.value:
-            torch.cuda.synchronize(self.device)
-            self._ck(self.L.ss_byte_destroy(self.base.ctx))
-
-    def reset(self, stream: int = -1):
-        """Restart the stream(s): ids from 1, and the next cmc_estimate frame gets no warp (G-04)."""
-        self._ck(self.L.ss_byte_reset(self.base.ctx, stream))
 
     def set_obb(self, on: bool):
         """docs/OBB.md §4: association on ProbIoU of rotated boxes on or off; every stream restarts.  While on, update_group takes
@@ -990,19 +1023,6 @@ class ByteTrackEngine:
         self._ck(self.L.ss_byte_set_gmc(self.base.ctx, _ptr(warps)))
         self._cmc_keep = warps
 
-    @property
-    def max_group_frames(self) -> int:
-        return self.base.max_group_frames
-
-    def _feats(self, feats, rows):
-        if not self.reid:
-            return None
-        if feats is None:
-            raise ValueError("ByteTrackEngine: with_reid needs the detections' features [.., 128, 512] f32")
-        if feats.dtype != torch.float32 or not feats.is_contiguous() or feats.numel() != rows * MAX_DETS * FEAT_DIM:
-            raise ValueError(f"ByteTrackEngine: feats must be contiguous float32 [{rows} x {MAX_DETS} x {FEAT_DIM}]")
-        return feats
-
     def _kpts(self, kpts, rows, kpt_col, geom):
         """with_pose: the rows' keypoints as (tensor, row stride, column, geometry) for ss_byte_update_group_kpts.  kpts: float32,
         [rows x 128 x C] with unit column stride — [.., K, 3] triplets (kpt_col 0) or whole NMS rows with the triplets from column
@@ -1022,9 +1042,8 @@ class ByteTrackEngine:
         """All streams, one frame: dets [S,128,6] f32, ndets [S] i32, with ReID feats [S,128,512] f32 (raw, device), with the
         keypoint term kpts (see update_group) -> (rows [S,256,8], counts [S]) device tensors, asynchronous.  img_hw is accepted
         for TrackerEngine's call shape and unused (no clipping); feats is unused without ReID."""
-        out = self.out if out is None else out
-        nout = self.nout if nout is None else nout
-        return self.update_group(1, dets, ndets, feats, img_hw, out, nout, kpts=kpts, kpt_col=kpt_col, geom=geom)
+        return self.update_group(1, dets, ndets, feats, img_hw, self.out if out is None else out, self.nout if nout is None else nout,
+                                 kpts=kpts, kpt_col=kpt_col, geom=geom)
 
     def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout, kpts=None, kpt_col=0, geom=None, rbox=None):
         """A group of n_frames (<= 32) frames of all streams in ONE launch: dets [F,S,128,6] f32, ndets [F,S] i32, with ReID
@@ -1095,53 +1114,18 @@ class ByteTrackEngine:
                     n_tracked=nt.value, n_lost=nl.value, next_id=nid.value, frame_id=fr.value)
 
 
-class OCSortEngine:
+class OCSortEngine(_AttachedTracker):
     """OC-SORT (csrc/ss_ocsort.hip, docs/OCSORT.md) on the context of a TrackerEngine: the same update_device / update_group /
     reset / check_errors shape as ByteTrackEngine, without features, keypoints or warps.  `engine`: share the context of an
     existing TrackerEngine (a pipeline's: its NMS, streams and error words); None: a context of its own."""
 
-    reid = pose = False
+    _name, _destroy, _reset = "OCSortEngine", "ss_ocsort_destroy", "ss_ocsort_reset"
 
     def __init__(self, cfg: OCSortConfig | None = None, n_streams: int = 1, device: int = 0, engine: TrackerEngine | None = None):
         self.cfg = cfg or OCSortConfig()
-        self._own = engine is None
-        self.base = TrackerEngine(StrongSortConfig(), n_streams, device) if engine is None else engine
-        self.S, self.device, self.L = self.base.S, self.base.device, self.base.L
+        super().__init__(n_streams, device, engine)
         c = _lib.make_ocsort_config(self.cfg)
         self._ck(self.L.ss_ocsort_create(self.base.ctx, C.byref(c)))
-        self.out = torch.zeros(self.S, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=self.device)
-        self.nout = torch.zeros(self.S, dtype=torch.int32, device=self.device)
-        self.use_stream, self.use_current_stream = self.base.use_stream, self.base.use_current_stream
-        self.check_errors = self.base.check_errors
-
-    @property
-    def ctx(self):
-        return self.base.ctx
-
-    @property
-    def max_group_frames(self) -> int:
-        return self.base.max_group_frames
-
-    def _ck(self, rc):
-        _lib.check(self.base.ctx, rc)
-
-    def close(self):
-        if self._own:
-            self.base.close()
-        elif getattr(self.base, "ctx", None) and self.base.ctx.value:
-            torch.cuda.synchronize(self.device)
-            self._ck(self.L.ss_ocsort_destroy(self.base.ctx))
-
-    def reset(self, stream: int = -1):
-        """Restart the stream(s): ids from 1, frame_count from 0."""
-        self._ck(self.L.ss_ocsort_reset(self.base.ctx, stream))
-
-    def update_device(self, dets, ndets, feats=None, img_hw=None, out=None, nout=None):
-        """All streams, one frame: dets [S,128,6] f32, ndets [S] i32 -> (rows [S,256,8], counts [S]) device tensors, asynchronous.
-        feats and img_hw are accepted for TrackerEngine's call shape and unused."""
-        out = self.out if out is None else out
-        nout = self.nout if nout is None else nout
-        return self.update_group(1, dets, ndets, feats, img_hw, out, nout)
 
     def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout):
         """A group of n_frames (<= 32) frames of all streams in ONE launch: dets [F,S,128,6] f32, ndets [F,S] i32 -> rows out
@@ -1173,55 +1157,22 @@ class DeepOCSortEngine(OCSortEngine):
     detections' raw features (read while cfg.appearance is on) and BoT-SORT's set_cmc.  It stands where the BYTE / OC-SORT engine
     stands.  `engine`: share the context of an existing TrackerEngine; None: a context of its own."""
 
-    pose = False
+    _name, _destroy, _reset, _feats_need = "DeepOCSortEngine", "ss_deepoc_destroy", "ss_deepoc_reset", "appearance"
+    _delegated = _AttachedTracker._delegated + ("cmc_estimate", "gmc_sparse_estimate", "estimate_warps")
 
     def __init__(self, cfg: DeepOCSortConfig | None = None, n_streams: int = 1, device: int = 0, engine: TrackerEngine | None = None):
         self.cfg = cfg or DeepOCSortConfig()
-        self._own = engine is None
-        self.base = TrackerEngine(StrongSortConfig(), n_streams, device) if engine is None else engine
-        self.S, self.device, self.L = self.base.S, self.base.device, self.base.L
+        _AttachedTracker.__init__(self, n_streams, device, engine)
         c = _lib.make_deepoc_config(self.cfg)
         self._ck(self.L.ss_deepoc_create(self.base.ctx, C.byref(c)))
         self.reid = bool(self.cfg.appearance)
         self._cmc_keep = None
-        self.out = torch.zeros(self.S, MAX_TRACKS, OUT_COLS, dtype=torch.float32, device=self.device)
-        self.nout = torch.zeros(self.S, dtype=torch.int32, device=self.device)
-        self.use_stream, self.use_current_stream = self.base.use_stream, self.base.use_current_stream
-        self.check_errors, self.cmc_estimate = self.base.check_errors, self.base.cmc_estimate
-        self.gmc_sparse_estimate, self.estimate_warps = self.base.gmc_sparse_estimate, self.base.estimate_warps
-
-    def close(self):
-        if self._own:
-            self.base.close()
-        elif getattr(self.base, "ctx", None) and self.base.ctx.value:
-            torch.cuda.synchronize(self.device)
-            self._ck(self.L.ss_deepoc_destroy(self.base.ctx))
-
-    def reset(self, stream: int = -1):
-        """Restart the stream(s): ids from 1, frame_count from 0, features cleared, and the next estimated frame gets no warp."""
-        self._ck(self.L.ss_deepoc_reset(self.base.ctx, stream))
 
     def set_cmc(self, warps):
         """Step 1b: the following update calls move every track by these warps ([F,S,8] float64, ss_cmc_estimate's layout, at least
         as many rows as the calls' frames) before predicting; None: off."""
         self._ck(self.L.ss_deepoc_set_gmc(self.base.ctx, _ptr(warps)))
         self._cmc_keep = warps
-
-    def _feats(self, feats, rows):
-        if not self.reid:
-            return None
-        if feats is None:
-            raise ValueError("DeepOCSortEngine: appearance needs the detections' features [.., 128, 512] f32")
-        if feats.dtype != torch.float32 or not feats.is_contiguous() or feats.numel() != rows * MAX_DETS * FEAT_DIM:
-            raise ValueError(f"DeepOCSortEngine: feats must be contiguous float32 [{rows} x {MAX_DETS} x {FEAT_DIM}]")
-        return feats
-
-    def update_device(self, dets, ndets, feats=None, img_hw=None, out=None, nout=None):
-        """All streams, one frame: dets [S,128,6] f32, ndets [S] i32, feats [S,128,512] f32 (raw, device) -> (rows [S,256,8],
-        counts [S]) device tensors, asynchronous.  img_hw is accepted for TrackerEngine's call shape and unused."""
-        out = self.out if out is None else out
-        nout = self.nout if nout is None else nout
-        return self.update_group(1, dets, ndets, feats, img_hw, out, nout)
 
     def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout):
         """A group of n_frames (<= 32) frames of all streams in one call: dets [F,S,128,6] f32, ndets [F,S] i32, feats
