@@ -859,6 +859,36 @@ int ss_mot_identity(ss_ctx* ctx, int n_pairs, const int* frame_off, const int* g
 /* Host only: the most ids one side of a pair may have in ss_mot_identity (4096: the workgroup-wide assignment solver's columns). */
 int ss_mot_max_ids(void);
 
+/* ---- scoring detections against ground truth: COCO AP and AR (csrc/ss_ap.hip, docs/DETEVAL.md) ---- */
+/* All host pointers.  similarity 0: boxes are [rows][4] x1, y1, x2, y2 scored by IoU; 1: [rows][5] cx, cy, w, h, theta scored by
+ * ProbIoU (the boxes rounded to float as csrc/ss_probiou.h takes them; no crowd rows).  A cell is one (class, image); the n_cells
+ * cells come by (class, image): class k owns cells class_cell_off[k] .. class_cell_off[k+1]-1, cell c is image cell_image[c] (rising
+ * inside a class; read only for messages) and owns the ground-truth rows cell_gt_off[c] .. cell_gt_off[c+1]-1 and the detections
+ * cell_det_off[c] .. cell_det_off[c+1]-1, both in input order (every offset array starts at 0 and does not decrease).  gt_crowd[row]
+ * is 1 for a crowd region.  iou_thrs [n_thrs] each in (0, 1], rec_thrs [n_recs] finite and not decreasing, areas [n_areas][2]
+ * inclusive ranges, max_dets [n_max_dets] at least 1 and rising.  The call orders each class's detections by (score descending,
+ * packed index rising; -0.0 ties 0.0), keeps the first max_dets[-1] of every cell, matches them greedily per (area range,
+ * threshold) and accumulates; it returns precision [n_thrs][n_recs][n_classes][n_areas][n_max_dets] and recall
+ * [n_thrs][n_classes][n_areas][n_max_dets] (-1 where a class has no ground truth that counts), and unless NULL det_rank [detections]
+ * (the place of each detection in its class's order) and rec_match / rec_ignored [n_areas][n_thrs][kept detections] (both or
+ * neither; the kept detections cell after cell by position: the matched ground-truth row's index within its cell or -1, and the
+ * ignored bit).  One upload, the launches (a local sort, one merge pass per doubling, the matching with one wave per cell, the
+ * accumulation with one workgroup per (class, area range, max_dets entry)) and one download; the call waits on an event of its own.
+ * Every argument is checked before the context or the device is touched: a refusal is SS_ERR_INVALID, a call over a cap (the four
+ * functions below; 16 thresholds, 8 area ranges, 4 max_dets entries, 1024 recall thresholds; 2^28 record entries) SS_ERR_CAPACITY,
+ * both with a message naming the class and image (with ctx NULL in ss_last_error(NULL)), and the context stays usable.  The results
+ * are the bits tests/deteval_ref.py computes (docs/DETEVAL.md section 1).  Not capturable. */
+int ss_ap_eval(ss_ctx* ctx, int similarity, int n_classes, int n_cells, const int* class_cell_off, const int* cell_image, const int* cell_gt_off,
+               const int* cell_det_off, const double* gt_boxes, const int* gt_crowd, const double* det_boxes, const double* det_scores,
+               int n_thrs, const double* iou_thrs, int n_recs, const double* rec_thrs, int n_areas, const double* areas, int n_max_dets,
+               const int* max_dets, double* precision, double* recall, int* det_rank, int* rec_match, int* rec_ignored);
+/* Host only: the most ground-truth rows a cell may hold (1024), the most detections a cell may hold before the cut (4096), the
+ * largest max_dets entry (1024) and the most detections of a call (4 194 304). */
+int ss_ap_max_gts(void);
+int ss_ap_max_cell_dets(void);
+int ss_ap_max_keep(void);
+int ss_ap_max_dets(void);
+
 /* ---- AFLink: linking of finished tracklets by a small convolutional network (csrc/ss_aflink.hip, docs/AFLINK.md) ---- */
 /* Host only: the floats of the weight blob (docs/AFLINK.md section 3), and the most tracklets a side one connected component of
  * surviving pairs may have in ss_aflink_match (256: the one-wave assignment solver's side). */

@@ -306,6 +306,65 @@ class LabelsWriter:
             self.f_obb.close()
 
 
+class DetsWriter:
+    """--eval-det-gt: every frame's boxes in the labels file's line format with id -1, `frame cls -1 conf x1 y1 x2 y2 -1 -1 -1 -1`,
+    tracked or not; with an oriented-box model also `<name>_dets_obb.txt`: `frame cls -1 conf cx cy w h theta` (docs/DETEVAL.md §4)."""
+
+    def __init__(self, path: str, obb: bool = False):
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        self.f = open(path, "w")
+        self.f_obb = open(path[:-4] + "_obb.txt", "w") if obb else None
+
+    def write(self, frame_id: int, results) -> int:
+        n = 0
+        for r in results:
+            b = None if r is None else r.boxes if r.boxes is not None else getattr(r, "obb", None)
+            if b is None or len(b) == 0:
+                continue
+            if self.f_obb is not None and b is not r.boxes:
+                for conf, cls, q in zip(b.conf, b.cls, b.xywhr.tolist()):
+                    self.f_obb.write(f"{frame_id} {int(cls)} -1 {round(float(conf), 3)} {q[0]:.2f} {q[1]:.2f} {q[2]:.2f} {q[3]:.2f} {q[4]:.5f}\n")
+            for conf, cls, xyxy in zip(b.conf, b.cls, b.xyxy):
+                x1, y1, x2, y2 = (int(v) for v in xyxy)
+                self.f.write(f"{frame_id} {int(cls)} -1 {round(float(conf), 3)} {x1} {y1} {x2} {y2} -1 -1 -1 -1\n")
+                n += 1
+        self.f.flush()
+        if self.f_obb is not None:
+            self.f_obb.flush()
+        return n
+
+    def close(self):
+        self.f.close()
+        if self.f_obb is not None:
+            self.f_obb.close()
+
+
+def eval_det_post(args: dict, eng, outdir: str, name: str, obb: bool, summary: dict) -> None:
+    """--eval-det-gt after the stream: <name>_dets.txt (an oriented-box model: <name>_dets_obb.txt by ProbIoU, against the ground
+    truth's own `_obb` file) scored on the device into <name>_det_metrics.json; AP, AP50, AR100 into the summary."""
+    from . import deteval
+    gt_path = args["eval_det_gt"]
+    if obb:
+        gt_path = gt_path if gt_path.endswith("_obb.txt") else gt_path[:-4] + "_obb.txt"
+        if not os.path.isfile(gt_path):
+            raise ValueError(f"--eval-det-gt: an oriented-box model is scored against the rotated ground truth: no such file: {gt_path}")
+        gt, dt = deteval.read_labels_obb(gt_path), deteval.read_labels_obb(os.path.join(outdir, f"{name}_dets_obb.txt"))
+        ok = lambda r: (r[:, 4] > 0) & (r[:, 5] > 0)
+    else:
+        gt, dt = deteval.read_labels(gt_path), deteval.read_labels(os.path.join(outdir, f"{name}_dets.txt"))
+        ok = lambda r: (r[:, 4] > r[:, 2]) & (r[:, 5] > r[:, 3])
+    dropped = int(np.count_nonzero(~ok(gt)) + np.count_nonzero(~ok(dt)))       # int() corners can close a box of less than a pixel
+    gt, dt = gt[ok(gt)], dt[ok(dt)]
+    kw = {"max_dets": tuple(args["eval_det_max_dets"])} if args.get("eval_det_max_dets") else {}
+    if args.get("eval_det_classes"):
+        kw["classes"] = list(args["eval_det_classes"])
+    m = deteval.evaluate(gt, dt, eng, similarity="probiou" if obb else "iou", **kw)
+    m.update(gt_rows=len(gt), det_rows=len(dt), dropped_rows=dropped, similarity="probiou" if obb else "iou")
+    deteval.write_metrics(os.path.join(outdir, f"{name}_det_metrics.json"), m)
+    for fig in ("AP", "AP50", "AR100"):
+        summary[fig] = m[fig]
+
+
 class ClassCounter:
     """Objects per class = number of track ids whose majority class is that class (yolo_multi_model.py:293-300),
     maintained incrementally: O(boxes) per frame instead of O(file)."""
@@ -372,6 +431,8 @@ def process_video(args: dict, model=None) -> dict:
     writer = LabelsWriter(os.path.join(args.get("outdir", "output"), f"{name}_labels.txt"), args.get("compat", False),
                           obb=getattr(model, "_obb", False))
     counter = ClassCounter(model.names)
+    det_writer = (DetsWriter(os.path.join(args.get("outdir", "output"), f"{name}_dets.txt"), obb=getattr(model, "_obb", False))
+                  if args.get("eval_det_gt") else None)                   # --eval-det-gt: the boxes of every frame, tracked or not (docs/DETEVAL.md)
     frames, t0, fps = 0, time.time(), 0.0
     batch = int(args.get("batch", 16))
     src = frame_source(str(source), args.get("limit"), encoded=bool(args.get("device_decode", False)))
@@ -392,6 +453,8 @@ def process_video(args: dict, model=None) -> dict:
     def emit(frame, res):
         """labels, counts and (with --save) the annotated frame of one processed frame; reference :284-331"""
         nonlocal frames, t0, fps, overlay, fps_str, zc, zf
+        if det_writer is not None:
+            det_writer.write(frames, res)
         if track:
             writer.write(frames, res)
             if keep_rows:
@@ -450,6 +513,8 @@ def process_video(args: dict, model=None) -> dict:
     if sink is not None:
         sink.close()
     writer.close()
+    if det_writer is not None:
+        det_writer.close()
     summary = {"source": str(source), "frames": frames, "fps": fps, "counts": counter.counts() if count and track else {}}
     if zc is not None:
         from . import zones
@@ -493,6 +558,9 @@ def process_video(args: dict, model=None) -> dict:
         for k, m in zip(names, scored):
             for fig in ("HOTA", "MOTA", "IDSW") + (("IDF1",) if with_identity else ()):
                 summary[fig + k[len("labels"):]] = m[fig]
+    if det_writer is not None and frames:
+        pipe = model._stream_pipe or model._pipe or model._pred_pipe      # (a detection-only run has no overlay to borrow the context from)
+        eval_det_post(args, overlay.eng if overlay is not None else pipe.eng, args.get("outdir", "output"), name, getattr(model, "_obb", False), summary)
     return summary
 
 
@@ -635,6 +703,12 @@ def main(argv=None):
     p.add_argument("--eval-thr", type=float, default=0.5, help="--eval-gt: CLEAR MOT's similarity threshold, in (0, 1]")
     p.add_argument("--eval-identity", action="store_true",
                    help="--eval-gt only: also the identity metrics IDTP, IDFN, IDFP, IDF1, IDP, IDR at --eval-thr, into the same <name>_metrics.json")
+    p.add_argument("--eval-det-gt", nargs="+", default=None, metavar="PATH",
+                   help="ground-truth labels files (the labels file's line format; id < 0 marks a crowd region), one per source; with or without "
+                        "--track every frame's boxes go to <name>_dets.txt with id -1 and after the stream are scored against it on the device, "
+                        "COCO AP and AR (docs/DETEVAL.md), into <name>_det_metrics.json; an -obb model is scored by ProbIoU from the _obb files")
+    p.add_argument("--eval-det-max-dets", type=int, nargs="+", default=None, metavar="N", help="--eval-det-gt: the detections kept per image and class, rising (1 10 100)")
+    p.add_argument("--eval-det-classes", type=int, nargs="+", default=None, metavar="CLS", help="--eval-det-gt: score only these classes")
     p.add_argument("--line", action="append", default=[], metavar="X0,Y0,X1,Y1",
                    help="--track only, repeatable (up to 16): count the tracks that cross the directed segment a -> b, inward (onto its s >= 0 side) "
                         "and outward, by class, on the device (docs/ZONES.md) into <name>_zones.json; any --tracker")
@@ -689,6 +763,15 @@ def main(argv=None):
             p.error(f"--eval-gt: no such file: {path}")
     if a.eval_gt and not 0.0 < a.eval_thr <= 1.0:
         p.error("--eval-thr must be in (0, 1]")
+    if (a.eval_det_max_dets or a.eval_det_classes) and not a.eval_det_gt:
+        p.error("--eval-det-max-dets and --eval-det-classes are options of detection scoring: each needs --eval-det-gt")
+    if a.eval_det_gt and len(a.eval_det_gt) != len(a.source):
+        p.error("--eval-det-gt takes one ground-truth file per --source")
+    for path in a.eval_det_gt or ():
+        if not os.path.isfile(path):
+            p.error(f"--eval-det-gt: no such file: {path}")
+    if a.eval_det_max_dets and (min(a.eval_det_max_dets) < 1 or any(y <= x for x, y in zip(a.eval_det_max_dets, a.eval_det_max_dets[1:]))):
+        p.error("--eval-det-max-dets must be positive and rising")
     if a.gsi and not a.track:
         p.error("--gsi post-processes tracked rows: it needs --track")
     if a.gsi and (a.gsi_interval < 1 or not a.gsi_tau > 0):
@@ -754,6 +837,7 @@ def main(argv=None):
     jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "ocsort_use_byte": a.ocsort_use_byte, "device_decode": a.device_decode, "device_entropy": a.device_entropy,
              "device_encode": a.device_encode, "device_encode_entropy": a.device_encode_entropy, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
              "gsi": a.gsi, "gsi_interval": a.gsi_interval, "gsi_tau": a.gsi_tau, "eval_gt": a.eval_gt[i] if a.eval_gt else None, "eval_thr": a.eval_thr, "eval_identity": a.eval_identity,
+             "eval_det_gt": a.eval_det_gt[i] if a.eval_det_gt else None, "eval_det_max_dets": a.eval_det_max_dets, "eval_det_classes": a.eval_det_classes,
              "aflink": a.aflink, "aflink_thr_t": tuple(a.aflink_thr_t), "aflink_thr_s": a.aflink_thr_s, "aflink_thr_p": a.aflink_thr_p,
              "lines": a.line, "zones": a.zone, "zone_anchor": a.zone_anchor, "zone_gap": a.zone_gap, "heatmap": a.heatmap, "heat_cell": a.heat_cell, "heat_alpha": a.heat_alpha,
              "slice": a.slice, "slice_overlap": a.slice_overlap, "slice_merge": a.slice_merge, "slice_metric": a.slice_metric, "slice_thr": a.slice_thr, "no_slice_full": a.no_slice_full,

@@ -76,6 +76,7 @@ struct ss_ctx {
     SSJpegEnc* jpeg_enc = nullptr;   // ss_jpeg_encode_batch's buffers, made by its first call
     SSGsi* gsi = nullptr;       // ss_gsi_smooth's staging and scratch slots, made by its first call
     SSMot* mot = nullptr;       // ss_mot_eval's and ss_mot_identity's staging, scratch and second stream, made by its first call
+    SSAp* ap = nullptr;         // ss_ap_eval's staging and scratch, made by its first call
     SSAflink* aflink = nullptr; // ss_aflink_*'s weights, staging and activation scratch, made by its first call
     SSZone* zone = nullptr;     // the analytics stage (ss_zone_create), NULL until attached
     SSBank* bank = nullptr;     // the track bank (ss_bank_create), NULL until attached
@@ -237,6 +238,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     ss_jpeg_enc_free(c->jpeg_enc);
     ss_gsi_free(c->gsi);
     ss_mot_free(c->mot);
+    ss_ap_free(c->ap);
     ss_aflink_free(c->aflink);
     ss_zone_free(c->zone);
     ss_bank_free(c->bank);
@@ -567,6 +569,26 @@ extern "C" int ss_aflink_set_weights(ss_ctx* c, const float* blob, long long n)
     return post_run(c, "ss_aflink_set_weights",
         [&](std::string& err) { return ss_aflink_set_weights_check_impl(blob, n, err); },
         [&](std::string& err) { return ss_aflink_set_weights_impl(c ? &c->aflink : nullptr, c ? c->stream : nullptr, blob, err); });
+}
+
+// ---- COCO AP and AR of detections against ground truth (ss_ap.hip, docs/DETEVAL.md) ----------------------------------------------
+extern "C" int ss_ap_max_gts(void) { return ss_ap_max_gts_impl(); }
+extern "C" int ss_ap_max_cell_dets(void) { return ss_ap_max_cell_dets_impl(); }
+extern "C" int ss_ap_max_keep(void) { return ss_ap_max_keep_impl(); }
+extern "C" int ss_ap_max_dets(void) { return ss_ap_max_dets_impl(); }
+
+extern "C" int ss_ap_eval(ss_ctx* c, int similarity, int n_classes, int n_cells, const int* class_cell_off, const int* cell_image, const int* cell_gt_off,
+                          const int* cell_det_off, const double* gt_boxes, const int* gt_crowd, const double* det_boxes, const double* det_scores,
+                          int n_thrs, const double* iou_thrs, int n_recs, const double* rec_thrs, int n_areas, const double* areas, int n_max_dets,
+                          const int* max_dets, double* precision, double* recall, int* det_rank, int* rec_match, int* rec_ignored)
+{
+    return post_run(c, "ss_ap_eval",
+        [&](std::string& err) { return ss_ap_check_impl(similarity, n_classes, n_cells, class_cell_off, cell_image, cell_gt_off, cell_det_off, gt_boxes, gt_crowd,
+                                                        det_boxes, det_scores, n_thrs, iou_thrs, n_recs, rec_thrs, n_areas, areas, n_max_dets, max_dets, precision,
+                                                        recall, det_rank, rec_match, rec_ignored, err); },
+        [&](std::string& err) { return ss_ap_eval_impl(c ? &c->ap : nullptr, c ? c->stream : nullptr, similarity, n_classes, n_cells, class_cell_off, cell_gt_off,
+                                                       cell_det_off, gt_boxes, gt_crowd, det_boxes, det_scores, n_thrs, iou_thrs, n_recs, rec_thrs, n_areas, areas,
+                                                       n_max_dets, max_dets, precision, recall, det_rank, rec_match, rec_ignored, err); });
 }
 
 extern "C" int ss_aflink_cost(ss_ctx* c, int n_tracklets, const int* offsets, const double* feats, int thr_t0, int thr_t1, double thr_s, long long cap,

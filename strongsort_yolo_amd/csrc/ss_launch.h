@@ -179,6 +179,23 @@ int  ss_mot_identity_impl(SSMot** pm, hipStream_t stream, int n_pairs, const int
                           int* idtp, int* gt_to_tr, int* pot, std::string& err);
 void ss_mot_free(SSMot* m);
 
+// ---- ss_ap.hip
+struct SSAp;
+int  ss_ap_max_gts_impl();
+int  ss_ap_max_cell_dets_impl();
+int  ss_ap_max_keep_impl();
+int  ss_ap_max_dets_impl();
+int  ss_ap_check_impl(int similarity, int n_classes, int n_cells, const int* class_cell_off, const int* cell_image, const int* cell_gt_off,
+                      const int* cell_det_off, const double* gt_boxes, const int* gt_crowd, const double* det_boxes, const double* det_scores,
+                      int n_thrs, const double* iou_thrs, int n_recs, const double* rec_thrs, int n_areas, const double* areas, int n_max_dets,
+                      const int* max_dets, const double* precision, const double* recall, const int* det_rank, const int* rec_match,
+                      const int* rec_ignored, std::string& err);
+int  ss_ap_eval_impl(SSAp** pp, hipStream_t stream, int similarity, int n_classes, int n_cells, const int* class_cell_off, const int* cell_gt_off,
+                     const int* cell_det_off, const double* gt_boxes, const int* gt_crowd, const double* det_boxes, const double* det_scores,
+                     int n_thrs, const double* iou_thrs, int n_recs, const double* rec_thrs, int n_areas, const double* areas, int n_max_dets,
+                     const int* max_dets, double* precision, double* recall, int* det_rank, int* rec_match, int* rec_ignored, std::string& err);
+void ss_ap_free(SSAp* p);
+
 // ---- ss_zone.hip
 struct SSZone;
 int  ss_zone_max_lines_impl();

@@ -21,6 +21,7 @@
 #include "ss_host.h"
 #include "ss_launch.h"
 #include "ss_lsap.h"
+#include "ss_mot_sim.h"
 
 #define MOT_MAX_BOXES 256
 #define MOT_MAX_PAIRS 64
@@ -69,16 +70,6 @@ struct MotArgs {
     int* id_match;                          // [all ground-truth ids] dense tracker id or -1
     int* id_tp;                             // [pairs]
 };
-
-// S of docs/MOTEVAL.md section 1 by its four written steps
-__device__ __forceinline__ double mot_sim(const double* __restrict__ A, const double* __restrict__ B)
-{
-    const double ax1 = A[0], ay1 = A[1], ax2 = A[2], ay2 = A[3], bx1 = B[0], by1 = B[1], bx2 = B[2], by2 = B[3];
-    const double w = fmax(0.0, fmin(ax2, bx2) - fmax(ax1, bx1)), h = fmax(0.0, fmin(ay2, by2) - fmax(ay1, by1));
-    const double inter = w * h;
-    const double uni = ((ax2 - ax1) * (ay2 - ay1) + (bx2 - bx1) * (by2 - by1)) - inter;
-    return inter / uni;
-}
 
 __global__ __launch_bounds__(256) void k_mot_sim(const MotArgs a)
 {

@@ -310,6 +310,47 @@ class TrackerEngine:
                                         pot.ctypes.data_as(pi) if pot is not None else None))
         return (idtp, match[:n_g]) + ((pot,) if want_pot else ())
 
+    def ap_eval(self, similarity, class_cell_off, cell_image, cell_gt_off, cell_det_off, gt_boxes, gt_crowd, det_boxes, det_scores, iou_thrs, rec_thrs,
+                areas, max_dets, want_rank: bool = False, want_record: bool = False):
+        """COCO's precision and recall arrays of detections against ground truth (csrc/ss_ap.hip, docs/DETEVAL.md), host arrays in and
+        out.  similarity 0: boxes [rows, 4] by IoU, 1: [rows, 5] by ProbIoU; the cells come by (class, image) with their row ranges on
+        both sides, rows in input order.  -> (precision [T,R,K,A,M], recall [T,K,A,M]), then with want_rank the place of every packed
+        detection in its class's order, then with want_record match and ignored [A,T,kept] int32.  Synchronous; one device call."""
+        ai = lambda v: np.ascontiguousarray(v, np.int32).reshape(-1)
+        ad = lambda v: np.ascontiguousarray(v, np.float64).reshape(-1)
+        width = 5 if int(similarity) else 4
+        class_cell_off, cell_image, cell_gt_off, cell_det_off, gt_crowd, max_dets = (ai(v) for v in (class_cell_off, cell_image, cell_gt_off, cell_det_off, gt_crowd, max_dets))
+        gt_boxes, det_boxes = (np.ascontiguousarray(v, np.float64).reshape(-1, width) for v in (gt_boxes, det_boxes))
+        det_scores, iou_thrs, rec_thrs, areas = ad(det_scores), ad(iou_thrs), ad(rec_thrs), ad(areas)
+        K, n_cells = len(class_cell_off) - 1, len(cell_image)
+        if (K < 1 or len(cell_gt_off) != n_cells + 1 or len(cell_det_off) != n_cells + 1 or len(gt_boxes) != cell_gt_off[-1] or len(gt_crowd) != len(gt_boxes)
+                or len(det_boxes) != cell_det_off[-1] or len(det_scores) != len(det_boxes) or len(areas) % 2 or not len(max_dets)):
+            raise ValueError("ap_eval: class_cell_off [classes + 1], cell_image [cells], cell offsets [cells + 1], boxes [rows, 4 or 5], crowd flags and "
+                             "scores [rows], areas [ranges, 2], max_dets [entries]")
+        T, R, A, M, n_det = len(iou_thrs), len(rec_thrs), len(areas) // 2, len(max_dets), len(det_scores)
+        kept = int(np.minimum(np.diff(cell_det_off.astype(np.int64)), max(int(max_dets[-1]), 0)).clip(0).sum())
+        precision, recall = np.zeros((T, R, K, A, M)), np.zeros((T, K, A, M))
+        rank = np.zeros(max(n_det, 1), np.int32) if want_rank else None
+        n_rec = A * T * kept if A * T * kept <= 1 << 28 else 0                 # (a call over the cap is the library's to refuse: its outputs stay small)
+        match, ignored = (np.full(max(n_rec, 1), -1, np.int32), np.zeros(max(n_rec, 1), np.int32)) if want_record else (None, None)
+        if not len(gt_boxes):                                                   # (a side without rows still passes a pointer)
+            gt_boxes, gt_crowd = np.zeros((1, width)), np.zeros(1, np.int32)
+        if not n_det:
+            det_boxes, det_scores = np.zeros((1, width)), np.zeros(1)
+        if not n_cells:
+            cell_image = np.zeros(1, np.int32)
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        p = lambda v: None if v is None else v.ctypes.data_as(pd if v.dtype == np.float64 else pi)
+        self._ck(self.L.ss_ap_eval(self.ctx, int(similarity), K, n_cells, p(class_cell_off), p(cell_image), p(cell_gt_off), p(cell_det_off), p(gt_boxes), p(gt_crowd),
+                                   p(det_boxes), p(det_scores), T, p(iou_thrs), R, p(rec_thrs), A, p(areas), M, p(max_dets), p(precision), p(recall),
+                                   p(rank), p(match), p(ignored)))
+        out = (precision, recall)
+        if want_rank:
+            out += (rank[:n_det],)
+        if want_record:
+            out += (match[:n_rec].reshape(A, T, -1), ignored[:n_rec].reshape(A, T, -1))
+        return out
+
     # ---- tracker --------------------------------------------------------------------------------
     # ---- analytics behind the trackers (csrc/ss_zone.hip, docs/ZONES.md); zones.ZoneCounter is the front of these ----
     def zone_create(self, cfg, lines, zones):
