@@ -186,8 +186,13 @@ def tlwh_to_xyah(t):
 class OracleStrongSort:
     """One stream's tracker.  update() consumes detections + their (raw) ReID features."""
 
-    def __init__(self, cfg, numerics: str = "c"):
+    def __init__(self, cfg, numerics: str = "c", max_tracks: Optional[int] = None):
+        """max_tracks: the device table's capacity (SS_MAX_TRACKS = 256), or None for a table without a limit.  A frame whose
+        survivors plus births exceed it starts tracks only for the unmatched detections of lowest index that fit (k_frame
+        stage C) and sets capacity_error, which stays set like the device's SS_ERR_CAPACITY."""
         self.cfg = cfg
+        self.max_tracks = max_tracks
+        self.capacity_error = False
         self.nx = CNumerics(cfg) if numerics == "c" else NumpyNumerics(cfg)
         self.tracks: List[Track] = []
         self.next_id = 1
@@ -290,8 +295,14 @@ class OracleStrongSort:
             t = self.tracks[ti]
             if t.state == TENTATIVE or t.tsu > cfg.max_age:
                 t.state = DELETED
-        # 6. births, ascending detection index (D-11)
-        for d in sorted(unmatched_dets):
+        # 6. births, ascending detection index (D-11); with a capacity only as many as the survivors leave room for
+        births = sorted(unmatched_dets)
+        if self.max_tracks is not None:
+            room = max(self.max_tracks - sum(t.state != DELETED for t in self.tracks), 0)
+            if len(births) > room:
+                self.capacity_error = True
+                births = births[:room]
+        for d in births:
             mean, cov = nx.kf_initiate(xyah[d])
             self.tracks.append(Track(self.next_id, mean, cov, f[d].copy(), int(dets[d, 5]),
                                      float(dets[d, 4]), det_idx=d))

@@ -342,7 +342,9 @@ def test_golden_tracker_vector_through_the_c_abi():
 
 
 def test_near_capacity_stream():
-    """110 identities at 1920x1080: 110 x 110 = 12,100 cost entries (LDS cap 14,336), 7 detection column tiles."""
+    """110 identities at 1920x1080: 110 x 110 = 12,100 cost entries, which still fit the LDS (SS_COST_CAP = 12,288; nothing spills),
+    7 detection column tiles.  The costs are unambiguous, so the LSAP does not run; for more tracks, spilled matrices and the LSAP
+    see tests/test_gpu_strongsort_crowd.py."""
     cfg = StrongSortConfig()
     eng, orc = engine(cfg, debug=False), OracleStrongSort(cfg, "c")
     sg, so = make_stream(44, 1920, 1080, 110), make_stream(44, 1920, 1080, 110)
@@ -357,29 +359,58 @@ def test_near_capacity_stream():
 def test_track_capacity_overflow_keeps_the_tables_consistent():
     """More births than free slots (256 per stream): the detections that do not fit start no track, SS_ERR_CAPACITY is raised at
     the next check and stays until ss_reset; the stream's tables stay consistent (unique ids, counts within capacity) —
-    the defined behaviour that include/strongsort_hip.h states."""
+    the defined behaviour that include/strongsort_hip.h states.  The rows of every frame and the track table
+    after the overflow frame equal the oracle with the same capacity (OracleStrongSort(..., max_tracks=256)); the overflow frame's
+    rows come from a second pass through the group call, whose error is checked afterwards."""
+    import torch
     from strongsort_yolo_amd import lib
     cfg = StrongSortConfig()
     eng = engine(cfg, debug=False)
+    orc = OracleStrongSort(cfg, "c", max_tracks=256)
     rng = np.random.default_rng(9)
     feats = [unit(rng, 128) for _ in range(3)]
+    frames, refs = [], []
     for k in range(7):                                   # three sets of 128 detections at disjoint places, three frames each: a set's
         g = k // 3                                       # tracks are confirmed and then coast (max_age 30) while the next set is born
         dets = np.zeros((128, 6), np.float32)
         gx, gy = np.meshgrid(np.arange(16), np.arange(8))
         dets[:, 0] = 10 + gx.ravel() * 110 + 36 * g; dets[:, 1] = 10 + gy.ravel() * 125 + 40 * g
         dets[:, 2] = dets[:, 0] + 30; dets[:, 3] = dets[:, 1] + 60; dets[:, 4] = 0.9
+        frames.append((dets, feats[g]))
+        refs.append(orc.update(dets, feats[g], (1080, 1920)))
+        assert orc.capacity_error == (k == 6), k
+        got = None
         try:
-            eng.update_host(dets, feats[g], (1080, 1920))
+            got = eng.update_host(dets, feats[g], (1080, 1920))
             raised = False
         except lib.SSError as e:
             raised = e.code == lib.SS_ERR_CAPACITY
         assert raised == (k == 6), k
+        if got is not None:
+            assert bits_equal(got, refs[k]), f"frame {k}: output rows differ"
     t = eng.tracks(0)
     assert len(t["track_id"]) == 256 and len(set(t["track_id"].tolist())) == 256 and t["next_id"] == 257
+    _compare_table(eng, orc)                              # the table after the overflow frame
     with pytest.raises(lib.SSError):
         eng.check_errors()                                # sticky until reset
     eng.reset(-1)
     eng.check_errors()
     assert len(eng.tracks(0)["track_id"]) == 0
+    # the same frames through the group call: the rows of every frame, the overflow frame included; the error afterwards
+    dev = eng.device
+    hw = torch.tensor([[1080, 1920]], dtype=torch.int32, device=dev)
+    out, nout = torch.zeros(1, 1, 256, 8, device=dev), torch.zeros(1, 1, dtype=torch.int32, device=dev)
+    nd = torch.tensor([[128]], dtype=torch.int32, device=dev)
+    for k, (dets, ft) in enumerate(frames):
+        eng.update_group(1, torch.from_numpy(dets[None, None]).to(dev), nd, torch.from_numpy(ft[None, None]).to(dev), hw, out, nout)
+        if k < 6:
+            eng.check_errors()
+        got = out[0, 0, :int(nout[0, 0])].cpu().numpy()
+        assert bits_equal(got, refs[k]), f"group call, frame {k}: output rows differ"
+    assert len(refs[6]) == 128                            # the second set's rows: the overflow frame is not an empty one
+    with pytest.raises(lib.SSError) as ei:
+        eng.check_errors()
+    assert ei.value.code == lib.SS_ERR_CAPACITY
+    _compare_table(eng, orc)
+    assert len(eng.tracks(0)["track_id"]) == 256
     eng.close()
