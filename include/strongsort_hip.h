@@ -592,6 +592,8 @@ int ss_op_v8_decode_f16(void* stream, const void* const* d_box, const void* cons
 int ss_op_v8_decode_ext_f16(void* stream, const void* const* d_box, const void* const* d_cls, const void* const* d_box_bias,
                             const void* const* d_cls_bias, const void* const* d_ext, int n_ext, int ext_ld, int ext_mode,
                             const int* H, const int* W, const int* strides, int B, int nc, int cls_ld, float* d_pred);
+/* Depthwise 3x3 / stride 1 / pad 1 on NHWC half: y = h(act(bias + the in-image taps)), fp32 sum, one rounding; d_w9 tap-major.
+ * SS_ERR_INVALID before any launch for a null tensor, C < 8 or C % 8, N, H or W < 1, act outside 0..3 (none, relu, silu, sigmoid). */
 int ss_op_dwconv3x3_f16(void* stream, const void* d_x, const void* d_w9 /*[9][C]*/, const void* d_bias, void* d_y,
                         int N, int H, int W, int C, int act);
 /* OSNet LightConv3x3 in one pass: y = relu(dw3x3(pw1x1(x)) + bias); w1 [C][C] (out, in), w9 [9][C], C in
@@ -668,7 +670,9 @@ int ss_op_psa_attention_f16(void* stream, const void* d_qkv, const void* d_pe, v
 int ss_op_osnet_head_f16(void* stream, const void* d_x, const void* d_w, const void* d_bias, void* d_out, int N, int HW, int C, int F);
 /* 2x2 / stride 2 average pooling, NHWC half (H, W even; C % 8 == 0). */
 int ss_op_avgpool2_f16(void* stream, const void* d_x, void* d_y, int N, int H, int W, int C);
-/* k x k max pooling (stride, pad with -inf), output floor((H+2p-k)/s)+1. */
+/* k x k max pooling (stride, pad with -inf) on NHWC half, output floor((H+2p-k)/s)+1 rows and columns alike.  SS_ERR_INVALID before any
+ * launch for a null tensor, C < 8 or C % 8, k or stride < 1, N, H or W < 1, pad < 0, 2 * pad > k (a window could lie wholly in the
+ * padding and yield -inf) and a window wider than the padded map (no output row or column: OH < 1 or OW < 1). */
 int ss_op_maxpool_f16(void* stream, const void* d_x, void* d_y, int N, int H, int W, int C, int k, int stride, int pad);
 /* OSNet unified aggregation gate: out = sum_t x_t * sigmoid(fc2(relu(fc1(mean_hw(x_t))))), T <= 4 streams. */
 int ss_op_gate_sum_f16(void* stream, const void* const* d_xs, int T, const void* d_w1, const void* d_b1,

@@ -2548,7 +2548,7 @@ extern "C" int ss_op_bias_act_f16(void* stream, void* x, const void* bias, const
 
 extern "C" int ss_op_dwconv3x3_f16(void* stream, const void* x, const void* w9, const void* bias, void* y, int N, int H, int W, int C, int act)
 {
-    if (!x || !w9 || !bias || !y || C % 8) return SS_ERR_INVALID;
+    if (!x || !w9 || !bias || !y || C < 8 || C % 8 || N < 1 || H < 1 || W < 1 || act < 0 || act > 3) return SS_ERR_INVALID;
     size_t total = (size_t)N * H * W * (C / 8);
     hipLaunchKernelGGL(k_dw3x3, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const __half*)x, (const __half*)w9,
                        (const __half*)bias, (__half*)y, N, H, W, C / 8, act);
@@ -2690,8 +2690,12 @@ extern "C" int ss_op_lightconv_f16(void* stream, const void* x, const void* w1, 
 
 extern "C" int ss_op_maxpool_f16(void* stream, const void* x, void* y, int N, int H, int W, int C, int k, int stride, int pad)
 {
-    if (!x || !y || C % 8 || k < 1 || stride < 1) return SS_ERR_INVALID;
+    if (!x || !y || C < 8 || C % 8 || k < 1 || stride < 1 || N < 1 || H < 1 || W < 1 || pad < 0 || 2 * pad > k) return SS_ERR_INVALID;
+    // a window wider than the padded map has no output (and two negative extents would multiply to a large positive total);
+    // 2 * pad <= k keeps at least one in-image element in every window, so no output is the -inf of the padding
+    if (H + 2 * pad < k || W + 2 * pad < k) return SS_ERR_INVALID;
     const int OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
+    if (OH < 1 || OW < 1) return SS_ERR_INVALID;
     size_t total = (size_t)N * OH * OW * (C / 8);
     hipLaunchKernelGGL(k_maxpool, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const __half*)x, (__half*)y,
                        N, H, W, C / 8, k, stride, pad, OH, OW);

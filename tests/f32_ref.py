@@ -571,7 +571,7 @@ def dfl_logits(B, seed=0):
     return [_ints(g, -32, 32, B, 64, h, w) / 8 for h, w in DECODE_LEVELS]
 
 
-def decode_box_bound(st, strides):
+def decode_box_bound(st, strides, rel=DFL_REL):
     """Per element bound of the four box rows [B, 4, A] from the reference's own intermediates `st` [B, 8, A] = (d0..d3, x1, y1, x2, y2).
     d = sw / se with e_k = expf(v_k - max) (v_k - max exact, e_k 1 ulp: 2 * 2^-24 relative), se and sw 16-term sums of non-negative terms
     (15 roundings each, 2^-24 relative each; sw one more per product e_k * k), the quotient correctly rounded (2^-24):
@@ -579,7 +579,7 @@ def decode_box_bound(st, strides):
     x1 = ax - d0, x2 = ax + d2 and their sum / difference round once each: at most ulp32 of the reference value (a full ulp where half
     would do: the kernel's value may sit in the next binade); * 0.5 and * stride (a power of two) are exact."""
     d, p = st[:, :4], st[:, 4:]
-    dd = DFL_REL * d
+    dd = rel * d                                                          # (rel: the half kernel re-derives it for __expf, tests/f16_ref.py)
     strides_a = torch.tensor([float(strides[l]) for l, _ in anchor_levels(DECODE_LEVELS)], dtype=torch.float64).view(1, 1, -1)
     ex = dd[:, 0] + dd[:, 2] + ulp32(p[:, 0]) + ulp32(p[:, 2])
     ey = dd[:, 1] + dd[:, 3] + ulp32(p[:, 1]) + ulp32(p[:, 3])

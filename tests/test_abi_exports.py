@@ -84,6 +84,33 @@ def test_host_side_entry_points_without_a_gpu():
     assert L.ss_op32_conv_plan(1, 8, 8, 16, 16, 3, 1, None, None, None, None) < 0      # null results; with them it plans on the host: test_f32_ref_cpu.py
 
 
+def test_pooling_depthwise_and_attention_entries_refuse_bad_extents_before_any_launch():
+    """ss_op_maxpool_f16, ss_op_dwconv3x3_f16 and ss_op_psa_attention_f16 check their extents before they launch: dummy non-null pointers
+    (never read: the refusal comes first) single out the argument that is refused.  A window wider than the padded map has no output -
+    two negative extents used to multiply to a large positive element count - and 2 * pad > k lets a window lie wholly in the padding."""
+    lib.build()
+    L = lib.load()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf)
+    INV = lib.SS_ERR_INVALID
+    pool = lambda N=1, H=4, W=4, C=8, k=3, s=1, pad=1, x=p, y=p: L.ss_op_maxpool_f16(None, x, y, N, H, W, C, k, s, pad)
+    assert pool(x=None) == INV and pool(y=None) == INV                                      # (the null-argument calls, as before)
+    for bad in (dict(N=0), dict(H=0), dict(W=0), dict(N=-1), dict(C=0), dict(C=12), dict(k=0), dict(s=0), dict(pad=-1),
+                dict(k=3, pad=2),                          # 2 * pad > k: the corner window holds padding alone
+                dict(H=2, W=2, k=5, pad=1),                # OH = OW = (2 + 2 - 5) / 1 + 1 = 0
+                dict(H=1, W=1, k=7, pad=2),                # both extents negative: their product was a positive count
+                dict(H=1, W=1, k=4, pad=1, s=2),           # (1 + 2 - 4) / 2 truncates to 0 in C: OH would read 1
+                dict(H=4, W=1, k=5, pad=1)):               # one extent only
+        assert pool(**bad) == INV, bad
+    dw = lambda N=1, H=4, W=4, C=8, act=1, x=p, w=p, b=p, y=p: L.ss_op_dwconv3x3_f16(None, x, w, b, y, N, H, W, C, act)
+    assert dw(x=None) == INV and dw(w=None) == INV and dw(b=None) == INV and dw(y=None) == INV
+    for bad in (dict(N=0), dict(H=0), dict(W=0), dict(H=-3), dict(C=0), dict(C=12), dict(act=-1), dict(act=4)):
+        assert dw(**bad) == INV, bad
+    att = lambda B=1, N=16, heads=2: L.ss_op_psa_attention_f16(None, p, None, p, B, N, heads, 1.0)
+    for bad in (dict(N=257), dict(N=0), dict(heads=0), dict(heads=65), dict(B=0)):
+        assert att(**bad) == INV, bad
+
+
 # ---- the binding is derived from the header (strongsort_yolo_amd/cheader.py): checked here with regular expressions of the test's own
 
 _CTYPE = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong, "void": None,

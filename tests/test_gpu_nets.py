@@ -5,6 +5,40 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
+def _fp32_on_cpu(m, x):
+    """The same module in float32 on the CPU, on the same half weights and input: no kernel of this project runs there."""
+    import copy
+    from strongsort_yolo_amd import fused
+    ref = copy.deepcopy(m).float().cpu()
+    fused.ENABLED = False
+    try:
+        with torch.no_grad():
+            out = ref(x.float().cpu())
+    finally:
+        fused.ENABLED = True
+    return out
+
+
+def _by_row_group(name, m, fused_out, plain_out, ref32):
+    """Box rows, class rows and ext rows of pred [B, 4 + nc + n_ext, A] (the embedding for OSNet) each on their own scale: the error of
+    the fused path against the float32 reference at most twice the error of the library's half path against the same reference, in the
+    maximum and in the root mean square.  The yardstick is the library path, never the fused path against itself; the factor 2 allows for
+    rounding points that sit in different places (measured ratios: docs/F16_OPERATORS.md section 11)."""
+    from strongsort_yolo_amd import nets
+    det = [mod for mod in m.modules() if isinstance(mod, nets.Detect)]
+    groups = {"embedding": slice(None)} if not det else {"box": slice(0, 4), "class": slice(4, 4 + det[0].nc)}
+    if det and fused_out.shape[1] > 4 + det[0].nc:
+        groups["ext"] = slice(4 + det[0].nc, None)
+    for g, rows in groups.items():
+        r = ref32.double()[:, rows]
+        ef, ep = (fused_out.double().cpu()[:, rows] - r).abs(), (plain_out.double().cpu()[:, rows] - r).abs()
+        mx, rms = (float(ef.max()), float(ep.max())), (float(ef.pow(2).mean().sqrt()), float(ep.pow(2).mean().sqrt()))
+        print(f"F16NET {name} {g}: max fused {mx[0]:.3e} plain {mx[1]:.3e} ratio {mx[0] / mx[1]:.3f}; rms fused {rms[0]:.3e} plain {rms[1]:.3e} "
+              f"ratio {rms[0] / rms[1]:.3f}; max |ref| {float(r.abs().max()):.3e}")
+        assert mx[0] <= 2 * mx[1], (name, g, "max", mx)
+        assert rms[0] <= 2 * rms[1], (name, g, "rms", rms)
+
+
 @pytest.mark.parametrize("name,shape", [("yolov8n", (1, 3, 384, 640)), ("osnet", (8, 3, 256, 128)), ("yolov8n-pose", (2, 3, 128, 160)),
                                         ("yolov8s", (2, 3, 192, 320)), ("yolov5n", (2, 3, 128, 160)), ("yolov7", (1, 3, 192, 320)),
                                         ("yolo11n", (2, 3, 192, 320)), ("yolo11n-pose", (1, 3, 384, 640))])
@@ -22,6 +56,7 @@ def test_fused_ops_match_torch_modules(name, shape):
     assert a.shape == b.shape and torch.isfinite(a).all()
     scale = b.abs().max().item() + 1e-6
     assert (a - b).abs().max().item() <= 2e-2 * scale, ((a - b).abs().max().item(), scale)
+    _by_row_group(name, m, a, b, _fp32_on_cpu(m, x))
 
 
 @pytest.mark.parametrize("name,shape", [("yolov8n-seg", (2, 3, 192, 320)), ("yolo11n-seg", (1, 3, 128, 160))])
@@ -45,6 +80,9 @@ def test_segmentation_head_fused_matches_torch_modules(name, shape):
         u, v = u.float(), v.float()
         scale = v.abs().max().item() + 1e-6
         assert torch.isfinite(u).all() and (u - v).abs().max().item() <= 2e-2 * scale, ((u - v).abs().max().item(), scale)
+    ref = _fp32_on_cpu(m, x)
+    _by_row_group(name, m, a[0].float(), b[0].float(), ref[0])
+    _by_row_group(name + " prototypes", torch.nn.Identity(), a[1].float(), b[1].float(), ref[1])
 
 
 @pytest.mark.parametrize("shape", [(3, 16, 64, 32), (2, 24, 32, 16), (5, 32, 16, 8), (1, 16, 20, 24), (2, 32, 7, 8)])
