@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string>
 #include "../../include/strongsort_hip.h"
+#include "ss_oplaunch.h"
 
 // Valid-image count of the OSNet kernels (ss_op_set_valid_images): the ReID crops of a frame group are packed (frame f's
 // crops follow frame f-1's), the launches keep their fixed grids (graph replay) and the workgroups of images >= *n leave at
@@ -46,6 +47,39 @@ __device__ inline float act_apply(float v, int act)
     if (act == 2) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));          // silu
     if (act == 3) return __builtin_amdgcn_rcpf(1.0f + __expf(-v));              // sigmoid
     return v;
+}
+
+// The epilogue of every convolution here, ONE place for its rounding points (docs/F16_OPERATORS.md §1): acc = the fp32 sum of
+// products, h = round to half:   c = h(acc);  f = c + bias (+ res);  f = act(f);  with res_after: f = h(f) + res;  out = h(f)
+// - what the unfused form (convolution to half, bias / activation pass, shortcut add) computes, which the fused launches are pinned to.
+// The empty asm makes the activated value opaque: silu's product is rounded to f32 THEN to half, never folded with the
+// conversion into one v_fma_mixlo_f16 (one rounding), whether or not `act` is a constant where this is inlined (not volatile:
+// the elements of a vector stay free to interleave; as volatile the 16-byte epilogue of k_pw<64, 1> ran 4-7 % longer).  Only a site
+// that is compiled for "no activation" goes without it: there f is the fp32 sum of halfs, whose rounding to half is the same
+// in one step or two (24 >= 2 * 11 + 2 bits), and the barrier would only keep the sums out of the packed half adder.
+__device__ __forceinline__ _Float16 ss_epi(float acc, _Float16 bias, int act, bool has_res = false, _Float16 res = (_Float16)0.f, bool res_after = false)
+{
+    float f = (float)(_Float16)acc + (float)bias;
+    if (has_res && !res_after) f += (float)res;
+    f = act_apply(f, act);
+    if (!(__builtin_constant_p(act) && act == 0)) asm("" : "+v"(f));
+    if (has_res && res_after) f = (float)(_Float16)f + (float)res;
+    return (_Float16)f;
+}
+// four accumulator elements of an MFMA tile / eight values that are half already (c = h(acc) is the identity on them)
+__device__ __forceinline__ h4 ss_epi4(const f4& acc, const h4& bias, int act, bool has_res = false, const h4& res = h4{ 0, 0, 0, 0 }, bool res_after = false)
+{
+    h4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = ss_epi(acc[j], bias[j], act, has_res, res[j], res_after);
+    return o;
+}
+__device__ __forceinline__ h8 ss_epi8(const h8& c, const h8& bias, int act, bool has_res, const h8& res, bool res_after)
+{
+    h8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = ss_epi((float)c[j], bias[j], act, has_res, res[j], res_after);
+    return o;
 }
 
 // x = act(x + bias[c] (+ res)), in place.  C % 8 == 0: 16-byte vectors.
@@ -143,18 +177,10 @@ __global__ __launch_bounds__(256) void k_bias_act_place(const __half* __restrict
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n_vec; i += (size_t)gridDim.x * blockDim.x) {
         const size_t pix = i / C8;
         const int c8 = (int)(i - pix * C8);
-        h8 v = reinterpret_cast<const h8*>(x)[i];
         const h8 b = reinterpret_cast<const h8*>(bias)[c8];
-        h8 r;
+        h8 r = { 0, 0, 0, 0, 0, 0, 0, 0 };
         if (res) r = reinterpret_cast<const h8*>(res)[i];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float f = (float)v[k] + (float)b[k];
-            if (res && !res_after) f += (float)r[k];
-            f = act_apply(f, act);
-            if (res && res_after) f = (float)(_Float16)f + (float)r[k];      // the unfused form rounds the activation first
-            v[k] = (_Float16)f;
-        }
+        const h8 v = ss_epi8(reinterpret_cast<const h8*>(x)[i], b, act, res != nullptr, r, res_after != 0);
         reinterpret_cast<h8*>(out)[pix * out_ld8 + c8] = v;
         if (out2 && c8 >= c0_8 && c8 < c0_8 + cn_8) reinterpret_cast<h8*>(out2)[pix * cn_8 + (c8 - c0_8)] = v;
     }
@@ -255,6 +281,26 @@ __global__ __launch_bounds__(128) void k_v8_decode(V8Levels L, int B, int nc, in
 // input pixel shifted by that tap (zeros outside the image).  Replaces MIOpen's zero-fill + igemm + our epilogue pass.
 struct ConvGeom { int H, W, Cin, OH, OW, stride; };
 
+// CONV3's gather: a lane's output pixel as image base (in pixels) and top-left input coordinate ...
+struct Conv3Px {
+    size_t ibase; int iy0, ix0;
+    __device__ __forceinline__ void set(size_t px, const ConvGeom& g)
+    {
+        const int ohw = g.OH * g.OW;
+        const int bimg = (int)(px / ohw), rem = (int)(px - (size_t)bimg * ohw), oy = rem / g.OW, ox = rem - oy * g.OW;
+        ibase = (size_t)bimg * g.H * g.W;
+        iy0 = oy * g.stride - 1; ix0 = ox * g.stride - 1;
+    }
+    // ... and its eight halfs k .. k + 7 of K = 9 * Cin; zeros past K, outside the image and for a pixel that does not exist (!px_ok)
+    __device__ __forceinline__ h8 load(const __half* __restrict__ x, int k, int K, bool px_ok, const ConvGeom& g) const
+    {
+        const int tap = k / g.Cin, c = k - tap * g.Cin, dy = tap / 3, dx = tap - dy * 3;
+        const int iy = iy0 + dy, ix = ix0 + dx;
+        const bool ok = px_ok && k < K && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W;
+        return ok ? *reinterpret_cast<const h8*>(x + (ibase + (size_t)iy * g.W + ix) * g.Cin + c) : h8{ 0, 0, 0, 0, 0, 0, 0, 0 };
+    }
+};
+
 // VEC_EPI: the accumulators (4 channels x 1 pixel per lane and tile) are transposed through a per-wave LDS tile so the
 // epilogue reads the shortcut and writes the output as 16-byte vectors, 128 contiguous bytes per 8 lanes, instead
 // of 8-byte pieces of 32-byte segments.
@@ -292,18 +338,10 @@ __device__ __forceinline__ void pw_body(const PwArgs& A, const int bx, const int
 #pragma unroll
         for (int pt = 0; pt < PT; ++pt) acc[mt][pt] = f4{ 0.f, 0.f, 0.f, 0.f };
     const h8 z8 = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    // CONV3: image base and top-left input coordinate of this lane's output pixel(s)
-    size_t ibase[PT];
-    int iy0[PT], ix0[PT];
+    Conv3Px cp[PT];                                         // CONV3: this lane's output pixel(s)
     if (CONV3) {
 #pragma unroll
-        for (int pt = 0; pt < PT; ++pt) {
-            const size_t px = px0 + pt * 16 + n;
-            const int ohw = g.OH * g.OW;
-            const int bimg = (int)(px / ohw), rem = (int)(px - (size_t)bimg * ohw), oy = rem / g.OW, ox = rem - oy * g.OW;
-            ibase[pt] = (size_t)bimg * g.H * g.W;
-            iy0[pt] = oy * g.stride - 1; ix0[pt] = ox * g.stride - 1;
-        }
+        for (int pt = 0; pt < PT; ++pt) cp[pt].set(px0 + pt * 16 + n, g);
     }
 
     // software pipeline over 64-wide K chunks: chunk kc+64's weights (to registers) and pixels are requested before
@@ -324,14 +362,8 @@ __device__ __forceinline__ void pw_body(const PwArgs& A, const int bx, const int
             for (int pt = 0; pt < PT; ++pt) {
                 const size_t px = px0 + pt * 16 + n;
                 const int k = kc + ks * 32 + 8 * q;
-                if (!CONV3) {
-                    b[ks][pt] = (px < (size_t)M && k < K) ? *reinterpret_cast<const h8*>(x + px * K + k) : z8;
-                } else {
-                    const int tap = k / g.Cin, c = k - tap * g.Cin, dy = tap / 3, dx = tap - dy * 3;
-                    const int iy = iy0[pt] + dy, ix = ix0[pt] + dx;
-                    const bool ok = px < (size_t)M && k < K && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W;
-                    b[ks][pt] = ok ? *reinterpret_cast<const h8*>(x + (ibase[pt] + (size_t)iy * g.W + ix) * g.Cin + c) : z8;
-                }
+                if (!CONV3) b[ks][pt] = (px < (size_t)M && k < K) ? *reinterpret_cast<const h8*>(x + px * K + k) : z8;
+                else b[ks][pt] = cp[pt].load(x, k, K, px < (size_t)M, g);
             }
     };
     // (weights two chunks ahead of their LDS store, pixels one chunk ahead of their MFMAs: a chunk's matrix work is shorter than
@@ -400,15 +432,7 @@ __device__ __forceinline__ void pw_body(const PwArgs& A, const int bx, const int
             const h8 bb = *reinterpret_cast<const h8*>(bias + oc);
             h8 r = z8;
             if (res) r = *reinterpret_cast<const h8*>(res + px * N + oc);
-            h8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float f = (float)v[j] + (float)bb[j];
-                if (res && !res_after) f += (float)r[j];
-                f = act_apply(f, act);
-                if (res && res_after) f = (float)(_Float16)f + (float)r[j];
-                o[j] = (_Float16)f;
-            }
+            const h8 o = ss_epi8(v, bb, act, res != nullptr, r, res_after != 0);
             *reinterpret_cast<h8*>(out + px * out_ld + oc) = o;
             if (out2 && oc >= c0 && oc < c0 + cn) *reinterpret_cast<h8*>(out2 + px * cn + (oc - c0)) = o;
         }
@@ -426,30 +450,15 @@ __device__ __forceinline__ void pw_body(const PwArgs& A, const int bx, const int
             const h4 bb = *reinterpret_cast<const h4*>(bias + oc0);
             h4 r = { 0, 0, 0, 0 };
             if (res) r = *reinterpret_cast<const h4*>(res + px * N + oc0);
-            h4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                // the unfused form rounds the convolution to half before the bias pass
-                float f = (float)(_Float16)acc[mt][pt][j] + (float)bb[j];
-                if (res && !res_after) f += (float)r[j];
-                f = act_apply(f, act);
-                if (res && res_after) f = (float)(_Float16)f + (float)r[j];
-                o[j] = (_Float16)f;
-            }
+            const h4 o = ss_epi4(acc[mt][pt], bb, act, res != nullptr, r, res_after != 0);
             *reinterpret_cast<h4*>(out + px * out_ld + oc0) = o;
             if (out2 && oc0 >= c0 && oc0 < c0 + cn) *reinterpret_cast<h4*>(out2 + px * cn + (oc0 - c0)) = o;
         }
     }
 }
 
-#ifndef SS_TAIL_BUMP
-#define SS_TAIL_BUMP 1
-#endif
-#ifndef SS_PW_BUMP
-#define SS_PW_BUMP 1
-#endif
 // waves per SIMD asked of the register allocator (it otherwise parks the accumulators in AGPRs and stops a few registers above a step)
-template <int BN, int PT, bool CONV3> constexpr int pw_waves() { return !SS_PW_BUMP ? 1 : BN * PT <= 32 ? 8 : (BN == 32 && PT == 2 && CONV3) ? 5 : BN * PT <= 80 ? 6 : BN * PT <= 128 ? 4 : BN * PT <= 160 ? 3 : 2; }   // (<32, 2, 3x3> at 6: spills)
+template <int BN, int PT, bool CONV3> constexpr int pw_waves() { return BN * PT <= 32 ? 8 : (BN == 32 && PT == 2 && CONV3) ? 5 : BN * PT <= 80 ? 6 : BN * PT <= 128 ? 4 : BN * PT <= 160 ? 3 : 2; }   // (<32, 2, 3x3> at 6: spills)
 template <int BN, int PT, bool CONV3, bool VEC_EPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_waves<BN, PT, CONV3>()))) void k_pw(PwArgs A)
 {
@@ -481,14 +490,8 @@ __device__ __forceinline__ void pw_splitk_body(const PwArgs& A, const int bx, co
     const int n0 = by * BN;
     const size_t px = (size_t)bx * 16 + n;
     const h8 z8 = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    size_t ibase = 0;
-    int iy0 = 0, ix0 = 0;
-    if (CONV3) {
-        const int ohw = g.OH * g.OW;
-        const int bimg = (int)(px / ohw), rem = (int)(px - (size_t)bimg * ohw), oy = rem / g.OW, ox = rem - oy * g.OW;
-        ibase = (size_t)bimg * g.H * g.W;
-        iy0 = oy * g.stride - 1; ix0 = ox * g.stride - 1;
-    }
+    Conv3Px cp{};
+    if (CONV3) cp.set(px, g);
     auto load_a = [&](int kc, h8 (&a)[MT][2]) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -502,14 +505,8 @@ __device__ __forceinline__ void pw_splitk_body(const PwArgs& A, const int bx, co
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int k = kc + ks * 32 + 8 * q;
-            if (!CONV3) {
-                b[ks] = (px < (size_t)M && k < K) ? *reinterpret_cast<const h8*>(x + px * K + k) : z8;
-            } else {
-                const int tap = k / g.Cin, c = k - tap * g.Cin, dy = tap / 3, dx = tap - dy * 3;
-                const int iy = iy0 + dy, ix = ix0 + dx;
-                const bool ok = px < (size_t)M && k < K && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W;
-                b[ks] = ok ? *reinterpret_cast<const h8*>(x + (ibase + (size_t)iy * g.W + ix) * g.Cin + c) : z8;
-            }
+            if (!CONV3) b[ks] = (px < (size_t)M && k < K) ? *reinterpret_cast<const h8*>(x + px * K + k) : z8;
+            else b[ks] = cp.load(x, k, K, px < (size_t)M, g);
         }
     };
     f4 acc[MT];
@@ -554,11 +551,7 @@ __device__ __forceinline__ void pw_splitk_body(const PwArgs& A, const int bx, co
                 const int ch = cg * 8 + j;
                 const float sum = ((Red[(0 * BN + ch) * RP + row] + Red[(1 * BN + ch) * RP + row]) + Red[(2 * BN + ch) * RP + row]) +
                                   Red[(3 * BN + ch) * RP + row];
-                float f = (float)(_Float16)sum + (float)bb[j];                // conv rounded to half, then the bias pass
-                if (res && !res_after) f += (float)r[j];
-                f = act_apply(f, act);
-                if (res && res_after) f = (float)(_Float16)f + (float)r[j];
-                o[j] = (_Float16)f;
+                o[j] = ss_epi(sum, bb[j], act, res != nullptr, r[j], res_after != 0);
             }
             *reinterpret_cast<h8*>(out + p * out_ld + oc) = o;
             if (out2 && oc >= c0 && oc < c0 + cn) *reinterpret_cast<h8*>(out2 + p * cn + (oc - c0)) = o;
@@ -586,12 +579,9 @@ struct PwGroup { PwArgs p[PW_GROUP_MAX]; int start[PW_GROUP_MAX + 1]; int form[P
 // chunk, but 118 VGPRs / 40 KB: 0.931 ms, slower than the per-branch problems at the higher occupancy.  Not kept.
 // Also measured and not kept (r05, detector at 0.87 ms): the split-K form for the plain 3x3 launches up to 8 192 pixels (0.91 ms), 128-wide K
 // chunks for the long K walks of the stride-32 level (neutral), 8 x 8 instead of 8 x 16 bottleneck tiles at the stride-8 level (0.88-0.89 ms).)
-#ifndef SS_GRP_WAVES
-#define SS_GRP_WAVES 6
-#endif
 template <int BN, bool CONV3, bool SPLITK>
 __global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(SPLITK || !SS_GRP_WAVES ? 1 : SS_GRP_WAVES)))
+__attribute__((amdgpu_waves_per_eu(SPLITK ? 1 : 6)))
 void k_pw_group(PwGroup G)
 {
     __shared__ __attribute__((aligned(16))) _Float16 pw_lds[pw_lds_halfs<BN, 1, true>()];
@@ -686,126 +676,164 @@ __device__ __forceinline__ void bn_conv(const _Float16* __restrict__ In, const i
     }
 }
 
-template <int C, int PT1, int PT2>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(!SS_TAIL_BUMP ? 1 : C == 16 ? 6 : 1))) void k_bneck(BnArgs A)
+template <int MT, int PT>
+__device__ __forceinline__ void bn_zero(f4 (&acc)[MT][PT])
 {
-    extern __shared__ __attribute__((aligned(16))) char bn_smem[];
-    constexpr int MT = C / 16, P = C + 8, WP = 72;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, n = lane & 15;
-    const int TW = A.TW, TH = A.TH, XW = TW + 4, XH = TH + 4, RW = TW + 2, RH = TH + 2;
-    _Float16* Xs = reinterpret_cast<_Float16*>(bn_smem);                               // [XH][XW][P]   input, origin (oy0-2, ox0-2)
-    _Float16* Ts = Xs + XH * XW * P;                                                   // [RH][RW][P]   first conv's output, origin (oy0-1, ox0-1)
-    _Float16* Ws = Ts + ((RH * RW * P + 7) & ~7);                                      // [2][C][WP]
-    int* tap1 = reinterpret_cast<int*>(Ws + 2 * C * WP);                               // [16] tap offsets in Xs / Ts
-    int* tap2 = tap1 + 16;
-    const int tpi = A.tiles_x * A.tiles_y;
-    const int img = blockIdx.x / tpi, trm = blockIdx.x - img * tpi, tyi = trm / A.tiles_x, txi = trm - tyi * A.tiles_x;
-    const int oy0 = tyi * TH, ox0 = txi * TW, H = A.H, W = A.W;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int pt = 0; pt < PT; ++pt) acc[mt][pt] = f4{ 0.f, 0.f, 0.f, 0.f };
+}
+
+// ---- the halo-tile scheme of k_bneck and k_head: a workgroup owns a TH x TW tile of one image's output -----------------------------
+struct HaloTile {
+    int TW, TH, XW, XH, RW, RH;                 // the tile, the tile + 2-pixel halo (input, Xs), the tile + 1-pixel ring (first convolution, Ts)
+    int oy0, ox0, img, H, W;                    // tile origin, image index, image size
+    __device__ __forceinline__ HaloTile(int tw, int th, int tiles_x, int tiles_y, int h, int w)
+        : TW(tw), TH(th), XW(tw + 4), XH(th + 4), RW(tw + 2), RH(th + 2), H(h), W(w)
+    {
+        const int tpi = tiles_x * tiles_y;
+        img = blockIdx.x / tpi;
+        const int trm = blockIdx.x - img * tpi, tyi = trm / tiles_x, txi = trm - tyi * tiles_x;
+        oy0 = tyi * TH; ox0 = txi * TW;
+    }
+};
+
+// Its LDS, worked out in ONE place for the kernel's carve and the launcher's request.  In halfs from the start: Xs [XH][XW][PX] at 0,
+// Ts [RH][RW][PM] at ts, the weight slices Ws [2][WR][72] at ws, the tap offsets in Xs / Ts (two [16] int tables) at taps.
+#define HALO_LDS_MAX (160 * 1024 - 512)        // what a launch may ask for (bytes)
+struct HaloLds {
+    int ts, ws, taps, bytes;
+    __host__ __device__ HaloLds(int TW, int TH, int PX, int PM, int WR)
+    {
+        ts = ((TH + 4) * (TW + 4) * PX + 7) & ~7;
+        ws = ts + (((TH + 2) * (TW + 2) * PM + 7) & ~7);
+        taps = ws + 2 * WR * 72;
+        bytes = taps * 2 + 2 * 16 * 4;
+    }
+};
+
+// stage the input tile with its halo (origin (oy0 - 2, ox0 - 2), pixel pitch PX = C + 8, zeros outside the image) and the tap offsets
+// of both convolutions (Ts: pixel pitch PM): a wave per row, 8 loads in flight per lane
+template <int C, int PX, int PM>
+__device__ __forceinline__ void halo_stage(const HaloTile& t, const __half* x, _Float16* Xs, int* tap1, int* tap2, const int tid)
+{
+    const int lane = tid & 63, wave = tid >> 6;
     const h8 z8 = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    if (tid < 9) { const int ky = tid / 3, kx = tid - ky * 3; tap1[tid] = (ky * XW + kx) * P; tap2[tid] = (ky * RW + kx) * P; }
-    // ---- stage the input tile (halo 2): a wave per row, 8 loads in flight per lane ----
-    const __half* xi = A.x + (size_t)img * H * W * C;
+    if (tid < 9) { const int ky = tid / 3, kx = tid - ky * 3; tap1[tid] = (ky * t.XW + kx) * PX; tap2[tid] = (ky * t.RW + kx) * PM; }
+    const __half* xi = x + (size_t)t.img * t.H * t.W * C;
     constexpr int VPC = C / 8;
-    const int rowv = XW * VPC;
-    for (int r = wave; r < XH; r += 4) {
-        const int iy = oy0 - 2 + r;
-        const bool rok = iy >= 0 && iy < H;
-        const __half* src = xi + (size_t)(rok ? iy : 0) * W * C;
-        _Float16* dst = Xs + r * XW * P;
+    const int rowv = t.XW * VPC;
+    for (int r = wave; r < t.XH; r += 4) {
+        const int iy = t.oy0 - 2 + r;
+        const bool rok = iy >= 0 && iy < t.H;
+        const __half* src = xi + (size_t)(rok ? iy : 0) * t.W * C;
+        _Float16* dst = Xs + r * t.XW * PX;
         for (int i0 = lane; i0 < rowv; i0 += 512) {
             h8 tmp[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                const int i = i0 + 64 * u, c = i / VPC, v = i % VPC, ix = ox0 - 2 + c;
-                const bool ok = rok && i < rowv && ix >= 0 && ix < W;
+                const int i = i0 + 64 * u, c = i / VPC, v = i % VPC, ix = t.ox0 - 2 + c;
+                const bool ok = rok && i < rowv && ix >= 0 && ix < t.W;
                 tmp[u] = ok ? *reinterpret_cast<const h8*>(src + (size_t)ix * C + v * 8) : z8;
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int i = i0 + 64 * u, c = i / VPC, v = i % VPC;
-                if (i < rowv) *reinterpret_cast<h8*>(dst + c * P + v * 8) = tmp[u];
+                if (i < rowv) *reinterpret_cast<h8*>(dst + c * PX + v * 8) = tmp[u];
             }
         }
     }
-    // ---- first convolution on the tile + 1-pixel ring -> Ts ----
-    {
-        int pb[PT1], tpix[PT1];
-        bool inimg[PT1];
+}
+
+// the first convolution (CI -> CO, + bias, SiLU) on the tile + 1-pixel ring -> Ts (origin (oy0 - 1, ox0 - 1)), as half exactly as the
+// separate launch rounds it; ZERO outside the image: it is the second convolution's padding
+template <int CI, int CO, int PT, int PX, int PM>
+__device__ __forceinline__ void halo_conv1(const HaloTile& t, const _Float16* Xs, _Float16* Ts, _Float16* Ws, const int* tap1,
+                                           const __half* w1, const __half* b1, const int tid, const int wave, const int q, const int n)
+{
+    constexpr int MT = CO / 16;                                    // (wave, q, n: the caller's values of this thread's place in the MFMA layout)
+    int pb[PT], tpix[PT];
+    bool inimg[PT];
 #pragma unroll
-        for (int pt = 0; pt < PT1; ++pt) {
-            const int p = (wave * PT1 + pt) * 16 + n;
-            int ry = p / RW, rx = p - ry * RW;
-            const bool ok = p < RH * RW;
-            if (!ok) { ry = 0; rx = 0; }
-            const int iy = oy0 - 1 + ry, ix = ox0 - 1 + rx;
-            inimg[pt] = ok && iy >= 0 && iy < H && ix >= 0 && ix < W;
-            tpix[pt] = ok ? p : -1;
-            pb[pt] = (ry * XW + rx) * P;
-        }
-        f4 acc[MT][PT1];
+    for (int pt = 0; pt < PT; ++pt) {
+        const int p = (wave * PT + pt) * 16 + n;
+        int ry = p / t.RW, rx = p - ry * t.RW;
+        const bool ok = p < t.RH * t.RW;
+        if (!ok) { ry = 0; rx = 0; }
+        const int iy = t.oy0 - 1 + ry, ix = t.ox0 - 1 + rx;
+        inimg[pt] = ok && iy >= 0 && iy < t.H && ix >= 0 && ix < t.W;
+        tpix[pt] = ok ? p : -1;
+        pb[pt] = (ry * t.XW + rx) * PX;
+    }
+    f4 acc[MT][PT];
+    bn_zero(acc);
+    bn_conv<CI, CO, PT>(Xs, pb, tap1, w1, Ws, acc, tid);
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
+    for (int mt = 0; mt < MT; ++mt) {
+        const h4 bb = *reinterpret_cast<const h4*>(b1 + mt * 16 + 4 * q);
 #pragma unroll
-            for (int pt = 0; pt < PT1; ++pt) acc[mt][pt] = f4{ 0.f, 0.f, 0.f, 0.f };
-        bn_conv<C, C, PT1>(Xs, pb, tap1, A.w1, Ws, acc, tid);
+        for (int pt = 0; pt < PT; ++pt) {
+            if (tpix[pt] < 0) continue;
+            h4 o;                                              // (the select per element, on the rounded half: as a packed select k_head<256> needs 4 more VGPRs)
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const h4 bb = *reinterpret_cast<const h4*>(A.b1 + mt * 16 + 4 * q);
-#pragma unroll
-            for (int pt = 0; pt < PT1; ++pt) {
-                if (tpix[pt] < 0) continue;
-                h4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float f = act_apply((float)(_Float16)acc[mt][pt][j] + (float)bb[j], 2);
-                    asm volatile("" : "+v"(f));                    // product rounded to f32 THEN to half, as k_pw (no v_fma_mixlo_f16: one rounding)
-                    o[j] = inimg[pt] ? (_Float16)f : (_Float16)0.f;
-                }
-                *reinterpret_cast<h4*>(Ts + tpix[pt] * P + mt * 16 + 4 * q) = o;
-            }
+            for (int j = 0; j < 4; ++j) { const _Float16 e = ss_epi(acc[mt][pt][j], bb[j], 2); o[j] = inimg[pt] ? e : (_Float16)0.f; }
+            *reinterpret_cast<h4*>(Ts + tpix[pt] * PM + mt * 16 + 4 * q) = o;
         }
     }
+}
+
+// pixels of the second pass: pixel n of this wave's tile pt -> its coordinates in the tile and its index in the output tensor
+// (opix; -1 outside the tile or the image, the coordinates then (0, 0))
+template <int PT>
+__device__ __forceinline__ void halo_map2(const HaloTile& t, const int wave, const int n, int (&ty_)[PT], int (&tx_)[PT], int (&opix)[PT])
+{
+#pragma unroll
+    for (int pt = 0; pt < PT; ++pt) {
+        const int p = (wave * PT + pt) * 16 + n;
+        int ty = p / t.TW, tx = p - ty * t.TW;
+        const bool ok = p < t.TH * t.TW && t.oy0 + ty < t.H && t.ox0 + tx < t.W;
+        if (!ok) { ty = 0; tx = 0; }
+        ty_[pt] = ty; tx_[pt] = tx;
+        opix[pt] = ok ? (t.img * t.H + t.oy0 + ty) * t.W + t.ox0 + tx : -1;
+    }
+}
+
+template <int C, int PT1, int PT2>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 16 ? 6 : 1))) void k_bneck(BnArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) char bn_smem[];
+    constexpr int MT = C / 16, P = C + 8;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, n = lane & 15;
+    const HaloTile t(A.TW, A.TH, A.tiles_x, A.tiles_y, A.H, A.W);
+    const HaloLds L(A.TW, A.TH, P, P, C);
+    _Float16* Xs = reinterpret_cast<_Float16*>(bn_smem);
+    _Float16 *Ts = Xs + L.ts, *Ws = Xs + L.ws;
+    int *tap1 = reinterpret_cast<int*>(Xs + L.taps), *tap2 = tap1 + 16;
+    halo_stage<C, P, P>(t, A.x, Xs, tap1, tap2, tid);
+    halo_conv1<C, C, PT1, P, P>(t, Xs, Ts, Ws, tap1, A.w1, A.b1, tid, wave, q, n);
     // (the first barrier inside bn_conv orders the Ts writes before the second convolution's reads; its weight buffers are free:
     //  every wave has left the first K walk's last slice before it writes Ts ... and the slice written next is the OTHER buffer only
     //  if the slice count is odd, so: one explicit barrier)
     __syncthreads();
-    // ---- second convolution on the tile, shortcut from the staged input ----
-    {
-        int pb[PT2], opix[PT2], xoff[PT2];
+    // ---- second convolution on the tile, shortcut from the staged input, placed into the concat slice (+ the dense copy) ----
+    int ty[PT2], tx[PT2], opix[PT2], pb[PT2], xoff[PT2];                 // pb: the pixel in Ts, xoff: the same pixel in Xs (the shortcut)
+    halo_map2<PT2>(t, wave, n, ty, tx, opix);
+#pragma unroll
+    for (int pt = 0; pt < PT2; ++pt) { pb[pt] = (ty[pt] * t.RW + tx[pt]) * P; xoff[pt] = ((ty[pt] + 2) * t.XW + tx[pt] + 2) * P; }
+    f4 acc[MT][PT2];
+    bn_zero(acc);
+    bn_conv<C, C, PT2>(Ts, pb, tap2, A.w2, Ws, acc, tid);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        const h4 bb = *reinterpret_cast<const h4*>(A.b2 + mt * 16 + 4 * q);
 #pragma unroll
         for (int pt = 0; pt < PT2; ++pt) {
-            const int p = (wave * PT2 + pt) * 16 + n;
-            int ty = p / TW, tx = p - ty * TW;
-            const bool ok = p < TH * TW && oy0 + ty < H && ox0 + tx < W;
-            if (!ok) { ty = 0; tx = 0; }
-            pb[pt] = (ty * RW + tx) * P;
-            xoff[pt] = ((ty + 2) * XW + tx + 2) * P;
-            opix[pt] = ok ? (img * H + oy0 + ty) * W + ox0 + tx : -1;
-        }
-        f4 acc[MT][PT2];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int pt = 0; pt < PT2; ++pt) acc[mt][pt] = f4{ 0.f, 0.f, 0.f, 0.f };
-        bn_conv<C, C, PT2>(Ts, pb, tap2, A.w2, Ws, acc, tid);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const h4 bb = *reinterpret_cast<const h4*>(A.b2 + mt * 16 + 4 * q);
-#pragma unroll
-            for (int pt = 0; pt < PT2; ++pt) {
-                if (opix[pt] < 0) continue;
-                const h4 xr = *reinterpret_cast<const h4*>(Xs + xoff[pt] + mt * 16 + 4 * q);
-                h4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float f = act_apply((float)(_Float16)acc[mt][pt][j] + (float)bb[j], 2);
-                    asm volatile("" : "+v"(f));
-                    if (A.add) f = (float)(_Float16)f + (float)xr[j];
-                    o[j] = (_Float16)f;
-                }
-                *reinterpret_cast<h4*>(A.out + (size_t)opix[pt] * A.out_ld + mt * 16 + 4 * q) = o;
-                if (A.out2) *reinterpret_cast<h4*>(A.out2 + (size_t)opix[pt] * C + mt * 16 + 4 * q) = o;
-            }
+            if (opix[pt] < 0) continue;
+            const h4 xr = *reinterpret_cast<const h4*>(Xs + xoff[pt] + mt * 16 + 4 * q);
+            const h4 o = ss_epi4(acc[mt][pt], bb, 2, A.add != 0, xr, true);
+            *reinterpret_cast<h4*>(A.out + (size_t)opix[pt] * A.out_ld + mt * 16 + 4 * q) = o;
+            if (A.out2) *reinterpret_cast<h4*>(A.out2 + (size_t)opix[pt] * C + mt * 16 + 4 * q) = o;
         }
     }
 }
@@ -828,120 +856,39 @@ struct HeadArgs {
     int B, H, W, TW, TH, tiles_x, tiles_y;
 };
 
+constexpr int HEAD_CM_MAX = 80;            // mid channels of the wider branch (class): its Ts pitch and weight rows size the launch's LDS
+
 template <int CI, int CM, int PT1, int PT2>
 __device__ __forceinline__ void head_body(const HeadArgs& A, const int br, char* smem)
 {
-    constexpr int MT = CM / 16, PX = CI + 8, PM = CM + 8, WP = 72, KB3 = (CM + 31) / 32;
+    static_assert(CM <= HEAD_CM_MAX, "the launcher sizes the LDS for HEAD_CM_MAX mid channels");
+    constexpr int MT = CM / 16, PX = CI + 8, PM = CM + 8, KB3 = (CM + 31) / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, n = lane & 15;
-    const int TW = A.TW, TH = A.TH, XW = TW + 4, XH = TH + 4, RW = TW + 2, RH = TH + 2;
-    _Float16* Xs = reinterpret_cast<_Float16*>(smem);                                  // [XH][XW][PX]  input, origin (oy0-2, ox0-2)
-    _Float16* Ts = Xs + ((XH * XW * PX + 7) & ~7);                                     // [RH][RW][PM]  first conv's output, origin (oy0-1, ox0-1)
-    _Float16* Ws = Ts + ((RH * RW * PM + 7) & ~7);                                     // [2][80][WP] weight slices; then the 1x1 weights [CM][PM]
-    int* tap1 = reinterpret_cast<int*>(Ws + 2 * 80 * WP);                              // [16] tap offsets in Xs / Ts
-    int* tap2 = tap1 + 16;
+    const HaloTile t(A.TW, A.TH, A.tiles_x, A.tiles_y, A.H, A.W);
+    const HaloLds L(A.TW, A.TH, PX, PM, HEAD_CM_MAX);                                  // (the weight rows of the wider branch in both: one tap table address)
+    _Float16* Xs = reinterpret_cast<_Float16*>(smem);
+    _Float16 *Ts = Xs + L.ts, *Ws = Xs + L.ws;                                         // Ws: the weight slices, then the 1x1 weights [CM][PM]
+    int *tap1 = reinterpret_cast<int*>(Xs + L.taps), *tap2 = tap1 + 16;
     _Float16* Us = Xs;                                                                 // [4 waves][PT2 * 16][PM]: second conv's output (Xs is dead by then)
-    const int tpi = A.tiles_x * A.tiles_y;
-    const int img = blockIdx.x / tpi, trm = blockIdx.x - img * tpi, tyi = trm / A.tiles_x, txi = trm - tyi * A.tiles_x;
-    const int oy0 = tyi * TH, ox0 = txi * TW, H = A.H, W = A.W;
     const h8 z8 = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    if (tid < 9) { const int ky = tid / 3, kx = tid - ky * 3; tap1[tid] = (ky * XW + kx) * PX; tap2[tid] = (ky * RW + kx) * PM; }
-    // ---- stage the input tile (halo 2): a wave per row, 8 loads in flight per lane ----
-    const __half* xi = A.x + (size_t)img * H * W * CI;
-    constexpr int VPC = CI / 8;
-    const int rowv = XW * VPC;
-    for (int r = wave; r < XH; r += 4) {
-        const int iy = oy0 - 2 + r;
-        const bool rok = iy >= 0 && iy < H;
-        const __half* src = xi + (size_t)(rok ? iy : 0) * W * CI;
-        _Float16* dst = Xs + r * XW * PX;
-        for (int i0 = lane; i0 < rowv; i0 += 512) {
-            h8 tmp[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + 64 * u, c = i / VPC, v = i % VPC, ix = ox0 - 2 + c;
-                const bool ok = rok && i < rowv && ix >= 0 && ix < W;
-                tmp[u] = ok ? *reinterpret_cast<const h8*>(src + (size_t)ix * CI + v * 8) : z8;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + 64 * u, c = i / VPC, v = i % VPC;
-                if (i < rowv) *reinterpret_cast<h8*>(dst + c * PX + v * 8) = tmp[u];
-            }
-        }
-    }
-    // ---- first convolution (CI -> CM) on the tile + 1-pixel ring -> Ts ----
-    {
-        int pb[PT1], tpix[PT1];
-        bool inimg[PT1];
-#pragma unroll
-        for (int pt = 0; pt < PT1; ++pt) {
-            const int p = (wave * PT1 + pt) * 16 + n;
-            int ry = p / RW, rx = p - ry * RW;
-            const bool ok = p < RH * RW;
-            if (!ok) { ry = 0; rx = 0; }
-            const int iy = oy0 - 1 + ry, ix = ox0 - 1 + rx;
-            inimg[pt] = ok && iy >= 0 && iy < H && ix >= 0 && ix < W;
-            tpix[pt] = ok ? p : -1;
-            pb[pt] = (ry * XW + rx) * PX;
-        }
-        f4 acc[MT][PT1];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int pt = 0; pt < PT1; ++pt) acc[mt][pt] = f4{ 0.f, 0.f, 0.f, 0.f };
-        bn_conv<CI, CM, PT1>(Xs, pb, tap1, A.w1[br], Ws, acc, tid);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const h4 bb = *reinterpret_cast<const h4*>(A.b1[br] + mt * 16 + 4 * q);
-#pragma unroll
-            for (int pt = 0; pt < PT1; ++pt) {
-                if (tpix[pt] < 0) continue;
-                h4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float f = act_apply((float)(_Float16)acc[mt][pt][j] + (float)bb[j], 2);
-                    asm volatile("" : "+v"(f));                    // rounded to f32 THEN to half, as the grouped launch (no v_fma_mixlo_f16)
-                    o[j] = inimg[pt] ? (_Float16)f : (_Float16)0.f;
-                }
-                *reinterpret_cast<h4*>(Ts + tpix[pt] * PM + mt * 16 + 4 * q) = o;
-            }
-        }
-    }
+    halo_stage<CI, PX, PM>(t, A.x, Xs, tap1, tap2, tid);
+    halo_conv1<CI, CM, PT1, PX, PM>(t, Xs, Ts, Ws, tap1, A.w1[br], A.b1[br], tid, wave, q, n);
     __syncthreads();                                               // Ts complete; the first K walk's weight buffers and Xs are free
     // ---- second convolution (CM -> CM) on the tile -> per-wave tile Us ----
-    int opix[PT2];
+    int ty[PT2], tx[PT2], opix[PT2], pb[PT2];
+    halo_map2<PT2>(t, wave, n, ty, tx, opix);
+#pragma unroll
+    for (int pt = 0; pt < PT2; ++pt) pb[pt] = (ty[pt] * t.RW + tx[pt]) * PM;
     {
-        int pb[PT2];
-#pragma unroll
-        for (int pt = 0; pt < PT2; ++pt) {
-            const int p = (wave * PT2 + pt) * 16 + n;
-            int ty = p / TW, tx = p - ty * TW;
-            const bool ok = p < TH * TW && oy0 + ty < H && ox0 + tx < W;
-            if (!ok) { ty = 0; tx = 0; }
-            pb[pt] = (ty * RW + tx) * PM;
-            opix[pt] = ok ? (img * H + oy0 + ty) * W + ox0 + tx : -1;
-        }
         f4 acc[MT][PT2];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int pt = 0; pt < PT2; ++pt) acc[mt][pt] = f4{ 0.f, 0.f, 0.f, 0.f };
+        bn_zero(acc);
         bn_conv<CM, CM, PT2>(Ts, pb, tap2, A.w2[br], Ws, acc, tid);
         _Float16* ut = Us + wave * (PT2 * 16 * PM);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const h4 bb = *reinterpret_cast<const h4*>(A.b2[br] + mt * 16 + 4 * q);
 #pragma unroll
-            for (int pt = 0; pt < PT2; ++pt) {
-                h4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float f = act_apply((float)(_Float16)acc[mt][pt][j] + (float)bb[j], 2);
-                    asm volatile("" : "+v"(f));
-                    o[j] = (_Float16)f;
-                }
-                *reinterpret_cast<h4*>(ut + (pt * 16 + n) * PM + mt * 16 + 4 * q) = o;
-            }
+            for (int pt = 0; pt < PT2; ++pt) *reinterpret_cast<h4*>(ut + (pt * 16 + n) * PM + mt * 16 + 4 * q) = ss_epi4(acc[mt][pt], bb, 2);
         }
     }
     __syncthreads();                                               // every wave has left the second K walk: the weight buffers are free
@@ -958,10 +905,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& A, const int br, char*
     {
         const _Float16* ut = Us + wave * (PT2 * 16 * PM);
         f4 acc[MT][PT2];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int pt = 0; pt < PT2; ++pt) acc[mt][pt] = f4{ 0.f, 0.f, 0.f, 0.f };
+        bn_zero(acc);
 #pragma unroll
         for (int kb = 0; kb < KB3; ++kb) {
             const int k = kb * 32 + 8 * q;
@@ -989,11 +933,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& A, const int br, char*
             const h4 bb = *reinterpret_cast<const h4*>(A.b3[br] + oc0);
 #pragma unroll
             for (int pt = 0; pt < PT2; ++pt) {
-                if (opix[pt] < 0) continue;
-                h4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = (_Float16)((float)(_Float16)acc[mt][pt][j] + (float)bb[j]);
-                *reinterpret_cast<h4*>(out + (size_t)opix[pt] * nout + oc0) = o;
+                if (opix[pt] >= 0) *reinterpret_cast<h4*>(out + (size_t)opix[pt] * nout + oc0) = ss_epi4(acc[mt][pt], bb, 0);
             }
         }
     }
@@ -1005,7 +945,7 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) char hd_smem[];
     if (blockIdx.y == 0) head_body<CI, 64, PT1, PT2>(A, 0, hd_smem);
-    else head_body<CI, 80, PT1, PT2>(A, 1, hd_smem);
+    else head_body<CI, HEAD_CM_MAX, PT1, PT2>(A, 1, hd_smem);
 }
 
 // OSNet stem in one pass: conv 7x7 / stride 2 / pad 3 (3 -> 16 channels) + bias + ReLU + max pool 3x3 / stride 2 /
@@ -1192,9 +1132,7 @@ __global__ __launch_bounds__(256) void k_conv0(const __half* __restrict__ x, con
             f4 d = { 0.f, 0.f, 0.f, 0.f };
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) d = __builtin_amdgcn_mfma_f32_16x16x16f16(a[mt][ky], bv[ky], d, 0, 0, 0);
-            h4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = (_Float16)act_apply((float)(_Float16)d[j] + (float)bb[mt][j], act);
+            const h4 o = ss_epi4(d, bb[mt], act);
             if (c < OW) *reinterpret_cast<h4*>(y + (((size_t)b * OH + oy) * OW + c) * COUT + mt * 16 + 4 * q) = o;
         }
     }
@@ -1622,12 +1560,9 @@ __device__ __forceinline__ unsigned ss_pk_relu(unsigned v) { unsigned d; asm("v_
 // of the wave at 16 channels; the (centre, right) operands and the bias — and at 24 / 32 channels all of them — are read from
 // the workgroup's LDS copy of DwTab in every step.
 // A step runs its T layers first to last, each consuming the row the one before just finished (xs).
-// OS_SKEW 1 (A/B build, -DOS_SKEW=1): layer l consumes the row layer l-1 finished in the PREVIOUS step, so the T layers of a step
-// are independent of one another — measured slower (150 vs 149 us at 16 channels, 101 vs 94 at 24: T-1 more steps, no better
-// overlap), as was asking the scheduler for "one MFMA, three vector instructions" groups (+10 us); profiles/r04_osnet_dw_mfma_ab.txt.
-#ifndef OS_SKEW
-#define OS_SKEW 0
-#endif
+// (Measured and not kept, profiles/r04_osnet_dw_mfma_ab.txt: layer l consuming the row layer l-1 finished in the PREVIOUS step, which
+// makes the T layers of a step independent of one another - 150 vs 149 us at 16 channels, 101 vs 94 at 24: T-1 more steps, no better
+// overlap; and asking the scheduler for "one MFMA, three vector instructions" groups, +10 us.)
 template <int C, int NT, int T, bool ALDS, bool PAIR>
 struct OsChain {
     static constexpr int MT = (C + 15) / 16, KS = MT, CP = MT * 16;
@@ -1681,8 +1616,7 @@ struct OsChain {
         constexpr int lbase = (T * (T - 1)) / 2;
         asm volatile("" : "+v"(aoff));                      // keeps the table reads inside the row loop (hoisted, they cost 24 VGPRs per layer)
 #pragma unroll
-        for (int li = 0; li < T; ++li) {
-            const int l = OS_SKEW ? T - 1 - li : li;         // (OS_SKEW: last to first, a layer reads xs[l-1] before layer l-1 replaces it)
+        for (int l = 0; l < T; ++l) {
             uint2 x[NT][KS];
 #pragma unroll
             for (int j = 0; j < NT; ++j)
@@ -1717,7 +1651,7 @@ struct OsChain {
                     }
                     if constexpr (PAIR) { pl[j][mt].x &= mL; pl[j][mt].y &= mL; pr[j][mt].x &= mR; pr[j][mt].y &= mR; }
                 }
-            const int orow = row - (OS_SKEW ? 2 * l : l) - 1;
+            const int orow = row - l - 1;
             const bool inside = orow >= 0 && orow < H;
 #pragma unroll
             for (int j = 0; j < NT; ++j)
@@ -1788,16 +1722,15 @@ __device__ __forceinline__ void os_chain_run(const __half* __restrict__ xi, cons
                 }
             }
     };
-    // rows y0 - T .. enter layer 0 (the band's last output row yend - 1 leaves the last layer DELAY steps after it entered; rows
+    // rows y0 - T .. enter layer 0 (the band's last output row yend - 1 leaves the last layer T steps after it entered; rows
     // past yend - 1 + T only feed discarded rows); three rows are in flight ahead of the one being processed
-    constexpr int DELAY = OS_SKEW ? 2 * T - 1 : T;          // steps between a row entering layer 0 and leaving the last layer
-    const int r_first = y0 - T, r_last = yend - 1 + DELAY;
+    const int r_first = y0 - T, r_last = yend - 1 + T;
     uint2 r0[NT][KS], r1[NT][KS], r2[NT][KS], o[NT][MT];
     load_row(r_first, r0); load_row(r_first + 1, r1); load_row(r_first + 2, r2);
     for (int row = r_first; row <= r_last; row += 3) {
-        ch.step(r0, row, H, tab, aoff, q, o); load_row(row + 3, r0); emit(row - DELAY, o);
-        if (row + 1 <= r_last) { ch.step(r1, row + 1, H, tab, aoff, q, o); load_row(row + 4, r1); emit(row + 1 - DELAY, o); }
-        if (row + 2 <= r_last) { ch.step(r2, row + 2, H, tab, aoff, q, o); load_row(row + 5, r2); emit(row + 2 - DELAY, o); }
+        ch.step(r0, row, H, tab, aoff, q, o); load_row(row + 3, r0); emit(row - T, o);
+        if (row + 1 <= r_last) { ch.step(r1, row + 1, H, tab, aoff, q, o); load_row(row + 4, r1); emit(row + 1 - T, o); }
+        if (row + 2 <= r_last) { ch.step(r2, row + 2, H, tab, aoff, q, o); load_row(row + 5, r2); emit(row + 2 - T, o); }
     }
     // band sums of this lane's channels: over the pixel lanes of the image (16, or 8 per image of a pair), fixed order
 #pragma unroll
@@ -2098,7 +2031,7 @@ __global__ __launch_bounds__(128) void k_gate_vec(const float* __restrict__ psum
 // as one more MFMA product (weights wd [C2][C1], bias bd) and applies it in the accumulator layout — the `down` launch
 // (56 us at stage 1 / 512 crops) and 0.1 GB of shortcut reads disappear.  Same products, roundings and order as k_pw.
 template <int MID, int C2, int N2, int C1>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(!SS_TAIL_BUMP ? 1 : MID == 16 ? 4 : MID == 24 ? 3 : 2))) void k_osnet_tail(GatePtrs ys, const float* __restrict__ gv,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MID == 16 ? 4 : MID == 24 ? 3 : 2))) void k_osnet_tail(GatePtrs ys, const float* __restrict__ gv,
                                                    const __half* __restrict__ w3, const __half* __restrict__ b3,
                                                    const __half* __restrict__ idn, const __half* __restrict__ wd,
                                                    const __half* __restrict__ bd, __half* __restrict__ out,
@@ -2530,6 +2463,17 @@ __global__ __launch_bounds__(256) void k_osnet_head(const __half* __restrict__ x
     }
 }
 
+// a halo-tile kernel (k_bneck, k_head) with its LDS request: the limit is raised once per kernel and device
+template <auto KERNEL, class Args>
+static int launch_halo(dim3 grid, const HaloLds& L, hipStream_t st, const Args& A)
+{
+    static unsigned long long attr = 0;
+    if (L.bytes > HALO_LDS_MAX) return SS_ERR_INVALID;
+    if (!lds_attr_once((const void*)KERNEL, attr, HALO_LDS_MAX)) return SS_ERR_HIP;
+    hipLaunchKernelGGL(KERNEL, grid, dim3(256), (size_t)L.bytes, st, A);
+    return op_launched();
+}
+
 static inline int grid_for(size_t n, int block) { size_t g = (n + block - 1) / block; return (int)(g > 4096 ? 4096 : (g ? g : 1)); }
 
 extern "C" int ss_op_bias_act_f16(void* stream, void* x, const void* bias, const void* res, long long n_pix, int C, int act)
@@ -2543,7 +2487,7 @@ extern "C" int ss_op_bias_act_f16(void* stream, void* x, const void* bias, const
         size_t n = (size_t)n_pix * C;
         hipLaunchKernelGGL(k_bias_act1, dim3(grid_for(n, 256)), dim3(256), 0, st, (__half*)x, (const __half*)bias, (const __half*)res, n, C, act);
     }
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_dwconv3x3_f16(void* stream, const void* x, const void* w9, const void* bias, void* y, int N, int H, int W, int C, int act)
@@ -2552,7 +2496,7 @@ extern "C" int ss_op_dwconv3x3_f16(void* stream, const void* x, const void* w9, 
     size_t total = (size_t)N * H * W * (C / 8);
     hipLaunchKernelGGL(k_dw3x3, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const __half*)x, (const __half*)w9,
                        (const __half*)bias, (__half*)y, N, H, W, C / 8, act);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_bias_act_place_f16(void* stream, const void* x, const void* bias, const void* res, long long n_pix, int C,
@@ -2564,7 +2508,7 @@ extern "C" int ss_op_bias_act_place_f16(void* stream, const void* x, const void*
     hipLaunchKernelGGL(k_bias_act_place, dim3(grid_for(nv, 256)), dim3(256), 0, (hipStream_t)stream, (const __half*)x,
                        (const __half*)bias, (const __half*)res, nv, C / 8, act, res_after, (__half*)out, out_ld / 8,
                        (__half*)out2, c0 / 8, cn / 8);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_v8_decode_ext_f16(void* stream, const void* const* box, const void* const* cls, const void* const* box_bias,
@@ -2584,7 +2528,7 @@ extern "C" int ss_op_v8_decode_ext_f16(void* stream, const void* const* box, con
         A += H[l] * W[l];
     }
     hipLaunchKernelGGL(k_v8_decode, dim3((A + 127) / 128, B), dim3(128), 0, (hipStream_t)stream, L, B, nc, A, pred);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_v8_decode_f16(void* stream, const void* const* box, const void* const* cls, const void* const* box_bias,
@@ -2620,11 +2564,9 @@ static int launch_pw(hipStream_t st, bool conv3, const void* x, const void* w, c
     const bool splitk_allowed = g_opt_pw_splitk != 0;
     if (splitk_allowed && vec && conv3 && K >= 512 && M <= 4096) {
         const dim3 grid((unsigned)((M + 15) / 16), (N + ((N <= 32) ? 31 : 63)) / ((N <= 32) ? 32 : 64));
-#define SS_SK(BN, CV) hipLaunchKernelGGL((k_pw_splitk<BN, CV>), grid, dim3(256), 0, st, A)
-        if (N <= 32) { if (conv3) SS_SK(32, true); else SS_SK(32, false); }
-        else { if (conv3) SS_SK(64, true); else SS_SK(64, false); }
-#undef SS_SK
-        return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+        if (N <= 32) hipLaunchKernelGGL((k_pw_splitk<32, true>), grid, dim3(256), 0, st, A);
+        else hipLaunchKernelGGL((k_pw_splitk<64, true>), grid, dim3(256), 0, st, A);
+        return op_launched();
     }
     const bool big = M >= 32768;                 // enough pixels to fill the chip with 128-pixel workgroups
     if (N <= 32) { if (big) SS_PW2(32, 2); else SS_PW2(32, 1); }
@@ -2633,7 +2575,7 @@ static int launch_pw(hipStream_t st, bool conv3, const void* x, const void* w, c
     else SS_PW2(128, 2);
 #undef SS_PW2
 #undef SS_PW
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_pointwise_f16(void* stream, const void* x, const void* w, const void* bias, const void* res, long long M,
@@ -2666,7 +2608,7 @@ extern "C" int ss_op_osnet_stem_f16(void* stream, const void* x, const void* w_p
     hipLaunchKernelGGL(k_osnet_stem, dim3((unsigned)((size_t)N * tiles)), dim3(256), 0, (hipStream_t)stream, (const __half*)x,
                        (const __half*)w_prep, (const __half*)bias, (__half*)y, H, tiles, nv_for(stream, N),
                        (const __half*)w1, (const __half*)b1, (__half*)y1);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_lightconv_f16(void* stream, const void* x, const void* w1, const void* w9, const void* bias, void* y,
@@ -2685,7 +2627,7 @@ extern "C" int ss_op_lightconv_f16(void* stream, const void* x, const void* w1, 
     else if (C == 32) SS_LC(32);
     else return SS_ERR_INVALID;
 #undef SS_LC
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_maxpool_f16(void* stream, const void* x, void* y, int N, int H, int W, int C, int k, int stride, int pad)
@@ -2699,7 +2641,7 @@ extern "C" int ss_op_maxpool_f16(void* stream, const void* x, void* y, int N, in
     size_t total = (size_t)N * OH * OW * (C / 8);
     hipLaunchKernelGGL(k_maxpool, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const __half*)x, (__half*)y,
                        N, H, W, C / 8, k, stride, pad, OH, OW);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_gate_sum_f16(void* stream, const void* const* xs, int T, const void* w1, const void* b1, const void* w2,
@@ -2713,7 +2655,7 @@ extern "C" int ss_op_gate_sum_f16(void* stream, const void* const* xs, int T, co
     const size_t nvec = (size_t)HW * (C / 8);
     hipLaunchKernelGGL(k_gate_apply, dim3(grid_for(nvec, 256) > 64 ? 64 : grid_for(nvec, 256), N), dim3(256), 0, st, p, T, means_ws, 1, 1.0f,
                        (const __half*)w1, (const __half*)b1, (const __half*)w2, (const __half*)b2, (__half*)out, N, HW, C, Cr);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 // register-resident row stream for 16- and 32-wide images (SS_OSNET_CHAINS=0: the LDS form, A/B switch).  A wave of the
@@ -2757,7 +2699,7 @@ extern "C" int ss_op_dwtab_f16(void* stream, const void* w9, const void* bias, i
     if (C == 16) hipLaunchKernelGGL(k_dwtab<16>, dim3(1), dim3(256), 0, st, (const __half*)w9, (const __half*)bias, layers, (char*)out);
     else if (C == 24) hipLaunchKernelGGL(k_dwtab<24>, dim3(1), dim3(256), 0, st, (const __half*)w9, (const __half*)bias, layers, (char*)out);
     else hipLaunchKernelGGL(k_dwtab<32>, dim3(1), dim3(256), 0, st, (const __half*)w9, (const __half*)bias, layers, (char*)out);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_osnet_streams_f16(void* stream, const void* x, const void* w1, const void* dwtab,
@@ -2780,7 +2722,7 @@ extern "C" int ss_op_osnet_streams_f16(void* stream, const void* x, const void* 
         else if (W == 16) { if (C == 16) SS_CHN(16, 1, false); else if (C == 24) SS_CHN(24, 1, false); else SS_CHN(32, 1, false); }
         else { if (C == 16) SS_CHN(16, 1, true); else if (C == 24) SS_CHN(24, 1, true); else SS_CHN(32, 1, true); }
 #undef SS_CHN
-        return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+        return op_launched();
     }
     if (C != 16 && C != 24 && C != 32) return SS_ERR_INVALID;
     const int PS = ((C + 15) / 16) * 16;                     // pixel stride of the pointwise buffer (lc_slot)
@@ -2793,7 +2735,7 @@ extern "C" int ss_op_osnet_streams_f16(void* stream, const void* x, const void* 
     else if (C == 24) SS_OS(24);
     else SS_OS(32);
 #undef SS_OS
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 // aggregation gate from precomputed partial channel sums (ss_op_osnet_streams_f16's psum): parts per (stream, image)
@@ -2808,7 +2750,7 @@ extern "C" int ss_op_gate_apply_f16(void* stream, const void* const* xs, int T, 
     hipLaunchKernelGGL(k_gate_apply, dim3(grid_for(nvec, 256) > 64 ? 64 : grid_for(nvec, 256), N), dim3(256), 0, (hipStream_t)stream,
                        p, T, sums, parts, scale, (const __half*)w1, (const __half*)b1, (const __half*)w2, (const __half*)b2,
                        (__half*)out, N, HW, C, Cr);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_avgpool2_f16(void* stream, const void* x, void* y, int N, int H, int W, int C)
@@ -2816,7 +2758,7 @@ extern "C" int ss_op_avgpool2_f16(void* stream, const void* x, void* y, int N, i
     if (!x || !y || C % 8 || H < 2 || W < 2 || H % 2 || W % 2) return SS_ERR_INVALID;
     size_t total = (size_t)N * (H / 2) * (W / 2) * (C / 8);
     hipLaunchKernelGGL(k_avgpool2, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const __half*)x, (__half*)y, N, H, W, C / 8);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_osnet_tail_f16(void* stream, const void* const* ys, const float* psum, int parts, float scale, const void* gw1,
@@ -2854,7 +2796,7 @@ extern "C" int ss_op_osnet_tail_f16(void* stream, const void* const* ys, const f
         else return SS_ERR_INVALID;
     }
 #undef SS_TAIL
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 // Independent convolutions (all 3x3 / pad 1 or all 1x1, stride 1|2, bias + activation, dense outputs) in one launch.
@@ -2904,7 +2846,7 @@ extern "C" int ss_op_conv_group_f16(void* stream, int n, const ss_conv_desc* d)
     else if (nmax <= 64) SS_GRP(64);
     else SS_GRP(80);
 #undef SS_GRP
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_upcat_f16(void* stream, const void* lo, const void* hi, void* out, int B, int h, int w, int C1, int C2, int lo_first)
@@ -2913,7 +2855,7 @@ extern "C" int ss_op_upcat_f16(void* stream, const void* lo, const void* hi, voi
     const size_t total = (size_t)B * 4 * h * w * ((C1 + C2) / 8);
     hipLaunchKernelGGL(k_upcat, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const __half*)lo, (const __half*)hi,
                        (__half*)out, B, h, w, C1 / 8, C2 / 8, lo_first);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_osnet_head_f16(void* stream, const void* x, const void* w, const void* bias, void* out, int N, int HW, int C, int F)
@@ -2921,7 +2863,7 @@ extern "C" int ss_op_osnet_head_f16(void* stream, const void* x, const void* w, 
     if (!x || !w || !bias || !out || N < 1 || HW < 1 || C != 128 || F < 1) return SS_ERR_INVALID;
     hipLaunchKernelGGL(k_osnet_head<128>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const __half*)x, (const __half*)w,
                        (const __half*)bias, (__half*)out, N, HW, F, nv_for(stream, N));
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_psa_attention_f16(void* stream, const void* qkv, const void* pe, void* out, int B, int N, int heads, float scale)
@@ -2930,7 +2872,7 @@ extern "C" int ss_op_psa_attention_f16(void* stream, const void* qkv, const void
     const int NP = (N + 31) & ~31;
     hipLaunchKernelGGL(k_psa_attn, dim3((N + 63) / 64, heads, B), dim3(256), (size_t)64 * (NP + 16) * 2, (hipStream_t)stream,
                        (const __half*)qkv, (const __half*)pe, (__half*)out, N, heads, scale);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_sppf_pools_f16(void* stream, const void* x, void* out, int B, int H, int W, int C)
@@ -2938,7 +2880,7 @@ extern "C" int ss_op_sppf_pools_f16(void* stream, const void* x, void* out, int 
     if (!x || !out || B < 1 || H < 1 || W < 1 || C < 8 || C % 8 || H * W > 1024) return SS_ERR_INVALID;
     hipLaunchKernelGGL(k_sppf_pools, dim3((unsigned)(B * (C / 8))), dim3(256), (size_t)2 * H * W * 16, (hipStream_t)stream,
                        (const __half*)x, (__half*)out, H, W, C / 8);
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 extern "C" int ss_op_conv0_f16(void* stream, const void* x, const void* w_prep, const void* bias, void* y, int B, int H, int W, int Cout,
@@ -2952,7 +2894,7 @@ extern "C" int ss_op_conv0_f16(void* stream, const void* x, const void* w_prep, 
 #define SS_C0(CO) hipLaunchKernelGGL(k_conv0<CO>, grid, block, 0, st, (const __half*)x, (const __half*)w_prep, (const __half*)bias, (__half*)y, H, W, act)
     if (Cout == 16) SS_C0(16); else if (Cout == 32) SS_C0(32); else SS_C0(48);
 #undef SS_C0
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
+    return op_launched();
 }
 
 // C2f bottleneck in one launch (k_bneck).  x dense [B][H][W][C] half, C in {16, 32, 64, 128}; w1 / w2 [C][3][3][C]; out = a channel slice
@@ -2969,16 +2911,13 @@ extern "C" int ss_op_bottleneck_f16(void* stream, const void* x, const void* w1,
     BnArgs A{ (const __half*)x, (const __half*)w1, (const __half*)b1, (const __half*)w2, (const __half*)b2, (__half*)out, out_ld, (__half*)out2,
               B, H, W, add, big ? 16 : 8, 8, 0, 0 };
     A.tiles_x = (W + A.TW - 1) / A.TW; A.tiles_y = (H + A.TH - 1) / A.TH;
-    const int P = C + 8;
-    const size_t lds = ((size_t)(A.TH + 4) * (A.TW + 4) * P + (((size_t)(A.TH + 2) * (A.TW + 2) * P + 7) & ~(size_t)7) + 2 * (size_t)C * 72) * 2 + 128;
+    const HaloLds L(A.TW, A.TH, C + 8, C + 8, C);                  // the kernel's own carve
     const dim3 grid((unsigned)(B * A.tiles_x * A.tiles_y));
     hipStream_t st = (hipStream_t)stream;
-#define SS_BN(CC, P1, P2) do { static unsigned long long attr = 0; int dv_ = 0; (void)hipGetDevice(&dv_); if (!(attr >> (dv_ & 63) & 1)) { (void)hipFuncSetAttribute((const void*)k_bneck<CC, P1, P2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); attr |= 1ull << (dv_ & 63); }   /* the attribute is per DEVICE */ \
-                               hipLaunchKernelGGL((k_bneck<CC, P1, P2>), grid, dim3(256), lds, st, A); } while (0)
+#define SS_BN(CC, P1, P2) return launch_halo<k_bneck<CC, P1, P2>>(grid, L, st, A)
     if (big) { if (C == 16) SS_BN(16, 3, 2); else if (C == 32) SS_BN(32, 3, 2); else SS_BN(64, 3, 2); }
     else { if (C == 16) SS_BN(16, 2, 1); else if (C == 32) SS_BN(32, 2, 1); else if (C == 64) SS_BN(64, 2, 1); else SS_BN(128, 2, 1); }
 #undef SS_BN
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
 }
 
 // One level of the v8 detect head, both branches, three layers each, in one launch (k_head).  x dense [B][H][W][Cin] half,
@@ -2994,7 +2933,7 @@ extern "C" int ss_op_head_f16(void* stream, const void* x, const void* const* w1
     HeadArgs A;
     A.x = (const __half*)x;
     for (int b = 0; b < 2; ++b) {
-        const int cm = b ? 80 : 64;
+        const int cm = b ? HEAD_CM_MAX : 64;
         if (!w1[b] || !b1[b] || !w2[b] || !b2[b] || !w3[b] || !b3[b] || !out[b] || nout[b] < 8 || nout[b] % 8 || nout[b] > cm ||
             ((uintptr_t)w1[b] % 16) || ((uintptr_t)w2[b] % 16) || ((uintptr_t)w3[b] % 16) || ((uintptr_t)out[b] % 8))
             return SS_ERR_INVALID;
@@ -3004,19 +2943,15 @@ extern "C" int ss_op_head_f16(void* stream, const void* x, const void* const* w1
     const bool big = tile16 != 0 && Cin == 64;
     A.B = B; A.H = H; A.W = W; A.TW = big ? 16 : 8; A.TH = 8;
     A.tiles_x = (W + A.TW - 1) / A.TW; A.tiles_y = (H + A.TH - 1) / A.TH;
-    const size_t xs = ((size_t)(A.TH + 4) * (A.TW + 4) * (Cin + 8) + 7) & ~(size_t)7, ts = ((size_t)(A.TH + 2) * (A.TW + 2) * 88 + 7) & ~(size_t)7;
-    const size_t lds = (xs + ts + 2 * 80 * 72) * 2 + 128;
-    if (lds > 160 * 1024 - 512) return SS_ERR_INVALID;
+    const HaloLds L(A.TW, A.TH, Cin + 8, HEAD_CM_MAX + 8, HEAD_CM_MAX);   // head_body's carve for the wider branch
     const dim3 grid((unsigned)(B * A.tiles_x * A.tiles_y), 2);
     hipStream_t st = (hipStream_t)stream;
-#define SS_HD(CC, P1, P2) do { static unsigned long long attr = 0; int dv_ = 0; (void)hipGetDevice(&dv_); if (!(attr >> (dv_ & 63) & 1)) { (void)hipFuncSetAttribute((const void*)k_head<CC, P1, P2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); attr |= 1ull << (dv_ & 63); }   /* the attribute is per DEVICE */ \
-                               hipLaunchKernelGGL((k_head<CC, P1, P2>), grid, dim3(256), lds, st, A); } while (0)
+#define SS_HD(CC, P1, P2) return launch_halo<k_head<CC, P1, P2>>(grid, L, st, A)
     if (big) SS_HD(64, 3, 2);
     else if (Cin == 64) SS_HD(64, 2, 1);
     else if (Cin == 128) SS_HD(128, 2, 1);
     else SS_HD(256, 2, 1);
 #undef SS_HD
-    return hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_HIP;
 }
 
 // The OSNet entry points above (stem, pointwise, streams, tail) launched on `stream` by this host thread compute only the first

@@ -29,6 +29,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/strongsort_hip.h"
+#include "ss_oplaunch.h"
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 #define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -1465,18 +1466,8 @@ __global__ __launch_bounds__(128) void k32_v8_decode(V8Levels32 L, int B, int nc
 }
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------
-#define OP32_CHECK() do { if (hipGetLastError() != hipSuccess) return SS_ERR_HIP; } while (0)
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies per DEVICE: `done` is a per-kernel bit set indexed by the current device
-// (a process-wide bool left the second GPU of a process without the attribute: launches asking for > 64 KB of LDS failed there)
-static bool lds_attr_once(const void* fn, unsigned long long& done)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return false;
-    if (done >> dev & 1) return true;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess) return false;
-    done |= 1ull << dev;
-    return true;
-}
+// (the launch check OP_CHECK and lds_attr_once: ss_oplaunch.h)
+static bool lds32_attr(const void* fn, unsigned long long& done) { return lds_attr_once(fn, done, 160 * 1024 - 256); }
 static int g_chains_pre = -1;         // k32_chains3: x1 tiles of a chain's first 1x1 requested a phase ahead: -1 = where it was measured faster (16 channels:
                                       // 618 -> 572 us per launch; 24 channels: 218 -> 330 us, the 32 extra registers spill), 0 / 1 = A/B
 static int g_chains_form = 2;        // 2: k32_chainsR (register row stream; 64 x 32 x 16 and 32 x 16 x 24 maps), 1: k32_chains3 (the 16 x 8 maps have no such form: k32_chains), 0: k32_chains
@@ -1501,7 +1492,7 @@ static int launch_pw32(hipStream_t st, const float* x, const float* w, const flo
     while (tpw < 8 && tiles / (4 * tpw) > 8192) tpw *= 2;      // a workgroup re-stages the weights: amortise over more tiles on large maps
     const long long grid = (tiles + 4 * tpw - 1) / (4 * tpw);
     hipLaunchKernelGGL((k32_pw<K, N>), dim3((unsigned)grid), dim3(256), 0, st, x, w, b, res, out, M, relu, tpw, nv, img_px);
-    OP32_CHECK();
+    OP_CHECK();
     return SS_OK;
 }
 
@@ -1551,10 +1542,10 @@ extern "C" int ss_op32_chains(void* stream, const void* d_x1, const void* d_w1, 
 #define CHR(CC, WW, AL) if (C == CC && W == WW) { \
         const size_t ldsr = (size_t)(ChR<CC>::TAB + (AL ? 10 * ChR<CC>::NPR * ChR<CC>::KP : 0)) * 4; \
         static unsigned long long attr = 0; \
-        if (ldsr > 64 * 1024 && !lds_attr_once((const void*)k32_chainsR<CC, WW, AL>, attr)) return SS_ERR_HIP; \
+        if (ldsr > 64 * 1024 && !lds32_attr((const void*)k32_chainsR<CC, WW, AL>, attr)) return SS_ERR_HIP; \
         const int ipw = WW == 8 ? 4 : 2;                      /* images per workgroup */ \
         hipLaunchKernelGGL((k32_chainsR<CC, WW, AL>), dim3((N + ipw - 1) / ipw), dim3(R32_THREADS), ldsr, st, x1, w1, w9, b, y0, y1, y2, y3, d_psum, N, H, d_nvalid, g_chains_probe); \
-        OP32_CHECK(); return SS_OK; }
+        OP_CHECK(); return SS_OK; }
         CHR(16, 32, false) CHR(24, 16, true) CHR(32, 8, true)
 #undef CHR
     }
@@ -1565,15 +1556,15 @@ extern "C" int ss_op32_chains(void* stream, const void* d_x1, const void* d_w1, 
     const dim3 grid(H / R, N);
 #define CH32(CC, WW) if (C == CC && W == WW) { \
         static unsigned long long attr = 0; \
-        if (!lds_attr_once((const void*)k32_chains<CC, WW>, attr)) return SS_ERR_HIP; \
+        if (!lds32_attr((const void*)k32_chains<CC, WW>, attr)) return SS_ERR_HIP; \
         hipLaunchKernelGGL((k32_chains<CC, WW>), grid, dim3(C32_THREADS), lds, st, x1, w1, w9, b, y0, y1, y2, y3, d_psum, N, H, R, halo, d_nvalid); \
-        OP32_CHECK(); return SS_OK; }
+        OP_CHECK(); return SS_OK; }
 #define CH32C(CC, WW, PRE_) if (C == CC && W == WW && g_chains_form >= 1 && (g_chains_pre < 0 ? CC == 16 : g_chains_pre != 0) == PRE_ && R + 2 * halo == (CC == 16 ? 24 : 32)) { \
         static unsigned long long attr = 0; \
-        if (!lds_attr_once((const void*)k32_chains3<CC, WW, PRE_>, attr)) return SS_ERR_HIP; \
+        if (!lds32_attr((const void*)k32_chains3<CC, WW, PRE_>, attr)) return SS_ERR_HIP; \
         const size_t lds3 = ((size_t)(R + 2 * halo + 2) * (WW + 2) + (size_t)(R + 2 * halo) * WW) * Ch3<CC>::PITCH * 4 + (size_t)(C32_THREADS / 64) * 16 * 4; \
         hipLaunchKernelGGL((k32_chains3<CC, WW, PRE_>), grid, dim3(C32_THREADS), lds3, st, x1, w1, w9, b, y0, y1, y2, y3, d_psum, N, H, R, halo, d_nvalid); \
-        OP32_CHECK(); return SS_OK; }
+        OP_CHECK(); return SS_OK; }
     CH32C(16, 32, true) CH32C(16, 32, false) CH32C(24, 16, true) CH32C(24, 16, false)
 #undef CH32C
     CH32(16, 32) CH32(24, 16) CH32(32, 8)
@@ -1607,7 +1598,7 @@ static int launch_tail32(hipStream_t st, const void* const* ys, const float* gat
     static int wgs_dev[64] = { 0 };                            // workgroups of the persistent grid per device: what fits on the chip at once (<= 4 per CU)
     static unsigned long long attr = 0;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63 || !lds_attr_once((const void*)k32_tail<MID, C2, C1, N2, POOL>, attr)) return SS_ERR_HIP;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63 || !lds32_attr((const void*)k32_tail<MID, C2, C1, N2, POOL>, attr)) return SS_ERR_HIP;
     if (!wgs_dev[dev]) {
         int cus = 0, per_cu = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -1622,7 +1613,7 @@ static int launch_tail32(hipStream_t st, const void* const* ys, const float* gat
     const int grid = g_tail_wgs > 0 ? g_tail_wgs : (N * splits < wgs ? N * splits : wgs);
     hipLaunchKernelGGL((k32_tail<MID, C2, C1, N2, POOL>), dim3(grid), dim3(T32_THREADS), lds, st, (const float*)ys[0], (const float*)ys[1], (const float*)ys[2],
                        (const float*)ys[3], gates, w3, b3, xin, wd, bd, out, w4, b4, out2, N, H, W, nv, splits);
-    OP32_CHECK();
+    OP_CHECK();
     return SS_OK;
 }
 
@@ -1640,7 +1631,7 @@ extern "C" int ss_op32_tail(void* stream, const void* const* d_ys, const float* 
         (const float*)d_gw2, (const float*)d_gb2, hidden, d_gates, N, d_nvalid)
     GT32(16); else GT32(24); else GT32(32); else return SS_ERR_INVALID;
 #undef GT32
-    OP32_CHECK();
+    OP_CHECK();
 #define TL32(M_, C2_, C1_, N2_, P_) if (MID == M_ && C2 == C2_ && C1 == C1_ && N2 == N2_ && (pool != 0) == P_) \
         return launch_tail32<M_, C2_, C1_, N2_, P_>(st, d_ys, d_gates, (const float*)d_w3, (const float*)d_b3, (const float*)d_xin, (const float*)d_wd, \
             (const float*)d_bd, (float*)d_out, (const float*)d_w4, (const float*)d_b4, (float*)d_out2, N, H, W, d_nvalid)
@@ -1663,15 +1654,15 @@ extern "C" int ss_op32_stem_conv1(void* stream, const void* d_x, int x_u8, const
     static unsigned long long attr8 = 0, attr32 = 0;
     const int nb = stem_bands(N);
     if (x_u8) {
-        if (!lds_attr_once((const void*)k32_stemW<true>, attr8)) return SS_ERR_HIP;
+        if (!lds32_attr((const void*)k32_stemW<true>, attr8)) return SS_ERR_HIP;
         hipLaunchKernelGGL(k32_stemW<true>, dim3(16 / nb, N), dim3(STW_THREADS), lds, (hipStream_t)stream, d_x, (const float*)d_w, (const float*)d_bias, (float*)d_y, N,
                            d_nvalid, nb, (const float*)d_w1, (const float*)d_b1, (float*)d_y1);
     } else {
-        if (!lds_attr_once((const void*)k32_stemW<false>, attr32)) return SS_ERR_HIP;
+        if (!lds32_attr((const void*)k32_stemW<false>, attr32)) return SS_ERR_HIP;
         hipLaunchKernelGGL(k32_stemW<false>, dim3(16 / nb, N), dim3(STW_THREADS), lds, (hipStream_t)stream, d_x, (const float*)d_w, (const float*)d_bias, (float*)d_y, N,
                            d_nvalid, nb, (const float*)d_w1, (const float*)d_b1, (float*)d_y1);
     }
-    OP32_CHECK();
+    OP_CHECK();
     return SS_OK;
 }
 
@@ -1681,10 +1672,10 @@ extern "C" int ss_op32_stem_u8(void* stream, const void* d_x, const void* d_w, c
     constexpr size_t lds = (size_t)(24 * ST_ROWP + (2 * ST_PR + 1) * 64 * 16 + 768) * 4;
     static unsigned long long attr = 0;
     const int nb = stem_bands(N);
-    if (!lds_attr_once((const void*)k32_stemW<true>, attr)) return SS_ERR_HIP;
+    if (!lds32_attr((const void*)k32_stemW<true>, attr)) return SS_ERR_HIP;
     hipLaunchKernelGGL(k32_stemW<true>, dim3(16 / nb, N), dim3(STW_THREADS), lds, (hipStream_t)stream, d_x, (const float*)d_w,
                        (const float*)d_bias, (float*)d_y, N, d_nvalid, nb, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
-    OP32_CHECK();
+    OP_CHECK();
     return SS_OK;
 }
 
@@ -1695,16 +1686,16 @@ extern "C" int ss_op32_stem(void* stream, const void* d_x, const void* d_w, cons
     static unsigned long long attr = 0, attr_w = 0;
     const int nb = g_stem_walk < 0 ? 0 : stem_bands(N);      // -1: one band per workgroup, k32_stem
     if (nb) {
-        if (!lds_attr_once((const void*)k32_stemW<false>, attr_w)) return SS_ERR_HIP;
+        if (!lds32_attr((const void*)k32_stemW<false>, attr_w)) return SS_ERR_HIP;
         hipLaunchKernelGGL(k32_stemW<false>, dim3(16 / nb, N), dim3(STW_THREADS), lds, (hipStream_t)stream, d_x, (const float*)d_w,
                            (const float*)d_bias, (float*)d_y, N, d_nvalid, nb, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
-        OP32_CHECK();
+        OP_CHECK();
         return SS_OK;
     }
-    if (!lds_attr_once((const void*)k32_stem, attr)) return SS_ERR_HIP;
+    if (!lds32_attr((const void*)k32_stem, attr)) return SS_ERR_HIP;
     hipLaunchKernelGGL(k32_stem, dim3(64 / ST_PR, N), dim3(C32_THREADS), lds, (hipStream_t)stream, (const float*)d_x, (const float*)d_w,
                        (const float*)d_bias, (float*)d_y, N, d_nvalid);
-    OP32_CHECK();
+    OP_CHECK();
     return SS_OK;
 }
 
@@ -1714,7 +1705,7 @@ extern "C" int ss_op32_head(void* stream, const void* d_x, const void* d_w, cons
     if (!d_x || !d_w || !d_bias || !d_out || N < 1 || HW < 1 || C != 128 || F < 1) return SS_ERR_INVALID;
     hipLaunchKernelGGL(k32_head, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)d_x, (const float*)d_w, (const float*)d_bias,
                        (float*)d_out, N, HW, F, d_nvalid);
-    OP32_CHECK();
+    OP_CHECK();
     return SS_OK;
 }
 
@@ -1772,7 +1763,7 @@ extern "C" int ss_op32_conv(void* stream, const void* d_x, int xs, const void* d
 #define CV32(KS_, ST_, MT_, WV_) if (ks == KS_ && stride == ST_ && mt == MT_ && wv == WV_) { \
         hipLaunchKernelGGL((k32_conv<KS_, ST_, MT_, 1, WV_>), grid, dim3(64 * WV_), 0, st, (const float*)d_x, xs, (const float*)d_w, (const float*)d_bias, \
                            (const float*)d_res, rs, (float*)d_out, os, N, H, W, OH, OW, Cin, Cout, act); \
-        OP32_CHECK(); return SS_OK; }
+        OP_CHECK(); return SS_OK; }
 #define CV32M(KS_, ST_) CV32(KS_, ST_, 1, 4) CV32(KS_, ST_, 1, 8) CV32(KS_, ST_, 2, 4) CV32(KS_, ST_, 2, 8) CV32(KS_, ST_, 4, 4) CV32(KS_, ST_, 4, 8) \
         CV32(KS_, ST_, 5, 4) CV32(KS_, ST_, 5, 8)
     CV32M(1, 1) CV32M(3, 1) CV32M(3, 2)
@@ -1790,7 +1781,7 @@ extern "C" int ss_op32_conv0(void* stream, const void* d_x, const void* d_w, con
     const long long M = (long long)N * OH * OW;
     hipLaunchKernelGGL(k32_conv0, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)d_x, (const float*)d_w,
                        (const float*)d_bias, (float*)d_out, os, N, H, W, OH, OW, act);
-    OP32_CHECK();
+    OP_CHECK();
     return SS_OK;
 }
 
@@ -1804,7 +1795,7 @@ extern "C" int ss_op32_upcat(void* stream, const void* d_lo, int ls, int Cl, con
     const long long tot = (long long)N * H * W * ((Cl + Ch) / 4);
     hipLaunchKernelGGL(k32_upcat, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)d_lo, ls, Cl, (const float*)d_hi, hs, Ch,
                        (float*)d_out, N, H, W, lo_first);
-    OP32_CHECK();
+    OP_CHECK();
     return SS_OK;
 }
 
@@ -1828,7 +1819,7 @@ extern "C" int ss_op32_v8_decode(void* stream, const void* const* d_box, const v
     }
     L.n_ext = n_ext; L.ext_ld = ext_ld; L.ext_mode = ext_mode; L.cls_ld = cls_ld;
     hipLaunchKernelGGL(k32_v8_decode, dim3((A + 127) / 128, B), dim3(128), 0, (hipStream_t)stream, L, B, nc, A, d_pred);
-    OP32_CHECK();
+    OP_CHECK();
     return SS_OK;
 }
 
@@ -1838,6 +1829,6 @@ extern "C" int ss_op32_sppf_pools(void* stream, const void* d_x, int xs, void* d
     if (!d_x || !d_out || N < 1 || H < 1 || W < 1 || C < 4 || (C | xs) % 4 || xs < C || (((uintptr_t)d_x | (uintptr_t)d_out) & 15)) return SS_ERR_INVALID;
     const long long tot = (long long)N * H * W * (C / 4);
     hipLaunchKernelGGL(k32_sppf, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)d_x, xs, (float*)d_out, N, H, W, C);
-    OP32_CHECK();
+    OP_CHECK();
     return SS_OK;
 }
