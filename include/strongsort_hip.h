@@ -974,6 +974,29 @@ int ss_zone_set_colormap(ss_ctx* ctx, const uint8_t* bgr_256x3);
 int ss_zone_heat_blend(ss_ctx* ctx, void* hip_stream, uint8_t* d_frames, int batch, long long frame_batch_stride, int h, int w, int row_stride,
                        const int* d_heat, long long heat_frame_stride, const int* d_max, int max_stride, int alpha);
 
+/* ---- redaction of regions of resident frames before they are saved: blur, pixelate, fill (csrc/ss_redact.hip, docs/REDACT.md; the
+ * bytes are those of tests/redact_ref.py) ---- */
+/* Host only: the caps (1024 regions a frame, 4096 vertices a polygon, blur radius 31) and the scratch a call needs, in bytes (sized
+ * for every 64 x 32 tile of every frame; negative: batch outside 1..65535 or a side outside 1..8192). */
+int ss_redact_max_regions(void);
+int ss_redact_max_vertices(void);
+int ss_redact_max_radius(void);
+long long ss_redact_scratch_bytes(int batch, int h, int w);
+/* In place over batch BGR frames laid out as ss_overlay's.  d_regions: 8 ints a region {type, x0, y0, x1, y1, vertex offset, vertices,
+ * 0}; frame b owns d_region_off[b] .. d_region_off[b+1] (at most ss_redact_max_regions() of them are read):
+ *   type 0 rectangle, inclusive corners in any order, clipped to the frame      type 1 the ellipse inscribed in that clipped rectangle
+ *   type 2 polygon: the even-odd interior by ss_overlay's rule united with its 2-pixel-thick outline; (x0,y0)-(x1,y1) is the bounding
+ *          box of its vertices, d_verts + 2 * offset its (x, y) pairs, each within -8192 .. 16383; fewer than 3 vertices cover nothing.
+ * effect 0: (2 strength + 1)^2 box mean, strength 1 .. ss_redact_max_radius(), reflect-101 borders by repeated reflection;
+ * effect 1: mosaic of strength x strength cells (4, 8, 16 or 32) aligned to the frame's origin, each the rounded mean of its pixels
+ * inside the frame; effect 2: fill_bgr (B | G << 8 | R << 16).  Every output pixel is a function of the untouched frame alone:
+ * overlap, order and splitting of regions change no byte; pixels outside every region and row padding are not written.  d_scratch: 16-byte
+ * aligned, scratch_bytes >= ss_redact_scratch_bytes(batch, h, w), owned by the call until it has run.  Asynchronous on hip_stream,
+ * capturable, no host dependency.  Every argument is checked before the context is touched (SS_ERR_INVALID, also with ctx NULL). */
+int ss_redact(ss_ctx* ctx, void* hip_stream, uint8_t* d_frames, int batch, long long frame_batch_stride, int h, int w, int row_stride,
+              const int* d_regions, const int* d_region_off, const int* d_verts, int effect, int strength, int fill_bgr, void* d_scratch,
+              long long scratch_bytes);
+
 /* ---- identities across cameras: a descriptor per track id kept beside a tracker, and the linking of the cameras' tracklets after
  * the run (csrc/ss_mtmc.hip, docs/MTMC.md; the bits are those of tests/mtmc_ref.py) ---- */
 /* Host only: the most ids a bank may be made for (65 536) and the most tracklets of one ss_mtmc_link (2048). */

@@ -449,10 +449,11 @@ def process_video(args: dict, model=None) -> dict:
     # --line / --zone / --heatmap: crossings, occupancy, dwell and heat counted on the device, frame by frame, on the rows the labels file records (docs/ZONES.md)
     zone_cfg, zc, zf = zone_config(args, len(model.names)) if track else None, None, None
     zone_asked = bool(args.get("lines") or args.get("zones") or args.get("heatmap"))
+    redact_cfg, redactor = (redact_config(args) if sink is not None else None), None      # --redact: the saved frames only (docs/REDACT.md)
 
     def emit(frame, res):
         """labels, counts and (with --save) the annotated frame of one processed frame; reference :284-331"""
-        nonlocal frames, t0, fps, overlay, fps_str, zc, zf
+        nonlocal frames, t0, fps, overlay, fps_str, zc, zf, redactor
         if det_writer is not None:
             det_writer.write(frames, res)
         if track:
@@ -479,6 +480,11 @@ def process_video(args: dict, model=None) -> dict:
                 sink.engine = overlay.eng
             cnt = counter.counts() if (count and track) else None
             zkw = {"zones": zf} if zf is not None else {}     # the heat blended on the resident frame, then the lines and zones drawn with the rest
+            if redact_cfg is not None:                       # the people are hidden first, on the device; labels, dets and metrics never see it
+                if redactor is None:
+                    from .redact import Redactor
+                    redactor = Redactor(redact_cfg, overlay.eng)
+                zkw["redact"] = redactor
             dev_frame = getattr(res[0], "orig_img_device", None) if res else None
             if dev_frame is not None and on_device:  # drawn and encoded where it is: only the sparse coefficients of its JPEG come back
                 sink.write_device(overlay.annotate_resident(dev_frame, res, cnt, fps_str, **zkw))
@@ -562,6 +568,37 @@ def process_video(args: dict, model=None) -> dict:
         pipe = model._stream_pipe or model._pipe or model._pred_pipe      # (a detection-only run has no overlay to borrow the context from)
         eval_det_post(args, overlay.eng if overlay is not None else pipe.eng, args.get("outdir", "output"), name, getattr(model, "_obb", False), summary)
     return summary
+
+
+def redact_config(args: dict):
+    """--redact and its options -> redact.RedactConfig, None without --redact; ValueError names a bad value."""
+    if not args.get("redact"):
+        return None
+    from .redact import RedactConfig
+    return RedactConfig(effect=args["redact"], strength=args.get("redact_strength"), region=args.get("redact_region", "box"),
+                        classes=args.get("redact_classes"), pad=float(args.get("redact_pad", 0.0)),
+                        fill_color=tuple(args.get("redact_color") or (0, 0, 0)))
+
+
+def redact_refusal(a) -> Optional[str]:
+    """Why the parsed --redact flags cannot be used, None when they can."""
+    opts = a.redact_region != "box" or a.redact_strength is not None or a.redact_classes is not None or a.redact_pad != 0.0 or a.redact_color is not None
+    if opts and not a.redact:
+        return "--redact-region, --redact-strength, --redact-classes, --redact-pad and --redact-color are options of --redact"
+    if a.redact and not a.save:
+        return "--redact hides people in the annotated output: it needs --save"
+    if a.redact == "fill" and a.redact_strength is not None:
+        return "--redact-strength does not apply to --redact fill"
+    if a.redact_color is not None and a.redact != "fill":
+        return "--redact-color is the colour of --redact fill"
+    base = os.path.basename(a.weights)
+    if a.redact and a.redact_region == "head" and "pose" not in base:
+        return "--redact-region head needs a pose model (--weights ...-pose.pt): this detector has no keypoint columns"
+    if a.redact and a.redact_region == "mask" and "seg" not in base:
+        return "--redact-region mask needs a segmentation model (--weights ...-seg.pt): this detector has no masks"
+    if a.redact and a.redact_region in ("head", "mask") and "obb" in base:
+        return f"--redact-region {a.redact_region} is not available on an oriented-box model"
+    return None
 
 
 def zone_config(args: dict, n_names: int):
@@ -733,6 +770,15 @@ def main(argv=None):
     p.add_argument("--slice-metric", choices=("ios", "iou"), default="ios", help="--slice: intersection over the smaller area, or over the union")
     p.add_argument("--slice-thr", type=float, default=0.5, help="--slice: the match threshold")
     p.add_argument("--no-slice-full", action="store_true", help="--slice: do not add the whole frame as one more tile")
+    p.add_argument("--redact", choices=("blur", "pixelate", "fill"), default=None,
+                   help="--save only: hide the detected objects in the saved frames on the device before anything is drawn (csrc/ss_redact.hip, docs/REDACT.md); "
+                        "labels, dets, zones and metrics files are unchanged")
+    p.add_argument("--redact-region", choices=("box", "ellipse", "head", "mask"), default="box",
+                   help="--redact: the box, the ellipse inscribed in it, the head from a pose model's face keypoints, or a segmentation model's silhouette")
+    p.add_argument("--redact-strength", type=int, default=None, help="--redact: blur radius 1 .. 31 (default 15) or pixelate cell 4, 8, 16, 32 (default 16)")
+    p.add_argument("--redact-classes", type=int, nargs="+", default=None, metavar="CLS", help="--redact: only these classes (default: every class)")
+    p.add_argument("--redact-pad", type=float, default=0.0, help="--redact with box / ellipse: this fraction of the box side is added on each side")
+    p.add_argument("--redact-color", type=int, nargs=3, default=None, metavar=("B", "G", "R"), help="--redact fill: the colour (default 0 0 0)")
     a = p.parse_args(argv)
     from . import zones as _zones
     try:
@@ -742,6 +788,10 @@ def main(argv=None):
             raise ValueError("--heat-alpha must be 0 .. 1")
         zone_config({"lines": a.line, "zones": a.zone, "heatmap": a.heatmap, "zone_anchor": a.zone_anchor, "zone_gap": a.zone_gap,
                      "heat_cell": a.heat_cell, "heat_alpha": a.heat_alpha}, 80)
+        why = redact_refusal(a)
+        if why:
+            raise ValueError(why)
+        redact_config(vars(a))
     except ValueError as e:
         p.error(str(e))
     if a.mtmc:
@@ -841,7 +891,8 @@ def main(argv=None):
              "aflink": a.aflink, "aflink_thr_t": tuple(a.aflink_thr_t), "aflink_thr_s": a.aflink_thr_s, "aflink_thr_p": a.aflink_thr_p,
              "lines": a.line, "zones": a.zone, "zone_anchor": a.zone_anchor, "zone_gap": a.zone_gap, "heatmap": a.heatmap, "heat_cell": a.heat_cell, "heat_alpha": a.heat_alpha,
              "slice": a.slice, "slice_overlap": a.slice_overlap, "slice_merge": a.slice_merge, "slice_metric": a.slice_metric, "slice_thr": a.slice_thr, "no_slice_full": a.no_slice_full,
-             "mtmc": a.mtmc, "save": _save_path(a, i)}
+             "redact": a.redact, "redact_region": a.redact_region, "redact_strength": a.redact_strength, "redact_classes": a.redact_classes, "redact_pad": a.redact_pad,
+             "redact_color": a.redact_color, "mtmc": a.mtmc, "save": _save_path(a, i)}
             for i, s in enumerate(a.source)]
     import torch
     ngpu = max(torch.cuda.device_count(), 1)

@@ -1706,6 +1706,30 @@ extern "C" int ss_zone_heat_blend(ss_ctx* c, void* hip_stream, uint8_t* d_frames
         });
 }
 
+// ---- redaction of regions of resident frames: blur, pixelate, fill (ss_redact.hip, docs/REDACT.md) ---------------------------------
+extern "C" int ss_redact_max_regions(void) { return ss_redact_max_regions_impl(); }
+extern "C" int ss_redact_max_vertices(void) { return ss_redact_max_vertices_impl(); }
+extern "C" int ss_redact_max_radius(void) { return ss_redact_max_radius_impl(); }
+extern "C" long long ss_redact_scratch_bytes(int batch, int h, int w) { return ss_redact_scratch_bytes_impl(batch, h, w); }
+
+extern "C" int ss_redact(ss_ctx* c, void* hip_stream, uint8_t* d_frames, int batch, long long frame_batch_stride, int h, int w, int row_stride,
+                         const int* d_regions, const int* d_region_off, const int* d_verts, int effect, int strength, int fill_bgr, void* d_scratch,
+                         long long scratch_bytes)
+{
+    return post_run(c, "ss_redact",
+        [&](std::string& err) {
+            if (int rc = ss_redact_check_impl(d_frames, batch, frame_batch_stride, h, w, row_stride, d_regions, d_region_off, d_verts, effect, strength,
+                                              fill_bgr, d_scratch, scratch_bytes, err))
+                return rc;
+            if (!c) { err = "ss_redact: null context"; return (int)SS_ERR_INVALID; }
+            return (int)SS_OK;
+        },
+        [&](std::string& err) {
+            return ss_redact_impl((hipStream_t)hip_stream, d_frames, batch, frame_batch_stride, h, w, row_stride, d_regions, d_region_off, d_verts, effect,
+                                  strength, fill_bgr, d_scratch, err);
+        });
+}
+
 // ---- the tracker families: BYTE (ss_byte.hip), OC-SORT (ss_ocsort.hip), Deep OC-SORT (ss_deepoc.hip) --------------------------------
 // Each family's state, tables, reset and read-back live beside its kernels; include/strongsort_hip.h says what each entry does.
 // An entry that needs the state: ok (it is there and the entry's own arguments are sound) and the stream, all worded "no <what>".

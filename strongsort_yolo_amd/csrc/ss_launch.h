@@ -223,6 +223,17 @@ int  ss_zone_blend_impl(SSZone* z, hipStream_t st, uint8_t* d_frames, int batch,
                         const int* d_heat, long long heat_frame_stride, const int* d_max, int max_stride, int alpha, std::string& err);
 void ss_zone_free(SSZone* z);
 
+// ---- ss_redact.hip
+int  ss_redact_max_regions_impl();
+int  ss_redact_max_vertices_impl();
+int  ss_redact_max_radius_impl();
+long long ss_redact_scratch_bytes_impl(int batch, int h, int w);
+int  ss_redact_check_impl(const uint8_t* d_frames, int batch, long long frame_batch_stride, int h, int w, int row_stride, const int* d_regions,
+                          const int* d_region_off, const int* d_verts, int effect, int strength, int fill_bgr, const void* d_scratch,
+                          long long scratch_bytes, std::string& err);
+int  ss_redact_impl(hipStream_t st, uint8_t* d_frames, int batch, long long frame_batch_stride, int h, int w, int row_stride, const int* d_regions,
+                    const int* d_region_off, const int* d_verts, int effect, int strength, int fill_bgr, void* d_scratch, std::string& err);
+
 // ---- ss_mtmc.hip
 struct SSBank;
 struct SSMtmc;

@@ -259,30 +259,35 @@ class Overlay:
         self._keep.append((d_prims, d_off, d_chars))
         return frames
 
-    def annotate_resident(self, dev_frame: torch.Tensor, results, counts: Optional[dict] = None, fps_text: str = "", stream=None, zones=None) -> torch.Tensor:
+    def annotate_resident(self, dev_frame: torch.Tensor, results, counts: Optional[dict] = None, fps_text: str = "", stream=None, zones=None,
+                          redact=None) -> torch.Tensor:
         """A frame that is ALREADY on the device (uint8 [H,W,3]) annotated in place and returned still on the device: what a
         device-side consumer (the JPEG sink, cli.FrameSink.write_device) takes; no transfer of the frame in either direction.
-        zones (a zones.ZoneFrame): its heat map is blended over the frame first, then its lines and zones are drawn with the rest."""
+        zones (a zones.ZoneFrame): its heat map is blended over the frame first, then its lines and zones are drawn with the rest.
+        redact (a redact.Redactor, docs/REDACT.md): the results' regions are blurred, pixelated or filled before anything else, so the
+        heat and the drawing (boxes, labels) lie legible on top; None (the default) leaves the frame's bytes as they were."""
+        if redact is not None:
+            redact.apply_device(dev_frame, results, stream)
         if zones is None:
             return self.draw_device(dev_frame, [self.commands(results, counts, fps_text)], stream)
         zones.blend_into(dev_frame, stream)
         return self.draw_device(dev_frame, [self.commands(results, counts, fps_text, zones)], stream)
 
-    def draw_resident(self, dev_frame: torch.Tensor, results, counts: Optional[dict] = None, fps_text: str = "", zones=None) -> np.ndarray:
+    def draw_resident(self, dev_frame: torch.Tensor, results, counts: Optional[dict] = None, fps_text: str = "", zones=None, redact=None) -> np.ndarray:
         """A frame that is ALREADY on the device (uint8 [H,W,3], e.g. `Results.orig_img_device` of track_stream) -> annotated
         host frame: ss_overlay in place, one download, no upload of the frame."""
-        self.annotate_resident(dev_frame, results, counts, fps_text, zones=zones)
+        self.annotate_resident(dev_frame, results, counts, fps_text, zones=zones, redact=redact)
         out = np.empty(tuple(dev_frame.shape), np.uint8)
         self.eng.download(out, dev_frame)
         return out
 
-    def draw(self, frame: np.ndarray, results, counts: Optional[dict] = None, fps_text: str = "", zones=None) -> np.ndarray:
+    def draw(self, frame: np.ndarray, results, counts: Optional[dict] = None, fps_text: str = "", zones=None, redact=None) -> np.ndarray:
         """Host frame in, annotated host frame out (upload -> ss_overlay -> download)."""
         e = self.eng
         if self._scratch is None or self._scratch.shape != frame.shape:
             self._scratch = torch.empty(frame.shape, dtype=torch.uint8, device=e.device)
         e.upload(self._scratch, frame)
-        self.annotate_resident(self._scratch, results, counts, fps_text, zones=zones)
+        self.annotate_resident(self._scratch, results, counts, fps_text, zones=zones, redact=redact)
         out = np.empty_like(frame)
         e.download(out, self._scratch)
         return out
