@@ -25,6 +25,10 @@
 //
 // Sums are fp32 in a fixed order (no atomics), so a launch is reproducible; the order is not PyTorch's, so the results agree
 // with the fp32 CPU network to rounding (1e-6 relative per layer), not bit for bit: tests/test_gpu_nets32.py states the bounds.
+//
+// One place per fact: a kernel with dynamic LDS carves it from a layout struct (ChainsLds, Ch3, ChR, TailLds, StemLds) and its launcher
+// sizes the launch from the same struct; the chain kernels share the pieces of a LightConv layer (ld_w1x1, ld_x1, mm_1x1, dw9_relu,
+// lane_sum), the stem kernels StemRows / stem_weights / stem_pool; every launch goes through launch32 (LDS limit, launch, check).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -50,6 +54,24 @@ static __device__ __forceinline__ f4 relu4(const f4 v)
 static __device__ __forceinline__ f4 max4(const f4 a, const f4 b)
 {
     return f4{ a[0] > b[0] ? a[0] : b[0], a[1] > b[1] ? a[1] : b[1], a[2] > b[2] ? a[2] : b[2], a[3] > b[3] ? a[3] : b[3] };
+}
+// the two activations with an exponential, in the forms docs/F32_OPERATORS.md section 4 derives its bounds from
+static __device__ __forceinline__ float silu32(float v) { return v / (1.0f + expf(-v)); }
+static __device__ __forceinline__ float sigmoid32(float v) { return 1.0f / (1.0f + expf(-v)); }
+// images a launch works on: the batch, or the device-side count when that is smaller
+static __device__ __forceinline__ int valid_count(int Nimg, const int* n_img)
+{
+    int nv = Nimg;
+    if (n_img && *n_img < nv) nv = *n_img;
+    return nv;
+}
+// sum of v over the LANES (8 | 16) lanes of this lane's group, in every lane of it (xor butterfly, distance 1 first)
+template <int LANES>
+static __device__ __forceinline__ float lane_sum(float v)
+{
+    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
+    if (LANES == 16) v += __shfl_xor(v, 8);
+    return v;
 }
 
 // Weight matrix [N][K] -> LDS rows of KP = 16 JJ + 4 floats, zero in the padding columns and in the rows N .. NP - 1 (24 output channels =
@@ -145,6 +167,60 @@ __global__ __launch_bounds__(256) void k32_pw(const float* __restrict__ x, const
 // Rows outside the image hold ZERO in P (they are the depthwise layer's padding); rows outside the LDS window count as zero too,
 // which only reaches halo rows whose values are never stored.  Outputs: ys[t] band rows, psum[t][img][band][c] = their channel sums.
 #define C32_THREADS 768
+// LDS of k32_chains, in floats: P, Q [RB rows][W][C + 4], S [C32_THREADS / (C / 4) slots][C]
+struct ChainsLds {
+    int Q, S, total;                                            // (P = 0)
+    __host__ __device__ ChainsLds(int RB, int W, int C) : Q(RB * W * (C + 4)), S(Q + Q), total(S + C32_THREADS / (C / 4) * C) {}
+    __host__ __device__ size_t bytes() const { return (size_t)total * 4; }
+};
+
+// ---- the pieces of a LightConv layer the three chain kernels share ---------------------------------------------------------------
+// the A fragments of a layer's 1x1 matrix wl [C][C]: a[mt][jj] = W[16 mt + n][chunk kq + 4 jj], zero past C (clamped address + select)
+template <int C>
+static __device__ __forceinline__ void ld_w1x1(const float* wl, int kq, int n, f4 (&a)[(C + 15) / 16][(C / 4 + 3) / 4])
+{
+    constexpr int CH = C / 4, JJ = (CH + 3) / 4, MT = (C + 15) / 16;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int jj = 0; jj < JJ; ++jj) {
+            const int row = 16 * mt + n, c = kq + 4 * jj;
+            const f4 v = ld4(wl + (unsigned)((row < C ? row : 0) * C + 4 * (c < CH ? c : 0)));
+            a[mt][jj] = (row < C && c < CH) ? v : zero4();
+        }
+}
+// chunk c (chunk 0 past the last) of pixel (row yc, column x) of the image at xi: the caller clamps the row and selects zero
+// where it has to, so the load is unconditional (no branch per vector)
+template <int C, int W>
+static __device__ __forceinline__ f4 ld_x1(const float* xi, int yc, int x, int c)
+{
+    return ld4(xi + (unsigned)((yc * W + x) * C + 4 * (c < C / 4 ? c : 0)));
+}
+static __device__ __forceinline__ int clamp_row(int y, int H) { return y < 0 ? 0 : (y >= H ? H - 1 : y); }
+// acc[mt] = W[16 mt .. + 15][:] x b for a 16-pixel tile, the K axis in the order (jj, s)
+template <int MT, int JJ>
+static __device__ __forceinline__ void mm_1x1(const f4 (&a)[MT][JJ], const f4 (&b)[JJ], f4 (&acc)[MT])
+{
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = zero4();
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int jj = 0; jj < JJ; ++jj)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc[mt] = MFMA4(a[mt][jj][s], b[jj][s], acc[mt]);
+}
+// depthwise 3x3 + bias + ReLU of one pixel from its window (t: row above, m: its row, b: row below), summed in the fixed order bias, taps 0 .. 8
+static __device__ __forceinline__ f4 dw9_relu(const f4 (&k9)[9], const f4 bb, const f4 t0, const f4 t1, const f4 t2, const f4 m0, const f4 m1,
+                                              const f4 m2, const f4 b0, const f4 b1, const f4 b2)
+{
+    f4 o = bb;
+    o = fma4(k9[0], t0, o); o = fma4(k9[1], t1, o); o = fma4(k9[2], t2, o);
+    o = fma4(k9[3], m0, o); o = fma4(k9[4], m1, o); o = fma4(k9[5], m2, o);
+    o = fma4(k9[6], b0, o); o = fma4(k9[7], b1, o); o = fma4(k9[8], b2, o);
+    return relu4(o);
+}
+
 template <int C, int W>
 __global__ __launch_bounds__(C32_THREADS) void k32_chains(const float* __restrict__ x1, const float* __restrict__ w1 /*[10][C][C]*/,
                                                         const float* __restrict__ w9 /*[10][9][C]*/, const float* __restrict__ bs /*[10][C]*/,
@@ -158,14 +234,16 @@ __global__ __launch_bounds__(C32_THREADS) void k32_chains(const float* __restric
     const int img = blockIdx.y, band = blockIdx.x, bands = gridDim.x;
     if (n_img && img >= *n_img) return;
     const int RB = R + 2 * HALO, r0 = band * R - HALO;          // image row of LDS row 0
+    const ChainsLds L(RB, W, C);
     float* __restrict__ P = smem32;
-    float* __restrict__ Q = P + RB * W * PITCH;
-    float* __restrict__ S = Q + RB * W * PITCH;                 // [SLOTS][C] partial channel sums of a chain's last layer
+    float* __restrict__ Q = smem32 + L.Q;
+    float* __restrict__ S = smem32 + L.S;                       // [SLOTS][C] partial channel sums of a chain's last layer
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, n = lane & 15;
     const int chunk = tid % CH, slot = tid / CH, xx = slot % W, rg = slot / W;
     const int RPG = (RB + RGS - 1) / RGS, ra = rg * RPG, rb = (ra + RPG < RB) ? ra + RPG : RB;
     const int ntiles = RB * W / 16;
     const size_t ibase = (size_t)img * H * W * C;
+    const float* __restrict__ xi = x1 + ibase;
     int layer = 0;
 #pragma unroll 1
     for (int t = 0; t < 4; ++t) {
@@ -175,14 +253,7 @@ __global__ __launch_bounds__(C32_THREADS) void k32_chains(const float* __restric
             // ---- 1x1 (no bias, no activation): source x1 (global) for a chain's first layer, Q afterwards
             {
                 f4 a[MT][JJ];
-                const float* wl = w1 + (size_t)layer * C * C;
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int jj = 0; jj < JJ; ++jj) {
-                        const int row = 16 * mt + n, c = kq + 4 * jj;
-                        a[mt][jj] = (row < C && c < CH) ? ld4(wl + row * C + 4 * c) : zero4();
-                    }
+                ld_w1x1<C>(w1 + (size_t)layer * C * C, kq, n, a);
                 for (int tile = wave; tile < ntiles; tile += C32_THREADS / 64) {
                     const int p = tile * 16 + n, r = p / W, y = r0 + r;
                     const bool inimg = y >= 0 && y < H;
@@ -190,19 +261,11 @@ __global__ __launch_bounds__(C32_THREADS) void k32_chains(const float* __restric
 #pragma unroll
                     for (int jj = 0; jj < JJ; ++jj) {
                         const int c = kq + 4 * jj;
-                        const int cc = c < CH ? c : 0, yc = y < 0 ? 0 : (y >= H ? H - 1 : y);
-                        const f4 v = d == 0 ? ld4(x1 + ibase + ((size_t)yc * W + (p - r * W)) * C + 4 * cc) : ld4(Q + p * PITCH + 4 * cc);
+                        const f4 v = d == 0 ? ld_x1<C, W>(xi, clamp_row(y, H), p - r * W, c) : ld4(Q + p * PITCH + 4 * (c < CH ? c : 0));
                         b[jj] = (c < CH && (d != 0 || inimg)) ? v : zero4();
                     }
                     f4 acc[MT];
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc[mt] = zero4();
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                        for (int jj = 0; jj < JJ; ++jj)
-#pragma unroll
-                            for (int s = 0; s < 4; ++s) acc[mt] = MFMA4(a[mt][jj][s], b[jj][s], acc[mt]);
+                    mm_1x1<MT, JJ>(a, b, acc);
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt) {
                         const int co = 4 * mt + kq;                 // output chunk
@@ -231,11 +294,7 @@ __global__ __launch_bounds__(C32_THREADS) void k32_chains(const float* __restric
                     f4 m0 = ld(ra, xx - 1), m1 = ld(ra, xx), m2 = ld(ra, xx + 1);
                     for (int r = ra; r < rb; ++r) {
                         const f4 b0 = ld(r + 1, xx - 1), b1 = ld(r + 1, xx), b2 = ld(r + 1, xx + 1);
-                        f4 o = bb;
-                        o = fma4(k9[0], t0, o); o = fma4(k9[1], t1, o); o = fma4(k9[2], t2, o);
-                        o = fma4(k9[3], m0, o); o = fma4(k9[4], m1, o); o = fma4(k9[5], m2, o);
-                        o = fma4(k9[6], b0, o); o = fma4(k9[7], b1, o); o = fma4(k9[8], b2, o);
-                        o = relu4(o);
+                        const f4 o = dw9_relu(k9, bb, t0, t1, t2, m0, m1, m2, b0, b1, b2);
                         st4(Q + (r * W + xx) * PITCH + 4 * chunk, o);
                         const int y = r0 + r;
                         if (last && r >= HALO && r < HALO + R && y >= 0 && y < H) {
@@ -270,8 +329,15 @@ __global__ __launch_bounds__(C32_THREADS) void k32_chains(const float* __restric
 //  * channel sums by wave shuffles, one LDS vector per (wave, lane row).
 // 24 channels = 6 chunks: waves 0..7 take chunks 0..3 of four rows each, waves 8..11 chunks 4, 5 of TWO row runs at once (lane
 // rows kq < 2 / kq >= 2), so all twelve waves walk four rows.
-template <int C> struct Ch3 {
-    static constexpr int PITCH = (C == 24) ? 24 : C + 8;
+// The thread maps cover a band of exactly ROWS LDS rows (R + 2 HALO of the launch): the 1x1 phase gives PWV waves TPW tiles of 16
+// pixels each, the depthwise phase gives DWV waves RPG rows each of a 16-column strip.  LDS in floats: P [(RB + 2)][W + 2][PITCH] (the
+// 1x1 output inside a one-pixel zero border), Q [RB][W][PITCH], S [NWV][4 lane rows][4] partial channel sums.
+template <int C, int W> struct Ch3 {
+    static constexpr int PITCH = (C == 24) ? 24 : C + 8, PW = W + 2, NWV = C32_THREADS / 64, RPG = 4, TPW = 4;
+    static constexpr int ROWS = (C == 16) ? 24 : 32, PWV = ROWS * W / (16 * TPW), DWV = ROWS / RPG;
+    int Q, S, total;                                            // (P = 0)
+    __host__ __device__ Ch3(int RB) : Q((RB + 2) * PW * PITCH), S(Q + RB * W * PITCH), total(S + NWV * 16) {}
+    __host__ __device__ size_t bytes() const { return (size_t)total * 4; }
 };
 template <int C, int W, bool PRE>
 __global__ __launch_bounds__(C32_THREADS) void k32_chains3(const float* __restrict__ x1, const float* __restrict__ w1 /*[10][C][C]*/,
@@ -280,38 +346,31 @@ __global__ __launch_bounds__(C32_THREADS) void k32_chains3(const float* __restri
                                                          float* __restrict__ y3, float* __restrict__ psum, int Nimg, int H, int R, int HALO,
                                                          const int* __restrict__ n_img)
 {
-    constexpr int CH = C / 4, JJ = (CH + 3) / 4, MT = (C + 15) / 16, PITCH = Ch3<C>::PITCH, NWV = C32_THREADS / 64, RPG = 4;
-    constexpr int TPW = 4, PWV = (C == 16) ? 12 : 8;             // 1x1 phase: 4 tiles of 16 pixels per wave on 12 (48 tiles) / 8 (32 tiles) waves
-    static_assert((C == 16 && W == 32) || (C == 24 && W == 16), "instantiated for the 64 x 32 x 16 and 32 x 16 x 24 maps");
+    using L3 = Ch3<C, W>;
+    constexpr int CH = C / 4, JJ = (CH + 3) / 4, MT = (C + 15) / 16, PITCH = L3::PITCH, NWV = L3::NWV, RPG = L3::RPG;
+    constexpr int TPW = L3::TPW, PWV = L3::PWV, DWV = L3::DWV;   // 1x1 phase: 4 tiles of 16 pixels per wave on 12 (48 tiles) / 8 (32 tiles) waves
+    static_assert((C == 16 && W == 32 && PWV == 12 && 2 * DWV == NWV) || (C == 24 && W == 16 && PWV == 8 && DWV == 8),
+                  "instantiated for the 64 x 32 x 16 and 32 x 16 x 24 maps");
     extern __shared__ __attribute__((aligned(16))) float smem32[];
     const int img = blockIdx.y, band = blockIdx.x, bands = gridDim.x;
     if (n_img && img >= *n_img) return;
-    const int RB = R + 2 * HALO, r0 = band * R - HALO;          // image row of LDS row 0 (host: RB == 24 for C 16, 32 for C 24)
+    const int RB = R + 2 * HALO, r0 = band * R - HALO;          // image row of LDS row 0 (the launcher checks RB == Ch3::ROWS)
     // P carries a one-pixel ZERO border (rows -1 and RB, columns -1 and W): the nine taps of a pixel are nine plain loads at
     // immediate offsets from one lane base — no bounds test, no clamp, no select (they were 60 % of the kernel's vector instructions)
-    constexpr int PW = W + 2;
-    float* __restrict__ P = smem32;                             // [(RB + 2)][W + 2][PITCH]
-    float* __restrict__ Q = P + (RB + 2) * PW * PITCH;          // [RB][W][PITCH]
-    float* __restrict__ S = Q + RB * W * PITCH;                 // [NWV][4 lane rows][4] partial channel sums
+    constexpr int PW = L3::PW;
+    const L3 L(RB);
+    float* __restrict__ P = smem32;
+    float* __restrict__ Q = smem32 + L.Q;
+    float* __restrict__ S = smem32 + L.S;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), kq = lane >> 4, n = lane & 15;
     // depthwise unit of this lane: chunk dc of column dx, rows dra .. dra + 3
     int dc, dx, dra;
-    if (C == 16) { const int xt = wave / 6; dc = kq; dx = 16 * xt + n; dra = (wave - 6 * xt) * RPG; }
-    else if (wave < 8) { dc = kq; dx = n; dra = wave * RPG; }
-    else { dc = 4 + (kq & 1); dx = n; dra = (2 * (wave - 8) + (kq >> 1)) * RPG; }
+    if (C == 16) { const int xt = wave / DWV; dc = kq; dx = 16 * xt + n; dra = (wave - DWV * xt) * RPG; }
+    else if (wave < DWV) { dc = kq; dx = n; dra = wave * RPG; }
+    else { dc = 4 + (kq & 1); dx = n; dra = (2 * (wave - DWV) + (kq >> 1)) * RPG; }
     const float* __restrict__ xi = x1 + (size_t)img * H * W * C;
 
-    auto load_a = [&](int layer, f4 (&a)[MT][JJ]) {
-        const float* wl = w1 + (size_t)layer * C * C;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int jj = 0; jj < JJ; ++jj) {
-                const int row = 16 * mt + n, c = kq + 4 * jj;
-                const f4 v = ld4(wl + (unsigned)((row < C ? row : 0) * C + 4 * (c < CH ? c : 0)));
-                a[mt][jj] = (row < C && c < CH) ? v : zero4();
-            }
-    };
+    auto load_a = [&](int layer, f4 (&a)[MT][JJ]) { ld_w1x1<C>(w1 + (size_t)layer * C * C, kq, n, a); };
     auto load_x1 = [&](f4 (&b)[PRE ? TPW : 1][JJ]) {                        // this wave's tiles of the band, straight from the block's conv1 output
 #pragma unroll
         for (int i = 0; i < (PRE ? TPW : 1); ++i) {
@@ -320,8 +379,7 @@ __global__ __launch_bounds__(C32_THREADS) void k32_chains3(const float* __restri
             for (int jj = 0; jj < JJ; ++jj) {
                 const int c = kq + 4 * jj;
                 const bool ok = c < CH && y >= 0 && y < H;
-                const int yc = y < 0 ? 0 : (y >= H ? H - 1 : y), cc = c < CH ? c : 0;
-                const f4 v = ld4(xi + (unsigned)((yc * W + (p - r * W)) * C + 4 * cc));      // unconditional load + select (see the depthwise taps)
+                const f4 v = ld_x1<C, W>(xi, clamp_row(y, H), p - r * W, c);
                 b[i][jj] = ok ? v : zero4();
             }
         }
@@ -358,20 +416,13 @@ __global__ __launch_bounds__(C32_THREADS) void k32_chains3(const float* __restri
                             const f4 qv = ld4(Q + p * PITCH + 4 * cc);
                             b[jj] = d == 0 ? bpre[i][jj] : (c < CH ? qv : zero4());
                         } else {
-                            const int yc = y < 0 ? 0 : (y >= H ? H - 1 : y);
-                            const f4 v = d == 0 ? ld4(xi + (unsigned)((yc * W + (p - r * W)) * C + 4 * cc)) : ld4(Q + p * PITCH + 4 * cc);
+                            const int yc = clamp_row(y, H);
+                            const f4 v = d == 0 ? ld_x1<C, W>(xi, yc, p - r * W, cc) : ld4(Q + p * PITCH + 4 * cc);
                             b[jj] = (c < CH && (d != 0 || inimg)) ? v : zero4();
                         }
                     }
                     f4 acc[MT];
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc[mt] = zero4();
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                        for (int jj = 0; jj < JJ; ++jj)
-#pragma unroll
-                            for (int s = 0; s < 4; ++s) acc[mt] = MFMA4(a[mt][jj][s], b[jj][s], acc[mt]);
+                    mm_1x1<MT, JJ>(a, b, acc);
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt) {
                         const int co = 4 * mt + kq;
@@ -394,11 +445,7 @@ __global__ __launch_bounds__(C32_THREADS) void k32_chains3(const float* __restri
                 for (int i = 0; i < RPG; ++i) {
                     const int r = dra + i;
                     const f4 b0 = ld(i + 2, 0), b1 = ld(i + 2, 1), b2 = ld(i + 2, 2);
-                    f4 o = bb;
-                    o = fma4(k9[0], t0, o); o = fma4(k9[1], t1, o); o = fma4(k9[2], t2, o);
-                    o = fma4(k9[3], m0, o); o = fma4(k9[4], m1, o); o = fma4(k9[5], m2, o);
-                    o = fma4(k9[6], b0, o); o = fma4(k9[7], b1, o); o = fma4(k9[8], b2, o);
-                    o = relu4(o);
+                    const f4 o = dw9_relu(k9, bb, t0, t1, t2, m0, m1, m2, b0, b1, b2);
                     st4(Q + (r * W + dx) * PITCH + 4 * dc, o);
                     const int y = r0 + r;
                     if (last && r >= HALO && r < HALO + R && y >= 0 && y < H) {
@@ -410,11 +457,7 @@ __global__ __launch_bounds__(C32_THREADS) void k32_chains3(const float* __restri
             }
             if (last) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float v = psa[j];
-                    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
-                    psa[j] = v;
-                }
+                for (int j = 0; j < 4; ++j) psa[j] = lane_sum<16>(psa[j]);
                 if (n == 0) st4(S + (wave * 4 + kq) * 4, psa);
             }
             LDS_BARRIER32();
@@ -422,9 +465,9 @@ __global__ __launch_bounds__(C32_THREADS) void k32_chains3(const float* __restri
                 const int cq = tid >> 2, j = tid & 3;
                 float sum = 0.f;
                 if (C == 16 || cq < 4) {
-                    for (int wv = 0; wv < (C == 16 ? NWV : 8); ++wv) sum += S[(wv * 4 + cq) * 4 + j];
+                    for (int wv = 0; wv < (C == 16 ? NWV : DWV); ++wv) sum += S[(wv * 4 + cq) * 4 + j];
                 } else {
-                    for (int wv = 8; wv < NWV; ++wv) { sum += S[(wv * 4 + (cq - 4)) * 4 + j]; sum += S[(wv * 4 + (cq - 2)) * 4 + j]; }
+                    for (int wv = DWV; wv < NWV; ++wv) { sum += S[(wv * 4 + (cq - 4)) * 4 + j]; sum += S[(wv * 4 + (cq - 2)) * 4 + j]; }
                 }
                 psum[(((size_t)t * Nimg + img) * bands + band) * C + tid] = sum;
             }
@@ -458,6 +501,7 @@ static __device__ __forceinline__ float dppf_shl1_z(float v) { return __builtin_
 template <int C> struct ChR {
     static constexpr int CH = C / 4, JJ = (CH + 3) / 4, MT = JJ, CP = 16 * JJ, KP = CP + 4, NPR = (C % 16) ? C + 1 : C;   // NPR: rows of a staged 1x1 matrix (+ one zero row)
     static constexpr int TAB = 10 * 10 * CP;                       // floats: [layer][9 taps + bias][CP]
+    static constexpr size_t bytes(bool alds) { return (size_t)(TAB + (alds ? 10 * NPR * KP : 0)) * 4; }     // ALDS: + [layer][NPR][KP] 1x1 matrices
 };
 
 // One chain of L layers (global layer indices l0 .. l0 + L - 1) over the H rows of one image, by one wave.
@@ -562,15 +606,7 @@ static __device__ __forceinline__ void chain_rows(const float* __restrict__ xi, 
     ChainState<C, W, L, ALDS> S;
     if (!ALDS) {
 #pragma unroll
-        for (int l = 0; l < L; ++l)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int jj = 0; jj < JJ; ++jj) {
-                    const int row = 16 * mt + n, c = kq + 4 * jj;
-                    const f4 v = ld4(w1g + (size_t)(l0 + l) * C * C + (unsigned)((row < C ? row : 0) * C + 4 * (c < CH ? c : 0)));
-                    S.a[l][mt][jj] = (row < C && c < CH) ? v : zero4();
-                }
+        for (int l = 0; l < L; ++l) ld_w1x1<C>(w1g + (size_t)(l0 + l) * C * C, kq, n, S.a[l]);
     }
     const int tl0 = l0 * 10 * CP + 4 * kq;                                     // this lane's chunk of the chain's first tap row (float offset)
     const int wl0 = ChR<C>::TAB + l0 * NPR * KP + 4 * kq;
@@ -590,10 +626,7 @@ static __device__ __forceinline__ void chain_rows(const float* __restrict__ xi, 
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int jj = 0; jj < JJ; ++jj) {
-                const int c = kq + 4 * jj;
-                d[t][jj] = ld4(xi + (unsigned)((rc * W + (W == 8 ? col0 : NT * n + t)) * C + 4 * (c < CH ? c : 0)));
-            }
+            for (int jj = 0; jj < JJ; ++jj) d[t][jj] = ld_x1<C, W>(xi, rc, W == 8 ? col0 : NT * n + t, kq + 4 * jj);
     };
     auto inside = [&](int r) -> float { return (r >= 0 && r < H) ? __builtin_inff() : 0.f; };
     f4 in0[NT][JJ];
@@ -654,12 +687,7 @@ static __device__ __forceinline__ void chain_rows(const float* __restrict__ xi, 
     for (int mt = 0; mt < MT; ++mt) {
         f4 v = S.sum[mt];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float s = v[j];
-            s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
-            if (W != 8) s += __shfl_xor(s, 8);
-            v[j] = s;
-        }
+        for (int j = 0; j < 4; ++j) v[j] = lane_sum<(W == 8 ? 8 : 16)>(v[j]);
         if (W == 8) { if ((n & 7) == 0 && (n == 0 || second)) st4(ps + (n >> 3) * C + 4 * (kq + 4 * mt), v); }      // (psum rows of consecutive images are C apart)
         else if (n == 0 && (MT * 4 == CH || kq + 4 * mt < CH)) st4(ps + 4 * (kq + 4 * mt), v);
     }
@@ -695,8 +723,7 @@ __global__ __launch_bounds__(R32_THREADS, 2) void k32_chainsR(const float* __res
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), kq = lane >> 4, n = lane & 15;
     constexpr int IPW = W == 8 ? 2 : 1;                          // images per wave (two 8-wide images side by side in the 16 lanes of a row)
     const int img = (blockIdx.x * 2 + (wave >> 1)) * IPW, pair = wave & 1;
-    int nv = Nimg;
-    if (n_img && *n_img < nv) nv = *n_img;
+    const int nv = valid_count(Nimg, n_img);
     if (img >= nv) return;
     const bool second = img + 1 < nv;
     const size_t ib = (size_t)img * H * W * C;
@@ -754,7 +781,7 @@ __global__ __launch_bounds__(128) void k32_gates(const float* __restrict__ psum,
     if (c < MID) {
         float s = gb2[c];
         for (int j = 0; j < hidden; ++j) s = __builtin_fmaf(gw2[c * hidden + j], Hd[t * 4 + j], s);
-        gates[((size_t)t * Nimg + img) * MID + c] = 1.0f / (1.0f + expf(-s));
+        gates[((size_t)t * Nimg + img) * MID + c] = sigmoid32(s);
     }
 }
 
@@ -764,6 +791,13 @@ __global__ __launch_bounds__(128) void k32_gates(const float* __restrict__ psum,
 // allow), each stages the three weight matrices ONCE and then walks its share of the images (all tiles of an image by its eight
 // waves), so the staging is paid once per CU instead of once per 8-32 tiles.
 #define T32_THREADS 512
+// LDS of k32_tail, in floats: the three staged matrices, behind them the biases ([C2] b3 (+ bd), [16 MT4] b4, zero past N2), then one
+// gate table [4][GP] per wave
+template <int MID, int C2, int C1, int N2> struct TailLds {
+    static constexpr int JM = (MID / 4 + 3) / 4, MT4 = (N2 + 15) / 16, GP = 16 * JM, WV = T32_THREADS / 64;
+    static constexpr int W3 = 0, WD = W3 + w_lds_floats<MID, C2>(), W4 = WD + (C1 ? w_lds_floats<(C1 ? C1 : 16), C2>() : 0);
+    static constexpr int B = W4 + w_lds_floats<C2, N2>(), G = B + C2 + 16 * MT4, TOTAL = G + WV * 4 * GP;
+};
 template <int MID, int C2, int C1, int N2, bool POOL>
 __global__ __launch_bounds__(T32_THREADS, 4) void k32_tail(const float* __restrict__ y0, const float* __restrict__ y1, const float* __restrict__ y2,
                                                 const float* __restrict__ y3, const float* __restrict__ gates, const float* __restrict__ w3,
@@ -772,19 +806,17 @@ __global__ __launch_bounds__(T32_THREADS, 4) void k32_tail(const float* __restri
                                                 const float* __restrict__ b4, float* __restrict__ out2, int Nimg, int H, int W,
                                                 const int* __restrict__ n_img, int splits)
 {
-    constexpr int CHM = MID / 4, JM = (CHM + 3) / 4, MT3 = C2 / 16, CH1 = C1 / 4, J1 = (CH1 + 3) / 4, MT4 = (N2 + 15) / 16, CH4 = N2 / 4;
-    constexpr int L3 = w_lds_floats<MID, C2>(), LD = C1 ? w_lds_floats<(C1 ? C1 : 16), C2>() : 0, WV = T32_THREADS / 64;
+    using TL = TailLds<MID, C2, C1, N2>;
+    constexpr int CHM = MID / 4, JM = TL::JM, MT3 = C2 / 16, CH1 = C1 / 4, J1 = (CH1 + 3) / 4, MT4 = TL::MT4, CH4 = N2 / 4, WV = TL::WV, GP = TL::GP;
     static_assert(C2 % 16 == 0, "C2");
     extern __shared__ __attribute__((aligned(16))) float smem32[];
-    constexpr int L4 = w_lds_floats<C2, N2>(), LB = L3 + LD + L4, GP = 16 * JM;     // biases behind the matrices, then one gate table per wave
-    float* __restrict__ W3s = smem32;
-    float* __restrict__ Wds = W3s + L3;
-    float* __restrict__ W4s = Wds + LD;
-    float* __restrict__ Bs = smem32 + LB;                        // [C2] b3 (+ bd), [16 MT4] b4 (zero past N2)
+    float* __restrict__ W3s = smem32 + TL::W3;
+    float* __restrict__ Wds = smem32 + TL::WD;
+    float* __restrict__ W4s = smem32 + TL::W4;
+    float* __restrict__ Bs = smem32 + TL::B;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, n = lane & 15;
-    float* __restrict__ Gw = Bs + C2 + 16 * MT4 + wave * 4 * GP; // this wave's copy of the image's gates: [4][GP], zero in the padding chunks
-    int nv = Nimg;
-    if (n_img && *n_img < nv) nv = *n_img;
+    float* __restrict__ Gw = smem32 + TL::G + wave * 4 * GP;     // this wave's copy of the image's gates: [4][GP], zero in the padding chunks
+    const int nv = valid_count(Nimg, n_img);
     // work items = (image, part of its tiles): `splits` parts per image when the batch alone cannot fill the chip (the per-frame call's 32 crops)
     const int items = nv * splits, per = (items + (int)gridDim.x - 1) / (int)gridDim.x, it0 = blockIdx.x * per, it1 = min(it0 + per, items);
     if (it0 >= it1) return;
@@ -824,7 +856,7 @@ __global__ __launch_bounds__(T32_THREADS, 4) void k32_tail(const float* __restri
             }
             // (the weight fragments, biases and gates are re-read from LDS for every tile: an offset the compiler cannot see through keeps
             //  it from hoisting the loop-invariant reads into registers — 256 registers and 110-290 spilled values when it did)
-            int o3 = 0, od = L3, o4 = L3 + LD, ob = LB + 4 * kq, og = LB + C2 + 16 * MT4 + wave * 4 * GP + 4 * kq;
+            int o3 = TL::W3, od = TL::WD, o4 = TL::W4, ob = TL::B + 4 * kq, og = TL::G + wave * 4 * GP + 4 * kq;
             asm volatile("" : "+v"(o3), "+v"(od), "+v"(o4), "+v"(ob), "+v"(og));
             f4 bm[JM];
 #pragma unroll
@@ -886,38 +918,115 @@ __global__ __launch_bounds__(T32_THREADS, 4) void k32_tail(const float* __restri
 // (columns of a tile are 6 floats apart: 32 lanes hit 32 banks), A (16 x 148 weights) lives in 37 registers per lane.
 #define ST_ROWP 404
 #define ST_PR 4
+// LDS of the two stem kernels, in floats: In [24][ST_ROWP] input rows, Cs [9][64][16] convolution rows after bias + ReLU (k32_stemW: both
+// are rings) and, for k32_stemW, the [3][256] table of the U8 crops (the float form carries it too: two workgroups per CU either way)
+struct StemLds {
+    static constexpr int RING = 24, CS = RING * ST_ROWP, LUT = CS + (2 * ST_PR + 1) * 64 * 16;
+    static constexpr size_t bytes(bool walk) { return (size_t)(LUT + (walk ? 768 : 0)) * 4; }
+};
+// the zero borders of the input rows (3 vectors left, 2 right), written once
+static __device__ __forceinline__ void stem_borders(float* __restrict__ In, int tid)
+{
+    if (tid < StemLds::RING * 5) {
+        const int r = tid / 5, j = tid - 5 * r;
+        st4(In + r * ST_ROWP + 4 * (j < 3 ? j : 96 + j), zero4());
+    }
+}
+// U8 crops: 16 bytes of a row (vector c16: positions 16 c16 .. + 15, channel = position mod 3 = (c16 + j) mod 3) -> 16 floats of a ring row,
+// through the [3][256] table Lut
+static __device__ __forceinline__ void stem_put16(float* __restrict__ dst, const float* __restrict__ Lut, const uint4 v, int c16, bool ok)
+{
+    const int c0 = c16 % 3, o0 = c0 * 256, o1 = (c0 == 2 ? 0 : c0 + 1) * 256, o2 = (c0 == 0 ? 2 : c0 - 1) * 256;
+    const unsigned wv[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        f4 f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = 4 * q + e;
+            const int b = (int)((wv[q] >> (8 * e)) & 255u);
+            f[e] = ok ? Lut[(j % 3 == 0 ? o0 : j % 3 == 1 ? o1 : o2) + b] : 0.f;
+        }
+        st4(dst + 4 * q, f);
+    }
+}
+// ROWS input rows of a crop (floats, or bytes: U8), from image row iy0 on, for the rows ring0 .. of the ring In, by NTHR threads: request()
+// asks for every 16-byte vector of a thread (from a clamped, always valid address), store() puts them into LDS (zeros for a row outside the
+// image); whatever the caller runs between the two lies over the loads' latency.  (The rolled `conditional load -> store` loop was four
+// dependent HBM round trips at the start of every workgroup.)
+template <int NTHR, int ROWS, bool U8 = false> struct StemRows {
+    static constexpr int H = 256, RV = 128 * 3 * (U8 ? 1 : 4) / 16, TOT = ROWS * RV, NIT = (TOT + NTHR - 1) / NTHR;   // RV: vectors of an input row (96, U8: 24)
+    uint4 v[NIT];
+    __device__ __forceinline__ void request(const void* __restrict__ xi, int iy0, int tid)
+    {
+#pragma unroll
+        for (int u = 0; u < NIT; ++u) {
+            const int i = TOT % NTHR ? min(tid + u * NTHR, TOT - 1) : tid + u * NTHR, lr = i / RV, c = i - lr * RV;
+            v[u] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(xi) + (unsigned)(clamp_row(iy0 + lr, H) * (16 * RV) + 16 * c));
+        }
+    }
+    __device__ __forceinline__ void store(float* __restrict__ In, const float* __restrict__ Lut, int ring0, int iy0, int tid) const
+    {
+#pragma unroll
+        for (int u = 0; u < NIT; ++u) {
+            const int i = tid + u * NTHR, lr = i / RV, c = i - lr * RV, iy = iy0 + lr;
+            int r = ring0 + lr; r = r >= StemLds::RING ? r - StemLds::RING : r; r = r >= StemLds::RING ? r - StemLds::RING : r;
+            float* dst = In + r * ST_ROWP + 12 + (U8 ? 16 : 4) * c;
+            const bool ok = iy >= 0 && iy < H;
+            if (TOT % NTHR && i >= TOT) continue;
+            if (U8) stem_put16(dst, Lut, v[u], c, ok);
+            else st4(dst, ok ? __builtin_bit_cast(f4, v[u]) : zero4());
+        }
+    }
+};
+// A (16 x 148 weights) as 37 registers per lane, and this lane's chunk of the bias
+static __device__ __forceinline__ void stem_weights(const float* __restrict__ w, const float* __restrict__ bias, int kq, int n, float (&a)[37], f4& bb)
+{
+#pragma unroll
+    for (int s = 0; s < 37; ++s) a[s] = w[n * 148 + 4 * s + kq];
+    bb = ld4(bias + 4 * kq);
+}
+// max pool 3x3 / stride 2 / pad 1: chunk q of the pooled pixel (row prl of the band, column pxl) from the convolution rows in Cs, where row
+// cy lies in slot (cy + 1) mod 9 (RING) or in slot cy - cy0
+template <bool RING>
+static __device__ __forceinline__ f4 stem_pool(const float* __restrict__ Cs, int cy0, int prl, int pxl, int q)
+{
+    constexpr int H = 256, OW = 64, CSP = 16;
+    f4 m = f4{ -INFINITY, -INFINITY, -INFINITY, -INFINITY };
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+        const int cyl = 2 * prl + dy, cy = cy0 + cyl;
+        if (cy < 0 || cy >= H / 2) continue;
+        const int slot = RING ? (cy + 1) % 9 : cyl;
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            const int cx = 2 * pxl - 1 + dx;
+            if (cx < 0 || cx >= OW) continue;
+            m = max4(m, ld4(Cs + (slot * OW + cx) * CSP + 4 * q));
+        }
+    }
+    return m;
+}
+
 __global__ __launch_bounds__(C32_THREADS) void k32_stem(const float* __restrict__ x, const float* __restrict__ w /*[16][148]*/,
                                                       const float* __restrict__ bias, float* __restrict__ y, int Nimg, const int* __restrict__ n_img)
 {
-    constexpr int H = 256, Wd = 128, OW = 64, PH = 64, PW = 32, IN_ROWS = 24, CROWS = 2 * ST_PR + 1, CSP = 16;
+    constexpr int H = 256, Wd = 128, OW = 64, PH = 64, PW = 32, CROWS = 2 * ST_PR + 1, CSP = 16;
     extern __shared__ __attribute__((aligned(16))) float smem32[];
-    float* __restrict__ In = smem32;                         // [24][404]
-    float* __restrict__ Cs = In + IN_ROWS * ST_ROWP;         // [9][64][16] convolution rows after bias + ReLU
+    float* __restrict__ In = smem32;
+    float* __restrict__ Cs = smem32 + StemLds::CS;
     const int img = blockIdx.y, band = blockIdx.x;
     if (n_img && img >= *n_img) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, n = lane & 15;
     const int pr0 = band * ST_PR, cy0 = 2 * pr0 - 1, iy0 = 2 * cy0 - 3;
-    const float* xi = x + (size_t)img * H * Wd * 3;
-    {   // the band's input rows: every vector of a thread requested (from a clamped, always valid address) before the first LDS store — the
-        // rolled `conditional load -> store` loop was four dependent HBM round trips at the start of every workgroup
-        constexpr int TOT = IN_ROWS * (ST_ROWP / 4), NIT = (TOT + C32_THREADS - 1) / C32_THREADS;
-        f4 v[NIT];
-#pragma unroll
-        for (int u = 0; u < NIT; ++u) {
-            const int i = min(tid + u * C32_THREADS, TOT - 1), lr = i / (ST_ROWP / 4), c4 = i - lr * (ST_ROWP / 4), iy = iy0 + lr;
-            const int iyc = iy < 0 ? 0 : (iy >= H ? H - 1 : iy), cc = c4 < 3 ? 0 : (c4 >= 99 ? 95 : c4 - 3);
-            v[u] = ld4(xi + (size_t)iyc * (Wd * 3) + 4 * cc);
-        }
-#pragma unroll
-        for (int u = 0; u < NIT; ++u) {
-            const int i = tid + u * C32_THREADS, lr = i / (ST_ROWP / 4), c4 = i - lr * (ST_ROWP / 4), iy = iy0 + lr;
-            if (i < TOT) st4(In + lr * ST_ROWP + 4 * c4, (iy >= 0 && iy < H && c4 >= 3 && c4 < 99) ? v[u] : zero4());
-        }
-    }
+    stem_borders(In, tid);
+    StemRows<C32_THREADS, StemLds::RING> rows;               // the band's input rows
+    rows.request(x + (size_t)img * H * Wd * 3, iy0, tid);
+    rows.store(In, nullptr, 0, iy0, tid);
+    __builtin_amdgcn_sched_barrier(0);                       // (the weight loads stay behind the row stores: hoisted above them they cost a 65th register, 7 waves per SIMD for 8)
     float a[37];
-#pragma unroll
-    for (int s = 0; s < 37; ++s) a[s] = w[n * 148 + 4 * s + kq];
-    const f4 bb = ld4(bias + 4 * kq);
+    f4 bb;
+    stem_weights(w, bias, kq, n, a, bb);
     __syncthreads();
     for (int tile = wave; tile < CROWS * 4; tile += C32_THREADS / 64) {
         const int cyl = tile >> 2, cx0 = (tile & 3) * 16, cy = cy0 + cyl;
@@ -934,19 +1043,7 @@ __global__ __launch_bounds__(C32_THREADS) void k32_stem(const float* __restrict_
     __syncthreads();
     if (tid < ST_PR * PW * 4) {
         const int q = tid & 3, pxl = (tid >> 2) & 31, prl = tid >> 7;
-        f4 m = f4{ -INFINITY, -INFINITY, -INFINITY, -INFINITY };
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-            const int cyl = 2 * prl + dy, cy = cy0 + cyl;
-            if (cy < 0 || cy >= H / 2) continue;
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const int cx = 2 * pxl - 1 + dx;
-                if (cx < 0 || cx >= OW) continue;
-                m = max4(m, ld4(Cs + (cyl * OW + cx) * CSP + 4 * q));
-            }
-        }
-        st4(y + (((size_t)img * PH + pr0 + prl) * PW + pxl) * 16 + 4 * q, m);
+        st4(y + (((size_t)img * PH + pr0 + prl) * PW + pxl) * 16 + 4 * q, stem_pool<false>(Cs, cy0, prl, pxl, q));
     }
 }
 
@@ -968,77 +1065,27 @@ __global__ __launch_bounds__(STW_THREADS, 4) void k32_stemW(const void* __restri
                                                             const float* __restrict__ bias, float* __restrict__ y, int Nimg, const int* __restrict__ n_img, int nb,
                                                             const float* __restrict__ w1 /*[16][16] or null*/, const float* __restrict__ b1, float* __restrict__ y1)
 {
-    constexpr int H = 256, Wd = 128, OW = 64, PH = 64, PW = 32, RING = 24, CSP = 16, RV = Wd * 3 / 4;   // RV: data vectors of an input row (96)
-    constexpr int RB = Wd * 3 / 16;                          // U8: 16-byte vectors of an input row (24)
+    constexpr int H = 256, Wd = 128, OW = 64, PH = 64, PW = 32, RING = StemLds::RING, CSP = 16;
     extern __shared__ __attribute__((aligned(16))) float smem32[];
-    float* __restrict__ In = smem32;                         // [24][404] ring of input rows
-    float* __restrict__ Cs = In + RING * ST_ROWP;            // [9][64][16] ring of convolution rows after bias + ReLU
-    float* __restrict__ Lut = Cs + 9 * OW * CSP;             // U8: [3][256]
+    float* __restrict__ In = smem32;
+    float* __restrict__ Cs = smem32 + StemLds::CS;
+    float* __restrict__ Lut = smem32 + StemLds::LUT;
     const int img = blockIdx.y, b0 = blockIdx.x * nb;
     if (n_img && img >= *n_img) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), kq = lane >> 4, n = lane & 15;
-    const float* xi = reinterpret_cast<const float*>(xv) + (size_t)img * H * Wd * 3;
-    const uint8_t* xb = reinterpret_cast<const uint8_t*>(xv) + (size_t)img * H * Wd * 3;
-    auto inrow = [&](int iy) { return iy < 0 ? 0 : (iy >= H ? H - 1 : iy); };
-    if (tid < RING * 5) {                                    // the rows' zero borders (3 vectors left, 2 right), written once
-        const int r = tid / 5, j = tid - 5 * r;
-        st4(In + r * ST_ROWP + 4 * (j < 3 ? j : RV + j), zero4());
-    }
-    // U8: 16 bytes of a row (vector c16: positions 16 c16 .. + 15, channel = position mod 3 = (c16 + j) mod 3) -> 16 floats of the ring row
-    auto cvt16 = [&](f4 (&f)[4], const uint4 v, int c16, bool ok) __attribute__((always_inline)) {
-        const int c0 = c16 % 3, o0 = c0 * 256, o1 = (c0 == 2 ? 0 : c0 + 1) * 256, o2 = (c0 == 0 ? 2 : c0 - 1) * 256;
-        const unsigned wv[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int j = 4 * q + e;
-                const int b = (int)((wv[q] >> (8 * e)) & 255u);
-                f[q][e] = ok ? Lut[(j % 3 == 0 ? o0 : j % 3 == 1 ? o1 : o2) + b] : 0.f;
-            }
-    };
-    auto put16 = [&](float* dst, const uint4 v, int c16, bool ok) __attribute__((always_inline)) {
-        f4 f[4];
-        cvt16(f, v, c16, ok);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) st4(dst + 4 * q, f[q]);
-    };
+    const char* xi = reinterpret_cast<const char*>(xv) + (size_t)img * H * Wd * 3 * (U8 ? 1 : 4);
+    stem_borders(In, tid);
     if (U8) {
         const float mean[3] = { 0.485f, 0.456f, 0.406f }, sd[3] = { 0.229f, 0.224f, 0.225f };
         for (int i = tid; i < 768; i += STW_THREADS) { const int c = i >> 8; const float q = (float)(i & 255) / 255.0f; Lut[i] = (q - mean[c]) / sd[c]; }
         __syncthreads();
-        constexpr int TOT = 23 * RB, NIT = (TOT + STW_THREADS - 1) / STW_THREADS;
-        const int iy0 = 16 * b0 - 5;
-        uint4 v[NIT];
-#pragma unroll
-        for (int u = 0; u < NIT; ++u) {
-            const int i = min(tid + u * STW_THREADS, TOT - 1), lr = i / RB, c16 = i - lr * RB;
-            v[u] = *reinterpret_cast<const uint4*>(xb + (size_t)inrow(iy0 + lr) * (Wd * 3) + 16 * c16);
-        }
-#pragma unroll
-        for (int u = 0; u < NIT; ++u) {
-            const int i = tid + u * STW_THREADS, lr = i / RB, c16 = i - lr * RB, iy = iy0 + lr;
-            if (i < TOT) put16(In + lr * ST_ROWP + 12 + 16 * c16, v[u], c16, iy >= 0 && iy < H);
-        }
-    } else {   // the first band's 23 rows (ring rows 0 .. 22): every vector requested before the first LDS store
-        constexpr int TOT = 23 * RV, NIT = (TOT + STW_THREADS - 1) / STW_THREADS;
-        const int iy0 = 16 * b0 - 5;
-        f4 v[NIT];
-#pragma unroll
-        for (int u = 0; u < NIT; ++u) {
-            const int i = min(tid + u * STW_THREADS, TOT - 1), lr = i / RV, c4 = i - lr * RV;
-            v[u] = ld4(xi + (size_t)inrow(iy0 + lr) * (Wd * 3) + 4 * c4);
-        }
-#pragma unroll
-        for (int u = 0; u < NIT; ++u) {
-            const int i = tid + u * STW_THREADS, lr = i / RV, c4 = i - lr * RV, iy = iy0 + lr;
-            if (i < TOT) st4(In + lr * ST_ROWP + 12 + 4 * c4, (iy >= 0 && iy < H) ? v[u] : zero4());
-        }
     }
+    StemRows<STW_THREADS, 23, U8> rows;                      // the first band's 23 rows (ring rows 0 .. 22)
+    rows.request(xi, 16 * b0 - 5, tid);
+    rows.store(In, Lut, 0, 16 * b0 - 5, tid);
     float a[37];
-#pragma unroll
-    for (int s = 0; s < 37; ++s) a[s] = w[n * 148 + 4 * s + kq];
-    const f4 bb = ld4(bias + 4 * kq);
+    f4 bb;
+    stem_weights(w, bias, kq, n, a, bb);
 #pragma unroll
     for (int s = 0; s < 37; ++s) asm volatile("" ::"v"(a[s]));
     asm volatile("" ::"v"(bb[0]), "v"(bb[1]), "v"(bb[2]), "v"(bb[3]));   // the weights have arrived HERE: inside the loop their wait would also cover the rows requested ahead
@@ -1054,20 +1101,8 @@ __global__ __launch_bounds__(STW_THREADS, 4) void k32_stemW(const void* __restri
         const int band = b0 + bi, cy0 = 8 * band - 1, iy0 = 16 * band - 5;
         const bool more = bi + 1 < nb;
         __syncthreads();                                     // this band's rows are in the ring; the previous band's pool is done with Cs
-        f4 pf[U8 ? 1 : 3];
-        uint4 pb = { 0u, 0u, 0u, 0u };
-        if (more) {
-            if (U8) {                                        // the next band's 16 new rows: 384 vectors of 16 bytes
-                const int i = min(tid, 16 * RB - 1), j = i / RB, c16 = i - j * RB;
-                pb = *reinterpret_cast<const uint4*>(xb + (size_t)inrow(iy0 + 23 + j) * (Wd * 3) + 16 * c16);
-            } else {
-#pragma unroll
-                for (int u = 0; u < 3; ++u) {                // the next band's 16 new rows: 1 536 vectors
-                    const int i = tid + u * STW_THREADS, j = i / RV, c4 = i - j * RV;
-                    pf[u] = ld4(xi + (size_t)inrow(iy0 + 23 + j) * (Wd * 3) + 4 * c4);
-                }
-            }
-        }
+        StemRows<STW_THREADS, 16, U8> next;                  // the next band's 16 new rows: 1 536 vectors (U8: 384)
+        if (more) next.request(xi, iy0 + 23, tid);
         const int first = bi ? 1 : 0;                        // convolution row 0 of a later band is the previous band's row 8
         for (int t = 2 * wave; t < (9 - first) * 4; t += 2 * (STW_THREADS / 64)) {
             const int cyl = first + (t >> 2), cx0 = (t & 3) * 16, cy = cy0 + cyl;
@@ -1111,37 +1146,10 @@ __global__ __launch_bounds__(STW_THREADS, 4) void k32_stemW(const void* __restri
             st4(cs + 16 * CSP, relu4(acc1 + bb));
         }
         __syncthreads();                                     // Cs complete; local rows 0 .. 15 of the ring are dead
-        if (more) {
-            if (U8) {
-                if (tid < 16 * RB) {
-                    const int j = tid / RB, c16 = tid - j * RB, iy = iy0 + 23 + j;
-                    int r = base + 23 + j; r = r >= RING ? r - RING : r; r = r >= RING ? r - RING : r;
-                    put16(In + r * ST_ROWP + 12 + 16 * c16, pb, c16, iy >= 0 && iy < H);
-                }
-            } else {
-#pragma unroll
-                for (int u = 0; u < 3; ++u) {
-                    const int i = tid + u * STW_THREADS, j = i / RV, c4 = i - j * RV, iy = iy0 + 23 + j;
-                    int r = base + 23 + j; r = r >= RING ? r - RING : r; r = r >= RING ? r - RING : r;
-                    st4(In + r * ST_ROWP + 12 + 4 * c4, (iy >= 0 && iy < H) ? pf[u] : zero4());
-                }
-            }
-        }
+        if (more) next.store(In, Lut, base + 23, iy0 + 23, tid);
         {
             const int q = kq, pxl = 16 * (wave & 1) + n, prl = wave >> 1;       // a wave = 16 pixels of one pooled row x 4 channel chunks (lane (q, n))
-            f4 m = f4{ -INFINITY, -INFINITY, -INFINITY, -INFINITY };
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy) {
-                const int cy = cy0 + 2 * prl + dy;
-                if (cy < 0 || cy >= H / 2) continue;
-                const int slot = (cy + 1) % 9;
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    const int cx = 2 * pxl - 1 + dx;
-                    if (cx < 0 || cx >= OW) continue;
-                    m = max4(m, ld4(Cs + (slot * OW + cx) * CSP + 4 * q));
-                }
-            }
+            const f4 m = stem_pool<true>(Cs, cy0, prl, pxl, q);
             const size_t po = (((size_t)img * PH + 4 * band + prl) * PW + pxl) * 16 + 4 * q;
             st4(y + po, m);
             if (w1) {
@@ -1163,8 +1171,7 @@ __global__ __launch_bounds__(256) void k32_head(const float* __restrict__ x, con
     constexpr int C = 128;
     __shared__ __attribute__((aligned(16))) float mean[4][C];
     const int tid = threadIdx.x, i0 = blockIdx.x * 4;
-    int nv = Nimg;
-    if (n_img && *n_img < nv) nv = *n_img;
+    const int nv = valid_count(Nimg, n_img);
     if (i0 >= nv) return;
     const float inv = 1.0f / (float)HW;
 #pragma unroll 1
@@ -1312,7 +1319,7 @@ __global__ __launch_bounds__(64 * WAVES) void k32_conv(const float* __restrict__
             f4 v = acc[mt][t] + bv;
             if (act) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = v[j] / (1.0f + expf(-v[j]));          // SiLU
+                for (int j = 0; j < 4; ++j) v[j] = silu32(v[j]);
             }
             if (res) v = v + ld4(res + (size_t)p[t] * rs + oc);
             st4(out + (size_t)p[t] * os + oc, v);
@@ -1348,7 +1355,7 @@ __global__ __launch_bounds__(256) void k32_conv0(const float* __restrict__ x, co
             float s = bias[co];
 #pragma unroll
             for (int k = 0; k < 27; ++k) s = __builtin_fmaf(w[co * 27 + k], v[k], s);
-            o[j] = act ? s / (1.0f + expf(-s)) : s;
+            o[j] = act ? silu32(s) : s;
         }
         st4(out + (size_t)pp * os + 4 * c4, o);
     }
@@ -1443,7 +1450,7 @@ __global__ __launch_bounds__(128) void k32_v8_decode(V8Levels32 L, int B, int nc
     float* o = pred + (size_t)b * (4 + nc + L.n_ext) * A + a;
     if (L.n_ext && L.ext_mode == 2) {
         // oriented box (docs/OBB.md §2): theta = (sigmoid(v) - 1/4) pi, dist2rbox: the centre's offset from the anchor turned by theta
-        const float th = (1.0f / (1.0f + expf(-L.ext[l][((size_t)b * hw + p) * L.ext_ld])) - 0.25f) * 3.14159274101257324f;
+        const float th = (sigmoid32(L.ext[l][((size_t)b * hw + p) * L.ext_ld]) - 0.25f) * 3.14159274101257324f;
         const float cs = cosf(th), sn = sinf(th);
         const float xf = (d[2] - d[0]) * 0.5f, yf = (d[3] - d[1]) * 0.5f;
         o[0] = (ax + (xf * cs - yf * sn)) * st; o[(size_t)A] = (ay + (xf * sn + yf * cs)) * st;
@@ -1457,17 +1464,35 @@ __global__ __launch_bounds__(128) void k32_v8_decode(V8Levels32 L, int B, int nc
         float* oe = o + (size_t)(4 + nc) * A;
         for (int k = 0, j = 0; k < L.n_ext; ++k, j = j == 2 ? 0 : j + 1) {
             const float v = e[k];
-            oe[(size_t)k * A] = L.ext_mode == 0 ? v : j == 0 ? (v * 2.0f + (float)px) * st : j == 1 ? (v * 2.0f + (float)py) * st : 1.0f / (1.0f + expf(-v));
+            oe[(size_t)k * A] = L.ext_mode == 0 ? v : j == 0 ? (v * 2.0f + (float)px) * st : j == 1 ? (v * 2.0f + (float)py) * st : sigmoid32(v);
         }
     }
     }
     const float* cl = L.cls[l] + ((size_t)b * hw + p) * L.cls_ld;
-    for (int k = 0; k < nc; ++k) o[(size_t)(4 + k) * A] = 1.0f / (1.0f + expf(-cl[k]));
+    for (int k = 0; k < nc; ++k) o[(size_t)(4 + k) * A] = sigmoid32(cl[k]);
 }
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------
-// (the launch check OP_CHECK and lds_attr_once: ss_oplaunch.h)
-static bool lds32_attr(const void* fn, unsigned long long& done) { return lds_attr_once(fn, done, 160 * 1024 - 256); }
+// (op_launched and lds_attr_once: ss_oplaunch.h)
+#define LDS32_LIMIT (160 * 1024 - 256)
+// the dynamic LDS a launch of kernel K asks for: SS_ERR_CAPACITY past the limit; past the 64 KB a kernel may ask for as it is, the
+// kernel's limit is raised (once per device)
+template <auto K>
+static int lds32_ready(size_t lds)
+{
+    static unsigned long long attr = 0;
+    if (lds > LDS32_LIMIT) return SS_ERR_CAPACITY;
+    return (lds <= 64 * 1024 || lds_attr_once((const void*)K, attr, LDS32_LIMIT)) ? SS_OK : SS_ERR_HIP;
+}
+// every launch of this file: raise the attribute once, launch, check
+template <auto K, typename... A>
+static int launch32(dim3 grid, int threads, size_t lds, hipStream_t st, A... args)
+{
+    const int rc = lds32_ready<K>(lds);
+    if (rc != SS_OK) return rc;
+    hipLaunchKernelGGL(K, grid, dim3(threads), lds, st, args...);
+    return op_launched();
+}
 static int g_chains_pre = -1;         // k32_chains3: x1 tiles of a chain's first 1x1 requested a phase ahead: -1 = where it was measured faster (16 channels:
                                       // 618 -> 572 us per launch; 24 channels: 218 -> 330 us, the 32 extra registers spill), 0 / 1 = A/B
 static int g_chains_form = 2;        // 2: k32_chainsR (register row stream; 64 x 32 x 16 and 32 x 16 x 24 maps), 1: k32_chains3 (the 16 x 8 maps have no such form: k32_chains), 0: k32_chains
@@ -1491,9 +1516,7 @@ static int launch_pw32(hipStream_t st, const float* x, const float* w, const flo
     int tpw = 1;
     while (tpw < 8 && tiles / (4 * tpw) > 8192) tpw *= 2;      // a workgroup re-stages the weights: amortise over more tiles on large maps
     const long long grid = (tiles + 4 * tpw - 1) / (4 * tpw);
-    hipLaunchKernelGGL((k32_pw<K, N>), dim3((unsigned)grid), dim3(256), 0, st, x, w, b, res, out, M, relu, tpw, nv, img_px);
-    OP_CHECK();
-    return SS_OK;
+    return launch32<k32_pw<K, N>>(dim3((unsigned)grid), 256, 0, st, x, w, b, res, out, M, relu, tpw, nv, img_px);
 }
 
 extern "C" int ss_op32_pointwise(void* stream, const void* d_x, const void* d_w, const void* d_bias, const void* d_res, void* d_out,
@@ -1514,11 +1537,10 @@ extern "C" int ss_op32_pointwise(void* stream, const void* d_x, const void* d_w,
 // the smaller maps one band = the whole image (no halo)
 static int chains_rows(int H, int W, int C, int* halo)
 {
-    const size_t whole = 2ull * H * W * (C + 4) * 4 + (size_t)C32_THREADS * 16;
-    if (whole <= 150 * 1024) { *halo = 0; return H; }
+    if (ChainsLds(H, W, C).bytes() <= 150 * 1024) { *halo = 0; return H; }
     *halo = 4;
     for (int R = H / 2; R >= 8; R /= 2)
-        if (H % R == 0 && 2ull * (R + 8) * W * (C + 4) * 4 + (size_t)C32_THREADS * 16 <= 150 * 1024) return R;
+        if (H % R == 0 && ChainsLds(R + 2 * 4, W, C).bytes() <= 150 * 1024) return R;
     return -1;
 }
 
@@ -1538,37 +1560,26 @@ extern "C" int ss_op32_chains(void* stream, const void* d_x1, const void* d_w1, 
     hipStream_t st = (hipStream_t)stream;
     const float *x1 = (const float*)d_x1, *w1 = (const float*)d_w1, *w9 = (const float*)d_w9, *b = (const float*)d_bias;
     float *y0 = (float*)d_ys[0], *y1 = (float*)d_ys[1], *y2 = (float*)d_ys[2], *y3 = (float*)d_ys[3];
-    if (chains_rowstream(N, H, W, C)) {                       // two images (four waves) per workgroup
-#define CHR(CC, WW, AL) if (C == CC && W == WW) { \
-        const size_t ldsr = (size_t)(ChR<CC>::TAB + (AL ? 10 * ChR<CC>::NPR * ChR<CC>::KP : 0)) * 4; \
-        static unsigned long long attr = 0; \
-        if (ldsr > 64 * 1024 && !lds32_attr((const void*)k32_chainsR<CC, WW, AL>, attr)) return SS_ERR_HIP; \
-        const int ipw = WW == 8 ? 4 : 2;                      /* images per workgroup */ \
-        hipLaunchKernelGGL((k32_chainsR<CC, WW, AL>), dim3((N + ipw - 1) / ipw), dim3(R32_THREADS), ldsr, st, x1, w1, w9, b, y0, y1, y2, y3, d_psum, N, H, d_nvalid, g_chains_probe); \
-        OP_CHECK(); return SS_OK; }
+#define CH_ARGS x1, w1, w9, b, y0, y1, y2, y3, d_psum, N, H
+    if (chains_rowstream(N, H, W, C)) {                       // two images (four waves) per workgroup, four where a wave takes two
+#define CHR(CC, WW, AL) if (C == CC && W == WW) \
+        return launch32<k32_chainsR<CC, WW, AL>>(dim3((N + (WW == 8 ? 4 : 2) - 1) / (WW == 8 ? 4 : 2)), R32_THREADS, ChR<CC>::bytes(AL), st, CH_ARGS, d_nvalid, g_chains_probe);
         CHR(16, 32, false) CHR(24, 16, true) CHR(32, 8, true)
 #undef CHR
     }
     int halo;
     const int R = chains_rows(H, W, C, &halo);
     if (R < 1) return SS_ERR_CAPACITY;
-    const size_t lds = 2ull * (R + 2 * halo) * W * (C + 4) * 4 + (size_t)(C32_THREADS / (C / 4)) * C * 4;
+    const int RB = R + 2 * halo;
     const dim3 grid(H / R, N);
-#define CH32(CC, WW) if (C == CC && W == WW) { \
-        static unsigned long long attr = 0; \
-        if (!lds32_attr((const void*)k32_chains<CC, WW>, attr)) return SS_ERR_HIP; \
-        hipLaunchKernelGGL((k32_chains<CC, WW>), grid, dim3(C32_THREADS), lds, st, x1, w1, w9, b, y0, y1, y2, y3, d_psum, N, H, R, halo, d_nvalid); \
-        OP_CHECK(); return SS_OK; }
-#define CH32C(CC, WW, PRE_) if (C == CC && W == WW && g_chains_form >= 1 && (g_chains_pre < 0 ? CC == 16 : g_chains_pre != 0) == PRE_ && R + 2 * halo == (CC == 16 ? 24 : 32)) { \
-        static unsigned long long attr = 0; \
-        if (!lds32_attr((const void*)k32_chains3<CC, WW, PRE_>, attr)) return SS_ERR_HIP; \
-        const size_t lds3 = ((size_t)(R + 2 * halo + 2) * (WW + 2) + (size_t)(R + 2 * halo) * WW) * Ch3<CC>::PITCH * 4 + (size_t)(C32_THREADS / 64) * 16 * 4; \
-        hipLaunchKernelGGL((k32_chains3<CC, WW, PRE_>), grid, dim3(C32_THREADS), lds3, st, x1, w1, w9, b, y0, y1, y2, y3, d_psum, N, H, R, halo, d_nvalid); \
-        OP_CHECK(); return SS_OK; }
+#define CH32C(CC, WW, PRE_) if (C == CC && W == WW && g_chains_form >= 1 && (g_chains_pre < 0 ? CC == 16 : g_chains_pre != 0) == PRE_ && RB == Ch3<CC, WW>::ROWS) \
+        return launch32<k32_chains3<CC, WW, PRE_>>(grid, C32_THREADS, Ch3<CC, WW>(RB).bytes(), st, CH_ARGS, R, halo, d_nvalid);
     CH32C(16, 32, true) CH32C(16, 32, false) CH32C(24, 16, true) CH32C(24, 16, false)
 #undef CH32C
+#define CH32(CC, WW) if (C == CC && W == WW) return launch32<k32_chains<CC, WW>>(grid, C32_THREADS, ChainsLds(RB, W, C).bytes(), st, CH_ARGS, R, halo, d_nvalid);
     CH32(16, 32) CH32(24, 16) CH32(32, 8)
 #undef CH32
+#undef CH_ARGS
     return SS_ERR_INVALID;
 }
 
@@ -1593,12 +1604,12 @@ template <int MID, int C2, int C1, int N2, bool POOL>
 static int launch_tail32(hipStream_t st, const void* const* ys, const float* gates, const float* w3, const float* b3, const float* xin,
                          const float* wd, const float* bd, float* out, const float* w4, const float* b4, float* out2, int N, int H, int W, const int* nv)
 {
-    constexpr size_t lds = (size_t)(w_lds_floats<MID, C2>() + (C1 ? w_lds_floats<(C1 ? C1 : 16), C2>() : 0) + w_lds_floats<C2, N2>() + C2 + (N2 + 15) / 16 * 16 +
-                                    (T32_THREADS / 64) * 4 * 16 * ((MID / 4 + 3) / 4)) * 4;
+    constexpr size_t lds = (size_t)TailLds<MID, C2, C1, N2>::TOTAL * 4;
     static int wgs_dev[64] = { 0 };                            // workgroups of the persistent grid per device: what fits on the chip at once (<= 4 per CU)
-    static unsigned long long attr = 0;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63 || !lds32_attr((const void*)k32_tail<MID, C2, C1, N2, POOL>, attr)) return SS_ERR_HIP;
+    const int rc = lds32_ready<k32_tail<MID, C2, C1, N2, POOL>>(lds);
+    if (rc != SS_OK) return rc;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return SS_ERR_HIP;
     if (!wgs_dev[dev]) {
         int cus = 0, per_cu = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -1611,10 +1622,8 @@ static int launch_tail32(hipStream_t st, const void* const* ys, const float* gat
     int splits = 1;
     while (N * splits * 2 <= wgs && splits * 2 <= tiles_wv) splits *= 2;
     const int grid = g_tail_wgs > 0 ? g_tail_wgs : (N * splits < wgs ? N * splits : wgs);
-    hipLaunchKernelGGL((k32_tail<MID, C2, C1, N2, POOL>), dim3(grid), dim3(T32_THREADS), lds, st, (const float*)ys[0], (const float*)ys[1], (const float*)ys[2],
-                       (const float*)ys[3], gates, w3, b3, xin, wd, bd, out, w4, b4, out2, N, H, W, nv, splits);
-    OP_CHECK();
-    return SS_OK;
+    return launch32<k32_tail<MID, C2, C1, N2, POOL>>(dim3(grid), T32_THREADS, lds, st, (const float*)ys[0], (const float*)ys[1], (const float*)ys[2],
+                                                      (const float*)ys[3], gates, w3, b3, xin, wd, bd, out, w4, b4, out2, N, H, W, nv, splits);
 }
 
 extern "C" int ss_op32_tail(void* stream, const void* const* d_ys, const float* d_psum, int bands, const void* d_gw1, const void* d_gb1,
@@ -1627,11 +1636,12 @@ extern "C" int ss_op32_tail(void* stream, const void* const* d_ys, const float* 
         return SS_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const float scale = 1.0f / (float)(H * W);
-#define GT32(M_) if (MID == M_) hipLaunchKernelGGL((k32_gates<M_>), dim3(N), dim3(128), 0, st, d_psum, bands, scale, (const float*)d_gw1, (const float*)d_gb1, \
+    int rc = SS_ERR_INVALID;
+#define GT32(M_) if (MID == M_) rc = launch32<k32_gates<M_>>(dim3(N), 128, 0, st, d_psum, bands, scale, (const float*)d_gw1, (const float*)d_gb1, \
         (const float*)d_gw2, (const float*)d_gb2, hidden, d_gates, N, d_nvalid)
-    GT32(16); else GT32(24); else GT32(32); else return SS_ERR_INVALID;
+    GT32(16); GT32(24); GT32(32);
 #undef GT32
-    OP_CHECK();
+    if (rc != SS_OK) return rc;
 #define TL32(M_, C2_, C1_, N2_, P_) if (MID == M_ && C2 == C2_ && C1 == C1_ && N2 == N2_ && (pool != 0) == P_) \
         return launch_tail32<M_, C2_, C1_, N2_, P_>(st, d_ys, d_gates, (const float*)d_w3, (const float*)d_b3, (const float*)d_xin, (const float*)d_wd, \
             (const float*)d_bd, (float*)d_out, (const float*)d_w4, (const float*)d_b4, (float*)d_out2, N, H, W, d_nvalid)
@@ -1643,70 +1653,50 @@ extern "C" int ss_op32_tail(void* stream, const void* const* d_ys, const float* 
 
 static int stem_bands(int N) { return g_stem_walk > 0 ? g_stem_walk : (N >= 1024 ? 16 : N >= 512 ? 8 : N >= 128 ? 4 : 2); }   // bands a workgroup walks down (measured at 1 024 / 860 / 430 / 28 crops: tools/stem32_time.py)
 
-// The stem on BYTE crops [N][256][128][3] (ss_crop_norm* with SS_DST_U8): the normalisation happens while the rows are staged.
-// ... and with the first block's conv1 (1x1, 16 -> 16, bias, ReLU) applied to the pooled pixels in the same launch: d_y1 = relu(W1 d_y + b1), bit-equal
-// to ss_op32_pointwise on d_y.  x_u8: byte crops (ss_op32_stem_u8) or float crops.
+// The walking stem (k32_stemW) on float crops or on BYTE crops [N][256][128][3] (U8; ss_crop_norm* with SS_DST_U8: the normalisation
+// happens while the rows are staged), alone (d_w1 null) or with the first block's conv1 (1x1, 16 -> 16, bias, ReLU) applied to the pooled
+// pixels in the same launch: d_y1 = relu(W1 d_y + b1), bit-equal to ss_op32_pointwise on d_y.
+template <bool U8>
+static int launch_stemW(void* stream, const void* d_x, const void* d_w, const void* d_bias, void* d_y, const void* d_w1, const void* d_b1, void* d_y1,
+                        int N, const int* d_nvalid)
+{
+    const int nb = stem_bands(N);
+    return launch32<k32_stemW<U8>>(dim3(16 / nb, N), STW_THREADS, StemLds::bytes(true), (hipStream_t)stream, d_x, (const float*)d_w, (const float*)d_bias,
+                                   (float*)d_y, N, d_nvalid, nb, (const float*)d_w1, (const float*)d_b1, (float*)d_y1);
+}
+static bool stem_args_ok(const void* d_x, const void* d_w, const void* d_bias, const void* d_y, int N, int H, int W)
+{
+    return d_x && d_w && d_bias && d_y && N >= 1 && N <= 65535 && H == 256 && W == 128;
+}
+
+// x_u8: byte crops (as ss_op32_stem_u8) or float crops
 extern "C" int ss_op32_stem_conv1(void* stream, const void* d_x, int x_u8, const void* d_w, const void* d_bias, void* d_y, const void* d_w1, const void* d_b1,
                                   void* d_y1, int N, int H, int W, const int* d_nvalid)
 {
-    if (!d_x || !d_w || !d_bias || !d_y || !d_w1 || !d_b1 || !d_y1 || N < 1 || N > 65535 || H != 256 || W != 128) return SS_ERR_INVALID;
-    constexpr size_t lds = (size_t)(24 * ST_ROWP + (2 * ST_PR + 1) * 64 * 16 + 768) * 4;
-    static unsigned long long attr8 = 0, attr32 = 0;
-    const int nb = stem_bands(N);
-    if (x_u8) {
-        if (!lds32_attr((const void*)k32_stemW<true>, attr8)) return SS_ERR_HIP;
-        hipLaunchKernelGGL(k32_stemW<true>, dim3(16 / nb, N), dim3(STW_THREADS), lds, (hipStream_t)stream, d_x, (const float*)d_w, (const float*)d_bias, (float*)d_y, N,
-                           d_nvalid, nb, (const float*)d_w1, (const float*)d_b1, (float*)d_y1);
-    } else {
-        if (!lds32_attr((const void*)k32_stemW<false>, attr32)) return SS_ERR_HIP;
-        hipLaunchKernelGGL(k32_stemW<false>, dim3(16 / nb, N), dim3(STW_THREADS), lds, (hipStream_t)stream, d_x, (const float*)d_w, (const float*)d_bias, (float*)d_y, N,
-                           d_nvalid, nb, (const float*)d_w1, (const float*)d_b1, (float*)d_y1);
-    }
-    OP_CHECK();
-    return SS_OK;
+    if (!stem_args_ok(d_x, d_w, d_bias, d_y, N, H, W) || !d_w1 || !d_b1 || !d_y1) return SS_ERR_INVALID;
+    return x_u8 ? launch_stemW<true>(stream, d_x, d_w, d_bias, d_y, d_w1, d_b1, d_y1, N, d_nvalid)
+                : launch_stemW<false>(stream, d_x, d_w, d_bias, d_y, d_w1, d_b1, d_y1, N, d_nvalid);
 }
 
 extern "C" int ss_op32_stem_u8(void* stream, const void* d_x, const void* d_w, const void* d_bias, void* d_y, int N, int H, int W, const int* d_nvalid)
 {
-    if (!d_x || !d_w || !d_bias || !d_y || N < 1 || N > 65535 || H != 256 || W != 128) return SS_ERR_INVALID;
-    constexpr size_t lds = (size_t)(24 * ST_ROWP + (2 * ST_PR + 1) * 64 * 16 + 768) * 4;
-    static unsigned long long attr = 0;
-    const int nb = stem_bands(N);
-    if (!lds32_attr((const void*)k32_stemW<true>, attr)) return SS_ERR_HIP;
-    hipLaunchKernelGGL(k32_stemW<true>, dim3(16 / nb, N), dim3(STW_THREADS), lds, (hipStream_t)stream, d_x, (const float*)d_w,
-                       (const float*)d_bias, (float*)d_y, N, d_nvalid, nb, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
-    OP_CHECK();
-    return SS_OK;
+    if (!stem_args_ok(d_x, d_w, d_bias, d_y, N, H, W)) return SS_ERR_INVALID;
+    return launch_stemW<true>(stream, d_x, d_w, d_bias, d_y, nullptr, nullptr, nullptr, N, d_nvalid);
 }
 
 extern "C" int ss_op32_stem(void* stream, const void* d_x, const void* d_w, const void* d_bias, void* d_y, int N, int H, int W, const int* d_nvalid)
 {
-    if (!d_x || !d_w || !d_bias || !d_y || N < 1 || N > 65535 || H != 256 || W != 128) return SS_ERR_INVALID;
-    constexpr size_t lds = (size_t)(24 * ST_ROWP + (2 * ST_PR + 1) * 64 * 16) * 4;
-    static unsigned long long attr = 0, attr_w = 0;
-    const int nb = g_stem_walk < 0 ? 0 : stem_bands(N);      // -1: one band per workgroup, k32_stem
-    if (nb) {
-        if (!lds32_attr((const void*)k32_stemW<false>, attr_w)) return SS_ERR_HIP;
-        hipLaunchKernelGGL(k32_stemW<false>, dim3(16 / nb, N), dim3(STW_THREADS), lds, (hipStream_t)stream, d_x, (const float*)d_w,
-                           (const float*)d_bias, (float*)d_y, N, d_nvalid, nb, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
-        OP_CHECK();
-        return SS_OK;
-    }
-    if (!lds32_attr((const void*)k32_stem, attr)) return SS_ERR_HIP;
-    hipLaunchKernelGGL(k32_stem, dim3(64 / ST_PR, N), dim3(C32_THREADS), lds, (hipStream_t)stream, (const float*)d_x, (const float*)d_w,
-                       (const float*)d_bias, (float*)d_y, N, d_nvalid);
-    OP_CHECK();
-    return SS_OK;
+    if (!stem_args_ok(d_x, d_w, d_bias, d_y, N, H, W)) return SS_ERR_INVALID;
+    if (g_stem_walk >= 0) return launch_stemW<false>(stream, d_x, d_w, d_bias, d_y, nullptr, nullptr, nullptr, N, d_nvalid);
+    return launch32<k32_stem>(dim3(64 / ST_PR, N), C32_THREADS, StemLds::bytes(false), (hipStream_t)stream, (const float*)d_x, (const float*)d_w,
+                              (const float*)d_bias, (float*)d_y, N, d_nvalid);       // stem_walk -1: one band per workgroup
 }
 
 extern "C" int ss_op32_head(void* stream, const void* d_x, const void* d_w, const void* d_bias, void* d_out, int N, int HW, int C, int F,
                             const int* d_nvalid)
 {
     if (!d_x || !d_w || !d_bias || !d_out || N < 1 || HW < 1 || C != 128 || F < 1) return SS_ERR_INVALID;
-    hipLaunchKernelGGL(k32_head, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)d_x, (const float*)d_w, (const float*)d_bias,
-                       (float*)d_out, N, HW, F, d_nvalid);
-    OP_CHECK();
-    return SS_OK;
+    return launch32<k32_head>(dim3((N + 3) / 4), 256, 0, (hipStream_t)stream, (const float*)d_x, (const float*)d_w, (const float*)d_bias, (float*)d_out, N, HW, F, d_nvalid);
 }
 
 // The launch of ss_op32_conv for a problem, computed on the host alone (no HIP call): argument checks, then the choice of mt (16-channel
@@ -1760,10 +1750,9 @@ extern "C" int ss_op32_conv(void* stream, const void* d_x, int xs, const void* d
     const int OH = (H + 2 * (ks / 2) - ks) / stride + 1, OW = (W + 2 * (ks / 2) - ks) / stride + 1;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(gx, gy);
-#define CV32(KS_, ST_, MT_, WV_) if (ks == KS_ && stride == ST_ && mt == MT_ && wv == WV_) { \
-        hipLaunchKernelGGL((k32_conv<KS_, ST_, MT_, 1, WV_>), grid, dim3(64 * WV_), 0, st, (const float*)d_x, xs, (const float*)d_w, (const float*)d_bias, \
-                           (const float*)d_res, rs, (float*)d_out, os, N, H, W, OH, OW, Cin, Cout, act); \
-        OP_CHECK(); return SS_OK; }
+#define CV32(KS_, ST_, MT_, WV_) if (ks == KS_ && stride == ST_ && mt == MT_ && wv == WV_) \
+        return launch32<k32_conv<KS_, ST_, MT_, 1, WV_>>(grid, 64 * WV_, 0, st, (const float*)d_x, xs, (const float*)d_w, (const float*)d_bias, \
+                                                         (const float*)d_res, rs, (float*)d_out, os, N, H, W, OH, OW, Cin, Cout, act);
 #define CV32M(KS_, ST_) CV32(KS_, ST_, 1, 4) CV32(KS_, ST_, 1, 8) CV32(KS_, ST_, 2, 4) CV32(KS_, ST_, 2, 8) CV32(KS_, ST_, 4, 4) CV32(KS_, ST_, 4, 8) \
         CV32(KS_, ST_, 5, 4) CV32(KS_, ST_, 5, 8)
     CV32M(1, 1) CV32M(3, 1) CV32M(3, 2)
@@ -1779,10 +1768,8 @@ extern "C" int ss_op32_conv0(void* stream, const void* d_x, const void* d_w, con
     if (!d_x || !d_w || !d_bias || !d_out || N < 1 || H < 2 || W < 2 || os < 16 || os % 4 || ((uintptr_t)d_out & 15)) return SS_ERR_INVALID;
     const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
     const long long M = (long long)N * OH * OW;
-    hipLaunchKernelGGL(k32_conv0, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)d_x, (const float*)d_w,
-                       (const float*)d_bias, (float*)d_out, os, N, H, W, OH, OW, act);
-    OP_CHECK();
-    return SS_OK;
+    return launch32<k32_conv0>(dim3((unsigned)((M + 255) / 256)), 256, 0, (hipStream_t)stream, (const float*)d_x, (const float*)d_w, (const float*)d_bias,
+                               (float*)d_out, os, N, H, W, OH, OW, act);
 }
 
 /* cat(upsample2x_nearest(lo), hi) (lo_first != 0) or cat(hi, upsample2x_nearest(lo)) along channels, fp32 NHWC: d_lo [N][H/2][W/2][.]
@@ -1793,10 +1780,8 @@ extern "C" int ss_op32_upcat(void* stream, const void* d_lo, int ls, int Cl, con
         (((uintptr_t)d_lo | (uintptr_t)d_hi | (uintptr_t)d_out) & 15))
         return SS_ERR_INVALID;
     const long long tot = (long long)N * H * W * ((Cl + Ch) / 4);
-    hipLaunchKernelGGL(k32_upcat, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)d_lo, ls, Cl, (const float*)d_hi, hs, Ch,
-                       (float*)d_out, N, H, W, lo_first);
-    OP_CHECK();
-    return SS_OK;
+    return launch32<k32_upcat>(dim3((unsigned)((tot + 255) / 256)), 256, 0, (hipStream_t)stream, (const float*)d_lo, ls, Cl, (const float*)d_hi, hs, Ch,
+                               (float*)d_out, N, H, W, lo_first);
 }
 
 /* YOLOv8 head decode in fp32: the three levels' branch outputs (dense NHWC float, bias included: box [B][H][W][64], cls [B][H][W][cls_ld]
@@ -1818,9 +1803,7 @@ extern "C" int ss_op32_v8_decode(void* stream, const void* const* d_box, const v
         A += H[l] * W[l];
     }
     L.n_ext = n_ext; L.ext_ld = ext_ld; L.ext_mode = ext_mode; L.cls_ld = cls_ld;
-    hipLaunchKernelGGL(k32_v8_decode, dim3((A + 127) / 128, B), dim3(128), 0, (hipStream_t)stream, L, B, nc, A, d_pred);
-    OP_CHECK();
-    return SS_OK;
+    return launch32<k32_v8_decode>(dim3((A + 127) / 128, B), 128, 0, (hipStream_t)stream, L, B, nc, A, d_pred);
 }
 
 /* SPPF's pools + concat in fp32: d_x NHWC [N][H][W][.] pixel stride xs -> d_out dense [N][H][W][4 C] = (x, pool5 x, pool5 pool5 x, ...). */
@@ -1828,7 +1811,5 @@ extern "C" int ss_op32_sppf_pools(void* stream, const void* d_x, int xs, void* d
 {
     if (!d_x || !d_out || N < 1 || H < 1 || W < 1 || C < 4 || (C | xs) % 4 || xs < C || (((uintptr_t)d_x | (uintptr_t)d_out) & 15)) return SS_ERR_INVALID;
     const long long tot = (long long)N * H * W * (C / 4);
-    hipLaunchKernelGGL(k32_sppf, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)d_x, xs, (float*)d_out, N, H, W, C);
-    OP_CHECK();
-    return SS_OK;
+    return launch32<k32_sppf>(dim3((unsigned)((tot + 255) / 256)), 256, 0, (hipStream_t)stream, (const float*)d_x, xs, (float*)d_out, N, H, W, C);
 }
