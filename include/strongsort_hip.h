@@ -363,6 +363,42 @@ int ss_ocsort_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracks, int* n
                          int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
                          double* velocity);
 
+/* ---- Hybrid-SORT (docs/HYBRIDSORT.md): OC-SORT's machinery with the confidence as a Kalman state and a cost term (TCM), the
+ * height-modulated IoU and the direction term over the four box corners and delta_t time offsets ------------------------------
+ * No weights, no frames.  The state is hung off an existing context like the OC-SORT state (they may coexist);
+ * ss_hybridsort_create on a context that already has one replaces it.  SS_ERR_INVALID unless 1 <= max_tracks <= SS_MAX_TRACKS,
+ * 1 <= max_dets <= SS_MAX_DETS, 1 <= delta_t <= 8, max_age >= 1, min_hits >= 0, 0 < iou_threshold <= 1, inertia >= 0, both TCM
+ * weights >= 0, low_thresh <= det_thresh, and use_byte and hmiou are 0 or 1. */
+typedef struct ss_hybridsort_config {
+    double det_thresh;           /* 0.25  first association and births: score > this                          */
+    double low_thresh;           /* 0.1   BYTE stage rows: low < score < det_thresh                            */
+    double iou_threshold;        /* 0.3   a pair is kept when its (height-modulated) IoU >= this               */
+    double inertia;              /* 0.05  weight of each corner's direction-consistency term                   */
+    double tcm_first_weight;     /* 1.0   weight of |score - Kalman confidence| in the first association       */
+    double tcm_byte_weight;      /* 1.0   weight of |score - linear confidence| in the BYTE stage              */
+    int    max_age;              /* 30    removed when time_since_update > max_age                             */
+    int    min_hits;             /* 3     shown from this hit streak on (and during the first min_hits frames) */
+    int    delta_t;              /* 3     time offsets of the direction term, 1..8                             */
+    int    use_byte;             /* 1     1: the second association on the low-score rows                      */
+    int    hmiou;                /* 1     1: height-modulated IoU, 0: IoU                                      */
+    int    max_tracks;           /* <= SS_MAX_TRACKS per stream                                                */
+    int    max_dets;             /* <= SS_MAX_DETS per frame                                                   */
+} ss_hybridsort_config;
+int ss_hybridsort_create(ss_ctx* ctx, const ss_hybridsort_config* cfg);
+int ss_hybridsort_destroy(ss_ctx* ctx);
+/* A group of n_frames (1..32) frames of every stream in ONE launch: the layouts, checks and capacity errors of
+ * ss_ocsort_update_group (set until ss_hybridsort_reset).  Asynchronous on the context's stream, capturable. */
+int ss_hybridsort_update_group(ss_ctx* ctx, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
+int ss_hybridsort_update(ss_ctx* ctx, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout);
+int ss_hybridsort_reset(ss_ctx* ctx, int stream);          /* stream < 0: all streams; ids restart at 1, frame_count at 0 */
+/* Synchronous: the table of one stream in list order (oldest track first); any array may be NULL.  x [n][9] (x, y, s, c, r, vx,
+ * vy, vs, vc), P [n][81] (entries outside the components' blocks are +0.0), frozen as ss_ocsort_get_tracks, last_obs [n][4] xyxy
+ * (-1 four times while the track has none), velocity [n][8] the corners' direction sums (lt, rt, lb, rb; x, y; zeros while none),
+ * conf [n] the score of the last match (the birth row's before any), conf_prev [n] of the match before it (-1 while none). */
+int ss_hybridsort_get_tracks(ss_ctx* ctx, int stream, int cap, int* n_tracks, int* next_id, int* frame_count, int* track_id, int* age,
+                             int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
+                             double* velocity, float* conf, float* conf_prev);
+
 /* ---- Deep OC-SORT (docs/DEEPOCSORT.md): OC-SORT with camera-motion compensation, dynamic appearance and adaptive weighting -------
  * OC-SORT's frame procedure without the BYTE stage; the first association adds w_association_emb x (adaptive weight) x the
  * similarity of the row's unit feature and the track's feature, and every track keeps a feature whose EMA weight follows the

@@ -425,6 +425,8 @@ def process_video(args: dict, model=None) -> dict:
                      camera_motion=args.get("camera_motion", False), with_reid=args.get("with_reid", False),
                      reid_model=args.get("reid_model", "osnet"), with_pose=args.get("with_pose", False),
                      gmc_method=args.get("gmc_method", "ecc"), ocsort_use_byte=args.get("ocsort_use_byte", False), **slice_kwargs(args),
+                     **({"hybrid_asso": args.get("hybrid_asso", "hmiou"), "hybrid_use_byte": not args.get("hybrid_no_byte", False)}
+                        if args.get("tracker") == "hybridsort" else {}),
                      **({"track_bank": True} if args.get("mtmc") and track else {}))
         model.overrides.update(conf=0.3, iou=0.4, agnostic_nms=False, max_det=1000)      # :18-21
     name = os.path.splitext(os.path.basename(str(source)))[0] or "stream"
@@ -684,10 +686,14 @@ def main(argv=None):
     p.add_argument("--fp32", action="store_true", help="every network operation in fp32 (the reference passes no half=): detector on the fp32 convolution kernels too — NMS keep lists equal the CPU fp32 network's; about 0.39x the f16 throughput")
     p.add_argument("--reid-weights", default=None, help="OSNet-x0.25 state_dict for the tracker's appearance features (required with --track unless --random-init; "
                                                           "used by --tracker botsort only with --with-reid, by deep_ocsort always, not by bytetrack or ocsort)")
-    p.add_argument("--tracker", choices=("strongsort", "bytetrack", "botsort", "ocsort", "deep_ocsort"), default="strongsort",
+    p.add_argument("--tracker", choices=("strongsort", "bytetrack", "botsort", "ocsort", "deep_ocsort", "hybridsort"), default="strongsort",
                    help="strongsort (default): OSNet appearance + NSA Kalman; bytetrack / botsort: the BYTE family on IoU and scores, no ReID network (docs/BYTETRACK.md); "
                         "ocsort: OC-SORT, motion only, no ReID network (docs/OCSORT.md); deep_ocsort: Deep OC-SORT, OC-SORT with OSNet appearance and, "
                         "with --camera-motion, compensated filters and observations (docs/DEEPOCSORT.md; needs --reid-weights or --random-init)")
+    p.add_argument("--hybrid-asso", choices=("hmiou", "iou"), default="hmiou",
+                   help="--tracker hybridsort only: the association value, height-modulated IoU (default) or plain IoU (docs/HYBRIDSORT.md)")
+    p.add_argument("--hybrid-no-byte", action="store_true",
+                   help="--tracker hybridsort only: without its BYTE stage, the second association on the rows scoring between 0.1 and 0.25")
     p.add_argument("--ocsort-use-byte", action="store_true",
                    help="--tracker ocsort only: OC-SORT's BYTE stage, a second association on the rows scoring between 0.1 and 0.25")
     p.add_argument("--camera-motion", action="store_true",
@@ -840,6 +846,19 @@ def main(argv=None):
         for flag, on in (("--camera-motion", a.camera_motion), ("--with-reid", a.with_reid), ("--with-pose", a.with_pose)):
             if on:
                 p.error(f"{flag} is not available with --tracker ocsort (OC-SORT is motion only, docs/OCSORT.md)")
+    if a.tracker == "hybridsort":
+        for flag, on in (("--camera-motion", a.camera_motion), ("--with-reid", a.with_reid), ("--with-pose", a.with_pose),
+                         ("--ocsort-use-byte", a.ocsort_use_byte)):
+            if on:
+                p.error(f"{flag} is not available with --tracker hybridsort (Hybrid-SORT is motion only and its BYTE stage is its own, docs/HYBRIDSORT.md)")
+        if a.reid_model != "osnet":
+            p.error("--reid-model auto is BoT-SORT's: --tracker hybridsort reads no features")
+        if a.gmc_method != "ecc":
+            p.error("--gmc-method is a camera-motion estimator: --tracker hybridsort has no camera-motion compensation")
+        if "-obb" in os.path.basename(a.weights):
+            p.error("--tracker hybridsort associates on axis-aligned boxes: an oriented-box model needs --tracker bytetrack or botsort")
+    elif a.hybrid_asso != "hmiou" or a.hybrid_no_byte:
+        p.error("--hybrid-asso and --hybrid-no-byte are Hybrid-SORT's: they need --tracker hybridsort")
     if a.tracker == "deep_ocsort":
         for flag, on in (("--with-reid", a.with_reid), ("--with-pose", a.with_pose), ("--ocsort-use-byte", a.ocsort_use_byte)):
             if on:
@@ -884,7 +903,7 @@ def main(argv=None):
             p.error(f"--device-encode: --save '{a.save}' must be a .mjpeg / .mjpg file or a directory (a path ending in '/' or an existing directory)")
         if not 1 <= a.save_quality <= 100:
             p.error("--save-quality must be 1 .. 100")
-    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "ocsort_use_byte": a.ocsort_use_byte, "device_decode": a.device_decode, "device_entropy": a.device_entropy,
+    jobs = [{"source": s, "track": a.track, "count": a.count, "weights": a.weights, "reid_weights": a.reid_weights, "limit": a.limit, "device": i, "random_init": a.random_init, "batch": a.batch, "reid_f16": a.reid_f16, "fp32": a.fp32, "device_masks": a.device_masks, "tracker": a.tracker, "camera_motion": a.camera_motion, "with_reid": a.with_reid, "reid_model": a.reid_model, "with_pose": a.with_pose, "gmc_method": a.gmc_method, "ocsort_use_byte": a.ocsort_use_byte, "hybrid_asso": a.hybrid_asso, "hybrid_no_byte": a.hybrid_no_byte, "device_decode": a.device_decode, "device_entropy": a.device_entropy,
              "device_encode": a.device_encode, "device_encode_entropy": a.device_encode_entropy, "save_quality": a.save_quality, "save_subsampling": a.save_subsampling,
              "gsi": a.gsi, "gsi_interval": a.gsi_interval, "gsi_tau": a.gsi_tau, "eval_gt": a.eval_gt[i] if a.eval_gt else None, "eval_thr": a.eval_thr, "eval_identity": a.eval_identity,
              "eval_det_gt": a.eval_det_gt[i] if a.eval_det_gt else None, "eval_det_max_dets": a.eval_det_max_dets, "eval_det_classes": a.eval_det_classes,

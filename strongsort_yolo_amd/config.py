@@ -192,8 +192,71 @@ class DeepOCSortConfig:
         return asdict(self)
 
 
-# tracker_type of YOLO / FramePipeline / the CLI -> the BYTE configuration it runs (None: StrongSORT, OC-SORT and Deep OC-SORT)
-TRACKER_TYPES = ("strongsort", "bytetrack", "botsort", "ocsort", "deep_ocsort")
+@dataclass(frozen=True)
+class HybridSortConfig:
+    """Hybrid-SORT (docs/HYBRIDSORT.md, decisions H-01..): OC-SORT's machinery with three weak cues — the detection confidence as
+    a Kalman state and a cost term (tcm_first_weight, tcm_byte_weight; 0 switches the cue off), the height-modulated IoU
+    (asso "hmiou", or plain "iou"), and the direction-consistency term over the four box corners and delta_t time offsets
+    (inertia is the weight of each corner's term)."""
+    det_thresh: float = 0.25
+    low_thresh: float = 0.1
+    max_age: int = 30
+    min_hits: int = 3
+    iou_threshold: float = 0.3
+    delta_t: int = 3
+    inertia: float = 0.05
+    use_byte: bool = True
+    asso: str = "hmiou"
+    tcm_first_weight: float = 1.0
+    tcm_byte_weight: float = 1.0
+    # capacities of the device-resident track table (per stream) and of a frame
+    max_tracks: int = 256
+    max_dets: int = 128
+
+    ASSO = ("hmiou", "iou")
+
+    def __post_init__(self):
+        if not 1 <= self.delta_t <= 8:
+            raise ValueError(f"HybridSortConfig.delta_t: 1..8, not {self.delta_t}")
+        if self.max_age < 1 or self.min_hits < 0:
+            raise ValueError("HybridSortConfig: max_age >= 1 and min_hits >= 0")
+        if not 0.0 < self.iou_threshold <= 1.0:
+            raise ValueError(f"HybridSortConfig.iou_threshold: in (0, 1], not {self.iou_threshold}")
+        if not self.inertia >= 0.0:
+            raise ValueError(f"HybridSortConfig.inertia: >= 0, not {self.inertia}")
+        if not self.low_thresh <= self.det_thresh:
+            raise ValueError("HybridSortConfig: low_thresh <= det_thresh")
+        if self.asso not in self.ASSO:
+            raise ValueError(f"HybridSortConfig.asso: one of {self.ASSO}, not {self.asso!r}")
+        if not (self.tcm_first_weight >= 0.0 and self.tcm_byte_weight >= 0.0):
+            raise ValueError("HybridSortConfig: tcm_first_weight >= 0 and tcm_byte_weight >= 0")
+        if not (0 < self.max_tracks <= 256 and 0 < self.max_dets <= 128):
+            raise ValueError("HybridSortConfig: max_tracks <= 256 and max_dets <= 128 (the device table's capacity)")
+
+    def as_dict(self):
+        return asdict(self)
+
+
+# tracker_type of YOLO / FramePipeline / the CLI -> the BYTE configuration it runs (None: StrongSORT, the OC-SORT family)
+TRACKER_TYPES = ("strongsort", "bytetrack", "botsort", "ocsort", "deep_ocsort", "hybridsort")
+
+
+def hybridsort_config(tracker_type: str, asso: str = "hmiou", use_byte: bool = True, camera_motion: bool = False, with_reid: bool = False,
+                      with_pose: bool = False, ocsort_use_byte: bool = False):
+    """tracker_type -> the Hybrid-SORT configuration it runs (None: another tracker).  Hybrid-SORT is motion only: BoT-SORT's
+    options are refused by name, and its BYTE stage has a switch of its own (use_byte), not OC-SORT's."""
+    if tracker_type not in TRACKER_TYPES:
+        raise ValueError(f"tracker_type must be one of {TRACKER_TYPES}, not {tracker_type!r}")
+    if tracker_type != "hybridsort":
+        if asso != "hmiou" or not use_byte:
+            raise ValueError(f"hybrid_asso and hybrid_use_byte are Hybrid-SORT's: tracker_type 'hybridsort', not {tracker_type!r}")
+        return None
+    for name, on in (("camera_motion", camera_motion), ("with_reid", with_reid), ("with_pose", with_pose)):
+        if on:
+            raise ValueError(f"{name} is not available with tracker_type 'hybridsort' (Hybrid-SORT is motion only, docs/HYBRIDSORT.md)")
+    if ocsort_use_byte:
+        raise ValueError("ocsort_use_byte is OC-SORT's BYTE stage: Hybrid-SORT's is hybrid_use_byte, on by default (docs/HYBRIDSORT.md)")
+    return HybridSortConfig(asso=asso, use_byte=bool(use_byte))
 
 
 def deep_ocsort_config(tracker_type: str, with_reid: bool = False, with_pose: bool = False, ocsort_use_byte: bool = False):
@@ -237,7 +300,7 @@ def byte_config(tracker_type: str, with_reid: bool = False, with_pose: bool = Fa
         raise ValueError(f"with_reid is BoT-SORT's ReID branch: tracker_type 'botsort', not {tracker_type!r}")
     if with_pose and tracker_type != "botsort":
         raise ValueError(f"with_pose is BoT-SORT's keypoint term: tracker_type 'botsort', not {tracker_type!r}")
-    if tracker_type in ("strongsort", "deep_ocsort"):
+    if tracker_type in ("strongsort", "deep_ocsort", "hybridsort"):
         return None
     return ByteTrackConfig(kalman="xywh" if tracker_type == "botsort" else "xyah", with_reid=bool(with_reid), with_pose=bool(with_pose))
 

@@ -72,6 +72,7 @@ struct ss_ctx {
     SSByte* byte = nullptr;     // the BYTE tracker family (ss_byte_create), NULL until attached
     SSOc* oc = nullptr;         // the OC-SORT tracker (ss_ocsort_create), NULL until attached
     SSDeepOc* deepoc = nullptr; // the Deep OC-SORT tracker (ss_deepoc_create), NULL until attached
+    SSHybrid* hybrid = nullptr; // the Hybrid-SORT tracker (ss_hybridsort_create), NULL until attached
     SSJpeg* jpeg = nullptr;     // ss_jpeg_decode_batch's staging areas and planes, made by its first call
     SSJpegEnc* jpeg_enc = nullptr;   // ss_jpeg_encode_batch's buffers, made by its first call
     SSGsi* gsi = nullptr;       // ss_gsi_smooth's staging and scratch slots, made by its first call
@@ -234,6 +235,7 @@ extern "C" void ss_destroy(ss_ctx* c)
     ss_byte_free(c->byte);
     ss_ocsort_free(c->oc);
     ss_deepoc_free(c->deepoc);
+    ss_hybrid_free(c->hybrid);
     ss_jpeg_free(c->jpeg);
     ss_jpeg_enc_free(c->jpeg_enc);
     ss_gsi_free(c->gsi);
@@ -1094,6 +1096,7 @@ extern "C" int ss_check_errors(ss_ctx* c)
     int rc = ss_byte_pending_impl(c->byte, c->stream, err);                     // the tracker families' (capacity, infeasible)
     if (rc == SS_OK) rc = ss_ocsort_pending_impl(c->oc, c->stream, err);
     if (rc == SS_OK) rc = ss_deepoc_pending_impl(c->deepoc, c->stream, err);
+    if (rc == SS_OK) rc = ss_hybrid_pending_impl(c->hybrid, c->stream, err);
     if (rc == SS_OK) rc = ss_zone_pending_impl(c->zone, c->stream, err);        // more live tracks than the analytics table holds
     if (rc == SS_OK) rc = ss_bank_pending_impl(c->bank, c->stream, err);        // an id above the track bank's max_ids
     if (rc == SS_OK) rc = ss_jpeg_pending_impl(c->jpeg, err);                   // images a device-entropy JPEG call refused (docs/JPEG.md section 12)
@@ -1730,7 +1733,7 @@ extern "C" int ss_redact(ss_ctx* c, void* hip_stream, uint8_t* d_frames, int bat
         });
 }
 
-// ---- the tracker families: BYTE (ss_byte.hip), OC-SORT (ss_ocsort.hip), Deep OC-SORT (ss_deepoc.hip) --------------------------------
+// ---- the tracker families: BYTE (ss_byte.hip), OC-SORT (ss_ocsort.hip), Deep OC-SORT (ss_deepoc.hip), Hybrid-SORT (ss_hybrid.hip) --------------------------------
 // Each family's state, tables, reset and read-back live beside its kernels; include/strongsort_hip.h says what each entry does.
 // An entry that needs the state: ok (it is there and the entry's own arguments are sound) and the stream, all worded "no <what>".
 template <class Work>
@@ -1848,6 +1851,41 @@ extern "C" int ss_deepoc_get_features(ss_ctx* c, int s, int cap, float* emb)
 {
     return tracker_run(c, "ss_deepoc_get_features", c && c->deepoc && cap >= 0 && emb, "Deep OC-SORT state, bad stream or NULL", s, true,
                        [&](std::string& err) { return ss_deepoc_get_features_impl(c->deepoc, c->stream, s, cap, emb, err); });
+}
+
+// ---- Hybrid-SORT (docs/HYBRIDSORT.md)
+static const char *const HY_STATE = "Hybrid-SORT state (ss_hybridsort_create)", *const HY_OR_STREAM = "Hybrid-SORT state or bad stream";
+
+extern "C" int ss_hybridsort_destroy(ss_ctx* c) { return stage_destroy(c, "ss_hybridsort_destroy", &ss_ctx::hybrid, ss_hybrid_free); }
+
+extern "C" int ss_hybridsort_create(ss_ctx* c, const ss_hybridsort_config* cfg)
+{
+    return create_run(c, "ss_hybridsort_create", &ss_ctx::hybrid, ss_hybrid_free, [&](std::string& err) { return ss_hybrid_create_check_impl(cfg, err); },
+                      [&](std::string& err) { return ss_hybrid_create_impl(&c->hybrid, c->stream, c->dev.S, cfg, err); });
+}
+
+extern "C" int ss_hybridsort_reset(ss_ctx* c, int stream)
+{
+    return tracker_run(c, "ss_hybridsort_reset", c && c->hybrid, HY_OR_STREAM, stream, false,
+                       [&](std::string& err) { return ss_hybrid_reset_impl(c->hybrid, c->stream, stream, err); });
+}
+
+extern "C" int ss_hybridsort_update_group(ss_ctx* c, int n_frames, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout)
+{
+    return update_run(c, "ss_hybridsort_update_group", d_dets && d_ndets && d_out && d_nout, n_frames, c && c->hybrid, HY_STATE,
+                      [&](std::string&) { ss_launch_hybrid_group(ss_hybrid_dev(c->hybrid), n_frames, d_dets, d_ndets, d_out, d_nout, c->stream); return (int)SS_OK; });
+}
+
+extern "C" int ss_hybridsort_update(ss_ctx* c, const float* d_dets, const int* d_ndets, float* d_out, int* d_nout) { return ss_hybridsort_update_group(c, 1, d_dets, d_ndets, d_out, d_nout); }
+
+extern "C" int ss_hybridsort_get_tracks(ss_ctx* c, int s, int cap, int* n_tracks, int* next_id, int* frame_count, int* track_id, int* age,
+                                        int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P, float* last_obs,
+                                        double* velocity, float* conf, float* conf_prev)
+{
+    return tracker_run(c, "ss_hybridsort_get_tracks", c && c->hybrid && cap >= 0, HY_OR_STREAM, s, true, [&](std::string& err) {
+        return ss_hybrid_get_tracks_impl(c->hybrid, c->stream, s, cap, n_tracks, next_id, frame_count, track_id, age, time_since_update, hits,
+                                         hit_streak, frozen, x, P, last_obs, velocity, conf, conf_prev, err);
+    });
 }
 
 // ---- BYTE tracker family (docs/BYTETRACK.md; oriented boxes: docs/OBB.md §4)

@@ -404,6 +404,27 @@ struct SSDeepOcDev {
     const double* gmc;                  // [F][S][8] warps (ss_deepoc_set_gmc), NULL: off
 };
 
+// Device state of the Hybrid-SORT tracker (csrc/ss_hybrid.hip, docs/HYBRIDSORT.md), hung off a context by ss_hybridsort_create.  The
+// list and slot fields are OC-SORT's; the filter is kept as its five independent components (H-02).
+#define SS_HY_FLT 26                    // doubles per filter: [p, v, P00, P01, P10, P11] of x, y, s, c, then r and its variance
+struct SSHyDev {
+    int S;
+    int max_age, min_hits, delta_t, use_byte, hmiou, max_tracks, max_dets;
+    float det_thresh, low_thresh;       // score thresholds of the split, compared in float32
+    double det_thr64, low_thr64;        // the same as configured: the bounds of the two confidences
+    double iou_thr, inertia, tcm_first, tcm_byte;
+    int *frame, *next_id, *err, *n_trk; // [S]
+    int* trk;                           // [S][MAXT] slots in list order
+    int *tid, *age, *tsu, *hits, *streak, *hasobs, *obsd, *frozen, *det, *hasprev;   // [S][MAXT] by slot
+    float *score, *cls, *cprev;         // [S][MAXT]; score is the confidence of the last match, cprev of the one before (hasprev)
+    float* lobs;                        // [S][MAXT][4] last observation (the birth row while hasobs is 0)
+    float* ring;                        // [S][MAXT][SS_OC_MAXDT][4] observations, entry age % delta_t
+    int* rage;                          // [S][MAXT][SS_OC_MAXDT] the age an entry was stored at, -1: empty
+    double* vel;                        // [S][MAXT][8] the corners' velocities (lt, rt, lb, rb; x, y); zero: none
+    double *flt, *fltf;                 // [S][MAXT][SS_HY_FLT] the filter and its frozen copy
+    double* spill;                      // [S][MAXT * MAXD] cost matrices that do not fit the LDS
+};
+
 // Device state of the sparse-optical-flow camera-motion estimator (csrc/ss_gmc.hip, docs/BYTETRACK.md §1f), hung off a context by
 // the first ss_gmc_sparse_estimate call for a frame size.  Image slot 0 of a stream is the remembered frame, slots 1..F the group's.
 #define SS_GMC_MAXC 1000                // corners per image (S-05)

@@ -71,6 +71,7 @@ void ss_launch_byte_group_obb(const SSByteDev& b, int F, const float* dets, cons
 void ss_launch_ocsort_group(const SSOcDev& o, int F, const float* dets, const int* ndets, float* out, int* nout, hipStream_t st);
 void ss_launch_deepoc_group(const SSDeepOcDev& x, int F, const float* dets, const int* ndets, const float* feats, float* out, int* nout,
                             hipStream_t st);
+void ss_launch_hybrid_group(const SSHyDev& o, int F, const float* dets, const int* ndets, float* out, int* nout, hipStream_t st);
 void ss_launch_native_feats(int n_img, int half, const void* const* p, const long long* img_stride, const long long* row_stride,
                             const long long* pix_stride, const int* channels, const int* height, const int* width, int s,
                             const int* keep, long long keep_stride, const int* counts, float* out, hipStream_t st);
@@ -122,6 +123,16 @@ void ss_deepoc_set_gmc_impl(SSDeepOc* d, const double* d_warps);
 int  ss_deepoc_get_features_impl(SSDeepOc* d, hipStream_t st, int s, int cap, float* emb, std::string& err);
 int  ss_deepoc_pending_impl(SSDeepOc* d, hipStream_t st, std::string& err);
 void ss_deepoc_free(SSDeepOc* d);
+struct SSHybrid;                                        // Hybrid-SORT (ss_hybrid.hip, docs/HYBRIDSORT.md)
+const SSHyDev& ss_hybrid_dev(const SSHybrid* h);
+int  ss_hybrid_create_check_impl(const ss_hybridsort_config* cfg, std::string& err);
+int  ss_hybrid_create_impl(SSHybrid** ph, hipStream_t st, int S, const ss_hybridsort_config* cfg, std::string& err);
+int  ss_hybrid_reset_impl(SSHybrid* h, hipStream_t st, int stream, std::string& err);
+int  ss_hybrid_get_tracks_impl(SSHybrid* h, hipStream_t st, int s, int cap, int* n_tracks, int* next_id, int* frame_count, int* track_id,
+                               int* age, int* time_since_update, int* hits, int* hit_streak, int* frozen, double* x, double* P,
+                               float* last_obs, double* velocity, float* conf, float* conf_prev, std::string& err);
+int  ss_hybrid_pending_impl(SSHybrid* h, hipStream_t st, std::string& err);
+void ss_hybrid_free(SSHybrid* h);
 
 // ---- ss_jpeg.hip: decoder state of a context (created on first use)
 struct SSJpeg;

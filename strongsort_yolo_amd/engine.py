@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from .config import StrongSortConfig, DetectConfig, ByteTrackConfig, OCSortConfig, DeepOCSortConfig
+from .config import StrongSortConfig, DetectConfig, ByteTrackConfig, OCSortConfig, DeepOCSortConfig, HybridSortConfig
 from .lib import MAX_TRACKS, MAX_DETS, FEAT_DIM, OUT_COLS
 
 
@@ -1191,6 +1191,41 @@ class OCSortEngine(_AttachedTracker):
         k = nt.value
         return dict({n: iv[n][:k].copy() for n in names}, x=x[:k].copy(), P=P[:k].copy(), last_obs=lo[:k].copy(), velocity=vel[:k].copy(),
                     n_tracks=k, next_id=nid.value, frame_count=fr.value)
+
+
+class HybridSortEngine(_AttachedTracker):
+    """Hybrid-SORT (csrc/ss_hybrid.hip, docs/HYBRIDSORT.md) on the context of a TrackerEngine: OCSortEngine's shape, without
+    features, keypoints or warps.  `engine`: share the context of an existing TrackerEngine; None: a context of its own."""
+
+    _name, _destroy, _reset = "HybridSortEngine", "ss_hybridsort_destroy", "ss_hybridsort_reset"
+
+    def __init__(self, cfg: HybridSortConfig | None = None, n_streams: int = 1, device: int = 0, engine: TrackerEngine | None = None):
+        self.cfg = cfg or HybridSortConfig()
+        super().__init__(n_streams, device, engine)
+        c = _lib.make_hybridsort_config(self.cfg)
+        self._ck(self.L.ss_hybridsort_create(self.base.ctx, C.byref(c)))
+
+    def update_group(self, n_frames, dets, ndets, feats, img_hw, out, nout):
+        """A group of n_frames (<= 32) frames of all streams in ONE launch: dets [F,S,128,6] f32, ndets [F,S] i32 -> rows out
+        [F,S,256,8], counts nout [F,S] (device tensors, asynchronous); frames are associated in order.  feats, img_hw unused."""
+        self._ck(self.L.ss_hybridsort_update_group(self.base.ctx, int(n_frames), _ptr(dets), _ptr(ndets), _ptr(out), _ptr(nout)))
+        return out, nout
+
+    def tracks(self, stream: int = 0) -> dict:
+        """The table of one stream in list order (oldest track first): what tests/hybridsort_ref.py's tracks() returns."""
+        T = MAX_TRACKS
+        nt, nid, fr = C.c_int(), C.c_int(), C.c_int()
+        names = ("track_id", "age", "time_since_update", "hits", "hit_streak", "frozen")
+        iv = {n: np.zeros(T, np.int32) for n in names}
+        x, P, lo, vel = np.zeros((T, 9)), np.zeros((T, 81)), np.zeros((T, 4), np.float32), np.zeros((T, 8))
+        conf, prev = np.zeros(T, np.float32), np.zeros(T, np.float32)
+        ip, dp, fp = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
+        self._ck(self.L.ss_hybridsort_get_tracks(self.base.ctx, stream, T, C.byref(nt), C.byref(nid), C.byref(fr),
+                                                 *[iv[n].ctypes.data_as(ip) for n in names], x.ctypes.data_as(dp), P.ctypes.data_as(dp),
+                                                 lo.ctypes.data_as(fp), vel.ctypes.data_as(dp), conf.ctypes.data_as(fp), prev.ctypes.data_as(fp)))
+        k = nt.value
+        return dict({n: iv[n][:k].copy() for n in names}, x=x[:k].copy(), P=P[:k].copy(), last_obs=lo[:k].copy(), velocity=vel[:k].copy(),
+                    conf=conf[:k].copy(), conf_prev=prev[:k].copy(), n_tracks=k, next_id=nid.value, frame_count=fr.value)
 
 
 class DeepOCSortEngine(OCSortEngine):

@@ -22,8 +22,9 @@ SS_OK, SS_ERR_INVALID, SS_ERR_CAPACITY, SS_ERR_HIP, SS_ERR_INFEASIBLE = (
 MAX_TRACKS, MAX_DETS, FEAT_DIM, OUT_COLS, DST_F16, DST_HWC, DST_U8 = (
     _H.defines["SS_" + n] for n in ("MAX_TRACKS", "MAX_DETS", "FEAT_DIM", "OUT_COLS", "DST_F16", "DST_HWC", "DST_U8"))
 EXPORTS = list(_H.functions)
-ss_config, ss_byte_config, ss_ocsort_config, ss_deepoc_config, ss_conv_desc, ss_native_map, ss_zone_config = (
-    _H.structs[n] for n in ("ss_config", "ss_byte_config", "ss_ocsort_config", "ss_deepoc_config", "ss_conv_desc", "ss_native_map", "ss_zone_config"))
+ss_config, ss_byte_config, ss_ocsort_config, ss_deepoc_config, ss_hybridsort_config, ss_conv_desc, ss_native_map, ss_zone_config = (
+    _H.structs[n] for n in ("ss_config", "ss_byte_config", "ss_ocsort_config", "ss_deepoc_config", "ss_hybridsort_config", "ss_conv_desc",
+                            "ss_native_map", "ss_zone_config"))
 
 
 class SSError(RuntimeError):
@@ -84,6 +85,11 @@ def make_byte_config(cfg) -> ss_byte_config:
 def make_ocsort_config(cfg) -> ss_ocsort_config:
     return ss_ocsort_config(cfg.det_thresh, cfg.low_thresh, cfg.iou_threshold, cfg.inertia, cfg.max_age, cfg.min_hits, cfg.delta_t,
                             int(cfg.use_byte), cfg.max_tracks, cfg.max_dets)
+
+
+def make_hybridsort_config(cfg) -> ss_hybridsort_config:
+    return ss_hybridsort_config(cfg.det_thresh, cfg.low_thresh, cfg.iou_threshold, cfg.inertia, cfg.tcm_first_weight, cfg.tcm_byte_weight,
+                                cfg.max_age, cfg.min_hits, cfg.delta_t, int(cfg.use_byte), int(cfg.asso == "hmiou"), cfg.max_tracks, cfg.max_dets)
 
 
 def make_deepoc_config(cfg) -> ss_deepoc_config:

@@ -29,7 +29,7 @@ def bank_refusal(tracker_type: str, with_reid: bool = False, reid_model: str = "
     """Why a model of this kind cannot keep a track bank (None: it can)."""
     if obb:
         return f"an oriented-box model has {NO_FEATURES}"
-    if tracker_type in ("bytetrack", "ocsort"):
+    if tracker_type in ("bytetrack", "ocsort", "hybridsort"):
         return f"tracker_type {tracker_type!r} has {NO_FEATURES}"
     if tracker_type == "botsort" and not with_reid:
         return f"tracker_type 'botsort' without with_reid has {NO_FEATURES}"

@@ -41,7 +41,7 @@ class FramePipeline:
                  graph: str = "all", debug: bool = False, run_nets: bool = True, seed: int = 0, detect_only_rows: int = 0, cmc: bool = False,
                  reid_half: Optional[bool] = None, crops_u8: bool = True, tracker: str = "strongsort", with_reid: bool = False,
                  reid_model: str = "osnet", with_pose: bool = False, gmc_method: str = "ecc", ocsort_use_byte: bool = False, slice_cfg=None,
-                 track_bank: bool = False, bank_max_ids: int = 4096):
+                 track_bank: bool = False, bank_max_ids: int = 4096, hybrid_asso: str = "hmiou", hybrid_use_byte: bool = True):
         self.cfg, self.dcfg = cfg or StrongSortConfig(), dcfg or DetectConfig()
         self.S, (self.H, self.W) = n_streams, frame_hw
         # tracker = "bytetrack" / "botsort": the BYTE tracker family (csrc/ss_byte.hip) on IoU and scores — no OSNet is built, no
@@ -59,12 +59,14 @@ class FramePipeline:
         # OSNet and cuts no crops, and its engine stands where the BYTE engine stands (self.byte / self.trk: the same stage bodies).
         # tracker = "deep_ocsort": Deep OC-SORT (csrc/ss_deepoc.hip, docs/DEEPOCSORT.md) — OSNet, crops and ReID stages stay as for botsort
         # with with_reid, the warps stage as for botsort; its engine stands where the BYTE engine stands.
+        # tracker = "hybridsort": Hybrid-SORT (csrc/ss_hybrid.hip, docs/HYBRIDSORT.md) — motion only, as "ocsort": no OSNet, no crops, its
+        # engine stands where the BYTE engine stands; hybrid_asso ("hmiou" / "iou") and hybrid_use_byte are its two switches.
         # slice_cfg (slicing.SliceConfig): sliced inference (csrc/ss_slice.hip, docs/SLICE.md) — the detector sees T tiles of every frame
         # (S * T images: lb, pred_in and the per-tile NMS rows carry that leading dimension), one launch letterboxes them, one launch
         # merges the tiles' rows into b.dets / b.ndets; from there on nothing differs.  None: nothing of it is allocated or launched.
         # track_bank: one pooled appearance descriptor per track id, kept on the device behind every tracker call (csrc/ss_mtmc.hip,
         # docs/MTMC.md): one more launch per call that reads the rows and the features where they are.  Off: nothing is allocated or launched.
-        from .config import byte_config, ocsort_config, deep_ocsort_config, check_reid_model, check_pose, check_gmc_method
+        from .config import byte_config, ocsort_config, deep_ocsort_config, hybridsort_config, check_reid_model, check_pose, check_gmc_method
         self.slice = slice_cfg
         self.bank = None
         if track_bank and not detect_only_rows:
@@ -76,7 +78,7 @@ class FramePipeline:
         # the BYTE family on ProbIoU; what is not built for rotated boxes is refused by name before anything is allocated
         self.ne = 1 if detector.lower().replace(".pt", "") in nets.OBB_DETECTORS else 0
         if self.ne:
-            if tracker in ("ocsort", "deep_ocsort") or (tracker == "strongsort" and not detect_only_rows):
+            if tracker in ("ocsort", "deep_ocsort", "hybridsort") or (tracker == "strongsort" and not detect_only_rows):
                 raise ValueError(f"'{detector}' is an oriented-box model: tracker '{tracker}' associates on axis-aligned boxes; use 'bytetrack' or "
                                  "'botsort' (ProbIoU of the rotated boxes, docs/OBB.md §4)")
             for on, what in ((with_reid, "with_reid"), (reid_model == "auto", "reid_model='auto'"), (with_pose, "with_pose"),
@@ -85,6 +87,7 @@ class FramePipeline:
                     raise ValueError(f"'{detector}' is an oriented-box model: {what} is not built for rotated boxes (docs/OBB.md §5)")
         if self.slice is not None and reid_model == "auto":
             raise ValueError("sliced inference cannot feed reid_model='auto': the detector's anchor indices are per tile")
+        self.hy_cfg = hybridsort_config(tracker, hybrid_asso, hybrid_use_byte, cmc, with_reid, with_pose, ocsort_use_byte)
         self.deep_cfg = deep_ocsort_config(tracker, with_reid, with_pose, ocsort_use_byte)
         self.oc_cfg = ocsort_config(tracker, ocsort_use_byte, cmc, with_reid, with_pose)
         self.byte_cfg = byte_config(tracker, with_reid, with_pose)
@@ -92,7 +95,7 @@ class FramePipeline:
         self.reid_model = check_reid_model(reid_model, with_reid)
         self.tracker = tracker
         self.native = self.reid_model == "auto" and not detect_only_rows
-        self.need_reid = (self.byte_cfg is None and self.oc_cfg is None) or (self.byte_cfg is not None and self.byte_cfg.with_reid and self.reid_model == "osnet")
+        self.need_reid = (self.byte_cfg is None and self.oc_cfg is None and self.hy_cfg is None) or (self.byte_cfg is not None and self.byte_cfg.with_reid and self.reid_model == "osnet")
         if self.byte_cfg is not None and cmc and self.byte_cfg.kalman != "xywh":
             raise ValueError("camera-motion compensation needs tracker 'strongsort' or 'botsort' (ByteTrack has no GMC)")
         self.eng = TrackerEngine(self.cfg, n_streams, device, debug=debug)
@@ -104,6 +107,9 @@ class FramePipeline:
         elif self.oc_cfg is not None:
             from .engine import OCSortEngine
             self.byte = self.trk = OCSortEngine(self.oc_cfg, engine=self.eng)
+        elif self.hy_cfg is not None:
+            from .engine import HybridSortEngine
+            self.byte = self.trk = HybridSortEngine(self.hy_cfg, engine=self.eng)
         elif self.deep_cfg is not None:
             from .engine import DeepOCSortEngine
             self.byte = self.trk = DeepOCSortEngine(self.deep_cfg, engine=self.eng)

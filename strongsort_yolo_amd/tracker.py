@@ -13,8 +13,8 @@ import numpy as np
 import torch
 
 from . import nets
-from .config import StrongSortConfig, ByteTrackConfig, OCSortConfig, DeepOCSortConfig, check_reid_model, check_gmc_method
-from .engine import TrackerEngine, ByteTrackEngine, OCSortEngine, DeepOCSortEngine
+from .config import StrongSortConfig, ByteTrackConfig, OCSortConfig, DeepOCSortConfig, HybridSortConfig, check_reid_model, check_gmc_method
+from .engine import TrackerEngine, ByteTrackEngine, OCSortEngine, DeepOCSortEngine, HybridSortEngine
 from .lib import MAX_DETS, FEAT_DIM
 
 
@@ -231,6 +231,17 @@ class OCSORTTracker:
 
     def close(self):
         self.eng.close()
+
+
+class HybridSORTTracker(OCSORTTracker):
+    """Hybrid-SORT for one video stream (docs/HYBRIDSORT.md): `update(dets)` as OCSORTTracker.update, no weights and no frame."""
+
+    def __init__(self, cfg: Optional[HybridSortConfig] = None, device: int = 0):
+        self.cfg = cfg or HybridSortConfig()
+        self.eng = HybridSortEngine(self.cfg, 1, device)
+        self.dev = self.eng.device
+        self._dets = torch.zeros(1, MAX_DETS, 6, dtype=torch.float32, device=self.dev)
+        self._n = torch.zeros(1, dtype=torch.int32, device=self.dev)
 
 
 class DeepOCSORTTracker:

@@ -18,7 +18,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .config import DetectConfig, StrongSortConfig, byte_config, ocsort_config, deep_ocsort_config, check_reid_model, check_gmc_method
+from .config import DetectConfig, StrongSortConfig, byte_config, ocsort_config, deep_ocsort_config, hybridsort_config, check_reid_model, check_gmc_method
 
 COCO_NAMES = ("person bicycle car motorcycle airplane bus train truck boat traffic_light fire_hydrant stop_sign "
               "parking_meter bench bird cat dog horse sheep cow elephant bear zebra giraffe backpack umbrella handbag tie "
@@ -344,7 +344,7 @@ class YOLO:
                  device_masks: bool = False, tracker_type: str = "strongsort", with_reid: bool = False, reid_model: str = "osnet",
                  with_pose: bool = False, gmc_method: str = "ecc", ocsort_use_byte: bool = False, slice_hw=None, slice_overlap=0.2,
                  slice_full: bool = True, slice_merge: str = "nmm", slice_metric: str = "ios", slice_thr: float = 0.5,
-                 track_bank: bool = False):
+                 track_bank: bool = False, hybrid_asso: str = "hmiou", hybrid_use_byte: bool = True):
         """reid_fp32 (default since round 6): ReID crops + OSNet-x0.25 in fp32 on the fp32 kernels — appearance distances within 1e-4 of a CPU fp32
         network, which f16 activations miss by 330x (reid_fp32=False: the f16 throughput mode, ~1.2x the per-frame rate, 1.7x the stream rate).
         half=False: the DETECTOR in fp32 as well (the reference's own precision: it passes no half=, yolo_multi_model.py:41) on the
@@ -377,6 +377,10 @@ class YOLO:
         features of every tracked row (reid_weights, reid_fp32 and half as for StrongSORT) in an adaptively weighted appearance cost,
         a feature EMA that follows the detection score, and, with camera_motion, the warps (gmc_method "ecc" or "sparseOptFlow")
         applied to filters and observations.  with_reid, with_pose, ocsort_use_byte and reid_model="auto" are ValueErrors.
+        tracker_type "hybridsort": Hybrid-SORT on the device (docs/HYBRIDSORT.md) — OC-SORT's machinery with the detection confidence as a
+        Kalman state and a cost term, the height-modulated IoU (hybrid_asso "hmiou", or "iou") and the direction term over the four box
+        corners; its BYTE stage is on unless hybrid_use_byte=False.  Motion only, as "ocsort": camera_motion, with_reid, with_pose,
+        reid_model="auto", ocsort_use_byte and track_bank are ValueErrors.
         slice_hw (sh, sw): sliced inference (SAHI; docs/SLICE.md) — the detector runs on overlapping sh x sw tiles of the frame as one
         batch (slice_overlap: one ratio or (oh, ow); slice_full: the whole frame as one more tile) and the tiles' rows are merged on the
         device (slice_merge "nmm" = GREEDYNMM or "nms", slice_metric "ios" or "iou", slice_thr); predict, track and track_stream then
@@ -394,6 +398,7 @@ class YOLO:
                 raise ValueError("sliced inference cannot run a segmentation model: a row's mask coefficients belong to its tile's prototypes")
             if reid_model == "auto":
                 raise ValueError("sliced inference cannot feed reid_model='auto': the detector's anchor indices are per tile")
+        hybridsort_config(tracker_type, hybrid_asso, hybrid_use_byte, camera_motion, with_reid, with_pose, ocsort_use_byte)
         deep_ocsort_config(tracker_type, with_reid, with_pose, ocsort_use_byte)               # ValueError on anything else
         ocsort_config(tracker_type, ocsort_use_byte, camera_motion, with_reid, with_pose)      # ValueError on anything else
         byte_config(tracker_type, with_reid, with_pose)
@@ -406,7 +411,7 @@ class YOLO:
         from .nets import OBB_DETECTORS
         self._obb = os.path.basename(weights).lower().replace(".pt", "") in OBB_DETECTORS
         if self._obb:                             # docs/OBB.md §5: what is not built for rotated boxes is refused by name
-            if tracker_type in ("ocsort", "deep_ocsort"):
+            if tracker_type in ("ocsort", "deep_ocsort", "hybridsort"):
                 raise ValueError(f"{weights!r} is an oriented-box model: tracker_type {tracker_type!r} associates on axis-aligned boxes; use "
                                  "'bytetrack' or 'botsort' (ProbIoU of the rotated boxes)")
             for on, what in ((with_reid, "with_reid"), (reid_model == "auto", "reid_model='auto'"), (with_pose, "with_pose"),
@@ -452,6 +457,11 @@ class YOLO:
                 self._pipe_kw["with_pose"] = True
             if ocsort_use_byte:
                 self._pipe_kw["ocsort_use_byte"] = True
+            if tracker_type == "hybridsort":
+                if hybrid_asso != "hmiou":
+                    self._pipe_kw["hybrid_asso"] = hybrid_asso
+                if not hybrid_use_byte:
+                    self._pipe_kw["hybrid_use_byte"] = False
         if self.slice is not None:
             self._pipe_kw["slice_cfg"] = self.slice
         self._track_bank, self._bank_pipe = bool(track_bank), None
@@ -630,7 +640,7 @@ class YOLO:
         return [Results(image, self.names, Boxes(rows[:, :4], rows[:, 6], rows[:, 5], rows[:, 4]),
                         None if kpts is None else Keypoints(kpts[di]), None if masks is None else masks[di])]
 
-    TRACKERS = ("strongsort.yaml", "strongsort", "botsort.yaml", "bytetrack.yaml", "ocsort.yaml", "deep_ocsort.yaml")
+    TRACKERS = ("strongsort.yaml", "strongsort", "botsort.yaml", "bytetrack.yaml", "ocsort.yaml", "deep_ocsort.yaml", "hybridsort.yaml")
 
     def _check_tracker(self, tracker):
         """`tracker=`: the tracker is chosen when the model is built (`tracker_type`), StrongSORT by default (BASELINE north_star).
@@ -645,7 +655,7 @@ class YOLO:
                 import warnings
                 self._tracker_warned = True
                 warnings.warn(f"tracker={tracker!r}: this model was built with tracker_type={self.tracker_type!r}, which rules; "
-                              f"its parameters are strongsort_yolo_amd.config.{ {'ocsort': 'OCSortConfig', 'deep_ocsort': 'DeepOCSortConfig'}.get(self.tracker_type, 'ByteTrackConfig') }",
+                              f"its parameters are strongsort_yolo_amd.config.{ {'ocsort': 'OCSortConfig', 'deep_ocsort': 'DeepOCSortConfig', 'hybridsort': 'HybridSortConfig'}.get(self.tracker_type, 'ByteTrackConfig') }",
                               RuntimeWarning, stacklevel=3)
             return
         if not name.startswith("strongsort") and not self._tracker_warned:
